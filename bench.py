@@ -4,6 +4,11 @@
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N>1 launched through
 torch.distributed.run, one rank per GPU (RCCL).  One JSON line on rank 0.
 
+A plain run sets up, warms up, times the K steps and prints the line (headline, `ms_per_step`, and the roofline
+figures computed from the timed steps themselves).  `--full` adds everything that takes runs of its own: at N = 1
+the extras (other workloads and RNG modes), the parity of the workload against the oracle and the CPU legs below.
+`--dump-outputs DIR` writes what the last timed step returned, one float64 array per name, as DIR/<name>.npy.
+
   N = 1   step = ONE trial of BASELINE configs[1]: RandomAccessSimulatorBeta.c as committed — nUE=100 000,
           Beta(3,4) arrivals, 54 preambles, nGrantUL=54, backoff 20, retx limit 10 (maxMsg2TxCount=9),
           --times 1 — i.e. 10 000 dependent subframes x 100 000 UEs = 1e9 UE-subframe updates, production RNG
@@ -21,7 +26,7 @@ torch.distributed.run, one rank per GPU (RCCL).  One JSON line on rank 0.
           HIP events on the engine's own stream (prach_last_timing) — an ALGORITHMIC rate: a single trial is
           10 000 dependent subframes over LDS/L2-resident state, bounded by per-subframe latency, not by HBM
           (measured HBM traffic: `traffic_from_profile`, a separate rocprofv3 --pmc pass, profiles/).
-  cpu_baseline  the real reference program AT THE METRIC'S OWN SIZE, timed in this run: oracle/_ref/RandomAccessSimulatorBeta_100k
+  cpu_baseline  (--full) the real reference program AT THE METRIC'S OWN SIZE, timed in this run: oracle/_ref/RandomAccessSimulatorBeta_100k
           (RandomAccessSimulatorBeta.c compiled with its hard-coded sweep started at nUE = 100 000, built from /root/reference in the
           build container) is started as a child process on one host core right behind the timed region, runs while the extras and the
           other CPU legs do, and is joined at the end (about 67 s on a GPU box);
@@ -186,6 +191,28 @@ def host_cores() -> int:
         return max(1, min(os.cpu_count() or 1, 32))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def result_arrays(results):
+    """The PrachResult records a run_trials call returned, as one float64 array per field (trial order kept).  Every field is an
+    integer below 2**53 or a float32, so float64 holds it exactly."""
+    import numpy as np
+    return {name: np.array([getattr(r, name) for r in results], dtype=np.float64) for name, _ in results[0]._fields_}
+
+
+def dump_outputs(d: str, arrays: dict):
+    """--dump-outputs: write each array as d/<name>.npy (float64).  The timed path's inputs depend on the arguments only (fixed seeds),
+    so two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def traffic_from_profile():
     tf = os.path.join(ROOT, "profiles", "traffic.json")
     if not os.path.exists(tf):
@@ -263,17 +290,22 @@ def main():
     ap.add_argument("--nue", type=int, default=100000)
     ap.add_argument("--times", type=int, default=1000, help="N>1 (or --workload grid): seeds of the --times x sweep grid (BASELINE configs[4]: 1000)")
     ap.add_argument("--workload", choices=("auto", "single", "grid"), default="auto", help="auto: single trial at N=1, the sharded grid at N>1")
+    ap.add_argument("--full", action="store_true", help="N=1: also run the extras, the oracle parity check and the CPU legs (runs of their own, after the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's results as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of reference-CPU timing (rank 0, N=1 only)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--cpu-full", action="store_true", help="(kept for old command lines: the reference's own nUE = 100 000 point now runs by default, as a child process)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the parity check and the CPU legs")
+    ap.add_argument("--cpu-full", action="store_true", help="(kept for old command lines: implies --full, which runs the reference's own nUE = 100 000 point as a child process)")
     ap.add_argument("--cpu-ref-timeout", type=float, default=420.0, help="seconds after which the reference's 100 000-UE child process is given up (67 s on a GPU box, 265 s in the build container)")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extras")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl == RCCL over xGMI; gloo only to rehearse on one GPU)")
     ap.add_argument("--same-device", action="store_true", help="rehearsal: every rank uses cuda:0")
     args = ap.parse_args()
+    args.full = args.full or args.cpu_full
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as a plain `python bench.py --gpus N`: nothing here has touched the GPU yet, so start the N ranks as a fresh
         # child (one process per GPU under torch.distributed.run), relay its one JSON line and leave with its exit code.  It never
@@ -351,19 +383,24 @@ def run_grid(args, pkg, eng, torch, dist, rank, world, dev, cdev, barrier):
         tot = distmod.allreduce_aggregates(agg, device=cdev if (dist is not None and args.backend == "nccl") else None)
         rows = [(i, pkg.format_results(cfgs[i], r, 0.0).decode()) for i, r in zip(mine, res)]
         allrows = distmod.gather_trial_rows(rows, dst=0, device=cdev if (dist is not None and args.backend == "nccl") else None)
-        return tot, allrows, t_sim, kms, time.perf_counter() - t0, own
+        return tot, allrows, t_sim, kms, time.perf_counter() - t0, own, res
 
     for _ in range(args.warmup):
         step()
     barrier()
     t0 = time.perf_counter()
     sims, kmss, steps_t, owns = [], [], [], []
-    tot = allrows = None
+    tot = allrows = res = None
     for _ in range(args.steps):
-        tot, allrows, t_sim, kms, t_step, own = step()
+        tot, allrows, t_sim, kms, t_step, own, res = step()
         sims.append(t_sim); kmss.append(kms); steps_t.append(t_step); owns.append(own)
     barrier()
     dt = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        # the all-reduced aggregate block (one row per sweep point, columns dist.AGG_FIELDS) and rank 0's own trials (trial_index: their
+        # place in the grid, seed-major)
+        dump_outputs(args.dump_outputs, dict(aggregates=np.asarray(tot, dtype=np.float64), trial_index=np.asarray(mine, dtype=np.float64),
+                                             **result_arrays(res)))
     fi = {n: k for k, n in enumerate(distmod.AGG_FIELDS)}
     max_dt, per_rank = dt, [sum(sims) / args.steps]
     if dist is not None:
@@ -445,8 +482,10 @@ def run_single(args, pkg, eng, torch, dist, rank, world, cdev, barrier):
     barrier()
     dt = time.perf_counter() - t0
     assert fallbacks == 0, "a timed trial was rerun on the fallback kernel"
-    # the reference's own 100 000-UE point: a child process on one host core, started behind the timed region, joined at the very end
-    ref100k = start_reference_100k() if (world == 1 and rank == 0 and not args.no_cpu) else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, result_arrays([res]))
+    # (--full) the reference's own 100 000-UE point: a child process on one host core, started behind the timed region, joined at the very end
+    ref100k = start_reference_100k() if (world == 1 and rank == 0 and args.full and not args.no_cpu) else None
 
     tot_updates, max_dt = updates, dt
     if dist is not None:
@@ -485,7 +524,7 @@ def run_single(args, pkg, eng, torch, dist, rank, world, cdev, barrier):
         "success_ratio_mean": agg_succ / (args.steps * world * args.nue),
         "host_cores": {"os_cpu_count": os.cpu_count(), "usable_by_this_process": host_cores()},
     }
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         extras = {}
         # (1) reference-bit-exact mode: the 100k point of the reference's own chained sweep (glibc rand stream)
         try:
@@ -597,7 +636,7 @@ def run_single(args, pkg, eng, torch, dist, rank, world, cdev, barrier):
                                                       "launches": tmg2.launches, "rerun_with_host_activation": tmg2.fallback_trials, "bad": sum(r_.status != 0 for r_ in rs),
                                                       "nSuccessUE_seed0": rs[0].nSuccessUE, "reference_nSuccessUE_seed0_at_its_own_stream_offset": "tests/golden/noma_c.json (the chained run is test_gpu_noma_glibc_reproduces_reference_lines)"}
         out["extras"] = extras
-    if world == 1 and not args.no_cpu:
+    if world == 1 and args.full and not args.no_cpu:
         from oracle import binding as ob
         # parity of THIS bench's workload against the oracle + the O(N)/subframe CPU port, 1 core
         ocfg = ob.make_cfg(args.nue, variant=ob.VARIANT_BETA_C)

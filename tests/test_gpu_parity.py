@@ -761,6 +761,26 @@ def test_bench_grid_two_ranks_rccl(pkg, ob):
     _check_grid_line(pkg, ob, _run_bench_ranks(2, "nccl", [], 29542), 2)
 
 
+def test_bench_plain_line_and_dumped_outputs(pkg, ob, tmp_path):
+    """`bench.py --gpus 1 --steps 2 --warmup 0 --dump-outputs DIR`: the plain run prints the headline line without the legs of --full, and DIR
+    holds the last timed step's result (seed 1 of the configs[1] workload) field by field as float64 arrays — equal to the oracle's trial."""
+    import json
+    from conftest import ROOT
+    d = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = json.loads([l for l in p.stdout.split("\n") if l.startswith("{")][-1])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert not {"extras", "parity", "cpu_port", "cpu_baseline"} & set(out)
+    got = {f.name[:-len(".npy")]: np.load(f) for f in d.iterdir()}
+    assert set(got) == {n for n, _ in pkg.PrachResult._fields_}
+    assert all(a.dtype == np.float64 and a.shape == (1,) for a in got.values())
+    ores, _ = ob.run_trial(ob.make_cfg(100000, variant=ob.VARIANT_BETA_C), ob.Rng(ob.RNG_PHILOX, 1), want_ues=False)
+    assert got["status"][0] == 0
+    assert {k: got[k][0] for k in KEYS + ("totalDelay",)} == {k: getattr(ores, k) for k in KEYS + ("totalDelay",)}
+
+
 def test_beyond_reference_sizes(pkg, ob, engine):
     """nUE = 250 000 (2.5x the reference's largest point): still bit-exact vs the oracle, and one workgroup cluster
     per trial still covers it (interleaved ownership scales with nUE, not with a per-CU capacity)."""
