@@ -57,19 +57,13 @@ struct prach_engine {
     int64_t opt_lds_records = 1;   // 0: clusters keep their UE records in global memory (diagnostic)
 #endif
     int64_t opt_xcd_pack = 1;      // 1: lean clusters are launched XCD-packed (a cluster per XCD; granules stay in that XCD's L2 once verified)
-    bool pack_off = false;         // (set for the rerun of a packed launch that timed out)
     int64_t opt_fast = 1;          // 0: LDS-resident clusters run on the general kernel (prach_cluster.hip) instead of prach_lcluster.hip
-    int64_t opt_batch = 1;         // 0: one-workgroup-per-trial Philox launches run on the general kernel instead of prach_batch.hip
     int64_t opt_batch_waves = 0;   // wavefronts per batch-kernel workgroup: 8 (512 threads, two trials per CU), 16 (one), 0 = chosen per launch
     int64_t opt_plain_arena = 0;   // 1: the arena is one hipMalloc allocation, re-allocated when it grows (diagnostic)
     int64_t opt_vmm_fail_after = 0; // test hook: the reserved-range arena cannot map a further piece once it has this many (0: no limit)
     int64_t opt_noma_host_activation = 0; // 1: NOMA.c's activeUE table is built on the host (the reference's libm) instead of by noma_activation_kernel
     int64_t opt_noma_ambiguity_test = 0;  // test hook: the resolver reports every gain sort as ambiguous (exercises the rerun with the host-built table)
-    bool force_host_act = false;   // (set for the rerun of trials whose device-built table left a gain comparison inside the error band)
     int64_t opt_calendar_cap = 0;  // test hook: entries per calendar list of the batch kernel (0 = sized per trial)
-    bool full_calendars = false;   // (set for the rerun of batch-kernel trials that filled a calendar list: lists of nUE entries cannot fill)
-    std::vector<int> cal_overflow; // last launch: the trials that filled a calendar list
-    int noma_flagged = 0, noma_ambiguous = 0; // last call: UEs recomputed on the host, trials rerun with the host-built table
     int num_cus = 256;
     size_t mem_budget = (size_t)200 << 30; // arena bytes one launch may take (3/4 of the device's memory): a call that needs more runs as several launches
 };
@@ -333,7 +327,6 @@ static int engine_create_impl(int device, prach_engine **out) {
     return PRACH_OK;
 }
 
-// one launch over the trials idx[0..m) (all the same rng_mode); attempt = glibc stream retry level
 // LDS-resident records (prach_cluster.hip REC_L16): a Philox cluster whose owned UE slots (the launch's maximum) fit LDS next to
 // the per-subframe structures.  Returns the slot count per workgroup, 0 = records stay in global memory.
 static int lds_record_slots(const prach_engine *e, const prach_cfg *cfgs, const int *idx, int m, int G, int maxP, int *maxgroups) {
@@ -358,7 +351,7 @@ static bool use_fast_kernel(const prach_engine *e, int lslots, int maxP) {
 // one workgroup per trial: can prach::batch_kernel (prach_batch.hip) run this trial?  (Philox: both workgroup shapes; the reference's own rand()
 // stream: the 1024-thread shape with its per-group call marks in LDS, up to 131 072 UEs)
 static bool batch_eligible(const prach_engine *e, const prach_cfg &c) {
-    if (c.variant == PRACH_VARIANT_NOMA_C || !e->opt_batch || e->opt_dense || e->opt_wide_records) return false;
+    if (c.variant == PRACH_VARIANT_NOMA_C || e->opt_dense || e->opt_wide_records) return false;
     const bool glibc = c.rng_mode == PRACH_RNG_GLIBC;
     return c.nPreamble <= batch_max_preambles() && c.maxRarWindow <= batch_max_rar_window() && batch_calendar_slots(c.backoff, c.accessTime, c.maxRarWindow) <= batch_max_calendar_slots() &&
            (int64_t)prach_max_time(&c) + c.backoff + c.accessTime + 128 < batch_max_subframes() && c.nUE < (1 << 20) - 1 && (c.nUE + 63) / 64 <= batch_max_groups(glibc);
@@ -370,7 +363,7 @@ static bool batch_eligible(const prach_engine *e, const prach_cfg &c) {
 struct ActTab { char *pre0, *sec, *gain, *lgain, *nd0; };
 constexpr int NOMA_ACT_OVERFLOW_RC = -1099; // (internal) noma_activation_kernel flagged more UEs than its list holds
 static int noma_device_activation(prach_engine *e, const TrialDev *dparams, const prach_cfg *cfgs, const int *idx, int m, const std::vector<ActTab> &tabs,
-                                  unsigned *dflags, std::vector<std::pair<int, int>> *flagged) {
+                                  unsigned *dflags, std::vector<std::pair<int, int>> *flagged, int &nflagged) {
     int maxUE = 0;
     for (int k = 0; k < m; k++) maxUE = std::max(maxUE, cfgs[idx[k]].nUE);
     HIPCHK(launch_noma_activation(dparams, m, maxUE, dflags, e->stream));
@@ -403,12 +396,120 @@ static int noma_device_activation(prach_engine *e, const TrialDev *dparams, cons
         if (flagged) flagged->push_back({k, i});
     }
     HIPCHK(hipStreamSynchronize(e->stream));
-    e->noma_flagged += (int)nflag;
+    nflagged += (int)nflag;
     return PRACH_OK;
 }
 
-static int run_group(prach_engine *e, const prach_cfg *cfgs, const int *idx, int m, prach_result *results,
-                     prach_ue_log *const *ue_logs, int attempt, int G, double &kernel_ms, double &upload_ms) {
+// What one prach_run_trials call carries from launch to launch
+struct CallCtx {
+    const prach_cfg *cfgs;
+    prach_result *results;
+    prach_ue_log *const *ue_logs;
+    double kernel_ms = 0, upload_ms = 0;
+    int noma_flagged = 0, noma_ambiguous = 0; // UEs recomputed on the host, trials rerun with the host-built table
+};
+// How a rerun's launch differs from the first one
+struct LaunchOpts {
+    bool full_calendars = false; // batch kernel: lists of nUE entries, which cannot fill (trials that filled a calendar list)
+    bool host_act = false;       // NOMA.c: the activeUE table built on the host (trials whose device-built table left a gain comparison inside the error band)
+    bool no_pack = false;        // no XCD-packed placement (trials of a packed launch that timed out)
+};
+
+enum class Kernel { noma, batch, lcluster, cluster, trial };
+struct KernelChoice { // (rec_mode -1: noma_kernel and trial_kernel have no record layout, prach_timing keeps the previous launch's)
+    Kernel kind;
+    int rec_mode = -1, lslots = 0, maxgroups = 0, waves = 0, xpack = 0;
+};
+
+// the kernel, and its shape, of one launch over the trials idx[0..m) with G workgroups each (0: trial_kernel)
+static KernelChoice choose_kernel(const prach_engine *e, const prach_cfg *cfgs, const int *idx, int m, int G, int maxP, LaunchOpts o) {
+    const bool glibc = cfgs[idx[0]].rng_mode == PRACH_RNG_GLIBC;
+    KernelChoice kc{Kernel::trial};
+    if (G == 0) return kc;
+    // XCD-packed launch (prach_lcluster.hip): each cluster on one XCD, eight clusters side by side — when the clusters of the launch fit
+    // the XCDs' CUs that way (budgeted at one workgroup per CU: LDS-resident state fills a CU, the general layouts take more than half)
+    kc.xpack = e->opt_xcd_pack && !o.no_pack && G > 1 && ((m + 7) / 8) * G <= e->num_cus / 8;
+    if (cfgs[idx[0]].variant == PRACH_VARIANT_NOMA_C) { kc.kind = Kernel::noma; return kc; }
+    // one workgroup per trial, Philox: the batch kernel (prach_batch.hip), within its limits
+    bool batch = G == 1;
+    for (int k = 0; k < m && batch; k++) batch = batch_eligible(e, cfgs[idx[k]]);
+    if (batch) {
+        kc.kind = Kernel::batch;
+        kc.rec_mode = CLUSTER_REC_BATCH;
+        // Workgroup shape (speed only, same results).  A launch is as long as its longest trial alone or as its work needs, whichever is more: a 100 000-UE
+        // trial runs 127 ms on 16 wavefronts and 152 ms on 8, so while the trials fit the CUs in two rounds the 1024-thread shape wins (510 sweep trials:
+        // 159 / 272 ms — Beta.c / WithNOMA — against 163 / 290 ms); past two per CU a third round starts, and two 512-thread workgroups = two trials per CU,
+        // which hide each other's barriers, win (560 trials: 165 / 288 against 171 / 294 ms; 740: 171 / 327 against 218 / 395; 1000: 207 / 442 against
+        // 288 / 517; 2000: 381 / 811 against 566 / 1 005): scripts/gpu_shape_probe.sh.
+        kc.waves = glibc ? 16 : e->opt_batch_waves ? (int)e->opt_batch_waves : m > 2 * e->num_cus ? 8 : 16;
+        return kc;
+    }
+    // one workgroup per trial in the reference's rand() stream: 8 + 4 byte hot records, if every subframe number of every trial of
+    // the launch fits 16 bits (txTime <= t + 59 + backoff + accessTime).  (Philox with one workgroup per trial is the batch kernel's.)
+    bool compact = G == 1 && !e->opt_wide_records && glibc;
+    for (int k = 0; k < m && compact; k++) {
+        const prach_cfg &c = cfgs[idx[k]];
+        compact = (int64_t)prach_max_time(&c) + c.backoff + c.accessTime + 64 < 63000;
+    }
+    kc.lslots = lds_record_slots(e, cfgs, idx, m, G, maxP, &kc.maxgroups);
+    kc.rec_mode = (glibc ? kc.lslots > 0 : use_fast_kernel(e, kc.lslots, maxP)) ? CLUSTER_REC_LFAST : (kc.lslots > 0 ? CLUSTER_REC_L16 : (compact ? CLUSTER_REC_H8 : CLUSTER_REC_G16));
+    kc.kind = kc.rec_mode == CLUSTER_REC_LFAST ? Kernel::lcluster : Kernel::cluster;
+    if (kc.rec_mode == CLUSTER_REC_H8) kc.xpack = 0;
+    return kc;
+}
+
+// f(0), ..., f(n - 1) dealt round-robin to up to nth host threads (the caller's among them)
+template <class F> static void parallel_for(int nth, size_t n, const F &f) {
+    nth = (int)std::min<size_t>((size_t)std::max(1, nth), std::max<size_t>(1, n));
+    auto work = [&](int tix) { for (size_t j = (size_t)tix; j < n; j += (size_t)nth) f(j); };
+    std::vector<std::thread> th;
+    for (int tix = 1; tix < nth; tix++) th.emplace_back(work, tix);
+    work(0);
+    for (auto &x : th) x.join();
+}
+
+// PRACH_PRINT_STAMPS (the diagnostic build's cycle stamps) and PRACH_VERBOSE (why a trial left its kernel): one trial of a finished launch
+static int print_launch_diagnostics(const prach_engine *e, const prach_cfg &c, const DevResult &dr, const TrialLayout &L, const char *A, int G, bool noma) {
+    if (const char *stamps = std::getenv("PRACH_PRINT_STAMPS")) {
+        std::fprintf(stderr, "[prach stamps/step] pass=%.0f publish=%.0f barrier=%.0f gather=%.0f r1b=%.0f leavers=%.0f checks=%.0f grants=%.0f cycles | N avg %.1f max %llu, resetcand avg %.2f, singles avg %.1f max %llu\n",
+                     dr.stamps6[0] / (double)dr.steps, dr.stamps6[1] / (double)dr.steps, dr.stamps6[2] / (double)dr.steps, dr.stamps6[3] / (double)dr.steps,
+                     dr.stamps6[4] / (double)dr.steps, dr.stamps6[5] / (double)dr.steps, dr.stamps6[6] / (double)dr.steps, dr.stamps6[7] / (double)dr.steps,
+                     dr.dbg[0] / (double)dr.steps, dr.dbg[1], dr.dbg[2] / (double)dr.steps, (dr.dbg[3] >> 20) / (double)dr.steps, dr.dbg[3] & 0xfffff);
+        static const char *const nm[24] = {"head", "phaseB", "S1", "leavers", "S2", "publish", "window-rest", "take1", "S3", "round2", "S4", "calls", "S5", "grants", "S6", "phaseA",
+                                           "w:phaseA|A-barrier", "w:loads", "w:refill", "t:buckets", "-", "-", "-", "-"};
+        static const char *const nmb[24] = {"head", "joins", "-", "body", "S1", "leavers", "S2", "classify", "S4", "calls", "S5", "grants", "S6", "-", "-", "-",
+                                            "-", "-", "-", "-", "-", "-", "-", "-"}; // prach_batch.hip
+        static const char *const nmn[24] = {"head", "publish+gather", "gather-barrier", "resolve(w0)", "resolve-barrier", "passB+A(w0)", "pass-barrier", "-", "r:to-gains", "r:rank+sort", "r:pairing", "-", "-", "-", "-", "-",
+                                            "-", "-", "-", "-", "-", "-", "-", "-"}; // prach_noma.hip, per SUBFRAME (x accessTime = per slot)
+        const char *const *const names = noma ? nmn : e->last.rec_mode == CLUSTER_REC_BATCH ? nmb : nm;
+        std::fprintf(stderr, "[prach fine stamps/step] nUE=%d steps=%llu", c.nUE, (unsigned long long)dr.steps);
+        for (int q = 0; q < 20; q++) if (names[q][0] != '-') std::fprintf(stderr, " %s=%.0f", names[q], dr.fstamps[q] / (double)dr.steps);
+        std::fprintf(stderr, "\n");
+        if (L.diag && e->last.rec_mode == CLUSTER_REC_LFAST && std::atoi(stamps) >= 2) {
+            // every workgroup of the cluster on its own clock (thread PRACH_STAMP_TID): cycles per subframe and phase, then its event UEs per subframe
+            std::vector<unsigned long long> dg(32 * (size_t)G);
+            HIPCHK(hipMemcpy(dg.data(), A + L.diag, 8 * dg.size(), hipMemcpyDeviceToHost));
+            static const char *const nmw[20] = {"head", "phaseB", "S1", "leavers", "S2", "publish", "window-rest", "take1", "S3", "round2", "S4", "calls", "S5", "grants", "S6", "-",
+                                                "w:phaseA", "w:loads", "w:refill", "t:buckets"};
+            for (int b_ = 0; b_ < G; b_++) {
+                std::fprintf(stderr, "[prach wg stamps/step] nUE=%d steps=%llu b=%d", c.nUE, (unsigned long long)dr.steps, b_);
+                for (int q = 0; q < 20; q++) if (nmw[q][0] != '-') std::fprintf(stderr, " %s=%.0f", nmw[q], dg[32 * (size_t)b_ + q] / (double)dr.steps);
+                std::fprintf(stderr, " queued=%.2f late-buckets=%.3f late-header=%.3f refills=%.2f\n", dg[32 * (size_t)b_ + 24] / (double)dr.steps, dg[32 * (size_t)b_ + 25] / (double)dr.steps,
+                             dg[32 * (size_t)b_ + 26] / (double)dr.steps, dg[32 * (size_t)b_ + 27] / (double)dr.steps);
+            }
+        }
+    }
+    if (dr.status != PRACH_OK && e->last.rec_mode == CLUSTER_REC_LFAST && std::getenv("PRACH_VERBOSE"))
+        std::fprintf(stderr, "[prach] lcluster_kernel: trial nUE=%d left at subframe %d with status %d, capacity code %d\n", c.nUE, dr.time_exit, dr.status, dr.hard_error);
+    if (dr.status == PRACH_ERR_INTERNAL && e->last.rec_mode == CLUSTER_REC_BATCH && std::getenv("PRACH_VERBOSE"))
+        std::fprintf(stderr, "[prach] batch_kernel: trial nUE=%d (P %d B %d G %d R %d M %d A %d u %d) left at subframe %d: capacity %d (2 reset-cycle candidates, 3 singleton callers, 4 crossing bin, 5 a join list, 6 the grant notes, 8 a chunk table, 9 the chunk pool)\n", c.nUE, c.nPreamble, c.backoff, c.nGrantUL, c.maxRarWindow, c.maxMsg2TxCount, c.accessTime, c.uniform, dr.time_exit, dr.hard_error);
+    return PRACH_OK;
+}
+
+// one launch over the trials idx[0..m) (all the same rng_mode); attempt = glibc stream retry level.  Batch-kernel trials that filled a calendar list
+// are appended to cal_overflow.
+static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int attempt, int G, LaunchOpts o, std::vector<int> &cal_overflow) {
+    const prach_cfg *const cfgs = cx.cfgs;
     const int rng_mode = cfgs[idx[0]].rng_mode;
     const bool noma = cfgs[idx[0]].variant == PRACH_VARIANT_NOMA_C;
     std::vector<size_t> slen(m, 0);
@@ -418,19 +519,18 @@ static int run_group(prach_engine *e, const prach_cfg *cfgs, const int *idx, int
         if (rng_mode == PRACH_RNG_GLIBC) slen[k] = (size_t)stream_budget(c, attempt, e->opt_stream_factor, e->draws_per_ue_seen);
         if (c.nPreamble > maxP) maxP = c.nPreamble;
     }
-    // one workgroup per trial, Philox: the batch kernel (prach_batch.hip), within its limits
-    bool batch = G == 1;
-    for (int k = 0; k < m && batch; k++) batch = batch_eligible(e, cfgs[idx[k]]);
+    const KernelChoice kc = choose_kernel(e, cfgs, idx, m, G, maxP, o);
+    const bool batch = kc.kind == Kernel::batch;
     for (int k = 0; k < m; k++) // the dormant per-sector grant path exists in trial_kernel (G == 0) and in the batch kernel only
         if ((cfgs[idx[k]].flags & PRACH_FLAG_SECTOR_GRANTS) && G > 0 && !batch) return PRACH_ERR_INTERNAL;
     // NOMA.c's activeUE table: built by the device (noma_activation_kernel) unless the option or a rerun asks for the host's libm
-    const bool host_act = noma && (e->opt_noma_host_activation || e->force_host_act);
-    const LaunchLayout LL = layout_launch(cfgs, idx, m, ue_logs, slen, G, batch, e->full_calendars, e->opt_calendar_cap);
+    const bool host_act = noma && (e->opt_noma_host_activation || o.host_act);
+    const LaunchLayout LL = layout_launch(cfgs, idx, m, cx.ue_logs, slen, G, batch, o.full_calendars, e->opt_calendar_cap);
     if (LL.end > e->mem_budget && m > 1) { // (e.g. the 10 000-trial grid with its calendars on ONE GPU: two or three launches instead of one)
         const int h = m / 2;
-        int rc = run_group(e, cfgs, idx, h, results, ue_logs, attempt, G, kernel_ms, upload_ms);
+        int rc = run_group(e, cx, idx, h, attempt, G, o, cal_overflow);
         if (rc != PRACH_OK) return rc;
-        return run_group(e, cfgs, idx + h, m - h, results, ue_logs, attempt, G, kernel_ms, upload_ms);
+        return run_group(e, cx, idx + h, m - h, attempt, G, o, cal_overflow);
     }
     { int rc = ensure_arena(e, LL.end); if (rc != PRACH_OK) return rc; }
     { int rc = ensure_pinned(e, std::max(LL.staged_end, sizeof(DevResult) * (size_t)m)); if (rc != PRACH_OK) return rc; }
@@ -505,20 +605,12 @@ static int run_group(prach_engine *e, const prach_cfg *cfgs, const int *idx, int
             d.n_devact = host_act ? 0 : (e->opt_noma_ambiguity_test ? 2 : 1);
         }
     }
-    if (rng_mode == PRACH_RNG_GLIBC) { // one 31-word window per chunk of every trial's stream window: the trials dealt to the host cores (100 trials x 200 jump-aheads: 25 ms on one)
-        const int nth = std::min(host_threads(e), std::max(1, m));
-        auto work = [&](int tix) {
-            for (int k = tix; k < m; k += nth) {
-                const prach_cfg &c = cfgs[idx[k]];
-                const TrialLayout &L = LL.t[k];
-                prach_internal_glibc_seeds((uint32_t)c.seed, c.stream_offset, L.nchunks, STREAM_CHUNK, reinterpret_cast<uint32_t *>(H + L.seeds));
-            }
-        };
-        std::vector<std::thread> th;
-        for (int tix = 1; tix < nth; tix++) th.emplace_back(work, tix);
-        work(0);
-        for (auto &x : th) x.join();
-    }
+    if (rng_mode == PRACH_RNG_GLIBC) // one 31-word window per chunk of every trial's stream window: the trials dealt to the host cores (100 trials x 200 jump-aheads: 25 ms on one)
+        parallel_for(host_threads(e), (size_t)m, [&](size_t k) {
+            const prach_cfg &c = cfgs[idx[k]];
+            const TrialLayout &L = LL.t[k];
+            prach_internal_glibc_seeds((uint32_t)c.seed, c.stream_offset, L.nchunks, STREAM_CHUNK, reinterpret_cast<uint32_t *>(H + L.seeds));
+        });
     if (noma && host_act) {
         // activeUE's per-UE attributes (NOMA.c:131-192: double-precision libm work, once per UE): built on the host with the
         // libm the reference links, UE ranges of all trials dealt to all host cores, then copied trial by trial
@@ -534,18 +626,12 @@ static int run_group(prach_engine *e, const prach_cfg *cfgs, const int *idx, int
             for (int lo = 0; lo < n; lo += step) jobs.push_back({k, lo, std::min(n, lo + step)});
         }
         std::vector<int> jrc(jobs.size(), PRACH_OK);
-        auto work = [&](int tix) {
-            for (size_t j = (size_t)tix; j < jobs.size(); j += (size_t)nth) {
-                const Job &J = jobs[j];
-                Tab &T = tabs[J.k];
-                jrc[j] = prach_noma_activation_range(&cfgs[idx[J.k]], J.lo, J.hi, T.pre0.data() + J.lo, T.sec.data() + J.lo, T.gn.data() + J.lo,
-                                                     T.lg.data() + J.lo, T.nd0.data() + J.lo);
-            }
-        };
-        std::vector<std::thread> th;
-        for (int tix = 1; tix < nth; tix++) th.emplace_back(work, tix);
-        work(0);
-        for (auto &x : th) x.join();
+        parallel_for(nth, jobs.size(), [&](size_t j) {
+            const Job &J = jobs[j];
+            Tab &T = tabs[J.k];
+            jrc[j] = prach_noma_activation_range(&cfgs[idx[J.k]], J.lo, J.hi, T.pre0.data() + J.lo, T.sec.data() + J.lo, T.gn.data() + J.lo,
+                                                 T.lg.data() + J.lo, T.nd0.data() + J.lo);
+        });
         for (int r : jrc) if (r != PRACH_OK) return r;
         for (int k = 0; k < m; k++) {
             const size_t nn = (size_t)cfgs[idx[k]].nUE;
@@ -564,8 +650,9 @@ static int run_group(prach_engine *e, const prach_cfg *cfgs, const int *idx, int
     HIPCHK(hipMemsetAsync(A + LL.zero_begin, 0, LL.zero_end - LL.zero_begin, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     auto t1 = std::chrono::steady_clock::now();
-    upload_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    cx.upload_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
 
+    const TrialDev *const dp = reinterpret_cast<const TrialDev *>(A);
     HIPCHK(hipEventRecord(e->ev0, e->stream));
     if (rng_mode == PRACH_RNG_GLIBC) { // every trial's stream window, ONE launch (a launch per trial: 0.45 ms each, prach_stream.hip)
         unsigned long long max_n = 0;
@@ -575,66 +662,32 @@ static int run_group(prach_engine *e, const prach_cfg *cfgs, const int *idx, int
     if (noma && !host_act) { // activeUE for every UE of the launch, inside the timed region
         std::vector<ActTab> tabs(m);
         for (int k = 0; k < m; k++) tabs[k] = {A + LL.t[k].n_pre0, A + LL.t[k].n_sector, A + LL.t[k].n_gain, A + LL.t[k].n_lgain, A + LL.t[k].n_nd0};
-        int rc = noma_device_activation(e, reinterpret_cast<const TrialDev *>(A), cfgs, idx, m, tabs, reinterpret_cast<unsigned *>(A + LL.act_flags), nullptr);
-        if (rc == NOMA_ACT_OVERFLOW_RC && !e->force_host_act) { // the same launch once more with the host-built table (the path a NOMA_AMBIGUOUS rerun takes)
-            e->force_host_act = true;
-            rc = run_group(e, cfgs, idx, m, results, ue_logs, attempt, G, kernel_ms, upload_ms);
-            e->force_host_act = false;
-            return rc;
+        int rc = noma_device_activation(e, dp, cfgs, idx, m, tabs, reinterpret_cast<unsigned *>(A + LL.act_flags), nullptr, cx.noma_flagged);
+        if (rc == NOMA_ACT_OVERFLOW_RC) { // the same launch once more with the host-built table (the path a NOMA_AMBIGUOUS rerun takes)
+            o.host_act = true;
+            return run_group(e, cx, idx, m, attempt, G, o, cal_overflow);
         }
         if (rc != PRACH_OK) return rc;
     }
-    if (noma) {
-        const int xpack = e->opt_xcd_pack && !e->pack_off && G > 1 && ((m + 7) / 8) * G <= e->num_cus / 8;
-        e->last.xcd_packed = xpack;
-        HIPCHK(launch_noma_kernel(reinterpret_cast<const TrialDev *>(A), m, G, maxP, xpack, e->stream));
+    const bool glibc = rng_mode == PRACH_RNG_GLIBC;
+    switch (kc.kind) {
+    case Kernel::noma: HIPCHK(launch_noma_kernel(dp, m, G, maxP, kc.xpack, e->stream)); break;
+    case Kernel::batch: HIPCHK(launch_batch_kernel(dp, m, kc.waves, glibc, e->stream)); break;
+    case Kernel::lcluster: HIPCHK(launch_lcluster_kernel(dp, m, G, kc.lslots, kc.xpack, glibc, kc.maxgroups, e->stream)); break;
+    case Kernel::cluster: HIPCHK(launch_cluster_kernel(dp, m, G, maxP, rng_mode, kc.rec_mode, kc.lslots, kc.xpack, e->stream)); break;
+    case Kernel::trial: HIPCHK(launch_trial_kernel(dp, m, rng_mode, maxP, e->stream)); break;
     }
-    else if (batch) {
-        e->last.rec_mode = CLUSTER_REC_BATCH;
-        e->last.xcd_packed = 0;
-        // Workgroup shape (speed only, same results).  A launch is as long as its longest trial alone or as its work needs, whichever is more: a 100 000-UE
-        // trial runs 127 ms on 16 wavefronts and 152 ms on 8, so while the trials fit the CUs in two rounds the 1024-thread shape wins (510 sweep trials:
-        // 159 / 272 ms — Beta.c / WithNOMA — against 163 / 290 ms); past two per CU a third round starts, and two 512-thread workgroups = two trials per CU,
-        // which hide each other's barriers, win (560 trials: 165 / 288 against 171 / 294 ms; 740: 171 / 327 against 218 / 395; 1000: 207 / 442 against
-        // 288 / 517; 2000: 381 / 811 against 566 / 1 005): scripts/gpu_shape_probe.sh.
-        int waves = (int)e->opt_batch_waves;
-        if (rng_mode == PRACH_RNG_GLIBC) waves = 16;
-        if (waves == 0) waves = m > 2 * e->num_cus ? 8 : 16;
-        e->last.workgroups = m;
-        HIPCHK(launch_batch_kernel(reinterpret_cast<const TrialDev *>(A), m, waves, rng_mode == PRACH_RNG_GLIBC, e->stream));
-    }
-    else if (G > 0) {
-        // one workgroup per trial in the reference's rand() stream: 8 + 4 byte hot records, if every subframe number of every trial of
-        // the launch fits 16 bits (txTime <= t + 59 + backoff + accessTime).  (Philox with one workgroup per trial is the batch kernel's.)
-        bool compact = G == 1 && !e->opt_wide_records && rng_mode == PRACH_RNG_GLIBC;
-        for (int k = 0; k < m && compact; k++) {
-            const prach_cfg &c = cfgs[idx[k]];
-            compact = (int64_t)prach_max_time(&c) + c.backoff + c.accessTime + 64 < 63000;
-        }
-        int maxgroups = 0;
-        const int lslots = lds_record_slots(e, cfgs, idx, m, G, maxP, &maxgroups);
-        const bool glibc = rng_mode == PRACH_RNG_GLIBC;
-        const int rec_mode = (glibc ? lslots > 0 : use_fast_kernel(e, lslots, maxP)) ? CLUSTER_REC_LFAST : (lslots > 0 ? CLUSTER_REC_L16 : (compact ? CLUSTER_REC_H8 : CLUSTER_REC_G16));
-        e->last.rec_mode = rec_mode;
-        // XCD-packed launch (prach_lcluster.hip): each cluster on one XCD, eight clusters side by side — when the clusters of the launch fit
-        // the XCDs' CUs that way (budgeted at one workgroup per CU: LDS-resident state fills a CU, the general layouts take more than half)
-        const int xpack = e->opt_xcd_pack && !e->pack_off && G > 1 && rec_mode != CLUSTER_REC_H8 && ((m + 7) / 8) * G <= e->num_cus / 8;
-        e->last.xcd_packed = xpack;
-        if (rec_mode == CLUSTER_REC_LFAST) HIPCHK(launch_lcluster_kernel(reinterpret_cast<const TrialDev *>(A), m, G, lslots, xpack, glibc, maxgroups, e->stream));
-        else {
-            HIPCHK(launch_cluster_kernel(reinterpret_cast<const TrialDev *>(A), m, G, maxP, rng_mode, rec_mode, lslots, xpack, e->stream));
-        }
-    }
-    else HIPCHK(launch_trial_kernel(reinterpret_cast<const TrialDev *>(A), m, rng_mode, maxP, e->stream));
     HIPCHK(hipEventRecord(e->ev1, e->stream));
     HIPCHK(hipMemcpyAsync(H, A + LL.out0, sizeof(DevResult) * (size_t)m, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    kernel_ms += ms;
+    cx.kernel_ms += ms;
     e->last.launches++;
     e->last.workgroups = m * (G > 0 ? G : 1);
     e->last.cluster_size = G;
+    if (kc.kind != Kernel::trial) e->last.xcd_packed = kc.xpack; // (trial_kernel has no placement: prach_timing keeps the previous launch's)
+    if (kc.rec_mode >= 0) e->last.rec_mode = kc.rec_mode;
 
     const DevResult *const drs = reinterpret_cast<const DevResult *>(H);
     std::vector<int32_t> timers;
@@ -642,10 +695,10 @@ static int run_group(prach_engine *e, const prach_cfg *cfgs, const int *idx, int
         const prach_cfg &c = cfgs[idx[k]];
         const TrialLayout &L = LL.t[k];
         const DevResult &dr = drs[k];
-        prach_result &r = results[idx[k]];
+        prach_result &r = cx.results[idx[k]];
         std::memset(&r, 0, sizeof(r));
         r.status = (dr.hard_error && dr.status == PRACH_ERR_TIMEOUT) ? PRACH_ERR_INTERNAL : dr.status; // (a capacity overflow somewhere in the cluster is the cause, a peer's time-out its effect)
-        if (noma && dr.hard_error == NOMA_AMBIGUOUS && r.status == PRACH_OK) { r.status = PRACH_ERR_INTERNAL; e->noma_ambiguous++; } // (rerun with the host-built table: run_trials)
+        if (noma && dr.hard_error == NOMA_AMBIGUOUS && r.status == PRACH_OK) { r.status = PRACH_ERR_INTERNAL; cx.noma_ambiguous++; } // (rerun with the host-built table: run_trials)
         r.time_exit = dr.time_exit;
         r.maxTime = prach_max_time(&c);
         r.nSuccessUE = dr.nSuccess;
@@ -667,41 +720,8 @@ static int run_group(prach_engine *e, const prach_cfg *cfgs, const int *idx, int
             r.time_exit = (int32_t)dr.dbg[0] - 1;
             r.steps = dr.dbg[0];
         }
-        if (std::getenv("PRACH_PRINT_STAMPS"))
-            std::fprintf(stderr, "[prach stamps/step] pass=%.0f publish=%.0f barrier=%.0f gather=%.0f r1b=%.0f leavers=%.0f checks=%.0f grants=%.0f cycles | N avg %.1f max %llu, resetcand avg %.2f, singles avg %.1f max %llu\n",
-                         dr.stamps6[0] / (double)dr.steps, dr.stamps6[1] / (double)dr.steps, dr.stamps6[2] / (double)dr.steps, dr.stamps6[3] / (double)dr.steps,
-                         dr.stamps6[4] / (double)dr.steps, dr.stamps6[5] / (double)dr.steps, dr.stamps6[6] / (double)dr.steps, dr.stamps6[7] / (double)dr.steps,
-                         dr.dbg[0] / (double)dr.steps, dr.dbg[1], dr.dbg[2] / (double)dr.steps, (dr.dbg[3] >> 20) / (double)dr.steps, dr.dbg[3] & 0xfffff);
-        if (std::getenv("PRACH_PRINT_STAMPS")) {
-            static const char *const nm[24] = {"head", "phaseB", "S1", "leavers", "S2", "publish", "window-rest", "take1", "S3", "round2", "S4", "calls", "S5", "grants", "S6", "phaseA",
-                                               "w:phaseA|A-barrier", "w:loads", "w:refill", "t:buckets", "-", "-", "-", "-"};
-            static const char *const nmb[24] = {"head", "joins", "-", "body", "S1", "leavers", "S2", "classify", "S4", "calls", "S5", "grants", "S6", "-", "-", "-",
-                                                "-", "-", "-", "-", "-", "-", "-", "-"}; // prach_batch.hip
-            static const char *const nmn[24] = {"head", "publish+gather", "gather-barrier", "resolve(w0)", "resolve-barrier", "passB+A(w0)", "pass-barrier", "-", "r:to-gains", "r:rank+sort", "r:pairing", "-", "-", "-", "-", "-",
-                                                "-", "-", "-", "-", "-", "-", "-", "-"}; // prach_noma.hip, per SUBFRAME (x accessTime = per slot)
-            const char *const *const names = noma ? nmn : e->last.rec_mode == CLUSTER_REC_BATCH ? nmb : nm;
-            std::fprintf(stderr, "[prach fine stamps/step] nUE=%d steps=%llu", c.nUE, (unsigned long long)dr.steps);
-            for (int q = 0; q < 20; q++) if (names[q][0] != '-') std::fprintf(stderr, " %s=%.0f", names[q], dr.fstamps[q] / (double)dr.steps);
-            std::fprintf(stderr, "\n");
-        }
-        if (L.diag && e->last.rec_mode == CLUSTER_REC_LFAST && std::getenv("PRACH_PRINT_STAMPS") && std::atoi(std::getenv("PRACH_PRINT_STAMPS")) >= 2) {
-            // every workgroup of the cluster on its own clock (thread PRACH_STAMP_TID): cycles per subframe and phase, then its event UEs per subframe
-            std::vector<unsigned long long> dg(32 * (size_t)G);
-            HIPCHK(hipMemcpy(dg.data(), A + L.diag, 8 * dg.size(), hipMemcpyDeviceToHost));
-            static const char *const nm[20] = {"head", "phaseB", "S1", "leavers", "S2", "publish", "window-rest", "take1", "S3", "round2", "S4", "calls", "S5", "grants", "S6", "-",
-                                               "w:phaseA", "w:loads", "w:refill", "t:buckets"};
-            for (int b_ = 0; b_ < G; b_++) {
-                std::fprintf(stderr, "[prach wg stamps/step] nUE=%d steps=%llu b=%d", c.nUE, (unsigned long long)dr.steps, b_);
-                for (int q = 0; q < 20; q++) if (nm[q][0] != '-') std::fprintf(stderr, " %s=%.0f", nm[q], dg[32 * (size_t)b_ + q] / (double)dr.steps);
-                std::fprintf(stderr, " queued=%.2f late-buckets=%.3f late-header=%.3f refills=%.2f\n", dg[32 * (size_t)b_ + 24] / (double)dr.steps, dg[32 * (size_t)b_ + 25] / (double)dr.steps,
-                             dg[32 * (size_t)b_ + 26] / (double)dr.steps, dg[32 * (size_t)b_ + 27] / (double)dr.steps);
-            }
-        }
-        if (dr.status != PRACH_OK && e->last.rec_mode == CLUSTER_REC_LFAST && std::getenv("PRACH_VERBOSE"))
-            std::fprintf(stderr, "[prach] lcluster_kernel: trial nUE=%d left at subframe %d with status %d, capacity code %d\n", c.nUE, dr.time_exit, dr.status, dr.hard_error);
-        if (batch && dr.status == PRACH_ERR_INTERNAL && (dr.hard_error == 5 || dr.hard_error == 8 || dr.hard_error == 9) && !e->full_calendars) e->cal_overflow.push_back(idx[k]);
-        if (dr.status == PRACH_ERR_INTERNAL && e->last.rec_mode == CLUSTER_REC_BATCH && std::getenv("PRACH_VERBOSE"))
-            std::fprintf(stderr, "[prach] batch_kernel: trial nUE=%d (P %d B %d G %d R %d M %d A %d u %d) left at subframe %d: capacity %d (2 reset-cycle candidates, 3 singleton callers, 4 crossing bin, 5 a join list, 6 the grant notes, 8 a chunk table, 9 the chunk pool)\n", c.nUE, c.nPreamble, c.backoff, c.nGrantUL, c.maxRarWindow, c.maxMsg2TxCount, c.accessTime, c.uniform, dr.time_exit, dr.hard_error);
+        { int rc = print_launch_diagnostics(e, c, dr, L, A, G, noma); if (rc != PRACH_OK) return rc; }
+        if (batch && dr.status == PRACH_ERR_INTERNAL && (dr.hard_error == 5 || dr.hard_error == 8 || dr.hard_error == 9) && !o.full_calendars) cal_overflow.push_back(idx[k]);
         if (dr.status != PRACH_OK) continue;
         // totalDelay is a FLOAT running sum in index order (Beta.c:186,193): exact in integer
         // arithmetic while it stays below 2^24, otherwise replay the float additions on the host.
@@ -716,7 +736,7 @@ static int run_group(prach_engine *e, const prach_cfg *cfgs, const int *idx, int
             r.totalDelay = td_;
         }
         if (L.logs)
-            HIPCHK(hipMemcpy(ue_logs[idx[k]], A + L.logs, sizeof(prach_ue_log) * (size_t)c.nUE, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(cx.ue_logs[idx[k]], A + L.logs, sizeof(prach_ue_log) * (size_t)c.nUE, hipMemcpyDeviceToHost));
     }
     return PRACH_OK;
 }
@@ -724,33 +744,115 @@ static int run_group(prach_engine *e, const prach_cfg *cfgs, const int *idx, int
 // A trial that a cluster launch could not finish — a per-subframe LDS capacity exceeded (PRACH_ERR_INTERNAL) or a workgroup
 // that waited too long for a peer (PRACH_ERR_TIMEOUT: the cluster's workgroups were not all resident, e.g. another process
 // holds CUs) — is rerun, exactly, on a kernel that needs neither.  Never silently: counted in prach_timing and reported.
-static void note_fallback(prach_engine *e, const char *what, size_t ntrials, size_t ntimeouts, int G) {
+static void note_fallback(prach_engine *e, const CallCtx &cx, const char *what, const std::vector<int> &trials, int G) {
+    const size_t ntrials = trials.size();
+    size_t ntimeouts = 0;
+    for (int k : trials) ntimeouts += cx.results[k].status == PRACH_ERR_TIMEOUT;
     e->last.fallback_trials += (int32_t)ntrials;
     e->last.spin_timeouts += (int32_t)ntimeouts;
     std::fprintf(stderr, "[prach] %zu trial(s) of a %d-workgroup cluster launch are rerun on %s (%zu exceeded a per-subframe capacity, %zu timed out "
                          "waiting for a peer workgroup: cluster not co-resident?)\n", ntrials, G, what, ntrials - ntimeouts, ntimeouts);
 }
 
-// Batch-kernel trials that filled a calendar list (a parameter set that synchronises more UEs onto one subframe than the list was sized for): once more on the
-// same kernel with lists of nUE entries, which cannot fill.  Never silently: counted as fallback trials and reported.
-static int rerun_full_calendars(prach_engine *e, const prach_cfg *cfgs, prach_result *results, prach_ue_log *const *ue_logs, double &kernel_ms, double &upload_ms) {
-    if (e->cal_overflow.empty()) return PRACH_OK;
-    std::vector<int> todo;
-    todo.swap(e->cal_overflow);
-    e->last.fallback_trials += (int32_t)todo.size();
-    std::fprintf(stderr, "[prach] %zu trial(s) filled a calendar list of prach::batch_kernel: rerun with lists of nUE entries\n", todo.size());
-    e->full_calendars = true;
-    int rc = PRACH_OK;
-    for (int attempt = 0; !todo.empty() && rc == PRACH_OK; attempt++) {
-        if (attempt > 6) { rc = PRACH_ERR_STREAM; break; }
-        rc = run_group(e, cfgs, todo.data(), (int)todo.size(), results, ue_logs, attempt, 1, kernel_ms, upload_ms);
-        std::vector<int> again;
-        for (int k : todo) if (results[k].status == PRACH_ERR_STREAM) again.push_back(k); // (the reference's stream: a larger window)
+// The trials `todo` with G workgroups each (0: trial_kernel) until each has finished or left its kernel: a trial whose glibc draw-stream window ran out
+// is rerun with a larger one (attempt + 1; after 7 attempts: PRACH_ERR_STREAM); batch-kernel trials that filled a calendar list (a parameter set that
+// synchronises more UEs onto one subframe than the list was sized for) once more with lists of nUE entries, which cannot fill — never silently: counted
+// as fallback trials and reported; with `unpack`, trials that timed out on an XCD-packed launch at attempt + 1 as a plain one (not a fallback either).
+// `left`: the trials that ended in PRACH_ERR_INTERNAL or PRACH_ERR_TIMEOUT.
+static int run_with_retries(prach_engine *e, CallCtx &cx, std::vector<int> todo, int G, LaunchOpts o, std::vector<int> *left = nullptr, bool unpack = false) {
+    if (left) left->clear();
+    for (int attempt = 0; !todo.empty(); attempt++) {
+        if (attempt > 6) return PRACH_ERR_STREAM;
+        std::vector<int> cal, again;
+        int rc = run_group(e, cx, todo.data(), (int)todo.size(), attempt, G, o, cal);
+        if (rc != PRACH_OK) return rc;
+        if (!cal.empty()) {
+            e->last.fallback_trials += (int32_t)cal.size();
+            std::fprintf(stderr, "[prach] %zu trial(s) filled a calendar list of prach::batch_kernel: rerun with lists of nUE entries\n", cal.size());
+            LaunchOpts full = o;
+            full.full_calendars = true;
+            rc = run_with_retries(e, cx, cal, G, full); // (these trials are in `todo` as well: their statuses are read below)
+            if (rc != PRACH_OK) return rc;
+        }
+        const bool was_packed = e->last.xcd_packed != 0;
+        o.no_pack = false;
+        for (int k : todo) {
+            const int s = cx.results[k].status;
+            if (s == PRACH_ERR_STREAM) again.push_back(k); // (the reference's stream: a larger window)
+            else if (s == PRACH_ERR_TIMEOUT && was_packed && unpack) { // the packed placement did not hold: plain cluster launch
+                again.push_back(k);
+                o.no_pack = true;
+            }
+            else if ((s == PRACH_ERR_INTERNAL || s == PRACH_ERR_TIMEOUT) && left) left->push_back(k);
+        }
+        if (o.no_pack) {
+            std::fprintf(stderr, "[prach] %zu trial(s) of an XCD-packed cluster launch timed out waiting for a peer workgroup: rerun as a plain cluster launch\n", again.size());
+            e->last.spin_timeouts += (int32_t)again.size();
+        }
         todo.swap(again);
     }
-    e->full_calendars = false;
-    e->cal_overflow.clear();
-    return rc;
+    return PRACH_OK;
+}
+
+// The fallback ladder of Beta.c / WithNOMA trials, cluster(G) -> prach::batch_kernel -> trial_kernel, entered at cluster(G) (G = 1 on batch-eligible
+// trials: the batch kernel itself).  What is left for trial_kernel is appended to `to_trial`, which the caller runs with the trials that start there.
+static int descend_ladder(prach_engine *e, CallCtx &cx, const std::vector<int> &idx, int G, std::vector<int> &to_trial) {
+    std::vector<int> left;
+    int rc = run_with_retries(e, cx, idx, G, LaunchOpts{}, &left, true);
+    if (rc != PRACH_OK) return rc;
+    if (left.empty()) return PRACH_OK;
+    bool to_batch = G > 1;
+    for (int k : left) to_batch = to_batch && batch_eligible(e, cx.cfgs[k]);
+    note_fallback(e, cx, to_batch ? "prach::batch_kernel (one workgroup per trial, event queue without a capacity)"
+                                  : "trial_kernel (one workgroup per trial, no per-subframe capacity)", left, G);
+    if (to_batch) {
+        // Overflow without the cliff: most capacities a cluster trips over are PER WORKGROUP (512 event granules per mailbox, the
+        // candidate list) or come with its LDS-resident layout; prach::batch_kernel has neither (one workgroup, the event queue
+        // continues in global memory) and still runs all 16 wavefronts on the trial, so such trials go there first — the
+        // one-workgroup, index-ordered trial_kernel (no per-subframe capacity at all, ~10x slower) only gets what is left.
+        std::vector<int> still;
+        rc = run_with_retries(e, cx, left, 1, LaunchOpts{}, &still);
+        if (rc != PRACH_OK) return rc;
+        left.swap(still);
+        if (!left.empty()) std::fprintf(stderr, "[prach] %zu of them exceeded a capacity of the batch kernel's resolver too: rerun on trial_kernel\n", left.size());
+    }
+    e->last.trial_kernel_reruns += (int32_t)left.size();
+    to_trial.insert(to_trial.end(), left.begin(), left.end());
+    return PRACH_OK;
+}
+
+// Workgroups per trial of a cluster launch over the trials idx: the engine option, or else the largest power of two up to `cap` that fits the resident
+// workgroups and leaves each workgroup 16 UE groups or more (`overrides`: then the measured exceptions); last, halved until every cluster is resident.
+static int cluster_size(const prach_engine *e, const prach_cfg *cfgs, const std::vector<int> &idx, size_t resident, int cap, bool overrides) {
+    int minGroups = INT_MAX;
+    for (int k : idx) minGroups = std::min(minGroups, (cfgs[k].nUE + 63) / 64);
+    int G = (int)e->opt_cluster;
+    if (G <= 0) {
+        G = 1;
+        while (G * 2 <= cap && (size_t)G * 2 * idx.size() <= resident && G * 2 <= std::max(1, minGroups / 16)) G *= 2;
+        if (overrides) {
+            bool all_batch = true;
+            for (int k : idx) all_batch = all_batch && batch_eligible(e, cfgs[k]);
+            // two workgroups per trial are not worth their exchange: 100 sweep trials run 151 / 242 ms (Beta.c / WithNOMA) on the batch kernel, one
+            // workgroup each, against 221 / 471 ms on 2-workgroup clusters, whose halves of a 100 000-UE trial also overflow the 512 event
+            // granules of a mailbox (32 of 100 trials rerun); from four workgroups per trial on, clusters win (scripts/gpu_probe_mid_batches.py)
+            // (the reference's own stream, 100 trials of one sweep point: 246 / 431 ms on batch_kernel<16, true> against 657 / 2 126 ms — Beta.c / WithNOMA,
+            //  nUE = 100 000, the latter with every trial overflowing its mailboxes — on 2-workgroup clusters: scripts/gpu_probe_glibc_batches.py)
+            // (in the reference's stream also against four workgroups per trial, which run on the general kernel: 50 trials 210 / 338 ms against 351 / 501 ms
+            //  at nUE = 100 000, 73 / 100 against 84 / 108 ms at 20 000; from eight workgroups per trial on the clusters are level or ahead)
+            // (round 4's batch kernel is level with four workgroups per trial in Philox mode as well: 60 sweep trials 126 / 185 ms — Beta.c / WithNOMA — against
+            //  136 / 190 ms on 4-workgroup clusters; eight workgroups per trial stay ahead: 30 trials 95 / 118 against 126 / 184 ms)
+            if ((G == 2 || G == 4) && all_batch) G = 1;
+            // Uniform arrivals over 60 000 subframes (Beta.c:92-95): only nUE / 60 000 arrivals per subframe, a UE lives some
+            // tens of subframes, finished groups are skipped 32 at a time — the live band is a few groups and one workgroup
+            // steps through a subframe faster than a cluster exchanges (nUE = 100 000: 5.1 vs 6.2 us per subframe)
+            bool light = cfgs[idx[0]].rng_mode == PRACH_RNG_PHILOX;
+            for (int k : idx) light = light && cfgs[k].uniform && cfgs[k].nUE <= 2000000;
+            if (light) G = 1;
+        }
+    }
+    while (G > 1 && (size_t)G * idx.size() > resident) G /= 2;
+    return G;
 }
 
 static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs) {
@@ -766,8 +868,7 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
     HIPCHK(hipSetDevice(e->device));
     auto t0 = std::chrono::steady_clock::now();
     e->last = prach_timing{};
-    e->noma_flagged = e->noma_ambiguous = 0;
-    double kernel_ms = 0, upload_ms = 0;
+    CallCtx cx{cfgs, results, ue_logs};
     // NOMA.c in the reference's OWN rand() stream: activeUE's rejection loops make every stream position data dependent and its libm
     // calls must be the reference's, so the arrivals are activated on the host between device steps (prach_noma_glibc.hip): one trial
     // at a time, one launch per access slot — the bit-exact-vs-the-reference's-files mode, not the throughput mode
@@ -784,7 +885,7 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
                 const unsigned long long len = window(k, attempt);
                 std::vector<int32_t> hs((size_t)len);
                 prach_glibc_stream((uint32_t)cfgs[k].seed, cfgs[k].stream_offset, len, hs.data());
-                rc = run_noma_glibc_trial(e->stream, cfgs[k], hs.data(), len, &results[k], ue_logs ? ue_logs[k] : nullptr, &kernel_ms);
+                rc = run_noma_glibc_trial(e->stream, cfgs[k], hs.data(), len, &results[k], ue_logs ? ue_logs[k] : nullptr, &cx.kernel_ms);
                 e->last.launches++;
             }
             return rc;
@@ -806,7 +907,7 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
             for (int j = 0; j < m; j++) { pc[j] = &cfgs[todo[j]]; lens[j] = window(todo[j], attempt); pr[j] = &results[todo[j]]; pl[j] = ue_logs ? ue_logs[todo[j]] : nullptr; }
             if (e->opt_noma_ambiguity_test) std::fill(rcs.begin(), rcs.end(), NOMA_GLIBC_AMBIGUOUS_RC); // (test hook: as if the kernel had found a value inside the band)
             else {
-                int rc = run_noma_glibc_batch(e->stream, pc.data(), m, lens.data(), pr.data(), pl.data(), &kernel_ms, rcs.data());
+                int rc = run_noma_glibc_batch(e->stream, pc.data(), m, lens.data(), pr.data(), pl.data(), &cx.kernel_ms, rcs.data());
                 e->last.launches++;
                 if (rc != PRACH_OK) return rc;
             }
@@ -816,7 +917,7 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
                 if (rcs[j] == PRACH_OK) continue;
                 if (rcs[j] == PRACH_ERR_STREAM) { again.push_back(k); continue; }
                 if (rcs[j] != NOMA_GLIBC_AMBIGUOUS_RC) return rcs[j];
-                e->noma_ambiguous++;
+                cx.noma_ambiguous++;
                 e->last.fallback_trials++;
                 if (std::getenv("PRACH_VERBOSE")) std::fprintf(stderr, "[prach] NOMA.c trial nUE=%d in the reference's stream: a value inside the device libm's error band, rerun with host-side activation\n", cfgs[k].nUE);
                 int rc = host_form(k);
@@ -830,33 +931,26 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
         for (int k = 0; k < n; k++)
             if (cfgs[k].variant == PRACH_VARIANT_NOMA_C && cfgs[k].rng_mode == PRACH_RNG_PHILOX) idx.push_back(k);
         if (!idx.empty()) {
-            int minGroups = INT_MAX, maxP = 1;
+            int maxP = 1;
             bool small = true;
             for (int k : idx) {
-                minGroups = std::min(minGroups, (cfgs[k].nUE + 63) / 64);
                 small = small && cfgs[k].nUE < (1 << 20) - 1;
                 maxP = std::max(maxP, cfgs[k].nPreamble);
             }
-            int G = (int)e->opt_cluster;
             const size_t resident = (size_t)resident_workgroups(e, noma_kernel_blocks_per_cu(maxP));
             e->last.resident_limit = (int32_t)resident;
             // (measured at nUE = 100 000: 23.2 ms with 16 workgroups, 24.3 with 32, 26.6 with 8: 6 x nPreamble bins per mailbox)
             // (NOMA.c's own experiment — 10 seeds x the sweep = 100 trials in one call — measured 106 ms with one workgroup per trial, 61 ms with two:
             //  the clusters may fill the CUs the occupancy query admits, not half of them)
-            if (G <= 0) { G = 1; while (G * 2 <= 16 && (size_t)G * 2 * idx.size() <= resident && G * 2 <= std::max(1, minGroups / 16)) G *= 2; }
-            while (G > 1 && (size_t)G * idx.size() > resident) G /= 2;
-            if (!small) G = 1; // 20-bit granule fields
-            int rc = run_group(e, cfgs, idx.data(), (int)idx.size(), results, ue_logs, 0, G, kernel_ms, upload_ms);
-            if (rc != PRACH_OK) return rc;
+            const int G = small ? cluster_size(e, cfgs, idx, resident, 16, false) : 1; // (!small: 20-bit granule fields)
             std::vector<int> again;
-            size_t nto = 0;
-            for (int k : idx)
-                if (results[k].status == PRACH_ERR_TIMEOUT || results[k].status == PRACH_ERR_INTERNAL) { again.push_back(k); nto += results[k].status == PRACH_ERR_TIMEOUT; }
-            if (!again.empty() && (G > 1 || e->noma_ambiguous > 0)) { // one workgroup per trial waits for nobody; the host-built table needs no error band
-                note_fallback(e, "noma_kernel with one workgroup per trial and the host-built activation table", again.size(), nto, G);
-                e->force_host_act = true;
-                rc = run_group(e, cfgs, again.data(), (int)again.size(), results, ue_logs, 0, 1, kernel_ms, upload_ms);
-                e->force_host_act = false;
+            int rc = run_with_retries(e, cx, idx, G, LaunchOpts{}, &again);
+            if (rc != PRACH_OK) return rc;
+            if (!again.empty() && (G > 1 || cx.noma_ambiguous > 0)) { // one workgroup per trial waits for nobody; the host-built table needs no error band
+                note_fallback(e, cx, "noma_kernel with one workgroup per trial and the host-built activation table", again, G);
+                LaunchOpts host;
+                host.host_act = true;
+                rc = run_with_retries(e, cx, again, 1, host);
                 if (rc != PRACH_OK) return rc;
             }
         }
@@ -874,131 +968,35 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
         });
         // trials only trial_kernel runs (index-ordered, exact, one workgroup each): the dormant per-sector grant path, sizes beyond the
         // cluster kernels' 20-bit granule fields / group tables — they leave the others on the cluster kernels
-        std::vector<int> solo;
-        {
-            std::vector<int> rest, sect;
-            for (int k : idx) {
-                const bool sector = (cfgs[k].flags & PRACH_FLAG_SECTOR_GRANTS) != 0;
-                const bool only_trial_kernel = sector || cfgs[k].nUE >= (1 << 20) - 1 || (mode == PRACH_RNG_GLIBC && cfgs[k].nUE > CLUSTER_GLIBC_MAX_UE);
-                (sector && !e->opt_legacy && batch_eligible(e, cfgs[k]) ? sect : only_trial_kernel ? solo : rest).push_back(k);
-            }
-            idx.swap(rest);
-            if (!sect.empty()) {
-                // the per-sector grant path in Philox mode: the batch kernel keeps the six budgets (one launch for these trials, one workgroup each;
-                // what exceeds a capacity of its resolver goes on to trial_kernel like any other trial)
-                int rc = run_group(e, cfgs, sect.data(), (int)sect.size(), results, ue_logs, 0, 1, kernel_ms, upload_ms);
-                if (rc != PRACH_OK) return rc;
-                rc = rerun_full_calendars(e, cfgs, results, ue_logs, kernel_ms, upload_ms);
-                if (rc != PRACH_OK) return rc;
-                size_t nbad = 0;
-                for (int k : sect) if (results[k].status != PRACH_OK) { solo.push_back(k); nbad++; }
-                if (nbad) { note_fallback(e, "trial_kernel (one workgroup per trial, no per-subframe capacity)", nbad, 0, 1); e->last.trial_kernel_reruns += (int32_t)nbad; }
-            }
+        std::vector<int> rest, sect, solo;
+        for (int k : idx) {
+            const bool sector = (cfgs[k].flags & PRACH_FLAG_SECTOR_GRANTS) != 0;
+            const bool only_trial_kernel = sector || cfgs[k].nUE >= (1 << 20) - 1 || (mode == PRACH_RNG_GLIBC && cfgs[k].nUE > CLUSTER_GLIBC_MAX_UE);
+            (sector && !e->opt_legacy && batch_eligible(e, cfgs[k]) ? sect : only_trial_kernel ? solo : rest).push_back(k);
         }
-        const bool cluster_ok = !e->opt_legacy && !idx.empty();
-        int maxP = 1;
-        for (int k : idx) maxP = std::max(maxP, cfgs[k].nPreamble);
-        if (!cluster_ok) { idx.insert(idx.end(), solo.begin(), solo.end()); solo.clear(); }
-        if (cluster_ok) {
+        std::vector<int> trial, sect_left;
+        // the per-sector grant path: the batch kernel keeps the six budgets (one launch for these trials, one workgroup each; a trial whose draw-stream
+        // window runs out retries there with a larger one, what exceeds a capacity of its resolver goes on to trial_kernel like any other trial)
+        if (!sect.empty()) { int rc = descend_ladder(e, cx, sect, 1, sect_left); if (rc != PRACH_OK) return rc; }
+        if (!e->opt_legacy && !rest.empty()) {
             // production path: cluster kernel, G workgroups per trial.  The workgroups of a cluster wait for each other, so
             // every cluster of the launch must be resident: G x trials <= what the occupancy query admits for this kernel
             // and LDS size (members of a cluster are consecutive workgroups: in-order dispatch completes whole clusters)
-            int minGroups = INT_MAX;
-            for (int k : idx) minGroups = std::min(minGroups, (cfgs[k].nUE + 63) / 64);
-            int G = (int)e->opt_cluster;
+            int maxP = 1;
+            for (int k : rest) maxP = std::max(maxP, cfgs[k].nPreamble);
             // (every cluster layout of this library takes more than half a CU's LDS: one workgroup per CU.  Asked of the runtime for the
             //  general kernel's smallest layout; the lean kernel and the LDS-resident layouts only ever need more LDS, never admit more)
             const size_t resident = (size_t)resident_workgroups(e, std::min(cluster_kernel_blocks_per_cu(maxP, mode, CLUSTER_REC_G16, 0), 1));
             e->last.resident_limit = (int32_t)resident;
-            if (G <= 0) {
-                G = 1;
-                // (the clusters of a call may fill the CUs: 8 trials of 100 000 UEs run 52 ms on 8 x 32 workgroups — the lean kernel, one XCD each —
-                //  against 78 ms on 8 x 16, 16 trials 78 ms on 16 x 16 against 96 ms on 16 x 8: scripts/gpu_probe_cluster_sizes.py)
-                while (G * 2 <= 32 && (size_t)G * 2 * idx.size() <= resident && G * 2 <= std::max(1, minGroups / 16)) G *= 2;
-                // Uniform arrivals over 60 000 subframes (Beta.c:92-95): only nUE / 60 000 arrivals per subframe, a UE lives some
-                // tens of subframes, finished groups are skipped 32 at a time — the live band is a few groups and one workgroup
-                // steps through a subframe faster than a cluster exchanges (nUE = 100 000: 5.1 vs 6.2 us per subframe)
-                // two workgroups per trial are not worth their exchange: 100 sweep trials run 151 / 242 ms (Beta.c / WithNOMA) on the batch kernel, one
-                // workgroup each, against 221 / 471 ms on 2-workgroup clusters, whose halves of a 100 000-UE trial also overflow the 512 event
-                // granules of a mailbox (32 of 100 trials rerun); from four workgroups per trial on, clusters win (scripts/gpu_probe_mid_batches.py)
-                // (the reference's own stream, 100 trials of one sweep point: 246 / 431 ms on batch_kernel<16, true> against 657 / 2 126 ms — Beta.c / WithNOMA,
-                //  nUE = 100 000, the latter with every trial overflowing its mailboxes — on 2-workgroup clusters: scripts/gpu_probe_glibc_batches.py)
-                bool all_batch = e->opt_batch != 0;
-                for (int k : idx) all_batch = all_batch && batch_eligible(e, cfgs[k]);
-                if (G == 2 && all_batch) G = 1;
-                // (in the reference's stream also against four workgroups per trial, which run on the general kernel: 50 trials 210 / 338 ms against 351 / 501 ms
-                //  at nUE = 100 000, 73 / 100 against 84 / 108 ms at 20 000; from eight workgroups per trial on the clusters are level or ahead)
-                if (G == 4 && all_batch && mode == PRACH_RNG_GLIBC) G = 1;
-                // (round 4's batch kernel is level with four workgroups per trial in Philox mode as well: 60 sweep trials 126 / 185 ms — Beta.c / WithNOMA — against
-                //  136 / 190 ms on 4-workgroup clusters; eight workgroups per trial stay ahead: 30 trials 95 / 118 against 126 / 184 ms)
-                if (G == 4 && all_batch) G = 1;
-                bool light = mode == PRACH_RNG_PHILOX;
-                for (int k : idx) light = light && cfgs[k].uniform && cfgs[k].nUE <= 2000000;
-                if (light) G = 1;
-            }
-            while (G > 1 && (size_t)G * idx.size() > resident) G /= 2;
-            std::vector<int> todo = idx, fallback;
-            size_t nto = 0;
-            for (int attempt = 0; !todo.empty(); attempt++) {
-                if (attempt > 6) return PRACH_ERR_STREAM;
-                int rc = run_group(e, cfgs, todo.data(), (int)todo.size(), results, ue_logs, attempt, G, kernel_ms, upload_ms);
-                if (rc != PRACH_OK) return rc;
-                rc = rerun_full_calendars(e, cfgs, results, ue_logs, kernel_ms, upload_ms); // (one workgroup per trial on the batch kernel: a full calendar list)
-                if (rc != PRACH_OK) return rc;
-                std::vector<int> again;
-                const bool was_packed = e->last.xcd_packed != 0;
-                e->pack_off = false;
-                for (int k : todo) {
-                    if (results[k].status == PRACH_ERR_STREAM) again.push_back(k);         // glibc: draw-stream window ran out: larger one
-                    else if (results[k].status == PRACH_ERR_TIMEOUT && was_packed) {       // the packed placement did not hold: plain cluster launch
-                        again.push_back(k);
-                        e->pack_off = true;
-                    }
-                    else if (results[k].status == PRACH_ERR_INTERNAL || results[k].status == PRACH_ERR_TIMEOUT) {
-                        fallback.push_back(k);
-                        nto += results[k].status == PRACH_ERR_TIMEOUT;
-                    }
-                }
-                if (e->pack_off) {
-                    std::fprintf(stderr, "[prach] %zu trial(s) of an XCD-packed cluster launch timed out waiting for a peer workgroup: rerun as a plain cluster launch\n", again.size());
-                    e->last.spin_timeouts += (int32_t)again.size();
-                }
-                todo.swap(again);
-            }
-            e->pack_off = false;
-            idx.swap(fallback);
-            bool to_batch = G > 1 && e->opt_batch && !idx.empty();
-            for (int k : idx) to_batch = to_batch && batch_eligible(e, cfgs[k]);
-            if (!idx.empty()) note_fallback(e, to_batch ? "prach::batch_kernel (one workgroup per trial, event queue without a capacity)"
-                                                        : "trial_kernel (one workgroup per trial, no per-subframe capacity)", idx.size(), nto, G);
-            if (to_batch) {
-                // Overflow without the cliff: most capacities a cluster trips over are PER WORKGROUP (512 event granules per mailbox, the
-                // candidate list) or come with its LDS-resident layout; prach::batch_kernel has neither (one workgroup, the event queue
-                // continues in global memory) and still runs all 16 wavefronts on the trial, so such trials go there first — the
-                // one-workgroup, index-ordered trial_kernel (no per-subframe capacity at all, ~10x slower) only gets what is left.
-                int rc = run_group(e, cfgs, idx.data(), (int)idx.size(), results, ue_logs, 0, 1, kernel_ms, upload_ms);
-                if (rc != PRACH_OK) return rc;
-                rc = rerun_full_calendars(e, cfgs, results, ue_logs, kernel_ms, upload_ms);
-                if (rc != PRACH_OK) return rc;
-                std::vector<int> still;
-                for (int k : idx) if (results[k].status != PRACH_OK) still.push_back(k);
-                idx.swap(still);
-                if (!idx.empty()) std::fprintf(stderr, "[prach] %zu of them exceeded a capacity of the batch kernel's resolver too: rerun on trial_kernel\n", idx.size());
-            }
-            e->last.trial_kernel_reruns += (int32_t)idx.size();
-            idx.insert(idx.end(), solo.begin(), solo.end());
-            if (idx.empty()) continue;
-        }
-        int attempt = 0;
-        while (!idx.empty()) {
-            int rc = run_group(e, cfgs, idx.data(), (int)idx.size(), results, ue_logs, attempt, 0, kernel_ms, upload_ms);
+            // (the clusters of a call may fill the CUs: 8 trials of 100 000 UEs run 52 ms on 8 x 32 workgroups — the lean kernel, one XCD each —
+            //  against 78 ms on 8 x 16, 16 trials 78 ms on 16 x 16 against 96 ms on 16 x 8: scripts/gpu_probe_cluster_sizes.py)
+            int rc = descend_ladder(e, cx, rest, cluster_size(e, cfgs, rest, resident, 32, true), trial);
             if (rc != PRACH_OK) return rc;
-            std::vector<int> again; // glibc trials whose draw-stream window ran out: rerun with a larger one
-            for (int k : idx)
-                if (results[k].status == PRACH_ERR_STREAM) again.push_back(k);
-            idx.swap(again);
-            if (++attempt > 6) return PRACH_ERR_STREAM;
-        }
+        } else trial = rest; // (engine option `legacy`: every trial on trial_kernel)
+        trial.insert(trial.end(), solo.begin(), solo.end());
+        trial.insert(trial.end(), sect_left.begin(), sect_left.end());
+        int rc = run_with_retries(e, cx, trial, 0, LaunchOpts{}); // (trial_kernel has no capacity to exceed and no peer to wait for)
+        if (rc != PRACH_OK) return rc;
     }
     uint64_t upd = 0;
     int worst = PRACH_OK;
@@ -1009,9 +1007,9 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
         else if (cfgs[k].rng_mode == PRACH_RNG_GLIBC && cfgs[k].variant != PRACH_VARIANT_NOMA_C) seen = std::max(seen, (double)results[k].draws / (double)cfgs[k].nUE);
     }
     if (seen > 0) e->draws_per_ue_seen = seen; // (sizes the stream windows of the next call: stream_budget)
-    e->last.kernel_ms = kernel_ms;
-    e->last.noma_host_ues = e->noma_flagged;
-    e->last.upload_ms = upload_ms;
+    e->last.kernel_ms = cx.kernel_ms;
+    e->last.noma_host_ues = cx.noma_flagged;
+    e->last.upload_ms = cx.upload_ms;
     e->last.updates = upd;
     e->last.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return worst;
@@ -1055,7 +1053,6 @@ int prach_engine_set(prach_engine *e, const char *key, int64_t value) {
     if (std::strcmp(key, "host_threads") == 0) { if (value < 0) return PRACH_ERR_ARG; e->opt_host_threads = value; return PRACH_OK; }
     if (std::strcmp(key, "lds_records") == 0) { e->opt_lds_records = value != 0; return PRACH_OK; }
     if (std::strcmp(key, "fast") == 0) { e->opt_fast = value != 0; return PRACH_OK; }
-    if (std::strcmp(key, "batch") == 0) { e->opt_batch = value != 0; return PRACH_OK; }
     if (std::strcmp(key, "vmm_fail_after") == 0) { if (value < 0) return PRACH_ERR_ARG; e->opt_vmm_fail_after = value; return PRACH_OK; }
     if (std::strcmp(key, "plain_arena") == 0) { if (e->arena_cap) return PRACH_ERR_ARG; e->opt_plain_arena = value != 0; return PRACH_OK; } // (before the first call only)
     if (std::strcmp(key, "noma_ambiguity_test") == 0) { e->opt_noma_ambiguity_test = value != 0; return PRACH_OK; }
@@ -1110,8 +1107,8 @@ static int activation_table_device_impl(prach_engine *e, const prach_cfg *cfg, i
     const int idx0 = 0;
     std::vector<ActTab> tabs(1, ActTab{A + opre, A + osec, A + ogain, A + olg, A + ond});
     std::vector<std::pair<int, int>> fl;
-    e->noma_flagged = 0;
-    { int rc = noma_device_activation(e, reinterpret_cast<const TrialDev *>(A), cfg, &idx0, 1, tabs, reinterpret_cast<unsigned *>(A + oflags), &fl); if (rc != PRACH_OK) return rc == NOMA_ACT_OVERFLOW_RC ? PRACH_ERR_INTERNAL : rc; }
+    int nflagged = 0;
+    { int rc = noma_device_activation(e, reinterpret_cast<const TrialDev *>(A), cfg, &idx0, 1, tabs, reinterpret_cast<unsigned *>(A + oflags), &fl, nflagged); if (rc != PRACH_OK) return rc == NOMA_ACT_OVERFLOW_RC ? PRACH_ERR_INTERNAL : rc; }
     HIPCHK(hipMemcpy(preamble0, A + opre, 4 * n, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(sector, A + osec, 4 * n, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(gain, A + ogain, 8 * n, hipMemcpyDeviceToHost));

@@ -6,7 +6,7 @@ sys.path.insert(0, ROOT)
 import __graft_entry__ as g
 m = g.load_package()
 eng = m.Engine(0)
-for kv in filter(None, os.environ.get("PRACH_ENG_OPTS", "").split(",")):  # e.g. PRACH_ENG_OPTS=batch_waves=16,batch=0
+for kv in filter(None, os.environ.get("PRACH_ENG_OPTS", "").split(",")):  # e.g. PRACH_ENG_OPTS=batch_waves=16,xcd_pack=0
     eng.set(kv.split("=")[0], int(kv.split("=")[1]))
 times = int(sys.argv[1]) if len(sys.argv) > 1 else 26
 variant = int(sys.argv[2]) if len(sys.argv) > 2 else 1

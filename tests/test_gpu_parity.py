@@ -428,6 +428,47 @@ def test_cluster_residency_is_explicit(pkg, ob, engine):
         engine.set("cluster", 0)
 
 
+def test_mem_budget_splits_a_call_exactly(pkg, engine):
+    """mem_budget_mb (test hook): a call whose arena would take more than the budget runs as several launches (halves of halves) — with the results and UE
+    logs of every trial byte for byte those of the same call in one launch.  300 sweep trials on the batch kernel, about 2 GB of arena in all."""
+    cfgs = [pkg.make_cfg(n, variant=v, rng_mode=pkg.RNG_PHILOX, seed=s) for s in range(25) for v in (0, 1) for n in (1000, 2000, 3000, 4000, 5000, 6000)]
+    res, logs = engine.run_trials(cfgs, want_logs=True)
+    whole = engine.timing()
+    eng = pkg.Engine(0)
+    try:
+        eng.set("mem_budget_mb", 512)
+        res2, logs2 = eng.run_trials(cfgs, want_logs=True)
+        split = eng.timing()
+    finally:
+        eng.close()
+    assert all(r.status == 0 for r in res)
+    assert split.launches >= 2 and split.launches > whole.launches, (split.launches, whole.launches)
+    assert [bytes(r) for r in res2] == [bytes(r) for r in res]
+    assert all(bytes(a) == bytes(b) for a, b in zip(logs2, logs))
+
+
+def test_calendar_cap_rerun_is_exact(pkg, ob, engine, capfd):
+    """calendar_cap (test hook): join lists of 64 entries on the batch kernel.  The overloaded trials of a small sweep fill one; the engine reruns exactly
+    those once with lists of nUE entries, says so once on stderr and counts them as fallback trials — the results and logs are the oracle's."""
+    cases = [(3000, {}), (8000, dict(nGrantUL=3)), (12000, dict(nGrantUL=2))]
+    cfgs = [pkg.make_cfg(n, variant=1, rng_mode=pkg.RNG_PHILOX, seed=s, **kw) for s in (0, 1) for n, kw in cases]
+    engine.set("calendar_cap", 64)
+    try:
+        capfd.readouterr()
+        res, logs = engine.run_trials(cfgs, want_logs=True)
+        tm = engine.timing()
+        err = capfd.readouterr().err
+    finally:
+        engine.set("calendar_cap", 0)
+    lines = [l for l in err.splitlines() if "filled a calendar list" in l]
+    assert len(lines) == 1, err[-2000:]
+    nfilled = int(lines[0].split("[prach] ")[1].split()[0])
+    assert 1 <= nfilled <= len(cfgs) and tm.fallback_trials == nfilled, (nfilled, tm.fallback_trials, err[-2000:])
+    for c, r, l in zip(cfgs, res, logs):
+        ores, oues = ob.run_trial(ob.make_cfg(c.nUE, variant=1, nGrantUL=c.nGrantUL), ob.Rng(ob.RNG_PHILOX, int(c.seed)))
+        assert_same(pkg, r, l, ores, oues, ("calendar_cap", c.nUE, c.nGrantUL, c.seed))
+
+
 def test_two_engines_share_one_device(pkg, ob):
     """Two engines (two host threads, two HIP streams) on ONE device, each launching 4 trials x 64 workgroups at the same
     time: together more workgroups than the device holds.  Members of a cluster are consecutive blocks, so whole clusters
@@ -965,6 +1006,22 @@ def test_gpu_sector_grants_on_the_batch_kernel(pkg, ob, engine):
     assert (slow_r.nSuccessUE, slow_r.sumTimer, slow_r.draws) == (res[0].nSuccessUE, res[0].sumTimer, res[0].draws)
     print(f"sector grants, nUE = 100 000, 12 grants per sector: batch_kernel {fast.kernel_ms:.1f} ms, trial_kernel {slow.kernel_ms:.1f} ms")
     assert slow.kernel_ms > 5 * fast.kernel_ms
+
+
+def test_sector_grants_stream_retry_stays_on_the_batch_kernel(pkg, ob, engine):
+    """A per-sector-grant trial in the reference's stream whose draw-stream window runs out on the batch kernel is rerun there with a larger window, like
+    every other trial of that kernel — not on trial_kernel, and not counted as a fallback.  (engine option stream_factor: 8 draws per UE at first.)"""
+    cfg = pkg.make_cfg(100000, variant=1, rng_mode=pkg.RNG_GLIBC, seed=12, flags=pkg.FLAG_SECTOR_GRANTS)
+    engine.set("stream_factor", 8)
+    try:
+        (res,), (logs,) = engine.run_trials([cfg], want_logs=True)
+        tm = engine.timing()
+    finally:
+        engine.set("stream_factor", 0)
+    assert tm.launches >= 2 and tm.rec_mode == 4, (tm.launches, tm.rec_mode)
+    assert tm.fallback_trials == 0 and tm.trial_kernel_reruns == 0, (tm.fallback_trials, tm.trial_kernel_reruns)
+    ores, oues = ob.run_trial(ob.make_cfg(100000, variant=1, sector_grants=1), ob.Rng(ob.RNG_GLIBC, 12))
+    assert_same(pkg, res, logs, ores, oues, "sector grants, stream retry")
 
 
 def test_dense_pass_option_agrees(pkg, ob, engine):
