@@ -1139,15 +1139,27 @@ def test_branch_free_event_body_equals_the_branched_form_on_the_device(tmp_path)
     assert p.returncode == 0 and " 0 differences" in p.stdout, p.stdout[-2000:]
 
 
+def _nobitop3_library():
+    """libprach_hip_nobitop3.so, built (`make NOBITOP3=1 lib`) when it is missing or older than a source file: never a stale cross-check."""
+    import glob
+    from conftest import ROOT, _stale
+    pkg_dir = os.path.join(ROOT, "5g-nr-randomaccess_amd")
+    csrc = os.path.join(pkg_dir, "csrc")
+    nb = os.path.join(pkg_dir, "libprach_hip_nobitop3.so")
+    srcs = glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.c")) + [os.path.join(ROOT, "include", "prach.h")]
+    if _stale(nb, srcs):
+        subprocess.check_call(["make", "-C", csrc, "lib", "NOBITOP3=1", "ARCH=gfx950"])
+    assert os.path.exists(nb)
+    return nb
+
+
 def test_library_without_bitop3_agrees():
     """ROCm 7.2 folded a tree of the batched kernel's mask algebra into a WRONG v_bitop3_b32 in an experimental kernel shape (LABNOTES, round 4).  The shipped
     shape is fenced (prach_ue_body.h: lopaque) and checked against the oracle elsewhere in this suite; here the same library built WITHOUT the instruction
     (libprach_hip_nobitop3.so, `make NOBITOP3=1 lib`) must return the same results: 100-trial sweeps of both programs on the batched kernel in both workgroup
     shapes — a difference means some kernel's results depend on how the compiler selected its boolean instructions."""
     from conftest import ROOT
-    nb = os.path.join(ROOT, "5g-nr-randomaccess_amd", "libprach_hip_nobitop3.so")
-    if not os.path.exists(nb):
-        pytest.skip("libprach_hip_nobitop3.so not built")
+    nb = _nobitop3_library()
 
     def digests(lib):
         out = []
@@ -1165,3 +1177,28 @@ def test_library_without_bitop3_agrees():
 
     a, b = digests(None), digests(nb)
     assert a == b and a[0] == a[1] and a[2] == a[3], (a, b)
+
+
+def test_kernel_matrix_with_and_without_bitop3(pkg):
+    """Every kernel with a compiler-chosen v_bitop3 truth table (tests/golden/bitop3_inventory.json), pinned by engine options and prach_timing
+    (tests/tools/kernel_matrix.py: rec_mode, cluster size, no fallback trial, no rerun on trial_kernel), at the parameter corners where mask algebra
+    goes wrong — maxMsg2TxCount = 0 with one UL grant and a one-subframe RAR window among them —, every trial against the oracle with the full bar;
+    once with the shipped library and once with libprach_hip_nobitop3.so, in two child processes.  Both clean, and the same digest row by row: a
+    difference only the shipped library shows points to the compiler's boolean instructions, one both show to the kernels' logic."""
+    from conftest import ROOT
+    nb = _nobitop3_library()
+    runner = os.path.join(ROOT, "tests", "tools", "gpu_kernel_matrix.py")
+
+    def run(lib):
+        env = dict(os.environ)
+        env.pop("PRACH_LIB", None)
+        if lib:
+            env["PRACH_LIB"] = lib
+        p = subprocess.run([sys.executable, runner], env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0 and " cases 0 bad" in p.stdout, (lib, p.stdout[-4000:], p.stderr[-2000:])
+        rows = {l.split()[1]: l.split("digest=")[1].split()[0] for l in p.stdout.split("\n") if l.startswith("row ")}
+        assert rows, p.stdout[-2000:]
+        return rows
+
+    a, b = run(None), run(nb)
+    assert a == b, {k: (a.get(k), b.get(k)) for k in set(a) | set(b) if a.get(k) != b.get(k)}
