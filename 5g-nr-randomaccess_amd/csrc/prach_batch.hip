@@ -35,6 +35,7 @@
 #include "prach_device.h"
 #include "prach_device_fn.h"
 #include "prach_ue_body.h"
+#include "prach_resolve.h"
 #include <limits.h>
 #include <type_traits>
 
@@ -86,7 +87,6 @@ template <int NWB> struct BCap {
 #endif
 };
 
-constexpr int EVB_CALLER = UEV_CALLER, EVB_RESETCAND = UEV_RESETCAND, EVB_RJOIN = UEV_RJOIN, EVB_LEAVER = 4;
 
 // (the event / candidate counts and the free-chunk pool exist twice, by subframe parity: a wavefront that is already in the next subframe's body uses the other one)
 enum { B_NSUCC = 0, B_COLL, B_TXOP, B_CONTF, B_NS, B_NRC, B_NRJ, B_OVF /* the chunk pool, a chunk table or a join list is full: the trial leaves */, B_NEV = 8 /* [2] */, B_NCAND = 10 /* [2] */,
@@ -663,7 +663,7 @@ __global__ __launch_bounds__(NWB * 64, NWB == 8 ? PRACH_B_W8_WAVES : 4) void bat
                     int b_ev = 0;
                     if (lane == 0) b_ev = atomicAdd(&scal[B_NEV + parity], __popcll(lm));
                     b_ev = __builtin_amdgcn_readfirstlane(b_ev);
-                    if ((lm >> lane) & 1ull) ev_set(b_ev + __popcll(lm & lanemask_lt(lane)), ci, EVB_LEAVER | (cp << 4));
+                    if ((lm >> lane) & 1ull) ev_set(b_ev + __popcll(lm & lanemask_lt(lane)), ci, EV_LEAVER | (cp << 4));
                 }
             }
             if (GLIBC) // every draw of this subframe has been read: the marks go (all of them: 2 x 16 bytes per thread)
@@ -692,21 +692,8 @@ __global__ __launch_bounds__(NWB * 64, NWB == 8 ? PRACH_B_W8_WAVES : 4) void bat
         if (tid < NPB) { histx[tid] = 0; mlocx[tid] = INT_MAX; BI(bl::ER)[(t & (HRING - 1)) * NPB + tid] = INT_MAX; } // (these ring rows are the subframe t + HRING from here on; ER's row t held the windows that ended before t)
         const int nsucc_tot = scal[B_NSUCC];
         // classify the events against the lowest DEFINITE caller of every bucket
-        for (int k = tid; k < N; k += TB) {
-            const int2 ev = ev_get(k);
-            const int type = ev.y & 7, p = (ev.y >> 4) & 0xff;
-            if (type == EVB_RESETCAND) {
-                // a call on its old bucket by a definite caller with a lower index bumps it: cannot re-join (99.7 % of them)
-                if (fcallA[(ev.y >> 12) & 0xff] < ev.x) ev_kill(k);
-                else { const int s = atomicAdd(&scal[B_NRC], 1); if (s < RCCAP) BI(bl::RCL)[s] = k; }
-            } else if (type == EVB_RJOIN) {
-                atomicAdd(&scal[B_NRJ], 1);
-            } else if (type == EVB_LEAVER) {
-                if (ev.x < fcallA[p]) atomicAdd(&BI(bl::NLV)[p], 1);
-            } else if (type == EVB_CALLER) {
-                if (ev.x == fcallA[p]) BI(bl::FIE)[p] = 1;
-            }
-        }
+        const ResolveTables RT{fcallA, BI(bl::NLV), BI(bl::FIE), BI(bl::RCL), BI(bl::SIDX), &scal[B_NRC], &scal[B_NRJ]}; // (prach_resolve.h)
+        for (int k = tid; k < N; k += TB) classify_event(RT, k, ev_get(k), ev_kill);
         BSTAMP(7); // classify
         if (N > 0) __syncthreads(); // S4 (N is uniform)
         BSTAMP(8);
@@ -715,40 +702,15 @@ __global__ __launch_bounds__(NWB * 64, NWB == 8 ? PRACH_B_W8_WAVES : 4) void bat
         const int nrc = scal[B_NRC];
         if (nrc > 0) { // rare: reset cycles that may re-join — decided strictly in index order by one wavefront, then recount
             if (nrc > RCCAP) { status = PRACH_ERR_INTERNAL; why = 2; time_exit = t; break; }
-            if (tid < 64) { // (first-caller table in registers, lane = bucket: prach_cluster.hip resolve_reset_candidates)
-                const int n = __builtin_amdgcn_readfirstlane(nrc);
-                int *const rcl = BI(bl::RCL), *const sidx = BI(bl::SIDX);
-                int f0 = lane < nP ? fcallA[lane] : INT_MAX;
-                for (int c = lane; c < n; c += 64) { // rank-sort the candidates by UE index into SIDX (free at this point)
-                    const int myidx = ev_get(rcl[c]).x;
-                    int rank = 0;
-                    for (int j = 0; j < n; j++) rank += ev_get(rcl[j]).x < myidx ? 1 : 0;
-                    sidx[rank] = rcl[c];
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                for (int base = 0; base < n; base += 64) {
-                    const int mm = min(64, n - base);
-                    int es = 0, cidx = 0, cinfo = 0;
-                    if (lane < mm) { es = sidx[base + lane]; const int2 e = ev_get(es); cidx = e.x; cinfo = e.y; }
-                    int cancelled = 0;
-                    for (int s_ = 0; s_ < mm; s_++) {
-                        const int idx = __builtin_amdgcn_readlane(cidx, s_), info = __builtin_amdgcn_readlane(cinfo, s_);
-                        const int p = (info >> 4) & 0xff, q = (info >> 12) & 0xff;
-                        if (__builtin_amdgcn_readlane(f0, q & 63) < idx) { if (lane == s_) cancelled = 1; } // bumped before its turn
-                        else if (idx < __builtin_amdgcn_readlane(f0, p & 63)) { if (lane == (p & 63)) f0 = idx; } // its call becomes the first on p
-                    }
-                    if (lane < mm && cancelled) ev_kill(es);
-                }
-                if (lane < nP) fcallA[lane] = f0;
+            if (tid < 64) { // (first-caller table in registers, lane = bucket)
+                resolve_reset_candidates<1>(RT, nrc, nP, ev_get, ev_kill);
             } else if (tid < 64 + NPB) { BI(bl::NLV)[tid - 64] = 0; BI(bl::FIE)[tid - 64] = 0; }
             __syncthreads();
             for (int k = tid; k < N; k += TB) {
                 const int2 e = ev_get(k);
                 const int type = e.y & 7, p = (e.y >> 4) & 0xff;
-                if (type == EVB_LEAVER) { if (e.x < fcallA[p]) atomicAdd(&BI(bl::NLV)[p], 1); }
-                else if ((type == EVB_CALLER || type == EVB_RESETCAND) && e.x == fcallA[p]) BI(bl::FIE)[p] = 1;
+                if (type == EV_LEAVER) { if (e.x < fcallA[p]) atomicAdd(&BI(bl::NLV)[p], 1); }
+                else if ((type == UEV_CALLER || type == UEV_RESETCAND) && e.x == fcallA[p]) BI(bl::FIE)[p] = 1;
             }
             __syncthreads();
         }
@@ -762,7 +724,7 @@ __global__ __launch_bounds__(NWB * 64, NWB == 8 ? PRACH_B_W8_WAVES : 4) void bat
                 if (k < N) {
                     const int2 e = ev_get(k);
                     const int type = e.y & 7;
-                    if (type == EVB_CALLER || type == EVB_RESETCAND) { caller = true; idx = e.x; p = (e.y >> 4) & 0xff; ispre = (e.y >> 3) & 1; }
+                    if (type == UEV_CALLER || type == UEV_RESETCAND) { caller = true; idx = e.x; p = (e.y >> 4) & 0xff; ispre = (e.y >> 3) & 1; }
                 } else {
                     p = k - N;
                     if (fcallA[p] != INT_MAX && !BI(bl::FIE)[p]) { caller = true; idx = fcallA[p]; ispre = 1; } // a matched UE calls first
@@ -775,11 +737,11 @@ __global__ __launch_bounds__(NWB * 64, NWB == 8 ? PRACH_B_W8_WAVES : 4) void bat
                     for (int j = 0; j < N; j++) {
                         const int2 ej = ev_get(j);
                         const int tj = ej.y & 7;
-                        if ((tj == EVB_CALLER || tj == EVB_RESETCAND) && ((ej.y >> 4) & 0xff) == p && ej.x < idx && ej.x > prev) prev = ej.x;
+                        if ((tj == UEV_CALLER || tj == UEV_RESETCAND) && ((ej.y >> 4) & 0xff) == p && ej.x < idx && ej.x > prev) prev = ej.x;
                     }
                     for (int j = 0; j < N; j++) {
                         const int2 ej = ev_get(j);
-                        if ((ej.y & 7) == EVB_RJOIN && ((ej.y >> 4) & 0xff) == p && ej.x < idx && ej.x > prev) rj++;
+                        if ((ej.y & 7) == UEV_RJOIN && ((ej.y >> 4) & 0xff) == p && ej.x < idx && ej.x > prev) rj++;
                     }
                 }
                 const int check = 1 + (first ? BI(bl::TOTAL)[p] - ispre - BI(bl::NLV)[p] : 0) + rj;
@@ -1071,14 +1033,9 @@ int batch_max_calendar_slots() { return CR; }
 hipError_t launch_batch_kernel(const TrialDev *params, int ntrials, int waves, bool glibc, hipStream_t stream) {
     if (glibc) waves = 16;
     const size_t lds = batch_kernel_lds_bytes(waves, glibc);
-    const void *fn = glibc ? reinterpret_cast<const void *>(&batch_kernel<16, true>)
-                           : waves == 8 ? reinterpret_cast<const void *>(&batch_kernel<8>) : reinterpret_cast<const void *>(&batch_kernel<16>);
-    hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (rc != hipSuccess) return rc;
-    if (glibc) hipLaunchKernelGGL((batch_kernel<16, true>), dim3(ntrials), dim3(1024), lds, stream, params);
-    else if (waves == 8) hipLaunchKernelGGL(batch_kernel<8>, dim3(ntrials), dim3(512), lds, stream, params);
-    else hipLaunchKernelGGL(batch_kernel<16>, dim3(ntrials), dim3(1024), lds, stream, params);
-    return hipGetLastError();
+    if (glibc) return launch_with_lds(batch_kernel<16, true>, ntrials, 1024, lds, stream, params);
+    if (waves == 8) return launch_with_lds(batch_kernel<8>, ntrials, 512, lds, stream, params);
+    return launch_with_lds(batch_kernel<16>, ntrials, 1024, lds, stream, params);
 }
 
 } // namespace prach

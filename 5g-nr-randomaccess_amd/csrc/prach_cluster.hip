@@ -33,6 +33,8 @@
 #include "prach_device.h"
 #include "prach_device_fn.h"
 #include "prach_ue_body.h"
+#include "prach_exchange.h"
+#include "prach_resolve.h"
 #include <limits.h>
 
 namespace prach {
@@ -55,11 +57,9 @@ namespace {
 #define FSTAMP(k) do { } while (0)
 #endif
 
-constexpr int EVC_CALLER = UEV_CALLER, EVC_RESETCAND = UEV_RESETCAND, EVC_RJOIN = UEV_RJOIN, EVC_LEAVER = 4;
 constexpr int EVCAPC = 4096; // gathered events per subframe held in LDS
 constexpr int SCAPC = 2048;  // singleton callers per subframe held in LDS
 constexpr int DEADW = 512;   // dead-group bitmap words (16384 local groups): one run of DEADW / NW words per wavefront, see dead_skip
-constexpr unsigned SPIN_LIMIT = 1u << 22;
 
 enum { C_NSUCC = 0, C_COLL, C_TXOP, C_CONTF, C_NS, C_NRC, C_NRJ, C_STATUS, C_NEV, C_NCAND, C_OVF, C_NSUCCTOT, C_NTOT,
        C_PTC, C_FC, C_SUMT = 16, C_ND = 18, C_NCROSS = 20, C_GTOT = 21, C_QN = 22, C_QEND = 23, C_VISITS = 24, C_EVENTS = 25, C_SX = 27 };
@@ -204,42 +204,9 @@ __device__ __forceinline__ CLds ccarve(char *smem, bool glibc, int lslots) {
     return L;
 }
 
-// shared words: every access is a device-scope relaxed atomic == global_load/store ... sc1
-__device__ __forceinline__ long long ld_sc1_64(const PRACH_G long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_sc1_64(PRACH_G long long *p, long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// granule store of a cluster: write-through, or — once the cluster has VERIFIED that all its workgroups run on one XCD (handshake in the
-// kernel prologue, as in prach_lcluster.hip) — resident in that XCD's L2, where the peers' sc1 loads find it an L2 round trip later
-__device__ __forceinline__ void st_gr(const bool same_xcd, PRACH_G long long *p, long long v) {
-    if (same_xcd) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 struct FastMods { FastMod nP, backoff, aT, five; };
 
-// Event info word (20 bits): type[2:0] ispre[3] bucket p[11:4] old bucket q[19:12].
-// Exchange granule: ONE naturally aligned 8-byte write-through store {20-bit value | tag[11:0]} {20-bit value | tag[15:12]}.
-// Every granule carries the subframe tag (t+1 <= 60001 fits 16 bits), so it validates itself: the consumer
-// re-reads until the tag matches — no drain, no flag, no fence (cdna_hip_programming.md G16, R2).
-constexpr unsigned GR_NONE = 0xFFFFFu;
-__device__ __forceinline__ long long mk_granule(unsigned lo20, unsigned hi20, unsigned tag) {
-    const unsigned w0 = (lo20 & 0xFFFFFu) | ((tag & 0xFFFu) << 20), w1 = (hi20 & 0xFFFFFu) | (((tag >> 12) & 0xFu) << 20);
-    return (long long)(((unsigned long long)w1 << 32) | w0);
-}
-__device__ __forceinline__ bool granule_ok(long long g, unsigned tag) {
-    const unsigned w0 = (unsigned)g, w1 = (unsigned)((unsigned long long)g >> 32);
-    return (w0 >> 20) == (tag & 0xFFFu) && ((w1 >> 20) & 0xFu) == ((tag >> 12) & 0xFu);
-}
-// bounded re-read of one granule until it carries `tag`
-__device__ __forceinline__ long long wait_granule(const PRACH_G long long *p, unsigned tag, int *status_word) {
-    long long g = ld_sc1_64(p);
-    unsigned spins = 0;
-    while (!granule_ok(g, tag)) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > SPIN_LIMIT) { *status_word = PRACH_ERR_TIMEOUT; break; } // peer not resident? the engine reruns the trial
-        g = ld_sc1_64(p);
-    }
-    return g;
-}
+// The granule itself: prach_exchange.h.
 
 // Where the hot records of a trial live:
 //   REC_G16  global memory, 16 bytes per UE (clusters whose owned UEs do not fit LDS; the glibc modes; the dense pass)
@@ -450,7 +417,7 @@ __device__ __forceinline__ void ue_step(const TrialG &P, const CLds &L, const CX
     // ---- bucket bookkeeping (workgroup-level LDS atomics) ----
     if (member_pre) atomicAdd(&L.hist[oldp], 1);
     if (u.pend == PEND_STAY) { if (__atomic_load_n(&L.mloc[oldp], __ATOMIC_RELAXED) > i) atomicMin(&L.mloc[oldp], i); }
-    if (evtype == EVC_CALLER) atomicMin(&L.mloc[evp], i);
+    if (evtype == UEV_CALLER) atomicMin(&L.mloc[evp], i);
     {
         const unsigned long long em = __ballot(evtype != 0);
         if (em) {
@@ -546,17 +513,6 @@ __device__ __forceinline__ void cluster_pass(const TrialG &P, const CLds &L, con
 // runs ue_step on the queued UEs 64 at a time, all lanes busy.  ue_step never looks at a lane's neighbours in MODE 0,
 // so the result is the same whichever wavefront a UE lands in.
 // ---------------------------------------------------------------------------------------------
-// Is a UE whose deferred outcome is none / "matched, stays" / "called" (and not granted) in the light case of phase A at
-// subframe t: contending with a RAR window that stays open?  A PEND_STAY record may be `age` subframes old (written at
-// subframe r.x, not touched since): rarWindow has grown by age.  Shared by phase A and by the grant fix-up of the pipeline.
-__device__ __forceinline__ bool light_case(const unsigned pk, const int rx, const int rz, const int t, const unsigned rarlim) {
-    const unsigned pg = pk >> PK_PEND_SHIFT;
-    const bool contend = (pk & 3u) == (unsigned)ACT_M1 && (pk & (0xffu << PK_PRE_SHIFT)) != 0u && rz <= t;
-    const int age = pg == (unsigned)PEND_STAY ? t - 1 - rx : 0;
-    const unsigned rarnow = (pk & (0xffu << PK_RAR_SHIFT)) + ((unsigned)age << PK_RAR_SHIFT);
-    return pg < 3u && contend && rarnow < rarlim;
-}
-
 // Phase A of the compacted pass.  SPEC: for the NEXT subframe, while the exchange of the current one is in flight (see
 // the kernel).
 template <bool SPEC, class CX, class HOOK>
@@ -733,77 +689,6 @@ __device__ __forceinline__ void compact_phase_b(const TrialG &P, const CLds &L, 
     }
 }
 
-
-// One gathered event against the lowest DEFINITE caller of every bucket (complete after round 1).
-__device__ __forceinline__ void classify_event(const CLds &L, int *fcallA, const int k, const int2 ev) {
-    const int type = ev.y & 7, p = (ev.y >> 4) & 0xff;
-    if (type == EVC_RESETCAND) {
-        // a call on its old bucket by a definite caller with a lower index bumps it: cannot re-join (99.7 % of
-        // them); only the survivors need the index-ordered treatment
-        if (fcallA[(ev.y >> 12) & 0xff] < ev.x) L.gev[k].y = 0;
-        else { const int s = atomicAdd(&L.scal[C_NRC], 1); if (s < RCCAP) L.rclist[s] = k; }
-    } else if (type == EVC_RJOIN) {
-        atomicAdd(&L.scal[C_NRJ], 1);
-    } else if (type == EVC_LEAVER) {
-        if (ev.x < fcallA[p]) atomicAdd(&L.nlv[p], 1);
-    } else if (type == EVC_CALLER) {
-        if (ev.x == fcallA[p]) L.fie[p] = 1;
-    }
-}
-
-// Reset-cycle candidates (Beta.c:250-281 with tmp == 0 on a subframe = 1 mod accessTime): candidate i
-// re-joins (and calls on its NEW preamble) iff nobody called on its OLD preamble before it, and a
-// re-join is itself a call that later candidates must see.  Inherently sequential in index order,
-// but tiny: ONE wavefront keeps the per-bucket first-caller table in registers (lane = bucket, up to
-// 4 x 64 buckets) and walks the index-sorted candidates with v_readlane — no LDS round trip per step.
-__device__ __forceinline__ int fc_get(int f0, int f1, int f2, int f3, int q) {
-    const int l = q & 63;
-    switch (q >> 6) {
-    case 0: return __builtin_amdgcn_readlane(f0, l);
-    case 1: return __builtin_amdgcn_readlane(f1, l);
-    case 2: return __builtin_amdgcn_readlane(f2, l);
-    default: return __builtin_amdgcn_readlane(f3, l);
-    }
-}
-__device__ __forceinline__ void resolve_reset_candidates(const CLds &L, int *fcall, const int nrc_in, const int nP) {
-    const int lane = threadIdx.x & 63;
-    const int n = __builtin_amdgcn_readfirstlane(nrc_in);
-    int f0 = lane < nP ? fcall[lane] : INT_MAX, f1 = lane + 64 < nP ? fcall[lane + 64] : INT_MAX,
-        f2 = lane + 128 < nP ? fcall[lane + 128] : INT_MAX, f3 = lane + 192 < nP ? fcall[lane + 192] : INT_MAX;
-    // rank-sort the candidate list by UE index into L.sidx (free at this point of the subframe)
-    for (int c = lane; c < n; c += 64) {
-        const int myidx = L.gev[L.rclist[c]].x;
-        int rank = 0;
-        for (int j = 0; j < n; j++) rank += L.gev[L.rclist[j]].x < myidx ? 1 : 0;
-        L.sidx[rank] = L.rclist[c];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    for (int base = 0; base < n; base += 64) {
-        const int m = min(64, n - base);
-        int slot = 0, cidx = 0, cinfo = 0;
-        if (lane < m) { slot = L.sidx[base + lane]; const int2 e = L.gev[slot]; cidx = e.x; cinfo = e.y; }
-        int cancelled = 0;
-        for (int s_ = 0; s_ < m; s_++) {
-            const int idx = __builtin_amdgcn_readlane(cidx, s_), info = __builtin_amdgcn_readlane(cinfo, s_);
-            const int p = (info >> 4) & 0xff, q = (info >> 12) & 0xff;
-            if (fc_get(f0, f1, f2, f3, q) < idx) { // bumped before its turn: does not re-join
-                if (lane == s_) cancelled = 1;
-            } else if (idx < fc_get(f0, f1, f2, f3, p)) { // its call becomes the first one on p
-                if (lane == (p & 63)) {
-                    switch (p >> 6) { case 0: f0 = idx; break; case 1: f1 = idx; break; case 2: f2 = idx; break; default: f3 = idx; break; }
-                }
-            }
-        }
-        if (lane < m && cancelled) L.gev[slot].y = 0;
-    }
-    if (lane < nP) fcall[lane] = f0;
-    if (lane + 64 < nP) fcall[lane + 64] = f1;
-    if (lane + 128 < nP) fcall[lane + 128] = f2;
-    if (lane + 192 < nP) fcall[lane + 192] = f3;
-}
-
 } // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -815,14 +700,8 @@ __global__ __launch_bounds__(WG_THREADS, 4) void cluster_kernel(const TrialDev *
     // compile-time 1 and every exchange / mailbox / pipeline path of this kernel is dead code the compiler drops (half the code, fewer
     // live scalars in the pass)
     const int G = REC == REC_H8 ? 1 : Garg;
-    // the workgroups of a cluster are CONSECUTIVE blocks: in-order dispatch completes whole clusters even when not every
-    // block of the grid is resident at once (the engine keeps G x trials within the occupancy query's answer anyway)
-    int T = blockIdx.x / G, b = blockIdx.x % G;
-    if (REC != REC_H8 && xpack) { // XCD-packed launch (prach_lcluster.hip): a cluster = the blocks of equal blockIdx % 8 of a chunk of 8 G blocks
-        const int chunk = blockIdx.x / (8 * G), within = blockIdx.x % (8 * G);
-        T = chunk * 8 + (within & 7); b = within >> 3;
-        if (T >= ntrials) return;
-    }
+    int T, b; // (prach_exchange.h: consecutive blocks, or XCD-packed)
+    if (!cluster_block(G, REC != REC_H8 ? xpack : 0, ntrials, T, b)) return;
     const TrialG P(params[T]);
     const CLds L = ccarve<LO>(smem, GLIBC, REC == REC_L16 ? lslots : 0);
     const int tid = threadIdx.x;
@@ -861,22 +740,7 @@ __global__ __launch_bounds__(WG_THREADS, 4) void cluster_kernel(const TrialDev *
     for (int k = tid; k < DEADW; k += WG_THREADS) L.dead[k] = 0;
     if (GLIBC) for (int k = tid; k < GSCAP; k += WG_THREADS) { L.gsum[k] = 0; L.gpre[k] = 0; }
     __syncthreads();
-    if (REC != REC_H8 && xpack && G > 1 && G <= 64) {
-        // same-XCD handshake (prach_lcluster.hip): every workgroup publishes the XCD it runs on (write-through granule, tag 0xFFFF, header of
-        // its parity-1 mailbox: first used by subframe 1, which nobody reaches before every peer is past this point) and reads all G
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        xcc &= 0xfu;
-        if (tid == 0) st_sc1_64(gr_of(C, 1, b), mk_granule(xcc, 0u, 0xFFFFu));
-        if (tid < 64) {
-            bool same = true;
-            if (tid < G) same = ((unsigned)wait_granule(gr_of(C, 1, tid), 0xFFFFu, &L.scal[C_STATUS]) & 0xFFFFFu) == xcc;
-            const bool all = __ballot(!same) == 0ull;
-            if (tid == 0) L.scal[C_SX] = all ? 1 : 0;
-        }
-        __syncthreads();
-        C.sx = L.scal[C_SX] != 0 && L.scal[C_STATUS] == PRACH_OK;
-    }
+    if (REC != REC_H8 && xpack && G > 1 && G <= 64) C.sx = same_xcd_handshake(gr_of(C, 1, 0), (size_t)(C.mbstride >> 1), b, G, &L.scal[C_STATUS], &L.scal[C_SX]); // (mbstride counts ints and is a multiple of 4 — mbox_bytes, prach_engine.hip — so mbstride >> 1 granules is exact)
 
     int activeCheck = 0, grantCheck = 0, tlast = -1, time_exit = P.stop;
     unsigned long long steps = 0;
@@ -1018,7 +882,7 @@ __global__ __launch_bounds__(WG_THREADS, 4) void cluster_kernel(const TrialDev *
             else c = C.cand[k];
             if (c.x < min(Lc.mloc[c.y], Lc.mloc_stay[c.y])) {
                 const int slot = atomicAdd(&L.scal[C_NEV], 1);
-                const int info = EVC_LEAVER | (c.y << 4);
+                const int info = EV_LEAVER | (c.y << 4);
                 if (G == 1) { if (slot < EVCAPC) L.gev[slot] = make_int2(c.x, info); }
                 else if (slot < C.evw) st_gr(C.sx, mbev + slot, mk_granule((unsigned)c.x, (unsigned)info, tag));
             }
@@ -1032,6 +896,9 @@ __global__ __launch_bounds__(WG_THREADS, 4) void cluster_kernel(const TrialDev *
         __syncthreads(); // S2
         FSTAMP(4); // S2
         int N;
+        const ResolveTables RT{fcallA, L.nlv, L.fie, L.rclist, L.sidx, &L.scal[C_NRC], &L.scal[C_NRJ]}; // (prach_resolve.h)
+        auto ev_get = [&](const int k) __attribute__((always_inline)) { return L.gev[k]; };
+        auto ev_kill = [&](const int k) __attribute__((always_inline)) { L.gev[k].y = 0; };
         if (G == 1) {
             // one workgroup owns the whole trial: its histogram / lowest callers ARE the totals; events are in LDS
             const int nevraw = L.scal[C_NEV];
@@ -1045,7 +912,7 @@ __global__ __launch_bounds__(WG_THREADS, 4) void cluster_kernel(const TrialDev *
             if (tid == 0) { L.scal[C_NEV] = 0; L.scal[C_NCAND] = 0; L.scal[C_NSUCCTOT] = L.scal[C_NSUCC]; }
             STAMP(1); STAMP(2);
             // classify the events: reset-cycle candidates, Msg3 re-entries, early leavers below / callers at the first call
-            for (int k = tid; k < N; k += WG_THREADS) classify_event(L, fcallA, k, L.gev[k]);
+            for (int k = tid; k < N; k += WG_THREADS) classify_event(RT, k, L.gev[k], ev_kill);
         } else {
             // publish: per bucket {histogram, lowest caller}, header {#events, overflow, #successes}: self-validating granules
             for (int k = tid; k < nP; k += WG_THREADS) {
@@ -1127,7 +994,7 @@ __global__ __launch_bounds__(WG_THREADS, 4) void cluster_kernel(const TrialDev *
                 const long long e = wait_granule(gr_of(C, parity, lo) + 1 + nP + (k - L.evoff[lo]), tag, &L.scal[C_STATUS]);
                 const int2 ev = make_int2((int)((unsigned)e & 0xFFFFFu), (int)((unsigned)((unsigned long long)e >> 32) & 0xFFFFFu));
                 L.gev[k] = ev;
-                classify_event(L, fcallA, k, ev);
+                classify_event(RT, k, ev, ev_kill);
             }
         }
         FSTAMP(9); // round 2
@@ -1139,14 +1006,14 @@ __global__ __launch_bounds__(WG_THREADS, 4) void cluster_kernel(const TrialDev *
         const int nrc = L.scal[C_NRC];
         if (nrc > 0) { // rare: reset cycles that may re-join — decided strictly in index order, then recount
             if (nrc > RCCAP) { status = PRACH_ERR_INTERNAL; time_exit = t; break; }
-            if (tid < 64) resolve_reset_candidates(L, fcallA, nrc, nP);
+            if (tid < 64) resolve_reset_candidates<4>(RT, nrc, nP, ev_get, ev_kill);
             for (int k = 64 + tid; k < 64 + nP; k += WG_THREADS) { L.nlv[k - 64] = 0; L.fie[k - 64] = 0; }
             __syncthreads();
             for (int k = tid; k < N; k += WG_THREADS) {
                 const int2 e = L.gev[k];
                 const int type = e.y & 7, p = (e.y >> 4) & 0xff;
-                if (type == EVC_LEAVER) { if (e.x < fcallA[p]) atomicAdd(&L.nlv[p], 1); }
-                else if ((type == EVC_CALLER || type == EVC_RESETCAND) && e.x == fcallA[p]) L.fie[p] = 1;
+                if (type == EV_LEAVER) { if (e.x < fcallA[p]) atomicAdd(&L.nlv[p], 1); }
+                else if ((type == UEV_CALLER || type == UEV_RESETCAND) && e.x == fcallA[p]) L.fie[p] = 1;
             }
             __syncthreads();
         }
@@ -1163,7 +1030,7 @@ __global__ __launch_bounds__(WG_THREADS, 4) void cluster_kernel(const TrialDev *
             if (k < N) {
                 const int2 e = L.gev[k];
                 const int type = e.y & 7;
-                if (type == EVC_CALLER || type == EVC_RESETCAND) { caller = true; idx = e.x; p = (e.y >> 4) & 0xff; ispre = (e.y >> 3) & 1; }
+                if (type == UEV_CALLER || type == UEV_RESETCAND) { caller = true; idx = e.x; p = (e.y >> 4) & 0xff; ispre = (e.y >> 3) & 1; }
             } else {
                 p = k - N;
                 if (fcallA[p] != INT_MAX && !L.fie[p]) { caller = true; idx = fcallA[p]; ispre = 1; } // a STAY pre-member calls first
@@ -1176,11 +1043,11 @@ __global__ __launch_bounds__(WG_THREADS, 4) void cluster_kernel(const TrialDev *
                 for (int j = 0; j < N; j++) {
                     const int2 ej = L.gev[j];
                     const int tj = ej.y & 7;
-                    if ((tj == EVC_CALLER || tj == EVC_RESETCAND) && ((ej.y >> 4) & 0xff) == p && ej.x < idx && ej.x > prev) prev = ej.x;
+                    if ((tj == UEV_CALLER || tj == UEV_RESETCAND) && ((ej.y >> 4) & 0xff) == p && ej.x < idx && ej.x > prev) prev = ej.x;
                 }
                 for (int j = 0; j < N; j++) {
                     const int2 ej = L.gev[j];
-                    if ((ej.y & 7) == EVC_RJOIN && ((ej.y >> 4) & 0xff) == p && ej.x < idx && ej.x > prev) rj++;
+                    if ((ej.y & 7) == UEV_RJOIN && ((ej.y >> 4) & 0xff) == p && ej.x < idx && ej.x > prev) rj++;
                 }
             }
             const int check = 1 + (first ? L.total[p] - ispre - L.nlv[p] : 0) + rj;
@@ -1357,12 +1224,9 @@ hipError_t launch_cluster_kernel(const TrialDev *params, int ntrials, int G, int
     if (rec_mode == REC_H8 && rng_mode != PRACH_RNG_GLIBC) rec_mode = REC_G16;
     const size_t lds = cluster_kernel_lds_bytes(maxP, rng_mode == PRACH_RNG_GLIBC, lslots);
     const cluster_kernel_t fn = pick_cluster_kernel(rng_mode, rec_mode);
-    hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (rc != hipSuccess) return rc;
     if (rec_mode == REC_H8 || G <= 1) xpack = 0;
     const int grid = xpack ? ((ntrials + 7) / 8) * 8 * G : ntrials * G;
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(WG_THREADS), lds, stream, params, G, lslots, xpack, ntrials);
-    return hipGetLastError();
+    return launch_with_lds(fn, grid, WG_THREADS, lds, stream, params, G, lslots, xpack, ntrials);
 }
 
 // workgroups of this kernel (with its dynamic LDS) the runtime admits per CU: what a cooperative launch would be checked against
@@ -1371,10 +1235,7 @@ int cluster_kernel_blocks_per_cu(int maxP, int rng_mode, int rec_mode, int lslot
     if (rec_mode == REC_H8 && rng_mode != PRACH_RNG_GLIBC) rec_mode = REC_G16;
     const size_t lds = cluster_kernel_lds_bytes(maxP, rng_mode == PRACH_RNG_GLIBC, lslots);
     const cluster_kernel_t fn = pick_cluster_kernel(rng_mode, rec_mode);
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(fn), WG_THREADS, lds) != hipSuccess || nb < 1) return 1;
-    return nb;
+    return kernel_blocks_per_cu(fn, WG_THREADS, lds);
 }
 
 } // namespace prach

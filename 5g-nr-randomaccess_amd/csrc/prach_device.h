@@ -99,6 +99,23 @@ constexpr int EVCAP = 1024;         // events staged in LDS (more: resolved from
 constexpr int SCAP = 1024;          // singleton callers staged in LDS
 constexpr int RCCAP = 256;          // reset-cycle re-join candidates per subframe
 
+// host side, every kernel with dynamic LDS: raise the kernel's dynamic-LDS ceiling to `lds` and launch it; and the workgroups of the kernel
+// (threads, that much dynamic LDS) the runtime admits per CU — at least 1, also when the query fails
+template <class... KA, class... A>
+inline hipError_t launch_with_lds(void (*fn)(KA...), int grid, int threads, size_t lds, hipStream_t stream, A... args) {
+    const hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (rc != hipSuccess) return rc;
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds, stream, args...);
+    return hipGetLastError();
+}
+template <class... KA>
+inline int kernel_blocks_per_cu(void (*fn)(KA...), int threads, size_t lds) {
+    int nb = 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(fn), threads, lds) != hipSuccess || nb < 1) return 1;
+    return nb;
+}
+
 size_t trial_kernel_lds_bytes(int nP);
 hipError_t launch_trial_kernel(const TrialDev *params, int ntrials, int rng_mode, int maxP, hipStream_t stream);
 size_t cluster_kernel_lds_bytes(int nP, bool glibc, int lslots);

@@ -231,6 +231,16 @@ __device__ __forceinline__ PassMasks pass_masks(const unsigned pk, const int rx,
     }
     return PassMasks{mLight, mQuiet, mDone, mTrig};
 }
+// The same `light` test for ONE record (no SPEC, no arrival front): is a UE whose deferred outcome is none / "matched, stays" / "called"
+// (and not granted) in the light case of phase A at subframe t: contending with a RAR window that stays open?  A PEND_STAY record may be
+// `age` subframes old (written at subframe rx, not touched since): rarWindow has grown by age.  Used by the grant fix-up of the pipeline.
+__device__ __forceinline__ bool light_case(const unsigned pk, const int rx, const int rz, const int t, const unsigned rarlim) {
+    const unsigned pg = pk >> PK_PEND_SHIFT;
+    const bool contend = (pk & 3u) == (unsigned)ACT_M1 && (pk & (0xffu << PK_PRE_SHIFT)) != 0u && rz <= t;
+    const int age = pg == (unsigned)PEND_STAY ? t - 1 - rx : 0;
+    const unsigned rarnow = (pk & (0xffu << PK_RAR_SHIFT)) + ((unsigned)age << PK_RAR_SHIFT);
+    return pg < 3u && contend && rarnow < rarlim;
+}
 
 template <class T> __device__ __forceinline__ void gadd(PRACH_G T *p, const T v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 template <class T> __device__ __forceinline__ void gmin(PRACH_G T *p, const T v) { __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

@@ -513,17 +513,7 @@ __global__ __launch_bounds__(WG_THREADS) void trial_kernel(const TrialDev *__res
 
 hipError_t launch_trial_kernel(const TrialDev *params, int ntrials, int rng_mode, int maxP, hipStream_t stream) {
     const size_t lds = trial_kernel_lds_bytes(maxP);
-    hipError_t rc;
-    if (rng_mode == PRACH_RNG_GLIBC) {
-        rc = hipFuncSetAttribute(reinterpret_cast<const void *>(&trial_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (rc != hipSuccess) return rc;
-        hipLaunchKernelGGL(trial_kernel<true>, dim3(ntrials), dim3(WG_THREADS), lds, stream, params);
-    } else {
-        rc = hipFuncSetAttribute(reinterpret_cast<const void *>(&trial_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (rc != hipSuccess) return rc;
-        hipLaunchKernelGGL(trial_kernel<false>, dim3(ntrials), dim3(WG_THREADS), lds, stream, params);
-    }
-    return hipGetLastError();
+    return launch_with_lds(rng_mode == PRACH_RNG_GLIBC ? trial_kernel<true> : trial_kernel<false>, ntrials, WG_THREADS, lds, stream, params);
 }
 
 } // namespace prach

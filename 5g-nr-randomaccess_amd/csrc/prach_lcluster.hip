@@ -27,6 +27,8 @@
 #include "prach_device.h"
 #include "prach_device_fn.h"
 #include "prach_ue_body.h"
+#include "prach_exchange.h"
+#include "prach_resolve.h"
 #include <limits.h>
 
 namespace prach {
@@ -65,8 +67,6 @@ constexpr int LGB = 1024;    // grant selection bins
 constexpr int LEPF = 32;     // event granules of every mailbox fetched together with the bucket granules (more: a second round)
 constexpr int LRQ = 1024;    // UEs per subframe whose next two Philox draws are recomputed ahead (more: drawn in place)
 constexpr unsigned ND_READY = 0x80000000u; // lnd[slot] bit 31: ldraw[slot] holds draws nd, nd + 1 of this UE
-constexpr unsigned LSPIN = 1u << 22;
-constexpr int EVL_CALLER = UEV_CALLER, EVL_RESETCAND = UEV_RESETCAND, EVL_RJOIN = UEV_RJOIN, EVL_LEAVER = 4; // (= prach_cluster.hip's EVC_*)
 
 // scalars in LDS
 enum { S_NSUCC = 0, S_COLL, S_TXOP, S_CONTF, S_NS, S_NRC, S_NRJ, S_NEV = 8, S_NCAND /* = S_NEV + 1: read as a pair; both [2] by subframe parity (+ 2): slots 8..11 */, S_PTC = 13, S_FC, S_SUMT = 16,
@@ -106,38 +106,6 @@ static_assert(SIDX % 16 == 0 && TAIL % 16 == 0 && LCAND % 8 == 0, "alignment");
 #define LU(off) (reinterpret_cast<unsigned *>(smem + (off)))
 #define LI2(off) (reinterpret_cast<int2 *>(smem + (off)))
 
-// ---- exchange granules (as in prach_cluster.hip): ONE naturally aligned 8-byte write-through store {20-bit value | tag[11:0]}
-// {20-bit value | tag[15:12]}; the consumer re-reads until the tag (subframe + 1) matches: no flag, no fence (guide G16 / R2)
-constexpr unsigned GRL_NONE = 0xFFFFFu;
-__device__ __forceinline__ long long lmk(unsigned lo20, unsigned hi20, unsigned tag) {
-    const unsigned w0 = (lo20 & 0xFFFFFu) | ((tag & 0xFFFu) << 20), w1 = (hi20 & 0xFFFFFu) | (((tag >> 12) & 0xFu) << 20);
-    return (long long)(((unsigned long long)w1 << 32) | w0);
-}
-__device__ __forceinline__ bool lok(long long g, unsigned tag) {
-    const unsigned w0 = (unsigned)g, w1 = (unsigned)((unsigned long long)g >> 32);
-    return (w0 >> 20) == (tag & 0xFFFu) && ((w1 >> 20) & 0xFu) == ((tag >> 12) & 0xFu);
-}
-__device__ __forceinline__ long long lld(const PRACH_G long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void lst(PRACH_G long long *p, long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// A cluster whose workgroups have VERIFIED (handshake before the step loop) that they all run on one XCD shares that XCD's L2: its
-// granule stores may then stay in L2 (workgroup-scope store: no write-through to the fabric), where the peers' `sc1` loads — which
-// bypass only the per-CU L1 — find them after an L2 round trip instead of a fabric one (guide: `sc1` stores DROP the line from the
-// XCD's L2, plain / `sc0` stores KEEP it).  Any other placement keeps the write-through stores.
-__device__ __forceinline__ void lstx(const bool same_xcd, PRACH_G long long *p, long long v) {
-    if (same_xcd) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ long long lwait(const PRACH_G long long *p, unsigned tag, char *smem) {
-    long long g = lld(p);
-    unsigned spins = 0;
-    while (!lok(g, tag)) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > LSPIN) { LI(lo::SCAL)[S_STATUS] = PRACH_ERR_TIMEOUT; break; } // peer not resident? the engine reruns the trial
-        g = lld(p);
-    }
-    return g;
-}
-
 // per-trial constants of the step loop (wave-uniform)
 struct LK {
     int nUE, nP, aT, maxRar, maxMsg2, variant, b, G;
@@ -148,15 +116,6 @@ struct LK {
 };
 
 __device__ __forceinline__ int l_idx_of(const LK &K, const int slot) { return (K.b + K.G * (slot >> 6)) * 64 + (slot & 63); }
-
-// contending with a RAR window that stays open (prach_cluster.hip light_case)
-__device__ __forceinline__ bool l_light(const unsigned pk, const int rx, const int rz, const int t, const unsigned rarlim) {
-    const unsigned pg = pk >> PK_PEND_SHIFT;
-    const bool contend = (pk & 3u) == (unsigned)ACT_M1 && (pk & (0xffu << PK_PRE_SHIFT)) != 0u && rz <= t;
-    const int age = pg == (unsigned)PEND_STAY ? t - 1 - rx : 0;
-    const unsigned rarnow = (pk & (0xffu << PK_RAR_SHIFT)) + ((unsigned)age << PK_RAR_SHIFT);
-    return pg < 3u && contend && rarnow < rarlim;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The full per-UE body for one queued UE per lane (prach_cluster.hip ue_step<0>: deferred outcome of subframe t-1, activation,
@@ -234,7 +193,7 @@ __device__ __forceinline__ void l_step(char *smem, const LK &K, int4 *lrec, unsi
     // ---- bucket bookkeeping (workgroup-level LDS atomics) ----
     if (member_pre) atomicAdd(&hist[oldp], 1);
     if (u.pend == PEND_STAY) { if (__atomic_load_n(&mloc[oldp], __ATOMIC_RELAXED) > i) atomicMin(&mloc[oldp], i); }
-    if (evtype == EVL_CALLER) atomicMin(&mloc[evp], i);
+    if (evtype == UEV_CALLER) atomicMin(&mloc[evp], i);
     {
         // special events -> this workgroup's mailbox, early-leaver candidates and refills -> their lists: the three list positions are
         // taken by lane 0 with three returning LDS atomics issued back to back — ONE wait instead of three dependent round trips
@@ -250,7 +209,7 @@ __device__ __forceinline__ void l_step(char *smem, const LK &K, int4 *lrec, unsi
             if (evtype != 0) {
                 const int es = b_ev + __popcll(em & lanemask_lt(lane));
                 const int info = ue_event_info(o);
-                if (es < CLUSTER_EVW) lstx(K.sx, mbev + es, lmk((unsigned)i, (unsigned)info, tag));
+                if (es < CLUSTER_EVW) st_gr(K.sx, mbev + es, mk_granule((unsigned)i, (unsigned)info, tag));
             }
             if (eclass) {
                 const int cs = b_cd + __popcll(cm & lanemask_lt(lane));
@@ -268,59 +227,6 @@ __device__ __forceinline__ void l_step(char *smem, const LK &K, int4 *lrec, unsi
     if (dirty) lrec[slot] = pack(u);
 }
 
-// One gathered event against the lowest DEFINITE caller of every bucket (complete after round 1).
-__device__ __forceinline__ void l_classify(char *smem, const int fa, const int k, const int2 ev) {
-    const int *const fcallA = LI(lo::FCALL + fa);
-    const int type = ev.y & 7, p = (ev.y >> 4) & 0xff;
-    if (type == EVL_RESETCAND) {
-        if (fcallA[(ev.y >> 12) & 0xff] < ev.x) LI2(lo::GEV)[k].y = 0; // bumped on its old bucket before its turn: cannot re-join
-        else { const int s = atomicAdd(&LI(lo::SCAL)[S_NRC], 1); if (s < RCCAP) LI(lo::RCL)[s] = k; }
-    } else if (type == EVL_RJOIN) {
-        atomicAdd(&LI(lo::SCAL)[S_NRJ], 1);
-    } else if (type == EVL_LEAVER) {
-        if (ev.x < fcallA[p]) atomicAdd(&LI(lo::NLV + fa)[p], 1);
-    } else if (type == EVL_CALLER) {
-        if (ev.x == fcallA[p]) LI(lo::FIE + fa)[p] = 1;
-    }
-}
-
-// Reset-cycle re-join candidates, strictly in index order, by ONE wavefront with the first-caller table in registers
-// (lane = bucket; nPreamble <= 64).  prach_cluster.hip resolve_reset_candidates.
-__device__ __forceinline__ void l_resolve_reset_candidates(char *smem, const int fa, const int nrc_in, const int nP) {
-    const int lane = threadIdx.x & 63;
-    const int n = __builtin_amdgcn_readfirstlane(nrc_in);
-    int *const fcall = LI(lo::FCALL + fa);
-    int *const rcl = LI(lo::RCL), *const sidx = LI(lo::SIDX);
-    int2 *const gev = LI2(lo::GEV);
-    int f0 = lane < nP ? fcall[lane] : INT_MAX;
-    for (int c = lane; c < n; c += 64) { // rank-sort the candidate list by UE index into SIDX (free at this point of the subframe)
-        const int myidx = gev[rcl[c]].x;
-        int rank = 0;
-        for (int j = 0; j < n; j++) rank += gev[rcl[j]].x < myidx ? 1 : 0;
-        sidx[rank] = rcl[c];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    for (int base = 0; base < n; base += 64) {
-        const int m = min(64, n - base);
-        int es = 0, cidx = 0, cinfo = 0;
-        if (lane < m) { es = sidx[base + lane]; const int2 e = gev[es]; cidx = e.x; cinfo = e.y; }
-        int cancelled = 0;
-        for (int s_ = 0; s_ < m; s_++) {
-            const int idx = __builtin_amdgcn_readlane(cidx, s_), info = __builtin_amdgcn_readlane(cinfo, s_);
-            const int p = (info >> 4) & 0xff, q = (info >> 12) & 0xff;
-            if (__builtin_amdgcn_readlane(f0, q & 63) < idx) { // bumped before its turn: does not re-join
-                if (lane == s_) cancelled = 1;
-            } else if (idx < __builtin_amdgcn_readlane(f0, p & 63)) { // its call becomes the first one on p
-                if (lane == (p & 63)) f0 = idx;
-            }
-        }
-        if (lane < m && cancelled) gev[es].y = 0;
-    }
-    if (lane < nP) fcall[lane] = f0;
-}
-
 } // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -328,15 +234,8 @@ __device__ __forceinline__ void l_resolve_reset_candidates(char *smem, const int
 template <bool GLIBC>
 __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__restrict__ params, const int G, const int lslots, const int xpack, const int ntrials, const int gcap) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    int T = blockIdx.x / G, b = blockIdx.x % G; // a cluster = consecutive blocks (in-order dispatch completes whole clusters)
-    if (xpack) {
-        // XCD-packed launch: blocks bx and bx + 8 are dealt to the same XCD (observed round-robin dispatch, for speed only — the
-        // handshake below checks it), so a cluster is made of the blocks of equal bx % 8 of one chunk of 8 G blocks, and eight
-        // clusters — one per XCD — share a chunk.  Blocks of trials past the last one leave at once.
-        const int chunk = blockIdx.x / (8 * G), within = blockIdx.x % (8 * G);
-        T = chunk * 8 + (within & 7); b = within >> 3;
-        if (T >= ntrials) return;
-    }
+    int T, b; // (prach_exchange.h: consecutive blocks, or XCD-packed)
+    if (!cluster_block(G, xpack, ntrials, T, b)) return;
     const TrialDev *const PD = params + T;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     LK K;
@@ -440,25 +339,8 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
     if (tid < SCHR) LI(lo::SCHED)[tid] = ((const PRACH_G int *)PD->sched)[min(tid, PD->maxTime / K.aT + 1)];
     __syncthreads();
 
-    // ---- same-XCD handshake: every workgroup publishes the id of the XCD it runs on (write-through granule, tag 0xFFFF, in the
-    // header of its parity-1 mailbox — first used by subframe 1, which no workgroup reaches before every peer is past this point,
-    // because subframe 0's exchange needs every peer's subframe-0 granules) and reads all G of them: the cluster keeps its granules
-    // in L2 only if they are all equal.  Every workgroup reads the same G values, so all decide alike.
-    if (xpack && G > 1 && G <= 64) {
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        xcc &= 0xfu;
-        PRACH_G long long *const hs = mbox + parstride;
-        if (tid == 0) lst(hs + myoff, lmk(xcc, 0u, 0xFFFFu));
-        if (tid < 64) {
-            bool same = true;
-            if (tid < G) same = ((unsigned)lwait(hs + (unsigned)tid * mbs, 0xFFFFu, smem) & 0xFFFFFu) == xcc;
-            const bool all = __ballot(!same) == 0ull;
-            if (tid == 0) scal[S_SX] = all ? 1 : 0;
-        }
-        __syncthreads();
-        K.sx = scal[S_SX] != 0 && scal[S_STATUS] == PRACH_OK;
-    }
+    // ---- same-XCD handshake (prach_exchange.h): a cluster that runs on ONE XCD keeps its granules in that XCD's L2
+    if (xpack && G > 1 && G <= 64) K.sx = same_xcd_handshake(mbox + parstride, mbs, b, G, &scal[S_STATUS], &scal[S_SX]);
     const bool sx = K.sx;
 
     int activeCheck = 0, grantCheck = 0, tlast = -1, time_exit = stop;
@@ -545,7 +427,7 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
             if (k < N_) {
                 const int2 e = gev[k];
                 const int type = e.y & 7;
-                if (type == EVL_CALLER || type == EVL_RESETCAND) { caller = true; idx = e.x; p = (e.y >> 4) & 0xff; ispre = (e.y >> 3) & 1; }
+                if (type == UEV_CALLER || type == UEV_RESETCAND) { caller = true; idx = e.x; p = (e.y >> 4) & 0xff; ispre = (e.y >> 3) & 1; }
             } else {
                 p = k - N_;
                 if (fcallA[p] != INT_MAX && !LI(lo::FIE + fa_)[p]) { caller = true; idx = fcallA[p]; ispre = 1; } // a STAY pre-member calls first
@@ -558,11 +440,11 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
                 for (int j = 0; j < N_; j++) {
                     const int2 ej = gev[j];
                     const int tj = ej.y & 7;
-                    if ((tj == EVL_CALLER || tj == EVL_RESETCAND) && ((ej.y >> 4) & 0xff) == p && ej.x < idx && ej.x > prev) prev = ej.x;
+                    if ((tj == UEV_CALLER || tj == UEV_RESETCAND) && ((ej.y >> 4) & 0xff) == p && ej.x < idx && ej.x > prev) prev = ej.x;
                 }
                 for (int j = 0; j < N_; j++) {
                     const int2 ej = gev[j];
-                    if ((ej.y & 7) == EVL_RJOIN && ((ej.y >> 4) & 0xff) == p && ej.x < idx && ej.x > prev) rj++;
+                    if ((ej.y & 7) == UEV_RJOIN && ((ej.y >> 4) & 0xff) == p && ej.x < idx && ej.x > prev) rj++;
                 }
             }
             const int check = 1 + (first ? LI(lo::TOTAL + fa_)[p] - ispre - LI(lo::NLV + fa_)[p] : 0) + rj;
@@ -609,6 +491,9 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
         PRACH_G long long *const mygr = mbpar + myoff;
         PRACH_G long long *const mbev = mygr + 1 + nP;
         int *const fcallA = LI(lo::FCALL + fa);
+        const ResolveTables RT{fcallA, LI(lo::NLV + fa), LI(lo::FIE + fa), LI(lo::RCL), LI(lo::SIDX), &scal[S_NRC], &scal[S_NRJ]}; // (prach_resolve.h)
+        auto ev_get = [&](const int k) __attribute__((always_inline)) { return gev[k]; };
+        auto ev_kill = [&](const int k) __attribute__((always_inline)) { gev[k].y = 0; };
         LSTAMP(0); // loop head
 
         if (t == 0) { // (every later subframe's phase A has run ahead, inside the exchange of the subframe before)
@@ -655,7 +540,7 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
                         unsigned c5[5];
 #pragma unroll
                         for (int u_ = 0; u_ < 5; u_++) { const int g = b + G * (5 * q + u_); c5[u_] = g < totgroups ? (unsigned)gsum[g] : 0u; }
-                        lstx(sx, mine + q, lmk(c5[0] | (c5[1] << 8) | ((c5[2] & 0xFu) << 16), (c5[2] >> 4) | (c5[3] << 4) | (c5[4] << 12), tag));
+                        st_gr(sx, mine + q, mk_granule(c5[0] | (c5[1] << 8) | ((c5[2] & 0xFu) << 16), (c5[2] >> 4) | (c5[3] << 4) | (c5[4] << 12), tag));
                     }
                     // (five 8-bit counts per granule — a 64-UE group makes at most 128 calls: fewer granules, fewer pollers.  Gathering them directly
                     //  into the scanning threads' registers, four polls per thread and no staging barrier, measured 2.5 ms SLOWER per trial:
@@ -663,7 +548,7 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
                     for (int k = tl; k < G * nq; k += WG_THREADS) {
                         const int wg = k / nq, q = k - wg * nq;
                         if (wg == b) continue;
-                        const long long g_ = lwait(mbpar + (unsigned)wg * mbs + 1u + (unsigned)nP + (unsigned)CLUSTER_EVW + (unsigned)q, tag, smem);
+                        const long long g_ = wait_granule(mbpar + (unsigned)wg * mbs + 1u + (unsigned)nP + (unsigned)CLUSTER_EVW + (unsigned)q, tag, &scal[S_STATUS]);
                         const unsigned lo_ = (unsigned)g_ & 0xFFFFFu, hi_ = (unsigned)((unsigned long long)g_ >> 32) & 0xFFFFFu;
                         const unsigned c5[5] = {lo_ & 0xFFu, (lo_ >> 8) & 0xFFu, (lo_ >> 16) | ((hi_ & 0xFu) << 4), (hi_ >> 4) & 0xFFu, (hi_ >> 12) & 0xFFu};
 #pragma unroll
@@ -729,7 +614,7 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
         if (tl >= WG_THREADS - 64 && tl - (WG_THREADS - 64) < nP) { // (the last wavefront: the first ones run the leaver filter)
             const int k = tl - (WG_THREADS - 64);
             const int ml = min(LI(lo::PAR + pc + lo::P_MLOC)[k], LI(lo::PAR + pc + lo::P_MLOCS)[k]);
-            lstx(sx, mygr + 1 + k, lmk((unsigned)LI(lo::PAR + pc + lo::P_HIST)[k], ml == INT_MAX ? GRL_NONE : (unsigned)ml, tag));
+            st_gr(sx, mygr + 1 + k, mk_granule((unsigned)LI(lo::PAR + pc + lo::P_HIST)[k], ml == INT_MAX ? GR_NONE : (unsigned)ml, tag));
         }
 
         // early leavers below this workgroup's lowest caller are the only ones a rank can need.  No candidate (the usual case outside
@@ -745,7 +630,7 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
                     const int2 c = LI2(lo::LCAND)[k];
                     if (c.x < min(mloc[c.y], mlocs[c.y])) {
                         const int es = atomicAdd(nevp, 1);
-                        if (es < CLUSTER_EVW) lstx(sx, mbev + es, lmk((unsigned)c.x, (unsigned)(EVL_LEAVER | (c.y << 4)), tag));
+                        if (es < CLUSTER_EVW) st_gr(sx, mbev + es, mk_granule((unsigned)c.x, (unsigned)(EV_LEAVER | (c.y << 4)), tag));
                     }
                 }
                 LSTAMP(3); // leaver filter
@@ -757,7 +642,7 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
             // then — and used again by the pass of subframe t + 2, two unconditional barriers later)
             // (the overflow bit also carries a capacity this workgroup ALONE has exceeded in its pass — the candidate list — so that every
             //  workgroup of the cluster leaves at the same S3 with PRACH_ERR_INTERNAL instead of spinning for a peer that has left)
-            if (tl == 64) lstx(sx, mygr, lmk((unsigned)min(nevraw, CLUSTER_EVW) | ((nevraw > CLUSTER_EVW || scal[S_STATUS] == PRACH_ERR_INTERNAL) ? (1u << 13) : 0u), (unsigned)scal[S_NSUCC], tag));
+            if (tl == 64) st_gr(sx, mygr, mk_granule((unsigned)min(nevraw, CLUSTER_EVW) | ((nevraw > CLUSTER_EVW || scal[S_STATUS] == PRACH_ERR_INTERNAL) ? (1u << 13) : 0u), (unsigned)scal[S_NSUCC], tag));
         }
         LSTAMP(5); // publish
         // Phase A of the NEXT subframe runs while the other workgroups' granules are on their way; then round 1 is issued — the bucket
@@ -777,12 +662,12 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
         long long gv[3] = {0, 0, 0}, hv = 0;
 #pragma unroll
         for (int u = 0; u < 3; u++)
-            if (r1p[u] >= 0) gv[u] = lld(mbpar + r1off[u]);
-        if (hl >= 0 && hl < G) hv = lld(mbpar + hoff);
+            if (r1p[u] >= 0) gv[u] = ld_sc1_64(mbpar + r1off[u]);
+        if (hl >= 0 && hl < G) hv = ld_sc1_64(mbpar + hoff);
         long long ev2[2] = {0, 0};
 #pragma unroll
         for (int u = 0; u < 2; u++)
-            if (r2wg[u] >= 0) ev2[u] = lld(mbpar + r2off[u]);
+            if (r2wg[u] >= 0) ev2[u] = ld_sc1_64(mbpar + r2off[u]);
         LSTAMP(17);
         if (!GLIBC) { // refill: the next two draws of every UE that drew in this subframe's phase B (off the chain: the exchange is in flight)
             const int nrq = min(scal[S_NRQ], LRQ);
@@ -805,26 +690,26 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
             for (int u = 0; u < 3; u++) {
                 if (r1p[u] >= 0) {
                     long long g_ = gv[u];
-                    if (!lok(g_, tag)) { LSTAT(1, 1); g_ = lwait(mbpar + r1off[u], tag, smem); }
+                    if (!granule_ok(g_, tag)) { LSTAT(1, 1); g_ = wait_granule(mbpar + r1off[u], tag, &scal[S_STATUS]); }
                     const unsigned h = (unsigned)g_ & 0xFFFFFu, ml = (unsigned)((unsigned long long)g_ >> 32) & 0xFFFFFu;
                     if (h) atomicAdd(&total[r1p[u]], (int)h);
-                    if (ml != GRL_NONE) atomicMin(&fcallA[r1p[u]], (int)ml);
+                    if (ml != GR_NONE) atomicMin(&fcallA[r1p[u]], (int)ml);
                 }
             }
             for (int k = tl + 3 * WG_THREADS; k < G * nP; k += WG_THREADS) { // (more than 3072 bucket granules)
                 const int wg = k / nP, p = k - wg * nP;
-                const long long g_ = lwait(mbpar + (unsigned)wg * mbs + 1u + (unsigned)p, tag, smem);
+                const long long g_ = wait_granule(mbpar + (unsigned)wg * mbs + 1u + (unsigned)p, tag, &scal[S_STATUS]);
                 const unsigned h = (unsigned)g_ & 0xFFFFFu, ml = (unsigned)((unsigned long long)g_ >> 32) & 0xFFFFFu;
                 if (h) atomicAdd(&total[p], (int)h);
-                if (ml != GRL_NONE) atomicMin(&fcallA[p], (int)ml);
+                if (ml != GR_NONE) atomicMin(&fcallA[p], (int)ml);
             }
             LSTAMP(19);
             if (hl >= 0) {
                 int nev = 0, nsuc = 0, ovf = 0;
                 if (hl < G) {
                     long long g_ = hv;
-                    LSTAT(2, __popcll(__ballot(!lok(g_, tag))) ? 1 : 0); // (subframes in which a header was late)
-                    if (!lok(g_, tag)) g_ = lwait(mbpar + hoff, tag, smem);
+                    LSTAT(2, __popcll(__ballot(!granule_ok(g_, tag))) ? 1 : 0); // (subframes in which a header was late)
+                    if (!granule_ok(g_, tag)) g_ = wait_granule(mbpar + hoff, tag, &scal[S_STATUS]);
                     const unsigned w0 = (unsigned)g_ & 0xFFFFFu;
                     nev = (int)(w0 & 0x1FFFu); ovf = (int)((w0 >> 13) & 1u); nsuc = (int)((unsigned)((unsigned long long)g_ >> 32) & 0xFFFFFu);
                 }
@@ -863,10 +748,10 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
                     const int o0 = evoff[r2wg[u]], nev = evoff[r2wg[u] + 1] - o0;
                     if (r2es[u] < nev) {
                         long long e = ev2[u];
-                        if (!lok(e, tag)) { e = lwait(mbpar + r2off[u], tag, smem); }
+                        if (!granule_ok(e, tag)) { e = wait_granule(mbpar + r2off[u], tag, &scal[S_STATUS]); }
                         const int2 ev = make_int2((int)((unsigned)e & 0xFFFFFu), (int)((unsigned)((unsigned long long)e >> 32) & 0xFFFFFu));
                         gev[o0 + r2es[u]] = ev;
-                        l_classify(smem, fa, o0 + r2es[u], ev);
+                        classify_event(RT, o0 + r2es[u], ev, ev_kill);
                     }
                 }
             }
@@ -876,10 +761,10 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
                     while (hi_ - lo_ > 1) { const int mid = (lo_ + hi_) >> 1; if (evoff[mid] <= k) lo_ = mid; else hi_ = mid; }
                     const int es = k - evoff[lo_];
                     if (es < LEPF) continue;
-                    const long long e = lwait(mbpar + (unsigned)lo_ * mbs + 1u + (unsigned)nP + (unsigned)es, tag, smem);
+                    const long long e = wait_granule(mbpar + (unsigned)lo_ * mbs + 1u + (unsigned)nP + (unsigned)es, tag, &scal[S_STATUS]);
                     const int2 ev = make_int2((int)((unsigned)e & 0xFFFFFu), (int)((unsigned)((unsigned long long)e >> 32) & 0xFFFFFu));
                     gev[k] = ev;
-                    l_classify(smem, fa, k, ev);
+                    classify_event(RT, k, ev, ev_kill);
                 }
             }
         }
@@ -891,14 +776,14 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
         const int nrc = scal[S_NRC];
         if (nrc > 0) { // rare: reset cycles that may re-join — decided strictly in index order, then recount
             if (nrc > RCCAP) { status = PRACH_ERR_INTERNAL; time_exit = t; break; }
-            if (tl < 64) l_resolve_reset_candidates(smem, fa, nrc, nP);
+            if (tl < 64) resolve_reset_candidates<1>(RT, nrc, nP, ev_get, ev_kill);
             else if (tl < 64 + NPCL) { LI(lo::NLV + fa)[tl - 64] = 0; LI(lo::FIE + fa)[tl - 64] = 0; }
             __syncthreads();
             for (int k = tl; k < N; k += WG_THREADS) {
                 const int2 e = gev[k];
                 const int type = e.y & 7, p = (e.y >> 4) & 0xff;
-                if (type == EVL_LEAVER) { if (e.x < fcallA[p]) atomicAdd(&LI(lo::NLV + fa)[p], 1); }
-                else if ((type == EVL_CALLER || type == EVL_RESETCAND) && e.x == fcallA[p]) LI(lo::FIE + fa)[p] = 1;
+                if (type == EV_LEAVER) { if (e.x < fcallA[p]) atomicAdd(&LI(lo::NLV + fa)[p], 1); }
+                else if ((type == UEV_CALLER || type == UEV_RESETCAND) && e.x == fcallA[p]) LI(lo::FIE + fa)[p] = 1;
             }
             __syncthreads();
         }
@@ -927,7 +812,7 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
             if (ahead) {
                 const int4 r = lrec[sl];
                 const unsigned pk = (unsigned)r.w & ~PK_GRANT_BIT;
-                if ((pk >> PK_PEND_SHIFT) == (unsigned)PEND_STAY && l_light(pk, r.x, r.z, t + 1, K.rarlim)) {
+                if ((pk >> PK_PEND_SHIFT) == (unsigned)PEND_STAY && light_case(pk, r.x, r.z, t + 1, K.rarlim)) {
                     const int p1 = (int)((pk >> PK_PRE_SHIFT) & 0xffu) - 1;
                     atomicSub(&LI(lo::PAR + pn + lo::P_HIST)[p1], 1);
                     LI(lo::PAR + pn + lo::P_MLOCS)[p1] = INT_MAX;
@@ -1085,14 +970,9 @@ int lcluster_max_preambles() { return NPCL; }
 
 hipError_t launch_lcluster_kernel(const TrialDev *params, int ntrials, int G, int lslots, int xpack, bool glibc, int groups, hipStream_t stream) {
     const size_t lds = lcluster_kernel_lds_bytes(lslots, glibc, groups);
-    const void *fn = glibc ? reinterpret_cast<const void *>(&lcluster_kernel<true>) : reinterpret_cast<const void *>(&lcluster_kernel<false>);
-    hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (rc != hipSuccess) return rc;
     const int grid = xpack ? ((ntrials + 7) / 8) * 8 * G : ntrials * G;
     const int gcap = lcluster_group_capacity(groups);
-    if (glibc) hipLaunchKernelGGL(lcluster_kernel<true>, dim3(grid), dim3(WG_THREADS), lds, stream, params, G, lslots, xpack, ntrials, gcap);
-    else hipLaunchKernelGGL(lcluster_kernel<false>, dim3(grid), dim3(WG_THREADS), lds, stream, params, G, lslots, xpack, ntrials, gcap);
-    return hipGetLastError();
+    return launch_with_lds(glibc ? lcluster_kernel<true> : lcluster_kernel<false>, grid, WG_THREADS, lds, stream, params, G, lslots, xpack, ntrials, gcap);
 }
 
 } // namespace prach

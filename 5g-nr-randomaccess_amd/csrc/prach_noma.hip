@@ -29,6 +29,8 @@
 #include "prach_device.h"
 #include "prach_device_fn.h"
 #include "prach_noma_act.h"
+#include "prach_exchange.h"
+#include "prach_noma_resolve.h"
 #include <limits.h>
 
 #ifdef PRACH_STAMPS
@@ -50,8 +52,6 @@ namespace {
 constexpr unsigned N_RA_BIT = 1u << 2, N_FAIL_BIT = 1u << 3, N_MSG2_BIT = 1u << 4, N_M3W_BIT = 1u << 5, N_PRE_SHIFT = 6,
                    N_RETX_SHIFT = 14, N_RAR5_BIT = 1u << 22;
 constexpr int NOMA_VARIANT = 2;
-constexpr unsigned NGR_NONE = 0xFFFFFu;
-constexpr unsigned NSPIN_LIMIT = 1u << 22;
 
 struct NLds {
     int *cnt;    // [6*nP] this workgroup's transmitters per (sector, preamble)
@@ -77,32 +77,6 @@ __device__ __forceinline__ NLds ncarve(char *smem, int nP) {
     L.tcnt = ip; ip += 6 * nP;
     L.twho = ip; ip += 6 * nP;
     return L;
-}
-
-__device__ __forceinline__ long long nld(const PRACH_G long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void nst(PRACH_G long long *p, long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// ... or, for a cluster that has verified that it runs on one XCD (prologue handshake, as in prach_lcluster.hip), resident in that XCD's L2
-__device__ __forceinline__ void nstx(const bool same_xcd, PRACH_G long long *p, long long v) {
-    if (same_xcd) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ long long nmk(unsigned lo20, unsigned hi20, unsigned tag) {
-    const unsigned w0 = (lo20 & 0xFFFFFu) | ((tag & 0xFFFu) << 20), w1 = (hi20 & 0xFFFFFu) | (((tag >> 12) & 0xFu) << 20);
-    return (long long)(((unsigned long long)w1 << 32) | w0);
-}
-__device__ __forceinline__ bool nok(long long g, unsigned tag) {
-    const unsigned w0 = (unsigned)g, w1 = (unsigned)((unsigned long long)g >> 32);
-    return (w0 >> 20) == (tag & 0xFFFu) && ((w1 >> 20) & 0xFu) == ((tag >> 12) & 0xFu);
-}
-__device__ __forceinline__ long long nwait(const PRACH_G long long *p, unsigned tag, int *status_word) {
-    long long g = nld(p);
-    unsigned spins = 0;
-    while (!nok(g, tag)) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > NSPIN_LIMIT) { *status_word = PRACH_ERR_TIMEOUT; break; } // peer not resident? the engine reruns with one workgroup per trial
-        g = nld(p);
-    }
-    return g;
 }
 
 // ---- activeUE on the device (NOMA.c:131-192): one thread per UE of every trial of the launch; the UE's own Philox counter gives its draws, so UEs are
@@ -133,12 +107,8 @@ size_t noma_kernel_lds_bytes(int nP) { return sizeof(double) * 2 * 6 * 64 + size
 
 __global__ __launch_bounds__(WG_THREADS) void noma_kernel(const TrialDev *__restrict__ params, const int G, const int nT, const int xpack) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    int T = blockIdx.x / G, b = blockIdx.x % G; // a cluster = consecutive blocks (in-order dispatch completes whole clusters)
-    if (xpack) { // XCD-packed launch (prach_lcluster.hip): a cluster = the blocks of equal blockIdx % 8 of a chunk of 8 G blocks
-        const int chunk = blockIdx.x / (8 * G), within = blockIdx.x % (8 * G);
-        T = chunk * 8 + (within & 7); b = within >> 3;
-        if (T >= nT) return;
-    }
+    int T, b; // (prach_exchange.h: consecutive blocks, or XCD-packed)
+    if (!cluster_block(G, xpack, nT, T, b)) return;
     const TrialG P(params[T]);
     const NLds L = ncarve(smem, P.nP);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -162,22 +132,8 @@ __global__ __launch_bounds__(WG_THREADS) void noma_kernel(const TrialDev *__rest
     __syncthreads();
     if (tid == 0) L.scal[N_MAXT] = -1;
     __syncthreads();
-    bool sx = false;
-    if (xpack && G > 1 && G <= 64) { // same-XCD handshake: XCC ids through write-through granules (tag 0xFFFF, header of the parity-1 mailbox)
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        xcc &= 0xfu;
-        PRACH_G long long *const hs = mbox + (size_t)G * mbstride;
-        if (tid == 0) nst(hs + (size_t)b * mbstride, nmk(xcc, 0u, 0xFFFFu));
-        if (tid < 64) {
-            bool same = true;
-            if (tid < G) same = ((unsigned)nwait(hs + (size_t)tid * mbstride, 0xFFFFu, &L.scal[N_STATUS]) & 0xFFFFFu) == xcc;
-            const bool all = __ballot(!same) == 0ull;
-            if (tid == 0) L.scal[N_SX] = all ? 1 : 0;
-        }
-        __syncthreads();
-        sx = L.scal[N_SX] != 0 && L.scal[N_STATUS] == PRACH_OK;
-    }
+    bool sx = false; // same-XCD handshake (prach_exchange.h)
+    if (xpack && G > 1 && G <= 64) sx = same_xcd_handshake(mbox + (size_t)G * mbstride, (size_t)mbstride, b, G, &L.scal[N_STATUS], &L.scal[N_SX]);
 
     int activeCheck = 0, time_exit = P.stop, status = PRACH_OK;
     bool all_done = false;
@@ -189,7 +145,6 @@ __global__ __launch_bounds__(WG_THREADS) void noma_kernel(const TrialDev *__rest
     // "one of the two" always decodes the weaker UE, without the second draw (NOMA.c:413-415 vs :287-290)
     const bool nonsector = (P.flags & PRACH_FLAG_NOMA_NONSECTOR) != 0;
     const int nsect = nonsector ? 1 : 6;
-    const bool devact = P.n_devact != 0;
 
     // pass A for one UE of the slot whose subframe is tA: activation of the newly arrived (activeUE, NOMA.c:131-140: everything
     // else comes from the activation table) and the transmitter gather (NOMA.c:207: RA==0, txTime==time+1, msg2==0,
@@ -248,27 +203,27 @@ __global__ __launch_bounds__(WG_THREADS) void noma_kernel(const TrialDev *__rest
             PRACH_G long long *const mygr = mbox + ((size_t)(s & 1) * G + b) * mbstride;
             for (int k = tid; k < nb; k += WG_THREADS) {
                 const int wv = L.who[k];
-                nstx(sx, mygr + 1 + k, nmk((unsigned)L.cnt[k], wv == INT_MAX ? NGR_NONE : (unsigned)wv, tag));
+                st_gr(sx, mygr + 1 + k, mk_granule((unsigned)L.cnt[k], wv == INT_MAX ? GR_NONE : (unsigned)wv, tag));
                 L.cnt[k] = 0; L.who[k] = INT_MAX; // the next slot's gather starts in this slot's pass B
             }
-            if (tid == 0) nstx(sx, mygr, nmk((unsigned)L.scal[N_NSUCC], (unsigned)(L.scal[N_MAXT] + 1), tag));
+            if (tid == 0) st_gr(sx, mygr, mk_granule((unsigned)L.scal[N_NSUCC], (unsigned)(L.scal[N_MAXT] + 1), tag));
             for (int k0 = tid; k0 < G * nb; k0 += 4 * WG_THREADS) { // four granule loads in flight per thread
                 long long gv[4];
                 int kk[4];
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     kk[u] = k0 + u * WG_THREADS;
-                    if (kk[u] < G * nb) { const int wg = kk[u] / nb, bin = kk[u] - wg * nb; gv[u] = nld(mbox + ((size_t)(s & 1) * G + wg) * mbstride + 1 + bin); }
+                    if (kk[u] < G * nb) { const int wg = kk[u] / nb, bin = kk[u] - wg * nb; gv[u] = ld_sc1_64(mbox + ((size_t)(s & 1) * G + wg) * mbstride + 1 + bin); }
                     else gv[u] = 0;
                 }
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     if (kk[u] >= G * nb) continue;
                     const int wg = kk[u] / nb, bin = kk[u] - wg * nb;
-                    if (!nok(gv[u], tag)) gv[u] = nwait(mbox + ((size_t)(s & 1) * G + wg) * mbstride + 1 + bin, tag, &L.scal[N_STATUS]);
+                    if (!granule_ok(gv[u], tag)) gv[u] = wait_granule(mbox + ((size_t)(s & 1) * G + wg) * mbstride + 1 + bin, tag, &L.scal[N_STATUS]);
                     const unsigned c = (unsigned)gv[u] & 0xFFFFFu, wv = (unsigned)((unsigned long long)gv[u] >> 32) & 0xFFFFFu;
                     if (c) atomicAdd(&L.tcnt[bin], (int)c);
-                    if (wv != NGR_NONE) atomicMin(&L.twho[bin], (int)wv);
+                    if (wv != GR_NONE) atomicMin(&L.twho[bin], (int)wv);
                 }
             }
             NSTAMP(1); // publish + bins gathered
@@ -276,7 +231,7 @@ __global__ __launch_bounds__(WG_THREADS) void noma_kernel(const TrialDev *__rest
                 const int l = tid - (WG_THREADS - 64);
                 int ns = 0, mt = -1;
                 if (l < G) {
-                    const long long g_ = nwait(mbox + ((size_t)(s & 1) * G + l) * mbstride, tag, &L.scal[N_STATUS]);
+                    const long long g_ = wait_granule(mbox + ((size_t)(s & 1) * G + l) * mbstride, tag, &L.scal[N_STATUS]);
                     ns = (int)((unsigned)g_ & 0xFFFFFu);
                     mt = (int)((unsigned)((unsigned long long)g_ >> 32) & 0xFFFFFu) - 1;
                 }
@@ -295,86 +250,22 @@ __global__ __launch_bounds__(WG_THREADS) void noma_kernel(const TrialDev *__rest
             const int sct = w;
             const bool single = lane < nP && L.tcnt[sct * nP + lane] == 1;
             const int myidx = single ? L.twho[sct * nP + lane] : -1;
-            const unsigned long long sm = __ballot(single);
-            const int count = __popcll(sm);
-            if (count > 0) {
-                const int pos = __popcll(sm & lanemask_lt(lane));
-                if (count <= nGrantUL) { // NOMA.c:252-260
-                    if (single && ((myidx >> 6) % G) == b) grant_rec(&P.rec[myidx]);
-                } else {
-                    if (single) { L.sidx[sct * 64 + pos] = myidx; L.sg[sct * 64 + pos] = gain[myidx]; L.slg[sct * 64 + pos] = lgain[myidx]; }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    NSTAMP(8); // resolve: gains loaded
-                    // stable ascending rank by gain == the bubble sort with strict < (NOMA.c:90-103)
-                    int uidx = -1;
-                    double ug = 0, ulg = 0;
-                    int rank = 0;
-                    bool ambiguous = false;
-                    if (lane < count) {
-                        uidx = L.sidx[sct * 64 + lane]; ug = L.sg[sct * 64 + lane]; ulg = L.slg[sct * 64 + lane];
-#pragma unroll 8
-                        for (int j = 0; j < count; j++) { // (unrolled: eight broadcast reads in flight instead of one LDS round trip per comparison)
-                            const double gj = L.sg[sct * 64 + j];
-                            rank += (gj < ug || (gj == ug && j < lane)) ? 1 : 0;
-                        }
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    if (lane < count) { L.sidx[sct * 64 + rank] = uidx; L.slg[sct * 64 + rank] = ulg; L.sg[sct * 64 + rank] = ug; } // (every lane has read the unsorted gains: barrier above)
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    int cidx = -1;
-                    double clg = 0;
-                    if (lane < count) { cidx = L.sidx[sct * 64 + lane]; clg = L.slg[sct * 64 + lane]; }
-                    // device-built table: two gains closer than the error band of the device's libm (ACT_GAIN_ORDER_BAND, prach_noma_act.h: twice the asserted per-gain error, with margin) could be ordered the other way by the reference's —
-                    // in sorted order it is enough to look at neighbours (n_devact == 2: test hook, every sort counts as ambiguous)
-                    if (devact && lane + 1 < count) { const double ga = L.sg[sct * 64 + lane], gb = L.sg[sct * 64 + lane + 1]; if (__dsub_rn(gb, ga) <= ACT_GAIN_ORDER_BAND * gb || P.n_devact == 2) ambiguous = true; }
-                    NSTAMP(9); // resolve: ranked and sorted
-                    unsigned long long valid = count >= 64 ? ~0ull : ((1ull << count) - 1ull);
-                    const double clg10 = __dmul_rn(10.0, clg); // (NOMA.c:272: 10 * log(gain), the same product on either side of the difference)
-                    int grants = 0, npd = 0;
-                    bool grantme = false;
-                    const unsigned long long lows = count >= 2 ? ((1ull << (count - 1)) - 1ull) : 0ull; // i < count - 1
-                    unsigned long long above = ~0ull;                                                    // bits behind the last i looked at
-                    for (;;) { // NOMA.c:268-298, over the still unpaired i in ascending order
-                        const unsigned long long rest = valid & lows & above;
-                        if (!rest) break;
-                        const int i = __ffsll((long long)rest) - 1;
-                        above = ~((2ull << i) - 1ull);
-                        // (lane i's 10 ln g through two v_readlane — i is wave-uniform — instead of a ds_bpermute round trip per comparison: this loop is a latency chain)
-                        const double lgi10 = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(clg10), i), __builtin_amdgcn_readlane(__double2loint(clg10), i));
-                        const double diff = __dsub_rn(clg10, lgi10); // 10*log(high) - 10*log(low)
-                        if (devact && lane < count && fabs(__dsub_rn(diff, 15.0)) < 1e-9) ambiguous = true; // (|error| of 10 ln g1 - 10 ln g2 < 1e-12)
-                        // (the lanes still unpaired, not lane 0, not i itself: scalar mask algebra on the comparison's ballot instead of a 64-bit shift per lane)
-                        const unsigned long long mj = __ballot(diff > 15.0) & valid & ~(1ull << i) & ~1ull;
-                        if (!mj) continue;
-                        const int j = __ffsll((long long)mj) - 1;
-                        valid &= ~((1ull << i) | (1ull << j));
-                        if (grants < nGrantUL) {
-                            const unsigned kd = (unsigned)(((s * 6 + sct) * nGrantUL + grants) * 2);
-                            grants++;
-                            const int d1 = philox_draw31(P.seed_lo, P.seed_hi, 0xFFFFFFFFu, kd, (unsigned)nUE, NOMA_VARIANT);
-                            int decoded = 2; // both
-                            npd++;
-                            if (d1 <= 644245094) { // (double)rand()/RAND_MAX < 0.3 (NOMA.c:284-285)
-                                if (nonsector) decoded = 0; // rx[0], the weaker UE: NOMA.c:413-415
-                                else {
-                                    const int d2 = philox_draw31(P.seed_lo, P.seed_hi, 0xFFFFFFFFu, kd + 1, (unsigned)nUE, NOMA_VARIANT);
-                                    decoded = d2 % 2; // index into rx[] = {low, high}
-                                    npd++;
-                                }
-                            }
-                            if ((lane == i && (decoded == 2 || decoded == 0)) || (lane == j && (decoded == 2 || decoded == 1))) grantme = true;
-                        }
-                    }
-                    { // leftovers in sorted order while grants remain (NOMA.c:299-307)
-                        const bool left = lane < count && ((valid >> lane) & 1ull);
-                        const unsigned long long lm = __ballot(left);
-                        if (left && __popcll(lm & lanemask_lt(lane)) < nGrantUL - grants) grantme = true;
-                    }
-                    NSTAMP(10); // resolve: paired
-                    if (grantme && ((cidx >> 6) % G) == b) grant_rec(&P.rec[cidx]);
-                    if (b == 0 && lane == 0 && npd) atomicAdd(&L.scal[N_PAIRD], npd);
-                    if (__any(ambiguous) && lane == 0) L.scal[N_AMBIG] = 1;
-                }
+            const int count = __popcll(__ballot(single));
+            if (count > 0 && count <= nGrantUL) { // NOMA.c:252-260
+                if (single && ((myidx >> 6) % G) == b) grant_rec(&P.rec[myidx]);
+            } else if (count > 0) { // (prach_noma_resolve.h; the pair draws: the stateless counter ((slot * 6 + sector) * nGrantUL + pair) * 2 (+ 1))
+                int npd = 0;
+                const NomaResolved R = noma_resolve_sector(single, myidx, nGrantUL, nonsector, P.n_devact, L.sidx + sct * 64, L.sg + sct * 64, L.slg + sct * 64,
+                    [&](const int idx) __attribute__((always_inline)) { return NomaGain{gain[idx], lgain[idx]}; },
+                    [&](const int pair, const int which, int &d) __attribute__((always_inline)) {
+                        d = philox_draw31(P.seed_lo, P.seed_hi, 0xFFFFFFFFu, (unsigned)(((s * 6 + sct) * nGrantUL + pair) * 2 + which), (unsigned)nUE, NOMA_VARIANT);
+                        npd++;
+                        return true;
+                    },
+                    [&](const int idx) __attribute__((always_inline)) { if (((idx >> 6) % G) == b) grant_rec(&P.rec[idx]); }, // (by the record's owner only)
+                    [&](const int k) __attribute__((always_inline)) { NSTAMP(k); (void)k; });
+                if (b == 0 && lane == 0 && npd) atomicAdd(&L.scal[N_PAIRD], npd);
+                if (R.ambiguous && lane == 0) L.scal[N_AMBIG] = 1;
             }
         }
         NSTAMP(3); // resolve (sector 0), rest
@@ -576,20 +467,14 @@ __global__ __launch_bounds__(WG_THREADS) void noma_kernel(const TrialDev *__rest
 
 hipError_t launch_noma_kernel(const TrialDev *params, int ntrials, int G, int maxP, int xpack, hipStream_t stream) {
     const size_t lds = noma_kernel_lds_bytes(maxP);
-    hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void *>(&noma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (rc != hipSuccess) return rc;
     if (G <= 1) xpack = 0;
     const int grid = xpack ? ((ntrials + 7) / 8) * 8 * G : ntrials * G;
-    hipLaunchKernelGGL(noma_kernel, dim3(grid), dim3(WG_THREADS), lds, stream, params, G, ntrials, xpack);
-    return hipGetLastError();
+    return launch_with_lds(noma_kernel, grid, WG_THREADS, lds, stream, params, G, ntrials, xpack);
 }
 
 int noma_kernel_blocks_per_cu(int maxP) {
     const size_t lds = noma_kernel_lds_bytes(maxP);
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&noma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(&noma_kernel), WG_THREADS, lds) != hipSuccess || nb < 1) return 1;
-    return nb;
+    return kernel_blocks_per_cu(noma_kernel, WG_THREADS, lds);
 }
 
 hipError_t launch_noma_activation(const TrialDev *params, int ntrials, int maxUE, unsigned *flags, hipStream_t stream) {

@@ -103,9 +103,10 @@ __device__ __forceinline__ void noma_glibc_slot(NG NUe *const ue, const NG int *
     }
     __syncthreads();
     // ---- grouping (NOMA.c:214-309 per sector / :341-437 cell-wide) by ONE wavefront, sectors in order because the pair draws come straight from the
-    // stream: lane = preamble.  Singleton transmitters in preamble order (ballot compaction), stable ascending rank by gain == the reference's bubble
-    // sort with strict < (NOMA.c:90-103), greedy pairing over the sorted lanes (ballot + find-first), leftovers while grants remain — prach_noma.hip's
-    // resolver with the reference's stream instead of a counter.  (Before: one thread and the O(count^2) bubble sort on scratch arrays, ~1 ms per slot.)
+    // stream.  The algorithm is noma_resolve_sector's (prach_noma_resolve.h: read it there); this kernel keeps its OWN statement of it, on purpose.  Routed
+    // through the shared function, noma_glibc_trial_kernel came out with 83 SGPR spills (87 with the shared rank loop's `#pragma unroll 8`) instead of the
+    // 81 of this form, whatever the shape of the draw source (lambda, by-value policy, draw-or-minus-one), of the unroll (template constant 1, 2, 4, 8, none)
+    // or of the loop masks (LABNOTES, "Shared kernel headers").  A change of the algorithm lands in both places.
     if (tid < 64) {
         const int lane = tid;
         int status = PRACH_OK;

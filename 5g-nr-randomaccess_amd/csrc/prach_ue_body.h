@@ -354,7 +354,7 @@ PRACH_HD FlatOut flat_select(UeState &u, ColdRegs &cold, const FlatPlan &p, cons
     const int sa = slot_align_flat(lsel(p.retx, t, u.tx) + lsel(p.reset, fB2, fB1), fm);
     const lmask sanow = S & lm(sa == t);
     const float pf = (float)d1 / (float)2147483647;                      // Beta.c:374 ((float)RAND_MAX == 2^31)
-    const lmask ok = p.m3first & lm((double)pf > 0.1), nok = p.m3first & ~ok;
+    const lmask ok = p.m3first & lm((double)pf > 0.1), m3late = p.m3first & ~ok;
     const lmask fs = p.firstsel;
     const lmask callF = fs & txnow, callS = (rsn | p.retx) & sanow, rj = p.m3to & sanow;
     const lmask rc = rsm & lm(fB2 == 0) & rc_slot;                       // reset cycle that may re-join its slot (ue_select: UEV_RESETCAND)
@@ -370,7 +370,7 @@ PRACH_HD FlatOut flat_select(UeState &u, ColdRegs &cold, const FlatPlan &p, cons
     u.pre = lsel(fs | p.reset, fP1 + 1, lsel(p.m3to, fP2 + 1, u.pre));
     const int enc = lsel(lm(sa > t), sa, sa - t);                        // enc_backoff(sa - t, t)
     u.bo = lsel(rsm, oldp, lsel(S, enc, u.bo & ~fs));
-    u.tx = lsel(rsm, fB2, lsel(S, sa, u.tx + (48 & nok)));
+    u.tx = lsel(rsm, fB2, lsel(S, sa, u.tx + (48 & m3late)));
     u.tb = lsel(p.reset | p.m3to, t, lsel(ok, (t - u.tb) + 6, u.tb));
     u.conn = lsel(p.m3first, lsel(ok, 1, 2), u.conn & ~p.m3to);
     u.act = lsel(ok, ACT_DONE, lsel(p.m3to, ACT_M1, u.act));

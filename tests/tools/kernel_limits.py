@@ -11,51 +11,51 @@ oracle, no package import.  The engine (prach_engine.hip) is cited by function n
 # name -> where it is stated, which exported limit functions / constants of prach_device.h it covers, last value inside, first outside
 LIMITS = {
     "batch_preambles": dict(
-        source=["prach_engine.hip batch_eligible", "prach_batch.hip:69 NPB", "prach_batch.hip:241 guard", "prach_batch.hip:1055"],
+        source=["prach_engine.hip batch_eligible", "prach_batch.hip:70 NPB", "prach_batch.hip:241 guard", "prach_batch.hip:1017"],
         covers=["batch_max_preambles"], inside=64, outside=65, what="nPreamble, cluster=1"),
     "lcluster_preambles": dict(
-        source=["prach_engine.hip lds_record_slots / use_fast_kernel", "prach_lcluster.hip:51 NPCL", "prach_lcluster.hip:466 guard", "prach_lcluster.hip:1084"],
+        source=["prach_engine.hip lds_record_slots / use_fast_kernel", "prach_lcluster.hip:53 NPCL", "prach_lcluster.hip:348 guard", "prach_lcluster.hip:969"],
         covers=["lcluster_max_preambles"], inside=64, outside=65, what="nPreamble, cluster=4 and 16"),
     "noma_preambles": dict(
         source=["prach_engine.hip run_trials_impl"], covers=[], inside=64, outside=65, what="nPreamble of NOMA.c: 65 is PRACH_ERR_UNSUPPORTED"),
     "batch_rar_window": dict(
-        source=["prach_engine.hip batch_eligible", "prach_batch.hip:241 guard (literal 11)", "prach_batch.hip:1056,1059"],
+        source=["prach_engine.hip batch_eligible", "prach_batch.hip:241 guard (literal 11)", "prach_batch.hip:1018,1021"],
         covers=["batch_max_rar_window", "batch_max_rar_window_two_per_cu"], inside=11, outside=12,
         what="maxRarWindow, cluster=1.  The engine asks batch_max_rar_window() for both workgroup shapes; batch_max_rar_window_two_per_cu() has no caller and the same "
              "value: the 512-thread shape (batch_waves=8) has a pair of its own all the same"),
     "calendar_128_256": dict(
-        source=["prach_batch.hip:1061 batch_calendar_slots", "prach_engine.hip layout_launch (slots and chunk pool)", "prach_batch.hip:242 guard"],
+        source=["prach_batch.hip:1023 batch_calendar_slots", "prach_engine.hip layout_launch (slots and chunk pool)", "prach_batch.hip:242 guard"],
         covers=["batch_calendar_slots"], inside=128, outside=129, what="need = backoff + max(accessTime, 5) + maxRarWindow + 70: 128 slots / 256 slots, both the batch kernel"),
     "calendar_256_leave": dict(
-        source=["prach_engine.hip batch_eligible", "prach_batch.hip:72 CR", "prach_batch.hip:241 guard", "prach_batch.hip:1067"],
+        source=["prach_engine.hip batch_eligible", "prach_batch.hip:73 CR", "prach_batch.hip:241 guard", "prach_batch.hip:1029"],
         covers=["batch_max_calendar_slots"], inside=256, outside=257, what="the same need: 256 slots / no batch kernel"),
     "compact_record": dict(
-        source=["prach_engine.hip choose_kernel", "prach_cluster.hip:297 hot_fits"],
+        source=["prach_engine.hip choose_kernel", "prach_cluster.hip:264 hot_fits"],
         covers=[], inside=2935, outside=2936, what="backoff + accessTime with Uniform arrivals (60 000 + backoff + accessTime + 64 < 63 000), glibc, cluster=1, batch kernel ineligible"),
     "subframe_16bit": dict(
-        source=["prach_cluster.hip:294 hot record (16-bit txTime + 1)", "prach_lcluster.hip:466 / prach_cluster.hip:883 guards (stop >= 0xFFFE: the 16-bit granule tags)",
+        source=["prach_cluster.hip:261 hot record (16-bit txTime + 1)", "prach_lcluster.hip:348 / prach_cluster.hip:747 guards (stop >= 0xFFFE: the 16-bit granule tags)",
                 "prach_engine.hip batch_eligible and choose_kernel keep the 16-bit forms away"],
         covers=[], inside=65535, outside=65536, what="largest txTime of the trial (the oracle's log): every route must carry it in 32 bits"),
     "glibc_batch_groups": dict(
-        source=["prach_engine.hip batch_eligible", "prach_batch.hip:131 BGG", "prach_batch.hip:241 guard", "prach_batch.hip:1058"],
+        source=["prach_engine.hip batch_eligible", "prach_batch.hip:131 BGG", "prach_batch.hip:241 guard", "prach_batch.hip:1020"],
         covers=["batch_max_groups"], inside=131072, outside=131073, what="nUE in the reference's stream, cluster=1 (Philox: 2^14 groups = 2^20 UEs, behind the 20-bit limit: never deciding)"),
     "glibc_cluster_size": dict(
-        source=["prach_engine.hip run_trials_impl", "prach_device.h:135 CLUSTER_GLIBC_MAX_UE", "prach_cluster.hip:96 GSCAP", "prach_cluster.hip:883 guard", "prach_lcluster.hip:1083"],
+        source=["prach_engine.hip run_trials_impl", "prach_device.h:152 CLUSTER_GLIBC_MAX_UE", "prach_cluster.hip:96 GSCAP", "prach_cluster.hip:747 guard", "prach_lcluster.hip:968"],
         covers=["CLUSTER_GLIBC_MAX_UE", "lcluster_max_groups_glibc"], inside=262144, outside=262145,
         what="nUE in the reference's stream on any cluster kernel.  lcluster_max_groups_glibc() = 4096 groups is the same size and never decides on its own: "
              "4096 groups in lslots <= CLUSTER_LQCAP need 64 workgroups, whose layout (175 232 bytes) is past CLUSTER_LDS_LIMIT"),
     "lds_slots_philox": dict(
-        source=["prach_engine.hip lds_record_slots / use_fast_kernel", "prach_lcluster.hip:1079 lcluster_kernel_lds_bytes", "prach_cluster.hip:1342 cluster_kernel_lds_bytes"],
+        source=["prach_engine.hip lds_record_slots / use_fast_kernel", "prach_lcluster.hip:964 lcluster_kernel_lds_bytes", "prach_cluster.hip:1209 cluster_kernel_lds_bytes"],
         covers=["lcluster_kernel_lds_bytes"], inside=3136, outside=3200,
         what="owned UE slots per workgroup, Philox, lean kernel: the LDS-BYTE test binds, not CLUSTER_LQCAP — 75 904 + 28 x slots <= 163 840 admits 3 136 slots "
              "(rec_mode 3); beyond, the records stay in LDS on the general kernel (rec_mode 2)"),
     "lds_slots_general": dict(
-        source=["prach_engine.hip lds_record_slots", "prach_cluster.hip:1342 cluster_kernel_lds_bytes"],
+        source=["prach_engine.hip lds_record_slots", "prach_cluster.hip:1209 cluster_kernel_lds_bytes"],
         covers=["cluster_kernel_lds_bytes"], inside=3712, outside=3776,
         what="owned UE slots per workgroup, Philox, the general kernel's LDS-resident layout: bytes again — 88 704 + 20 x slots <= 163 840 admits 3 712 slots "
              "(rec_mode 2), beyond: global records (rec_mode 0)"),
     "lds_slots_glibc": dict(
-        source=["prach_engine.hip lds_record_slots", "prach_device.h:115 CLUSTER_LQCAP", "prach_lcluster.hip:63,466", "prach_cluster.hip:148,883"],
+        source=["prach_engine.hip lds_record_slots", "prach_device.h:132 CLUSTER_LQCAP", "prach_lcluster.hip:65,348", "prach_cluster.hip:148,747"],
         covers=["CLUSTER_LQCAP"], inside=4096, outside=4160,
         what="owned UE slots per workgroup, the reference's stream (16 bytes per slot): CLUSTER_LQCAP binds with 16 and with 32 workgroups — 4 096 slots take 150 656 bytes "
              "in a 16-workgroup cluster (1 024 groups) and 158 848 in a 32-workgroup one (2 048 groups); 4 160 slots would still fit the bytes (152 720 / 160 400)"),
