@@ -54,7 +54,58 @@ class PrachTiming(C.Structure):
                 ("launches", C.c_int32), ("workgroups", C.c_int32), ("updates", C.c_uint64),
                 ("cluster_size", C.c_int32), ("resident_limit", C.c_int32), ("fallback_trials", C.c_int32), ("spin_timeouts", C.c_int32),
                 ("rec_mode", C.c_int32), ("xcd_packed", C.c_int32), ("group_visits", C.c_uint64), ("event_ues", C.c_uint64),
-                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32)]
+                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("dist_ms", C.c_double)]
+
+
+DIST_PTC_BINS, DIST_MAX_DELAY_BINS = 256, 16384
+DIST_FIELDS = ("trials", "ues", "success", "delay_overflow", "delay_sum", "ptc_sum", "delay_max")
+
+
+class PrachDistSpec(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("delay_bins", "delay_bin_ms", "ngroups", "reserved")]
+
+
+class PrachDist(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in DIST_FIELDS[:-1]] + [("delay_max", C.c_int64)]
+
+
+class Dist:
+    """The distributions of ``ngroups`` trial groups (include/prach.h, prach_dist): ``delay_hist`` [ngroups, delay_bins] and ``ptc_hist``
+    [ngroups, 256] as numpy uint64, and one int64 array of length ngroups per scalar field of DIST_FIELDS."""
+
+    def __init__(self, ngroups, delay_bins, delay_bin_ms=1):
+        import numpy as np
+        self.delay_bins, self.delay_bin_ms, self.ngroups = int(delay_bins), int(delay_bin_ms), int(ngroups)
+        self.delay_hist = np.zeros((self.ngroups, self.delay_bins), dtype=np.uint64)
+        self.ptc_hist = np.zeros((self.ngroups, DIST_PTC_BINS), dtype=np.uint64)
+        for f in DIST_FIELDS:
+            setattr(self, f, np.zeros(self.ngroups, dtype=np.int64))
+        self.delay_max[:] = -1
+
+    def spec(self):
+        return PrachDistSpec(self.delay_bins, self.delay_bin_ms, self.ngroups, 0)
+
+    def _group(self, g):
+        return PrachDist(*[int(getattr(self, f)[g]) for f in DIST_FIELDS])
+
+    def _store(self, g, d):
+        for f in DIST_FIELDS:
+            getattr(self, f)[g] = getattr(d, f)
+
+    def _hists(self, g):
+        u64 = C.POINTER(C.c_uint64)
+        return self.delay_hist[g].ctypes.data_as(u64), self.ptc_hist[g].ctypes.data_as(u64)
+
+    def merge_group(self, g, other, og):
+        """Adds group ``og`` of ``other`` to group ``g`` (prach_dist_merge)."""
+        sp, a, b = self.spec(), self._group(g), other._group(og)
+        lib().prach_dist_merge(C.byref(sp), C.byref(a), *self._hists(g), C.byref(b), *other._hists(og))
+        self._store(g, a)
+
+    def same_as(self, other):
+        import numpy as np
+        return (self.delay_bins, self.delay_bin_ms) == (other.delay_bins, other.delay_bin_ms) and np.array_equal(self.delay_hist, other.delay_hist) and \
+            np.array_equal(self.ptc_hist, other.ptc_hist) and all(np.array_equal(getattr(self, f), getattr(other, f)) for f in DIST_FIELDS)
 
 
 class PrachError(RuntimeError):
@@ -85,6 +136,17 @@ def lib():
         L.prach_engine_set.argtypes = [vp, C.c_char_p, C.c_int64]
         L.prach_run_trials.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog))]
         L.prach_last_timing.argtypes = [vp, C.POINTER(PrachTiming)]
+        u64p = C.POINTER(C.c_uint64)
+        L.prach_run_trials_dist.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachDistSpec),
+                                            C.POINTER(C.c_int32), C.POINTER(PrachDist), u64p, u64p]
+        L.prach_dist_accumulate_logs.argtypes = [C.POINTER(PrachDistSpec), C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachDist), u64p, u64p]
+        L.prach_dist_merge.argtypes = [C.POINTER(PrachDistSpec), C.POINTER(PrachDist), u64p, u64p, C.POINTER(PrachDist), u64p, u64p]
+        L.prach_dist_merge.restype = None
+        L.prach_dist_delay_quantile.argtypes = [C.POINTER(PrachDistSpec), C.POINTER(PrachDist), u64p, C.c_double]
+        L.prach_dist_delay_quantile.restype = C.c_int64
+        L.prach_dist_format_csv.argtypes = [C.POINTER(PrachDistSpec), C.POINTER(PrachDist), u64p, u64p, C.c_char_p, C.c_char_p, C.c_size_t]
+        L.prach_dist_format_csv.restype = C.c_size_t
+        L.prach_dist_tile_ues.argtypes = []
         L.prach_cfg_defaults.argtypes = [C.POINTER(PrachCfg), C.c_int]
         L.prach_cfg_defaults.restype = None
         L.prach_cfg_validate.argtypes = [C.POINTER(PrachCfg)]
@@ -122,7 +184,8 @@ EXPORTS = ("prach_engine_create", "prach_engine_destroy", "prach_engine_set", "p
            "prach_strerror", "prach_format_logs", "prach_format_results", "prach_format_stdout",
            "prach_result_file_name", "prach_write_trial_files", "prach_noma_activation_table", "prach_format_noma_line",
            "prach_results_csv_accumulate", "prach_results_csv_row", "prach_device_glibc_stream", "prach_noma_activation_range", "prach_noma_activation_stream",
-           "prach_noma_activation_table_device")
+           "prach_noma_activation_table_device", "prach_run_trials_dist", "prach_dist_accumulate_logs", "prach_dist_merge", "prach_dist_delay_quantile",
+           "prach_dist_format_csv", "prach_dist_tile_ues")
 
 
 def make_cfg(nUE, variant=VARIANT_BETA_C, uniform=0, rng_mode=RNG_GLIBC, seed=0, stream_offset=0, **kw) -> PrachCfg:
@@ -169,6 +232,40 @@ class Engine:
         n = len(cfgs)
         arr = (PrachCfg * n)(*cfgs)
         res = (PrachResult * n)()
+        logs, lp = self._log_buffers(cfgs, want_logs)
+        rc = lib().prach_run_trials(self._h, arr, n, res, lp)
+        if rc != OK:
+            raise PrachError(rc, "(prach_run_trials)")
+        return list(res), logs
+
+    def run_trials_dist(self, cfgs, delay_bins, delay_bin_ms=1, groups=None, want_logs=False, ngroups=None):
+        """run_trials plus the distributions of access delay and preamble transmissions of the successful UEs, reduced on the device
+        (prach_run_trials_dist).  groups: the group of every trial (None: one group per trial); ngroups: the number of groups (default: the
+        largest group id + 1).  Returns (results, logs, Dist)."""
+        n = len(cfgs)
+        if ngroups is None:
+            ngroups = n if groups is None else int(max(groups)) + 1
+        return self._run_dist(cfgs, Dist(ngroups, delay_bins, delay_bin_ms), groups, want_logs)
+
+    def _run_dist(self, cfgs, dist, groups, want_logs):
+        n = len(cfgs)
+        arr = (PrachCfg * n)(*cfgs)
+        res = (PrachResult * n)()
+        logs, lp = self._log_buffers(cfgs, want_logs)
+        sp = dist.spec()
+        dd = (PrachDist * dist.ngroups)()
+        gp = None if groups is None else (C.c_int32 * n)(*[int(g) for g in groups])
+        u64 = C.POINTER(C.c_uint64)
+        rc = lib().prach_run_trials_dist(self._h, arr, n, res, lp, C.byref(sp), gp, dd, dist.delay_hist.ctypes.data_as(u64), dist.ptc_hist.ctypes.data_as(u64))
+        if rc != OK:
+            raise PrachError(rc, "(prach_run_trials_dist)")
+        for g in range(dist.ngroups):
+            dist._store(g, dd[g])
+        return list(res), logs, dist
+
+    @staticmethod
+    def _log_buffers(cfgs, want_logs):
+        n = len(cfgs)
         logs = [None] * n
         lp = None
         if want_logs:
@@ -177,10 +274,7 @@ class Engine:
                 logs[k] = (PrachUeLog * cfgs[k].nUE)()
             lp = (C.POINTER(PrachUeLog) * n)(*[C.cast(l, C.POINTER(PrachUeLog)) if l is not None else C.POINTER(PrachUeLog)()
                                                for l in logs])
-        rc = lib().prach_run_trials(self._h, arr, n, res, lp)
-        if rc != OK:
-            raise PrachError(rc, "(prach_run_trials)")
-        return list(res), logs
+        return logs, lp
 
     def device_glibc_stream(self, seed, first, n):
         import numpy as np
@@ -274,5 +368,54 @@ def results_csv(rows_of_results_texts):
                 raise PrachError(rc, "(prach_results_csv_accumulate)")
         buf = C.create_string_buffer(512)
         n = lib().prach_results_csv_row(acc, len(texts), buf, 512)
+        out += buf.raw[:n]
+    return out
+
+
+def dist_tile_ues() -> int:
+    return lib().prach_dist_tile_ues()
+
+
+def dist_from_logs(logs, delay_bins, delay_bin_ms=1, groups=None, ngroups=None) -> Dist:
+    """The host-side definition of the distributions (prach_dist_accumulate_logs): logs[k] is one trial's per-UE log — a ctypes array of PrachUeLog
+    or an int32 array of shape [nUE, 16] — added to group groups[k] (None: group k)."""
+    import numpy as np
+    n = len(logs)
+    if ngroups is None:
+        ngroups = n if groups is None else int(max(groups)) + 1
+    dist = Dist(ngroups, delay_bins, delay_bin_ms)
+    sp = dist.spec()
+    for k, lg in enumerate(logs):
+        g = k if groups is None else int(groups[k])
+        if isinstance(lg, np.ndarray):
+            a = np.ascontiguousarray(lg, dtype=np.int32).reshape(-1, 16)
+            ptr, nue = a.ctypes.data_as(C.POINTER(PrachUeLog)), a.shape[0]
+        else:
+            ptr, nue = C.cast(lg, C.POINTER(PrachUeLog)), len(lg)
+        d = dist._group(g)
+        rc = lib().prach_dist_accumulate_logs(C.byref(sp), ptr, nue, C.byref(d), *dist._hists(g))
+        if rc != OK:
+            raise PrachError(rc, "(prach_dist_accumulate_logs)")
+        dist._store(g, d)
+    return dist
+
+
+def dist_quantile(dist: Dist, g: int, q: float) -> int:
+    """Lower edge (ms) of the delay bin holding the ceil(q * success)-th smallest delay of group g; -1: no successful UE, or in the overflow."""
+    sp, d = dist.spec(), dist._group(g)
+    return int(lib().prach_dist_delay_quantile(C.byref(sp), C.byref(d), dist._hists(g)[0], q))
+
+
+def dist_csv(dist: Dist, labels=None) -> bytes:
+    """The CSV text of every group (prach_dist_format_csv), labelled labels[g] (default: the group number)."""
+    out = b""
+    sp = dist.spec()
+    for g in range(dist.ngroups):
+        label = str(g if labels is None else labels[g]).encode()
+        d = dist._group(g)
+        dh, ph = dist._hists(g)
+        need = lib().prach_dist_format_csv(C.byref(sp), C.byref(d), dh, ph, label, None, 0)
+        buf = C.create_string_buffer(need + 1)
+        n = lib().prach_dist_format_csv(C.byref(sp), C.byref(d), dh, ph, label, buf, need + 1)
         out += buf.raw[:n]
     return out

@@ -17,6 +17,9 @@
  * AveragePerformance.py over the --times seeds of every sweep point, written by prach_results_csv_*),
  * --sector-grants 1 (--program withnoma) / --nonsector 1 (--program noma): the two code paths the reference carries
  * commented out (WithNOMA:312,626-637 / NOMA.c:325-447,688);
+ * --cdf FILE [--cdf-bins N] [--cdf-bin-ms W]: the distributions of access delay and of the number of preamble transmissions of the successful UEs
+ * (prach_run_trials_dist: reduced on the device, so it works with --logs 0), one group per sweep point with the --times seeds merged, labelled nUE
+ * (default 4096 bins of 1 ms);
  * --devices LIST: the same with explicit HIP ordinals (an ordinal may repeat);
  * --gpus N: the --times x sweep grid sharded over N devices of the node by host C — one forked child per device,
  * forked BEFORE any HIP call, trials dealt by descending cost (Philox: any trial anywhere; glibc: whole seeds, because
@@ -89,8 +92,29 @@ static double now_s(void) {
  * 1024 trials (one workgroup or cluster per trial); in glibc mode `idx` holds whole seeds in grid order and the sweep of a
  * seed is chained through cfg.stream_offset like the reference's single srand() per seed (WithNOMA:219-221): one call per
  * sweep point with all the worker's seeds in it.  Returns 0 or an exit code. */
+/* A worker's distributions (--cdf): prach_dist[npts] | delay_hist[npts][bins] | ptc_hist[npts][256], one group per sweep point */
+static size_t cdf_block_bytes(const prach_dist_spec *s) {
+    return (size_t)s->ngroups * (sizeof(prach_dist) + 8 * ((size_t)s->delay_bins + PRACH_DIST_PTC_BINS));
+}
+static prach_dist *cdf_d(const prach_dist_spec *s, char *b) { (void)s; return (prach_dist *)b; }
+static uint64_t *cdf_dh(const prach_dist_spec *s, char *b) { return (uint64_t *)(b + (size_t)s->ngroups * sizeof(prach_dist)); }
+static uint64_t *cdf_ph(const prach_dist_spec *s, char *b) { return cdf_dh(s, b) + (size_t)s->ngroups * (size_t)s->delay_bins; }
+static void cdf_merge_block(const prach_dist_spec *s, char *into, char *from) {
+    for (int g = 0; g < s->ngroups; g++)
+        prach_dist_merge(s, cdf_d(s, into) + g, cdf_dh(s, into) + (size_t)g * (size_t)s->delay_bins, cdf_ph(s, into) + (size_t)g * PRACH_DIST_PTC_BINS,
+                         cdf_d(s, from) + g, cdf_dh(s, from) + (size_t)g * (size_t)s->delay_bins, cdf_ph(s, from) + (size_t)g * PRACH_DIST_PTC_BINS);
+}
+/* prach_run_trials, or with --cdf prach_run_trials_dist: the call's distributions (group = sweep point, grp[k]) are merged into the worker's block */
+static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *r, prach_ue_log *const *logs, const prach_dist_spec *cdf, const int32_t *grp,
+                    char *call_block, char *worker_block) {
+    if (!cdf) return prach_run_trials(eng, c, n, r, logs);
+    const int rc = prach_run_trials_dist(eng, c, n, r, logs, cdf, grp, cdf_d(cdf, call_block), cdf_dh(cdf, call_block), cdf_ph(cdf, call_block));
+    if (rc == PRACH_OK) cdf_merge_block(cdf, worker_block, call_block);
+    return rc;
+}
+
 static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, prach_result *res, double *lat_out, int want_logs,
-                      const char *outdir, int glibc, int npts) {
+                      const char *outdir, int glibc, int npts, const prach_dist_spec *cdf, char *cdf_block) {
     prach_engine *eng = NULL;
     int rc = prach_engine_create(device, &eng);
     if (rc != PRACH_OK) { fprintf(stderr, "prach_sim: device %d: %s\n", device, prach_strerror(rc)); return 2; }
@@ -100,17 +124,21 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
     prach_result *r = (prach_result *)malloc(sizeof(prach_result) * (size_t)(m > 0 ? m : 1));
     prach_ue_log **logs = want_logs ? (prach_ue_log **)calloc((size_t)(m > 0 ? m : 1), sizeof(prach_ue_log *)) : NULL;
     if (!c || !r || (want_logs && !logs)) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+    int32_t *grp = cdf ? (int32_t *)malloc(sizeof(int32_t) * (size_t)(m > 0 ? m : 1)) : NULL;
+    char *call_block = cdf ? (char *)malloc(cdf_block_bytes(cdf)) : NULL;
+    if (cdf && (!grp || !call_block)) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
     if (!glibc) {
         for (int a = 0; a < m; a += CH) {
             const int n = m - a < CH ? m - a : CH;
             for (int k = 0; k < n; k++) {
                 c[k] = cfgs[idx[a + k]];
+                if (cdf) grp[k] = idx[a + k] % npts;
                 if (want_logs) {
                     logs[k] = (prach_ue_log *)malloc(sizeof(prach_ue_log) * (size_t)c[k].nUE);
                     if (!logs[k]) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
                 }
             }
-            rc = prach_run_trials(eng, c, n, r, logs);
+            rc = run_call(eng, c, n, r, logs, cdf, grp, call_block, cdf_block);
             if (rc != PRACH_OK) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(rc)); return 2; }
             const double lat = now_s() - t0;
             for (int k = 0; k < n; k++) {
@@ -131,12 +159,13 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
             for (int s_ = 0; s_ < nseeds; s_++) {
                 c[s_] = cfgs[idx[s_ * npts + k]];
                 c[s_].stream_offset = offset[s_];
+                if (cdf) grp[s_] = k;
                 if (want_logs) {
                     logs[s_] = (prach_ue_log *)malloc(sizeof(prach_ue_log) * (size_t)c[s_].nUE);
                     if (!logs[s_]) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
                 }
             }
-            rc = prach_run_trials(eng, c, nseeds, r, logs);
+            rc = run_call(eng, c, nseeds, r, logs, cdf, grp, call_block, cdf_block);
             if (rc != PRACH_OK) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(rc)); return 2; }
             const double lat = now_s() - t0;
             for (int s_ = 0; s_ < nseeds; s_++) {
@@ -152,7 +181,7 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
         }
         free(offset);
     }
-    free(c); free(r); free(logs);
+    free(c); free(r); free(logs); free(grp); free(call_block);
     prach_engine_destroy(eng);
     return 0;
 }
@@ -160,7 +189,8 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
 int main(int argc, char *argv[]) {
     int randomMax = 1, variant = PRACH_VARIANT_WITHNOMA_C, rng = PRACH_RNG_GLIBC, device = 0, want_logs = 1, gpus = 1, rng_given = 0;
     int sweep_lo = 10000, sweep_hi = 100000, sweep_step = 10000; /* WithNOMA:221 */
-    const char *outdir = ".", *csv_path = NULL, *devlist = NULL;
+    const char *outdir = ".", *csv_path = NULL, *devlist = NULL, *cdf_path = NULL;
+    int cdf_bins = 4096, cdf_bin_ms = 1;
     int devs[64];
     /* --program must be known before the defaults are laid down */
     for (int i = 1; i + 1 < argc; i += 2)
@@ -235,6 +265,14 @@ int main(int argc, char *argv[]) {
             devlist = v;
         } else if (strcmp(a, "--csv") == 0) {
             csv_path = v;
+        } else if (strcmp(a, "--cdf") == 0) {
+            cdf_path = v;
+        } else if (strcmp(a, "--cdf-bins") == 0) {
+            if (atoi(v) < 1 || atoi(v) > PRACH_DIST_MAX_DELAY_BINS) die("--cdf-bins N: 1..16384 delay bins");
+            cdf_bins = atoi(v);
+        } else if (strcmp(a, "--cdf-bin-ms") == 0) {
+            if (atoi(v) < 1) die("--cdf-bin-ms W: the width of a delay bin in ms, at least 1");
+            cdf_bin_ms = atoi(v);
         } else {
             usage_and_exit();
         }
@@ -306,8 +344,18 @@ int main(int argc, char *argv[]) {
             }
     }
 
+    /* --cdf: one block of distributions per worker in a shared mapping, like the results; the parent merges them (integers: exact in any order) */
+    const prach_dist_spec cdf_spec = {cdf_bins, cdf_bin_ms, npts, 0};
+    const prach_dist_spec *const cdf = cdf_path ? &cdf_spec : NULL;
+    char *cdf_blocks = NULL;
+    if (cdf) {
+        cdf_blocks = (char *)mmap(NULL, cdf_block_bytes(cdf) * (size_t)gpus, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0); /* (zero-filled: empty groups) */
+        if (cdf_blocks == MAP_FAILED) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+    }
+#define CDF_BLOCK(w) (cdf ? cdf_blocks + cdf_block_bytes(cdf) * (size_t)(w) : NULL)
+
     if (gpus == 1) {
-        int rcw = run_worker(devs[0], cfgs, widx[0], wn[0], res, lat, want_logs, outdir, glibc, npts);
+        int rcw = run_worker(devs[0], cfgs, widx[0], wn[0], res, lat, want_logs, outdir, glibc, npts, cdf, CDF_BLOCK(0));
         if (rcw) return rcw;
     } else {
         /* one child per device, forked BEFORE this process touches HIP (a forked copy of an initialised runtime is not usable) */
@@ -316,7 +364,7 @@ int main(int argc, char *argv[]) {
         for (int w = 0; w < gpus; w++) {
             pid[w] = fork();
             if (pid[w] < 0) { perror("prach_sim: fork"); return 2; }
-            if (pid[w] == 0) _exit(run_worker(devs[w], cfgs, widx[w], wn[w], res, lat, want_logs, outdir, glibc, npts));
+            if (pid[w] == 0) _exit(run_worker(devs[w], cfgs, widx[w], wn[w], res, lat, want_logs, outdir, glibc, npts, cdf, CDF_BLOCK(w)));
         }
         int bad = 0;
         for (int w = 0; w < gpus; w++) {
@@ -328,6 +376,25 @@ int main(int argc, char *argv[]) {
         }
         free(pid);
         if (bad) return 2;
+    }
+
+    if (cdf) { /* worker 0's block takes the others'; one group per sweep point, labelled nUE */
+        for (int w = 1; w < gpus; w++) cdf_merge_block(cdf, CDF_BLOCK(0), CDF_BLOCK(w));
+        FILE *fp = fopen(cdf_path, "wb");
+        if (!fp) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_IO)); return 2; }
+        const size_t cap = 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1; /* a line: a label of at most 10 digits, three numbers, a share */
+        char *out = (char *)malloc(cap);
+        if (!out) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+        for (int k = 0; k < npts; k++) {
+            char label[16];
+            snprintf(label, sizeof label, "%d", sweep_lo + k * sweep_step);
+            const size_t n = prach_dist_format_csv(cdf, cdf_d(cdf, CDF_BLOCK(0)) + k, cdf_dh(cdf, CDF_BLOCK(0)) + (size_t)k * (size_t)cdf_bins,
+                                                   cdf_ph(cdf, CDF_BLOCK(0)) + (size_t)k * PRACH_DIST_PTC_BINS, label, out, cap);
+            if (n >= cap) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_INTERNAL)); return 2; }
+            fwrite(out, 1, n, fp);
+        }
+        free(out);
+        fclose(fp);
     }
 
     /* the parent prints in the reference's order and merges */

@@ -162,9 +162,24 @@ constexpr int NOMA_AMBIGUOUS = 77; // DevResult::hard_error: a gain comparison o
 hipError_t launch_noma_activation(const TrialDev *params, int ntrials, int maxUE, unsigned *flags, hipStream_t stream);
 // NOMA_C in the reference's own rand() stream (prach_noma_glibc.hip): one trial, host-activated arrivals + one device step per access slot
 constexpr int NOMA_GLIBC_AMBIGUOUS_RC = -1077; // run_noma_glibc_batch: a value inside the device libm's error band — run that trial on the host-activated path
+// (sink / sinks[j]: where a finished trial's distributions are added on the host, prach_run_trials_dist; null without a spec)
+struct DistSink { const prach_dist_spec *spec; prach_dist *d; uint64_t *delay_hist, *ptc_hist; }; // one group's host-side accumulators
 int run_noma_glibc_trial(hipStream_t stream, const prach_cfg &c, const int32_t *hstream, unsigned long long len, prach_result *res, prach_ue_log *logs,
-                         double *kernel_ms);
+                         double *kernel_ms, const DistSink *sink = nullptr);
 int run_noma_glibc_batch(hipStream_t stream, const prach_cfg *const *cfgs, int n, const unsigned long long *lens, prach_result *const *res, prach_ue_log *const *logs,
-                         double *kernel_ms, int *rcs);
+                         double *kernel_ms, int *rcs, const DistSink *sinks = nullptr);
+extern "C" void prach_internal_dist_add_ue(const prach_dist_spec *spec, prach_dist *d, uint64_t *delay_hist, uint64_t *ptc_hist, int32_t timer, int32_t ptc); // prach_host.c
+
+// prach_dist.hip: the distributions of a launch's accepted trials (prach_run_trials_dist).  One job per trial; a workgroup reduces one tile of
+// DIST_TILE UEs of one trial in LDS and flushes its non-zero bins into the call's buffers with 64-bit device-scope atomics.
+constexpr int DIST_TILE = 8192, DIST_THREADS = 256;
+constexpr int DIST_SCALARS = 8; // per group: success, delay_overflow, delay_sum, ptc_sum, delay_max + 1 (0: no successful UE), 3 spare
+struct DistJob {
+    const int *timers; // [nUE] the delay of a successful UE, INT_MIN otherwise
+    const int *ptc;    // form 0: [nUE] preambleTxCounter; form 1: the 32-byte records of prach::batch_kernel (word 5 of a record, low half)
+    int nUE, group, wg0, form; // wg0: the first workgroup of this job
+};
+hipError_t launch_dist_kernel(const DistJob *jobs, int njobs, int workgroups, int delay_bins, int delay_bin_ms, int scheme, unsigned long long *delay_hist,
+                              unsigned long long *ptc_hist, unsigned long long *scalars, hipStream_t stream);
 
 } // namespace prach

@@ -31,6 +31,7 @@ struct prach_engine {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev2 = nullptr, ev3 = nullptr; // around the distribution kernel of a launch (prach_timing.dist_ms)
     char *arena = nullptr;
     size_t arena_cap = 0;
     // the arena as ONE reserved virtual range that physical memory is mapped into piece by piece (hipMemAddressReserve / hipMemCreate / hipMemMap): growing it
@@ -41,6 +42,13 @@ struct prach_engine {
     std::vector<std::pair<hipMemGenericAllocationHandle_t, size_t>> vmm_parts;
     char *pinned = nullptr; // host staging mirror of the head of the arena (parameter blocks, arrival tables, stream seeds, results)
     size_t pinned_cap = 0;
+    // prach_run_trials_dist: the call's histograms and scalars (zeroed once per call, copied out once at its end — not part of the arena, which is laid out
+    // again for every launch) and the job table of one launch, pinned and on the device; all grown at the start of a call, never per launch
+    char *dist_buf = nullptr;
+    size_t dist_cap = 0;
+    DistJob *dist_jobs_h = nullptr, *dist_jobs_d = nullptr;
+    int dist_jobs_cap = 0;
+    int64_t opt_dist_scheme = 1;   // dist_kernel's binning of the preamble counts (prach_dist.hip): 0 plain LDS adds, 1 per-wavefront copies (measured fastest), 2 match and aggregate
     prach_timing last{};
     int64_t opt_stream_factor = 0; // glibc: initial draws-per-UE budget override (0 = auto)
     double draws_per_ue_seen = 0;  // glibc: the largest rand() consumption per UE of the last call's trials (0: none yet) — sizes the next call's stream windows
@@ -407,6 +415,26 @@ struct CallCtx {
     prach_ue_log *const *ue_logs;
     double kernel_ms = 0, upload_ms = 0;
     int noma_flagged = 0, noma_ambiguous = 0; // UEs recomputed on the host, trials rerun with the host-built table
+    // prach_run_trials_dist (spec == nullptr: plain prach_run_trials, nothing below is touched)
+    const prach_dist_spec *spec = nullptr;
+    const int32_t *group = nullptr; // nullable: trial k is group k
+    double dist_ms = 0;
+    unsigned long long *d_delay = nullptr, *d_ptc = nullptr, *d_scal = nullptr; // the call's device buffers: [ngroups][delay_bins], [ngroups][256], [ngroups][DIST_SCALARS]
+    std::vector<uint64_t> trials, ues;        // per group, counted on the host as launches are accepted
+    std::vector<prach_dist> host_d;           // NOMA.c in the reference's stream finishes on the host: its groups' accumulators (sized on first use)
+    std::vector<uint64_t> host_dh, host_ph;
+    int group_of(int k) const { return group ? group[k] : k; }
+    DistSink sink(int k) { // the host-side accumulators of trial k's group
+        if (host_d.empty()) {
+            prach_dist z{};
+            z.delay_max = -1;
+            host_d.assign((size_t)spec->ngroups, z);
+            host_dh.assign((size_t)spec->ngroups * (size_t)spec->delay_bins, 0);
+            host_ph.assign((size_t)spec->ngroups * PRACH_DIST_PTC_BINS, 0);
+        }
+        const size_t g = (size_t)group_of(k);
+        return DistSink{spec, &host_d[g], host_dh.data() + g * (size_t)spec->delay_bins, host_ph.data() + g * PRACH_DIST_PTC_BINS};
+    }
 };
 // How a rerun's launch differs from the first one
 struct LaunchOpts {
@@ -690,6 +718,30 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
     if (kc.rec_mode >= 0) e->last.rec_mode = kc.rec_mode;
 
     const DevResult *const drs = reinterpret_cast<const DevResult *>(H);
+    // the distributions of the trials this launch finished (the ones the loop below accepts), behind the simulation kernel on the same stream; it runs
+    // while the host turns DevResult into prach_result
+    bool dist_launched = false;
+    if (cx.spec) {
+        int njobs = 0, wgs = 0;
+        for (int k = 0; k < m; k++) {
+            const DevResult &dr = drs[k];
+            if (dr.status != PRACH_OK || (noma && dr.hard_error == NOMA_AMBIGUOUS)) continue;
+            const prach_cfg &c = cfgs[idx[k]];
+            const TrialLayout &L = LL.t[k];
+            const int g = cx.group_of(idx[k]);
+            e->dist_jobs_h[njobs++] = DistJob{reinterpret_cast<const int *>(A + L.timers), reinterpret_cast<const int *>(A + (batch ? L.rec32 : L.ptc)), c.nUE, g, wgs, batch ? 1 : 0};
+            wgs += (c.nUE + DIST_TILE - 1) / DIST_TILE;
+            cx.trials[(size_t)g]++;
+            cx.ues[(size_t)g] += (uint64_t)c.nUE;
+        }
+        if (njobs > 0) {
+            HIPCHK(hipMemcpyAsync(e->dist_jobs_d, e->dist_jobs_h, sizeof(DistJob) * (size_t)njobs, hipMemcpyHostToDevice, e->stream));
+            HIPCHK(hipEventRecord(e->ev2, e->stream));
+            HIPCHK(launch_dist_kernel(e->dist_jobs_d, njobs, wgs, cx.spec->delay_bins, cx.spec->delay_bin_ms, (int)e->opt_dist_scheme, cx.d_delay, cx.d_ptc, cx.d_scal, e->stream));
+            HIPCHK(hipEventRecord(e->ev3, e->stream));
+            dist_launched = true;
+        }
+    }
     std::vector<int32_t> timers;
     for (int k = 0; k < m; k++) {
         const prach_cfg &c = cfgs[idx[k]];
@@ -737,6 +789,12 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
         }
         if (L.logs)
             HIPCHK(hipMemcpy(cx.ue_logs[idx[k]], A + L.logs, sizeof(prach_ue_log) * (size_t)c.nUE, hipMemcpyDeviceToHost));
+    }
+    if (dist_launched) { // (the next launch lays the arena out again and reuses the pinned job table)
+        HIPCHK(hipStreamSynchronize(e->stream));
+        float dms = 0;
+        HIPCHK(hipEventElapsedTime(&dms, e->ev2, e->ev3));
+        cx.dist_ms += dms;
     }
     return PRACH_OK;
 }
@@ -855,10 +913,70 @@ static int cluster_size(const prach_engine *e, const prach_cfg *cfgs, const std:
     return G;
 }
 
-static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs) {
+// the caller's outputs of prach_run_trials_dist (spec == nullptr: prach_run_trials)
+struct DistOut { const prach_dist_spec *spec; const int32_t *group; prach_dist *dist; uint64_t *delay_hist, *ptc_hist; };
+
+// grows the call's device buffers and the job table of a launch (n: the most trials one launch can hold), zeroes the buffers on the engine's stream
+static int dist_begin(prach_engine *e, CallCtx &cx, int n) {
+    const prach_dist_spec &s = *cx.spec;
+    const size_t ng = (size_t)s.ngroups;
+    const size_t o_ptc = align_up(8 * ng * (size_t)s.delay_bins, 256), o_scal = align_up(o_ptc + 8 * ng * PRACH_DIST_PTC_BINS, 256), need = o_scal + 8 * ng * DIST_SCALARS;
+    if (need > e->dist_cap) {
+        if (e->dist_buf) HIPCHK(hipFree(e->dist_buf));
+        e->dist_buf = nullptr; e->dist_cap = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->dist_buf), need));
+        e->dist_cap = need;
+    }
+    if (n > e->dist_jobs_cap) {
+        if (e->dist_jobs_h) HIPCHK(hipHostFree(e->dist_jobs_h));
+        if (e->dist_jobs_d) HIPCHK(hipFree(e->dist_jobs_d));
+        e->dist_jobs_h = e->dist_jobs_d = nullptr; e->dist_jobs_cap = 0;
+        const int want = n + (n >> 2) + 64;
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&e->dist_jobs_h), sizeof(DistJob) * (size_t)want, hipHostMallocDefault));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->dist_jobs_d), sizeof(DistJob) * (size_t)want));
+        e->dist_jobs_cap = want;
+    }
+    if (!e->ev2) HIPCHK(hipEventCreate(&e->ev2));
+    if (!e->ev3) HIPCHK(hipEventCreate(&e->ev3));
+    cx.d_delay = reinterpret_cast<unsigned long long *>(e->dist_buf);
+    cx.d_ptc = reinterpret_cast<unsigned long long *>(e->dist_buf + o_ptc);
+    cx.d_scal = reinterpret_cast<unsigned long long *>(e->dist_buf + o_scal);
+    cx.trials.assign(ng, 0);
+    cx.ues.assign(ng, 0);
+    HIPCHK(hipMemsetAsync(e->dist_buf, 0, need, e->stream));
+    return PRACH_OK;
+}
+// ONE copy-out at the end of the call (every distribution kernel has completed: run_group waits for its own), plus what finished on the host
+static int dist_end(prach_engine *e, CallCtx &cx, const DistOut &out) {
+    const prach_dist_spec &s = *cx.spec;
+    const size_t ng = (size_t)s.ngroups;
+    std::vector<unsigned long long> sc(ng * DIST_SCALARS);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(out.delay_hist, cx.d_delay, 8 * ng * (size_t)s.delay_bins, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out.ptc_hist, cx.d_ptc, 8 * ng * PRACH_DIST_PTC_BINS, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sc.data(), cx.d_scal, 8 * sc.size(), hipMemcpyDeviceToHost));
+    for (size_t g = 0; g < ng; g++) {
+        const unsigned long long *const q = &sc[g * DIST_SCALARS];
+        prach_dist &d = out.dist[g];
+        d.trials = cx.trials[g]; d.ues = cx.ues[g]; d.success = q[0]; d.delay_overflow = q[1]; d.delay_sum = q[2]; d.ptc_sum = q[3];
+        d.delay_max = (int64_t)q[4] - 1;
+        if (!cx.host_d.empty())
+            prach_dist_merge(&s, &d, out.delay_hist + g * (size_t)s.delay_bins, out.ptc_hist + g * PRACH_DIST_PTC_BINS, &cx.host_d[g],
+                             cx.host_dh.data() + g * (size_t)s.delay_bins, cx.host_ph.data() + g * PRACH_DIST_PTC_BINS);
+    }
+    return PRACH_OK;
+}
+
+static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const DistOut *dout = nullptr) {
     for (int k = 0; k < n; k++) { // nothing is left uninitialised on an early error return
         std::memset(&results[k], 0, sizeof(results[k]));
         results[k].status = PRACH_ERR_INTERNAL;
+    }
+    if (dout) { // (the same for the distributions: empty groups)
+        const size_t ng = (size_t)dout->spec->ngroups;
+        std::memset(dout->delay_hist, 0, 8 * ng * (size_t)dout->spec->delay_bins);
+        std::memset(dout->ptc_hist, 0, 8 * ng * PRACH_DIST_PTC_BINS);
+        for (size_t g = 0; g < ng; g++) { dout->dist[g] = prach_dist{}; dout->dist[g].delay_max = -1; }
     }
     for (int k = 0; k < n; k++) {
         int v = prach_cfg_validate(&cfgs[k]);
@@ -869,6 +987,12 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
     auto t0 = std::chrono::steady_clock::now();
     e->last = prach_timing{};
     CallCtx cx{cfgs, results, ue_logs};
+    if (dout) {
+        cx.spec = dout->spec;
+        cx.group = dout->group;
+        int rc = dist_begin(e, cx, n);
+        if (rc != PRACH_OK) return rc;
+    }
     // NOMA.c in the reference's OWN rand() stream: activeUE's rejection loops make every stream position data dependent and its libm
     // calls must be the reference's, so the arrivals are activated on the host between device steps (prach_noma_glibc.hip): one trial
     // at a time, one launch per access slot — the bit-exact-vs-the-reference's-files mode, not the throughput mode
@@ -885,7 +1009,9 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
                 const unsigned long long len = window(k, attempt);
                 std::vector<int32_t> hs((size_t)len);
                 prach_glibc_stream((uint32_t)cfgs[k].seed, cfgs[k].stream_offset, len, hs.data());
-                rc = run_noma_glibc_trial(e->stream, cfgs[k], hs.data(), len, &results[k], ue_logs ? ue_logs[k] : nullptr, &cx.kernel_ms);
+                DistSink sk{};
+                if (cx.spec) sk = cx.sink(k);
+                rc = run_noma_glibc_trial(e->stream, cfgs[k], hs.data(), len, &results[k], ue_logs ? ue_logs[k] : nullptr, &cx.kernel_ms, cx.spec ? &sk : nullptr);
                 e->last.launches++;
             }
             return rc;
@@ -904,10 +1030,12 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
             std::vector<prach_result *> pr(m);
             std::vector<prach_ue_log *> pl(m);
             std::vector<int> rcs(m, PRACH_ERR_INTERNAL);
+            std::vector<DistSink> sinks;
+            if (cx.spec) for (int j = 0; j < m; j++) sinks.push_back(cx.sink(todo[j]));
             for (int j = 0; j < m; j++) { pc[j] = &cfgs[todo[j]]; lens[j] = window(todo[j], attempt); pr[j] = &results[todo[j]]; pl[j] = ue_logs ? ue_logs[todo[j]] : nullptr; }
             if (e->opt_noma_ambiguity_test) std::fill(rcs.begin(), rcs.end(), NOMA_GLIBC_AMBIGUOUS_RC); // (test hook: as if the kernel had found a value inside the band)
             else {
-                int rc = run_noma_glibc_batch(e->stream, pc.data(), m, lens.data(), pr.data(), pl.data(), &cx.kernel_ms, rcs.data());
+                int rc = run_noma_glibc_batch(e->stream, pc.data(), m, lens.data(), pr.data(), pl.data(), &cx.kernel_ms, rcs.data(), cx.spec ? sinks.data() : nullptr);
                 e->last.launches++;
                 if (rc != PRACH_OK) return rc;
             }
@@ -1011,6 +1139,11 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
     e->last.noma_host_ues = cx.noma_flagged;
     e->last.upload_ms = cx.upload_ms;
     e->last.updates = upd;
+    if (dout) {
+        int rc = dist_end(e, cx, *dout);
+        if (rc != PRACH_OK) return rc;
+        e->last.dist_ms = cx.dist_ms;
+    }
     e->last.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return worst;
 }
@@ -1037,6 +1170,11 @@ void prach_engine_destroy(prach_engine *e) {
     if (e->pinned) (void)hipHostFree(e->pinned);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
+    if (e->ev2) (void)hipEventDestroy(e->ev2);
+    if (e->ev3) (void)hipEventDestroy(e->ev3);
+    if (e->dist_buf) (void)hipFree(e->dist_buf);
+    if (e->dist_jobs_d) (void)hipFree(e->dist_jobs_d);
+    if (e->dist_jobs_h) (void)hipHostFree(e->dist_jobs_h);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -1060,6 +1198,7 @@ int prach_engine_set(prach_engine *e, const char *key, int64_t value) {
     if (std::strcmp(key, "mem_budget_mb") == 0) { if (value <= 0) return PRACH_ERR_ARG; e->mem_budget = (size_t)value << 20; return PRACH_OK; } // (test hook: split launches)
     if (std::strcmp(key, "calendar_cap") == 0) { if (value < 0) return PRACH_ERR_ARG; e->opt_calendar_cap = value; return PRACH_OK; }
     if (std::strcmp(key, "batch_waves") == 0) { if (value != 0 && value != 8 && value != 16) return PRACH_ERR_ARG; e->opt_batch_waves = value; return PRACH_OK; }
+    if (std::strcmp(key, "dist_scheme") == 0) { if (value < 0 || value > 2) return PRACH_ERR_ARG; e->opt_dist_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "xcd_pack") == 0) { e->opt_xcd_pack = value != 0; return PRACH_OK; }
     return PRACH_ERR_ARG;
 }
@@ -1136,5 +1275,20 @@ int prach_run_trials(prach_engine *e, const prach_cfg *cfgs, int n, prach_result
     if (!e || !cfgs || !results || n <= 0) return PRACH_ERR_ARG;
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs);)
 }
+
+int prach_run_trials_dist(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_dist_spec *spec,
+                          const int32_t *group, prach_dist *dist, uint64_t *delay_hist, uint64_t *ptc_hist) {
+    // (the spec is judged first: what it asks for does not depend on a device)
+    if (!cfgs || !results || n <= 0 || !spec || !dist || !delay_hist || !ptc_hist) return PRACH_ERR_ARG;
+    if (spec->delay_bins < 1 || spec->delay_bins > PRACH_DIST_MAX_DELAY_BINS || spec->delay_bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
+    if (!group && spec->ngroups != n) return PRACH_ERR_ARG;
+    if (group) for (int k = 0; k < n; k++) if (group[k] < 0 || group[k] >= spec->ngroups) return PRACH_ERR_ARG;
+    if ((uint64_t)spec->ngroups * (uint64_t)(spec->delay_bins + PRACH_DIST_PTC_BINS) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
+    if (!e) return PRACH_ERR_ARG;
+    const DistOut out{spec, group, dist, delay_hist, ptc_hist};
+    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &out);)
+}
+
+int prach_dist_tile_ues(void) { return DIST_TILE; }
 
 } // extern "C"

@@ -564,3 +564,89 @@ size_t prach_results_csv_row(const double acc[6], int nseeds, char *buf, size_t 
     if (buf && (size_t)n < cap) memcpy(buf, tmp, (size_t)n + 1);
     return (size_t)n;
 }
+
+/* ---- distributions of the successful UEs (prach_run_trials_dist) -------------------------------- */
+
+static int dist_spec_ok(const prach_dist_spec *s) {
+    return s && s->delay_bins >= 1 && s->delay_bins <= PRACH_DIST_MAX_DELAY_BINS && s->delay_bin_ms >= 1;
+}
+
+/* one successful UE (timer >= 0): what prach::dist_kernel does per lane */
+void prach_internal_dist_add_ue(const prach_dist_spec *s, prach_dist *d, uint64_t *delay_hist, uint64_t *ptc_hist, int32_t timer, int32_t ptc) {
+    const int64_t b = (int64_t)timer / s->delay_bin_ms;
+    if (b < s->delay_bins) delay_hist[b]++;
+    else d->delay_overflow++;
+    ptc_hist[(uint32_t)ptc < PRACH_DIST_PTC_BINS - 1 ? ptc : PRACH_DIST_PTC_BINS - 1]++;
+    d->success++;
+    d->delay_sum += (uint64_t)timer;
+    d->ptc_sum += (uint64_t)(uint32_t)ptc;
+    if (timer > d->delay_max) d->delay_max = timer;
+}
+
+int prach_dist_accumulate_logs(const prach_dist_spec *s, const prach_ue_log *ue, int nUE, prach_dist *d, uint64_t *delay_hist, uint64_t *ptc_hist) {
+    if (!dist_spec_ok(s) || !d || !delay_hist || !ptc_hist || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    for (int i = 0; i < nUE; i++)
+        if (ue[i].msg4Flag == 1 && ue[i].timer < 0) return PRACH_ERR_ARG;
+    if (d->trials == 0 && d->success == 0) d->delay_max = -1; /* (a zero-filled group is an empty one) */
+    for (int i = 0; i < nUE; i++)
+        if (ue[i].msg4Flag == 1) prach_internal_dist_add_ue(s, d, delay_hist, ptc_hist, ue[i].timer, ue[i].preambleTxCounter);
+    d->trials++;
+    d->ues += (uint64_t)nUE;
+    return PRACH_OK;
+}
+
+void prach_dist_merge(const prach_dist_spec *s, prach_dist *into, uint64_t *dh_into, uint64_t *ph_into, const prach_dist *from, const uint64_t *dh_from,
+                      const uint64_t *ph_from) {
+    if (!dist_spec_ok(s) || !into || !dh_into || !ph_into || !from || !dh_from || !ph_from) return;
+    const int64_t a = into->success ? into->delay_max : -1, b = from->success ? from->delay_max : -1;
+    into->trials += from->trials; into->ues += from->ues; into->success += from->success; into->delay_overflow += from->delay_overflow;
+    into->delay_sum += from->delay_sum; into->ptc_sum += from->ptc_sum;
+    into->delay_max = a > b ? a : b;
+    for (int i = 0; i < s->delay_bins; i++) dh_into[i] += dh_from[i];
+    for (int i = 0; i < PRACH_DIST_PTC_BINS; i++) ph_into[i] += ph_from[i];
+}
+
+int64_t prach_dist_delay_quantile(const prach_dist_spec *s, const prach_dist *d, const uint64_t *delay_hist, double q) {
+    if (!dist_spec_ok(s) || !d || !delay_hist || d->success == 0 || !(q >= 0.0) || q > 1.0) return -1;
+    uint64_t rank = (uint64_t)ceil(q * (double)d->success);
+    if (rank < 1) rank = 1;
+    if (rank > d->success) rank = d->success;
+    uint64_t cum = 0;
+    for (int b = 0; b < s->delay_bins; b++) {
+        cum += delay_hist[b];
+        if (cum >= rank) return (int64_t)b * s->delay_bin_ms;
+    }
+    return -1; /* in the overflow */
+}
+
+size_t prach_dist_format_csv(const prach_dist_spec *s, const prach_dist *d, const uint64_t *delay_hist, const uint64_t *ptc_hist, const char *label, char *buf,
+                             size_t cap) {
+    if (!dist_spec_ok(s) || !d || !delay_hist || !ptc_hist || !label) return 0;
+    size_t off = 0;
+    char line[512];
+    const double tot = d->success ? (double)d->success : 1.0;
+    uint64_t cum = 0;
+#define DIST_EMIT(...)                                                          \
+    do {                                                                        \
+        const int n_ = snprintf(line, sizeof line, __VA_ARGS__);                \
+        if (n_ < 0 || (size_t)n_ >= sizeof line) return 0;                      \
+        if (buf && off + (size_t)n_ < cap) memcpy(buf + off, line, (size_t)n_); \
+        off += (size_t)n_;                                                      \
+    } while (0)
+    for (int b = 0; b < s->delay_bins; b++) {
+        if (!delay_hist[b]) continue;
+        cum += delay_hist[b];
+        DIST_EMIT("%.200s,delay,%lld,%llu,%.6f\n", label, (long long)b * s->delay_bin_ms, (unsigned long long)delay_hist[b], (double)cum / tot);
+    }
+    if (d->delay_overflow) DIST_EMIT("%.200s,delay,overflow,%llu,1.000000\n", label, (unsigned long long)d->delay_overflow);
+    cum = 0;
+    for (int k = 0; k < PRACH_DIST_PTC_BINS; k++) {
+        if (!ptc_hist[k]) continue;
+        cum += ptc_hist[k];
+        DIST_EMIT("%.200s,ptx,%d,%llu,%.6f\n", label, k, (unsigned long long)ptc_hist[k], (double)cum / tot);
+    }
+#undef DIST_EMIT
+    if (buf && off < cap) buf[off] = 0;
+    else if (buf && cap) buf[0] = 0; /* (did not fit: nothing partial is left behind as a string) */
+    return off;
+}

@@ -423,8 +423,14 @@ __global__ __launch_bounds__(WG_THREADS) void noma_glibc_trial_kernel(const Tria
 
 // saveResult (NOMA.c:618-625) and the logged fields from the final UE records
 static void noma_glibc_finish(const prach_cfg &c, const NUe *hue, unsigned long long pos, int nSuccess, int time_exit, unsigned long long steps, int activeCheck,
-                              int32_t nAccess, prach_result *res, prach_ue_log *logs) {
+                              int32_t nAccess, prach_result *res, prach_ue_log *logs, const DistSink *sink) {
     const int nUE = c.nUE;
+    if (sink) { // prach_run_trials_dist: this trial's successful UEs, as prach_dist_accumulate_logs counts them from the log written below
+        for (int i = 0; i < nUE; i++)
+            if (hue[i].RA == 1) prach_internal_dist_add_ue(sink->spec, sink->d, sink->delay_hist, sink->ptc_hist, hue[i].timer, hue[i].nTxPreamble);
+        sink->d->trials++;
+        sink->d->ues += (uint64_t)nUE;
+    }
     long long delay = 0;
     int nTxP = 0, failed = 0;
     for (int i = 0; i < nUE; i++) {
@@ -460,7 +466,7 @@ static void noma_glibc_finish(const prach_cfg &c, const NUe *hue, unsigned long 
 // Returns PRACH_OK, PRACH_ERR_STREAM (window too small: the caller retries with a larger one) or a device error.
 // This is the slot-by-slot form (the arrivals activated by the host between the launches); run_noma_glibc_batch below is the single-launch form.
 int run_noma_glibc_trial(hipStream_t stream, const prach_cfg &c, const int32_t *hstream, unsigned long long len, prach_result *res, prach_ue_log *logs,
-                         double *kernel_ms) {
+                         double *kernel_ms, const DistSink *sink) {
 #define NHIP(expr)                                                                                                            \
     do {                                                                                                                      \
         hipError_t e_ = (expr);                                                                                               \
@@ -535,7 +541,7 @@ int run_noma_glibc_trial(hipStream_t stream, const prach_cfg &c, const int32_t *
         float ms = 0;
         NHIP(hipEventElapsedTime(&ms, ev0, ev1));
         if (kernel_ms) *kernel_ms += ms;
-        noma_glibc_finish(c, hue.data(), pos, nSuccess, time_exit, steps, activeCheck, nAccess, res, logs);
+        noma_glibc_finish(c, hue.data(), pos, nSuccess, time_exit, steps, activeCheck, nAccess, res, logs, sink);
     }
 done:
     if (d_ue) (void)hipFree(d_ue);
@@ -554,7 +560,7 @@ done:
 // [stream_offset, + lens[j]) generated on the device before it.  rcs[j]: PRACH_OK (res[j] / logs[j] filled), PRACH_ERR_STREAM (window too small),
 // NOMA_GLIBC_AMBIGUOUS_RC (a value inside the device math library's error band: run that trial slot by slot, run_noma_glibc_trial) or a device error.
 int run_noma_glibc_batch(hipStream_t stream, const prach_cfg *const *cfgs, int n, const unsigned long long *lens, prach_result *const *res, prach_ue_log *const *logs,
-                         double *kernel_ms, int *rcs) {
+                         double *kernel_ms, int *rcs, const DistSink *sinks) {
 #define BHIP(expr)                                                                                                            \
     do {                                                                                                                      \
         hipError_t e_ = (expr);                                                                                               \
@@ -634,7 +640,7 @@ int run_noma_glibc_batch(hipStream_t stream, const prach_cfg *const *cfgs, int n
         if (tc.status != PRACH_OK) { rcs[j] = tc.status; continue; }
         hue.resize((size_t)c.nUE);
         BHIP(hipMemcpy(hue.data(), dbuf + off[j].ue, sizeof(NUe) * (size_t)c.nUE, hipMemcpyDeviceToHost));
-        noma_glibc_finish(c, hue.data(), tc.pos, tc.nSuccess, tc.time_exit, tc.steps, tc.activeCheck, off[j].nAccess, res[j], logs ? logs[j] : nullptr);
+        noma_glibc_finish(c, hue.data(), tc.pos, tc.nSuccess, tc.time_exit, tc.steps, tc.activeCheck, off[j].nAccess, res[j], logs ? logs[j] : nullptr, sinks ? &sinks[j] : nullptr);
         rcs[j] = PRACH_OK;
     }
 done:

@@ -74,6 +74,31 @@ def allreduce_aggregates(agg: np.ndarray, device=None):
     return t.cpu().numpy()
 
 
+def allreduce_dist(d, device=None):
+    """Merges the distributions (a `Dist` of the package: same groups, bins and width on every rank) across ranks, in place: ONE int64 sum all-reduce of the
+    concatenated block — both histograms and the summed scalars — and delay_max by a max all-reduce of ngroups values.  Integers: exact in any order."""
+    import torch
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return d
+    from . import DIST_FIELDS
+    sums = [f for f in DIST_FIELDS if f != "delay_max"]
+    block = np.concatenate([d.delay_hist.astype(np.int64).ravel(), d.ptc_hist.astype(np.int64).ravel()] + [getattr(d, f).astype(np.int64) for f in sums])
+    t, mx = torch.from_numpy(block), torch.from_numpy(d.delay_max.astype(np.int64))
+    if device is not None:
+        t, mx = t.to(device), mx.to(device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    dist.all_reduce(mx, op=dist.ReduceOp.MAX)
+    block = t.cpu().numpy()
+    nd, npc, g = d.delay_hist.size, d.ptc_hist.size, d.ngroups
+    d.delay_hist[...] = block[:nd].reshape(d.delay_hist.shape).astype(np.uint64)
+    d.ptc_hist[...] = block[nd:nd + npc].reshape(d.ptc_hist.shape).astype(np.uint64)
+    for k, f in enumerate(sums):
+        getattr(d, f)[:] = block[nd + npc + k * g:nd + npc + (k + 1) * g]
+    d.delay_max[:] = mx.cpu().numpy()
+    return d
+
+
 ROW_BYTES = 256  # a row = trial index (8 bytes) + kind (1) + payload length (2) + up to ROW_PAYLOAD bytes of text
 ROW_PAYLOAD = ROW_BYTES - 11  # (Beta.c's six-line Results.txt is ~45 bytes, RandomAccessWithNOMA's eight lines ~115 at nUE = 100 000)
 

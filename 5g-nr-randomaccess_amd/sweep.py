@@ -32,6 +32,9 @@ def main(argv=None):
     ap.add_argument("--sweep", default="10000:100000:10000")
     ap.add_argument("--out", default=".")
     ap.add_argument("--backend", default="nccl")
+    ap.add_argument("--cdf", default=None, help="write the delay / preamble-count distributions of the successful UEs, one group per sweep point, to this CSV file")
+    ap.add_argument("--cdf-bins", type=int, default=4096)
+    ap.add_argument("--cdf-bin-ms", type=int, default=1)
     ap.add_argument("--same-device", action="store_true", help="rehearsal on one GPU: every rank uses cuda:0")
     args = ap.parse_args(argv)
 
@@ -63,8 +66,15 @@ def main(argv=None):
     t0 = time.perf_counter()
     res = []
     CH = 1024  # trials per call: bounds the device arena (2.7 GB per 1024 trials of the sweep)
+    cdf = pkg.Dist(len(points), args.cdf_bins, args.cdf_bin_ms) if args.cdf else None
     for a in range(0, len(mine), CH):
-        r, _ = eng.run_trials([cfgs[i] for i in mine[a:a + CH]])
+        part = mine[a:a + CH]
+        if cdf is None:
+            r, _ = eng.run_trials([cfgs[i] for i in part])
+        else:  # the distributions come from the device with the results: no per-UE log is copied
+            r, _, d = eng.run_trials_dist([cfgs[i] for i in part], args.cdf_bins, args.cdf_bin_ms, groups=[i % len(points) for i in part], ngroups=len(points))
+            for k in range(len(points)):
+                cdf.merge_group(k, d, k)
         res.extend(r)
     dt = time.perf_counter() - t0
     agg = distmod.aggregate_rows([cfgs[i] for i in mine], res, points)
@@ -75,6 +85,11 @@ def main(argv=None):
     if variant == pkg.VARIANT_BETA_C:
         rows = [(i, pkg.format_results(cfgs[i], r, 0.0).decode()) for i, r in zip(mine, res)]
         allrows = distmod.gather_trial_rows(rows, dst=0, device=dev if (world > 1 and args.backend == "nccl") else None)
+    if cdf is not None:
+        distmod.allreduce_dist(cdf, device=dev if (world > 1 and args.backend == "nccl") else None)
+        if rank == 0:
+            with open(args.cdf, "wb") as f:
+                f.write(pkg.dist_csv(cdf, labels=points))
     if rank == 0:
         fi = {n: k for k, n in enumerate(distmod.AGG_FIELDS)}
         summary = {"program": args.program, "times": args.times, "points": points, "world": world,

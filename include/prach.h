@@ -129,6 +129,7 @@ typedef struct prach_timing {
     int32_t trial_kernel_reruns; /* of fallback_trials: trials that were (also) rerun on the one-workgroup, index-ordered trial_kernel */
     int32_t noma_host_ues;       /* NOMA_C, Philox: UEs of the device-built activeUE table that the host recomputed with its libm (a value inside the
                                     device math library's error band of a rounding / comparison boundary: ~1e-6 of the UEs) */
+    double dist_ms;              /* HIP-event time of the distribution kernel launches (prach_run_trials_dist) of the last call; 0 without a spec */
 } prach_timing;
 
 typedef struct prach_engine prach_engine;
@@ -143,6 +144,38 @@ void prach_engine_destroy(prach_engine *);
 int prach_run_trials(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results,
                      prach_ue_log *const *ue_logs);
 int prach_last_timing(const prach_engine *, prach_timing *out);
+
+/* Distributions per trial group, built on the device: the histogram of the access delay (`timer`) and of the number of preamble
+ * transmissions (`preambleTxCounter`) of the successful UEs (msg4Flag == 1; NOMA_C: RA == 1 and nTxPreamble) — the CDFs TR 37.868 and the
+ * papers present next to the scalar results.  prach::dist_kernel (csrc/prach_dist.hip) reduces the per-UE state a simulation kernel leaves on
+ * the device, so no per-UE log crosses the bus.  Integers only: merging is order-free and exact. */
+#define PRACH_DIST_PTC_BINS        256     /* bin min(preambleTxCounter, 255) */
+#define PRACH_DIST_MAX_DELAY_BINS  16384
+
+typedef struct prach_dist_spec {
+    int32_t delay_bins;    /* 1 .. PRACH_DIST_MAX_DELAY_BINS */
+    int32_t delay_bin_ms;  /* >= 1; bin b counts successful UEs with b*w <= timer < (b+1)*w */
+    int32_t ngroups;       /* number of output distributions */
+    int32_t reserved;      /* 0 */
+} prach_dist_spec;
+
+typedef struct prach_dist {          /* one per group */
+    uint64_t trials;                 /* trials accumulated (status PRACH_OK) */
+    uint64_t ues;                    /* sum of their nUE */
+    uint64_t success;                /* UEs counted in the histograms (msg4Flag == 1) */
+    uint64_t delay_overflow;         /* successful UEs with timer >= delay_bins * delay_bin_ms (in no delay bin) */
+    uint64_t delay_sum, ptc_sum;     /* sum of timer / of preambleTxCounter over the successful UEs, unbinned */
+    int64_t  delay_max;              /* -1 if success == 0 */
+} prach_dist;
+
+/* prach_run_trials plus the distributions: trial k is added to group group[k] (in [0, ngroups); group == NULL: trial k is group k and ngroups
+ * must equal n).  delay_hist[ngroups * delay_bins], ptc_hist[ngroups * PRACH_DIST_PTC_BINS] and dist[ngroups] are caller-owned and OVERWRITTEN.
+ * A trial whose final status is not PRACH_OK contributes nothing; a trial the engine reruns contributes once, from the launch whose result is kept.
+ * PRACH_ERR_ARG: a NULL output, a bin count or width out of range, a group id out of range, NULL group with ngroups != n;
+ * PRACH_ERR_UNSUPPORTED: ngroups * (delay_bins + 256) > 2^27 words (1 GiB of device buffer). */
+int prach_run_trials_dist(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results,
+                          prach_ue_log *const *ue_logs, const prach_dist_spec *spec, const int32_t *group,
+                          prach_dist *dist, uint64_t *delay_hist, uint64_t *ptc_hist);
 
 /* engine tunables; none changes a result, all are covered by parity tests:
  *   "cluster"       workgroups cooperating on one trial (1..64; 0 = auto)
@@ -160,6 +193,8 @@ int prach_last_timing(const prach_engine *, prach_timing *out);
  *   "batch_waves"   prach::batch_kernel's workgroup shape: 8 (512 threads, two trials per CU), 16 (1024 threads), 0 = chosen per launch
  *   "plain_arena"   1: the device arena is one hipMalloc allocation, re-allocated when it grows (before the first call only; diagnostic)
  *   "mem_budget_mb" arena megabytes one launch may take (default: three quarters of the device's memory): a call that needs more runs as several launches
+ *   "dist_scheme"   prach::dist_kernel's binning of the preamble counts: 0 one LDS atomic per UE, 1 the same into per-wavefront copies of the 256 bins
+ *                   (the default: measured fastest), 2 one LDS atomic per distinct value of a wavefront (match and aggregate)
  *   "calendar_cap", "vmm_fail_after", "noma_ambiguity_test", "noma_host_activation"   test hooks (prach_engine.hip) */
 int prach_engine_set(prach_engine *, const char *key, int64_t value);
 
@@ -204,6 +239,22 @@ int prach_noma_activation_table_device(prach_engine *, const prach_cfg *cfg, int
 int prach_noma_activation_stream(const prach_cfg *cfg, const int32_t *stream, uint64_t *pos, uint64_t avail, int32_t *preamble0, int32_t *sector,
                                  double *gain, double *lgain);
 size_t prach_format_noma_line(const prach_cfg *, const prach_result *, char *buf, size_t cap); /* NOMA.c:606-632 */
+
+/* Distributions, host side (no device needed).  d / delay_hist / ptc_hist: ONE group (delay_bins and PRACH_DIST_PTC_BINS entries).
+ * prach_dist_accumulate_logs ADDS one trial's per-UE log to a group: the definition prach::dist_kernel equals, integer for integer
+ * (PRACH_ERR_ARG: a bad spec, or a successful UE with a negative timer — nothing has been added then). */
+int prach_dist_accumulate_logs(const prach_dist_spec *, const prach_ue_log *ue, int nUE, prach_dist *d, uint64_t *delay_hist, uint64_t *ptc_hist);
+/* counts are summed, delay_max is the maximum */
+void prach_dist_merge(const prach_dist_spec *, prach_dist *into, uint64_t *dh_into, uint64_t *ph_into, const prach_dist *from, const uint64_t *dh_from,
+                      const uint64_t *ph_from);
+/* lower edge (ms) of the first delay bin whose cumulative count reaches max(1, ceil(q * success)); -1 if success == 0 or that rank lies in the overflow */
+int64_t prach_dist_delay_quantile(const prach_dist_spec *, const prach_dist *, const uint64_t *delay_hist, double q);
+/* one group as text: `label,delay,<lower edge ms>,<count>,<cumulative share %.6f>` per non-empty delay bin, `label,delay,overflow,<count>,1.000000` if the
+ * overflow is non-zero, then `label,ptx,<k>,<count>,<cumulative share>` per non-empty preamble-count bin; lines end in \n.  Returns the length needed
+ * (without the terminating 0); the text is written only if it fits cap with its terminator. */
+size_t prach_dist_format_csv(const prach_dist_spec *, const prach_dist *, const uint64_t *delay_hist, const uint64_t *ptc_hist, const char *label, char *buf,
+                             size_t cap);
+int prach_dist_tile_ues(void); /* UEs of one trial that one workgroup of prach::dist_kernel reduces (tests place sizes around it) */
 
 /* Text surfaces, byte-compatible with the reference (latency values excepted) */
 size_t prach_format_logs(const prach_ue_log *ue, int nUE, char *buf, size_t cap);           /* Beta.c:501 */

@@ -92,7 +92,7 @@ def diff(old, new):
     lines = []
     for k in sorted(set(old) | set(new)):
         a, b = old.get(k), new.get(k)
-        if a == b:
+        if a == b or (a is None and not b):  # (a kernel that is not on file and has no site has no table to put on file: the same as listed with {})
             continue
         if a is None or b is None:
             lines.append(f"{k}: {'new kernel' if a is None else 'kernel gone'} ({a} -> {b})")
