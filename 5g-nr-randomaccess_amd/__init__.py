@@ -54,7 +54,7 @@ class PrachTiming(C.Structure):
                 ("launches", C.c_int32), ("workgroups", C.c_int32), ("updates", C.c_uint64),
                 ("cluster_size", C.c_int32), ("resident_limit", C.c_int32), ("fallback_trials", C.c_int32), ("spin_timeouts", C.c_int32),
                 ("rec_mode", C.c_int32), ("xcd_packed", C.c_int32), ("group_visits", C.c_uint64), ("event_ues", C.c_uint64),
-                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("dist_ms", C.c_double)]
+                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("dist_ms", C.c_double), ("timeline_ms", C.c_double)]
 
 
 DIST_PTC_BINS, DIST_MAX_DELAY_BINS = 256, 16384
@@ -108,6 +108,58 @@ class Dist:
             np.array_equal(self.ptc_hist, other.ptc_hist) and all(np.array_equal(getattr(self, f), getattr(other, f)) for f in DIST_FIELDS)
 
 
+TIMELINE_MAX_BINS = 65536
+TIMELINE_SERIES = ("arrivals", "success", "sojourn_sum", "timer_sum", "done")
+TIMELINE_FIELDS = ("trials", "ues", "arrived", "success", "restarted", "arrival_overflow", "done_overflow", "sojourn_sum", "timer_sum", "done_max")
+
+
+class PrachTimelineSpec(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("bins", "bin_ms", "ngroups", "reserved")]
+
+
+class PrachTimeline(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in TIMELINE_FIELDS[:-1]] + [("done_max", C.c_int64)]
+
+
+class Timeline:
+    """The timelines of ``ngroups`` trial groups (include/prach.h, prach_timeline): ``series[name]`` [ngroups, bins] as numpy uint64 for every name of
+    TIMELINE_SERIES (bin b covers [b * bin_ms, (b + 1) * bin_ms)), and ``scalars[field]``, one int64 array of length ngroups per field of
+    TIMELINE_FIELDS.  (Two dicts: `success` and `sojourn_sum` name a series and a scalar.)"""
+
+    def __init__(self, ngroups, bins, bin_ms=1):
+        import numpy as np
+        self.bins, self.bin_ms, self.ngroups = int(bins), int(bin_ms), int(ngroups)
+        self.series = {n: np.zeros((self.ngroups, self.bins), dtype=np.uint64) for n in TIMELINE_SERIES}
+        self.scalars = {f: np.zeros(self.ngroups, dtype=np.int64) for f in TIMELINE_FIELDS}
+        self.scalars["done_max"][:] = -1
+
+    def spec(self):
+        return PrachTimelineSpec(self.bins, self.bin_ms, self.ngroups, 0)
+
+    def _group(self, g):
+        return PrachTimeline(*[int(self.scalars[f][g]) for f in TIMELINE_FIELDS])
+
+    def _store(self, g, t):
+        for f in TIMELINE_FIELDS:
+            self.scalars[f][g] = getattr(t, f)
+
+    def _series(self, g):
+        """The five series of group g as the uint64_t *[5] the C side takes."""
+        u64 = C.POINTER(C.c_uint64)
+        return (u64 * 5)(*[self.series[n][g].ctypes.data_as(u64) for n in TIMELINE_SERIES])
+
+    def merge_group(self, g, other, og):
+        """Adds group ``og`` of ``other`` to group ``g`` (prach_timeline_merge)."""
+        sp, a, b = self.spec(), self._group(g), other._group(og)
+        lib().prach_timeline_merge(C.byref(sp), C.byref(a), self._series(g), C.byref(b), other._series(og))
+        self._store(g, a)
+
+    def same_as(self, other):
+        import numpy as np
+        return (self.bins, self.bin_ms) == (other.bins, other.bin_ms) and all(np.array_equal(self.series[n], other.series[n]) for n in TIMELINE_SERIES) and \
+            all(np.array_equal(self.scalars[f], other.scalars[f]) for f in TIMELINE_FIELDS)
+
+
 class PrachError(RuntimeError):
     def __init__(self, status, what=""):
         self.status = status
@@ -147,6 +199,17 @@ def lib():
         L.prach_dist_format_csv.argtypes = [C.POINTER(PrachDistSpec), C.POINTER(PrachDist), u64p, u64p, C.c_char_p, C.c_char_p, C.c_size_t]
         L.prach_dist_format_csv.restype = C.c_size_t
         L.prach_dist_tile_ues.argtypes = []
+        u64pp = C.POINTER(u64p)
+        L.prach_run_trials_timeline.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachTimelineSpec),
+                                                C.POINTER(C.c_int32), C.POINTER(PrachTimeline), u64p, u64p, u64p, u64p, u64p]
+        L.prach_timeline_accumulate_logs.argtypes = [C.POINTER(PrachTimelineSpec), C.POINTER(PrachCfg), C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachTimeline),
+                                                     u64p, u64p, u64p, u64p, u64p]
+        L.prach_timeline_merge.argtypes = [C.POINTER(PrachTimelineSpec), C.POINTER(PrachTimeline), u64pp, C.POINTER(PrachTimeline), u64pp]
+        L.prach_timeline_merge.restype = None
+        L.prach_timeline_format_csv.argtypes = [C.POINTER(PrachTimelineSpec), C.POINTER(PrachTimeline), u64pp, C.c_char_p, C.c_char_p, C.c_size_t]
+        L.prach_timeline_format_csv.restype = C.c_size_t
+        L.prach_timeline_tile_ues.argtypes = []
+        L.prach_timeline_window_bins.argtypes = []
         L.prach_cfg_defaults.argtypes = [C.POINTER(PrachCfg), C.c_int]
         L.prach_cfg_defaults.restype = None
         L.prach_cfg_validate.argtypes = [C.POINTER(PrachCfg)]
@@ -185,7 +248,8 @@ EXPORTS = ("prach_engine_create", "prach_engine_destroy", "prach_engine_set", "p
            "prach_result_file_name", "prach_write_trial_files", "prach_noma_activation_table", "prach_format_noma_line",
            "prach_results_csv_accumulate", "prach_results_csv_row", "prach_device_glibc_stream", "prach_noma_activation_range", "prach_noma_activation_stream",
            "prach_noma_activation_table_device", "prach_run_trials_dist", "prach_dist_accumulate_logs", "prach_dist_merge", "prach_dist_delay_quantile",
-           "prach_dist_format_csv", "prach_dist_tile_ues")
+           "prach_dist_format_csv", "prach_dist_tile_ues", "prach_run_trials_timeline", "prach_timeline_accumulate_logs", "prach_timeline_merge",
+           "prach_timeline_format_csv", "prach_timeline_tile_ues", "prach_timeline_window_bins")
 
 
 def make_cfg(nUE, variant=VARIANT_BETA_C, uniform=0, rng_mode=RNG_GLIBC, seed=0, stream_offset=0, **kw) -> PrachCfg:
@@ -262,6 +326,28 @@ class Engine:
         for g in range(dist.ngroups):
             dist._store(g, dd[g])
         return list(res), logs, dist
+
+    def run_trials_timeline(self, cfgs, bins, bin_ms=1, groups=None, want_logs=False, ngroups=None):
+        """run_trials plus the timelines per trial group — arrivals, successes, sojourn and timer sums by arrival time, completions by completion time —
+        reduced on the device from the per-UE log records the simulation kernels leave there (prach_run_trials_timeline; Beta.c and
+        RandomAccessWithNOMA trials only).  groups / ngroups / want_logs as in run_trials_dist.  Returns (results, logs, Timeline)."""
+        n = len(cfgs)
+        if ngroups is None:
+            ngroups = n if groups is None else int(max(groups)) + 1
+        tl = Timeline(ngroups, bins, bin_ms)
+        arr = (PrachCfg * n)(*cfgs)
+        res = (PrachResult * n)()
+        logs, lp = self._log_buffers(cfgs, want_logs)
+        sp = tl.spec()
+        tt = (PrachTimeline * tl.ngroups)()
+        gp = None if groups is None else (C.c_int32 * n)(*[int(g) for g in groups])
+        u64 = C.POINTER(C.c_uint64)
+        rc = lib().prach_run_trials_timeline(self._h, arr, n, res, lp, C.byref(sp), gp, tt, *[tl.series[s].ctypes.data_as(u64) for s in TIMELINE_SERIES])
+        if rc != OK:
+            raise PrachError(rc, "(prach_run_trials_timeline)")
+        for g in range(tl.ngroups):
+            tl._store(g, tt[g])
+        return list(res), logs, tl
 
     @staticmethod
     def _log_buffers(cfgs, want_logs):
@@ -417,5 +503,52 @@ def dist_csv(dist: Dist, labels=None) -> bytes:
         need = lib().prach_dist_format_csv(C.byref(sp), C.byref(d), dh, ph, label, None, 0)
         buf = C.create_string_buffer(need + 1)
         n = lib().prach_dist_format_csv(C.byref(sp), C.byref(d), dh, ph, label, buf, need + 1)
+        out += buf.raw[:n]
+    return out
+
+
+def timeline_tile_ues() -> int:
+    return lib().prach_timeline_tile_ues()
+
+
+def timeline_window_bins() -> int:
+    return lib().prach_timeline_window_bins()
+
+
+def timeline_from_logs(cfgs, logs, bins, bin_ms=1, groups=None, ngroups=None) -> Timeline:
+    """The host-side definition of the timelines (prach_timeline_accumulate_logs): logs[k] is the per-UE log of the trial with config cfgs[k] — a ctypes
+    array of PrachUeLog or an int32 array of shape [nUE, 16] — added to group groups[k] (None: group k)."""
+    import numpy as np
+    n = len(logs)
+    if ngroups is None:
+        ngroups = n if groups is None else int(max(groups)) + 1
+    tl = Timeline(ngroups, bins, bin_ms)
+    sp = tl.spec()
+    u64 = C.POINTER(C.c_uint64)
+    for k, lg in enumerate(logs):
+        g = k if groups is None else int(groups[k])
+        if isinstance(lg, np.ndarray):
+            a = np.ascontiguousarray(lg, dtype=np.int32).reshape(-1, 16)
+            ptr, nue = a.ctypes.data_as(C.POINTER(PrachUeLog)), a.shape[0]
+        else:
+            ptr, nue = C.cast(lg, C.POINTER(PrachUeLog)), len(lg)
+        t = tl._group(g)
+        rc = lib().prach_timeline_accumulate_logs(C.byref(sp), C.byref(cfgs[k]), ptr, nue, C.byref(t), *[tl.series[s][g].ctypes.data_as(u64) for s in TIMELINE_SERIES])
+        if rc != OK:
+            raise PrachError(rc, "(prach_timeline_accumulate_logs)")
+        tl._store(g, t)
+    return tl
+
+
+def timeline_csv(tl: Timeline, labels=None) -> bytes:
+    """The CSV text of every group (prach_timeline_format_csv), labelled labels[g] (default: the group number)."""
+    out = b""
+    sp = tl.spec()
+    for g in range(tl.ngroups):
+        label = str(g if labels is None else labels[g]).encode()
+        t, ser = tl._group(g), tl._series(g)
+        need = lib().prach_timeline_format_csv(C.byref(sp), C.byref(t), ser, label, None, 0)
+        buf = C.create_string_buffer(need + 1)
+        n = lib().prach_timeline_format_csv(C.byref(sp), C.byref(t), ser, label, buf, need + 1)
         out += buf.raw[:n]
     return out

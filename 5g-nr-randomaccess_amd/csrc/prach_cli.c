@@ -20,6 +20,9 @@
  * --cdf FILE [--cdf-bins N] [--cdf-bin-ms W]: the distributions of access delay and of the number of preamble transmissions of the successful UEs
  * (prach_run_trials_dist: reduced on the device, so it works with --logs 0), one group per sweep point with the --times seeds merged, labelled nUE
  * (default 4096 bins of 1 ms);
+ * --timeline FILE [--timeline-bin MS]: arrivals, successes, sojourn and timer sums by arrival time and completions by completion time
+ * (prach_run_trials_timeline: reduced on the device, so it works with --logs 0), one group per sweep point with the --times seeds merged, labelled nUE;
+ * bins of MS ms (default 5) that cover the whole horizon, maxTime + 6 ms; --program beta|withnoma only, and not together with --cdf (one reduction per call);
  * --devices LIST: the same with explicit HIP ordinals (an ordinal may repeat);
  * --gpus N: the --times x sweep grid sharded over N devices of the node by host C — one forked child per device,
  * forked BEFORE any HIP call, trials dealt by descending cost (Philox: any trial anywhere; glibc: whole seeds, because
@@ -104,9 +107,34 @@ static void cdf_merge_block(const prach_dist_spec *s, char *into, char *from) {
         prach_dist_merge(s, cdf_d(s, into) + g, cdf_dh(s, into) + (size_t)g * (size_t)s->delay_bins, cdf_ph(s, into) + (size_t)g * PRACH_DIST_PTC_BINS,
                          cdf_d(s, from) + g, cdf_dh(s, from) + (size_t)g * (size_t)s->delay_bins, cdf_ph(s, from) + (size_t)g * PRACH_DIST_PTC_BINS);
 }
-/* prach_run_trials, or with --cdf prach_run_trials_dist: the call's distributions (group = sweep point, grp[k]) are merged into the worker's block */
-static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *r, prach_ue_log *const *logs, const prach_dist_spec *cdf, const int32_t *grp,
+/* A worker's timelines (--timeline): prach_timeline[npts] | five series [npts][bins] each (arrivals, success, sojourn_sum, timer_sum, done) */
+static size_t tl_block_bytes(const prach_timeline_spec *s) { return (size_t)s->ngroups * (sizeof(prach_timeline) + 5 * 8 * (size_t)s->bins); }
+static prach_timeline *tl_t(char *b) { return (prach_timeline *)b; }
+static uint64_t *tl_series(const prach_timeline_spec *s, char *b, int q, int g) {
+    return (uint64_t *)(b + (size_t)s->ngroups * sizeof(prach_timeline)) + ((size_t)q * (size_t)s->ngroups + (size_t)g) * (size_t)s->bins;
+}
+static void tl_merge_block(const prach_timeline_spec *s, char *into, char *from) {
+    for (int g = 0; g < s->ngroups; g++) {
+        uint64_t *a[5];
+        const uint64_t *b[5];
+        for (int q = 0; q < 5; q++) { a[q] = tl_series(s, into, q, g); b[q] = tl_series(s, from, q, g); }
+        prach_timeline_merge(s, tl_t(into) + g, a, tl_t(from) + g, b);
+    }
+}
+/* what a call reduces on the device next to its results: the distributions (--cdf), the timelines (--timeline) or nothing */
+typedef struct reduce_spec { const prach_dist_spec *cdf; const prach_timeline_spec *tl; } reduce_spec;
+
+/* prach_run_trials, or with --timeline prach_run_trials_timeline, or with --cdf prach_run_trials_dist: the call's distributions (group = sweep point, grp[k]) are merged into the worker's block */
+static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *r, prach_ue_log *const *logs, reduce_spec red, const int32_t *grp,
                     char *call_block, char *worker_block) {
+    const prach_dist_spec *const cdf = red.cdf;
+    if (red.tl) {
+        const prach_timeline_spec *const s = red.tl;
+        const int rc = prach_run_trials_timeline(eng, c, n, r, logs, s, grp, tl_t(call_block), tl_series(s, call_block, 0, 0), tl_series(s, call_block, 1, 0),
+                                                 tl_series(s, call_block, 2, 0), tl_series(s, call_block, 3, 0), tl_series(s, call_block, 4, 0));
+        if (rc == PRACH_OK) tl_merge_block(s, worker_block, call_block);
+        return rc;
+    }
     if (!cdf) return prach_run_trials(eng, c, n, r, logs);
     const int rc = prach_run_trials_dist(eng, c, n, r, logs, cdf, grp, cdf_d(cdf, call_block), cdf_dh(cdf, call_block), cdf_ph(cdf, call_block));
     if (rc == PRACH_OK) cdf_merge_block(cdf, worker_block, call_block);
@@ -114,7 +142,8 @@ static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *
 }
 
 static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, prach_result *res, double *lat_out, int want_logs,
-                      const char *outdir, int glibc, int npts, const prach_dist_spec *cdf, char *cdf_block) {
+                      const char *outdir, int glibc, int npts, reduce_spec red, char *cdf_block) {
+    const int cdf = red.cdf || red.tl; /* (the group table and the call's own block serve either reduction) */
     prach_engine *eng = NULL;
     int rc = prach_engine_create(device, &eng);
     if (rc != PRACH_OK) { fprintf(stderr, "prach_sim: device %d: %s\n", device, prach_strerror(rc)); return 2; }
@@ -125,7 +154,7 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
     prach_ue_log **logs = want_logs ? (prach_ue_log **)calloc((size_t)(m > 0 ? m : 1), sizeof(prach_ue_log *)) : NULL;
     if (!c || !r || (want_logs && !logs)) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
     int32_t *grp = cdf ? (int32_t *)malloc(sizeof(int32_t) * (size_t)(m > 0 ? m : 1)) : NULL;
-    char *call_block = cdf ? (char *)malloc(cdf_block_bytes(cdf)) : NULL;
+    char *call_block = cdf ? (char *)malloc(red.tl ? tl_block_bytes(red.tl) : cdf_block_bytes(red.cdf)) : NULL;
     if (cdf && (!grp || !call_block)) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
     if (!glibc) {
         for (int a = 0; a < m; a += CH) {
@@ -138,7 +167,7 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
                     if (!logs[k]) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
                 }
             }
-            rc = run_call(eng, c, n, r, logs, cdf, grp, call_block, cdf_block);
+            rc = run_call(eng, c, n, r, logs, red, grp, call_block, cdf_block);
             if (rc != PRACH_OK) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(rc)); return 2; }
             const double lat = now_s() - t0;
             for (int k = 0; k < n; k++) {
@@ -165,7 +194,7 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
                     if (!logs[s_]) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
                 }
             }
-            rc = run_call(eng, c, nseeds, r, logs, cdf, grp, call_block, cdf_block);
+            rc = run_call(eng, c, nseeds, r, logs, red, grp, call_block, cdf_block);
             if (rc != PRACH_OK) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(rc)); return 2; }
             const double lat = now_s() - t0;
             for (int s_ = 0; s_ < nseeds; s_++) {
@@ -189,8 +218,8 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
 int main(int argc, char *argv[]) {
     int randomMax = 1, variant = PRACH_VARIANT_WITHNOMA_C, rng = PRACH_RNG_GLIBC, device = 0, want_logs = 1, gpus = 1, rng_given = 0;
     int sweep_lo = 10000, sweep_hi = 100000, sweep_step = 10000; /* WithNOMA:221 */
-    const char *outdir = ".", *csv_path = NULL, *devlist = NULL, *cdf_path = NULL;
-    int cdf_bins = 4096, cdf_bin_ms = 1;
+    const char *outdir = ".", *csv_path = NULL, *devlist = NULL, *cdf_path = NULL, *tl_path = NULL;
+    int cdf_bins = 4096, cdf_bin_ms = 1, tl_bin_ms = 5;
     int devs[64];
     /* --program must be known before the defaults are laid down */
     for (int i = 1; i + 1 < argc; i += 2)
@@ -273,11 +302,18 @@ int main(int argc, char *argv[]) {
         } else if (strcmp(a, "--cdf-bin-ms") == 0) {
             if (atoi(v) < 1) die("--cdf-bin-ms W: the width of a delay bin in ms, at least 1");
             cdf_bin_ms = atoi(v);
+        } else if (strcmp(a, "--timeline") == 0) {
+            tl_path = v;
+        } else if (strcmp(a, "--timeline-bin") == 0) {
+            if (atoi(v) < 1) die("--timeline-bin MS: the width of a timeline bin in ms, at least 1");
+            tl_bin_ms = atoi(v);
         } else {
             usage_and_exit();
         }
     }
     base.rng_mode = rng;
+    if (tl_path && variant == PRACH_VARIANT_NOMA_C) die("--timeline needs --program beta or withnoma (NOMA.c logs no trace of a UE's cycle start)");
+    if (tl_path && cdf_path) die("--timeline and --cdf cannot be combined: one reduction per call");
     if (csv_path && variant != PRACH_VARIANT_BETA_C) die("--csv needs --program beta (AveragePerformance.py reads its six-number Results.txt)");
     if (variant == PRACH_VARIANT_NOMA_C) { want_logs = 0; if (!rng_given) rng = PRACH_RNG_PHILOX; base.rng_mode = rng; } /* --rng glibc: NOMA.c's own rand() stream */
 
@@ -352,10 +388,22 @@ int main(int argc, char *argv[]) {
         cdf_blocks = (char *)mmap(NULL, cdf_block_bytes(cdf) * (size_t)gpus, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0); /* (zero-filled: empty groups) */
         if (cdf_blocks == MAP_FAILED) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
     }
-#define CDF_BLOCK(w) (cdf ? cdf_blocks + cdf_block_bytes(cdf) * (size_t)(w) : NULL)
+    /* --timeline: the same, one block of timelines per worker; the bins cover the horizon (a completion is at most maxTime + 5) */
+    const int tl_bins = (prach_max_time(&base) + 6 + tl_bin_ms - 1) / tl_bin_ms;
+    const prach_timeline_spec tl_spec = {tl_bins, tl_bin_ms, npts, 0};
+    const prach_timeline_spec *const tls = tl_path ? &tl_spec : NULL;
+    if (tls && tl_bins > PRACH_TIMELINE_MAX_BINS) die("--timeline-bin MS: too many bins");
+    if (tls) {
+        cdf_blocks = (char *)mmap(NULL, tl_block_bytes(tls) * (size_t)gpus, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
+        if (cdf_blocks == MAP_FAILED) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+        for (int w = 0; w < gpus; w++)
+            for (int k = 0; k < npts; k++) tl_t(cdf_blocks + tl_block_bytes(tls) * (size_t)w)[k].done_max = -1; /* (empty groups) */
+    }
+    const reduce_spec red = {cdf, tls};
+#define CDF_BLOCK(w) (tls ? cdf_blocks + tl_block_bytes(tls) * (size_t)(w) : cdf ? cdf_blocks + cdf_block_bytes(cdf) * (size_t)(w) : NULL)
 
     if (gpus == 1) {
-        int rcw = run_worker(devs[0], cfgs, widx[0], wn[0], res, lat, want_logs, outdir, glibc, npts, cdf, CDF_BLOCK(0));
+        int rcw = run_worker(devs[0], cfgs, widx[0], wn[0], res, lat, want_logs, outdir, glibc, npts, red, CDF_BLOCK(0));
         if (rcw) return rcw;
     } else {
         /* one child per device, forked BEFORE this process touches HIP (a forked copy of an initialised runtime is not usable) */
@@ -364,7 +412,7 @@ int main(int argc, char *argv[]) {
         for (int w = 0; w < gpus; w++) {
             pid[w] = fork();
             if (pid[w] < 0) { perror("prach_sim: fork"); return 2; }
-            if (pid[w] == 0) _exit(run_worker(devs[w], cfgs, widx[w], wn[w], res, lat, want_logs, outdir, glibc, npts, cdf, CDF_BLOCK(w)));
+            if (pid[w] == 0) _exit(run_worker(devs[w], cfgs, widx[w], wn[w], res, lat, want_logs, outdir, glibc, npts, red, CDF_BLOCK(w)));
         }
         int bad = 0;
         for (int w = 0; w < gpus; w++) {
@@ -390,6 +438,26 @@ int main(int argc, char *argv[]) {
             snprintf(label, sizeof label, "%d", sweep_lo + k * sweep_step);
             const size_t n = prach_dist_format_csv(cdf, cdf_d(cdf, CDF_BLOCK(0)) + k, cdf_dh(cdf, CDF_BLOCK(0)) + (size_t)k * (size_t)cdf_bins,
                                                    cdf_ph(cdf, CDF_BLOCK(0)) + (size_t)k * PRACH_DIST_PTC_BINS, label, out, cap);
+            if (n >= cap) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_INTERNAL)); return 2; }
+            fwrite(out, 1, n, fp);
+        }
+        free(out);
+        fclose(fp);
+    }
+
+    if (tls) { /* likewise: worker 0's block takes the others'; one group per sweep point, labelled nUE */
+        for (int w = 1; w < gpus; w++) tl_merge_block(tls, CDF_BLOCK(0), CDF_BLOCK(w));
+        FILE *fp = fopen(tl_path, "wb");
+        if (!fp) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_IO)); return 2; }
+        const size_t cap = 64 * (5 * (size_t)tl_bins + 2) + 1; /* a line: a label of at most 10 digits, a series name, two numbers */
+        char *out = (char *)malloc(cap);
+        if (!out) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+        for (int k = 0; k < npts; k++) {
+            char label[16];
+            const uint64_t *ser[5];
+            for (int q = 0; q < 5; q++) ser[q] = tl_series(tls, CDF_BLOCK(0), q, k);
+            snprintf(label, sizeof label, "%d", sweep_lo + k * sweep_step);
+            const size_t n = prach_timeline_format_csv(tls, tl_t(CDF_BLOCK(0)) + k, ser, label, out, cap);
             if (n >= cap) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_INTERNAL)); return 2; }
             fwrite(out, 1, n, fp);
         }

@@ -182,4 +182,20 @@ struct DistJob {
 hipError_t launch_dist_kernel(const DistJob *jobs, int njobs, int workgroups, int delay_bins, int delay_bin_ms, int scheme, unsigned long long *delay_hist,
                               unsigned long long *ptc_hist, unsigned long long *scalars, hipStream_t stream);
 
+// prach_timeline.hip: the timelines of a launch's accepted trials (prach_run_trials_timeline).  One job per trial; a workgroup reduces one tile of
+// TL_TILE consecutive UEs of one trial from the 64-byte log records the simulation kernel wrote on the device and from the trial's arrival schedule.
+// scheme 1 privatises TL_WINDOW bins from the tile's first arrival bin on in LDS (four 32-bit counters per by-arrival bin, one per done bin) and
+// flushes the non-zero ones; what falls outside, and everything under scheme 0, goes straight to the call's buffers with 64-bit agent-scope atomics.
+constexpr int TL_TILE = 8192, TL_THREADS = 256, TL_WINDOW = 2048;
+constexpr int TL_MAX_SOJOURN = 60000 + 6; // c(i) - a(i) at most: Uniform arrivals run 60 000 subframes, the completion is 6 behind the last Msg3
+static_assert((unsigned long long)TL_TILE * TL_MAX_SOJOURN < (1ull << 32), "a 32-bit LDS counter holds the sojourn sum of a whole tile");
+constexpr int TL_SCALARS = 8; // per group: arrived, success, restarted, arrival_overflow, done_overflow, sojourn_sum, timer_sum, done_max + 1 (0: no successful UE)
+struct TimelineJob {
+    const int4 *logs; // [nUE][4] prach_ue_log records
+    const int *sched; // [nslots] activeCheck after the arrival update of every access slot
+    int nUE, group, wg0, aT, nslots, pad; // wg0: the first workgroup of this job
+};
+struct TimelineOut { unsigned long long *arrivals, *success, *sojourn, *timer, *done, *scalars; }; // [ngroups][bins] each, [ngroups][TL_SCALARS]
+hipError_t launch_timeline_kernel(const TimelineJob *jobs, int njobs, int workgroups, int bins, int bin_ms, int scheme, TimelineOut out, hipStream_t stream);
+
 } // namespace prach

@@ -48,6 +48,13 @@ struct prach_engine {
     size_t dist_cap = 0;
     DistJob *dist_jobs_h = nullptr, *dist_jobs_d = nullptr;
     int dist_jobs_cap = 0;
+    // prach_run_trials_timeline: the same three for the five series and the scalars of the call, with events of their own (prach_timing.timeline_ms)
+    hipEvent_t ev4 = nullptr, ev5 = nullptr;
+    char *tl_buf = nullptr;
+    size_t tl_cap = 0;
+    TimelineJob *tl_jobs_h = nullptr, *tl_jobs_d = nullptr;
+    int tl_jobs_cap = 0;
+    int64_t opt_timeline_scheme = 1; // timeline_kernel's binning (prach_timeline.hip): 0 global atomics only, 1 windows of bins privatised in LDS (measured faster: DESIGN.md 4)
     int64_t opt_dist_scheme = 1;   // dist_kernel's binning of the preamble counts (prach_dist.hip): 0 plain LDS adds, 1 per-wavefront copies (measured fastest), 2 match and aggregate
     prach_timing last{};
     int64_t opt_stream_factor = 0; // glibc: initial draws-per-UE budget override (0 = auto)
@@ -116,7 +123,8 @@ size_t mbox_bytes(const prach_cfg &c, int G, int &evw, int &mbstride) {
 }
 
 // stream_len[k]: glibc draw-stream window of trial k (0 in Philox mode); G: workgroups per trial (0 = trial_kernel)
-LaunchLayout layout_launch(const prach_cfg *cfgs, const int *idx, int m, prach_ue_log *const *ue_logs, const std::vector<size_t> &stream_len, int G, bool batch, bool full_calendars, int64_t calendar_cap) {
+// all_logs: every trial gets a device log region (prach_run_trials_timeline reduces it there), not only the ones whose log the host asked for
+LaunchLayout layout_launch(const prach_cfg *cfgs, const int *idx, int m, prach_ue_log *const *ue_logs, bool all_logs, const std::vector<size_t> &stream_len, int G, bool batch, bool full_calendars, int64_t calendar_cap) {
     LaunchLayout L;
     L.t.resize(m);
     size_t o = align_up(sizeof(TrialDev) * (size_t)m, 256);
@@ -183,7 +191,7 @@ LaunchLayout layout_launch(const prach_cfg *cfgs, const int *idx, int m, prach_u
             T.cand = take(8 * (n + 64 * (size_t)G + 64)); // cluster kernel: early-leaver candidates
         }
         T.stream = T.stream_len ? take(4 * (T.stream_len + 2)) : 0;
-        T.logs = (ue_logs && ue_logs[idx[k]]) ? take(sizeof(prach_ue_log) * n) : 0;
+        T.logs = (all_logs || (ue_logs && ue_logs[idx[k]])) ? take(sizeof(prach_ue_log) * n) : 0;
         T.timers = take(4 * n);
         T.sector = (c.flags & PRACH_FLAG_SECTOR_GRANTS) ? take(4 * n) : 0;
         T.n_pre0 = T.n_sector = T.n_gain = T.n_lgain = T.n_nd0 = 0;
@@ -424,6 +432,10 @@ struct CallCtx {
     std::vector<prach_dist> host_d;           // NOMA.c in the reference's stream finishes on the host: its groups' accumulators (sized on first use)
     std::vector<uint64_t> host_dh, host_ph;
     int group_of(int k) const { return group ? group[k] : k; }
+    // prach_run_trials_timeline (tspec == nullptr: any other call).  group, trials and ues above serve whichever of the two specs is set
+    const prach_timeline_spec *tspec = nullptr;
+    double timeline_ms = 0;
+    TimelineOut d_tl{};
     DistSink sink(int k) { // the host-side accumulators of trial k's group
         if (host_d.empty()) {
             prach_dist z{};
@@ -553,7 +565,7 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
         if ((cfgs[idx[k]].flags & PRACH_FLAG_SECTOR_GRANTS) && G > 0 && !batch) return PRACH_ERR_INTERNAL;
     // NOMA.c's activeUE table: built by the device (noma_activation_kernel) unless the option or a rerun asks for the host's libm
     const bool host_act = noma && (e->opt_noma_host_activation || o.host_act);
-    const LaunchLayout LL = layout_launch(cfgs, idx, m, cx.ue_logs, slen, G, batch, o.full_calendars, e->opt_calendar_cap);
+    const LaunchLayout LL = layout_launch(cfgs, idx, m, cx.ue_logs, cx.tspec != nullptr, slen, G, batch, o.full_calendars, e->opt_calendar_cap);
     if (LL.end > e->mem_budget && m > 1) { // (e.g. the 10 000-trial grid with its calendars on ONE GPU: two or three launches instead of one)
         const int h = m / 2;
         int rc = run_group(e, cx, idx, h, attempt, G, o, cal_overflow);
@@ -742,6 +754,29 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
             dist_launched = true;
         }
     }
+    // the timelines likewise: from the log records the simulation kernel left on the device and the launch's own copy of every arrival schedule
+    bool tl_launched = false;
+    if (cx.tspec) {
+        int njobs = 0, wgs = 0;
+        for (int k = 0; k < m; k++) {
+            if (drs[k].status != PRACH_OK) continue;
+            const prach_cfg &c = cfgs[idx[k]];
+            const TrialLayout &L = LL.t[k];
+            const int g = cx.group_of(idx[k]);
+            const int nslots = (prach_max_time(&c) + c.accessTime - 1) / c.accessTime; // (what prach_arrival_schedule fills; the table has one entry more)
+            e->tl_jobs_h[njobs++] = TimelineJob{reinterpret_cast<const int4 *>(A + L.logs), reinterpret_cast<const int *>(A + L.sched), c.nUE, g, wgs, c.accessTime, nslots, 0};
+            wgs += (c.nUE + TL_TILE - 1) / TL_TILE;
+            cx.trials[(size_t)g]++;
+            cx.ues[(size_t)g] += (uint64_t)c.nUE;
+        }
+        if (njobs > 0) {
+            HIPCHK(hipMemcpyAsync(e->tl_jobs_d, e->tl_jobs_h, sizeof(TimelineJob) * (size_t)njobs, hipMemcpyHostToDevice, e->stream));
+            HIPCHK(hipEventRecord(e->ev4, e->stream));
+            HIPCHK(launch_timeline_kernel(e->tl_jobs_d, njobs, wgs, cx.tspec->bins, cx.tspec->bin_ms, (int)e->opt_timeline_scheme, cx.d_tl, e->stream));
+            HIPCHK(hipEventRecord(e->ev5, e->stream));
+            tl_launched = true;
+        }
+    }
     std::vector<int32_t> timers;
     for (int k = 0; k < m; k++) {
         const prach_cfg &c = cfgs[idx[k]];
@@ -787,7 +822,7 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
                 if (timers[i] != INT_MIN) td_ += (float)timers[i];
             r.totalDelay = td_;
         }
-        if (L.logs)
+        if (L.logs && cx.ue_logs && cx.ue_logs[idx[k]]) // (a timeline call lays out every trial's log; only the ones asked for cross the bus)
             HIPCHK(hipMemcpy(cx.ue_logs[idx[k]], A + L.logs, sizeof(prach_ue_log) * (size_t)c.nUE, hipMemcpyDeviceToHost));
     }
     if (dist_launched) { // (the next launch lays the arena out again and reuses the pinned job table)
@@ -795,6 +830,12 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
         float dms = 0;
         HIPCHK(hipEventElapsedTime(&dms, e->ev2, e->ev3));
         cx.dist_ms += dms;
+    }
+    if (tl_launched) {
+        HIPCHK(hipStreamSynchronize(e->stream));
+        float tms = 0;
+        HIPCHK(hipEventElapsedTime(&tms, e->ev4, e->ev5));
+        cx.timeline_ms += tms;
     }
     return PRACH_OK;
 }
@@ -967,7 +1008,57 @@ static int dist_end(prach_engine *e, CallCtx &cx, const DistOut &out) {
     return PRACH_OK;
 }
 
-static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const DistOut *dout = nullptr) {
+// the caller's outputs of prach_run_trials_timeline; series: arrivals, success, sojourn_sum, timer_sum, done
+struct TimelineCallOut { const prach_timeline_spec *spec; const int32_t *group; prach_timeline *tl; uint64_t *series[5]; };
+
+static int timeline_begin(prach_engine *e, CallCtx &cx, int n) {
+    const prach_timeline_spec &s = *cx.tspec;
+    const size_t ng = (size_t)s.ngroups, one = align_up(8 * ng * (size_t)s.bins, 256), need = 5 * one + 8 * ng * TL_SCALARS;
+    if (need > e->tl_cap) {
+        if (e->tl_buf) HIPCHK(hipFree(e->tl_buf));
+        e->tl_buf = nullptr; e->tl_cap = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->tl_buf), need));
+        e->tl_cap = need;
+    }
+    if (n > e->tl_jobs_cap) {
+        if (e->tl_jobs_h) HIPCHK(hipHostFree(e->tl_jobs_h));
+        if (e->tl_jobs_d) HIPCHK(hipFree(e->tl_jobs_d));
+        e->tl_jobs_h = e->tl_jobs_d = nullptr; e->tl_jobs_cap = 0;
+        const int want = n + (n >> 2) + 64;
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&e->tl_jobs_h), sizeof(TimelineJob) * (size_t)want, hipHostMallocDefault));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->tl_jobs_d), sizeof(TimelineJob) * (size_t)want));
+        e->tl_jobs_cap = want;
+    }
+    if (!e->ev4) HIPCHK(hipEventCreate(&e->ev4));
+    if (!e->ev5) HIPCHK(hipEventCreate(&e->ev5));
+    auto at = [&](size_t q) { return reinterpret_cast<unsigned long long *>(e->tl_buf + q * one); };
+    cx.d_tl = TimelineOut{at(0), at(1), at(2), at(3), at(4), at(5)};
+    cx.trials.assign(ng, 0);
+    cx.ues.assign(ng, 0);
+    HIPCHK(hipMemsetAsync(e->tl_buf, 0, need, e->stream));
+    return PRACH_OK;
+}
+// ONE copy-out per series at the end of the call (every timeline kernel has completed: run_group waits for its own)
+static int timeline_end(prach_engine *e, CallCtx &cx, const TimelineCallOut &out) {
+    const prach_timeline_spec &s = *cx.tspec;
+    const size_t ng = (size_t)s.ngroups;
+    std::vector<unsigned long long> sc(ng * TL_SCALARS);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    unsigned long long *const dev[5] = {cx.d_tl.arrivals, cx.d_tl.success, cx.d_tl.sojourn, cx.d_tl.timer, cx.d_tl.done};
+    for (int q = 0; q < 5; q++) HIPCHK(hipMemcpy(out.series[q], dev[q], 8 * ng * (size_t)s.bins, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sc.data(), cx.d_tl.scalars, 8 * sc.size(), hipMemcpyDeviceToHost));
+    for (size_t g = 0; g < ng; g++) {
+        const unsigned long long *const q = &sc[g * TL_SCALARS];
+        prach_timeline &t = out.tl[g];
+        t.trials = cx.trials[g]; t.ues = cx.ues[g]; t.arrived = q[0]; t.success = q[1]; t.restarted = q[2]; t.arrival_overflow = q[3]; t.done_overflow = q[4];
+        t.sojourn_sum = q[5]; t.timer_sum = q[6];
+        t.done_max = (int64_t)q[7] - 1;
+    }
+    return PRACH_OK;
+}
+
+static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const DistOut *dout = nullptr,
+                           const TimelineCallOut *tout = nullptr) {
     for (int k = 0; k < n; k++) { // nothing is left uninitialised on an early error return
         std::memset(&results[k], 0, sizeof(results[k]));
         results[k].status = PRACH_ERR_INTERNAL;
@@ -977,6 +1068,11 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
         std::memset(dout->delay_hist, 0, 8 * ng * (size_t)dout->spec->delay_bins);
         std::memset(dout->ptc_hist, 0, 8 * ng * PRACH_DIST_PTC_BINS);
         for (size_t g = 0; g < ng; g++) { dout->dist[g] = prach_dist{}; dout->dist[g].delay_max = -1; }
+    }
+    if (tout) { // (and for the timelines)
+        const size_t ng = (size_t)tout->spec->ngroups;
+        for (int q = 0; q < 5; q++) std::memset(tout->series[q], 0, 8 * ng * (size_t)tout->spec->bins);
+        for (size_t g = 0; g < ng; g++) { tout->tl[g] = prach_timeline{}; tout->tl[g].done_max = -1; }
     }
     for (int k = 0; k < n; k++) {
         int v = prach_cfg_validate(&cfgs[k]);
@@ -991,6 +1087,12 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
         cx.spec = dout->spec;
         cx.group = dout->group;
         int rc = dist_begin(e, cx, n);
+        if (rc != PRACH_OK) return rc;
+    }
+    if (tout) {
+        cx.tspec = tout->spec;
+        cx.group = tout->group;
+        int rc = timeline_begin(e, cx, n);
         if (rc != PRACH_OK) return rc;
     }
     // NOMA.c in the reference's OWN rand() stream: activeUE's rejection loops make every stream position data dependent and its libm
@@ -1144,6 +1246,11 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
         if (rc != PRACH_OK) return rc;
         e->last.dist_ms = cx.dist_ms;
     }
+    if (tout) {
+        int rc = timeline_end(e, cx, *tout);
+        if (rc != PRACH_OK) return rc;
+        e->last.timeline_ms = cx.timeline_ms;
+    }
     e->last.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return worst;
 }
@@ -1172,6 +1279,11 @@ void prach_engine_destroy(prach_engine *e) {
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->ev2) (void)hipEventDestroy(e->ev2);
     if (e->ev3) (void)hipEventDestroy(e->ev3);
+    if (e->ev4) (void)hipEventDestroy(e->ev4);
+    if (e->ev5) (void)hipEventDestroy(e->ev5);
+    if (e->tl_buf) (void)hipFree(e->tl_buf);
+    if (e->tl_jobs_d) (void)hipFree(e->tl_jobs_d);
+    if (e->tl_jobs_h) (void)hipHostFree(e->tl_jobs_h);
     if (e->dist_buf) (void)hipFree(e->dist_buf);
     if (e->dist_jobs_d) (void)hipFree(e->dist_jobs_d);
     if (e->dist_jobs_h) (void)hipHostFree(e->dist_jobs_h);
@@ -1199,6 +1311,7 @@ int prach_engine_set(prach_engine *e, const char *key, int64_t value) {
     if (std::strcmp(key, "calendar_cap") == 0) { if (value < 0) return PRACH_ERR_ARG; e->opt_calendar_cap = value; return PRACH_OK; }
     if (std::strcmp(key, "batch_waves") == 0) { if (value != 0 && value != 8 && value != 16) return PRACH_ERR_ARG; e->opt_batch_waves = value; return PRACH_OK; }
     if (std::strcmp(key, "dist_scheme") == 0) { if (value < 0 || value > 2) return PRACH_ERR_ARG; e->opt_dist_scheme = value; return PRACH_OK; }
+    if (std::strcmp(key, "timeline_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_timeline_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "xcd_pack") == 0) { e->opt_xcd_pack = value != 0; return PRACH_OK; }
     return PRACH_ERR_ARG;
 }
@@ -1290,5 +1403,22 @@ int prach_run_trials_dist(prach_engine *e, const prach_cfg *cfgs, int n, prach_r
 }
 
 int prach_dist_tile_ues(void) { return DIST_TILE; }
+
+int prach_run_trials_timeline(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_timeline_spec *spec,
+                              const int32_t *group, prach_timeline *tl, uint64_t *arrivals, uint64_t *success, uint64_t *sojourn_sum, uint64_t *timer_sum, uint64_t *done) {
+    // (spec, groups and variants are judged first: what they ask for does not depend on a device)
+    if (!cfgs || !results || n <= 0 || !spec || !tl || !arrivals || !success || !sojourn_sum || !timer_sum || !done) return PRACH_ERR_ARG;
+    if (spec->bins < 1 || spec->bins > PRACH_TIMELINE_MAX_BINS || spec->bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
+    if (!group && spec->ngroups != n) return PRACH_ERR_ARG;
+    if (group) for (int k = 0; k < n; k++) if (group[k] < 0 || group[k] >= spec->ngroups) return PRACH_ERR_ARG;
+    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
+    if (5 * (uint64_t)spec->ngroups * (uint64_t)spec->bins > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
+    if (!e) return PRACH_ERR_ARG;
+    const TimelineCallOut out{spec, group, tl, {arrivals, success, sojourn_sum, timer_sum, done}};
+    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, nullptr, &out);)
+}
+
+int prach_timeline_tile_ues(void) { return TL_TILE; }
+int prach_timeline_window_bins(void) { return TL_WINDOW; }
 
 } // extern "C"

@@ -650,3 +650,92 @@ size_t prach_dist_format_csv(const prach_dist_spec *s, const prach_dist *d, cons
     else if (buf && cap) buf[0] = 0; /* (did not fit: nothing partial is left behind as a string) */
     return off;
 }
+
+/* ---- timelines per trial group (prach_run_trials_timeline) -------------------------------------- */
+
+static int timeline_spec_ok(const prach_timeline_spec *s) {
+    return s && s->bins >= 1 && s->bins <= PRACH_TIMELINE_MAX_BINS && s->bin_ms >= 1;
+}
+
+/* THE DEFINITION (include/prach.h).  Two passes: the first only judges, so that a refused log leaves nothing behind */
+int prach_timeline_accumulate_logs(const prach_timeline_spec *s, const prach_cfg *cfg, const prach_ue_log *ue, int nUE, prach_timeline *t, uint64_t *arrivals,
+                                   uint64_t *success, uint64_t *sojourn_sum, uint64_t *timer_sum, uint64_t *done) {
+    if (!timeline_spec_ok(s) || !cfg || !t || !arrivals || !success || !sojourn_sum || !timer_sum || !done || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    if (cfg->variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED;
+    if (prach_cfg_validate(cfg) != PRACH_OK || nUE != cfg->nUE) return PRACH_ERR_ARG;
+    const int nslots = (prach_max_time(cfg) + cfg->accessTime - 1) / cfg->accessTime;
+    int32_t *sched = (int32_t *)malloc(sizeof(int32_t) * (size_t)nslots);
+    if (!sched) return PRACH_ERR_INTERNAL;
+    prach_arrival_schedule(cfg, sched, nslots, NULL);
+    for (int pass = 0; pass < 2; pass++) {
+        if (pass == 1 && t->trials == 0 && t->success == 0) t->done_max = -1; /* (a zero-filled group is an empty one) */
+        int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
+        for (int i = 0; i < nUE; i++) {
+            while (slot < nslots && sched[slot] <= i) slot++;
+            const int64_t a = (int64_t)cfg->accessTime * slot;
+            const int ok = ue[i].msg4Flag == 1;
+            const int64_t c = (int64_t)ue[i].txTime + 6;
+            if (pass == 0) {
+                if (ue[i].active != -1 && ok && (ue[i].timer < 0 || c < a)) { free(sched); return PRACH_ERR_ARG; }
+                continue;
+            }
+            if (ue[i].active == -1) continue; /* not arrived */
+            const int64_t ab = a / s->bin_ms;
+            t->arrived++;
+            if (ab < s->bins) arrivals[ab]++;
+            else t->arrival_overflow++;
+            if (!ok) continue;
+            const int64_t db = c / s->bin_ms;
+            t->success++;
+            t->restarted += c - ue[i].timer != a;
+            t->sojourn_sum += (uint64_t)(c - a);
+            t->timer_sum += (uint64_t)ue[i].timer;
+            if (c > t->done_max) t->done_max = c;
+            if (ab < s->bins) { success[ab]++; sojourn_sum[ab] += (uint64_t)(c - a); timer_sum[ab] += (uint64_t)ue[i].timer; }
+            if (db < s->bins) done[db]++;
+            else t->done_overflow++;
+        }
+    }
+    free(sched);
+    t->trials++;
+    t->ues += (uint64_t)nUE;
+    return PRACH_OK;
+}
+
+void prach_timeline_merge(const prach_timeline_spec *s, prach_timeline *into, uint64_t *const into_series[5], const prach_timeline *from,
+                          const uint64_t *const from_series[5]) {
+    if (!timeline_spec_ok(s) || !into || !into_series || !from || !from_series) return;
+    for (int q = 0; q < 5; q++) if (!into_series[q] || !from_series[q]) return;
+    const int64_t a = into->success ? into->done_max : -1, b = from->success ? from->done_max : -1;
+    into->trials += from->trials; into->ues += from->ues; into->arrived += from->arrived; into->success += from->success; into->restarted += from->restarted;
+    into->arrival_overflow += from->arrival_overflow; into->done_overflow += from->done_overflow; into->sojourn_sum += from->sojourn_sum;
+    into->timer_sum += from->timer_sum;
+    into->done_max = a > b ? a : b;
+    for (int q = 0; q < 5; q++)
+        for (int i = 0; i < s->bins; i++) into_series[q][i] += from_series[q][i];
+}
+
+size_t prach_timeline_format_csv(const prach_timeline_spec *s, const prach_timeline *t, const uint64_t *const series[5], const char *label, char *buf, size_t cap) {
+    static const char *const names[5] = {"arrivals", "success", "sojourn_sum", "timer_sum", "done"};
+    if (!timeline_spec_ok(s) || !t || !series || !label) return 0;
+    for (int q = 0; q < 5; q++) if (!series[q]) return 0;
+    size_t off = 0;
+    char line[512];
+#define TL_EMIT(...)                                                            \
+    do {                                                                        \
+        const int n_ = snprintf(line, sizeof line, __VA_ARGS__);                \
+        if (n_ < 0 || (size_t)n_ >= sizeof line) return 0;                      \
+        if (buf && off + (size_t)n_ < cap) memcpy(buf + off, line, (size_t)n_); \
+        off += (size_t)n_;                                                      \
+    } while (0)
+    for (int q = 0; q < 5; q++) {
+        for (int b = 0; b < s->bins; b++)
+            if (series[q][b]) TL_EMIT("%.200s,%s,%lld,%llu\n", label, names[q], (long long)b * s->bin_ms, (unsigned long long)series[q][b]);
+        if (q == 0 && t->arrival_overflow) TL_EMIT("%.200s,arrivals,overflow,%llu\n", label, (unsigned long long)t->arrival_overflow);
+        if (q == 4 && t->done_overflow) TL_EMIT("%.200s,done,overflow,%llu\n", label, (unsigned long long)t->done_overflow);
+    }
+#undef TL_EMIT
+    if (buf && off < cap) buf[off] = 0;
+    else if (buf && cap) buf[0] = 0; /* (did not fit: nothing partial is left behind as a string) */
+    return off;
+}

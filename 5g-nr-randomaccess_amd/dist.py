@@ -99,6 +99,31 @@ def allreduce_dist(d, device=None):
     return d
 
 
+def allreduce_timeline(tl, device=None):
+    """Merges the timelines (a `Timeline` of the package: same groups, bins and width on every rank) across ranks, in place: ONE int64 sum all-reduce of the
+    concatenated block — the five series and the summed scalars — and done_max by a max all-reduce of ngroups values.  Integers: exact in any order."""
+    import torch
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return tl
+    from . import TIMELINE_FIELDS, TIMELINE_SERIES
+    sums = [f for f in TIMELINE_FIELDS if f != "done_max"]
+    block = np.concatenate([tl.series[n].astype(np.int64).ravel() for n in TIMELINE_SERIES] + [tl.scalars[f].astype(np.int64) for f in sums])
+    t, mx = torch.from_numpy(block), torch.from_numpy(tl.scalars["done_max"].astype(np.int64))
+    if device is not None:
+        t, mx = t.to(device), mx.to(device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    dist.all_reduce(mx, op=dist.ReduceOp.MAX)
+    block = t.cpu().numpy()
+    ns, g = tl.ngroups * tl.bins, tl.ngroups
+    for k, n in enumerate(TIMELINE_SERIES):
+        tl.series[n][...] = block[k * ns:(k + 1) * ns].reshape(tl.series[n].shape).astype(np.uint64)
+    for k, f in enumerate(sums):
+        tl.scalars[f][:] = block[5 * ns + k * g:5 * ns + (k + 1) * g]
+    tl.scalars["done_max"][:] = mx.cpu().numpy()
+    return tl
+
+
 ROW_BYTES = 256  # a row = trial index (8 bytes) + kind (1) + payload length (2) + up to ROW_PAYLOAD bytes of text
 ROW_PAYLOAD = ROW_BYTES - 11  # (Beta.c's six-line Results.txt is ~45 bytes, RandomAccessWithNOMA's eight lines ~115 at nUE = 100 000)
 

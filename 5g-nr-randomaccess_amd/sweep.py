@@ -35,8 +35,13 @@ def main(argv=None):
     ap.add_argument("--cdf", default=None, help="write the delay / preamble-count distributions of the successful UEs, one group per sweep point, to this CSV file")
     ap.add_argument("--cdf-bins", type=int, default=4096)
     ap.add_argument("--cdf-bin-ms", type=int, default=1)
+    ap.add_argument("--timeline", default=None, help="write arrivals, successes, sojourn / timer sums by arrival time and completions by completion time, "
+                    "one group per sweep point, to this CSV file (not together with --cdf)")
+    ap.add_argument("--timeline-bin", type=int, default=5, help="width of a timeline bin in ms; the bins cover the horizon")
     ap.add_argument("--same-device", action="store_true", help="rehearsal on one GPU: every rank uses cuda:0")
     args = ap.parse_args(argv)
+    if args.cdf and args.timeline:
+        ap.error("--cdf and --timeline cannot be combined: one reduction per call")
 
     import torch
     import __graft_entry__ as g
@@ -67,9 +72,15 @@ def main(argv=None):
     res = []
     CH = 1024  # trials per call: bounds the device arena (2.7 GB per 1024 trials of the sweep)
     cdf = pkg.Dist(len(points), args.cdf_bins, args.cdf_bin_ms) if args.cdf else None
+    tl_bins = -(-(10000 + 6) // args.timeline_bin)  # Beta arrivals: 10 000 subframes, a completion at most 6 behind
+    tl = pkg.Timeline(len(points), tl_bins, args.timeline_bin) if args.timeline else None
     for a in range(0, len(mine), CH):
         part = mine[a:a + CH]
-        if cdf is None:
+        if tl is not None:  # the timelines come from the device with the results: no per-UE log is copied
+            r, _, t = eng.run_trials_timeline([cfgs[i] for i in part], tl_bins, args.timeline_bin, groups=[i % len(points) for i in part], ngroups=len(points))
+            for k in range(len(points)):
+                tl.merge_group(k, t, k)
+        elif cdf is None:
             r, _ = eng.run_trials([cfgs[i] for i in part])
         else:  # the distributions come from the device with the results: no per-UE log is copied
             r, _, d = eng.run_trials_dist([cfgs[i] for i in part], args.cdf_bins, args.cdf_bin_ms, groups=[i % len(points) for i in part], ngroups=len(points))
@@ -90,6 +101,11 @@ def main(argv=None):
         if rank == 0:
             with open(args.cdf, "wb") as f:
                 f.write(pkg.dist_csv(cdf, labels=points))
+    if tl is not None:
+        distmod.allreduce_timeline(tl, device=dev if (world > 1 and args.backend == "nccl") else None)
+        if rank == 0:
+            with open(args.timeline, "wb") as f:
+                f.write(pkg.timeline_csv(tl, labels=points))
     if rank == 0:
         fi = {n: k for k, n in enumerate(distmod.AGG_FIELDS)}
         summary = {"program": args.program, "times": args.times, "points": points, "world": world,

@@ -130,6 +130,7 @@ typedef struct prach_timing {
     int32_t noma_host_ues;       /* NOMA_C, Philox: UEs of the device-built activeUE table that the host recomputed with its libm (a value inside the
                                     device math library's error band of a rounding / comparison boundary: ~1e-6 of the UEs) */
     double dist_ms;              /* HIP-event time of the distribution kernel launches (prach_run_trials_dist) of the last call; 0 without a spec */
+    double timeline_ms;          /* HIP-event time of the timeline kernel launches (prach_run_trials_timeline) of the last call; 0 in every other call */
 } prach_timing;
 
 typedef struct prach_engine prach_engine;
@@ -177,6 +178,57 @@ int prach_run_trials_dist(prach_engine *, const prach_cfg *cfgs, int n, prach_re
                           prach_ue_log *const *ue_logs, const prach_dist_spec *spec, const int32_t *group,
                           prach_dist *dist, uint64_t *delay_hist, uint64_t *ptc_hist);
 
+/* Timeline per trial group, built on the device: what arrived, was served and completed in each stretch of the simulation.  Everything is derived from
+ * fields every simulation kernel already logs, the UE index and the arrival schedule (no new simulation semantics).  For UE i of a trial with config cfg:
+ *   a(i)  = accessTime x the first slot s with sched[s] > i, sched = prach_arrival_schedule(cfg) (UEs are activated in index order, Beta.c:121-147;
+ *           a UE no slot activates has a(i) = accessTime x the number of slots, which is not below maxTime)
+ *   UE i ARRIVED iff its logged active != -1
+ *   a successful UE (msg4Flag == 1): txTime is the subframe of its successful Msg3, c(i) = txTime + 6 its completion, c(i) - a(i) its SOJOURN, and
+ *           txTime + 6 - timer the start of its last attempt cycle; it RESTARTED iff that start differs from a(i)
+ * The reference zeroes `timer` whenever a UE starts over (after maxMsg2TxCount retransmissions, Beta.c:250-281; after a Msg3 timeout, Beta.c:384-410): its
+ * "access delay" is the length of the LAST cycle.  The sojourn is the time since the UE arrived; both sums are reported.
+ * Bin b covers [b * bin_ms, (b + 1) * bin_ms).  Five series of `bins` entries per group:
+ *   arrivals[b]     arrived UEs with a(i) in bin b
+ *   success[b]      successful UEs with a(i) in bin b
+ *   sojourn_sum[b]  sum of c(i) - a(i) over the successful UEs with a(i) in bin b
+ *   timer_sum[b]    sum of timer over the same UEs
+ *   done[b]         successful UEs with c(i) in bin b   (c(i) can exceed time_exit by up to 6)
+ * A UE whose bin index is >= bins counts in the scalars and in the matching overflow counter, and in no bin of that axis.  Integers only: device, host,
+ * forked workers and ranks merge exactly in any order.
+ * PRACH_VARIANT_BETA_C and PRACH_VARIANT_WITHNOMA_C only, in both RNG modes: NOMA.c zeroes its timer without any logged trace of the cycle start (its
+ * log has no txTime of the successful Msg3), so a NOMA_C cfg is PRACH_ERR_UNSUPPORTED, before anything is launched. */
+#define PRACH_TIMELINE_MAX_BINS 65536      /* Uniform traffic at 1 ms: 60 006 bins */
+
+typedef struct prach_timeline_spec {
+    int32_t bins;      /* 1 .. PRACH_TIMELINE_MAX_BINS */
+    int32_t bin_ms;    /* >= 1 */
+    int32_t ngroups;   /* number of output timelines */
+    int32_t reserved;  /* 0 */
+} prach_timeline_spec;
+
+typedef struct prach_timeline {      /* one per group */
+    uint64_t trials;                 /* trials accumulated (status PRACH_OK) */
+    uint64_t ues;                    /* sum of their nUE */
+    uint64_t arrived;                /* UEs with active != -1 */
+    uint64_t success;                /* UEs with msg4Flag == 1 */
+    uint64_t restarted;              /* successful UEs whose last cycle did not start at their arrival */
+    uint64_t arrival_overflow;       /* arrived UEs with a(i) >= bins * bin_ms (in no bin of arrivals; the successful ones in no bin of success, sojourn_sum, timer_sum) */
+    uint64_t done_overflow;          /* successful UEs with c(i) >= bins * bin_ms (in no bin of done) */
+    uint64_t sojourn_sum, timer_sum; /* over the successful UEs, unbinned */
+    int64_t  done_max;               /* the largest c(i); -1 if success == 0 */
+} prach_timeline;
+
+/* prach_run_trials plus the timelines, with the contract of prach_run_trials_dist: trial k is added to group group[k] (group == NULL: trial k is group k and
+ * ngroups must equal n); tl[ngroups] and the five series [ngroups * bins] are caller-owned and OVERWRITTEN; a trial whose final status is not PRACH_OK
+ * contributes nothing; a trial the engine reruns contributes once, from the launch whose result is kept.  prach::timeline_kernel (csrc/prach_timeline.hip)
+ * reduces the per-UE log records the simulation kernels write ON THE DEVICE: the engine lays them out for every trial of such a call and copies out only
+ * the ones the caller asked for (ue_logs as in prach_run_trials), so the arena of the call grows by 64 bytes per UE.
+ * PRACH_ERR_ARG: a NULL output, a bin count or width out of range, a group id out of range, NULL group with ngroups != n;
+ * PRACH_ERR_UNSUPPORTED: any NOMA_C cfg; 5 * ngroups * bins > 2^27 words (1 GiB of device buffer). */
+int prach_run_trials_timeline(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs,
+                              const prach_timeline_spec *spec, const int32_t *group, prach_timeline *tl, uint64_t *arrivals, uint64_t *success,
+                              uint64_t *sojourn_sum, uint64_t *timer_sum, uint64_t *done);
+
 /* engine tunables; none changes a result, all are covered by parity tests:
  *   "cluster"       workgroups cooperating on one trial (1..64; 0 = auto)
  *   "stream_factor" glibc mode: initial draws-per-UE budget of the rand() stream window (0 = auto; it grows on demand)
@@ -195,6 +247,8 @@ int prach_run_trials_dist(prach_engine *, const prach_cfg *cfgs, int n, prach_re
  *   "mem_budget_mb" arena megabytes one launch may take (default: three quarters of the device's memory): a call that needs more runs as several launches
  *   "dist_scheme"   prach::dist_kernel's binning of the preamble counts: 0 one LDS atomic per UE, 1 the same into per-wavefront copies of the 256 bins
  *                   (the default: measured fastest), 2 one LDS atomic per distinct value of a wavefront (match and aggregate)
+ *   "timeline_scheme" prach::timeline_kernel's binning: 0 every contribution is a 64-bit global atomic, 1 windows of bins privatised in LDS per workgroup
+ *                   (the default: measured 15-20x faster on the sweep grids)
  *   "calendar_cap", "vmm_fail_after", "noma_ambiguity_test", "noma_host_activation"   test hooks (prach_engine.hip) */
 int prach_engine_set(prach_engine *, const char *key, int64_t value);
 
@@ -255,6 +309,22 @@ int64_t prach_dist_delay_quantile(const prach_dist_spec *, const prach_dist *, c
 size_t prach_dist_format_csv(const prach_dist_spec *, const prach_dist *, const uint64_t *delay_hist, const uint64_t *ptc_hist, const char *label, char *buf,
                              size_t cap);
 int prach_dist_tile_ues(void); /* UEs of one trial that one workgroup of prach::dist_kernel reduces (tests place sizes around it) */
+
+/* Timelines, host side (no device needed).  t and the five series: ONE group (`bins` entries each).
+ * prach_timeline_accumulate_logs ADDS one trial's per-UE log to a group: THE DEFINITION prach::timeline_kernel equals, integer for integer.
+ * PRACH_ERR_UNSUPPORTED: a NOMA_C cfg.  PRACH_ERR_ARG: a bad spec or cfg, nUE != cfg->nUE, or a successful UE with a negative timer or with
+ * c(i) < a(i) (nothing has been added then). */
+int prach_timeline_accumulate_logs(const prach_timeline_spec *, const prach_cfg *cfg, const prach_ue_log *ue, int nUE, prach_timeline *t, uint64_t *arrivals,
+                                   uint64_t *success, uint64_t *sojourn_sum, uint64_t *timer_sum, uint64_t *done);
+/* counts and sums are added, done_max is the maximum.  The series arguments are, for `into` and then for `from`: arrivals, success, sojourn_sum, timer_sum, done */
+void prach_timeline_merge(const prach_timeline_spec *, prach_timeline *into, uint64_t *const into_series[5], const prach_timeline *from,
+                          const uint64_t *const from_series[5]);
+/* one group as text: `label,<series>,<lower edge ms>,<value>` per non-zero bin, series by series (arrivals, success, sojourn_sum, timer_sum, done), with
+ * `label,arrivals,overflow,<count>` behind the arrivals and `label,done,overflow,<count>` behind the done lines where the counter is non-zero; lines end in \n.
+ * Returns the length needed (without the terminating 0); the text is written only if it fits cap with its terminator. */
+size_t prach_timeline_format_csv(const prach_timeline_spec *, const prach_timeline *, const uint64_t *const series[5], const char *label, char *buf, size_t cap);
+int prach_timeline_tile_ues(void);    /* UEs of one trial that one workgroup of prach::timeline_kernel reduces (tests place sizes around it) */
+int prach_timeline_window_bins(void); /* bins of the LDS windows of prach::timeline_kernel (timeline_scheme 1), anchored at a tile's first arrival bin */
 
 /* Text surfaces, byte-compatible with the reference (latency values excepted) */
 size_t prach_format_logs(const prach_ue_log *ue, int nUE, char *buf, size_t cap);           /* Beta.c:501 */
