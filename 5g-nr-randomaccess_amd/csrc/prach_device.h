@@ -188,7 +188,7 @@ hipError_t launch_dist_kernel(const DistJob *jobs, int njobs, int workgroups, in
 // flushes the non-zero ones; what falls outside, and everything under scheme 0, goes straight to the call's buffers with 64-bit agent-scope atomics.
 constexpr int TL_TILE = 8192, TL_THREADS = 256, TL_WINDOW = 2048;
 constexpr int TL_MAX_SOJOURN = 60000 + 6; // c(i) - a(i) at most: Uniform arrivals run 60 000 subframes, the completion is 6 behind the last Msg3
-static_assert((unsigned long long)TL_TILE * TL_MAX_SOJOURN < (1ull << 32), "a 32-bit LDS counter holds the sojourn sum of a whole tile");
+static_assert((unsigned long long)TL_TILE * TL_MAX_SOJOURN < (1ull << 32), "a 32-bit LDS counter holds the sojourn sum, and the timer sum, of a whole tile");
 constexpr int TL_SCALARS = 8; // per group: arrived, success, restarted, arrival_overflow, done_overflow, sojourn_sum, timer_sum, done_max + 1 (0: no successful UE)
 struct TimelineJob {
     const int4 *logs; // [nUE][4] prach_ue_log records

@@ -92,7 +92,9 @@ __global__ __launch_bounds__(TL_THREADS) void timeline_kernel(const TimelineJob 
         ssum += soj;
         tsum += timer;
         dmax1 = max(dmax1, c + 1u);
-        if (awin && soj <= (unsigned)TL_MAX_SOJOURN) { // (a sum past the 32-bit budget of a tile cannot come from a simulation kernel; it would go the exact way)
+        // (a sum past the 32-bit budget of a tile cannot come from a simulation kernel, whose timer never exceeds the sojourn; the definition takes any
+        // timer >= 0, so both addends are held to the budget and a larger one goes the exact way)
+        if (awin && soj <= (unsigned)TL_MAX_SOJOURN && timer <= (unsigned)TL_MAX_SOJOURN) {
             atomicAdd(&lwin[4 * (ab - bin0) + 1], 1u);
             atomicAdd(&lwin[4 * (ab - bin0) + 2], soj);
             atomicAdd(&lwin[4 * (ab - bin0) + 3], timer);

@@ -12,6 +12,7 @@ from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
 from kernel_matrix import ROWS  # noqa: E402
+from reduce_cases import bincount_dist  # noqa: E402  (np.bincount form of the distributions over int32 [nUE, 16] per-UE arrays)
 
 pytestmark = pytest.mark.gpu
 
@@ -28,22 +29,6 @@ def eng(pkg):
     e = pkg.Engine(0)
     yield e
     e.close()
-
-
-def bincount_dist(pkg, ue_arrays, bins, width, groups, ngroups):
-    """np.bincount form of the distributions over int32 [nUE, 16] per-UE arrays."""
-    d = pkg.Dist(ngroups, bins, width)
-    for a, g in zip(ue_arrays, groups):
-        ok = a[:, FLAG] == 1
-        t, p = a[ok, TIMER].astype(np.int64), a[ok, PTC].astype(np.int64)
-        b = t // width
-        d.delay_hist[g] += np.bincount(b[b < bins], minlength=bins).astype(np.uint64)
-        d.ptc_hist[g] += np.bincount(np.minimum(p, 255), minlength=256).astype(np.uint64)
-        d.trials[g] += 1; d.ues[g] += len(a); d.success[g] += t.size; d.delay_overflow[g] += int((b >= bins).sum())
-        d.delay_sum[g] += int(t.sum()); d.ptc_sum[g] += int(p.sum())
-        if t.size:
-            d.delay_max[g] = max(int(d.delay_max[g]), int(t.max()))
-    return d
 
 
 def as_array(log):
