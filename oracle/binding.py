@@ -222,3 +222,61 @@ def noma_format_line(cfg, res) -> bytes:
     buf = C.create_string_buffer(256)
     n = L.noma_format_result_line(C.byref(cfg), C.byref(res), buf, 256)
     return buf.raw[:n]
+
+
+def noma_group_sector(idx, gain, nGrantUL, nonsector, draws, logs_in=None):
+    """The grouping of ONE sector by the function the NOMA trial loop calls per sector (noma_oracle.c: noma_group_sector): `idx`, `gain` the
+    singleton transmitters in preamble order, `draws[grant][which]` the decode draws.  Returns (granted indices in the order msg2 is set,
+    [(grant, which), ...] the draws consumed in order, the natural logs of the gains from the C library's log)."""
+    import numpy as np
+    L = lib()
+    L.noma_oracle_group_sector.restype = C.c_int
+    L.noma_oracle_group_sector.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    gain = np.ascontiguousarray(gain, dtype=np.float64)
+    draws = np.ascontiguousarray(draws, dtype=np.int32).reshape(-1, 2)
+    n = len(idx)
+    assert len(gain) == n
+    granted = np.zeros(n, dtype=np.int32)
+    consumed = np.zeros(max(1, 4 * nGrantUL), dtype=np.int32)
+    logs = np.zeros(n, dtype=np.float64)
+    ng, nc = C.c_int32(0), C.c_int32(0)
+    li = None if logs_in is None else np.ascontiguousarray(logs_in, dtype=np.float64)  # (a table that is not the log of the gains: one crafted case)
+    rc = L.noma_oracle_group_sector(idx.ctypes.data, gain.ctypes.data, n, nGrantUL, nonsector, draws.ctypes.data, len(draws), granted.ctypes.data,
+                                    C.byref(ng), consumed.ctypes.data, C.byref(nc), logs.ctypes.data, li.ctypes.data if li is not None else None)
+    if rc != 0:
+        raise RuntimeError(f"noma_oracle_group_sector rc={rc}")
+    return granted[:ng.value].tolist(), [tuple(p) for p in consumed[:2 * nc.value].reshape(-1, 2).tolist()], logs
+
+
+def noma_run_trial_traced(cfg: NomaCfg, rng: Rng, cap_sectors=20000):
+    """noma_run_trial with every sector the trial loop resolved recorded: (res, [dict(slot, sector, idx, gain, granted, draws=[(grant, which,
+    value), ...]), ...])."""
+    import numpy as np
+    L = lib()
+    L.noma_oracle_set_sector_trace.restype = None
+    L.noma_oracle_set_sector_trace.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    per = 5 + 2 * cfg.nPreamble + 6 * cfg.nGrantUL
+    words = np.zeros(cap_sectors * per, dtype=np.int32)
+    gains = np.zeros(cap_sectors * cfg.nPreamble, dtype=np.float64)
+    used = np.zeros(4, dtype=np.int32)
+    L.noma_oracle_set_sector_trace(words.ctypes.data, len(words), gains.ctypes.data, len(gains), used.ctypes.data)
+    try:
+        res, _ = noma_run_trial(cfg, rng, want_ues=False)
+    finally:
+        L.noma_oracle_set_sector_trace(None, 0, None, 0, None)
+    if used[3]:
+        raise RuntimeError(f"sector trace: {used[3]} sectors dropped")
+    out, w, g = [], 0, 0
+    for _ in range(int(used[2])):
+        slot, sector, count, ngr, nd = (int(v) for v in words[w:w + 5])
+        w += 5
+        rec = dict(slot=slot, sector=sector, idx=words[w:w + count].copy(), gain=gains[g:g + count].copy(),
+                   granted=words[w + count:w + count + ngr].tolist(),
+                   draws=[tuple(t) for t in words[w + count + ngr:w + count + ngr + 3 * nd].reshape(-1, 3).tolist()])
+        w += count + ngr + 3 * nd
+        g += count
+        out.append(rec)
+    assert w == used[0] and g == used[1]
+    return res, out

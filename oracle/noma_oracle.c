@@ -106,7 +106,86 @@ static void activeUE(nctx_t *c, nue_t *user, int time) {
     user->channelGain = ch_g;
 }
 
-typedef struct { int idx; double channelGain; } tx_t;
+typedef struct { int idx; double channelGain, lg; } tx_t; /* lg: log(channelGain), the C library's */
+
+typedef int (*noma_draw_fn)(void *ctx, int grant, int which); /* decode draw `which` (0, 1) of the sector's grant-th pair */
+typedef void (*noma_grant_fn)(void *ctx, int idx);            /* msg2 = 1 */
+
+/* ONE sector's singleton transmitters txUEs[0 .. count) (preamble order, count > 0) onto the sector's grants: the count <= nGrantUL shortcut
+ * (NOMA.c:245-250 / :377-382), else the sort, the pairing and the leftovers (NOMA.c:251-307 / :383-437).  Called by the trial loop below and by
+ * noma_oracle_group_sector; sorts txUEs in place and marks paired entries with idx = -1. */
+static void noma_group_sector(tx_t *txUEs, int count, int nGrantUL, int nonsector, int *grantCheck, noma_draw_fn draw, void *dctx, noma_grant_fn grant,
+                              void *gctx) {
+    if (count <= nGrantUL) {
+        for (int i = 0; i < count; i++) {
+            if (nonsector) { /* NOMA.c:377-382: msg2 = 1 sits OUTSIDE the budget test */
+                if (*grantCheck < nGrantUL) (*grantCheck)++;
+                grant(gctx, txUEs[i].idx);
+            } else if (*grantCheck < nGrantUL) { (*grantCheck)++; grant(gctx, txUEs[i].idx); } /* NOMA.c:245-250 */
+        }
+        return;
+    }
+    for (int i = 0; i < count; i++) /* sortUE: bubble sort, strict < (stable), NOMA.c:90-103 */
+        for (int j = 0; j < count - 1; j++)
+            if (txUEs[j + 1].channelGain < txUEs[j].channelGain) { tx_t t = txUEs[j]; txUEs[j] = txUEs[j + 1]; txUEs[j + 1] = t; }
+    int pair = 0;
+    for (int i = 0; i < count - 1; i++) {
+        for (int j = 0 + 1; j < count; j++) {
+            int rx[2] = {txUEs[i].idx, txUEs[j].idx};
+            double llow = txUEs[i].lg, lhigh = txUEs[j].lg; /* log(low), log(high) */
+            if (rx[0] != -1 && rx[1] != -1 && 10 * lhigh - 10 * llow > 15.) {
+                pair += 2;
+                txUEs[i].idx = -1;
+                txUEs[j].idx = -1;
+                if (*grantCheck < nGrantUL) {
+                    const int gi = *grantCheck;
+                    (*grantCheck)++;
+                    double p = (double)draw(dctx, gi, 0) / (double)2147483647;
+                    if (p < 0.3) {
+                        if (nonsector) grant(gctx, rx[0]); /* NOMA.c:413-415: always the weaker UE, no second draw */
+                        else {
+                            int randomUE = draw(dctx, gi, 1) % 2; /* NOMA.c:287-290 */
+                            grant(gctx, rx[randomUE]);
+                        }
+                    } else {
+                        grant(gctx, rx[0]);
+                        grant(gctx, rx[1]);
+                    }
+                }
+                break;
+            }
+        }
+    }
+    if (count - pair > 0)
+        for (int i = 0; i < count; i++)
+            if (txUEs[i].idx != -1 && *grantCheck < nGrantUL) { (*grantCheck)++; grant(gctx, txUEs[i].idx); }
+}
+
+/* test hook: the NEXT noma_oracle_run_trial calls record every sector with a singleton, as the trial loop resolved it.  words: per sector
+ * [slot, sector, count, ngranted, ndraws, idx[count], granted[ngranted], (grant, which, value)[ndraws]]; gains: channelGain[count] per sector;
+ * used[0 .. 4) = words written, gains written, sectors recorded, sectors dropped for want of room.  NULL: off. */
+static struct { int32_t *words; double *gains; int32_t *used; int cap_words, cap_gains; } g_trace;
+void noma_oracle_set_sector_trace(int32_t *words, int cap_words, double *gains, int cap_gains, int32_t *used) {
+    g_trace.words = words; g_trace.cap_words = cap_words; g_trace.gains = gains; g_trace.cap_gains = cap_gains; g_trace.used = used;
+    if (used) used[0] = used[1] = used[2] = used[3] = 0;
+}
+
+typedef struct { nctx_t *c; int slot, sector, ngranted, ndraws; int granted[256], draws[3 * 512]; } trial_sector_t;
+
+static int trial_draw(void *ctx, int grant, int which) {
+    trial_sector_t *t = (trial_sector_t *)ctx;
+    const int v = pair_draw(t->c, t->slot, t->sector, grant, which);
+    if (t->ndraws < 512) { t->draws[3 * t->ndraws] = grant; t->draws[3 * t->ndraws + 1] = which; t->draws[3 * t->ndraws + 2] = v; }
+    t->ndraws++;
+    return v;
+}
+
+static void trial_grant(void *ctx, int idx) {
+    trial_sector_t *t = (trial_sector_t *)ctx;
+    t->c->UE[idx].msg2 = 1;
+    if (t->ngranted < 256) t->granted[t->ngranted] = idx;
+    t->ngranted++;
+}
 
 /* NOMA.c:194-324 */
 static void preambleSectorCollisionDetection(nctx_t *c, int activeCheck, int time, int *grantCheck, int *tmpIdx, int *cnt, int *who) {
@@ -116,7 +195,7 @@ static void preambleSectorCollisionDetection(nctx_t *c, int activeCheck, int tim
     tx_t txUEs[256];
     (void)tmpIdx;
     /* k->nonsector: the cell-wide variant preambleCollisionDetection (NOMA.c:325-447; its call at NOMA.c:688 is commented out in
-     * the reference): ONE group and ONE grant budget; it differs from the per-sector function in exactly two more places, marked below */
+     * the reference): ONE group and ONE grant budget; it differs from the per-sector function in exactly two more places, marked in noma_group_sector */
     const int nonsector = k->nonsector != 0, nsect = nonsector ? 1 : 6;
     /* per (sector, preamble): count and the (only relevant) member when count == 1 */
     memset(cnt, 0, sizeof(int) * 6 * (size_t)nP);
@@ -129,52 +208,60 @@ static void preambleSectorCollisionDetection(nctx_t *c, int activeCheck, int tim
     for (int s = 0; s < nsect; s++) {
         int count = 0;
         for (int p = 0; p < nP; p++)
-            if (cnt[s * nP + p] == 1) { txUEs[count].idx = who[s * nP + p]; txUEs[count].channelGain = user[who[s * nP + p]].channelGain; count++; }
+            if (cnt[s * nP + p] == 1) {
+                txUEs[count].idx = who[s * nP + p]; txUEs[count].channelGain = user[who[s * nP + p]].channelGain; txUEs[count].lg = log(txUEs[count].channelGain);
+                count++;
+            }
         if (count <= 0) continue;
-        if (count <= nGrantUL) {
-            for (int i = 0; i < count; i++) {
-                if (nonsector) { /* NOMA.c:377-382: msg2 = 1 sits OUTSIDE the budget test */
-                    if (grantCheck[s] < nGrantUL) grantCheck[s]++;
-                    user[txUEs[i].idx].msg2 = 1;
-                } else if (grantCheck[s] < nGrantUL) { grantCheck[s]++; user[txUEs[i].idx].msg2 = 1; } /* NOMA.c:245-250 */
-            }
-        } else {
-            for (int i = 0; i < count; i++) /* sortUE: bubble sort, strict < (stable), NOMA.c:90-103 */
-                for (int j = 0; j < count - 1; j++)
-                    if (txUEs[j + 1].channelGain < txUEs[j].channelGain) { tx_t t = txUEs[j]; txUEs[j] = txUEs[j + 1]; txUEs[j + 1] = t; }
-            int pair = 0;
-            for (int i = 0; i < count - 1; i++) {
-                for (int j = 0 + 1; j < count; j++) {
-                    int rx[2] = {txUEs[i].idx, txUEs[j].idx};
-                    double low = txUEs[i].channelGain, high = txUEs[j].channelGain;
-                    if (rx[0] != -1 && rx[1] != -1 && 10 * log(high) - 10 * log(low) > 15.) {
-                        pair += 2;
-                        txUEs[i].idx = -1;
-                        txUEs[j].idx = -1;
-                        if (grantCheck[s] < nGrantUL) {
-                            const int gi = grantCheck[s];
-                            grantCheck[s]++;
-                            double p = (double)pair_draw(c, time / k->accessTime, s, gi, 0) / (double)2147483647;
-                            if (p < 0.3) {
-                                if (nonsector) user[rx[0]].msg2 = 1; /* NOMA.c:413-415: always the weaker UE, no second draw */
-                                else {
-                                    int randomUE = pair_draw(c, time / k->accessTime, s, gi, 1) % 2; /* NOMA.c:287-290 */
-                                    user[rx[randomUE]].msg2 = 1;
-                                }
-                            } else {
-                                user[rx[0]].msg2 = 1;
-                                user[rx[1]].msg2 = 1;
-                            }
-                        }
-                        break;
-                    }
-                }
-            }
-            if (count - pair > 0)
-                for (int i = 0; i < count; i++)
-                    if (txUEs[i].idx != -1 && grantCheck[s] < nGrantUL) { grantCheck[s]++; user[txUEs[i].idx].msg2 = 1; }
-        }
+        trial_sector_t ts;
+        ts.c = c; ts.slot = time / k->accessTime; ts.sector = s; ts.ngranted = 0; ts.ndraws = 0;
+        const int room = g_trace.words && g_trace.used[0] + 5 + 2 * count + 3 * 2 * nGrantUL <= g_trace.cap_words && g_trace.used[1] + count <= g_trace.cap_gains &&
+                         count <= 256 && nGrantUL <= 256;
+        int32_t *w = room ? g_trace.words + g_trace.used[0] : NULL;
+        if (room)
+            for (int i = 0; i < count; i++) { w[5 + i] = txUEs[i].idx; g_trace.gains[g_trace.used[1] + i] = txUEs[i].channelGain; }
+        noma_group_sector(txUEs, count, nGrantUL, nonsector, &grantCheck[s], trial_draw, &ts, trial_grant, &ts);
+        if (room) {
+            w[0] = ts.slot; w[1] = s; w[2] = count; w[3] = ts.ngranted; w[4] = ts.ndraws;
+            memcpy(w + 5 + count, ts.granted, sizeof(int) * (size_t)ts.ngranted);
+            memcpy(w + 5 + count + ts.ngranted, ts.draws, sizeof(int) * 3 * (size_t)ts.ndraws);
+            g_trace.used[0] += 5 + count + ts.ngranted + 3 * ts.ndraws; g_trace.used[1] += count; g_trace.used[2]++;
+        } else if (g_trace.words) g_trace.used[3]++;
     }
+}
+
+/* The grouping of ONE sector on its own (tests/tools/resolve_cases.py): the singleton transmitters in preamble order (idx >= 0, gain > 0),
+ * a fresh grant budget, the decode draws from draws[grant][which] (ngrants_in_table rows).  Out: granted[] in the order msg2 is set (room for
+ * count), consumed[] = the (grant, which) pairs drawn, in order (room for 2 x 2 nGrantUL ints), logs[i] = log(gain[i]) as the pairing test
+ * reads it (logs_in != NULL: a table of logs to read instead, for a case whose table is not the log of its gains).  Returns 0; -1 bad arguments;
+ * -3 a draw beyond the table. */
+typedef struct { const int32_t *draws; int rows, bad; int32_t *granted, *consumed; int ngranted, nconsumed; } entry_ctx_t;
+
+static int entry_draw(void *ctx, int grant, int which) {
+    entry_ctx_t *e = (entry_ctx_t *)ctx;
+    e->consumed[2 * e->nconsumed] = grant; e->consumed[2 * e->nconsumed + 1] = which; e->nconsumed++;
+    if (grant < 0 || grant >= e->rows) { e->bad = 1; return 0; }
+    return e->draws[2 * grant + which];
+}
+
+static void entry_grant(void *ctx, int idx) {
+    entry_ctx_t *e = (entry_ctx_t *)ctx;
+    e->granted[e->ngranted++] = idx;
+}
+
+int noma_oracle_group_sector(const int32_t *idx, const double *gain, int count, int nGrantUL, int nonsector, const int32_t *draws, int ngrants_in_table,
+                             int32_t *granted, int32_t *ngranted, int32_t *consumed, int32_t *nconsumed, double *logs, const double *logs_in) {
+    if (!idx || !gain || count <= 0 || count > 256 || nGrantUL < 0 || !granted || !ngranted || !consumed || !nconsumed || !logs) return -1;
+    tx_t txUEs[256];
+    for (int i = 0; i < count; i++) {
+        if (idx[i] < 0 || !(gain[i] > 0)) return -1;
+        txUEs[i].idx = idx[i]; txUEs[i].channelGain = gain[i]; txUEs[i].lg = logs[i] = logs_in ? logs_in[i] : log(gain[i]);
+    }
+    entry_ctx_t e = {draws, ngrants_in_table, 0, granted, consumed, 0, 0};
+    int grantCheck = 0;
+    noma_group_sector(txUEs, count, nGrantUL, nonsector != 0, &grantCheck, entry_draw, &e, entry_grant, &e);
+    *ngranted = e.ngranted; *nconsumed = e.nconsumed;
+    return e.bad ? -3 : 0;
 }
 
 /* NOMA.c:449-498 */
