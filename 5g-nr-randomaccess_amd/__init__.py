@@ -69,9 +69,37 @@ class PrachDist(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in DIST_FIELDS[:-1]] + [("delay_max", C.c_int64)]
 
 
-class Dist:
+class _Reduction:
+    """What Dist and Timeline share.  A subclass names its scalar fields (_FIELDS), the C struct of one group (_STRUCT), the library's merge and its
+    defining parameters (_PARAMS), and gives ``_arrays()`` — its [ngroups, n] uint64 arrays in the order of the C ABI — ``_scalar(f)``, the int64 array of
+    length ngroups of scalar field f, and ``_cargs(g)``, group g's arrays as the library's merge and CSV functions take them."""
+
+    def _group(self, g):
+        return self._STRUCT(*[int(self._scalar(f)[g]) for f in self._FIELDS])
+
+    def _store(self, g, d):
+        for f in self._FIELDS:
+            self._scalar(f)[g] = getattr(d, f)
+
+    def _rows(self, g):
+        return [a[g].ctypes.data_as(C.POINTER(C.c_uint64)) for a in self._arrays()]
+
+    def merge_group(self, g, other, og):
+        """Adds group ``og`` of ``other`` to group ``g`` (prach_dist_merge / prach_timeline_merge)."""
+        sp, a, b = self.spec(), self._group(g), other._group(og)
+        getattr(lib(), self._MERGE)(C.byref(sp), C.byref(a), *self._cargs(g), C.byref(b), *other._cargs(og))
+        self._store(g, a)
+
+    def same_as(self, other):
+        import numpy as np
+        return all(getattr(self, p) == getattr(other, p) for p in self._PARAMS) and all(np.array_equal(x, y) for x, y in zip(self._arrays(), other._arrays())) and \
+            all(np.array_equal(self._scalar(f), other._scalar(f)) for f in self._FIELDS)
+
+
+class Dist(_Reduction):
     """The distributions of ``ngroups`` trial groups (include/prach.h, prach_dist): ``delay_hist`` [ngroups, delay_bins] and ``ptc_hist``
     [ngroups, 256] as numpy uint64, and one int64 array of length ngroups per scalar field of DIST_FIELDS."""
+    _FIELDS, _STRUCT, _MERGE, _PARAMS = DIST_FIELDS, PrachDist, "prach_dist_merge", ("delay_bins", "delay_bin_ms")
 
     def __init__(self, ngroups, delay_bins, delay_bin_ms=1):
         import numpy as np
@@ -85,27 +113,16 @@ class Dist:
     def spec(self):
         return PrachDistSpec(self.delay_bins, self.delay_bin_ms, self.ngroups, 0)
 
-    def _group(self, g):
-        return PrachDist(*[int(getattr(self, f)[g]) for f in DIST_FIELDS])
+    def _arrays(self):
+        return [self.delay_hist, self.ptc_hist]
 
-    def _store(self, g, d):
-        for f in DIST_FIELDS:
-            getattr(self, f)[g] = getattr(d, f)
+    def _scalar(self, f):
+        return getattr(self, f)
 
     def _hists(self, g):
-        u64 = C.POINTER(C.c_uint64)
-        return self.delay_hist[g].ctypes.data_as(u64), self.ptc_hist[g].ctypes.data_as(u64)
+        return tuple(self._rows(g))
 
-    def merge_group(self, g, other, og):
-        """Adds group ``og`` of ``other`` to group ``g`` (prach_dist_merge)."""
-        sp, a, b = self.spec(), self._group(g), other._group(og)
-        lib().prach_dist_merge(C.byref(sp), C.byref(a), *self._hists(g), C.byref(b), *other._hists(og))
-        self._store(g, a)
-
-    def same_as(self, other):
-        import numpy as np
-        return (self.delay_bins, self.delay_bin_ms) == (other.delay_bins, other.delay_bin_ms) and np.array_equal(self.delay_hist, other.delay_hist) and \
-            np.array_equal(self.ptc_hist, other.ptc_hist) and all(np.array_equal(getattr(self, f), getattr(other, f)) for f in DIST_FIELDS)
+    _cargs = _hists
 
 
 TIMELINE_MAX_BINS = 65536
@@ -121,10 +138,11 @@ class PrachTimeline(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in TIMELINE_FIELDS[:-1]] + [("done_max", C.c_int64)]
 
 
-class Timeline:
+class Timeline(_Reduction):
     """The timelines of ``ngroups`` trial groups (include/prach.h, prach_timeline): ``series[name]`` [ngroups, bins] as numpy uint64 for every name of
     TIMELINE_SERIES (bin b covers [b * bin_ms, (b + 1) * bin_ms)), and ``scalars[field]``, one int64 array of length ngroups per field of
     TIMELINE_FIELDS.  (Two dicts: `success` and `sojourn_sum` name a series and a scalar.)"""
+    _FIELDS, _STRUCT, _MERGE, _PARAMS = TIMELINE_FIELDS, PrachTimeline, "prach_timeline_merge", ("bins", "bin_ms")
 
     def __init__(self, ngroups, bins, bin_ms=1):
         import numpy as np
@@ -136,28 +154,18 @@ class Timeline:
     def spec(self):
         return PrachTimelineSpec(self.bins, self.bin_ms, self.ngroups, 0)
 
-    def _group(self, g):
-        return PrachTimeline(*[int(self.scalars[f][g]) for f in TIMELINE_FIELDS])
+    def _arrays(self):
+        return [self.series[n] for n in TIMELINE_SERIES]
 
-    def _store(self, g, t):
-        for f in TIMELINE_FIELDS:
-            self.scalars[f][g] = getattr(t, f)
+    def _scalar(self, f):
+        return self.scalars[f]
 
     def _series(self, g):
         """The five series of group g as the uint64_t *[5] the C side takes."""
-        u64 = C.POINTER(C.c_uint64)
-        return (u64 * 5)(*[self.series[n][g].ctypes.data_as(u64) for n in TIMELINE_SERIES])
+        return (C.POINTER(C.c_uint64) * 5)(*self._rows(g))
 
-    def merge_group(self, g, other, og):
-        """Adds group ``og`` of ``other`` to group ``g`` (prach_timeline_merge)."""
-        sp, a, b = self.spec(), self._group(g), other._group(og)
-        lib().prach_timeline_merge(C.byref(sp), C.byref(a), self._series(g), C.byref(b), other._series(og))
-        self._store(g, a)
-
-    def same_as(self, other):
-        import numpy as np
-        return (self.bins, self.bin_ms) == (other.bins, other.bin_ms) and all(np.array_equal(self.series[n], other.series[n]) for n in TIMELINE_SERIES) and \
-            all(np.array_equal(self.scalars[f], other.scalars[f]) for f in TIMELINE_FIELDS)
+    def _cargs(self, g):
+        return (self._series(g),)
 
 
 class PrachError(RuntimeError):
@@ -289,65 +297,44 @@ class Engine:
         if rc != OK:
             raise PrachError(rc, f"(set {key})")
 
-    def run_trials(self, cfgs, want_logs=False):
-        """Run the trials concurrently on the device. Returns (results, logs) — logs[k] is a ctypes
-        array of PrachUeLog or None.  want_logs: True (every trial), False, or the indices of the trials
-        whose per-UE log is wanted (the C ABI takes NULL for the others)."""
+    def _call(self, name, cfgs, want_logs, *more):
+        """What every prach_run_trials* call shares: the config array, the results, the log buffers, the status check.  Returns (results, logs)."""
         n = len(cfgs)
         arr = (PrachCfg * n)(*cfgs)
         res = (PrachResult * n)()
         logs, lp = self._log_buffers(cfgs, want_logs)
-        rc = lib().prach_run_trials(self._h, arr, n, res, lp)
+        rc = getattr(lib(), name)(self._h, arr, n, res, lp, *more)
         if rc != OK:
-            raise PrachError(rc, "(prach_run_trials)")
+            raise PrachError(rc, f"({name})")
         return list(res), logs
+
+    def _call_reduced(self, name, cfgs, red, groups, want_logs):
+        """... with the reduction `red` (a Dist or a Timeline), which takes what the device made.  Returns (results, logs, red)."""
+        sp = red.spec()
+        gg = (red._STRUCT * red.ngroups)()
+        gp = None if groups is None else (C.c_int32 * len(cfgs))(*[int(g) for g in groups])
+        res, logs = self._call(name, cfgs, want_logs, C.byref(sp), gp, gg, *[a.ctypes.data_as(C.POINTER(C.c_uint64)) for a in red._arrays()])
+        for g in range(red.ngroups):
+            red._store(g, gg[g])
+        return res, logs, red
+
+    def run_trials(self, cfgs, want_logs=False):
+        """Run the trials concurrently on the device. Returns (results, logs) — logs[k] is a ctypes
+        array of PrachUeLog or None.  want_logs: True (every trial), False, or the indices of the trials
+        whose per-UE log is wanted (the C ABI takes NULL for the others)."""
+        return self._call("prach_run_trials", cfgs, want_logs)
 
     def run_trials_dist(self, cfgs, delay_bins, delay_bin_ms=1, groups=None, want_logs=False, ngroups=None):
         """run_trials plus the distributions of access delay and preamble transmissions of the successful UEs, reduced on the device
         (prach_run_trials_dist).  groups: the group of every trial (None: one group per trial); ngroups: the number of groups (default: the
         largest group id + 1).  Returns (results, logs, Dist)."""
-        n = len(cfgs)
-        if ngroups is None:
-            ngroups = n if groups is None else int(max(groups)) + 1
-        return self._run_dist(cfgs, Dist(ngroups, delay_bins, delay_bin_ms), groups, want_logs)
-
-    def _run_dist(self, cfgs, dist, groups, want_logs):
-        n = len(cfgs)
-        arr = (PrachCfg * n)(*cfgs)
-        res = (PrachResult * n)()
-        logs, lp = self._log_buffers(cfgs, want_logs)
-        sp = dist.spec()
-        dd = (PrachDist * dist.ngroups)()
-        gp = None if groups is None else (C.c_int32 * n)(*[int(g) for g in groups])
-        u64 = C.POINTER(C.c_uint64)
-        rc = lib().prach_run_trials_dist(self._h, arr, n, res, lp, C.byref(sp), gp, dd, dist.delay_hist.ctypes.data_as(u64), dist.ptc_hist.ctypes.data_as(u64))
-        if rc != OK:
-            raise PrachError(rc, "(prach_run_trials_dist)")
-        for g in range(dist.ngroups):
-            dist._store(g, dd[g])
-        return list(res), logs, dist
+        return self._call_reduced("prach_run_trials_dist", cfgs, Dist(_ngroups(len(cfgs), groups, ngroups), delay_bins, delay_bin_ms), groups, want_logs)
 
     def run_trials_timeline(self, cfgs, bins, bin_ms=1, groups=None, want_logs=False, ngroups=None):
         """run_trials plus the timelines per trial group — arrivals, successes, sojourn and timer sums by arrival time, completions by completion time —
         reduced on the device from the per-UE log records the simulation kernels leave there (prach_run_trials_timeline; Beta.c and
         RandomAccessWithNOMA trials only).  groups / ngroups / want_logs as in run_trials_dist.  Returns (results, logs, Timeline)."""
-        n = len(cfgs)
-        if ngroups is None:
-            ngroups = n if groups is None else int(max(groups)) + 1
-        tl = Timeline(ngroups, bins, bin_ms)
-        arr = (PrachCfg * n)(*cfgs)
-        res = (PrachResult * n)()
-        logs, lp = self._log_buffers(cfgs, want_logs)
-        sp = tl.spec()
-        tt = (PrachTimeline * tl.ngroups)()
-        gp = None if groups is None else (C.c_int32 * n)(*[int(g) for g in groups])
-        u64 = C.POINTER(C.c_uint64)
-        rc = lib().prach_run_trials_timeline(self._h, arr, n, res, lp, C.byref(sp), gp, tt, *[tl.series[s].ctypes.data_as(u64) for s in TIMELINE_SERIES])
-        if rc != OK:
-            raise PrachError(rc, "(prach_run_trials_timeline)")
-        for g in range(tl.ngroups):
-            tl._store(g, tt[g])
-        return list(res), logs, tl
+        return self._call_reduced("prach_run_trials_timeline", cfgs, Timeline(_ngroups(len(cfgs), groups, ngroups), bins, bin_ms), groups, want_logs)
 
     @staticmethod
     def _log_buffers(cfgs, want_logs):
@@ -462,28 +449,52 @@ def dist_tile_ues() -> int:
     return lib().prach_dist_tile_ues()
 
 
+def _ngroups(n, groups, ngroups):
+    """The number of groups of n trials: as given, or one per trial without a group table, or the largest group id + 1."""
+    return ngroups if ngroups is not None else n if groups is None else int(max(groups)) + 1
+
+
+def _log_ptr(lg):
+    """One trial's per-UE log — a ctypes array of PrachUeLog or an int32 array of shape [nUE, 16] — as (pointer, nUE, what keeps the memory alive)."""
+    import numpy as np
+    if isinstance(lg, np.ndarray):
+        a = np.ascontiguousarray(lg, dtype=np.int32).reshape(-1, 16)
+        return a.ctypes.data_as(C.POINTER(PrachUeLog)), a.shape[0], a
+    return C.cast(lg, C.POINTER(PrachUeLog)), len(lg), lg
+
+
+def _from_logs(name, red, logs, groups, cfgs=None):
+    """Adds every log to its group of `red` with the library's host-side definition `name` (which takes the trial's config in front of the log, if cfgs)."""
+    sp = red.spec()
+    for k, lg in enumerate(logs):
+        g = k if groups is None else int(groups[k])
+        ptr, nue, _keep = _log_ptr(lg)
+        d = red._group(g)
+        rc = getattr(lib(), name)(C.byref(sp), *([C.byref(cfgs[k])] if cfgs is not None else []), ptr, nue, C.byref(d), *red._rows(g))
+        if rc != OK:
+            raise PrachError(rc, f"({name})")
+        red._store(g, d)
+    return red
+
+
+def _csv(name, red, labels):
+    """The CSV text of every group of `red` from the library's formatter `name`: asked for its size first, then filled."""
+    out = b""
+    sp = red.spec()
+    for g in range(red.ngroups):
+        d = red._group(g)
+        args = (C.byref(sp), C.byref(d), *red._cargs(g), str(g if labels is None else labels[g]).encode())
+        need = getattr(lib(), name)(*args, None, 0)
+        buf = C.create_string_buffer(need + 1)
+        n = getattr(lib(), name)(*args, buf, need + 1)
+        out += buf.raw[:n]
+    return out
+
+
 def dist_from_logs(logs, delay_bins, delay_bin_ms=1, groups=None, ngroups=None) -> Dist:
     """The host-side definition of the distributions (prach_dist_accumulate_logs): logs[k] is one trial's per-UE log — a ctypes array of PrachUeLog
     or an int32 array of shape [nUE, 16] — added to group groups[k] (None: group k)."""
-    import numpy as np
-    n = len(logs)
-    if ngroups is None:
-        ngroups = n if groups is None else int(max(groups)) + 1
-    dist = Dist(ngroups, delay_bins, delay_bin_ms)
-    sp = dist.spec()
-    for k, lg in enumerate(logs):
-        g = k if groups is None else int(groups[k])
-        if isinstance(lg, np.ndarray):
-            a = np.ascontiguousarray(lg, dtype=np.int32).reshape(-1, 16)
-            ptr, nue = a.ctypes.data_as(C.POINTER(PrachUeLog)), a.shape[0]
-        else:
-            ptr, nue = C.cast(lg, C.POINTER(PrachUeLog)), len(lg)
-        d = dist._group(g)
-        rc = lib().prach_dist_accumulate_logs(C.byref(sp), ptr, nue, C.byref(d), *dist._hists(g))
-        if rc != OK:
-            raise PrachError(rc, "(prach_dist_accumulate_logs)")
-        dist._store(g, d)
-    return dist
+    return _from_logs("prach_dist_accumulate_logs", Dist(_ngroups(len(logs), groups, ngroups), delay_bins, delay_bin_ms), logs, groups)
 
 
 def dist_quantile(dist: Dist, g: int, q: float) -> int:
@@ -494,17 +505,7 @@ def dist_quantile(dist: Dist, g: int, q: float) -> int:
 
 def dist_csv(dist: Dist, labels=None) -> bytes:
     """The CSV text of every group (prach_dist_format_csv), labelled labels[g] (default: the group number)."""
-    out = b""
-    sp = dist.spec()
-    for g in range(dist.ngroups):
-        label = str(g if labels is None else labels[g]).encode()
-        d = dist._group(g)
-        dh, ph = dist._hists(g)
-        need = lib().prach_dist_format_csv(C.byref(sp), C.byref(d), dh, ph, label, None, 0)
-        buf = C.create_string_buffer(need + 1)
-        n = lib().prach_dist_format_csv(C.byref(sp), C.byref(d), dh, ph, label, buf, need + 1)
-        out += buf.raw[:n]
-    return out
+    return _csv("prach_dist_format_csv", dist, labels)
 
 
 def timeline_tile_ues() -> int:
@@ -518,37 +519,9 @@ def timeline_window_bins() -> int:
 def timeline_from_logs(cfgs, logs, bins, bin_ms=1, groups=None, ngroups=None) -> Timeline:
     """The host-side definition of the timelines (prach_timeline_accumulate_logs): logs[k] is the per-UE log of the trial with config cfgs[k] — a ctypes
     array of PrachUeLog or an int32 array of shape [nUE, 16] — added to group groups[k] (None: group k)."""
-    import numpy as np
-    n = len(logs)
-    if ngroups is None:
-        ngroups = n if groups is None else int(max(groups)) + 1
-    tl = Timeline(ngroups, bins, bin_ms)
-    sp = tl.spec()
-    u64 = C.POINTER(C.c_uint64)
-    for k, lg in enumerate(logs):
-        g = k if groups is None else int(groups[k])
-        if isinstance(lg, np.ndarray):
-            a = np.ascontiguousarray(lg, dtype=np.int32).reshape(-1, 16)
-            ptr, nue = a.ctypes.data_as(C.POINTER(PrachUeLog)), a.shape[0]
-        else:
-            ptr, nue = C.cast(lg, C.POINTER(PrachUeLog)), len(lg)
-        t = tl._group(g)
-        rc = lib().prach_timeline_accumulate_logs(C.byref(sp), C.byref(cfgs[k]), ptr, nue, C.byref(t), *[tl.series[s][g].ctypes.data_as(u64) for s in TIMELINE_SERIES])
-        if rc != OK:
-            raise PrachError(rc, "(prach_timeline_accumulate_logs)")
-        tl._store(g, t)
-    return tl
+    return _from_logs("prach_timeline_accumulate_logs", Timeline(_ngroups(len(logs), groups, ngroups), bins, bin_ms), logs, groups, cfgs)
 
 
 def timeline_csv(tl: Timeline, labels=None) -> bytes:
     """The CSV text of every group (prach_timeline_format_csv), labelled labels[g] (default: the group number)."""
-    out = b""
-    sp = tl.spec()
-    for g in range(tl.ngroups):
-        label = str(g if labels is None else labels[g]).encode()
-        t, ser = tl._group(g), tl._series(g)
-        need = lib().prach_timeline_format_csv(C.byref(sp), C.byref(t), ser, label, None, 0)
-        buf = C.create_string_buffer(need + 1)
-        n = lib().prach_timeline_format_csv(C.byref(sp), C.byref(t), ser, label, buf, need + 1)
-        out += buf.raw[:n]
-    return out
+    return _csv("prach_timeline_format_csv", tl, labels)

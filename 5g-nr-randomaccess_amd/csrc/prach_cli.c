@@ -90,60 +90,72 @@ static double now_s(void) {
     return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
+/* The reduction a run makes on the device next to its results: the distributions (--cdf, prach_run_trials_dist) or the timelines (--timeline,
+ * prach_run_trials_timeline), never both; neither spec: none, plain prach_run_trials.  A block holds the groups of one worker or of one call, one group per
+ * sweep point: --cdf prach_dist[npts] | delay_hist[npts][bins] | ptc_hist[npts][256]; --timeline prach_timeline[npts] | five series [npts][bins] each
+ * (arrivals, success, sojourn_sum, timer_sum, done). */
+typedef struct reduction {
+    const prach_dist_spec *cdf;
+    const prach_timeline_spec *tl;
+    const char *path; /* the CSV file */
+    size_t text_cap;  /* the CSV text of one group at most */
+} reduction;
+static int red_on(const reduction *r) { return r->cdf || r->tl; }
+static size_t red_block_bytes(const reduction *r) {
+    if (r->tl) return (size_t)r->tl->ngroups * (sizeof(prach_timeline) + 5 * 8 * (size_t)r->tl->bins);
+    return r->cdf ? (size_t)r->cdf->ngroups * (sizeof(prach_dist) + 8 * ((size_t)r->cdf->delay_bins + PRACH_DIST_PTC_BINS)) : 0;
+}
+/* group g of block b: --cdf its q-th histogram (0 delay, 1 preamble count), --timeline its q-th series */
+static uint64_t *red_array(const reduction *r, char *b, int q, int g) {
+    if (r->tl) return (uint64_t *)(b + (size_t)r->tl->ngroups * sizeof(prach_timeline)) + ((size_t)q * (size_t)r->tl->ngroups + (size_t)g) * (size_t)r->tl->bins;
+    uint64_t *const dh = (uint64_t *)(b + (size_t)r->cdf->ngroups * sizeof(prach_dist));
+    return q == 0 ? dh + (size_t)g * (size_t)r->cdf->delay_bins : dh + (size_t)r->cdf->ngroups * (size_t)r->cdf->delay_bins + (size_t)g * PRACH_DIST_PTC_BINS;
+}
+/* a zero-filled block becomes one of empty groups */
+static void red_init_block(const reduction *r, char *b) {
+    for (int g = 0; r->tl && g < r->tl->ngroups; g++) ((prach_timeline *)b)[g].done_max = -1;
+    for (int g = 0; r->cdf && g < r->cdf->ngroups; g++) ((prach_dist *)b)[g].delay_max = -1;
+}
+static void red_merge_block(const reduction *r, char *into, char *from) {
+    for (int g = 0; r->tl && g < r->tl->ngroups; g++) {
+        uint64_t *a[5];
+        const uint64_t *b[5];
+        for (int q = 0; q < 5; q++) { a[q] = red_array(r, into, q, g); b[q] = red_array(r, from, q, g); }
+        prach_timeline_merge(r->tl, (prach_timeline *)into + g, a, (prach_timeline *)from + g, b);
+    }
+    for (int g = 0; r->cdf && g < r->cdf->ngroups; g++)
+        prach_dist_merge(r->cdf, (prach_dist *)into + g, red_array(r, into, 0, g), red_array(r, into, 1, g), (prach_dist *)from + g, red_array(r, from, 0, g), red_array(r, from, 1, g));
+}
+/* the CSV text of group g of block b; returns its length (>= cap: it did not fit) */
+static size_t red_format_group(const reduction *r, char *b, int g, const char *label, char *out, size_t cap) {
+    if (r->tl) {
+        const uint64_t *ser[5];
+        for (int q = 0; q < 5; q++) ser[q] = red_array(r, b, q, g);
+        return prach_timeline_format_csv(r->tl, (prach_timeline *)b + g, ser, label, out, cap);
+    }
+    return prach_dist_format_csv(r->cdf, (prach_dist *)b + g, red_array(r, b, 0, g), red_array(r, b, 1, g), label, out, cap);
+}
+
+/* one call into the library with the run's reduction: its groups (group = sweep point, grp[k]) come back in call_block and are merged into the worker's block */
+static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *r, prach_ue_log *const *logs, const reduction *red, const int32_t *grp,
+                    char *call_block, char *worker_block) {
+    if (!red_on(red)) return prach_run_trials(eng, c, n, r, logs);
+    char *const b = call_block;
+    const int rc = red->tl ? prach_run_trials_timeline(eng, c, n, r, logs, red->tl, grp, (prach_timeline *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0),
+                                                       red_array(red, b, 2, 0), red_array(red, b, 3, 0), red_array(red, b, 4, 0))
+                           : prach_run_trials_dist(eng, c, n, r, logs, red->cdf, grp, (prach_dist *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0));
+    if (rc == PRACH_OK) red_merge_block(red, worker_block, call_block);
+    return rc;
+}
+
 /* One worker = one device: runs the trials idx[0..m) of the grid on `device` and leaves every prach_result in the (shared)
  * array `res`; per-trial files are written by the worker itself (independent files).  Philox trials go out in calls of up to
  * 1024 trials (one workgroup or cluster per trial); in glibc mode `idx` holds whole seeds in grid order and the sweep of a
  * seed is chained through cfg.stream_offset like the reference's single srand() per seed (WithNOMA:219-221): one call per
  * sweep point with all the worker's seeds in it.  Returns 0 or an exit code. */
-/* A worker's distributions (--cdf): prach_dist[npts] | delay_hist[npts][bins] | ptc_hist[npts][256], one group per sweep point */
-static size_t cdf_block_bytes(const prach_dist_spec *s) {
-    return (size_t)s->ngroups * (sizeof(prach_dist) + 8 * ((size_t)s->delay_bins + PRACH_DIST_PTC_BINS));
-}
-static prach_dist *cdf_d(const prach_dist_spec *s, char *b) { (void)s; return (prach_dist *)b; }
-static uint64_t *cdf_dh(const prach_dist_spec *s, char *b) { return (uint64_t *)(b + (size_t)s->ngroups * sizeof(prach_dist)); }
-static uint64_t *cdf_ph(const prach_dist_spec *s, char *b) { return cdf_dh(s, b) + (size_t)s->ngroups * (size_t)s->delay_bins; }
-static void cdf_merge_block(const prach_dist_spec *s, char *into, char *from) {
-    for (int g = 0; g < s->ngroups; g++)
-        prach_dist_merge(s, cdf_d(s, into) + g, cdf_dh(s, into) + (size_t)g * (size_t)s->delay_bins, cdf_ph(s, into) + (size_t)g * PRACH_DIST_PTC_BINS,
-                         cdf_d(s, from) + g, cdf_dh(s, from) + (size_t)g * (size_t)s->delay_bins, cdf_ph(s, from) + (size_t)g * PRACH_DIST_PTC_BINS);
-}
-/* A worker's timelines (--timeline): prach_timeline[npts] | five series [npts][bins] each (arrivals, success, sojourn_sum, timer_sum, done) */
-static size_t tl_block_bytes(const prach_timeline_spec *s) { return (size_t)s->ngroups * (sizeof(prach_timeline) + 5 * 8 * (size_t)s->bins); }
-static prach_timeline *tl_t(char *b) { return (prach_timeline *)b; }
-static uint64_t *tl_series(const prach_timeline_spec *s, char *b, int q, int g) {
-    return (uint64_t *)(b + (size_t)s->ngroups * sizeof(prach_timeline)) + ((size_t)q * (size_t)s->ngroups + (size_t)g) * (size_t)s->bins;
-}
-static void tl_merge_block(const prach_timeline_spec *s, char *into, char *from) {
-    for (int g = 0; g < s->ngroups; g++) {
-        uint64_t *a[5];
-        const uint64_t *b[5];
-        for (int q = 0; q < 5; q++) { a[q] = tl_series(s, into, q, g); b[q] = tl_series(s, from, q, g); }
-        prach_timeline_merge(s, tl_t(into) + g, a, tl_t(from) + g, b);
-    }
-}
-/* what a call reduces on the device next to its results: the distributions (--cdf), the timelines (--timeline) or nothing */
-typedef struct reduce_spec { const prach_dist_spec *cdf; const prach_timeline_spec *tl; } reduce_spec;
-
-/* prach_run_trials, or with --timeline prach_run_trials_timeline, or with --cdf prach_run_trials_dist: the call's distributions (group = sweep point, grp[k]) are merged into the worker's block */
-static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *r, prach_ue_log *const *logs, reduce_spec red, const int32_t *grp,
-                    char *call_block, char *worker_block) {
-    const prach_dist_spec *const cdf = red.cdf;
-    if (red.tl) {
-        const prach_timeline_spec *const s = red.tl;
-        const int rc = prach_run_trials_timeline(eng, c, n, r, logs, s, grp, tl_t(call_block), tl_series(s, call_block, 0, 0), tl_series(s, call_block, 1, 0),
-                                                 tl_series(s, call_block, 2, 0), tl_series(s, call_block, 3, 0), tl_series(s, call_block, 4, 0));
-        if (rc == PRACH_OK) tl_merge_block(s, worker_block, call_block);
-        return rc;
-    }
-    if (!cdf) return prach_run_trials(eng, c, n, r, logs);
-    const int rc = prach_run_trials_dist(eng, c, n, r, logs, cdf, grp, cdf_d(cdf, call_block), cdf_dh(cdf, call_block), cdf_ph(cdf, call_block));
-    if (rc == PRACH_OK) cdf_merge_block(cdf, worker_block, call_block);
-    return rc;
-}
-
 static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, prach_result *res, double *lat_out, int want_logs,
-                      const char *outdir, int glibc, int npts, reduce_spec red, char *cdf_block) {
-    const int cdf = red.cdf || red.tl; /* (the group table and the call's own block serve either reduction) */
+                      const char *outdir, int glibc, int npts, const reduction *red, char *worker_block) {
+    const int reduces = red_on(red);
     prach_engine *eng = NULL;
     int rc = prach_engine_create(device, &eng);
     if (rc != PRACH_OK) { fprintf(stderr, "prach_sim: device %d: %s\n", device, prach_strerror(rc)); return 2; }
@@ -153,21 +165,21 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
     prach_result *r = (prach_result *)malloc(sizeof(prach_result) * (size_t)(m > 0 ? m : 1));
     prach_ue_log **logs = want_logs ? (prach_ue_log **)calloc((size_t)(m > 0 ? m : 1), sizeof(prach_ue_log *)) : NULL;
     if (!c || !r || (want_logs && !logs)) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
-    int32_t *grp = cdf ? (int32_t *)malloc(sizeof(int32_t) * (size_t)(m > 0 ? m : 1)) : NULL;
-    char *call_block = cdf ? (char *)malloc(red.tl ? tl_block_bytes(red.tl) : cdf_block_bytes(red.cdf)) : NULL;
-    if (cdf && (!grp || !call_block)) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+    int32_t *grp = reduces ? (int32_t *)malloc(sizeof(int32_t) * (size_t)(m > 0 ? m : 1)) : NULL;
+    char *call_block = reduces ? (char *)malloc(red_block_bytes(red)) : NULL;
+    if (reduces && (!grp || !call_block)) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
     if (!glibc) {
         for (int a = 0; a < m; a += CH) {
             const int n = m - a < CH ? m - a : CH;
             for (int k = 0; k < n; k++) {
                 c[k] = cfgs[idx[a + k]];
-                if (cdf) grp[k] = idx[a + k] % npts;
+                if (reduces) grp[k] = idx[a + k] % npts;
                 if (want_logs) {
                     logs[k] = (prach_ue_log *)malloc(sizeof(prach_ue_log) * (size_t)c[k].nUE);
                     if (!logs[k]) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
                 }
             }
-            rc = run_call(eng, c, n, r, logs, red, grp, call_block, cdf_block);
+            rc = run_call(eng, c, n, r, logs, red, grp, call_block, worker_block);
             if (rc != PRACH_OK) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(rc)); return 2; }
             const double lat = now_s() - t0;
             for (int k = 0; k < n; k++) {
@@ -188,13 +200,13 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
             for (int s_ = 0; s_ < nseeds; s_++) {
                 c[s_] = cfgs[idx[s_ * npts + k]];
                 c[s_].stream_offset = offset[s_];
-                if (cdf) grp[s_] = k;
+                if (reduces) grp[s_] = k;
                 if (want_logs) {
                     logs[s_] = (prach_ue_log *)malloc(sizeof(prach_ue_log) * (size_t)c[s_].nUE);
                     if (!logs[s_]) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
                 }
             }
-            rc = run_call(eng, c, nseeds, r, logs, red, grp, call_block, cdf_block);
+            rc = run_call(eng, c, nseeds, r, logs, red, grp, call_block, worker_block);
             if (rc != PRACH_OK) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(rc)); return 2; }
             const double lat = now_s() - t0;
             for (int s_ = 0; s_ < nseeds; s_++) {
@@ -380,30 +392,26 @@ int main(int argc, char *argv[]) {
             }
     }
 
-    /* --cdf: one block of distributions per worker in a shared mapping, like the results; the parent merges them (integers: exact in any order) */
+    /* --cdf / --timeline: one block of groups per worker in a shared mapping, like the results; the parent merges them (integers: exact in any order).
+     * The timeline's bins cover the horizon (a completion is at most maxTime + 5) */
     const prach_dist_spec cdf_spec = {cdf_bins, cdf_bin_ms, npts, 0};
-    const prach_dist_spec *const cdf = cdf_path ? &cdf_spec : NULL;
-    char *cdf_blocks = NULL;
-    if (cdf) {
-        cdf_blocks = (char *)mmap(NULL, cdf_block_bytes(cdf) * (size_t)gpus, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0); /* (zero-filled: empty groups) */
-        if (cdf_blocks == MAP_FAILED) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
-    }
-    /* --timeline: the same, one block of timelines per worker; the bins cover the horizon (a completion is at most maxTime + 5) */
     const int tl_bins = (prach_max_time(&base) + 6 + tl_bin_ms - 1) / tl_bin_ms;
     const prach_timeline_spec tl_spec = {tl_bins, tl_bin_ms, npts, 0};
-    const prach_timeline_spec *const tls = tl_path ? &tl_spec : NULL;
-    if (tls && tl_bins > PRACH_TIMELINE_MAX_BINS) die("--timeline-bin MS: too many bins");
-    if (tls) {
-        cdf_blocks = (char *)mmap(NULL, tl_block_bytes(tls) * (size_t)gpus, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
-        if (cdf_blocks == MAP_FAILED) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
-        for (int w = 0; w < gpus; w++)
-            for (int k = 0; k < npts; k++) tl_t(cdf_blocks + tl_block_bytes(tls) * (size_t)w)[k].done_max = -1; /* (empty groups) */
+    if (tl_path && tl_bins > PRACH_TIMELINE_MAX_BINS) die("--timeline-bin MS: too many bins");
+    /* a line of --cdf: a label of at most 10 digits, three numbers, a share; of --timeline: the label, a series name, two numbers */
+    const reduction red_ = {cdf_path ? &cdf_spec : NULL, tl_path ? &tl_spec : NULL, tl_path ? tl_path : cdf_path,
+                            tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1};
+    const reduction *const red = &red_;
+    char *red_blocks = NULL;
+    if (red_on(red)) {
+        red_blocks = (char *)mmap(NULL, red_block_bytes(red) * (size_t)gpus, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0); /* (zero-filled) */
+        if (red_blocks == MAP_FAILED) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+        for (int w = 0; w < gpus; w++) red_init_block(red, red_blocks + red_block_bytes(red) * (size_t)w);
     }
-    const reduce_spec red = {cdf, tls};
-#define CDF_BLOCK(w) (tls ? cdf_blocks + tl_block_bytes(tls) * (size_t)(w) : cdf ? cdf_blocks + cdf_block_bytes(cdf) * (size_t)(w) : NULL)
+#define RED_BLOCK(w) (red_on(red) ? red_blocks + red_block_bytes(red) * (size_t)(w) : NULL)
 
     if (gpus == 1) {
-        int rcw = run_worker(devs[0], cfgs, widx[0], wn[0], res, lat, want_logs, outdir, glibc, npts, red, CDF_BLOCK(0));
+        int rcw = run_worker(devs[0], cfgs, widx[0], wn[0], res, lat, want_logs, outdir, glibc, npts, red, RED_BLOCK(0));
         if (rcw) return rcw;
     } else {
         /* one child per device, forked BEFORE this process touches HIP (a forked copy of an initialised runtime is not usable) */
@@ -412,7 +420,7 @@ int main(int argc, char *argv[]) {
         for (int w = 0; w < gpus; w++) {
             pid[w] = fork();
             if (pid[w] < 0) { perror("prach_sim: fork"); return 2; }
-            if (pid[w] == 0) _exit(run_worker(devs[w], cfgs, widx[w], wn[w], res, lat, want_logs, outdir, glibc, npts, red, CDF_BLOCK(w)));
+            if (pid[w] == 0) _exit(run_worker(devs[w], cfgs, widx[w], wn[w], res, lat, want_logs, outdir, glibc, npts, red, RED_BLOCK(w)));
         }
         int bad = 0;
         for (int w = 0; w < gpus; w++) {
@@ -426,39 +434,17 @@ int main(int argc, char *argv[]) {
         if (bad) return 2;
     }
 
-    if (cdf) { /* worker 0's block takes the others'; one group per sweep point, labelled nUE */
-        for (int w = 1; w < gpus; w++) cdf_merge_block(cdf, CDF_BLOCK(0), CDF_BLOCK(w));
-        FILE *fp = fopen(cdf_path, "wb");
+    if (red_on(red)) { /* worker 0's block takes the others'; one group per sweep point, labelled nUE */
+        for (int w = 1; w < gpus; w++) red_merge_block(red, RED_BLOCK(0), RED_BLOCK(w));
+        FILE *fp = fopen(red->path, "wb");
         if (!fp) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_IO)); return 2; }
-        const size_t cap = 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1; /* a line: a label of at most 10 digits, three numbers, a share */
-        char *out = (char *)malloc(cap);
+        char *out = (char *)malloc(red->text_cap);
         if (!out) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
         for (int k = 0; k < npts; k++) {
             char label[16];
             snprintf(label, sizeof label, "%d", sweep_lo + k * sweep_step);
-            const size_t n = prach_dist_format_csv(cdf, cdf_d(cdf, CDF_BLOCK(0)) + k, cdf_dh(cdf, CDF_BLOCK(0)) + (size_t)k * (size_t)cdf_bins,
-                                                   cdf_ph(cdf, CDF_BLOCK(0)) + (size_t)k * PRACH_DIST_PTC_BINS, label, out, cap);
-            if (n >= cap) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_INTERNAL)); return 2; }
-            fwrite(out, 1, n, fp);
-        }
-        free(out);
-        fclose(fp);
-    }
-
-    if (tls) { /* likewise: worker 0's block takes the others'; one group per sweep point, labelled nUE */
-        for (int w = 1; w < gpus; w++) tl_merge_block(tls, CDF_BLOCK(0), CDF_BLOCK(w));
-        FILE *fp = fopen(tl_path, "wb");
-        if (!fp) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_IO)); return 2; }
-        const size_t cap = 64 * (5 * (size_t)tl_bins + 2) + 1; /* a line: a label of at most 10 digits, a series name, two numbers */
-        char *out = (char *)malloc(cap);
-        if (!out) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
-        for (int k = 0; k < npts; k++) {
-            char label[16];
-            const uint64_t *ser[5];
-            for (int q = 0; q < 5; q++) ser[q] = tl_series(tls, CDF_BLOCK(0), q, k);
-            snprintf(label, sizeof label, "%d", sweep_lo + k * sweep_step);
-            const size_t n = prach_timeline_format_csv(tls, tl_t(CDF_BLOCK(0)) + k, ser, label, out, cap);
-            if (n >= cap) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_INTERNAL)); return 2; }
+            const size_t n = red_format_group(red, RED_BLOCK(0), k, label, out, red->text_cap);
+            if (n >= red->text_cap) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_INTERNAL)); return 2; }
             fwrite(out, 1, n, fp);
         }
         free(out);

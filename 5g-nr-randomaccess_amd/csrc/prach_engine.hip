@@ -31,7 +31,6 @@ struct prach_engine {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t ev2 = nullptr, ev3 = nullptr; // around the distribution kernel of a launch (prach_timing.dist_ms)
     char *arena = nullptr;
     size_t arena_cap = 0;
     // the arena as ONE reserved virtual range that physical memory is mapped into piece by piece (hipMemAddressReserve / hipMemCreate / hipMemMap): growing it
@@ -42,18 +41,15 @@ struct prach_engine {
     std::vector<std::pair<hipMemGenericAllocationHandle_t, size_t>> vmm_parts;
     char *pinned = nullptr; // host staging mirror of the head of the arena (parameter blocks, arrival tables, stream seeds, results)
     size_t pinned_cap = 0;
-    // prach_run_trials_dist: the call's histograms and scalars (zeroed once per call, copied out once at its end — not part of the arena, which is laid out
-    // again for every launch) and the job table of one launch, pinned and on the device; all grown at the start of a call, never per launch
-    char *dist_buf = nullptr;
-    size_t dist_cap = 0;
-    DistJob *dist_jobs_h = nullptr, *dist_jobs_d = nullptr;
-    int dist_jobs_cap = 0;
-    // prach_run_trials_timeline: the same three for the five series and the scalars of the call, with events of their own (prach_timing.timeline_ms)
-    hipEvent_t ev4 = nullptr, ev5 = nullptr;
-    char *tl_buf = nullptr;
-    size_t tl_cap = 0;
-    TimelineJob *tl_jobs_h = nullptr, *tl_jobs_d = nullptr;
-    int tl_jobs_cap = 0;
+    // The device reduction of a call (prach_run_trials_dist or prach_run_trials_timeline: a call runs at most one, so both kinds share these): the call's
+    // counters (zeroed once per call, copied out once at its end — not part of the arena, which is laid out again for every launch), the job table of one
+    // launch, pinned and on the device, in bytes (DistJob or TimelineJob elements), and the events around the reduction kernel of a launch
+    // (prach_timing.dist_ms / timeline_ms).  All created and grown at the start of a call, never per launch.
+    char *red_buf = nullptr;
+    size_t red_cap = 0;
+    char *red_jobs_h = nullptr, *red_jobs_d = nullptr;
+    size_t red_jobs_cap = 0;
+    hipEvent_t red_ev0 = nullptr, red_ev1 = nullptr;
     int64_t opt_timeline_scheme = 1; // timeline_kernel's binning (prach_timeline.hip): 0 global atomics only, 1 windows of bins privatised in LDS (measured faster: DESIGN.md 4)
     int64_t opt_dist_scheme = 1;   // dist_kernel's binning of the preamble counts (prach_dist.hip): 0 plain LDS adds, 1 per-wavefront copies (measured fastest), 2 match and aggregate
     prach_timing last{};
@@ -123,7 +119,7 @@ size_t mbox_bytes(const prach_cfg &c, int G, int &evw, int &mbstride) {
 }
 
 // stream_len[k]: glibc draw-stream window of trial k (0 in Philox mode); G: workgroups per trial (0 = trial_kernel)
-// all_logs: every trial gets a device log region (prach_run_trials_timeline reduces it there), not only the ones whose log the host asked for
+// all_logs: every trial gets a device log region (the call's reduction reads it there: prach_run_trials_timeline), not only the ones whose log the host asked for
 LaunchLayout layout_launch(const prach_cfg *cfgs, const int *idx, int m, prach_ue_log *const *ue_logs, bool all_logs, const std::vector<size_t> &stream_len, int G, bool batch, bool full_calendars, int64_t calendar_cap) {
     LaunchLayout L;
     L.t.resize(m);
@@ -416,6 +412,30 @@ static int noma_device_activation(prach_engine *e, const TrialDev *dparams, cons
     return PRACH_OK;
 }
 
+// What a call reduces on the device next to its results: the caller's spec, groups and outputs of prach_run_trials_dist or prach_run_trials_timeline.
+// The call's device buffer is a row of parts, [ngroups][words] 64-bit counters each: the arrays the caller gets as they are (dist: delay_hist, ptc_hist;
+// timeline: the five series arrivals, success, sojourn_sum, timer_sum, done), then the scalars the kernel keeps per group.
+enum class Red { dist, timeline };
+constexpr int RED_MAX_PARTS = 6;
+struct Reduction {
+    Red kind;
+    const int32_t *group; // nullable: trial k is group k
+    int ngroups;
+    const prach_dist_spec *dspec; // dist
+    prach_dist *dist;
+    const prach_timeline_spec *tspec; // timeline
+    prach_timeline *tl;
+    uint64_t *out[RED_MAX_PARTS - 1]; // the caller's arrays, one per part in front of the scalars
+};
+// words per group of every part; returns their number
+static int red_parts(const Reduction &r, size_t words[RED_MAX_PARTS]) {
+    if (r.kind == Red::dist) { words[0] = (size_t)r.dspec->delay_bins; words[1] = PRACH_DIST_PTC_BINS; words[2] = DIST_SCALARS; return 3; }
+    for (int q = 0; q < 5; q++) words[q] = (size_t)r.tspec->bins;
+    words[5] = TL_SCALARS;
+    return 6;
+}
+static size_t red_job_bytes(Red kind) { return kind == Red::dist ? sizeof(DistJob) : sizeof(TimelineJob); }
+
 // What one prach_run_trials call carries from launch to launch
 struct CallCtx {
     const prach_cfg *cfgs;
@@ -423,20 +443,19 @@ struct CallCtx {
     prach_ue_log *const *ue_logs;
     double kernel_ms = 0, upload_ms = 0;
     int noma_flagged = 0, noma_ambiguous = 0; // UEs recomputed on the host, trials rerun with the host-built table
-    // prach_run_trials_dist (spec == nullptr: plain prach_run_trials, nothing below is touched)
-    const prach_dist_spec *spec = nullptr;
-    const int32_t *group = nullptr; // nullable: trial k is group k
-    double dist_ms = 0;
-    unsigned long long *d_delay = nullptr, *d_ptc = nullptr, *d_scal = nullptr; // the call's device buffers: [ngroups][delay_bins], [ngroups][256], [ngroups][DIST_SCALARS]
+    // the call's reduction (red == nullptr: plain prach_run_trials, nothing below is touched)
+    const Reduction *red = nullptr;
+    double red_ms = 0;
+    unsigned long long *d_part[RED_MAX_PARTS] = {}; // the call's device buffer, part by part (red_parts)
     std::vector<uint64_t> trials, ues;        // per group, counted on the host as launches are accepted
-    std::vector<prach_dist> host_d;           // NOMA.c in the reference's stream finishes on the host: its groups' accumulators (sized on first use)
+    int group_of(int k) const { return red->group ? red->group[k] : k; }
+    bool reads_device_logs() const { return red && red->kind == Red::timeline; }
+    // dist only: NOMA.c in the reference's stream finishes on the host: its groups' accumulators (sized on first use)
+    const prach_dist_spec *dist_spec() const { return red && red->kind == Red::dist ? red->dspec : nullptr; }
+    std::vector<prach_dist> host_d;
     std::vector<uint64_t> host_dh, host_ph;
-    int group_of(int k) const { return group ? group[k] : k; }
-    // prach_run_trials_timeline (tspec == nullptr: any other call).  group, trials and ues above serve whichever of the two specs is set
-    const prach_timeline_spec *tspec = nullptr;
-    double timeline_ms = 0;
-    TimelineOut d_tl{};
     DistSink sink(int k) { // the host-side accumulators of trial k's group
+        const prach_dist_spec *const spec = red->dspec;
         if (host_d.empty()) {
             prach_dist z{};
             z.delay_max = -1;
@@ -565,7 +584,7 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
         if ((cfgs[idx[k]].flags & PRACH_FLAG_SECTOR_GRANTS) && G > 0 && !batch) return PRACH_ERR_INTERNAL;
     // NOMA.c's activeUE table: built by the device (noma_activation_kernel) unless the option or a rerun asks for the host's libm
     const bool host_act = noma && (e->opt_noma_host_activation || o.host_act);
-    const LaunchLayout LL = layout_launch(cfgs, idx, m, cx.ue_logs, cx.tspec != nullptr, slen, G, batch, o.full_calendars, e->opt_calendar_cap);
+    const LaunchLayout LL = layout_launch(cfgs, idx, m, cx.ue_logs, cx.reads_device_logs(), slen, G, batch, o.full_calendars, e->opt_calendar_cap);
     if (LL.end > e->mem_budget && m > 1) { // (e.g. the 10 000-trial grid with its calendars on ONE GPU: two or three launches instead of one)
         const int h = m / 2;
         int rc = run_group(e, cx, idx, h, attempt, G, o, cal_overflow);
@@ -730,10 +749,13 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
     if (kc.rec_mode >= 0) e->last.rec_mode = kc.rec_mode;
 
     const DevResult *const drs = reinterpret_cast<const DevResult *>(H);
-    // the distributions of the trials this launch finished (the ones the loop below accepts), behind the simulation kernel on the same stream; it runs
-    // while the host turns DevResult into prach_result
-    bool dist_launched = false;
-    if (cx.spec) {
+    // the call's reduction over the trials this launch finished — the ones the loop below accepts, so a trial that is rerun is counted once — behind the
+    // simulation kernel on the same stream; it runs while the host turns DevResult into prach_result.  dist reads the timers and preamble counts the
+    // simulation kernel left in the arena, timeline its log records and the launch's own copy of every arrival schedule
+    bool red_launched = false;
+    if (cx.red) {
+        const Reduction &R = *cx.red;
+        const bool tl = R.kind == Red::timeline;
         int njobs = 0, wgs = 0;
         for (int k = 0; k < m; k++) {
             const DevResult &dr = drs[k];
@@ -741,40 +763,24 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
             const prach_cfg &c = cfgs[idx[k]];
             const TrialLayout &L = LL.t[k];
             const int g = cx.group_of(idx[k]);
-            e->dist_jobs_h[njobs++] = DistJob{reinterpret_cast<const int *>(A + L.timers), reinterpret_cast<const int *>(A + (batch ? L.rec32 : L.ptc)), c.nUE, g, wgs, batch ? 1 : 0};
-            wgs += (c.nUE + DIST_TILE - 1) / DIST_TILE;
+            if (tl) {
+                const int nslots = (prach_max_time(&c) + c.accessTime - 1) / c.accessTime; // (what prach_arrival_schedule fills; the table has one entry more)
+                reinterpret_cast<TimelineJob *>(e->red_jobs_h)[njobs++] = TimelineJob{reinterpret_cast<const int4 *>(A + L.logs), reinterpret_cast<const int *>(A + L.sched), c.nUE, g, wgs, c.accessTime, nslots, 0};
+            } else
+                reinterpret_cast<DistJob *>(e->red_jobs_h)[njobs++] = DistJob{reinterpret_cast<const int *>(A + L.timers), reinterpret_cast<const int *>(A + (batch ? L.rec32 : L.ptc)), c.nUE, g, wgs, batch ? 1 : 0};
+            const int tile = tl ? TL_TILE : DIST_TILE;
+            wgs += (c.nUE + tile - 1) / tile;
             cx.trials[(size_t)g]++;
             cx.ues[(size_t)g] += (uint64_t)c.nUE;
         }
         if (njobs > 0) {
-            HIPCHK(hipMemcpyAsync(e->dist_jobs_d, e->dist_jobs_h, sizeof(DistJob) * (size_t)njobs, hipMemcpyHostToDevice, e->stream));
-            HIPCHK(hipEventRecord(e->ev2, e->stream));
-            HIPCHK(launch_dist_kernel(e->dist_jobs_d, njobs, wgs, cx.spec->delay_bins, cx.spec->delay_bin_ms, (int)e->opt_dist_scheme, cx.d_delay, cx.d_ptc, cx.d_scal, e->stream));
-            HIPCHK(hipEventRecord(e->ev3, e->stream));
-            dist_launched = true;
-        }
-    }
-    // the timelines likewise: from the log records the simulation kernel left on the device and the launch's own copy of every arrival schedule
-    bool tl_launched = false;
-    if (cx.tspec) {
-        int njobs = 0, wgs = 0;
-        for (int k = 0; k < m; k++) {
-            if (drs[k].status != PRACH_OK) continue;
-            const prach_cfg &c = cfgs[idx[k]];
-            const TrialLayout &L = LL.t[k];
-            const int g = cx.group_of(idx[k]);
-            const int nslots = (prach_max_time(&c) + c.accessTime - 1) / c.accessTime; // (what prach_arrival_schedule fills; the table has one entry more)
-            e->tl_jobs_h[njobs++] = TimelineJob{reinterpret_cast<const int4 *>(A + L.logs), reinterpret_cast<const int *>(A + L.sched), c.nUE, g, wgs, c.accessTime, nslots, 0};
-            wgs += (c.nUE + TL_TILE - 1) / TL_TILE;
-            cx.trials[(size_t)g]++;
-            cx.ues[(size_t)g] += (uint64_t)c.nUE;
-        }
-        if (njobs > 0) {
-            HIPCHK(hipMemcpyAsync(e->tl_jobs_d, e->tl_jobs_h, sizeof(TimelineJob) * (size_t)njobs, hipMemcpyHostToDevice, e->stream));
-            HIPCHK(hipEventRecord(e->ev4, e->stream));
-            HIPCHK(launch_timeline_kernel(e->tl_jobs_d, njobs, wgs, cx.tspec->bins, cx.tspec->bin_ms, (int)e->opt_timeline_scheme, cx.d_tl, e->stream));
-            HIPCHK(hipEventRecord(e->ev5, e->stream));
-            tl_launched = true;
+            unsigned long long *const *const d = cx.d_part;
+            HIPCHK(hipMemcpyAsync(e->red_jobs_d, e->red_jobs_h, red_job_bytes(R.kind) * (size_t)njobs, hipMemcpyHostToDevice, e->stream));
+            HIPCHK(hipEventRecord(e->red_ev0, e->stream));
+            if (tl) HIPCHK(launch_timeline_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, wgs, R.tspec->bins, R.tspec->bin_ms, (int)e->opt_timeline_scheme, TimelineOut{d[0], d[1], d[2], d[3], d[4], d[5]}, e->stream));
+            else HIPCHK(launch_dist_kernel(reinterpret_cast<const DistJob *>(e->red_jobs_d), njobs, wgs, R.dspec->delay_bins, R.dspec->delay_bin_ms, (int)e->opt_dist_scheme, d[0], d[1], d[2], e->stream));
+            HIPCHK(hipEventRecord(e->red_ev1, e->stream));
+            red_launched = true;
         }
     }
     std::vector<int32_t> timers;
@@ -825,17 +831,11 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
         if (L.logs && cx.ue_logs && cx.ue_logs[idx[k]]) // (a timeline call lays out every trial's log; only the ones asked for cross the bus)
             HIPCHK(hipMemcpy(cx.ue_logs[idx[k]], A + L.logs, sizeof(prach_ue_log) * (size_t)c.nUE, hipMemcpyDeviceToHost));
     }
-    if (dist_launched) { // (the next launch lays the arena out again and reuses the pinned job table)
+    if (red_launched) { // (the next launch lays the arena out again and reuses the pinned job table)
         HIPCHK(hipStreamSynchronize(e->stream));
-        float dms = 0;
-        HIPCHK(hipEventElapsedTime(&dms, e->ev2, e->ev3));
-        cx.dist_ms += dms;
-    }
-    if (tl_launched) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        float tms = 0;
-        HIPCHK(hipEventElapsedTime(&tms, e->ev4, e->ev5));
-        cx.timeline_ms += tms;
+        float rms = 0;
+        HIPCHK(hipEventElapsedTime(&rms, e->red_ev0, e->red_ev1));
+        cx.red_ms += rms;
     }
     return PRACH_OK;
 }
@@ -954,125 +954,83 @@ static int cluster_size(const prach_engine *e, const prach_cfg *cfgs, const std:
     return G;
 }
 
-// the caller's outputs of prach_run_trials_dist (spec == nullptr: prach_run_trials)
-struct DistOut { const prach_dist_spec *spec; const int32_t *group; prach_dist *dist; uint64_t *delay_hist, *ptc_hist; };
-
-// grows the call's device buffers and the job table of a launch (n: the most trials one launch can hold), zeroes the buffers on the engine's stream
-static int dist_begin(prach_engine *e, CallCtx &cx, int n) {
-    const prach_dist_spec &s = *cx.spec;
-    const size_t ng = (size_t)s.ngroups;
-    const size_t o_ptc = align_up(8 * ng * (size_t)s.delay_bins, 256), o_scal = align_up(o_ptc + 8 * ng * PRACH_DIST_PTC_BINS, 256), need = o_scal + 8 * ng * DIST_SCALARS;
-    if (need > e->dist_cap) {
-        if (e->dist_buf) HIPCHK(hipFree(e->dist_buf));
-        e->dist_buf = nullptr; e->dist_cap = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->dist_buf), need));
-        e->dist_cap = need;
+// grows the call's device buffer and the job table of a launch (n: the most trials one launch can hold), carves the buffer into its parts and zeroes it on
+// the engine's stream
+static int reduction_begin(prach_engine *e, CallCtx &cx, int n) {
+    const Reduction &R = *cx.red;
+    const size_t ng = (size_t)R.ngroups;
+    size_t words[RED_MAX_PARTS], at[RED_MAX_PARTS], need = 0;
+    const int np = red_parts(R, words);
+    for (int q = 0; q < np; q++) { at[q] = align_up(need, 256); need = at[q] + 8 * ng * words[q]; }
+    if (need > e->red_cap) {
+        if (e->red_buf) HIPCHK(hipFree(e->red_buf));
+        e->red_buf = nullptr; e->red_cap = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->red_buf), need));
+        e->red_cap = need;
     }
-    if (n > e->dist_jobs_cap) {
-        if (e->dist_jobs_h) HIPCHK(hipHostFree(e->dist_jobs_h));
-        if (e->dist_jobs_d) HIPCHK(hipFree(e->dist_jobs_d));
-        e->dist_jobs_h = e->dist_jobs_d = nullptr; e->dist_jobs_cap = 0;
-        const int want = n + (n >> 2) + 64;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&e->dist_jobs_h), sizeof(DistJob) * (size_t)want, hipHostMallocDefault));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->dist_jobs_d), sizeof(DistJob) * (size_t)want));
-        e->dist_jobs_cap = want;
+    if (red_job_bytes(R.kind) * (size_t)n > e->red_jobs_cap) {
+        if (e->red_jobs_h) HIPCHK(hipHostFree(e->red_jobs_h));
+        if (e->red_jobs_d) HIPCHK(hipFree(e->red_jobs_d));
+        e->red_jobs_h = e->red_jobs_d = nullptr; e->red_jobs_cap = 0;
+        const size_t want = red_job_bytes(R.kind) * (size_t)(n + (n >> 2) + 64);
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&e->red_jobs_h), want, hipHostMallocDefault));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->red_jobs_d), want));
+        e->red_jobs_cap = want;
     }
-    if (!e->ev2) HIPCHK(hipEventCreate(&e->ev2));
-    if (!e->ev3) HIPCHK(hipEventCreate(&e->ev3));
-    cx.d_delay = reinterpret_cast<unsigned long long *>(e->dist_buf);
-    cx.d_ptc = reinterpret_cast<unsigned long long *>(e->dist_buf + o_ptc);
-    cx.d_scal = reinterpret_cast<unsigned long long *>(e->dist_buf + o_scal);
+    if (!e->red_ev0) HIPCHK(hipEventCreate(&e->red_ev0));
+    if (!e->red_ev1) HIPCHK(hipEventCreate(&e->red_ev1));
+    for (int q = 0; q < np; q++) cx.d_part[q] = reinterpret_cast<unsigned long long *>(e->red_buf + at[q]);
     cx.trials.assign(ng, 0);
     cx.ues.assign(ng, 0);
-    HIPCHK(hipMemsetAsync(e->dist_buf, 0, need, e->stream));
+    HIPCHK(hipMemsetAsync(e->red_buf, 0, need, e->stream));
     return PRACH_OK;
 }
-// ONE copy-out at the end of the call (every distribution kernel has completed: run_group waits for its own), plus what finished on the host
-static int dist_end(prach_engine *e, CallCtx &cx, const DistOut &out) {
-    const prach_dist_spec &s = *cx.spec;
-    const size_t ng = (size_t)s.ngroups;
-    std::vector<unsigned long long> sc(ng * DIST_SCALARS);
+// ONE copy-out per part at the end of the call (every reduction kernel has completed: run_group waits for its own); the scalars are unpacked group by
+// group, and dist adds what finished on the host
+static int reduction_end(prach_engine *e, CallCtx &cx) {
+    const Reduction &R = *cx.red;
+    const size_t ng = (size_t)R.ngroups;
+    size_t words[RED_MAX_PARTS];
+    const int np = red_parts(R, words);
+    const size_t nsc = words[np - 1];
+    std::vector<unsigned long long> sc(ng * nsc);
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(out.delay_hist, cx.d_delay, 8 * ng * (size_t)s.delay_bins, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out.ptc_hist, cx.d_ptc, 8 * ng * PRACH_DIST_PTC_BINS, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(sc.data(), cx.d_scal, 8 * sc.size(), hipMemcpyDeviceToHost));
+    for (int q = 0; q + 1 < np; q++) HIPCHK(hipMemcpy(R.out[q], cx.d_part[q], 8 * ng * words[q], hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sc.data(), cx.d_part[np - 1], 8 * sc.size(), hipMemcpyDeviceToHost));
     for (size_t g = 0; g < ng; g++) {
-        const unsigned long long *const q = &sc[g * DIST_SCALARS];
-        prach_dist &d = out.dist[g];
-        d.trials = cx.trials[g]; d.ues = cx.ues[g]; d.success = q[0]; d.delay_overflow = q[1]; d.delay_sum = q[2]; d.ptc_sum = q[3];
-        d.delay_max = (int64_t)q[4] - 1;
-        if (!cx.host_d.empty())
-            prach_dist_merge(&s, &d, out.delay_hist + g * (size_t)s.delay_bins, out.ptc_hist + g * PRACH_DIST_PTC_BINS, &cx.host_d[g],
-                             cx.host_dh.data() + g * (size_t)s.delay_bins, cx.host_ph.data() + g * PRACH_DIST_PTC_BINS);
+        const unsigned long long *const q = &sc[g * nsc];
+        if (R.kind == Red::dist) {
+            const prach_dist_spec &s = *R.dspec;
+            prach_dist &d = R.dist[g];
+            d.trials = cx.trials[g]; d.ues = cx.ues[g]; d.success = q[0]; d.delay_overflow = q[1]; d.delay_sum = q[2]; d.ptc_sum = q[3];
+            d.delay_max = (int64_t)q[4] - 1;
+            if (!cx.host_d.empty())
+                prach_dist_merge(&s, &d, R.out[0] + g * (size_t)s.delay_bins, R.out[1] + g * PRACH_DIST_PTC_BINS, &cx.host_d[g],
+                                 cx.host_dh.data() + g * (size_t)s.delay_bins, cx.host_ph.data() + g * PRACH_DIST_PTC_BINS);
+        } else {
+            prach_timeline &t = R.tl[g];
+            t.trials = cx.trials[g]; t.ues = cx.ues[g]; t.arrived = q[0]; t.success = q[1]; t.restarted = q[2]; t.arrival_overflow = q[3]; t.done_overflow = q[4];
+            t.sojourn_sum = q[5]; t.timer_sum = q[6];
+            t.done_max = (int64_t)q[7] - 1;
+        }
     }
     return PRACH_OK;
 }
 
-// the caller's outputs of prach_run_trials_timeline; series: arrivals, success, sojourn_sum, timer_sum, done
-struct TimelineCallOut { const prach_timeline_spec *spec; const int32_t *group; prach_timeline *tl; uint64_t *series[5]; };
-
-static int timeline_begin(prach_engine *e, CallCtx &cx, int n) {
-    const prach_timeline_spec &s = *cx.tspec;
-    const size_t ng = (size_t)s.ngroups, one = align_up(8 * ng * (size_t)s.bins, 256), need = 5 * one + 8 * ng * TL_SCALARS;
-    if (need > e->tl_cap) {
-        if (e->tl_buf) HIPCHK(hipFree(e->tl_buf));
-        e->tl_buf = nullptr; e->tl_cap = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->tl_buf), need));
-        e->tl_cap = need;
-    }
-    if (n > e->tl_jobs_cap) {
-        if (e->tl_jobs_h) HIPCHK(hipHostFree(e->tl_jobs_h));
-        if (e->tl_jobs_d) HIPCHK(hipFree(e->tl_jobs_d));
-        e->tl_jobs_h = e->tl_jobs_d = nullptr; e->tl_jobs_cap = 0;
-        const int want = n + (n >> 2) + 64;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&e->tl_jobs_h), sizeof(TimelineJob) * (size_t)want, hipHostMallocDefault));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->tl_jobs_d), sizeof(TimelineJob) * (size_t)want));
-        e->tl_jobs_cap = want;
-    }
-    if (!e->ev4) HIPCHK(hipEventCreate(&e->ev4));
-    if (!e->ev5) HIPCHK(hipEventCreate(&e->ev5));
-    auto at = [&](size_t q) { return reinterpret_cast<unsigned long long *>(e->tl_buf + q * one); };
-    cx.d_tl = TimelineOut{at(0), at(1), at(2), at(3), at(4), at(5)};
-    cx.trials.assign(ng, 0);
-    cx.ues.assign(ng, 0);
-    HIPCHK(hipMemsetAsync(e->tl_buf, 0, need, e->stream));
-    return PRACH_OK;
-}
-// ONE copy-out per series at the end of the call (every timeline kernel has completed: run_group waits for its own)
-static int timeline_end(prach_engine *e, CallCtx &cx, const TimelineCallOut &out) {
-    const prach_timeline_spec &s = *cx.tspec;
-    const size_t ng = (size_t)s.ngroups;
-    std::vector<unsigned long long> sc(ng * TL_SCALARS);
-    HIPCHK(hipStreamSynchronize(e->stream));
-    unsigned long long *const dev[5] = {cx.d_tl.arrivals, cx.d_tl.success, cx.d_tl.sojourn, cx.d_tl.timer, cx.d_tl.done};
-    for (int q = 0; q < 5; q++) HIPCHK(hipMemcpy(out.series[q], dev[q], 8 * ng * (size_t)s.bins, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(sc.data(), cx.d_tl.scalars, 8 * sc.size(), hipMemcpyDeviceToHost));
-    for (size_t g = 0; g < ng; g++) {
-        const unsigned long long *const q = &sc[g * TL_SCALARS];
-        prach_timeline &t = out.tl[g];
-        t.trials = cx.trials[g]; t.ues = cx.ues[g]; t.arrived = q[0]; t.success = q[1]; t.restarted = q[2]; t.arrival_overflow = q[3]; t.done_overflow = q[4];
-        t.sojourn_sum = q[5]; t.timer_sum = q[6];
-        t.done_max = (int64_t)q[7] - 1;
-    }
-    return PRACH_OK;
-}
-
-static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const DistOut *dout = nullptr,
-                           const TimelineCallOut *tout = nullptr) {
+static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const Reduction *red = nullptr) {
     for (int k = 0; k < n; k++) { // nothing is left uninitialised on an early error return
         std::memset(&results[k], 0, sizeof(results[k]));
         results[k].status = PRACH_ERR_INTERNAL;
     }
-    if (dout) { // (the same for the distributions: empty groups)
-        const size_t ng = (size_t)dout->spec->ngroups;
-        std::memset(dout->delay_hist, 0, 8 * ng * (size_t)dout->spec->delay_bins);
-        std::memset(dout->ptc_hist, 0, 8 * ng * PRACH_DIST_PTC_BINS);
-        for (size_t g = 0; g < ng; g++) { dout->dist[g] = prach_dist{}; dout->dist[g].delay_max = -1; }
-    }
-    if (tout) { // (and for the timelines)
-        const size_t ng = (size_t)tout->spec->ngroups;
-        for (int q = 0; q < 5; q++) std::memset(tout->series[q], 0, 8 * ng * (size_t)tout->spec->bins);
-        for (size_t g = 0; g < ng; g++) { tout->tl[g] = prach_timeline{}; tout->tl[g].done_max = -1; }
+    if (red) { // (the same for the reduction's outputs: empty groups)
+        const size_t ng = (size_t)red->ngroups;
+        size_t words[RED_MAX_PARTS];
+        const int np = red_parts(*red, words);
+        for (int q = 0; q + 1 < np; q++) std::memset(red->out[q], 0, 8 * ng * words[q]);
+        for (size_t g = 0; g < ng; g++) {
+            if (red->kind == Red::dist) { red->dist[g] = prach_dist{}; red->dist[g].delay_max = -1; }
+            else { red->tl[g] = prach_timeline{}; red->tl[g].done_max = -1; }
+        }
     }
     for (int k = 0; k < n; k++) {
         int v = prach_cfg_validate(&cfgs[k]);
@@ -1083,16 +1041,9 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
     auto t0 = std::chrono::steady_clock::now();
     e->last = prach_timing{};
     CallCtx cx{cfgs, results, ue_logs};
-    if (dout) {
-        cx.spec = dout->spec;
-        cx.group = dout->group;
-        int rc = dist_begin(e, cx, n);
-        if (rc != PRACH_OK) return rc;
-    }
-    if (tout) {
-        cx.tspec = tout->spec;
-        cx.group = tout->group;
-        int rc = timeline_begin(e, cx, n);
+    if (red) {
+        cx.red = red;
+        int rc = reduction_begin(e, cx, n);
         if (rc != PRACH_OK) return rc;
     }
     // NOMA.c in the reference's OWN rand() stream: activeUE's rejection loops make every stream position data dependent and its libm
@@ -1112,8 +1063,8 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
                 std::vector<int32_t> hs((size_t)len);
                 prach_glibc_stream((uint32_t)cfgs[k].seed, cfgs[k].stream_offset, len, hs.data());
                 DistSink sk{};
-                if (cx.spec) sk = cx.sink(k);
-                rc = run_noma_glibc_trial(e->stream, cfgs[k], hs.data(), len, &results[k], ue_logs ? ue_logs[k] : nullptr, &cx.kernel_ms, cx.spec ? &sk : nullptr);
+                if (cx.dist_spec()) sk = cx.sink(k);
+                rc = run_noma_glibc_trial(e->stream, cfgs[k], hs.data(), len, &results[k], ue_logs ? ue_logs[k] : nullptr, &cx.kernel_ms, cx.dist_spec() ? &sk : nullptr);
                 e->last.launches++;
             }
             return rc;
@@ -1133,11 +1084,11 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
             std::vector<prach_ue_log *> pl(m);
             std::vector<int> rcs(m, PRACH_ERR_INTERNAL);
             std::vector<DistSink> sinks;
-            if (cx.spec) for (int j = 0; j < m; j++) sinks.push_back(cx.sink(todo[j]));
+            if (cx.dist_spec()) for (int j = 0; j < m; j++) sinks.push_back(cx.sink(todo[j]));
             for (int j = 0; j < m; j++) { pc[j] = &cfgs[todo[j]]; lens[j] = window(todo[j], attempt); pr[j] = &results[todo[j]]; pl[j] = ue_logs ? ue_logs[todo[j]] : nullptr; }
             if (e->opt_noma_ambiguity_test) std::fill(rcs.begin(), rcs.end(), NOMA_GLIBC_AMBIGUOUS_RC); // (test hook: as if the kernel had found a value inside the band)
             else {
-                int rc = run_noma_glibc_batch(e->stream, pc.data(), m, lens.data(), pr.data(), pl.data(), &cx.kernel_ms, rcs.data(), cx.spec ? sinks.data() : nullptr);
+                int rc = run_noma_glibc_batch(e->stream, pc.data(), m, lens.data(), pr.data(), pl.data(), &cx.kernel_ms, rcs.data(), cx.dist_spec() ? sinks.data() : nullptr);
                 e->last.launches++;
                 if (rc != PRACH_OK) return rc;
             }
@@ -1241,18 +1192,20 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
     e->last.noma_host_ues = cx.noma_flagged;
     e->last.upload_ms = cx.upload_ms;
     e->last.updates = upd;
-    if (dout) {
-        int rc = dist_end(e, cx, *dout);
+    if (red) {
+        int rc = reduction_end(e, cx);
         if (rc != PRACH_OK) return rc;
-        e->last.dist_ms = cx.dist_ms;
-    }
-    if (tout) {
-        int rc = timeline_end(e, cx, *tout);
-        if (rc != PRACH_OK) return rc;
-        e->last.timeline_ms = cx.timeline_ms;
+        (red->kind == Red::dist ? e->last.dist_ms : e->last.timeline_ms) = cx.red_ms;
     }
     e->last.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return worst;
+}
+
+// the groups of a reduction call: without a table trial k is group k, so there are n of them; with one, every entry names a group
+static bool groups_ok(const int32_t *group, int ngroups, int n) {
+    if (!group) return ngroups == n;
+    for (int k = 0; k < n; k++) if (group[k] < 0 || group[k] >= ngroups) return false;
+    return true;
 }
 
 // C++ exceptions (std::bad_alloc from the staging vectors) never cross the C boundary
@@ -1277,16 +1230,11 @@ void prach_engine_destroy(prach_engine *e) {
     if (e->pinned) (void)hipHostFree(e->pinned);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
-    if (e->ev2) (void)hipEventDestroy(e->ev2);
-    if (e->ev3) (void)hipEventDestroy(e->ev3);
-    if (e->ev4) (void)hipEventDestroy(e->ev4);
-    if (e->ev5) (void)hipEventDestroy(e->ev5);
-    if (e->tl_buf) (void)hipFree(e->tl_buf);
-    if (e->tl_jobs_d) (void)hipFree(e->tl_jobs_d);
-    if (e->tl_jobs_h) (void)hipHostFree(e->tl_jobs_h);
-    if (e->dist_buf) (void)hipFree(e->dist_buf);
-    if (e->dist_jobs_d) (void)hipFree(e->dist_jobs_d);
-    if (e->dist_jobs_h) (void)hipHostFree(e->dist_jobs_h);
+    if (e->red_ev0) (void)hipEventDestroy(e->red_ev0);
+    if (e->red_ev1) (void)hipEventDestroy(e->red_ev1);
+    if (e->red_buf) (void)hipFree(e->red_buf);
+    if (e->red_jobs_d) (void)hipFree(e->red_jobs_d);
+    if (e->red_jobs_h) (void)hipHostFree(e->red_jobs_h);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -1394,12 +1342,11 @@ int prach_run_trials_dist(prach_engine *e, const prach_cfg *cfgs, int n, prach_r
     // (the spec is judged first: what it asks for does not depend on a device)
     if (!cfgs || !results || n <= 0 || !spec || !dist || !delay_hist || !ptc_hist) return PRACH_ERR_ARG;
     if (spec->delay_bins < 1 || spec->delay_bins > PRACH_DIST_MAX_DELAY_BINS || spec->delay_bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
-    if (!group && spec->ngroups != n) return PRACH_ERR_ARG;
-    if (group) for (int k = 0; k < n; k++) if (group[k] < 0 || group[k] >= spec->ngroups) return PRACH_ERR_ARG;
+    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
     if ((uint64_t)spec->ngroups * (uint64_t)(spec->delay_bins + PRACH_DIST_PTC_BINS) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
-    const DistOut out{spec, group, dist, delay_hist, ptc_hist};
-    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &out);)
+    const Reduction red{Red::dist, group, spec->ngroups, spec, dist, nullptr, nullptr, {delay_hist, ptc_hist}};
+    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
 int prach_dist_tile_ues(void) { return DIST_TILE; }
@@ -1409,13 +1356,12 @@ int prach_run_trials_timeline(prach_engine *e, const prach_cfg *cfgs, int n, pra
     // (spec, groups and variants are judged first: what they ask for does not depend on a device)
     if (!cfgs || !results || n <= 0 || !spec || !tl || !arrivals || !success || !sojourn_sum || !timer_sum || !done) return PRACH_ERR_ARG;
     if (spec->bins < 1 || spec->bins > PRACH_TIMELINE_MAX_BINS || spec->bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
-    if (!group && spec->ngroups != n) return PRACH_ERR_ARG;
-    if (group) for (int k = 0; k < n; k++) if (group[k] < 0 || group[k] >= spec->ngroups) return PRACH_ERR_ARG;
+    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
     for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
     if (5 * (uint64_t)spec->ngroups * (uint64_t)spec->bins > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
-    const TimelineCallOut out{spec, group, tl, {arrivals, success, sojourn_sum, timer_sum, done}};
-    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, nullptr, &out);)
+    const Reduction red{Red::timeline, group, spec->ngroups, nullptr, nullptr, spec, tl, {arrivals, success, sojourn_sum, timer_sum, done}};
+    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
 int prach_timeline_tile_ues(void) { return TL_TILE; }

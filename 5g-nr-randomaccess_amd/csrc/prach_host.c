@@ -12,6 +12,7 @@
 #include <errno.h>
 #include <math.h>
 #include <pthread.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -565,6 +566,26 @@ size_t prach_results_csv_row(const double acc[6], int nseeds, char *buf, size_t 
     return (size_t)n;
 }
 
+/* ---- the CSV text of a reduction: one line at a time into buf[cap]; the size is counted also where nothing (more) fits ---- */
+
+__attribute__((format(printf, 4, 5))) static int csv_emit(char *buf, size_t cap, size_t *off, const char *fmt, ...) {
+    char line[512];
+    va_list ap;
+    va_start(ap, fmt);
+    const int n = vsnprintf(line, sizeof line, fmt, ap);
+    va_end(ap);
+    if (n < 0 || (size_t)n >= sizeof line) return 0;
+    if (buf && *off + (size_t)n < cap) memcpy(buf + *off, line, (size_t)n);
+    *off += (size_t)n;
+    return 1;
+}
+#define CSV_EMIT(...) do { if (!csv_emit(buf, cap, &off, __VA_ARGS__)) return 0; } while (0)
+static size_t csv_end(char *buf, size_t cap, size_t off) {
+    if (buf && off < cap) buf[off] = 0;
+    else if (buf && cap) buf[0] = 0; /* (did not fit: nothing partial is left behind as a string) */
+    return off;
+}
+
 /* ---- distributions of the successful UEs (prach_run_trials_dist) -------------------------------- */
 
 static int dist_spec_ok(const prach_dist_spec *s) {
@@ -623,32 +644,21 @@ size_t prach_dist_format_csv(const prach_dist_spec *s, const prach_dist *d, cons
                              size_t cap) {
     if (!dist_spec_ok(s) || !d || !delay_hist || !ptc_hist || !label) return 0;
     size_t off = 0;
-    char line[512];
     const double tot = d->success ? (double)d->success : 1.0;
     uint64_t cum = 0;
-#define DIST_EMIT(...)                                                          \
-    do {                                                                        \
-        const int n_ = snprintf(line, sizeof line, __VA_ARGS__);                \
-        if (n_ < 0 || (size_t)n_ >= sizeof line) return 0;                      \
-        if (buf && off + (size_t)n_ < cap) memcpy(buf + off, line, (size_t)n_); \
-        off += (size_t)n_;                                                      \
-    } while (0)
     for (int b = 0; b < s->delay_bins; b++) {
         if (!delay_hist[b]) continue;
         cum += delay_hist[b];
-        DIST_EMIT("%.200s,delay,%lld,%llu,%.6f\n", label, (long long)b * s->delay_bin_ms, (unsigned long long)delay_hist[b], (double)cum / tot);
+        CSV_EMIT("%.200s,delay,%lld,%llu,%.6f\n", label, (long long)b * s->delay_bin_ms, (unsigned long long)delay_hist[b], (double)cum / tot);
     }
-    if (d->delay_overflow) DIST_EMIT("%.200s,delay,overflow,%llu,1.000000\n", label, (unsigned long long)d->delay_overflow);
+    if (d->delay_overflow) CSV_EMIT("%.200s,delay,overflow,%llu,1.000000\n", label, (unsigned long long)d->delay_overflow);
     cum = 0;
     for (int k = 0; k < PRACH_DIST_PTC_BINS; k++) {
         if (!ptc_hist[k]) continue;
         cum += ptc_hist[k];
-        DIST_EMIT("%.200s,ptx,%d,%llu,%.6f\n", label, k, (unsigned long long)ptc_hist[k], (double)cum / tot);
+        CSV_EMIT("%.200s,ptx,%d,%llu,%.6f\n", label, k, (unsigned long long)ptc_hist[k], (double)cum / tot);
     }
-#undef DIST_EMIT
-    if (buf && off < cap) buf[off] = 0;
-    else if (buf && cap) buf[0] = 0; /* (did not fit: nothing partial is left behind as a string) */
-    return off;
+    return csv_end(buf, cap, off);
 }
 
 /* ---- timelines per trial group (prach_run_trials_timeline) -------------------------------------- */
@@ -720,22 +730,11 @@ size_t prach_timeline_format_csv(const prach_timeline_spec *s, const prach_timel
     if (!timeline_spec_ok(s) || !t || !series || !label) return 0;
     for (int q = 0; q < 5; q++) if (!series[q]) return 0;
     size_t off = 0;
-    char line[512];
-#define TL_EMIT(...)                                                            \
-    do {                                                                        \
-        const int n_ = snprintf(line, sizeof line, __VA_ARGS__);                \
-        if (n_ < 0 || (size_t)n_ >= sizeof line) return 0;                      \
-        if (buf && off + (size_t)n_ < cap) memcpy(buf + off, line, (size_t)n_); \
-        off += (size_t)n_;                                                      \
-    } while (0)
     for (int q = 0; q < 5; q++) {
         for (int b = 0; b < s->bins; b++)
-            if (series[q][b]) TL_EMIT("%.200s,%s,%lld,%llu\n", label, names[q], (long long)b * s->bin_ms, (unsigned long long)series[q][b]);
-        if (q == 0 && t->arrival_overflow) TL_EMIT("%.200s,arrivals,overflow,%llu\n", label, (unsigned long long)t->arrival_overflow);
-        if (q == 4 && t->done_overflow) TL_EMIT("%.200s,done,overflow,%llu\n", label, (unsigned long long)t->done_overflow);
+            if (series[q][b]) CSV_EMIT("%.200s,%s,%lld,%llu\n", label, names[q], (long long)b * s->bin_ms, (unsigned long long)series[q][b]);
+        if (q == 0 && t->arrival_overflow) CSV_EMIT("%.200s,arrivals,overflow,%llu\n", label, (unsigned long long)t->arrival_overflow);
+        if (q == 4 && t->done_overflow) CSV_EMIT("%.200s,done,overflow,%llu\n", label, (unsigned long long)t->done_overflow);
     }
-#undef TL_EMIT
-    if (buf && off < cap) buf[off] = 0;
-    else if (buf && cap) buf[0] = 0; /* (did not fit: nothing partial is left behind as a string) */
-    return off;
+    return csv_end(buf, cap, off);
 }

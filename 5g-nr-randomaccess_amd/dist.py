@@ -74,53 +74,39 @@ def allreduce_aggregates(agg: np.ndarray, device=None):
     return t.cpu().numpy()
 
 
-def allreduce_dist(d, device=None):
-    """Merges the distributions (a `Dist` of the package: same groups, bins and width on every rank) across ranks, in place: ONE int64 sum all-reduce of the
-    concatenated block — both histograms and the summed scalars — and delay_max by a max all-reduce of ngroups values.  Integers: exact in any order."""
+def _allreduce_sums_and_max(sum_arrays, max_array, device):
+    """In place across ranks: ONE int64 sum all-reduce of the concatenated sum_arrays (any integer dtype and shape) and ONE int64 max all-reduce of
+    max_array.  Integers: exact in any order.  Nothing to do, and no collective, without an initialised group of more than one rank."""
     import torch
     import torch.distributed as dist
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-        return d
-    from . import DIST_FIELDS
-    sums = [f for f in DIST_FIELDS if f != "delay_max"]
-    block = np.concatenate([d.delay_hist.astype(np.int64).ravel(), d.ptc_hist.astype(np.int64).ravel()] + [getattr(d, f).astype(np.int64) for f in sums])
-    t, mx = torch.from_numpy(block), torch.from_numpy(d.delay_max.astype(np.int64))
+        return
+    t = torch.from_numpy(np.concatenate([a.astype(np.int64).ravel() for a in sum_arrays]))
+    mx = torch.from_numpy(max_array.astype(np.int64))
     if device is not None:
         t, mx = t.to(device), mx.to(device)
     dist.all_reduce(t, op=dist.ReduceOp.SUM)
     dist.all_reduce(mx, op=dist.ReduceOp.MAX)
-    block = t.cpu().numpy()
-    nd, npc, g = d.delay_hist.size, d.ptc_hist.size, d.ngroups
-    d.delay_hist[...] = block[:nd].reshape(d.delay_hist.shape).astype(np.uint64)
-    d.ptc_hist[...] = block[nd:nd + npc].reshape(d.ptc_hist.shape).astype(np.uint64)
-    for k, f in enumerate(sums):
-        getattr(d, f)[:] = block[nd + npc + k * g:nd + npc + (k + 1) * g]
-    d.delay_max[:] = mx.cpu().numpy()
+    block, at = t.cpu().numpy(), 0
+    for a in sum_arrays:
+        a[...] = block[at:at + a.size].reshape(a.shape).astype(a.dtype)
+        at += a.size
+    max_array[...] = mx.cpu().numpy()
+
+
+def allreduce_dist(d, device=None):
+    """Merges the distributions (a `Dist` of the package: same groups, bins and width on every rank) across ranks, in place: ONE int64 sum all-reduce of the
+    concatenated block — both histograms and the summed scalars — and delay_max by a max all-reduce of ngroups values."""
+    from . import DIST_FIELDS
+    _allreduce_sums_and_max([d.delay_hist, d.ptc_hist] + [getattr(d, f) for f in DIST_FIELDS if f != "delay_max"], d.delay_max, device)
     return d
 
 
 def allreduce_timeline(tl, device=None):
     """Merges the timelines (a `Timeline` of the package: same groups, bins and width on every rank) across ranks, in place: ONE int64 sum all-reduce of the
-    concatenated block — the five series and the summed scalars — and done_max by a max all-reduce of ngroups values.  Integers: exact in any order."""
-    import torch
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-        return tl
+    concatenated block — the five series and the summed scalars — and done_max by a max all-reduce of ngroups values."""
     from . import TIMELINE_FIELDS, TIMELINE_SERIES
-    sums = [f for f in TIMELINE_FIELDS if f != "done_max"]
-    block = np.concatenate([tl.series[n].astype(np.int64).ravel() for n in TIMELINE_SERIES] + [tl.scalars[f].astype(np.int64) for f in sums])
-    t, mx = torch.from_numpy(block), torch.from_numpy(tl.scalars["done_max"].astype(np.int64))
-    if device is not None:
-        t, mx = t.to(device), mx.to(device)
-    dist.all_reduce(t, op=dist.ReduceOp.SUM)
-    dist.all_reduce(mx, op=dist.ReduceOp.MAX)
-    block = t.cpu().numpy()
-    ns, g = tl.ngroups * tl.bins, tl.ngroups
-    for k, n in enumerate(TIMELINE_SERIES):
-        tl.series[n][...] = block[k * ns:(k + 1) * ns].reshape(tl.series[n].shape).astype(np.uint64)
-    for k, f in enumerate(sums):
-        tl.scalars[f][:] = block[5 * ns + k * g:5 * ns + (k + 1) * g]
-    tl.scalars["done_max"][:] = mx.cpu().numpy()
+    _allreduce_sums_and_max([tl.series[n] for n in TIMELINE_SERIES] + [tl.scalars[f] for f in TIMELINE_FIELDS if f != "done_max"], tl.scalars["done_max"], device)
     return tl
 
 

@@ -71,21 +71,23 @@ def main(argv=None):
     t0 = time.perf_counter()
     res = []
     CH = 1024  # trials per call: bounds the device arena (2.7 GB per 1024 trials of the sweep)
-    cdf = pkg.Dist(len(points), args.cdf_bins, args.cdf_bin_ms) if args.cdf else None
     tl_bins = -(-(10000 + 6) // args.timeline_bin)  # Beta arrivals: 10 000 subframes, a completion at most 6 behind
-    tl = pkg.Timeline(len(points), tl_bins, args.timeline_bin) if args.timeline else None
+    # the sweep's reduction, one group per sweep point: its accumulator, the engine call that makes a chunk's and its leading arguments, then the
+    # all-reduce across ranks, the CSV formatter and the file
+    red = None
+    if args.cdf:
+        red = (pkg.Dist(len(points), args.cdf_bins, args.cdf_bin_ms), eng.run_trials_dist, (args.cdf_bins, args.cdf_bin_ms), distmod.allreduce_dist, pkg.dist_csv, args.cdf)
+    elif args.timeline:
+        red = (pkg.Timeline(len(points), tl_bins, args.timeline_bin), eng.run_trials_timeline, (tl_bins, args.timeline_bin), distmod.allreduce_timeline, pkg.timeline_csv, args.timeline)
     for a in range(0, len(mine), CH):
         part = mine[a:a + CH]
-        if tl is not None:  # the timelines come from the device with the results: no per-UE log is copied
-            r, _, t = eng.run_trials_timeline([cfgs[i] for i in part], tl_bins, args.timeline_bin, groups=[i % len(points) for i in part], ngroups=len(points))
-            for k in range(len(points)):
-                tl.merge_group(k, t, k)
-        elif cdf is None:
+        if red is None:
             r, _ = eng.run_trials([cfgs[i] for i in part])
-        else:  # the distributions come from the device with the results: no per-UE log is copied
-            r, _, d = eng.run_trials_dist([cfgs[i] for i in part], args.cdf_bins, args.cdf_bin_ms, groups=[i % len(points) for i in part], ngroups=len(points))
+        else:  # the chunk's reduction comes from the device with the results: no per-UE log is copied
+            acc, run, params = red[:3]
+            r, _, got = run([cfgs[i] for i in part], *params, groups=[i % len(points) for i in part], ngroups=len(points))
             for k in range(len(points)):
-                cdf.merge_group(k, d, k)
+                acc.merge_group(k, got, k)
         res.extend(r)
     dt = time.perf_counter() - t0
     agg = distmod.aggregate_rows([cfgs[i] for i in mine], res, points)
@@ -96,16 +98,12 @@ def main(argv=None):
     if variant == pkg.VARIANT_BETA_C:
         rows = [(i, pkg.format_results(cfgs[i], r, 0.0).decode()) for i, r in zip(mine, res)]
         allrows = distmod.gather_trial_rows(rows, dst=0, device=dev if (world > 1 and args.backend == "nccl") else None)
-    if cdf is not None:
-        distmod.allreduce_dist(cdf, device=dev if (world > 1 and args.backend == "nccl") else None)
+    if red is not None:
+        acc, _, _, allreduce, to_csv, path = red
+        allreduce(acc, device=dev if (world > 1 and args.backend == "nccl") else None)
         if rank == 0:
-            with open(args.cdf, "wb") as f:
-                f.write(pkg.dist_csv(cdf, labels=points))
-    if tl is not None:
-        distmod.allreduce_timeline(tl, device=dev if (world > 1 and args.backend == "nccl") else None)
-        if rank == 0:
-            with open(args.timeline, "wb") as f:
-                f.write(pkg.timeline_csv(tl, labels=points))
+            with open(path, "wb") as f:
+                f.write(to_csv(acc, labels=points))
     if rank == 0:
         fi = {n: k for k, n in enumerate(distmod.AGG_FIELDS)}
         summary = {"program": args.program, "times": args.times, "points": points, "world": world,

@@ -263,3 +263,42 @@ def test_cli_timeline_equals_the_logs(pkg, eng, tmp_path, workers):
     _, logs = eng.run_trials(cfgs, want_logs=True)
     exp = pkg.timeline_from_logs(cfgs, logs, 2002, 5, groups=[k % 3 for k in range(9)], ngroups=3)  # the CLI's default: 5 ms bins over maxTime + 6 ms
     assert out.read_bytes() == pkg.timeline_csv(exp, labels=points) and len(out.read_bytes()) > 1000
+
+
+def test_alternating_reductions_share_one_engine(pkg, eng):
+    """The two reductions of an engine share one device buffer, one job table and one pair of events: timeline and dist calls alternate on one engine —
+    a small buffer after a large one (anything stale or unzeroed would show), then growing ones — and a plain call ends the row.  Every reduction equals
+    the host-side definition over the logs of its own call and the same call on an engine that has made no other; the results of all calls are the same."""
+    cfgs = [pkg.make_cfg(n, variant=pkg.VARIANT_BETA_C, rng_mode=pkg.RNG_PHILOX, seed=k) for k, n in enumerate((300, 8192, 8193))]  # the edges of both kernels' tile
+    cfgs.append(pkg.make_cfg(2000, variant=pkg.VARIANT_WITHNOMA_C, rng_mode=pkg.RNG_PHILOX, seed=3, maxMsg2TxCount=3))  # some UEs start over
+    assert pkg.timeline_tile_ues() == pkg.dist_tile_ues() == 8192
+    steps = [("timeline", (horizon(cfgs[0], 5), 5), [0, 1, 2, 0]), ("dist", (16, 1), [0, 0, 0, 0]), ("timeline", (horizon(cfgs[0], 1), 1), None),
+             ("dist", (16384, 1), None)]
+    all_res = []
+    for kind, params, groups in steps:
+        def call(e):
+            return (e.run_trials_timeline if kind == "timeline" else e.run_trials_dist)(cfgs, *params, groups=groups, want_logs=True)
+        res, logs, red = call(eng)
+        tm = eng.timing()
+        assert all(r.status == 0 for r in res)
+        if kind == "timeline":
+            assert tm.timeline_ms > 0 and tm.dist_ms == 0
+            host = pkg.timeline_from_logs(cfgs, logs, *params, groups=groups)
+            assert int(red.scalars["restarted"].sum()) > 0
+        else:
+            assert tm.dist_ms > 0 and tm.timeline_ms == 0
+            host = pkg.dist_from_logs(logs, *params, groups=groups)
+        assert red.ngroups == host.ngroups == (4 if groups is None else max(groups) + 1) and red.same_as(host)
+        fresh = pkg.Engine(0)
+        try:
+            assert red.same_as(call(fresh)[2])
+        finally:
+            fresh.close()
+        all_res.append(res)
+    res, _ = eng.run_trials(cfgs)
+    tm = eng.timing()
+    assert tm.dist_ms == 0 and tm.timeline_ms == 0
+    all_res.append(res)
+    assert len(all_res) == 5
+    for res in all_res[1:]:
+        assert [r.as_dict() for r in res] == [r.as_dict() for r in all_res[0]]
