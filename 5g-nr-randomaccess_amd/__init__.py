@@ -54,7 +54,8 @@ class PrachTiming(C.Structure):
                 ("launches", C.c_int32), ("workgroups", C.c_int32), ("updates", C.c_uint64),
                 ("cluster_size", C.c_int32), ("resident_limit", C.c_int32), ("fallback_trials", C.c_int32), ("spin_timeouts", C.c_int32),
                 ("rec_mode", C.c_int32), ("xcd_packed", C.c_int32), ("group_visits", C.c_uint64), ("event_ues", C.c_uint64),
-                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("dist_ms", C.c_double), ("timeline_ms", C.c_double)]
+                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
+                ("sojourn_ms", C.c_double)]
 
 
 DIST_PTC_BINS, DIST_MAX_DELAY_BINS = 256, 16384
@@ -70,7 +71,7 @@ class PrachDist(C.Structure):
 
 
 class _Reduction:
-    """What Dist and Timeline share.  A subclass names its scalar fields (_FIELDS), the C struct of one group (_STRUCT), the library's merge and its
+    """What Dist, Timeline and Sojourn share.  A subclass names its scalar fields (_FIELDS), the C struct of one group (_STRUCT), the library's merge and its
     defining parameters (_PARAMS), and gives ``_arrays()`` — its [ngroups, n] uint64 arrays in the order of the C ABI — ``_scalar(f)``, the int64 array of
     length ngroups of scalar field f, and ``_cargs(g)``, group g's arrays as the library's merge and CSV functions take them."""
 
@@ -85,7 +86,7 @@ class _Reduction:
         return [a[g].ctypes.data_as(C.POINTER(C.c_uint64)) for a in self._arrays()]
 
     def merge_group(self, g, other, og):
-        """Adds group ``og`` of ``other`` to group ``g`` (prach_dist_merge / prach_timeline_merge)."""
+        """Adds group ``og`` of ``other`` to group ``g`` (prach_dist_merge / prach_timeline_merge / prach_sojourn_merge)."""
         sp, a, b = self.spec(), self._group(g), other._group(og)
         getattr(lib(), self._MERGE)(C.byref(sp), C.byref(a), *self._cargs(g), C.byref(b), *other._cargs(og))
         self._store(g, a)
@@ -168,6 +169,53 @@ class Timeline(_Reduction):
         return (self._series(g),)
 
 
+SOJOURN_MAX_ARRIVAL_BINS, SOJOURN_MAX_DELAY_BINS = 4096, 16384
+SOJOURN_FIELDS = ("trials", "ues", "arrived", "success", "restarted", "arrival_overflow", "delay_overflow", "sojourn_sum", "sojourn_max")
+
+
+class PrachSojournSpec(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("arrival_bins", "arrival_bin_ms", "delay_bins", "delay_bin_ms", "ngroups", "reserved")]
+
+
+class PrachSojourn(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in SOJOURN_FIELDS[:-1]] + [("sojourn_max", C.c_int64)]
+
+
+class Sojourn(_Reduction):
+    """The sojourn histograms of ``ngroups`` trial groups (include/prach.h, prach_sojourn): ``hist`` [ngroups, arrival_bins, delay_bins], ``row_arrived`` and
+    ``row_delay_overflow`` [ngroups, arrival_bins] as numpy uint64 (row r covers arrivals in [r * arrival_bin_ms, (r + 1) * arrival_bin_ms)), and
+    ``scalars[field]``, one int64 array of length ngroups per field of SOJOURN_FIELDS."""
+    _FIELDS, _STRUCT, _MERGE, _PARAMS = SOJOURN_FIELDS, PrachSojourn, "prach_sojourn_merge", ("arrival_bins", "arrival_bin_ms", "delay_bins", "delay_bin_ms")
+
+    def __init__(self, ngroups, arrival_bins, arrival_bin_ms, delay_bins, delay_bin_ms=1):
+        import numpy as np
+        self.arrival_bins, self.arrival_bin_ms, self.delay_bins, self.delay_bin_ms = int(arrival_bins), int(arrival_bin_ms), int(delay_bins), int(delay_bin_ms)
+        self.ngroups = int(ngroups)
+        self.hist = np.zeros((self.ngroups, self.arrival_bins, self.delay_bins), dtype=np.uint64)
+        self.row_arrived = np.zeros((self.ngroups, self.arrival_bins), dtype=np.uint64)
+        self.row_delay_overflow = np.zeros((self.ngroups, self.arrival_bins), dtype=np.uint64)
+        self.scalars = {f: np.zeros(self.ngroups, dtype=np.int64) for f in SOJOURN_FIELDS}
+        self.scalars["sojourn_max"][:] = -1
+
+    def spec(self):
+        return PrachSojournSpec(self.arrival_bins, self.arrival_bin_ms, self.delay_bins, self.delay_bin_ms, self.ngroups, 0)
+
+    def _arrays(self):
+        return [self.hist, self.row_arrived, self.row_delay_overflow]
+
+    def _scalar(self, f):
+        return self.scalars[f]
+
+    def _cargs(self, g):
+        return tuple(self._rows(g))
+
+    def quantile(self, g, row, q):
+        """Lower edge (ms) of the delay bin holding the max(1, ceil(q * n))-th smallest sojourn of arrival row ``row`` of group g (row -1: pooled over all
+        rows), n counting the row's overflow too; -1: no successful UE there, or that rank lies in the overflow (prach_sojourn_quantile)."""
+        sp, (h, _, o) = self.spec(), self._rows(g)
+        return int(lib().prach_sojourn_quantile(C.byref(sp), h, o, int(row), float(q)))
+
+
 class PrachError(RuntimeError):
     def __init__(self, status, what=""):
         self.status = status
@@ -218,6 +266,18 @@ def lib():
         L.prach_timeline_format_csv.restype = C.c_size_t
         L.prach_timeline_tile_ues.argtypes = []
         L.prach_timeline_window_bins.argtypes = []
+        L.prach_run_trials_sojourn.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachSojournSpec),
+                                               C.POINTER(C.c_int32), C.POINTER(PrachSojourn), u64p, u64p, u64p]
+        L.prach_sojourn_accumulate_logs.argtypes = [C.POINTER(PrachSojournSpec), C.POINTER(PrachCfg), C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachSojourn),
+                                                    u64p, u64p, u64p]
+        L.prach_sojourn_merge.argtypes = [C.POINTER(PrachSojournSpec), C.POINTER(PrachSojourn), u64p, u64p, u64p, C.POINTER(PrachSojourn), u64p, u64p, u64p]
+        L.prach_sojourn_merge.restype = None
+        L.prach_sojourn_quantile.argtypes = [C.POINTER(PrachSojournSpec), u64p, u64p, C.c_int, C.c_double]
+        L.prach_sojourn_quantile.restype = C.c_int64
+        L.prach_sojourn_format_csv.argtypes = [C.POINTER(PrachSojournSpec), C.POINTER(PrachSojourn), u64p, u64p, u64p, C.c_char_p, C.c_char_p, C.c_size_t]
+        L.prach_sojourn_format_csv.restype = C.c_size_t
+        L.prach_sojourn_tile_ues.argtypes = []
+        L.prach_sojourn_window_words.argtypes = []
         L.prach_cfg_defaults.argtypes = [C.POINTER(PrachCfg), C.c_int]
         L.prach_cfg_defaults.restype = None
         L.prach_cfg_validate.argtypes = [C.POINTER(PrachCfg)]
@@ -257,7 +317,8 @@ EXPORTS = ("prach_engine_create", "prach_engine_destroy", "prach_engine_set", "p
            "prach_results_csv_accumulate", "prach_results_csv_row", "prach_device_glibc_stream", "prach_noma_activation_range", "prach_noma_activation_stream",
            "prach_noma_activation_table_device", "prach_run_trials_dist", "prach_dist_accumulate_logs", "prach_dist_merge", "prach_dist_delay_quantile",
            "prach_dist_format_csv", "prach_dist_tile_ues", "prach_run_trials_timeline", "prach_timeline_accumulate_logs", "prach_timeline_merge",
-           "prach_timeline_format_csv", "prach_timeline_tile_ues", "prach_timeline_window_bins")
+           "prach_timeline_format_csv", "prach_timeline_tile_ues", "prach_timeline_window_bins", "prach_run_trials_sojourn", "prach_sojourn_accumulate_logs",
+           "prach_sojourn_merge", "prach_sojourn_quantile", "prach_sojourn_format_csv", "prach_sojourn_tile_ues", "prach_sojourn_window_words")
 
 
 def make_cfg(nUE, variant=VARIANT_BETA_C, uniform=0, rng_mode=RNG_GLIBC, seed=0, stream_offset=0, **kw) -> PrachCfg:
@@ -309,7 +370,7 @@ class Engine:
         return list(res), logs
 
     def _call_reduced(self, name, cfgs, red, groups, want_logs):
-        """... with the reduction `red` (a Dist or a Timeline), which takes what the device made.  Returns (results, logs, red)."""
+        """... with the reduction `red` (a Dist, a Timeline or a Sojourn), which takes what the device made.  Returns (results, logs, red)."""
         sp = red.spec()
         gg = (red._STRUCT * red.ngroups)()
         gp = None if groups is None else (C.c_int32 * len(cfgs))(*[int(g) for g in groups])
@@ -335,6 +396,13 @@ class Engine:
         reduced on the device from the per-UE log records the simulation kernels leave there (prach_run_trials_timeline; Beta.c and
         RandomAccessWithNOMA trials only).  groups / ngroups / want_logs as in run_trials_dist.  Returns (results, logs, Timeline)."""
         return self._call_reduced("prach_run_trials_timeline", cfgs, Timeline(_ngroups(len(cfgs), groups, ngroups), bins, bin_ms), groups, want_logs)
+
+    def run_trials_sojourn(self, cfgs, arrival_bins, arrival_bin_ms, delay_bins, delay_bin_ms, groups=None, want_logs=False, ngroups=None):
+        """run_trials plus the histogram of the time from arrival to Msg4 by arrival row per trial group, reduced on the device from the per-UE log records
+        the simulation kernels leave there (prach_run_trials_sojourn; Beta.c and RandomAccessWithNOMA trials only).  groups / ngroups / want_logs as in
+        run_trials_dist.  Returns (results, logs, Sojourn)."""
+        return self._call_reduced("prach_run_trials_sojourn", cfgs,
+                                  Sojourn(_ngroups(len(cfgs), groups, ngroups), arrival_bins, arrival_bin_ms, delay_bins, delay_bin_ms), groups, want_logs)
 
     @staticmethod
     def _log_buffers(cfgs, want_logs):
@@ -525,3 +593,23 @@ def timeline_from_logs(cfgs, logs, bins, bin_ms=1, groups=None, ngroups=None) ->
 def timeline_csv(tl: Timeline, labels=None) -> bytes:
     """The CSV text of every group (prach_timeline_format_csv), labelled labels[g] (default: the group number)."""
     return _csv("prach_timeline_format_csv", tl, labels)
+
+
+def sojourn_tile_ues() -> int:
+    return lib().prach_sojourn_tile_ues()
+
+
+def sojourn_window_words() -> int:
+    return lib().prach_sojourn_window_words()
+
+
+def sojourn_from_logs(cfgs, logs, arrival_bins, arrival_bin_ms, delay_bins, delay_bin_ms, groups=None, ngroups=None) -> Sojourn:
+    """The host-side definition of the sojourn histograms (prach_sojourn_accumulate_logs): logs[k] is the per-UE log of the trial with config cfgs[k] — a
+    ctypes array of PrachUeLog or an int32 array of shape [nUE, 16] — added to group groups[k] (None: group k)."""
+    return _from_logs("prach_sojourn_accumulate_logs", Sojourn(_ngroups(len(logs), groups, ngroups), arrival_bins, arrival_bin_ms, delay_bins, delay_bin_ms),
+                      logs, groups, cfgs)
+
+
+def sojourn_csv(sj: Sojourn, labels=None) -> bytes:
+    """The CSV text of every group (prach_sojourn_format_csv), labelled labels[g] (default: the group number)."""
+    return _csv("prach_sojourn_format_csv", sj, labels)

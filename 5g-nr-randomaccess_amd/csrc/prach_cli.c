@@ -23,6 +23,9 @@
  * --timeline FILE [--timeline-bin MS]: arrivals, successes, sojourn and timer sums by arrival time and completions by completion time
  * (prach_run_trials_timeline: reduced on the device, so it works with --logs 0), one group per sweep point with the --times seeds merged, labelled nUE;
  * bins of MS ms (default 5) that cover the whole horizon, maxTime + 6 ms; --program beta|withnoma only, and not together with --cdf (one reduction per call);
+ * --sojourn FILE [--sojourn-arrival-ms MS] [--sojourn-bin MS]: the histogram of the time from arrival to Msg4 by arrival row (prach_run_trials_sojourn: reduced
+ * on the device, so it works with --logs 0), one group per sweep point with the --times seeds merged, labelled nUE; rows of MS ms (default 500) over maxTime,
+ * delay bins of MS ms (default 5) over maxTime + 6 ms; --program beta|withnoma only, and not together with --cdf or --timeline;
  * --devices LIST: the same with explicit HIP ordinals (an ordinal may repeat);
  * --gpus N: the --times x sweep grid sharded over N devices of the node by host C — one forked child per device,
  * forked BEFORE any HIP call, trials dealt by descending cost (Philox: any trial anywhere; glibc: whole seeds, because
@@ -90,23 +93,31 @@ static double now_s(void) {
     return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
-/* The reduction a run makes on the device next to its results: the distributions (--cdf, prach_run_trials_dist) or the timelines (--timeline,
- * prach_run_trials_timeline), never both; neither spec: none, plain prach_run_trials.  A block holds the groups of one worker or of one call, one group per
+/* The reduction a run makes on the device next to its results: the distributions (--cdf, prach_run_trials_dist), the timelines (--timeline,
+ * prach_run_trials_timeline) or the sojourn histograms (--sojourn, prach_run_trials_sojourn), never two of them; no spec: none, plain prach_run_trials.  A block holds the groups of one worker or of one call, one group per
  * sweep point: --cdf prach_dist[npts] | delay_hist[npts][bins] | ptc_hist[npts][256]; --timeline prach_timeline[npts] | five series [npts][bins] each
- * (arrivals, success, sojourn_sum, timer_sum, done). */
+ * (arrivals, success, sojourn_sum, timer_sum, done); --sojourn prach_sojourn[npts] | hist[npts][rows][bins] | row_arrived[npts][rows] | row_delay_overflow[npts][rows]. */
 typedef struct reduction {
     const prach_dist_spec *cdf;
     const prach_timeline_spec *tl;
+    const prach_sojourn_spec *sj;
     const char *path; /* the CSV file */
     size_t text_cap;  /* the CSV text of one group at most */
 } reduction;
-static int red_on(const reduction *r) { return r->cdf || r->tl; }
+static int red_on(const reduction *r) { return r->cdf || r->tl || r->sj; }
+static size_t sj_cells(const prach_sojourn_spec *s) { return (size_t)s->arrival_bins * (size_t)s->delay_bins; }
 static size_t red_block_bytes(const reduction *r) {
     if (r->tl) return (size_t)r->tl->ngroups * (sizeof(prach_timeline) + 5 * 8 * (size_t)r->tl->bins);
+    if (r->sj) return (size_t)r->sj->ngroups * (sizeof(prach_sojourn) + 8 * (sj_cells(r->sj) + 2 * (size_t)r->sj->arrival_bins));
     return r->cdf ? (size_t)r->cdf->ngroups * (sizeof(prach_dist) + 8 * ((size_t)r->cdf->delay_bins + PRACH_DIST_PTC_BINS)) : 0;
 }
-/* group g of block b: --cdf its q-th histogram (0 delay, 1 preamble count), --timeline its q-th series */
+/* group g of block b: --cdf its q-th histogram (0 delay, 1 preamble count), --timeline its q-th series, --sojourn 0 hist, 1 row_arrived, 2 row_delay_overflow */
 static uint64_t *red_array(const reduction *r, char *b, int q, int g) {
+    if (r->sj) {
+        uint64_t *const h = (uint64_t *)(b + (size_t)r->sj->ngroups * sizeof(prach_sojourn));
+        const size_t ng = (size_t)r->sj->ngroups, rows = (size_t)r->sj->arrival_bins;
+        return q == 0 ? h + (size_t)g * sj_cells(r->sj) : h + ng * sj_cells(r->sj) + ((size_t)(q - 1) * ng + (size_t)g) * rows;
+    }
     if (r->tl) return (uint64_t *)(b + (size_t)r->tl->ngroups * sizeof(prach_timeline)) + ((size_t)q * (size_t)r->tl->ngroups + (size_t)g) * (size_t)r->tl->bins;
     uint64_t *const dh = (uint64_t *)(b + (size_t)r->cdf->ngroups * sizeof(prach_dist));
     return q == 0 ? dh + (size_t)g * (size_t)r->cdf->delay_bins : dh + (size_t)r->cdf->ngroups * (size_t)r->cdf->delay_bins + (size_t)g * PRACH_DIST_PTC_BINS;
@@ -115,6 +126,7 @@ static uint64_t *red_array(const reduction *r, char *b, int q, int g) {
 static void red_init_block(const reduction *r, char *b) {
     for (int g = 0; r->tl && g < r->tl->ngroups; g++) ((prach_timeline *)b)[g].done_max = -1;
     for (int g = 0; r->cdf && g < r->cdf->ngroups; g++) ((prach_dist *)b)[g].delay_max = -1;
+    for (int g = 0; r->sj && g < r->sj->ngroups; g++) ((prach_sojourn *)b)[g].sojourn_max = -1;
 }
 static void red_merge_block(const reduction *r, char *into, char *from) {
     for (int g = 0; r->tl && g < r->tl->ngroups; g++) {
@@ -123,6 +135,9 @@ static void red_merge_block(const reduction *r, char *into, char *from) {
         for (int q = 0; q < 5; q++) { a[q] = red_array(r, into, q, g); b[q] = red_array(r, from, q, g); }
         prach_timeline_merge(r->tl, (prach_timeline *)into + g, a, (prach_timeline *)from + g, b);
     }
+    for (int g = 0; r->sj && g < r->sj->ngroups; g++)
+        prach_sojourn_merge(r->sj, (prach_sojourn *)into + g, red_array(r, into, 0, g), red_array(r, into, 1, g), red_array(r, into, 2, g), (prach_sojourn *)from + g,
+                            red_array(r, from, 0, g), red_array(r, from, 1, g), red_array(r, from, 2, g));
     for (int g = 0; r->cdf && g < r->cdf->ngroups; g++)
         prach_dist_merge(r->cdf, (prach_dist *)into + g, red_array(r, into, 0, g), red_array(r, into, 1, g), (prach_dist *)from + g, red_array(r, from, 0, g), red_array(r, from, 1, g));
 }
@@ -133,6 +148,7 @@ static size_t red_format_group(const reduction *r, char *b, int g, const char *l
         for (int q = 0; q < 5; q++) ser[q] = red_array(r, b, q, g);
         return prach_timeline_format_csv(r->tl, (prach_timeline *)b + g, ser, label, out, cap);
     }
+    if (r->sj) return prach_sojourn_format_csv(r->sj, (prach_sojourn *)b + g, red_array(r, b, 0, g), red_array(r, b, 1, g), red_array(r, b, 2, g), label, out, cap);
     return prach_dist_format_csv(r->cdf, (prach_dist *)b + g, red_array(r, b, 0, g), red_array(r, b, 1, g), label, out, cap);
 }
 
@@ -143,6 +159,7 @@ static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *
     char *const b = call_block;
     const int rc = red->tl ? prach_run_trials_timeline(eng, c, n, r, logs, red->tl, grp, (prach_timeline *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0),
                                                        red_array(red, b, 2, 0), red_array(red, b, 3, 0), red_array(red, b, 4, 0))
+                   : red->sj ? prach_run_trials_sojourn(eng, c, n, r, logs, red->sj, grp, (prach_sojourn *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0), red_array(red, b, 2, 0))
                            : prach_run_trials_dist(eng, c, n, r, logs, red->cdf, grp, (prach_dist *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0));
     if (rc == PRACH_OK) red_merge_block(red, worker_block, call_block);
     return rc;
@@ -230,8 +247,8 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
 int main(int argc, char *argv[]) {
     int randomMax = 1, variant = PRACH_VARIANT_WITHNOMA_C, rng = PRACH_RNG_GLIBC, device = 0, want_logs = 1, gpus = 1, rng_given = 0;
     int sweep_lo = 10000, sweep_hi = 100000, sweep_step = 10000; /* WithNOMA:221 */
-    const char *outdir = ".", *csv_path = NULL, *devlist = NULL, *cdf_path = NULL, *tl_path = NULL;
-    int cdf_bins = 4096, cdf_bin_ms = 1, tl_bin_ms = 5;
+    const char *outdir = ".", *csv_path = NULL, *devlist = NULL, *cdf_path = NULL, *tl_path = NULL, *sj_path = NULL;
+    int cdf_bins = 4096, cdf_bin_ms = 1, tl_bin_ms = 5, sj_row_ms = 500, sj_bin_ms = 5;
     int devs[64];
     /* --program must be known before the defaults are laid down */
     for (int i = 1; i + 1 < argc; i += 2)
@@ -319,11 +336,21 @@ int main(int argc, char *argv[]) {
         } else if (strcmp(a, "--timeline-bin") == 0) {
             if (atoi(v) < 1) die("--timeline-bin MS: the width of a timeline bin in ms, at least 1");
             tl_bin_ms = atoi(v);
+        } else if (strcmp(a, "--sojourn") == 0) {
+            sj_path = v;
+        } else if (strcmp(a, "--sojourn-arrival-ms") == 0) {
+            if (atoi(v) < 1) die("--sojourn-arrival-ms MS: the width of an arrival row in ms, at least 1");
+            sj_row_ms = atoi(v);
+        } else if (strcmp(a, "--sojourn-bin") == 0) {
+            if (atoi(v) < 1) die("--sojourn-bin MS: the width of a delay bin in ms, at least 1");
+            sj_bin_ms = atoi(v);
         } else {
             usage_and_exit();
         }
     }
     base.rng_mode = rng;
+    if (sj_path && variant == PRACH_VARIANT_NOMA_C) die("--sojourn needs --program beta or withnoma (NOMA.c logs no trace of a UE's cycle start)");
+    if (sj_path && (tl_path || cdf_path)) die("--sojourn cannot be combined with --cdf or --timeline: one reduction per call");
     if (tl_path && variant == PRACH_VARIANT_NOMA_C) die("--timeline needs --program beta or withnoma (NOMA.c logs no trace of a UE's cycle start)");
     if (tl_path && cdf_path) die("--timeline and --cdf cannot be combined: one reduction per call");
     if (csv_path && variant != PRACH_VARIANT_BETA_C) die("--csv needs --program beta (AveragePerformance.py reads its six-number Results.txt)");
@@ -392,15 +419,22 @@ int main(int argc, char *argv[]) {
             }
     }
 
-    /* --cdf / --timeline: one block of groups per worker in a shared mapping, like the results; the parent merges them (integers: exact in any order).
+    /* --cdf / --timeline / --sojourn: one block of groups per worker in a shared mapping, like the results; the parent merges them (integers: exact in any order).
      * The timeline's bins cover the horizon (a completion is at most maxTime + 5) */
     const prach_dist_spec cdf_spec = {cdf_bins, cdf_bin_ms, npts, 0};
     const int tl_bins = (prach_max_time(&base) + 6 + tl_bin_ms - 1) / tl_bin_ms;
     const prach_timeline_spec tl_spec = {tl_bins, tl_bin_ms, npts, 0};
     if (tl_path && tl_bins > PRACH_TIMELINE_MAX_BINS) die("--timeline-bin MS: too many bins");
-    /* a line of --cdf: a label of at most 10 digits, three numbers, a share; of --timeline: the label, a series name, two numbers */
-    const reduction red_ = {cdf_path ? &cdf_spec : NULL, tl_path ? &tl_spec : NULL, tl_path ? tl_path : cdf_path,
-                            tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1};
+    /* the sojourn's rows cover the arrivals (below maxTime), its delay bins the horizon */
+    const int sj_rows = (prach_max_time(&base) + sj_row_ms - 1) / sj_row_ms, sj_bins = (prach_max_time(&base) + 6 + sj_bin_ms - 1) / sj_bin_ms;
+    const prach_sojourn_spec sj_spec = {sj_rows, sj_row_ms, sj_bins, sj_bin_ms, npts, 0};
+    if (sj_path && sj_rows > PRACH_SOJOURN_MAX_ARRIVAL_BINS) die("--sojourn-arrival-ms MS: too many rows");
+    if (sj_path && sj_bins > PRACH_SOJOURN_MAX_DELAY_BINS) die("--sojourn-bin MS: too many bins");
+    /* a line of --cdf: a label of at most 10 digits, three numbers, a share; of --timeline: the label, a series name, two numbers; of --sojourn: the label and
+     * three numbers, per cell and twice per row */
+    const reduction red_ = {cdf_path ? &cdf_spec : NULL, tl_path ? &tl_spec : NULL, sj_path ? &sj_spec : NULL, sj_path ? sj_path : tl_path ? tl_path : cdf_path,
+                            sj_path ? 64 * ((size_t)sj_rows * ((size_t)sj_bins + 2) + 1) + 1
+                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1};
     const reduction *const red = &red_;
     char *red_blocks = NULL;
     if (red_on(red)) {

@@ -198,4 +198,16 @@ struct TimelineJob {
 struct TimelineOut { unsigned long long *arrivals, *success, *sojourn, *timer, *done, *scalars; }; // [ngroups][bins] each, [ngroups][TL_SCALARS]
 hipError_t launch_timeline_kernel(const TimelineJob *jobs, int njobs, int workgroups, int bins, int bin_ms, int scheme, TimelineOut out, hipStream_t stream);
 
+// prach_sojourn.hip: the sojourn histograms by arrival row of a launch's accepted trials (prach_run_trials_sojourn).  The jobs are the timeline's
+// (TimelineJob: log records and schedule of one trial), and so are tile and workgroup: one tile of TL_TILE consecutive UEs of one trial per workgroup.
+// scheme 1 privatises the first R = min(rows from the tile's first arrival row on, SJ_WINDOW_WORDS / delay_bins) rows in LDS, one 32-bit counter per
+// cell plus one arrived and one overflow counter per row, and flushes the non-zero ones; what falls outside, and everything under scheme 0, goes
+// straight to the call's buffers with 64-bit agent-scope atomics.
+constexpr int SJ_WINDOW_WORDS = 28672; // 112 KiB of cells, fourteen 500 ms rows of 2002 five-millisecond bins: measured against 8192 and 16384 words
+static_assert((unsigned long long)TL_TILE < (1ull << 32), "a 32-bit LDS counter holds what one tile adds to a cell or a row: at most one per UE");
+constexpr int SJ_SCALARS = 8; // per group: arrived, success, restarted, arrival_overflow, delay_overflow, sojourn_sum, sojourn_max + 1 (0: no successful UE), 1 spare
+struct SojournOut { unsigned long long *hist, *row_arrived, *row_overflow, *scalars; }; // [ngroups][rows][delay_bins], [ngroups][rows] twice, [ngroups][SJ_SCALARS]
+hipError_t launch_sojourn_kernel(const TimelineJob *jobs, int njobs, int workgroups, int rows, int row_ms, int delay_bins, int delay_bin_ms, int scheme, SojournOut out,
+                                 hipStream_t stream);
+
 } // namespace prach

@@ -41,15 +41,16 @@ struct prach_engine {
     std::vector<std::pair<hipMemGenericAllocationHandle_t, size_t>> vmm_parts;
     char *pinned = nullptr; // host staging mirror of the head of the arena (parameter blocks, arrival tables, stream seeds, results)
     size_t pinned_cap = 0;
-    // The device reduction of a call (prach_run_trials_dist or prach_run_trials_timeline: a call runs at most one, so both kinds share these): the call's
+    // The device reduction of a call (prach_run_trials_dist, prach_run_trials_timeline or prach_run_trials_sojourn: a call runs at most one, so all kinds share these): the call's
     // counters (zeroed once per call, copied out once at its end — not part of the arena, which is laid out again for every launch), the job table of one
     // launch, pinned and on the device, in bytes (DistJob or TimelineJob elements), and the events around the reduction kernel of a launch
-    // (prach_timing.dist_ms / timeline_ms).  All created and grown at the start of a call, never per launch.
+    // (prach_timing.dist_ms / timeline_ms / sojourn_ms).  All created and grown at the start of a call, never per launch.
     char *red_buf = nullptr;
     size_t red_cap = 0;
     char *red_jobs_h = nullptr, *red_jobs_d = nullptr;
     size_t red_jobs_cap = 0;
     hipEvent_t red_ev0 = nullptr, red_ev1 = nullptr;
+    int64_t opt_sojourn_scheme = 1;  // sojourn_kernel's binning (prach_sojourn.hip): 0 global atomics only, 1 rows of the histogram privatised in LDS
     int64_t opt_timeline_scheme = 1; // timeline_kernel's binning (prach_timeline.hip): 0 global atomics only, 1 windows of bins privatised in LDS (measured faster: DESIGN.md 4)
     int64_t opt_dist_scheme = 1;   // dist_kernel's binning of the preamble counts (prach_dist.hip): 0 plain LDS adds, 1 per-wavefront copies (measured fastest), 2 match and aggregate
     prach_timing last{};
@@ -119,7 +120,7 @@ size_t mbox_bytes(const prach_cfg &c, int G, int &evw, int &mbstride) {
 }
 
 // stream_len[k]: glibc draw-stream window of trial k (0 in Philox mode); G: workgroups per trial (0 = trial_kernel)
-// all_logs: every trial gets a device log region (the call's reduction reads it there: prach_run_trials_timeline), not only the ones whose log the host asked for
+// all_logs: every trial gets a device log region (the call's reduction reads it there: prach_run_trials_timeline, prach_run_trials_sojourn), not only the ones whose log the host asked for
 LaunchLayout layout_launch(const prach_cfg *cfgs, const int *idx, int m, prach_ue_log *const *ue_logs, bool all_logs, const std::vector<size_t> &stream_len, int G, bool batch, bool full_calendars, int64_t calendar_cap) {
     LaunchLayout L;
     L.t.resize(m);
@@ -412,10 +413,11 @@ static int noma_device_activation(prach_engine *e, const TrialDev *dparams, cons
     return PRACH_OK;
 }
 
-// What a call reduces on the device next to its results: the caller's spec, groups and outputs of prach_run_trials_dist or prach_run_trials_timeline.
-// The call's device buffer is a row of parts, [ngroups][words] 64-bit counters each: the arrays the caller gets as they are (dist: delay_hist, ptc_hist;
-// timeline: the five series arrivals, success, sojourn_sum, timer_sum, done), then the scalars the kernel keeps per group.
-enum class Red { dist, timeline };
+// What a call reduces on the device next to its results: the caller's spec, groups and outputs of prach_run_trials_dist, prach_run_trials_timeline or
+// prach_run_trials_sojourn.  The call's device buffer is a row of parts, [ngroups][words] 64-bit counters each: the arrays the caller gets as they are (dist:
+// delay_hist, ptc_hist; timeline: the five series arrivals, success, sojourn_sum, timer_sum, done; sojourn: hist, row_arrived, row_delay_overflow), then the
+// scalars the kernel keeps per group.
+enum class Red { dist, timeline, sojourn };
 constexpr int RED_MAX_PARTS = 6;
 struct Reduction {
     Red kind;
@@ -425,16 +427,22 @@ struct Reduction {
     prach_dist *dist;
     const prach_timeline_spec *tspec; // timeline
     prach_timeline *tl;
+    const prach_sojourn_spec *sspec; // sojourn
+    prach_sojourn *sj;
     uint64_t *out[RED_MAX_PARTS - 1]; // the caller's arrays, one per part in front of the scalars
 };
 // words per group of every part; returns their number
 static int red_parts(const Reduction &r, size_t words[RED_MAX_PARTS]) {
     if (r.kind == Red::dist) { words[0] = (size_t)r.dspec->delay_bins; words[1] = PRACH_DIST_PTC_BINS; words[2] = DIST_SCALARS; return 3; }
+    if (r.kind == Red::sojourn) {
+        words[0] = (size_t)r.sspec->arrival_bins * (size_t)r.sspec->delay_bins; words[1] = words[2] = (size_t)r.sspec->arrival_bins; words[3] = SJ_SCALARS;
+        return 4;
+    }
     for (int q = 0; q < 5; q++) words[q] = (size_t)r.tspec->bins;
     words[5] = TL_SCALARS;
     return 6;
 }
-static size_t red_job_bytes(Red kind) { return kind == Red::dist ? sizeof(DistJob) : sizeof(TimelineJob); }
+static size_t red_job_bytes(Red kind) { return kind == Red::dist ? sizeof(DistJob) : sizeof(TimelineJob); } // (sojourn takes the timeline's jobs)
 
 // What one prach_run_trials call carries from launch to launch
 struct CallCtx {
@@ -449,7 +457,7 @@ struct CallCtx {
     unsigned long long *d_part[RED_MAX_PARTS] = {}; // the call's device buffer, part by part (red_parts)
     std::vector<uint64_t> trials, ues;        // per group, counted on the host as launches are accepted
     int group_of(int k) const { return red->group ? red->group[k] : k; }
-    bool reads_device_logs() const { return red && red->kind == Red::timeline; }
+    bool reads_device_logs() const { return red && red->kind != Red::dist; }
     // dist only: NOMA.c in the reference's stream finishes on the host: its groups' accumulators (sized on first use)
     const prach_dist_spec *dist_spec() const { return red && red->kind == Red::dist ? red->dspec : nullptr; }
     std::vector<prach_dist> host_d;
@@ -751,11 +759,11 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
     const DevResult *const drs = reinterpret_cast<const DevResult *>(H);
     // the call's reduction over the trials this launch finished — the ones the loop below accepts, so a trial that is rerun is counted once — behind the
     // simulation kernel on the same stream; it runs while the host turns DevResult into prach_result.  dist reads the timers and preamble counts the
-    // simulation kernel left in the arena, timeline its log records and the launch's own copy of every arrival schedule
+    // simulation kernel left in the arena, timeline and sojourn its log records and the launch's own copy of every arrival schedule
     bool red_launched = false;
     if (cx.red) {
         const Reduction &R = *cx.red;
-        const bool tl = R.kind == Red::timeline;
+        const bool tl = R.kind != Red::dist; // (the jobs and the tile of the timeline are the sojourn's too)
         int njobs = 0, wgs = 0;
         for (int k = 0; k < m; k++) {
             const DevResult &dr = drs[k];
@@ -777,7 +785,8 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
             unsigned long long *const *const d = cx.d_part;
             HIPCHK(hipMemcpyAsync(e->red_jobs_d, e->red_jobs_h, red_job_bytes(R.kind) * (size_t)njobs, hipMemcpyHostToDevice, e->stream));
             HIPCHK(hipEventRecord(e->red_ev0, e->stream));
-            if (tl) HIPCHK(launch_timeline_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, wgs, R.tspec->bins, R.tspec->bin_ms, (int)e->opt_timeline_scheme, TimelineOut{d[0], d[1], d[2], d[3], d[4], d[5]}, e->stream));
+            if (R.kind == Red::sojourn) HIPCHK(launch_sojourn_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, wgs, R.sspec->arrival_bins, R.sspec->arrival_bin_ms, R.sspec->delay_bins, R.sspec->delay_bin_ms, (int)e->opt_sojourn_scheme, SojournOut{d[0], d[1], d[2], d[3]}, e->stream));
+            else if (tl) HIPCHK(launch_timeline_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, wgs, R.tspec->bins, R.tspec->bin_ms, (int)e->opt_timeline_scheme, TimelineOut{d[0], d[1], d[2], d[3], d[4], d[5]}, e->stream));
             else HIPCHK(launch_dist_kernel(reinterpret_cast<const DistJob *>(e->red_jobs_d), njobs, wgs, R.dspec->delay_bins, R.dspec->delay_bin_ms, (int)e->opt_dist_scheme, d[0], d[1], d[2], e->stream));
             HIPCHK(hipEventRecord(e->red_ev1, e->stream));
             red_launched = true;
@@ -1007,6 +1016,11 @@ static int reduction_end(prach_engine *e, CallCtx &cx) {
             if (!cx.host_d.empty())
                 prach_dist_merge(&s, &d, R.out[0] + g * (size_t)s.delay_bins, R.out[1] + g * PRACH_DIST_PTC_BINS, &cx.host_d[g],
                                  cx.host_dh.data() + g * (size_t)s.delay_bins, cx.host_ph.data() + g * PRACH_DIST_PTC_BINS);
+        } else if (R.kind == Red::sojourn) {
+            prach_sojourn &j = R.sj[g];
+            j.trials = cx.trials[g]; j.ues = cx.ues[g]; j.arrived = q[0]; j.success = q[1]; j.restarted = q[2]; j.arrival_overflow = q[3]; j.delay_overflow = q[4];
+            j.sojourn_sum = q[5];
+            j.sojourn_max = (int64_t)q[6] - 1;
         } else {
             prach_timeline &t = R.tl[g];
             t.trials = cx.trials[g]; t.ues = cx.ues[g]; t.arrived = q[0]; t.success = q[1]; t.restarted = q[2]; t.arrival_overflow = q[3]; t.done_overflow = q[4];
@@ -1029,6 +1043,7 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
         for (int q = 0; q + 1 < np; q++) std::memset(red->out[q], 0, 8 * ng * words[q]);
         for (size_t g = 0; g < ng; g++) {
             if (red->kind == Red::dist) { red->dist[g] = prach_dist{}; red->dist[g].delay_max = -1; }
+            else if (red->kind == Red::sojourn) { red->sj[g] = prach_sojourn{}; red->sj[g].sojourn_max = -1; }
             else { red->tl[g] = prach_timeline{}; red->tl[g].done_max = -1; }
         }
     }
@@ -1195,7 +1210,7 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
     if (red) {
         int rc = reduction_end(e, cx);
         if (rc != PRACH_OK) return rc;
-        (red->kind == Red::dist ? e->last.dist_ms : e->last.timeline_ms) = cx.red_ms;
+        (red->kind == Red::dist ? e->last.dist_ms : red->kind == Red::timeline ? e->last.timeline_ms : e->last.sojourn_ms) = cx.red_ms;
     }
     e->last.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return worst;
@@ -1260,6 +1275,7 @@ int prach_engine_set(prach_engine *e, const char *key, int64_t value) {
     if (std::strcmp(key, "batch_waves") == 0) { if (value != 0 && value != 8 && value != 16) return PRACH_ERR_ARG; e->opt_batch_waves = value; return PRACH_OK; }
     if (std::strcmp(key, "dist_scheme") == 0) { if (value < 0 || value > 2) return PRACH_ERR_ARG; e->opt_dist_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "timeline_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_timeline_scheme = value; return PRACH_OK; }
+    if (std::strcmp(key, "sojourn_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_sojourn_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "xcd_pack") == 0) { e->opt_xcd_pack = value != 0; return PRACH_OK; }
     return PRACH_ERR_ARG;
 }
@@ -1345,7 +1361,7 @@ int prach_run_trials_dist(prach_engine *e, const prach_cfg *cfgs, int n, prach_r
     if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
     if ((uint64_t)spec->ngroups * (uint64_t)(spec->delay_bins + PRACH_DIST_PTC_BINS) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
-    const Reduction red{Red::dist, group, spec->ngroups, spec, dist, nullptr, nullptr, {delay_hist, ptc_hist}};
+    const Reduction red{Red::dist, group, spec->ngroups, spec, dist, nullptr, nullptr, nullptr, nullptr, {delay_hist, ptc_hist}};
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
@@ -1360,11 +1376,28 @@ int prach_run_trials_timeline(prach_engine *e, const prach_cfg *cfgs, int n, pra
     for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
     if (5 * (uint64_t)spec->ngroups * (uint64_t)spec->bins > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
-    const Reduction red{Red::timeline, group, spec->ngroups, nullptr, nullptr, spec, tl, {arrivals, success, sojourn_sum, timer_sum, done}};
+    const Reduction red{Red::timeline, group, spec->ngroups, nullptr, nullptr, spec, tl, nullptr, nullptr, {arrivals, success, sojourn_sum, timer_sum, done}};
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
 int prach_timeline_tile_ues(void) { return TL_TILE; }
 int prach_timeline_window_bins(void) { return TL_WINDOW; }
+
+int prach_run_trials_sojourn(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_sojourn_spec *spec,
+                             const int32_t *group, prach_sojourn *sj, uint64_t *hist, uint64_t *row_arrived, uint64_t *row_delay_overflow) {
+    // (spec, groups and variants are judged first: what they ask for does not depend on a device)
+    if (!cfgs || !results || n <= 0 || !spec || !sj || !hist || !row_arrived || !row_delay_overflow) return PRACH_ERR_ARG;
+    if (spec->arrival_bins < 1 || spec->arrival_bins > PRACH_SOJOURN_MAX_ARRIVAL_BINS || spec->arrival_bin_ms < 1 || spec->delay_bins < 1 ||
+        spec->delay_bins > PRACH_SOJOURN_MAX_DELAY_BINS || spec->delay_bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
+    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
+    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
+    if ((uint64_t)spec->ngroups * (uint64_t)spec->arrival_bins * ((uint64_t)spec->delay_bins + 2) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
+    if (!e) return PRACH_ERR_ARG;
+    const Reduction red{Red::sojourn, group, spec->ngroups, nullptr, nullptr, nullptr, nullptr, spec, sj, {hist, row_arrived, row_delay_overflow}};
+    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
+}
+
+int prach_sojourn_tile_ues(void) { return TL_TILE; }
+int prach_sojourn_window_words(void) { return SJ_WINDOW_WORDS; }
 
 } // extern "C"

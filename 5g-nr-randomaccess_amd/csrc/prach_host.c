@@ -738,3 +738,103 @@ size_t prach_timeline_format_csv(const prach_timeline_spec *s, const prach_timel
     }
     return csv_end(buf, cap, off);
 }
+
+/* ---- sojourn histograms by arrival row per trial group (prach_run_trials_sojourn) ---------------- */
+
+static int sojourn_spec_ok(const prach_sojourn_spec *s) {
+    return s && s->arrival_bins >= 1 && s->arrival_bins <= PRACH_SOJOURN_MAX_ARRIVAL_BINS && s->arrival_bin_ms >= 1 && s->delay_bins >= 1 &&
+           s->delay_bins <= PRACH_SOJOURN_MAX_DELAY_BINS && s->delay_bin_ms >= 1;
+}
+
+/* THE DEFINITION (include/prach.h).  Two passes, like the timeline's: the first only judges, so that a refused log leaves nothing behind */
+int prach_sojourn_accumulate_logs(const prach_sojourn_spec *s, const prach_cfg *cfg, const prach_ue_log *ue, int nUE, prach_sojourn *j, uint64_t *hist,
+                                  uint64_t *row_arrived, uint64_t *row_delay_overflow) {
+    if (!sojourn_spec_ok(s) || !cfg || !j || !hist || !row_arrived || !row_delay_overflow || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    if (cfg->variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED;
+    if (prach_cfg_validate(cfg) != PRACH_OK || nUE != cfg->nUE) return PRACH_ERR_ARG;
+    const int nslots = (prach_max_time(cfg) + cfg->accessTime - 1) / cfg->accessTime;
+    int32_t *sched = (int32_t *)malloc(sizeof(int32_t) * (size_t)nslots);
+    if (!sched) return PRACH_ERR_INTERNAL;
+    prach_arrival_schedule(cfg, sched, nslots, NULL);
+    for (int pass = 0; pass < 2; pass++) {
+        if (pass == 1 && j->trials == 0 && j->success == 0) j->sojourn_max = -1; /* (a zero-filled group is an empty one) */
+        int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
+        for (int i = 0; i < nUE; i++) {
+            while (slot < nslots && sched[slot] <= i) slot++;
+            const int64_t a = (int64_t)cfg->accessTime * slot;
+            const int ok = ue[i].msg4Flag == 1;
+            const int64_t c = (int64_t)ue[i].txTime + 6;
+            if (pass == 0) {
+                if (ue[i].active != -1 && ok && (ue[i].timer < 0 || c < a)) { free(sched); return PRACH_ERR_ARG; }
+                continue;
+            }
+            if (ue[i].active == -1) continue; /* not arrived */
+            const int64_t r = a / s->arrival_bin_ms;
+            j->arrived++;
+            if (r < s->arrival_bins) row_arrived[r]++;
+            else j->arrival_overflow++;
+            if (!ok) continue;
+            const int64_t soj = c - a, d = soj / s->delay_bin_ms;
+            j->success++;
+            j->restarted += c - ue[i].timer != a;
+            j->sojourn_sum += (uint64_t)soj;
+            if (soj > j->sojourn_max) j->sojourn_max = soj;
+            if (d >= s->delay_bins) j->delay_overflow++;
+            if (r >= s->arrival_bins) continue;
+            if (d < s->delay_bins) hist[(size_t)r * (size_t)s->delay_bins + (size_t)d]++;
+            else row_delay_overflow[r]++;
+        }
+    }
+    free(sched);
+    j->trials++;
+    j->ues += (uint64_t)nUE;
+    return PRACH_OK;
+}
+
+void prach_sojourn_merge(const prach_sojourn_spec *s, prach_sojourn *into, uint64_t *hist_into, uint64_t *arrived_into, uint64_t *overflow_into,
+                         const prach_sojourn *from, const uint64_t *hist_from, const uint64_t *arrived_from, const uint64_t *overflow_from) {
+    if (!sojourn_spec_ok(s) || !into || !hist_into || !arrived_into || !overflow_into || !from || !hist_from || !arrived_from || !overflow_from) return;
+    const int64_t a = into->success ? into->sojourn_max : -1, b = from->success ? from->sojourn_max : -1;
+    into->trials += from->trials; into->ues += from->ues; into->arrived += from->arrived; into->success += from->success; into->restarted += from->restarted;
+    into->arrival_overflow += from->arrival_overflow; into->delay_overflow += from->delay_overflow; into->sojourn_sum += from->sojourn_sum;
+    into->sojourn_max = a > b ? a : b;
+    const size_t cells = (size_t)s->arrival_bins * (size_t)s->delay_bins;
+    for (size_t i = 0; i < cells; i++) hist_into[i] += hist_from[i];
+    for (int r = 0; r < s->arrival_bins; r++) { arrived_into[r] += arrived_from[r]; overflow_into[r] += overflow_from[r]; }
+}
+
+int64_t prach_sojourn_quantile(const prach_sojourn_spec *s, const uint64_t *hist, const uint64_t *row_delay_overflow, int row, double q) {
+    if (!sojourn_spec_ok(s) || !hist || !row_delay_overflow || row < -1 || row >= s->arrival_bins || !(q >= 0.0) || q > 1.0) return -1;
+    const int r0 = row < 0 ? 0 : row, r1 = row < 0 ? s->arrival_bins : row + 1;
+    uint64_t n = 0;
+    for (int r = r0; r < r1; r++) {
+        n += row_delay_overflow[r];
+        for (int d = 0; d < s->delay_bins; d++) n += hist[(size_t)r * (size_t)s->delay_bins + (size_t)d];
+    }
+    if (n == 0) return -1;
+    uint64_t rank = (uint64_t)ceil(q * (double)n);
+    if (rank < 1) rank = 1;
+    if (rank > n) rank = n;
+    uint64_t cum = 0;
+    for (int d = 0; d < s->delay_bins; d++) {
+        for (int r = r0; r < r1; r++) cum += hist[(size_t)r * (size_t)s->delay_bins + (size_t)d];
+        if (cum >= rank) return (int64_t)d * s->delay_bin_ms;
+    }
+    return -1; /* in the overflow */
+}
+
+size_t prach_sojourn_format_csv(const prach_sojourn_spec *s, const prach_sojourn *j, const uint64_t *hist, const uint64_t *row_arrived,
+                                const uint64_t *row_delay_overflow, const char *label, char *buf, size_t cap) {
+    if (!sojourn_spec_ok(s) || !j || !hist || !row_arrived || !row_delay_overflow || !label) return 0;
+    size_t off = 0;
+    for (int r = 0; r < s->arrival_bins; r++) {
+        const long long edge = (long long)r * s->arrival_bin_ms;
+        const uint64_t *const h = hist + (size_t)r * (size_t)s->delay_bins;
+        if (row_arrived[r]) CSV_EMIT("%.200s,%lld,arrived,%llu\n", label, edge, (unsigned long long)row_arrived[r]);
+        for (int d = 0; d < s->delay_bins; d++)
+            if (h[d]) CSV_EMIT("%.200s,%lld,%lld,%llu\n", label, edge, (long long)d * s->delay_bin_ms, (unsigned long long)h[d]);
+        if (row_delay_overflow[r]) CSV_EMIT("%.200s,%lld,overflow,%llu\n", label, edge, (unsigned long long)row_delay_overflow[r]);
+    }
+    if (j->arrival_overflow) CSV_EMIT("%.200s,arrivals,overflow,%llu\n", label, (unsigned long long)j->arrival_overflow);
+    return csv_end(buf, cap, off);
+}

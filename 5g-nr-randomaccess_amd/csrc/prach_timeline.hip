@@ -14,6 +14,7 @@
 // with the same atomics, and so does everything under SCHEME 0.  The scalars are reduced per wavefront.  Integers only: the result does not
 // depend on any order.  Engine option "timeline_scheme"; DESIGN.md 4 has the measurements.
 #include "prach_device.h"
+#include "prach_slot_search.h"
 
 namespace prach {
 
@@ -23,16 +24,6 @@ constexpr int TL_SCHED_CAP = 2048; // schedule entries of a tile's slot range st
 
 __device__ __forceinline__ void gadd(unsigned long long *p, unsigned long long v) {
     (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the first slot in [lo, hi] whose schedule entry exceeds i; hi itself is never read (it may be the slot count: no slot activates the UE).
-// sched[0] is the entry of slot `base` (a staged range starts at the tile's first slot: an LDS pointer is never moved below its array)
-__device__ __forceinline__ int first_slot_above(const int *sched, int base, int lo, int hi, int i) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (sched[mid - base] > i) hi = mid; else lo = mid + 1;
-    }
-    return lo;
 }
 
 template <int SCHEME>

@@ -110,6 +110,14 @@ def allreduce_timeline(tl, device=None):
     return tl
 
 
+def allreduce_sojourn(sj, device=None):
+    """Merges the sojourn histograms (a `Sojourn` of the package: same groups, bins and widths on every rank) across ranks, in place: ONE int64 sum all-reduce of
+    the concatenated block — the histogram, the two per-row counters and the summed scalars — and sojourn_max by a max all-reduce of ngroups values."""
+    from . import SOJOURN_FIELDS
+    _allreduce_sums_and_max(sj._arrays() + [sj.scalars[f] for f in SOJOURN_FIELDS if f != "sojourn_max"], sj.scalars["sojourn_max"], device)
+    return sj
+
+
 ROW_BYTES = 256  # a row = trial index (8 bytes) + kind (1) + payload length (2) + up to ROW_PAYLOAD bytes of text
 ROW_PAYLOAD = ROW_BYTES - 11  # (Beta.c's six-line Results.txt is ~45 bytes, RandomAccessWithNOMA's eight lines ~115 at nUE = 100 000)
 

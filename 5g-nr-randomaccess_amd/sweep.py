@@ -38,10 +38,16 @@ def main(argv=None):
     ap.add_argument("--timeline", default=None, help="write arrivals, successes, sojourn / timer sums by arrival time and completions by completion time, "
                     "one group per sweep point, to this CSV file (not together with --cdf)")
     ap.add_argument("--timeline-bin", type=int, default=5, help="width of a timeline bin in ms; the bins cover the horizon")
+    ap.add_argument("--sojourn", default=None, help="write the histogram of the time from arrival to Msg4 by arrival row, one group per sweep point, to this CSV "
+                    "file (not together with --cdf or --timeline)")
+    ap.add_argument("--sojourn-arrival-ms", type=int, default=500, help="width of an arrival row in ms; the rows cover the arrivals")
+    ap.add_argument("--sojourn-bin", type=int, default=5, help="width of a delay bin in ms; the bins cover the horizon")
     ap.add_argument("--same-device", action="store_true", help="rehearsal on one GPU: every rank uses cuda:0")
     args = ap.parse_args(argv)
     if args.cdf and args.timeline:
         ap.error("--cdf and --timeline cannot be combined: one reduction per call")
+    if args.sojourn and (args.cdf or args.timeline):
+        ap.error("--sojourn cannot be combined with --cdf or --timeline: one reduction per call")
 
     import torch
     import __graft_entry__ as g
@@ -79,6 +85,9 @@ def main(argv=None):
         red = (pkg.Dist(len(points), args.cdf_bins, args.cdf_bin_ms), eng.run_trials_dist, (args.cdf_bins, args.cdf_bin_ms), distmod.allreduce_dist, pkg.dist_csv, args.cdf)
     elif args.timeline:
         red = (pkg.Timeline(len(points), tl_bins, args.timeline_bin), eng.run_trials_timeline, (tl_bins, args.timeline_bin), distmod.allreduce_timeline, pkg.timeline_csv, args.timeline)
+    elif args.sojourn:
+        sj = (-(-10000 // args.sojourn_arrival_ms), args.sojourn_arrival_ms, -(-(10000 + 6) // args.sojourn_bin), args.sojourn_bin)
+        red = (pkg.Sojourn(len(points), *sj), eng.run_trials_sojourn, sj, distmod.allreduce_sojourn, pkg.sojourn_csv, args.sojourn)
     for a in range(0, len(mine), CH):
         part = mine[a:a + CH]
         if red is None:

@@ -131,6 +131,8 @@ typedef struct prach_timing {
                                     device math library's error band of a rounding / comparison boundary: ~1e-6 of the UEs) */
     double dist_ms;              /* HIP-event time of the distribution kernel launches (prach_run_trials_dist) of the last call; 0 without a spec */
     double timeline_ms;          /* HIP-event time of the timeline kernel launches (prach_run_trials_timeline) of the last call; 0 in every other call */
+    double sojourn_ms;           /* HIP-event time of the sojourn kernel launches (prach_run_trials_sojourn) of the last call; 0 in every other call (a sojourn
+                                    call leaves dist_ms and timeline_ms 0) */
 } prach_timing;
 
 typedef struct prach_engine prach_engine;
@@ -229,6 +231,51 @@ int prach_run_trials_timeline(prach_engine *, const prach_cfg *cfgs, int n, prac
                               const prach_timeline_spec *spec, const int32_t *group, prach_timeline *tl, uint64_t *arrivals, uint64_t *success,
                               uint64_t *sojourn_sum, uint64_t *timer_sum, uint64_t *done);
 
+/* Sojourn distribution by arrival time per trial group, built on the device: the histogram of the time from a UE's arrival to its Msg4 — the access-delay
+ * CDF of TR 37.868, which prach_dist cannot give (its `timer` is the length of the LAST attempt cycle) and prach_timeline gives only as a sum per bin —
+ * by the stretch of the simulation the UE arrived in.  a(i), c(i), ARRIVED, successful and RESTARTED are those of the timeline block above.  For UE i:
+ *   arrival row  r = a(i) / arrival_bin_ms          sojourn  s = c(i) - a(i)          delay bin  d = s / delay_bin_ms
+ *   an arrived UE with r < arrival_bins adds 1 to row_arrived[r], otherwise to arrival_overflow (it is in no row)
+ *   a successful UE with r < arrival_bins adds 1 to hist[r][d] if d < delay_bins, otherwise to row_delay_overflow[r]
+ *   the scalars count every successful UE, whether or not its row is in range
+ * arrival_bins = 1 with arrival_bin_ms >= maxTime is the pooled CDF: the counterpart, for the time since arrival, of the `timer` histogram of prach_dist.
+ * Integers only: device, host, forked workers and ranks merge exactly in any order.  Beta.c and RandomAccessWithNOMA.c only, like the timeline. */
+#define PRACH_SOJOURN_MAX_ARRIVAL_BINS 4096
+#define PRACH_SOJOURN_MAX_DELAY_BINS   16384
+
+typedef struct prach_sojourn_spec {
+    int32_t arrival_bins;    /* 1 .. PRACH_SOJOURN_MAX_ARRIVAL_BINS rows */
+    int32_t arrival_bin_ms;  /* >= 1; row r covers arrivals in [r * arrival_bin_ms, (r + 1) * arrival_bin_ms) */
+    int32_t delay_bins;      /* 1 .. PRACH_SOJOURN_MAX_DELAY_BINS */
+    int32_t delay_bin_ms;    /* >= 1 */
+    int32_t ngroups;         /* number of output histograms */
+    int32_t reserved;        /* 0 */
+} prach_sojourn_spec;
+
+typedef struct prach_sojourn {       /* one per group */
+    uint64_t trials;                 /* trials accumulated (status PRACH_OK) */
+    uint64_t ues;                    /* sum of their nUE */
+    uint64_t arrived;                /* UEs with active != -1 */
+    uint64_t success;                /* UEs with msg4Flag == 1 */
+    uint64_t restarted;              /* successful UEs whose last cycle did not start at their arrival */
+    uint64_t arrival_overflow;       /* arrived UEs with a(i) >= arrival_bins * arrival_bin_ms: in no row */
+    uint64_t delay_overflow;         /* successful UEs, in a row or not, with sojourn >= delay_bins * delay_bin_ms */
+    uint64_t sojourn_sum;            /* over all successful UEs, unbinned */
+    int64_t  sojourn_max;            /* the largest sojourn; -1 if success == 0 */
+} prach_sojourn;
+
+/* prach_run_trials plus the sojourn histograms, with the contract of prach_run_trials_timeline: trial k is added to group group[k] (group == NULL: trial k is
+ * group k and ngroups must equal n); sj[ngroups], hist[ngroups][arrival_bins][delay_bins], row_arrived[ngroups][arrival_bins] and
+ * row_delay_overflow[ngroups][arrival_bins] are caller-owned and OVERWRITTEN; a trial whose final status is not PRACH_OK contributes nothing; a trial the
+ * engine reruns contributes once, from the launch whose result is kept.  prach::sojourn_kernel (csrc/prach_sojourn.hip) reduces the per-UE log records the
+ * simulation kernels write ON THE DEVICE: the engine lays them out for every trial of such a call and copies out only the ones the caller asked for, so
+ * the arena of the call grows by 64 bytes per UE.
+ * PRACH_ERR_ARG: a NULL output, a bin count or width out of range, a group id out of range, NULL group with ngroups != n;
+ * PRACH_ERR_UNSUPPORTED: any NOMA_C cfg (before anything is launched); ngroups * arrival_bins * (delay_bins + 2) > 2^27 words (1 GiB of device buffer). */
+int prach_run_trials_sojourn(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs,
+                             const prach_sojourn_spec *spec, const int32_t *group, prach_sojourn *sj, uint64_t *hist, uint64_t *row_arrived,
+                             uint64_t *row_delay_overflow);
+
 /* engine tunables; none changes a result, all are covered by parity tests:
  *   "cluster"       workgroups cooperating on one trial (1..64; 0 = auto)
  *   "stream_factor" glibc mode: initial draws-per-UE budget of the rand() stream window (0 = auto; it grows on demand)
@@ -249,6 +296,8 @@ int prach_run_trials_timeline(prach_engine *, const prach_cfg *cfgs, int n, prac
  *                   (the default: measured fastest), 2 one LDS atomic per distinct value of a wavefront (match and aggregate)
  *   "timeline_scheme" prach::timeline_kernel's binning: 0 every contribution is a 64-bit global atomic, 1 windows of bins privatised in LDS per workgroup
  *                   (the default: measured 15-20x faster on the sweep grids)
+ *   "sojourn_scheme" prach::sojourn_kernel's binning: 0 every contribution is a 64-bit agent-scope global atomic, 1 rows of the histogram privatised in LDS
+ *                   per workgroup (the default: measured 95x faster on the sweep grids)
  *   "calendar_cap", "vmm_fail_after", "noma_ambiguity_test", "noma_host_activation"   test hooks (prach_engine.hip) */
 int prach_engine_set(prach_engine *, const char *key, int64_t value);
 
@@ -325,6 +374,27 @@ void prach_timeline_merge(const prach_timeline_spec *, prach_timeline *into, uin
 size_t prach_timeline_format_csv(const prach_timeline_spec *, const prach_timeline *, const uint64_t *const series[5], const char *label, char *buf, size_t cap);
 int prach_timeline_tile_ues(void);    /* UEs of one trial that one workgroup of prach::timeline_kernel reduces (tests place sizes around it) */
 int prach_timeline_window_bins(void); /* bins of the LDS windows of prach::timeline_kernel (timeline_scheme 1), anchored at a tile's first arrival bin */
+
+/* Sojourn histograms, host side (no device needed).  j, hist [arrival_bins][delay_bins], row_arrived and row_delay_overflow [arrival_bins]: ONE group.
+ * prach_sojourn_accumulate_logs ADDS one trial's per-UE log to a group: THE DEFINITION prach::sojourn_kernel equals, integer for integer.  Errors as
+ * prach_timeline_accumulate_logs: PRACH_ERR_UNSUPPORTED: a NOMA_C cfg.  PRACH_ERR_ARG: a bad spec or cfg, nUE != cfg->nUE, or a successful UE with a negative
+ * timer or with c(i) < a(i) (nothing has been added then). */
+int prach_sojourn_accumulate_logs(const prach_sojourn_spec *, const prach_cfg *cfg, const prach_ue_log *ue, int nUE, prach_sojourn *j, uint64_t *hist,
+                                  uint64_t *row_arrived, uint64_t *row_delay_overflow);
+/* counts and sums are added, sojourn_max is the maximum */
+void prach_sojourn_merge(const prach_sojourn_spec *, prach_sojourn *into, uint64_t *hist_into, uint64_t *arrived_into, uint64_t *overflow_into,
+                         const prach_sojourn *from, const uint64_t *hist_from, const uint64_t *arrived_from, const uint64_t *overflow_from);
+/* the rule of prach_dist_delay_quantile on one arrival row, or pooled over all rows (row == -1): the lower edge (ms) of the first delay bin whose cumulative
+ * count reaches max(1, ceil(q * n)), n = the row's successful UEs including its overflow; -1 if n == 0, that rank lies in the overflow, or an argument is bad */
+int64_t prach_sojourn_quantile(const prach_sojourn_spec *, const uint64_t *hist, const uint64_t *row_delay_overflow, int row, double q);
+/* one group as text, row by row: `label,<row lower edge ms>,arrived,<count>` where the row has arrivals, `label,<row lower edge ms>,<delay lower edge ms>,<count>`
+ * per non-zero cell, `label,<row lower edge ms>,overflow,<count>` where the row's overflow is non-zero; behind the rows `label,arrivals,overflow,<count>` where
+ * arrival_overflow is non-zero; lines end in \n.  Returns the length needed (without the terminating 0); the text is written only if it fits cap with its
+ * terminator. */
+size_t prach_sojourn_format_csv(const prach_sojourn_spec *, const prach_sojourn *, const uint64_t *hist, const uint64_t *row_arrived,
+                                const uint64_t *row_delay_overflow, const char *label, char *buf, size_t cap);
+int prach_sojourn_tile_ues(void);     /* UEs of one trial that one workgroup of prach::sojourn_kernel reduces (tests place sizes around it) */
+int prach_sojourn_window_words(void); /* 32-bit cells of the LDS window of prach::sojourn_kernel (sojourn_scheme 1): it holds window_words / delay_bins rows */
 
 /* Text surfaces, byte-compatible with the reference (latency values excepted) */
 size_t prach_format_logs(const prach_ue_log *ue, int nUE, char *buf, size_t cap);           /* Beta.c:501 */
