@@ -54,7 +54,7 @@ class PrachTiming(C.Structure):
                 ("launches", C.c_int32), ("workgroups", C.c_int32), ("updates", C.c_uint64),
                 ("cluster_size", C.c_int32), ("resident_limit", C.c_int32), ("fallback_trials", C.c_int32), ("spin_timeouts", C.c_int32),
                 ("rec_mode", C.c_int32), ("xcd_packed", C.c_int32), ("group_visits", C.c_uint64), ("event_ues", C.c_uint64),
-                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
+                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
                 ("sojourn_ms", C.c_double)]
 
 
@@ -216,6 +216,76 @@ class Sojourn(_Reduction):
         return int(lib().prach_sojourn_quantile(C.byref(sp), h, o, int(row), float(q)))
 
 
+SUMMARY_MAX_Q = 8
+SUMMARY_QUANTITIES = ("sojourn", "timer", "ptx")
+SUMMARY_FIXED_METRICS = ("success_ratio", "restart_ratio", "sojourn_mean", "timer_mean", "ptx_mean")
+
+
+class PrachSummarySpec(C.Structure):
+    _fields_ = [("nq", C.c_int32), ("permille", C.c_int32 * SUMMARY_MAX_Q), ("reserved", C.c_int32 * 3)]
+
+
+class PrachTrialSummary(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("status", "nUE", "arrived", "success", "restarted", "range_errors")] + \
+               [(n, C.c_int64) for n in ("sojourn_sum", "timer_sum", "ptc_sum")] + [(n, C.c_int32) for n in ("sojourn_max", "timer_max", "ptc_max")] + \
+               [("q", (C.c_int32 * SUMMARY_MAX_Q) * 3)]
+
+
+class PrachStat(C.Structure):
+    _fields_ = [("n", C.c_uint64)] + [(n, C.c_double) for n in ("mean", "sd", "sem", "min", "max")]
+
+
+def summary_row_dtype():
+    """prach_trial_summary as a numpy structured dtype (the C layout: 160 bytes, twenty 64-bit words)."""
+    import numpy as np
+    dt = np.dtype([(n, np.int32) for n in ("status", "nUE", "arrived", "success", "restarted", "range_errors")] +
+                  [(n, np.int64) for n in ("sojourn_sum", "timer_sum", "ptc_sum")] + [(n, np.int32) for n in ("sojourn_max", "timer_max", "ptc_max")] +
+                  [("q", np.int32, (3, SUMMARY_MAX_Q))], align=True)
+    assert dt.itemsize == C.sizeof(PrachTrialSummary)
+    return dt
+
+
+def summary_stat_dtype():
+    import numpy as np
+    return np.dtype([("n", np.uint64)] + [(n, np.float64) for n in ("mean", "sd", "sem", "min", "max")])
+
+
+class Summary:
+    """One row per trial (include/prach.h, prach_trial_summary): ``rows`` is a numpy structured array (summary_row_dtype) in trial order, ``permille`` the
+    levels of its q[quantity][level] columns."""
+
+    def __init__(self, n, permille=(500, 950, 990)):
+        import numpy as np
+        self.permille = tuple(int(m) for m in permille)
+        self.rows = np.zeros(int(n), dtype=summary_row_dtype())
+
+    def spec(self):
+        sp = PrachSummarySpec()
+        sp.nq = len(self.permille)  # (a count the library refuses stays visible to it)
+        for l, m in enumerate(self.permille[:SUMMARY_MAX_Q]):
+            sp.permille[l] = m
+        return sp
+
+    def metric_names(self):
+        return list(SUMMARY_FIXED_METRICS) + [f"{x}_p{m}" for x in SUMMARY_QUANTITIES for m in self.permille]
+
+    def _rows_ptr(self):
+        return self.rows.ctypes.data_as(C.POINTER(PrachTrialSummary))
+
+    def stats(self, groups=None, ngroups=None):
+        """Mean and spread per trial group (prach_summary_stats): a structured array [ngroups, 5 + 3 nq] of n, mean, sd, sem, min, max, the metrics in the
+        order of metric_names().  groups: the group of every row (None: all rows are one group)."""
+        import numpy as np
+        ng = 1 if groups is None and ngroups is None else _ngroups(len(self.rows), groups, ngroups)
+        out = np.zeros((ng, len(SUMMARY_FIXED_METRICS) + 3 * len(self.permille)), dtype=summary_stat_dtype())
+        sp = self.spec()
+        gp = None if groups is None else (C.c_int32 * len(self.rows))(*[int(g) for g in groups])
+        rc = lib().prach_summary_stats(C.byref(sp), self._rows_ptr(), len(self.rows), gp, ng, out.ctypes.data_as(C.POINTER(PrachStat)))
+        if rc != OK:
+            raise PrachError(rc, "(prach_summary_stats)")
+        return out
+
+
 class PrachError(RuntimeError):
     def __init__(self, status, what=""):
         self.status = status
@@ -278,6 +348,13 @@ def lib():
         L.prach_sojourn_format_csv.restype = C.c_size_t
         L.prach_sojourn_tile_ues.argtypes = []
         L.prach_sojourn_window_words.argtypes = []
+        L.prach_run_trials_summary.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachSummarySpec),
+                                               C.POINTER(PrachTrialSummary)]
+        L.prach_summary_from_logs.argtypes = [C.POINTER(PrachSummarySpec), C.POINTER(PrachCfg), C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachTrialSummary)]
+        L.prach_summary_stats.argtypes = [C.POINTER(PrachSummarySpec), C.POINTER(PrachTrialSummary), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(PrachStat)]
+        L.prach_summary_format_csv.argtypes = [C.POINTER(PrachSummarySpec), C.POINTER(PrachStat), C.c_char_p, C.c_char_p, C.c_size_t]
+        L.prach_summary_format_csv.restype = C.c_size_t
+        L.prach_summary_max_value.argtypes = []
         L.prach_cfg_defaults.argtypes = [C.POINTER(PrachCfg), C.c_int]
         L.prach_cfg_defaults.restype = None
         L.prach_cfg_validate.argtypes = [C.POINTER(PrachCfg)]
@@ -318,7 +395,8 @@ EXPORTS = ("prach_engine_create", "prach_engine_destroy", "prach_engine_set", "p
            "prach_noma_activation_table_device", "prach_run_trials_dist", "prach_dist_accumulate_logs", "prach_dist_merge", "prach_dist_delay_quantile",
            "prach_dist_format_csv", "prach_dist_tile_ues", "prach_run_trials_timeline", "prach_timeline_accumulate_logs", "prach_timeline_merge",
            "prach_timeline_format_csv", "prach_timeline_tile_ues", "prach_timeline_window_bins", "prach_run_trials_sojourn", "prach_sojourn_accumulate_logs",
-           "prach_sojourn_merge", "prach_sojourn_quantile", "prach_sojourn_format_csv", "prach_sojourn_tile_ues", "prach_sojourn_window_words")
+           "prach_sojourn_merge", "prach_sojourn_quantile", "prach_sojourn_format_csv", "prach_sojourn_tile_ues", "prach_sojourn_window_words",
+           "prach_run_trials_summary", "prach_summary_from_logs", "prach_summary_stats", "prach_summary_format_csv", "prach_summary_max_value")
 
 
 def make_cfg(nUE, variant=VARIANT_BETA_C, uniform=0, rng_mode=RNG_GLIBC, seed=0, stream_offset=0, **kw) -> PrachCfg:
@@ -403,6 +481,15 @@ class Engine:
         run_trials_dist.  Returns (results, logs, Sojourn)."""
         return self._call_reduced("prach_run_trials_sojourn", cfgs,
                                   Sojourn(_ngroups(len(cfgs), groups, ngroups), arrival_bins, arrival_bin_ms, delay_bins, delay_bin_ms), groups, want_logs)
+
+    def run_trials_summary(self, cfgs, permille=(500, 950, 990), want_logs=False):
+        """run_trials plus one summary row per trial — counts, sums, maxima and exact order statistics (levels in permille) of the sojourn, of `timer` and of
+        the preamble transmissions over the trial's successful UEs — selected on the device (prach_run_trials_summary; Beta.c and RandomAccessWithNOMA
+        trials only).  Returns (results, logs, Summary); Summary.stats() gives mean and spread across the trials."""
+        sm = Summary(len(cfgs), permille)
+        sp = sm.spec()
+        res, logs = self._call("prach_run_trials_summary", cfgs, want_logs, C.byref(sp), sm._rows_ptr())
+        return res, logs, sm
 
     @staticmethod
     def _log_buffers(cfgs, want_logs):
@@ -613,3 +700,36 @@ def sojourn_from_logs(cfgs, logs, arrival_bins, arrival_bin_ms, delay_bins, dela
 def sojourn_csv(sj: Sojourn, labels=None) -> bytes:
     """The CSV text of every group (prach_sojourn_format_csv), labelled labels[g] (default: the group number)."""
     return _csv("prach_sojourn_format_csv", sj, labels)
+
+
+def summary_max_value() -> int:
+    return lib().prach_summary_max_value()
+
+
+def summary_from_logs(cfgs, logs, permille=(500, 950, 990)) -> Summary:
+    """The host-side definition of the per-trial summary (prach_summary_from_logs): row k from logs[k], the per-UE log of the trial with config cfgs[k] — a
+    ctypes array of PrachUeLog or an int32 array of shape [nUE, 16]."""
+    sm = Summary(len(logs), permille)
+    sp = sm.spec()
+    rows = sm._rows_ptr()
+    for k, lg in enumerate(logs):
+        ptr, nue, _keep = _log_ptr(lg)
+        rc = lib().prach_summary_from_logs(C.byref(sp), C.byref(cfgs[k]), ptr, nue, C.byref(rows[k]))
+        if rc != OK:
+            raise PrachError(rc, "(prach_summary_from_logs)")
+    return sm
+
+
+def summary_csv(sm: Summary, groups=None, ngroups=None, labels=None) -> bytes:
+    """The CSV text of the statistics of every group of trials (prach_summary_stats, prach_summary_format_csv), labelled labels[g] (default: the group
+    number): `label,metric,n,mean,sd,sem,min,max`."""
+    st = sm.stats(groups, ngroups)
+    sp = sm.spec()
+    out = b""
+    for g in range(st.shape[0]):
+        args = (C.byref(sp), st[g].ctypes.data_as(C.POINTER(PrachStat)), str(g if labels is None else labels[g]).encode())
+        need = lib().prach_summary_format_csv(*args, None, 0)
+        buf = C.create_string_buffer(need + 1)
+        n = lib().prach_summary_format_csv(*args, buf, need + 1)
+        out += buf.raw[:n]
+    return out

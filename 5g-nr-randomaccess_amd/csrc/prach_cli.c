@@ -26,6 +26,10 @@
  * --sojourn FILE [--sojourn-arrival-ms MS] [--sojourn-bin MS]: the histogram of the time from arrival to Msg4 by arrival row (prach_run_trials_sojourn: reduced
  * on the device, so it works with --logs 0), one group per sweep point with the --times seeds merged, labelled nUE; rows of MS ms (default 500) over maxTime,
  * delay bins of MS ms (default 5) over maxTime + 6 ms; --program beta|withnoma only, and not together with --cdf or --timeline;
+ * --ci FILE [--ci-levels M1,M2,...]: mean, standard deviation, standard error, minimum and maximum ACROSS THE --times SEEDS of every sweep point (labelled nUE)
+ * of the success and restart ratio, the mean sojourn / timer / preamble transmissions and their exact per-trial percentiles at the given levels in permille
+ * (default 500,950,990; at most 8): one row per trial comes from the device (prach_run_trials_summary, so it works with --logs 0), the statistics are
+ * prach_summary_stats over the rows in trial order; --program beta|withnoma only, and not together with --cdf, --timeline or --sojourn;
  * --devices LIST: the same with explicit HIP ordinals (an ordinal may repeat);
  * --gpus N: the --times x sweep grid sharded over N devices of the node by host C — one forked child per device,
  * forked BEFORE any HIP call, trials dealt by descending cost (Philox: any trial anywhere; glibc: whole seeds, because
@@ -103,6 +107,9 @@ typedef struct reduction {
     const prach_sojourn_spec *sj;
     const char *path; /* the CSV file */
     size_t text_cap;  /* the CSV text of one group at most */
+    /* --ci (prach_run_trials_summary) is no block of groups: one row per trial of the grid, in a shared mapping like the results; the parent computes the statistics */
+    const prach_summary_spec *sm;
+    prach_trial_summary *sm_rows;
 } reduction;
 static int red_on(const reduction *r) { return r->cdf || r->tl || r->sj; }
 static size_t sj_cells(const prach_sojourn_spec *s) { return (size_t)s->arrival_bins * (size_t)s->delay_bins; }
@@ -154,7 +161,8 @@ static size_t red_format_group(const reduction *r, char *b, int g, const char *l
 
 /* one call into the library with the run's reduction: its groups (group = sweep point, grp[k]) come back in call_block and are merged into the worker's block */
 static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *r, prach_ue_log *const *logs, const reduction *red, const int32_t *grp,
-                    char *call_block, char *worker_block) {
+                    char *call_block, char *worker_block, prach_trial_summary *sm_rows) {
+    if (red->sm) return prach_run_trials_summary(eng, c, n, r, logs, red->sm, sm_rows);
     if (!red_on(red)) return prach_run_trials(eng, c, n, r, logs);
     char *const b = call_block;
     const int rc = red->tl ? prach_run_trials_timeline(eng, c, n, r, logs, red->tl, grp, (prach_timeline *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0),
@@ -185,6 +193,8 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
     int32_t *grp = reduces ? (int32_t *)malloc(sizeof(int32_t) * (size_t)(m > 0 ? m : 1)) : NULL;
     char *call_block = reduces ? (char *)malloc(red_block_bytes(red)) : NULL;
     if (reduces && (!grp || !call_block)) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+    prach_trial_summary *sr = red->sm ? (prach_trial_summary *)malloc(sizeof(prach_trial_summary) * (size_t)(m > 0 ? m : 1)) : NULL;
+    if (red->sm && !sr) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
     if (!glibc) {
         for (int a = 0; a < m; a += CH) {
             const int n = m - a < CH ? m - a : CH;
@@ -196,11 +206,12 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
                     if (!logs[k]) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
                 }
             }
-            rc = run_call(eng, c, n, r, logs, red, grp, call_block, worker_block);
+            rc = run_call(eng, c, n, r, logs, red, grp, call_block, worker_block, sr);
             if (rc != PRACH_OK) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(rc)); return 2; }
             const double lat = now_s() - t0;
             for (int k = 0; k < n; k++) {
                 res[idx[a + k]] = r[k];
+                if (red->sm) red->sm_rows[idx[a + k]] = sr[k];
                 lat_out[idx[a + k]] = lat;
                 if (cfgs[idx[a + k]].variant != PRACH_VARIANT_NOMA_C) {
                     rc = prach_write_trial_files(&c[k], &r[k], want_logs ? logs[k] : NULL, lat, outdir);
@@ -223,12 +234,13 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
                     if (!logs[s_]) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
                 }
             }
-            rc = run_call(eng, c, nseeds, r, logs, red, grp, call_block, worker_block);
+            rc = run_call(eng, c, nseeds, r, logs, red, grp, call_block, worker_block, sr);
             if (rc != PRACH_OK) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(rc)); return 2; }
             const double lat = now_s() - t0;
             for (int s_ = 0; s_ < nseeds; s_++) {
                 offset[s_] += r[s_].draws;
                 res[idx[s_ * npts + k]] = r[s_];
+                if (red->sm) red->sm_rows[idx[s_ * npts + k]] = sr[s_];
                 lat_out[idx[s_ * npts + k]] = lat;
                 if (c[s_].variant != PRACH_VARIANT_NOMA_C) { /* (NOMA.c's lines are printed and appended by the parent) */
                     rc = prach_write_trial_files(&c[s_], &r[s_], want_logs ? logs[s_] : NULL, lat, outdir);
@@ -239,7 +251,7 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
         }
         free(offset);
     }
-    free(c); free(r); free(logs); free(grp); free(call_block);
+    free(c); free(r); free(logs); free(grp); free(call_block); free(sr);
     prach_engine_destroy(eng);
     return 0;
 }
@@ -247,7 +259,8 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
 int main(int argc, char *argv[]) {
     int randomMax = 1, variant = PRACH_VARIANT_WITHNOMA_C, rng = PRACH_RNG_GLIBC, device = 0, want_logs = 1, gpus = 1, rng_given = 0;
     int sweep_lo = 10000, sweep_hi = 100000, sweep_step = 10000; /* WithNOMA:221 */
-    const char *outdir = ".", *csv_path = NULL, *devlist = NULL, *cdf_path = NULL, *tl_path = NULL, *sj_path = NULL;
+    const char *outdir = ".", *csv_path = NULL, *devlist = NULL, *cdf_path = NULL, *tl_path = NULL, *sj_path = NULL, *ci_path = NULL;
+    prach_summary_spec ci_spec = {3, {500, 950, 990, 0, 0, 0, 0, 0}, {0, 0, 0}};
     int cdf_bins = 4096, cdf_bin_ms = 1, tl_bin_ms = 5, sj_row_ms = 500, sj_bin_ms = 5;
     int devs[64];
     /* --program must be known before the defaults are laid down */
@@ -344,11 +357,25 @@ int main(int argc, char *argv[]) {
         } else if (strcmp(a, "--sojourn-bin") == 0) {
             if (atoi(v) < 1) die("--sojourn-bin MS: the width of a delay bin in ms, at least 1");
             sj_bin_ms = atoi(v);
+        } else if (strcmp(a, "--ci") == 0) {
+            ci_path = v;
+        } else if (strcmp(a, "--ci-levels") == 0) {
+            ci_spec.nq = 0;
+            for (const char *q = v; *q;) {
+                const int m_ = atoi(q);
+                if (ci_spec.nq >= PRACH_SUMMARY_MAX_Q || m_ < 1 || m_ > 1000) die("--ci-levels LIST: 1 to 8 comma-separated levels in permille, 1 to 1000 each");
+                ci_spec.permille[ci_spec.nq++] = m_;
+                while (*q && *q != ',') q++;
+                if (*q == ',') q++;
+            }
+            if (ci_spec.nq < 1) die("--ci-levels LIST: 1 to 8 comma-separated levels in permille, 1 to 1000 each");
         } else {
             usage_and_exit();
         }
     }
     base.rng_mode = rng;
+    if (ci_path && variant == PRACH_VARIANT_NOMA_C) die("--ci needs --program beta or withnoma (NOMA.c logs no trace of a UE's cycle start)");
+    if (ci_path && (sj_path || tl_path || cdf_path)) die("--ci cannot be combined with --cdf, --timeline or --sojourn: one reduction per call");
     if (sj_path && variant == PRACH_VARIANT_NOMA_C) die("--sojourn needs --program beta or withnoma (NOMA.c logs no trace of a UE's cycle start)");
     if (sj_path && (tl_path || cdf_path)) die("--sojourn cannot be combined with --cdf or --timeline: one reduction per call");
     if (tl_path && variant == PRACH_VARIANT_NOMA_C) die("--timeline needs --program beta or withnoma (NOMA.c logs no trace of a UE's cycle start)");
@@ -434,8 +461,15 @@ int main(int argc, char *argv[]) {
      * three numbers, per cell and twice per row */
     const reduction red_ = {cdf_path ? &cdf_spec : NULL, tl_path ? &tl_spec : NULL, sj_path ? &sj_spec : NULL, sj_path ? sj_path : tl_path ? tl_path : cdf_path,
                             sj_path ? 64 * ((size_t)sj_rows * ((size_t)sj_bins + 2) + 1) + 1
-                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1};
-    const reduction *const red = &red_;
+                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1, NULL, NULL};
+    reduction red_ci = red_;
+    if (ci_path) { /* --ci: the rows of the whole grid, filled by the workers */
+        red_ci.sm = &ci_spec;
+        red_ci.sm_rows = (prach_trial_summary *)mmap(NULL, sizeof(prach_trial_summary) * (size_t)ntr, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
+        if (red_ci.sm_rows == MAP_FAILED) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+        for (int q = 0; q < ntr; q++) red_ci.sm_rows[q].status = PRACH_ERR_INTERNAL; /* (a row no worker wrote counts nowhere) */
+    }
+    const reduction *const red = &red_ci;
     char *red_blocks = NULL;
     if (red_on(red)) {
         red_blocks = (char *)mmap(NULL, red_block_bytes(red) * (size_t)gpus, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0); /* (zero-filled) */
@@ -483,6 +517,28 @@ int main(int argc, char *argv[]) {
         }
         free(out);
         fclose(fp);
+    }
+
+    if (ci_path) { /* statistics over the seeds of every sweep point, from the rows in trial order: the same whatever the number of workers */
+        const int nm = 5 + 3 * ci_spec.nq;
+        int32_t *grp = (int32_t *)malloc(sizeof(int32_t) * (size_t)ntr);
+        prach_stat *st = (prach_stat *)malloc(sizeof(prach_stat) * (size_t)npts * (size_t)nm);
+        if (!grp || !st) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+        for (int q = 0; q < ntr; q++) grp[q] = q % npts;
+        const int rcs = prach_summary_stats(&ci_spec, red->sm_rows, ntr, grp, npts, st);
+        if (rcs != PRACH_OK) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(rcs)); return 2; }
+        FILE *fp = fopen(ci_path, "wb");
+        if (!fp) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_IO)); return 2; }
+        char out[8192]; /* 29 lines at most: a label of at most 10 digits, a name of at most 14 characters, seven numbers of at most 16 */
+        for (int k = 0; k < npts; k++) {
+            char label[16];
+            snprintf(label, sizeof label, "%d", sweep_lo + k * sweep_step);
+            const size_t n = prach_summary_format_csv(&ci_spec, st + (size_t)k * (size_t)nm, label, out, sizeof out);
+            if (n >= sizeof out) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_INTERNAL)); return 2; }
+            fwrite(out, 1, n, fp);
+        }
+        fclose(fp);
+        free(grp); free(st);
     }
 
     /* the parent prints in the reference's order and merges */

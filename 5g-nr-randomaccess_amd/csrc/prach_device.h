@@ -210,4 +210,14 @@ struct SojournOut { unsigned long long *hist, *row_arrived, *row_overflow, *scal
 hipError_t launch_sojourn_kernel(const TimelineJob *jobs, int njobs, int workgroups, int rows, int row_ms, int delay_bins, int delay_bin_ms, int scheme, SojournOut out,
                                  hipStream_t stream);
 
+// prach_summary.hip: one summary row per accepted trial of a launch (prach_run_trials_summary).  The jobs are the timeline's (TimelineJob: log records and
+// schedule of one trial; group = the row), ONE workgroup per trial.  A row is SM_WORDS 64-bit words, written with plain stores: arrived, success, restarted,
+// 3 range-error counts [sojourn, timer, preambleTxCounter], 3 sums, 3 maxima (-1: no successful UE), then [3][PRACH_SUMMARY_MAX_Q] levels (-1: not found or unused).
+constexpr int SM_WORDS = 12 + 3 * PRACH_SUMMARY_MAX_Q;
+constexpr int SM_MAX_VALUE = 65535; // the largest value the two-level selection ranks (prach_summary_max_value)
+struct SummaryLevels { int nq; int permille[PRACH_SUMMARY_MAX_Q]; };
+// threads: 512 or 1024; sched_cap: schedule entries staged in LDS (the longest schedule of the jobs, cut to summary_sched_cap())
+int summary_sched_cap();
+hipError_t launch_summary_kernel(const TimelineJob *jobs, int njobs, SummaryLevels levels, int threads, int sched_cap, unsigned long long *rows, hipStream_t stream);
+
 } // namespace prach

@@ -50,6 +50,7 @@ struct prach_engine {
     char *red_jobs_h = nullptr, *red_jobs_d = nullptr;
     size_t red_jobs_cap = 0;
     hipEvent_t red_ev0 = nullptr, red_ev1 = nullptr;
+    int64_t opt_summary_threads = 1024; // summary_kernel's workgroup (prach_summary.hip): 512 or 1024 threads, one workgroup per trial
     int64_t opt_sojourn_scheme = 1;  // sojourn_kernel's binning (prach_sojourn.hip): 0 global atomics only, 1 rows of the histogram privatised in LDS
     int64_t opt_timeline_scheme = 1; // timeline_kernel's binning (prach_timeline.hip): 0 global atomics only, 1 windows of bins privatised in LDS (measured faster: DESIGN.md 4)
     int64_t opt_dist_scheme = 1;   // dist_kernel's binning of the preamble counts (prach_dist.hip): 0 plain LDS adds, 1 per-wavefront copies (measured fastest), 2 match and aggregate
@@ -416,8 +417,9 @@ static int noma_device_activation(prach_engine *e, const TrialDev *dparams, cons
 // What a call reduces on the device next to its results: the caller's spec, groups and outputs of prach_run_trials_dist, prach_run_trials_timeline or
 // prach_run_trials_sojourn.  The call's device buffer is a row of parts, [ngroups][words] 64-bit counters each: the arrays the caller gets as they are (dist:
 // delay_hist, ptc_hist; timeline: the five series arrivals, success, sojourn_sum, timer_sum, done; sojourn: hist, row_arrived, row_delay_overflow), then the
-// scalars the kernel keeps per group.
-enum class Red { dist, timeline, sojourn };
+// scalars the kernel keeps per group.  prach_run_trials_summary is the fourth kind: every trial is its own group and the only part is the kernel's row of
+// SM_WORDS words per trial, unpacked into the caller's prach_trial_summary rows.
+enum class Red { dist, timeline, sojourn, summary };
 constexpr int RED_MAX_PARTS = 6;
 struct Reduction {
     Red kind;
@@ -430,9 +432,12 @@ struct Reduction {
     const prach_sojourn_spec *sspec; // sojourn
     prach_sojourn *sj;
     uint64_t *out[RED_MAX_PARTS - 1]; // the caller's arrays, one per part in front of the scalars
+    const prach_summary_spec *mspec;  // summary
+    prach_trial_summary *rows;
 };
 // words per group of every part; returns their number
 static int red_parts(const Reduction &r, size_t words[RED_MAX_PARTS]) {
+    if (r.kind == Red::summary) { words[0] = SM_WORDS; return 1; }
     if (r.kind == Red::dist) { words[0] = (size_t)r.dspec->delay_bins; words[1] = PRACH_DIST_PTC_BINS; words[2] = DIST_SCALARS; return 3; }
     if (r.kind == Red::sojourn) {
         words[0] = (size_t)r.sspec->arrival_bins * (size_t)r.sspec->delay_bins; words[1] = words[2] = (size_t)r.sspec->arrival_bins; words[3] = SJ_SCALARS;
@@ -442,7 +447,7 @@ static int red_parts(const Reduction &r, size_t words[RED_MAX_PARTS]) {
     words[5] = TL_SCALARS;
     return 6;
 }
-static size_t red_job_bytes(Red kind) { return kind == Red::dist ? sizeof(DistJob) : sizeof(TimelineJob); } // (sojourn takes the timeline's jobs)
+static size_t red_job_bytes(Red kind) { return kind == Red::dist ? sizeof(DistJob) : sizeof(TimelineJob); } // (sojourn and summary take the timeline's jobs)
 
 // What one prach_run_trials call carries from launch to launch
 struct CallCtx {
@@ -763,8 +768,8 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
     bool red_launched = false;
     if (cx.red) {
         const Reduction &R = *cx.red;
-        const bool tl = R.kind != Red::dist; // (the jobs and the tile of the timeline are the sojourn's too)
-        int njobs = 0, wgs = 0;
+        const bool tl = R.kind != Red::dist; // (the jobs and the tile of the timeline are the sojourn's too; the summary takes the jobs, and one workgroup per job)
+        int njobs = 0, wgs = 0, max_slots = 0;
         for (int k = 0; k < m; k++) {
             const DevResult &dr = drs[k];
             if (dr.status != PRACH_OK || (noma && dr.hard_error == NOMA_AMBIGUOUS)) continue;
@@ -773,6 +778,7 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
             const int g = cx.group_of(idx[k]);
             if (tl) {
                 const int nslots = (prach_max_time(&c) + c.accessTime - 1) / c.accessTime; // (what prach_arrival_schedule fills; the table has one entry more)
+                max_slots = std::max(max_slots, nslots);
                 reinterpret_cast<TimelineJob *>(e->red_jobs_h)[njobs++] = TimelineJob{reinterpret_cast<const int4 *>(A + L.logs), reinterpret_cast<const int *>(A + L.sched), c.nUE, g, wgs, c.accessTime, nslots, 0};
             } else
                 reinterpret_cast<DistJob *>(e->red_jobs_h)[njobs++] = DistJob{reinterpret_cast<const int *>(A + L.timers), reinterpret_cast<const int *>(A + (batch ? L.rec32 : L.ptc)), c.nUE, g, wgs, batch ? 1 : 0};
@@ -785,7 +791,12 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
             unsigned long long *const *const d = cx.d_part;
             HIPCHK(hipMemcpyAsync(e->red_jobs_d, e->red_jobs_h, red_job_bytes(R.kind) * (size_t)njobs, hipMemcpyHostToDevice, e->stream));
             HIPCHK(hipEventRecord(e->red_ev0, e->stream));
-            if (R.kind == Red::sojourn) HIPCHK(launch_sojourn_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, wgs, R.sspec->arrival_bins, R.sspec->arrival_bin_ms, R.sspec->delay_bins, R.sspec->delay_bin_ms, (int)e->opt_sojourn_scheme, SojournOut{d[0], d[1], d[2], d[3]}, e->stream));
+            if (R.kind == Red::summary) {
+                SummaryLevels lv{};
+                lv.nq = R.mspec->nq;
+                for (int l = 0; l < lv.nq; l++) lv.permille[l] = R.mspec->permille[l];
+                HIPCHK(launch_summary_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, lv, (int)e->opt_summary_threads, std::min(max_slots, summary_sched_cap()), d[0], e->stream));
+            } else if (R.kind == Red::sojourn) HIPCHK(launch_sojourn_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, wgs, R.sspec->arrival_bins, R.sspec->arrival_bin_ms, R.sspec->delay_bins, R.sspec->delay_bin_ms, (int)e->opt_sojourn_scheme, SojournOut{d[0], d[1], d[2], d[3]}, e->stream));
             else if (tl) HIPCHK(launch_timeline_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, wgs, R.tspec->bins, R.tspec->bin_ms, (int)e->opt_timeline_scheme, TimelineOut{d[0], d[1], d[2], d[3], d[4], d[5]}, e->stream));
             else HIPCHK(launch_dist_kernel(reinterpret_cast<const DistJob *>(e->red_jobs_d), njobs, wgs, R.dspec->delay_bins, R.dspec->delay_bin_ms, (int)e->opt_dist_scheme, d[0], d[1], d[2], e->stream));
             HIPCHK(hipEventRecord(e->red_ev1, e->stream));
@@ -1006,6 +1017,24 @@ static int reduction_end(prach_engine *e, CallCtx &cx) {
     HIPCHK(hipStreamSynchronize(e->stream));
     for (int q = 0; q + 1 < np; q++) HIPCHK(hipMemcpy(R.out[q], cx.d_part[q], 8 * ng * words[q], hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(sc.data(), cx.d_part[np - 1], 8 * sc.size(), hipMemcpyDeviceToHost));
+    if (R.kind == Red::summary) { // one row per trial: status and nUE from the host, the rest from the one launch that accepted the trial
+        int rc = PRACH_OK;
+        for (size_t k = 0; k < ng; k++) {
+            prach_trial_summary &row = R.rows[k];
+            row.status = cx.results[k].status; // (everything else is still the empty row run_trials_impl wrote)
+            if (row.status != PRACH_OK) continue;
+            if (cx.trials[k] != 1) { row.status = PRACH_ERR_INTERNAL; rc = PRACH_ERR_INTERNAL; continue; } // (no launch reduced this trial, or two did)
+            const long long *const q = reinterpret_cast<const long long *>(&sc[k * nsc]);
+            row.arrived = (int32_t)q[0]; row.success = (int32_t)q[1]; row.restarted = (int32_t)q[2];
+            row.range_errors = (int32_t)std::min<long long>(q[3] + q[4] + q[5], INT32_MAX);
+            row.sojourn_sum = q[6]; row.timer_sum = q[7]; row.ptc_sum = q[8];
+            row.sojourn_max = (int32_t)q[9]; row.timer_max = (int32_t)q[10]; row.ptc_max = (int32_t)q[11];
+            for (int x = 0; x < 3; x++)
+                for (int l = 0; l < R.mspec->nq; l++) row.q[x][l] = q[3 + x] ? -1 : (int32_t)q[12 + x * PRACH_SUMMARY_MAX_Q + l];
+            if (row.range_errors) rc = PRACH_ERR_INTERNAL; // (a value the kernel cannot rank: no trial produces one)
+        }
+        return rc;
+    }
     for (size_t g = 0; g < ng; g++) {
         const unsigned long long *const q = &sc[g * nsc];
         if (R.kind == Red::dist) {
@@ -1042,7 +1071,14 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
         const int np = red_parts(*red, words);
         for (int q = 0; q + 1 < np; q++) std::memset(red->out[q], 0, 8 * ng * words[q]);
         for (size_t g = 0; g < ng; g++) {
-            if (red->kind == Red::dist) { red->dist[g] = prach_dist{}; red->dist[g].delay_max = -1; }
+            if (red->kind == Red::summary) {
+                prach_trial_summary &row = red->rows[g];
+                std::memset(&row, 0, sizeof(row));
+                row.status = PRACH_ERR_INTERNAL;
+                row.nUE = cfgs[g].nUE;
+                row.sojourn_max = row.timer_max = row.ptc_max = -1;
+                std::memset(row.q, 0xff, sizeof(row.q)); // -1
+            } else if (red->kind == Red::dist) { red->dist[g] = prach_dist{}; red->dist[g].delay_max = -1; }
             else if (red->kind == Red::sojourn) { red->sj[g] = prach_sojourn{}; red->sj[g].sojourn_max = -1; }
             else { red->tl[g] = prach_timeline{}; red->tl[g].done_max = -1; }
         }
@@ -1209,8 +1245,8 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
     e->last.updates = upd;
     if (red) {
         int rc = reduction_end(e, cx);
+        (red->kind == Red::dist ? e->last.dist_ms : red->kind == Red::timeline ? e->last.timeline_ms : red->kind == Red::sojourn ? e->last.sojourn_ms : e->last.summary_ms) = cx.red_ms;
         if (rc != PRACH_OK) return rc;
-        (red->kind == Red::dist ? e->last.dist_ms : red->kind == Red::timeline ? e->last.timeline_ms : e->last.sojourn_ms) = cx.red_ms;
     }
     e->last.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return worst;
@@ -1275,6 +1311,7 @@ int prach_engine_set(prach_engine *e, const char *key, int64_t value) {
     if (std::strcmp(key, "batch_waves") == 0) { if (value != 0 && value != 8 && value != 16) return PRACH_ERR_ARG; e->opt_batch_waves = value; return PRACH_OK; }
     if (std::strcmp(key, "dist_scheme") == 0) { if (value < 0 || value > 2) return PRACH_ERR_ARG; e->opt_dist_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "timeline_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_timeline_scheme = value; return PRACH_OK; }
+    if (std::strcmp(key, "summary_threads") == 0) { if (value != 0 && value != 512 && value != 1024) return PRACH_ERR_ARG; e->opt_summary_threads = value ? value : 1024; return PRACH_OK; }
     if (std::strcmp(key, "sojourn_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_sojourn_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "xcd_pack") == 0) { e->opt_xcd_pack = value != 0; return PRACH_OK; }
     return PRACH_ERR_ARG;
@@ -1394,6 +1431,21 @@ int prach_run_trials_sojourn(prach_engine *e, const prach_cfg *cfgs, int n, prac
     if ((uint64_t)spec->ngroups * (uint64_t)spec->arrival_bins * ((uint64_t)spec->delay_bins + 2) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
     const Reduction red{Red::sojourn, group, spec->ngroups, nullptr, nullptr, nullptr, nullptr, spec, sj, {hist, row_arrived, row_delay_overflow}};
+    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
+}
+
+int prach_run_trials_summary(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_summary_spec *spec,
+                             prach_trial_summary *rows) {
+    // (spec and variants are judged first: what they ask for does not depend on a device)
+    if (!cfgs || !results || n <= 0 || !spec || !rows) return PRACH_ERR_ARG;
+    if (spec->nq < 1 || spec->nq > PRACH_SUMMARY_MAX_Q || spec->reserved[0] || spec->reserved[1] || spec->reserved[2]) return PRACH_ERR_ARG;
+    for (int l = 0; l < spec->nq; l++) if (spec->permille[l] < 1 || spec->permille[l] > 1000) return PRACH_ERR_ARG;
+    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
+    if (!e) return PRACH_ERR_ARG;
+    static_assert(SM_MAX_VALUE == 65535, "prach_summary_max_value (prach_host.c) states the kernel's bound");
+    Reduction red{Red::summary, nullptr, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {}};
+    red.mspec = spec;
+    red.rows = rows;
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 

@@ -838,3 +838,138 @@ size_t prach_sojourn_format_csv(const prach_sojourn_spec *s, const prach_sojourn
     if (j->arrival_overflow) CSV_EMIT("%.200s,arrivals,overflow,%llu\n", label, (unsigned long long)j->arrival_overflow);
     return csv_end(buf, cap, off);
 }
+
+/* ---- per-trial summaries: exact order statistics and the spread across trials (prach_run_trials_summary) ---- */
+
+static int summary_spec_ok(const prach_summary_spec *s) {
+    if (!s || s->nq < 1 || s->nq > PRACH_SUMMARY_MAX_Q || s->reserved[0] || s->reserved[1] || s->reserved[2]) return 0;
+    for (int l = 0; l < s->nq; l++)
+        if (s->permille[l] < 1 || s->permille[l] > 1000) return 0;
+    return 1;
+}
+
+int prach_summary_max_value(void) { return 65535; }
+
+static void summary_row_clear(prach_trial_summary *row, int status, int nUE) {
+    memset(row, 0, sizeof(*row));
+    row->status = status;
+    row->nUE = nUE;
+    row->sojourn_max = row->timer_max = row->ptc_max = -1;
+    for (int x = 0; x < 3; x++)
+        for (int l = 0; l < PRACH_SUMMARY_MAX_Q; l++) row->q[x][l] = -1;
+}
+
+static int cmp_i32(const void *a, const void *b) {
+    const int32_t x = *(const int32_t *)a, y = *(const int32_t *)b;
+    return (x > y) - (x < y);
+}
+
+/* THE DEFINITION (include/prach.h): the three quantities of the successful UEs are sorted, a level is the value at its integer rank */
+int prach_summary_from_logs(const prach_summary_spec *s, const prach_cfg *cfg, const prach_ue_log *ue, int nUE, prach_trial_summary *row) {
+    if (!summary_spec_ok(s) || !cfg || !row || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    if (cfg->variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED;
+    if (prach_cfg_validate(cfg) != PRACH_OK || nUE != cfg->nUE) return PRACH_ERR_ARG;
+    const int nslots = (prach_max_time(cfg) + cfg->accessTime - 1) / cfg->accessTime;
+    int32_t *sched = (int32_t *)malloc(sizeof(int32_t) * (size_t)nslots);
+    int32_t *val = (int32_t *)malloc(sizeof(int32_t) * 3 * (size_t)(nUE > 0 ? nUE : 1));
+    if (!sched || !val) { free(sched); free(val); return PRACH_ERR_INTERNAL; }
+    prach_arrival_schedule(cfg, sched, nslots, NULL);
+    prach_trial_summary r;
+    summary_row_clear(&r, PRACH_OK, nUE);
+    int32_t *const vx[3] = {val, val + nUE, val + 2 * (size_t)nUE};
+    int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
+    for (int i = 0; i < nUE; i++) {
+        while (slot < nslots && sched[slot] <= i) slot++;
+        if (ue[i].active == -1) continue; /* not arrived */
+        r.arrived++;
+        if (ue[i].msg4Flag != 1) continue;
+        const int64_t a = (int64_t)cfg->accessTime * slot, c = (int64_t)ue[i].txTime + 6;
+        if (ue[i].timer < 0 || c < a) { free(sched); free(val); return PRACH_ERR_ARG; } /* (*row is untouched) */
+        const int n = r.success++;
+        r.restarted += c - ue[i].timer != a;
+        vx[0][n] = (int32_t)(c - a); vx[1][n] = ue[i].timer; vx[2][n] = ue[i].preambleTxCounter;
+        r.sojourn_sum += c - a; r.timer_sum += ue[i].timer; r.ptc_sum += ue[i].preambleTxCounter;
+    }
+    const int64_t n = r.success;
+    if (n > 0) {
+        int32_t *const mx[3] = {&r.sojourn_max, &r.timer_max, &r.ptc_max};
+        for (int x = 0; x < 3; x++) {
+            qsort(vx[x], (size_t)n, sizeof(int32_t), cmp_i32);
+            *mx[x] = vx[x][n - 1];
+            for (int l = 0; l < s->nq; l++) {
+                int64_t rank = (n * (int64_t)s->permille[l] + 999) / 1000;
+                if (rank < 1) rank = 1;
+                r.q[x][l] = vx[x][rank - 1];
+            }
+        }
+    }
+    free(sched);
+    free(val);
+    *row = r;
+    return PRACH_OK;
+}
+
+#define SUMMARY_FIXED_METRICS 5
+/* metric m of a row; returns 0 where the row has no such value */
+static int summary_metric(const prach_summary_spec *s, const prach_trial_summary *r, int m, double *x) {
+    if (r->status != PRACH_OK) return 0;
+    if (m == 0) { *x = (double)r->success / (double)r->nUE; return r->nUE > 0; }
+    if (r->success == 0) return 0;
+    const double n = (double)r->success;
+    if (m == 1) *x = (double)r->restarted / n;
+    else if (m == 2) *x = (double)r->sojourn_sum / n;
+    else if (m == 3) *x = (double)r->timer_sum / n;
+    else if (m == 4) *x = (double)r->ptc_sum / n;
+    else *x = (double)r->q[(m - SUMMARY_FIXED_METRICS) / s->nq][(m - SUMMARY_FIXED_METRICS) % s->nq];
+    return 1;
+}
+
+int prach_summary_stats(const prach_summary_spec *s, const prach_trial_summary *rows, int n, const int32_t *group, int ngroups, prach_stat *out) {
+    if (!summary_spec_ok(s) || n < 0 || (n > 0 && !rows) || ngroups < 1 || !out || (!group && ngroups != 1)) return PRACH_ERR_ARG;
+    if (group)
+        for (int k = 0; k < n; k++)
+            if (group[k] < 0 || group[k] >= ngroups) return PRACH_ERR_ARG;
+    const int nm = SUMMARY_FIXED_METRICS + 3 * s->nq;
+    memset(out, 0, sizeof(prach_stat) * (size_t)ngroups * (size_t)nm);
+    for (int m = 0; m < nm; m++) {
+        double x;
+        for (int k = 0; k < n; k++) { /* pass 1: count, sum, extremes */
+            if (!summary_metric(s, &rows[k], m, &x)) continue;
+            prach_stat *const o = &out[(size_t)(group ? group[k] : 0) * (size_t)nm + (size_t)m];
+            if (o->n == 0 || x < o->min) o->min = x;
+            if (o->n == 0 || x > o->max) o->max = x;
+            o->n++;
+            o->mean += x;
+        }
+        for (int g = 0; g < ngroups; g++) {
+            prach_stat *const o = &out[(size_t)g * (size_t)nm + (size_t)m];
+            if (o->n) o->mean /= (double)o->n;
+        }
+        for (int k = 0; k < n; k++) { /* pass 2: squared deviations from the mean */
+            if (!summary_metric(s, &rows[k], m, &x)) continue;
+            prach_stat *const o = &out[(size_t)(group ? group[k] : 0) * (size_t)nm + (size_t)m];
+            o->sd += (x - o->mean) * (x - o->mean);
+        }
+        for (int g = 0; g < ngroups; g++) {
+            prach_stat *const o = &out[(size_t)g * (size_t)nm + (size_t)m];
+            o->sd = o->n > 1 ? sqrt(o->sd / (double)(o->n - 1)) : 0.0;
+            o->sem = o->n > 1 ? o->sd / sqrt((double)o->n) : 0.0;
+        }
+    }
+    return PRACH_OK;
+}
+
+size_t prach_summary_format_csv(const prach_summary_spec *s, const prach_stat *st, const char *label, char *buf, size_t cap) {
+    static const char *const fixed[SUMMARY_FIXED_METRICS] = {"success_ratio", "restart_ratio", "sojourn_mean", "timer_mean", "ptx_mean"};
+    static const char *const quant[3] = {"sojourn", "timer", "ptx"};
+    if (!summary_spec_ok(s) || !st || !label) return 0;
+    size_t off = 0;
+    const int nm = SUMMARY_FIXED_METRICS + 3 * s->nq;
+    for (int m = 0; m < nm; m++) {
+        char name[32];
+        if (m < SUMMARY_FIXED_METRICS) snprintf(name, sizeof name, "%s", fixed[m]);
+        else snprintf(name, sizeof name, "%s_p%d", quant[(m - SUMMARY_FIXED_METRICS) / s->nq], s->permille[(m - SUMMARY_FIXED_METRICS) % s->nq]);
+        CSV_EMIT("%.200s,%s,%llu,%.9g,%.9g,%.9g,%.9g,%.9g\n", label, name, (unsigned long long)st[m].n, st[m].mean, st[m].sd, st[m].sem, st[m].min, st[m].max);
+    }
+    return csv_end(buf, cap, off);
+}

@@ -174,3 +174,44 @@ def gather_trial_rows(rows, dst: int = 0, device=None):
             payload = raw[11:11 + ln]
             out.append((idx, int(payload) if raw[8:9] == b"i" else payload.decode()))
     return out
+
+
+def gather_summary_rows(rows, index, dst: int = 0, device=None):
+    """This rank's per-trial summary rows (the structured array of a package `Summary`, any order) with their trial indices `index`, gathered to `dst` as ONE
+    structured array in TRIAL order (None elsewhere): the statistics computed from it do not depend on the world size.  ONE all-gather of fixed-size int64
+    records (trial index + the 160-byte row), every rank padding to the largest shard; the shard sizes are agreed in a first all-gather, as in
+    gather_trial_rows."""
+    import torch
+    import torch.distributed as dist
+    rows = np.ascontiguousarray(rows)
+    index = np.asarray(index, dtype=np.int64).ravel()
+    if len(index) != len(rows):
+        raise ValueError(f"{len(rows)} rows but {len(index)} trial indices")
+    if rows.dtype.itemsize % 8:
+        raise ValueError("a summary row is a whole number of 64-bit words")
+    words = rows.dtype.itemsize // 8
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return rows[np.argsort(index, kind="stable")].copy()
+    world = dist.get_world_size()
+    n = torch.tensor([len(rows), words], dtype=torch.int64)
+    if device is not None:
+        n = n.to(device)
+    heads = [torch.zeros_like(n) for _ in range(world)]
+    dist.all_gather(heads, n)
+    heads = [h.cpu() for h in heads]
+    if any(int(h[1]) != words for h in heads):  # every rank sees the same numbers: all of them stop here
+        raise ValueError("the ranks disagree on the size of a summary row")
+    counts = [int(h[0]) for h in heads]
+    buf = np.zeros((max(max(counts), 1), 1 + words), dtype=np.int64)
+    buf[:len(rows), 0] = index
+    buf[:len(rows), 1:] = rows.view(np.int64).reshape(len(rows), words)
+    t = torch.from_numpy(buf)
+    if device is not None:
+        t = t.to(device)
+    parts = [torch.zeros_like(t) for _ in range(world)]
+    dist.all_gather(parts, t)
+    if dist.get_rank() != dst:
+        return None
+    allrec = np.concatenate([parts[r].cpu().numpy()[:counts[r]] for r in range(world)], axis=0)
+    allrec = allrec[np.argsort(allrec[:, 0], kind="stable")]
+    return np.ascontiguousarray(allrec[:, 1:]).view(rows.dtype).reshape(-1)

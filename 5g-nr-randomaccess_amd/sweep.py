@@ -42,12 +42,21 @@ def main(argv=None):
                     "file (not together with --cdf or --timeline)")
     ap.add_argument("--sojourn-arrival-ms", type=int, default=500, help="width of an arrival row in ms; the rows cover the arrivals")
     ap.add_argument("--sojourn-bin", type=int, default=5, help="width of a delay bin in ms; the bins cover the horizon")
+    ap.add_argument("--ci", default=None, help="write mean, standard deviation, standard error, minimum and maximum ACROSS THE SEEDS of every sweep point — success "
+                    "and restart ratio, mean sojourn / timer / preamble transmissions and their exact per-trial percentiles — to this CSV file (not together "
+                    "with --cdf, --timeline or --sojourn)")
+    ap.add_argument("--ci-levels", default="500,950,990", help="percentile levels in permille, at most 8")
     ap.add_argument("--same-device", action="store_true", help="rehearsal on one GPU: every rank uses cuda:0")
     args = ap.parse_args(argv)
     if args.cdf and args.timeline:
         ap.error("--cdf and --timeline cannot be combined: one reduction per call")
     if args.sojourn and (args.cdf or args.timeline):
         ap.error("--sojourn cannot be combined with --cdf or --timeline: one reduction per call")
+    if args.ci and (args.cdf or args.timeline or args.sojourn):
+        ap.error("--ci cannot be combined with --cdf, --timeline or --sojourn: one reduction per call")
+    ci_levels = [int(x) for x in args.ci_levels.split(",")]
+    if not 1 <= len(ci_levels) <= 8 or any(m < 1 or m > 1000 for m in ci_levels):
+        ap.error("--ci-levels takes 1 to 8 levels between 1 and 1000")
 
     import torch
     import __graft_entry__ as g
@@ -88,9 +97,13 @@ def main(argv=None):
     elif args.sojourn:
         sj = (-(-10000 // args.sojourn_arrival_ms), args.sojourn_arrival_ms, -(-(10000 + 6) // args.sojourn_bin), args.sojourn_bin)
         red = (pkg.Sojourn(len(points), *sj), eng.run_trials_sojourn, sj, distmod.allreduce_sojourn, pkg.sojourn_csv, args.sojourn)
+    ci_rows = []
     for a in range(0, len(mine), CH):
         part = mine[a:a + CH]
-        if red is None:
+        if args.ci:  # one row per trial comes from the device with the results
+            r, _, sm = eng.run_trials_summary([cfgs[i] for i in part], ci_levels)
+            ci_rows.append(sm.rows)
+        elif red is None:
             r, _ = eng.run_trials([cfgs[i] for i in part])
         else:  # the chunk's reduction comes from the device with the results: no per-UE log is copied
             acc, run, params = red[:3]
@@ -113,6 +126,15 @@ def main(argv=None):
         if rank == 0:
             with open(path, "wb") as f:
                 f.write(to_csv(acc, labels=points))
+    if args.ci:  # the rows travel to rank 0 and are put in trial order there: the statistics do not depend on the number of ranks
+        import numpy as np
+        mine_rows = np.concatenate(ci_rows) if ci_rows else np.zeros(0, dtype=pkg.summary_row_dtype())
+        every = distmod.gather_summary_rows(mine_rows, mine, dst=0, device=dev if (world > 1 and args.backend == "nccl") else None)
+        if rank == 0:
+            sm = pkg.Summary(len(cfgs), ci_levels)
+            sm.rows[:] = every
+            with open(args.ci, "wb") as f:
+                f.write(pkg.summary_csv(sm, groups=[i % len(points) for i in range(len(cfgs))], ngroups=len(points), labels=points))
     if rank == 0:
         fi = {n: k for k, n in enumerate(distmod.AGG_FIELDS)}
         summary = {"program": args.program, "times": args.times, "points": points, "world": world,

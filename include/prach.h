@@ -129,6 +129,8 @@ typedef struct prach_timing {
     int32_t trial_kernel_reruns; /* of fallback_trials: trials that were (also) rerun on the one-workgroup, index-ordered trial_kernel */
     int32_t noma_host_ues;       /* NOMA_C, Philox: UEs of the device-built activeUE table that the host recomputed with its libm (a value inside the
                                     device math library's error band of a rounding / comparison boundary: ~1e-6 of the UEs) */
+    double summary_ms;           /* HIP-event time of the summary kernel launches (prach_run_trials_summary) of the last call; 0 in every other call (a summary call
+                                    leaves dist_ms, timeline_ms and sojourn_ms 0) */
     double dist_ms;              /* HIP-event time of the distribution kernel launches (prach_run_trials_dist) of the last call; 0 without a spec */
     double timeline_ms;          /* HIP-event time of the timeline kernel launches (prach_run_trials_timeline) of the last call; 0 in every other call */
     double sojourn_ms;           /* HIP-event time of the sojourn kernel launches (prach_run_trials_sojourn) of the last call; 0 in every other call (a sojourn
@@ -276,6 +278,35 @@ int prach_run_trials_sojourn(prach_engine *, const prach_cfg *cfgs, int n, prach
                              const prach_sojourn_spec *spec, const int32_t *group, prach_sojourn *sj, uint64_t *hist, uint64_t *row_arrived,
                              uint64_t *row_delay_overflow);
 
+/* Per-trial summary, built on the device: ONE row per TRIAL — counts, sums, maxima and EXACT order statistics of the sojourn, of `timer` and of
+ * preambleTxCounter over the trial's successful UEs — so that the spread from seed to seed of any of them, a percentile included, can be stated
+ * (prach_summary_stats).  The pooled reductions above cannot give that: they add trials into shared bins.  a(i), c(i), ARRIVED, successful and RESTARTED are
+ * those of the timeline block above.
+ * THE DEFINITION of a level: for a quantity X over the n = success successful UEs of ONE trial and a level m in permille (1..1000), the rank is
+ *   r = max(1, (n * m + 999) / 1000)      in 64-bit integers
+ * and the value is the r-th smallest X.  No bins, no interpolation.  The rule is deliberately integer; at m = 500 it coincides with the ceil(q * n) of
+ * prach_sojourn_quantile (0.5 is exact in binary); no wider equivalence is claimed.
+ * Beta.c and RandomAccessWithNOMA.c only, like the timeline. */
+#define PRACH_SUMMARY_MAX_Q 8
+typedef struct prach_summary_spec { int32_t nq; int32_t permille[PRACH_SUMMARY_MAX_Q]; int32_t reserved[3]; } prach_summary_spec; /* nq 1..8, levels 1..1000 */
+typedef struct prach_trial_summary {      /* one per TRIAL */
+    int32_t status, nUE, arrived, success, restarted, range_errors;
+    int64_t sojourn_sum, timer_sum, ptc_sum;             /* over the successful UEs */
+    int32_t sojourn_max, timer_max, ptc_max;             /* -1 if success == 0 */
+    int32_t q[3][PRACH_SUMMARY_MAX_Q];                   /* [sojourn, timer, preambleTxCounter][level]; -1 if success == 0 or level unused */
+} prach_trial_summary;
+typedef struct prach_stat { uint64_t n; double mean, sd, sem, min, max; } prach_stat;
+
+/* prach_run_trials plus one summary row per trial: rows[n] is caller-owned and OVERWRITTEN.  Row k carries the final status of trial k and cfgs[k].nUE; unless
+ * that status is PRACH_OK everything else in it is 0, the maxima and levels -1.  A trial the engine reruns is written once, by the launch whose result is
+ * kept.  prach::summary_kernel (csrc/prach_summary.hip) selects the order statistics from the per-UE log records the simulation kernels write ON THE DEVICE,
+ * one workgroup per trial; it handles values 0 .. prach_summary_max_value().  range_errors counts the successful UEs with a value outside that range (no
+ * trial produces one): the levels of that quantity are -1 then and the call returns PRACH_ERR_INTERNAL.
+ * PRACH_ERR_ARG: a NULL output or spec, nq or a level out of range, a non-zero reserved word; PRACH_ERR_UNSUPPORTED: any NOMA_C cfg (before anything is
+ * launched). */
+int prach_run_trials_summary(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs,
+                             const prach_summary_spec *spec, prach_trial_summary *rows);
+
 /* engine tunables; none changes a result, all are covered by parity tests:
  *   "cluster"       workgroups cooperating on one trial (1..64; 0 = auto)
  *   "stream_factor" glibc mode: initial draws-per-UE budget of the rand() stream window (0 = auto; it grows on demand)
@@ -298,6 +329,7 @@ int prach_run_trials_sojourn(prach_engine *, const prach_cfg *cfgs, int n, prach
  *                   (the default: measured 15-20x faster on the sweep grids)
  *   "sojourn_scheme" prach::sojourn_kernel's binning: 0 every contribution is a 64-bit agent-scope global atomic, 1 rows of the histogram privatised in LDS
  *                   per workgroup (the default: measured 95x faster on the sweep grids)
+ *   "summary_threads" prach::summary_kernel's workgroup: 512 or 1024 threads (0 = the default, 1024)
  *   "calendar_cap", "vmm_fail_after", "noma_ambiguity_test", "noma_host_activation"   test hooks (prach_engine.hip) */
 int prach_engine_set(prach_engine *, const char *key, int64_t value);
 
@@ -395,6 +427,23 @@ size_t prach_sojourn_format_csv(const prach_sojourn_spec *, const prach_sojourn 
                                 const uint64_t *row_delay_overflow, const char *label, char *buf, size_t cap);
 int prach_sojourn_tile_ues(void);     /* UEs of one trial that one workgroup of prach::sojourn_kernel reduces (tests place sizes around it) */
 int prach_sojourn_window_words(void); /* 32-bit cells of the LDS window of prach::sojourn_kernel (sojourn_scheme 1): it holds window_words / delay_bins rows */
+
+/* Per-trial summaries, host side (no device needed).
+ * prach_summary_from_logs OVERWRITES *row with the summary of one trial's per-UE log: THE DEFINITION prach::summary_kernel equals, integer for integer (it
+ * sorts, so any int32 value is handled and range_errors is 0; status PRACH_OK).  Errors as prach_timeline_accumulate_logs. */
+int prach_summary_from_logs(const prach_summary_spec *, const prach_cfg *cfg, const prach_ue_log *ue, int nUE, prach_trial_summary *row);
+/* Mean and spread over the trials of each group: out[ngroups][5 + 3 * nq], the metrics in this order:
+ *   success_ratio (success / nUE), restart_ratio (restarted / success), sojourn_mean, timer_mean, ptx_mean (sum / success),
+ *   sojourn_p<m> for every level, timer_p<m> ..., ptx_p<m> ...
+ * Trial k belongs to group group[k] (group == NULL: all trials are group 0 and ngroups must be 1).  A row whose status is not PRACH_OK is skipped for every
+ * metric; a row with success == 0 is skipped for every metric but success_ratio.  Two passes in trial order, in doubles: mean = sum(x) / n,
+ * sd = sqrt(sum((x - mean)^2) / (n - 1)), sem = sd / sqrt(n); sd = sem = 0 for n = 1, everything 0 for n = 0.  No t-quantiles: n is given, the reader picks
+ * the interval.  PRACH_ERR_ARG: a bad spec, a NULL argument, a group id out of range. */
+int prach_summary_stats(const prach_summary_spec *, const prach_trial_summary *rows, int n, const int32_t *group, int ngroups, prach_stat *out);
+/* one group (5 + 3 * nq prach_stat) as text: `label,<metric>,<n>,<mean>,<sd>,<sem>,<min>,<max>` per metric, numbers as %.9g, lines end in \n.  Returns the
+ * length needed (without the terminating 0); the text is written only if it fits cap with its terminator. */
+size_t prach_summary_format_csv(const prach_summary_spec *, const prach_stat *stats_of_one_group, const char *label, char *buf, size_t cap);
+int prach_summary_max_value(void);    /* 65 535: the largest value prach::summary_kernel ranks */
 
 /* Text surfaces, byte-compatible with the reference (latency values excepted) */
 size_t prach_format_logs(const prach_ue_log *ue, int nUE, char *buf, size_t cap);           /* Beta.c:501 */
