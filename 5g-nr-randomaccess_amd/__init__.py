@@ -54,7 +54,7 @@ class PrachTiming(C.Structure):
                 ("launches", C.c_int32), ("workgroups", C.c_int32), ("updates", C.c_uint64),
                 ("cluster_size", C.c_int32), ("resident_limit", C.c_int32), ("fallback_trials", C.c_int32), ("spin_timeouts", C.c_int32),
                 ("rec_mode", C.c_int32), ("xcd_packed", C.c_int32), ("group_visits", C.c_uint64), ("event_ues", C.c_uint64),
-                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
+                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
                 ("sojourn_ms", C.c_double)]
 
 
@@ -71,7 +71,7 @@ class PrachDist(C.Structure):
 
 
 class _Reduction:
-    """What Dist, Timeline and Sojourn share.  A subclass names its scalar fields (_FIELDS), the C struct of one group (_STRUCT), the library's merge and its
+    """What Dist, Timeline, Sojourn and Trace share.  A subclass names its scalar fields (_FIELDS), the C struct of one group (_STRUCT), the library's merge and its
     defining parameters (_PARAMS), and gives ``_arrays()`` — its [ngroups, n] uint64 arrays in the order of the C ABI — ``_scalar(f)``, the int64 array of
     length ngroups of scalar field f, and ``_cargs(g)``, group g's arrays as the library's merge and CSV functions take them."""
 
@@ -216,6 +216,69 @@ class Sojourn(_Reduction):
         return int(lib().prach_sojourn_quantile(C.byref(sp), h, o, int(row), float(q)))
 
 
+TRACE_MAX_BINS = 65536
+TRACE_SERIES = ("calls", "singles", "txop", "collisions")
+TRACE_FIELDS = ("trials", "subframes", "calls", "singles", "txop", "collisions", "overflow_calls", "calls_max")
+
+
+class PrachTraceSpec(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("bins", "bin_ms", "ngroups", "reserved")]
+
+
+class PrachTrace(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in TRACE_FIELDS[:-1]] + [("calls_max", C.c_int64)]
+
+
+class Trace(_Reduction):
+    """The per-subframe preamble traces of ``ngroups`` trial groups (include/prach.h, prach_trace): ``series[name]`` [ngroups, bins] as numpy uint64 for every
+    name of TRACE_SERIES (bin b covers the subframes [b * bin_ms, (b + 1) * bin_ms)) — calls: preambles used, singles: preambles decoded, txop and
+    collisions: what the subframes added to totalPreambleTxop and collisionPreambles, as the programs count them — and ``scalars[field]``, one int64
+    array of length ngroups per field of TRACE_FIELDS.  There is no from_logs form: a per-UE log does not hold what happened per subframe."""
+    _FIELDS, _STRUCT, _MERGE, _PARAMS = TRACE_FIELDS, PrachTrace, "prach_trace_merge", ("bins", "bin_ms")
+
+    def __init__(self, ngroups, bins, bin_ms=1):
+        import numpy as np
+        self.bins, self.bin_ms, self.ngroups = int(bins), int(bin_ms), int(ngroups)
+        self.series = {n: np.zeros((self.ngroups, self.bins), dtype=np.uint64) for n in TRACE_SERIES}
+        self.scalars = {f: np.zeros(self.ngroups, dtype=np.int64) for f in TRACE_FIELDS}
+        self.scalars["calls_max"][:] = -1
+
+    def spec(self):
+        return PrachTraceSpec(self.bins, self.bin_ms, self.ngroups, 0)
+
+    def _arrays(self):
+        return [self.series[n] for n in TRACE_SERIES]
+
+    def _scalar(self, f):
+        return self.scalars[f]
+
+    def _series(self, g):
+        """The four series of group g as the uint64_t *[4] the C side takes."""
+        return (C.POINTER(C.c_uint64) * 4)(*self._rows(g))
+
+    def _cargs(self, g):
+        return (self._series(g),)
+
+    def merge(self, other):
+        """Adds every group of ``other`` (same bins, bin_ms and ngroups) to the same group of this one (prach_trace_merge).  Returns self."""
+        if (self.bins, self.bin_ms, self.ngroups) != (other.bins, other.bin_ms, other.ngroups):
+            raise ValueError("traces of different shapes do not merge")
+        for g in range(self.ngroups):
+            self.merge_group(g, other, g)
+        return self
+
+    def csv(self, labels=None) -> bytes:
+        """The CSV text of every group (prach_trace_format_csv), labelled labels[g] (default: the group number)."""
+        return _csv("prach_trace_format_csv", self, labels)
+
+    def collision_ratio(self, group):
+        """(calls - singles) / calls per bin of one group, as float64: the share of the used preambles that collided (NaN where no preamble was used)."""
+        import numpy as np
+        c, s = self.series["calls"][group].astype(np.float64), self.series["singles"][group].astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(c > 0, (c - s) / c, np.nan)
+
+
 SUMMARY_MAX_Q = 8
 SUMMARY_QUANTITIES = ("sojourn", "timer", "ptx")
 SUMMARY_FIXED_METRICS = ("success_ratio", "restart_ratio", "sojourn_mean", "timer_mean", "ptx_mean")
@@ -355,6 +418,13 @@ def lib():
         L.prach_summary_format_csv.argtypes = [C.POINTER(PrachSummarySpec), C.POINTER(PrachStat), C.c_char_p, C.c_char_p, C.c_size_t]
         L.prach_summary_format_csv.restype = C.c_size_t
         L.prach_summary_max_value.argtypes = []
+        L.prach_run_trials_trace.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachTraceSpec),
+                                             C.POINTER(C.c_int32), C.POINTER(PrachTrace), u64p, u64p, u64p, u64p]
+        L.prach_trace_merge.argtypes = [C.POINTER(PrachTraceSpec), C.POINTER(PrachTrace), u64pp, C.POINTER(PrachTrace), u64pp]
+        L.prach_trace_merge.restype = None
+        L.prach_trace_format_csv.argtypes = [C.POINTER(PrachTraceSpec), C.POINTER(PrachTrace), u64pp, C.c_char_p, C.c_char_p, C.c_size_t]
+        L.prach_trace_format_csv.restype = C.c_size_t
+        L.prach_trace_tile_subframes.argtypes = []
         L.prach_cfg_defaults.argtypes = [C.POINTER(PrachCfg), C.c_int]
         L.prach_cfg_defaults.restype = None
         L.prach_cfg_validate.argtypes = [C.POINTER(PrachCfg)]
@@ -396,7 +466,8 @@ EXPORTS = ("prach_engine_create", "prach_engine_destroy", "prach_engine_set", "p
            "prach_dist_format_csv", "prach_dist_tile_ues", "prach_run_trials_timeline", "prach_timeline_accumulate_logs", "prach_timeline_merge",
            "prach_timeline_format_csv", "prach_timeline_tile_ues", "prach_timeline_window_bins", "prach_run_trials_sojourn", "prach_sojourn_accumulate_logs",
            "prach_sojourn_merge", "prach_sojourn_quantile", "prach_sojourn_format_csv", "prach_sojourn_tile_ues", "prach_sojourn_window_words",
-           "prach_run_trials_summary", "prach_summary_from_logs", "prach_summary_stats", "prach_summary_format_csv", "prach_summary_max_value")
+           "prach_run_trials_summary", "prach_summary_from_logs", "prach_summary_stats", "prach_summary_format_csv", "prach_summary_max_value",
+           "prach_run_trials_trace", "prach_trace_merge", "prach_trace_format_csv", "prach_trace_tile_subframes")
 
 
 def make_cfg(nUE, variant=VARIANT_BETA_C, uniform=0, rng_mode=RNG_GLIBC, seed=0, stream_offset=0, **kw) -> PrachCfg:
@@ -490,6 +561,13 @@ class Engine:
         sp = sm.spec()
         res, logs = self._call("prach_run_trials_summary", cfgs, want_logs, C.byref(sp), sm._rows_ptr())
         return res, logs, sm
+
+    def run_trials_trace(self, cfgs, bins, bin_ms=1, groups=None, want_logs=False, ngroups=None):
+        """run_trials plus the per-subframe preamble trace per trial group — preambles used (calls), decoded (singles) and what the subframes added to
+        totalPreambleTxop and collisionPreambles, by time — recorded by the simulation kernels while they run and reduced on the device
+        (prach_run_trials_trace; Beta.c and RandomAccessWithNOMA trials only).  groups / ngroups / want_logs as in run_trials_dist.  Returns
+        (results, logs, Trace)."""
+        return self._call_reduced("prach_run_trials_trace", cfgs, Trace(_ngroups(len(cfgs), groups, ngroups), bins, bin_ms), groups, want_logs)
 
     @staticmethod
     def _log_buffers(cfgs, want_logs):
@@ -700,6 +778,15 @@ def sojourn_from_logs(cfgs, logs, arrival_bins, arrival_bin_ms, delay_bins, dela
 def sojourn_csv(sj: Sojourn, labels=None) -> bytes:
     """The CSV text of every group (prach_sojourn_format_csv), labelled labels[g] (default: the group number)."""
     return _csv("prach_sojourn_format_csv", sj, labels)
+
+
+def trace_tile_subframes() -> int:
+    return lib().prach_trace_tile_subframes()
+
+
+def trace_csv(tr: Trace, labels=None) -> bytes:
+    """The CSV text of every group (prach_trace_format_csv), labelled labels[g] (default: the group number)."""
+    return _csv("prach_trace_format_csv", tr, labels)
 
 
 def summary_max_value() -> int:

@@ -91,7 +91,8 @@ template <int NWB> struct BCap {
 // (the event / candidate counts and the free-chunk pool exist twice, by subframe parity: a wavefront that is already in the next subframe's body uses the other one)
 enum { B_NSUCC = 0, B_COLL, B_TXOP, B_CONTF, B_NS, B_NRC, B_NRJ, B_OVF /* the chunk pool, a chunk table or a join list is full: the trial leaves */, B_NEV = 8 /* [2] */, B_NCAND = 10 /* [2] */,
        B_POOLH = 12 /* [2] free chunk ids in the shared pool's two halves */, B_PTC = 14, B_FC, B_SUMT = 16, B_ND = 18, B_JOINS = 20, B_EVENTS = 21, B_NCROSS = 22, B_BUMP = 23 /* chunks never used yet */, B_TICK = 30 /* [2] event batches handed out beyond the wavefronts' own first three (second: the reference stream's select pass) */,
-       B_SGC = 24 /* [24, 30): sectorGrants[6], WithNOMA:260 (PRACH_FLAG_SECTOR_GRANTS) */, B_NROV = 32 /* [16] grants beyond the first of their bucket, per subframe of the ring */ };
+       B_SGC = 24 /* [24, 30): sectorGrants[6], WithNOMA:260 (PRACH_FLAG_SECTOR_GRANTS) */, B_NROV = 32 /* [16] grants beyond the first of their bucket, per subframe of the ring */,
+       B_CALLS = 48 /* preambleCollision calls so far */, B_TRACE = 49 /* 1: the trial's trace rows are wanted (prach_run_trials_trace) */, B_TRPREV = 50 /* [3] calls, txop, collisions as the previous row left them */ };
 
 // ---- LDS layout: byte offsets, all compile-time ------------------------------------------------------------------------------------
 template <int NWB> struct BL {
@@ -230,7 +231,7 @@ __global__ __launch_bounds__(NWB * 64, NWB == 8 ? PRACH_B_W8_WAVES : 4) void bat
         BI(bl::TOTAL)[tid] = 0; BI(bl::RUN)[tid] = 0; BI(bl::NLV)[tid] = 0; BI(bl::FIE)[tid] = 0; BI(bl::FMINP)[tid] = INT_MAX; bmk[tid] = 0u;
         BI(bl::FCALL)[tid] = INT_MAX; BI(bl::FCALL)[NPB + tid] = INT_MAX; BI(bl::LCALL)[tid] = -1; BI(bl::LCALL)[NPB + tid] = -1;
     }
-    if (tid < 64) scal[tid] = 0;
+    if (tid < 64) scal[tid] = tid == B_TRACE ? (PD->trace != nullptr) : 0;
     if (GLIBC) for (int k = tid; k < 4 * BGG; k += TB) gm[k] = 0u;
     __syncthreads();
 
@@ -717,7 +718,8 @@ __global__ __launch_bounds__(NWB * 64, NWB == 8 ? PRACH_B_W8_WAVES : 4) void bat
         // every call: scan count `check` (Beta.c:321-330), counters (Beta.c:334,349-351 / WithNOMA:650-652)
         {
             const int nrj = scal[B_NRJ];
-            int my_coll = 0, my_txop = 0;
+            const int tracing = __builtin_amdgcn_readfirstlane(scal[B_TRACE]); // (read next to nrj, a scalar: the calls are counted for a trace call only)
+            int my_coll = 0, my_txop = 0, my_calls = 0;
             for (int k = tid; k < N + nP; k += TB) {
                 int idx = 0, p = 0, ispre = 0;
                 bool caller = false;
@@ -730,6 +732,7 @@ __global__ __launch_bounds__(NWB * 64, NWB == 8 ? PRACH_B_W8_WAVES : 4) void bat
                     if (fcallA[p] != INT_MAX && !BI(bl::FIE)[p]) { caller = true; idx = fcallA[p]; ispre = 1; } // a matched UE calls first
                 }
                 if (!caller) continue;
+                my_calls += 1;
                 const bool first = idx == fcallA[p];
                 int rj = 0;
                 if (nrj > 0) { // Msg3-timeout re-entries that stayed matched since the previous call on this bucket (rare)
@@ -759,13 +762,26 @@ __global__ __launch_bounds__(NWB * 64, NWB == 8 ? PRACH_B_W8_WAVES : 4) void bat
             if (__any((my_coll | my_txop) != 0)) {
                 my_coll = wave_sum(my_coll); my_txop = wave_sum(my_txop);
                 if (lane == 0) { if (my_coll) atomicAdd(&scal[B_COLL], my_coll); if (my_txop) atomicAdd(&scal[B_TXOP], my_txop); }
+                if (tracing) { // (every call adds to txop: a wavefront with a call is here)
+                    my_calls = wave_sum(my_calls);
+                    if (lane == 0) atomicAdd(&scal[B_CALLS], my_calls);
+                }
             }
         }
         BSTAMP(9); // calls
         __syncthreads(); // S5: calls done; singles listed
         BSTAMP(10);
-        if (tid == 0) { scal[B_NEV + parity] = 0; scal[B_NCAND + parity] = 0; } // (every thread has read them; the next subframe appends to the other pair)
         const int ns = scal[B_NS];
+        if (tid == 0) {
+            scal[B_NEV + parity] = 0; scal[B_NCAND + parity] = 0; // (every thread has read them; the next subframe appends to the other pair)
+            if (scal[B_TRACE]) { // prach_run_trials_trace: the subframe's row (the counters move again behind the next subframe's barriers)
+                const int c = scal[B_CALLS], x = scal[B_TXOP], q = scal[B_COLL];
+                if (c != scal[B_TRPREV]) {
+                    st_i4((PRACH_G v4i_t *)rare()->trace + t, make_int4(c - scal[B_TRPREV], ns, x - scal[B_TRPREV + 1], q - scal[B_TRPREV + 2]));
+                    scal[B_TRPREV] = c; scal[B_TRPREV + 1] = x; scal[B_TRPREV + 2] = q;
+                }
+            }
+        }
         if (ns > BSC) { status = PRACH_ERR_INTERNAL; why = 3; time_exit = t; break; }
         const int Gr = max(0, nGrantUL - 1 - grantCheck); // Beta.c:336-347
         // An UL grant (Beta.c:338-343) for the singleton caller `my` of bucket bp: NOTED (its record is in some later subframe's list and takes the grant when it

@@ -30,6 +30,10 @@
  * of the success and restart ratio, the mean sojourn / timer / preamble transmissions and their exact per-trial percentiles at the given levels in permille
  * (default 500,950,990; at most 8): one row per trial comes from the device (prach_run_trials_summary, so it works with --logs 0), the statistics are
  * prach_summary_stats over the rows in trial order; --program beta|withnoma only, and not together with --cdf, --timeline or --sojourn;
+ * --trace FILE [--trace-bin MS]: the per-subframe preamble trace — preambles used (calls), decoded (singles), and what the programs add to totalPreambleTxop
+ * and collisionPreambles, by time (prach_run_trials_trace: recorded by the simulation kernels and reduced on the device, so it works with --logs 0), one group
+ * per sweep point with the --times seeds merged, labelled nUE; bins of MS ms (default 5) that cover maxTime; --program beta|withnoma only, and not together
+ * with --cdf, --timeline, --sojourn or --ci (one reduction per call);
  * --devices LIST: the same with explicit HIP ordinals (an ordinal may repeat);
  * --gpus N: the --times x sweep grid sharded over N devices of the node by host C — one forked child per device,
  * forked BEFORE any HIP call, trials dealt by descending cost (Philox: any trial anywhere; glibc: whole seeds, because
@@ -110,16 +114,19 @@ typedef struct reduction {
     /* --ci (prach_run_trials_summary) is no block of groups: one row per trial of the grid, in a shared mapping like the results; the parent computes the statistics */
     const prach_summary_spec *sm;
     prach_trial_summary *sm_rows;
+    const prach_trace_spec *tr; /* --trace: prach_trace[npts] | four series [npts][bins] each (calls, singles, txop, collisions) */
 } reduction;
-static int red_on(const reduction *r) { return r->cdf || r->tl || r->sj; }
+static int red_on(const reduction *r) { return r->cdf || r->tl || r->sj || r->tr; }
 static size_t sj_cells(const prach_sojourn_spec *s) { return (size_t)s->arrival_bins * (size_t)s->delay_bins; }
 static size_t red_block_bytes(const reduction *r) {
+    if (r->tr) return (size_t)r->tr->ngroups * (sizeof(prach_trace) + 4 * 8 * (size_t)r->tr->bins);
     if (r->tl) return (size_t)r->tl->ngroups * (sizeof(prach_timeline) + 5 * 8 * (size_t)r->tl->bins);
     if (r->sj) return (size_t)r->sj->ngroups * (sizeof(prach_sojourn) + 8 * (sj_cells(r->sj) + 2 * (size_t)r->sj->arrival_bins));
     return r->cdf ? (size_t)r->cdf->ngroups * (sizeof(prach_dist) + 8 * ((size_t)r->cdf->delay_bins + PRACH_DIST_PTC_BINS)) : 0;
 }
 /* group g of block b: --cdf its q-th histogram (0 delay, 1 preamble count), --timeline its q-th series, --sojourn 0 hist, 1 row_arrived, 2 row_delay_overflow */
 static uint64_t *red_array(const reduction *r, char *b, int q, int g) {
+    if (r->tr) return (uint64_t *)(b + (size_t)r->tr->ngroups * sizeof(prach_trace)) + ((size_t)q * (size_t)r->tr->ngroups + (size_t)g) * (size_t)r->tr->bins;
     if (r->sj) {
         uint64_t *const h = (uint64_t *)(b + (size_t)r->sj->ngroups * sizeof(prach_sojourn));
         const size_t ng = (size_t)r->sj->ngroups, rows = (size_t)r->sj->arrival_bins;
@@ -134,8 +141,16 @@ static void red_init_block(const reduction *r, char *b) {
     for (int g = 0; r->tl && g < r->tl->ngroups; g++) ((prach_timeline *)b)[g].done_max = -1;
     for (int g = 0; r->cdf && g < r->cdf->ngroups; g++) ((prach_dist *)b)[g].delay_max = -1;
     for (int g = 0; r->sj && g < r->sj->ngroups; g++) ((prach_sojourn *)b)[g].sojourn_max = -1;
+    for (int g = 0; r->tr && g < r->tr->ngroups; g++) ((prach_trace *)b)[g].calls_max = -1;
 }
 static void red_merge_block(const reduction *r, char *into, char *from) {
+    for (int g = 0; r->tr && g < r->tr->ngroups; g++) {
+        uint64_t *a[4];
+        const uint64_t *b[4];
+        for (int q = 0; q < 4; q++) { a[q] = red_array(r, into, q, g); b[q] = red_array(r, from, q, g); }
+        prach_trace_merge(r->tr, (prach_trace *)into + g, a, (prach_trace *)from + g, b);
+    }
+    if (r->tr) return;
     for (int g = 0; r->tl && g < r->tl->ngroups; g++) {
         uint64_t *a[5];
         const uint64_t *b[5];
@@ -150,6 +165,11 @@ static void red_merge_block(const reduction *r, char *into, char *from) {
 }
 /* the CSV text of group g of block b; returns its length (>= cap: it did not fit) */
 static size_t red_format_group(const reduction *r, char *b, int g, const char *label, char *out, size_t cap) {
+    if (r->tr) {
+        const uint64_t *ser[4];
+        for (int q = 0; q < 4; q++) ser[q] = red_array(r, b, q, g);
+        return prach_trace_format_csv(r->tr, (prach_trace *)b + g, ser, label, out, cap);
+    }
     if (r->tl) {
         const uint64_t *ser[5];
         for (int q = 0; q < 5; q++) ser[q] = red_array(r, b, q, g);
@@ -165,7 +185,9 @@ static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *
     if (red->sm) return prach_run_trials_summary(eng, c, n, r, logs, red->sm, sm_rows);
     if (!red_on(red)) return prach_run_trials(eng, c, n, r, logs);
     char *const b = call_block;
-    const int rc = red->tl ? prach_run_trials_timeline(eng, c, n, r, logs, red->tl, grp, (prach_timeline *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0),
+    const int rc = red->tr ? prach_run_trials_trace(eng, c, n, r, logs, red->tr, grp, (prach_trace *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0), red_array(red, b, 2, 0),
+                                                    red_array(red, b, 3, 0))
+                   : red->tl ? prach_run_trials_timeline(eng, c, n, r, logs, red->tl, grp, (prach_timeline *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0),
                                                        red_array(red, b, 2, 0), red_array(red, b, 3, 0), red_array(red, b, 4, 0))
                    : red->sj ? prach_run_trials_sojourn(eng, c, n, r, logs, red->sj, grp, (prach_sojourn *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0), red_array(red, b, 2, 0))
                            : prach_run_trials_dist(eng, c, n, r, logs, red->cdf, grp, (prach_dist *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0));
@@ -259,9 +281,9 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
 int main(int argc, char *argv[]) {
     int randomMax = 1, variant = PRACH_VARIANT_WITHNOMA_C, rng = PRACH_RNG_GLIBC, device = 0, want_logs = 1, gpus = 1, rng_given = 0;
     int sweep_lo = 10000, sweep_hi = 100000, sweep_step = 10000; /* WithNOMA:221 */
-    const char *outdir = ".", *csv_path = NULL, *devlist = NULL, *cdf_path = NULL, *tl_path = NULL, *sj_path = NULL, *ci_path = NULL;
+    const char *outdir = ".", *csv_path = NULL, *devlist = NULL, *cdf_path = NULL, *tl_path = NULL, *sj_path = NULL, *ci_path = NULL, *tr_path = NULL;
     prach_summary_spec ci_spec = {3, {500, 950, 990, 0, 0, 0, 0, 0}, {0, 0, 0}};
-    int cdf_bins = 4096, cdf_bin_ms = 1, tl_bin_ms = 5, sj_row_ms = 500, sj_bin_ms = 5;
+    int cdf_bins = 4096, cdf_bin_ms = 1, tl_bin_ms = 5, sj_row_ms = 500, sj_bin_ms = 5, tr_bin_ms = 5;
     int devs[64];
     /* --program must be known before the defaults are laid down */
     for (int i = 1; i + 1 < argc; i += 2)
@@ -357,6 +379,11 @@ int main(int argc, char *argv[]) {
         } else if (strcmp(a, "--sojourn-bin") == 0) {
             if (atoi(v) < 1) die("--sojourn-bin MS: the width of a delay bin in ms, at least 1");
             sj_bin_ms = atoi(v);
+        } else if (strcmp(a, "--trace") == 0) {
+            tr_path = v;
+        } else if (strcmp(a, "--trace-bin") == 0) {
+            if (atoi(v) < 1) die("--trace-bin MS: the width of a trace bin in ms, at least 1");
+            tr_bin_ms = atoi(v);
         } else if (strcmp(a, "--ci") == 0) {
             ci_path = v;
         } else if (strcmp(a, "--ci-levels") == 0) {
@@ -374,6 +401,8 @@ int main(int argc, char *argv[]) {
         }
     }
     base.rng_mode = rng;
+    if (tr_path && (ci_path || sj_path || tl_path || cdf_path)) die("--trace cannot be combined with --cdf, --timeline, --sojourn or --ci: one reduction per call");
+    if (tr_path && variant == PRACH_VARIANT_NOMA_C) die("--trace needs --program beta or withnoma (NOMA.c's resolver is another one)");
     if (ci_path && variant == PRACH_VARIANT_NOMA_C) die("--ci needs --program beta or withnoma (NOMA.c logs no trace of a UE's cycle start)");
     if (ci_path && (sj_path || tl_path || cdf_path)) die("--ci cannot be combined with --cdf, --timeline or --sojourn: one reduction per call");
     if (sj_path && variant == PRACH_VARIANT_NOMA_C) die("--sojourn needs --program beta or withnoma (NOMA.c logs no trace of a UE's cycle start)");
@@ -461,8 +490,13 @@ int main(int argc, char *argv[]) {
      * three numbers, per cell and twice per row */
     const reduction red_ = {cdf_path ? &cdf_spec : NULL, tl_path ? &tl_spec : NULL, sj_path ? &sj_spec : NULL, sj_path ? sj_path : tl_path ? tl_path : cdf_path,
                             sj_path ? 64 * ((size_t)sj_rows * ((size_t)sj_bins + 2) + 1) + 1
-                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1, NULL, NULL};
+                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1, NULL, NULL, NULL};
     reduction red_ci = red_;
+    /* the trace's bins cover maxTime */
+    const int tr_bins = (prach_max_time(&base) + tr_bin_ms - 1) / tr_bin_ms;
+    const prach_trace_spec tr_spec = {tr_bins, tr_bin_ms, npts, 0};
+    if (tr_path && tr_bins > PRACH_TRACE_MAX_BINS) die("--trace-bin MS: too many bins");
+    if (tr_path) { red_ci.tr = &tr_spec; red_ci.path = tr_path; red_ci.text_cap = 64 * (4 * (size_t)tr_bins + 1) + 1; } /* (a line: the label, a series name, two numbers) */
     if (ci_path) { /* --ci: the rows of the whole grid, filled by the workers */
         red_ci.sm = &ci_spec;
         red_ci.sm_rows = (prach_trial_summary *)mmap(NULL, sizeof(prach_trial_summary) * (size_t)ntr, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);

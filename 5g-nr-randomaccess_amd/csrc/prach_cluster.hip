@@ -62,7 +62,8 @@ constexpr int SCAPC = 2048;  // singleton callers per subframe held in LDS
 constexpr int DEADW = 512;   // dead-group bitmap words (16384 local groups): one run of DEADW / NW words per wavefront, see dead_skip
 
 enum { C_NSUCC = 0, C_COLL, C_TXOP, C_CONTF, C_NS, C_NRC, C_NRJ, C_STATUS, C_NEV, C_NCAND, C_OVF, C_NSUCCTOT, C_NTOT,
-       C_PTC, C_FC, C_SUMT = 16, C_ND = 18, C_NCROSS = 20, C_GTOT = 21, C_QN = 22, C_QEND = 23, C_VISITS = 24, C_EVENTS = 25, C_SX = 27 };
+       C_PTC, C_FC, C_SUMT = 16, C_ND = 18, C_NCROSS = 20, C_GTOT = 21, C_QN = 22, C_QEND = 23, C_VISITS = 24, C_EVENTS = 25, C_SX = 27,
+       C_CALLS = 28 /* preambleCollision calls so far */, C_TRACE = 29 /* 1: this workgroup writes the trial's trace rows */, C_TRPREV = 30 /* [3] calls, txop, collisions as the previous row left them */ };
 
 struct CLds {
     int2 *gev;    // [EVCAPC] gathered events of all workgroups
@@ -736,7 +737,7 @@ __global__ __launch_bounds__(WG_THREADS, 4) void cluster_kernel(const TrialDev *
         L.total[k] = 0; L.fcall[k] = INT_MAX; L.lcall[k] = -1; L.fcall[NPC + k] = INT_MAX; L.lcall[NPC + k] = -1;
         L.nlv[k] = 0; L.fie[k] = 0;
     }
-    if (tid < 64) L.scal[tid] = tid == C_QEND ? QCAP : 0;
+    if (tid < 64) L.scal[tid] = tid == C_QEND ? QCAP : tid == C_TRACE ? (P.trace != nullptr && b == 0) : 0;
     for (int k = tid; k < DEADW; k += WG_THREADS) L.dead[k] = 0;
     if (GLIBC) for (int k = tid; k < GSCAP; k += WG_THREADS) { L.gsum[k] = 0; L.gpre[k] = 0; }
     __syncthreads();
@@ -1023,7 +1024,8 @@ __global__ __launch_bounds__(WG_THREADS, 4) void cluster_kernel(const TrialDev *
 #endif
         // every call: scan count `check` (Beta.c:321-330), counters (Beta.c:334,349-351 / WithNOMA:650-652)
         const int nrj = L.scal[C_NRJ];
-        int my_coll = 0, my_txop = 0;
+        const int tracing = L.scal[C_TRACE]; // (read next to nrj: the calls are counted by the workgroup that writes a trace call's rows only)
+        int my_coll = 0, my_txop = 0, my_calls = 0;
         for (int k = tid; k < N + nP; k += WG_THREADS) {
             int idx = 0, p = 0, ispre = 0;
             bool caller = false;
@@ -1036,6 +1038,7 @@ __global__ __launch_bounds__(WG_THREADS, 4) void cluster_kernel(const TrialDev *
                 if (fcallA[p] != INT_MAX && !L.fie[p]) { caller = true; idx = fcallA[p]; ispre = 1; } // a STAY pre-member calls first
             }
             if (!caller) continue;
+            my_calls += 1;
             const bool first = idx == fcallA[p];
             int rj = 0;
             if (nrj > 0) { // Msg3-timeout re-entries that stayed matched since the previous call on this bucket (rare)
@@ -1064,11 +1067,24 @@ __global__ __launch_bounds__(WG_THREADS, 4) void cluster_kernel(const TrialDev *
         }
         my_coll = wave_sum(my_coll); my_txop = wave_sum(my_txop);
         if ((tid & 63) == 0) { if (my_coll) atomicAdd(&L.scal[C_COLL], my_coll); if (my_txop) atomicAdd(&L.scal[C_TXOP], my_txop); }
+        if (tracing) {
+            my_calls = wave_sum(my_calls);
+            if ((tid & 63) == 0 && my_calls) atomicAdd(&L.scal[C_CALLS], my_calls);
+        }
         FSTAMP(11); // calls
         __syncthreads(); // S5: calls done; singles listed
         FSTAMP(12); // S5
         STAMP(6);
         const int ns = L.scal[C_NS];
+        if (tid == 0 && tracing) { // prach_run_trials_trace: the subframe's row (the counters move again behind the next subframe's barriers)
+            const int c = L.scal[C_CALLS], x = L.scal[C_TXOP], q = L.scal[C_COLL];
+            if (c != L.scal[C_TRPREV]) {
+                v4i_t row;
+                row.x = c - L.scal[C_TRPREV]; row.y = ns; row.z = x - L.scal[C_TRPREV + 1]; row.w = q - L.scal[C_TRPREV + 2];
+                P.trace[t] = row;
+                L.scal[C_TRPREV] = c; L.scal[C_TRPREV + 1] = x; L.scal[C_TRPREV + 2] = q;
+            }
+        }
         if (ns > SCAPC) { status = PRACH_ERR_INTERNAL; time_exit = t; break; }
         const int Gr = max(0, P.nGrantUL - 1 - grantCheck); // Beta.c:336-347
         if (Gr > 0 && ns > 0 && ns <= 64) {

@@ -91,6 +91,10 @@ struct TrialDev {
     int *qov;                    // [nUE] early-leaver candidates of a subframe beyond their LDS part
     int2 *evov;                  // [2 nUE] the resolver's event list of a subframe beyond its LDS part
     unsigned long long *diag;    // diagnostic build (PRACH_STAMPS) only: [CLUSTER_MAX_G][32] per-workgroup phase stamps of a cluster trial; else null
+    // prach_run_trials_trace only (else null): [maxTime] one row per subframe, zeroed before the launch — x preambleCollision calls, y the calls with
+    // check == 1, z what the subframe added to totalPreambleTxop, w what it added to collisionPreambles.  Written by ONE lane behind the barrier that closes
+    // the subframe's calls (cluster_kernel: by the workgroup that writes DevResult; batch_kernel; trial_kernel), only where a call was made
+    int4 *trace;
 };
 
 constexpr int WG_THREADS = 1024;
@@ -219,5 +223,18 @@ struct SummaryLevels { int nq; int permille[PRACH_SUMMARY_MAX_Q]; };
 // threads: 512 or 1024; sched_cap: schedule entries staged in LDS (the longest schedule of the jobs, cut to summary_sched_cap())
 int summary_sched_cap();
 hipError_t launch_summary_kernel(const TimelineJob *jobs, int njobs, SummaryLevels levels, int threads, int sched_cap, unsigned long long *rows, hipStream_t stream);
+
+// prach_trace.hip: the per-subframe preamble trace of a launch's accepted trials (prach_run_trials_trace).  One job per trial: the rows the simulation kernel
+// wrote through TrialDev::trace, for the subframes [0, steps).  A workgroup reduces one tile of TR_TILE consecutive subframes of one trial, 16 bytes per lane
+// and load.  A tile covers at most TR_TILE consecutive bins (bin = t / bin_ms): scheme 1 adds them up in an LDS window of 64-bit counters anchored at the
+// tile's first bin and flushes the non-zero ones, scheme 0 sends every contribution straight to the call's buffers; both with 64-bit agent-scope atomics.
+constexpr int TR_TILE = 2048, TR_THREADS = 256;
+constexpr int TR_SCALARS = 8; // per group: subframes, calls, singles, txop, collisions, overflow_calls, calls_max + 1 (0: no subframe), 1 spare
+struct TraceJob {
+    const int4 *rows; // [steps] calls, singles, txop, collisions of every subframe
+    int steps, group, wg0, pad; // wg0: the first workgroup of this job
+};
+struct TraceOut { unsigned long long *calls, *singles, *txop, *collisions, *scalars; }; // [ngroups][bins] each, [ngroups][TR_SCALARS]
+hipError_t launch_trace_kernel(const TraceJob *jobs, int njobs, int workgroups, int bins, int bin_ms, int scheme, TraceOut out, hipStream_t stream);
 
 } // namespace prach

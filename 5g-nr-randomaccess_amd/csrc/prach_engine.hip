@@ -41,15 +41,16 @@ struct prach_engine {
     std::vector<std::pair<hipMemGenericAllocationHandle_t, size_t>> vmm_parts;
     char *pinned = nullptr; // host staging mirror of the head of the arena (parameter blocks, arrival tables, stream seeds, results)
     size_t pinned_cap = 0;
-    // The device reduction of a call (prach_run_trials_dist, prach_run_trials_timeline or prach_run_trials_sojourn: a call runs at most one, so all kinds share these): the call's
+    // The device reduction of a call (prach_run_trials_dist, _timeline, _sojourn, _summary or _trace: a call runs at most one, so all kinds share these): the call's
     // counters (zeroed once per call, copied out once at its end — not part of the arena, which is laid out again for every launch), the job table of one
-    // launch, pinned and on the device, in bytes (DistJob or TimelineJob elements), and the events around the reduction kernel of a launch
+    // launch, pinned and on the device, in bytes (DistJob, TimelineJob or TraceJob elements), and the events around the reduction kernel of a launch
     // (prach_timing.dist_ms / timeline_ms / sojourn_ms).  All created and grown at the start of a call, never per launch.
     char *red_buf = nullptr;
     size_t red_cap = 0;
     char *red_jobs_h = nullptr, *red_jobs_d = nullptr;
     size_t red_jobs_cap = 0;
     hipEvent_t red_ev0 = nullptr, red_ev1 = nullptr;
+    int64_t opt_trace_scheme = 1;    // trace_kernel's binning (prach_trace.hip): 0 global atomics only, 1 the tile's bins added up in an LDS window first
     int64_t opt_summary_threads = 1024; // summary_kernel's workgroup (prach_summary.hip): 512 or 1024 threads, one workgroup per trial
     int64_t opt_sojourn_scheme = 1;  // sojourn_kernel's binning (prach_sojourn.hip): 0 global atomics only, 1 rows of the histogram privatised in LDS
     int64_t opt_timeline_scheme = 1; // timeline_kernel's binning (prach_timeline.hip): 0 global atomics only, 1 windows of bins privatised in LDS (measured faster: DESIGN.md 4)
@@ -87,6 +88,7 @@ size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 struct TrialLayout {
     size_t rec, ptc, ftt, stt, fcnt, nd, evbuf, evbuf2, sidx, sched, stream, logs, timers, out, mbox, cand;
+    size_t trace; // prach_run_trials_trace: one 16-byte row per subframe, in the zeroed region (0: none)
     size_t n_pre0, n_sector, n_gain, n_lgain, n_nd0, sector;
     size_t rec32, chunks, ctab, cpool, jcal, qov, evov; // batch kernel
     int calcap, calslots, npool, tcap;
@@ -122,7 +124,8 @@ size_t mbox_bytes(const prach_cfg &c, int G, int &evw, int &mbstride) {
 
 // stream_len[k]: glibc draw-stream window of trial k (0 in Philox mode); G: workgroups per trial (0 = trial_kernel)
 // all_logs: every trial gets a device log region (the call's reduction reads it there: prach_run_trials_timeline, prach_run_trials_sojourn), not only the ones whose log the host asked for
-LaunchLayout layout_launch(const prach_cfg *cfgs, const int *idx, int m, prach_ue_log *const *ue_logs, bool all_logs, const std::vector<size_t> &stream_len, int G, bool batch, bool full_calendars, int64_t calendar_cap) {
+// trace: every trial gets its per-subframe rows (prach_run_trials_trace): 16 bytes x maxTime, zeroed with the rest of the zeroed region
+LaunchLayout layout_launch(const prach_cfg *cfgs, const int *idx, int m, prach_ue_log *const *ue_logs, bool all_logs, bool trace, const std::vector<size_t> &stream_len, int G, bool batch, bool full_calendars, int64_t calendar_cap) {
     LaunchLayout L;
     L.t.resize(m);
     size_t o = align_up(sizeof(TrialDev) * (size_t)m, 256);
@@ -151,6 +154,7 @@ LaunchLayout layout_launch(const prach_cfg *cfgs, const int *idx, int m, prach_u
 #else
         L.t[k].diag = 0;
 #endif
+        L.t[k].trace = trace ? take(16 * (size_t)prach_max_time(&cfgs[idx[k]])) : 0;
     }
     if (cfgs[idx[0]].variant == PRACH_VARIANT_NOMA_C) L.act_flags = take(4 * (2 + 2 * (size_t)NOMA_ACT_FLAG_CAP));
     L.zero_end = o;
@@ -419,7 +423,8 @@ static int noma_device_activation(prach_engine *e, const TrialDev *dparams, cons
 // delay_hist, ptc_hist; timeline: the five series arrivals, success, sojourn_sum, timer_sum, done; sojourn: hist, row_arrived, row_delay_overflow), then the
 // scalars the kernel keeps per group.  prach_run_trials_summary is the fourth kind: every trial is its own group and the only part is the kernel's row of
 // SM_WORDS words per trial, unpacked into the caller's prach_trial_summary rows.
-enum class Red { dist, timeline, sojourn, summary };
+// prach_run_trials_trace is the fifth: the four series calls, singles, txop, collisions, reduced from the rows the simulation kernels write per subframe.
+enum class Red { dist, timeline, sojourn, summary, trace };
 constexpr int RED_MAX_PARTS = 6;
 struct Reduction {
     Red kind;
@@ -434,10 +439,13 @@ struct Reduction {
     uint64_t *out[RED_MAX_PARTS - 1]; // the caller's arrays, one per part in front of the scalars
     const prach_summary_spec *mspec;  // summary
     prach_trial_summary *rows;
+    const prach_trace_spec *rspec;    // trace
+    prach_trace *tr;
 };
 // words per group of every part; returns their number
 static int red_parts(const Reduction &r, size_t words[RED_MAX_PARTS]) {
     if (r.kind == Red::summary) { words[0] = SM_WORDS; return 1; }
+    if (r.kind == Red::trace) { for (int q = 0; q < 4; q++) words[q] = (size_t)r.rspec->bins; words[4] = TR_SCALARS; return 5; }
     if (r.kind == Red::dist) { words[0] = (size_t)r.dspec->delay_bins; words[1] = PRACH_DIST_PTC_BINS; words[2] = DIST_SCALARS; return 3; }
     if (r.kind == Red::sojourn) {
         words[0] = (size_t)r.sspec->arrival_bins * (size_t)r.sspec->delay_bins; words[1] = words[2] = (size_t)r.sspec->arrival_bins; words[3] = SJ_SCALARS;
@@ -447,7 +455,7 @@ static int red_parts(const Reduction &r, size_t words[RED_MAX_PARTS]) {
     words[5] = TL_SCALARS;
     return 6;
 }
-static size_t red_job_bytes(Red kind) { return kind == Red::dist ? sizeof(DistJob) : sizeof(TimelineJob); } // (sojourn and summary take the timeline's jobs)
+static size_t red_job_bytes(Red kind) { return kind == Red::dist ? sizeof(DistJob) : kind == Red::trace ? sizeof(TraceJob) : sizeof(TimelineJob); } // (sojourn and summary take the timeline's jobs)
 
 // What one prach_run_trials call carries from launch to launch
 struct CallCtx {
@@ -462,7 +470,8 @@ struct CallCtx {
     unsigned long long *d_part[RED_MAX_PARTS] = {}; // the call's device buffer, part by part (red_parts)
     std::vector<uint64_t> trials, ues;        // per group, counted on the host as launches are accepted
     int group_of(int k) const { return red->group ? red->group[k] : k; }
-    bool reads_device_logs() const { return red && red->kind != Red::dist; }
+    bool reads_device_logs() const { return red && red->kind != Red::dist && red->kind != Red::trace; }
+    bool traces() const { return red && red->kind == Red::trace; }
     // dist only: NOMA.c in the reference's stream finishes on the host: its groups' accumulators (sized on first use)
     const prach_dist_spec *dist_spec() const { return red && red->kind == Red::dist ? red->dspec : nullptr; }
     std::vector<prach_dist> host_d;
@@ -597,7 +606,7 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
         if ((cfgs[idx[k]].flags & PRACH_FLAG_SECTOR_GRANTS) && G > 0 && !batch) return PRACH_ERR_INTERNAL;
     // NOMA.c's activeUE table: built by the device (noma_activation_kernel) unless the option or a rerun asks for the host's libm
     const bool host_act = noma && (e->opt_noma_host_activation || o.host_act);
-    const LaunchLayout LL = layout_launch(cfgs, idx, m, cx.ue_logs, cx.reads_device_logs(), slen, G, batch, o.full_calendars, e->opt_calendar_cap);
+    const LaunchLayout LL = layout_launch(cfgs, idx, m, cx.ue_logs, cx.reads_device_logs(), cx.traces(), slen, G, batch, o.full_calendars, e->opt_calendar_cap);
     if (LL.end > e->mem_budget && m > 1) { // (e.g. the 10 000-trial grid with its calendars on ONE GPU: two or three launches instead of one)
         const int h = m / 2;
         int rc = run_group(e, cx, idx, h, attempt, G, o, cal_overflow);
@@ -650,6 +659,7 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
         d.flags = c.flags;
         d.diag = L.diag ? reinterpret_cast<unsigned long long *>(A + L.diag) : nullptr;
         d.sector = L.sector ? reinterpret_cast<int *>(A + L.sector) : nullptr;
+        d.trace = L.trace ? reinterpret_cast<int4 *>(A + L.trace) : nullptr;
         int32_t *sched = reinterpret_cast<int32_t *>(H + L.sched);
         // the arrival table depends on (nUE, traffic law, accessTime) only: a sweep x seeds batch has a handful of distinct ones
         // (2000 pow() calls each) — copy the previous trial's table when its key is the same
@@ -768,7 +778,8 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
     bool red_launched = false;
     if (cx.red) {
         const Reduction &R = *cx.red;
-        const bool tl = R.kind != Red::dist; // (the jobs and the tile of the timeline are the sojourn's too; the summary takes the jobs, and one workgroup per job)
+        const bool trc = R.kind == Red::trace;
+        const bool tl = R.kind != Red::dist && !trc; // (the jobs and the tile of the timeline are the sojourn's too; the summary takes the jobs, and one workgroup per job)
         int njobs = 0, wgs = 0, max_slots = 0;
         for (int k = 0; k < m; k++) {
             const DevResult &dr = drs[k];
@@ -776,6 +787,14 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
             const prach_cfg &c = cfgs[idx[k]];
             const TrialLayout &L = LL.t[k];
             const int g = cx.group_of(idx[k]);
+            if (trc) { // the rows of the subframes [0, steps): what this launch's kernel wrote for the trial, and the zeros behind time_exit are never read
+                const int steps = (int)std::min<unsigned long long>(dr.steps, (unsigned long long)prach_max_time(&c));
+                reinterpret_cast<TraceJob *>(e->red_jobs_h)[njobs++] = TraceJob{reinterpret_cast<const int4 *>(A + L.trace), steps, g, wgs, 0};
+                wgs += (steps + TR_TILE - 1) / TR_TILE;
+                cx.trials[(size_t)g]++;
+                cx.ues[(size_t)g] += (uint64_t)c.nUE;
+                continue;
+            }
             if (tl) {
                 const int nslots = (prach_max_time(&c) + c.accessTime - 1) / c.accessTime; // (what prach_arrival_schedule fills; the table has one entry more)
                 max_slots = std::max(max_slots, nslots);
@@ -787,11 +806,12 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
             cx.trials[(size_t)g]++;
             cx.ues[(size_t)g] += (uint64_t)c.nUE;
         }
-        if (njobs > 0) {
+        if (njobs > 0 && wgs > 0) {
             unsigned long long *const *const d = cx.d_part;
             HIPCHK(hipMemcpyAsync(e->red_jobs_d, e->red_jobs_h, red_job_bytes(R.kind) * (size_t)njobs, hipMemcpyHostToDevice, e->stream));
             HIPCHK(hipEventRecord(e->red_ev0, e->stream));
-            if (R.kind == Red::summary) {
+            if (trc) HIPCHK(launch_trace_kernel(reinterpret_cast<const TraceJob *>(e->red_jobs_d), njobs, wgs, R.rspec->bins, R.rspec->bin_ms, (int)e->opt_trace_scheme, TraceOut{d[0], d[1], d[2], d[3], d[4]}, e->stream));
+            else if (R.kind == Red::summary) {
                 SummaryLevels lv{};
                 lv.nq = R.mspec->nq;
                 for (int l = 0; l < lv.nq; l++) lv.permille[l] = R.mspec->permille[l];
@@ -1037,7 +1057,11 @@ static int reduction_end(prach_engine *e, CallCtx &cx) {
     }
     for (size_t g = 0; g < ng; g++) {
         const unsigned long long *const q = &sc[g * nsc];
-        if (R.kind == Red::dist) {
+        if (R.kind == Red::trace) {
+            prach_trace &t = R.tr[g];
+            t.trials = cx.trials[g]; t.subframes = q[0]; t.calls = q[1]; t.singles = q[2]; t.txop = q[3]; t.collisions = q[4]; t.overflow_calls = q[5];
+            t.calls_max = (int64_t)q[6] - 1;
+        } else if (R.kind == Red::dist) {
             const prach_dist_spec &s = *R.dspec;
             prach_dist &d = R.dist[g];
             d.trials = cx.trials[g]; d.ues = cx.ues[g]; d.success = q[0]; d.delay_overflow = q[1]; d.delay_sum = q[2]; d.ptc_sum = q[3];
@@ -1078,7 +1102,8 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
                 row.nUE = cfgs[g].nUE;
                 row.sojourn_max = row.timer_max = row.ptc_max = -1;
                 std::memset(row.q, 0xff, sizeof(row.q)); // -1
-            } else if (red->kind == Red::dist) { red->dist[g] = prach_dist{}; red->dist[g].delay_max = -1; }
+            } else if (red->kind == Red::trace) { red->tr[g] = prach_trace{}; red->tr[g].calls_max = -1; }
+            else if (red->kind == Red::dist) { red->dist[g] = prach_dist{}; red->dist[g].delay_max = -1; }
             else if (red->kind == Red::sojourn) { red->sj[g] = prach_sojourn{}; red->sj[g].sojourn_max = -1; }
             else { red->tl[g] = prach_timeline{}; red->tl[g].done_max = -1; }
         }
@@ -1092,6 +1117,9 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
     auto t0 = std::chrono::steady_clock::now();
     e->last = prach_timing{};
     CallCtx cx{cfgs, results, ue_logs};
+    // a trace call takes the paths that "fast" = 0 takes: prach::lcluster_kernel writes no rows (its source and its speed stay what they are)
+    struct FastOff { prach_engine *e; int64_t was; ~FastOff() { e->opt_fast = was; } } fast_off{e, e->opt_fast};
+    if (red && red->kind == Red::trace) e->opt_fast = 0;
     if (red) {
         cx.red = red;
         int rc = reduction_begin(e, cx, n);
@@ -1245,7 +1273,7 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
     e->last.updates = upd;
     if (red) {
         int rc = reduction_end(e, cx);
-        (red->kind == Red::dist ? e->last.dist_ms : red->kind == Red::timeline ? e->last.timeline_ms : red->kind == Red::sojourn ? e->last.sojourn_ms : e->last.summary_ms) = cx.red_ms;
+        (red->kind == Red::dist ? e->last.dist_ms : red->kind == Red::timeline ? e->last.timeline_ms : red->kind == Red::sojourn ? e->last.sojourn_ms : red->kind == Red::trace ? e->last.trace_ms : e->last.summary_ms) = cx.red_ms;
         if (rc != PRACH_OK) return rc;
     }
     e->last.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1312,6 +1340,7 @@ int prach_engine_set(prach_engine *e, const char *key, int64_t value) {
     if (std::strcmp(key, "dist_scheme") == 0) { if (value < 0 || value > 2) return PRACH_ERR_ARG; e->opt_dist_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "timeline_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_timeline_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "summary_threads") == 0) { if (value != 0 && value != 512 && value != 1024) return PRACH_ERR_ARG; e->opt_summary_threads = value ? value : 1024; return PRACH_OK; }
+    if (std::strcmp(key, "trace_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_trace_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "sojourn_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_sojourn_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "xcd_pack") == 0) { e->opt_xcd_pack = value != 0; return PRACH_OK; }
     return PRACH_ERR_ARG;
@@ -1448,6 +1477,23 @@ int prach_run_trials_summary(prach_engine *e, const prach_cfg *cfgs, int n, prac
     red.rows = rows;
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
+
+int prach_run_trials_trace(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_trace_spec *spec,
+                           const int32_t *group, prach_trace *tr, uint64_t *calls, uint64_t *singles, uint64_t *txop, uint64_t *collisions) {
+    // (spec, groups and variants are judged first: what they ask for does not depend on a device)
+    if (!cfgs || !results || n <= 0 || !spec || !tr || !calls || !singles || !txop || !collisions) return PRACH_ERR_ARG;
+    if (spec->bins < 1 || spec->bins > PRACH_TRACE_MAX_BINS || spec->bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
+    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
+    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c's resolver is another one: include/prach.h)
+    if (4 * (uint64_t)spec->ngroups * (uint64_t)spec->bins > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
+    if (!e) return PRACH_ERR_ARG;
+    Reduction red{Red::trace, group, spec->ngroups, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {calls, singles, txop, collisions}};
+    red.rspec = spec;
+    red.tr = tr;
+    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
+}
+
+int prach_trace_tile_subframes(void) { return TR_TILE; }
 
 int prach_sojourn_tile_ues(void) { return TL_TILE; }
 int prach_sojourn_window_words(void) { return SJ_WINDOW_WORDS; }

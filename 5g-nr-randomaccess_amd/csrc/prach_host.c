@@ -739,6 +739,35 @@ size_t prach_timeline_format_csv(const prach_timeline_spec *s, const prach_timel
     return csv_end(buf, cap, off);
 }
 
+/* ---- per-subframe preamble traces per trial group (prach_run_trials_trace) ----------------------- */
+
+static int trace_spec_ok(const prach_trace_spec *s) {
+    return s && s->bins >= 1 && s->bins <= PRACH_TRACE_MAX_BINS && s->bin_ms >= 1;
+}
+
+void prach_trace_merge(const prach_trace_spec *s, prach_trace *into, uint64_t *const into_series[4], const prach_trace *from, const uint64_t *const from_series[4]) {
+    if (!trace_spec_ok(s) || !into || !into_series || !from || !from_series) return;
+    for (int q = 0; q < 4; q++) if (!into_series[q] || !from_series[q]) return;
+    const int64_t a = into->subframes ? into->calls_max : -1, b = from->subframes ? from->calls_max : -1;
+    into->trials += from->trials; into->subframes += from->subframes; into->calls += from->calls; into->singles += from->singles; into->txop += from->txop;
+    into->collisions += from->collisions; into->overflow_calls += from->overflow_calls;
+    into->calls_max = a > b ? a : b;
+    for (int q = 0; q < 4; q++)
+        for (int i = 0; i < s->bins; i++) into_series[q][i] += from_series[q][i];
+}
+
+size_t prach_trace_format_csv(const prach_trace_spec *s, const prach_trace *t, const uint64_t *const series[4], const char *label, char *buf, size_t cap) {
+    static const char *const names[4] = {"calls", "singles", "txop", "collisions"};
+    if (!trace_spec_ok(s) || !t || !series || !label) return 0;
+    for (int q = 0; q < 4; q++) if (!series[q]) return 0;
+    size_t off = 0;
+    for (int q = 0; q < 4; q++)
+        for (int b = 0; b < s->bins; b++)
+            if (series[q][b]) CSV_EMIT("%.200s,%s,%lld,%llu\n", label, names[q], (long long)b * s->bin_ms, (unsigned long long)series[q][b]);
+    if (t->overflow_calls) CSV_EMIT("%.200s,calls,overflow,%llu\n", label, (unsigned long long)t->overflow_calls);
+    return csv_end(buf, cap, off);
+}
+
 /* ---- sojourn histograms by arrival row per trial group (prach_run_trials_sojourn) ---------------- */
 
 static int sojourn_spec_ok(const prach_sojourn_spec *s) {

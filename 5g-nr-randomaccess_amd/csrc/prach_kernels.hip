@@ -50,7 +50,8 @@ struct Lds {
 };
 enum { S_NSUCC = 0, S_COLL, S_TXOP, S_CONTF, S_FINS, S_NS, S_NRC, S_NPOST, S_STATUS, S_PTC, S_FC, S_ND_LO,
        S_SUMT_LO = 16 /* 64-bit at [16,17] */, S_ND64 = 18 /* 64-bit at [18,19] */,
-       S_SGC = 24 /* [24,30): sectorGrants[6], WithNOMA:260 */, S_SGN = 32 /* [32,38): singleton callers of this subframe per sector */ };
+       S_SGC = 24 /* [24,30): sectorGrants[6], WithNOMA:260 */, S_SGN = 32 /* [32,38): singleton callers of this subframe per sector */,
+       S_CALLS = 40 /* preambleCollision calls so far (read by the trace row only) */ };
 
 __device__ __forceinline__ Lds carve(char *smem, int nP) {
     Lds L;
@@ -317,6 +318,7 @@ __device__ __forceinline__ void resolve(const TrialG &P, const Lds &L, const int
             if (sm != INT_MAX && sm == L.fcall[p]) { caller = true; idx = sm; le = L.gsmle[p]; }
         }
         if (!caller) continue;
+        atomicAdd(&L.scal[S_CALLS], 1);
         const bool first = idx == L.fcall[p];
         int post = 0;
         if (npost > 0) { // members that stayed matched after their own turn (passive / Msg3 re-entry): rare
@@ -413,6 +415,7 @@ __global__ __launch_bounds__(WG_THREADS) void trial_kernel(const TrialDev *__res
     unsigned long long base = 0; // glibc: draws consumed so far (relative to the stream window)
     unsigned long long steps = 0;
     int status = PRACH_OK;
+    int tr_calls = 0, tr_txop = 0, tr_coll = 0; // (thread 0, trace calls: the counters as the previous subframe left them)
 
     for (int t = 0; t < P.stop; t++) {
         steps++;
@@ -448,6 +451,11 @@ __global__ __launch_bounds__(WG_THREADS) void trial_kernel(const TrialDev *__res
             ue_pass<0, false>(P, L, t, prevAC, activeCheck, 0);
         }
         resolve(P, L, activeCheck, grantCheck);
+        if (P.trace && tid == 0) { // the subframe's row (resolve ends behind a barrier; the counters move again behind the next subframe's)
+            const int c = L.scal[S_CALLS], x = L.scal[S_TXOP], q = L.scal[S_COLL];
+            if (c != tr_calls) { v4i_t row; row.x = c - tr_calls; row.y = L.scal[S_NS]; row.z = x - tr_txop; row.w = q - tr_coll; P.trace[t] = row; }
+            tr_calls = c; tr_txop = x; tr_coll = q;
+        }
         if (L.scal[S_NSUCC] == nUE) { time_exit = t; break; } // Beta.c:180 (loop variable not advanced)
     }
     __syncthreads();

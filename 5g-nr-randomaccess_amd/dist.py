@@ -118,6 +118,14 @@ def allreduce_sojourn(sj, device=None):
     return sj
 
 
+def allreduce_trace(tr, device=None):
+    """Merges the per-subframe preamble traces (a `Trace` of the package: same groups, bins and width on every rank) across ranks, in place: ONE int64 sum
+    all-reduce of the concatenated block — the four series and the summed scalars — and calls_max by a max all-reduce of ngroups values."""
+    from . import TRACE_FIELDS
+    _allreduce_sums_and_max(tr._arrays() + [tr.scalars[f] for f in TRACE_FIELDS if f != "calls_max"], tr.scalars["calls_max"], device)
+    return tr
+
+
 ROW_BYTES = 256  # a row = trial index (8 bytes) + kind (1) + payload length (2) + up to ROW_PAYLOAD bytes of text
 ROW_PAYLOAD = ROW_BYTES - 11  # (Beta.c's six-line Results.txt is ~45 bytes, RandomAccessWithNOMA's eight lines ~115 at nUE = 100 000)
 

@@ -46,6 +46,10 @@ def main(argv=None):
                     "and restart ratio, mean sojourn / timer / preamble transmissions and their exact per-trial percentiles — to this CSV file (not together "
                     "with --cdf, --timeline or --sojourn)")
     ap.add_argument("--ci-levels", default="500,950,990", help="percentile levels in permille, at most 8")
+    ap.add_argument("--trace", default=None, help="write the per-subframe preamble trace — preambles used (calls), decoded (singles), and what the programs add to "
+                    "totalPreambleTxop and collisionPreambles, by time — one group per sweep point, to this CSV file (not together with --cdf, --timeline, "
+                    "--sojourn or --ci)")
+    ap.add_argument("--trace-bin", type=int, default=5, help="width of a trace bin in ms; the bins cover the horizon")
     ap.add_argument("--same-device", action="store_true", help="rehearsal on one GPU: every rank uses cuda:0")
     args = ap.parse_args(argv)
     if args.cdf and args.timeline:
@@ -54,6 +58,8 @@ def main(argv=None):
         ap.error("--sojourn cannot be combined with --cdf or --timeline: one reduction per call")
     if args.ci and (args.cdf or args.timeline or args.sojourn):
         ap.error("--ci cannot be combined with --cdf, --timeline or --sojourn: one reduction per call")
+    if args.trace and (args.cdf or args.timeline or args.sojourn or args.ci):
+        ap.error("--trace cannot be combined with --cdf, --timeline, --sojourn or --ci: one reduction per call")
     ci_levels = [int(x) for x in args.ci_levels.split(",")]
     if not 1 <= len(ci_levels) <= 8 or any(m < 1 or m > 1000 for m in ci_levels):
         ap.error("--ci-levels takes 1 to 8 levels between 1 and 1000")
@@ -97,6 +103,9 @@ def main(argv=None):
     elif args.sojourn:
         sj = (-(-10000 // args.sojourn_arrival_ms), args.sojourn_arrival_ms, -(-(10000 + 6) // args.sojourn_bin), args.sojourn_bin)
         red = (pkg.Sojourn(len(points), *sj), eng.run_trials_sojourn, sj, distmod.allreduce_sojourn, pkg.sojourn_csv, args.sojourn)
+    elif args.trace:
+        tr_bins = -(-10000 // args.trace_bin)  # Beta arrivals: 10 000 subframes
+        red = (pkg.Trace(len(points), tr_bins, args.trace_bin), eng.run_trials_trace, (tr_bins, args.trace_bin), distmod.allreduce_trace, pkg.trace_csv, args.trace)
     ci_rows = []
     for a in range(0, len(mine), CH):
         part = mine[a:a + CH]

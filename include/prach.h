@@ -129,6 +129,8 @@ typedef struct prach_timing {
     int32_t trial_kernel_reruns; /* of fallback_trials: trials that were (also) rerun on the one-workgroup, index-ordered trial_kernel */
     int32_t noma_host_ues;       /* NOMA_C, Philox: UEs of the device-built activeUE table that the host recomputed with its libm (a value inside the
                                     device math library's error band of a rounding / comparison boundary: ~1e-6 of the UEs) */
+    double trace_ms;             /* HIP-event time of the trace kernel launches (prach_run_trials_trace) of the last call; 0 in every other call (a trace call leaves
+                                    summary_ms, dist_ms, timeline_ms and sojourn_ms 0) */
     double summary_ms;           /* HIP-event time of the summary kernel launches (prach_run_trials_summary) of the last call; 0 in every other call (a summary call
                                     leaves dist_ms, timeline_ms and sojourn_ms 0) */
     double dist_ms;              /* HIP-event time of the distribution kernel launches (prach_run_trials_dist) of the last call; 0 without a spec */
@@ -307,6 +309,48 @@ typedef struct prach_stat { uint64_t n; double mean, sd, sem, min, max; } prach_
 int prach_run_trials_summary(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs,
                              const prach_summary_spec *spec, prach_trial_summary *rows);
 
+/* Per-subframe preamble trace per trial group, recorded by the simulation kernels WHILE THEY RUN and reduced on the device: how many preambles were used,
+ * decoded and collided in each stretch of the simulation — the quantities TR 37.868's collision probability is defined on.  Unlike the four reductions above
+ * this is not a function of the per-UE state a trial leaves behind (prach_result has only the two whole-trial totals collisionPreambles and
+ * totalPreambleTxop), so there is no prach_trace_accumulate_logs: the logs do not hold it.  Per subframe t of a trial, in the reference's own terms:
+ *   calls       preambleCollision invocations (Beta.c:315 / WithNOMA:607): one per preamble that at least one matched UE transmits = preambles USED
+ *   singles     the calls with check == 1 = preambles DECODED; calls - singles = preambles COLLIDED.  These three mean the same in both programs
+ *   txop        what the subframe added to totalPreambleTxop   } as the programs count them, and they weight them differently: Beta.c adds 1 per call and 1
+ *   collisions  what the subframe added to collisionPreambles  } per collided call (Beta.c:334,349-351: txop = calls, collisions = calls - singles);
+ *               RandomAccessWithNOMA.c adds 1 per single and `check`, the number of UEs on the preamble, per collided call to both (WithNOMA:650-652)
+ * A trial's rows cover the subframes [0, steps); a subframe in which nothing was resolved is all zero.  Bin b covers [b * bin_ms, (b + 1) * bin_ms).  A
+ * subframe at or behind bins * bin_ms counts in the scalars and in no bin; its calls are in overflow_calls.  Summed over a trial, txop and collisions are
+ * the trial's prach_result.totalPreambleTxop and collisionPreambles.  Integers only: device, host, forked workers and ranks merge exactly in any order.
+ * Beta.c and RandomAccessWithNOMA.c only, in both RNG modes: NOMA.c's resolver is another one (a NOMA_C cfg is PRACH_ERR_UNSUPPORTED, before anything is
+ * launched).  A trace call runs the kernels engine option "fast" = 0 selects (prach::lcluster_kernel records nothing); results, logs and the other timing
+ * fields are those of the same prach_run_trials call. */
+#define PRACH_TRACE_MAX_BINS 65536         /* Uniform traffic at 1 ms: 60 000 bins */
+
+typedef struct prach_trace_spec {
+    int32_t bins;      /* 1 .. PRACH_TRACE_MAX_BINS */
+    int32_t bin_ms;    /* >= 1 */
+    int32_t ngroups;   /* number of output traces */
+    int32_t reserved;  /* 0 */
+} prach_trace_spec;
+
+typedef struct prach_trace {         /* one per group */
+    uint64_t trials;                 /* trials accumulated (status PRACH_OK) */
+    uint64_t subframes;              /* sum of their steps */
+    uint64_t calls, singles, txop, collisions; /* over all their subframes, unbinned */
+    uint64_t overflow_calls;         /* calls in subframes at or behind bins * bin_ms (in no bin) */
+    int64_t  calls_max;              /* the largest `calls` of one subframe of one trial; -1 without subframes */
+} prach_trace;
+
+/* prach_run_trials plus the traces, with the contract of prach_run_trials_timeline: trial k is added to group group[k] (group == NULL: trial k is group k and
+ * ngroups must equal n); tr[ngroups] and the four series [ngroups * bins] are caller-owned and OVERWRITTEN; a trial whose final status is not PRACH_OK
+ * contributes nothing; a trial the engine reruns contributes once, from the launch whose result is kept.  The simulation kernels write one 16-byte row per
+ * subframe ON THE DEVICE (the arena of the call grows by 16 bytes x maxTime per trial) and prach::trace_kernel (csrc/prach_trace.hip) reduces them there.
+ * PRACH_ERR_ARG: a NULL output, a bin count or width out of range, a group id out of range, NULL group with ngroups != n;
+ * PRACH_ERR_UNSUPPORTED: any NOMA_C cfg; 4 * ngroups * bins > 2^27 words (1 GiB of device buffer). */
+int prach_run_trials_trace(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs,
+                           const prach_trace_spec *spec, const int32_t *group, prach_trace *tr, uint64_t *calls, uint64_t *singles, uint64_t *txop,
+                           uint64_t *collisions);
+
 /* engine tunables; none changes a result, all are covered by parity tests:
  *   "cluster"       workgroups cooperating on one trial (1..64; 0 = auto)
  *   "stream_factor" glibc mode: initial draws-per-UE budget of the rand() stream window (0 = auto; it grows on demand)
@@ -329,6 +373,8 @@ int prach_run_trials_summary(prach_engine *, const prach_cfg *cfgs, int n, prach
  *                   (the default: measured 15-20x faster on the sweep grids)
  *   "sojourn_scheme" prach::sojourn_kernel's binning: 0 every contribution is a 64-bit agent-scope global atomic, 1 rows of the histogram privatised in LDS
  *                   per workgroup (the default: measured 95x faster on the sweep grids)
+ *   "trace_scheme"  prach::trace_kernel's binning: 0 every contribution is a 64-bit agent-scope global atomic, 1 a tile's bins added up in an LDS window first
+ *                   (the default)
  *   "summary_threads" prach::summary_kernel's workgroup: 512 or 1024 threads (0 = the default, 1024)
  *   "calendar_cap", "vmm_fail_after", "noma_ambiguity_test", "noma_host_activation"   test hooks (prach_engine.hip) */
 int prach_engine_set(prach_engine *, const char *key, int64_t value);
@@ -444,6 +490,16 @@ int prach_summary_stats(const prach_summary_spec *, const prach_trial_summary *r
  * length needed (without the terminating 0); the text is written only if it fits cap with its terminator. */
 size_t prach_summary_format_csv(const prach_summary_spec *, const prach_stat *stats_of_one_group, const char *label, char *buf, size_t cap);
 int prach_summary_max_value(void);    /* 65 535: the largest value prach::summary_kernel ranks */
+
+/* Traces, host side (no device needed).  t and the four series (calls, singles, txop, collisions): ONE group (`bins` entries each).  There is no
+ * prach_trace_accumulate_logs: a per-UE log does not hold what happened per subframe (the block above).
+ * counts and sums are added, calls_max is the maximum */
+void prach_trace_merge(const prach_trace_spec *, prach_trace *into, uint64_t *const into_series[4], const prach_trace *from, const uint64_t *const from_series[4]);
+/* one group as text: `label,<series>,<lower edge ms>,<value>` per non-zero bin, series by series (calls, singles, txop, collisions), then
+ * `label,calls,overflow,<count>` where overflow_calls is non-zero; lines end in \n.  Returns the length needed (without the terminating 0); the text is
+ * written only if it fits cap with its terminator. */
+size_t prach_trace_format_csv(const prach_trace_spec *, const prach_trace *, const uint64_t *const series[4], const char *label, char *buf, size_t cap);
+int prach_trace_tile_subframes(void); /* subframes of one trial that one workgroup of prach::trace_kernel reduces (tests place sizes around it) */
 
 /* Text surfaces, byte-compatible with the reference (latency values excepted) */
 size_t prach_format_logs(const prach_ue_log *ue, int nUE, char *buf, size_t cap);           /* Beta.c:501 */

@@ -1,0 +1,137 @@
+// tests/tools/gpu_trace_harness.hip — TEST INFRASTRUCTURE (GPU box): prach::trace_kernel launched directly, through launch_trace_kernel, on rows of this
+// program's own: per-subframe rows no trial writes.  One case and one launch per process; every trial's rows sit at a 256-byte-aligned device offset, as in
+// the engine's arena (the kernel's 16-byte loads rely on it).  The kernel's source file is compiled into this program as it is; no product entry point is
+// involved.  The reference is the plain host loop below: the definition the kernel's header comment names.
+//
+// usage: gpu_trace_harness CASE SCHEME      prints `case CASE scheme S workgroups W: ok` and exits 0, or the first differences and exits 1;
+//                                           2 / 3: a HIP error / a bad argument (message on stderr)
+//        gpu_trace_harness --cases          the case names, one per line (no device needed)
+//        gpu_trace_harness --constants      the kernel's compile-time constants, one "NAME value" per line (no device needed)
+#include "../../5g-nr-randomaccess_amd/csrc/prach_trace.hip"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+namespace {
+
+#define CHK(call)                                                                                            \
+    do {                                                                                                     \
+        const hipError_t rc_ = (call);                                                                       \
+        if (rc_ != hipSuccess) {                                                                             \
+            fprintf(stderr, "gpu_trace_harness: %s: %s (line %d)\n", #call, hipGetErrorString(rc_), __LINE__); \
+            return 2;                                                                                        \
+        }                                                                                                    \
+    } while (0)
+
+int fail(const char *what) {
+    fprintf(stderr, "gpu_trace_harness: %s\n", what);
+    return 3;
+}
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct Trial { int steps, group; std::vector<int> rows; }; // rows[steps][4]
+struct Case { const char *name; int bins, bin_ms, ngroups; std::vector<Trial> trials; };
+
+unsigned lcg(unsigned &s) { s = s * 1664525u + 1013904223u; return s >> 8; }
+
+// fill: 0 all zero, 1 every word 2^31 - 1 - (t % 3) (the 64-bit sums of a tile are exercised), 2 small counts with zero subframes in between
+Trial make_trial(int steps, int group, int fill, unsigned seed) {
+    Trial T{steps, group, std::vector<int>(4 * (size_t)steps, 0)};
+    for (int t = 0; t < steps; t++) {
+        int *const r = &T.rows[4 * (size_t)t];
+        if (fill == 1) { for (int q = 0; q < 4; q++) r[q] = 0x7fffffff - (t + q) % 3; }
+        else if (fill == 2 && lcg(seed) % 3) { const int c = 1 + (int)(lcg(seed) % 61), s = (int)(lcg(seed) % (unsigned)(c + 1)); r[0] = c; r[1] = s; r[2] = s + 2 * (c - s) + (int)(lcg(seed) % 7); r[3] = r[2] - s; }
+    }
+    return T;
+}
+
+std::vector<Case> all_cases() {
+    const int T = prach::TR_TILE;
+    std::vector<Case> cs;
+    cs.push_back({"huge_values_full_tile", T, 1, 1, {make_trial(T, 0, 1, 1)}});                                   // every lane of a tile near 2^31 - 1, one bin each
+    cs.push_back({"huge_values_one_bin", 4, 3 * T, 2, {make_trial(3 * T, 1, 1, 2), make_trial(T + 5, 1, 1, 3)}}); // ... and all of three tiles into ONE 64-bit bin
+    cs.push_back({"tile_minus_one", T, 1, 1, {make_trial(T - 1, 0, 2, 4)}});
+    cs.push_back({"tile_plus_one", T + 1, 1, 1, {make_trial(T + 1, 0, 2, 5)}});
+    cs.push_back({"tile_edges_bin7", (2 * T + 1 + 6) / 7, 7, 3, {make_trial(2 * T + 1, 2, 2, 6), make_trial(T - 1, 0, 2, 7), make_trial(1, 2, 2, 8), make_trial(T, 0, 1, 9)}});
+    cs.push_back({"bin_wider_than_row", 2, 100000, 2, {make_trial(777, 0, 2, 10), make_trial(3 * T + 3, 1, 2, 11)}});
+    cs.push_back({"all_zero", 100, 50, 2, {make_trial(2 * T + 9, 0, 0, 12), make_trial(5, 1, 0, 13)}});
+    cs.push_back({"overflow_behind_bins", 10, 100, 2, {make_trial(3 * T, 0, 2, 14), make_trial(999, 1, 2, 15), make_trial(1001, 1, 1, 16)}});
+    return cs;
+}
+
+} // namespace
+
+int main(int argc, char **argv) {
+    using namespace prach;
+    const std::vector<Case> cases = all_cases();
+    if (argc == 2 && !strcmp(argv[1], "--cases")) { for (const Case &c : cases) printf("%s\n", c.name); return 0; }
+    if (argc == 2 && !strcmp(argv[1], "--constants")) { printf("TR_TILE %d\nTR_THREADS %d\nTR_SCALARS %d\n", TR_TILE, TR_THREADS, TR_SCALARS); return 0; }
+    if (argc != 3) return fail("usage: gpu_trace_harness CASE SCHEME | --cases | --constants");
+    const Case *cp = nullptr;
+    for (const Case &c : cases) if (!strcmp(c.name, argv[1])) cp = &c;
+    if (!cp) return fail("no such case");
+    const Case &c = *cp;
+    const int scheme = atoi(argv[2]);
+    if (scheme < 0 || scheme > 1) return fail("scheme out of range");
+    if (c.bins < 1 || c.bins > PRACH_TRACE_MAX_BINS || c.bin_ms < 1 || c.ngroups < 1) return fail("case: spec out of range");
+
+    // ---- the reference: a plain host loop
+    const size_t ng = (size_t)c.ngroups, per = ng * (size_t)c.bins, out_words = 4 * per + ng * TR_SCALARS;
+    std::vector<unsigned long long> ref(out_words, 0);
+    for (const Trial &T : c.trials) {
+        if (T.group < 0 || T.group >= c.ngroups || T.steps < 1) return fail("case: trial out of range");
+        unsigned long long *const sc = &ref[4 * per + (size_t)T.group * TR_SCALARS];
+        sc[0] += (unsigned long long)T.steps;
+        for (int t = 0; t < T.steps; t++) {
+            const int *const r = &T.rows[4 * (size_t)t];
+            for (int q = 0; q < 4; q++) sc[1 + q] += (unsigned long long)(unsigned)r[q];
+            sc[6] = std::max(sc[6], (unsigned long long)(unsigned)r[0] + 1ull);
+            const long long b = (long long)t / c.bin_ms;
+            if (b >= c.bins) { sc[5] += (unsigned long long)(unsigned)r[0]; continue; }
+            for (int q = 0; q < 4; q++) ref[(size_t)q * per + (size_t)T.group * (size_t)c.bins + (size_t)b] += (unsigned long long)(unsigned)r[q];
+        }
+    }
+
+    // ---- device: arena (a pattern, never zeros, between the rows), job table, zeroed outputs; ONE launch
+    std::vector<size_t> at(c.trials.size());
+    size_t arena = 0;
+    int wgs = 0;
+    for (size_t j = 0; j < c.trials.size(); j++) { at[j] = arena; arena = align256(arena + 16 * (size_t)c.trials[j].steps) + 256; }
+    std::vector<unsigned char> stage(arena, 0xA5);
+    for (size_t j = 0; j < c.trials.size(); j++) memcpy(stage.data() + at[j], c.trials[j].rows.data(), 16 * (size_t)c.trials[j].steps);
+    unsigned char *A = nullptr;
+    CHK(hipMalloc(reinterpret_cast<void **>(&A), arena));
+    CHK(hipMemcpy(A, stage.data(), arena, hipMemcpyHostToDevice));
+    unsigned long long *O = nullptr;
+    CHK(hipMalloc(reinterpret_cast<void **>(&O), 8 * out_words));
+    CHK(hipMemset(O, 0, 8 * out_words));
+    std::vector<TraceJob> jobs(c.trials.size());
+    for (size_t j = 0; j < c.trials.size(); j++) {
+        jobs[j] = TraceJob{reinterpret_cast<const int4 *>(A + at[j]), c.trials[j].steps, c.trials[j].group, wgs, 0};
+        wgs += (c.trials[j].steps + TR_TILE - 1) / TR_TILE;
+    }
+    TraceJob *dj = nullptr;
+    CHK(hipMalloc(reinterpret_cast<void **>(&dj), sizeof(TraceJob) * jobs.size()));
+    CHK(hipMemcpy(dj, jobs.data(), sizeof(TraceJob) * jobs.size(), hipMemcpyHostToDevice));
+    CHK(launch_trace_kernel(dj, (int)jobs.size(), wgs, c.bins, c.bin_ms, scheme, TraceOut{O, O + per, O + 2 * per, O + 3 * per, O + 4 * per}, nullptr));
+    CHK(hipDeviceSynchronize());
+    std::vector<unsigned long long> got(out_words);
+    CHK(hipMemcpy(got.data(), O, 8 * out_words, hipMemcpyDeviceToHost));
+
+    static const char *const part[5] = {"calls", "singles", "txop", "collisions", "scalars"};
+    int nbad = 0;
+    for (size_t i = 0; i < out_words; i++) {
+        if (got[i] == ref[i]) continue;
+        if (nbad++ < 10) {
+            const size_t q = std::min<size_t>(i / per, 4), off = i - q * per;
+            printf("case %s scheme %d: %s[%zu] = %llu, the host loop has %llu\n", c.name, scheme, part[q], off, got[i], ref[i]);
+        }
+    }
+    if (nbad) { printf("case %s scheme %d: %d words differ\n", c.name, scheme, nbad); return 1; }
+    printf("case %s scheme %d workgroups %d: ok\n", c.name, scheme, wgs);
+    return 0;
+}
