@@ -54,7 +54,7 @@ class PrachTiming(C.Structure):
                 ("launches", C.c_int32), ("workgroups", C.c_int32), ("updates", C.c_uint64),
                 ("cluster_size", C.c_int32), ("resident_limit", C.c_int32), ("fallback_trials", C.c_int32), ("spin_timeouts", C.c_int32),
                 ("rec_mode", C.c_int32), ("xcd_packed", C.c_int32), ("group_visits", C.c_uint64), ("event_ues", C.c_uint64),
-                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
+                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("xtab_ms", C.c_double), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
                 ("sojourn_ms", C.c_double)]
 
 
@@ -349,6 +349,77 @@ class Summary:
         return out
 
 
+XTAB_SERVED, XTAB_UNSERVED, XTAB_IDLE = 1, 2, 4
+XTAB_WHO = {"served": XTAB_SERVED, "unserved": XTAB_UNSERVED, "arrived": XTAB_SERVED | XTAB_UNSERVED, "idle": XTAB_IDLE, "all": XTAB_SERVED | XTAB_UNSERVED | XTAB_IDLE}
+XTAB_FIELD_NAMES = ("one", "arrival", "sojourn", "completion", "timer", "ptc", "failcount", "age", "state")
+XTAB_MAX_BINS = 65536
+XTAB_FIELDS = ("trials", "ues", "idle", "served", "unserved", "selected", "binned", "undefined", "row_sum", "col_sum", "row_max", "col_max")
+
+
+class PrachXtabSpec(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("who", "row_field", "row_width", "row_bins", "col_field", "col_width", "col_bins", "ngroups")] + [("reserved", C.c_int32 * 2)]
+
+
+class PrachXtab(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in XTAB_FIELDS[:-2]] + [("row_max", C.c_int64), ("col_max", C.c_int64)]
+
+
+def xtab_axis(ax):
+    """An axis of a cross-tabulation as (field id, width, bins): from such a tuple, whose field may be a name of XTAB_FIELD_NAMES, or from the text
+    FIELD:WIDTH:BINS the drivers take."""
+    f, w, b = ax.split(":") if isinstance(ax, str) else ax
+    f = XTAB_FIELD_NAMES.index(f.lower()) if isinstance(f, str) and not f.lstrip("-").isdigit() else int(f)
+    return f, int(w), int(b)
+
+
+def xtab_parse_axis(text, max_time):
+    """FIELD[:WIDTH[:BINS]] of the drivers as (field id, width, bins).  Defaults: width 500 for arrival, otherwise 1; as many bins as cover max_time (arrival)
+    or max_time + 6 (the other times), 7 for state, 1 for one, 255 for ptc and failcount (prach_sim takes the same)."""
+    parts = text.split(":")
+    if not 1 <= len(parts) <= 3 or parts[0].lower() not in XTAB_FIELD_NAMES:
+        raise ValueError(f"an axis is FIELD[:WIDTH[:BINS]], FIELD one of {', '.join(XTAB_FIELD_NAMES)}: {text!r}")
+    f = XTAB_FIELD_NAMES.index(parts[0].lower())
+    w = int(parts[1]) if len(parts) > 1 else 500 if f == 1 else 1
+    if w < 1:
+        raise ValueError(f"the width of an axis is at least 1: {text!r}")
+    cover = {0: 1, 8: 7, 5: 255, 6: 255}.get(f, -(-(max_time + (0 if f == 1 else 6)) // w))
+    b = int(parts[2]) if len(parts) > 2 else min(cover, XTAB_MAX_BINS)
+    return f, w, b
+
+
+class Xtab(_Reduction):
+    """The outcome cross-tabulations of ``ngroups`` trial groups (include/prach.h, prach_xtab): ``cells`` [ngroups, row_bins + 1, col_bins + 1] as numpy uint64
+    (the last index of an axis is its overflow bin) and ``scalars[field]``, one int64 array of length ngroups per field of XTAB_FIELDS.  rows, cols: an axis
+    each, (field, width, bins); who: the classes that enter, bits XTAB_SERVED | XTAB_UNSERVED | XTAB_IDLE."""
+    _FIELDS, _STRUCT, _MERGE, _PARAMS = XTAB_FIELDS, PrachXtab, "prach_xtab_merge", ("who", "rows", "cols")
+
+    def __init__(self, ngroups, rows, cols, who=XTAB_WHO["all"]):
+        import numpy as np
+        self.rows, self.cols, self.who, self.ngroups = xtab_axis(rows), xtab_axis(cols), int(who), int(ngroups)
+        self.cells = np.zeros((self.ngroups, max(self.rows[2], 0) + 1, max(self.cols[2], 0) + 1), dtype=np.uint64)
+        self.scalars = {f: np.zeros(self.ngroups, dtype=np.int64) for f in XTAB_FIELDS}
+        self.scalars["row_max"][:] = -1
+        self.scalars["col_max"][:] = -1
+
+    def spec(self):
+        return PrachXtabSpec(self.who, *self.rows, *self.cols, self.ngroups, (C.c_int32 * 2)(0, 0))
+
+    def _arrays(self):
+        return [self.cells]
+
+    def _scalar(self, f):
+        return self.scalars[f]
+
+    def _cargs(self, g):
+        return tuple(self._rows(g))
+
+    def quantile(self, g, row, q):
+        """Lower edge of the column bin holding the max(1, ceil(q * n))-th smallest column value of row ``row`` of group g (row -1: pooled over all rows), n
+        counting the overflow column too; -1: nothing there, or that rank lies in the overflow column (prach_xtab_quantile)."""
+        sp = self.spec()
+        return int(lib().prach_xtab_quantile(C.byref(sp), self._rows(g)[0], int(row), float(q)))
+
+
 class PrachError(RuntimeError):
     def __init__(self, status, what=""):
         self.status = status
@@ -411,6 +482,17 @@ def lib():
         L.prach_sojourn_format_csv.restype = C.c_size_t
         L.prach_sojourn_tile_ues.argtypes = []
         L.prach_sojourn_window_words.argtypes = []
+        L.prach_run_trials_xtab.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachXtabSpec),
+                                            C.POINTER(C.c_int32), C.POINTER(PrachXtab), u64p]
+        L.prach_xtab_accumulate_logs.argtypes = [C.POINTER(PrachXtabSpec), C.POINTER(PrachCfg), C.c_uint64, C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachXtab), u64p]
+        L.prach_xtab_merge.argtypes = [C.POINTER(PrachXtabSpec), C.POINTER(PrachXtab), u64p, C.POINTER(PrachXtab), u64p]
+        L.prach_xtab_merge.restype = None
+        L.prach_xtab_quantile.argtypes = [C.POINTER(PrachXtabSpec), u64p, C.c_int, C.c_double]
+        L.prach_xtab_quantile.restype = C.c_int64
+        L.prach_xtab_format_csv.argtypes = [C.POINTER(PrachXtabSpec), C.POINTER(PrachXtab), u64p, C.c_char_p, C.c_char_p, C.c_size_t]
+        L.prach_xtab_format_csv.restype = C.c_size_t
+        L.prach_xtab_tile_ues.argtypes = []
+        L.prach_xtab_window_words.argtypes = []
         L.prach_run_trials_summary.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachSummarySpec),
                                                C.POINTER(PrachTrialSummary)]
         L.prach_summary_from_logs.argtypes = [C.POINTER(PrachSummarySpec), C.POINTER(PrachCfg), C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachTrialSummary)]
@@ -467,7 +549,8 @@ EXPORTS = ("prach_engine_create", "prach_engine_destroy", "prach_engine_set", "p
            "prach_timeline_format_csv", "prach_timeline_tile_ues", "prach_timeline_window_bins", "prach_run_trials_sojourn", "prach_sojourn_accumulate_logs",
            "prach_sojourn_merge", "prach_sojourn_quantile", "prach_sojourn_format_csv", "prach_sojourn_tile_ues", "prach_sojourn_window_words",
            "prach_run_trials_summary", "prach_summary_from_logs", "prach_summary_stats", "prach_summary_format_csv", "prach_summary_max_value",
-           "prach_run_trials_trace", "prach_trace_merge", "prach_trace_format_csv", "prach_trace_tile_subframes")
+           "prach_run_trials_trace", "prach_trace_merge", "prach_trace_format_csv", "prach_trace_tile_subframes", "prach_run_trials_xtab", "prach_xtab_accumulate_logs",
+           "prach_xtab_merge", "prach_xtab_quantile", "prach_xtab_format_csv", "prach_xtab_tile_ues", "prach_xtab_window_words")
 
 
 def make_cfg(nUE, variant=VARIANT_BETA_C, uniform=0, rng_mode=RNG_GLIBC, seed=0, stream_offset=0, **kw) -> PrachCfg:
@@ -552,6 +635,13 @@ class Engine:
         run_trials_dist.  Returns (results, logs, Sojourn)."""
         return self._call_reduced("prach_run_trials_sojourn", cfgs,
                                   Sojourn(_ngroups(len(cfgs), groups, ngroups), arrival_bins, arrival_bin_ms, delay_bins, delay_bin_ms), groups, want_logs)
+
+    def run_trials_xtab(self, cfgs, rows=("arrival", 500, 20), cols=("state", 1, 7), who=XTAB_WHO["all"], groups=None, want_logs=False, ngroups=None):
+        """run_trials plus the outcome cross-tabulation per trial group — a table of two per-UE quantities (rows, cols: (field, width, bins), a field of
+        XTAB_FIELD_NAMES) over the classes of UEs in ``who`` — reduced on the device from the per-UE log records the simulation kernels leave there
+        (prach_run_trials_xtab; Beta.c and RandomAccessWithNOMA trials only).  The default: what became of the UEs by when they arrived.  groups / ngroups /
+        want_logs as in run_trials_dist.  Returns (results, logs, Xtab)."""
+        return self._call_reduced("prach_run_trials_xtab", cfgs, Xtab(_ngroups(len(cfgs), groups, ngroups), rows, cols, who), groups, want_logs)
 
     def run_trials_summary(self, cfgs, permille=(500, 950, 990), want_logs=False):
         """run_trials plus one summary row per trial — counts, sums, maxima and exact order statistics (levels in permille) of the sojourn, of `timer` and of
@@ -820,3 +910,32 @@ def summary_csv(sm: Summary, groups=None, ngroups=None, labels=None) -> bytes:
         n = lib().prach_summary_format_csv(*args, buf, need + 1)
         out += buf.raw[:n]
     return out
+
+
+def xtab_tile_ues() -> int:
+    return lib().prach_xtab_tile_ues()
+
+
+def xtab_window_words() -> int:
+    return lib().prach_xtab_window_words()
+
+
+def xtab_from_logs(cfgs, steps, logs, rows=("arrival", 500, 20), cols=("state", 1, 7), who=XTAB_WHO["all"], groups=None, ngroups=None) -> Xtab:
+    """The host-side definition of the cross-tabulation (prach_xtab_accumulate_logs): logs[k] is the per-UE log of the trial with config cfgs[k] that ran
+    steps[k] subframes (prach_result.steps) — a ctypes array of PrachUeLog or an int32 array of shape [nUE, 16] — added to group groups[k] (None: group k)."""
+    xt = Xtab(_ngroups(len(logs), groups, ngroups), rows, cols, who)
+    sp = xt.spec()
+    for k, lg in enumerate(logs):
+        g = k if groups is None else int(groups[k])
+        ptr, nue, _keep = _log_ptr(lg)
+        d = xt._group(g)
+        rc = lib().prach_xtab_accumulate_logs(C.byref(sp), C.byref(cfgs[k]), int(steps[k]), ptr, nue, C.byref(d), *xt._rows(g))
+        if rc != OK:
+            raise PrachError(rc, "(prach_xtab_accumulate_logs)")
+        xt._store(g, d)
+    return xt
+
+
+def xtab_csv(xt: Xtab, labels=None) -> bytes:
+    """The CSV text of every group (prach_xtab_format_csv), labelled labels[g] (default: the group number)."""
+    return _csv("prach_xtab_format_csv", xt, labels)

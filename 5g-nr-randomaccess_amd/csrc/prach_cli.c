@@ -34,6 +34,11 @@
  * and collisionPreambles, by time (prach_run_trials_trace: recorded by the simulation kernels and reduced on the device, so it works with --logs 0), one group
  * per sweep point with the --times seeds merged, labelled nUE; bins of MS ms (default 5) that cover maxTime; --program beta|withnoma only, and not together
  * with --cdf, --timeline, --sojourn or --ci (one reduction per call);
+ * --xtab FILE [--xtab-rows FIELD[:WIDTH[:BINS]]] [--xtab-cols FIELD[:WIDTH[:BINS]]] [--xtab-who served|unserved|arrived|all]: the outcome cross-tabulation
+ * (prach_run_trials_xtab: reduced on the device, so it works with --logs 0), one group per sweep point with the --times seeds merged, labelled nUE; FIELD is
+ * one of one, arrival, sojourn, completion, timer, ptc, failcount, age, state; the defaults — rows arrival:500 with as many bins as cover maxTime, columns
+ * state:1:7, everybody — say what became of the UEs by when they arrived; --program beta|withnoma only, and not together with --cdf, --timeline, --sojourn,
+ * --ci or --trace (one reduction per call);
  * --devices LIST: the same with explicit HIP ordinals (an ordinal may repeat);
  * --gpus N: the --times x sweep grid sharded over N devices of the node by host C — one forked child per device,
  * forked BEFORE any HIP call, trials dealt by descending cost (Philox: any trial anywhere; glibc: whole seeds, because
@@ -46,6 +51,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <strings.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <sys/wait.h>
@@ -115,10 +121,13 @@ typedef struct reduction {
     const prach_summary_spec *sm;
     prach_trial_summary *sm_rows;
     const prach_trace_spec *tr; /* --trace: prach_trace[npts] | four series [npts][bins] each (calls, singles, txop, collisions) */
+    const prach_xtab_spec *xt;  /* --xtab: prach_xtab[npts] | cells[npts][row_bins + 1][col_bins + 1] */
 } reduction;
-static int red_on(const reduction *r) { return r->cdf || r->tl || r->sj || r->tr; }
+static int red_on(const reduction *r) { return r->cdf || r->tl || r->sj || r->tr || r->xt; }
+static size_t xt_cells(const prach_xtab_spec *s) { return ((size_t)s->row_bins + 1) * ((size_t)s->col_bins + 1); }
 static size_t sj_cells(const prach_sojourn_spec *s) { return (size_t)s->arrival_bins * (size_t)s->delay_bins; }
 static size_t red_block_bytes(const reduction *r) {
+    if (r->xt) return (size_t)r->xt->ngroups * (sizeof(prach_xtab) + 8 * xt_cells(r->xt));
     if (r->tr) return (size_t)r->tr->ngroups * (sizeof(prach_trace) + 4 * 8 * (size_t)r->tr->bins);
     if (r->tl) return (size_t)r->tl->ngroups * (sizeof(prach_timeline) + 5 * 8 * (size_t)r->tl->bins);
     if (r->sj) return (size_t)r->sj->ngroups * (sizeof(prach_sojourn) + 8 * (sj_cells(r->sj) + 2 * (size_t)r->sj->arrival_bins));
@@ -126,6 +135,7 @@ static size_t red_block_bytes(const reduction *r) {
 }
 /* group g of block b: --cdf its q-th histogram (0 delay, 1 preamble count), --timeline its q-th series, --sojourn 0 hist, 1 row_arrived, 2 row_delay_overflow */
 static uint64_t *red_array(const reduction *r, char *b, int q, int g) {
+    if (r->xt) return (uint64_t *)(b + (size_t)r->xt->ngroups * sizeof(prach_xtab)) + (size_t)g * xt_cells(r->xt);
     if (r->tr) return (uint64_t *)(b + (size_t)r->tr->ngroups * sizeof(prach_trace)) + ((size_t)q * (size_t)r->tr->ngroups + (size_t)g) * (size_t)r->tr->bins;
     if (r->sj) {
         uint64_t *const h = (uint64_t *)(b + (size_t)r->sj->ngroups * sizeof(prach_sojourn));
@@ -142,8 +152,11 @@ static void red_init_block(const reduction *r, char *b) {
     for (int g = 0; r->cdf && g < r->cdf->ngroups; g++) ((prach_dist *)b)[g].delay_max = -1;
     for (int g = 0; r->sj && g < r->sj->ngroups; g++) ((prach_sojourn *)b)[g].sojourn_max = -1;
     for (int g = 0; r->tr && g < r->tr->ngroups; g++) ((prach_trace *)b)[g].calls_max = -1;
+    for (int g = 0; r->xt && g < r->xt->ngroups; g++) ((prach_xtab *)b)[g].row_max = ((prach_xtab *)b)[g].col_max = -1;
 }
 static void red_merge_block(const reduction *r, char *into, char *from) {
+    for (int g = 0; r->xt && g < r->xt->ngroups; g++) prach_xtab_merge(r->xt, (prach_xtab *)into + g, red_array(r, into, 0, g), (prach_xtab *)from + g, red_array(r, from, 0, g));
+    if (r->xt) return;
     for (int g = 0; r->tr && g < r->tr->ngroups; g++) {
         uint64_t *a[4];
         const uint64_t *b[4];
@@ -165,6 +178,7 @@ static void red_merge_block(const reduction *r, char *into, char *from) {
 }
 /* the CSV text of group g of block b; returns its length (>= cap: it did not fit) */
 static size_t red_format_group(const reduction *r, char *b, int g, const char *label, char *out, size_t cap) {
+    if (r->xt) return prach_xtab_format_csv(r->xt, (prach_xtab *)b + g, red_array(r, b, 0, g), label, out, cap);
     if (r->tr) {
         const uint64_t *ser[4];
         for (int q = 0; q < 4; q++) ser[q] = red_array(r, b, q, g);
@@ -179,13 +193,35 @@ static size_t red_format_group(const reduction *r, char *b, int g, const char *l
     return prach_dist_format_csv(r->cdf, (prach_dist *)b + g, red_array(r, b, 0, g), red_array(r, b, 1, g), label, out, cap);
 }
 
+/* FIELD[:WIDTH[:BINS]] of --xtab-rows / --xtab-cols.  Defaults: width 500 for arrival, otherwise 1; as many bins as cover max_time (arrival) or max_time + 6 (the
+ * other times), 7 for state, 1 for one, 255 for ptc and failcount.  Returns 0 for a text that is none */
+static int xtab_axis(const char *text, int max_time, int32_t *field, int32_t *width, int32_t *bins) {
+    static const char *const names[PRACH_XTAB_NFIELDS] = {"one", "arrival", "sojourn", "completion", "timer", "ptc", "failcount", "age", "state"};
+    const char *c1 = strchr(text, ':'), *c2 = c1 ? strchr(c1 + 1, ':') : NULL;
+    const size_t len = c1 ? (size_t)(c1 - text) : strlen(text);
+    int f = -1;
+    for (int q = 0; q < PRACH_XTAB_NFIELDS; q++)
+        if (strlen(names[q]) == len && strncasecmp(names[q], text, len) == 0) f = q;
+    if (f < 0 || (c2 && strchr(c2 + 1, ':'))) return 0;
+    const long w = c1 ? atol(c1 + 1) : f == PRACH_XTAB_ARRIVAL ? 500 : 1;
+    if (w < 1 || w > INT32_MAX) return 0;
+    long b = f == PRACH_XTAB_ONE ? 1 : f == PRACH_XTAB_STATE ? 7 : f == PRACH_XTAB_PTC || f == PRACH_XTAB_FAILCOUNT ? 255
+             : (max_time + (f == PRACH_XTAB_ARRIVAL ? 0 : 6) + w - 1) / w;
+    if (b > PRACH_XTAB_MAX_BINS) b = PRACH_XTAB_MAX_BINS;
+    if (c2) b = atol(c2 + 1);
+    if (b < 1 || b > PRACH_XTAB_MAX_BINS) return 0;
+    *field = f; *width = (int32_t)w; *bins = (int32_t)b;
+    return 1;
+}
+
 /* one call into the library with the run's reduction: its groups (group = sweep point, grp[k]) come back in call_block and are merged into the worker's block */
 static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *r, prach_ue_log *const *logs, const reduction *red, const int32_t *grp,
                     char *call_block, char *worker_block, prach_trial_summary *sm_rows) {
     if (red->sm) return prach_run_trials_summary(eng, c, n, r, logs, red->sm, sm_rows);
     if (!red_on(red)) return prach_run_trials(eng, c, n, r, logs);
     char *const b = call_block;
-    const int rc = red->tr ? prach_run_trials_trace(eng, c, n, r, logs, red->tr, grp, (prach_trace *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0), red_array(red, b, 2, 0),
+    const int rc = red->xt ? prach_run_trials_xtab(eng, c, n, r, logs, red->xt, grp, (prach_xtab *)b, red_array(red, b, 0, 0))
+                   : red->tr ? prach_run_trials_trace(eng, c, n, r, logs, red->tr, grp, (prach_trace *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0), red_array(red, b, 2, 0),
                                                     red_array(red, b, 3, 0))
                    : red->tl ? prach_run_trials_timeline(eng, c, n, r, logs, red->tl, grp, (prach_timeline *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0),
                                                        red_array(red, b, 2, 0), red_array(red, b, 3, 0), red_array(red, b, 4, 0))
@@ -281,7 +317,8 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
 int main(int argc, char *argv[]) {
     int randomMax = 1, variant = PRACH_VARIANT_WITHNOMA_C, rng = PRACH_RNG_GLIBC, device = 0, want_logs = 1, gpus = 1, rng_given = 0;
     int sweep_lo = 10000, sweep_hi = 100000, sweep_step = 10000; /* WithNOMA:221 */
-    const char *outdir = ".", *csv_path = NULL, *devlist = NULL, *cdf_path = NULL, *tl_path = NULL, *sj_path = NULL, *ci_path = NULL, *tr_path = NULL;
+    const char *outdir = ".", *csv_path = NULL, *devlist = NULL, *cdf_path = NULL, *tl_path = NULL, *sj_path = NULL, *ci_path = NULL, *tr_path = NULL, *xt_path = NULL;
+    const char *xt_rows = "arrival:500", *xt_cols = "state:1:7", *xt_who = "all";
     prach_summary_spec ci_spec = {3, {500, 950, 990, 0, 0, 0, 0, 0}, {0, 0, 0}};
     int cdf_bins = 4096, cdf_bin_ms = 1, tl_bin_ms = 5, sj_row_ms = 500, sj_bin_ms = 5, tr_bin_ms = 5;
     int devs[64];
@@ -384,6 +421,14 @@ int main(int argc, char *argv[]) {
         } else if (strcmp(a, "--trace-bin") == 0) {
             if (atoi(v) < 1) die("--trace-bin MS: the width of a trace bin in ms, at least 1");
             tr_bin_ms = atoi(v);
+        } else if (strcmp(a, "--xtab") == 0) {
+            xt_path = v;
+        } else if (strcmp(a, "--xtab-rows") == 0) {
+            xt_rows = v;
+        } else if (strcmp(a, "--xtab-cols") == 0) {
+            xt_cols = v;
+        } else if (strcmp(a, "--xtab-who") == 0) {
+            xt_who = v;
         } else if (strcmp(a, "--ci") == 0) {
             ci_path = v;
         } else if (strcmp(a, "--ci-levels") == 0) {
@@ -401,6 +446,8 @@ int main(int argc, char *argv[]) {
         }
     }
     base.rng_mode = rng;
+    if (xt_path && (tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--xtab cannot be combined with --cdf, --timeline, --sojourn, --ci or --trace: one reduction per call");
+    if (xt_path && variant == PRACH_VARIANT_NOMA_C) die("--xtab needs --program beta or withnoma (NOMA.c logs no trace of a UE's cycle start)");
     if (tr_path && (ci_path || sj_path || tl_path || cdf_path)) die("--trace cannot be combined with --cdf, --timeline, --sojourn or --ci: one reduction per call");
     if (tr_path && variant == PRACH_VARIANT_NOMA_C) die("--trace needs --program beta or withnoma (NOMA.c's resolver is another one)");
     if (ci_path && variant == PRACH_VARIANT_NOMA_C) die("--ci needs --program beta or withnoma (NOMA.c logs no trace of a UE's cycle start)");
@@ -490,13 +537,24 @@ int main(int argc, char *argv[]) {
      * three numbers, per cell and twice per row */
     const reduction red_ = {cdf_path ? &cdf_spec : NULL, tl_path ? &tl_spec : NULL, sj_path ? &sj_spec : NULL, sj_path ? sj_path : tl_path ? tl_path : cdf_path,
                             sj_path ? 64 * ((size_t)sj_rows * ((size_t)sj_bins + 2) + 1) + 1
-                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1, NULL, NULL, NULL};
+                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1, NULL, NULL, NULL, NULL};
     reduction red_ci = red_;
     /* the trace's bins cover maxTime */
     const int tr_bins = (prach_max_time(&base) + tr_bin_ms - 1) / tr_bin_ms;
     const prach_trace_spec tr_spec = {tr_bins, tr_bin_ms, npts, 0};
     if (tr_path && tr_bins > PRACH_TRACE_MAX_BINS) die("--trace-bin MS: too many bins");
     if (tr_path) { red_ci.tr = &tr_spec; red_ci.path = tr_path; red_ci.text_cap = 64 * (4 * (size_t)tr_bins + 1) + 1; } /* (a line: the label, a series name, two numbers) */
+    /* --xtab: the axes as given, the defaults of a field where width or bins are left out */
+    prach_xtab_spec xt_spec = {0, 0, 0, 0, 0, 0, 0, npts, {0, 0}};
+    if (xt_path) {
+        xt_spec.who = strcmp(xt_who, "served") == 0 ? PRACH_XTAB_SERVED : strcmp(xt_who, "unserved") == 0 ? PRACH_XTAB_UNSERVED
+                      : strcmp(xt_who, "arrived") == 0 ? (PRACH_XTAB_SERVED | PRACH_XTAB_UNSERVED) : strcmp(xt_who, "all") == 0 ? (PRACH_XTAB_SERVED | PRACH_XTAB_UNSERVED | PRACH_XTAB_IDLE) : 0;
+        if (!xt_spec.who) die("--xtab-who served|unserved|arrived|all");
+        if (!xtab_axis(xt_rows, prach_max_time(&base), &xt_spec.row_field, &xt_spec.row_width, &xt_spec.row_bins)) die("--xtab-rows FIELD[:WIDTH[:BINS]]: a field of the menu, a width of at least 1, 1 to 65536 bins");
+        if (!xtab_axis(xt_cols, prach_max_time(&base), &xt_spec.col_field, &xt_spec.col_width, &xt_spec.col_bins)) die("--xtab-cols FIELD[:WIDTH[:BINS]]: a field of the menu, a width of at least 1, 1 to 65536 bins");
+        if ((uint64_t)npts * xt_cells(&xt_spec) > (1ull << 24)) die("--xtab: too many cells");
+        red_ci.xt = &xt_spec; red_ci.path = xt_path; red_ci.text_cap = 64 * (xt_cells(&xt_spec) + 1) + 1; /* (a line: the label, two edges, a count) */
+    }
     if (ci_path) { /* --ci: the rows of the whole grid, filled by the workers */
         red_ci.sm = &ci_spec;
         red_ci.sm_rows = (prach_trial_summary *)mmap(NULL, sizeof(prach_trial_summary) * (size_t)ntr, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);

@@ -214,6 +214,17 @@ struct SojournOut { unsigned long long *hist, *row_arrived, *row_overflow, *scal
 hipError_t launch_sojourn_kernel(const TimelineJob *jobs, int njobs, int workgroups, int rows, int row_ms, int delay_bins, int delay_bin_ms, int scheme, SojournOut out,
                                  hipStream_t stream);
 
+// prach_xtab.hip: the outcome cross-tabulation of a launch's accepted trials (prach_run_trials_xtab).  The jobs are the timeline's (TimelineJob: log records
+// and schedule of one trial) with E = min(steps, maxTime) in `pad`, and so are tile and workgroup.  scheme 1 privatises a table of at most XT_WINDOW_WORDS
+// cells in LDS, whole, as 32-bit counters and flushes the non-zero ones; a larger table, and everything under scheme 0, goes straight to the call's buffer
+// with 64-bit agent-scope atomics.
+constexpr int XT_WINDOW_WORDS = SJ_WINDOW_WORDS; // the sojourn kernel's measured window
+static_assert((unsigned long long)TL_TILE < (1ull << 32), "a 32-bit LDS counter holds what one tile adds to a cell: at most one per UE");
+constexpr int XT_SCALARS = 16; // per group: idle, served, unserved, selected, binned, row_sum, col_sum, row_max + 1, col_max + 1 (0: nothing binned), 7 spare
+struct XtabAxes { int who, row_field, row_width, row_bins, col_field, col_width, col_bins; };
+struct XtabOut { unsigned long long *cells, *scalars; }; // [ngroups][row_bins + 1][col_bins + 1], [ngroups][XT_SCALARS]
+hipError_t launch_xtab_kernel(const TimelineJob *jobs, int njobs, int workgroups, XtabAxes ax, int scheme, XtabOut out, hipStream_t stream);
+
 // prach_summary.hip: one summary row per accepted trial of a launch (prach_run_trials_summary).  The jobs are the timeline's (TimelineJob: log records and
 // schedule of one trial; group = the row), ONE workgroup per trial.  A row is SM_WORDS 64-bit words, written with plain stores: arrived, success, restarted,
 // 3 range-error counts [sojourn, timer, preambleTxCounter], 3 sums, 3 maxima (-1: no successful UE), then [3][PRACH_SUMMARY_MAX_Q] levels (-1: not found or unused).

@@ -52,6 +52,7 @@ struct prach_engine {
     hipEvent_t red_ev0 = nullptr, red_ev1 = nullptr;
     int64_t opt_trace_scheme = 1;    // trace_kernel's binning (prach_trace.hip): 0 global atomics only, 1 the tile's bins added up in an LDS window first
     int64_t opt_summary_threads = 1024; // summary_kernel's workgroup (prach_summary.hip): 512 or 1024 threads, one workgroup per trial
+    int64_t opt_xtab_scheme = 1;     // xtab_kernel's binning (prach_xtab.hip): 0 global atomics only, 1 a table that fits privatised in LDS
     int64_t opt_sojourn_scheme = 1;  // sojourn_kernel's binning (prach_sojourn.hip): 0 global atomics only, 1 rows of the histogram privatised in LDS
     int64_t opt_timeline_scheme = 1; // timeline_kernel's binning (prach_timeline.hip): 0 global atomics only, 1 windows of bins privatised in LDS (measured faster: DESIGN.md 4)
     int64_t opt_dist_scheme = 1;   // dist_kernel's binning of the preamble counts (prach_dist.hip): 0 plain LDS adds, 1 per-wavefront copies (measured fastest), 2 match and aggregate
@@ -424,7 +425,8 @@ static int noma_device_activation(prach_engine *e, const TrialDev *dparams, cons
 // scalars the kernel keeps per group.  prach_run_trials_summary is the fourth kind: every trial is its own group and the only part is the kernel's row of
 // SM_WORDS words per trial, unpacked into the caller's prach_trial_summary rows.
 // prach_run_trials_trace is the fifth: the four series calls, singles, txop, collisions, reduced from the rows the simulation kernels write per subframe.
-enum class Red { dist, timeline, sojourn, summary, trace };
+// prach_run_trials_xtab is the sixth: the parts are {cells, scalars}; it takes the timeline's jobs with the trial's steps in their last word.
+enum class Red { dist, timeline, sojourn, summary, trace, xtab };
 constexpr int RED_MAX_PARTS = 6;
 struct Reduction {
     Red kind;
@@ -441,10 +443,13 @@ struct Reduction {
     prach_trial_summary *rows;
     const prach_trace_spec *rspec;    // trace
     prach_trace *tr;
+    const prach_xtab_spec *xspec;     // xtab
+    prach_xtab *xt;
 };
 // words per group of every part; returns their number
 static int red_parts(const Reduction &r, size_t words[RED_MAX_PARTS]) {
     if (r.kind == Red::summary) { words[0] = SM_WORDS; return 1; }
+    if (r.kind == Red::xtab) { words[0] = ((size_t)r.xspec->row_bins + 1) * ((size_t)r.xspec->col_bins + 1); words[1] = XT_SCALARS; return 2; }
     if (r.kind == Red::trace) { for (int q = 0; q < 4; q++) words[q] = (size_t)r.rspec->bins; words[4] = TR_SCALARS; return 5; }
     if (r.kind == Red::dist) { words[0] = (size_t)r.dspec->delay_bins; words[1] = PRACH_DIST_PTC_BINS; words[2] = DIST_SCALARS; return 3; }
     if (r.kind == Red::sojourn) {
@@ -455,7 +460,7 @@ static int red_parts(const Reduction &r, size_t words[RED_MAX_PARTS]) {
     words[5] = TL_SCALARS;
     return 6;
 }
-static size_t red_job_bytes(Red kind) { return kind == Red::dist ? sizeof(DistJob) : kind == Red::trace ? sizeof(TraceJob) : sizeof(TimelineJob); } // (sojourn and summary take the timeline's jobs)
+static size_t red_job_bytes(Red kind) { return kind == Red::dist ? sizeof(DistJob) : kind == Red::trace ? sizeof(TraceJob) : sizeof(TimelineJob); } // (sojourn, summary and xtab take the timeline's jobs)
 
 // What one prach_run_trials call carries from launch to launch
 struct CallCtx {
@@ -798,7 +803,8 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
             if (tl) {
                 const int nslots = (prach_max_time(&c) + c.accessTime - 1) / c.accessTime; // (what prach_arrival_schedule fills; the table has one entry more)
                 max_slots = std::max(max_slots, nslots);
-                reinterpret_cast<TimelineJob *>(e->red_jobs_h)[njobs++] = TimelineJob{reinterpret_cast<const int4 *>(A + L.logs), reinterpret_cast<const int *>(A + L.sched), c.nUE, g, wgs, c.accessTime, nslots, 0};
+                reinterpret_cast<TimelineJob *>(e->red_jobs_h)[njobs++] = TimelineJob{reinterpret_cast<const int4 *>(A + L.logs), reinterpret_cast<const int *>(A + L.sched), c.nUE, g, wgs, c.accessTime, nslots,
+                                                                                      R.kind == Red::xtab ? (int)std::min<unsigned long long>(dr.steps, (unsigned long long)prach_max_time(&c)) : 0}; // (xtab: E of include/prach.h)
             } else
                 reinterpret_cast<DistJob *>(e->red_jobs_h)[njobs++] = DistJob{reinterpret_cast<const int *>(A + L.timers), reinterpret_cast<const int *>(A + (batch ? L.rec32 : L.ptc)), c.nUE, g, wgs, batch ? 1 : 0};
             const int tile = tl ? TL_TILE : DIST_TILE;
@@ -816,6 +822,9 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
                 lv.nq = R.mspec->nq;
                 for (int l = 0; l < lv.nq; l++) lv.permille[l] = R.mspec->permille[l];
                 HIPCHK(launch_summary_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, lv, (int)e->opt_summary_threads, std::min(max_slots, summary_sched_cap()), d[0], e->stream));
+            } else if (R.kind == Red::xtab) {
+                const prach_xtab_spec &x = *R.xspec;
+                HIPCHK(launch_xtab_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, wgs, XtabAxes{x.who, x.row_field, x.row_width, x.row_bins, x.col_field, x.col_width, x.col_bins}, (int)e->opt_xtab_scheme, XtabOut{d[0], d[1]}, e->stream));
             } else if (R.kind == Red::sojourn) HIPCHK(launch_sojourn_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, wgs, R.sspec->arrival_bins, R.sspec->arrival_bin_ms, R.sspec->delay_bins, R.sspec->delay_bin_ms, (int)e->opt_sojourn_scheme, SojournOut{d[0], d[1], d[2], d[3]}, e->stream));
             else if (tl) HIPCHK(launch_timeline_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, wgs, R.tspec->bins, R.tspec->bin_ms, (int)e->opt_timeline_scheme, TimelineOut{d[0], d[1], d[2], d[3], d[4], d[5]}, e->stream));
             else HIPCHK(launch_dist_kernel(reinterpret_cast<const DistJob *>(e->red_jobs_d), njobs, wgs, R.dspec->delay_bins, R.dspec->delay_bin_ms, (int)e->opt_dist_scheme, d[0], d[1], d[2], e->stream));
@@ -1069,6 +1078,12 @@ static int reduction_end(prach_engine *e, CallCtx &cx) {
             if (!cx.host_d.empty())
                 prach_dist_merge(&s, &d, R.out[0] + g * (size_t)s.delay_bins, R.out[1] + g * PRACH_DIST_PTC_BINS, &cx.host_d[g],
                                  cx.host_dh.data() + g * (size_t)s.delay_bins, cx.host_ph.data() + g * PRACH_DIST_PTC_BINS);
+        } else if (R.kind == Red::xtab) {
+            prach_xtab &x = R.xt[g];
+            x.trials = cx.trials[g]; x.ues = cx.ues[g]; x.idle = q[0]; x.served = q[1]; x.unserved = q[2]; x.selected = q[3]; x.binned = q[4];
+            x.undefined = q[3] - q[4];
+            x.row_sum = q[5]; x.col_sum = q[6];
+            x.row_max = (int64_t)q[7] - 1; x.col_max = (int64_t)q[8] - 1;
         } else if (R.kind == Red::sojourn) {
             prach_sojourn &j = R.sj[g];
             j.trials = cx.trials[g]; j.ues = cx.ues[g]; j.arrived = q[0]; j.success = q[1]; j.restarted = q[2]; j.arrival_overflow = q[3]; j.delay_overflow = q[4];
@@ -1105,6 +1120,7 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
             } else if (red->kind == Red::trace) { red->tr[g] = prach_trace{}; red->tr[g].calls_max = -1; }
             else if (red->kind == Red::dist) { red->dist[g] = prach_dist{}; red->dist[g].delay_max = -1; }
             else if (red->kind == Red::sojourn) { red->sj[g] = prach_sojourn{}; red->sj[g].sojourn_max = -1; }
+            else if (red->kind == Red::xtab) { red->xt[g] = prach_xtab{}; red->xt[g].row_max = red->xt[g].col_max = -1; }
             else { red->tl[g] = prach_timeline{}; red->tl[g].done_max = -1; }
         }
     }
@@ -1273,7 +1289,7 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
     e->last.updates = upd;
     if (red) {
         int rc = reduction_end(e, cx);
-        (red->kind == Red::dist ? e->last.dist_ms : red->kind == Red::timeline ? e->last.timeline_ms : red->kind == Red::sojourn ? e->last.sojourn_ms : red->kind == Red::trace ? e->last.trace_ms : e->last.summary_ms) = cx.red_ms;
+        (red->kind == Red::dist ? e->last.dist_ms : red->kind == Red::timeline ? e->last.timeline_ms : red->kind == Red::sojourn ? e->last.sojourn_ms : red->kind == Red::trace ? e->last.trace_ms : red->kind == Red::xtab ? e->last.xtab_ms : e->last.summary_ms) = cx.red_ms;
         if (rc != PRACH_OK) return rc;
     }
     e->last.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1341,6 +1357,7 @@ int prach_engine_set(prach_engine *e, const char *key, int64_t value) {
     if (std::strcmp(key, "timeline_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_timeline_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "summary_threads") == 0) { if (value != 0 && value != 512 && value != 1024) return PRACH_ERR_ARG; e->opt_summary_threads = value ? value : 1024; return PRACH_OK; }
     if (std::strcmp(key, "trace_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_trace_scheme = value; return PRACH_OK; }
+    if (std::strcmp(key, "xtab_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_xtab_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "sojourn_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_sojourn_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "xcd_pack") == 0) { e->opt_xcd_pack = value != 0; return PRACH_OK; }
     return PRACH_ERR_ARG;
@@ -1497,5 +1514,25 @@ int prach_trace_tile_subframes(void) { return TR_TILE; }
 
 int prach_sojourn_tile_ues(void) { return TL_TILE; }
 int prach_sojourn_window_words(void) { return SJ_WINDOW_WORDS; }
+
+int prach_run_trials_xtab(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_xtab_spec *spec,
+                          const int32_t *group, prach_xtab *xt, uint64_t *cells) {
+    // (spec, groups and variants are judged first: what they ask for does not depend on a device)
+    if (!cfgs || !results || n <= 0 || !spec || !xt || !cells) return PRACH_ERR_ARG;
+    auto axis_ok = [](int f, int w, int b) { return f >= 0 && f < PRACH_XTAB_NFIELDS && w >= 1 && b >= 1 && b <= PRACH_XTAB_MAX_BINS; };
+    if (spec->who <= 0 || (spec->who & ~(PRACH_XTAB_SERVED | PRACH_XTAB_UNSERVED | PRACH_XTAB_IDLE)) != 0 || !axis_ok(spec->row_field, spec->row_width, spec->row_bins) ||
+        !axis_ok(spec->col_field, spec->col_width, spec->col_bins) || spec->ngroups < 1 || spec->reserved[0] != 0 || spec->reserved[1] != 0) return PRACH_ERR_ARG;
+    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
+    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
+    if ((uint64_t)spec->ngroups * ((uint64_t)spec->row_bins + 1) * ((uint64_t)spec->col_bins + 1) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
+    if (!e) return PRACH_ERR_ARG;
+    Reduction red{Red::xtab, group, spec->ngroups, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {cells}};
+    red.xspec = spec;
+    red.xt = xt;
+    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
+}
+
+int prach_xtab_tile_ues(void) { return TL_TILE; }
+int prach_xtab_window_words(void) { return XT_WINDOW_WORDS; }
 
 } // extern "C"

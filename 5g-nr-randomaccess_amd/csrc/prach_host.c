@@ -868,6 +868,131 @@ size_t prach_sojourn_format_csv(const prach_sojourn_spec *s, const prach_sojourn
     return csv_end(buf, cap, off);
 }
 
+/* ---- outcome cross-tabulation per trial group (prach_run_trials_xtab) ----------------------------- */
+
+static int xtab_axis_ok(int field, int width, int bins) {
+    return field >= 0 && field < PRACH_XTAB_NFIELDS && width >= 1 && bins >= 1 && bins <= PRACH_XTAB_MAX_BINS;
+}
+static int xtab_spec_ok(const prach_xtab_spec *s) {
+    return s && s->who > 0 && (s->who & ~(PRACH_XTAB_SERVED | PRACH_XTAB_UNSERVED | PRACH_XTAB_IDLE)) == 0 && xtab_axis_ok(s->row_field, s->row_width, s->row_bins) &&
+           xtab_axis_ok(s->col_field, s->col_width, s->col_bins) && s->reserved[0] == 0 && s->reserved[1] == 0;
+}
+
+/* the class bit of a UE and its STATE (include/prach.h) */
+static int xtab_class(const prach_ue_log *u) {
+    return u->active == -1 ? PRACH_XTAB_IDLE : u->msg4Flag == 1 ? PRACH_XTAB_SERVED : PRACH_XTAB_UNSERVED;
+}
+static int xtab_state(const prach_ue_log *u) {
+    const int cls = xtab_class(u);
+    if (cls == PRACH_XTAB_IDLE) return 0;
+    if (cls == PRACH_XTAB_SERVED) return 1;
+    if (u->active == 1) return u->nowBackoff > 0 ? 2 : 3;
+    if (u->active == 2) return u->connectionRequest < 48 ? 4 : 5;
+    return 6;
+}
+/* the value of a field for a UE of class cls that arrived at a; a negative value is UNDEFINED, and so is a field outside the classes it is defined for */
+static int64_t xtab_value(int field, const prach_ue_log *u, int cls, int64_t a, int64_t E) {
+    const int arrived = cls != PRACH_XTAB_IDLE, served = cls == PRACH_XTAB_SERVED;
+    switch (field) {
+    case PRACH_XTAB_ONE: return 0;
+    case PRACH_XTAB_ARRIVAL: return arrived ? a : -1;
+    case PRACH_XTAB_SOJOURN: return served ? (int64_t)u->txTime + 6 - a : -1;
+    case PRACH_XTAB_COMPLETION: return served ? (int64_t)u->txTime + 6 : -1;
+    case PRACH_XTAB_TIMER: return arrived ? u->timer : -1;
+    case PRACH_XTAB_PTC: return arrived ? u->preambleTxCounter : -1;
+    case PRACH_XTAB_FAILCOUNT: return arrived ? u->failCount : -1;
+    case PRACH_XTAB_AGE: return arrived ? E - a : -1;
+    default: return xtab_state(u);
+    }
+}
+
+/* THE DEFINITION (include/prach.h) */
+int prach_xtab_accumulate_logs(const prach_xtab_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_xtab *x, uint64_t *cells) {
+    if (!xtab_spec_ok(s) || !cfg || !x || !cells || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    if (cfg->variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED;
+    if (prach_cfg_validate(cfg) != PRACH_OK || nUE != cfg->nUE) return PRACH_ERR_ARG;
+    const int nslots = (prach_max_time(cfg) + cfg->accessTime - 1) / cfg->accessTime;
+    int32_t *sched = (int32_t *)malloc(sizeof(int32_t) * (size_t)nslots);
+    if (!sched) return PRACH_ERR_INTERNAL;
+    prach_arrival_schedule(cfg, sched, nslots, NULL);
+    const int64_t E = steps < (uint64_t)prach_max_time(cfg) ? (int64_t)steps : (int64_t)prach_max_time(cfg);
+    if (x->trials == 0 && x->binned == 0) x->row_max = x->col_max = -1; /* (a zero-filled group is an empty one) */
+    int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
+    for (int i = 0; i < nUE; i++) {
+        while (slot < nslots && sched[slot] <= i) slot++;
+        const int64_t a = (int64_t)cfg->accessTime * slot;
+        const int cls = xtab_class(&ue[i]);
+        if (cls == PRACH_XTAB_IDLE) x->idle++;
+        else if (cls == PRACH_XTAB_SERVED) x->served++;
+        else x->unserved++;
+        if (!(cls & s->who)) continue;
+        x->selected++;
+        const int64_t rv = xtab_value(s->row_field, &ue[i], cls, a, E), cv = xtab_value(s->col_field, &ue[i], cls, a, E);
+        if (rv < 0 || cv < 0) { x->undefined++; continue; }
+        const int64_t rq = rv / s->row_width, cq = cv / s->col_width;
+        const size_t r = rq < s->row_bins ? (size_t)rq : (size_t)s->row_bins, c = cq < s->col_bins ? (size_t)cq : (size_t)s->col_bins;
+        cells[r * ((size_t)s->col_bins + 1) + c]++;
+        x->binned++;
+        x->row_sum += (uint64_t)rv;
+        x->col_sum += (uint64_t)cv;
+        if (rv > x->row_max) x->row_max = rv;
+        if (cv > x->col_max) x->col_max = cv;
+    }
+    free(sched);
+    x->trials++;
+    x->ues += (uint64_t)nUE;
+    return PRACH_OK;
+}
+
+void prach_xtab_merge(const prach_xtab_spec *s, prach_xtab *into, uint64_t *cells_into, const prach_xtab *from, const uint64_t *cells_from) {
+    if (!xtab_spec_ok(s) || !into || !cells_into || !from || !cells_from) return;
+    const int64_t ra = into->binned ? into->row_max : -1, rb = from->binned ? from->row_max : -1;
+    const int64_t ca = into->binned ? into->col_max : -1, cb = from->binned ? from->col_max : -1;
+    into->trials += from->trials; into->ues += from->ues; into->idle += from->idle; into->served += from->served; into->unserved += from->unserved;
+    into->selected += from->selected; into->binned += from->binned; into->undefined += from->undefined; into->row_sum += from->row_sum;
+    into->col_sum += from->col_sum;
+    into->row_max = ra > rb ? ra : rb;
+    into->col_max = ca > cb ? ca : cb;
+    const size_t n = ((size_t)s->row_bins + 1) * ((size_t)s->col_bins + 1);
+    for (size_t i = 0; i < n; i++) cells_into[i] += cells_from[i];
+}
+
+int64_t prach_xtab_quantile(const prach_xtab_spec *s, const uint64_t *cells, int row, double q) {
+    if (!xtab_spec_ok(s) || !cells || row < -1 || row > s->row_bins || !(q >= 0.0) || q > 1.0) return -1;
+    const int r0 = row < 0 ? 0 : row, r1 = row < 0 ? s->row_bins + 1 : row + 1;
+    const size_t W = (size_t)s->col_bins + 1;
+    uint64_t n = 0;
+    for (int r = r0; r < r1; r++)
+        for (size_t c = 0; c < W; c++) n += cells[(size_t)r * W + c];
+    if (n == 0) return -1;
+    uint64_t rank = (uint64_t)ceil(q * (double)n);
+    if (rank < 1) rank = 1;
+    if (rank > n) rank = n;
+    uint64_t cum = 0;
+    for (int c = 0; c < s->col_bins; c++) {
+        for (int r = r0; r < r1; r++) cum += cells[(size_t)r * W + (size_t)c];
+        if (cum >= rank) return (int64_t)c * s->col_width;
+    }
+    return -1; /* in the overflow column */
+}
+
+size_t prach_xtab_format_csv(const prach_xtab_spec *s, const prach_xtab *x, const uint64_t *cells, const char *label, char *buf, size_t cap) {
+    if (!xtab_spec_ok(s) || !x || !cells || !label) return 0;
+    size_t off = 0;
+    const size_t W = (size_t)s->col_bins + 1;
+    for (int r = 0; r <= s->row_bins; r++)
+        for (int c = 0; c <= s->col_bins; c++) {
+            const uint64_t v = cells[(size_t)r * W + (size_t)c];
+            if (!v) continue;
+            char re[24], ce[24];
+            if (r < s->row_bins) snprintf(re, sizeof re, "%lld", (long long)r * s->row_width); else strcpy(re, "overflow");
+            if (c < s->col_bins) snprintf(ce, sizeof ce, "%lld", (long long)c * s->col_width); else strcpy(ce, "overflow");
+            CSV_EMIT("%.200s,%s,%s,%llu\n", label, re, ce, (unsigned long long)v);
+        }
+    if (x->undefined) CSV_EMIT("%.200s,undefined,,%llu\n", label, (unsigned long long)x->undefined);
+    return csv_end(buf, cap, off);
+}
+
 /* ---- per-trial summaries: exact order statistics and the spread across trials (prach_run_trials_summary) ---- */
 
 static int summary_spec_ok(const prach_summary_spec *s) {

@@ -118,6 +118,16 @@ def allreduce_sojourn(sj, device=None):
     return sj
 
 
+def allreduce_xtab(xt, device=None):
+    """Merges the outcome cross-tabulations (an `Xtab` of the package: same axes, classes and groups on every rank) across ranks, in place: ONE int64 sum
+    all-reduce of the concatenated block — the cells and the summed scalars — and row_max and col_max by one max all-reduce of 2 x ngroups values."""
+    from . import XTAB_FIELDS
+    mx = np.stack([xt.scalars["row_max"], xt.scalars["col_max"]])
+    _allreduce_sums_and_max(xt._arrays() + [xt.scalars[f] for f in XTAB_FIELDS if f not in ("row_max", "col_max")], mx, device)
+    xt.scalars["row_max"][...], xt.scalars["col_max"][...] = mx[0], mx[1]
+    return xt
+
+
 def allreduce_trace(tr, device=None):
     """Merges the per-subframe preamble traces (a `Trace` of the package: same groups, bins and width on every rank) across ranks, in place: ONE int64 sum
     all-reduce of the concatenated block — the four series and the summed scalars — and calls_max by a max all-reduce of ngroups values."""

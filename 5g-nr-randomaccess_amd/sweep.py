@@ -50,6 +50,12 @@ def main(argv=None):
                     "totalPreambleTxop and collisionPreambles, by time — one group per sweep point, to this CSV file (not together with --cdf, --timeline, "
                     "--sojourn or --ci)")
     ap.add_argument("--trace-bin", type=int, default=5, help="width of a trace bin in ms; the bins cover the horizon")
+    ap.add_argument("--xtab", default=None, help="write the outcome cross-tabulation — by default what became of the UEs (idle, served, in a backoff, in a RAR "
+                    "window, granted, waiting out a Msg3 timeout) by when they arrived — one group per sweep point, to this CSV file (not together with --cdf, "
+                    "--timeline, --sojourn, --ci or --trace)")
+    ap.add_argument("--xtab-rows", default="arrival:500", help="FIELD[:WIDTH[:BINS]], FIELD one of one, arrival, sojourn, completion, timer, ptc, failcount, age, state")
+    ap.add_argument("--xtab-cols", default="state:1:7", help="FIELD[:WIDTH[:BINS]]")
+    ap.add_argument("--xtab-who", default="all", choices=("served", "unserved", "arrived", "all"), help="the UEs that enter the table")
     ap.add_argument("--same-device", action="store_true", help="rehearsal on one GPU: every rank uses cuda:0")
     args = ap.parse_args(argv)
     if args.cdf and args.timeline:
@@ -60,6 +66,8 @@ def main(argv=None):
         ap.error("--ci cannot be combined with --cdf, --timeline or --sojourn: one reduction per call")
     if args.trace and (args.cdf or args.timeline or args.sojourn or args.ci):
         ap.error("--trace cannot be combined with --cdf, --timeline, --sojourn or --ci: one reduction per call")
+    if args.xtab and (args.cdf or args.timeline or args.sojourn or args.ci or args.trace):
+        ap.error("--xtab cannot be combined with --cdf, --timeline, --sojourn, --ci or --trace: one reduction per call")
     ci_levels = [int(x) for x in args.ci_levels.split(",")]
     if not 1 <= len(ci_levels) <= 8 or any(m < 1 or m > 1000 for m in ci_levels):
         ap.error("--ci-levels takes 1 to 8 levels between 1 and 1000")
@@ -106,6 +114,12 @@ def main(argv=None):
     elif args.trace:
         tr_bins = -(-10000 // args.trace_bin)  # Beta arrivals: 10 000 subframes
         red = (pkg.Trace(len(points), tr_bins, args.trace_bin), eng.run_trials_trace, (tr_bins, args.trace_bin), distmod.allreduce_trace, pkg.trace_csv, args.trace)
+    elif args.xtab:
+        try:
+            xa = (pkg.xtab_parse_axis(args.xtab_rows, 10000), pkg.xtab_parse_axis(args.xtab_cols, 10000), pkg.XTAB_WHO[args.xtab_who])
+        except ValueError as err:
+            ap.error(str(err))
+        red = (pkg.Xtab(len(points), *xa), eng.run_trials_xtab, xa, distmod.allreduce_xtab, pkg.xtab_csv, args.xtab)
     ci_rows = []
     for a in range(0, len(mine), CH):
         part = mine[a:a + CH]

@@ -129,6 +129,8 @@ typedef struct prach_timing {
     int32_t trial_kernel_reruns; /* of fallback_trials: trials that were (also) rerun on the one-workgroup, index-ordered trial_kernel */
     int32_t noma_host_ues;       /* NOMA_C, Philox: UEs of the device-built activeUE table that the host recomputed with its libm (a value inside the
                                     device math library's error band of a rounding / comparison boundary: ~1e-6 of the UEs) */
+    double xtab_ms;              /* HIP-event time of the cross-tabulation kernel launches (prach_run_trials_xtab) of the last call; 0 in every other call (an
+                                    xtab call leaves every other *_ms of a reduction 0) */
     double trace_ms;             /* HIP-event time of the trace kernel launches (prach_run_trials_trace) of the last call; 0 in every other call (a trace call leaves
                                     summary_ms, dist_ms, timeline_ms and sojourn_ms 0) */
     double summary_ms;           /* HIP-event time of the summary kernel launches (prach_run_trials_summary) of the last call; 0 in every other call (a summary call
@@ -280,6 +282,67 @@ int prach_run_trials_sojourn(prach_engine *, const prach_cfg *cfgs, int n, prach
                              const prach_sojourn_spec *spec, const int32_t *group, prach_sojourn *sj, uint64_t *hist, uint64_t *row_arrived,
                              uint64_t *row_delay_overflow);
 
+/* Outcome cross-tabulation per trial group, built on the device: a two-axis table over a FIXED MENU of per-UE quantities, with a choice of WHICH UEs enter.
+ * The other reductions describe the UEs a trial served; this one also says what became of the ones it left behind.  Everything comes from the 64-byte log
+ * record, the arrival schedule and the trial's `steps`: nothing new is simulated.  a(i), c(i), ARRIVED and successful are those of the timeline block above;
+ * E = min(prach_result.steps, maxTime) is the subframe the run ended at.  Every UE is in exactly one CLASS, the bits of `who`:
+ *   PRACH_XTAB_IDLE      active == -1 (not arrived)
+ *   PRACH_XTAB_SERVED    arrived and msg4Flag == 1
+ *   PRACH_XTAB_UNSERVED  arrived and not served
+ * `who` is a non-empty subset; a UE outside it counts in `ues` and in its class scalar only.  FIELDS: the value of UE i, or UNDEFINED for it:
+ *   0 ONE         0                              every UE
+ *   1 ARRIVAL     a(i)                           arrived
+ *   2 SOJOURN     c(i) - a(i)                    served
+ *   3 COMPLETION  c(i)                           served
+ *   4 TIMER       logged timer                   arrived (unserved: the time since its current cycle began)
+ *   5 PTC         logged preambleTxCounter       arrived (the transmissions of the current cycle)
+ *   6 FAILCOUNT   logged failCount               arrived (cycles started over; Beta.c logs 0)
+ *   7 AGE         E - a(i)                       arrived (the time in the system when the run ended)
+ *   8 STATE       0 idle, 1 served, then for the unserved: 2 active == 1 && nowBackoff > 0 (in a backoff), 3 active == 1 && nowBackoff <= 0 (in a RAR
+ *                 window), 4 active == 2 && connectionRequest < 48 (granted, Msg3 pending), 5 active == 2 && connectionRequest >= 48 (waiting out the
+ *                 Msg3 timeout), 6 anything else (no trial produces it)                          every UE
+ * ONE RULE for bad values: a NEGATIVE value is UNDEFINED (idle UEs log timer = txTime = -1; an E below an arrival makes that UE's AGE undefined — nothing is
+ * refused and nothing is clipped).
+ * An axis has `bins` regular bins of `width` (bin b covers [b * width, (b + 1) * width)) plus ONE OVERFLOW BIN at index `bins`; the table of a group is
+ * (row_bins + 1) x (col_bins + 1) 64-bit cells, row-major.  A UE in `who` whose row and column values are both defined adds 1 to exactly one cell; one with an
+ * undefined value adds 1 to `undefined` and to no cell: sum(cells) + undefined == selected, always.  Integers only: device, host, forked workers and ranks
+ * merge exactly in any order.  Beta.c and RandomAccessWithNOMA.c only, like the timeline.
+ * A fine ARRIVAL x SOJOURN table remains prach_run_trials_sojourn's job (its kernel windows such a table by arrival row; this one does not). */
+#define PRACH_XTAB_SERVED   1
+#define PRACH_XTAB_UNSERVED 2
+#define PRACH_XTAB_IDLE     4
+#define PRACH_XTAB_MAX_BINS 65536
+enum { PRACH_XTAB_ONE = 0, PRACH_XTAB_ARRIVAL, PRACH_XTAB_SOJOURN, PRACH_XTAB_COMPLETION, PRACH_XTAB_TIMER, PRACH_XTAB_PTC, PRACH_XTAB_FAILCOUNT, PRACH_XTAB_AGE,
+       PRACH_XTAB_STATE, PRACH_XTAB_NFIELDS };
+
+typedef struct prach_xtab_spec {
+    int32_t who;                              /* PRACH_XTAB_* class bits, not 0 */
+    int32_t row_field, row_width, row_bins;   /* a field id, width >= 1, 1 .. PRACH_XTAB_MAX_BINS regular bins */
+    int32_t col_field, col_width, col_bins;
+    int32_t ngroups;                          /* number of output tables */
+    int32_t reserved[2];                      /* 0 */
+} prach_xtab_spec;
+
+typedef struct prach_xtab {          /* one per group */
+    uint64_t trials;                 /* trials accumulated (status PRACH_OK) */
+    uint64_t ues;                    /* sum of their nUE */
+    uint64_t idle, served, unserved; /* the three classes, counted regardless of `who`: idle + served + unserved == ues */
+    uint64_t selected;               /* UEs whose class is in `who` */
+    uint64_t binned, undefined;      /* ... of which: in a cell (overflow cells included) / with an undefined row or column value */
+    uint64_t row_sum, col_sum;       /* sums of the two values over the binned UEs, unbinned */
+    int64_t  row_max, col_max;       /* the largest of each over the binned UEs; -1 if binned == 0 */
+} prach_xtab;
+
+/* prach_run_trials plus the cross-tabulation, with the contract of prach_run_trials_sojourn: trial k is added to group group[k] (group == NULL: trial k is
+ * group k and ngroups must equal n); xt[ngroups] and cells[ngroups][row_bins + 1][col_bins + 1] are caller-owned and OVERWRITTEN; a trial whose final status
+ * is not PRACH_OK contributes nothing; a trial the engine reruns contributes once, from the launch whose result is kept.  prach::xtab_kernel
+ * (csrc/prach_xtab.hip) reduces the per-UE log records the simulation kernels write ON THE DEVICE, as the timeline does.
+ * PRACH_ERR_ARG: a NULL output, an unknown field or class bit, an empty `who`, a bin count or width out of range, a non-zero reserved word, a group id out of
+ * range, NULL group with ngroups != n;
+ * PRACH_ERR_UNSUPPORTED: any NOMA_C cfg (before anything is launched); ngroups * (row_bins + 1) * (col_bins + 1) > 2^27 words (1 GiB of device buffer). */
+int prach_run_trials_xtab(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_xtab_spec *spec,
+                          const int32_t *group, prach_xtab *xt, uint64_t *cells);
+
 /* Per-trial summary, built on the device: ONE row per TRIAL — counts, sums, maxima and EXACT order statistics of the sojourn, of `timer` and of
  * preambleTxCounter over the trial's successful UEs — so that the spread from seed to seed of any of them, a percentile included, can be stated
  * (prach_summary_stats).  The pooled reductions above cannot give that: they add trials into shared bins.  a(i), c(i), ARRIVED, successful and RESTARTED are
@@ -373,6 +436,8 @@ int prach_run_trials_trace(prach_engine *, const prach_cfg *cfgs, int n, prach_r
  *                   (the default: measured 15-20x faster on the sweep grids)
  *   "sojourn_scheme" prach::sojourn_kernel's binning: 0 every contribution is a 64-bit agent-scope global atomic, 1 rows of the histogram privatised in LDS
  *                   per workgroup (the default: measured 95x faster on the sweep grids)
+ *   "xtab_scheme"   prach::xtab_kernel's binning: 0 every contribution is a 64-bit agent-scope global atomic, 1 a table of at most
+ *                   prach_xtab_window_words() cells privatised in LDS per workgroup, a larger one as under 0 (the default)
  *   "trace_scheme"  prach::trace_kernel's binning: 0 every contribution is a 64-bit agent-scope global atomic, 1 a tile's bins added up in an LDS window first
  *                   (the default)
  *   "summary_threads" prach::summary_kernel's workgroup: 512 or 1024 threads (0 = the default, 1024)
@@ -473,6 +538,24 @@ size_t prach_sojourn_format_csv(const prach_sojourn_spec *, const prach_sojourn 
                                 const uint64_t *row_delay_overflow, const char *label, char *buf, size_t cap);
 int prach_sojourn_tile_ues(void);     /* UEs of one trial that one workgroup of prach::sojourn_kernel reduces (tests place sizes around it) */
 int prach_sojourn_window_words(void); /* 32-bit cells of the LDS window of prach::sojourn_kernel (sojourn_scheme 1): it holds window_words / delay_bins rows */
+
+/* Cross-tabulation, host side (no device needed).  xt and cells [row_bins + 1][col_bins + 1]: ONE group.
+ * prach_xtab_accumulate_logs ADDS one trial's per-UE log to a group: THE DEFINITION prach::xtab_kernel equals, integer for integer.  steps is the trial's
+ * prach_result.steps.  PRACH_ERR_UNSUPPORTED: a NOMA_C cfg.  PRACH_ERR_ARG: a bad spec or cfg, nUE != cfg->nUE (no log content is refused: a bad value is
+ * UNDEFINED). */
+int prach_xtab_accumulate_logs(const prach_xtab_spec *, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_xtab *xt, uint64_t *cells);
+/* counts and sums are added, row_max and col_max are the maxima */
+void prach_xtab_merge(const prach_xtab_spec *, prach_xtab *into, uint64_t *cells_into, const prach_xtab *from, const uint64_t *cells_from);
+/* the rule of prach_sojourn_quantile along the column axis of one row (0 .. row_bins, the overflow row included), or pooled over all rows (row == -1): the
+ * lower edge of the first regular column bin whose cumulative count reaches max(1, ceil(q * n)), n = the row's UEs including its overflow column; -1 if
+ * n == 0, that rank lies in the overflow column, or an argument is bad */
+int64_t prach_xtab_quantile(const prach_xtab_spec *, const uint64_t *cells, int row, double q);
+/* one group as text: `label,<row lower edge>,<column lower edge>,<count>` per non-zero cell in row-major order, an overflow bin's edge spelled `overflow`;
+ * behind them `label,undefined,,<count>` where undefined is non-zero; lines end in \n.  Returns the length needed (without the terminating 0); the text is
+ * written only if it fits cap with its terminator. */
+size_t prach_xtab_format_csv(const prach_xtab_spec *, const prach_xtab *, const uint64_t *cells, const char *label, char *buf, size_t cap);
+int prach_xtab_tile_ues(void);     /* UEs of one trial that one workgroup of prach::xtab_kernel reduces (tests place sizes around it) */
+int prach_xtab_window_words(void); /* the largest table, in cells, that prach::xtab_kernel privatises in LDS (xtab_scheme 1) */
 
 /* Per-trial summaries, host side (no device needed).
  * prach_summary_from_logs OVERWRITES *row with the summary of one trial's per-UE log: THE DEFINITION prach::summary_kernel equals, integer for integer (it
