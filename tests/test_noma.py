@@ -356,6 +356,30 @@ def test_gpu_noma_glibc_equals_oracle(pkg, ob, engine):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("radius", [36.0, 40.0])
+def test_gpu_noma_glibc_small_cell_many_draws_per_ue(pkg, ob, engine, radius):
+    """A cell radius just outside the 35 m exclusion zone in glibc mode: activeUE's distance loop redraws about 18 (36.0) / 4 (40.0) times per UE, so the
+    arrivals of a slot take 8 to 21 stream values each instead of four, all different, and the start-position fix-up of noma_glibc_trial_kernel (rounds of
+    noma_active_ue + block_excl_scan until no start moves) has starts to move in every slot.  Every counter and every logged field of every UE against the
+    NOMA oracle in glibc mode (the whole-trial oracle of this variant; ob.run_trial is Beta.c's and WithNOMA.c's)."""
+    nUE, seed = 3000, 11
+    cfg = pkg.make_cfg(nUE, variant=pkg.VARIANT_NOMA_C, rng_mode=pkg.RNG_GLIBC, seed=seed, cellRadius=radius)
+    (res,), (logs,) = engine.run_trials([cfg], want_logs=True)
+    tm = engine.timing()
+    print(f"cellRadius {radius}: fallback_trials {tm.fallback_trials}, noma_host_ues {tm.noma_host_ues}, draws {res.draws} ({res.draws / nUE:.1f} per UE)")
+    ocfg = ob.make_noma_cfg(nUE, cellRadius=radius)
+    ores, oues = ob.noma_run_trial(ocfg, ob.Rng(ob.RNG_GLIBC, seed))
+    assert (res.status, res.nSuccessUE, res.sumTimer, res.preambleTxCount, res.failCounts, res.activeCheck, res.draws, res.time_exit, res.steps) == \
+           (0, ores.nSuccessUE, ores.delay, ores.nTxP, ores.raFailedUEs, ores.activeCheck, ores.draws, ores.time_exit, ores.steps), radius
+    assert res.draws > (20 if radius == 36.0 else 6) * nUE  # activation alone takes that many
+    a = np.frombuffer(logs, dtype=np.int32).reshape(-1, 16)
+    b = np.frombuffer(oues, dtype=np.dtype([("i", np.int32, 16), ("g", np.float64)]))["i"]
+    diff = np.where((a != b).any(axis=1))[0]
+    assert diff.size == 0, (radius, diff[:5], a[diff[:3]], b[diff[:3]])
+    assert res.nSuccessUE > 0 and pkg.format_noma_line(cfg, res) == ob.noma_format_line(ocfg, ores)
+
+
+@pytest.mark.gpu
 def test_gpu_noma_radius_just_above_the_exclusion_zone(pkg, ob, engine, capfd):
     """cellRadius = 35.01 is a valid configuration (NOMA.c:167-172 redraws the distance until it exceeds 35 m: ~1 750 draws per UE here): the device's redraw
     loop gives up after 4 096 iterations and flags such a UE for the host — every tenth one, more than the kernel's list holds.  The engine then builds the
