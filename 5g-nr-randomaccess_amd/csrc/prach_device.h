@@ -174,10 +174,14 @@ int run_noma_glibc_batch(hipStream_t stream, const prach_cfg *const *cfgs, int n
                          double *kernel_ms, int *rcs, const DistSink *sinks = nullptr);
 extern "C" void prach_internal_dist_add_ue(const prach_dist_spec *spec, prach_dist *d, uint64_t *delay_hist, uint64_t *ptc_hist, int32_t timer, int32_t ptc); // prach_host.c
 
+// The reducer kernels below.  What they share is in prach_reduce_tile.h, ONE copy: the job lookup over `wg0`, the 64-bit agent-scope add and maximum, the
+// wavefront folds, the slot range of a tile of UEs with its staging rule (TILE_SCHED_CAP), and the flush of a group's scalar row — the first *_SUMS words of
+// a row are sums, the next *_MAXIMA maxima (stored + 1, so that 0 means none), both flushed only where non-zero; the counts stand next to *_SCALARS.
+//
 // prach_dist.hip: the distributions of a launch's accepted trials (prach_run_trials_dist).  One job per trial; a workgroup reduces one tile of
 // DIST_TILE UEs of one trial in LDS and flushes its non-zero bins into the call's buffers with 64-bit device-scope atomics.
 constexpr int DIST_TILE = 8192, DIST_THREADS = 256;
-constexpr int DIST_SCALARS = 8; // per group: success, delay_overflow, delay_sum, ptc_sum, delay_max + 1 (0: no successful UE), 3 spare
+constexpr int DIST_SCALARS = 8, DIST_SUMS = 4, DIST_MAXIMA = 1; // per group: success, delay_overflow, delay_sum, ptc_sum | delay_max + 1 (0: no successful UE) | 3 spare
 struct DistJob {
     const int *timers; // [nUE] the delay of a successful UE, INT_MIN otherwise
     const int *ptc;    // form 0: [nUE] preambleTxCounter; form 1: the 32-byte records of prach::batch_kernel (word 5 of a record, low half)
@@ -193,7 +197,7 @@ hipError_t launch_dist_kernel(const DistJob *jobs, int njobs, int workgroups, in
 constexpr int TL_TILE = 8192, TL_THREADS = 256, TL_WINDOW = 2048;
 constexpr int TL_MAX_SOJOURN = 60000 + 6; // c(i) - a(i) at most: Uniform arrivals run 60 000 subframes, the completion is 6 behind the last Msg3
 static_assert((unsigned long long)TL_TILE * TL_MAX_SOJOURN < (1ull << 32), "a 32-bit LDS counter holds the sojourn sum, and the timer sum, of a whole tile");
-constexpr int TL_SCALARS = 8; // per group: arrived, success, restarted, arrival_overflow, done_overflow, sojourn_sum, timer_sum, done_max + 1 (0: no successful UE)
+constexpr int TL_SCALARS = 8, TL_SUMS = 7, TL_MAXIMA = 1; // per group: arrived, success, restarted, arrival_overflow, done_overflow, sojourn_sum, timer_sum | done_max + 1 (0: no successful UE)
 struct TimelineJob {
     const int4 *logs; // [nUE][4] prach_ue_log records
     const int *sched; // [nslots] activeCheck after the arrival update of every access slot
@@ -209,7 +213,7 @@ hipError_t launch_timeline_kernel(const TimelineJob *jobs, int njobs, int workgr
 // straight to the call's buffers with 64-bit agent-scope atomics.
 constexpr int SJ_WINDOW_WORDS = 28672; // 112 KiB of cells, fourteen 500 ms rows of 2002 five-millisecond bins: measured against 8192 and 16384 words
 static_assert((unsigned long long)TL_TILE < (1ull << 32), "a 32-bit LDS counter holds what one tile adds to a cell or a row: at most one per UE");
-constexpr int SJ_SCALARS = 8; // per group: arrived, success, restarted, arrival_overflow, delay_overflow, sojourn_sum, sojourn_max + 1 (0: no successful UE), 1 spare
+constexpr int SJ_SCALARS = 8, SJ_SUMS = 6, SJ_MAXIMA = 1; // per group: arrived, success, restarted, arrival_overflow, delay_overflow, sojourn_sum | sojourn_max + 1 (0: no successful UE) | 1 spare
 struct SojournOut { unsigned long long *hist, *row_arrived, *row_overflow, *scalars; }; // [ngroups][rows][delay_bins], [ngroups][rows] twice, [ngroups][SJ_SCALARS]
 hipError_t launch_sojourn_kernel(const TimelineJob *jobs, int njobs, int workgroups, int rows, int row_ms, int delay_bins, int delay_bin_ms, int scheme, SojournOut out,
                                  hipStream_t stream);
@@ -220,7 +224,7 @@ hipError_t launch_sojourn_kernel(const TimelineJob *jobs, int njobs, int workgro
 // with 64-bit agent-scope atomics.
 constexpr int XT_WINDOW_WORDS = SJ_WINDOW_WORDS; // the sojourn kernel's measured window
 static_assert((unsigned long long)TL_TILE < (1ull << 32), "a 32-bit LDS counter holds what one tile adds to a cell: at most one per UE");
-constexpr int XT_SCALARS = 16; // per group: idle, served, unserved, selected, binned, row_sum, col_sum, row_max + 1, col_max + 1 (0: nothing binned), 7 spare
+constexpr int XT_SCALARS = 16, XT_SUMS = 7, XT_MAXIMA = 2; // per group: idle, served, unserved, selected, binned, row_sum, col_sum | row_max + 1, col_max + 1 (0: nothing binned) | 7 spare
 struct XtabAxes { int who, row_field, row_width, row_bins, col_field, col_width, col_bins; };
 struct XtabOut { unsigned long long *cells, *scalars; }; // [ngroups][row_bins + 1][col_bins + 1], [ngroups][XT_SCALARS]
 hipError_t launch_xtab_kernel(const TimelineJob *jobs, int njobs, int workgroups, XtabAxes ax, int scheme, XtabOut out, hipStream_t stream);
@@ -240,7 +244,7 @@ hipError_t launch_summary_kernel(const TimelineJob *jobs, int njobs, SummaryLeve
 // and load.  A tile covers at most TR_TILE consecutive bins (bin = t / bin_ms): scheme 1 adds them up in an LDS window of 64-bit counters anchored at the
 // tile's first bin and flushes the non-zero ones, scheme 0 sends every contribution straight to the call's buffers; both with 64-bit agent-scope atomics.
 constexpr int TR_TILE = 2048, TR_THREADS = 256;
-constexpr int TR_SCALARS = 8; // per group: subframes, calls, singles, txop, collisions, overflow_calls, calls_max + 1 (0: no subframe), 1 spare
+constexpr int TR_SCALARS = 8, TR_SUMS = 6, TR_MAXIMA = 1; // per group: subframes, calls, singles, txop, collisions, overflow_calls | calls_max + 1 (0: no subframe) | 1 spare
 struct TraceJob {
     const int4 *rows; // [steps] calls, singles, txop, collisions of every subframe
     int steps, group, wg0, pad; // wg0: the first workgroup of this job

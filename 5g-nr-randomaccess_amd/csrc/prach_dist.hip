@@ -10,7 +10,7 @@
 // SCHEME: how the preamble counts are binned (the delays are spread over tens of bins and more; the counts of an overloaded trial sit in a handful,
 // and same-address LDS atomics serialise): 0 one LDS add per UE; 1 the same into a copy of the 256 bins per wavefront; 2 one LDS add per distinct
 // value of a wavefront (match and aggregate).  Engine option "dist_scheme"; DESIGN.md 4 has the measurements.
-#include "prach_device.h"
+#include "prach_reduce_tile.h"
 
 #include <limits.h>
 
@@ -31,18 +31,12 @@ __global__ __launch_bounds__(DIST_THREADS) void dist_kernel(const DistJob *__res
     unsigned *const lptc = lds + bins;
     unsigned long long *const lsc = reinterpret_cast<unsigned long long *>(lds + ((bins + PB * COPIES + 1) & ~1));
 
-    // the job of this workgroup: the last one whose first workgroup is not behind it
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].wg0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const DistJob J = jobs[lo];
+    const DistJob J = job_of_workgroup(jobs, njobs);
     const int first = ((int)blockIdx.x - J.wg0) * DIST_TILE;
     const int end = min(J.nUE, first + DIST_TILE);
 
     for (int b = tid; b < bins + PB * COPIES; b += DIST_THREADS) lds[b] = 0;
-    if (tid < 5) lsc[tid] = 0;
+    if (tid < DIST_SUMS + DIST_MAXIMA) lsc[tid] = 0;
     __syncthreads();
 
     unsigned nsucc = 0, nover = 0, dmax1 = 0;
@@ -92,11 +86,7 @@ __global__ __launch_bounds__(DIST_THREADS) void dist_kernel(const DistJob *__res
             }
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        nsucc += __shfl_down(nsucc, d); nover += __shfl_down(nover, d); dsum += __shfl_down(dsum, d); psum += __shfl_down(psum, d);
-        dmax1 = max(dmax1, (unsigned)__shfl_down(dmax1, d));
-    }
+    nsucc = fold_sum(nsucc); nover = fold_sum(nover); dsum = fold_sum(dsum); psum = fold_sum(psum); dmax1 = fold_max(dmax1);
     if (lane == 0 && nsucc) {
         atomicAdd(&lsc[0], (unsigned long long)nsucc); atomicAdd(&lsc[1], (unsigned long long)nover); atomicAdd(&lsc[2], dsum); atomicAdd(&lsc[3], psum);
         atomicMax(&lsc[4], (unsigned long long)dmax1);
@@ -106,19 +96,17 @@ __global__ __launch_bounds__(DIST_THREADS) void dist_kernel(const DistJob *__res
     // flush: only what this tile touched
     unsigned long long *const gdh = dh + (size_t)J.group * (size_t)bins;
     unsigned long long *const gph = ph + (size_t)J.group * PB;
-    unsigned long long *const gsc = sc + (size_t)J.group * DIST_SCALARS;
     for (int b = tid; b < bins; b += DIST_THREADS) {
         const unsigned v = ldel[b];
-        if (v) (void)__hip_atomic_fetch_add(&gdh[b], (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (v) agent_add(&gdh[b], (unsigned long long)v);
     }
     for (int b = tid; b < PB; b += DIST_THREADS) {
         unsigned v = 0;
 #pragma unroll
         for (int q = 0; q < COPIES; q++) v += lptc[q * PB + b];
-        if (v) (void)__hip_atomic_fetch_add(&gph[b], (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (v) agent_add(&gph[b], (unsigned long long)v);
     }
-    if (tid < 4 && lsc[tid]) (void)__hip_atomic_fetch_add(&gsc[tid], lsc[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid == 4 && lsc[4]) (void)__hip_atomic_fetch_max(&gsc[4], lsc[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    flush_scalars(lsc, sc + (size_t)J.group * DIST_SCALARS, DIST_SUMS, DIST_MAXIMA, tid);
 }
 
 size_t dist_lds_bytes(int bins, int scheme) {

@@ -419,48 +419,35 @@ static int noma_device_activation(prach_engine *e, const TrialDev *dparams, cons
     return PRACH_OK;
 }
 
-// What a call reduces on the device next to its results: the caller's spec, groups and outputs of prach_run_trials_dist, prach_run_trials_timeline or
-// prach_run_trials_sojourn.  The call's device buffer is a row of parts, [ngroups][words] 64-bit counters each: the arrays the caller gets as they are (dist:
-// delay_hist, ptc_hist; timeline: the five series arrivals, success, sojourn_sum, timer_sum, done; sojourn: hist, row_arrived, row_delay_overflow), then the
-// scalars the kernel keeps per group.  prach_run_trials_summary is the fourth kind: every trial is its own group and the only part is the kernel's row of
-// SM_WORDS words per trial, unpacked into the caller's prach_trial_summary rows.
-// prach_run_trials_trace is the fifth: the four series calls, singles, txop, collisions, reduced from the rows the simulation kernels write per subframe.
-// prach_run_trials_xtab is the sixth: the parts are {cells, scalars}; it takes the timeline's jobs with the trial's steps in their last word.
+// What a call reduces on the device next to its results (prach_run_trials_dist, _timeline, _sojourn, _summary, _trace, _xtab).  The call's device buffer is a
+// row of parts, [ngroups][words] 64-bit counters each: the arrays the caller gets as they are, one per part, then the scalars the kernel keeps per group,
+// which the engine unpacks into the caller's per-group structs.  Every launch of the call gets one job per trial it finished, and the kind's kernel behind
+// the simulation kernel.  What differs between the kinds is stated ONCE per kind: a block of functions behind CallCtx and its row of RED_KINDS.  The generic
+// code (reduction_begin, run_group, reduction_end, run_trials_impl) walks that row and never asks which kind it has; a new kind is an enumerator, a block and
+// a row.
 enum class Red { dist, timeline, sojourn, summary, trace, xtab };
 constexpr int RED_MAX_PARTS = 6;
 struct Reduction {
     Red kind;
     const int32_t *group; // nullable: trial k is group k
     int ngroups;
-    const prach_dist_spec *dspec; // dist
-    prach_dist *dist;
-    const prach_timeline_spec *tspec; // timeline
-    prach_timeline *tl;
-    const prach_sojourn_spec *sspec; // sojourn
-    prach_sojourn *sj;
     uint64_t *out[RED_MAX_PARTS - 1]; // the caller's arrays, one per part in front of the scalars
-    const prach_summary_spec *mspec;  // summary
-    prach_trial_summary *rows;
-    const prach_trace_spec *rspec;    // trace
-    prach_trace *tr;
-    const prach_xtab_spec *xspec;     // xtab
-    prach_xtab *xt;
+    const void *spec;                 // the caller's prach_*_spec, and its per-group structs (summary: its per-trial rows): the kind's block reads both
+    void *groups;                     // through its own casts
 };
-// words per group of every part; returns their number
-static int red_parts(const Reduction &r, size_t words[RED_MAX_PARTS]) {
-    if (r.kind == Red::summary) { words[0] = SM_WORDS; return 1; }
-    if (r.kind == Red::xtab) { words[0] = ((size_t)r.xspec->row_bins + 1) * ((size_t)r.xspec->col_bins + 1); words[1] = XT_SCALARS; return 2; }
-    if (r.kind == Red::trace) { for (int q = 0; q < 4; q++) words[q] = (size_t)r.rspec->bins; words[4] = TR_SCALARS; return 5; }
-    if (r.kind == Red::dist) { words[0] = (size_t)r.dspec->delay_bins; words[1] = PRACH_DIST_PTC_BINS; words[2] = DIST_SCALARS; return 3; }
-    if (r.kind == Red::sojourn) {
-        words[0] = (size_t)r.sspec->arrival_bins * (size_t)r.sspec->delay_bins; words[1] = words[2] = (size_t)r.sspec->arrival_bins; words[3] = SJ_SCALARS;
-        return 4;
-    }
-    for (int q = 0; q < 5; q++) words[q] = (size_t)r.tspec->bins;
-    words[5] = TL_SCALARS;
-    return 6;
-}
-static size_t red_job_bytes(Red kind) { return kind == Red::dist ? sizeof(DistJob) : kind == Red::trace ? sizeof(TraceJob) : sizeof(TimelineJob); } // (sojourn, summary and xtab take the timeline's jobs)
+struct CallCtx;
+struct JobSrc { const prach_cfg &c; const TrialLayout &L; const DevResult &dr; char *A; int group, wg0; bool batch; }; // a finished trial of a launch, as a job is filled from it (A: the arena)
+struct RedKind {
+    int (*parts)(const Reduction &, size_t words[RED_MAX_PARTS]); // words per group of every part, the scalars last; returns their number
+    size_t job_bytes; int tile;               // tile: UEs or subframes per workgroup
+    int (*fill_job)(void *job, const JobSrc &); // returns the trial's UEs or subframes: it takes ceil(that / tile) workgroups from wg0 on
+    bool device_logs, trace_rows, fast_off;   // every trial needs a device log region / trace rows; the call takes the paths that "fast" = 0 takes
+    hipError_t (*launch)(const prach_engine *e, const Reduction &, int njobs, int wgs, unsigned long long *const *d); // (jobs: e->red_jobs_d, on the host e->red_jobs_h)
+    void (*empty)(const Reduction &, size_t g, const prach_cfg *cfgs); // the caller's struct of group g before anything ran
+    int (*unpack)(const Reduction &, CallCtx &, size_t g, const unsigned long long *q); // ... and from the group's scalar words at the end of the call
+    double prach_timing::*ms;                 // where the kernel time of the call goes
+};
+const RedKind &kind_of(const Reduction &r);
 
 // What one prach_run_trials call carries from launch to launch
 struct CallCtx {
@@ -475,14 +462,14 @@ struct CallCtx {
     unsigned long long *d_part[RED_MAX_PARTS] = {}; // the call's device buffer, part by part (red_parts)
     std::vector<uint64_t> trials, ues;        // per group, counted on the host as launches are accepted
     int group_of(int k) const { return red->group ? red->group[k] : k; }
-    bool reads_device_logs() const { return red && red->kind != Red::dist && red->kind != Red::trace; }
-    bool traces() const { return red && red->kind == Red::trace; }
+    bool reads_device_logs() const { return red && kind_of(*red).device_logs; }
+    bool traces() const { return red && kind_of(*red).trace_rows; }
     // dist only: NOMA.c in the reference's stream finishes on the host: its groups' accumulators (sized on first use)
-    const prach_dist_spec *dist_spec() const { return red && red->kind == Red::dist ? red->dspec : nullptr; }
+    const prach_dist_spec *dist_spec() const { return red && red->kind == Red::dist ? static_cast<const prach_dist_spec *>(red->spec) : nullptr; }
     std::vector<prach_dist> host_d;
     std::vector<uint64_t> host_dh, host_ph;
     DistSink sink(int k) { // the host-side accumulators of trial k's group
-        const prach_dist_spec *const spec = red->dspec;
+        const prach_dist_spec *const spec = dist_spec();
         if (host_d.empty()) {
             prach_dist z{};
             z.delay_max = -1;
@@ -494,6 +481,152 @@ struct CallCtx {
         return DistSink{spec, &host_d[g], host_dh.data() + g * (size_t)spec->delay_bins, host_ph.data() + g * PRACH_DIST_PTC_BINS};
     }
 };
+// ---- the kinds of reduction, one block each --------------------------------------------------------------------------------------------------------------
+template <class T> const T &spec_of(const Reduction &r) { return *static_cast<const T *>(r.spec); }
+template <class T> T &group_of(const Reduction &r, size_t g) { return static_cast<T *>(r.groups)[g]; }
+// the caller's struct of a group before anything ran: zeros, and -1 where a maximum over nothing stands
+template <class T, int64_t T::*...MAX> void empty_group(const Reduction &r, size_t g, const prach_cfg *) { T &t = group_of<T>(r, g); t = T{}; ((t.*MAX = -1), ...); }
+int subframes_run(const JobSrc &s) { return (int)std::min<unsigned long long>(s.dr.steps, (unsigned long long)prach_max_time(&s.c)); }
+// timeline, sojourn, summary and xtab read a trial's log records and the launch's own copy of its arrival schedule; STEPS (xtab): E of include/prach.h in the last word
+template <bool STEPS> int fill_timeline_job(void *job, const JobSrc &s) {
+    const int nslots = (prach_max_time(&s.c) + s.c.accessTime - 1) / s.c.accessTime; // (what prach_arrival_schedule fills; the table has one entry more)
+    *static_cast<TimelineJob *>(job) = TimelineJob{reinterpret_cast<const int4 *>(s.A + s.L.logs), reinterpret_cast<const int *>(s.A + s.L.sched), s.c.nUE, s.group, s.wg0, s.c.accessTime, nslots,
+                                                   STEPS ? subframes_run(s) : 0};
+    return s.c.nUE;
+}
+const TimelineJob *timeline_jobs(const prach_engine *e) { return reinterpret_cast<const TimelineJob *>(e->red_jobs_d); }
+
+// dist: delay_hist, ptc_hist | scalars; reads the timers and preamble counts the simulation kernel left in the arena, and adds what finished on the host
+int dist_parts(const Reduction &r, size_t w[]) { w[0] = (size_t)spec_of<prach_dist_spec>(r).delay_bins; w[1] = PRACH_DIST_PTC_BINS; w[2] = DIST_SCALARS; return 3; }
+int dist_fill_job(void *job, const JobSrc &s) {
+    *static_cast<DistJob *>(job) = DistJob{reinterpret_cast<const int *>(s.A + s.L.timers), reinterpret_cast<const int *>(s.A + (s.batch ? s.L.rec32 : s.L.ptc)), s.c.nUE, s.group, s.wg0, s.batch ? 1 : 0};
+    return s.c.nUE;
+}
+hipError_t dist_launch(const prach_engine *e, const Reduction &r, int njobs, int wgs, unsigned long long *const *d) {
+    const prach_dist_spec &sp = spec_of<prach_dist_spec>(r);
+    return launch_dist_kernel(reinterpret_cast<const DistJob *>(e->red_jobs_d), njobs, wgs, sp.delay_bins, sp.delay_bin_ms, (int)e->opt_dist_scheme, d[0], d[1], d[2], e->stream);
+}
+int dist_unpack(const Reduction &r, CallCtx &cx, size_t g, const unsigned long long *q) {
+    const prach_dist_spec &s = spec_of<prach_dist_spec>(r);
+    prach_dist &d = group_of<prach_dist>(r, g);
+    d.trials = cx.trials[g]; d.ues = cx.ues[g]; d.success = q[0]; d.delay_overflow = q[1]; d.delay_sum = q[2]; d.ptc_sum = q[3]; d.delay_max = (int64_t)q[4] - 1;
+    if (!cx.host_d.empty())
+        prach_dist_merge(&s, &d, r.out[0] + g * (size_t)s.delay_bins, r.out[1] + g * PRACH_DIST_PTC_BINS, &cx.host_d[g], cx.host_dh.data() + g * (size_t)s.delay_bins,
+                         cx.host_ph.data() + g * PRACH_DIST_PTC_BINS);
+    return PRACH_OK;
+}
+
+// timeline: the five series arrivals, success, sojourn_sum, timer_sum, done | scalars
+int timeline_parts(const Reduction &r, size_t w[]) { for (int q = 0; q < 5; q++) w[q] = (size_t)spec_of<prach_timeline_spec>(r).bins; w[5] = TL_SCALARS; return 6; }
+hipError_t timeline_launch(const prach_engine *e, const Reduction &r, int njobs, int wgs, unsigned long long *const *d) {
+    const prach_timeline_spec &sp = spec_of<prach_timeline_spec>(r);
+    return launch_timeline_kernel(timeline_jobs(e), njobs, wgs, sp.bins, sp.bin_ms, (int)e->opt_timeline_scheme, TimelineOut{d[0], d[1], d[2], d[3], d[4], d[5]}, e->stream);
+}
+int timeline_unpack(const Reduction &r, CallCtx &cx, size_t g, const unsigned long long *q) {
+    prach_timeline &t = group_of<prach_timeline>(r, g);
+    t.trials = cx.trials[g]; t.ues = cx.ues[g]; t.arrived = q[0]; t.success = q[1]; t.restarted = q[2]; t.arrival_overflow = q[3]; t.done_overflow = q[4];
+    t.sojourn_sum = q[5]; t.timer_sum = q[6]; t.done_max = (int64_t)q[7] - 1;
+    return PRACH_OK;
+}
+
+// sojourn: hist, row_arrived, row_delay_overflow | scalars
+int sojourn_parts(const Reduction &r, size_t w[]) {
+    const prach_sojourn_spec &sp = spec_of<prach_sojourn_spec>(r);
+    w[0] = (size_t)sp.arrival_bins * (size_t)sp.delay_bins; w[1] = w[2] = (size_t)sp.arrival_bins; w[3] = SJ_SCALARS;
+    return 4;
+}
+hipError_t sojourn_launch(const prach_engine *e, const Reduction &r, int njobs, int wgs, unsigned long long *const *d) {
+    const prach_sojourn_spec &sp = spec_of<prach_sojourn_spec>(r);
+    return launch_sojourn_kernel(timeline_jobs(e), njobs, wgs, sp.arrival_bins, sp.arrival_bin_ms, sp.delay_bins, sp.delay_bin_ms, (int)e->opt_sojourn_scheme, SojournOut{d[0], d[1], d[2], d[3]}, e->stream);
+}
+int sojourn_unpack(const Reduction &r, CallCtx &cx, size_t g, const unsigned long long *q) {
+    prach_sojourn &j = group_of<prach_sojourn>(r, g);
+    j.trials = cx.trials[g]; j.ues = cx.ues[g]; j.arrived = q[0]; j.success = q[1]; j.restarted = q[2]; j.arrival_overflow = q[3]; j.delay_overflow = q[4];
+    j.sojourn_sum = q[5]; j.sojourn_max = (int64_t)q[6] - 1;
+    return PRACH_OK;
+}
+
+// summary: every trial is its own group, and the only part is the kernel's row of SM_WORDS words per trial; ONE workgroup per job, whatever the tile
+int summary_parts(const Reduction &, size_t w[]) { w[0] = SM_WORDS; return 1; }
+hipError_t summary_launch(const prach_engine *e, const Reduction &r, int njobs, int, unsigned long long *const *d) {
+    const prach_summary_spec &sp = spec_of<prach_summary_spec>(r);
+    SummaryLevels lv{};
+    lv.nq = sp.nq;
+    for (int l = 0; l < lv.nq; l++) lv.permille[l] = sp.permille[l];
+    int max_slots = 0; // the longest schedule of the jobs
+    for (int j = 0; j < njobs; j++) max_slots = std::max(max_slots, reinterpret_cast<const TimelineJob *>(e->red_jobs_h)[j].nslots);
+    return launch_summary_kernel(timeline_jobs(e), njobs, lv, (int)e->opt_summary_threads, std::min(max_slots, summary_sched_cap()), d[0], e->stream);
+}
+void summary_empty(const Reduction &r, size_t k, const prach_cfg *cfgs) {
+    prach_trial_summary &row = group_of<prach_trial_summary>(r, k);
+    std::memset(&row, 0, sizeof(row));
+    row.status = PRACH_ERR_INTERNAL;
+    row.nUE = cfgs[k].nUE;
+    row.sojourn_max = row.timer_max = row.ptc_max = -1;
+    std::memset(row.q, 0xff, sizeof(row.q)); // -1
+}
+int summary_unpack(const Reduction &r, CallCtx &cx, size_t k, const unsigned long long *words) { // status and nUE from the host, the rest from the one launch that accepted the trial
+    prach_trial_summary &row = group_of<prach_trial_summary>(r, k);
+    row.status = cx.results[k].status; // (everything else is still the empty row)
+    if (row.status != PRACH_OK) return PRACH_OK;
+    if (cx.trials[k] != 1) return row.status = PRACH_ERR_INTERNAL; // (no launch reduced this trial, or two did)
+    const long long *const q = reinterpret_cast<const long long *>(words);
+    row.arrived = (int32_t)q[0]; row.success = (int32_t)q[1]; row.restarted = (int32_t)q[2];
+    row.range_errors = (int32_t)std::min<long long>(q[3] + q[4] + q[5], INT32_MAX);
+    row.sojourn_sum = q[6]; row.timer_sum = q[7]; row.ptc_sum = q[8];
+    row.sojourn_max = (int32_t)q[9]; row.timer_max = (int32_t)q[10]; row.ptc_max = (int32_t)q[11];
+    for (int x = 0; x < 3; x++)
+        for (int l = 0; l < spec_of<prach_summary_spec>(r).nq; l++) row.q[x][l] = q[3 + x] ? -1 : (int32_t)q[12 + x * PRACH_SUMMARY_MAX_Q + l];
+    return row.range_errors ? PRACH_ERR_INTERNAL : PRACH_OK; // (a value the kernel cannot rank: no trial produces one)
+}
+
+// trace: the four series calls, singles, txop, collisions | scalars; reads the rows the simulation kernels write per subframe, which prach::lcluster_kernel does
+// not (its source and its speed stay what they are): the call takes the paths that "fast" = 0 takes
+int trace_parts(const Reduction &r, size_t w[]) { for (int q = 0; q < 4; q++) w[q] = (size_t)spec_of<prach_trace_spec>(r).bins; w[4] = TR_SCALARS; return 5; }
+int trace_fill_job(void *job, const JobSrc &s) { // the rows of the subframes [0, steps): what this launch's kernel wrote for the trial, and the zeros behind time_exit are never read
+    const int steps = subframes_run(s);
+    *static_cast<TraceJob *>(job) = TraceJob{reinterpret_cast<const int4 *>(s.A + s.L.trace), steps, s.group, s.wg0, 0};
+    return steps;
+}
+hipError_t trace_launch(const prach_engine *e, const Reduction &r, int njobs, int wgs, unsigned long long *const *d) {
+    const prach_trace_spec &sp = spec_of<prach_trace_spec>(r);
+    return launch_trace_kernel(reinterpret_cast<const TraceJob *>(e->red_jobs_d), njobs, wgs, sp.bins, sp.bin_ms, (int)e->opt_trace_scheme, TraceOut{d[0], d[1], d[2], d[3], d[4]}, e->stream);
+}
+int trace_unpack(const Reduction &r, CallCtx &cx, size_t g, const unsigned long long *q) {
+    prach_trace &t = group_of<prach_trace>(r, g);
+    t.trials = cx.trials[g]; t.subframes = q[0]; t.calls = q[1]; t.singles = q[2]; t.txop = q[3]; t.collisions = q[4]; t.overflow_calls = q[5]; t.calls_max = (int64_t)q[6] - 1;
+    return PRACH_OK;
+}
+
+// xtab: cells | scalars; the timeline's jobs with E = min(steps, maxTime) in their last word
+int xtab_parts(const Reduction &r, size_t w[]) {
+    const prach_xtab_spec &x = spec_of<prach_xtab_spec>(r);
+    w[0] = ((size_t)x.row_bins + 1) * ((size_t)x.col_bins + 1); w[1] = XT_SCALARS;
+    return 2;
+}
+hipError_t xtab_launch(const prach_engine *e, const Reduction &r, int njobs, int wgs, unsigned long long *const *d) {
+    const prach_xtab_spec &x = spec_of<prach_xtab_spec>(r);
+    return launch_xtab_kernel(timeline_jobs(e), njobs, wgs, XtabAxes{x.who, x.row_field, x.row_width, x.row_bins, x.col_field, x.col_width, x.col_bins}, (int)e->opt_xtab_scheme, XtabOut{d[0], d[1]}, e->stream);
+}
+int xtab_unpack(const Reduction &r, CallCtx &cx, size_t g, const unsigned long long *q) {
+    prach_xtab &x = group_of<prach_xtab>(r, g);
+    x.trials = cx.trials[g]; x.ues = cx.ues[g]; x.idle = q[0]; x.served = q[1]; x.unserved = q[2]; x.selected = q[3]; x.binned = q[4];
+    x.undefined = q[3] - q[4]; x.row_sum = q[5]; x.col_sum = q[6]; x.row_max = (int64_t)q[7] - 1; x.col_max = (int64_t)q[8] - 1;
+    return PRACH_OK;
+}
+
+// in the order of enum class Red:           parts, job bytes, tile, job, device logs, trace rows, "fast" off, launch, empty, unpack, prach_timing field
+const RedKind RED_KINDS[] = {
+    {dist_parts, sizeof(DistJob), DIST_TILE, dist_fill_job, false, false, false, dist_launch, empty_group<prach_dist, &prach_dist::delay_max>, dist_unpack, &prach_timing::dist_ms},
+    {timeline_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<false>, true, false, false, timeline_launch, empty_group<prach_timeline, &prach_timeline::done_max>, timeline_unpack, &prach_timing::timeline_ms},
+    {sojourn_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<false>, true, false, false, sojourn_launch, empty_group<prach_sojourn, &prach_sojourn::sojourn_max>, sojourn_unpack, &prach_timing::sojourn_ms},
+    {summary_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<false>, true, false, false, summary_launch, summary_empty, summary_unpack, &prach_timing::summary_ms},
+    {trace_parts, sizeof(TraceJob), TR_TILE, trace_fill_job, false, true, true, trace_launch, empty_group<prach_trace, &prach_trace::calls_max>, trace_unpack, &prach_timing::trace_ms},
+    {xtab_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, xtab_launch, empty_group<prach_xtab, &prach_xtab::row_max, &prach_xtab::col_max>, xtab_unpack, &prach_timing::xtab_ms},
+};
+static_assert(sizeof(RED_KINDS) / sizeof(RED_KINDS[0]) == (size_t)Red::xtab + 1, "one row per kind");
+const RedKind &kind_of(const Reduction &r) { return RED_KINDS[(int)r.kind]; }
+
 // How a rerun's launch differs from the first one
 struct LaunchOpts {
     bool full_calendars = false; // batch kernel: lists of nUE entries, which cannot fill (trials that filled a calendar list)
@@ -783,51 +916,22 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
     bool red_launched = false;
     if (cx.red) {
         const Reduction &R = *cx.red;
-        const bool trc = R.kind == Red::trace;
-        const bool tl = R.kind != Red::dist && !trc; // (the jobs and the tile of the timeline are the sojourn's too; the summary takes the jobs, and one workgroup per job)
-        int njobs = 0, wgs = 0, max_slots = 0;
+        const RedKind &K = kind_of(R);
+        int njobs = 0, wgs = 0;
         for (int k = 0; k < m; k++) {
             const DevResult &dr = drs[k];
             if (dr.status != PRACH_OK || (noma && dr.hard_error == NOMA_AMBIGUOUS)) continue;
             const prach_cfg &c = cfgs[idx[k]];
-            const TrialLayout &L = LL.t[k];
             const int g = cx.group_of(idx[k]);
-            if (trc) { // the rows of the subframes [0, steps): what this launch's kernel wrote for the trial, and the zeros behind time_exit are never read
-                const int steps = (int)std::min<unsigned long long>(dr.steps, (unsigned long long)prach_max_time(&c));
-                reinterpret_cast<TraceJob *>(e->red_jobs_h)[njobs++] = TraceJob{reinterpret_cast<const int4 *>(A + L.trace), steps, g, wgs, 0};
-                wgs += (steps + TR_TILE - 1) / TR_TILE;
-                cx.trials[(size_t)g]++;
-                cx.ues[(size_t)g] += (uint64_t)c.nUE;
-                continue;
-            }
-            if (tl) {
-                const int nslots = (prach_max_time(&c) + c.accessTime - 1) / c.accessTime; // (what prach_arrival_schedule fills; the table has one entry more)
-                max_slots = std::max(max_slots, nslots);
-                reinterpret_cast<TimelineJob *>(e->red_jobs_h)[njobs++] = TimelineJob{reinterpret_cast<const int4 *>(A + L.logs), reinterpret_cast<const int *>(A + L.sched), c.nUE, g, wgs, c.accessTime, nslots,
-                                                                                      R.kind == Red::xtab ? (int)std::min<unsigned long long>(dr.steps, (unsigned long long)prach_max_time(&c)) : 0}; // (xtab: E of include/prach.h)
-            } else
-                reinterpret_cast<DistJob *>(e->red_jobs_h)[njobs++] = DistJob{reinterpret_cast<const int *>(A + L.timers), reinterpret_cast<const int *>(A + (batch ? L.rec32 : L.ptc)), c.nUE, g, wgs, batch ? 1 : 0};
-            const int tile = tl ? TL_TILE : DIST_TILE;
-            wgs += (c.nUE + tile - 1) / tile;
+            const int units = K.fill_job(e->red_jobs_h + K.job_bytes * (size_t)njobs++, JobSrc{c, LL.t[k], dr, A, g, wgs, batch});
+            wgs += (units + K.tile - 1) / K.tile;
             cx.trials[(size_t)g]++;
             cx.ues[(size_t)g] += (uint64_t)c.nUE;
         }
         if (njobs > 0 && wgs > 0) {
-            unsigned long long *const *const d = cx.d_part;
-            HIPCHK(hipMemcpyAsync(e->red_jobs_d, e->red_jobs_h, red_job_bytes(R.kind) * (size_t)njobs, hipMemcpyHostToDevice, e->stream));
+            HIPCHK(hipMemcpyAsync(e->red_jobs_d, e->red_jobs_h, K.job_bytes * (size_t)njobs, hipMemcpyHostToDevice, e->stream));
             HIPCHK(hipEventRecord(e->red_ev0, e->stream));
-            if (trc) HIPCHK(launch_trace_kernel(reinterpret_cast<const TraceJob *>(e->red_jobs_d), njobs, wgs, R.rspec->bins, R.rspec->bin_ms, (int)e->opt_trace_scheme, TraceOut{d[0], d[1], d[2], d[3], d[4]}, e->stream));
-            else if (R.kind == Red::summary) {
-                SummaryLevels lv{};
-                lv.nq = R.mspec->nq;
-                for (int l = 0; l < lv.nq; l++) lv.permille[l] = R.mspec->permille[l];
-                HIPCHK(launch_summary_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, lv, (int)e->opt_summary_threads, std::min(max_slots, summary_sched_cap()), d[0], e->stream));
-            } else if (R.kind == Red::xtab) {
-                const prach_xtab_spec &x = *R.xspec;
-                HIPCHK(launch_xtab_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, wgs, XtabAxes{x.who, x.row_field, x.row_width, x.row_bins, x.col_field, x.col_width, x.col_bins}, (int)e->opt_xtab_scheme, XtabOut{d[0], d[1]}, e->stream));
-            } else if (R.kind == Red::sojourn) HIPCHK(launch_sojourn_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, wgs, R.sspec->arrival_bins, R.sspec->arrival_bin_ms, R.sspec->delay_bins, R.sspec->delay_bin_ms, (int)e->opt_sojourn_scheme, SojournOut{d[0], d[1], d[2], d[3]}, e->stream));
-            else if (tl) HIPCHK(launch_timeline_kernel(reinterpret_cast<const TimelineJob *>(e->red_jobs_d), njobs, wgs, R.tspec->bins, R.tspec->bin_ms, (int)e->opt_timeline_scheme, TimelineOut{d[0], d[1], d[2], d[3], d[4], d[5]}, e->stream));
-            else HIPCHK(launch_dist_kernel(reinterpret_cast<const DistJob *>(e->red_jobs_d), njobs, wgs, R.dspec->delay_bins, R.dspec->delay_bin_ms, (int)e->opt_dist_scheme, d[0], d[1], d[2], e->stream));
+            HIPCHK(K.launch(e, R, njobs, wgs, cx.d_part));
             HIPCHK(hipEventRecord(e->red_ev1, e->stream));
             red_launched = true;
         }
@@ -1007,9 +1111,10 @@ static int cluster_size(const prach_engine *e, const prach_cfg *cfgs, const std:
 // the engine's stream
 static int reduction_begin(prach_engine *e, CallCtx &cx, int n) {
     const Reduction &R = *cx.red;
+    const RedKind &K = kind_of(R);
     const size_t ng = (size_t)R.ngroups;
     size_t words[RED_MAX_PARTS], at[RED_MAX_PARTS], need = 0;
-    const int np = red_parts(R, words);
+    const int np = K.parts(R, words);
     for (int q = 0; q < np; q++) { at[q] = align_up(need, 256); need = at[q] + 8 * ng * words[q]; }
     if (need > e->red_cap) {
         if (e->red_buf) HIPCHK(hipFree(e->red_buf));
@@ -1017,11 +1122,11 @@ static int reduction_begin(prach_engine *e, CallCtx &cx, int n) {
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->red_buf), need));
         e->red_cap = need;
     }
-    if (red_job_bytes(R.kind) * (size_t)n > e->red_jobs_cap) {
+    if (K.job_bytes * (size_t)n > e->red_jobs_cap) {
         if (e->red_jobs_h) HIPCHK(hipHostFree(e->red_jobs_h));
         if (e->red_jobs_d) HIPCHK(hipFree(e->red_jobs_d));
         e->red_jobs_h = e->red_jobs_d = nullptr; e->red_jobs_cap = 0;
-        const size_t want = red_job_bytes(R.kind) * (size_t)(n + (n >> 2) + 64);
+        const size_t want = K.job_bytes * (size_t)(n + (n >> 2) + 64);
         HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&e->red_jobs_h), want, hipHostMallocDefault));
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->red_jobs_d), want));
         e->red_jobs_cap = want;
@@ -1035,68 +1140,24 @@ static int reduction_begin(prach_engine *e, CallCtx &cx, int n) {
     return PRACH_OK;
 }
 // ONE copy-out per part at the end of the call (every reduction kernel has completed: run_group waits for its own); the scalars are unpacked group by
-// group, and dist adds what finished on the host
+// group by the kind; the last failure is the call's
 static int reduction_end(prach_engine *e, CallCtx &cx) {
     const Reduction &R = *cx.red;
+    const RedKind &K = kind_of(R);
     const size_t ng = (size_t)R.ngroups;
     size_t words[RED_MAX_PARTS];
-    const int np = red_parts(R, words);
+    const int np = K.parts(R, words);
     const size_t nsc = words[np - 1];
     std::vector<unsigned long long> sc(ng * nsc);
     HIPCHK(hipStreamSynchronize(e->stream));
     for (int q = 0; q + 1 < np; q++) HIPCHK(hipMemcpy(R.out[q], cx.d_part[q], 8 * ng * words[q], hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(sc.data(), cx.d_part[np - 1], 8 * sc.size(), hipMemcpyDeviceToHost));
-    if (R.kind == Red::summary) { // one row per trial: status and nUE from the host, the rest from the one launch that accepted the trial
-        int rc = PRACH_OK;
-        for (size_t k = 0; k < ng; k++) {
-            prach_trial_summary &row = R.rows[k];
-            row.status = cx.results[k].status; // (everything else is still the empty row run_trials_impl wrote)
-            if (row.status != PRACH_OK) continue;
-            if (cx.trials[k] != 1) { row.status = PRACH_ERR_INTERNAL; rc = PRACH_ERR_INTERNAL; continue; } // (no launch reduced this trial, or two did)
-            const long long *const q = reinterpret_cast<const long long *>(&sc[k * nsc]);
-            row.arrived = (int32_t)q[0]; row.success = (int32_t)q[1]; row.restarted = (int32_t)q[2];
-            row.range_errors = (int32_t)std::min<long long>(q[3] + q[4] + q[5], INT32_MAX);
-            row.sojourn_sum = q[6]; row.timer_sum = q[7]; row.ptc_sum = q[8];
-            row.sojourn_max = (int32_t)q[9]; row.timer_max = (int32_t)q[10]; row.ptc_max = (int32_t)q[11];
-            for (int x = 0; x < 3; x++)
-                for (int l = 0; l < R.mspec->nq; l++) row.q[x][l] = q[3 + x] ? -1 : (int32_t)q[12 + x * PRACH_SUMMARY_MAX_Q + l];
-            if (row.range_errors) rc = PRACH_ERR_INTERNAL; // (a value the kernel cannot rank: no trial produces one)
-        }
-        return rc;
-    }
+    int rc = PRACH_OK;
     for (size_t g = 0; g < ng; g++) {
-        const unsigned long long *const q = &sc[g * nsc];
-        if (R.kind == Red::trace) {
-            prach_trace &t = R.tr[g];
-            t.trials = cx.trials[g]; t.subframes = q[0]; t.calls = q[1]; t.singles = q[2]; t.txop = q[3]; t.collisions = q[4]; t.overflow_calls = q[5];
-            t.calls_max = (int64_t)q[6] - 1;
-        } else if (R.kind == Red::dist) {
-            const prach_dist_spec &s = *R.dspec;
-            prach_dist &d = R.dist[g];
-            d.trials = cx.trials[g]; d.ues = cx.ues[g]; d.success = q[0]; d.delay_overflow = q[1]; d.delay_sum = q[2]; d.ptc_sum = q[3];
-            d.delay_max = (int64_t)q[4] - 1;
-            if (!cx.host_d.empty())
-                prach_dist_merge(&s, &d, R.out[0] + g * (size_t)s.delay_bins, R.out[1] + g * PRACH_DIST_PTC_BINS, &cx.host_d[g],
-                                 cx.host_dh.data() + g * (size_t)s.delay_bins, cx.host_ph.data() + g * PRACH_DIST_PTC_BINS);
-        } else if (R.kind == Red::xtab) {
-            prach_xtab &x = R.xt[g];
-            x.trials = cx.trials[g]; x.ues = cx.ues[g]; x.idle = q[0]; x.served = q[1]; x.unserved = q[2]; x.selected = q[3]; x.binned = q[4];
-            x.undefined = q[3] - q[4];
-            x.row_sum = q[5]; x.col_sum = q[6];
-            x.row_max = (int64_t)q[7] - 1; x.col_max = (int64_t)q[8] - 1;
-        } else if (R.kind == Red::sojourn) {
-            prach_sojourn &j = R.sj[g];
-            j.trials = cx.trials[g]; j.ues = cx.ues[g]; j.arrived = q[0]; j.success = q[1]; j.restarted = q[2]; j.arrival_overflow = q[3]; j.delay_overflow = q[4];
-            j.sojourn_sum = q[5];
-            j.sojourn_max = (int64_t)q[6] - 1;
-        } else {
-            prach_timeline &t = R.tl[g];
-            t.trials = cx.trials[g]; t.ues = cx.ues[g]; t.arrived = q[0]; t.success = q[1]; t.restarted = q[2]; t.arrival_overflow = q[3]; t.done_overflow = q[4];
-            t.sojourn_sum = q[5]; t.timer_sum = q[6];
-            t.done_max = (int64_t)q[7] - 1;
-        }
+        const int grc = K.unpack(R, cx, g, &sc[g * nsc]);
+        if (grc != PRACH_OK) rc = grc;
     }
-    return PRACH_OK;
+    return rc;
 }
 
 static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const Reduction *red = nullptr) {
@@ -1107,22 +1168,9 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
     if (red) { // (the same for the reduction's outputs: empty groups)
         const size_t ng = (size_t)red->ngroups;
         size_t words[RED_MAX_PARTS];
-        const int np = red_parts(*red, words);
+        const int np = kind_of(*red).parts(*red, words);
         for (int q = 0; q + 1 < np; q++) std::memset(red->out[q], 0, 8 * ng * words[q]);
-        for (size_t g = 0; g < ng; g++) {
-            if (red->kind == Red::summary) {
-                prach_trial_summary &row = red->rows[g];
-                std::memset(&row, 0, sizeof(row));
-                row.status = PRACH_ERR_INTERNAL;
-                row.nUE = cfgs[g].nUE;
-                row.sojourn_max = row.timer_max = row.ptc_max = -1;
-                std::memset(row.q, 0xff, sizeof(row.q)); // -1
-            } else if (red->kind == Red::trace) { red->tr[g] = prach_trace{}; red->tr[g].calls_max = -1; }
-            else if (red->kind == Red::dist) { red->dist[g] = prach_dist{}; red->dist[g].delay_max = -1; }
-            else if (red->kind == Red::sojourn) { red->sj[g] = prach_sojourn{}; red->sj[g].sojourn_max = -1; }
-            else if (red->kind == Red::xtab) { red->xt[g] = prach_xtab{}; red->xt[g].row_max = red->xt[g].col_max = -1; }
-            else { red->tl[g] = prach_timeline{}; red->tl[g].done_max = -1; }
-        }
+        for (size_t g = 0; g < ng; g++) kind_of(*red).empty(*red, g, cfgs);
     }
     for (int k = 0; k < n; k++) {
         int v = prach_cfg_validate(&cfgs[k]);
@@ -1133,9 +1181,9 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
     auto t0 = std::chrono::steady_clock::now();
     e->last = prach_timing{};
     CallCtx cx{cfgs, results, ue_logs};
-    // a trace call takes the paths that "fast" = 0 takes: prach::lcluster_kernel writes no rows (its source and its speed stay what they are)
+    // (a trace call takes the paths that "fast" = 0 takes)
     struct FastOff { prach_engine *e; int64_t was; ~FastOff() { e->opt_fast = was; } } fast_off{e, e->opt_fast};
-    if (red && red->kind == Red::trace) e->opt_fast = 0;
+    if (red && kind_of(*red).fast_off) e->opt_fast = 0;
     if (red) {
         cx.red = red;
         int rc = reduction_begin(e, cx, n);
@@ -1289,7 +1337,7 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
     e->last.updates = upd;
     if (red) {
         int rc = reduction_end(e, cx);
-        (red->kind == Red::dist ? e->last.dist_ms : red->kind == Red::timeline ? e->last.timeline_ms : red->kind == Red::sojourn ? e->last.sojourn_ms : red->kind == Red::trace ? e->last.trace_ms : red->kind == Red::xtab ? e->last.xtab_ms : e->last.summary_ms) = cx.red_ms;
+        e->last.*kind_of(*red).ms = cx.red_ms;
         if (rc != PRACH_OK) return rc;
     }
     e->last.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1444,7 +1492,7 @@ int prach_run_trials_dist(prach_engine *e, const prach_cfg *cfgs, int n, prach_r
     if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
     if ((uint64_t)spec->ngroups * (uint64_t)(spec->delay_bins + PRACH_DIST_PTC_BINS) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
-    const Reduction red{Red::dist, group, spec->ngroups, spec, dist, nullptr, nullptr, nullptr, nullptr, {delay_hist, ptc_hist}};
+    const Reduction red{.kind = Red::dist, .group = group, .ngroups = spec->ngroups, .out = {delay_hist, ptc_hist}, .spec = spec, .groups = dist};
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
@@ -1459,7 +1507,7 @@ int prach_run_trials_timeline(prach_engine *e, const prach_cfg *cfgs, int n, pra
     for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
     if (5 * (uint64_t)spec->ngroups * (uint64_t)spec->bins > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
-    const Reduction red{Red::timeline, group, spec->ngroups, nullptr, nullptr, spec, tl, nullptr, nullptr, {arrivals, success, sojourn_sum, timer_sum, done}};
+    const Reduction red{.kind = Red::timeline, .group = group, .ngroups = spec->ngroups, .out = {arrivals, success, sojourn_sum, timer_sum, done}, .spec = spec, .groups = tl};
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
@@ -1476,7 +1524,7 @@ int prach_run_trials_sojourn(prach_engine *e, const prach_cfg *cfgs, int n, prac
     for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
     if ((uint64_t)spec->ngroups * (uint64_t)spec->arrival_bins * ((uint64_t)spec->delay_bins + 2) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
-    const Reduction red{Red::sojourn, group, spec->ngroups, nullptr, nullptr, nullptr, nullptr, spec, sj, {hist, row_arrived, row_delay_overflow}};
+    const Reduction red{.kind = Red::sojourn, .group = group, .ngroups = spec->ngroups, .out = {hist, row_arrived, row_delay_overflow}, .spec = spec, .groups = sj};
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
@@ -1489,9 +1537,7 @@ int prach_run_trials_summary(prach_engine *e, const prach_cfg *cfgs, int n, prac
     for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
     if (!e) return PRACH_ERR_ARG;
     static_assert(SM_MAX_VALUE == 65535, "prach_summary_max_value (prach_host.c) states the kernel's bound");
-    Reduction red{Red::summary, nullptr, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {}};
-    red.mspec = spec;
-    red.rows = rows;
+    const Reduction red{.kind = Red::summary, .group = nullptr, .ngroups = n, .out = {}, .spec = spec, .groups = rows};
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
@@ -1504,9 +1550,7 @@ int prach_run_trials_trace(prach_engine *e, const prach_cfg *cfgs, int n, prach_
     for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c's resolver is another one: include/prach.h)
     if (4 * (uint64_t)spec->ngroups * (uint64_t)spec->bins > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
-    Reduction red{Red::trace, group, spec->ngroups, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {calls, singles, txop, collisions}};
-    red.rspec = spec;
-    red.tr = tr;
+    const Reduction red{.kind = Red::trace, .group = group, .ngroups = spec->ngroups, .out = {calls, singles, txop, collisions}, .spec = spec, .groups = tr};
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
@@ -1526,9 +1570,7 @@ int prach_run_trials_xtab(prach_engine *e, const prach_cfg *cfgs, int n, prach_r
     for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
     if ((uint64_t)spec->ngroups * ((uint64_t)spec->row_bins + 1) * ((uint64_t)spec->col_bins + 1) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
-    Reduction red{Red::xtab, group, spec->ngroups, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {cells}};
-    red.xspec = spec;
-    red.xt = xt;
+    const Reduction red{.kind = Red::xtab, .group = group, .ngroups = spec->ngroups, .out = {cells}, .spec = spec, .groups = xt};
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 

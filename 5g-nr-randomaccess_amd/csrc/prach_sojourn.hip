@@ -3,8 +3,8 @@
 // (words 1-3 timer, active, txTime; word 14 msg4Flag) and from the trial's arrival schedule.  gfx950 only.  prach_sojourn_accumulate_logs
 // (prach_host.c) is the definition; this kernel equals it integer for integer.
 //
-// Shape and jobs are prach::timeline_kernel's: a workgroup takes ONE tile of TL_TILE consecutive UEs of ONE trial, the tile's slot range comes from
-// two searches over the whole schedule and is staged in LDS when it fits, every UE's own slot from a search inside it.
+// Shape and jobs are prach_reduce_tile.h's, as prach::timeline_kernel's are: a workgroup takes ONE tile of TL_TILE consecutive UEs of ONE trial, and the
+// tile's slot range and every UE's arrival come from tile_slots.
 //
 // UEs are activated in index order, so a tile's arrival rows are one contiguous range from row0 = a(first UE of the tile) / row_ms on.  SCHEME 1
 // privatises its first R = min(rows - row0, SJ_WINDOW_WORDS / delay_bins) rows in LDS: R x delay_bins 32-bit cells (a tile adds at most TL_TILE to
@@ -12,20 +12,14 @@
 // counters are flushed, with 64-bit agent-scope atomic adds (trials of one group run on different XCDs).  What falls outside the window goes straight
 // to the global cell with the same atomics (R may be 0: everything does), and so does everything under SCHEME 0.  The scalars are reduced per
 // wavefront.  Integers only: the result does not depend on any order.  Engine option "sojourn_scheme".
-#include "prach_device.h"
-#include "prach_slot_search.h"
+#include "prach_reduce_tile.h"
 
 namespace prach {
 
 namespace {
 
-constexpr int SJ_SCHED_CAP = 2048; // schedule entries of a tile's slot range staged in LDS (a longer range is searched in global memory)
-static_assert(4 * (SJ_SCHED_CAP + 2 * SJ_SCALARS + 2 * PRACH_SOJOURN_MAX_ARRIVAL_BINS + SJ_WINDOW_WORDS) <= 160 * 1024,
+static_assert(4 * (TILE_SCHED_CAP + 2 * SJ_SCALARS + 2 * PRACH_SOJOURN_MAX_ARRIVAL_BINS + SJ_WINDOW_WORDS) <= 160 * 1024,
               "the largest layout (every row privatised: the two per-row arrays at their longest next to a full window) fits the 160 KiB of LDS of a gfx950 CU");
-
-__device__ __forceinline__ void gadd(unsigned long long *p, unsigned long long v) {
-    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // rows a workgroup can privatise at most: the launch sizes the two per-row counter arrays by it
 int window_rows(int rows, int delay_bins) { return rows < SJ_WINDOW_WORDS / delay_bins ? rows : SJ_WINDOW_WORDS / delay_bins; }
@@ -33,38 +27,26 @@ int window_rows(int rows, int delay_bins) { return rows < SJ_WINDOW_WORDS / dela
 template <int SCHEME>
 __global__ __launch_bounds__(TL_THREADS) void sojourn_kernel(const TimelineJob *__restrict__ jobs, int njobs, int rows, int row_ms, int dbins, int dwidth, int rcap,
                                                              SojournOut out) {
-    extern __shared__ unsigned lds[]; // [SJ_SCHED_CAP] schedule range | 8 x 64-bit scalars | SCHEME 1: [rcap] arrived | [rcap] overflow | [rcap x dbins] cells
+    extern __shared__ unsigned lds[]; // [TILE_SCHED_CAP] schedule range | 8 x 64-bit scalars | SCHEME 1: [rcap] arrived | [rcap] overflow | [rcap x dbins] cells
     const int tid = threadIdx.x, lane = tid & 63;
     int *const lsched = reinterpret_cast<int *>(lds);
-    unsigned long long *const lsc = reinterpret_cast<unsigned long long *>(lds + SJ_SCHED_CAP);
-    unsigned *const larr = lds + SJ_SCHED_CAP + 2 * SJ_SCALARS;
+    unsigned long long *const lsc = reinterpret_cast<unsigned long long *>(lds + TILE_SCHED_CAP);
+    unsigned *const larr = lds + TILE_SCHED_CAP + 2 * SJ_SCALARS;
     unsigned *const lovf = larr + rcap;
     unsigned *const lcell = lovf + rcap;
 
-    // the job of this workgroup: the last one whose first workgroup is not behind it
-    int jlo = 0, jhi = njobs - 1;
-    while (jlo < jhi) {
-        const int mid = (jlo + jhi + 1) >> 1;
-        if (jobs[mid].wg0 <= (int)blockIdx.x) jlo = mid; else jhi = mid - 1;
-    }
-    const TimelineJob J = jobs[jlo];
+    const TimelineJob J = job_of_workgroup(jobs, njobs);
     const int first = ((int)blockIdx.x - J.wg0) * TL_TILE;
     const int end = min(J.nUE, first + TL_TILE);
 
     // the tile's slot range (the same in every thread), its first arrival row and the rows of its window: row0 + R <= rows, R <= rcap
-    const int slo = first_slot_above(J.sched, 0, 0, J.nslots, first);
-    const int shi = first_slot_above(J.sched, 0, slo, J.nslots, end - 1);
-    const unsigned row0 = (unsigned)(J.aT * slo) / (unsigned)row_ms;
+    const TileSlots S = tile_slots<TL_THREADS>(J, first, end, lsched, tid);
+    const unsigned row0 = (unsigned)(J.aT * S.slo) / (unsigned)row_ms;
     unsigned R = 0;
     if (SCHEME == 1) {
         if (row0 < (unsigned)rows) R = min((unsigned)rows - row0, (unsigned)rcap);
     }
     const unsigned ncell = R * (unsigned)dbins; // <= SJ_WINDOW_WORDS
-    const bool staged = shi - slo <= SJ_SCHED_CAP;
-    if (staged)
-        for (int s = tid; s < shi - slo; s += TL_THREADS) lsched[s] = J.sched[slo + s];
-    const int *const sp = staged ? lsched : J.sched;
-    const int sbase = staged ? slo : 0;
     if (SCHEME == 1) {
         for (unsigned w = tid; w < ncell; w += TL_THREADS) lcell[w] = 0;
         for (unsigned r = tid; r < R; r += TL_THREADS) { larr[r] = 0; lovf[r] = 0; }
@@ -80,12 +62,12 @@ __global__ __launch_bounds__(TL_THREADS) void sojourn_kernel(const TimelineJob *
         const int4 head = J.logs[4 * (size_t)i]; // idx, timer, active, txTime
         if (head.z == -1) continue;              // not arrived
         const bool ok = J.logs[4 * (size_t)i + 3].z == 1; // msg4Flag
-        const unsigned a = (unsigned)(J.aT * first_slot_above(sp, sbase, slo, shi, i));
+        const unsigned a = (unsigned)S.arrival(J, i);
         const unsigned r = a / (unsigned)row_ms, wr = r - row0; // (r >= row0: arrivals follow the index)
         arrived++;
         if (r >= (unsigned)rows) aover++;
         else if (wr < R) atomicAdd(&larr[wr], 1u);
-        else gadd(&g_arr[r], 1ull);
+        else agent_add(&g_arr[r], 1ull);
         if (!ok) continue;
         const unsigned c = (unsigned)(head.w + 6), soj = c - a;
         const unsigned d = dwidth == 1 ? soj : soj / (unsigned)dwidth;
@@ -97,18 +79,14 @@ __global__ __launch_bounds__(TL_THREADS) void sojourn_kernel(const TimelineJob *
         if (r >= (unsigned)rows) continue;
         if (d < (unsigned)dbins) {
             if (wr < R) atomicAdd(&lcell[wr * (unsigned)dbins + d], 1u);
-            else gadd(&g_cell[(size_t)r * (size_t)dbins + d], 1ull);
+            else agent_add(&g_cell[(size_t)r * (size_t)dbins + d], 1ull);
         } else {
             if (wr < R) atomicAdd(&lovf[wr], 1u);
-            else gadd(&g_ovf[r], 1ull);
+            else agent_add(&g_ovf[r], 1ull);
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        arrived += __shfl_down(arrived, d); nsucc += __shfl_down(nsucc, d); nrest += __shfl_down(nrest, d); aover += __shfl_down(aover, d);
-        dover += __shfl_down(dover, d); ssum += __shfl_down(ssum, d);
-        smax1 = max(smax1, (unsigned)__shfl_down(smax1, d));
-    }
+    arrived = fold_sum(arrived); nsucc = fold_sum(nsucc); nrest = fold_sum(nrest); aover = fold_sum(aover); dover = fold_sum(dover);
+    ssum = fold_sum(ssum); smax1 = fold_max(smax1);
     if (lane == 0 && arrived) {
         atomicAdd(&lsc[0], (unsigned long long)arrived); atomicAdd(&lsc[1], (unsigned long long)nsucc); atomicAdd(&lsc[2], (unsigned long long)nrest);
         atomicAdd(&lsc[3], (unsigned long long)aover); atomicAdd(&lsc[4], (unsigned long long)dover); atomicAdd(&lsc[5], ssum);
@@ -121,17 +99,15 @@ __global__ __launch_bounds__(TL_THREADS) void sojourn_kernel(const TimelineJob *
         unsigned long long *const g_win = g_cell + (size_t)row0 * (size_t)dbins;
         for (unsigned w = tid; w < ncell; w += TL_THREADS) {
             const unsigned v = lcell[w];
-            if (v) gadd(&g_win[w], (unsigned long long)v);
+            if (v) agent_add(&g_win[w], (unsigned long long)v);
         }
         for (unsigned r = tid; r < R; r += TL_THREADS) {
             const unsigned va = larr[r], vo = lovf[r];
-            if (va) gadd(&g_arr[row0 + r], (unsigned long long)va);
-            if (vo) gadd(&g_ovf[row0 + r], (unsigned long long)vo);
+            if (va) agent_add(&g_arr[row0 + r], (unsigned long long)va);
+            if (vo) agent_add(&g_ovf[row0 + r], (unsigned long long)vo);
         }
     }
-    unsigned long long *const gsc = out.scalars + (size_t)J.group * SJ_SCALARS;
-    if (tid < 6 && lsc[tid]) gadd(&gsc[tid], lsc[tid]);
-    if (tid == 6 && lsc[6]) (void)__hip_atomic_fetch_max(&gsc[6], lsc[6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    flush_scalars(lsc, out.scalars + (size_t)J.group * SJ_SCALARS, SJ_SUMS, SJ_MAXIMA, tid);
 }
 
 } // namespace
@@ -139,7 +115,7 @@ __global__ __launch_bounds__(TL_THREADS) void sojourn_kernel(const TimelineJob *
 hipError_t launch_sojourn_kernel(const TimelineJob *jobs, int njobs, int workgroups, int rows, int row_ms, int delay_bins, int delay_bin_ms, int scheme, SojournOut out,
                                  hipStream_t stream) {
     const int rcap = scheme == 1 ? window_rows(rows, delay_bins) : 0;
-    const size_t lds = 4 * ((size_t)SJ_SCHED_CAP + 2 * SJ_SCALARS + 2 * (size_t)rcap + (size_t)rcap * (size_t)delay_bins);
+    const size_t lds = 4 * ((size_t)TILE_SCHED_CAP + 2 * SJ_SCALARS + 2 * (size_t)rcap + (size_t)rcap * (size_t)delay_bins);
     if (scheme == 0) return launch_with_lds(sojourn_kernel<0>, workgroups, TL_THREADS, lds, stream, jobs, njobs, rows, row_ms, delay_bins, delay_bin_ms, rcap, out);
     return launch_with_lds(sojourn_kernel<1>, workgroups, TL_THREADS, lds, stream, jobs, njobs, rows, row_ms, delay_bins, delay_bin_ms, rcap, out);
 }

@@ -19,7 +19,7 @@
 // and subframe), of which a trial has at most 60 000 + 6.  Integers only: the result does not depend on any order.
 #include "prach_device.h"
 #include "prach_device_fn.h"
-#include "prach_slot_search.h"
+#include "prach_reduce_tile.h"
 
 namespace prach {
 
@@ -78,13 +78,9 @@ __global__ __launch_bounds__(THREADS) void summary_kernel(const TimelineJob *__r
             if ((unsigned)timer <= (unsigned)SM_MAX_VALUE) atomicAdd(&lcoarse[SM_COARSE + ((unsigned)timer >> 6)], 1u); else rerr1++;
             if ((unsigned)ptc <= (unsigned)SM_MAX_VALUE) atomicAdd(&lcoarse[2 * SM_COARSE + ((unsigned)ptc >> 6)], 1u); else rerr2++;
         }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            arrived += __shfl_down(arrived, d); nsucc += __shfl_down(nsucc, d); nrest += __shfl_down(nrest, d);
-            rerr0 += __shfl_down(rerr0, d); rerr1 += __shfl_down(rerr1, d); rerr2 += __shfl_down(rerr2, d);
-            sum0 += __shfl_down(sum0, d); sum1 += __shfl_down(sum1, d); sum2 += __shfl_down(sum2, d);
-            max0 = max(max0, __shfl_down(max0, d)); max1 = max(max1, __shfl_down(max1, d)); max2 = max(max2, __shfl_down(max2, d));
-        }
+        // (the folds of prach_reduce_tile.h, on signed values: a sum folds alike, a maximum may be -1)
+        arrived = fold_sum(arrived); nsucc = fold_sum(nsucc); nrest = fold_sum(nrest); rerr0 = fold_sum(rerr0); rerr1 = fold_sum(rerr1); rerr2 = fold_sum(rerr2);
+        sum0 = fold_sum(sum0); sum1 = fold_sum(sum1); sum2 = fold_sum(sum2); max0 = fold_max(max0); max1 = fold_max(max1); max2 = fold_max(max2);
         if (lane == 0 && arrived) {
             unsigned long long *const u = reinterpret_cast<unsigned long long *>(lsc);
             atomicAdd(&u[0], (unsigned long long)arrived); atomicAdd(&u[1], (unsigned long long)nsucc); atomicAdd(&u[2], (unsigned long long)nrest);

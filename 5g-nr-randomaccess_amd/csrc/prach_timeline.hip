@@ -5,55 +5,36 @@
 //
 // The engine launches it on its stream behind a simulation launch, for the trials whose result it keeps.  A workgroup takes ONE tile of TL_TILE
 // consecutive UEs of ONE trial (the job table gives every trial its first workgroup).  UEs are activated in index order, so the arrival slots of
-// a tile are one contiguous range of the schedule: its two ends come from a search over the whole schedule, the range is staged in LDS when it
-// fits, and every UE's own slot comes from a search inside it.
+// a tile are one contiguous range of the schedule (tile_slots of prach_reduce_tile.h, which also has the job lookup, the wavefront folds and the
+// flush of the scalars that the reducer kernels share).
 //
 // SCHEME 1 privatises TL_WINDOW bins, anchored at the tile's first arrival bin, in LDS: four 32-bit counters per by-arrival bin (arrivals,
 // success, sojourn sum, timer sum: a tile's sums fit 32 bits, prach_device.h) and one per done bin.  Only non-zero bins are flushed, with
 // 64-bit agent-scope atomic adds (trials of one group run on different XCDs).  What falls outside a window goes straight to the global bins
 // with the same atomics, and so does everything under SCHEME 0.  The scalars are reduced per wavefront.  Integers only: the result does not
 // depend on any order.  Engine option "timeline_scheme"; DESIGN.md 4 has the measurements.
-#include "prach_device.h"
-#include "prach_slot_search.h"
+#include "prach_reduce_tile.h"
 
 namespace prach {
 
 namespace {
 
-constexpr int TL_SCHED_CAP = 2048; // schedule entries of a tile's slot range staged in LDS (a longer range is searched in global memory)
-
-__device__ __forceinline__ void gadd(unsigned long long *p, unsigned long long v) {
-    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 template <int SCHEME>
 __global__ __launch_bounds__(TL_THREADS) void timeline_kernel(const TimelineJob *__restrict__ jobs, int njobs, int bins, int width, TimelineOut out) {
-    extern __shared__ unsigned lds[]; // [TL_SCHED_CAP] schedule range | 8 x 64-bit scalars | SCHEME 1: [TL_WINDOW][4] by-arrival | [TL_WINDOW] done
+    extern __shared__ unsigned lds[]; // [TILE_SCHED_CAP] schedule range | 8 x 64-bit scalars | SCHEME 1: [TL_WINDOW][4] by-arrival | [TL_WINDOW] done
     const int tid = threadIdx.x, lane = tid & 63;
     int *const lsched = reinterpret_cast<int *>(lds);
-    unsigned long long *const lsc = reinterpret_cast<unsigned long long *>(lds + TL_SCHED_CAP);
-    unsigned *const lwin = lds + TL_SCHED_CAP + 2 * TL_SCALARS;
+    unsigned long long *const lsc = reinterpret_cast<unsigned long long *>(lds + TILE_SCHED_CAP);
+    unsigned *const lwin = lds + TILE_SCHED_CAP + 2 * TL_SCALARS;
     unsigned *const ldone = lwin + 4 * TL_WINDOW;
 
-    // the job of this workgroup: the last one whose first workgroup is not behind it
-    int jlo = 0, jhi = njobs - 1;
-    while (jlo < jhi) {
-        const int mid = (jlo + jhi + 1) >> 1;
-        if (jobs[mid].wg0 <= (int)blockIdx.x) jlo = mid; else jhi = mid - 1;
-    }
-    const TimelineJob J = jobs[jlo];
+    const TimelineJob J = job_of_workgroup(jobs, njobs);
     const int first = ((int)blockIdx.x - J.wg0) * TL_TILE;
     const int end = min(J.nUE, first + TL_TILE);
 
     // the tile's slot range (the same in every thread) and its first arrival bin: the anchor of both windows
-    const int slo = first_slot_above(J.sched, 0, 0, J.nslots, first);
-    const int shi = first_slot_above(J.sched, 0, slo, J.nslots, end - 1);
-    const unsigned bin0 = (unsigned)(J.aT * slo) / (unsigned)width;
-    const bool staged = shi - slo <= TL_SCHED_CAP;
-    if (staged)
-        for (int s = tid; s < shi - slo; s += TL_THREADS) lsched[s] = J.sched[slo + s];
-    const int *const sp = staged ? lsched : J.sched;
-    const int sbase = staged ? slo : 0;
+    const TileSlots S = tile_slots<TL_THREADS>(J, first, end, lsched, tid);
+    const unsigned bin0 = (unsigned)(J.aT * S.slo) / (unsigned)width;
     if (SCHEME == 1)
         for (int b = tid; b < 5 * TL_WINDOW; b += TL_THREADS) lwin[b] = 0;
     if (tid < TL_SCALARS) lsc[tid] = 0;
@@ -68,13 +49,13 @@ __global__ __launch_bounds__(TL_THREADS) void timeline_kernel(const TimelineJob 
         const int4 head = J.logs[4 * (size_t)i]; // idx, timer, active, txTime
         if (head.z == -1) continue;              // not arrived
         const bool ok = J.logs[4 * (size_t)i + 3].z == 1; // msg4Flag
-        const unsigned a = (unsigned)(J.aT * first_slot_above(sp, sbase, slo, shi, i));
+        const unsigned a = (unsigned)S.arrival(J, i);
         const unsigned ab = width == 1 ? a : a / (unsigned)width;
         const bool abin = ab < (unsigned)bins, awin = SCHEME == 1 && abin && ab - bin0 < (unsigned)TL_WINDOW;
         arrived++;
         if (!abin) aover++;
         else if (awin) atomicAdd(&lwin[4 * (ab - bin0)], 1u);
-        else gadd(&g_arr[ab], 1ull);
+        else agent_add(&g_arr[ab], 1ull);
         if (!ok) continue;
         const unsigned timer = (unsigned)head.y, c = (unsigned)(head.w + 6), soj = c - a;
         const unsigned db = width == 1 ? c : c / (unsigned)width;
@@ -90,20 +71,16 @@ __global__ __launch_bounds__(TL_THREADS) void timeline_kernel(const TimelineJob 
             atomicAdd(&lwin[4 * (ab - bin0) + 2], soj);
             atomicAdd(&lwin[4 * (ab - bin0) + 3], timer);
         } else if (abin) {
-            gadd(&g_suc[ab], 1ull);
-            gadd(&g_soj[ab], (unsigned long long)soj);
-            gadd(&g_tim[ab], (unsigned long long)timer);
+            agent_add(&g_suc[ab], 1ull);
+            agent_add(&g_soj[ab], (unsigned long long)soj);
+            agent_add(&g_tim[ab], (unsigned long long)timer);
         }
         if (db >= (unsigned)bins) dover++;
         else if (SCHEME == 1 && db - bin0 < (unsigned)TL_WINDOW) atomicAdd(&ldone[db - bin0], 1u);
-        else gadd(&g_don[db], 1ull);
+        else agent_add(&g_don[db], 1ull);
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        arrived += __shfl_down(arrived, d); nsucc += __shfl_down(nsucc, d); nrest += __shfl_down(nrest, d); aover += __shfl_down(aover, d);
-        dover += __shfl_down(dover, d); ssum += __shfl_down(ssum, d); tsum += __shfl_down(tsum, d);
-        dmax1 = max(dmax1, (unsigned)__shfl_down(dmax1, d));
-    }
+    arrived = fold_sum(arrived); nsucc = fold_sum(nsucc); nrest = fold_sum(nrest); aover = fold_sum(aover); dover = fold_sum(dover);
+    ssum = fold_sum(ssum); tsum = fold_sum(tsum); dmax1 = fold_max(dmax1);
     if (lane == 0 && arrived) {
         atomicAdd(&lsc[0], (unsigned long long)arrived); atomicAdd(&lsc[1], (unsigned long long)nsucc); atomicAdd(&lsc[2], (unsigned long long)nrest);
         atomicAdd(&lsc[3], (unsigned long long)aover); atomicAdd(&lsc[4], (unsigned long long)dover); atomicAdd(&lsc[5], ssum); atomicAdd(&lsc[6], tsum);
@@ -116,20 +93,18 @@ __global__ __launch_bounds__(TL_THREADS) void timeline_kernel(const TimelineJob 
         for (int b = tid; b < TL_WINDOW; b += TL_THREADS) {
             const uint4 v = *reinterpret_cast<const uint4 *>(&lwin[4 * b]);
             const size_t at = (size_t)bin0 + (size_t)b;
-            if (v.x) gadd(&g_arr[at], (unsigned long long)v.x);
-            if (v.y) gadd(&g_suc[at], (unsigned long long)v.y);
-            if (v.z) gadd(&g_soj[at], (unsigned long long)v.z);
-            if (v.w) gadd(&g_tim[at], (unsigned long long)v.w);
+            if (v.x) agent_add(&g_arr[at], (unsigned long long)v.x);
+            if (v.y) agent_add(&g_suc[at], (unsigned long long)v.y);
+            if (v.z) agent_add(&g_soj[at], (unsigned long long)v.z);
+            if (v.w) agent_add(&g_tim[at], (unsigned long long)v.w);
             const unsigned dn = ldone[b];
-            if (dn) gadd(&g_don[at], (unsigned long long)dn);
+            if (dn) agent_add(&g_don[at], (unsigned long long)dn);
         }
     }
-    unsigned long long *const gsc = out.scalars + (size_t)J.group * TL_SCALARS;
-    if (tid < 7 && lsc[tid]) gadd(&gsc[tid], lsc[tid]);
-    if (tid == 7 && lsc[7]) (void)__hip_atomic_fetch_max(&gsc[7], lsc[7], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    flush_scalars(lsc, out.scalars + (size_t)J.group * TL_SCALARS, TL_SUMS, TL_MAXIMA, tid);
 }
 
-size_t timeline_lds_bytes(int scheme) { return 4 * (size_t)(TL_SCHED_CAP + 2 * TL_SCALARS + (scheme == 1 ? 5 * TL_WINDOW : 0)); }
+size_t timeline_lds_bytes(int scheme) { return 4 * (size_t)(TILE_SCHED_CAP + 2 * TL_SCALARS + (scheme == 1 ? 5 * TL_WINDOW : 0)); }
 
 } // namespace
 

@@ -11,15 +11,11 @@
 // atomic adds (trials of one group run on different XCDs).  SCHEME 0 sends every non-zero contribution straight to the global bins with the same atomics.
 // The scalars are reduced per wavefront.  Integers only: the result does not depend on any order.  Engine option "trace_scheme"; DESIGN.md 4 has the
 // measurements.  A row's words are counts, read as unsigned 32-bit values and added in 64 bits.
-#include "prach_device.h"
+#include "prach_reduce_tile.h"
 
 namespace prach {
 
 namespace {
-
-__device__ __forceinline__ void gadd(unsigned long long *p, unsigned long long v) {
-    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 template <int SCHEME>
 __global__ __launch_bounds__(TR_THREADS) void trace_kernel(const TraceJob *__restrict__ jobs, int njobs, int bins, int width, TraceOut out) {
@@ -28,13 +24,7 @@ __global__ __launch_bounds__(TR_THREADS) void trace_kernel(const TraceJob *__res
     unsigned long long *const lsc = lds64;
     unsigned long long *const lwin = lds64 + TR_SCALARS;
 
-    // the job of this workgroup: the last one whose first workgroup is not behind it
-    int jlo = 0, jhi = njobs - 1;
-    while (jlo < jhi) {
-        const int mid = (jlo + jhi + 1) >> 1;
-        if (jobs[mid].wg0 <= (int)blockIdx.x) jlo = mid; else jhi = mid - 1;
-    }
-    const TraceJob J = jobs[jlo];
+    const TraceJob J = job_of_workgroup(jobs, njobs);
     const int first = ((int)blockIdx.x - J.wg0) * TR_TILE;
     const int end = min(J.steps, first + TR_TILE);
     if (first >= end) return; // (uniform: a job without subframes has no tile)
@@ -62,18 +52,13 @@ __global__ __launch_bounds__(TR_THREADS) void trace_kernel(const TraceJob *__res
             if (x) atomicAdd(&w[2], (unsigned long long)x);
             if (q) atomicAdd(&w[3], (unsigned long long)q);
         } else {
-            if (c) gadd(&out.calls[gbase + b], (unsigned long long)c);
-            if (s) gadd(&out.singles[gbase + b], (unsigned long long)s);
-            if (x) gadd(&out.txop[gbase + b], (unsigned long long)x);
-            if (q) gadd(&out.collisions[gbase + b], (unsigned long long)q);
+            if (c) agent_add(&out.calls[gbase + b], (unsigned long long)c);
+            if (s) agent_add(&out.singles[gbase + b], (unsigned long long)s);
+            if (x) agent_add(&out.txop[gbase + b], (unsigned long long)x);
+            if (q) agent_add(&out.collisions[gbase + b], (unsigned long long)q);
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        calls += __shfl_down(calls, d); singles += __shfl_down(singles, d); txop += __shfl_down(txop, d); coll += __shfl_down(coll, d);
-        over += __shfl_down(over, d);
-        cmax1 = max(cmax1, (unsigned)__shfl_down(cmax1, d));
-    }
+    calls = fold_sum(calls); singles = fold_sum(singles); txop = fold_sum(txop); coll = fold_sum(coll); over = fold_sum(over); cmax1 = fold_max(cmax1);
     if (lane == 0) {
         atomicAdd(&lsc[1], calls); atomicAdd(&lsc[2], singles); atomicAdd(&lsc[3], txop); atomicAdd(&lsc[4], coll); atomicAdd(&lsc[5], over);
         atomicMax(&lsc[6], (unsigned long long)cmax1);
@@ -87,15 +72,13 @@ __global__ __launch_bounds__(TR_THREADS) void trace_kernel(const TraceJob *__res
             const unsigned long long *const w = lwin + 4 * (size_t)b;
             const size_t at = gbase + (size_t)bin0 + (size_t)b;
             const unsigned long long v0 = w[0], v1 = w[1], v2 = w[2], v3 = w[3];
-            if (v0) gadd(&out.calls[at], v0);
-            if (v1) gadd(&out.singles[at], v1);
-            if (v2) gadd(&out.txop[at], v2);
-            if (v3) gadd(&out.collisions[at], v3);
+            if (v0) agent_add(&out.calls[at], v0);
+            if (v1) agent_add(&out.singles[at], v1);
+            if (v2) agent_add(&out.txop[at], v2);
+            if (v3) agent_add(&out.collisions[at], v3);
         }
     }
-    unsigned long long *const gsc = out.scalars + (size_t)J.group * TR_SCALARS;
-    if (tid < 6 && lsc[tid]) gadd(&gsc[tid], lsc[tid]);
-    if (tid == 6 && lsc[6]) (void)__hip_atomic_fetch_max(&gsc[6], lsc[6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    flush_scalars(lsc, out.scalars + (size_t)J.group * TR_SCALARS, TR_SUMS, TR_MAXIMA, tid);
 }
 
 size_t trace_lds_bytes(int scheme) { return 8 * (size_t)(TR_SCALARS + (scheme == 1 ? 4 * TR_TILE : 0)); }

@@ -3,9 +3,9 @@
 // writes there, the trial's arrival schedule and its `steps`.  gfx950 only.  prach_xtab_accumulate_logs (prach_host.c) is the definition; this kernel
 // equals it integer for integer.
 //
-// Shape and jobs are prach::timeline_kernel's: a workgroup takes ONE tile of TL_TILE consecutive UEs of ONE trial; where an axis needs a(i), the tile's
-// slot range comes from two searches over the whole schedule and is staged in LDS when it fits, every UE's own slot from a search inside it
-// (prach_slot_search.h).  TimelineJob::pad carries E = min(steps, maxTime) for this kind.
+// Shape and jobs are prach_reduce_tile.h's, as prach::timeline_kernel's are: a workgroup takes ONE tile of TL_TILE consecutive UEs of ONE trial; where an
+// axis needs a(i), and only there, the tile's slot range and every UE's arrival come from tile_slots.  TimelineJob::pad carries E = min(steps, maxTime)
+// for this kind.
 //
 // A lane always reads words 0-3 (timer, active, txTime) and 12-15 (connectionRequest, msg4Flag, failCount) of a record; words 4-7 (nowBackoff) only
 // when an axis is STATE and words 8-11 (preambleTxCounter) only when an axis is PTC: both uniform for the launch, so a launch moves 32-64 B per UE.
@@ -19,25 +19,19 @@
 //   2  a larger table, and everything under SCHEME 0: every contribution goes straight to its global cell with the same atomics.
 // The arrival-anchored row window of prach::sojourn_kernel is NOT rebuilt here: a fine ARRIVAL x SOJOURN table remains prach_run_trials_sojourn's job.
 // The scalars are reduced per wavefront.  Integers only: the result does not depend on any order.  Engine option "xtab_scheme".
-#include "prach_device.h"
-#include "prach_slot_search.h"
+#include "prach_reduce_tile.h"
 
 namespace prach {
 
 namespace {
 
-constexpr int XT_SCHED_CAP = 2048; // schedule entries of a tile's slot range staged in LDS (a longer range is searched in global memory)
 #ifndef PRACH_XT_COPY_WORDS
 #define PRACH_XT_COPY_WORDS 4096 // (a build with 0 keeps one copy always: the measurement of DESIGN.md 4)
 #endif
 constexpr int XT_COPY_WORDS = PRACH_XT_COPY_WORDS; // LDS words that the per-wavefront copies of a table take at most
 constexpr int XT_WAVES = TL_THREADS / 64;
-static_assert(4 * (XT_SCHED_CAP + 2 * XT_SCALARS + XT_WINDOW_WORDS) <= 160 * 1024 && XT_COPY_WORDS <= XT_WINDOW_WORDS,
+static_assert(4 * (TILE_SCHED_CAP + 2 * XT_SCALARS + XT_WINDOW_WORDS) <= 160 * 1024 && XT_COPY_WORDS <= XT_WINDOW_WORDS,
               "the largest layout (a table of XT_WINDOW_WORDS cells) fits the 160 KiB of LDS of a gfx950 CU");
-
-__device__ __forceinline__ void gadd(unsigned long long *p, unsigned long long v) {
-    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // the value of a field (include/prach.h); negative: UNDEFINED.  cls: 0 idle, 1 served, 2 unserved
 __device__ __forceinline__ long long xt_value(int field, const int4 &head, const int4 &tail, int nowBackoff, int ptc, int cls, int a, int E) {
@@ -64,19 +58,13 @@ __host__ __device__ constexpr bool needs_arrival(int f) { return f == PRACH_XTAB
 
 template <int SCHEME>
 __global__ __launch_bounds__(TL_THREADS) void xtab_kernel(const TimelineJob *__restrict__ jobs, int njobs, XtabAxes ax, int copies, XtabOut out) {
-    extern __shared__ unsigned lds[]; // [XT_SCHED_CAP] schedule range | XT_SCALARS x 64-bit scalars | path 1: [copies][ncell] cells
+    extern __shared__ unsigned lds[]; // [TILE_SCHED_CAP] schedule range | XT_SCALARS x 64-bit scalars | path 1: [copies][ncell] cells
     const int tid = threadIdx.x, lane = tid & 63;
     int *const lsched = reinterpret_cast<int *>(lds);
-    unsigned long long *const lsc = reinterpret_cast<unsigned long long *>(lds + XT_SCHED_CAP);
-    unsigned *const lcell = lds + XT_SCHED_CAP + 2 * XT_SCALARS;
+    unsigned long long *const lsc = reinterpret_cast<unsigned long long *>(lds + TILE_SCHED_CAP);
+    unsigned *const lcell = lds + TILE_SCHED_CAP + 2 * XT_SCALARS;
 
-    // the job of this workgroup: the last one whose first workgroup is not behind it
-    int jlo = 0, jhi = njobs - 1;
-    while (jlo < jhi) {
-        const int mid = (jlo + jhi + 1) >> 1;
-        if (jobs[mid].wg0 <= (int)blockIdx.x) jlo = mid; else jhi = mid - 1;
-    }
-    const TimelineJob J = jobs[jlo];
+    const TimelineJob J = job_of_workgroup(jobs, njobs);
     const int first = ((int)blockIdx.x - J.wg0) * TL_TILE;
     const int end = min(J.nUE, first + TL_TILE);
     const int E = J.pad;
@@ -87,18 +75,9 @@ __global__ __launch_bounds__(TL_THREADS) void xtab_kernel(const TimelineJob *__r
     const bool need_b = ax.row_field == PRACH_XTAB_STATE || ax.col_field == PRACH_XTAB_STATE;
     const bool need_p = ax.row_field == PRACH_XTAB_PTC || ax.col_field == PRACH_XTAB_PTC;
 
-    // the tile's slot range (the same in every thread), staged where it fits
-    int slo = 0, shi = 0;
-    bool staged = false;
-    if (need_a) {
-        slo = first_slot_above(J.sched, 0, 0, J.nslots, first);
-        shi = first_slot_above(J.sched, 0, slo, J.nslots, end - 1);
-        staged = shi - slo <= XT_SCHED_CAP;
-        if (staged)
-            for (int s = tid; s < shi - slo; s += TL_THREADS) lsched[s] = J.sched[slo + s];
-    }
-    const int *const sp = staged ? lsched : J.sched;
-    const int sbase = staged ? slo : 0;
+    // the tile's slot range, only where an axis needs it: no search and no copy otherwise
+    TileSlots S{0, 0, J.sched, 0};
+    if (need_a) S = tile_slots<TL_THREADS>(J, first, end, lsched, tid);
     if (priv)
         for (unsigned w = tid; w < ncell * (unsigned)copies; w += TL_THREADS) lcell[w] = 0;
     if (tid < XT_SCALARS) lsc[tid] = 0;
@@ -118,7 +97,7 @@ __global__ __launch_bounds__(TL_THREADS) void xtab_kernel(const TimelineJob *__r
         const int bit = cls == 0 ? PRACH_XTAB_IDLE : cls == 1 ? PRACH_XTAB_SERVED : PRACH_XTAB_UNSERVED;
         if (!(ax.who & bit)) continue;
         nsel++;
-        const int a = need_a ? J.aT * first_slot_above(sp, sbase, slo, shi, i) : 0;
+        const int a = need_a ? S.arrival(J, i) : 0;
         const long long rv = xt_value(ax.row_field, head, tail, nowBackoff, ptc, cls, a, E), cv = xt_value(ax.col_field, head, tail, nowBackoff, ptc, cls, a, E);
         if (rv < 0 || cv < 0) continue; // UNDEFINED
         // (a value is below 2^31 + 6: it fits 32 unsigned bits, and the quotient is cut at the overflow bin)
@@ -128,14 +107,10 @@ __global__ __launch_bounds__(TL_THREADS) void xtab_kernel(const TimelineJob *__r
         rsum += (unsigned long long)rv; csum += (unsigned long long)cv;
         rmax1 = max(rmax1, (unsigned long long)rv + 1ull); cmax1 = max(cmax1, (unsigned long long)cv + 1ull);
         if (priv) atomicAdd(&mycell[cell], 1u);
-        else gadd(&g_cell[cell], 1ull);
+        else agent_add(&g_cell[cell], 1ull);
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        nidle += __shfl_down(nidle, d); nserved += __shfl_down(nserved, d); nunserved += __shfl_down(nunserved, d); nsel += __shfl_down(nsel, d);
-        nbinned += __shfl_down(nbinned, d); rsum += __shfl_down(rsum, d); csum += __shfl_down(csum, d);
-        rmax1 = max(rmax1, (unsigned long long)__shfl_down(rmax1, d)); cmax1 = max(cmax1, (unsigned long long)__shfl_down(cmax1, d));
-    }
+    nidle = fold_sum(nidle); nserved = fold_sum(nserved); nunserved = fold_sum(nunserved); nsel = fold_sum(nsel); nbinned = fold_sum(nbinned);
+    rsum = fold_sum(rsum); csum = fold_sum(csum); rmax1 = fold_max(rmax1); cmax1 = fold_max(cmax1);
     if (lane == 0) {
         atomicAdd(&lsc[0], (unsigned long long)nidle); atomicAdd(&lsc[1], (unsigned long long)nserved); atomicAdd(&lsc[2], (unsigned long long)nunserved);
         atomicAdd(&lsc[3], (unsigned long long)nsel); atomicAdd(&lsc[4], (unsigned long long)nbinned); atomicAdd(&lsc[5], rsum); atomicAdd(&lsc[6], csum);
@@ -148,11 +123,9 @@ __global__ __launch_bounds__(TL_THREADS) void xtab_kernel(const TimelineJob *__r
         for (unsigned w = tid; w < ncell; w += TL_THREADS) {
             unsigned v = lcell[w];
             for (int k = 1; k < copies; k++) v += lcell[(unsigned)k * ncell + w];
-            if (v) gadd(&g_cell[w], (unsigned long long)v);
+            if (v) agent_add(&g_cell[w], (unsigned long long)v);
         }
-    unsigned long long *const gsc = out.scalars + (size_t)J.group * XT_SCALARS;
-    if (tid < 7 && lsc[tid]) gadd(&gsc[tid], lsc[tid]);
-    if ((tid == 7 || tid == 8) && lsc[tid]) (void)__hip_atomic_fetch_max(&gsc[tid], lsc[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    flush_scalars(lsc, out.scalars + (size_t)J.group * XT_SCALARS, XT_SUMS, XT_MAXIMA, tid);
 }
 
 } // namespace
@@ -161,7 +134,7 @@ hipError_t launch_xtab_kernel(const TimelineJob *jobs, int njobs, int workgroups
     const size_t ncell = ((size_t)ax.row_bins + 1) * ((size_t)ax.col_bins + 1);
     const bool priv = scheme == 1 && ncell <= (size_t)XT_WINDOW_WORDS;
     const int copies = priv && ncell * XT_WAVES <= (size_t)XT_COPY_WORDS ? XT_WAVES : 1;
-    const size_t lds = 4 * ((size_t)XT_SCHED_CAP + 2 * XT_SCALARS + (priv ? ncell * (size_t)copies : 0));
+    const size_t lds = 4 * ((size_t)TILE_SCHED_CAP + 2 * XT_SCALARS + (priv ? ncell * (size_t)copies : 0));
     if (scheme == 0) return launch_with_lds(xtab_kernel<0>, workgroups, TL_THREADS, lds, stream, jobs, njobs, ax, copies, out);
     return launch_with_lds(xtab_kernel<1>, workgroups, TL_THREADS, lds, stream, jobs, njobs, ax, copies, out);
 }

@@ -1,6 +1,7 @@
 """prach::trace_kernel on rows no trial writes: tests/tools/gpu_trace_harness.hip launches the kernel directly on its own cases — every lane of a tile near
 2^31 - 1 so that the 64-bit sums are exercised, rows one subframe shorter and longer than a tile, a bin wider than the row, all-zero rows, subframes behind
-the last bin — under both binning schemes, one launch per child process, one child at a time; every output word equals the harness's plain host loop."""
+the last bin, jobs without subframes between the others — under both binning schemes, one launch per child process, one child at a time; every output
+word equals the harness's plain host loop."""
 import os
 import subprocess
 
@@ -11,7 +12,7 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 
 CASES = ["huge_values_full_tile", "huge_values_one_bin", "tile_minus_one", "tile_plus_one", "tile_edges_bin7", "bin_wider_than_row", "all_zero",
-         "overflow_behind_bins"]
+         "overflow_behind_bins", "jobs_without_subframes"]
 _abnormal = []  # a harness run that ended abnormally (a HIP error, a signal, a timeout): no later test of this file starts another one
 
 

@@ -60,6 +60,8 @@ std::vector<Case> all_cases() {
     cs.push_back({"bin_wider_than_row", 2, 100000, 2, {make_trial(777, 0, 2, 10), make_trial(3 * T + 3, 1, 2, 11)}});
     cs.push_back({"all_zero", 100, 50, 2, {make_trial(2 * T + 9, 0, 0, 12), make_trial(5, 1, 0, 13)}});
     cs.push_back({"overflow_behind_bins", 10, 100, 2, {make_trial(3 * T, 0, 2, 14), make_trial(999, 1, 2, 15), make_trial(1001, 1, 1, 16)}});
+    // jobs without subframes, so without workgroups: their wg0 is the next job's (or the launch's workgroup count) — in front, two in the middle, at the end
+    cs.push_back({"jobs_without_subframes", 4, 2, 3, {make_trial(0, 2, 2, 17), make_trial(5, 0, 2, 18), make_trial(0, 0, 2, 19), make_trial(0, 2, 2, 20), make_trial(3, 1, 2, 21), make_trial(0, 1, 2, 22)}});
     return cs;
 }
 
@@ -83,7 +85,7 @@ int main(int argc, char **argv) {
     const size_t ng = (size_t)c.ngroups, per = ng * (size_t)c.bins, out_words = 4 * per + ng * TR_SCALARS;
     std::vector<unsigned long long> ref(out_words, 0);
     for (const Trial &T : c.trials) {
-        if (T.group < 0 || T.group >= c.ngroups || T.steps < 1) return fail("case: trial out of range");
+        if (T.group < 0 || T.group >= c.ngroups || T.steps < 0) return fail("case: trial out of range");
         unsigned long long *const sc = &ref[4 * per + (size_t)T.group * TR_SCALARS];
         sc[0] += (unsigned long long)T.steps;
         for (int t = 0; t < T.steps; t++) {
