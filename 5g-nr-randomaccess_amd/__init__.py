@@ -54,7 +54,7 @@ class PrachTiming(C.Structure):
                 ("launches", C.c_int32), ("workgroups", C.c_int32), ("updates", C.c_uint64),
                 ("cluster_size", C.c_int32), ("resident_limit", C.c_int32), ("fallback_trials", C.c_int32), ("spin_timeouts", C.c_int32),
                 ("rec_mode", C.c_int32), ("xcd_packed", C.c_int32), ("group_visits", C.c_uint64), ("event_ues", C.c_uint64),
-                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("xtab_ms", C.c_double), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
+                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("pick_ms", C.c_double), ("xtab_ms", C.c_double), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
                 ("sojourn_ms", C.c_double)]
 
 
@@ -413,11 +413,104 @@ class Xtab(_Reduction):
     def _cargs(self, g):
         return tuple(self._rows(g))
 
+    def cell_clauses(self, row_bin, col_bin):
+        """The two clauses (field, lo, hi) of a pick (Engine.run_trials_pick, where=) that select exactly the UEs counted in cell [row_bin, col_bin]; the last
+        bin of an axis is its overflow bin, which has no upper edge (hi is the largest int32)."""
+        out = []
+        for (f, w, b), bin_ in ((self.rows, int(row_bin)), (self.cols, int(col_bin))):
+            if not 0 <= bin_ <= b:
+                raise ValueError(f"bin {bin_} is not one of the {b} + 1 bins of the axis")
+            out.append((f, bin_ * w, (bin_ + 1) * w - 1 if bin_ < b else 2 ** 31 - 1))
+        return out
+
     def quantile(self, g, row, q):
         """Lower edge of the column bin holding the max(1, ceil(q * n))-th smallest column value of row ``row`` of group g (row -1: pooled over all rows), n
         counting the overflow column too; -1: nothing there, or that rank lies in the overflow column (prach_xtab_quantile)."""
         sp = self.spec()
         return int(lib().prach_xtab_quantile(C.byref(sp), self._rows(g)[0], int(row), float(q)))
+
+
+PICK_MAX_K, PICK_MAX_CLAUSES = 4096, 4
+PICK_ORDERS = {"index": 0, "largest": 1, "smallest": 2}
+PICK_FIELDS = ("status", "nUE", "selected", "matched", "stored", "undefined", "range_errors", "threshold", "ties_left_out")
+
+
+class PrachPickClause(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("field", "lo", "hi")]
+
+
+class PrachPickSpec(C.Structure):
+    _fields_ = [("who", C.c_int32), ("nclauses", C.c_int32), ("clause", PrachPickClause * PICK_MAX_CLAUSES)] + [(n, C.c_int32) for n in ("order", "key_field", "k", "reserved")]
+
+
+class PrachPickRow(C.Structure):
+    _fields_ = [("log", PrachUeLog), ("arrival", C.c_int32), ("key", C.c_int32), ("pad", C.c_int32 * 2)]
+
+
+class PrachPick(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in PICK_FIELDS]
+
+
+def pick_row_dtype():
+    """prach_pick_row as a numpy structured dtype (80 bytes): the 16 logged fields by name, then arrival, key and two zero words."""
+    import numpy as np
+    dt = np.dtype([(n, np.int32) for n in UE_FIELDS + ("arrival", "key")] + [("pad", np.int32, (2,))])
+    assert dt.itemsize == C.sizeof(PrachPickRow) == 80
+    return dt
+
+
+def pick_header_dtype():
+    import numpy as np
+    dt = np.dtype([(n, np.int32) for n in PICK_FIELDS])
+    assert dt.itemsize == C.sizeof(PrachPick)
+    return dt
+
+
+def _xtab_field(f):
+    return XTAB_FIELD_NAMES.index(f.lower()) if isinstance(f, str) and not f.lstrip("-").isdigit() else int(f)
+
+
+def pick_parse_clause(text):
+    """FIELD:LO:HI of the drivers as (field id, lo, hi)."""
+    parts = text.split(":")
+    if len(parts) != 3 or parts[0].lower() not in XTAB_FIELD_NAMES:
+        raise ValueError(f"a clause is FIELD:LO:HI, FIELD one of {', '.join(XTAB_FIELD_NAMES)}: {text!r}")
+    return XTAB_FIELD_NAMES.index(parts[0].lower()), int(parts[1]), int(parts[2])
+
+
+class Pick:
+    """The picks of ``n`` trials (include/prach.h, prach_pick): ``headers`` is a numpy structured array (pick_header_dtype) in trial order and ``rows`` one of
+    shape [n, k] (pick_row_dtype); the first headers[t]["stored"] rows of trial t are its UEs in the defined order, the rows behind them are zero.
+    where: up to four clauses (field, lo, hi), a field of XTAB_FIELD_NAMES; order: "index", "largest" or "smallest", the last two by the field ``key``;
+    who: the classes that are selected, bits XTAB_SERVED | XTAB_UNSERVED | XTAB_IDLE."""
+
+    def __init__(self, n, where=(), order="index", key=None, k=16, who=XTAB_WHO["all"]):
+        import numpy as np
+        self.where = tuple((_xtab_field(f), int(lo), int(hi)) for f, lo, hi in where)
+        self.order = PICK_ORDERS[order] if isinstance(order, str) else int(order)
+        self.key = 0 if key is None else _xtab_field(key)
+        self.k, self.who = int(k), int(who)
+        self.headers = np.zeros(int(n), dtype=pick_header_dtype())
+        self.headers["threshold"] = -1
+        self.rows = np.zeros((int(n), max(self.k, 1)), dtype=pick_row_dtype())
+
+    def spec(self):
+        sp = PrachPickSpec()
+        sp.who, sp.nclauses, sp.order, sp.key_field, sp.k = self.who, len(self.where), self.order, self.key, self.k  # (a count the library refuses stays visible to it)
+        for c, (f, lo, hi) in enumerate(self.where[:PICK_MAX_CLAUSES]):
+            sp.clause[c] = PrachPickClause(f, lo, hi)
+        return sp
+
+    def _headers_ptr(self):
+        return self.headers.ctypes.data_as(C.POINTER(PrachPick))
+
+    def _rows_ptr(self, t=0):
+        return C.cast(self.rows.ctypes.data + t * self.rows.strides[0], C.POINTER(PrachPickRow))
+
+    def same_as(self, other):
+        import numpy as np
+        return (self.where, self.order, self.key, self.k, self.who) == (other.where, other.order, other.key, other.k, other.who) and \
+            all(np.array_equal(self.headers[f], other.headers[f]) for f in PICK_FIELDS) and all(np.array_equal(self.rows[f], other.rows[f]) for f in self.rows.dtype.names)
 
 
 class PrachError(RuntimeError):
@@ -500,6 +593,11 @@ def lib():
         L.prach_summary_format_csv.argtypes = [C.POINTER(PrachSummarySpec), C.POINTER(PrachStat), C.c_char_p, C.c_char_p, C.c_size_t]
         L.prach_summary_format_csv.restype = C.c_size_t
         L.prach_summary_max_value.argtypes = []
+        L.prach_run_trials_pick.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachPickSpec),
+                                            C.POINTER(PrachPick), C.POINTER(PrachPickRow)]
+        L.prach_pick_from_logs.argtypes = [C.POINTER(PrachPickSpec), C.POINTER(PrachCfg), C.c_uint64, C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachPick), C.POINTER(PrachPickRow)]
+        L.prach_pick_format_csv.argtypes = [C.POINTER(PrachPickSpec), C.POINTER(PrachPick), C.POINTER(PrachPickRow), C.c_char_p, C.c_int, C.c_uint64, C.c_char_p, C.c_size_t]
+        L.prach_pick_format_csv.restype = C.c_size_t
         L.prach_run_trials_trace.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachTraceSpec),
                                              C.POINTER(C.c_int32), C.POINTER(PrachTrace), u64p, u64p, u64p, u64p]
         L.prach_trace_merge.argtypes = [C.POINTER(PrachTraceSpec), C.POINTER(PrachTrace), u64pp, C.POINTER(PrachTrace), u64pp]
@@ -550,7 +648,8 @@ EXPORTS = ("prach_engine_create", "prach_engine_destroy", "prach_engine_set", "p
            "prach_sojourn_merge", "prach_sojourn_quantile", "prach_sojourn_format_csv", "prach_sojourn_tile_ues", "prach_sojourn_window_words",
            "prach_run_trials_summary", "prach_summary_from_logs", "prach_summary_stats", "prach_summary_format_csv", "prach_summary_max_value",
            "prach_run_trials_trace", "prach_trace_merge", "prach_trace_format_csv", "prach_trace_tile_subframes", "prach_run_trials_xtab", "prach_xtab_accumulate_logs",
-           "prach_xtab_merge", "prach_xtab_quantile", "prach_xtab_format_csv", "prach_xtab_tile_ues", "prach_xtab_window_words")
+           "prach_xtab_merge", "prach_xtab_quantile", "prach_xtab_format_csv", "prach_xtab_tile_ues", "prach_xtab_window_words", "prach_run_trials_pick",
+           "prach_pick_from_logs", "prach_pick_format_csv")
 
 
 def make_cfg(nUE, variant=VARIANT_BETA_C, uniform=0, rng_mode=RNG_GLIBC, seed=0, stream_offset=0, **kw) -> PrachCfg:
@@ -651,6 +750,16 @@ class Engine:
         sp = sm.spec()
         res, logs = self._call("prach_run_trials_summary", cfgs, want_logs, C.byref(sp), sm._rows_ptr())
         return res, logs, sm
+
+    def run_trials_pick(self, cfgs, where=(), order="index", key=None, k=16, who=XTAB_WHO["all"], want_logs=False):
+        """run_trials plus, per trial, the k UEs that match the clauses ``where`` ((field, lo, hi), a field of XTAB_FIELD_NAMES, lo <= value <= hi) among the
+        classes ``who`` — the first k by UE index (order "index"), or the k with the "largest" / "smallest" value of the field ``key``, equal keys in ascending
+        UE index — as records, and the exact number of matches, selected on the device (prach_run_trials_pick; Beta.c and RandomAccessWithNOMA trials only).
+        Xtab.cell_clauses gives the ``where`` of a cell of a cross-tabulation.  Returns (results, logs, Pick)."""
+        pk = Pick(len(cfgs), where, order, key, k, who)
+        sp = pk.spec()
+        res, logs = self._call("prach_run_trials_pick", cfgs, want_logs, C.byref(sp), pk._headers_ptr(), pk._rows_ptr())
+        return res, logs, pk
 
     def run_trials_trace(self, cfgs, bins, bin_ms=1, groups=None, want_logs=False, ngroups=None):
         """run_trials plus the per-subframe preamble trace per trial group — preambles used (calls), decoded (singles) and what the subframes added to
@@ -910,6 +1019,37 @@ def summary_csv(sm: Summary, groups=None, ngroups=None, labels=None) -> bytes:
         n = lib().prach_summary_format_csv(*args, buf, need + 1)
         out += buf.raw[:n]
     return out
+
+
+def pick_from_logs(cfgs, steps, logs, where=(), order="index", key=None, k=16, who=XTAB_WHO["all"]) -> Pick:
+    """The host-side definition of the pick (prach_pick_from_logs): trial t from logs[t], the per-UE log of the trial with config cfgs[t] that ran steps[t]
+    subframes (prach_result.steps) — a ctypes array of PrachUeLog, as Engine.run_trials returns it, or an int32 array of shape [nUE, 16]."""
+    pk = Pick(len(logs), where, order, key, k, who)
+    sp = pk.spec()
+    hdr = pk._headers_ptr()
+    for t, lg in enumerate(logs):
+        ptr, nue, _keep = _log_ptr(lg)
+        rc = lib().prach_pick_from_logs(C.byref(sp), C.byref(cfgs[t]), int(steps[t]), ptr, nue, C.byref(hdr[t]), pk._rows_ptr(t))
+        if rc != OK:
+            raise PrachError(rc, "(prach_pick_from_logs)")
+    return pk
+
+
+def pick_csv(pk: Pick, cfgs=None, labels=None) -> bytes:
+    """The CSV text of every trial's pick (prach_pick_format_csv), trial by trial: labelled labels[t] (default: the trial's nUE), with the seed of cfgs[t]
+    (default 0)."""
+    out = []
+    sp = pk.spec()
+    hdr = pk._headers_ptr()
+    for t in range(len(pk.headers)):
+        label = str(int(pk.headers["nUE"][t]) if labels is None else labels[t]).encode()
+        args = (C.byref(sp), C.byref(hdr[t]), pk._rows_ptr(t), label, t, int(cfgs[t].seed) if cfgs is not None else 0)
+        need = lib().prach_pick_format_csv(*args, None, 0)
+        buf = C.create_string_buffer(need + 1)
+        n = lib().prach_pick_format_csv(*args, buf, need + 1)
+        assert n == need
+        out.append(buf.raw[:n])
+    return b"".join(out)
 
 
 def xtab_tile_ues() -> int:

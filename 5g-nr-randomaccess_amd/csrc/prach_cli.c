@@ -39,6 +39,11 @@
  * one of one, arrival, sojourn, completion, timer, ptc, failcount, age, state; the defaults — rows arrival:500 with as many bins as cover maxTime, columns
  * state:1:7, everybody — say what became of the UEs by when they arrived; --program beta|withnoma only, and not together with --cdf, --timeline, --sojourn,
  * --ci or --trace (one reduction per call);
+ * --pick FILE [--pick-where FIELD:LO:HI]... [--pick-top FIELD | --pick-bottom FIELD] [--pick-k K] [--pick-who served|unserved|arrived|idle|all]: WHICH UEs stand
+ * behind a count (prach_run_trials_pick: selected on the device, so it works with --logs 0): per trial of the grid, in trial order, a header line with the
+ * exact number of matches and the K (default 16) UEs that pass every clause LO <= FIELD <= HI (at most 4) — the first K by index, or those with the largest
+ * (--pick-top) / smallest (--pick-bottom) FIELD — as one line each: label nUE, trial, seed, nUE, rank, key, arrival and the 16 logged fields; --program
+ * beta|withnoma only, and not together with --cdf, --timeline, --sojourn, --ci, --trace or --xtab (one reduction per call);
  * --devices LIST: the same with explicit HIP ordinals (an ordinal may repeat);
  * --gpus N: the --times x sweep grid sharded over N devices of the node by host C — one forked child per device,
  * forked BEFORE any HIP call, trials dealt by descending cost (Philox: any trial anywhere; glibc: whole seeds, because
@@ -122,6 +127,10 @@ typedef struct reduction {
     prach_trial_summary *sm_rows;
     const prach_trace_spec *tr; /* --trace: prach_trace[npts] | four series [npts][bins] each (calls, singles, txop, collisions) */
     const prach_xtab_spec *xt;  /* --xtab: prach_xtab[npts] | cells[npts][row_bins + 1][col_bins + 1] */
+    /* --pick (prach_run_trials_pick), like --ci: one header and k rows per trial of the grid, in shared mappings; the parent writes them in trial order */
+    const prach_pick_spec *pk;
+    prach_pick *pk_hdr;
+    prach_pick_row *pk_rows;
 } reduction;
 static int red_on(const reduction *r) { return r->cdf || r->tl || r->sj || r->tr || r->xt; }
 static size_t xt_cells(const prach_xtab_spec *s) { return ((size_t)s->row_bins + 1) * ((size_t)s->col_bins + 1); }
@@ -195,13 +204,28 @@ static size_t red_format_group(const reduction *r, char *b, int g, const char *l
 
 /* FIELD[:WIDTH[:BINS]] of --xtab-rows / --xtab-cols.  Defaults: width 500 for arrival, otherwise 1; as many bins as cover max_time (arrival) or max_time + 6 (the
  * other times), 7 for state, 1 for one, 255 for ptc and failcount.  Returns 0 for a text that is none */
+static const char *const xtab_names[PRACH_XTAB_NFIELDS] = {"one", "arrival", "sojourn", "completion", "timer", "ptc", "failcount", "age", "state"};
+/* the field of the menu that the first `len` characters of `text` name; -1: none */
+static int xtab_field(const char *text, size_t len) {
+    for (int q = 0; q < PRACH_XTAB_NFIELDS; q++)
+        if (strlen(xtab_names[q]) == len && strncasecmp(xtab_names[q], text, len) == 0) return q;
+    return -1;
+}
+/* FIELD:LO:HI of --pick-where.  Returns 0 for a text that is none */
+static int pick_clause(const char *text, prach_pick_clause *c) {
+    const char *c1 = strchr(text, ':'), *c2 = c1 ? strchr(c1 + 1, ':') : NULL;
+    if (!c2 || strchr(c2 + 1, ':')) return 0;
+    const int f = xtab_field(text, (size_t)(c1 - text));
+    char *end1, *end2;
+    const long lo = strtol(c1 + 1, &end1, 10), hi = strtol(c2 + 1, &end2, 10);
+    if (f < 0 || end1 != c2 || end1 == c1 + 1 || *end2 || end2 == c2 + 1 || lo < 0 || hi < lo || hi > INT32_MAX) return 0;
+    c->field = f; c->lo = (int32_t)lo; c->hi = (int32_t)hi;
+    return 1;
+}
 static int xtab_axis(const char *text, int max_time, int32_t *field, int32_t *width, int32_t *bins) {
-    static const char *const names[PRACH_XTAB_NFIELDS] = {"one", "arrival", "sojourn", "completion", "timer", "ptc", "failcount", "age", "state"};
     const char *c1 = strchr(text, ':'), *c2 = c1 ? strchr(c1 + 1, ':') : NULL;
     const size_t len = c1 ? (size_t)(c1 - text) : strlen(text);
-    int f = -1;
-    for (int q = 0; q < PRACH_XTAB_NFIELDS; q++)
-        if (strlen(names[q]) == len && strncasecmp(names[q], text, len) == 0) f = q;
+    const int f = xtab_field(text, len);
     if (f < 0 || (c2 && strchr(c2 + 1, ':'))) return 0;
     const long w = c1 ? atol(c1 + 1) : f == PRACH_XTAB_ARRIVAL ? 500 : 1;
     if (w < 1 || w > INT32_MAX) return 0;
@@ -216,8 +240,9 @@ static int xtab_axis(const char *text, int max_time, int32_t *field, int32_t *wi
 
 /* one call into the library with the run's reduction: its groups (group = sweep point, grp[k]) come back in call_block and are merged into the worker's block */
 static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *r, prach_ue_log *const *logs, const reduction *red, const int32_t *grp,
-                    char *call_block, char *worker_block, prach_trial_summary *sm_rows) {
+                    char *call_block, char *worker_block, prach_trial_summary *sm_rows, prach_pick *pk_hdr, prach_pick_row *pk_rows) {
     if (red->sm) return prach_run_trials_summary(eng, c, n, r, logs, red->sm, sm_rows);
+    if (red->pk) return prach_run_trials_pick(eng, c, n, r, logs, red->pk, pk_hdr, pk_rows);
     if (!red_on(red)) return prach_run_trials(eng, c, n, r, logs);
     char *const b = call_block;
     const int rc = red->xt ? prach_run_trials_xtab(eng, c, n, r, logs, red->xt, grp, (prach_xtab *)b, red_array(red, b, 0, 0))
@@ -253,6 +278,11 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
     if (reduces && (!grp || !call_block)) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
     prach_trial_summary *sr = red->sm ? (prach_trial_summary *)malloc(sizeof(prach_trial_summary) * (size_t)(m > 0 ? m : 1)) : NULL;
     if (red->sm && !sr) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+    /* --pick: the headers and rows of one call (at most CH trials, or the worker's seeds) */
+    const size_t pk_n = (size_t)(m < CH ? (m > 0 ? m : 1) : CH), pk_k = red->pk ? (size_t)red->pk->k : 0;
+    prach_pick *ph = red->pk ? (prach_pick *)malloc(sizeof(prach_pick) * pk_n) : NULL;
+    prach_pick_row *pr = red->pk ? (prach_pick_row *)malloc(sizeof(prach_pick_row) * pk_n * pk_k) : NULL;
+    if (red->pk && (!ph || !pr)) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
     if (!glibc) {
         for (int a = 0; a < m; a += CH) {
             const int n = m - a < CH ? m - a : CH;
@@ -264,12 +294,13 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
                     if (!logs[k]) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
                 }
             }
-            rc = run_call(eng, c, n, r, logs, red, grp, call_block, worker_block, sr);
+            rc = run_call(eng, c, n, r, logs, red, grp, call_block, worker_block, sr, ph, pr);
             if (rc != PRACH_OK) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(rc)); return 2; }
             const double lat = now_s() - t0;
             for (int k = 0; k < n; k++) {
                 res[idx[a + k]] = r[k];
                 if (red->sm) red->sm_rows[idx[a + k]] = sr[k];
+                if (red->pk) { red->pk_hdr[idx[a + k]] = ph[k]; memcpy(red->pk_rows + (size_t)idx[a + k] * pk_k, pr + (size_t)k * pk_k, sizeof(prach_pick_row) * pk_k); }
                 lat_out[idx[a + k]] = lat;
                 if (cfgs[idx[a + k]].variant != PRACH_VARIANT_NOMA_C) {
                     rc = prach_write_trial_files(&c[k], &r[k], want_logs ? logs[k] : NULL, lat, outdir);
@@ -292,13 +323,14 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
                     if (!logs[s_]) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
                 }
             }
-            rc = run_call(eng, c, nseeds, r, logs, red, grp, call_block, worker_block, sr);
+            rc = run_call(eng, c, nseeds, r, logs, red, grp, call_block, worker_block, sr, ph, pr);
             if (rc != PRACH_OK) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(rc)); return 2; }
             const double lat = now_s() - t0;
             for (int s_ = 0; s_ < nseeds; s_++) {
                 offset[s_] += r[s_].draws;
                 res[idx[s_ * npts + k]] = r[s_];
                 if (red->sm) red->sm_rows[idx[s_ * npts + k]] = sr[s_];
+                if (red->pk) { red->pk_hdr[idx[s_ * npts + k]] = ph[s_]; memcpy(red->pk_rows + (size_t)idx[s_ * npts + k] * pk_k, pr + (size_t)s_ * pk_k, sizeof(prach_pick_row) * pk_k); }
                 lat_out[idx[s_ * npts + k]] = lat;
                 if (c[s_].variant != PRACH_VARIANT_NOMA_C) { /* (NOMA.c's lines are printed and appended by the parent) */
                     rc = prach_write_trial_files(&c[s_], &r[s_], want_logs ? logs[s_] : NULL, lat, outdir);
@@ -309,7 +341,7 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
         }
         free(offset);
     }
-    free(c); free(r); free(logs); free(grp); free(call_block); free(sr);
+    free(c); free(r); free(logs); free(grp); free(call_block); free(sr); free(ph); free(pr);
     prach_engine_destroy(eng);
     return 0;
 }
@@ -317,7 +349,9 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
 int main(int argc, char *argv[]) {
     int randomMax = 1, variant = PRACH_VARIANT_WITHNOMA_C, rng = PRACH_RNG_GLIBC, device = 0, want_logs = 1, gpus = 1, rng_given = 0;
     int sweep_lo = 10000, sweep_hi = 100000, sweep_step = 10000; /* WithNOMA:221 */
-    const char *outdir = ".", *csv_path = NULL, *devlist = NULL, *cdf_path = NULL, *tl_path = NULL, *sj_path = NULL, *ci_path = NULL, *tr_path = NULL, *xt_path = NULL;
+    const char *outdir = ".", *csv_path = NULL, *devlist = NULL, *cdf_path = NULL, *tl_path = NULL, *sj_path = NULL, *ci_path = NULL, *tr_path = NULL, *xt_path = NULL, *pk_path = NULL;
+    const char *pk_who = "all";
+    prach_pick_spec pk_spec = {0, 0, {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, PRACH_PICK_BY_INDEX, PRACH_XTAB_ONE, 16, 0};
     const char *xt_rows = "arrival:500", *xt_cols = "state:1:7", *xt_who = "all";
     prach_summary_spec ci_spec = {3, {500, 950, 990, 0, 0, 0, 0, 0}, {0, 0, 0}};
     int cdf_bins = 4096, cdf_bin_ms = 1, tl_bin_ms = 5, sj_row_ms = 500, sj_bin_ms = 5, tr_bin_ms = 5;
@@ -429,6 +463,20 @@ int main(int argc, char *argv[]) {
             xt_cols = v;
         } else if (strcmp(a, "--xtab-who") == 0) {
             xt_who = v;
+        } else if (strcmp(a, "--pick") == 0) {
+            pk_path = v;
+        } else if (strcmp(a, "--pick-where") == 0) {
+            if (pk_spec.nclauses >= PRACH_PICK_MAX_CLAUSES || !pick_clause(v, &pk_spec.clause[pk_spec.nclauses])) die("--pick-where FIELD:LO:HI: a field of the menu, 0 <= LO <= HI, at most 4 clauses");
+            pk_spec.nclauses++;
+        } else if (strcmp(a, "--pick-top") == 0 || strcmp(a, "--pick-bottom") == 0) {
+            if (pk_spec.order != PRACH_PICK_BY_INDEX || xtab_field(v, strlen(v)) < 0) die("--pick-top FIELD or --pick-bottom FIELD: one of them, with a field of the menu");
+            pk_spec.order = strcmp(a, "--pick-top") == 0 ? PRACH_PICK_LARGEST : PRACH_PICK_SMALLEST;
+            pk_spec.key_field = xtab_field(v, strlen(v));
+        } else if (strcmp(a, "--pick-k") == 0) {
+            if (atoi(v) < 1 || atoi(v) > PRACH_PICK_MAX_K) die("--pick-k K: 1..4096 UEs per trial");
+            pk_spec.k = atoi(v);
+        } else if (strcmp(a, "--pick-who") == 0) {
+            pk_who = v;
         } else if (strcmp(a, "--ci") == 0) {
             ci_path = v;
         } else if (strcmp(a, "--ci-levels") == 0) {
@@ -446,6 +494,8 @@ int main(int argc, char *argv[]) {
         }
     }
     base.rng_mode = rng;
+    if (pk_path && (xt_path || tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--pick cannot be combined with --cdf, --timeline, --sojourn, --ci, --trace or --xtab: one reduction per call");
+    if (pk_path && variant == PRACH_VARIANT_NOMA_C) die("--pick needs --program beta or withnoma (NOMA.c logs no trace of a UE's cycle start)");
     if (xt_path && (tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--xtab cannot be combined with --cdf, --timeline, --sojourn, --ci or --trace: one reduction per call");
     if (xt_path && variant == PRACH_VARIANT_NOMA_C) die("--xtab needs --program beta or withnoma (NOMA.c logs no trace of a UE's cycle start)");
     if (tr_path && (ci_path || sj_path || tl_path || cdf_path)) die("--trace cannot be combined with --cdf, --timeline, --sojourn or --ci: one reduction per call");
@@ -537,7 +587,7 @@ int main(int argc, char *argv[]) {
      * three numbers, per cell and twice per row */
     const reduction red_ = {cdf_path ? &cdf_spec : NULL, tl_path ? &tl_spec : NULL, sj_path ? &sj_spec : NULL, sj_path ? sj_path : tl_path ? tl_path : cdf_path,
                             sj_path ? 64 * ((size_t)sj_rows * ((size_t)sj_bins + 2) + 1) + 1
-                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1, NULL, NULL, NULL, NULL};
+                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
     reduction red_ci = red_;
     /* the trace's bins cover maxTime */
     const int tr_bins = (prach_max_time(&base) + tr_bin_ms - 1) / tr_bin_ms;
@@ -560,6 +610,17 @@ int main(int argc, char *argv[]) {
         red_ci.sm_rows = (prach_trial_summary *)mmap(NULL, sizeof(prach_trial_summary) * (size_t)ntr, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
         if (red_ci.sm_rows == MAP_FAILED) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
         for (int q = 0; q < ntr; q++) red_ci.sm_rows[q].status = PRACH_ERR_INTERNAL; /* (a row no worker wrote counts nowhere) */
+    }
+    if (pk_path) { /* --pick: the headers and rows of the whole grid, filled by the workers */
+        pk_spec.who = strcmp(pk_who, "served") == 0 ? PRACH_XTAB_SERVED : strcmp(pk_who, "unserved") == 0 ? PRACH_XTAB_UNSERVED : strcmp(pk_who, "idle") == 0 ? PRACH_XTAB_IDLE
+                      : strcmp(pk_who, "arrived") == 0 ? (PRACH_XTAB_SERVED | PRACH_XTAB_UNSERVED) : strcmp(pk_who, "all") == 0 ? (PRACH_XTAB_SERVED | PRACH_XTAB_UNSERVED | PRACH_XTAB_IDLE) : 0;
+        if (!pk_spec.who) die("--pick-who served|unserved|arrived|idle|all");
+        if ((uint64_t)ntr * (uint64_t)pk_spec.k > (1ull << 22)) die("--pick: too many rows");
+        red_ci.pk = &pk_spec;
+        red_ci.pk_hdr = (prach_pick *)mmap(NULL, sizeof(prach_pick) * (size_t)ntr, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
+        red_ci.pk_rows = (prach_pick_row *)mmap(NULL, sizeof(prach_pick_row) * (size_t)ntr * (size_t)pk_spec.k, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
+        if (red_ci.pk_hdr == MAP_FAILED || red_ci.pk_rows == MAP_FAILED) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+        for (int q = 0; q < ntr; q++) { red_ci.pk_hdr[q].status = PRACH_ERR_INTERNAL; red_ci.pk_hdr[q].nUE = cfgs[q].nUE; red_ci.pk_hdr[q].threshold = -1; } /* (a trial no worker wrote) */
     }
     const reduction *const red = &red_ci;
     char *red_blocks = NULL;
@@ -631,6 +692,23 @@ int main(int argc, char *argv[]) {
         }
         fclose(fp);
         free(grp); free(st);
+    }
+
+    if (pk_path) { /* every trial of the grid in trial order, labelled nUE: the same whatever the number of workers */
+        FILE *fp = fopen(pk_path, "wb");
+        if (!fp) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_IO)); return 2; }
+        const size_t cap = 512 * ((size_t)pk_spec.k + 1) + 1; /* (a line is shorter than the 512 bytes of the formatter's own line buffer) */
+        char *out = (char *)malloc(cap);
+        if (!out) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+        for (int q = 0; q < ntr; q++) {
+            char label[16];
+            snprintf(label, sizeof label, "%d", cfgs[q].nUE);
+            const size_t n = prach_pick_format_csv(&pk_spec, &red->pk_hdr[q], red->pk_rows + (size_t)q * (size_t)pk_spec.k, label, q, cfgs[q].seed, out, cap);
+            if (n == 0 || n >= cap) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_INTERNAL)); return 2; }
+            fwrite(out, 1, n, fp);
+        }
+        free(out);
+        fclose(fp);
     }
 
     /* the parent prints in the reference's order and merges */

@@ -239,6 +239,19 @@ struct SummaryLevels { int nq; int permille[PRACH_SUMMARY_MAX_Q]; };
 int summary_sched_cap();
 hipError_t launch_summary_kernel(const TimelineJob *jobs, int njobs, SummaryLevels levels, int threads, int sched_cap, unsigned long long *rows, hipStream_t stream);
 
+// prach_pick.hip: the pick of every accepted trial of a launch (prach_run_trials_pick).  The jobs are the timeline's with E = min(steps, maxTime) in `pad`
+// (group = the trial's row block), ONE workgroup per trial.  Per trial the kernel stores up to spec.k rows of PK_ROW_WORDS 64-bit words (prach_pick_row: the
+// 64-byte log record, a(i), the key, two zero words) IN UE-INDEX ORDER — the engine sorts them into the defined order — and PK_SCALARS 64-bit scalars:
+// selected, matched, stored, undefined, range_errors, threshold (signed, -1: nothing stored), ties_left_out, 0.  Plain stores; rows behind `stored` are not
+// written.
+constexpr int PK_ROW_WORDS = 10, PK_SCALARS = 8;
+static_assert(8 * PK_ROW_WORDS == sizeof(prach_pick_row) && sizeof(prach_pick_row) % 16 == 0 && alignof(prach_pick_row) == 8, "a row is five 16-byte stores");
+extern "C" int prach_internal_pick_spec_ok(const prach_pick_spec *spec); // prach_host.c
+// threads: 512 or 1024; sched_cap: schedule entries staged in LDS (the longest schedule of the jobs, cut to pick_sched_cap()); spec: a valid one
+int pick_sched_cap();
+hipError_t launch_pick_kernel(const TimelineJob *jobs, int njobs, prach_pick_spec spec, int threads, int sched_cap, unsigned long long *rows, unsigned long long *scalars,
+                              hipStream_t stream);
+
 // prach_trace.hip: the per-subframe preamble trace of a launch's accepted trials (prach_run_trials_trace).  One job per trial: the rows the simulation kernel
 // wrote through TrialDev::trace, for the subframes [0, steps).  A workgroup reduces one tile of TR_TILE consecutive subframes of one trial, 16 bytes per lane
 // and load.  A tile covers at most TR_TILE consecutive bins (bin = t / bin_ms): scheme 1 adds them up in an LDS window of 64-bit counters anchored at the

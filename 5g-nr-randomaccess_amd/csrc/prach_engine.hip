@@ -52,6 +52,7 @@ struct prach_engine {
     hipEvent_t red_ev0 = nullptr, red_ev1 = nullptr;
     int64_t opt_trace_scheme = 1;    // trace_kernel's binning (prach_trace.hip): 0 global atomics only, 1 the tile's bins added up in an LDS window first
     int64_t opt_summary_threads = 1024; // summary_kernel's workgroup (prach_summary.hip): 512 or 1024 threads, one workgroup per trial
+    int64_t opt_pick_threads = 1024;    // pick_kernel's workgroup (prach_pick.hip): 512 or 1024 threads, one workgroup per trial
     int64_t opt_xtab_scheme = 1;     // xtab_kernel's binning (prach_xtab.hip): 0 global atomics only, 1 a table that fits privatised in LDS
     int64_t opt_sojourn_scheme = 1;  // sojourn_kernel's binning (prach_sojourn.hip): 0 global atomics only, 1 rows of the histogram privatised in LDS
     int64_t opt_timeline_scheme = 1; // timeline_kernel's binning (prach_timeline.hip): 0 global atomics only, 1 windows of bins privatised in LDS (measured faster: DESIGN.md 4)
@@ -419,13 +420,13 @@ static int noma_device_activation(prach_engine *e, const TrialDev *dparams, cons
     return PRACH_OK;
 }
 
-// What a call reduces on the device next to its results (prach_run_trials_dist, _timeline, _sojourn, _summary, _trace, _xtab).  The call's device buffer is a
+// What a call reduces on the device next to its results (prach_run_trials_dist, _timeline, _sojourn, _summary, _trace, _xtab, _pick).  The call's device buffer is a
 // row of parts, [ngroups][words] 64-bit counters each: the arrays the caller gets as they are, one per part, then the scalars the kernel keeps per group,
 // which the engine unpacks into the caller's per-group structs.  Every launch of the call gets one job per trial it finished, and the kind's kernel behind
 // the simulation kernel.  What differs between the kinds is stated ONCE per kind: a block of functions behind CallCtx and its row of RED_KINDS.  The generic
 // code (reduction_begin, run_group, reduction_end, run_trials_impl) walks that row and never asks which kind it has; a new kind is an enumerator, a block and
 // a row.
-enum class Red { dist, timeline, sojourn, summary, trace, xtab };
+enum class Red { dist, timeline, sojourn, summary, trace, xtab, pick };
 constexpr int RED_MAX_PARTS = 6;
 struct Reduction {
     Red kind;
@@ -487,7 +488,7 @@ template <class T> T &group_of(const Reduction &r, size_t g) { return static_cas
 // the caller's struct of a group before anything ran: zeros, and -1 where a maximum over nothing stands
 template <class T, int64_t T::*...MAX> void empty_group(const Reduction &r, size_t g, const prach_cfg *) { T &t = group_of<T>(r, g); t = T{}; ((t.*MAX = -1), ...); }
 int subframes_run(const JobSrc &s) { return (int)std::min<unsigned long long>(s.dr.steps, (unsigned long long)prach_max_time(&s.c)); }
-// timeline, sojourn, summary and xtab read a trial's log records and the launch's own copy of its arrival schedule; STEPS (xtab): E of include/prach.h in the last word
+// timeline, sojourn, summary, xtab and pick read a trial's log records and the launch's own copy of its arrival schedule; STEPS (xtab, pick): E of include/prach.h in the last word
 template <bool STEPS> int fill_timeline_job(void *job, const JobSrc &s) {
     const int nslots = (prach_max_time(&s.c) + s.c.accessTime - 1) / s.c.accessTime; // (what prach_arrival_schedule fills; the table has one entry more)
     *static_cast<TimelineJob *>(job) = TimelineJob{reinterpret_cast<const int4 *>(s.A + s.L.logs), reinterpret_cast<const int *>(s.A + s.L.sched), s.c.nUE, s.group, s.wg0, s.c.accessTime, nslots,
@@ -615,6 +616,44 @@ int xtab_unpack(const Reduction &r, CallCtx &cx, size_t g, const unsigned long l
     return PRACH_OK;
 }
 
+// pick: every trial is its own group, as in the summary; the rows, k x PK_ROW_WORDS words per trial, go to the caller as they are and are then sorted in
+// place, trial by trial, into the defined order (the kernel leaves them in UE-index order: prach_pick.hip) | scalars; ONE workgroup per job
+int pick_parts(const Reduction &r, size_t w[]) { w[0] = (size_t)spec_of<prach_pick_spec>(r).k * PK_ROW_WORDS; w[1] = PK_SCALARS; return 2; }
+hipError_t pick_launch(const prach_engine *e, const Reduction &r, int njobs, int, unsigned long long *const *d) {
+    int max_slots = 0; // the longest schedule of the jobs
+    for (int j = 0; j < njobs; j++) max_slots = std::max(max_slots, reinterpret_cast<const TimelineJob *>(e->red_jobs_h)[j].nslots);
+    return launch_pick_kernel(timeline_jobs(e), njobs, spec_of<prach_pick_spec>(r), (int)e->opt_pick_threads, std::min(max_slots, pick_sched_cap()), d[0], d[1], e->stream);
+}
+void pick_empty(const Reduction &r, size_t t, const prach_cfg *cfgs) {
+    prach_pick &h = group_of<prach_pick>(r, t);
+    h = prach_pick{};
+    h.status = PRACH_ERR_INTERNAL;
+    h.nUE = cfgs[t].nUE;
+    h.threshold = -1;
+}
+int pick_unpack(const Reduction &r, CallCtx &cx, size_t t, const unsigned long long *words) { // status and nUE from the host, the rest from the one launch that accepted the trial
+    const prach_pick_spec &sp = spec_of<prach_pick_spec>(r);
+    prach_pick &h = group_of<prach_pick>(r, t);
+    prach_pick_row *const rows = reinterpret_cast<prach_pick_row *>(r.out[0]) + t * (size_t)sp.k;
+    h.status = cx.results[t].status; // (everything else is still the empty header, and no launch wrote a row of a trial it did not accept)
+    if (h.status != PRACH_OK) return PRACH_OK;
+    const long long *const q = reinterpret_cast<const long long *>(words);
+    if (cx.trials[t] != 1 || q[2] < 0 || q[2] > sp.k) { // (no launch picked from this trial, or two did)
+        std::memset(rows, 0, sizeof(prach_pick_row) * (size_t)sp.k);
+        return h.status = PRACH_ERR_INTERNAL;
+    }
+    h.selected = (int32_t)q[0]; h.matched = (int32_t)q[1]; h.undefined = (int32_t)q[3]; h.range_errors = (int32_t)q[4];
+    if (h.range_errors) { // (a key the kernel cannot rank: no trial produces one) the rows are void
+        std::memset(rows, 0, sizeof(prach_pick_row) * (size_t)sp.k);
+        return PRACH_ERR_INTERNAL;
+    }
+    h.stored = (int32_t)q[2]; h.threshold = (int32_t)q[5]; h.ties_left_out = (int32_t)q[6];
+    // stable: equal keys stay in ascending UE index
+    if (sp.order == PRACH_PICK_LARGEST) std::stable_sort(rows, rows + h.stored, [](const prach_pick_row &a, const prach_pick_row &b) { return a.key > b.key; });
+    if (sp.order == PRACH_PICK_SMALLEST) std::stable_sort(rows, rows + h.stored, [](const prach_pick_row &a, const prach_pick_row &b) { return a.key < b.key; });
+    return PRACH_OK;
+}
+
 // in the order of enum class Red:           parts, job bytes, tile, job, device logs, trace rows, "fast" off, launch, empty, unpack, prach_timing field
 const RedKind RED_KINDS[] = {
     {dist_parts, sizeof(DistJob), DIST_TILE, dist_fill_job, false, false, false, dist_launch, empty_group<prach_dist, &prach_dist::delay_max>, dist_unpack, &prach_timing::dist_ms},
@@ -623,8 +662,9 @@ const RedKind RED_KINDS[] = {
     {summary_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<false>, true, false, false, summary_launch, summary_empty, summary_unpack, &prach_timing::summary_ms},
     {trace_parts, sizeof(TraceJob), TR_TILE, trace_fill_job, false, true, true, trace_launch, empty_group<prach_trace, &prach_trace::calls_max>, trace_unpack, &prach_timing::trace_ms},
     {xtab_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, xtab_launch, empty_group<prach_xtab, &prach_xtab::row_max, &prach_xtab::col_max>, xtab_unpack, &prach_timing::xtab_ms},
+    {pick_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, pick_launch, pick_empty, pick_unpack, &prach_timing::pick_ms},
 };
-static_assert(sizeof(RED_KINDS) / sizeof(RED_KINDS[0]) == (size_t)Red::xtab + 1, "one row per kind");
+static_assert(sizeof(RED_KINDS) / sizeof(RED_KINDS[0]) == (size_t)Red::pick + 1, "one row per kind");
 const RedKind &kind_of(const Reduction &r) { return RED_KINDS[(int)r.kind]; }
 
 // How a rerun's launch differs from the first one
@@ -1404,6 +1444,7 @@ int prach_engine_set(prach_engine *e, const char *key, int64_t value) {
     if (std::strcmp(key, "dist_scheme") == 0) { if (value < 0 || value > 2) return PRACH_ERR_ARG; e->opt_dist_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "timeline_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_timeline_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "summary_threads") == 0) { if (value != 0 && value != 512 && value != 1024) return PRACH_ERR_ARG; e->opt_summary_threads = value ? value : 1024; return PRACH_OK; }
+    if (std::strcmp(key, "pick_threads") == 0) { if (value != 0 && value != 512 && value != 1024) return PRACH_ERR_ARG; e->opt_pick_threads = value ? value : 1024; return PRACH_OK; }
     if (std::strcmp(key, "trace_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_trace_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "xtab_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_xtab_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "sojourn_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_sojourn_scheme = value; return PRACH_OK; }
@@ -1571,6 +1612,17 @@ int prach_run_trials_xtab(prach_engine *e, const prach_cfg *cfgs, int n, prach_r
     if ((uint64_t)spec->ngroups * ((uint64_t)spec->row_bins + 1) * ((uint64_t)spec->col_bins + 1) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
     const Reduction red{.kind = Red::xtab, .group = group, .ngroups = spec->ngroups, .out = {cells}, .spec = spec, .groups = xt};
+    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
+}
+
+int prach_run_trials_pick(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_pick_spec *spec,
+                          prach_pick *picks, prach_pick_row *rows) {
+    // (spec and variants are judged first: what they ask for does not depend on a device)
+    if (!cfgs || !results || n <= 0 || !spec || !picks || !rows || !prach_internal_pick_spec_ok(spec)) return PRACH_ERR_ARG;
+    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
+    if ((uint64_t)n * ((uint64_t)spec->k * PK_ROW_WORDS + PK_SCALARS) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
+    if (!e) return PRACH_ERR_ARG;
+    const Reduction red{.kind = Red::pick, .group = nullptr, .ngroups = n, .out = {reinterpret_cast<uint64_t *>(rows)}, .spec = spec, .groups = picks};
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 

@@ -993,6 +993,98 @@ size_t prach_xtab_format_csv(const prach_xtab_spec *s, const prach_xtab *x, cons
     return csv_end(buf, cap, off);
 }
 
+/* ---- picks: the UEs behind a count, per trial (prach_run_trials_pick) ----------------------------- */
+
+/* (the engine judges a spec with this too: csrc/prach_device.h) */
+int prach_internal_pick_spec_ok(const prach_pick_spec *s) {
+    if (!s || s->who <= 0 || (s->who & ~(PRACH_XTAB_SERVED | PRACH_XTAB_UNSERVED | PRACH_XTAB_IDLE)) != 0 || s->nclauses < 0 || s->nclauses > PRACH_PICK_MAX_CLAUSES ||
+        s->k < 1 || s->k > PRACH_PICK_MAX_K || s->reserved != 0 || s->key_field < 0 || s->key_field >= PRACH_XTAB_NFIELDS) return 0;
+    if (s->order != PRACH_PICK_BY_INDEX && s->order != PRACH_PICK_LARGEST && s->order != PRACH_PICK_SMALLEST) return 0;
+    if (s->order == PRACH_PICK_BY_INDEX && s->key_field != PRACH_XTAB_ONE) return 0;
+    for (int c = 0; c < PRACH_PICK_MAX_CLAUSES; c++) {
+        const prach_pick_clause *q = &s->clause[c];
+        if (c < s->nclauses ? (q->field < 0 || q->field >= PRACH_XTAB_NFIELDS || q->lo < 0 || q->lo > q->hi) : (q->field || q->lo || q->hi)) return 0;
+    }
+    return 1;
+}
+
+typedef struct pick_cand { int64_t key; int32_t i, arrival; } pick_cand;
+static int cmp_pick_desc(const void *a, const void *b) { /* descending key, equal keys in ascending UE index */
+    const pick_cand *x = (const pick_cand *)a, *y = (const pick_cand *)b;
+    return x->key != y->key ? (x->key < y->key) - (x->key > y->key) : (x->i > y->i) - (x->i < y->i);
+}
+static int cmp_pick_asc(const void *a, const void *b) {
+    const pick_cand *x = (const pick_cand *)a, *y = (const pick_cand *)b;
+    return x->key != y->key ? (x->key > y->key) - (x->key < y->key) : (x->i > y->i) - (x->i < y->i);
+}
+
+/* THE DEFINITION (include/prach.h): every match is listed, the list is sorted, the first k are the rows */
+int prach_pick_from_logs(const prach_pick_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_pick *hdr, prach_pick_row *rows) {
+    if (!prach_internal_pick_spec_ok(s) || !cfg || !hdr || !rows || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    if (cfg->variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED;
+    if (prach_cfg_validate(cfg) != PRACH_OK || nUE != cfg->nUE) return PRACH_ERR_ARG;
+    const int nslots = (prach_max_time(cfg) + cfg->accessTime - 1) / cfg->accessTime;
+    int32_t *sched = (int32_t *)malloc(sizeof(int32_t) * (size_t)nslots);
+    pick_cand *cand = (pick_cand *)malloc(sizeof(pick_cand) * (size_t)(nUE > 0 ? nUE : 1));
+    if (!sched || !cand) { free(sched); free(cand); return PRACH_ERR_INTERNAL; }
+    prach_arrival_schedule(cfg, sched, nslots, NULL);
+    const int64_t E = steps < (uint64_t)prach_max_time(cfg) ? (int64_t)steps : (int64_t)prach_max_time(cfg);
+    const int keyed = s->order != PRACH_PICK_BY_INDEX;
+    prach_pick h;
+    memset(&h, 0, sizeof h);
+    h.status = PRACH_OK; h.nUE = nUE; h.threshold = -1;
+    int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
+    for (int i = 0; i < nUE; i++) {
+        while (slot < nslots && sched[slot] <= i) slot++;
+        const int64_t a = (int64_t)cfg->accessTime * slot;
+        const int cls = xtab_class(&ue[i]);
+        if (!(cls & s->who)) continue;
+        h.selected++;
+        int fails = 0, undef = 0;
+        for (int c = 0; c < s->nclauses; c++) {
+            const int64_t v = xtab_value(s->clause[c].field, &ue[i], cls, a, E);
+            if (v < 0) undef = 1;
+            else if (v < s->clause[c].lo || v > s->clause[c].hi) fails = 1;
+        }
+        const int64_t key = keyed ? xtab_value(s->key_field, &ue[i], cls, a, E) : 0;
+        if (key < 0) undef = 1;
+        if (fails) continue;
+        if (undef) { h.undefined++; continue; }
+        cand[h.matched++] = (pick_cand){key, i, cls == PRACH_XTAB_IDLE ? -1 : (int32_t)a};
+    }
+    if (keyed) qsort(cand, (size_t)h.matched, sizeof(pick_cand), s->order == PRACH_PICK_LARGEST ? cmp_pick_desc : cmp_pick_asc);
+    h.stored = h.matched < s->k ? h.matched : s->k;
+    memset(rows, 0, sizeof(prach_pick_row) * (size_t)s->k);
+    for (int r = 0; r < h.stored; r++) {
+        rows[r].log = ue[cand[r].i];
+        rows[r].arrival = cand[r].arrival;
+        rows[r].key = (int32_t)cand[r].key;
+    }
+    if (keyed && h.stored > 0) {
+        h.threshold = rows[h.stored - 1].key;
+        for (int r = h.stored; r < h.matched && cand[r].key == cand[h.stored - 1].key; r++) h.ties_left_out++;
+    }
+    free(sched);
+    free(cand);
+    *hdr = h;
+    return PRACH_OK;
+}
+
+size_t prach_pick_format_csv(const prach_pick_spec *s, const prach_pick *h, const prach_pick_row *rows, const char *label, int trial, uint64_t seed, char *buf,
+                             size_t cap) {
+    if (!prach_internal_pick_spec_ok(s) || !h || !rows || !label || h->stored < 0 || h->stored > s->k) return 0;
+    size_t off = 0;
+    CSV_EMIT("%.200s,%d,%llu,%d,header,%d,%d,%d,%d,%d,%d,%d\n", label, trial, (unsigned long long)seed, h->nUE, h->status, h->selected, h->matched, h->stored, h->undefined,
+             h->threshold, h->ties_left_out);
+    for (int r = 0; r < h->stored; r++) {
+        const prach_ue_log *u = &rows[r].log;
+        CSV_EMIT("%.200s,%d,%llu,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d\n", label, trial, (unsigned long long)seed, h->nUE, r, rows[r].key, rows[r].arrival,
+                 u->idx, u->timer, u->active, u->txTime, u->firstTxTime, u->secondTxTime, u->nowBackoff, u->preamble, u->preambleChange, u->rarWindow, u->maxRarCounter,
+                 u->preambleTxCounter, u->msg2Flag, u->connectionRequest, u->msg4Flag, u->failCount);
+    }
+    return csv_end(buf, cap, off);
+}
+
 /* ---- per-trial summaries: exact order statistics and the spread across trials (prach_run_trials_summary) ---- */
 
 static int summary_spec_ok(const prach_summary_spec *s) {

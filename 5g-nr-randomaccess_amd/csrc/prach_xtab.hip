@@ -20,6 +20,7 @@
 // The arrival-anchored row window of prach::sojourn_kernel is NOT rebuilt here: a fine ARRIVAL x SOJOURN table remains prach_run_trials_sojourn's job.
 // The scalars are reduced per wavefront.  Integers only: the result does not depend on any order.  Engine option "xtab_scheme".
 #include "prach_reduce_tile.h"
+#include "prach_xtab_menu.h"
 
 namespace prach {
 
@@ -32,29 +33,6 @@ constexpr int XT_COPY_WORDS = PRACH_XT_COPY_WORDS; // LDS words that the per-wav
 constexpr int XT_WAVES = TL_THREADS / 64;
 static_assert(4 * (TILE_SCHED_CAP + 2 * XT_SCALARS + XT_WINDOW_WORDS) <= 160 * 1024 && XT_COPY_WORDS <= XT_WINDOW_WORDS,
               "the largest layout (a table of XT_WINDOW_WORDS cells) fits the 160 KiB of LDS of a gfx950 CU");
-
-// the value of a field (include/prach.h); negative: UNDEFINED.  cls: 0 idle, 1 served, 2 unserved
-__device__ __forceinline__ long long xt_value(int field, const int4 &head, const int4 &tail, int nowBackoff, int ptc, int cls, int a, int E) {
-    long long v = -1;
-    switch (field) {
-    case PRACH_XTAB_ONE: v = 0; break;
-    case PRACH_XTAB_ARRIVAL: if (cls != 0) v = a; break;
-    case PRACH_XTAB_SOJOURN: if (cls == 1) v = (long long)head.w + 6 - a; break;
-    case PRACH_XTAB_COMPLETION: if (cls == 1) v = (long long)head.w + 6; break;
-    case PRACH_XTAB_TIMER: if (cls != 0) v = head.y; break;
-    case PRACH_XTAB_PTC: if (cls != 0) v = ptc; break;
-    case PRACH_XTAB_FAILCOUNT: if (cls != 0) v = tail.w; break;
-    case PRACH_XTAB_AGE: if (cls != 0) v = (long long)E - a; break;
-    default: // STATE
-        if (cls != 2) v = cls;
-        else if (head.z == 1) v = nowBackoff > 0 ? 2 : 3;
-        else if (head.z == 2) v = tail.y < 48 ? 4 : 5;
-        else v = 6;
-        break;
-    }
-    return v;
-}
-__host__ __device__ constexpr bool needs_arrival(int f) { return f == PRACH_XTAB_ARRIVAL || f == PRACH_XTAB_SOJOURN || f == PRACH_XTAB_AGE; }
 
 template <int SCHEME>
 __global__ __launch_bounds__(TL_THREADS) void xtab_kernel(const TimelineJob *__restrict__ jobs, int njobs, XtabAxes ax, int copies, XtabOut out) {

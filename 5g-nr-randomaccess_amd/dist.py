@@ -233,3 +233,18 @@ def gather_summary_rows(rows, index, dst: int = 0, device=None):
     allrec = np.concatenate([parts[r].cpu().numpy()[:counts[r]] for r in range(world)], axis=0)
     allrec = allrec[np.argsort(allrec[:, 0], kind="stable")]
     return np.ascontiguousarray(allrec[:, 1:]).view(rows.dtype).reshape(-1)
+
+
+def gather_pick_rows(headers, rows, index, dst: int = 0, device=None):
+    """This rank's picks (`headers` [m] and `rows` [m, k] of a package `Pick`, any order) with their trial indices `index`, gathered to `dst` as
+    (headers, rows) in TRIAL order (None elsewhere).  A trial travels as one fixed-size record — its header, padded to 64-bit words, and its k rows — through
+    gather_summary_rows: ONE all-gather of the records, the shard sizes and the record size (so also k) agreed in a first all-gather before the payload."""
+    headers, rows = np.ascontiguousarray(headers), np.ascontiguousarray(rows)
+    if rows.ndim != 2 or len(rows) != len(headers):
+        raise ValueError(f"{len(headers)} headers but rows of shape {rows.shape}")
+    pad = -headers.dtype.itemsize % 8
+    rec = np.dtype([("h", headers.dtype), ("pad", np.uint8, (pad,)), ("r", rows.dtype, (rows.shape[1],))])
+    both = np.zeros(len(headers), dtype=rec)
+    both["h"], both["r"] = headers, rows
+    got = gather_summary_rows(both, index, dst, device)
+    return None if got is None else (np.ascontiguousarray(got["h"]), np.ascontiguousarray(got["r"]))

@@ -56,6 +56,14 @@ def main(argv=None):
     ap.add_argument("--xtab-rows", default="arrival:500", help="FIELD[:WIDTH[:BINS]], FIELD one of one, arrival, sojourn, completion, timer, ptc, failcount, age, state")
     ap.add_argument("--xtab-cols", default="state:1:7", help="FIELD[:WIDTH[:BINS]]")
     ap.add_argument("--xtab-who", default="all", choices=("served", "unserved", "arrived", "all"), help="the UEs that enter the table")
+    ap.add_argument("--pick", default=None, help="write WHICH UEs stand behind a count: per trial, in trial order, a header line with the exact number of matches and "
+                    "the K UEs that pass every --pick-where clause — the first K by index, or those with the largest (--pick-top) / smallest (--pick-bottom) FIELD — "
+                    "to this CSV file (not together with --cdf, --timeline, --sojourn, --ci, --trace or --xtab)")
+    ap.add_argument("--pick-where", action="append", default=[], help="FIELD:LO:HI, LO <= FIELD <= HI; at most 4; FIELD as for --xtab-rows")
+    ap.add_argument("--pick-top", default=None, help="FIELD: the K UEs with the largest value")
+    ap.add_argument("--pick-bottom", default=None, help="FIELD: the K UEs with the smallest value")
+    ap.add_argument("--pick-k", type=int, default=16, help="UEs per trial, 1 to 4096")
+    ap.add_argument("--pick-who", default="all", choices=("served", "unserved", "arrived", "idle", "all"), help="the UEs that are selected")
     ap.add_argument("--same-device", action="store_true", help="rehearsal on one GPU: every rank uses cuda:0")
     args = ap.parse_args(argv)
     if args.cdf and args.timeline:
@@ -68,6 +76,10 @@ def main(argv=None):
         ap.error("--trace cannot be combined with --cdf, --timeline, --sojourn or --ci: one reduction per call")
     if args.xtab and (args.cdf or args.timeline or args.sojourn or args.ci or args.trace):
         ap.error("--xtab cannot be combined with --cdf, --timeline, --sojourn, --ci or --trace: one reduction per call")
+    if args.pick and (args.cdf or args.timeline or args.sojourn or args.ci or args.trace or args.xtab):
+        ap.error("--pick cannot be combined with --cdf, --timeline, --sojourn, --ci, --trace or --xtab: one reduction per call")
+    if args.pick_top and args.pick_bottom:
+        ap.error("--pick-top FIELD or --pick-bottom FIELD: one of them")
     ci_levels = [int(x) for x in args.ci_levels.split(",")]
     if not 1 <= len(ci_levels) <= 8 or any(m < 1 or m > 1000 for m in ci_levels):
         ap.error("--ci-levels takes 1 to 8 levels between 1 and 1000")
@@ -120,12 +132,24 @@ def main(argv=None):
         except ValueError as err:
             ap.error(str(err))
         red = (pkg.Xtab(len(points), *xa), eng.run_trials_xtab, xa, distmod.allreduce_xtab, pkg.xtab_csv, args.xtab)
-    ci_rows = []
+    pick = None
+    if args.pick:
+        try:
+            pick = dict(where=[pkg.pick_parse_clause(t) for t in args.pick_where], order="largest" if args.pick_top else "smallest" if args.pick_bottom else "index",
+                        key=args.pick_top or args.pick_bottom, k=args.pick_k, who=pkg.XTAB_WHO[args.pick_who])
+            if pick["key"] is not None and pick["key"].lower() not in pkg.XTAB_FIELD_NAMES:
+                raise ValueError(f"--pick-top / --pick-bottom FIELD, one of {', '.join(pkg.XTAB_FIELD_NAMES)}: {pick['key']!r}")
+        except ValueError as err:
+            ap.error(str(err))
+    ci_rows, pick_parts = [], []
     for a in range(0, len(mine), CH):
         part = mine[a:a + CH]
         if args.ci:  # one row per trial comes from the device with the results
             r, _, sm = eng.run_trials_summary([cfgs[i] for i in part], ci_levels)
             ci_rows.append(sm.rows)
+        elif pick:  # the headers and rows of the chunk's trials come from the device with the results
+            r, _, pk = eng.run_trials_pick([cfgs[i] for i in part], **pick)
+            pick_parts.append(pk)
         elif red is None:
             r, _ = eng.run_trials([cfgs[i] for i in part])
         else:  # the chunk's reduction comes from the device with the results: no per-UE log is copied
@@ -158,6 +182,16 @@ def main(argv=None):
             sm.rows[:] = every
             with open(args.ci, "wb") as f:
                 f.write(pkg.summary_csv(sm, groups=[i % len(points) for i in range(len(cfgs))], ngroups=len(points), labels=points))
+    if pick:  # the trials travel to rank 0 and are put in trial order there: the file does not depend on the number of ranks
+        import numpy as np
+        every = pkg.Pick(len(cfgs), **pick)
+        heads = np.concatenate([p.headers for p in pick_parts]) if pick_parts else every.headers[:0]
+        rows = np.concatenate([p.rows for p in pick_parts]) if pick_parts else every.rows[:0]
+        got = distmod.gather_pick_rows(heads, rows, mine, dst=0, device=dev if (world > 1 and args.backend == "nccl") else None)
+        if rank == 0:
+            every.headers[:], every.rows[:] = got
+            with open(args.pick, "wb") as f:
+                f.write(pkg.pick_csv(every, cfgs))
     if rank == 0:
         fi = {n: k for k, n in enumerate(distmod.AGG_FIELDS)}
         summary = {"program": args.program, "times": args.times, "points": points, "world": world,

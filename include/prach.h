@@ -129,6 +129,8 @@ typedef struct prach_timing {
     int32_t trial_kernel_reruns; /* of fallback_trials: trials that were (also) rerun on the one-workgroup, index-ordered trial_kernel */
     int32_t noma_host_ues;       /* NOMA_C, Philox: UEs of the device-built activeUE table that the host recomputed with its libm (a value inside the
                                     device math library's error band of a rounding / comparison boundary: ~1e-6 of the UEs) */
+    double pick_ms;              /* HIP-event time of the pick kernel launches (prach_run_trials_pick) of the last call; 0 in every other call (a pick call
+                                    leaves every other *_ms of a reduction 0) */
     double xtab_ms;              /* HIP-event time of the cross-tabulation kernel launches (prach_run_trials_xtab) of the last call; 0 in every other call (an
                                     xtab call leaves every other *_ms of a reduction 0) */
     double trace_ms;             /* HIP-event time of the trace kernel launches (prach_run_trials_trace) of the last call; 0 in every other call (a trace call leaves
@@ -372,6 +374,60 @@ typedef struct prach_stat { uint64_t n; double mean, sd, sem, min, max; } prach_
 int prach_run_trials_summary(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs,
                              const prach_summary_spec *spec, prach_trial_summary *rows);
 
+/* Pick per trial, selected on the device: WHICH UEs stand behind a count — per TRIAL the k UEs that match a predicate over the menu of the cross-tabulation
+ * above, as records, and the exact number of matches.  The other reductions answer "how many" and "how long"; the only other route to the individuals is
+ * every per-UE log over the bus and a filter on the host.  `who` is the PRACH_XTAB_* class bits (the same three classes); the value of a field, a(i), c(i)
+ * and E = min(steps, maxTime) are exactly those of the xtab block, with its ONE RULE: a negative value is UNDEFINED.
+ *   selected   the UEs whose class is in `who`
+ *   a clause {field, lo, hi} HOLDS for a UE when the field's value v is defined and lo <= v <= hi (inclusive; lo >= 0), and FAILS when v is defined and
+ *              outside; the values a UE NEEDS are those of its clauses and, under LARGEST / SMALLEST, that of key_field
+ *   matched    the selected UEs all of whose needed values are defined and all of whose clauses hold; exact, whatever k is
+ *   undefined  the selected UEs of which no clause fails and at least one needed value is undefined (they fail to match only for that)
+ * ORDER: which of the matches are returned, and in which order:
+ *   PRACH_PICK_BY_INDEX   the first k matches in UE-index order; key_field must be PRACH_XTAB_ONE (0), every row's `key` is 0, threshold -1, ties_left_out 0
+ *   PRACH_PICK_LARGEST    the k matches that come first when sorted by descending key (the value of key_field), equal keys in ascending UE index, in that
+ *                         order; threshold is the key of the last stored row (-1: none), ties_left_out the matches with key == threshold that are not stored
+ *   PRACH_PICK_SMALLEST   the mirror image: ascending key, equal keys in ascending UE index
+ * stored = min(matched, k); the rows behind `stored` are zero.  A row is the UE's 64-byte log record, its arrival a(i) (-1 for an idle UE) and its key.
+ * Keys are RANKED in the range 0 .. prach_summary_max_value() (65 535), like the summary's order statistics; a match with a key outside it is counted in
+ * range_errors.  No trial produces one: SOJOURN, TIMER and PTC are bounded as csrc/prach_summary.hip states, ARRIVAL, COMPLETION and AGE by the 60 000 + 6
+ * subframes of the longest trial, FAILCOUNT by one cycle per subframe, STATE by 6.  When range_errors is non-zero the trial's rows are void (zero, stored 0,
+ * threshold -1) and the call returns PRACH_ERR_INTERNAL, as for the summary.
+ * The output is defined per trial: it does not depend on how a call is split into launches, on reruns, or on how trials are dealt to devices and ranks.
+ * Beta.c and RandomAccessWithNOMA.c only, like the timeline. */
+#define PRACH_PICK_MAX_K        4096
+#define PRACH_PICK_MAX_CLAUSES  4
+enum { PRACH_PICK_BY_INDEX = 0, PRACH_PICK_LARGEST = 1, PRACH_PICK_SMALLEST = 2 };
+typedef struct prach_pick_clause { int32_t field, lo, hi; } prach_pick_clause; /* a PRACH_XTAB_* field id, 0 <= lo <= hi */
+typedef struct prach_pick_spec {
+    int32_t who;                                        /* PRACH_XTAB_* class bits, not 0 */
+    int32_t nclauses;                                   /* 0 .. PRACH_PICK_MAX_CLAUSES; the clauses behind it must be zero */
+    prach_pick_clause clause[PRACH_PICK_MAX_CLAUSES];
+    int32_t order, key_field;                           /* PRACH_PICK_*; a PRACH_XTAB_* field id (BY_INDEX: 0) */
+    int32_t k;                                          /* 1 .. PRACH_PICK_MAX_K rows per trial */
+    int32_t reserved;                                   /* 0 */
+} prach_pick_spec;
+typedef struct prach_pick_row { /* 80 bytes, 8-byte aligned */
+    __attribute__((aligned(8))) prach_ue_log log;
+    int32_t arrival;            /* a(i); -1 for an idle UE */
+    int32_t key;                /* the value of key_field (BY_INDEX: 0) */
+    int32_t pad[2];             /* 0 */
+} prach_pick_row;
+typedef struct prach_pick {     /* one per TRIAL */
+    int32_t status, nUE, selected, matched, stored, undefined, range_errors, threshold, ties_left_out;
+} prach_pick;
+
+/* prach_run_trials plus the pick: picks[n] and rows[n * spec->k] (trial t's rows at rows + t * k) are caller-owned and OVERWRITTEN.  picks[t] carries the final
+ * status of trial t and cfgs[t].nUE; unless that status is PRACH_OK everything else in it is 0 (threshold -1) and its rows are zero.  A trial the engine reruns
+ * is written once, by the launch whose result is kept.  prach::pick_kernel (csrc/prach_pick.hip) selects from the per-UE log records the simulation kernels
+ * write ON THE DEVICE, one workgroup per trial, and leaves a trial's rows in UE-index order; the engine sorts the at most k rows of a trial into the defined
+ * order on the host.
+ * PRACH_ERR_ARG: a NULL output or spec, an unknown field, class bit or order, an empty `who`, k or nclauses out of range, lo < 0 or lo > hi, a non-zero unused
+ * clause, a key field other than 0 with BY_INDEX, a non-zero reserved word; PRACH_ERR_UNSUPPORTED: any NOMA_C cfg (before anything is launched);
+ * n * k * 10 + n * 8 > 2^27 words (1 GiB of device buffer). */
+int prach_run_trials_pick(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_pick_spec *spec,
+                          prach_pick *picks, prach_pick_row *rows);
+
 /* Per-subframe preamble trace per trial group, recorded by the simulation kernels WHILE THEY RUN and reduced on the device: how many preambles were used,
  * decoded and collided in each stretch of the simulation — the quantities TR 37.868's collision probability is defined on.  Unlike the four reductions above
  * this is not a function of the per-UE state a trial leaves behind (prach_result has only the two whole-trial totals collisionPreambles and
@@ -441,6 +497,7 @@ int prach_run_trials_trace(prach_engine *, const prach_cfg *cfgs, int n, prach_r
  *   "trace_scheme"  prach::trace_kernel's binning: 0 every contribution is a 64-bit agent-scope global atomic, 1 a tile's bins added up in an LDS window first
  *                   (the default)
  *   "summary_threads" prach::summary_kernel's workgroup: 512 or 1024 threads (0 = the default, 1024)
+ *   "pick_threads"  prach::pick_kernel's workgroup: 512 or 1024 threads (0 = the default, 1024)
  *   "calendar_cap", "vmm_fail_after", "noma_ambiguity_test", "noma_host_activation"   test hooks (prach_engine.hip) */
 int prach_engine_set(prach_engine *, const char *key, int64_t value);
 
@@ -573,6 +630,18 @@ int prach_summary_stats(const prach_summary_spec *, const prach_trial_summary *r
  * length needed (without the terminating 0); the text is written only if it fits cap with its terminator. */
 size_t prach_summary_format_csv(const prach_summary_spec *, const prach_stat *stats_of_one_group, const char *label, char *buf, size_t cap);
 int prach_summary_max_value(void);    /* 65 535: the largest value prach::summary_kernel ranks */
+
+/* Picks, host side (no device needed).
+ * prach_pick_from_logs OVERWRITES *hdr and rows[spec->k] with the pick of one trial's per-UE log: THE DEFINITION prach::pick_kernel and the engine's sort
+ * equal, integer for integer, by filtering and sorting (it sorts, so any key is handled and range_errors is 0; status PRACH_OK).  steps is the trial's
+ * prach_result.steps.  PRACH_ERR_UNSUPPORTED: a NOMA_C cfg.  PRACH_ERR_ARG: a bad spec or cfg, nUE != cfg->nUE (no log content is refused: a bad value is
+ * UNDEFINED). */
+int prach_pick_from_logs(const prach_pick_spec *, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_pick *hdr, prach_pick_row *rows);
+/* one trial as text: the header line `label,<trial>,<seed>,<nUE>,header,<status>,<selected>,<matched>,<stored>,<undefined>,<threshold>,<ties_left_out>`, then
+ * one line per stored row, `label,<trial>,<seed>,<nUE>,<rank from 0>,<key>,<arrival>,` and the 16 logged fields in the order of prach_ue_log; lines end in \n.
+ * Returns the length needed (without the terminating 0); the text is written only if it fits cap with its terminator. */
+size_t prach_pick_format_csv(const prach_pick_spec *, const prach_pick *hdr, const prach_pick_row *rows, const char *label, int trial, uint64_t seed, char *buf,
+                             size_t cap);
 
 /* Traces, host side (no device needed).  t and the four series (calls, singles, txop, collisions): ONE group (`bins` entries each).  There is no
  * prach_trace_accumulate_logs: a per-UE log does not hold what happened per subframe (the block above).

@@ -1,0 +1,50 @@
+"""prach::pick_kernel on per-UE state no simulation leaves behind: tests/tools/gpu_pick_harness.hip launches the kernel directly on the cases of
+tests/tools/pick_cases.py — both workgroup shapes, one launch per child process, one child at a time — and every scalar and every row, the untouched rows
+behind `stored` included, equals the numpy restatement integer for integer, the host definition (prach_pick_from_logs) where it applies, and the other
+shape.  tests/test_pick_cases_cpu.py holds the references against the host definition without a GPU."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+from conftest import ROOT
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import pick_cases as PC  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+_abnormal = []  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    return PC.build_harness(tmp_path_factory.mktemp("pick_harness"))
+
+
+@pytest.fixture(scope="module")
+def cases(pkg):
+    return {c.name: c for c in PC.cases(pkg)}
+
+
+@pytest.mark.parametrize("name", PC.CASE_NAMES)
+def test_kernel_equals_reference_under_both_shapes(pkg, harness, cases, tmp_path, name):
+    case = cases[name]
+    ref = case.reference()
+    host = case.host_definition(pkg) if case.host else None
+    path = str(tmp_path / "case.bin")
+    PC.write_case(case, path)
+    outs = []
+    for threads in PC.THREADS:
+        assert not _abnormal, f"not started: {_abnormal[0]}"
+        try:
+            out = PC.run_harness(harness, case, path, threads, tmp_path)
+        except (RuntimeError, subprocess.TimeoutExpired) as e:
+            _abnormal.append(f"{name} threads {threads}: {e}")
+            raise
+        outs.append(out)
+        assert PC.same(out, ref) is None, f"{threads} threads against numpy: {PC.same(out, ref)}"
+        if host is not None:
+            assert PC.same(out, host) is None, f"{threads} threads against the host definition: {PC.same(out, host)}"
+    assert PC.same(outs[1], outs[0]) is None
