@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PRACH_LIB") or os.path.join(HERE, "libprach_hip.so")  # PRACH_LIB: diagnostic builds only
@@ -54,7 +55,7 @@ class PrachTiming(C.Structure):
                 ("launches", C.c_int32), ("workgroups", C.c_int32), ("updates", C.c_uint64),
                 ("cluster_size", C.c_int32), ("resident_limit", C.c_int32), ("fallback_trials", C.c_int32), ("spin_timeouts", C.c_int32),
                 ("rec_mode", C.c_int32), ("xcd_packed", C.c_int32), ("group_visits", C.c_uint64), ("event_ues", C.c_uint64),
-                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("pick_ms", C.c_double), ("xtab_ms", C.c_double), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
+                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("columns_ms", C.c_double), ("pick_ms", C.c_double), ("xtab_ms", C.c_double), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
                 ("sojourn_ms", C.c_double)]
 
 
@@ -513,6 +514,67 @@ class Pick:
             all(np.array_equal(self.headers[f], other.headers[f]) for f in PICK_FIELDS) and all(np.array_equal(self.rows[f], other.rows[f]) for f in self.rows.dtype.names)
 
 
+COL_MAX, COL_RAW, COL_MAX_WORDS = 16, 16, 1 << 31
+COLUMNS_FIELDS = ("status", "nUE", "offset", "idle", "served", "unserved", "reserved")
+
+
+class PrachColumnsSpec(C.Structure):
+    _fields_ = [("ncols", C.c_int32), ("field", C.c_int32 * COL_MAX), ("reserved", C.c_int32 * 3)]
+
+
+class PrachColumns(C.Structure):
+    _fields_ = [("status", C.c_int32), ("nUE", C.c_int32), ("offset", C.c_uint64)] + [(n, C.c_int32) for n in ("idle", "served", "unserved", "reserved")]
+
+
+def columns_header_dtype():
+    import numpy as np
+    dt = np.dtype([("status", np.int32), ("nUE", np.int32), ("offset", np.uint64)] + [(n, np.int32) for n in ("idle", "served", "unserved", "reserved")])
+    assert dt.itemsize == C.sizeof(PrachColumns) == 32
+    return dt
+
+
+def columns_field(f):
+    """A column's field id: a name of XTAB_FIELD_NAMES, ``raw:NAME`` with a field name of PrachUeLog (COL_RAW + its word), or the id itself."""
+    if isinstance(f, str) and f.lower().startswith("raw:"):
+        return COL_RAW + UE_FIELDS.index(f[4:])
+    return _xtab_field(f)
+
+
+def columns_field_name(f):
+    return XTAB_FIELD_NAMES[f] if 0 <= f < len(XTAB_FIELD_NAMES) else "raw:" + UE_FIELDS[f - COL_RAW] if COL_RAW <= f < COL_RAW + 16 else str(f)
+
+
+def columns_spec(fields):
+    sp = PrachColumnsSpec()
+    ids = [columns_field(f) for f in fields]
+    sp.ncols = len(ids)  # (a count the library refuses stays visible to it)
+    for c, f in enumerate(ids[:COL_MAX]):
+        sp.field[c] = f
+    return sp, ids
+
+
+class Columns:
+    """The per-UE columns of ``n`` trials (include/prach.h, prach_columns): ``data`` is [ncols, rows] int32 — a numpy array, or a torch CUDA tensor when the
+    call was made with device=True — with trial k in the rows offsets[k] .. offsets[k] + nUE_k of every column; ``fields`` the columns' names (a name of
+    XTAB_FIELD_NAMES or raw:NAME), ``headers`` a numpy structured array (columns_header_dtype) in trial order.  A menu field holds -1 where it is undefined,
+    and every word of a trial that did not end PRACH_OK is -1."""
+
+    def __init__(self, fields, headers, data):
+        self.field_ids = tuple(columns_field(f) for f in fields)
+        self.fields = tuple(columns_field_name(f) for f in self.field_ids)
+        self.headers, self.data = headers, data
+        self.offsets = headers["offset"].astype("int64")
+
+    def trial(self, k):
+        """[ncols, nUE_k]: the columns of trial k, a view."""
+        o = int(self.offsets[k])
+        return self.data[:, o:o + int(self.headers["nUE"][k])]
+
+    def column(self, name):
+        """[rows]: the (first) column of that field, a view."""
+        return self.data[self.field_ids.index(columns_field(name))]
+
+
 class PrachError(RuntimeError):
     def __init__(self, status, what=""):
         self.status = status
@@ -524,6 +586,17 @@ class PrachError(RuntimeError):
 
 
 _lib = None
+_lib_before_torch = None  # whether libprach_hip.so was loaded before torch was imported (lib())
+
+
+def hip_runtimes():
+    """The files named libamdhip64.so* that are mapped into this process: more than one means two HIP runtimes, and a device pointer of one means nothing to
+    the other."""
+    try:
+        with open("/proc/self/maps") as f:
+            return sorted({os.path.realpath(ln.split()[-1]) for ln in f if "libamdhip64.so" in ln})
+    except OSError:
+        return []
 
 
 def lib():
@@ -533,6 +606,8 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise FileNotFoundError(f"{LIB_PATH} is missing: run __graft_entry__.build() "
                                     f"(make -C 5g-nr-randomaccess_amd/csrc); there is no CPU fallback")
+        global _lib_before_torch
+        _lib_before_torch = "torch" not in sys.modules
         L = C.CDLL(LIB_PATH)
         vp = C.c_void_p
         L.prach_engine_create.argtypes = [C.c_int, C.POINTER(vp)]
@@ -598,6 +673,11 @@ def lib():
         L.prach_pick_from_logs.argtypes = [C.POINTER(PrachPickSpec), C.POINTER(PrachCfg), C.c_uint64, C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachPick), C.POINTER(PrachPickRow)]
         L.prach_pick_format_csv.argtypes = [C.POINTER(PrachPickSpec), C.POINTER(PrachPick), C.POINTER(PrachPickRow), C.c_char_p, C.c_int, C.c_uint64, C.c_char_p, C.c_size_t]
         L.prach_pick_format_csv.restype = C.c_size_t
+        L.prach_run_trials_columns.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachColumnsSpec),
+                                               C.POINTER(PrachColumns), C.c_void_p, C.c_uint64]
+        L.prach_run_trials_columns_device.argtypes = L.prach_run_trials_columns.argtypes
+        L.prach_columns_from_logs.argtypes = [C.POINTER(PrachColumnsSpec), C.POINTER(PrachCfg), C.c_uint64, C.POINTER(PrachUeLog), C.c_int, C.c_void_p, C.c_uint64]
+        L.prach_columns_tile_ues.argtypes = []
         L.prach_run_trials_trace.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachTraceSpec),
                                              C.POINTER(C.c_int32), C.POINTER(PrachTrace), u64p, u64p, u64p, u64p]
         L.prach_trace_merge.argtypes = [C.POINTER(PrachTraceSpec), C.POINTER(PrachTrace), u64pp, C.POINTER(PrachTrace), u64pp]
@@ -649,7 +729,8 @@ EXPORTS = ("prach_engine_create", "prach_engine_destroy", "prach_engine_set", "p
            "prach_run_trials_summary", "prach_summary_from_logs", "prach_summary_stats", "prach_summary_format_csv", "prach_summary_max_value",
            "prach_run_trials_trace", "prach_trace_merge", "prach_trace_format_csv", "prach_trace_tile_subframes", "prach_run_trials_xtab", "prach_xtab_accumulate_logs",
            "prach_xtab_merge", "prach_xtab_quantile", "prach_xtab_format_csv", "prach_xtab_tile_ues", "prach_xtab_window_words", "prach_run_trials_pick",
-           "prach_pick_from_logs", "prach_pick_format_csv")
+           "prach_pick_from_logs", "prach_pick_format_csv", "prach_run_trials_columns", "prach_run_trials_columns_device", "prach_columns_from_logs",
+           "prach_columns_tile_ues")
 
 
 def make_cfg(nUE, variant=VARIANT_BETA_C, uniform=0, rng_mode=RNG_GLIBC, seed=0, stream_offset=0, **kw) -> PrachCfg:
@@ -669,6 +750,7 @@ class Engine:
 
     def __init__(self, device: int = 0):
         self._h = C.c_void_p()
+        self.device = int(device)
         rc = lib().prach_engine_create(device, C.byref(self._h))
         if rc != OK:
             raise PrachError(rc, "(prach_engine_create)")
@@ -760,6 +842,34 @@ class Engine:
         sp = pk.spec()
         res, logs = self._call("prach_run_trials_pick", cfgs, want_logs, C.byref(sp), pk._headers_ptr(), pk._rows_ptr())
         return res, logs, pk
+
+    def run_trials_columns(self, cfgs, fields, device=False, want_logs=False):
+        """run_trials plus the per-UE columns: for every UE of every trial the asked-for ``fields`` — names of XTAB_FIELD_NAMES, the menu of the
+        cross-tabulation, -1 where undefined, or ``raw:NAME`` for a word of the log record as it is — as int32 columns computed on the device
+        (prach_run_trials_columns; Beta.c and RandomAccessWithNOMA trials only).  device=False: Columns.data is a numpy array, 4 bytes per UE and field over
+        the bus.  device=True: it is a torch tensor on this engine's GPU that the kernel wrote straight into (prach_run_trials_columns_device), and nothing
+        but the headers crosses the bus; torch must have been imported BEFORE this package loaded its library, so that both use one HIP runtime.
+        Returns (results, logs, Columns)."""
+        import numpy as np
+        sp, ids = columns_spec(fields)
+        rows = sum(int(c.nUE) for c in cfgs)
+        hdr = np.zeros(len(cfgs), dtype=columns_header_dtype())
+        hp = hdr.ctypes.data_as(C.POINTER(PrachColumns))
+        if not device:
+            data = np.empty((max(len(ids), 1), rows), dtype=np.int32)
+            res, logs = self._call("prach_run_trials_columns", cfgs, want_logs, C.byref(sp), hp, data.ctypes.data, rows)
+            return res, logs, Columns(ids, hdr, data[:len(ids)])
+        lib()
+        if _lib_before_torch:
+            raise PrachError(-1, "(run_trials_columns device=True: libprach_hip.so was loaded before torch was imported, so torch brought a HIP runtime of its "
+                                 "own and its device pointers mean nothing to the library's: import torch first, then make the first call into this package)")
+        import torch
+        if len(hip_runtimes()) > 1:
+            raise PrachError(-1, f"(run_trials_columns device=True: two HIP runtimes are loaded, {', '.join(hip_runtimes())}: torch and libprach_hip.so must share one)")
+        data = torch.empty((max(len(ids), 1), rows), dtype=torch.int32, device=torch.device("cuda", self.device))
+        torch.cuda.synchronize(self.device)  # (the engine's stream is not torch's)
+        res, logs = self._call("prach_run_trials_columns_device", cfgs, want_logs, C.byref(sp), hp, data.data_ptr(), rows)
+        return res, logs, Columns(ids, hdr, data[:len(ids)])
 
     def run_trials_trace(self, cfgs, bins, bin_ms=1, groups=None, want_logs=False, ngroups=None):
         """run_trials plus the per-subframe preamble trace per trial group — preambles used (calls), decoded (singles) and what the subframes added to
@@ -1079,3 +1189,30 @@ def xtab_from_logs(cfgs, steps, logs, rows=("arrival", 500, 20), cols=("state", 
 def xtab_csv(xt: Xtab, labels=None) -> bytes:
     """The CSV text of every group (prach_xtab_format_csv), labelled labels[g] (default: the group number)."""
     return _csv("prach_xtab_format_csv", xt, labels)
+
+
+def columns_tile_ues() -> int:
+    return lib().prach_columns_tile_ues()
+
+
+def columns_from_logs(cfgs, steps, logs, fields) -> Columns:
+    """The host-side definition of the columns (prach_columns_from_logs): trial k from logs[k], the per-UE log of the trial with config cfgs[k] that ran
+    steps[k] subframes (prach_result.steps) — a ctypes array of PrachUeLog, as Engine.run_trials returns it, or an int32 array of shape [nUE, 16].  The class
+    counts of the headers are those of the definition's own STATE column."""
+    import numpy as np
+    sp, ids = columns_spec(fields)
+    state, _ = columns_spec(["state"])
+    hdr = np.zeros(len(logs), dtype=columns_header_dtype())
+    ptrs = [_log_ptr(lg) for lg in logs]
+    hdr["nUE"] = [nue for _, nue, _ in ptrs]
+    hdr["offset"] = np.concatenate([[0], np.cumsum(hdr["nUE"], dtype=np.uint64)[:-1]]) if len(logs) else []
+    rows = int(hdr["nUE"].sum())
+    data = np.empty((max(len(ids), 1), rows), dtype=np.int32)
+    for k, (ptr, nue, _keep) in enumerate(ptrs):
+        st = np.empty(nue, dtype=np.int32)
+        for spec, out, stride in ((sp, data.ctypes.data + 4 * int(hdr["offset"][k]), rows), (state, st.ctypes.data, nue)):
+            rc = lib().prach_columns_from_logs(C.byref(spec), C.byref(cfgs[k]), int(steps[k]), ptr, nue, out, stride)
+            if rc != OK:
+                raise PrachError(rc, "(prach_columns_from_logs)")
+        hdr["idle"][k], hdr["served"][k], hdr["unserved"][k] = (st == 0).sum(), (st == 1).sum(), (st >= 2).sum()
+    return Columns(ids, hdr, data[:len(ids)])

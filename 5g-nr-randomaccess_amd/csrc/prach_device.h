@@ -252,6 +252,15 @@ int pick_sched_cap();
 hipError_t launch_pick_kernel(const TimelineJob *jobs, int njobs, prach_pick_spec spec, int threads, int sched_cap, unsigned long long *rows, unsigned long long *scalars,
                               hipStream_t stream);
 
+// prach_columns.hip: the per-UE columns of a launch's accepted trials (prach_run_trials_columns, prach_run_trials_columns_device).  The jobs are the timeline's
+// with E = min(steps, maxTime) in `pad` (group = the trial), and so are tile and workgroup.  Column c of UE i of trial k is the 32-bit word
+// data[c * stride + offset[k] + i]: `data` is the call's own buffer or device memory of the caller's, `offset` the call's table of first rows, one per trial.
+// Plain 4-byte stores; what no job names is not written.  Per trial CL_SCALARS 64-bit scalars, added with agent-scope atomics: idle, served, unserved | 1 spare.
+constexpr int CL_SCALARS = 4, CL_SUMS = 3;
+struct ColumnsOut { int *data; unsigned long long stride; const unsigned long long *offset; unsigned long long *scalars; }; // stride in words; [ntrials], [ntrials][CL_SCALARS]
+extern "C" int prach_internal_columns_spec_ok(const prach_columns_spec *spec); // prach_host.c
+hipError_t launch_columns_kernel(const TimelineJob *jobs, int njobs, int workgroups, const prach_columns_spec &spec, ColumnsOut out, hipStream_t stream); // spec: a valid one
+
 // prach_trace.hip: the per-subframe preamble trace of a launch's accepted trials (prach_run_trials_trace).  One job per trial: the rows the simulation kernel
 // wrote through TrialDev::trace, for the subframes [0, steps).  A workgroup reduces one tile of TR_TILE consecutive subframes of one trial, 16 bytes per lane
 // and load.  A tile covers at most TR_TILE consecutive bins (bin = t / bin_ms): scheme 1 adds them up in an LDS window of 64-bit counters anchored at the

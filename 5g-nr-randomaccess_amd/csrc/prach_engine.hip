@@ -50,6 +50,13 @@ struct prach_engine {
     char *red_jobs_h = nullptr, *red_jobs_d = nullptr;
     size_t red_jobs_cap = 0;
     hipEvent_t red_ev0 = nullptr, red_ev1 = nullptr;
+    // ... and, where the kind has them (Reduction): the bulk part the kernel writes with plain stores — the engine's own buffer (bulk_buf, grown at the start
+    // of a call) or device memory of the caller's — with the bytes from one of its rows to the next, and the call's table behind the counters in red_buf
+    char *bulk_buf = nullptr;
+    size_t bulk_cap = 0;
+    char *red_bulk = nullptr;
+    size_t red_bulk_pitch = 0;
+    const char *red_table = nullptr;
     int64_t opt_trace_scheme = 1;    // trace_kernel's binning (prach_trace.hip): 0 global atomics only, 1 the tile's bins added up in an LDS window first
     int64_t opt_summary_threads = 1024; // summary_kernel's workgroup (prach_summary.hip): 512 or 1024 threads, one workgroup per trial
     int64_t opt_pick_threads = 1024;    // pick_kernel's workgroup (prach_pick.hip): 512 or 1024 threads, one workgroup per trial
@@ -420,13 +427,13 @@ static int noma_device_activation(prach_engine *e, const TrialDev *dparams, cons
     return PRACH_OK;
 }
 
-// What a call reduces on the device next to its results (prach_run_trials_dist, _timeline, _sojourn, _summary, _trace, _xtab, _pick).  The call's device buffer is a
+// What a call reduces on the device next to its results (prach_run_trials_dist, _timeline, _sojourn, _summary, _trace, _xtab, _pick, _columns).  The call's device buffer is a
 // row of parts, [ngroups][words] 64-bit counters each: the arrays the caller gets as they are, one per part, then the scalars the kernel keeps per group,
 // which the engine unpacks into the caller's per-group structs.  Every launch of the call gets one job per trial it finished, and the kind's kernel behind
 // the simulation kernel.  What differs between the kinds is stated ONCE per kind: a block of functions behind CallCtx and its row of RED_KINDS.  The generic
 // code (reduction_begin, run_group, reduction_end, run_trials_impl) walks that row and never asks which kind it has; a new kind is an enumerator, a block and
 // a row.
-enum class Red { dist, timeline, sojourn, summary, trace, xtab, pick };
+enum class Red { dist, timeline, sojourn, summary, trace, xtab, pick, columns };
 constexpr int RED_MAX_PARTS = 6;
 struct Reduction {
     Red kind;
@@ -435,6 +442,16 @@ struct Reduction {
     uint64_t *out[RED_MAX_PARTS - 1]; // the caller's arrays, one per part in front of the scalars
     const void *spec;                 // the caller's prach_*_spec, and its per-group structs (summary: its per-trial rows): the kind's block reads both
     void *groups;                     // through its own casts
+    // A BULK PART (bulk_width == 0: none): bulk_rows rows of bulk_width bytes that the kind's kernel writes with plain stores, every byte of them set to
+    // bulk_fill once in front of the first launch; what lies between two rows is never touched.  Either the engine owns the device copy (rows without gaps)
+    // and copies it out once at the end of the call, to bulk_host, rows bulk_pitch bytes apart — or the part is CALLER-OWNED DEVICE MEMORY, bulk_dev, rows
+    // bulk_pitch bytes apart, and the kernel writes straight into it.
+    void *bulk_host = nullptr, *bulk_dev = nullptr;
+    size_t bulk_width = 0, bulk_rows = 0, bulk_pitch = 0;
+    int bulk_fill = 0;
+    // A TABLE of the call that the kernel reads (table_bytes == 0: none): uploaded once, behind the counters
+    const void *table = nullptr;
+    size_t table_bytes = 0;
 };
 struct CallCtx;
 struct JobSrc { const prach_cfg &c; const TrialLayout &L; const DevResult &dr; char *A; int group, wg0; bool batch; }; // a finished trial of a launch, as a job is filled from it (A: the arena)
@@ -654,6 +671,29 @@ int pick_unpack(const Reduction &r, CallCtx &cx, size_t t, const unsigned long l
     return PRACH_OK;
 }
 
+// columns: every trial is its own group, as in the summary; the columns are the call's bulk part, ncols rows of (sum of nUE) words, and the table is the first
+// row of every trial; the only counters are the scalars: the three class counts of a trial
+int columns_parts(const Reduction &, size_t w[]) { w[0] = CL_SCALARS; return 1; }
+hipError_t columns_launch(const prach_engine *e, const Reduction &r, int njobs, int wgs, unsigned long long *const *d) {
+    return launch_columns_kernel(timeline_jobs(e), njobs, wgs, spec_of<prach_columns_spec>(r),
+                                 ColumnsOut{reinterpret_cast<int *>(e->red_bulk), e->red_bulk_pitch / 4, reinterpret_cast<const unsigned long long *>(e->red_table), d[0]}, e->stream);
+}
+void columns_empty(const Reduction &r, size_t k, const prach_cfg *cfgs) {
+    prach_columns &h = group_of<prach_columns>(r, k);
+    h = prach_columns{};
+    h.status = PRACH_ERR_INTERNAL;
+    h.nUE = cfgs[k].nUE;
+    h.offset = static_cast<const uint64_t *>(r.table)[k];
+}
+int columns_unpack(const Reduction &r, CallCtx &cx, size_t k, const unsigned long long *q) { // status and nUE from the host, the counts from the one launch that accepted the trial
+    prach_columns &h = group_of<prach_columns>(r, k);
+    h.status = cx.results[k].status; // (everything else is still the empty header, and no launch wrote a word of a trial it did not accept)
+    if (h.status != PRACH_OK) return PRACH_OK;
+    if (cx.trials[k] != 1 || q[0] + q[1] + q[2] != (unsigned long long)h.nUE) return h.status = PRACH_ERR_INTERNAL; // (no launch wrote this trial, or two did)
+    h.idle = (int32_t)q[0]; h.served = (int32_t)q[1]; h.unserved = (int32_t)q[2];
+    return PRACH_OK;
+}
+
 // in the order of enum class Red:           parts, job bytes, tile, job, device logs, trace rows, "fast" off, launch, empty, unpack, prach_timing field
 const RedKind RED_KINDS[] = {
     {dist_parts, sizeof(DistJob), DIST_TILE, dist_fill_job, false, false, false, dist_launch, empty_group<prach_dist, &prach_dist::delay_max>, dist_unpack, &prach_timing::dist_ms},
@@ -663,8 +703,9 @@ const RedKind RED_KINDS[] = {
     {trace_parts, sizeof(TraceJob), TR_TILE, trace_fill_job, false, true, true, trace_launch, empty_group<prach_trace, &prach_trace::calls_max>, trace_unpack, &prach_timing::trace_ms},
     {xtab_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, xtab_launch, empty_group<prach_xtab, &prach_xtab::row_max, &prach_xtab::col_max>, xtab_unpack, &prach_timing::xtab_ms},
     {pick_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, pick_launch, pick_empty, pick_unpack, &prach_timing::pick_ms},
+    {columns_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, columns_launch, columns_empty, columns_unpack, &prach_timing::columns_ms},
 };
-static_assert(sizeof(RED_KINDS) / sizeof(RED_KINDS[0]) == (size_t)Red::pick + 1, "one row per kind");
+static_assert(sizeof(RED_KINDS) / sizeof(RED_KINDS[0]) == (size_t)Red::columns + 1, "one row per kind");
 const RedKind &kind_of(const Reduction &r) { return RED_KINDS[(int)r.kind]; }
 
 // How a rerun's launch differs from the first one
@@ -1156,6 +1197,8 @@ static int reduction_begin(prach_engine *e, CallCtx &cx, int n) {
     size_t words[RED_MAX_PARTS], at[RED_MAX_PARTS], need = 0;
     const int np = K.parts(R, words);
     for (int q = 0; q < np; q++) { at[q] = align_up(need, 256); need = at[q] + 8 * ng * words[q]; }
+    const size_t at_table = align_up(need, 256);
+    if (R.table_bytes) need = at_table + R.table_bytes;
     if (need > e->red_cap) {
         if (e->red_buf) HIPCHK(hipFree(e->red_buf));
         e->red_buf = nullptr; e->red_cap = 0;
@@ -1177,6 +1220,22 @@ static int reduction_begin(prach_engine *e, CallCtx &cx, int n) {
     cx.trials.assign(ng, 0);
     cx.ues.assign(ng, 0);
     HIPCHK(hipMemsetAsync(e->red_buf, 0, need, e->stream));
+    e->red_table = R.table_bytes ? e->red_buf + at_table : nullptr;
+    if (R.table_bytes) HIPCHK(hipMemcpyAsync(e->red_buf + at_table, R.table, R.table_bytes, hipMemcpyHostToDevice, e->stream));
+    e->red_bulk = nullptr; e->red_bulk_pitch = 0;
+    if (R.bulk_width) { // the bulk part: the engine's own buffer, rows without gaps, or the caller's device memory; ONE fill on the engine's stream
+        const size_t bytes = R.bulk_width * R.bulk_rows;
+        if (!R.bulk_dev && bytes > e->bulk_cap) {
+            if (e->bulk_buf) HIPCHK(hipFree(e->bulk_buf));
+            e->bulk_buf = nullptr; e->bulk_cap = 0;
+            HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->bulk_buf), bytes));
+            e->bulk_cap = bytes;
+        }
+        e->red_bulk = R.bulk_dev ? static_cast<char *>(R.bulk_dev) : e->bulk_buf;
+        e->red_bulk_pitch = R.bulk_dev ? R.bulk_pitch : R.bulk_width;
+        if (e->red_bulk_pitch == R.bulk_width || R.bulk_rows == 1) HIPCHK(hipMemsetAsync(e->red_bulk, R.bulk_fill, bytes, e->stream));
+        else HIPCHK(hipMemset2DAsync(e->red_bulk, e->red_bulk_pitch, R.bulk_fill, R.bulk_width, R.bulk_rows, e->stream));
+    }
     return PRACH_OK;
 }
 // ONE copy-out per part at the end of the call (every reduction kernel has completed: run_group waits for its own); the scalars are unpacked group by
@@ -1192,6 +1251,10 @@ static int reduction_end(prach_engine *e, CallCtx &cx) {
     HIPCHK(hipStreamSynchronize(e->stream));
     for (int q = 0; q + 1 < np; q++) HIPCHK(hipMemcpy(R.out[q], cx.d_part[q], 8 * ng * words[q], hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(sc.data(), cx.d_part[np - 1], 8 * sc.size(), hipMemcpyDeviceToHost));
+    if (R.bulk_width && !R.bulk_dev) { // the engine's copy of the bulk part, once
+        if (R.bulk_pitch == R.bulk_width || R.bulk_rows == 1) HIPCHK(hipMemcpy(R.bulk_host, e->red_bulk, R.bulk_width * R.bulk_rows, hipMemcpyDeviceToHost));
+        else HIPCHK(hipMemcpy2D(R.bulk_host, R.bulk_pitch, e->red_bulk, R.bulk_width, R.bulk_width, R.bulk_rows, hipMemcpyDeviceToHost));
+    }
     int rc = PRACH_OK;
     for (size_t g = 0; g < ng; g++) {
         const int grc = K.unpack(R, cx, g, &sc[g * nsc]);
@@ -1416,6 +1479,7 @@ void prach_engine_destroy(prach_engine *e) {
     if (e->red_ev0) (void)hipEventDestroy(e->red_ev0);
     if (e->red_ev1) (void)hipEventDestroy(e->red_ev1);
     if (e->red_buf) (void)hipFree(e->red_buf);
+    if (e->bulk_buf) (void)hipFree(e->bulk_buf);
     if (e->red_jobs_d) (void)hipFree(e->red_jobs_d);
     if (e->red_jobs_h) (void)hipHostFree(e->red_jobs_h);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -1626,6 +1690,54 @@ int prach_run_trials_pick(prach_engine *e, const prach_cfg *cfgs, int n, prach_r
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
+// what the two columns entry points share: the refusals that need no device, then the table of first rows.  dev: the destination is the caller's device memory
+static int run_trials_columns(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_columns_spec *spec,
+                              prach_columns *hdr, void *out, uint64_t rows_cap, bool dev) {
+    // (spec, sizes and variants are judged first: what they ask for does not depend on a device)
+    if (!cfgs || !results || n <= 0 || !hdr || !out || !prach_internal_columns_spec_ok(spec)) return PRACH_ERR_ARG;
+    std::vector<uint64_t> offset((size_t)n);
+    uint64_t rows = 0;
+    for (int k = 0; k < n; k++) {
+        if (cfgs[k].nUE < 0) return PRACH_ERR_ARG;
+        offset[(size_t)k] = rows;
+        rows += (uint64_t)cfgs[k].nUE;
+    }
+    if (rows_cap < rows) return PRACH_ERR_ARG;
+    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
+    if (rows_cap > PRACH_COL_MAX_WORDS || (uint64_t)spec->ncols * rows_cap > PRACH_COL_MAX_WORDS) return PRACH_ERR_UNSUPPORTED;
+    if (!e) return PRACH_ERR_ARG;
+    if (dev) { // device memory of the engine's device, all of it: asked before the fill and before any launch
+        HIPCHK(hipSetDevice(e->device));
+        hipPointerAttribute_t attr{};
+        void *base = nullptr;
+        size_t size = 0;
+        const size_t span = 4 * ((size_t)(spec->ncols - 1) * (size_t)rows_cap + (size_t)rows);
+        if (hipPointerGetAttributes(&attr, out) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != e->device ||
+            hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t *>(&base), &size, out) != hipSuccess || (reinterpret_cast<uintptr_t>(out) & 3) != 0 ||
+            static_cast<char *>(out) + span > static_cast<char *>(base) + size) {
+            (void)hipGetLastError();
+            return PRACH_ERR_ARG;
+        }
+    }
+    Reduction red{.kind = Red::columns, .group = nullptr, .ngroups = n, .out = {}, .spec = spec, .groups = hdr};
+    (dev ? red.bulk_dev : red.bulk_host) = out;
+    red.bulk_width = 4 * (size_t)rows; red.bulk_rows = rows ? (size_t)spec->ncols : 0; red.bulk_pitch = 4 * (size_t)rows_cap; red.bulk_fill = 0xff; // -1
+    if (!rows) red.bulk_width = 0;
+    red.table = offset.data(); red.table_bytes = 8 * offset.size();
+    return run_trials_impl(e, cfgs, n, results, ue_logs, &red);
+}
+
+int prach_run_trials_columns(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_columns_spec *spec,
+                             prach_columns *hdr, int32_t *out, uint64_t rows_cap) {
+    PRACH_GUARD(return run_trials_columns(e, cfgs, n, results, ue_logs, spec, hdr, out, rows_cap, false);)
+}
+
+int prach_run_trials_columns_device(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_columns_spec *spec,
+                                    prach_columns *hdr, void *dev_out, uint64_t rows_cap) {
+    PRACH_GUARD(return run_trials_columns(e, cfgs, n, results, ue_logs, spec, hdr, dev_out, rows_cap, true);)
+}
+
+int prach_columns_tile_ues(void) { return TL_TILE; }
 int prach_xtab_tile_ues(void) { return TL_TILE; }
 int prach_xtab_window_words(void) { return XT_WINDOW_WORDS; }
 

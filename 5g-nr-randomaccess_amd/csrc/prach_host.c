@@ -993,6 +993,48 @@ size_t prach_xtab_format_csv(const prach_xtab_spec *s, const prach_xtab *x, cons
     return csv_end(buf, cap, off);
 }
 
+/* ---- columns: the menu's fields of every UE (prach_run_trials_columns) ---------------------------- */
+
+/* (the engine judges a spec with this too: csrc/prach_device.h) */
+int prach_internal_columns_spec_ok(const prach_columns_spec *s) {
+    if (!s || s->ncols < 1 || s->ncols > PRACH_COL_MAX || s->reserved[0] || s->reserved[1] || s->reserved[2]) return 0;
+    for (int c = 0; c < s->ncols; c++) {
+        const int f = s->field[c];
+        if (!((f >= 0 && f < PRACH_XTAB_NFIELDS) || (f >= PRACH_COL_RAW && f < PRACH_COL_RAW + 16))) return 0;
+    }
+    return 1;
+}
+
+/* THE DEFINITION (include/prach.h) */
+int prach_columns_from_logs(const prach_columns_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, int32_t *out, uint64_t stride) {
+    if (!prach_internal_columns_spec_ok(s) || !cfg || !out || nUE < 0 || (nUE > 0 && !ue) || stride < (uint64_t)nUE) return PRACH_ERR_ARG;
+    if (cfg->variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED;
+    if (prach_cfg_validate(cfg) != PRACH_OK || nUE != cfg->nUE) return PRACH_ERR_ARG;
+    const int nslots = (prach_max_time(cfg) + cfg->accessTime - 1) / cfg->accessTime;
+    int32_t *sched = (int32_t *)malloc(sizeof(int32_t) * (size_t)nslots);
+    if (!sched) return PRACH_ERR_INTERNAL;
+    prach_arrival_schedule(cfg, sched, nslots, NULL);
+    const int64_t E = steps < (uint64_t)prach_max_time(cfg) ? (int64_t)steps : (int64_t)prach_max_time(cfg);
+    int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
+    for (int i = 0; i < nUE; i++) {
+        while (slot < nslots && sched[slot] <= i) slot++;
+        const int64_t a = (int64_t)cfg->accessTime * slot;
+        const int cls = xtab_class(&ue[i]);
+        for (int c = 0; c < s->ncols; c++) {
+            const int f = s->field[c];
+            int32_t v;
+            if (f >= PRACH_COL_RAW) v = ((const int32_t *)&ue[i])[f - PRACH_COL_RAW]; /* the log word as it is */
+            else {
+                const int64_t x = xtab_value(f, &ue[i], cls, a, E);
+                v = x < 0 ? -1 : (int32_t)x; /* a negative value is UNDEFINED */
+            }
+            out[(size_t)c * (size_t)stride + (size_t)i] = v;
+        }
+    }
+    free(sched);
+    return PRACH_OK;
+}
+
 /* ---- picks: the UEs behind a count, per trial (prach_run_trials_pick) ----------------------------- */
 
 /* (the engine judges a spec with this too: csrc/prach_device.h) */

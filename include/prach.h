@@ -129,6 +129,8 @@ typedef struct prach_timing {
     int32_t trial_kernel_reruns; /* of fallback_trials: trials that were (also) rerun on the one-workgroup, index-ordered trial_kernel */
     int32_t noma_host_ues;       /* NOMA_C, Philox: UEs of the device-built activeUE table that the host recomputed with its libm (a value inside the
                                     device math library's error band of a rounding / comparison boundary: ~1e-6 of the UEs) */
+    double columns_ms;           /* HIP-event time of the columns kernel launches (prach_run_trials_columns, prach_run_trials_columns_device) of the last call; 0 in
+                                    every other call (a columns call leaves every other *_ms of a reduction 0) */
     double pick_ms;              /* HIP-event time of the pick kernel launches (prach_run_trials_pick) of the last call; 0 in every other call (a pick call
                                     leaves every other *_ms of a reduction 0) */
     double xtab_ms;              /* HIP-event time of the cross-tabulation kernel launches (prach_run_trials_xtab) of the last call; 0 in every other call (an
@@ -427,6 +429,46 @@ typedef struct prach_pick {     /* one per TRIAL */
  * n * k * 10 + n * 8 > 2^27 words (1 GiB of device buffer). */
 int prach_run_trials_pick(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_pick_spec *spec,
                           prach_pick *picks, prach_pick_row *rows);
+
+/* Per-UE columns, computed on the device: the menu of the cross-tabulation above for EVERY UE of every trial, as plain int32 columns — the escape hatch for
+ * a question outside the fixed kinds (a correlation, a survival curve, a quantile by two conditions).  The other route to the same values is 64 bytes per UE
+ * over the bus and a restatement of a(i), the classes and the STATE rule on the host; this one moves 4 bytes per asked-for field, or nothing at all: the
+ * columns go to the host, or into DEVICE memory the caller owns (a torch tensor), where any further reduction runs.
+ * A FIELD is a PRACH_XTAB_* id (0 .. 8) or PRACH_COL_RAW + w, w = 0 .. 15: word w of the UE's prach_ue_log, exactly as logged.  A menu field holds the
+ * menu's value with E = min(steps, maxTime), and -1 where the menu says UNDEFINED (its ONE RULE: a negative value is undefined, so is a field outside the
+ * classes it is defined for); every menu value of a trial fits int32 (csrc/prach_columns.hip states the bound).  A field may be named twice.
+ * LAYOUT: column c of UE i of trial k is out[c * rows_cap + hdr[k].offset + i]; hdr[k].offset is the sum of cfgs[j].nUE over j < k, whatever their status.
+ * A trial whose final status is not PRACH_OK has -1 in every word of every column and its status in its header.  Words at rows >= the sum of all nUE are
+ * not touched.  Beta.c and RandomAccessWithNOMA.c only, like the timeline. */
+#define PRACH_COL_MAX 16
+#define PRACH_COL_RAW 16   /* field PRACH_COL_RAW + w, w = 0..15: word w of the UE's prach_ue_log, exactly as logged */
+#define PRACH_COL_MAX_WORDS (1ull << 31) /* ncols * rows_cap at most: 8 GiB of columns (the 1000-trial grid, 55 M UEs, with 16 columns is 0.9 x 2^30 words) */
+typedef struct prach_columns_spec { int32_t ncols; int32_t field[PRACH_COL_MAX]; int32_t reserved[3]; } prach_columns_spec; /* ncols 1..16; the fields behind it are ignored */
+typedef struct prach_columns {            /* one per TRIAL */
+    int32_t status, nUE; uint64_t offset; /* first row of this trial: the sum of cfgs[j].nUE over j < k, whatever their status */
+    int32_t idle, served, unserved, reserved; /* the three classes, counted by the kernel: idle + served + unserved == nUE; 0 unless status is PRACH_OK */
+} prach_columns;
+
+/* prach_run_trials plus the columns: hdr[n] and out[ncols * rows_cap] are caller-owned; hdr is OVERWRITTEN, and so are the rows [0, sum of nUE) of every
+ * column.  A trial the engine reruns — the calendar rerun, a call split by its memory budget, the fallback ladder, a timeout — is written by the ONE launch
+ * whose result is kept; the output does not depend on how a call is split.  prach::columns_kernel (csrc/prach_columns.hip) writes into a buffer of the
+ * engine's, which is filled with -1 once in front of the first launch and copied out once at the end of the call.
+ * prach_run_trials_columns_device: the same with dev_out in DEVICE memory of the engine's device (hipPointerGetAttributes must say so): the kernel writes
+ * straight into it, nothing but the headers crosses the bus.  The memory must be made by the HIP runtime this library is linked to (one process, one
+ * runtime: README.md), and work queued on it on other streams must have completed.
+ * Refused before anything is launched or written —
+ * PRACH_ERR_ARG: a NULL spec, header or destination, ncols outside 1 .. PRACH_COL_MAX, a field outside the menu and outside 16 .. 31, a non-zero reserved
+ * word, rows_cap below the sum of all nUE; _device: a destination that is not device memory of the engine's device;
+ * PRACH_ERR_UNSUPPORTED: any NOMA_C cfg; ncols * rows_cap > PRACH_COL_MAX_WORDS. */
+int prach_run_trials_columns(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_columns_spec *spec,
+                             prach_columns *hdr, int32_t *out, uint64_t rows_cap);
+int prach_run_trials_columns_device(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs,
+                                    const prach_columns_spec *spec, prach_columns *hdr, void *dev_out, uint64_t rows_cap);
+/* THE DEFINITION prach::columns_kernel equals, integer for integer: the columns of ONE trial from its per-UE log; steps is the trial's prach_result.steps.
+ * Column c of UE i at out[c * stride + i] (stride >= nUE).  PRACH_ERR_ARG: a bad spec, a NULL pointer, nUE != cfg->nUE, stride < nUE;
+ * PRACH_ERR_UNSUPPORTED: a NOMA_C cfg. */
+int prach_columns_from_logs(const prach_columns_spec *, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, int32_t *out, uint64_t stride);
+int prach_columns_tile_ues(void); /* UEs of one trial that one workgroup of prach::columns_kernel writes (tests place sizes around it) */
 
 /* Per-subframe preamble trace per trial group, recorded by the simulation kernels WHILE THEY RUN and reduced on the device: how many preambles were used,
  * decoded and collided in each stretch of the simulation — the quantities TR 37.868's collision probability is defined on.  Unlike the four reductions above
