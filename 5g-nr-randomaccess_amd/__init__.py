@@ -55,7 +55,7 @@ class PrachTiming(C.Structure):
                 ("launches", C.c_int32), ("workgroups", C.c_int32), ("updates", C.c_uint64),
                 ("cluster_size", C.c_int32), ("resident_limit", C.c_int32), ("fallback_trials", C.c_int32), ("spin_timeouts", C.c_int32),
                 ("rec_mode", C.c_int32), ("xcd_packed", C.c_int32), ("group_visits", C.c_uint64), ("event_ues", C.c_uint64),
-                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("columns_ms", C.c_double), ("pick_ms", C.c_double), ("xtab_ms", C.c_double), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
+                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("noma_census_ms", C.c_double), ("noma_columns_ms", C.c_double), ("columns_ms", C.c_double), ("pick_ms", C.c_double), ("xtab_ms", C.c_double), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
                 ("sojourn_ms", C.c_double)]
 
 
@@ -575,6 +575,117 @@ class Columns:
         return self.data[self.field_ids.index(columns_field(name))]
 
 
+NOMA_SERVED, NOMA_PENDING, NOMA_IDLE, NOMA_DROPPED = 1, 2, 4, 8
+NOMA_WHO = {"served": NOMA_SERVED, "pending": NOMA_PENDING, "dropped": NOMA_DROPPED, "idle": NOMA_IDLE, "arrived": NOMA_SERVED | NOMA_PENDING | NOMA_DROPPED,
+            "all": NOMA_SERVED | NOMA_PENDING | NOMA_IDLE | NOMA_DROPPED}
+NOMA_FIELD_NAMES = ("one", "arrival", "sojourn", "completion", "timer", "ptc", "retx", "msg3fail", "age", "state", "sector", "preamble", "lost")
+NOMA_STATE_NAMES = ("idle", "served", "dropped", "backoff", "tx_ahead", "stranded", "msg3_pending", "msg3_timeout", "other")
+NOMA_CENSUS_FIELDS = ("trials", "ues", "idle", "served", "dropped", "pending", "selected", "binned", "undefined", "row_sum", "col_sum", "row_max", "col_max")
+
+
+class PrachNomaCensus(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in NOMA_CENSUS_FIELDS[:-2]] + [("row_max", C.c_int64), ("col_max", C.c_int64)]
+
+
+class PrachNomaColumns(C.Structure):
+    _fields_ = [("status", C.c_int32), ("nUE", C.c_int32), ("offset", C.c_uint64)] + [(n, C.c_int32) for n in ("idle", "served", "dropped", "pending")]
+
+
+def noma_field(f):
+    """A field id of the NOMA menu: a name of NOMA_FIELD_NAMES or the id itself."""
+    return NOMA_FIELD_NAMES.index(f.lower()) if isinstance(f, str) and not f.lstrip("-").isdigit() else int(f)
+
+
+def noma_axis(ax):
+    """An axis of a NOMA census as (field id, width, bins): from such a tuple, whose field may be a name of NOMA_FIELD_NAMES, or from the text FIELD:WIDTH:BINS."""
+    f, w, b = ax.split(":") if isinstance(ax, str) else ax
+    return noma_field(f), int(w), int(b)
+
+
+class NomaCensus(_Reduction):
+    """The NOMA.c outcome census of ``ngroups`` trial groups (include/prach.h, prach_noma_census): ``cells`` [ngroups, row_bins + 1, col_bins + 1] as numpy uint64
+    (the last index of an axis is its overflow bin) and ``scalars[field]``, one int64 array of length ngroups per field of NOMA_CENSUS_FIELDS.  rows, cols: an
+    axis each, (field, width, bins), a field of NOMA_FIELD_NAMES; who: the classes that enter, bits NOMA_SERVED | NOMA_PENDING | NOMA_IDLE | NOMA_DROPPED."""
+    _FIELDS, _STRUCT, _MERGE, _PARAMS = NOMA_CENSUS_FIELDS, PrachNomaCensus, "prach_noma_census_merge", ("who", "rows", "cols")
+
+    def __init__(self, ngroups, rows, cols, who=NOMA_WHO["all"]):
+        import numpy as np
+        self.rows, self.cols, self.who, self.ngroups = noma_axis(rows), noma_axis(cols), int(who), int(ngroups)
+        self.cells = np.zeros((self.ngroups, max(self.rows[2], 0) + 1, max(self.cols[2], 0) + 1), dtype=np.uint64)
+        self.scalars = {f: np.zeros(self.ngroups, dtype=np.int64) for f in NOMA_CENSUS_FIELDS}
+        self.scalars["row_max"][:] = -1
+        self.scalars["col_max"][:] = -1
+
+    def spec(self):
+        return PrachXtabSpec(self.who, *self.rows, *self.cols, self.ngroups, (C.c_int32 * 2)(0, 0))
+
+    def _arrays(self):
+        return [self.cells]
+
+    def _scalar(self, f):
+        return self.scalars[f]
+
+    def _cargs(self, g):
+        return tuple(self._rows(g))
+
+    def cell_clauses(self, row_bin, col_bin):
+        """The two clauses (field, lo, hi) that describe exactly the UEs counted in cell [row_bin, col_bin] — NOMA field ids; the last bin of an axis is its
+        overflow bin, which has no upper edge (hi is the largest int32).  There is no NOMA pick to hand them to: they filter the columns of
+        Engine.run_trials_noma_columns (lo <= column <= hi)."""
+        out = []
+        for (f, w, b), bin_ in ((self.rows, int(row_bin)), (self.cols, int(col_bin))):
+            if not 0 <= bin_ <= b:
+                raise ValueError(f"bin {bin_} is not one of the {b} + 1 bins of the axis")
+            out.append((f, bin_ * w, (bin_ + 1) * w - 1 if bin_ < b else 2 ** 31 - 1))
+        return out
+
+    def quantile(self, g, row, q):
+        """Xtab.quantile on this census's cells: prach_xtab_quantile reads only widths and bin counts, so it gets an xtab spec with those."""
+        sp = PrachXtabSpec(XTAB_SERVED, 0, self.rows[1], self.rows[2], 0, self.cols[1], self.cols[2], self.ngroups, (C.c_int32 * 2)(0, 0))
+        return int(lib().prach_xtab_quantile(C.byref(sp), self._rows(g)[0], int(row), float(q)))
+
+
+def noma_columns_header_dtype():
+    import numpy as np
+    dt = np.dtype([("status", np.int32), ("nUE", np.int32), ("offset", np.uint64)] + [(n, np.int32) for n in ("idle", "served", "dropped", "pending")])
+    assert dt.itemsize == C.sizeof(PrachNomaColumns) == 32
+    return dt
+
+
+def noma_columns_field(f):
+    """A NOMA column's field id: a name of NOMA_FIELD_NAMES, ``raw:NAME`` with a field name of PrachUeLog (COL_RAW + its word), or the id itself."""
+    if isinstance(f, str) and f.lower().startswith("raw:"):
+        return COL_RAW + UE_FIELDS.index(f[4:])
+    return noma_field(f)
+
+
+def noma_columns_field_name(f):
+    return NOMA_FIELD_NAMES[f] if 0 <= f < len(NOMA_FIELD_NAMES) else "raw:" + UE_FIELDS[f - COL_RAW] if COL_RAW <= f < COL_RAW + 16 else str(f)
+
+
+def noma_columns_spec(fields):
+    sp = PrachColumnsSpec()
+    ids = [noma_columns_field(f) for f in fields]
+    sp.ncols = len(ids)  # (a count the library refuses stays visible to it)
+    for c, f in enumerate(ids[:COL_MAX]):
+        sp.field[c] = f
+    return sp, ids
+
+
+class NomaColumns(Columns):
+    """Columns over the NOMA menu (include/prach.h, prach_noma_columns): fields are names of NOMA_FIELD_NAMES or raw:NAME, headers have noma_columns_header_dtype."""
+
+    def __init__(self, fields, headers, data):
+        self.field_ids = tuple(noma_columns_field(f) for f in fields)
+        self.fields = tuple(noma_columns_field_name(f) for f in self.field_ids)
+        self.headers, self.data = headers, data
+        self.offsets = headers["offset"].astype("int64")
+
+    def column(self, name):
+        """[rows]: the (first) column of that field, a view."""
+        return self.data[self.field_ids.index(noma_columns_field(name))]
+
+
 class PrachError(RuntimeError):
     def __init__(self, status, what=""):
         self.status = status
@@ -678,6 +789,18 @@ def lib():
         L.prach_run_trials_columns_device.argtypes = L.prach_run_trials_columns.argtypes
         L.prach_columns_from_logs.argtypes = [C.POINTER(PrachColumnsSpec), C.POINTER(PrachCfg), C.c_uint64, C.POINTER(PrachUeLog), C.c_int, C.c_void_p, C.c_uint64]
         L.prach_columns_tile_ues.argtypes = []
+        L.prach_run_trials_noma_census.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachXtabSpec),
+                                                   C.POINTER(C.c_int32), C.POINTER(PrachNomaCensus), u64p]
+        L.prach_noma_census_accumulate_logs.argtypes = [C.POINTER(PrachXtabSpec), C.POINTER(PrachCfg), C.c_uint64, C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachNomaCensus), u64p]
+        L.prach_noma_census_merge.argtypes = [C.POINTER(PrachXtabSpec), C.POINTER(PrachNomaCensus), u64p, C.POINTER(PrachNomaCensus), u64p]
+        L.prach_noma_census_merge.restype = None
+        L.prach_noma_census_format_csv.argtypes = [C.POINTER(PrachXtabSpec), C.POINTER(PrachNomaCensus), u64p, C.c_char_p, C.c_char_p, C.c_size_t]
+        L.prach_noma_census_format_csv.restype = C.c_size_t
+        L.prach_noma_census_tile_ues.argtypes = []
+        L.prach_run_trials_noma_columns.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachColumnsSpec),
+                                                    C.POINTER(PrachNomaColumns), C.c_void_p, C.c_uint64]
+        L.prach_run_trials_noma_columns_device.argtypes = L.prach_run_trials_noma_columns.argtypes
+        L.prach_noma_columns_from_logs.argtypes = [C.POINTER(PrachColumnsSpec), C.POINTER(PrachCfg), C.c_uint64, C.POINTER(PrachUeLog), C.c_int, C.c_void_p, C.c_uint64]
         L.prach_run_trials_trace.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachTraceSpec),
                                              C.POINTER(C.c_int32), C.POINTER(PrachTrace), u64p, u64p, u64p, u64p]
         L.prach_trace_merge.argtypes = [C.POINTER(PrachTraceSpec), C.POINTER(PrachTrace), u64pp, C.POINTER(PrachTrace), u64pp]
@@ -730,7 +853,8 @@ EXPORTS = ("prach_engine_create", "prach_engine_destroy", "prach_engine_set", "p
            "prach_run_trials_trace", "prach_trace_merge", "prach_trace_format_csv", "prach_trace_tile_subframes", "prach_run_trials_xtab", "prach_xtab_accumulate_logs",
            "prach_xtab_merge", "prach_xtab_quantile", "prach_xtab_format_csv", "prach_xtab_tile_ues", "prach_xtab_window_words", "prach_run_trials_pick",
            "prach_pick_from_logs", "prach_pick_format_csv", "prach_run_trials_columns", "prach_run_trials_columns_device", "prach_columns_from_logs",
-           "prach_columns_tile_ues")
+           "prach_columns_tile_ues", "prach_run_trials_noma_census", "prach_noma_census_accumulate_logs", "prach_noma_census_merge", "prach_noma_census_format_csv",
+           "prach_noma_census_tile_ues", "prach_run_trials_noma_columns", "prach_run_trials_noma_columns_device", "prach_noma_columns_from_logs")
 
 
 def make_cfg(nUE, variant=VARIANT_BETA_C, uniform=0, rng_mode=RNG_GLIBC, seed=0, stream_offset=0, **kw) -> PrachCfg:
@@ -850,26 +974,43 @@ class Engine:
         the bus.  device=True: it is a torch tensor on this engine's GPU that the kernel wrote straight into (prach_run_trials_columns_device), and nothing
         but the headers crosses the bus; torch must have been imported BEFORE this package loaded its library, so that both use one HIP runtime.
         Returns (results, logs, Columns)."""
+        return self._run_columns("run_trials_columns", "prach_run_trials_columns", cfgs, fields, device, want_logs, columns_spec, columns_header_dtype(), PrachColumns, Columns)
+
+    def _run_columns(self, what, name, cfgs, fields, device, want_logs, make_spec, hdr_dtype, hdr_struct, cls):
+        """What run_trials_columns and run_trials_noma_columns share: the spec, the headers, the host or torch destination (and the one-runtime guard)."""
         import numpy as np
-        sp, ids = columns_spec(fields)
+        sp, ids = make_spec(fields)
         rows = sum(int(c.nUE) for c in cfgs)
-        hdr = np.zeros(len(cfgs), dtype=columns_header_dtype())
-        hp = hdr.ctypes.data_as(C.POINTER(PrachColumns))
+        hdr = np.zeros(len(cfgs), dtype=hdr_dtype)
+        hp = hdr.ctypes.data_as(C.POINTER(hdr_struct))
         if not device:
             data = np.empty((max(len(ids), 1), rows), dtype=np.int32)
-            res, logs = self._call("prach_run_trials_columns", cfgs, want_logs, C.byref(sp), hp, data.ctypes.data, rows)
-            return res, logs, Columns(ids, hdr, data[:len(ids)])
+            res, logs = self._call(name, cfgs, want_logs, C.byref(sp), hp, data.ctypes.data, rows)
+            return res, logs, cls(ids, hdr, data[:len(ids)])
         lib()
         if _lib_before_torch:
-            raise PrachError(-1, "(run_trials_columns device=True: libprach_hip.so was loaded before torch was imported, so torch brought a HIP runtime of its "
+            raise PrachError(-1, f"({what} device=True: libprach_hip.so was loaded before torch was imported, so torch brought a HIP runtime of its "
                                  "own and its device pointers mean nothing to the library's: import torch first, then make the first call into this package)")
         import torch
         if len(hip_runtimes()) > 1:
-            raise PrachError(-1, f"(run_trials_columns device=True: two HIP runtimes are loaded, {', '.join(hip_runtimes())}: torch and libprach_hip.so must share one)")
+            raise PrachError(-1, f"({what} device=True: two HIP runtimes are loaded, {', '.join(hip_runtimes())}: torch and libprach_hip.so must share one)")
         data = torch.empty((max(len(ids), 1), rows), dtype=torch.int32, device=torch.device("cuda", self.device))
         torch.cuda.synchronize(self.device)  # (the engine's stream is not torch's)
-        res, logs = self._call("prach_run_trials_columns_device", cfgs, want_logs, C.byref(sp), hp, data.data_ptr(), rows)
-        return res, logs, Columns(ids, hdr, data[:len(ids)])
+        res, logs = self._call(name + "_device", cfgs, want_logs, C.byref(sp), hp, data.data_ptr(), rows)
+        return res, logs, cls(ids, hdr, data[:len(ids)])
+
+    def run_trials_noma_census(self, cfgs, rows=("arrival", 500, 20), cols=("state", 1, 9), who=NOMA_WHO["all"], groups=None, want_logs=False, ngroups=None):
+        """run_trials plus the NOMA.c outcome census per trial group — a table of two quantities of the NOMA menu (rows, cols: (field, width, bins), a field of
+        NOMA_FIELD_NAMES) over the classes of UEs in ``who`` — reduced on the device from the log records prach::noma_kernel leaves there
+        (prach_run_trials_noma_census; NOMA.c trials with Philox only).  The default: what became of the UEs by when they arrived.  groups / ngroups /
+        want_logs as in run_trials_dist.  Returns (results, logs, NomaCensus)."""
+        return self._call_reduced("prach_run_trials_noma_census", cfgs, NomaCensus(_ngroups(len(cfgs), groups, ngroups), rows, cols, who), groups, want_logs)
+
+    def run_trials_noma_columns(self, cfgs, fields, device=False, want_logs=False):
+        """run_trials_columns for NOMA.c trials with Philox: ``fields`` are names of NOMA_FIELD_NAMES, -1 where undefined, or ``raw:NAME``
+        (prach_run_trials_noma_columns, prach_run_trials_noma_columns_device).  device as in run_trials_columns.  Returns (results, logs, NomaColumns)."""
+        return self._run_columns("run_trials_noma_columns", "prach_run_trials_noma_columns", cfgs, fields, device, want_logs, noma_columns_spec, noma_columns_header_dtype(),
+                                 PrachNomaColumns, NomaColumns)
 
     def run_trials_trace(self, cfgs, bins, bin_ms=1, groups=None, want_logs=False, ngroups=None):
         """run_trials plus the per-subframe preamble trace per trial group — preambles used (calls), decoded (singles) and what the subframes added to
@@ -1216,3 +1357,50 @@ def columns_from_logs(cfgs, steps, logs, fields) -> Columns:
                 raise PrachError(rc, "(prach_columns_from_logs)")
         hdr["idle"][k], hdr["served"][k], hdr["unserved"][k] = (st == 0).sum(), (st == 1).sum(), (st >= 2).sum()
     return Columns(ids, hdr, data[:len(ids)])
+
+
+def noma_census_tile_ues() -> int:
+    return lib().prach_noma_census_tile_ues()
+
+
+def noma_census_from_logs(cfgs, steps, logs, rows=("arrival", 500, 20), cols=("state", 1, 9), who=NOMA_WHO["all"], groups=None, ngroups=None) -> NomaCensus:
+    """The host-side definition of the NOMA census (prach_noma_census_accumulate_logs): logs[k] is the per-UE log of the NOMA.c trial with config cfgs[k] that
+    ran steps[k] subframes (prach_result.steps) — a ctypes array of PrachUeLog or an int32 array of shape [nUE, 16] — added to group groups[k] (None: group k)."""
+    cs = NomaCensus(_ngroups(len(logs), groups, ngroups), rows, cols, who)
+    sp = cs.spec()
+    for k, lg in enumerate(logs):
+        g = k if groups is None else int(groups[k])
+        ptr, nue, _keep = _log_ptr(lg)
+        d = cs._group(g)
+        rc = lib().prach_noma_census_accumulate_logs(C.byref(sp), C.byref(cfgs[k]), int(steps[k]), ptr, nue, C.byref(d), *cs._rows(g))
+        if rc != OK:
+            raise PrachError(rc, "(prach_noma_census_accumulate_logs)")
+        cs._store(g, d)
+    return cs
+
+
+def noma_census_csv(cs: NomaCensus, labels=None) -> bytes:
+    """The CSV text of every group (prach_noma_census_format_csv: the lines of xtab_csv), labelled labels[g] (default: the group number)."""
+    return _csv("prach_noma_census_format_csv", cs, labels)
+
+
+def noma_columns_from_logs(cfgs, steps, logs, fields) -> NomaColumns:
+    """The host-side definition of the NOMA columns (prach_noma_columns_from_logs), as columns_from_logs.  The class counts of the headers are those of the
+    definition's own STATE column."""
+    import numpy as np
+    sp, ids = noma_columns_spec(fields)
+    state, _ = noma_columns_spec(["state"])
+    hdr = np.zeros(len(logs), dtype=noma_columns_header_dtype())
+    ptrs = [_log_ptr(lg) for lg in logs]
+    hdr["nUE"] = [nue for _, nue, _ in ptrs]
+    hdr["offset"] = np.concatenate([[0], np.cumsum(hdr["nUE"], dtype=np.uint64)[:-1]]) if len(logs) else []
+    rows = int(hdr["nUE"].sum())
+    data = np.empty((max(len(ids), 1), rows), dtype=np.int32)
+    for k, (ptr, nue, _keep) in enumerate(ptrs):
+        st = np.empty(nue, dtype=np.int32)
+        for spec, out, stride in ((sp, data.ctypes.data + 4 * int(hdr["offset"][k]), rows), (state, st.ctypes.data, nue)):
+            rc = lib().prach_noma_columns_from_logs(C.byref(spec), C.byref(cfgs[k]), int(steps[k]), ptr, nue, out, stride)
+            if rc != OK:
+                raise PrachError(rc, "(prach_noma_columns_from_logs)")
+        hdr["idle"][k], hdr["served"][k], hdr["dropped"][k], hdr["pending"][k] = (st == 0).sum(), (st == 1).sum(), (st == 2).sum(), (st >= 3).sum()
+    return NomaColumns(ids, hdr, data[:len(ids)])

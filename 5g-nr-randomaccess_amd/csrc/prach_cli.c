@@ -44,6 +44,11 @@
  * exact number of matches and the K (default 16) UEs that pass every clause LO <= FIELD <= HI (at most 4) — the first K by index, or those with the largest
  * (--pick-top) / smallest (--pick-bottom) FIELD — as one line each: label nUE, trial, seed, nUE, rank, key, arrival and the 16 logged fields; --program
  * beta|withnoma only, and not together with --cdf, --timeline, --sojourn, --ci, --trace or --xtab (one reduction per call);
+ * --census FILE [--census-rows FIELD[:WIDTH[:BINS]]] [--census-cols FIELD[:WIDTH[:BINS]]] [--census-who served|pending|dropped|arrived|all]: NOMA.c's outcome
+ * census (prach_run_trials_noma_census: reduced on the device), one group per sweep point with the --times seeds merged, labelled nUE, in --xtab's line format;
+ * FIELD is one of one, arrival, sojourn, completion, timer, ptc, retx, msg3fail, age, state, sector, preamble, lost (the NOMA menu of include/prach.h); the
+ * defaults — rows arrival:500, columns state:1:9, everybody — say what became of the UEs by when they arrived; --program noma with Philox only, and not
+ * together with another reduction;
  * --devices LIST: the same with explicit HIP ordinals (an ordinal may repeat);
  * --gpus N: the --times x sweep grid sharded over N devices of the node by host C — one forked child per device,
  * forked BEFORE any HIP call, trials dealt by descending cost (Philox: any trial anywhere; glibc: whole seeds, because
@@ -131,11 +136,13 @@ typedef struct reduction {
     const prach_pick_spec *pk;
     prach_pick *pk_hdr;
     prach_pick_row *pk_rows;
+    const prach_xtab_spec *nc;  /* --census (--program noma): prach_noma_census[npts] | cells[npts][row_bins + 1][col_bins + 1] */
 } reduction;
-static int red_on(const reduction *r) { return r->cdf || r->tl || r->sj || r->tr || r->xt; }
+static int red_on(const reduction *r) { return r->cdf || r->tl || r->sj || r->tr || r->xt || r->nc; }
 static size_t xt_cells(const prach_xtab_spec *s) { return ((size_t)s->row_bins + 1) * ((size_t)s->col_bins + 1); }
 static size_t sj_cells(const prach_sojourn_spec *s) { return (size_t)s->arrival_bins * (size_t)s->delay_bins; }
 static size_t red_block_bytes(const reduction *r) {
+    if (r->nc) return (size_t)r->nc->ngroups * (sizeof(prach_noma_census) + 8 * xt_cells(r->nc));
     if (r->xt) return (size_t)r->xt->ngroups * (sizeof(prach_xtab) + 8 * xt_cells(r->xt));
     if (r->tr) return (size_t)r->tr->ngroups * (sizeof(prach_trace) + 4 * 8 * (size_t)r->tr->bins);
     if (r->tl) return (size_t)r->tl->ngroups * (sizeof(prach_timeline) + 5 * 8 * (size_t)r->tl->bins);
@@ -144,6 +151,7 @@ static size_t red_block_bytes(const reduction *r) {
 }
 /* group g of block b: --cdf its q-th histogram (0 delay, 1 preamble count), --timeline its q-th series, --sojourn 0 hist, 1 row_arrived, 2 row_delay_overflow */
 static uint64_t *red_array(const reduction *r, char *b, int q, int g) {
+    if (r->nc) return (uint64_t *)(b + (size_t)r->nc->ngroups * sizeof(prach_noma_census)) + (size_t)g * xt_cells(r->nc);
     if (r->xt) return (uint64_t *)(b + (size_t)r->xt->ngroups * sizeof(prach_xtab)) + (size_t)g * xt_cells(r->xt);
     if (r->tr) return (uint64_t *)(b + (size_t)r->tr->ngroups * sizeof(prach_trace)) + ((size_t)q * (size_t)r->tr->ngroups + (size_t)g) * (size_t)r->tr->bins;
     if (r->sj) {
@@ -162,8 +170,12 @@ static void red_init_block(const reduction *r, char *b) {
     for (int g = 0; r->sj && g < r->sj->ngroups; g++) ((prach_sojourn *)b)[g].sojourn_max = -1;
     for (int g = 0; r->tr && g < r->tr->ngroups; g++) ((prach_trace *)b)[g].calls_max = -1;
     for (int g = 0; r->xt && g < r->xt->ngroups; g++) ((prach_xtab *)b)[g].row_max = ((prach_xtab *)b)[g].col_max = -1;
+    for (int g = 0; r->nc && g < r->nc->ngroups; g++) ((prach_noma_census *)b)[g].row_max = ((prach_noma_census *)b)[g].col_max = -1;
 }
 static void red_merge_block(const reduction *r, char *into, char *from) {
+    for (int g = 0; r->nc && g < r->nc->ngroups; g++)
+        prach_noma_census_merge(r->nc, (prach_noma_census *)into + g, red_array(r, into, 0, g), (prach_noma_census *)from + g, red_array(r, from, 0, g));
+    if (r->nc) return;
     for (int g = 0; r->xt && g < r->xt->ngroups; g++) prach_xtab_merge(r->xt, (prach_xtab *)into + g, red_array(r, into, 0, g), (prach_xtab *)from + g, red_array(r, from, 0, g));
     if (r->xt) return;
     for (int g = 0; r->tr && g < r->tr->ngroups; g++) {
@@ -187,6 +199,7 @@ static void red_merge_block(const reduction *r, char *into, char *from) {
 }
 /* the CSV text of group g of block b; returns its length (>= cap: it did not fit) */
 static size_t red_format_group(const reduction *r, char *b, int g, const char *label, char *out, size_t cap) {
+    if (r->nc) return prach_noma_census_format_csv(r->nc, (prach_noma_census *)b + g, red_array(r, b, 0, g), label, out, cap);
     if (r->xt) return prach_xtab_format_csv(r->xt, (prach_xtab *)b + g, red_array(r, b, 0, g), label, out, cap);
     if (r->tr) {
         const uint64_t *ser[4];
@@ -238,6 +251,27 @@ static int xtab_axis(const char *text, int max_time, int32_t *field, int32_t *wi
     return 1;
 }
 
+/* FIELD[:WIDTH[:BINS]] of --census-rows / --census-cols: a field of the NOMA menu.  Defaults: width 500 for arrival, otherwise 1; as many bins as cover max_time
+ * (arrival) or max_time + 6 (the other times), 9 for state, 1 for one, 6 for sector, 64 for preamble, 255 for ptc, retx and msg3fail.  Returns 0 for a text that is none */
+static const char *const noma_names[PRACH_NOMA_NFIELDS] = {"one", "arrival", "sojourn", "completion", "timer", "ptc", "retx", "msg3fail", "age", "state", "sector", "preamble", "lost"};
+static int noma_axis(const char *text, int max_time, int32_t *field, int32_t *width, int32_t *bins) {
+    const char *c1 = strchr(text, ':'), *c2 = c1 ? strchr(c1 + 1, ':') : NULL;
+    const size_t len = c1 ? (size_t)(c1 - text) : strlen(text);
+    int f = -1;
+    for (int q = 0; q < PRACH_NOMA_NFIELDS; q++)
+        if (strlen(noma_names[q]) == len && strncasecmp(noma_names[q], text, len) == 0) f = q;
+    if (f < 0 || (c2 && strchr(c2 + 1, ':'))) return 0;
+    const long w = c1 ? atol(c1 + 1) : f == PRACH_NOMA_ARRIVAL ? 500 : 1;
+    if (w < 1 || w > INT32_MAX) return 0;
+    long b = f == PRACH_NOMA_ONE ? 1 : f == PRACH_NOMA_STATE ? 9 : f == PRACH_NOMA_SECTOR ? 6 : f == PRACH_NOMA_PREAMBLE ? 64
+             : f == PRACH_NOMA_PTC || f == PRACH_NOMA_RETX || f == PRACH_NOMA_MSG3FAIL ? 255 : (max_time + (f == PRACH_NOMA_ARRIVAL ? 0 : 6) + w - 1) / w;
+    if (b > PRACH_XTAB_MAX_BINS) b = PRACH_XTAB_MAX_BINS;
+    if (c2) b = atol(c2 + 1);
+    if (b < 1 || b > PRACH_XTAB_MAX_BINS) return 0;
+    *field = f; *width = (int32_t)w; *bins = (int32_t)b;
+    return 1;
+}
+
 /* one call into the library with the run's reduction: its groups (group = sweep point, grp[k]) come back in call_block and are merged into the worker's block */
 static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *r, prach_ue_log *const *logs, const reduction *red, const int32_t *grp,
                     char *call_block, char *worker_block, prach_trial_summary *sm_rows, prach_pick *pk_hdr, prach_pick_row *pk_rows) {
@@ -245,7 +279,8 @@ static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *
     if (red->pk) return prach_run_trials_pick(eng, c, n, r, logs, red->pk, pk_hdr, pk_rows);
     if (!red_on(red)) return prach_run_trials(eng, c, n, r, logs);
     char *const b = call_block;
-    const int rc = red->xt ? prach_run_trials_xtab(eng, c, n, r, logs, red->xt, grp, (prach_xtab *)b, red_array(red, b, 0, 0))
+    const int rc = red->nc ? prach_run_trials_noma_census(eng, c, n, r, logs, red->nc, grp, (prach_noma_census *)b, red_array(red, b, 0, 0))
+                   : red->xt ? prach_run_trials_xtab(eng, c, n, r, logs, red->xt, grp, (prach_xtab *)b, red_array(red, b, 0, 0))
                    : red->tr ? prach_run_trials_trace(eng, c, n, r, logs, red->tr, grp, (prach_trace *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0), red_array(red, b, 2, 0),
                                                     red_array(red, b, 3, 0))
                    : red->tl ? prach_run_trials_timeline(eng, c, n, r, logs, red->tl, grp, (prach_timeline *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0),
@@ -353,6 +388,7 @@ int main(int argc, char *argv[]) {
     const char *pk_who = "all";
     prach_pick_spec pk_spec = {0, 0, {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, PRACH_PICK_BY_INDEX, PRACH_XTAB_ONE, 16, 0};
     const char *xt_rows = "arrival:500", *xt_cols = "state:1:7", *xt_who = "all";
+    const char *nc_path = NULL, *nc_rows = "arrival:500", *nc_cols = "state:1:9", *nc_who = "all";
     prach_summary_spec ci_spec = {3, {500, 950, 990, 0, 0, 0, 0, 0}, {0, 0, 0}};
     int cdf_bins = 4096, cdf_bin_ms = 1, tl_bin_ms = 5, sj_row_ms = 500, sj_bin_ms = 5, tr_bin_ms = 5;
     int devs[64];
@@ -463,6 +499,14 @@ int main(int argc, char *argv[]) {
             xt_cols = v;
         } else if (strcmp(a, "--xtab-who") == 0) {
             xt_who = v;
+        } else if (strcmp(a, "--census") == 0) {
+            nc_path = v;
+        } else if (strcmp(a, "--census-rows") == 0) {
+            nc_rows = v;
+        } else if (strcmp(a, "--census-cols") == 0) {
+            nc_cols = v;
+        } else if (strcmp(a, "--census-who") == 0) {
+            nc_who = v;
         } else if (strcmp(a, "--pick") == 0) {
             pk_path = v;
         } else if (strcmp(a, "--pick-where") == 0) {
@@ -494,6 +538,9 @@ int main(int argc, char *argv[]) {
         }
     }
     base.rng_mode = rng;
+    if (nc_path && variant != PRACH_VARIANT_NOMA_C) die("--census needs --program noma (the other programs have --xtab)");
+    if (nc_path && (pk_path || xt_path || tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--census cannot be combined with --cdf, --timeline, --sojourn, --ci, --trace, --xtab or --pick: one reduction per call");
+    if (nc_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census needs --rng philox (a NOMA.c trial in the reference's stream can finish on the host and leaves no device record)");
     if (pk_path && (xt_path || tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--pick cannot be combined with --cdf, --timeline, --sojourn, --ci, --trace or --xtab: one reduction per call");
     if (pk_path && variant == PRACH_VARIANT_NOMA_C) die("--pick needs --program beta or withnoma (NOMA.c logs no trace of a UE's cycle start)");
     if (xt_path && (tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--xtab cannot be combined with --cdf, --timeline, --sojourn, --ci or --trace: one reduction per call");
@@ -587,7 +634,7 @@ int main(int argc, char *argv[]) {
      * three numbers, per cell and twice per row */
     const reduction red_ = {cdf_path ? &cdf_spec : NULL, tl_path ? &tl_spec : NULL, sj_path ? &sj_spec : NULL, sj_path ? sj_path : tl_path ? tl_path : cdf_path,
                             sj_path ? 64 * ((size_t)sj_rows * ((size_t)sj_bins + 2) + 1) + 1
-                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
     reduction red_ci = red_;
     /* the trace's bins cover maxTime */
     const int tr_bins = (prach_max_time(&base) + tr_bin_ms - 1) / tr_bin_ms;
@@ -604,6 +651,18 @@ int main(int argc, char *argv[]) {
         if (!xtab_axis(xt_cols, prach_max_time(&base), &xt_spec.col_field, &xt_spec.col_width, &xt_spec.col_bins)) die("--xtab-cols FIELD[:WIDTH[:BINS]]: a field of the menu, a width of at least 1, 1 to 65536 bins");
         if ((uint64_t)npts * xt_cells(&xt_spec) > (1ull << 24)) die("--xtab: too many cells");
         red_ci.xt = &xt_spec; red_ci.path = xt_path; red_ci.text_cap = 64 * (xt_cells(&xt_spec) + 1) + 1; /* (a line: the label, two edges, a count) */
+    }
+    /* --census: the NOMA menu's axes as given, the defaults of a field where width or bins are left out */
+    prach_xtab_spec nc_spec = {0, 0, 0, 0, 0, 0, 0, npts, {0, 0}};
+    if (nc_path) {
+        nc_spec.who = strcmp(nc_who, "served") == 0 ? PRACH_NOMA_SERVED : strcmp(nc_who, "pending") == 0 ? PRACH_NOMA_PENDING : strcmp(nc_who, "dropped") == 0 ? PRACH_NOMA_DROPPED
+                      : strcmp(nc_who, "arrived") == 0 ? (PRACH_NOMA_SERVED | PRACH_NOMA_PENDING | PRACH_NOMA_DROPPED)
+                      : strcmp(nc_who, "all") == 0 ? (PRACH_NOMA_SERVED | PRACH_NOMA_PENDING | PRACH_NOMA_DROPPED | PRACH_NOMA_IDLE) : 0;
+        if (!nc_spec.who) die("--census-who served|pending|dropped|arrived|all");
+        if (!noma_axis(nc_rows, prach_max_time(&base), &nc_spec.row_field, &nc_spec.row_width, &nc_spec.row_bins)) die("--census-rows FIELD[:WIDTH[:BINS]]: a field of the NOMA menu, a width of at least 1, 1 to 65536 bins");
+        if (!noma_axis(nc_cols, prach_max_time(&base), &nc_spec.col_field, &nc_spec.col_width, &nc_spec.col_bins)) die("--census-cols FIELD[:WIDTH[:BINS]]: a field of the NOMA menu, a width of at least 1, 1 to 65536 bins");
+        if ((uint64_t)npts * xt_cells(&nc_spec) > (1ull << 24)) die("--census: too many cells");
+        red_ci.nc = &nc_spec; red_ci.path = nc_path; red_ci.text_cap = 64 * (xt_cells(&nc_spec) + 1) + 1; /* (a line: the label, two edges, a count) */
     }
     if (ci_path) { /* --ci: the rows of the whole grid, filled by the workers */
         red_ci.sm = &ci_spec;

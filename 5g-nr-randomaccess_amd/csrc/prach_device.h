@@ -261,6 +261,17 @@ struct ColumnsOut { int *data; unsigned long long stride; const unsigned long lo
 extern "C" int prach_internal_columns_spec_ok(const prach_columns_spec *spec); // prach_host.c
 hipError_t launch_columns_kernel(const TimelineJob *jobs, int njobs, int workgroups, const prach_columns_spec &spec, ColumnsOut out, hipStream_t stream); // spec: a valid one
 
+// prach_noma_census.hip: the census and the columns of a launch's accepted NOMA.c trials over THE NOMA MENU of include/prach.h (prach_run_trials_noma_census,
+// prach_run_trials_noma_columns, _device).  Jobs, tile, workgroup, table paths and column layout are those of prach_xtab.hip and prach_columns.hip above; NOMA
+// has four classes, so a group's scalar row and a trial's count one more.
+constexpr int NC_SCALARS = 16, NC_SUMS = 8, NC_MAXIMA = 2; // per group: idle, served, dropped, pending, selected, binned, row_sum, col_sum | row_max + 1, col_max + 1 (0: nothing binned) | 6 spare
+constexpr int NCL_SCALARS = 4, NCL_SUMS = 4;               // per trial: idle, served, dropped, pending
+extern "C" int prach_internal_noma_census_spec_ok(const prach_xtab_spec *spec);     // prach_host.c
+extern "C" int prach_internal_noma_columns_spec_ok(const prach_columns_spec *spec); // prach_host.c
+hipError_t launch_noma_census_kernel(const TimelineJob *jobs, int njobs, int workgroups, XtabAxes ax, int scheme, XtabOut out, hipStream_t stream); // ax: a valid spec's
+int noma_census_copy_words(); // LDS words that the per-wavefront copies of a census table take at most
+hipError_t launch_noma_columns_kernel(const TimelineJob *jobs, int njobs, int workgroups, const prach_columns_spec &spec, ColumnsOut out, hipStream_t stream); // spec: a valid one
+
 // prach_trace.hip: the per-subframe preamble trace of a launch's accepted trials (prach_run_trials_trace).  One job per trial: the rows the simulation kernel
 // wrote through TrialDev::trace, for the subframes [0, steps).  A workgroup reduces one tile of TR_TILE consecutive subframes of one trial, 16 bytes per lane
 // and load.  A tile covers at most TR_TILE consecutive bins (bin = t / bin_ms): scheme 1 adds them up in an LDS window of 64-bit counters anchored at the

@@ -427,13 +427,13 @@ static int noma_device_activation(prach_engine *e, const TrialDev *dparams, cons
     return PRACH_OK;
 }
 
-// What a call reduces on the device next to its results (prach_run_trials_dist, _timeline, _sojourn, _summary, _trace, _xtab, _pick, _columns).  The call's device buffer is a
+// What a call reduces on the device next to its results (prach_run_trials_dist, _timeline, _sojourn, _summary, _trace, _xtab, _pick, _columns, _noma_census, _noma_columns).  The call's device buffer is a
 // row of parts, [ngroups][words] 64-bit counters each: the arrays the caller gets as they are, one per part, then the scalars the kernel keeps per group,
 // which the engine unpacks into the caller's per-group structs.  Every launch of the call gets one job per trial it finished, and the kind's kernel behind
 // the simulation kernel.  What differs between the kinds is stated ONCE per kind: a block of functions behind CallCtx and its row of RED_KINDS.  The generic
 // code (reduction_begin, run_group, reduction_end, run_trials_impl) walks that row and never asks which kind it has; a new kind is an enumerator, a block and
 // a row.
-enum class Red { dist, timeline, sojourn, summary, trace, xtab, pick, columns };
+enum class Red { dist, timeline, sojourn, summary, trace, xtab, pick, columns, noma_census, noma_columns };
 constexpr int RED_MAX_PARTS = 6;
 struct Reduction {
     Red kind;
@@ -504,7 +504,12 @@ template <class T> const T &spec_of(const Reduction &r) { return *static_cast<co
 template <class T> T &group_of(const Reduction &r, size_t g) { return static_cast<T *>(r.groups)[g]; }
 // the caller's struct of a group before anything ran: zeros, and -1 where a maximum over nothing stands
 template <class T, int64_t T::*...MAX> void empty_group(const Reduction &r, size_t g, const prach_cfg *) { T &t = group_of<T>(r, g); t = T{}; ((t.*MAX = -1), ...); }
-int subframes_run(const JobSrc &s) { return (int)std::min<unsigned long long>(s.dr.steps, (unsigned long long)prach_max_time(&s.c)); }
+// prach_result.steps of a finished trial: what the kernel counted, except where every UE of a NOMA.c trial succeeded — NOMA.c:707-710 breaks behind the last
+// success, prach::noma_kernel sees that only at a slot head (or not at all before `stop`), and dbg[0] holds the latest success subframe + 1
+unsigned long long steps_of(const prach_cfg &c, const DevResult &dr) {
+    return c.variant == PRACH_VARIANT_NOMA_C && dr.nSuccess == c.nUE && dr.dbg[0] > 0 ? dr.dbg[0] : dr.steps;
+}
+int subframes_run(const JobSrc &s) { return (int)std::min<unsigned long long>(steps_of(s.c, s.dr), (unsigned long long)prach_max_time(&s.c)); } // E of include/prach.h: from prach_result.steps
 // timeline, sojourn, summary, xtab and pick read a trial's log records and the launch's own copy of its arrival schedule; STEPS (xtab, pick): E of include/prach.h in the last word
 template <bool STEPS> int fill_timeline_job(void *job, const JobSrc &s) {
     const int nslots = (prach_max_time(&s.c) + s.c.accessTime - 1) / s.c.accessTime; // (what prach_arrival_schedule fills; the table has one entry more)
@@ -694,6 +699,45 @@ int columns_unpack(const Reduction &r, CallCtx &cx, size_t k, const unsigned lon
     return PRACH_OK;
 }
 
+// noma_census: xtab's parts and jobs with the NOMA menu (prach_noma_census.hip): cells | scalars, one class more
+int noma_census_parts(const Reduction &r, size_t w[]) {
+    const prach_xtab_spec &x = spec_of<prach_xtab_spec>(r);
+    w[0] = ((size_t)x.row_bins + 1) * ((size_t)x.col_bins + 1); w[1] = NC_SCALARS;
+    return 2;
+}
+hipError_t noma_census_launch(const prach_engine *e, const Reduction &r, int njobs, int wgs, unsigned long long *const *d) {
+    const prach_xtab_spec &x = spec_of<prach_xtab_spec>(r);
+    return launch_noma_census_kernel(timeline_jobs(e), njobs, wgs, XtabAxes{x.who, x.row_field, x.row_width, x.row_bins, x.col_field, x.col_width, x.col_bins}, (int)e->opt_xtab_scheme, XtabOut{d[0], d[1]}, e->stream);
+}
+int noma_census_unpack(const Reduction &r, CallCtx &cx, size_t g, const unsigned long long *q) {
+    prach_noma_census &x = group_of<prach_noma_census>(r, g);
+    x.trials = cx.trials[g]; x.ues = cx.ues[g]; x.idle = q[0]; x.served = q[1]; x.dropped = q[2]; x.pending = q[3]; x.selected = q[4]; x.binned = q[5];
+    x.undefined = q[4] - q[5]; x.row_sum = q[6]; x.col_sum = q[7]; x.row_max = (int64_t)q[8] - 1; x.col_max = (int64_t)q[9] - 1;
+    return PRACH_OK;
+}
+
+// noma_columns: the columns' bulk part and table with the NOMA menu; the scalars are the four class counts of a trial
+int noma_columns_parts(const Reduction &, size_t w[]) { w[0] = NCL_SCALARS; return 1; }
+hipError_t noma_columns_launch(const prach_engine *e, const Reduction &r, int njobs, int wgs, unsigned long long *const *d) {
+    return launch_noma_columns_kernel(timeline_jobs(e), njobs, wgs, spec_of<prach_columns_spec>(r),
+                                      ColumnsOut{reinterpret_cast<int *>(e->red_bulk), e->red_bulk_pitch / 4, reinterpret_cast<const unsigned long long *>(e->red_table), d[0]}, e->stream);
+}
+void noma_columns_empty(const Reduction &r, size_t k, const prach_cfg *cfgs) {
+    prach_noma_columns &h = group_of<prach_noma_columns>(r, k);
+    h = prach_noma_columns{};
+    h.status = PRACH_ERR_INTERNAL;
+    h.nUE = cfgs[k].nUE;
+    h.offset = static_cast<const uint64_t *>(r.table)[k];
+}
+int noma_columns_unpack(const Reduction &r, CallCtx &cx, size_t k, const unsigned long long *q) { // status and nUE from the host, the counts from the one launch that accepted the trial
+    prach_noma_columns &h = group_of<prach_noma_columns>(r, k);
+    h.status = cx.results[k].status; // (everything else is still the empty header, and no launch wrote a word of a trial it did not accept)
+    if (h.status != PRACH_OK) return PRACH_OK;
+    if (cx.trials[k] != 1 || q[0] + q[1] + q[2] + q[3] != (unsigned long long)h.nUE) return h.status = PRACH_ERR_INTERNAL; // (no launch wrote this trial, or two did)
+    h.idle = (int32_t)q[0]; h.served = (int32_t)q[1]; h.dropped = (int32_t)q[2]; h.pending = (int32_t)q[3];
+    return PRACH_OK;
+}
+
 // in the order of enum class Red:           parts, job bytes, tile, job, device logs, trace rows, "fast" off, launch, empty, unpack, prach_timing field
 const RedKind RED_KINDS[] = {
     {dist_parts, sizeof(DistJob), DIST_TILE, dist_fill_job, false, false, false, dist_launch, empty_group<prach_dist, &prach_dist::delay_max>, dist_unpack, &prach_timing::dist_ms},
@@ -704,8 +748,10 @@ const RedKind RED_KINDS[] = {
     {xtab_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, xtab_launch, empty_group<prach_xtab, &prach_xtab::row_max, &prach_xtab::col_max>, xtab_unpack, &prach_timing::xtab_ms},
     {pick_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, pick_launch, pick_empty, pick_unpack, &prach_timing::pick_ms},
     {columns_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, columns_launch, columns_empty, columns_unpack, &prach_timing::columns_ms},
+    {noma_census_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, noma_census_launch, empty_group<prach_noma_census, &prach_noma_census::row_max, &prach_noma_census::col_max>, noma_census_unpack, &prach_timing::noma_census_ms},
+    {noma_columns_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, noma_columns_launch, noma_columns_empty, noma_columns_unpack, &prach_timing::noma_columns_ms},
 };
-static_assert(sizeof(RED_KINDS) / sizeof(RED_KINDS[0]) == (size_t)Red::columns + 1, "one row per kind");
+static_assert(sizeof(RED_KINDS) / sizeof(RED_KINDS[0]) == (size_t)Red::noma_columns + 1, "one row per kind");
 const RedKind &kind_of(const Reduction &r) { return RED_KINDS[(int)r.kind]; }
 
 // How a rerun's launch differs from the first one
@@ -1040,12 +1086,11 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
         r.finalSuccessUEs = dr.finalSuccess;
         r.sumTimer = dr.sumTimer;
         r.draws = dr.draws;
-        r.steps = dr.steps;
+        r.steps = steps_of(c, dr);
         e->last.group_visits += dr.visits;
         e->last.event_ues += dr.events;
         if (c.variant == PRACH_VARIANT_NOMA_C && dr.nSuccess == c.nUE && dr.dbg[0] > 0) { // all UEs succeeded: NOMA.c:707-710 breaks there
-            r.time_exit = (int32_t)dr.dbg[0] - 1;
-            r.steps = dr.dbg[0];
+            r.time_exit = (int32_t)dr.dbg[0] - 1; // (r.steps: steps_of above)
         }
         { int rc = print_launch_diagnostics(e, c, dr, L, A, G, noma); if (rc != PRACH_OK) return rc; }
         if (batch && dr.status == PRACH_ERR_INTERNAL && (dr.hard_error == 5 || dr.hard_error == 8 || dr.hard_error == 9) && !o.full_calendars) cal_overflow.push_back(idx[k]);
@@ -1609,7 +1654,7 @@ int prach_run_trials_timeline(prach_engine *e, const prach_cfg *cfgs, int n, pra
     if (!cfgs || !results || n <= 0 || !spec || !tl || !arrivals || !success || !sojourn_sum || !timer_sum || !done) return PRACH_ERR_ARG;
     if (spec->bins < 1 || spec->bins > PRACH_TIMELINE_MAX_BINS || spec->bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
     if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
-    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
+    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c has a menu of its own: include/prach.h)
     if (5 * (uint64_t)spec->ngroups * (uint64_t)spec->bins > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
     const Reduction red{.kind = Red::timeline, .group = group, .ngroups = spec->ngroups, .out = {arrivals, success, sojourn_sum, timer_sum, done}, .spec = spec, .groups = tl};
@@ -1626,7 +1671,7 @@ int prach_run_trials_sojourn(prach_engine *e, const prach_cfg *cfgs, int n, prac
     if (spec->arrival_bins < 1 || spec->arrival_bins > PRACH_SOJOURN_MAX_ARRIVAL_BINS || spec->arrival_bin_ms < 1 || spec->delay_bins < 1 ||
         spec->delay_bins > PRACH_SOJOURN_MAX_DELAY_BINS || spec->delay_bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
     if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
-    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
+    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c has a menu of its own: include/prach.h)
     if ((uint64_t)spec->ngroups * (uint64_t)spec->arrival_bins * ((uint64_t)spec->delay_bins + 2) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
     const Reduction red{.kind = Red::sojourn, .group = group, .ngroups = spec->ngroups, .out = {hist, row_arrived, row_delay_overflow}, .spec = spec, .groups = sj};
@@ -1639,7 +1684,7 @@ int prach_run_trials_summary(prach_engine *e, const prach_cfg *cfgs, int n, prac
     if (!cfgs || !results || n <= 0 || !spec || !rows) return PRACH_ERR_ARG;
     if (spec->nq < 1 || spec->nq > PRACH_SUMMARY_MAX_Q || spec->reserved[0] || spec->reserved[1] || spec->reserved[2]) return PRACH_ERR_ARG;
     for (int l = 0; l < spec->nq; l++) if (spec->permille[l] < 1 || spec->permille[l] > 1000) return PRACH_ERR_ARG;
-    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
+    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c has a menu of its own: include/prach.h)
     if (!e) return PRACH_ERR_ARG;
     static_assert(SM_MAX_VALUE == 65535, "prach_summary_max_value (prach_host.c) states the kernel's bound");
     const Reduction red{.kind = Red::summary, .group = nullptr, .ngroups = n, .out = {}, .spec = spec, .groups = rows};
@@ -1672,7 +1717,7 @@ int prach_run_trials_xtab(prach_engine *e, const prach_cfg *cfgs, int n, prach_r
     if (spec->who <= 0 || (spec->who & ~(PRACH_XTAB_SERVED | PRACH_XTAB_UNSERVED | PRACH_XTAB_IDLE)) != 0 || !axis_ok(spec->row_field, spec->row_width, spec->row_bins) ||
         !axis_ok(spec->col_field, spec->col_width, spec->col_bins) || spec->ngroups < 1 || spec->reserved[0] != 0 || spec->reserved[1] != 0) return PRACH_ERR_ARG;
     if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
-    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
+    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c has a menu of its own: include/prach.h)
     if ((uint64_t)spec->ngroups * ((uint64_t)spec->row_bins + 1) * ((uint64_t)spec->col_bins + 1) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
     const Reduction red{.kind = Red::xtab, .group = group, .ngroups = spec->ngroups, .out = {cells}, .spec = spec, .groups = xt};
@@ -1683,18 +1728,43 @@ int prach_run_trials_pick(prach_engine *e, const prach_cfg *cfgs, int n, prach_r
                           prach_pick *picks, prach_pick_row *rows) {
     // (spec and variants are judged first: what they ask for does not depend on a device)
     if (!cfgs || !results || n <= 0 || !spec || !picks || !rows || !prach_internal_pick_spec_ok(spec)) return PRACH_ERR_ARG;
-    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
+    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c has a menu of its own: include/prach.h)
     if ((uint64_t)n * ((uint64_t)spec->k * PK_ROW_WORDS + PK_SCALARS) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
     const Reduction red{.kind = Red::pick, .group = nullptr, .ngroups = n, .out = {reinterpret_cast<uint64_t *>(rows)}, .spec = spec, .groups = picks};
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
+// a trial the NOMA menu's device calls take: NOMA.c with Philox (in the reference's stream a trial can finish on the host slot by slot and leave no device record)
+static bool noma_device_cfg(const prach_cfg &c) { return c.variant == PRACH_VARIANT_NOMA_C && c.rng_mode != PRACH_RNG_GLIBC; }
+
+int prach_run_trials_noma_census(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_xtab_spec *spec,
+                                 const int32_t *group, prach_noma_census *cs, uint64_t *cells) {
+    // (spec, groups and variants are judged first: what they ask for does not depend on a device)
+    if (!cfgs || !results || n <= 0 || !spec || !cs || !cells) return PRACH_ERR_ARG;
+    if (!prach_internal_noma_census_spec_ok(spec) || spec->ngroups < 1) return PRACH_ERR_ARG;
+    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
+    for (int k = 0; k < n; k++) if (!noma_device_cfg(cfgs[k])) return PRACH_ERR_UNSUPPORTED;
+    if ((uint64_t)spec->ngroups * ((uint64_t)spec->row_bins + 1) * ((uint64_t)spec->col_bins + 1) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
+    if (!e) return PRACH_ERR_ARG;
+    const Reduction red{.kind = Red::noma_census, .group = group, .ngroups = spec->ngroups, .out = {cells}, .spec = spec, .groups = cs};
+    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
+}
+
 // what the two columns entry points share: the refusals that need no device, then the table of first rows.  dev: the destination is the caller's device memory
+// The headers of a columns call, typed: the header's type says which menu the call is over (is_noma: THE NOMA MENU, whose refusals are the census's)
+struct ColumnsHdr {
+    void *p;
+    bool is_noma;
+    ColumnsHdr(prach_columns *h) : p(h), is_noma(false) {}
+    ColumnsHdr(prach_noma_columns *h) : p(h), is_noma(true) {}
+};
 static int run_trials_columns(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_columns_spec *spec,
-                              prach_columns *hdr, void *out, uint64_t rows_cap, bool dev) {
+                              ColumnsHdr h, void *out, uint64_t rows_cap, bool dev) {
+    const bool noma = h.is_noma;
+    void *const hdr = h.p;
     // (spec, sizes and variants are judged first: what they ask for does not depend on a device)
-    if (!cfgs || !results || n <= 0 || !hdr || !out || !prach_internal_columns_spec_ok(spec)) return PRACH_ERR_ARG;
+    if (!cfgs || !results || n <= 0 || !hdr || !out || !(noma ? prach_internal_noma_columns_spec_ok(spec) : prach_internal_columns_spec_ok(spec))) return PRACH_ERR_ARG;
     std::vector<uint64_t> offset((size_t)n);
     uint64_t rows = 0;
     for (int k = 0; k < n; k++) {
@@ -1703,7 +1773,7 @@ static int run_trials_columns(prach_engine *e, const prach_cfg *cfgs, int n, pra
         rows += (uint64_t)cfgs[k].nUE;
     }
     if (rows_cap < rows) return PRACH_ERR_ARG;
-    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c logs no trace of a cycle start: include/prach.h)
+    for (int k = 0; k < n; k++) if (noma ? !noma_device_cfg(cfgs[k]) : cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (the menu is the other programs': include/prach.h)
     if (rows_cap > PRACH_COL_MAX_WORDS || (uint64_t)spec->ncols * rows_cap > PRACH_COL_MAX_WORDS) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
     if (dev) { // device memory of the engine's device, all of it: asked before the fill and before any launch
@@ -1719,7 +1789,7 @@ static int run_trials_columns(prach_engine *e, const prach_cfg *cfgs, int n, pra
             return PRACH_ERR_ARG;
         }
     }
-    Reduction red{.kind = Red::columns, .group = nullptr, .ngroups = n, .out = {}, .spec = spec, .groups = hdr};
+    Reduction red{.kind = noma ? Red::noma_columns : Red::columns, .group = nullptr, .ngroups = n, .out = {}, .spec = spec, .groups = hdr};
     (dev ? red.bulk_dev : red.bulk_host) = out;
     red.bulk_width = 4 * (size_t)rows; red.bulk_rows = rows ? (size_t)spec->ncols : 0; red.bulk_pitch = 4 * (size_t)rows_cap; red.bulk_fill = 0xff; // -1
     if (!rows) red.bulk_width = 0;
@@ -1737,6 +1807,17 @@ int prach_run_trials_columns_device(prach_engine *e, const prach_cfg *cfgs, int 
     PRACH_GUARD(return run_trials_columns(e, cfgs, n, results, ue_logs, spec, hdr, dev_out, rows_cap, true);)
 }
 
+int prach_run_trials_noma_columns(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_columns_spec *spec,
+                                  prach_noma_columns *hdr, int32_t *out, uint64_t rows_cap) {
+    PRACH_GUARD(return run_trials_columns(e, cfgs, n, results, ue_logs, spec, hdr, out, rows_cap, false);)
+}
+
+int prach_run_trials_noma_columns_device(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs,
+                                         const prach_columns_spec *spec, prach_noma_columns *hdr, void *dev_out, uint64_t rows_cap) {
+    PRACH_GUARD(return run_trials_columns(e, cfgs, n, results, ue_logs, spec, hdr, dev_out, rows_cap, true);)
+}
+
+int prach_noma_census_tile_ues(void) { return TL_TILE; }
 int prach_columns_tile_ues(void) { return TL_TILE; }
 int prach_xtab_tile_ues(void) { return TL_TILE; }
 int prach_xtab_window_words(void) { return XT_WINDOW_WORDS; }

@@ -1035,6 +1035,163 @@ int prach_columns_from_logs(const prach_columns_spec *s, const prach_cfg *cfg, u
     return PRACH_OK;
 }
 
+/* ---- the NOMA menu: census and columns of NOMA.c trials (prach_run_trials_noma_census, _noma_columns) ---- */
+
+#define NOMA_ALL_CLASSES (PRACH_NOMA_SERVED | PRACH_NOMA_PENDING | PRACH_NOMA_IDLE | PRACH_NOMA_DROPPED)
+static int noma_axis_ok(int field, int width, int bins) {
+    return field >= 0 && field < PRACH_NOMA_NFIELDS && width >= 1 && bins >= 1 && bins <= PRACH_XTAB_MAX_BINS;
+}
+/* (the engine judges a spec with these too: csrc/prach_device.h) */
+int prach_internal_noma_census_spec_ok(const prach_xtab_spec *s) {
+    return s && s->who > 0 && (s->who & ~NOMA_ALL_CLASSES) == 0 && noma_axis_ok(s->row_field, s->row_width, s->row_bins) &&
+           noma_axis_ok(s->col_field, s->col_width, s->col_bins) && s->reserved[0] == 0 && s->reserved[1] == 0;
+}
+int prach_internal_noma_columns_spec_ok(const prach_columns_spec *s) {
+    if (!s || s->ncols < 1 || s->ncols > PRACH_COL_MAX || s->reserved[0] || s->reserved[1] || s->reserved[2]) return 0;
+    for (int c = 0; c < s->ncols; c++) {
+        const int f = s->field[c];
+        if (!((f >= 0 && f < PRACH_NOMA_NFIELDS) || (f >= PRACH_COL_RAW && f < PRACH_COL_RAW + 16))) return 0;
+    }
+    return 1;
+}
+
+/* the class bit of a UE and its STATE (include/prach.h) */
+static int noma_class(const prach_ue_log *u) {
+    if (u->preambleChange == -1) return PRACH_NOMA_IDLE;
+    if (u->msg4Flag == 1) return PRACH_NOMA_SERVED;
+    return (u->failCount & 0xffff) != 0 ? PRACH_NOMA_DROPPED : PRACH_NOMA_PENDING;
+}
+static int noma_state(const prach_ue_log *u, int cls, int64_t E) {
+    if (cls == PRACH_NOMA_IDLE) return 0;
+    if (cls == PRACH_NOMA_SERVED) return 1;
+    if (cls == PRACH_NOMA_DROPPED) return 2;
+    if (u->active == 1) return u->nowBackoff > 0 ? 3 : (int64_t)u->txTime >= E ? 4 : 5;
+    if (u->active == 2) return u->connectionRequest == 0 ? 6 : 7;
+    return 8;
+}
+/* the value of a field for a UE of class cls that arrived at a; a negative value is UNDEFINED, and so is a field outside the classes it is defined for */
+static int64_t noma_value(int field, const prach_ue_log *u, int cls, int64_t a, int64_t E) {
+    const int arrived = cls != PRACH_NOMA_IDLE, served = cls == PRACH_NOMA_SERVED;
+    switch (field) {
+    case PRACH_NOMA_ONE: return 0;
+    case PRACH_NOMA_ARRIVAL: return arrived ? a : -1;
+    case PRACH_NOMA_SOJOURN: return served ? (int64_t)u->txTime + 6 - a : -1;
+    case PRACH_NOMA_COMPLETION: return served ? (int64_t)u->txTime + 6 : -1;
+    case PRACH_NOMA_TIMER: return arrived ? u->timer : -1;
+    case PRACH_NOMA_PTC: return arrived ? u->preambleTxCounter : -1;
+    case PRACH_NOMA_RETX: return arrived ? u->maxRarCounter : -1;
+    case PRACH_NOMA_MSG3FAIL: return arrived ? (int64_t)(u->failCount >> 16) : -1; /* (arithmetic shift: a negative word is undefined) */
+    case PRACH_NOMA_AGE: return arrived ? E - a : -1;
+    case PRACH_NOMA_STATE: return noma_state(u, cls, E);
+    case PRACH_NOMA_SECTOR: return arrived ? u->preambleChange : -1;
+    case PRACH_NOMA_PREAMBLE: return arrived ? u->preamble : -1;
+    default: /* LOST: a negative sojourn or timer makes it undefined, and so does a timer beyond the sojourn */
+        if (!served) return -1;
+        { const int64_t sj = (int64_t)u->txTime + 6 - a; return sj < 0 || u->timer < 0 ? -1 : sj - u->timer; }
+    }
+}
+/* the schedule of a NOMA_C cfg and E; 0: a status is in *rc */
+static int32_t *noma_schedule(const prach_cfg *cfg, int nUE, uint64_t steps, int *nslots, int64_t *E, int *rc) {
+    *rc = PRACH_ERR_ARG;
+    if (!cfg) return NULL;
+    if (cfg->variant != PRACH_VARIANT_NOMA_C) { *rc = PRACH_ERR_UNSUPPORTED; return NULL; }
+    if (prach_cfg_validate(cfg) != PRACH_OK || nUE != cfg->nUE) return NULL;
+    *nslots = (prach_max_time(cfg) + cfg->accessTime - 1) / cfg->accessTime;
+    int32_t *sched = (int32_t *)malloc(sizeof(int32_t) * (size_t)*nslots);
+    if (!sched) { *rc = PRACH_ERR_INTERNAL; return NULL; }
+    prach_arrival_schedule(cfg, sched, *nslots, NULL);
+    *E = steps < (uint64_t)prach_max_time(cfg) ? (int64_t)steps : (int64_t)prach_max_time(cfg);
+    *rc = PRACH_OK;
+    return sched;
+}
+
+/* THE DEFINITION (include/prach.h) */
+int prach_noma_census_accumulate_logs(const prach_xtab_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_noma_census *x,
+                                      uint64_t *cells) {
+    if (!prach_internal_noma_census_spec_ok(s) || !cfg || !x || !cells || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    int nslots = 0, rc;
+    int64_t E = 0;
+    int32_t *sched = noma_schedule(cfg, nUE, steps, &nslots, &E, &rc);
+    if (!sched) return rc;
+    if (x->trials == 0 && x->binned == 0) x->row_max = x->col_max = -1; /* (a zero-filled group is an empty one) */
+    int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
+    for (int i = 0; i < nUE; i++) {
+        while (slot < nslots && sched[slot] <= i) slot++;
+        const int64_t a = (int64_t)cfg->accessTime * slot;
+        const int cls = noma_class(&ue[i]);
+        if (cls == PRACH_NOMA_IDLE) x->idle++;
+        else if (cls == PRACH_NOMA_SERVED) x->served++;
+        else if (cls == PRACH_NOMA_DROPPED) x->dropped++;
+        else x->pending++;
+        if (!(cls & s->who)) continue;
+        x->selected++;
+        const int64_t rv = noma_value(s->row_field, &ue[i], cls, a, E), cv = noma_value(s->col_field, &ue[i], cls, a, E);
+        if (rv < 0 || cv < 0) { x->undefined++; continue; }
+        const int64_t rq = rv / s->row_width, cq = cv / s->col_width;
+        const size_t r = rq < s->row_bins ? (size_t)rq : (size_t)s->row_bins, c = cq < s->col_bins ? (size_t)cq : (size_t)s->col_bins;
+        cells[r * ((size_t)s->col_bins + 1) + c]++;
+        x->binned++;
+        x->row_sum += (uint64_t)rv;
+        x->col_sum += (uint64_t)cv;
+        if (rv > x->row_max) x->row_max = rv;
+        if (cv > x->col_max) x->col_max = cv;
+    }
+    free(sched);
+    x->trials++;
+    x->ues += (uint64_t)nUE;
+    return PRACH_OK;
+}
+
+void prach_noma_census_merge(const prach_xtab_spec *s, prach_noma_census *into, uint64_t *cells_into, const prach_noma_census *from, const uint64_t *cells_from) {
+    if (!prach_internal_noma_census_spec_ok(s) || !into || !cells_into || !from || !cells_from) return;
+    const int64_t ra = into->binned ? into->row_max : -1, rb = from->binned ? from->row_max : -1;
+    const int64_t ca = into->binned ? into->col_max : -1, cb = from->binned ? from->col_max : -1;
+    into->trials += from->trials; into->ues += from->ues; into->idle += from->idle; into->served += from->served; into->dropped += from->dropped;
+    into->pending += from->pending; into->selected += from->selected; into->binned += from->binned; into->undefined += from->undefined;
+    into->row_sum += from->row_sum; into->col_sum += from->col_sum;
+    into->row_max = ra > rb ? ra : rb;
+    into->col_max = ca > cb ? ca : cb;
+    const size_t n = ((size_t)s->row_bins + 1) * ((size_t)s->col_bins + 1);
+    for (size_t i = 0; i < n; i++) cells_into[i] += cells_from[i];
+}
+
+size_t prach_noma_census_format_csv(const prach_xtab_spec *s, const prach_noma_census *x, const uint64_t *cells, const char *label, char *buf, size_t cap) {
+    if (!prach_internal_noma_census_spec_ok(s) || !x || !cells || !label) return 0;
+    /* xtab's lines: only widths, bin counts and `undefined` enter them */
+    prach_xtab_spec t = *s;
+    t.who = PRACH_XTAB_SERVED; t.row_field = t.col_field = PRACH_XTAB_ONE;
+    prach_xtab u = {0};
+    u.undefined = x->undefined;
+    return prach_xtab_format_csv(&t, &u, cells, label, buf, cap);
+}
+
+/* THE DEFINITION (include/prach.h) */
+int prach_noma_columns_from_logs(const prach_columns_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, int32_t *out, uint64_t stride) {
+    if (!prach_internal_noma_columns_spec_ok(s) || !cfg || !out || nUE < 0 || (nUE > 0 && !ue) || stride < (uint64_t)nUE) return PRACH_ERR_ARG;
+    int nslots = 0, rc;
+    int64_t E = 0;
+    int32_t *sched = noma_schedule(cfg, nUE, steps, &nslots, &E, &rc);
+    if (!sched) return rc;
+    int slot = 0;
+    for (int i = 0; i < nUE; i++) {
+        while (slot < nslots && sched[slot] <= i) slot++;
+        const int64_t a = (int64_t)cfg->accessTime * slot;
+        const int cls = noma_class(&ue[i]);
+        for (int c = 0; c < s->ncols; c++) {
+            const int f = s->field[c];
+            int32_t v;
+            if (f >= PRACH_COL_RAW) v = ((const int32_t *)&ue[i])[f - PRACH_COL_RAW]; /* the log word as it is */
+            else {
+                const int64_t x = noma_value(f, &ue[i], cls, a, E);
+                v = x < 0 ? -1 : (int32_t)x; /* a negative value is UNDEFINED */
+            }
+            out[(size_t)c * (size_t)stride + (size_t)i] = v;
+        }
+    }
+    free(sched);
+    return PRACH_OK;
+}
+
 /* ---- picks: the UEs behind a count, per trial (prach_run_trials_pick) ----------------------------- */
 
 /* (the engine judges a spec with this too: csrc/prach_device.h) */

@@ -129,6 +129,10 @@ typedef struct prach_timing {
     int32_t trial_kernel_reruns; /* of fallback_trials: trials that were (also) rerun on the one-workgroup, index-ordered trial_kernel */
     int32_t noma_host_ues;       /* NOMA_C, Philox: UEs of the device-built activeUE table that the host recomputed with its libm (a value inside the
                                     device math library's error band of a rounding / comparison boundary: ~1e-6 of the UEs) */
+    double noma_census_ms;       /* HIP-event time of the NOMA census kernel launches (prach_run_trials_noma_census) of the last call; 0 in every other call (a
+                                    census call leaves every other *_ms of a reduction 0) */
+    double noma_columns_ms;      /* HIP-event time of the NOMA columns kernel launches (prach_run_trials_noma_columns, prach_run_trials_noma_columns_device) of the
+                                    last call; 0 in every other call (such a call leaves every other *_ms of a reduction 0) */
     double columns_ms;           /* HIP-event time of the columns kernel launches (prach_run_trials_columns, prach_run_trials_columns_device) of the last call; 0 in
                                     every other call (a columns call leaves every other *_ms of a reduction 0) */
     double pick_ms;              /* HIP-event time of the pick kernel launches (prach_run_trials_pick) of the last call; 0 in every other call (a pick call
@@ -207,8 +211,9 @@ int prach_run_trials_dist(prach_engine *, const prach_cfg *cfgs, int n, prach_re
  *   done[b]         successful UEs with c(i) in bin b   (c(i) can exceed time_exit by up to 6)
  * A UE whose bin index is >= bins counts in the scalars and in the matching overflow counter, and in no bin of that axis.  Integers only: device, host,
  * forked workers and ranks merge exactly in any order.
- * PRACH_VARIANT_BETA_C and PRACH_VARIANT_WITHNOMA_C only, in both RNG modes: NOMA.c zeroes its timer without any logged trace of the cycle start (its
- * log has no txTime of the successful Msg3), so a NOMA_C cfg is PRACH_ERR_UNSUPPORTED, before anything is launched. */
+ * PRACH_VARIANT_BETA_C and PRACH_VARIANT_WITHNOMA_C only, in both RNG modes: a NOMA_C cfg is PRACH_ERR_UNSUPPORTED, before anything is launched.  NOMA.c
+ * does log the txTime of the successful Msg3 (c(i) = txTime + 6 holds there too), but its records tell arrival by the sector, have a fourth outcome and give
+ * other meanings to three words: this menu must not be let loose on them.  NOMA.c has a menu of its own, the NOMA block below (prach_run_trials_noma_census). */
 #define PRACH_TIMELINE_MAX_BINS 65536      /* Uniform traffic at 1 ms: 60 006 bins */
 
 typedef struct prach_timeline_spec {
@@ -469,6 +474,97 @@ int prach_run_trials_columns_device(prach_engine *, const prach_cfg *cfgs, int n
  * PRACH_ERR_UNSUPPORTED: a NOMA_C cfg. */
 int prach_columns_from_logs(const prach_columns_spec *, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, int32_t *out, uint64_t stride);
 int prach_columns_tile_ues(void); /* UEs of one trial that one workgroup of prach::columns_kernel writes (tests place sizes around it) */
+
+/* THE NOMA MENU: NOMA.c's own outcome census and per-UE columns, on the device.  PRACH_VARIANT_NOMA_C trials only; the menu above stays what it is and keeps
+ * refusing them.  Everything comes from the 64-byte log record of a NOMA.c trial, the arrival schedule and the trial's `steps`.
+ *   a(i)  the timeline block's arrival: the same schedule and the same search
+ *   E     min(prach_result.steps, maxTime)
+ *   c(i)  txTime + 6.  A NOMA.c success happens in the subframe time == txTime, leaves txTime alone and adds 6 to `timer` (NOMA.c:499-546), and `timer` was
+ *         zeroed at activation and at a Msg3 timeout: c(i) - timer is the start of the last cycle, as in the other two programs.
+ * What differs: `active` cannot tell an idle UE from a served one (both log 0), so ARRIVED is `preambleChange != -1` (NOMA.c logs the sector there); a UE whose
+ * msg1ReTx reaches maxMsg1ReTx is DROPPED for good (RaFailed); failCount = RaFailed | msg3Faile << 16, maxRarCounter = msg1ReTx, connectionRequest = msg3Wait.
+ * CLASSES, by precedence, the bits of `who`:
+ *   PRACH_NOMA_IDLE     preambleChange == -1
+ *   PRACH_NOMA_SERVED   arrived and msg4Flag == 1
+ *   PRACH_NOMA_DROPPED  arrived, not served, (failCount & 0xffff) != 0
+ *   PRACH_NOMA_PENDING  arrived, neither served nor dropped
+ * FIELDS: the value of UE i, or UNDEFINED outside the classes named:
+ *    0 ONE         0                                        every UE
+ *    1 ARRIVAL     a(i)                                     arrived
+ *    2 SOJOURN     c(i) - a(i)                              served
+ *    3 COMPLETION  c(i)                                     served
+ *    4 TIMER       logged timer (a dropped UE logs 0)       arrived
+ *    5 PTC         logged preambleTxCounter (nTxPreamble)   arrived
+ *    6 RETX        logged maxRarCounter (msg1ReTx)          arrived
+ *    7 MSG3FAIL    failCount >> 16 (msg3Faile)              arrived
+ *    8 AGE         E - a(i)                                 arrived
+ *    9 STATE       0 idle, 1 served, 2 dropped, then for the pending: 3 active == 1 && nowBackoff > 0 (in a backoff), 4 active == 1 && nowBackoff <= 0 &&
+ *                  txTime >= E (its transmit subframe is ahead), 5 active == 1 && nowBackoff <= 0 && txTime < E (STRANDED: its transmit subframe has
+ *                  passed), 6 active == 2 && connectionRequest == 0 (Msg3 pending), 7 active == 2 && connectionRequest != 0 (waiting out a Msg3
+ *                  timeout), 8 anything else (no trial produces it)                                         every UE
+ *   10 SECTOR      logged preambleChange, 0..5              arrived
+ *   11 PREAMBLE    logged preamble                          arrived
+ *   12 LOST        SOJOURN - TIMER: arrival to the start of the last cycle; 0 iff the UE never started over   served
+ *                  (undefined where SOJOURN or TIMER is, and where the difference is negative)
+ * STATE 5 IS FINAL.  NOMA.c moves a UE with active == 1 in two places, the collision detection (NOMA.c:325-447, the oracle's noma_oracle.c:203) and
+ * msg2Results (:325 there); both ask txTime == time + 1.  The Msg3 step (:331) asks txTime == time.  All three need txTime >= time, and time only grows: a UE
+ * with active == 1, nowBackoff <= 0 and txTime below the current subframe is never touched again, only its timer ticks to the end of the run.  NOMA.c reports
+ * no such UE; the backoff's off-by-one makes them.
+ * ONE RULE as in the xtab block: a NEGATIVE value is UNDEFINED, nothing is refused, nothing is clipped.  Every menu value of a trial fits int32
+ * (csrc/prach_noma_menu.h states the bounds).  The channel gain is NOT in the menu: with Philox it is available per UE through prach_noma_activation_table,
+ * in the reference's stream it exists only inside the launch.
+ * PRACH_RNG_GLIBC trials of NOMA_C can finish on the host slot by slot and leave no device record: the device calls below refuse them, and
+ * prach_run_trials with logs plus the host definitions serves them. */
+#define PRACH_NOMA_SERVED  1
+#define PRACH_NOMA_PENDING 2
+#define PRACH_NOMA_IDLE    4
+#define PRACH_NOMA_DROPPED 8
+enum { PRACH_NOMA_ONE = 0, PRACH_NOMA_ARRIVAL, PRACH_NOMA_SOJOURN, PRACH_NOMA_COMPLETION, PRACH_NOMA_TIMER, PRACH_NOMA_PTC, PRACH_NOMA_RETX, PRACH_NOMA_MSG3FAIL,
+       PRACH_NOMA_AGE, PRACH_NOMA_STATE, PRACH_NOMA_SECTOR, PRACH_NOMA_PREAMBLE, PRACH_NOMA_LOST, PRACH_NOMA_NFIELDS };
+
+typedef struct prach_noma_census {            /* one per group */
+    uint64_t trials;                          /* trials accumulated (status PRACH_OK) */
+    uint64_t ues;                             /* sum of their nUE */
+    uint64_t idle, served, dropped, pending;  /* the four classes, counted regardless of `who`: idle + served + dropped + pending == ues */
+    uint64_t selected;                        /* UEs whose class is in `who` */
+    uint64_t binned, undefined;               /* ... of which: in a cell (overflow cells included) / with an undefined row or column value */
+    uint64_t row_sum, col_sum;                /* sums of the two values over the binned UEs, unbinned */
+    int64_t  row_max, col_max;                /* the largest of each over the binned UEs; -1 if binned == 0 */
+} prach_noma_census;
+
+/* prach_run_trials plus the NOMA census: the contract of prach_run_trials_xtab word for word (groups, OVERWRITTEN outputs, a rerun trial counted once), with a
+ * prach_xtab_spec whose `who` is PRACH_NOMA_* class bits and whose fields are PRACH_NOMA_* ids; the cells are laid out as xtab's are: sum(cells) + undefined
+ * == selected.  prach::noma_census_kernel (csrc/prach_noma_census.hip) reduces the log records on the device; engine option "xtab_scheme" applies.
+ * PRACH_ERR_ARG: the argument cases of prach_run_trials_xtab, with NOMA's ids and bits;
+ * PRACH_ERR_UNSUPPORTED, before anything is launched: any cfg that is not NOMA_C; any NOMA_C cfg with rng_mode == PRACH_RNG_GLIBC; ngroups * (row_bins + 1) *
+ * (col_bins + 1) > 2^27 words.  PRACH_FLAG_NOMA_NONSECTOR is accepted. */
+int prach_run_trials_noma_census(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_xtab_spec *spec,
+                                 const int32_t *group, prach_noma_census *cs, uint64_t *cells);
+
+/* Per-UE columns of NOMA_C trials: the contract of prach_run_trials_columns and prach_run_trials_columns_device (layout, rows_cap, -1 for undefined,
+ * PRACH_COL_RAW + w, the device-pointer check, refusals before anything is written) with PRACH_NOMA_* field ids; the refusals are the census's.
+ * prach::noma_columns_kernel (csrc/prach_noma_census.hip) writes them. */
+typedef struct prach_noma_columns {           /* one per TRIAL */
+    int32_t status, nUE; uint64_t offset;     /* first row of this trial: the sum of cfgs[j].nUE over j < k, whatever their status */
+    int32_t idle, served, dropped, pending;   /* the four classes, counted by the kernel: their sum is nUE; 0 unless status is PRACH_OK */
+} prach_noma_columns;
+int prach_run_trials_noma_columns(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs,
+                                  const prach_columns_spec *spec, prach_noma_columns *hdr, int32_t *out, uint64_t rows_cap);
+int prach_run_trials_noma_columns_device(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs,
+                                         const prach_columns_spec *spec, prach_noma_columns *hdr, void *dev_out, uint64_t rows_cap);
+
+/* NOMA menu, host side (no device needed; both RNG modes).  cs and cells [row_bins + 1][col_bins + 1]: ONE group.
+ * prach_noma_census_accumulate_logs ADDS one trial's per-UE log to a group: THE DEFINITION prach::noma_census_kernel equals, integer for integer.  steps is the
+ * trial's prach_result.steps.  PRACH_ERR_UNSUPPORTED: a cfg that is not NOMA_C.  PRACH_ERR_ARG: a bad spec or cfg, nUE != cfg->nUE (no log content is refused).
+ * _merge adds counts and sums and takes the maxima; _format_csv writes prach_xtab_format_csv's lines.  prach_xtab_quantile reads the cells of a census with a
+ * spec of the same widths and bin counts. */
+int prach_noma_census_accumulate_logs(const prach_xtab_spec *, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_noma_census *cs,
+                                      uint64_t *cells);
+void prach_noma_census_merge(const prach_xtab_spec *, prach_noma_census *into, uint64_t *cells_into, const prach_noma_census *from, const uint64_t *cells_from);
+size_t prach_noma_census_format_csv(const prach_xtab_spec *, const prach_noma_census *, const uint64_t *cells, const char *label, char *buf, size_t cap);
+int prach_noma_census_tile_ues(void); /* UEs of one trial that one workgroup of prach::noma_census_kernel reduces (tests place sizes around it) */
+/* THE DEFINITION prach::noma_columns_kernel equals, integer for integer: prach_columns_from_logs with the NOMA menu.  PRACH_ERR_UNSUPPORTED: not a NOMA_C cfg. */
+int prach_noma_columns_from_logs(const prach_columns_spec *, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, int32_t *out, uint64_t stride);
 
 /* Per-subframe preamble trace per trial group, recorded by the simulation kernels WHILE THEY RUN and reduced on the device: how many preambles were used,
  * decoded and collided in each stretch of the simulation — the quantities TR 37.868's collision probability is defined on.  Unlike the four reductions above
