@@ -55,7 +55,7 @@ class PrachTiming(C.Structure):
                 ("launches", C.c_int32), ("workgroups", C.c_int32), ("updates", C.c_uint64),
                 ("cluster_size", C.c_int32), ("resident_limit", C.c_int32), ("fallback_trials", C.c_int32), ("spin_timeouts", C.c_int32),
                 ("rec_mode", C.c_int32), ("xcd_packed", C.c_int32), ("group_visits", C.c_uint64), ("event_ues", C.c_uint64),
-                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("noma_census_ms", C.c_double), ("noma_columns_ms", C.c_double), ("columns_ms", C.c_double), ("pick_ms", C.c_double), ("xtab_ms", C.c_double), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
+                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("noma_summary_ms", C.c_double), ("noma_pick_ms", C.c_double), ("noma_census_ms", C.c_double), ("noma_columns_ms", C.c_double), ("columns_ms", C.c_double), ("pick_ms", C.c_double), ("xtab_ms", C.c_double), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
                 ("sojourn_ms", C.c_double)]
 
 
@@ -487,13 +487,15 @@ class Pick:
 
     def __init__(self, n, where=(), order="index", key=None, k=16, who=XTAB_WHO["all"]):
         import numpy as np
-        self.where = tuple((_xtab_field(f), int(lo), int(hi)) for f, lo, hi in where)
+        self.where = tuple((self._field(f), int(lo), int(hi)) for f, lo, hi in where)
         self.order = PICK_ORDERS[order] if isinstance(order, str) else int(order)
-        self.key = 0 if key is None else _xtab_field(key)
+        self.key = 0 if key is None else self._field(key)
         self.k, self.who = int(k), int(who)
         self.headers = np.zeros(int(n), dtype=pick_header_dtype())
         self.headers["threshold"] = -1
         self.rows = np.zeros((int(n), max(self.k, 1)), dtype=pick_row_dtype())
+
+    _field = staticmethod(_xtab_field)  # a field name or id of this pick's menu
 
     def spec(self):
         sp = PrachPickSpec()
@@ -630,8 +632,8 @@ class NomaCensus(_Reduction):
 
     def cell_clauses(self, row_bin, col_bin):
         """The two clauses (field, lo, hi) that describe exactly the UEs counted in cell [row_bin, col_bin] — NOMA field ids; the last bin of an axis is its
-        overflow bin, which has no upper edge (hi is the largest int32).  There is no NOMA pick to hand them to: they filter the columns of
-        Engine.run_trials_noma_columns (lo <= column <= hi)."""
+        overflow bin, which has no upper edge (hi is the largest int32).  They are the ``where`` of Engine.run_trials_noma_pick, whose ``matched`` is then the
+        cell (with the census's ``who``), and they filter the columns of Engine.run_trials_noma_columns (lo <= column <= hi)."""
         out = []
         for (f, w, b), bin_ in ((self.rows, int(row_bin)), (self.cols, int(col_bin))):
             if not 0 <= bin_ <= b:
@@ -643,6 +645,91 @@ class NomaCensus(_Reduction):
         """Xtab.quantile on this census's cells: prach_xtab_quantile reads only widths and bin counts, so it gets an xtab spec with those."""
         sp = PrachXtabSpec(XTAB_SERVED, 0, self.rows[1], self.rows[2], 0, self.cols[1], self.cols[2], self.ngroups, (C.c_int32 * 2)(0, 0))
         return int(lib().prach_xtab_quantile(C.byref(sp), self._rows(g)[0], int(row), float(q)))
+
+
+NOMA_SUMMARY_MAX_FIELDS = 4
+NOMA_SUMMARY_FIXED_METRICS = ("served_ratio", "dropped_ratio", "pending_ratio", "restart_ratio")
+
+
+class PrachNomaSummarySpec(C.Structure):
+    _fields_ = [("who", C.c_int32), ("nfields", C.c_int32), ("field", C.c_int32 * NOMA_SUMMARY_MAX_FIELDS), ("nq", C.c_int32), ("permille", C.c_int32 * SUMMARY_MAX_Q),
+                ("reserved", C.c_int32 * 2)]
+
+
+class PrachNomaTrialSummary(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("status", "nUE", "idle", "served", "dropped", "pending", "selected", "restarted", "range_errors", "reserved")] + \
+               [("n", C.c_int32 * NOMA_SUMMARY_MAX_FIELDS), ("sum", C.c_int64 * NOMA_SUMMARY_MAX_FIELDS), ("max", C.c_int32 * NOMA_SUMMARY_MAX_FIELDS),
+                ("q", (C.c_int32 * SUMMARY_MAX_Q) * NOMA_SUMMARY_MAX_FIELDS)]
+
+
+def noma_summary_row_dtype():
+    """prach_noma_trial_summary as a numpy structured dtype (the C layout: 232 bytes)."""
+    import numpy as np
+    dt = np.dtype([(n, np.int32) for n in ("status", "nUE", "idle", "served", "dropped", "pending", "selected", "restarted", "range_errors", "reserved")] +
+                  [("n", np.int32, (NOMA_SUMMARY_MAX_FIELDS,)), ("sum", np.int64, (NOMA_SUMMARY_MAX_FIELDS,)), ("max", np.int32, (NOMA_SUMMARY_MAX_FIELDS,)),
+                   ("q", np.int32, (NOMA_SUMMARY_MAX_FIELDS, SUMMARY_MAX_Q))], align=True)
+    assert dt.itemsize == C.sizeof(PrachNomaTrialSummary) == 232
+    return dt
+
+
+class NomaSummary:
+    """One row per NOMA.c trial (include/prach.h, prach_noma_trial_summary): ``rows`` is a numpy structured array (noma_summary_row_dtype) in trial order;
+    ``fields`` the up to four fields of NOMA_FIELD_NAMES behind n[x], sum[x], max[x] and q[x][level], ``permille`` the levels, ``who`` the classes whose UEs
+    enter (bits NOMA_SERVED | NOMA_PENDING | NOMA_IDLE | NOMA_DROPPED)."""
+
+    def __init__(self, n, fields=("sojourn", "timer", "ptc", "lost"), who=NOMA_WHO["served"], permille=(500, 950, 990)):
+        import numpy as np
+        self.field_ids = tuple(noma_field(f) for f in fields)
+        self.who, self.permille = int(who), tuple(int(m) for m in permille)
+        self.rows = np.zeros(int(n), dtype=noma_summary_row_dtype())
+
+    def spec(self):
+        sp = PrachNomaSummarySpec()
+        sp.who, sp.nfields, sp.nq = self.who, len(self.field_ids), len(self.permille)  # (a count the library refuses stays visible to it)
+        for x, f in enumerate(self.field_ids[:NOMA_SUMMARY_MAX_FIELDS]):
+            sp.field[x] = f
+        for l, m in enumerate(self.permille[:SUMMARY_MAX_Q]):
+            sp.permille[l] = m
+        return sp
+
+    @property
+    def metric_names(self):
+        names = [NOMA_FIELD_NAMES[f] if 0 <= f < len(NOMA_FIELD_NAMES) else str(f) for f in self.field_ids]
+        return list(NOMA_SUMMARY_FIXED_METRICS) + [n + suffix for n in names for suffix in ["_mean"] + [f"_p{m}" for m in self.permille]]
+
+    def _rows_ptr(self):
+        return self.rows.ctypes.data_as(C.POINTER(PrachNomaTrialSummary))
+
+    def stats(self, groups=None, ngroups=None):
+        """Mean and spread per trial group (prach_noma_summary_stats): a structured array [ngroups, 4 + nfields (1 + nq)] of n, mean, sd, sem, min, max, the
+        metrics in the order of metric_names.  groups: the group of every row (None: all rows are one group)."""
+        import numpy as np
+        ng = 1 if groups is None and ngroups is None else _ngroups(len(self.rows), groups, ngroups)
+        out = np.zeros((ng, len(self.metric_names)), dtype=summary_stat_dtype())
+        sp = self.spec()
+        gp = None if groups is None else (C.c_int32 * len(self.rows))(*[int(g) for g in groups])
+        rc = lib().prach_noma_summary_stats(C.byref(sp), self._rows_ptr(), len(self.rows), gp, ng, out.ctypes.data_as(C.POINTER(PrachStat)))
+        if rc != OK:
+            raise PrachError(rc, "(prach_noma_summary_stats)")
+        return out
+
+
+def noma_pick_parse_clause(text):
+    """FIELD:LO:HI of the drivers as (field id, lo, hi), FIELD of the NOMA menu."""
+    parts = text.split(":")
+    if len(parts) != 3 or parts[0].lower() not in NOMA_FIELD_NAMES:
+        raise ValueError(f"a clause is FIELD:LO:HI, FIELD one of {', '.join(NOMA_FIELD_NAMES)}: {text!r}")
+    return NOMA_FIELD_NAMES.index(parts[0].lower()), int(parts[1]), int(parts[2])
+
+
+class NomaPick(Pick):
+    """The picks of ``n`` NOMA.c trials (include/prach.h, prach_run_trials_noma_pick): Pick's headers and rows over the NOMA menu.  where: up to four clauses
+    (field, lo, hi), a field of NOMA_FIELD_NAMES; order and key as in Pick, the key a field of NOMA_FIELD_NAMES; who: bits NOMA_SERVED | NOMA_PENDING |
+    NOMA_IDLE | NOMA_DROPPED."""
+    _field = staticmethod(noma_field)
+
+    def __init__(self, n, where=(), order="index", key=None, k=16, who=NOMA_WHO["all"]):
+        super().__init__(n, where, order, key, k, who)
 
 
 def noma_columns_header_dtype():
@@ -800,6 +887,16 @@ def lib():
         L.prach_run_trials_noma_columns.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachColumnsSpec),
                                                     C.POINTER(PrachNomaColumns), C.c_void_p, C.c_uint64]
         L.prach_run_trials_noma_columns_device.argtypes = L.prach_run_trials_noma_columns.argtypes
+        L.prach_run_trials_noma_summary.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachNomaSummarySpec),
+                                                    C.POINTER(PrachNomaTrialSummary)]
+        L.prach_noma_summary_from_logs.argtypes = [C.POINTER(PrachNomaSummarySpec), C.POINTER(PrachCfg), C.c_uint64, C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachNomaTrialSummary)]
+        L.prach_noma_summary_stats.argtypes = [C.POINTER(PrachNomaSummarySpec), C.POINTER(PrachNomaTrialSummary), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(PrachStat)]
+        L.prach_noma_summary_format_csv.argtypes = [C.POINTER(PrachNomaSummarySpec), C.POINTER(PrachStat), C.c_char_p, C.c_char_p, C.c_size_t]
+        L.prach_noma_summary_format_csv.restype = C.c_size_t
+        L.prach_run_trials_noma_pick.argtypes = L.prach_run_trials_pick.argtypes
+        L.prach_noma_pick_from_logs.argtypes = L.prach_pick_from_logs.argtypes
+        L.prach_noma_pick_format_csv.argtypes = L.prach_pick_format_csv.argtypes
+        L.prach_noma_pick_format_csv.restype = C.c_size_t
         L.prach_noma_columns_from_logs.argtypes = [C.POINTER(PrachColumnsSpec), C.POINTER(PrachCfg), C.c_uint64, C.POINTER(PrachUeLog), C.c_int, C.c_void_p, C.c_uint64]
         L.prach_run_trials_trace.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachTraceSpec),
                                              C.POINTER(C.c_int32), C.POINTER(PrachTrace), u64p, u64p, u64p, u64p]
@@ -854,7 +951,9 @@ EXPORTS = ("prach_engine_create", "prach_engine_destroy", "prach_engine_set", "p
            "prach_xtab_merge", "prach_xtab_quantile", "prach_xtab_format_csv", "prach_xtab_tile_ues", "prach_xtab_window_words", "prach_run_trials_pick",
            "prach_pick_from_logs", "prach_pick_format_csv", "prach_run_trials_columns", "prach_run_trials_columns_device", "prach_columns_from_logs",
            "prach_columns_tile_ues", "prach_run_trials_noma_census", "prach_noma_census_accumulate_logs", "prach_noma_census_merge", "prach_noma_census_format_csv",
-           "prach_noma_census_tile_ues", "prach_run_trials_noma_columns", "prach_run_trials_noma_columns_device", "prach_noma_columns_from_logs")
+           "prach_noma_census_tile_ues", "prach_run_trials_noma_columns", "prach_run_trials_noma_columns_device", "prach_noma_columns_from_logs",
+           "prach_run_trials_noma_pick", "prach_noma_pick_from_logs", "prach_noma_pick_format_csv", "prach_run_trials_noma_summary", "prach_noma_summary_from_logs",
+           "prach_noma_summary_stats", "prach_noma_summary_format_csv")
 
 
 def make_cfg(nUE, variant=VARIANT_BETA_C, uniform=0, rng_mode=RNG_GLIBC, seed=0, stream_offset=0, **kw) -> PrachCfg:
@@ -1005,6 +1104,24 @@ class Engine:
         (prach_run_trials_noma_census; NOMA.c trials with Philox only).  The default: what became of the UEs by when they arrived.  groups / ngroups /
         want_logs as in run_trials_dist.  Returns (results, logs, NomaCensus)."""
         return self._call_reduced("prach_run_trials_noma_census", cfgs, NomaCensus(_ngroups(len(cfgs), groups, ngroups), rows, cols, who), groups, want_logs)
+
+    def run_trials_noma_summary(self, cfgs, fields=("sojourn", "timer", "ptc", "lost"), who=NOMA_WHO["served"], permille=(500, 950, 990), want_logs=False):
+        """run_trials plus one summary row per NOMA.c trial — the four class counts and, for up to four ``fields`` of NOMA_FIELD_NAMES over the UEs of the
+        classes ``who`` whose value is defined, their number, sum, maximum and EXACT order statistics at the levels ``permille`` — selected on the device
+        (prach_run_trials_noma_summary; NOMA.c trials with Philox only).  NomaSummary.stats gives the spread between the trials of a group.  Returns
+        (results, logs, NomaSummary)."""
+        sm = NomaSummary(len(cfgs), fields, who, permille)
+        sp = sm.spec()
+        res, logs = self._call("prach_run_trials_noma_summary", cfgs, want_logs, C.byref(sp), sm._rows_ptr())
+        return res, logs, sm
+
+    def run_trials_noma_pick(self, cfgs, where=(), order="index", key=None, k=16, who=NOMA_WHO["all"], want_logs=False):
+        """run_trials_pick for NOMA.c trials with Philox: clauses, key and ``who`` over the NOMA menu (fields of NOMA_FIELD_NAMES, classes of NOMA_WHO), selected
+        on the device (prach_run_trials_noma_pick).  NomaCensus.cell_clauses gives the ``where`` of a census cell.  Returns (results, logs, NomaPick)."""
+        pk = NomaPick(len(cfgs), where, order, key, k, who)
+        sp = pk.spec()
+        res, logs = self._call("prach_run_trials_noma_pick", cfgs, want_logs, C.byref(sp), pk._headers_ptr(), pk._rows_ptr())
+        return res, logs, pk
 
     def run_trials_noma_columns(self, cfgs, fields, device=False, want_logs=False):
         """run_trials_columns for NOMA.c trials with Philox: ``fields`` are names of NOMA_FIELD_NAMES, -1 where undefined, or ``raw:NAME``
@@ -1272,32 +1389,75 @@ def summary_csv(sm: Summary, groups=None, ngroups=None, labels=None) -> bytes:
     return out
 
 
-def pick_from_logs(cfgs, steps, logs, where=(), order="index", key=None, k=16, who=XTAB_WHO["all"]) -> Pick:
-    """The host-side definition of the pick (prach_pick_from_logs): trial t from logs[t], the per-UE log of the trial with config cfgs[t] that ran steps[t]
-    subframes (prach_result.steps) — a ctypes array of PrachUeLog, as Engine.run_trials returns it, or an int32 array of shape [nUE, 16]."""
-    pk = Pick(len(logs), where, order, key, k, who)
+def noma_summary_from_logs(cfgs, steps, logs, fields=("sojourn", "timer", "ptc", "lost"), who=NOMA_WHO["served"], permille=(500, 950, 990)) -> NomaSummary:
+    """The host-side definition of the NOMA summary (prach_noma_summary_from_logs): row k from logs[k], the per-UE log of the NOMA.c trial with config cfgs[k]
+    that ran steps[k] subframes (prach_result.steps) — a ctypes array of PrachUeLog or an int32 array of shape [nUE, 16].  Both RNG modes."""
+    sm = NomaSummary(len(logs), fields, who, permille)
+    sp = sm.spec()
+    rows = sm._rows_ptr()
+    for k, lg in enumerate(logs):
+        ptr, nue, _keep = _log_ptr(lg)
+        rc = lib().prach_noma_summary_from_logs(C.byref(sp), C.byref(cfgs[k]), int(steps[k]), ptr, nue, C.byref(rows[k]))
+        if rc != OK:
+            raise PrachError(rc, "(prach_noma_summary_from_logs)")
+    return sm
+
+
+def noma_summary_csv(sm: NomaSummary, groups=None, ngroups=None, labels=None) -> bytes:
+    """The CSV text of the statistics of every group of trials (prach_noma_summary_stats, prach_noma_summary_format_csv), labelled labels[g] (default: the
+    group number): `label,metric,n,mean,sd,sem,min,max`."""
+    st = sm.stats(groups, ngroups)
+    sp = sm.spec()
+    out = b""
+    for g in range(st.shape[0]):
+        args = (C.byref(sp), st[g].ctypes.data_as(C.POINTER(PrachStat)), str(g if labels is None else labels[g]).encode())
+        need = lib().prach_noma_summary_format_csv(*args, None, 0)
+        buf = C.create_string_buffer(need + 1)
+        n = lib().prach_noma_summary_format_csv(*args, buf, need + 1)
+        out += buf.raw[:n]
+    return out
+
+
+def _pick_from_logs(fn, pk, cfgs, steps, logs):
     sp = pk.spec()
     hdr = pk._headers_ptr()
     for t, lg in enumerate(logs):
         ptr, nue, _keep = _log_ptr(lg)
-        rc = lib().prach_pick_from_logs(C.byref(sp), C.byref(cfgs[t]), int(steps[t]), ptr, nue, C.byref(hdr[t]), pk._rows_ptr(t))
+        rc = getattr(lib(), fn)(C.byref(sp), C.byref(cfgs[t]), int(steps[t]), ptr, nue, C.byref(hdr[t]), pk._rows_ptr(t))
         if rc != OK:
-            raise PrachError(rc, "(prach_pick_from_logs)")
+            raise PrachError(rc, f"({fn})")
     return pk
 
 
-def pick_csv(pk: Pick, cfgs=None, labels=None) -> bytes:
+def pick_from_logs(cfgs, steps, logs, where=(), order="index", key=None, k=16, who=XTAB_WHO["all"]) -> Pick:
+    """The host-side definition of the pick (prach_pick_from_logs): trial t from logs[t], the per-UE log of the trial with config cfgs[t] that ran steps[t]
+    subframes (prach_result.steps) — a ctypes array of PrachUeLog, as Engine.run_trials returns it, or an int32 array of shape [nUE, 16]."""
+    return _pick_from_logs("prach_pick_from_logs", Pick(len(logs), where, order, key, k, who), cfgs, steps, logs)
+
+
+def noma_pick_from_logs(cfgs, steps, logs, where=(), order="index", key=None, k=16, who=NOMA_WHO["all"]) -> NomaPick:
+    """The host-side definition of the NOMA pick (prach_noma_pick_from_logs), as pick_from_logs: NOMA.c trials, both RNG modes."""
+    return _pick_from_logs("prach_noma_pick_from_logs", NomaPick(len(logs), where, order, key, k, who), cfgs, steps, logs)
+
+
+def noma_pick_csv(pk: NomaPick, cfgs=None, labels=None) -> bytes:
+    """pick_csv for a NOMA pick (prach_noma_pick_format_csv: the same lines)."""
+    return pick_csv(pk, cfgs, labels, _fn="prach_noma_pick_format_csv")
+
+
+def pick_csv(pk: Pick, cfgs=None, labels=None, _fn="prach_pick_format_csv") -> bytes:
     """The CSV text of every trial's pick (prach_pick_format_csv), trial by trial: labelled labels[t] (default: the trial's nUE), with the seed of cfgs[t]
     (default 0)."""
+    fmt = getattr(lib(), _fn)
     out = []
     sp = pk.spec()
     hdr = pk._headers_ptr()
     for t in range(len(pk.headers)):
         label = str(int(pk.headers["nUE"][t]) if labels is None else labels[t]).encode()
         args = (C.byref(sp), C.byref(hdr[t]), pk._rows_ptr(t), label, t, int(cfgs[t].seed) if cfgs is not None else 0)
-        need = lib().prach_pick_format_csv(*args, None, 0)
+        need = fmt(*args, None, 0)
         buf = C.create_string_buffer(need + 1)
-        n = lib().prach_pick_format_csv(*args, buf, need + 1)
+        n = fmt(*args, buf, need + 1)
         assert n == need
         out.append(buf.raw[:n])
     return b"".join(out)

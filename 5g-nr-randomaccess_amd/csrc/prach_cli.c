@@ -49,6 +49,15 @@
  * FIELD is one of one, arrival, sojourn, completion, timer, ptc, retx, msg3fail, age, state, sector, preamble, lost (the NOMA menu of include/prach.h); the
  * defaults — rows arrival:500, columns state:1:9, everybody — say what became of the UEs by when they arrived; --program noma with Philox only, and not
  * together with another reduction;
+ * --census-ci FILE [--census-ci-fields F1,F2,..] [--census-ci-who served|pending|dropped|arrived|all] [--census-ci-levels M1,..]: how far one seed lies from the
+ * next, for NOMA.c (prach_run_trials_noma_summary: one row per trial, selected on the device; prach_noma_summary_stats in the parent, in trial order, so the
+ * file does not depend on --gpus): per sweep point, labelled nUE, in --ci's line format, served_ratio, dropped_ratio, pending_ratio, restart_ratio and, per
+ * field of the NOMA menu (at most 4; default sojourn,timer,ptc,lost) over the UEs of the class (default served), its mean and its exact order statistics at
+ * the levels (permille, at most 8; default 500,950,990); --program noma with Philox only, and not together with another reduction;
+ * --census-pick FILE [--census-pick-where FIELD:LO:HI]... [--census-pick-top FIELD | --census-pick-bottom FIELD] [--census-pick-k K] [--census-pick-who
+ * served|pending|dropped|arrived|idle|all]: WHICH UEs stand behind a count of the census (prach_run_trials_noma_pick: selected on the device), --pick's lines
+ * with fields of the NOMA menu: one header and at most K (default 16) rows per trial, in trial order; --program noma with Philox only, and not together with
+ * another reduction;
  * --devices LIST: the same with explicit HIP ordinals (an ordinal may repeat);
  * --gpus N: the --times x sweep grid sharded over N devices of the node by host C — one forked child per device,
  * forked BEFORE any HIP call, trials dealt by descending cost (Philox: any trial anywhere; glibc: whole seeds, because
@@ -137,6 +146,10 @@ typedef struct reduction {
     prach_pick *pk_hdr;
     prach_pick_row *pk_rows;
     const prach_xtab_spec *nc;  /* --census (--program noma): prach_noma_census[npts] | cells[npts][row_bins + 1][col_bins + 1] */
+    int pk_noma;                /* --census-pick: `pk` is over the NOMA menu (prach_run_trials_noma_pick) */
+    /* --census-ci (prach_run_trials_noma_summary), like --ci: one row per trial of the grid in a shared mapping; the parent computes the statistics */
+    const prach_noma_summary_spec *nsm;
+    prach_noma_trial_summary *nsm_rows;
 } reduction;
 static int red_on(const reduction *r) { return r->cdf || r->tl || r->sj || r->tr || r->xt || r->nc; }
 static size_t xt_cells(const prach_xtab_spec *s) { return ((size_t)s->row_bins + 1) * ((size_t)s->col_bins + 1); }
@@ -254,12 +267,33 @@ static int xtab_axis(const char *text, int max_time, int32_t *field, int32_t *wi
 /* FIELD[:WIDTH[:BINS]] of --census-rows / --census-cols: a field of the NOMA menu.  Defaults: width 500 for arrival, otherwise 1; as many bins as cover max_time
  * (arrival) or max_time + 6 (the other times), 9 for state, 1 for one, 6 for sector, 64 for preamble, 255 for ptc, retx and msg3fail.  Returns 0 for a text that is none */
 static const char *const noma_names[PRACH_NOMA_NFIELDS] = {"one", "arrival", "sojourn", "completion", "timer", "ptc", "retx", "msg3fail", "age", "state", "sector", "preamble", "lost"};
+static int noma_field(const char *text, size_t len) {
+    for (int q = 0; q < PRACH_NOMA_NFIELDS; q++)
+        if (strlen(noma_names[q]) == len && strncasecmp(noma_names[q], text, len) == 0) return q;
+    return -1;
+}
+/* FIELD:LO:HI of --census-pick-where.  Returns 0 for a text that is none */
+static int noma_pick_clause(const char *text, prach_pick_clause *c) {
+    const char *c1 = strchr(text, ':'), *c2 = c1 ? strchr(c1 + 1, ':') : NULL;
+    if (!c2 || strchr(c2 + 1, ':')) return 0;
+    const int f = noma_field(text, (size_t)(c1 - text));
+    char *end1, *end2;
+    const long lo = strtol(c1 + 1, &end1, 10), hi = strtol(c2 + 1, &end2, 10);
+    if (f < 0 || end1 != c2 || end1 == c1 + 1 || *end2 || end2 == c2 + 1 || lo < 0 || hi < lo || hi > INT32_MAX) return 0;
+    c->field = f; c->lo = (int32_t)lo; c->hi = (int32_t)hi;
+    return 1;
+}
+/* the classes of --census-who, --census-ci-who and --census-pick-who (idle: the pick only); 0 for a text that is none */
+static int noma_who(const char *t, int idle_too) {
+    return strcmp(t, "served") == 0 ? PRACH_NOMA_SERVED : strcmp(t, "pending") == 0 ? PRACH_NOMA_PENDING : strcmp(t, "dropped") == 0 ? PRACH_NOMA_DROPPED
+           : strcmp(t, "arrived") == 0 ? (PRACH_NOMA_SERVED | PRACH_NOMA_PENDING | PRACH_NOMA_DROPPED)
+           : strcmp(t, "all") == 0 ? (PRACH_NOMA_SERVED | PRACH_NOMA_PENDING | PRACH_NOMA_DROPPED | PRACH_NOMA_IDLE)
+           : idle_too && strcmp(t, "idle") == 0 ? PRACH_NOMA_IDLE : 0;
+}
 static int noma_axis(const char *text, int max_time, int32_t *field, int32_t *width, int32_t *bins) {
     const char *c1 = strchr(text, ':'), *c2 = c1 ? strchr(c1 + 1, ':') : NULL;
     const size_t len = c1 ? (size_t)(c1 - text) : strlen(text);
-    int f = -1;
-    for (int q = 0; q < PRACH_NOMA_NFIELDS; q++)
-        if (strlen(noma_names[q]) == len && strncasecmp(noma_names[q], text, len) == 0) f = q;
+    const int f = noma_field(text, len);
     if (f < 0 || (c2 && strchr(c2 + 1, ':'))) return 0;
     const long w = c1 ? atol(c1 + 1) : f == PRACH_NOMA_ARRIVAL ? 500 : 1;
     if (w < 1 || w > INT32_MAX) return 0;
@@ -274,8 +308,10 @@ static int noma_axis(const char *text, int max_time, int32_t *field, int32_t *wi
 
 /* one call into the library with the run's reduction: its groups (group = sweep point, grp[k]) come back in call_block and are merged into the worker's block */
 static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *r, prach_ue_log *const *logs, const reduction *red, const int32_t *grp,
-                    char *call_block, char *worker_block, prach_trial_summary *sm_rows, prach_pick *pk_hdr, prach_pick_row *pk_rows) {
+                    char *call_block, char *worker_block, prach_trial_summary *sm_rows, prach_pick *pk_hdr, prach_pick_row *pk_rows, prach_noma_trial_summary *nsm_rows) {
     if (red->sm) return prach_run_trials_summary(eng, c, n, r, logs, red->sm, sm_rows);
+    if (red->nsm) return prach_run_trials_noma_summary(eng, c, n, r, logs, red->nsm, nsm_rows);
+    if (red->pk && red->pk_noma) return prach_run_trials_noma_pick(eng, c, n, r, logs, red->pk, pk_hdr, pk_rows);
     if (red->pk) return prach_run_trials_pick(eng, c, n, r, logs, red->pk, pk_hdr, pk_rows);
     if (!red_on(red)) return prach_run_trials(eng, c, n, r, logs);
     char *const b = call_block;
@@ -313,6 +349,8 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
     if (reduces && (!grp || !call_block)) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
     prach_trial_summary *sr = red->sm ? (prach_trial_summary *)malloc(sizeof(prach_trial_summary) * (size_t)(m > 0 ? m : 1)) : NULL;
     if (red->sm && !sr) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+    prach_noma_trial_summary *nsr = red->nsm ? (prach_noma_trial_summary *)malloc(sizeof(prach_noma_trial_summary) * (size_t)(m > 0 ? m : 1)) : NULL;
+    if (red->nsm && !nsr) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
     /* --pick: the headers and rows of one call (at most CH trials, or the worker's seeds) */
     const size_t pk_n = (size_t)(m < CH ? (m > 0 ? m : 1) : CH), pk_k = red->pk ? (size_t)red->pk->k : 0;
     prach_pick *ph = red->pk ? (prach_pick *)malloc(sizeof(prach_pick) * pk_n) : NULL;
@@ -329,12 +367,13 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
                     if (!logs[k]) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
                 }
             }
-            rc = run_call(eng, c, n, r, logs, red, grp, call_block, worker_block, sr, ph, pr);
+            rc = run_call(eng, c, n, r, logs, red, grp, call_block, worker_block, sr, ph, pr, nsr);
             if (rc != PRACH_OK) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(rc)); return 2; }
             const double lat = now_s() - t0;
             for (int k = 0; k < n; k++) {
                 res[idx[a + k]] = r[k];
                 if (red->sm) red->sm_rows[idx[a + k]] = sr[k];
+                if (red->nsm) red->nsm_rows[idx[a + k]] = nsr[k];
                 if (red->pk) { red->pk_hdr[idx[a + k]] = ph[k]; memcpy(red->pk_rows + (size_t)idx[a + k] * pk_k, pr + (size_t)k * pk_k, sizeof(prach_pick_row) * pk_k); }
                 lat_out[idx[a + k]] = lat;
                 if (cfgs[idx[a + k]].variant != PRACH_VARIANT_NOMA_C) {
@@ -358,13 +397,14 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
                     if (!logs[s_]) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
                 }
             }
-            rc = run_call(eng, c, nseeds, r, logs, red, grp, call_block, worker_block, sr, ph, pr);
+            rc = run_call(eng, c, nseeds, r, logs, red, grp, call_block, worker_block, sr, ph, pr, nsr);
             if (rc != PRACH_OK) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(rc)); return 2; }
             const double lat = now_s() - t0;
             for (int s_ = 0; s_ < nseeds; s_++) {
                 offset[s_] += r[s_].draws;
                 res[idx[s_ * npts + k]] = r[s_];
                 if (red->sm) red->sm_rows[idx[s_ * npts + k]] = sr[s_];
+                if (red->nsm) red->nsm_rows[idx[s_ * npts + k]] = nsr[s_];
                 if (red->pk) { red->pk_hdr[idx[s_ * npts + k]] = ph[s_]; memcpy(red->pk_rows + (size_t)idx[s_ * npts + k] * pk_k, pr + (size_t)s_ * pk_k, sizeof(prach_pick_row) * pk_k); }
                 lat_out[idx[s_ * npts + k]] = lat;
                 if (c[s_].variant != PRACH_VARIANT_NOMA_C) { /* (NOMA.c's lines are printed and appended by the parent) */
@@ -376,7 +416,7 @@ static int run_worker(int device, const prach_cfg *cfgs, const int *idx, int m, 
         }
         free(offset);
     }
-    free(c); free(r); free(logs); free(grp); free(call_block); free(sr); free(ph); free(pr);
+    free(c); free(r); free(logs); free(grp); free(call_block); free(sr); free(nsr); free(ph); free(pr);
     prach_engine_destroy(eng);
     return 0;
 }
@@ -390,6 +430,10 @@ int main(int argc, char *argv[]) {
     const char *xt_rows = "arrival:500", *xt_cols = "state:1:7", *xt_who = "all";
     const char *nc_path = NULL, *nc_rows = "arrival:500", *nc_cols = "state:1:9", *nc_who = "all";
     prach_summary_spec ci_spec = {3, {500, 950, 990, 0, 0, 0, 0, 0}, {0, 0, 0}};
+    /* --census-ci, --census-pick (--program noma) */
+    const char *nci_path = NULL, *nci_who = "served", *npk_path = NULL, *npk_who = "all";
+    prach_noma_summary_spec nci_spec = {0, 4, {PRACH_NOMA_SOJOURN, PRACH_NOMA_TIMER, PRACH_NOMA_PTC, PRACH_NOMA_LOST}, 3, {500, 950, 990, 0, 0, 0, 0, 0}, {0, 0}};
+    prach_pick_spec npk_spec = {0, 0, {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, PRACH_PICK_BY_INDEX, PRACH_NOMA_ONE, 16, 0};
     int cdf_bins = 4096, cdf_bin_ms = 1, tl_bin_ms = 5, sj_row_ms = 500, sj_bin_ms = 5, tr_bin_ms = 5;
     int devs[64];
     /* --program must be known before the defaults are laid down */
@@ -507,6 +551,46 @@ int main(int argc, char *argv[]) {
             nc_cols = v;
         } else if (strcmp(a, "--census-who") == 0) {
             nc_who = v;
+        } else if (strcmp(a, "--census-ci") == 0) {
+            nci_path = v;
+        } else if (strcmp(a, "--census-ci-who") == 0) {
+            nci_who = v;
+        } else if (strcmp(a, "--census-ci-fields") == 0) {
+            nci_spec.nfields = 0;
+            memset(nci_spec.field, 0, sizeof nci_spec.field);
+            for (const char *q = v; *q;) {
+                const char *e = strchr(q, ',') ? strchr(q, ',') : q + strlen(q);
+                const int f = noma_field(q, (size_t)(e - q));
+                if (nci_spec.nfields >= PRACH_NOMA_SUMMARY_MAX_FIELDS || f < 0) die("--census-ci-fields LIST: 1 to 4 comma-separated fields of the NOMA menu");
+                nci_spec.field[nci_spec.nfields++] = f;
+                q = *e ? e + 1 : e;
+            }
+            if (nci_spec.nfields < 1) die("--census-ci-fields LIST: 1 to 4 comma-separated fields of the NOMA menu");
+        } else if (strcmp(a, "--census-ci-levels") == 0) {
+            nci_spec.nq = 0;
+            memset(nci_spec.permille, 0, sizeof nci_spec.permille);
+            for (const char *q = v; *q;) {
+                const int m_ = atoi(q);
+                if (nci_spec.nq >= PRACH_SUMMARY_MAX_Q || m_ < 1 || m_ > 1000) die("--census-ci-levels LIST: 1 to 8 comma-separated levels in permille, 1 to 1000 each");
+                nci_spec.permille[nci_spec.nq++] = m_;
+                while (*q && *q != ',') q++;
+                if (*q == ',') q++;
+            }
+            if (nci_spec.nq < 1) die("--census-ci-levels LIST: 1 to 8 comma-separated levels in permille, 1 to 1000 each");
+        } else if (strcmp(a, "--census-pick") == 0) {
+            npk_path = v;
+        } else if (strcmp(a, "--census-pick-where") == 0) {
+            if (npk_spec.nclauses >= PRACH_PICK_MAX_CLAUSES || !noma_pick_clause(v, &npk_spec.clause[npk_spec.nclauses])) die("--census-pick-where FIELD:LO:HI: a field of the NOMA menu, 0 <= LO <= HI, at most 4 clauses");
+            npk_spec.nclauses++;
+        } else if (strcmp(a, "--census-pick-top") == 0 || strcmp(a, "--census-pick-bottom") == 0) {
+            if (npk_spec.order != PRACH_PICK_BY_INDEX || noma_field(v, strlen(v)) < 0) die("--census-pick-top FIELD or --census-pick-bottom FIELD: one of them, with a field of the NOMA menu");
+            npk_spec.order = strcmp(a, "--census-pick-top") == 0 ? PRACH_PICK_LARGEST : PRACH_PICK_SMALLEST;
+            npk_spec.key_field = noma_field(v, strlen(v));
+        } else if (strcmp(a, "--census-pick-k") == 0) {
+            if (atoi(v) < 1 || atoi(v) > PRACH_PICK_MAX_K) die("--census-pick-k K: 1..4096 UEs per trial");
+            npk_spec.k = atoi(v);
+        } else if (strcmp(a, "--census-pick-who") == 0) {
+            npk_who = v;
         } else if (strcmp(a, "--pick") == 0) {
             pk_path = v;
         } else if (strcmp(a, "--pick-where") == 0) {
@@ -538,6 +622,12 @@ int main(int argc, char *argv[]) {
         }
     }
     base.rng_mode = rng;
+    if (nci_path && variant != PRACH_VARIANT_NOMA_C) die("--census-ci needs --program noma (the other programs have --ci)");
+    if (npk_path && variant != PRACH_VARIANT_NOMA_C) die("--census-pick needs --program noma (the other programs have --pick)");
+    if (nci_path && (npk_path || nc_path || pk_path || xt_path || tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--census-ci cannot be combined with --cdf, --timeline, --sojourn, --ci, --trace, --xtab, --pick, --census or --census-pick: one reduction per call");
+    if (npk_path && (nc_path || pk_path || xt_path || tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--census-pick cannot be combined with --cdf, --timeline, --sojourn, --ci, --trace, --xtab, --pick or --census: one reduction per call");
+    if (nci_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census-ci needs --rng philox (a NOMA.c trial in the reference's stream can finish on the host and leaves no device record)");
+    if (npk_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census-pick needs --rng philox (a NOMA.c trial in the reference's stream can finish on the host and leaves no device record)");
     if (nc_path && variant != PRACH_VARIANT_NOMA_C) die("--census needs --program noma (the other programs have --xtab)");
     if (nc_path && (pk_path || xt_path || tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--census cannot be combined with --cdf, --timeline, --sojourn, --ci, --trace, --xtab or --pick: one reduction per call");
     if (nc_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census needs --rng philox (a NOMA.c trial in the reference's stream can finish on the host and leaves no device record)");
@@ -634,7 +724,7 @@ int main(int argc, char *argv[]) {
      * three numbers, per cell and twice per row */
     const reduction red_ = {cdf_path ? &cdf_spec : NULL, tl_path ? &tl_spec : NULL, sj_path ? &sj_spec : NULL, sj_path ? sj_path : tl_path ? tl_path : cdf_path,
                             sj_path ? 64 * ((size_t)sj_rows * ((size_t)sj_bins + 2) + 1) + 1
-                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, 0, NULL, NULL};
     reduction red_ci = red_;
     /* the trace's bins cover maxTime */
     const int tr_bins = (prach_max_time(&base) + tr_bin_ms - 1) / tr_bin_ms;
@@ -670,11 +760,26 @@ int main(int argc, char *argv[]) {
         if (red_ci.sm_rows == MAP_FAILED) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
         for (int q = 0; q < ntr; q++) red_ci.sm_rows[q].status = PRACH_ERR_INTERNAL; /* (a row no worker wrote counts nowhere) */
     }
+    if (nci_path) { /* --census-ci: the rows of the whole grid, filled by the workers */
+        nci_spec.who = noma_who(nci_who, 0);
+        if (!nci_spec.who) die("--census-ci-who served|pending|dropped|arrived|all");
+        red_ci.nsm = &nci_spec;
+        red_ci.nsm_rows = (prach_noma_trial_summary *)mmap(NULL, sizeof(prach_noma_trial_summary) * (size_t)ntr, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
+        if (red_ci.nsm_rows == MAP_FAILED) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+        for (int q = 0; q < ntr; q++) red_ci.nsm_rows[q].status = PRACH_ERR_INTERNAL; /* (a row no worker wrote counts nowhere) */
+    }
+    if (npk_path) { /* --census-pick: --pick's mappings and lines, over the NOMA menu */
+        npk_spec.who = noma_who(npk_who, 1);
+        if (!npk_spec.who) die("--census-pick-who served|pending|dropped|arrived|idle|all");
+        pk_spec = npk_spec;
+        pk_path = npk_path;
+        red_ci.pk_noma = 1;
+    }
     if (pk_path) { /* --pick: the headers and rows of the whole grid, filled by the workers */
-        pk_spec.who = strcmp(pk_who, "served") == 0 ? PRACH_XTAB_SERVED : strcmp(pk_who, "unserved") == 0 ? PRACH_XTAB_UNSERVED : strcmp(pk_who, "idle") == 0 ? PRACH_XTAB_IDLE
+        if (!red_ci.pk_noma) pk_spec.who = strcmp(pk_who, "served") == 0 ? PRACH_XTAB_SERVED : strcmp(pk_who, "unserved") == 0 ? PRACH_XTAB_UNSERVED : strcmp(pk_who, "idle") == 0 ? PRACH_XTAB_IDLE
                       : strcmp(pk_who, "arrived") == 0 ? (PRACH_XTAB_SERVED | PRACH_XTAB_UNSERVED) : strcmp(pk_who, "all") == 0 ? (PRACH_XTAB_SERVED | PRACH_XTAB_UNSERVED | PRACH_XTAB_IDLE) : 0;
         if (!pk_spec.who) die("--pick-who served|unserved|arrived|idle|all");
-        if ((uint64_t)ntr * (uint64_t)pk_spec.k > (1ull << 22)) die("--pick: too many rows");
+        if ((uint64_t)ntr * (uint64_t)pk_spec.k > (1ull << 22)) die(red_ci.pk_noma ? "--census-pick: too many rows" : "--pick: too many rows");
         red_ci.pk = &pk_spec;
         red_ci.pk_hdr = (prach_pick *)mmap(NULL, sizeof(prach_pick) * (size_t)ntr, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
         red_ci.pk_rows = (prach_pick_row *)mmap(NULL, sizeof(prach_pick_row) * (size_t)ntr * (size_t)pk_spec.k, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
@@ -753,6 +858,28 @@ int main(int argc, char *argv[]) {
         free(grp); free(st);
     }
 
+    if (nci_path) { /* statistics over the seeds of every sweep point, from the rows in trial order: the same whatever the number of workers */
+        const int nm = 4 + nci_spec.nfields * (1 + nci_spec.nq);
+        int32_t *grp = (int32_t *)malloc(sizeof(int32_t) * (size_t)ntr);
+        prach_stat *st = (prach_stat *)malloc(sizeof(prach_stat) * (size_t)npts * (size_t)nm);
+        if (!grp || !st) { fprintf(stderr, "prach_sim: out of memory\n"); return 2; }
+        for (int q = 0; q < ntr; q++) grp[q] = q % npts;
+        const int rcs = prach_noma_summary_stats(&nci_spec, red->nsm_rows, ntr, grp, npts, st);
+        if (rcs != PRACH_OK) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(rcs)); return 2; }
+        FILE *fp = fopen(nci_path, "wb");
+        if (!fp) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_IO)); return 2; }
+        char out[8192]; /* 40 lines at most: a label of at most 10 digits, a name of at most 16 characters, seven numbers of at most 16 */
+        for (int k = 0; k < npts; k++) {
+            char label[16];
+            snprintf(label, sizeof label, "%d", sweep_lo + k * sweep_step);
+            const size_t n = prach_noma_summary_format_csv(&nci_spec, st + (size_t)k * (size_t)nm, label, out, sizeof out);
+            if (n >= sizeof out) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_INTERNAL)); return 2; }
+            fwrite(out, 1, n, fp);
+        }
+        fclose(fp);
+        free(grp); free(st);
+    }
+
     if (pk_path) { /* every trial of the grid in trial order, labelled nUE: the same whatever the number of workers */
         FILE *fp = fopen(pk_path, "wb");
         if (!fp) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_IO)); return 2; }
@@ -762,7 +889,8 @@ int main(int argc, char *argv[]) {
         for (int q = 0; q < ntr; q++) {
             char label[16];
             snprintf(label, sizeof label, "%d", cfgs[q].nUE);
-            const size_t n = prach_pick_format_csv(&pk_spec, &red->pk_hdr[q], red->pk_rows + (size_t)q * (size_t)pk_spec.k, label, q, cfgs[q].seed, out, cap);
+            const size_t n = (red->pk_noma ? prach_noma_pick_format_csv : prach_pick_format_csv)(&pk_spec, &red->pk_hdr[q], red->pk_rows + (size_t)q * (size_t)pk_spec.k, label, q,
+                                                                                                 cfgs[q].seed, out, cap);
             if (n == 0 || n >= cap) { fprintf(stderr, "prach_sim: %s\n", prach_strerror(PRACH_ERR_INTERNAL)); return 2; }
             fwrite(out, 1, n, fp);
         }

@@ -272,6 +272,20 @@ hipError_t launch_noma_census_kernel(const TimelineJob *jobs, int njobs, int wor
 int noma_census_copy_words(); // LDS words that the per-wavefront copies of a census table take at most
 hipError_t launch_noma_columns_kernel(const TimelineJob *jobs, int njobs, int workgroups, const prach_columns_spec &spec, ColumnsOut out, hipStream_t stream); // spec: a valid one
 
+// prach_noma_select.hip: the summary row and the pick of every accepted NOMA.c trial of a launch over THE NOMA MENU (prach_run_trials_noma_summary, _noma_pick).
+// The jobs are the timeline's with E = min(steps, maxTime) in `pad` (group = the trial), ONE workgroup per trial, plain stores.
+// SUMMARY: a row is NSM_WORDS 64-bit words: idle, served, dropped, pending, selected, restarted, 4 range-error counts, 4 counts n[x], 4 sums, 4 maxima (-1:
+// n[x] == 0), then [4][PRACH_SUMMARY_MAX_Q] levels (-1: not found or unused).  PICK: rows (PK_ROW_WORDS) and scalars (PK_SCALARS) are those of prach_pick.hip
+// above; `who`, the clause fields and the key field of the spec are PRACH_NOMA_*.
+constexpr int NSM_WORDS = 22 + PRACH_NOMA_SUMMARY_MAX_FIELDS * PRACH_SUMMARY_MAX_Q;
+extern "C" int prach_internal_noma_summary_spec_ok(const prach_noma_summary_spec *spec); // prach_host.c
+extern "C" int prach_internal_noma_pick_spec_ok(const prach_pick_spec *spec);            // prach_host.c
+// threads: 512 or 1024; sched_cap: schedule entries staged in LDS (the longest schedule of the jobs, cut to noma_select_sched_cap()); spec: a valid one
+int noma_select_sched_cap();
+hipError_t launch_noma_summary_kernel(const TimelineJob *jobs, int njobs, prach_noma_summary_spec spec, int threads, int sched_cap, unsigned long long *rows, hipStream_t stream);
+hipError_t launch_noma_pick_kernel(const TimelineJob *jobs, int njobs, prach_pick_spec spec, int threads, int sched_cap, unsigned long long *rows, unsigned long long *scalars,
+                                   hipStream_t stream);
+
 // prach_trace.hip: the per-subframe preamble trace of a launch's accepted trials (prach_run_trials_trace).  One job per trial: the rows the simulation kernel
 // wrote through TrialDev::trace, for the subframes [0, steps).  A workgroup reduces one tile of TR_TILE consecutive subframes of one trial, 16 bytes per lane
 // and load.  A tile covers at most TR_TILE consecutive bins (bin = t / bin_ms): scheme 1 adds them up in an LDS window of 64-bit counters anchored at the

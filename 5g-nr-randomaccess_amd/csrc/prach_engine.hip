@@ -427,13 +427,13 @@ static int noma_device_activation(prach_engine *e, const TrialDev *dparams, cons
     return PRACH_OK;
 }
 
-// What a call reduces on the device next to its results (prach_run_trials_dist, _timeline, _sojourn, _summary, _trace, _xtab, _pick, _columns, _noma_census, _noma_columns).  The call's device buffer is a
+// What a call reduces on the device next to its results (prach_run_trials_dist, _timeline, _sojourn, _summary, _trace, _xtab, _pick, _columns, _noma_census, _noma_columns, _noma_summary, _noma_pick).  The call's device buffer is a
 // row of parts, [ngroups][words] 64-bit counters each: the arrays the caller gets as they are, one per part, then the scalars the kernel keeps per group,
 // which the engine unpacks into the caller's per-group structs.  Every launch of the call gets one job per trial it finished, and the kind's kernel behind
 // the simulation kernel.  What differs between the kinds is stated ONCE per kind: a block of functions behind CallCtx and its row of RED_KINDS.  The generic
 // code (reduction_begin, run_group, reduction_end, run_trials_impl) walks that row and never asks which kind it has; a new kind is an enumerator, a block and
 // a row.
-enum class Red { dist, timeline, sojourn, summary, trace, xtab, pick, columns, noma_census, noma_columns };
+enum class Red { dist, timeline, sojourn, summary, trace, xtab, pick, columns, noma_census, noma_columns, noma_summary, noma_pick };
 constexpr int RED_MAX_PARTS = 6;
 struct Reduction {
     Red kind;
@@ -738,6 +738,48 @@ int noma_columns_unpack(const Reduction &r, CallCtx &cx, size_t k, const unsigne
     return PRACH_OK;
 }
 
+// noma_summary: every trial is its own group, and the only part is the kernel's row of NSM_WORDS words per trial (prach_noma_select.hip); the unpack follows
+// summary's.  ONE workgroup per job; the workgroup size is the summary's option ("summary_threads"): taken over from summary_kernel, NOT measured for this kernel
+int noma_summary_parts(const Reduction &, size_t w[]) { w[0] = NSM_WORDS; return 1; }
+hipError_t noma_summary_launch(const prach_engine *e, const Reduction &r, int njobs, int, unsigned long long *const *d) {
+    int max_slots = 0; // the longest schedule of the jobs
+    for (int j = 0; j < njobs; j++) max_slots = std::max(max_slots, reinterpret_cast<const TimelineJob *>(e->red_jobs_h)[j].nslots);
+    return launch_noma_summary_kernel(timeline_jobs(e), njobs, spec_of<prach_noma_summary_spec>(r), (int)e->opt_summary_threads, std::min(max_slots, noma_select_sched_cap()), d[0], e->stream);
+}
+void noma_summary_empty(const Reduction &r, size_t k, const prach_cfg *cfgs) {
+    prach_noma_trial_summary &row = group_of<prach_noma_trial_summary>(r, k);
+    std::memset(&row, 0, sizeof(row));
+    row.status = PRACH_ERR_INTERNAL;
+    row.nUE = cfgs[k].nUE;
+    std::memset(row.max, 0xff, sizeof(row.max)); // -1
+    std::memset(row.q, 0xff, sizeof(row.q));
+}
+int noma_summary_unpack(const Reduction &r, CallCtx &cx, size_t k, const unsigned long long *words) { // status and nUE from the host, the rest from the one launch that accepted the trial
+    const prach_noma_summary_spec &sp = spec_of<prach_noma_summary_spec>(r);
+    prach_noma_trial_summary &row = group_of<prach_noma_trial_summary>(r, k);
+    row.status = cx.results[k].status; // (everything else is still the empty row)
+    if (row.status != PRACH_OK) return PRACH_OK;
+    const long long *const q = reinterpret_cast<const long long *>(words);
+    if (cx.trials[k] != 1 || q[0] + q[1] + q[2] + q[3] != (long long)row.nUE) return row.status = PRACH_ERR_INTERNAL; // (no launch reduced this trial, or two did)
+    row.idle = (int32_t)q[0]; row.served = (int32_t)q[1]; row.dropped = (int32_t)q[2]; row.pending = (int32_t)q[3]; row.selected = (int32_t)q[4]; row.restarted = (int32_t)q[5];
+    long long rerr = 0;
+    for (int x = 0; x < sp.nfields; x++) {
+        rerr += q[6 + x];
+        row.n[x] = (int32_t)q[10 + x]; row.sum[x] = q[14 + x]; row.max[x] = (int32_t)q[18 + x];
+        for (int l = 0; l < sp.nq; l++) row.q[x][l] = q[6 + x] ? -1 : (int32_t)q[22 + x * PRACH_SUMMARY_MAX_Q + l];
+    }
+    row.range_errors = (int32_t)std::min<long long>(rerr, INT32_MAX);
+    return row.range_errors ? PRACH_ERR_INTERNAL : PRACH_OK; // (a value the kernel cannot rank: no trial produces one)
+}
+
+// noma_pick: pick's parts, empty header, unpack and host sort with the NOMA menu's kernel (prach_noma_select.hip).  The workgroup size is pick's option
+// ("pick_threads", 1024 by default): taken over from pick_kernel, NOT measured for this kernel
+hipError_t noma_pick_launch(const prach_engine *e, const Reduction &r, int njobs, int, unsigned long long *const *d) {
+    int max_slots = 0; // the longest schedule of the jobs
+    for (int j = 0; j < njobs; j++) max_slots = std::max(max_slots, reinterpret_cast<const TimelineJob *>(e->red_jobs_h)[j].nslots);
+    return launch_noma_pick_kernel(timeline_jobs(e), njobs, spec_of<prach_pick_spec>(r), (int)e->opt_pick_threads, std::min(max_slots, noma_select_sched_cap()), d[0], d[1], e->stream);
+}
+
 // in the order of enum class Red:           parts, job bytes, tile, job, device logs, trace rows, "fast" off, launch, empty, unpack, prach_timing field
 const RedKind RED_KINDS[] = {
     {dist_parts, sizeof(DistJob), DIST_TILE, dist_fill_job, false, false, false, dist_launch, empty_group<prach_dist, &prach_dist::delay_max>, dist_unpack, &prach_timing::dist_ms},
@@ -750,8 +792,10 @@ const RedKind RED_KINDS[] = {
     {columns_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, columns_launch, columns_empty, columns_unpack, &prach_timing::columns_ms},
     {noma_census_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, noma_census_launch, empty_group<prach_noma_census, &prach_noma_census::row_max, &prach_noma_census::col_max>, noma_census_unpack, &prach_timing::noma_census_ms},
     {noma_columns_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, noma_columns_launch, noma_columns_empty, noma_columns_unpack, &prach_timing::noma_columns_ms},
+    {noma_summary_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, noma_summary_launch, noma_summary_empty, noma_summary_unpack, &prach_timing::noma_summary_ms},
+    {pick_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, noma_pick_launch, pick_empty, pick_unpack, &prach_timing::noma_pick_ms},
 };
-static_assert(sizeof(RED_KINDS) / sizeof(RED_KINDS[0]) == (size_t)Red::noma_columns + 1, "one row per kind");
+static_assert(sizeof(RED_KINDS) / sizeof(RED_KINDS[0]) == (size_t)Red::noma_pick + 1, "one row per kind");
 const RedKind &kind_of(const Reduction &r) { return RED_KINDS[(int)r.kind]; }
 
 // How a rerun's launch differs from the first one
@@ -1815,6 +1859,27 @@ int prach_run_trials_noma_columns(prach_engine *e, const prach_cfg *cfgs, int n,
 int prach_run_trials_noma_columns_device(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs,
                                          const prach_columns_spec *spec, prach_noma_columns *hdr, void *dev_out, uint64_t rows_cap) {
     PRACH_GUARD(return run_trials_columns(e, cfgs, n, results, ue_logs, spec, hdr, dev_out, rows_cap, true);)
+}
+
+int prach_run_trials_noma_summary(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_noma_summary_spec *spec,
+                                  prach_noma_trial_summary *rows) {
+    // (spec and variants are judged first: what they ask for does not depend on a device)
+    if (!cfgs || !results || n <= 0 || !spec || !rows || !prach_internal_noma_summary_spec_ok(spec)) return PRACH_ERR_ARG;
+    for (int k = 0; k < n; k++) if (!noma_device_cfg(cfgs[k])) return PRACH_ERR_UNSUPPORTED;
+    if (!e) return PRACH_ERR_ARG;
+    const Reduction red{.kind = Red::noma_summary, .group = nullptr, .ngroups = n, .out = {}, .spec = spec, .groups = rows};
+    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
+}
+
+int prach_run_trials_noma_pick(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_pick_spec *spec,
+                               prach_pick *picks, prach_pick_row *rows) {
+    // (spec and variants are judged first: what they ask for does not depend on a device)
+    if (!cfgs || !results || n <= 0 || !spec || !picks || !rows || !prach_internal_noma_pick_spec_ok(spec)) return PRACH_ERR_ARG;
+    for (int k = 0; k < n; k++) if (!noma_device_cfg(cfgs[k])) return PRACH_ERR_UNSUPPORTED;
+    if ((uint64_t)n * ((uint64_t)spec->k * PK_ROW_WORDS + PK_SCALARS) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
+    if (!e) return PRACH_ERR_ARG;
+    const Reduction red{.kind = Red::noma_pick, .group = nullptr, .ngroups = n, .out = {reinterpret_cast<uint64_t *>(rows)}, .spec = spec, .groups = picks};
+    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
 int prach_noma_census_tile_ues(void) { return TL_TILE; }

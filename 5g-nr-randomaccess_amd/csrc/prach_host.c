@@ -1284,6 +1284,222 @@ size_t prach_pick_format_csv(const prach_pick_spec *s, const prach_pick *h, cons
     return csv_end(buf, cap, off);
 }
 
+/* ---- the NOMA pick: prach_run_trials_pick's contract over the NOMA menu (prach_run_trials_noma_pick) ---- */
+
+/* (the engine judges a spec with this too: csrc/prach_device.h) */
+int prach_internal_noma_pick_spec_ok(const prach_pick_spec *s) {
+    if (!s || s->who <= 0 || (s->who & ~NOMA_ALL_CLASSES) != 0 || s->nclauses < 0 || s->nclauses > PRACH_PICK_MAX_CLAUSES || s->k < 1 || s->k > PRACH_PICK_MAX_K ||
+        s->reserved != 0 || s->key_field < 0 || s->key_field >= PRACH_NOMA_NFIELDS) return 0;
+    if (s->order != PRACH_PICK_BY_INDEX && s->order != PRACH_PICK_LARGEST && s->order != PRACH_PICK_SMALLEST) return 0;
+    if (s->order == PRACH_PICK_BY_INDEX && s->key_field != PRACH_NOMA_ONE) return 0;
+    for (int c = 0; c < PRACH_PICK_MAX_CLAUSES; c++) {
+        const prach_pick_clause *q = &s->clause[c];
+        if (c < s->nclauses ? (q->field < 0 || q->field >= PRACH_NOMA_NFIELDS || q->lo < 0 || q->lo > q->hi) : (q->field || q->lo || q->hi)) return 0;
+    }
+    return 1;
+}
+
+/* THE DEFINITION (include/prach.h): every match is listed, the list is sorted, the first k are the rows */
+int prach_noma_pick_from_logs(const prach_pick_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_pick *hdr, prach_pick_row *rows) {
+    if (!prach_internal_noma_pick_spec_ok(s) || !cfg || !hdr || !rows || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    int nslots = 0, rc;
+    int64_t E = 0;
+    int32_t *sched = noma_schedule(cfg, nUE, steps, &nslots, &E, &rc);
+    if (!sched) return rc;
+    pick_cand *cand = (pick_cand *)malloc(sizeof(pick_cand) * (size_t)(nUE > 0 ? nUE : 1));
+    if (!cand) { free(sched); return PRACH_ERR_INTERNAL; }
+    const int keyed = s->order != PRACH_PICK_BY_INDEX;
+    prach_pick h;
+    memset(&h, 0, sizeof h);
+    h.status = PRACH_OK; h.nUE = nUE; h.threshold = -1;
+    int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
+    for (int i = 0; i < nUE; i++) {
+        while (slot < nslots && sched[slot] <= i) slot++;
+        const int64_t a = (int64_t)cfg->accessTime * slot;
+        const int cls = noma_class(&ue[i]);
+        if (!(cls & s->who)) continue;
+        h.selected++;
+        int fails = 0, undef = 0;
+        for (int c = 0; c < s->nclauses; c++) {
+            const int64_t v = noma_value(s->clause[c].field, &ue[i], cls, a, E);
+            if (v < 0) undef = 1;
+            else if (v < s->clause[c].lo || v > s->clause[c].hi) fails = 1;
+        }
+        const int64_t key = keyed ? noma_value(s->key_field, &ue[i], cls, a, E) : 0;
+        if (key < 0) undef = 1;
+        if (fails) continue;
+        if (undef) { h.undefined++; continue; }
+        cand[h.matched++] = (pick_cand){key, i, cls == PRACH_NOMA_IDLE ? -1 : (int32_t)a};
+    }
+    if (keyed) qsort(cand, (size_t)h.matched, sizeof(pick_cand), s->order == PRACH_PICK_LARGEST ? cmp_pick_desc : cmp_pick_asc);
+    h.stored = h.matched < s->k ? h.matched : s->k;
+    memset(rows, 0, sizeof(prach_pick_row) * (size_t)s->k);
+    for (int r = 0; r < h.stored; r++) {
+        rows[r].log = ue[cand[r].i];
+        rows[r].arrival = cand[r].arrival;
+        rows[r].key = (int32_t)cand[r].key;
+    }
+    if (keyed && h.stored > 0) {
+        h.threshold = rows[h.stored - 1].key;
+        for (int r = h.stored; r < h.matched && cand[r].key == cand[h.stored - 1].key; r++) h.ties_left_out++;
+    }
+    free(sched);
+    free(cand);
+    *hdr = h;
+    return PRACH_OK;
+}
+
+size_t prach_noma_pick_format_csv(const prach_pick_spec *s, const prach_pick *h, const prach_pick_row *rows, const char *label, int trial, uint64_t seed, char *buf,
+                                  size_t cap) {
+    if (!prach_internal_noma_pick_spec_ok(s)) return 0;
+    /* the pick's lines: only k enters them */
+    prach_pick_spec t;
+    memset(&t, 0, sizeof t);
+    t.who = PRACH_XTAB_SERVED; t.order = PRACH_PICK_BY_INDEX; t.key_field = PRACH_XTAB_ONE; t.k = s->k;
+    return prach_pick_format_csv(&t, h, rows, label, trial, seed, buf, cap);
+}
+
+/* ---- the NOMA summary: one row per trial over named fields of the NOMA menu (prach_run_trials_noma_summary) ---- */
+
+/* (the engine judges a spec with this too: csrc/prach_device.h) */
+int prach_internal_noma_summary_spec_ok(const prach_noma_summary_spec *s) {
+    if (!s || s->who <= 0 || (s->who & ~NOMA_ALL_CLASSES) != 0 || s->nfields < 1 || s->nfields > PRACH_NOMA_SUMMARY_MAX_FIELDS || s->nq < 1 ||
+        s->nq > PRACH_SUMMARY_MAX_Q || s->reserved[0] || s->reserved[1]) return 0;
+    for (int x = 0; x < PRACH_NOMA_SUMMARY_MAX_FIELDS; x++)
+        if (x < s->nfields ? (s->field[x] < 0 || s->field[x] >= PRACH_NOMA_NFIELDS) : s->field[x] != 0) return 0;
+    for (int l = 0; l < s->nq; l++)
+        if (s->permille[l] < 1 || s->permille[l] > 1000) return 0;
+    return 1;
+}
+
+static void noma_summary_row_clear(prach_noma_trial_summary *row, int status, int nUE) {
+    memset(row, 0, sizeof(*row));
+    row->status = status;
+    row->nUE = nUE;
+    for (int x = 0; x < PRACH_NOMA_SUMMARY_MAX_FIELDS; x++) {
+        row->max[x] = -1;
+        for (int l = 0; l < PRACH_SUMMARY_MAX_Q; l++) row->q[x][l] = -1;
+    }
+}
+
+static int cmp_i64(const void *a, const void *b) {
+    const int64_t x = *(const int64_t *)a, y = *(const int64_t *)b;
+    return (x > y) - (x < y);
+}
+
+/* THE DEFINITION (include/prach.h): the defined values of every named field over the selected UEs are sorted, a level is the value at its integer rank */
+int prach_noma_summary_from_logs(const prach_noma_summary_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE,
+                                 prach_noma_trial_summary *row) {
+    if (!prach_internal_noma_summary_spec_ok(s) || !cfg || !row || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    int nslots = 0, rc;
+    int64_t E = 0;
+    int32_t *sched = noma_schedule(cfg, nUE, steps, &nslots, &E, &rc);
+    if (!sched) return rc;
+    int64_t *val = (int64_t *)malloc(sizeof(int64_t) * PRACH_NOMA_SUMMARY_MAX_FIELDS * (size_t)(nUE > 0 ? nUE : 1));
+    if (!val) { free(sched); return PRACH_ERR_INTERNAL; }
+    prach_noma_trial_summary r;
+    noma_summary_row_clear(&r, PRACH_OK, nUE);
+    int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
+    for (int i = 0; i < nUE; i++) {
+        while (slot < nslots && sched[slot] <= i) slot++;
+        const int64_t a = (int64_t)cfg->accessTime * slot;
+        const int cls = noma_class(&ue[i]);
+        if (cls == PRACH_NOMA_IDLE) r.idle++;
+        else if (cls == PRACH_NOMA_SERVED) r.served++;
+        else if (cls == PRACH_NOMA_DROPPED) r.dropped++;
+        else r.pending++;
+        r.restarted += noma_value(PRACH_NOMA_LOST, &ue[i], cls, a, E) > 0; /* (defined for the served only) */
+        if (!(cls & s->who)) continue;
+        r.selected++;
+        for (int x = 0; x < s->nfields; x++) {
+            const int64_t v = noma_value(s->field[x], &ue[i], cls, a, E);
+            if (v < 0) continue; /* UNDEFINED */
+            val[(size_t)x * (size_t)nUE + (size_t)r.n[x]++] = v;
+            r.sum[x] += v;
+        }
+    }
+    for (int x = 0; x < s->nfields; x++) {
+        const int64_t n = r.n[x];
+        if (n == 0) continue;
+        int64_t *const v = val + (size_t)x * (size_t)nUE;
+        qsort(v, (size_t)n, sizeof(int64_t), cmp_i64);
+        r.max[x] = (int32_t)v[n - 1];
+        for (int l = 0; l < s->nq; l++) {
+            int64_t rank = (n * (int64_t)s->permille[l] + 999) / 1000;
+            if (rank < 1) rank = 1;
+            r.q[x][l] = (int32_t)v[rank - 1];
+        }
+    }
+    free(sched);
+    free(val);
+    *row = r;
+    return PRACH_OK;
+}
+
+#define NOMA_SUMMARY_FIXED_METRICS 4
+/* metric m of a row; returns 0 where the row has no such value */
+static int noma_summary_metric(const prach_noma_summary_spec *s, const prach_noma_trial_summary *r, int m, double *x) {
+    if (r->status != PRACH_OK) return 0;
+    if (m < 3) { *x = (double)(m == 0 ? r->served : m == 1 ? r->dropped : r->pending) / (double)r->nUE; return r->nUE > 0; }
+    if (m == 3) { *x = (double)r->restarted / (double)r->served; return r->served > 0; }
+    const int f = (m - NOMA_SUMMARY_FIXED_METRICS) / (1 + s->nq), j = (m - NOMA_SUMMARY_FIXED_METRICS) % (1 + s->nq);
+    if (r->n[f] == 0) return 0;
+    *x = j == 0 ? (double)r->sum[f] / (double)r->n[f] : (double)r->q[f][j - 1];
+    return 1;
+}
+
+int prach_noma_summary_stats(const prach_noma_summary_spec *s, const prach_noma_trial_summary *rows, int n, const int32_t *group, int ngroups, prach_stat *out) {
+    if (!prach_internal_noma_summary_spec_ok(s) || n < 0 || (n > 0 && !rows) || ngroups < 1 || !out || (!group && ngroups != 1)) return PRACH_ERR_ARG;
+    if (group)
+        for (int k = 0; k < n; k++)
+            if (group[k] < 0 || group[k] >= ngroups) return PRACH_ERR_ARG;
+    const int nm = NOMA_SUMMARY_FIXED_METRICS + s->nfields * (1 + s->nq);
+    memset(out, 0, sizeof(prach_stat) * (size_t)ngroups * (size_t)nm);
+    for (int m = 0; m < nm; m++) {
+        double x;
+        for (int k = 0; k < n; k++) { /* pass 1: count, sum, extremes */
+            if (!noma_summary_metric(s, &rows[k], m, &x)) continue;
+            prach_stat *const o = &out[(size_t)(group ? group[k] : 0) * (size_t)nm + (size_t)m];
+            if (o->n == 0 || x < o->min) o->min = x;
+            if (o->n == 0 || x > o->max) o->max = x;
+            o->n++;
+            o->mean += x;
+        }
+        for (int g = 0; g < ngroups; g++) {
+            prach_stat *const o = &out[(size_t)g * (size_t)nm + (size_t)m];
+            if (o->n) o->mean /= (double)o->n;
+        }
+        for (int k = 0; k < n; k++) { /* pass 2: squared deviations from the mean */
+            if (!noma_summary_metric(s, &rows[k], m, &x)) continue;
+            prach_stat *const o = &out[(size_t)(group ? group[k] : 0) * (size_t)nm + (size_t)m];
+            o->sd += (x - o->mean) * (x - o->mean);
+        }
+        for (int g = 0; g < ngroups; g++) {
+            prach_stat *const o = &out[(size_t)g * (size_t)nm + (size_t)m];
+            o->sd = o->n > 1 ? sqrt(o->sd / (double)(o->n - 1)) : 0.0;
+            o->sem = o->n > 1 ? o->sd / sqrt((double)o->n) : 0.0;
+        }
+    }
+    return PRACH_OK;
+}
+
+size_t prach_noma_summary_format_csv(const prach_noma_summary_spec *s, const prach_stat *st, const char *label, char *buf, size_t cap) {
+    static const char *const fixed[NOMA_SUMMARY_FIXED_METRICS] = {"served_ratio", "dropped_ratio", "pending_ratio", "restart_ratio"};
+    static const char *const names[PRACH_NOMA_NFIELDS] = {"one", "arrival", "sojourn", "completion", "timer", "ptc", "retx", "msg3fail", "age", "state", "sector", "preamble", "lost"};
+    if (!prach_internal_noma_summary_spec_ok(s) || !st || !label) return 0;
+    size_t off = 0;
+    const int nm = NOMA_SUMMARY_FIXED_METRICS + s->nfields * (1 + s->nq);
+    for (int m = 0; m < nm; m++) {
+        char name[32];
+        const int f = (m - NOMA_SUMMARY_FIXED_METRICS) / (1 + s->nq), j = (m - NOMA_SUMMARY_FIXED_METRICS) % (1 + s->nq);
+        if (m < NOMA_SUMMARY_FIXED_METRICS) snprintf(name, sizeof name, "%s", fixed[m]);
+        else if (j == 0) snprintf(name, sizeof name, "%s_mean", names[s->field[f]]);
+        else snprintf(name, sizeof name, "%s_p%d", names[s->field[f]], s->permille[j - 1]);
+        CSV_EMIT("%.200s,%s,%llu,%.9g,%.9g,%.9g,%.9g,%.9g\n", label, name, (unsigned long long)st[m].n, st[m].mean, st[m].sd, st[m].sem, st[m].min, st[m].max);
+    }
+    return csv_end(buf, cap, off);
+}
+
 /* ---- per-trial summaries: exact order statistics and the spread across trials (prach_run_trials_summary) ---- */
 
 static int summary_spec_ok(const prach_summary_spec *s) {

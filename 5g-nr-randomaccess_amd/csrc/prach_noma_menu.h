@@ -1,5 +1,6 @@
 // prach_noma_menu.h — THE NOMA MENU of include/prach.h (PRACH_NOMA_ONE ... PRACH_NOMA_LOST and the four classes), device side, ONE copy: what
-// prach::noma_census_kernel bins and prach::noma_columns_kernel stores (prach_noma_census.hip).  noma_value of prach_host.c is the host's statement.
+// prach::noma_census_kernel bins and prach::noma_columns_kernel stores (prach_noma_census.hip), and what prach::noma_summary_kernel ranks and
+// prach::noma_pick_kernel filters and ranks (prach_noma_select.hip).  noma_value of prach_host.c is the host's statement.
 //
 // A record is four 16-byte quarters: q0 idx, timer, active, txTime | q1 firstTxTime, secondTxTime, nowBackoff, preamble | q2 preambleChange (NOMA.c: the
 // sector), rarWindow, maxRarCounter (msg1ReTx), preambleTxCounter (nTxPreamble) | q3 msg2Flag, connectionRequest (msg3Wait), msg4Flag (RA), failCount

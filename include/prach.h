@@ -129,6 +129,10 @@ typedef struct prach_timing {
     int32_t trial_kernel_reruns; /* of fallback_trials: trials that were (also) rerun on the one-workgroup, index-ordered trial_kernel */
     int32_t noma_host_ues;       /* NOMA_C, Philox: UEs of the device-built activeUE table that the host recomputed with its libm (a value inside the
                                     device math library's error band of a rounding / comparison boundary: ~1e-6 of the UEs) */
+    double noma_summary_ms;      /* HIP-event time of the NOMA summary kernel launches (prach_run_trials_noma_summary) of the last call; 0 in every other call (such a
+                                    call leaves every other *_ms of a reduction 0) */
+    double noma_pick_ms;         /* HIP-event time of the NOMA pick kernel launches (prach_run_trials_noma_pick) of the last call; 0 in every other call (such a call
+                                    leaves every other *_ms of a reduction 0) */
     double noma_census_ms;       /* HIP-event time of the NOMA census kernel launches (prach_run_trials_noma_census) of the last call; 0 in every other call (a
                                     census call leaves every other *_ms of a reduction 0) */
     double noma_columns_ms;      /* HIP-event time of the NOMA columns kernel launches (prach_run_trials_noma_columns, prach_run_trials_noma_columns_device) of the
@@ -565,6 +569,85 @@ size_t prach_noma_census_format_csv(const prach_xtab_spec *, const prach_noma_ce
 int prach_noma_census_tile_ues(void); /* UEs of one trial that one workgroup of prach::noma_census_kernel reduces (tests place sizes around it) */
 /* THE DEFINITION prach::noma_columns_kernel equals, integer for integer: prach_columns_from_logs with the NOMA menu.  PRACH_ERR_UNSUPPORTED: not a NOMA_C cfg. */
 int prach_noma_columns_from_logs(const prach_columns_spec *, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, int32_t *out, uint64_t stride);
+
+/* Per-trial summaries of NOMA_C trials: ONE ROW PER TRIAL — the four class counts, and for up to four NAMED fields of THE NOMA MENU above, over the UEs of
+ * the classes in `who` whose value of the field is DEFINED (the menu's ONE RULE: >= 0), their number, sum, maximum and EXACT order statistics — selected on the
+ * device, so that the spread between the seeds of a sweep point can be stated (prach_noma_summary_stats); the census pools the seeds into shared cells and
+ * cannot.  NOMA's interesting quantities are spread over the classes (SOJOURN, TIMER, LOST and PTC of the served, AGE of the pending, RETX and MSG3FAIL of
+ * the arrived), so the spec names them.
+ * THE DEFINITION of a level is the summary's, taken per field: field x over its n[x] defined values in ONE trial at level m (permille) has rank
+ * r = max(1, (n[x] * m + 999) / 1000), in 64-bit integers; the value is the r-th smallest.  No bins, no interpolation.
+ * A defined value above prach_summary_max_value() (65 535) is a RANGE ERROR: it enters n, sum and max and no histogram; the levels of that field are -1 then
+ * and the call returns PRACH_ERR_INTERNAL, as for the summary.  No trial produces one (csrc/prach_noma_menu.h, csrc/prach_noma_select.hip state the bounds).
+ * `restarted` is counted over the SERVED UEs regardless of `who`: those whose LOST is defined and > 0. */
+#define PRACH_NOMA_SUMMARY_MAX_FIELDS 4
+typedef struct prach_noma_summary_spec {
+    int32_t who;                 /* PRACH_NOMA_* class bits, not 0 */
+    int32_t nfields;             /* 1 .. 4; the fields behind it must be 0 */
+    int32_t field[PRACH_NOMA_SUMMARY_MAX_FIELDS];   /* PRACH_NOMA_* ids; ONE is allowed (its levels are 0); a field may be named twice */
+    int32_t nq;                  /* 1 .. PRACH_SUMMARY_MAX_Q */
+    int32_t permille[PRACH_SUMMARY_MAX_Q];          /* 1 .. 1000; the levels behind nq are ignored, as in prach_summary_spec */
+    int32_t reserved[2];         /* 0 */
+} prach_noma_summary_spec;
+typedef struct prach_noma_trial_summary {   /* one per TRIAL */
+    int32_t status, nUE;
+    int32_t idle, served, dropped, pending;  /* counted regardless of `who`; their sum is nUE */
+    int32_t selected;                        /* class in `who` */
+    int32_t restarted;                       /* served UEs with LOST defined and > 0, regardless of `who` */
+    int32_t range_errors, reserved;
+    int32_t n[PRACH_NOMA_SUMMARY_MAX_FIELDS];    /* selected UEs whose value of field x is DEFINED */
+    int64_t sum[PRACH_NOMA_SUMMARY_MAX_FIELDS];  /* over those */
+    int32_t max[PRACH_NOMA_SUMMARY_MAX_FIELDS];  /* -1 if n[x] == 0 */
+    int32_t q[PRACH_NOMA_SUMMARY_MAX_FIELDS][PRACH_SUMMARY_MAX_Q]; /* -1 if n[x] == 0, level unused or field unused */
+} prach_noma_trial_summary;
+
+/* prach_run_trials plus one NOMA summary row per trial; the row contract is prach_run_trials_summary's: rows[n] is caller-owned and OVERWRITTEN; a trial that
+ * is not PRACH_OK carries its status and nUE, zeros, and -1 in every maximum and level; a trial the engine reruns — a split call, the resolver's ambiguity
+ * rerun — is written once, by the launch whose result is kept.  prach::noma_summary_kernel (csrc/prach_noma_select.hip) selects from the log records
+ * prach::noma_kernel writes ON THE DEVICE, one workgroup per trial.
+ * PRACH_ERR_ARG: a NULL spec or output; an unknown field or class bit, an empty `who`; nfields, nq or a level out of range; a non-zero unused field or
+ * reserved word;
+ * PRACH_ERR_UNSUPPORTED, before anything is launched: any cfg that is not NOMA_C; any NOMA_C cfg with rng_mode == PRACH_RNG_GLIBC.  PRACH_FLAG_NOMA_NONSECTOR
+ * is accepted. */
+int prach_run_trials_noma_summary(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs,
+                                  const prach_noma_summary_spec *spec, prach_noma_trial_summary *rows);
+/* NOMA summaries, host side (no device needed; both RNG modes).
+ * prach_noma_summary_from_logs OVERWRITES *row with the summary of one trial's per-UE log: THE DEFINITION prach::noma_summary_kernel equals, integer for
+ * integer (it sorts, so any int32 value is handled and range_errors is 0; status PRACH_OK).  steps is the trial's prach_result.steps.
+ * PRACH_ERR_UNSUPPORTED: a cfg that is not NOMA_C.  PRACH_ERR_ARG: a bad spec or cfg, a NULL pointer, nUE != cfg->nUE (no log content is refused). */
+int prach_noma_summary_from_logs(const prach_noma_summary_spec *, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE,
+                                 prach_noma_trial_summary *row);
+/* Mean and spread over the trials of each group, with prach_summary_stats' rules (groups, two passes in trial order, in doubles, sd and sem, n = 0 and 1):
+ * out[ngroups][4 + nfields * (1 + nq)], the metrics in this order:
+ *   served_ratio (served / nUE), dropped_ratio (dropped / nUE), pending_ratio (pending / nUE), restart_ratio (restarted / served),
+ *   then per field x, in the spec's order: <name>_mean (sum[x] / n[x]) and <name>_p<m> for every level, <name> the field's name in lower case.
+ * A row whose status is not PRACH_OK is skipped for every metric; a row with nUE == 0 for the three class ratios, one with served == 0 for restart_ratio, one
+ * with n[x] == 0 for field x's metrics.  PRACH_ERR_ARG: a bad spec, a NULL argument, a group id out of range. */
+int prach_noma_summary_stats(const prach_noma_summary_spec *, const prach_noma_trial_summary *rows, int n, const int32_t *group, int ngroups, prach_stat *out);
+/* one group (4 + nfields * (1 + nq) prach_stat) as text, in prach_summary_format_csv's line format */
+size_t prach_noma_summary_format_csv(const prach_noma_summary_spec *, const prach_stat *stats_of_one_group, const char *label, char *buf, size_t cap);
+
+/* Pick per trial of NOMA_C trials, selected on the device: WHICH UEs stand behind a count of the census — the contract of prach_run_trials_pick word for word
+ * (selected, matched and undefined; the three orders; stored = min(matched, k), threshold and ties_left_out; OVERWRITTEN outputs, zero rows behind `stored`, a
+ * rerun trial written once; keys RANKED in 0 .. prach_summary_max_value(), range_errors voiding the trial's rows and failing the call with
+ * PRACH_ERR_INTERNAL), with a prach_pick_spec whose `who` is PRACH_NOMA_* class bits (all four) and whose clause fields and key field are PRACH_NOMA_* ids, the
+ * values those of THE NOMA MENU above with its ONE RULE.  The header is prach_pick, a row the 80-byte prach_pick_row: the log record as logged, a(i) (-1 for an
+ * IDLE UE) and the key.  No trial produces a key outside the ranked range: ARRIVAL, COMPLETION and AGE are subframe numbers of a trial of 10 000 + 6 subframes,
+ * SOJOURN and LOST at most that, STATE at most 8, SECTOR at most 5, MSG3FAIL the upper half of a word; TIMER, PTC, RETX and PREAMBLE are logged words that
+ * grow by at most one per subframe or name one of at most 64 preambles (csrc/prach_noma_select.hip restates the bounds).
+ * prach::noma_pick_kernel (csrc/prach_noma_select.hip) selects from the log records prach::noma_kernel writes ON THE DEVICE, one workgroup per trial, and
+ * leaves a trial's rows in UE-index order; the engine sorts the at most k rows of a trial into the defined order on the host.
+ * PRACH_ERR_ARG: the argument cases of prach_run_trials_pick, with NOMA's ids and bits;
+ * PRACH_ERR_UNSUPPORTED, before anything is launched: any cfg that is not NOMA_C; any NOMA_C cfg with rng_mode == PRACH_RNG_GLIBC; n * k * 10 + n * 8 > 2^27
+ * words.  PRACH_FLAG_NOMA_NONSECTOR is accepted. */
+int prach_run_trials_noma_pick(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_pick_spec *spec,
+                               prach_pick *picks, prach_pick_row *rows);
+/* THE DEFINITION prach::noma_pick_kernel plus the engine's sort equal, integer for integer (no device needed; both RNG modes): the pick of ONE trial from its
+ * per-UE log; steps is the trial's prach_result.steps.  It lists and sorts, so any int32 key is handled and its range_errors is 0.  PRACH_ERR_ARG: a bad spec
+ * or cfg, a NULL pointer, nUE != cfg->nUE; PRACH_ERR_UNSUPPORTED: a cfg that is not NOMA_C.  _format_csv writes prach_pick_format_csv's lines. */
+int prach_noma_pick_from_logs(const prach_pick_spec *, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_pick *hdr, prach_pick_row *rows);
+size_t prach_noma_pick_format_csv(const prach_pick_spec *, const prach_pick *, const prach_pick_row *rows, const char *label, int trial, uint64_t seed, char *buf,
+                                  size_t cap);
 
 /* Per-subframe preamble trace per trial group, recorded by the simulation kernels WHILE THEY RUN and reduced on the device: how many preambles were used,
  * decoded and collided in each stretch of the simulation — the quantities TR 37.868's collision probability is defined on.  Unlike the four reductions above
