@@ -19,70 +19,18 @@
 // THE BOUND: every menu value of a trial fits int32.  ARRIVAL, COMPLETION and AGE are subframe numbers of a trial of at most 60 000 + 6 subframes, SOJOURN is
 // at most TL_MAX_SOJOURN, TIMER, PTC and FAILCOUNT are logged int32 words, STATE is at most 6; xt_value computes in 64 bits and the column takes the low
 // word.  A NEGATIVE menu value is UNDEFINED (the one rule of the menu) and is stored as -1; a raw word is stored as it is.
-#include "prach_reduce_tile.h"
+// THE BODY is columns_body<XtabMenu> of prach_menu_body.h, shared with prach::noma_columns_kernel; the kernel's name, arguments and launch are here.
+#include "prach_menu_body.h"
 #include "prach_xtab_menu.h"
 
 namespace prach {
 
 namespace {
 
-// word w (0 .. 15) of a record from its four quarters; w is uniform
-__device__ __forceinline__ int record_word(int w, const int4 &q0, const int4 &q1, const int4 &q2, const int4 &q3) {
-    const int4 q = (w >> 2) == 0 ? q0 : (w >> 2) == 1 ? q1 : (w >> 2) == 2 ? q2 : q3;
-    return (w & 3) == 0 ? q.x : (w & 3) == 1 ? q.y : (w & 3) == 2 ? q.z : q.w;
-}
+static_assert(XtabMenu::NCLASSES == CL_SUMS, "the body's scalar row is the one prach_device.h states");
 
 __global__ __launch_bounds__(TL_THREADS) void columns_kernel(const TimelineJob *__restrict__ jobs, int njobs, prach_columns_spec sp, ColumnsOut out) {
-    __shared__ int lsched[TILE_SCHED_CAP];
-    __shared__ unsigned long long lsc[CL_SCALARS];
-    const int tid = threadIdx.x, lane = tid & 63;
-
-    const TimelineJob J = job_of_workgroup(jobs, njobs);
-    const int first = ((int)blockIdx.x - J.wg0) * TL_TILE;
-    const int end = min(J.nUE, first + TL_TILE);
-    const int E = J.pad;
-
-    // what the columns need, as 0 / 1
-    int need_a = 0, need_q1 = 0, need_q2 = 0;
-    for (int c = 0; c < sp.ncols; c++) {
-        const int f = sp.field[c], w = f - PRACH_COL_RAW;
-        need_a |= (int)needs_arrival(f);
-        need_q1 |= (int)(f == PRACH_XTAB_STATE) | (int)((w >> 2) == 1);
-        need_q2 |= (int)(f == PRACH_XTAB_PTC) | (int)((w >> 2) == 2);
-    }
-
-    // the tile's slot range, only where a column needs it: no search and no copy otherwise
-    TileSlots S{0, 0, J.sched, 0};
-    if (need_a) S = tile_slots<TL_THREADS>(J, first, end, lsched, tid);
-    if (tid < CL_SCALARS) lsc[tid] = 0;
-    __syncthreads();
-
-    int *const col0 = out.data + out.offset[J.group]; // the trial's segment of column 0
-    unsigned nidle = 0, nserved = 0, nunserved = 0;
-    for (int i = first + tid; i < end; i += TL_THREADS) {
-        const int4 head = J.logs[4 * (size_t)i];     // idx, timer, active, txTime
-        const int4 tail = J.logs[4 * (size_t)i + 3]; // msg2Flag, connectionRequest, msg4Flag, failCount
-        int4 q1 = make_int4(0, 0, 0, 0), q2 = make_int4(0, 0, 0, 0);
-        if (need_q1) q1 = J.logs[4 * (size_t)i + 1]; // firstTxTime, secondTxTime, nowBackoff, preamble
-        if (need_q2) q2 = J.logs[4 * (size_t)i + 2]; // preambleChange, rarWindow, maxRarCounter, preambleTxCounter
-        const int cls = head.z == -1 ? 0 : tail.z == 1 ? 1 : 2;
-        nidle += cls == 0; nserved += cls == 1; nunserved += cls == 2;
-        const int a = need_a ? S.arrival(J, i) : 0;
-        for (int c = 0; c < sp.ncols; c++) {
-            const int f = sp.field[c];
-            int v;
-            if (f >= PRACH_COL_RAW) v = record_word(f - PRACH_COL_RAW, head, q1, q2, tail);
-            else {
-                const long long x = xt_value(f, head, tail, q1.z, q2.w, cls, a, E);
-                v = x < 0 ? -1 : (int)x;
-            }
-            col0[(size_t)c * out.stride + (size_t)i] = v;
-        }
-    }
-    nidle = fold_sum(nidle); nserved = fold_sum(nserved); nunserved = fold_sum(nunserved);
-    if (lane == 0) { atomicAdd(&lsc[0], (unsigned long long)nidle); atomicAdd(&lsc[1], (unsigned long long)nserved); atomicAdd(&lsc[2], (unsigned long long)nunserved); }
-    __syncthreads();
-    flush_scalars(lsc, out.scalars + (size_t)J.group * CL_SCALARS, CL_SUMS, 0, tid);
+    columns_body<XtabMenu>(jobs, njobs, sp, out);
 }
 
 } // namespace

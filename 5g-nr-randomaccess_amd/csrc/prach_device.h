@@ -264,8 +264,9 @@ hipError_t launch_columns_kernel(const TimelineJob *jobs, int njobs, int workgro
 // prach_noma_census.hip: the census and the columns of a launch's accepted NOMA.c trials over THE NOMA MENU of include/prach.h (prach_run_trials_noma_census,
 // prach_run_trials_noma_columns, _device).  Jobs, tile, workgroup, table paths and column layout are those of prach_xtab.hip and prach_columns.hip above; NOMA
 // has four classes, so a group's scalar row and a trial's count one more.
-constexpr int NC_SCALARS = 16, NC_SUMS = 8, NC_MAXIMA = 2; // per group: idle, served, dropped, pending, selected, binned, row_sum, col_sum | row_max + 1, col_max + 1 (0: nothing binned) | 6 spare
-constexpr int NCL_SCALARS = 4, NCL_SUMS = 4;               // per trial: idle, served, dropped, pending
+constexpr int NC_SCALARS = XT_SCALARS, NC_SUMS = 8, NC_MAXIMA = XT_MAXIMA; // per group: idle, served, dropped, pending, selected, binned, row_sum, col_sum | row_max + 1, col_max + 1 (0: nothing binned) | 6 spare
+constexpr int NCL_SCALARS = CL_SCALARS, NCL_SUMS = 4;                      // per trial: idle, served, dropped, pending
+static_assert(NC_SCALARS == XT_SCALARS && NC_MAXIMA == XT_MAXIMA && NCL_SCALARS == CL_SCALARS, "one row size per kind for both menus: the kernels' bodies are shared (prach_menu_body.h)");
 extern "C" int prach_internal_noma_census_spec_ok(const prach_xtab_spec *spec);     // prach_host.c
 extern "C" int prach_internal_noma_columns_spec_ok(const prach_columns_spec *spec); // prach_host.c
 hipError_t launch_noma_census_kernel(const TimelineJob *jobs, int njobs, int workgroups, XtabAxes ax, int scheme, XtabOut out, hipStream_t stream); // ax: a valid spec's

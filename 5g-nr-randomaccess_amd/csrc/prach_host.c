@@ -868,17 +868,9 @@ size_t prach_sojourn_format_csv(const prach_sojourn_spec *s, const prach_sojourn
     return csv_end(buf, cap, off);
 }
 
-/* ---- outcome cross-tabulation per trial group (prach_run_trials_xtab) ----------------------------- */
+/* ---- the two menus of per-UE quantities (include/prach.h) and THE DEFINITIONS over them: census, columns, pick ---- */
 
-static int xtab_axis_ok(int field, int width, int bins) {
-    return field >= 0 && field < PRACH_XTAB_NFIELDS && width >= 1 && bins >= 1 && bins <= PRACH_XTAB_MAX_BINS;
-}
-static int xtab_spec_ok(const prach_xtab_spec *s) {
-    return s && s->who > 0 && (s->who & ~(PRACH_XTAB_SERVED | PRACH_XTAB_UNSERVED | PRACH_XTAB_IDLE)) == 0 && xtab_axis_ok(s->row_field, s->row_width, s->row_bins) &&
-           xtab_axis_ok(s->col_field, s->col_width, s->col_bins) && s->reserved[0] == 0 && s->reserved[1] == 0;
-}
-
-/* the class bit of a UE and its STATE (include/prach.h) */
+/* the menu of PRACH_XTAB_*: the class bit of a UE and its STATE */
 static int xtab_class(const prach_ue_log *u) {
     return u->active == -1 ? PRACH_XTAB_IDLE : u->msg4Flag == 1 ? PRACH_XTAB_SERVED : PRACH_XTAB_UNSERVED;
 }
@@ -906,43 +898,260 @@ static int64_t xtab_value(int field, const prach_ue_log *u, int cls, int64_t a, 
     }
 }
 
-/* THE DEFINITION (include/prach.h) */
-int prach_xtab_accumulate_logs(const prach_xtab_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_xtab *x, uint64_t *cells) {
-    if (!xtab_spec_ok(s) || !cfg || !x || !cells || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
-    if (cfg->variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED;
-    if (prach_cfg_validate(cfg) != PRACH_OK || nUE != cfg->nUE) return PRACH_ERR_ARG;
-    const int nslots = (prach_max_time(cfg) + cfg->accessTime - 1) / cfg->accessTime;
-    int32_t *sched = (int32_t *)malloc(sizeof(int32_t) * (size_t)nslots);
-    if (!sched) return PRACH_ERR_INTERNAL;
-    prach_arrival_schedule(cfg, sched, nslots, NULL);
-    const int64_t E = steps < (uint64_t)prach_max_time(cfg) ? (int64_t)steps : (int64_t)prach_max_time(cfg);
-    if (x->trials == 0 && x->binned == 0) x->row_max = x->col_max = -1; /* (a zero-filled group is an empty one) */
+/* the menu of PRACH_NOMA_*: the class bit of a UE and its STATE */
+static int noma_class(const prach_ue_log *u) {
+    if (u->preambleChange == -1) return PRACH_NOMA_IDLE;
+    if (u->msg4Flag == 1) return PRACH_NOMA_SERVED;
+    return (u->failCount & 0xffff) != 0 ? PRACH_NOMA_DROPPED : PRACH_NOMA_PENDING;
+}
+static int noma_state(const prach_ue_log *u, int cls, int64_t E) {
+    if (cls == PRACH_NOMA_IDLE) return 0;
+    if (cls == PRACH_NOMA_SERVED) return 1;
+    if (cls == PRACH_NOMA_DROPPED) return 2;
+    if (u->active == 1) return u->nowBackoff > 0 ? 3 : (int64_t)u->txTime >= E ? 4 : 5;
+    if (u->active == 2) return u->connectionRequest == 0 ? 6 : 7;
+    return 8;
+}
+static int64_t noma_value(int field, const prach_ue_log *u, int cls, int64_t a, int64_t E) {
+    const int arrived = cls != PRACH_NOMA_IDLE, served = cls == PRACH_NOMA_SERVED;
+    switch (field) {
+    case PRACH_NOMA_ONE: return 0;
+    case PRACH_NOMA_ARRIVAL: return arrived ? a : -1;
+    case PRACH_NOMA_SOJOURN: return served ? (int64_t)u->txTime + 6 - a : -1;
+    case PRACH_NOMA_COMPLETION: return served ? (int64_t)u->txTime + 6 : -1;
+    case PRACH_NOMA_TIMER: return arrived ? u->timer : -1;
+    case PRACH_NOMA_PTC: return arrived ? u->preambleTxCounter : -1;
+    case PRACH_NOMA_RETX: return arrived ? u->maxRarCounter : -1;
+    case PRACH_NOMA_MSG3FAIL: return arrived ? (int64_t)(u->failCount >> 16) : -1; /* (arithmetic shift: a negative word is undefined) */
+    case PRACH_NOMA_AGE: return arrived ? E - a : -1;
+    case PRACH_NOMA_STATE: return noma_state(u, cls, E);
+    case PRACH_NOMA_SECTOR: return arrived ? u->preambleChange : -1;
+    case PRACH_NOMA_PREAMBLE: return arrived ? u->preamble : -1;
+    default: /* LOST: a negative sojourn or timer makes it undefined, and so does a timer beyond the sojourn */
+        if (!served) return -1;
+        { const int64_t sj = (int64_t)u->txTime + 6 - a; return sj < 0 || u->timer < 0 ? -1 : sj - u->timer; }
+    }
+}
+
+/* what a definition needs to know about a menu */
+#define MENU_MAX_CLASSES 4
+typedef struct host_menu {
+    int (*class_of)(const prach_ue_log *u);
+    int64_t (*value)(int field, const prach_ue_log *u, int cls, int64_t a, int64_t E);
+    int classes, nfields, idle;              /* every class bit; the number of fields; the idle bit */
+    int nclasses, counter[MENU_MAX_CLASSES]; /* the class bits in the order of the class counters */
+    int noma_c;                              /* the cfgs the menu is defined for: 1 NOMA_C only, 0 every other variant (the rest: PRACH_ERR_UNSUPPORTED) */
+} host_menu;
+#define NOMA_ALL_CLASSES (PRACH_NOMA_SERVED | PRACH_NOMA_PENDING | PRACH_NOMA_IDLE | PRACH_NOMA_DROPPED)
+static const host_menu XTAB_MENU = {xtab_class, xtab_value, PRACH_XTAB_SERVED | PRACH_XTAB_UNSERVED | PRACH_XTAB_IDLE, PRACH_XTAB_NFIELDS, PRACH_XTAB_IDLE,
+                                    3, {PRACH_XTAB_IDLE, PRACH_XTAB_SERVED, PRACH_XTAB_UNSERVED, 0}, 0};
+static const host_menu NOMA_MENU = {noma_class, noma_value, NOMA_ALL_CLASSES, PRACH_NOMA_NFIELDS, PRACH_NOMA_IDLE,
+                                    4, {PRACH_NOMA_IDLE, PRACH_NOMA_SERVED, PRACH_NOMA_DROPPED, PRACH_NOMA_PENDING}, 1};
+
+/* the schedule of a cfg of the menu's variants and E = min(steps, maxTime); NULL: a status is in *rc (ARG before UNSUPPORTED before the cfg's own validity) */
+static int32_t *menu_schedule(const host_menu *m, const prach_cfg *cfg, int nUE, uint64_t steps, int *nslots, int64_t *E, int *rc) {
+    *rc = PRACH_ERR_ARG;
+    if (!cfg) return NULL;
+    if ((cfg->variant == PRACH_VARIANT_NOMA_C) != m->noma_c) { *rc = PRACH_ERR_UNSUPPORTED; return NULL; }
+    if (prach_cfg_validate(cfg) != PRACH_OK || nUE != cfg->nUE) return NULL;
+    *nslots = (prach_max_time(cfg) + cfg->accessTime - 1) / cfg->accessTime;
+    int32_t *sched = (int32_t *)malloc(sizeof(int32_t) * (size_t)*nslots);
+    if (!sched) { *rc = PRACH_ERR_INTERNAL; return NULL; }
+    prach_arrival_schedule(cfg, sched, *nslots, NULL);
+    *E = steps < (uint64_t)prach_max_time(cfg) ? (int64_t)steps : (int64_t)prach_max_time(cfg);
+    *rc = PRACH_OK;
+    return sched;
+}
+
+/* the three judges of a spec */
+static int menu_axis_ok(const host_menu *m, int field, int width, int bins) {
+    return field >= 0 && field < m->nfields && width >= 1 && bins >= 1 && bins <= PRACH_XTAB_MAX_BINS;
+}
+static int menu_census_spec_ok(const host_menu *m, const prach_xtab_spec *s) {
+    return s && s->who > 0 && (s->who & ~m->classes) == 0 && menu_axis_ok(m, s->row_field, s->row_width, s->row_bins) &&
+           menu_axis_ok(m, s->col_field, s->col_width, s->col_bins) && s->reserved[0] == 0 && s->reserved[1] == 0;
+}
+static int menu_columns_spec_ok(const host_menu *m, const prach_columns_spec *s) {
+    if (!s || s->ncols < 1 || s->ncols > PRACH_COL_MAX || s->reserved[0] || s->reserved[1] || s->reserved[2]) return 0;
+    for (int c = 0; c < s->ncols; c++) {
+        const int f = s->field[c];
+        if (!((f >= 0 && f < m->nfields) || (f >= PRACH_COL_RAW && f < PRACH_COL_RAW + 16))) return 0;
+    }
+    return 1;
+}
+static int menu_pick_spec_ok(const host_menu *m, const prach_pick_spec *s) {
+    if (!s || s->who <= 0 || (s->who & ~m->classes) != 0 || s->nclauses < 0 || s->nclauses > PRACH_PICK_MAX_CLAUSES || s->k < 1 || s->k > PRACH_PICK_MAX_K ||
+        s->reserved != 0 || s->key_field < 0 || s->key_field >= m->nfields) return 0;
+    if (s->order != PRACH_PICK_BY_INDEX && s->order != PRACH_PICK_LARGEST && s->order != PRACH_PICK_SMALLEST) return 0;
+    if (s->order == PRACH_PICK_BY_INDEX && s->key_field != 0) return 0; /* (field 0 is ONE in both menus) */
+    for (int c = 0; c < PRACH_PICK_MAX_CLAUSES; c++) {
+        const prach_pick_clause *q = &s->clause[c];
+        if (c < s->nclauses ? (q->field < 0 || q->field >= m->nfields || q->lo < 0 || q->lo > q->hi) : (q->field || q->lo || q->hi)) return 0;
+    }
+    return 1;
+}
+/* (the engine judges a spec with these too: csrc/prach_device.h) */
+static int xtab_spec_ok(const prach_xtab_spec *s) { return menu_census_spec_ok(&XTAB_MENU, s); }
+int prach_internal_noma_census_spec_ok(const prach_xtab_spec *s) { return menu_census_spec_ok(&NOMA_MENU, s); }
+int prach_internal_columns_spec_ok(const prach_columns_spec *s) { return menu_columns_spec_ok(&XTAB_MENU, s); }
+int prach_internal_noma_columns_spec_ok(const prach_columns_spec *s) { return menu_columns_spec_ok(&NOMA_MENU, s); }
+int prach_internal_pick_spec_ok(const prach_pick_spec *s) { return menu_pick_spec_ok(&XTAB_MENU, s); }
+int prach_internal_noma_pick_spec_ok(const prach_pick_spec *s) { return menu_pick_spec_ok(&NOMA_MENU, s); }
+
+/* THE DEFINITION of the census (prach_xtab_accumulate_logs, prach_noma_census_accumulate_logs).  The two group structs differ in their class counters, so the
+ * loop reaches a group through pointers to its words */
+typedef struct census_group {
+    uint64_t *trials, *ues, *cls[MENU_MAX_CLASSES], *selected, *binned, *undefined, *row_sum, *col_sum;
+    int64_t *row_max, *col_max;
+} census_group;
+static int menu_census_accumulate(const host_menu *m, const prach_xtab_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE,
+                                  const census_group *x, uint64_t *cells) {
+    if (!menu_census_spec_ok(m, s) || !cfg || !cells || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    int nslots = 0, rc;
+    int64_t E = 0;
+    int32_t *sched = menu_schedule(m, cfg, nUE, steps, &nslots, &E, &rc);
+    if (!sched) return rc;
+    if (*x->trials == 0 && *x->binned == 0) *x->row_max = *x->col_max = -1; /* (a zero-filled group is an empty one) */
     int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
     for (int i = 0; i < nUE; i++) {
         while (slot < nslots && sched[slot] <= i) slot++;
         const int64_t a = (int64_t)cfg->accessTime * slot;
-        const int cls = xtab_class(&ue[i]);
-        if (cls == PRACH_XTAB_IDLE) x->idle++;
-        else if (cls == PRACH_XTAB_SERVED) x->served++;
-        else x->unserved++;
+        const int cls = m->class_of(&ue[i]);
+        for (int k = 0; k < m->nclasses; k++)
+            if (cls == m->counter[k]) (*x->cls[k])++;
         if (!(cls & s->who)) continue;
-        x->selected++;
-        const int64_t rv = xtab_value(s->row_field, &ue[i], cls, a, E), cv = xtab_value(s->col_field, &ue[i], cls, a, E);
-        if (rv < 0 || cv < 0) { x->undefined++; continue; }
+        (*x->selected)++;
+        const int64_t rv = m->value(s->row_field, &ue[i], cls, a, E), cv = m->value(s->col_field, &ue[i], cls, a, E);
+        if (rv < 0 || cv < 0) { (*x->undefined)++; continue; }
         const int64_t rq = rv / s->row_width, cq = cv / s->col_width;
         const size_t r = rq < s->row_bins ? (size_t)rq : (size_t)s->row_bins, c = cq < s->col_bins ? (size_t)cq : (size_t)s->col_bins;
         cells[r * ((size_t)s->col_bins + 1) + c]++;
-        x->binned++;
-        x->row_sum += (uint64_t)rv;
-        x->col_sum += (uint64_t)cv;
-        if (rv > x->row_max) x->row_max = rv;
-        if (cv > x->col_max) x->col_max = cv;
+        (*x->binned)++;
+        *x->row_sum += (uint64_t)rv;
+        *x->col_sum += (uint64_t)cv;
+        if (rv > *x->row_max) *x->row_max = rv;
+        if (cv > *x->col_max) *x->col_max = cv;
     }
     free(sched);
-    x->trials++;
-    x->ues += (uint64_t)nUE;
+    (*x->trials)++;
+    *x->ues += (uint64_t)nUE;
     return PRACH_OK;
 }
+int prach_xtab_accumulate_logs(const prach_xtab_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_xtab *x, uint64_t *cells) {
+    if (!x) return PRACH_ERR_ARG;
+    const census_group g = {&x->trials, &x->ues, {&x->idle, &x->served, &x->unserved, NULL}, &x->selected, &x->binned, &x->undefined, &x->row_sum, &x->col_sum,
+                            &x->row_max, &x->col_max};
+    return menu_census_accumulate(&XTAB_MENU, s, cfg, steps, ue, nUE, &g, cells);
+}
+int prach_noma_census_accumulate_logs(const prach_xtab_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_noma_census *x,
+                                      uint64_t *cells) {
+    if (!x) return PRACH_ERR_ARG;
+    const census_group g = {&x->trials, &x->ues, {&x->idle, &x->served, &x->dropped, &x->pending}, &x->selected, &x->binned, &x->undefined, &x->row_sum, &x->col_sum,
+                            &x->row_max, &x->col_max};
+    return menu_census_accumulate(&NOMA_MENU, s, cfg, steps, ue, nUE, &g, cells);
+}
+
+/* THE DEFINITION of the columns (prach_columns_from_logs, prach_noma_columns_from_logs) */
+static int menu_columns(const host_menu *m, const prach_columns_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, int32_t *out,
+                        uint64_t stride) {
+    if (!menu_columns_spec_ok(m, s) || !cfg || !out || nUE < 0 || (nUE > 0 && !ue) || stride < (uint64_t)nUE) return PRACH_ERR_ARG;
+    int nslots = 0, rc;
+    int64_t E = 0;
+    int32_t *sched = menu_schedule(m, cfg, nUE, steps, &nslots, &E, &rc);
+    if (!sched) return rc;
+    int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
+    for (int i = 0; i < nUE; i++) {
+        while (slot < nslots && sched[slot] <= i) slot++;
+        const int64_t a = (int64_t)cfg->accessTime * slot;
+        const int cls = m->class_of(&ue[i]);
+        for (int c = 0; c < s->ncols; c++) {
+            const int f = s->field[c];
+            int32_t v;
+            if (f >= PRACH_COL_RAW) v = ((const int32_t *)&ue[i])[f - PRACH_COL_RAW]; /* the log word as it is */
+            else {
+                const int64_t x = m->value(f, &ue[i], cls, a, E);
+                v = x < 0 ? -1 : (int32_t)x; /* a negative value is UNDEFINED */
+            }
+            out[(size_t)c * (size_t)stride + (size_t)i] = v;
+        }
+    }
+    free(sched);
+    return PRACH_OK;
+}
+int prach_columns_from_logs(const prach_columns_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, int32_t *out, uint64_t stride) {
+    return menu_columns(&XTAB_MENU, s, cfg, steps, ue, nUE, out, stride);
+}
+int prach_noma_columns_from_logs(const prach_columns_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, int32_t *out, uint64_t stride) {
+    return menu_columns(&NOMA_MENU, s, cfg, steps, ue, nUE, out, stride);
+}
+
+/* THE DEFINITION of the pick (prach_pick_from_logs, prach_noma_pick_from_logs): every match is listed, the list is sorted, the first k are the rows */
+typedef struct pick_cand { int64_t key; int32_t i, arrival; } pick_cand;
+static int cmp_pick_desc(const void *a, const void *b) { /* descending key, equal keys in ascending UE index */
+    const pick_cand *x = (const pick_cand *)a, *y = (const pick_cand *)b;
+    return x->key != y->key ? (x->key < y->key) - (x->key > y->key) : (x->i > y->i) - (x->i < y->i);
+}
+static int cmp_pick_asc(const void *a, const void *b) {
+    const pick_cand *x = (const pick_cand *)a, *y = (const pick_cand *)b;
+    return x->key != y->key ? (x->key > y->key) - (x->key < y->key) : (x->i > y->i) - (x->i < y->i);
+}
+static int menu_pick(const host_menu *m, const prach_pick_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_pick *hdr,
+                     prach_pick_row *rows) {
+    if (!menu_pick_spec_ok(m, s) || !cfg || !hdr || !rows || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    int nslots = 0, rc;
+    int64_t E = 0;
+    int32_t *sched = menu_schedule(m, cfg, nUE, steps, &nslots, &E, &rc);
+    if (!sched) return rc;
+    pick_cand *cand = (pick_cand *)malloc(sizeof(pick_cand) * (size_t)(nUE > 0 ? nUE : 1));
+    if (!cand) { free(sched); return PRACH_ERR_INTERNAL; }
+    const int keyed = s->order != PRACH_PICK_BY_INDEX;
+    prach_pick h;
+    memset(&h, 0, sizeof h);
+    h.status = PRACH_OK; h.nUE = nUE; h.threshold = -1;
+    int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
+    for (int i = 0; i < nUE; i++) {
+        while (slot < nslots && sched[slot] <= i) slot++;
+        const int64_t a = (int64_t)cfg->accessTime * slot;
+        const int cls = m->class_of(&ue[i]);
+        if (!(cls & s->who)) continue;
+        h.selected++;
+        int fails = 0, undef = 0;
+        for (int c = 0; c < s->nclauses; c++) {
+            const int64_t v = m->value(s->clause[c].field, &ue[i], cls, a, E);
+            if (v < 0) undef = 1;
+            else if (v < s->clause[c].lo || v > s->clause[c].hi) fails = 1;
+        }
+        const int64_t key = keyed ? m->value(s->key_field, &ue[i], cls, a, E) : 0;
+        if (key < 0) undef = 1;
+        if (fails) continue;
+        if (undef) { h.undefined++; continue; }
+        cand[h.matched++] = (pick_cand){key, i, cls == m->idle ? -1 : (int32_t)a};
+    }
+    if (keyed) qsort(cand, (size_t)h.matched, sizeof(pick_cand), s->order == PRACH_PICK_LARGEST ? cmp_pick_desc : cmp_pick_asc);
+    h.stored = h.matched < s->k ? h.matched : s->k;
+    memset(rows, 0, sizeof(prach_pick_row) * (size_t)s->k);
+    for (int r = 0; r < h.stored; r++) {
+        rows[r].log = ue[cand[r].i];
+        rows[r].arrival = cand[r].arrival;
+        rows[r].key = (int32_t)cand[r].key;
+    }
+    if (keyed && h.stored > 0) {
+        h.threshold = rows[h.stored - 1].key;
+        for (int r = h.stored; r < h.matched && cand[r].key == cand[h.stored - 1].key; r++) h.ties_left_out++;
+    }
+    free(sched);
+    free(cand);
+    *hdr = h;
+    return PRACH_OK;
+}
+int prach_pick_from_logs(const prach_pick_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_pick *hdr, prach_pick_row *rows) {
+    return menu_pick(&XTAB_MENU, s, cfg, steps, ue, nUE, hdr, rows);
+}
+int prach_noma_pick_from_logs(const prach_pick_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_pick *hdr, prach_pick_row *rows) {
+    return menu_pick(&NOMA_MENU, s, cfg, steps, ue, nUE, hdr, rows);
+}
+
+/* ---- outcome cross-tabulation per trial group (prach_run_trials_xtab): merge, quantile, CSV ---------- */
 
 void prach_xtab_merge(const prach_xtab_spec *s, prach_xtab *into, uint64_t *cells_into, const prach_xtab *from, const uint64_t *cells_from) {
     if (!xtab_spec_ok(s) || !into || !cells_into || !from || !cells_from) return;
@@ -993,154 +1202,7 @@ size_t prach_xtab_format_csv(const prach_xtab_spec *s, const prach_xtab *x, cons
     return csv_end(buf, cap, off);
 }
 
-/* ---- columns: the menu's fields of every UE (prach_run_trials_columns) ---------------------------- */
-
-/* (the engine judges a spec with this too: csrc/prach_device.h) */
-int prach_internal_columns_spec_ok(const prach_columns_spec *s) {
-    if (!s || s->ncols < 1 || s->ncols > PRACH_COL_MAX || s->reserved[0] || s->reserved[1] || s->reserved[2]) return 0;
-    for (int c = 0; c < s->ncols; c++) {
-        const int f = s->field[c];
-        if (!((f >= 0 && f < PRACH_XTAB_NFIELDS) || (f >= PRACH_COL_RAW && f < PRACH_COL_RAW + 16))) return 0;
-    }
-    return 1;
-}
-
-/* THE DEFINITION (include/prach.h) */
-int prach_columns_from_logs(const prach_columns_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, int32_t *out, uint64_t stride) {
-    if (!prach_internal_columns_spec_ok(s) || !cfg || !out || nUE < 0 || (nUE > 0 && !ue) || stride < (uint64_t)nUE) return PRACH_ERR_ARG;
-    if (cfg->variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED;
-    if (prach_cfg_validate(cfg) != PRACH_OK || nUE != cfg->nUE) return PRACH_ERR_ARG;
-    const int nslots = (prach_max_time(cfg) + cfg->accessTime - 1) / cfg->accessTime;
-    int32_t *sched = (int32_t *)malloc(sizeof(int32_t) * (size_t)nslots);
-    if (!sched) return PRACH_ERR_INTERNAL;
-    prach_arrival_schedule(cfg, sched, nslots, NULL);
-    const int64_t E = steps < (uint64_t)prach_max_time(cfg) ? (int64_t)steps : (int64_t)prach_max_time(cfg);
-    int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
-    for (int i = 0; i < nUE; i++) {
-        while (slot < nslots && sched[slot] <= i) slot++;
-        const int64_t a = (int64_t)cfg->accessTime * slot;
-        const int cls = xtab_class(&ue[i]);
-        for (int c = 0; c < s->ncols; c++) {
-            const int f = s->field[c];
-            int32_t v;
-            if (f >= PRACH_COL_RAW) v = ((const int32_t *)&ue[i])[f - PRACH_COL_RAW]; /* the log word as it is */
-            else {
-                const int64_t x = xtab_value(f, &ue[i], cls, a, E);
-                v = x < 0 ? -1 : (int32_t)x; /* a negative value is UNDEFINED */
-            }
-            out[(size_t)c * (size_t)stride + (size_t)i] = v;
-        }
-    }
-    free(sched);
-    return PRACH_OK;
-}
-
-/* ---- the NOMA menu: census and columns of NOMA.c trials (prach_run_trials_noma_census, _noma_columns) ---- */
-
-#define NOMA_ALL_CLASSES (PRACH_NOMA_SERVED | PRACH_NOMA_PENDING | PRACH_NOMA_IDLE | PRACH_NOMA_DROPPED)
-static int noma_axis_ok(int field, int width, int bins) {
-    return field >= 0 && field < PRACH_NOMA_NFIELDS && width >= 1 && bins >= 1 && bins <= PRACH_XTAB_MAX_BINS;
-}
-/* (the engine judges a spec with these too: csrc/prach_device.h) */
-int prach_internal_noma_census_spec_ok(const prach_xtab_spec *s) {
-    return s && s->who > 0 && (s->who & ~NOMA_ALL_CLASSES) == 0 && noma_axis_ok(s->row_field, s->row_width, s->row_bins) &&
-           noma_axis_ok(s->col_field, s->col_width, s->col_bins) && s->reserved[0] == 0 && s->reserved[1] == 0;
-}
-int prach_internal_noma_columns_spec_ok(const prach_columns_spec *s) {
-    if (!s || s->ncols < 1 || s->ncols > PRACH_COL_MAX || s->reserved[0] || s->reserved[1] || s->reserved[2]) return 0;
-    for (int c = 0; c < s->ncols; c++) {
-        const int f = s->field[c];
-        if (!((f >= 0 && f < PRACH_NOMA_NFIELDS) || (f >= PRACH_COL_RAW && f < PRACH_COL_RAW + 16))) return 0;
-    }
-    return 1;
-}
-
-/* the class bit of a UE and its STATE (include/prach.h) */
-static int noma_class(const prach_ue_log *u) {
-    if (u->preambleChange == -1) return PRACH_NOMA_IDLE;
-    if (u->msg4Flag == 1) return PRACH_NOMA_SERVED;
-    return (u->failCount & 0xffff) != 0 ? PRACH_NOMA_DROPPED : PRACH_NOMA_PENDING;
-}
-static int noma_state(const prach_ue_log *u, int cls, int64_t E) {
-    if (cls == PRACH_NOMA_IDLE) return 0;
-    if (cls == PRACH_NOMA_SERVED) return 1;
-    if (cls == PRACH_NOMA_DROPPED) return 2;
-    if (u->active == 1) return u->nowBackoff > 0 ? 3 : (int64_t)u->txTime >= E ? 4 : 5;
-    if (u->active == 2) return u->connectionRequest == 0 ? 6 : 7;
-    return 8;
-}
-/* the value of a field for a UE of class cls that arrived at a; a negative value is UNDEFINED, and so is a field outside the classes it is defined for */
-static int64_t noma_value(int field, const prach_ue_log *u, int cls, int64_t a, int64_t E) {
-    const int arrived = cls != PRACH_NOMA_IDLE, served = cls == PRACH_NOMA_SERVED;
-    switch (field) {
-    case PRACH_NOMA_ONE: return 0;
-    case PRACH_NOMA_ARRIVAL: return arrived ? a : -1;
-    case PRACH_NOMA_SOJOURN: return served ? (int64_t)u->txTime + 6 - a : -1;
-    case PRACH_NOMA_COMPLETION: return served ? (int64_t)u->txTime + 6 : -1;
-    case PRACH_NOMA_TIMER: return arrived ? u->timer : -1;
-    case PRACH_NOMA_PTC: return arrived ? u->preambleTxCounter : -1;
-    case PRACH_NOMA_RETX: return arrived ? u->maxRarCounter : -1;
-    case PRACH_NOMA_MSG3FAIL: return arrived ? (int64_t)(u->failCount >> 16) : -1; /* (arithmetic shift: a negative word is undefined) */
-    case PRACH_NOMA_AGE: return arrived ? E - a : -1;
-    case PRACH_NOMA_STATE: return noma_state(u, cls, E);
-    case PRACH_NOMA_SECTOR: return arrived ? u->preambleChange : -1;
-    case PRACH_NOMA_PREAMBLE: return arrived ? u->preamble : -1;
-    default: /* LOST: a negative sojourn or timer makes it undefined, and so does a timer beyond the sojourn */
-        if (!served) return -1;
-        { const int64_t sj = (int64_t)u->txTime + 6 - a; return sj < 0 || u->timer < 0 ? -1 : sj - u->timer; }
-    }
-}
-/* the schedule of a NOMA_C cfg and E; 0: a status is in *rc */
-static int32_t *noma_schedule(const prach_cfg *cfg, int nUE, uint64_t steps, int *nslots, int64_t *E, int *rc) {
-    *rc = PRACH_ERR_ARG;
-    if (!cfg) return NULL;
-    if (cfg->variant != PRACH_VARIANT_NOMA_C) { *rc = PRACH_ERR_UNSUPPORTED; return NULL; }
-    if (prach_cfg_validate(cfg) != PRACH_OK || nUE != cfg->nUE) return NULL;
-    *nslots = (prach_max_time(cfg) + cfg->accessTime - 1) / cfg->accessTime;
-    int32_t *sched = (int32_t *)malloc(sizeof(int32_t) * (size_t)*nslots);
-    if (!sched) { *rc = PRACH_ERR_INTERNAL; return NULL; }
-    prach_arrival_schedule(cfg, sched, *nslots, NULL);
-    *E = steps < (uint64_t)prach_max_time(cfg) ? (int64_t)steps : (int64_t)prach_max_time(cfg);
-    *rc = PRACH_OK;
-    return sched;
-}
-
-/* THE DEFINITION (include/prach.h) */
-int prach_noma_census_accumulate_logs(const prach_xtab_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_noma_census *x,
-                                      uint64_t *cells) {
-    if (!prach_internal_noma_census_spec_ok(s) || !cfg || !x || !cells || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
-    int nslots = 0, rc;
-    int64_t E = 0;
-    int32_t *sched = noma_schedule(cfg, nUE, steps, &nslots, &E, &rc);
-    if (!sched) return rc;
-    if (x->trials == 0 && x->binned == 0) x->row_max = x->col_max = -1; /* (a zero-filled group is an empty one) */
-    int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
-    for (int i = 0; i < nUE; i++) {
-        while (slot < nslots && sched[slot] <= i) slot++;
-        const int64_t a = (int64_t)cfg->accessTime * slot;
-        const int cls = noma_class(&ue[i]);
-        if (cls == PRACH_NOMA_IDLE) x->idle++;
-        else if (cls == PRACH_NOMA_SERVED) x->served++;
-        else if (cls == PRACH_NOMA_DROPPED) x->dropped++;
-        else x->pending++;
-        if (!(cls & s->who)) continue;
-        x->selected++;
-        const int64_t rv = noma_value(s->row_field, &ue[i], cls, a, E), cv = noma_value(s->col_field, &ue[i], cls, a, E);
-        if (rv < 0 || cv < 0) { x->undefined++; continue; }
-        const int64_t rq = rv / s->row_width, cq = cv / s->col_width;
-        const size_t r = rq < s->row_bins ? (size_t)rq : (size_t)s->row_bins, c = cq < s->col_bins ? (size_t)cq : (size_t)s->col_bins;
-        cells[r * ((size_t)s->col_bins + 1) + c]++;
-        x->binned++;
-        x->row_sum += (uint64_t)rv;
-        x->col_sum += (uint64_t)cv;
-        if (rv > x->row_max) x->row_max = rv;
-        if (cv > x->col_max) x->col_max = cv;
-    }
-    free(sched);
-    x->trials++;
-    x->ues += (uint64_t)nUE;
-    return PRACH_OK;
-}
+/* ---- the NOMA census (prach_run_trials_noma_census): merge, CSV ---------------------------------------- */
 
 void prach_noma_census_merge(const prach_xtab_spec *s, prach_noma_census *into, uint64_t *cells_into, const prach_noma_census *from, const uint64_t *cells_from) {
     if (!prach_internal_noma_census_spec_ok(s) || !into || !cells_into || !from || !cells_from) return;
@@ -1165,109 +1227,7 @@ size_t prach_noma_census_format_csv(const prach_xtab_spec *s, const prach_noma_c
     return prach_xtab_format_csv(&t, &u, cells, label, buf, cap);
 }
 
-/* THE DEFINITION (include/prach.h) */
-int prach_noma_columns_from_logs(const prach_columns_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, int32_t *out, uint64_t stride) {
-    if (!prach_internal_noma_columns_spec_ok(s) || !cfg || !out || nUE < 0 || (nUE > 0 && !ue) || stride < (uint64_t)nUE) return PRACH_ERR_ARG;
-    int nslots = 0, rc;
-    int64_t E = 0;
-    int32_t *sched = noma_schedule(cfg, nUE, steps, &nslots, &E, &rc);
-    if (!sched) return rc;
-    int slot = 0;
-    for (int i = 0; i < nUE; i++) {
-        while (slot < nslots && sched[slot] <= i) slot++;
-        const int64_t a = (int64_t)cfg->accessTime * slot;
-        const int cls = noma_class(&ue[i]);
-        for (int c = 0; c < s->ncols; c++) {
-            const int f = s->field[c];
-            int32_t v;
-            if (f >= PRACH_COL_RAW) v = ((const int32_t *)&ue[i])[f - PRACH_COL_RAW]; /* the log word as it is */
-            else {
-                const int64_t x = noma_value(f, &ue[i], cls, a, E);
-                v = x < 0 ? -1 : (int32_t)x; /* a negative value is UNDEFINED */
-            }
-            out[(size_t)c * (size_t)stride + (size_t)i] = v;
-        }
-    }
-    free(sched);
-    return PRACH_OK;
-}
-
-/* ---- picks: the UEs behind a count, per trial (prach_run_trials_pick) ----------------------------- */
-
-/* (the engine judges a spec with this too: csrc/prach_device.h) */
-int prach_internal_pick_spec_ok(const prach_pick_spec *s) {
-    if (!s || s->who <= 0 || (s->who & ~(PRACH_XTAB_SERVED | PRACH_XTAB_UNSERVED | PRACH_XTAB_IDLE)) != 0 || s->nclauses < 0 || s->nclauses > PRACH_PICK_MAX_CLAUSES ||
-        s->k < 1 || s->k > PRACH_PICK_MAX_K || s->reserved != 0 || s->key_field < 0 || s->key_field >= PRACH_XTAB_NFIELDS) return 0;
-    if (s->order != PRACH_PICK_BY_INDEX && s->order != PRACH_PICK_LARGEST && s->order != PRACH_PICK_SMALLEST) return 0;
-    if (s->order == PRACH_PICK_BY_INDEX && s->key_field != PRACH_XTAB_ONE) return 0;
-    for (int c = 0; c < PRACH_PICK_MAX_CLAUSES; c++) {
-        const prach_pick_clause *q = &s->clause[c];
-        if (c < s->nclauses ? (q->field < 0 || q->field >= PRACH_XTAB_NFIELDS || q->lo < 0 || q->lo > q->hi) : (q->field || q->lo || q->hi)) return 0;
-    }
-    return 1;
-}
-
-typedef struct pick_cand { int64_t key; int32_t i, arrival; } pick_cand;
-static int cmp_pick_desc(const void *a, const void *b) { /* descending key, equal keys in ascending UE index */
-    const pick_cand *x = (const pick_cand *)a, *y = (const pick_cand *)b;
-    return x->key != y->key ? (x->key < y->key) - (x->key > y->key) : (x->i > y->i) - (x->i < y->i);
-}
-static int cmp_pick_asc(const void *a, const void *b) {
-    const pick_cand *x = (const pick_cand *)a, *y = (const pick_cand *)b;
-    return x->key != y->key ? (x->key > y->key) - (x->key < y->key) : (x->i > y->i) - (x->i < y->i);
-}
-
-/* THE DEFINITION (include/prach.h): every match is listed, the list is sorted, the first k are the rows */
-int prach_pick_from_logs(const prach_pick_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_pick *hdr, prach_pick_row *rows) {
-    if (!prach_internal_pick_spec_ok(s) || !cfg || !hdr || !rows || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
-    if (cfg->variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED;
-    if (prach_cfg_validate(cfg) != PRACH_OK || nUE != cfg->nUE) return PRACH_ERR_ARG;
-    const int nslots = (prach_max_time(cfg) + cfg->accessTime - 1) / cfg->accessTime;
-    int32_t *sched = (int32_t *)malloc(sizeof(int32_t) * (size_t)nslots);
-    pick_cand *cand = (pick_cand *)malloc(sizeof(pick_cand) * (size_t)(nUE > 0 ? nUE : 1));
-    if (!sched || !cand) { free(sched); free(cand); return PRACH_ERR_INTERNAL; }
-    prach_arrival_schedule(cfg, sched, nslots, NULL);
-    const int64_t E = steps < (uint64_t)prach_max_time(cfg) ? (int64_t)steps : (int64_t)prach_max_time(cfg);
-    const int keyed = s->order != PRACH_PICK_BY_INDEX;
-    prach_pick h;
-    memset(&h, 0, sizeof h);
-    h.status = PRACH_OK; h.nUE = nUE; h.threshold = -1;
-    int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
-    for (int i = 0; i < nUE; i++) {
-        while (slot < nslots && sched[slot] <= i) slot++;
-        const int64_t a = (int64_t)cfg->accessTime * slot;
-        const int cls = xtab_class(&ue[i]);
-        if (!(cls & s->who)) continue;
-        h.selected++;
-        int fails = 0, undef = 0;
-        for (int c = 0; c < s->nclauses; c++) {
-            const int64_t v = xtab_value(s->clause[c].field, &ue[i], cls, a, E);
-            if (v < 0) undef = 1;
-            else if (v < s->clause[c].lo || v > s->clause[c].hi) fails = 1;
-        }
-        const int64_t key = keyed ? xtab_value(s->key_field, &ue[i], cls, a, E) : 0;
-        if (key < 0) undef = 1;
-        if (fails) continue;
-        if (undef) { h.undefined++; continue; }
-        cand[h.matched++] = (pick_cand){key, i, cls == PRACH_XTAB_IDLE ? -1 : (int32_t)a};
-    }
-    if (keyed) qsort(cand, (size_t)h.matched, sizeof(pick_cand), s->order == PRACH_PICK_LARGEST ? cmp_pick_desc : cmp_pick_asc);
-    h.stored = h.matched < s->k ? h.matched : s->k;
-    memset(rows, 0, sizeof(prach_pick_row) * (size_t)s->k);
-    for (int r = 0; r < h.stored; r++) {
-        rows[r].log = ue[cand[r].i];
-        rows[r].arrival = cand[r].arrival;
-        rows[r].key = (int32_t)cand[r].key;
-    }
-    if (keyed && h.stored > 0) {
-        h.threshold = rows[h.stored - 1].key;
-        for (int r = h.stored; r < h.matched && cand[r].key == cand[h.stored - 1].key; r++) h.ties_left_out++;
-    }
-    free(sched);
-    free(cand);
-    *hdr = h;
-    return PRACH_OK;
-}
+/* ---- picks: the UEs behind a count, per trial (prach_run_trials_pick, prach_run_trials_noma_pick): CSV ---- */
 
 size_t prach_pick_format_csv(const prach_pick_spec *s, const prach_pick *h, const prach_pick_row *rows, const char *label, int trial, uint64_t seed, char *buf,
                              size_t cap) {
@@ -1282,71 +1242,6 @@ size_t prach_pick_format_csv(const prach_pick_spec *s, const prach_pick *h, cons
                  u->preambleTxCounter, u->msg2Flag, u->connectionRequest, u->msg4Flag, u->failCount);
     }
     return csv_end(buf, cap, off);
-}
-
-/* ---- the NOMA pick: prach_run_trials_pick's contract over the NOMA menu (prach_run_trials_noma_pick) ---- */
-
-/* (the engine judges a spec with this too: csrc/prach_device.h) */
-int prach_internal_noma_pick_spec_ok(const prach_pick_spec *s) {
-    if (!s || s->who <= 0 || (s->who & ~NOMA_ALL_CLASSES) != 0 || s->nclauses < 0 || s->nclauses > PRACH_PICK_MAX_CLAUSES || s->k < 1 || s->k > PRACH_PICK_MAX_K ||
-        s->reserved != 0 || s->key_field < 0 || s->key_field >= PRACH_NOMA_NFIELDS) return 0;
-    if (s->order != PRACH_PICK_BY_INDEX && s->order != PRACH_PICK_LARGEST && s->order != PRACH_PICK_SMALLEST) return 0;
-    if (s->order == PRACH_PICK_BY_INDEX && s->key_field != PRACH_NOMA_ONE) return 0;
-    for (int c = 0; c < PRACH_PICK_MAX_CLAUSES; c++) {
-        const prach_pick_clause *q = &s->clause[c];
-        if (c < s->nclauses ? (q->field < 0 || q->field >= PRACH_NOMA_NFIELDS || q->lo < 0 || q->lo > q->hi) : (q->field || q->lo || q->hi)) return 0;
-    }
-    return 1;
-}
-
-/* THE DEFINITION (include/prach.h): every match is listed, the list is sorted, the first k are the rows */
-int prach_noma_pick_from_logs(const prach_pick_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_pick *hdr, prach_pick_row *rows) {
-    if (!prach_internal_noma_pick_spec_ok(s) || !cfg || !hdr || !rows || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
-    int nslots = 0, rc;
-    int64_t E = 0;
-    int32_t *sched = noma_schedule(cfg, nUE, steps, &nslots, &E, &rc);
-    if (!sched) return rc;
-    pick_cand *cand = (pick_cand *)malloc(sizeof(pick_cand) * (size_t)(nUE > 0 ? nUE : 1));
-    if (!cand) { free(sched); return PRACH_ERR_INTERNAL; }
-    const int keyed = s->order != PRACH_PICK_BY_INDEX;
-    prach_pick h;
-    memset(&h, 0, sizeof h);
-    h.status = PRACH_OK; h.nUE = nUE; h.threshold = -1;
-    int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
-    for (int i = 0; i < nUE; i++) {
-        while (slot < nslots && sched[slot] <= i) slot++;
-        const int64_t a = (int64_t)cfg->accessTime * slot;
-        const int cls = noma_class(&ue[i]);
-        if (!(cls & s->who)) continue;
-        h.selected++;
-        int fails = 0, undef = 0;
-        for (int c = 0; c < s->nclauses; c++) {
-            const int64_t v = noma_value(s->clause[c].field, &ue[i], cls, a, E);
-            if (v < 0) undef = 1;
-            else if (v < s->clause[c].lo || v > s->clause[c].hi) fails = 1;
-        }
-        const int64_t key = keyed ? noma_value(s->key_field, &ue[i], cls, a, E) : 0;
-        if (key < 0) undef = 1;
-        if (fails) continue;
-        if (undef) { h.undefined++; continue; }
-        cand[h.matched++] = (pick_cand){key, i, cls == PRACH_NOMA_IDLE ? -1 : (int32_t)a};
-    }
-    if (keyed) qsort(cand, (size_t)h.matched, sizeof(pick_cand), s->order == PRACH_PICK_LARGEST ? cmp_pick_desc : cmp_pick_asc);
-    h.stored = h.matched < s->k ? h.matched : s->k;
-    memset(rows, 0, sizeof(prach_pick_row) * (size_t)s->k);
-    for (int r = 0; r < h.stored; r++) {
-        rows[r].log = ue[cand[r].i];
-        rows[r].arrival = cand[r].arrival;
-        rows[r].key = (int32_t)cand[r].key;
-    }
-    if (keyed && h.stored > 0) {
-        h.threshold = rows[h.stored - 1].key;
-        for (int r = h.stored; r < h.matched && cand[r].key == cand[h.stored - 1].key; r++) h.ties_left_out++;
-    }
-    free(sched);
-    free(cand);
-    *hdr = h;
-    return PRACH_OK;
 }
 
 size_t prach_noma_pick_format_csv(const prach_pick_spec *s, const prach_pick *h, const prach_pick_row *rows, const char *label, int trial, uint64_t seed, char *buf,
@@ -1393,7 +1288,7 @@ int prach_noma_summary_from_logs(const prach_noma_summary_spec *s, const prach_c
     if (!prach_internal_noma_summary_spec_ok(s) || !cfg || !row || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
     int nslots = 0, rc;
     int64_t E = 0;
-    int32_t *sched = noma_schedule(cfg, nUE, steps, &nslots, &E, &rc);
+    int32_t *sched = menu_schedule(&NOMA_MENU, cfg, nUE, steps, &nslots, &E, &rc);
     if (!sched) return rc;
     int64_t *val = (int64_t *)malloc(sizeof(int64_t) * PRACH_NOMA_SUMMARY_MAX_FIELDS * (size_t)(nUE > 0 ? nUE : 1));
     if (!val) { free(sched); return PRACH_ERR_INTERNAL; }

@@ -61,4 +61,31 @@ __host__ __device__ constexpr bool nm_needs_q0(int f) {
 }
 __host__ __device__ constexpr bool nm_needs_q1(int f) { return f == PRACH_NOMA_STATE || f == PRACH_NOMA_PREAMBLE; }
 
+// THE POLICY of this menu for the shared bodies of prach_menu_body.h: what a launch needs, the loads, the class, the value
+struct NomaMenu {
+    static constexpr int NCLASSES = 4; // cls is the class bit; the counters stand in the order idle, served, dropped, pending
+    struct Needs { bool a, x, y; };    // uniform for the launch: a(i), x: quarter 0, y: quarter 1
+    static __device__ __forceinline__ Needs needs(int f) { return Needs{nm_needs_arrival(f), nm_needs_q0(f), nm_needs_q1(f)}; }
+    static __device__ __forceinline__ Needs needs(int f, int g) { // either of two fields (the axes of a census)
+        return Needs{nm_needs_arrival(f) || nm_needs_arrival(g), nm_needs_q0(f) || nm_needs_q0(g), nm_needs_q1(f) || nm_needs_q1(g)};
+    }
+    static __device__ __forceinline__ Needs needs_raw(int w) { return Needs{false, (w >> 2) == 0, (w >> 2) == 1}; } // record word w of the columns
+    struct Rec { int4 q0, q1, q2, q3; };
+    template <bool WHOLE> static __device__ __forceinline__ Rec load(const int4 *logs, int i, const Needs &n) { // (a quarter is loaded whole or not at all)
+        Rec r;
+        r.q0 = r.q1 = make_int4(0, 0, 0, 0);
+        if (n.x) r.q0 = logs[4 * (size_t)i];     // idx, timer, active, txTime
+        if (n.y) r.q1 = logs[4 * (size_t)i + 1]; // firstTxTime, secondTxTime, nowBackoff, preamble
+        r.q2 = logs[4 * (size_t)i + 2];           // preambleChange (sector), rarWindow, maxRarCounter, preambleTxCounter
+        r.q3 = logs[4 * (size_t)i + 3];           // msg2Flag, connectionRequest, msg4Flag, failCount
+        return r;
+    }
+    static __device__ __forceinline__ int cls(const Rec &r) { return nm_class(r.q2, r.q3); }
+    static __device__ __forceinline__ int bit(int cls) { return cls; }
+    static __device__ __forceinline__ bool counted(int cls, int k) { // whether class counter k takes this UE
+        return cls == (k == 0 ? PRACH_NOMA_IDLE : k == 1 ? PRACH_NOMA_SERVED : k == 2 ? PRACH_NOMA_DROPPED : PRACH_NOMA_PENDING);
+    }
+    static __device__ __forceinline__ long long value(int f, const Rec &r, int cls, int a, int E) { return nm_value(f, r.q0, r.q1, r.q2, r.q3, cls, a, E); }
+};
+
 } // namespace prach

@@ -7,11 +7,13 @@
 //                               the largest / smallest value of one menu field, equal keys in ascending UE index — as 80-byte records (prach_pick_row), and the
 //                               exact number of matches; prach_noma_pick_from_logs is the definition
 // Both equal their definition integer for integer.  They have the shape of prach::summary_kernel and prach::pick_kernel (prach_summary.hip, prach_pick.hip) and
-// share what those share (prach_reduce_tile.h: the jobs, the slot search, the folds; the launch helper; SM_MAX_VALUE); the menu is prach_noma_menu.h.  They are
-// bodies of their own, not instantiations of one template with the two existing kernels: NOMA takes its class from other record quarters, has a fourth class
-// and thirteen fields, and the summary's quantities are named by the caller where summary_kernel has three fixed ones, so a shared body would be
-// parameterised on the loads, the class, the row and the value — all of it — and the existing kernels' code objects would no longer be the ones the project
-// has measured and pinned.
+// share what those share (prach_reduce_tile.h: the jobs, the slot search, the folds; the launch helper; SM_MAX_VALUE); the menu is prach_noma_menu.h.
+// The SUMMARY keeps its own pass 1, pass 2 and row — its quantities are named by the caller where summary_kernel has three fixed ones, and the rows differ —
+// and shares the three steps around them with summary_kernel: select_coarse, select_fine_slots, select_level of prach_menu_body.h.
+// The PICK is a body of its own next to pick_kernel's, and that is a measured decision, not the mangled names (a __global__ function can keep its name and
+// call a shared body, as the census and the columns kernels do): as one pick_body<Menu, THREADS> both picks ran 1.4 - 6.7 % slower on keyed picks, beyond the
+// spread of the probes.  The compiler loads every word of the 72-byte spec at the kernel's entry when the spec reaches the body through a reference, where
+// the kernels here read them from the kernel arguments at their uses, and these kernels already sit at the SGPR limit (profiles/menu_bodies.md 2).
 //
 // The jobs are the timeline's with E = min(steps, maxTime) in `pad` (TimelineJob, group = the trial; E from steps_of(), as for the census).  ONE workgroup per
 // trial: rows and scalars are written with plain stores, nothing is shared between trials, so a trial that is rerun needs no subtraction (only the launch that
@@ -53,17 +55,15 @@
 // PREAMBLE (one of at most 64), SECTOR (0..5), MSG3FAIL (the upper half of failCount, at most one per subframe).  STATE is at most 8, ONE is 0.  A logged word
 // the simulation did not write can be anything: above 65 535 it is a range error, negative it is UNDEFINED.
 // The class and clause tests are selects on compares and products of 0 / 1 flags, as in the census kernels.
-#include "prach_device.h"
-#include "prach_device_fn.h"
-#include "prach_reduce_tile.h"
+#include "prach_menu_body.h"
 #include "prach_noma_menu.h"
 
 namespace prach {
 
 namespace {
 
-constexpr int NS_COARSE = 1024, NS_FINE = 64, NS_MAX_KEY = SM_MAX_VALUE;
-static_assert(NS_COARSE * NS_FINE == NS_MAX_KEY + 1 && NS_COARSE % 64 == 0 && 10000 + 6 <= NS_MAX_KEY, "coarse << 6 | fine covers every key a trial produces; a wavefront scans the histogram in one go");
+constexpr int NS_COARSE = SEL_COARSE, NS_FINE = SEL_FINE, NS_MAX_KEY = SM_MAX_VALUE; // (the selection's two sizes: prach_menu_body.h)
+static_assert(NS_COARSE == SEL_COARSE && NS_FINE == SEL_FINE && 10000 + 6 <= NS_MAX_KEY, "coarse << 6 | fine covers every key a trial produces; a wavefront scans the histogram in one go");
 constexpr int NS_SCHED_CAP = 12288; // schedule entries staged in LDS: pick_kernel's cap (a NOMA.c trial has at most 10 000; a longer schedule is searched in global memory)
 // the pick's layout (its kernel stands behind the summary's)
 constexpr int NS_MAX_WAVES = 16;
@@ -159,27 +159,10 @@ __global__ __launch_bounds__(THREADS) void noma_summary_kernel(const TimelineJob
         if (x >= sp.nfields || l >= sp.nq || n <= 0) continue;
         long long r = (n * (long long)sp.permille[l] + 999) / 1000;
         if (r < 1) r = 1;
-        const unsigned *const h = lcoarse + x * NS_COARSE + lane * (NS_COARSE / 64);
-        int s = 0;
-#pragma unroll
-        for (int b = 0; b < NS_COARSE / 64; b++) s += (int)h[b];
-        const int incl = wave_scan_incl(s), excl = incl - s;
-        if ((long long)excl < r && r <= (long long)incl) { // one lane at most; none where range errors left the histogram short of the rank
-            unsigned left = (unsigned)(r - excl);
-            int b = 0;
-            while (left > h[b]) left -= h[b++]; // (ends inside the lane's bins: their sum s >= left)
-            tcoarse[t] = lane * (NS_COARSE / 64) + b;
-            trem[t] = left;
-        }
+        select_coarse(lcoarse + x * NS_COARSE, r, lane, &tcoarse[t], &trem[t]);
     }
     __syncthreads();
-    if (tid < NSM_TARGETS && tcoarse[tid] >= 0) { // the fine histogram of a target: the first target of its field with the same coarse bin
-        const int t0 = tid - tid % PRACH_SUMMARY_MAX_Q;
-        int slot = tid;
-        for (int u = tid - 1; u >= t0; u--)
-            if (tcoarse[u] == tcoarse[tid]) slot = u;
-        tslot[tid] = slot;
-    }
+    select_fine_slots<NSM_TARGETS>(tcoarse, tslot, tid);
     __syncthreads();
 
     // pass 2
@@ -210,17 +193,7 @@ __global__ __launch_bounds__(THREADS) void noma_summary_kernel(const TimelineJob
     // the row: NSM_WORDS 64-bit words (prach_device.h)
     unsigned long long *const row = rows + (size_t)J.group * NSM_WORDS;
     if (tid < S_END) row[tid] = (unsigned long long)lsc[tid];
-    if (tid < NSM_TARGETS) {
-        long long val = -1;
-        if (tcoarse[tid] >= 0) {
-            const unsigned *const f = lfine + tslot[tid] * NS_FINE;
-            unsigned left = trem[tid];
-            int b = 0;
-            while (b < NS_FINE - 1 && left > f[b]) left -= f[b++];
-            val = ((long long)tcoarse[tid] << 6) | b;
-        }
-        row[S_END + tid] = (unsigned long long)val;
-    }
+    if (tid < NSM_TARGETS) row[S_END + tid] = (unsigned long long)select_level(lfine, tcoarse, trem, tslot, tid);
 }
 
 // ---- the pick -------------------------------------------------------------------------------------------------------------------------------------------

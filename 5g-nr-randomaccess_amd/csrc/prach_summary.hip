@@ -17,17 +17,14 @@
 // fails the call).  No trial produces one: the sojourn is at most TL_MAX_SOJOURN, `timer` at most the same (it is a stretch of one UE's sojourn, the
 // timeline's own bound), and preambleTxCounter is set to 1 or grows by at most one per subframe (prach_ue_body.h: ptc_set1 / ptc_inc, one event per UE
 // and subframe), of which a trial has at most 60 000 + 6.  Integers only: the result does not depend on any order.
-#include "prach_device.h"
-#include "prach_device_fn.h"
-#include "prach_reduce_tile.h"
+#include "prach_menu_body.h"
 
 namespace prach {
 
 namespace {
 
 static_assert(TL_MAX_SOJOURN < 65536, "every sojourn and timer a trial can produce is inside the range the two-level selection ranks");
-constexpr int SM_COARSE = 1024, SM_FINE = 64, SM_TARGETS = 3 * PRACH_SUMMARY_MAX_Q;
-static_assert(SM_COARSE * SM_FINE == SM_MAX_VALUE + 1 && SM_COARSE % 64 == 0, "coarse << 6 | fine covers 0 .. SM_MAX_VALUE; a wavefront scans a histogram in one go");
+constexpr int SM_COARSE = SEL_COARSE, SM_FINE = SEL_FINE, SM_TARGETS = 3 * PRACH_SUMMARY_MAX_Q; // (the selection's steps and its two sizes: prach_menu_body.h)
 constexpr int SM_SCHED_CAP = 12288; // schedule entries staged in LDS: Uniform traffic at accessTime 5 has 12 002 (a longer schedule is searched in global memory)
 // LDS words: 3 coarse histograms | the fine histograms | 9 x 64-bit scalars (+ pad) | 3 maxima | per target: coarse bin, rank left, fine histogram used | schedule
 constexpr int SM_FIXED_WORDS = 3 * SM_COARSE + SM_TARGETS * SM_FINE + 2 * 10 + 4 + 3 * SM_TARGETS; // 18.4 KB
@@ -99,27 +96,10 @@ __global__ __launch_bounds__(THREADS) void summary_kernel(const TimelineJob *__r
             if (l >= lv.nq) continue;
             long long r = (n * (long long)lv.permille[l] + 999) / 1000;
             if (r < 1) r = 1;
-            const unsigned *const h = lcoarse + x * SM_COARSE + lane * (SM_COARSE / 64);
-            int s = 0;
-#pragma unroll
-            for (int b = 0; b < SM_COARSE / 64; b++) s += (int)h[b];
-            const int incl = wave_scan_incl(s), excl = incl - s;
-            if ((long long)excl < r && r <= (long long)incl) { // one lane at most; none where range errors left the histogram short of the rank
-                unsigned left = (unsigned)(r - excl);
-                int b = 0;
-                while (left > h[b]) left -= h[b++]; // (ends inside the lane's bins: their sum s >= left)
-                tcoarse[t] = lane * (SM_COARSE / 64) + b;
-                trem[t] = left;
-            }
+            select_coarse(lcoarse + x * SM_COARSE, r, lane, &tcoarse[t], &trem[t]);
         }
     __syncthreads();
-    if (tid < SM_TARGETS && tcoarse[tid] >= 0) { // the fine histogram of a target: the first target of its quantity with the same coarse bin
-        const int t0 = tid - tid % PRACH_SUMMARY_MAX_Q;
-        int slot = tid;
-        for (int u = tid - 1; u >= t0; u--)
-            if (tcoarse[u] == tcoarse[tid]) slot = u;
-        tslot[tid] = slot;
-    }
+    select_fine_slots<SM_TARGETS>(tcoarse, tslot, tid);
     __syncthreads();
 
     // pass 2
@@ -144,17 +124,7 @@ __global__ __launch_bounds__(THREADS) void summary_kernel(const TimelineJob *__r
     unsigned long long *const row = rows + (size_t)J.group * SM_WORDS;
     if (tid < 9) row[tid] = (unsigned long long)lsc[tid];
     if (tid >= 9 && tid < 12) row[tid] = (unsigned long long)(long long)(n > 0 ? lmax[tid - 9] : -1);
-    if (tid < SM_TARGETS) {
-        long long val = -1;
-        if (tcoarse[tid] >= 0) {
-            const unsigned *const f = lfine + tslot[tid] * SM_FINE;
-            unsigned left = trem[tid];
-            int b = 0;
-            while (b < SM_FINE - 1 && left > f[b]) left -= f[b++];
-            val = ((long long)tcoarse[tid] << 6) | b;
-        }
-        row[12 + tid] = (unsigned long long)val;
-    }
+    if (tid < SM_TARGETS) row[12 + tid] = (unsigned long long)select_level(lfine, tcoarse, trem, tslot, tid);
 }
 
 } // namespace

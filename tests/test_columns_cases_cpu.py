@@ -63,6 +63,8 @@ def test_generator_is_deterministic_and_contains_what_it_exists_for(pkg, cases, 
     sizes = [j.nue for j in by["very_different_sizes"].jobs]
     assert min(sizes) == 1 and max(sizes) >= 4 * CC.TILE
     assert not any(f in (X.ARRIVAL, X.SOJOURN, X.AGE, X.STATE, X.PTC) or CC.COL_RAW + 4 <= f < CC.COL_RAW + 12 for f in by["no_arrival_no_optional_quarters"].fields)
+    f = by["raw_words_of_every_quarter"].fields  # the optional quarters are loaded for the raw words alone, next to a field that needs a(i)
+    assert {(x - CC.COL_RAW) >> 2 for x in f if x >= CC.COL_RAW} == {0, 1, 2, 3} and {x for x in f if x < CC.COL_RAW} == {X.TIMER, X.AGE}
     p = str(tmp_path / "case.bin")
     CC.write_case(by["thresholds"], p)
     assert os.path.getsize(p) == 4 * (32 + 8 * 3 + sum(16 * j.nue + len(j.sched) for j in by["thresholds"].jobs))

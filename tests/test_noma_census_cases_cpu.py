@@ -56,6 +56,9 @@ def test_generator_is_deterministic_and_reaches_its_states(pkg, cases, tmp_path)
     j = c.jobs[0]
     at = R.arrival_times(j.nue, j.sched, 1)
     assert int(at[NC.TILE - 1] - at[0]) > NC.CONSTANTS["TILE_SCHED_CAP"] and [x.E for x in c.jobs] == [int(at[-1]) - 1, int(at[-1]), 6000, 0]
+    c = by["raw_words_of_every_quarter"]  # no menu field of these columns reads quarter 0 or 1; a raw word of every quarter stands next to them
+    assert c.columns != NC.COLUMN_FIELDS and {(f - N.RAW) >> 2 for f in c.columns if f >= N.RAW} == {0, 1, 2, 3}
+    assert {f for f in c.columns if f < N.RAW} == {N.PTC, N.ARRIVAL} and not {c.spec[0][0], c.spec[1][0]} & {N.SOJOURN, N.COMPLETION, N.TIMER, N.STATE, N.LOST, N.PREAMBLE}
     p = str(tmp_path / "case.bin")
     NC.write_case(by["all_lanes_one_cell"], p)
     assert os.path.getsize(p) == 4 * (32 + 8 + 16 * (2 * NC.TILE + 1) + 2)
@@ -71,7 +74,7 @@ def test_references_equal_the_host_definitions(pkg, cases):
         (rd, rc), (hd, hc) = c.reference_columns(), c.host_columns(pkg)
         assert np.array_equal(rd, hd) and np.array_equal(rc, hc), c.name
         seen += 1
-    assert seen == 8
+    assert seen == 9
 
 
 def test_harness_compiles_and_carries_the_constants(pkg, tmp_path):

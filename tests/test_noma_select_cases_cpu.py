@@ -115,6 +115,12 @@ def test_pick_cases_reach_their_states(cases, refs):
     assert out[3][0]["undefined"] > 100 and out[3][0]["matched"] < 10  # E = 0: AGE is undefined for whoever arrives later
     assert out[2][0]["undefined"] == 0 and out[2][0]["stored"] == out[2][0]["matched"] > 100 and out[2][0]["ties_left_out"] == 0
 
+    c = by["pick_index_idle_rows"]  # three blocks of either shape, idle UEs (arrival -1) among the 300 stored rows of each trial
+    assert [j.nue for j in c.jobs] == [1025, 2049] and c.spec[3] == 300
+    for j, (h, rows) in zip(c.jobs, refs[c.name]):
+        idle = N.classes(j.logs[rows[:, 0]]) == N.IDLE
+        assert h["stored"] == 300 and rows[:, 0].tolist() == list(range(300)) and 0 < idle.sum() < 300 and (rows[idle, 16] == -1).all() and (rows[~idle, 16] >= 0).all()
+
 
 def test_references_equal_the_host_definitions(pkg, cases, refs):
     seen = 0
@@ -124,7 +130,7 @@ def test_references_equal_the_host_definitions(pkg, cases, refs):
         host = SC.host_rows(c, c.host_definition(pkg))
         assert SC.same(c, host, refs[c.name]) is None, (c.name, SC.same(c, host, refs[c.name]))
         seen += 1
-    assert seen == 3
+    assert seen == 4
 
 
 def test_harness_compiles_and_carries_the_constants(pkg, tmp_path):

@@ -156,7 +156,7 @@ def threshold_job(lead=1):
 SIZES = (1, 63, 64, 65, 255, 256, 257, 8191, 8192, 8193)
 LEADS = (3, 1, 4, 7, 5, 6, 1, 2, 6, 6)  # the offsets of the trials take every residue mod 4 rows; odd offsets behind the trials of 8191 and 8192 UEs
 CASE_NAMES = ("sizes_all_menu", "sizes_all_raw", "one_column_arrival", "one_column_raw_timer", "sixteen_columns_mixed", "repeated_fields", "thresholds",
-              "no_arrival_no_optional_quarters", "schedules_around_the_staging_limit", "very_different_sizes", "real_schedules")
+              "no_arrival_no_optional_quarters", "schedules_around_the_staging_limit", "very_different_sizes", "real_schedules", "raw_words_of_every_quarter")
 
 
 def sizes_jobs(rng):
@@ -195,6 +195,9 @@ def cases(pkg):
     out.append(Case("very_different_sizes", [X.STATE, X.AGE, COL_RAW + 11], [random_job(rng, n, lead=l) for n, l in ((1, 1), (40000, 2), (3, 3), (8192, 1), (2, 1), (17000, 6), (1, 1))]))
     rng = np.random.default_rng(610)
     out.append(Case("real_schedules", list(MENU) + [COL_RAW + 3], [real_job(pkg, rng, n, kw, lead=1 + q) for kw in R.REAL_SCHEDULES for q, n in enumerate((1, 65, 1025, 8193))], host=True))
+    # menu fields that need neither optional quarter (TIMER; AGE needs a(i)) next to a raw word of each of the four quarters: quarters 1 and 2 are loaded for the raw words alone
+    rng = np.random.default_rng(611)
+    out.append(Case("raw_words_of_every_quarter", [X.TIMER, COL_RAW + 2, COL_RAW + 5, COL_RAW + 10, COL_RAW + 14, X.AGE], [random_job(rng, n, lead=l) for n, l in ((700, 2), (8193, 1))]))
     assert tuple(c.name for c in out) == CASE_NAMES
     return out
 

@@ -18,7 +18,7 @@ NC_SCALARS, NCL_SCALARS, GUARD, PATTERN = 16, 4, 64, 0x7FFF7FFF
 HARNESS_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpu_noma_census_harness.hip")
 SIZES = (1, 63, 64, 65, TILE - 1, TILE, TILE + 1, 2 * TILE + 1)
 NOMA_KW = dict(variant=2, accessTime=5)  # the product's NOMA.c schedule
-# the columns every case is also written as: the whole menu and three raw words (failCount, the sector, txTime)
+# the columns a case is also written as unless it names its own: the whole menu and three raw words (failCount, the sector, txTime)
 COLUMN_FIELDS = tuple(range(13)) + (N.RAW + 15, N.RAW + 8, N.RAW + 3)
 
 
@@ -47,8 +47,8 @@ class Job(R.TimelineJob):
 class Case:
     """spec = (rows, cols, who), an axis (field id, width, bins); host: every schedule is the product's own NOMA.c schedule."""
 
-    def __init__(self, name, spec, ngroups, jobs, host):
-        self.name, self.spec, self.ngroups, self.jobs, self.host = name, spec, int(ngroups), jobs, host
+    def __init__(self, name, spec, ngroups, jobs, host, columns=COLUMN_FIELDS):
+        self.name, self.spec, self.ngroups, self.jobs, self.host, self.columns = name, spec, int(ngroups), jobs, host, tuple(columns)
 
     def __repr__(self):
         return self.name
@@ -59,7 +59,7 @@ class Case:
 
     def reference_columns(self):
         """(int32 [ncols, rows], int64 [njobs, 4] class counts idle, served, dropped, pending)"""
-        data = np.concatenate([N.columns(COLUMN_FIELDS, j.logs, j.sched, j.access_time, j.E) for j in self.jobs], axis=1)
+        data = np.concatenate([N.columns(self.columns, j.logs, j.sched, j.access_time, j.E) for j in self.jobs], axis=1)
         counts = np.array([[int((N.classes(j.logs) == b).sum()) for b in (N.IDLE, N.SERVED, N.DROPPED, N.PENDING)] for j in self.jobs], dtype=np.int64)
         return data, counts
 
@@ -71,12 +71,12 @@ class Case:
         return {"cells": c.cells, "scalars": c.scalars}
 
     def host_columns(self, pkg):
-        col = pkg.noma_columns_from_logs(self.cfgs(pkg), [j.E for j in self.jobs], [j.logs for j in self.jobs], list(COLUMN_FIELDS))
+        col = pkg.noma_columns_from_logs(self.cfgs(pkg), [j.E for j in self.jobs], [j.logs for j in self.jobs], list(self.columns))
         return col.data, np.stack([col.headers[f].astype(np.int64) for f in ("idle", "served", "dropped", "pending")], axis=1)
 
 
 CASE_NAMES = ("real_census_who_all", "real_copies_below", "real_copies_exact", "real_copies_above", "real_window_below", "real_window_exact", "real_window_above",
-              "real_one_by_one_idle", "bin_edges_and_overflows", "all_lanes_one_cell", "tiles_without_a_selected_ue", "long_schedule_and_short_runs")
+              "real_one_by_one_idle", "bin_edges_and_overflows", "all_lanes_one_cell", "tiles_without_a_selected_ue", "long_schedule_and_short_runs", "raw_words_of_every_quarter")
 
 
 def wild_logs(rng, at, E):
@@ -168,6 +168,11 @@ def cases(pkg):
         a[:, N.W_SECTOR] = np.abs(a[:, N.W_SECTOR]) % 6
         jobs.append(Job(a, sched, 1, g, E))
     out.append(Case("long_schedule_and_short_runs", ((N.AGE, 100, 60), (N.LOST, 50, 12), N.ALL), 4, jobs, False))
+
+    # columns whose menu fields need neither quarter 0 nor quarter 1 (PTC reads quarter 2, ARRIVAL a(i)) next to a raw word of each of the four quarters: the
+    # two optional quarters are loaded for the raw words alone.  The census beside them reads the two quarters every launch loads and nothing else
+    out.append(Case("raw_words_of_every_quarter", ((N.PTC, 2, 5), (N.SECTOR, 1, 6), N.ALL), 2, _real_jobs(pkg, np.random.default_rng(950), 2, few), True,
+                    columns=(N.PTC, N.RAW + 1, N.RAW + 6, N.RAW + 11, N.RAW + 12, N.ARRIVAL)))
     assert tuple(c.name for c in out) == CASE_NAMES
     return out
 
@@ -183,8 +188,8 @@ def build_harness(out_dir):
 
 def write_case(case, path):
     head = np.zeros(32, dtype=np.int32)
-    head[:12] = [R.MAGIC, 9, len(case.jobs), case.spec[2], *case.spec[0], *case.spec[1], case.ngroups, len(COLUMN_FIELDS)]
-    head[12:12 + len(COLUMN_FIELDS)] = COLUMN_FIELDS
+    head[:12] = [R.MAGIC, 9, len(case.jobs), case.spec[2], *case.spec[0], *case.spec[1], case.ngroups, len(case.columns)]
+    head[12:12 + len(case.columns)] = case.columns
     rows = np.zeros((len(case.jobs), 8), dtype=np.int32)
     parts = [head, rows]
     for k, j in enumerate(case.jobs):
@@ -221,7 +226,7 @@ def read_census(case, path, scheme):
 def read_columns(case, path):
     """(int32 [ncols, rows], int64 [njobs, 4]) of the harness's columns result; the guard words behind the rows of every column hold the pattern."""
     raw = np.fromfile(path, dtype="<u4")
-    njobs, rows, ncols = len(case.jobs), sum(j.nue for j in case.jobs), len(COLUMN_FIELDS)
+    njobs, rows, ncols = len(case.jobs), sum(j.nue for j in case.jobs), len(case.columns)
     head = raw[:8].view("<u8")
     assert [int(v) for v in head] == [R.MAGIC, 10, 0, sum(-(-j.nue // TILE) for j in case.jobs)], head
     counts = raw[8:8 + 2 * njobs * NCL_SCALARS].view("<u8").astype(np.int64).reshape(njobs, NCL_SCALARS)

@@ -49,7 +49,7 @@ class Case:
 
 
 CASE_NAMES = ("summary_sizes_eight_levels", "summary_values_and_ranks", "summary_undefined_field_and_one", "summary_schedules_and_ends", "pick_index_k1_sizes",
-              "pick_index_k4096_four_clauses", "pick_largest_ties", "pick_smallest_ties", "pick_largest_age_schedules_and_ends")
+              "pick_index_k4096_four_clauses", "pick_largest_ties", "pick_smallest_ties", "pick_largest_age_schedules_and_ends", "pick_index_idle_rows")
 
 
 def _real_jobs(pkg, rng, sizes=SIZES):
@@ -156,6 +156,8 @@ def cases(pkg):
     out.append(Case("pick_largest_ties", ((), S.LARGEST, N.TIMER, 64, N.ALL), _tie_jobs(False), False))
     out.append(Case("pick_smallest_ties", ((), S.SMALLEST, N.TIMER, 64, N.ALL), _tie_jobs(True), False))
     out.append(Case("pick_largest_age_schedules_and_ends", (((N.STATE, 2, 8),), S.LARGEST, N.AGE, 4096, N.ALL), _schedule_jobs(np.random.default_rng(1060)), False))
+    # idle UEs among the stored rows (wild records: one sector in ten is -1), three blocks of either shape: their arrival is -1
+    out.append(Case("pick_index_idle_rows", ((), S.BY_INDEX, N.ONE, 300, N.ALL), _real_jobs(pkg, np.random.default_rng(1070), (1025, 2049)), True))
     assert tuple(c.name for c in out) == CASE_NAMES
     return out
 
