@@ -20,6 +20,10 @@
 //     granules in that XCD's L2 (handshake in the prologue; any other placement keeps the write-through granules);
 //   * the last wavefront is the exchange's (bucket publish, headers, event offsets) and walks no UE groups; the header leaves right
 //     behind S1 when there is no early-leaver candidate (no barrier S2);
+//   * a QUIET subframe — no gathered call, reset-cycle candidate or re-join, and no bucket whose lowest matched member calls alone: four
+//     subframes of five of a loaded trial — does not run the resolver chain: every wavefront sees that from lane = bucket's row of the
+//     resolver tables, wavefront 0 adds the two counters, and calls(), the barrier S5 and the grant selection are skipped; a subframe
+//     without any event skips the gather block as well (profiles/lcluster_quiet_subframes.md);
 //   * only the Philox path, only clusters (G > 1), only the pipelined compacted pass: the engine falls back to
 //     prach::cluster_kernel for everything else (glibc streams, one workgroup per trial, nPreamble > 64, more owned UEs than
 //     LDS holds, diagnostic options).
@@ -69,7 +73,7 @@ constexpr int LRQ = 1024;    // UEs per subframe whose next two Philox draws are
 constexpr unsigned ND_READY = 0x80000000u; // lnd[slot] bit 31: ldraw[slot] holds draws nd, nd + 1 of this UE
 
 // scalars in LDS
-enum { S_NSUCC = 0, S_COLL, S_TXOP, S_CONTF, S_NS, S_NRC, S_NRJ, S_NEV = 8, S_NCAND /* = S_NEV + 1: read as a pair; both [2] by subframe parity (+ 2): slots 8..11 */, S_PTC = 13, S_FC, S_SUMT = 16,
+enum { S_NSUCC = 0, S_COLL, S_TXOP, S_CONTF, S_NS, S_NRC, S_NRJ, S_NCE /* gathered calls; slots 4..7 are read as ONE int4 behind S4 */, S_NEV = 8, S_NCAND /* = S_NEV + 1: read as a pair; both [2] by subframe parity (+ 2): slots 8..11 */, S_PTC = 13, S_FC, S_SUMT = 16,
        S_ND = 18, S_NCROSS = 20, S_NRQ = 23, S_SX = 24,
        S_QN = 26, // [2] event queue length, by subframe parity: phase A of subframe t+1 fills one while phase B of subframe t has just read the other
        // what every thread needs behind S3, in ONE 16-byte LDS read: status, gathered events | overflow flag << 30, events beyond round 1,
@@ -623,7 +627,7 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
             int *const nevp = &scal[S_NEV + 2 * parity]; // (this subframe's pair of counters)
             const int2 nc = *reinterpret_cast<const int2 *>(nevp); // {events so far, early-leaver candidates}
             int nevraw = nc.x;
-            if (tl == 64) { scal[S_NS] = 0; scal[S_NRC] = 0; scal[S_NRJ] = 0; scal[S_QN + parity] = 0; } // (this subframe's queue has been consumed)
+            if (tl == 64) { scal[S_NS] = 0; scal[S_NRC] = 0; scal[S_NRJ] = 0; scal[S_NCE] = 0; scal[S_QN + parity] = 0; } // (this subframe's queue has been consumed; the resolver's counters are cleared in FRONT of S3: round 2 adds to them right behind it)
             if (nc.y > 0) {
                 const int *const mloc = LI(lo::PAR + pc + lo::P_MLOC), *const mlocs = LI(lo::PAR + pc + lo::P_MLOCS);
                 for (int k = tl; k < nc.y; k += WG_THREADS) {
@@ -739,11 +743,16 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
         const int N = ctl.y & 0x3FFFFFFF;
         if ((ctl.y >> 30) || N > LEV) { status = PRACH_ERR_INTERNAL; time_exit = t; break; } // engine: exact rerun on the general kernels
         // the event granules: the first LEPF of every mailbox came with round 1 (each by the thread that fetched it), classified
-        // against the lowest definite callers; a mailbox with more has the rest read now (a second round trip, rare)
-        {
+        // against the lowest definite callers; a mailbox with more has the rest read now (a second round trip, rare).
+        // S_NCE: the gathered calls (UEV_CALLER / UEV_RESETCAND, as gathered) of the whole subframe, one atomic per wavefront that has any
+        // (read behind S4: a subframe without one, without a reset-cycle candidate and without a re-join is `quiet`, below).
+        // A subframe without an event (N is uniform) has nothing to gather: no read of the event offsets either.
+        if (N > 0) {
             const int *const evoff = LI(lo::EVOFF);
+            unsigned long long cmask[2] = {0ull, 0ull};
 #pragma unroll
             for (int u = 0; u < 2; u++) {
+                bool iscall = false;
                 if (r2wg[u] >= 0) {
                     const int o0 = evoff[r2wg[u]], nev = evoff[r2wg[u] + 1] - o0;
                     if (r2es[u] < nev) {
@@ -751,10 +760,13 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
                         if (!granule_ok(e, tag)) { e = wait_granule(mbpar + r2off[u], tag, &scal[S_STATUS]); }
                         const int2 ev = make_int2((int)((unsigned)e & 0xFFFFFu), (int)((unsigned)((unsigned long long)e >> 32) & 0xFFFFFu));
                         gev[o0 + r2es[u]] = ev;
+                        iscall = (ev.y & 7) == UEV_CALLER || (ev.y & 7) == UEV_RESETCAND;
                         classify_event(RT, o0 + r2es[u], ev, ev_kill);
                     }
                 }
+                cmask[u] = __ballot(iscall);
             }
+            if ((cmask[0] | cmask[1]) != 0ull && lane == 0) atomicAdd(&scal[S_NCE], __popcll(cmask[0]) + __popcll(cmask[1]));
             if (ctl.z > 0) {
                 for (int k = tl; k < N; k += WG_THREADS) {
                     int lo_ = 0, hi_ = G; // workgroup whose segment holds event k
@@ -764,6 +776,7 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
                     const long long e = wait_granule(mbpar + (unsigned)lo_ * mbs + 1u + (unsigned)nP + (unsigned)es, tag, &scal[S_STATUS]);
                     const int2 ev = make_int2((int)((unsigned)e & 0xFFFFFu), (int)((unsigned)((unsigned long long)e >> 32) & 0xFFFFFu));
                     gev[k] = ev;
+                    if ((ev.y & 7) == UEV_CALLER || (ev.y & 7) == UEV_RESETCAND) atomicAdd(&scal[S_NCE], 1); // (the second round is rare)
                     classify_event(RT, k, ev, ev_kill);
                 }
             }
@@ -773,7 +786,11 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
         LSTAMP(10);
 
         // ---- resolve (identical on every workgroup of the cluster) ----
-        const int nrc = scal[S_NRC];
+        // {singletons (0 here), reset-cycle candidates, re-joins, gathered calls} in ONE 16-byte LDS read, issued together with lane p's
+        // row of the resolver tables (the quiet test below).  N == 0: nothing was gathered, the four are 0 as they were cleared behind S1.
+        const int4 rs = N > 0 ? *reinterpret_cast<const int4 *>(&scal[S_NS]) : make_int4(0, 0, 0, 0);
+        const int qfc = fcallA[lane], qtot = LI(lo::TOTAL + fa)[lane], qnlv = LI(lo::NLV + fa)[lane]; // (rows >= nP: INT_MAX, 0, 0 for the whole trial)
+        const int nrc = rs.y;
         if (nrc > 0) { // rare: reset cycles that may re-join — decided strictly in index order, then recount
             if (nrc > RCCAP) { status = PRACH_ERR_INTERNAL; time_exit = t; break; }
             if (tl < 64) resolve_reset_candidates<1>(RT, nrc, nP, ev_get, ev_kill);
@@ -792,13 +809,38 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
         // singleton list only feeds the grant selection, the last-caller table only PEND_RJOIN — so they are DEFERRED into the
         // next subframe's exchange window (off the critical chain; the counters are the same whenever they are added up).
         const int Gr = max(0, nGrantUL - 1 - grantCheck); // Beta.c:336-347
-        const bool defer = Gr == 0 && nrc == 0 && scal[S_NRJ] == 0 && t + 1 < stop;
-        if (defer) { pendN = N; pendFa = fa; }
+        //
+        // QUIET subframe: no gathered call, no reset-cycle candidate, no re-join.  Then every call of calls() is a bucket's lowest matched
+        // member calling again (its k >= N branch: ispre = 1, first, FIE[p] == 0, rj = 0), check = TOTAL[p] - NLV[p], and one wavefront
+        // sees all of them, lane = bucket.  If none of them is a singleton the calls produce two counter increments and the last-caller
+        // table, nothing else: no singleton list, no grant, ns = 0.  Wavefront 0 adds the counters; calls(), S5, the read of S_NS, the
+        // grant selection and S6 are skipped.  A singleton among them (a matched UE left alone in its bucket) takes the general path.
+        // The decision reads S_NRC / S_NRJ / S_NCE and [fa]'s FCALL / TOTAL / NLV: complete at S3 (N == 0) or S4, not written again
+        // before the S3 of the next subframe, and the same on every workgroup of the cluster (they hold the same gathered subframe) —
+        // so every wavefront of every workgroup takes the same branch, and only barriers inside a workgroup are skipped.  The last-caller
+        // table has no reader before the next barrier: only PEND_RJOIN looks at it, and a quiet subframe has no re-join.
+        bool quiet = false;
+        if ((rs.y | rs.z | rs.w) == 0) {
+            const bool qc = qfc != INT_MAX;
+            const int check = qtot - qnlv;
+            if (__ballot(qc && check == 1) == 0ull) {
+                quiet = true;
+                const unsigned long long cm = __ballot(qc);
+                if (w == 0 && cm) {
+                    if (qc) LI(lo::LCALL + fa)[lane] = qfc; // (max with the -1 it was reset to: nobody else writes [fa]'s last callers in this subframe)
+                    const int add = withnoma ? wave_sum(qc ? check : 0) : __popcll(cm); // WithNOMA:650-652 / Beta.c:349-351
+                    if (lane == 0) { atomicAdd(&scal[S_COLL], add); atomicAdd(&scal[S_TXOP], add); }
+                }
+            }
+        }
+        const bool defer = !quiet && Gr == 0 && nrc == 0 && rs.z == 0 && t + 1 < stop;
+        if (quiet) { } // (never deferred: pendN stays as it is)
+        else if (defer) { pendN = N; pendFa = fa; }
         else calls(fa, N, true);
         LSTAMP(11); // calls
-        if (!defer) __syncthreads(); // S5: calls done; singles listed
+        if (!defer && !quiet) __syncthreads(); // S5: calls done; singles listed
         LSTAMP(12);
-        const int ns = defer ? 0 : scal[S_NS]; // (deferred: the window's grants are used up, grantCheck no longer matters: Beta.c:336)
+        const int ns = (defer || quiet) ? 0 : scal[S_NS]; // (deferred: the window's grants are used up, grantCheck no longer matters: Beta.c:336)
         if (ns > LSC) { status = PRACH_ERR_INTERNAL; time_exit = t; break; }
         // An UL grant: the grant bit into the UE's record.  Phase A of subframe t+1 has already run: it took a matched UE
         // (PEND_STAY) for steadily contending, counted it into its bucket and did not queue it — take it out again and queue it.
