@@ -26,7 +26,8 @@ PRACH_HD FastMod make_fastmod(int d) {
     return f;
 }
 PRACH_HD int fastmod(int x, const FastMod f) {
-    if (f.d == 1u) return 0;
+    // (no branch for d == 1: M = 0xFFFFFFFF makes q = x - 1 for x > 0, r = 1, and the correction below returns 0; x = 0 gives q = r = 0.  A divisor
+    //  held in a vector register made that test a 64-bit lane mask, spilled to lanes and read back in front of every use: profiles/lcluster_registers.md)
     const unsigned q = mulhi32((unsigned)x, f.M);
     const unsigned r = (unsigned)x - q * f.d;
     return (int)(r >= f.d ? r - f.d : r);

@@ -10,8 +10,14 @@
 // 64-bit mailbox address arithmetic per granule, run-time LDS table offsets and loops around single-trip work.  Here:
 //   * every LDS table sits at a COMPILE-TIME offset (bucket tables have the fixed stride NPCL = 64: nPreamble <= 64, the
 //     reference's 54 / 64); an LDS address is an instruction immediate, not a live register;
-//   * each thread's role in the exchange (which granules it loads, which bucket it publishes) is computed ONCE before the
-//     step loop and kept in vector registers as 32-bit offsets from the mailbox base;
+//   * each thread's role in the exchange (which granules it loads, which bucket it publishes) is fixed before the step loop; what is
+//     kept of it across the loop is FIVE vector registers (three bucket-granule offsets from the mailbox base, the three buckets a byte
+//     each, one event-granule offset) — the event roles' (workgroup, slot), the second event role's offset and the header role follow
+//     from the thread index where they are used, a cluster of at most 32 workgroups (the headline) skips the second event role behind
+//     one wave-uniform test, and every role predicate is recomputed at its use from an opaque copy instead of living in (and spilling
+//     from) scalar registers as a lane mask.  Fifteen such registers had sent two loop-invariant LDS addresses to scratch, reloaded with
+//     a vmcnt(0) each in round 2 of every subframe: the kernel has no scratch now, in any build but the diagnostic one
+//     (tests/test_lcluster_registers.py, profiles/lcluster_registers.md);
 //   * the hot record (16 B) and the Philox draw index of every owned UE live in LDS for the whole trial (no L2 round trip
 //     for a record, a draw index or an early-leaver candidate anywhere in the step loop); finished groups are a per-wavefront
 //     register bit mask; subframe bookkeeping (t mod 5, t mod accessTime, the arrival table) is incremental scalar state;
@@ -286,27 +292,32 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
     const unsigned mbs = (unsigned)PD->mbstride >> 1; // granules per mailbox
     PRACH_G long long *const mbox = (PRACH_G long long *)PD->mbox;
     const unsigned parstride = (unsigned)G * mbs;       // granules per parity
-    // this thread's fixed roles in the exchange, as granule offsets inside a parity block
-    unsigned r1off[3];
-    int r1p[3];
+    // This thread's fixed roles in the exchange, as granule offsets inside a parity block.  Only what cannot be had from the thread index in
+    // an instruction or two is kept in a register across the step loop — FIVE of them (fifteen made the compiler send two loop-invariant
+    // LDS addresses to scratch and reload them, vmcnt(0) each, in round 2 on the chain: profiles/lcluster_registers.md):
+    //   bucket roles  r1off[u] (granule offset) and the bucket p of all three in ONE register, a byte each, R1NONE = no such role;
+    //   event roles   granule k = tid + u * WG_THREADS is slot k % LEPF of workgroup k / LEPF: with LEPF = 32 that is slot tid & 31 of
+    //                 workgroup (tid >> 5) + u * R2W — derived where it is used; one offset, the second role's is R2W mailboxes further
+    //                 on, and a cluster of at most R2W workgroups (the headline's 32) has no second role at all: one wave-uniform test;
+    //   header role   the last wavefront, lane = workgroup: offset lane * mbs, computed there.
+    // No role PREDICATE is carried through the loop either (a 64-bit lane mask each, in scalar registers that are not there: spilled
+    // to lanes and read back in front of every use): each is recomputed at its use from an opaque copy of the register it tests.
+    static_assert(LEPF == 32 && WG_THREADS % LEPF == 0, "event roles are derived from the thread index");
+    constexpr int R2W = WG_THREADS / LEPF; // mailboxes whose first LEPF event granules one role of the workgroup covers
+    constexpr unsigned R1NONE = 0xFFu;
+    static_assert(NPCL <= (int)R1NONE, "a bucket fits a byte beside the sentinel");
+    unsigned r1off[3], r1pk = 0u;
 #pragma unroll
     for (int u = 0; u < 3; u++) { // round 1: up to 3072 bucket granules (G = 48 x 64 preambles); more: the tail loop below
         const int k = tid + u * WG_THREADS;
         const int wg = k / max(nP, 1), p = k - wg * nP;
-        r1p[u] = k < G * nP ? p : -1;
+        r1pk |= (k < G * nP ? (unsigned)p & 0xFFu : R1NONE) << (8 * u);
         r1off[u] = (unsigned)wg * mbs + 1u + (unsigned)p;
     }
-    unsigned r2off[2]; // round 1 also fetches the first LEPF event granules of every mailbox: this thread's (workgroup, slot)
-    int r2wg[2], r2es[2];
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-        const int k = tid + u * WG_THREADS;
-        r2wg[u] = k < G * LEPF ? k / LEPF : -1;
-        r2es[u] = k % LEPF;
-        r2off[u] = (unsigned)(k / LEPF) * mbs + 1u + (unsigned)nP + (unsigned)(k % LEPF);
-    }
-    const int hl = tid - (WG_THREADS - 64);            // the last wavefront reads the headers: lane = workgroup
-    const unsigned hoff = (unsigned)max(hl, 0) * mbs;
+    // round 1 also fetches the first LEPF event granules of every mailbox: this thread's (workgroup, slot) of the first role
+    const unsigned r2off0 = (unsigned)(tid / LEPF) * mbs + 1u + (unsigned)nP + (unsigned)(tid % LEPF);
+    const bool ev1 = G > R2W; // (wave-uniform) the cluster has workgroups for the second event role
+#define L_OPAQUE(x) asm volatile("" : "+v"(x))
     const unsigned myoff = (unsigned)b * mbs;           // own mailbox
 
     // calloc + initialUE (Beta.c:78-83) for the groups this workgroup owns
@@ -664,14 +675,25 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
         }
         LSTAMP(16);
         long long gv[3] = {0, 0, 0}, hv = 0;
+        {
+            unsigned rp = r1pk;
+            L_OPAQUE(rp);
 #pragma unroll
-        for (int u = 0; u < 3; u++)
-            if (r1p[u] >= 0) gv[u] = ld_sc1_64(mbpar + r1off[u]);
-        if (hl >= 0 && hl < G) hv = ld_sc1_64(mbpar + hoff);
+            for (int u = 0; u < 3; u++)
+                if (((rp >> (8 * u)) & 0xFFu) != R1NONE) gv[u] = ld_sc1_64(mbpar + r1off[u]);
+        }
         long long ev2[2] = {0, 0};
-#pragma unroll
-        for (int u = 0; u < 2; u++)
-            if (r2wg[u] >= 0) ev2[u] = ld_sc1_64(mbpar + r2off[u]);
+        {
+            int tq = tl;
+            L_OPAQUE(tq);
+            if (w == NW - 1) { // the last wavefront reads the headers: lane = workgroup
+                const int hl = tq & 63;
+                if (hl < G) hv = ld_sc1_64(mbpar + (unsigned)hl * mbs);
+            }
+            const int wg0 = tq / LEPF;
+            if (wg0 < G) ev2[0] = ld_sc1_64(mbpar + r2off0);
+            if (ev1) { if (wg0 + R2W < G) ev2[1] = ld_sc1_64(mbpar + (r2off0 + (unsigned)R2W * mbs)); }
+        }
         LSTAMP(17);
         if (!GLIBC) { // refill: the next two draws of every UE that drew in this subframe's phase B (off the chain: the exchange is in flight)
             const int nrq = min(scal[S_NRQ], LRQ);
@@ -690,14 +712,17 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
         LSTAMP(6); // phase A ahead
         {
             int *const total = LI(lo::TOTAL + fa);
+            unsigned rp = r1pk;
+            L_OPAQUE(rp);
 #pragma unroll
             for (int u = 0; u < 3; u++) {
-                if (r1p[u] >= 0) {
+                const unsigned p = (rp >> (8 * u)) & 0xFFu;
+                if (p != R1NONE) {
                     long long g_ = gv[u];
                     if (!granule_ok(g_, tag)) { LSTAT(1, 1); g_ = wait_granule(mbpar + r1off[u], tag, &scal[S_STATUS]); }
                     const unsigned h = (unsigned)g_ & 0xFFFFFu, ml = (unsigned)((unsigned long long)g_ >> 32) & 0xFFFFFu;
-                    if (h) atomicAdd(&total[r1p[u]], (int)h);
-                    if (ml != GR_NONE) atomicMin(&fcallA[r1p[u]], (int)ml);
+                    if (h) atomicAdd(&total[p], (int)h);
+                    if (ml != GR_NONE) atomicMin(&fcallA[p], (int)ml);
                 }
             }
             for (int k = tl + 3 * WG_THREADS; k < G * nP; k += WG_THREADS) { // (more than 3072 bucket granules)
@@ -708,12 +733,15 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
                 if (ml != GR_NONE) atomicMin(&fcallA[p], (int)ml);
             }
             LSTAMP(19);
-            if (hl >= 0) {
+            if (w == NW - 1) {
+                int hl = tl;
+                L_OPAQUE(hl);
+                hl &= 63;
                 int nev = 0, nsuc = 0, ovf = 0;
                 if (hl < G) {
                     long long g_ = hv;
                     LSTAT(2, __popcll(__ballot(!granule_ok(g_, tag))) ? 1 : 0); // (subframes in which a header was late)
-                    if (!granule_ok(g_, tag)) g_ = wait_granule(mbpar + hoff, tag, &scal[S_STATUS]);
+                    if (!granule_ok(g_, tag)) g_ = wait_granule(mbpar + (unsigned)hl * mbs, tag, &scal[S_STATUS]);
                     const unsigned w0 = (unsigned)g_ & 0xFFFFFu;
                     nev = (int)(w0 & 0x1FFFu); ovf = (int)((w0 >> 13) & 1u); nsuc = (int)((unsigned)((unsigned long long)g_ >> 32) & 0xFFFFFu);
                 }
@@ -750,18 +778,24 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
         if (N > 0) {
             const int *const evoff = LI(lo::EVOFF);
             unsigned long long cmask[2] = {0ull, 0ull};
+            int tq = tl;
+            L_OPAQUE(tq);
+            const int es = tq % LEPF;
 #pragma unroll
             for (int u = 0; u < 2; u++) {
+                if (u == 1 && !ev1) break; // (no workgroup for the second role: wave-uniform)
                 bool iscall = false;
-                if (r2wg[u] >= 0) {
-                    const int o0 = evoff[r2wg[u]], nev = evoff[r2wg[u] + 1] - o0;
-                    if (r2es[u] < nev) {
+                const int wg = tq / LEPF + u * R2W;
+                if (wg < G) {
+                    // (two adjacent words at a 4-byte-aligned address — wg may be odd: one ds_read2_b32, not a ds_read_b64)
+                    const int o0 = evoff[wg], nev = evoff[wg + 1] - o0;
+                    if (es < nev) {
                         long long e = ev2[u];
-                        if (!granule_ok(e, tag)) { e = wait_granule(mbpar + r2off[u], tag, &scal[S_STATUS]); }
+                        if (!granule_ok(e, tag)) { e = wait_granule(mbpar + (r2off0 + (unsigned)(u * R2W) * mbs), tag, &scal[S_STATUS]); }
                         const int2 ev = make_int2((int)((unsigned)e & 0xFFFFFu), (int)((unsigned)((unsigned long long)e >> 32) & 0xFFFFFu));
-                        gev[o0 + r2es[u]] = ev;
+                        gev[o0 + es] = ev;
                         iscall = (ev.y & 7) == UEV_CALLER || (ev.y & 7) == UEV_RESETCAND;
-                        classify_event(RT, o0 + r2es[u], ev, ev_kill);
+                        classify_event(RT, o0 + es, ev, ev_kill);
                     }
                 }
                 cmask[u] = __ballot(iscall);
@@ -998,6 +1032,7 @@ __global__ __launch_bounds__(WG_THREADS) void lcluster_kernel(const TrialDev *__
             o->steps = steps;
         }
     }
+#undef L_OPAQUE
 }
 
 // glibc (the reference's own rand() stream): no draws computed ahead (16 B per slot), but the per-group call counts of the whole trial and
