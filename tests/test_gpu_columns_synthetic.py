@@ -3,7 +3,6 @@ tests/tools/columns_cases.py — one launch per child process, one child at a ti
 every trial's segment included, every offset and every class count equals the numpy restatement integer for integer, and the host definition
 (prach_columns_from_logs) where it applies.  tests/test_columns_cases_cpu.py holds the references against the host definition without a GPU."""
 import os
-import subprocess
 import sys
 
 import pytest
@@ -11,11 +10,12 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import harness as H  # noqa: E402
 import columns_cases as CC  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-_abnormal = []  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
+latch = H.Latch()  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
 
 
 @pytest.fixture(scope="module")
@@ -35,12 +35,8 @@ def test_kernel_equals_reference(pkg, harness, cases, tmp_path, name):
     host = case.host_definition(pkg) if case.host else None
     path = str(tmp_path / "case.bin")
     CC.write_case(case, path)
-    assert not _abnormal, f"not started: {_abnormal[0]}"
-    try:
+    with latch.child(name):
         out = CC.run_harness(harness, case, path, tmp_path)
-    except (RuntimeError, subprocess.TimeoutExpired) as e:
-        _abnormal.append(f"{name}: {e}")
-        raise
     assert CC.same(out, ref) is None, f"against numpy: {CC.same(out, ref)}"
     if host is not None:
         assert CC.same(out, host) is None, f"against the host definition: {CC.same(out, host)}"

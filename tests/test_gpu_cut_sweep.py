@@ -5,7 +5,6 @@ and all 16 logged fields of every UE, bit-exact.  One row per test, each in a fr
 after a child that was killed, timed out or died on a signal the remaining rows fail without starting anything.  tests/test_cut_cases_cpu.py shows
 without a GPU what the cuts contain; tests/tools/CUT_SWEEP.md has the table of rows and the measured figures."""
 import os
-import subprocess
 import sys
 
 import pytest
@@ -13,11 +12,12 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import harness as H  # noqa: E402
 import cut_cases as CC  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-_abnormal = []  # a child that ended abnormally (signal, timeout): no later row of this file starts another one
+latch = H.Latch()  # a child that ended abnormally (signal, timeout): no later row of this file starts another one
 
 # seconds per row: the oracle's prefix runs (a few seconds on 16 threads), the package import and the GPU calls (measured: tests/tools/CUT_SWEEP.md) take
 # well under a minute together; the slot-by-slot NOMA.c form makes one launch per access slot of every trial
@@ -26,17 +26,9 @@ LIMIT = 240
 
 @pytest.mark.parametrize("row", [r["name"] for r in CC.CUT_ROWS])
 def test_row_equals_oracle_at_every_cut(pkg, row):
-    assert not _abnormal, f"not started: {_abnormal[0]}"
     env = dict(os.environ)
     env.pop("PRACH_LIB", None)
-    cmd = ["timeout", "-k", "10", str(LIMIT), sys.executable, os.path.join(ROOT, "tests", "tools", "gpu_cut_sweep.py"), row]
-    try:
-        p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=LIMIT + 30)
-    except subprocess.TimeoutExpired as e:
-        _abnormal.append(f"{row}: {e}")
-        raise
-    if p.returncode not in (0, 1) or "run ended" in p.stdout:  # (1: trials differ — the child ended on its own; a failed call may have been a device error)
-        _abnormal.append(f"{row}: exit status {p.returncode}: {p.stdout[-300:]}")
+    p = latch.python_child(row, [sys.executable, os.path.join(ROOT, "tests", "tools", "gpu_cut_sweep.py"), row], LIMIT, env)
     assert p.returncode == 0 and " 0 bad" in p.stdout.splitlines()[-1], (p.returncode, p.stdout[-6000:], p.stderr[-2000:])
     lines = [l for l in p.stdout.splitlines() if l.startswith("row ")]
     assert len(lines) == len(CC.ROW[row].get("pipeline", (None,))) and all(" bad=0 " in l for l in lines), p.stdout[-3000:]

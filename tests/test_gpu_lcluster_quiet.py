@@ -5,7 +5,6 @@ trial, no rerun on trial_kernel).  One case per test, each in a fresh child proc
 a child that was killed, timed out or died on a signal the remaining cases fail without starting anything.  tests/test_lcluster_quiet_cases_cpu.py
 shows without a GPU what the trials contain."""
 import os
-import subprocess
 import sys
 
 import pytest
@@ -13,11 +12,12 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import harness as H  # noqa: E402
 import quiet_cases as QC  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-_abnormal = []  # a child that ended abnormally (signal, timeout): no later case of this file starts another one
+latch = H.Latch()  # a child that ended abnormally (signal, timeout): no later case of this file starts another one
 
 LIMIT = 120  # seconds per case: 129 short oracle runs, the package import and at most 17 calls of small trials take a few seconds together
 
@@ -27,16 +27,8 @@ LIMIT = 120  # seconds per case: 129 short oracle runs, the package import and a
 @pytest.mark.parametrize("variant", [0, 1])
 @pytest.mark.parametrize("name", [b[0] for b in QC.BASES])
 def test_quiet_path_equals_oracle(pkg, name, variant, rng, cluster):
-    assert not _abnormal, f"not started: {_abnormal[0]}"
     env = dict(os.environ)
     env.pop("PRACH_LIB", None)
-    cmd = ["timeout", "-k", "10", str(LIMIT), sys.executable, os.path.join(ROOT, "tests", "tools", "gpu_lcluster_quiet.py"),
-           name, str(variant), str(rng), str(cluster)]
-    try:
-        p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=LIMIT + 30)
-    except subprocess.TimeoutExpired as e:
-        _abnormal.append(f"{name} {variant} {rng} {cluster}: {e}")
-        raise
-    if p.returncode not in (0, 1) or "run ended" in p.stdout:  # (1: trials differ — the child ended on its own; a failed call may have been a device error)
-        _abnormal.append(f"{name} {variant} {rng} {cluster}: exit status {p.returncode}: {p.stdout[-300:]}")
+    cmd = [sys.executable, os.path.join(ROOT, "tests", "tools", "gpu_lcluster_quiet.py"), name, str(variant), str(rng), str(cluster)]
+    p = latch.python_child(f"{name} {variant} {rng} {cluster}", cmd, LIMIT, env)
     assert p.returncode == 0 and p.stdout.splitlines()[-1].startswith(f"done {2 * QC.CUTS + 1} cases 0 bad"), (p.returncode, p.stdout[-4000:], p.stderr[-2000:])

@@ -6,7 +6,6 @@ the case's size (rec_mode 3, no fallback trial, no rerun on trial_kernel).  One 
 (tests/tools/gpu_lcluster_roles.py) under `timeout -k 10`; after a child that was killed, timed out or died on a signal the remaining cases fail without
 starting anything.  tests/test_lcluster_roles_cases_cpu.py shows without a GPU what the trials contain."""
 import os
-import subprocess
 import sys
 
 import pytest
@@ -14,27 +13,20 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import harness as H  # noqa: E402
 import roles_cases as RC  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-_abnormal = []  # a child that ended abnormally (signal, timeout): no later case of this file starts another one
+latch = H.Latch()  # a child that ended abnormally (signal, timeout): no later case of this file starts another one
 
 LIMIT = 120  # seconds per case: 24 oracle runs of a few thousand UEs, the package import and at most 12 calls of small trials take a few seconds together
 
 
 @pytest.mark.parametrize("name", [c[0] for c in RC.CASES])
 def test_roles_equal_oracle(pkg, name):
-    assert not _abnormal, f"not started: {_abnormal[0]}"
     env = dict(os.environ)
     env.pop("PRACH_LIB", None)
-    cmd = ["timeout", "-k", "10", str(LIMIT), sys.executable, os.path.join(ROOT, "tests", "tools", "gpu_lcluster_roles.py"), name]
-    try:
-        p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=LIMIT + 30)
-    except subprocess.TimeoutExpired as e:
-        _abnormal.append(f"{name}: {e}")
-        raise
-    if p.returncode not in (0, 1) or "run ended" in p.stdout:  # (1: trials differ — the child ended on its own; a failed call may have been a device error)
-        _abnormal.append(f"{name}: exit status {p.returncode}: {p.stdout[-300:]}")
+    p = latch.python_child(name, [sys.executable, os.path.join(ROOT, "tests", "tools", "gpu_lcluster_roles.py"), name], LIMIT, env)
     print(p.stdout[-1500:])
     assert p.returncode == 0 and p.stdout.splitlines()[-1].startswith(f"done {4 * (1 + len(RC.CUTS))} trials 0 bad"), (p.returncode, p.stdout[-4000:], p.stderr[-2000:])

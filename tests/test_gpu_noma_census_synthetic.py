@@ -4,7 +4,6 @@ child at a time, each under its own timeout — and every output equals the nump
 the other scheme.  After an abnormal end no further child is started.  tests/test_noma_census_cases_cpu.py holds the references against the host definitions
 without a GPU."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,11 +12,12 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import harness as H  # noqa: E402
 import noma_census_cases as NC  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-_abnormal = []  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
+latch = H.Latch()  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
 
 
 @pytest.fixture(scope="module")
@@ -31,12 +31,8 @@ def cases(pkg):
 
 
 def launch(harness, case, path, mode, out_dir, name):
-    assert not _abnormal, f"not started: {_abnormal[0]}"
-    try:
+    with latch.child(f"{name} {mode}"):
         return NC.run_harness(harness, case, path, mode, out_dir)
-    except (RuntimeError, subprocess.TimeoutExpired) as e:
-        _abnormal.append(f"{name} {mode}: {e}")
-        raise
 
 
 @pytest.mark.parametrize("name", NC.CASE_NAMES)

@@ -4,7 +4,6 @@ a time, each under its own timeout — and every output equals the numpy restate
 the product's, and the other instantiation.  After an abnormal end no further child is started.  tests/test_noma_select_cases_cpu.py holds the references
 against the host definitions without a GPU."""
 import os
-import subprocess
 import sys
 
 import pytest
@@ -12,11 +11,12 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import harness as H  # noqa: E402
 import noma_select_cases as SC  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-_abnormal = []  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
+latch = H.Latch()  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
 
 
 @pytest.fixture(scope="module")
@@ -30,12 +30,8 @@ def cases(pkg):
 
 
 def launch(harness, case, path, threads, out_dir):
-    assert not _abnormal, f"not started: {_abnormal[0]}"
-    try:
+    with latch.child(f"{case.name} {threads}"):
         return SC.run_harness(harness, case, path, threads, out_dir)
-    except (RuntimeError, subprocess.TimeoutExpired) as e:
-        _abnormal.append(f"{case.name} {threads}: {e}")
-        raise
 
 
 @pytest.mark.parametrize("name", SC.CASE_NAMES)

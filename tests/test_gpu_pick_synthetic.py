@@ -3,7 +3,6 @@ tests/tools/pick_cases.py — both workgroup shapes, one launch per child proces
 behind `stored` included, equals the numpy restatement integer for integer, the host definition (prach_pick_from_logs) where it applies, and the other
 shape.  tests/test_pick_cases_cpu.py holds the references against the host definition without a GPU."""
 import os
-import subprocess
 import sys
 
 import pytest
@@ -11,11 +10,12 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import harness as H  # noqa: E402
 import pick_cases as PC  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-_abnormal = []  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
+latch = H.Latch()  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
 
 
 @pytest.fixture(scope="module")
@@ -37,12 +37,8 @@ def test_kernel_equals_reference_under_both_shapes(pkg, harness, cases, tmp_path
     PC.write_case(case, path)
     outs = []
     for threads in PC.THREADS:
-        assert not _abnormal, f"not started: {_abnormal[0]}"
-        try:
+        with latch.child(f"{name} threads {threads}"):
             out = PC.run_harness(harness, case, path, threads, tmp_path)
-        except (RuntimeError, subprocess.TimeoutExpired) as e:
-            _abnormal.append(f"{name} threads {threads}: {e}")
-            raise
         outs.append(out)
         assert PC.same(out, ref) is None, f"{threads} threads against numpy: {PC.same(out, ref)}"
         if host is not None:

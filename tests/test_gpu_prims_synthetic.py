@@ -5,7 +5,6 @@ build (the product's flags, and the NOBITOP3 flags of csrc/Makefile): sixteen on
 that never opens the device.  Every section's output is identical under the two builds and equals a plain reference: the pinned oracle's Philox, numpy in
 int64, Python integer arithmetic, and for the masks the branched per-UE body.  tests/test_prims_cases_cpu.py holds the cases and references without a GPU."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -14,11 +13,12 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import harness as H  # noqa: E402
 import prims_cases as P  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-_abnormal = []  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
+latch = H.Latch()  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
 
 
 @pytest.fixture(scope="module")
@@ -37,13 +37,9 @@ def _both_builds(harness, section, n, payload, d, **kw):
     P.write_case(case, section, n, payload, **kw)
     out = {}
     for build in P.BUILDS:
-        assert not _abnormal, f"not started: {_abnormal[0]}"
         res = str(d / f"result_{build}.bin")
-        try:
+        with latch.child(f"{section} ({build})"):
             P.run_harness(harness[build], section, case, res, timeout=120)
-        except (RuntimeError, subprocess.TimeoutExpired) as e:
-            _abnormal.append(f"{section} ({build}): {e}")
-            raise
         out[build] = P.read_result(res, section, 0, n)
     assert out["product"].shape == out["nobitop3"].shape and (out["product"] == out["nobitop3"]).all(), \
         f"{section}: the two builds differ in {(out['product'] != out['nobitop3']).sum()} words, first at {np.flatnonzero(out['product'] != out['nobitop3'])[:5]}"
@@ -76,13 +72,9 @@ def masks(harness, consts, tmp_path_factory):
     P.write_masks(case, M)
     bits = None
     for build in P.BUILDS:
-        assert not _abnormal, f"not started: {_abnormal[0]}"
         res = str(d / f"result_{build}.bin")
-        try:
+        with latch.child(f"masks ({build})"):
             P.run_harness(harness[build], "masks", case, res, timeout=120)
-        except (RuntimeError, subprocess.TimeoutExpired) as e:
-            _abnormal.append(f"masks ({build}): {e}")
-            raise
         b = P.read_result(res, "masks", 0, M.n)
         assert bits is None or (bits == b).all(), f"masks: the two builds differ, first at {np.flatnonzero(bits != b)[:5]}"
         bits = b

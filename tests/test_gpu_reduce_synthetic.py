@@ -4,7 +4,6 @@ integer for integer, the host definition (prach_dist_accumulate_logs / prach_tim
 tests/test_reduce_cases_cpu.py holds the references against the host definitions without a GPU.  Below that, the two edges a simulation does reach:
 preamble counts spread over a whole wavefront and past the last bin, and a truncated trial with whole tiles of UEs that never arrived."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,12 +12,13 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import harness as H  # noqa: E402
 import reduce_cases as R  # noqa: E402
 import timeline_ref as T  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-_abnormal = []  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
+latch = H.Latch()  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
 
 
 @pytest.fixture(scope="module")
@@ -49,12 +49,8 @@ def test_kernel_equals_reference_under_every_scheme(pkg, harness, cases, tmp_pat
     R.write_case(case, path)
     outs = []
     for scheme in ((0, 1, 2) if case.kind == "dist" else (0, 1)):
-        assert not _abnormal, f"not started: {_abnormal[0]}"
-        try:
+        with latch.child(f"{name} scheme {scheme}"):
             out = R.run_harness(harness, case, path, scheme, tmp_path)
-        except (RuntimeError, subprocess.TimeoutExpired) as e:
-            _abnormal.append(f"{name} scheme {scheme}: {e}")
-            raise
         outs.append(out)
         assert case.same(out, ref) is None, f"scheme {scheme} against numpy: {case.same(out, ref)}"
         if host is not None:

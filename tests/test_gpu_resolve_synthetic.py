@@ -4,7 +4,6 @@ tests/tools/resolve_cases.py — every case of a mode in ONE launch, one launch 
 status equal the pinned oracle's per-sector function exactly, the two NOMA copies equal each other, and every output word of the reset-candidate resolver
 equals the sequential definition.  tests/test_resolve_cases_cpu.py holds the cases and the references themselves without a GPU."""
 import os
-import subprocess
 import sys
 
 import pytest
@@ -12,11 +11,12 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import harness as H  # noqa: E402
 import resolve_cases as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-_abnormal = []  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
+latch = H.Latch()  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
 
 
 @pytest.fixture(scope="module")
@@ -30,12 +30,8 @@ def consts(harness):
 
 
 def _child(harness, case_path, result_path, devact, what):
-    assert not _abnormal, f"not started: {_abnormal[0]}"
-    try:
+    with latch.child(what):
         R.run_harness(harness, case_path, result_path, devact, timeout=120)
-    except (RuntimeError, subprocess.TimeoutExpired) as e:
-        _abnormal.append(f"{what}: {e}")
-        raise
 
 
 @pytest.fixture(scope="module")

@@ -7,7 +7,6 @@ prach_noma_activation_stream on every case, the gain of every unflagged case lie
 libm puts within ACT_BAND / 2 of a float rounding boundary is flagged, and at most 1 in 10^5 of the near misses and of 200 000 random UEs is.
 tests/test_stream_act_cases_cpu.py holds the cases and references without a GPU."""
 import os
-import subprocess
 import sys
 
 import pytest
@@ -15,20 +14,17 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import harness as H  # noqa: E402
 import stream_act_cases as S  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-_abnormal = []  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
+latch = H.Latch()  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
 
 
 def _child(exe, case, res):
-    assert not _abnormal, f"not started: {_abnormal[0]}"
-    try:
+    with latch.child(os.path.basename(case)):
         S.run_harness(exe, case, res, timeout=120)
-    except (RuntimeError, subprocess.TimeoutExpired) as e:
-        _abnormal.append(f"{os.path.basename(case)}: {e}")
-        raise
 
 
 def stream_launch(exe, pkg, consts, jobs, d, tag, mode=1):
@@ -112,7 +108,7 @@ def background(exe, host, consts, tmp_path_factory):
 
 
 def _report(A, got, figures):
-    """The figures tests/tools/STREAM_ACT_HARNESS.md records (pytest -s shows them)."""
+    """The figures tests/tools/HARNESS.md records (pytest -s shows them)."""
     print("figures:", figures)
     must = [k for k in range(len(A)) if A.expect.get(A.name[k], {}).get("kind") == "must"]
     if must:

@@ -3,7 +3,6 @@ tests/tools/xtab_cases.py — both schemes, one launch per child process, one ch
 integer, the host definition (prach_xtab_accumulate_logs) where it applies, and the other scheme.  tests/test_xtab_cases_cpu.py holds the references
 against the host definition without a GPU."""
 import os
-import subprocess
 import sys
 
 import pytest
@@ -11,11 +10,12 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import harness as H  # noqa: E402
 import xtab_cases as XC  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-_abnormal = []  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
+latch = H.Latch()  # a harness run that ended abnormally (exit status, signal, timeout): no later test of this file starts another one
 
 
 @pytest.fixture(scope="module")
@@ -37,12 +37,8 @@ def test_kernel_equals_reference_under_both_schemes(pkg, harness, cases, tmp_pat
     XC.write_case(case, path)
     outs = []
     for scheme in (0, 1):
-        assert not _abnormal, f"not started: {_abnormal[0]}"
-        try:
+        with latch.child(f"{name} scheme {scheme}"):
             out = XC.run_harness(harness, case, path, scheme, tmp_path)
-        except (RuntimeError, subprocess.TimeoutExpired) as e:
-            _abnormal.append(f"{name} scheme {scheme}: {e}")
-            raise
         outs.append(out)
         assert XC.same(out, ref) is None, f"scheme {scheme} against numpy: {XC.same(out, ref)}"
         if host is not None:

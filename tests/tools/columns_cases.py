@@ -3,10 +3,10 @@ state no simulation leaves behind and the glue around tests/tools/gpu_columns_ha
 tests/test_columns_cpu.py, tests/test_columns_cases_cpu.py and the GPU tests.  No GPU and no package import here."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
+import harness as H
 import reduce_cases as R
 import xtab_ref as X
 
@@ -15,7 +15,7 @@ TILE, THREADS, TILE_SCHED_CAP = 8192, 256, 2048  # TL_TILE, TL_THREADS, TILE_SCH
 CL_SCALARS = 4
 CONSTANTS = dict(TL_TILE=TILE, TL_THREADS=THREADS, TILE_SCHED_CAP=TILE_SCHED_CAP, CL_SCALARS=CL_SCALARS, CL_SUMS=3, PRACH_COL_MAX=COL_MAX, PRACH_COL_RAW=COL_RAW,
                  PRACH_XTAB_NFIELDS=NFIELDS)
-HARNESS_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpu_columns_harness.hip")
+HARNESS = "gpu_columns_harness.hip"
 FILL = 0x5A5A5A5A  # what the harness fills the arena with: a word the kernel does not write
 NAMES = ("one", "arrival", "sojourn", "completion", "timer", "ptc", "failcount", "age", "state")
 MENU = tuple(range(NFIELDS))
@@ -205,10 +205,7 @@ def cases(pkg):
 # ---- the harness --------------------------------------------------------------------------------------------------------------------------------------
 
 def build_harness(out_dir):
-    """Compiles tests/tools/gpu_columns_harness.hip (host program + the kernel for gfx950) into out_dir; returns the executable's path."""
-    exe = os.path.join(str(out_dir), "gpu_columns_harness")
-    subprocess.check_call([R.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", HARNESS_SRC, "-o", exe])
-    return exe
+    return H.build(HARNESS, out_dir)
 
 
 def write_case(case, path):
@@ -216,14 +213,7 @@ def write_case(case, path):
     head[:4] = [R.MAGIC, 5, len(case.jobs), len(case.fields)]
     head[4:4 + len(case.fields)] = case.fields
     head[20] = case.tail
-    rows = np.zeros((len(case.jobs), 8), dtype=np.int32)
-    parts = [head, rows]
-    for t, j in enumerate(case.jobs):
-        rows[t, :7] = [j.nue, t, 0, j.access_time, len(j.sched), j.E, j.lead]
-        parts += [j.logs.reshape(-1), j.sched]
-    with open(path, "wb") as f:
-        for p in parts:
-            f.write(np.ascontiguousarray(p, dtype="<i4").tobytes())
+    H.write_job_case(path, head, *H.log_jobs(case.jobs, lambda t, j: [t, j.E, j.lead]))
 
 
 def read_result(case, path):
@@ -240,9 +230,7 @@ def read_result(case, path):
 
 
 def run_harness(exe, case, case_path, out_dir, timeout=120):
-    """One launch in a fresh child process.  Raises on a non-zero or signalled exit and on a timeout: the caller starts nothing more on the device."""
+    """One launch in a fresh child process (harness.run)."""
     res = os.path.join(str(out_dir), f"{case.name}.result")
-    p = subprocess.run([exe, case_path, res], capture_output=True, text=True, timeout=timeout)
-    if p.returncode != 0:
-        raise RuntimeError(f"gpu_columns_harness {case.name}: exit {p.returncode}: {p.stderr[-2000:]}")
+    H.run(exe, [case_path, res], timeout)
     return read_result(case, res)

@@ -1,27 +1,17 @@
 // tests/tools/gpu_columns_harness.hip — TEST INFRASTRUCTURE (GPU box): prach::columns_kernel launched directly, through launch_columns_kernel, on buffers of
-// this program's own, filled from a case file that tests/tools/columns_cases.py writes: per-UE state no simulation leaves behind.  One launch per process.
-// Every array — the records and the schedule of every job, the offset table, the scalars, the columns — sits at a 256-byte-aligned offset of ONE arena that
-// is filled with a pattern first, as in the engine's arena; inside the columns every trial's segment of every column has guard words in front of it and
-// behind it, which the kernel must leave at the pattern.  The kernel's source file is compiled into this program as it is; no product entry point is
-// involved (the spec check of prach_host.c is restated below: the host C file is not part of this program).
+// this program's own, filled from a case file that tests/tools/columns_cases.py writes: per-UE state no simulation leaves behind.  Every array — the
+// records and the schedule of every job, the offset table, the scalars, the columns — sits at a 256-byte-aligned offset of ONE arena that is filled with
+// the pattern 0x5A first; inside the columns every trial's segment of every column has guard words in front of it and behind it, which the kernel must
+// leave at the pattern.  The kernel's source file is compiled into this program as it is; no product entry point is involved (the spec check of
+// prach_host.c is restated below: the host C file is not part of this program).  The frame (arguments, case file, placement, upload, result file) is
+// tests/tools/harness_frame.h; the file formats are in tests/tools/HARNESS.md.
 //
-// usage: gpu_columns_harness CASE RESULT     exit code 0 = launched, synchronised and written; anything else is an error (message on stderr)
-//        gpu_columns_harness --constants     the kernel's compile-time constants, one "NAME value" per line (no device needed)
-//
-// CASE (int32, little endian):   header[32] = magic, 5, njobs, ncols, field[16], tail_guard, 0 ...
-//                                jobs[njobs][8] = nUE, trial (= the job's index), 0, aT, nslots, E, lead_guard, 0
-//                                per job, in job order: logs[nUE][16], then sched[nslots]
-//                                The rows of a column: per trial, lead_guard >= 1 guard words, then its nUE words; tail_guard >= 1 guard words at the end.
-// RESULT (int32):                header[8] = magic, 5, njobs, ncols, rows_cap, 0, 0, 0
-//                                offset[njobs] (rows), scalars[njobs][CL_SCALARS] as 64-bit words, then data[ncols][rows_cap]: as the kernel leaves them (what
-//                                it does not write stays at the fill pattern 0x5A)
+// CASE header[32] = magic, 5, njobs, ncols, field[16], tail_guard; a row's group is the job's index, word 5 its E, word 6 its lead_guard
+// RESULT (int32) header[8] = magic, 5, njobs, ncols, rows_cap, 0, 0, 0
 #include "../../5g-nr-randomaccess_amd/csrc/prach_columns.hip"
 
-#include <climits>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#define HARNESS_PROGRAM "gpu_columns_harness"
+#include "harness_frame.h"
 
 extern "C" int prach_internal_columns_spec_ok(const prach_columns_spec *s) { // prach_host.c's, for this program
     if (!s || s->ncols < 1 || s->ncols > PRACH_COL_MAX || s->reserved[0] || s->reserved[1] || s->reserved[2]) return 0;
@@ -30,130 +20,57 @@ extern "C" int prach_internal_columns_spec_ok(const prach_columns_spec *s) { // 
     return 1;
 }
 
-namespace {
-
-constexpr int MAGIC = 0x52445543;
-constexpr long long MAX_UE_TOTAL = 1ll << 22, MAX_JOBS = 1 << 12, MAX_GUARD = 1 << 12;
-
-#define CHK(call)                                                                                               \
-    do {                                                                                                        \
-        const hipError_t rc_ = (call);                                                                          \
-        if (rc_ != hipSuccess) {                                                                                \
-            fprintf(stderr, "gpu_columns_harness: %s: %s (line %d)\n", #call, hipGetErrorString(rc_), __LINE__); \
-            return 2;                                                                                           \
-        }                                                                                                       \
-    } while (0)
-
-int fail(const char *what) {
-    fprintf(stderr, "gpu_columns_harness: %s\n", what);
-    return 3;
-}
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct JobRow { int nUE, group, form, aT, nslots, E, lead, pad; };
-
-} // namespace
+static const char USAGE[] = "usage: gpu_columns_harness CASE RESULT | --check CASE | --constants";
+constexpr int MAX_GUARD = 1 << 12;
 
 int main(int argc, char **argv) {
     using namespace prach;
-    if (argc == 2 && !strcmp(argv[1], "--constants")) {
+    Args a;
+    const int rc = arguments(argc, argv, USAGE, [] {
         printf("TL_TILE %d\nTL_THREADS %d\nTILE_SCHED_CAP %d\nCL_SCALARS %d\nCL_SUMS %d\nPRACH_COL_MAX %d\nPRACH_COL_RAW %d\nPRACH_XTAB_NFIELDS %d\n", TL_TILE, TL_THREADS, TILE_SCHED_CAP,
                CL_SCALARS, CL_SUMS, PRACH_COL_MAX, PRACH_COL_RAW, (int)PRACH_XTAB_NFIELDS);
-        return 0;
-    }
-    if (argc != 3) return fail("usage: gpu_columns_harness CASE RESULT | --constants");
+    }, a);
+    if (rc >= 0) return rc;
+    if (a.n != 0) return fail(USAGE);
 
-    // ---- the case file, whole
-    FILE *f = fopen(argv[1], "rb");
-    if (!f) return fail("cannot open the case file");
-    fseek(f, 0, SEEK_END);
-    const long fbytes = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    if (fbytes < 128 || fbytes % 4) { fclose(f); return fail("case file: bad length"); }
-    std::vector<int> w((size_t)fbytes / 4);
-    const size_t got = fread(w.data(), 4, w.size(), f);
-    fclose(f);
-    if (got != w.size()) return fail("case file: short read");
-    const int kind = w[1], njobs = w[2], tail_guard = w[20];
-    if (w[0] != MAGIC || kind != 5) return fail("case file: bad header");
+    Case c;
+    if (const int e = c.read(a.in, 32, {5}, 1 << 12)) return e;
+    const int njobs = c.njobs, tail_guard = c.w[20];
     prach_columns_spec sp{};
-    sp.ncols = w[3];
-    for (int c = 0; c < PRACH_COL_MAX; c++) sp.field[c] = w[4 + c];
-    if (njobs < 1 || njobs > MAX_JOBS || !prach_internal_columns_spec_ok(&sp)) return fail("case file: njobs out of range or a bad spec"); // (ncols bounds every column store)
+    sp.ncols = c.w[3];
+    for (int q = 0; q < PRACH_COL_MAX; q++) sp.field[q] = c.w[4 + q];
+    if (!prach_internal_columns_spec_ok(&sp)) return fail("case file: a bad spec"); // (ncols bounds every column store)
     if (tail_guard < 1 || tail_guard > MAX_GUARD) return fail("case file: tail guard out of range");
-    if (w.size() < 32 + 8 * (size_t)njobs) return fail("case file: job table cut short");
-    const JobRow *const jr = reinterpret_cast<const JobRow *>(w.data() + 32);
+    const Rule rule{true, 0, TL_TILE, E_PASSED, 1ll << 22, false}; // (a trial index is the offset of the stores: it is the job's index)
+    if (const int e = c.place(rule)) return e;
 
-    // ---- every array of every job: checked against the file, placed at a 256-byte-aligned arena offset; the rows of a column laid out with their guards
-    struct Place { size_t src_a, n_a, dst_a, src_b, n_b, dst_b; }; // in ints (src, n) and bytes (dst)
-    std::vector<Place> pl((size_t)njobs);
-    std::vector<unsigned long long> offset((size_t)njobs);
-    size_t src = 32 + 8 * (size_t)njobs, arena = 0, rows = 0;
-    long long total_ue = 0;
+    // ---- the rows of a column: per trial its lead guard, then its nUE words; the tail guard at the end.  Offset table, scalars and columns go into the arena
+    std::vector<int> head(8 + 2 * (size_t)njobs, 0); // the result's header, then offset[njobs] as 64-bit words
+    size_t rows = 0;
     for (int j = 0; j < njobs; j++) {
-        const JobRow &r = jr[j];
-        if (r.nUE < 1 || r.group != j) return fail("job: nUE out of range, or the trial is not the job's index"); // (a trial index is the offset of the stores)
-        if (r.lead < 1 || r.lead > MAX_GUARD) return fail("job: lead guard out of range");
-        total_ue += r.nUE;
-        if (total_ue > MAX_UE_TOTAL) return fail("case file: too many UEs");
-        if (r.aT < 1 || r.nslots < 1 || r.nslots > (1 << 20) || (long long)r.aT * r.nslots > INT_MAX) return fail("job: aT / nslots out of range");
-        const size_t na = 16 * (size_t)r.nUE, nb = (size_t)r.nslots;
-        if (src + na + nb > w.size()) return fail("case file: arrays cut short");
-        pl[(size_t)j] = Place{src, na, arena, src + na, nb, align256(arena + 4 * na)};
-        arena = align256(pl[(size_t)j].dst_b + 4 * nb);
-        src += na + nb;
-        const int *const s = w.data() + pl[(size_t)j].src_b; // a schedule is non-decreasing and counts UEs of this trial: the kernel's searches assume it
-        for (int q = 0; q < r.nslots; q++)
-            if (s[q] < 0 || s[q] > r.nUE || (q && s[q] < s[q - 1])) return fail("job: schedule not a non-decreasing count of UEs");
-        rows += (size_t)r.lead;
-        offset[(size_t)j] = rows; // [offset, offset + nUE) is inside [0, rows_cap) of every column: rows only grows, and rows_cap is its final value
-        rows += (size_t)r.nUE;
+        if (c.rows[j].lead < 1 || c.rows[j].lead > MAX_GUARD) return fail("job: lead guard out of range");
+        rows += (size_t)c.rows[j].lead;
+        head[8 + 2 * (size_t)j] = (int)rows; // [offset, offset + nUE) is inside [0, rows_cap) of every column: rows only grows, and rows_cap is its final value
+        rows += (size_t)c.rows[j].nUE;
     }
-    if (src != w.size()) return fail("case file: trailing data");
-    const size_t rows_cap = rows + (size_t)tail_guard;
-    const size_t at_off = arena, at_sc = align256(at_off + 8 * (size_t)njobs), at_data = align256(at_sc + 8 * (size_t)njobs * CL_SCALARS);
-    const size_t data_words = (size_t)sp.ncols * rows_cap;
-    arena = align256(at_data + 4 * data_words);
+    const size_t rows_cap = rows + (size_t)tail_guard, sc_bytes = 8 * (size_t)njobs * CL_SCALARS, data_bytes = 4 * (size_t)sp.ncols * rows_cap;
+    const size_t at_off = c.arena, at_sc = align256(at_off + 8 * (size_t)njobs), at_data = align256(at_sc + sc_bytes);
+    c.arena = align256(at_data + data_bytes);
+    if (a.check) return 0;
 
-    std::vector<unsigned char> stage(arena, 0x5A); // (the gaps between arrays, the guards and the columns hold a pattern, never zeros)
-    for (int j = 0; j < njobs; j++) {
-        const Place &p = pl[(size_t)j];
-        memcpy(stage.data() + p.dst_a, w.data() + p.src_a, 4 * p.n_a);
-        memcpy(stage.data() + p.dst_b, w.data() + p.src_b, 4 * p.n_b);
-    }
-    memcpy(stage.data() + at_off, offset.data(), 8 * (size_t)njobs);
-    memset(stage.data() + at_sc, 0, 8 * (size_t)njobs * CL_SCALARS); // (the scalars are added to: the engine zeroes them)
+    c.stage(0x5A); // (the gaps between arrays, the guards and the columns hold a pattern, never zeros)
+    memcpy(c.staged.data() + at_off, head.data() + 8, 8 * (size_t)njobs);
+    memset(c.staged.data() + at_sc, 0, sc_bytes); // (the scalars are added to: the engine zeroes them)
 
     // ---- device: ONE arena, the job table; ONE launch
-    unsigned char *A = nullptr;
-    CHK(hipMalloc(reinterpret_cast<void **>(&A), arena));
-    CHK(hipMemcpy(A, stage.data(), arena, hipMemcpyHostToDevice));
-    std::vector<TimelineJob> jobs((size_t)njobs);
-    int wgs = 0;
-    for (int j = 0; j < njobs; j++) {
-        jobs[(size_t)j] = TimelineJob{reinterpret_cast<const int4 *>(A + pl[(size_t)j].dst_a), reinterpret_cast<const int *>(A + pl[(size_t)j].dst_b), jr[j].nUE, jr[j].group, wgs,
-                                      jr[j].aT, jr[j].nslots, jr[j].E};
-        wgs += (jr[j].nUE + TL_TILE - 1) / TL_TILE;
-    }
+    if (const int e = c.upload()) return e;
     TimelineJob *tj = nullptr;
-    CHK(hipMalloc(reinterpret_cast<void **>(&tj), sizeof(TimelineJob) * jobs.size()));
-    CHK(hipMemcpy(tj, jobs.data(), sizeof(TimelineJob) * jobs.size(), hipMemcpyHostToDevice));
-    CHK(launch_columns_kernel(tj, njobs, wgs, sp,
-                              ColumnsOut{reinterpret_cast<int *>(A + at_data), (unsigned long long)rows_cap, reinterpret_cast<const unsigned long long *>(A + at_off),
-                                         reinterpret_cast<unsigned long long *>(A + at_sc)},
+    if (const int e = c.timeline_table(rule, tj)) return e;
+    CHK(launch_columns_kernel(tj, njobs, c.wgs, sp,
+                              ColumnsOut{reinterpret_cast<int *>(c.A + at_data), (unsigned long long)rows_cap, reinterpret_cast<const unsigned long long *>(c.A + at_off),
+                                         reinterpret_cast<unsigned long long *>(c.A + at_sc)},
                               nullptr));
     CHK(hipDeviceSynchronize());
-
-    const size_t tail_words = 2 * (size_t)njobs + 2 * (size_t)njobs * CL_SCALARS + data_words;
-    std::vector<int> res(8 + tail_words, 0);
-    res[0] = MAGIC; res[1] = 5; res[2] = njobs; res[3] = sp.ncols; res[4] = (int)rows_cap;
-    for (int j = 0; j < njobs; j++) { res[8 + 2 * (size_t)j] = (int)offset[(size_t)j]; res[9 + 2 * (size_t)j] = 0; }
-    CHK(hipMemcpy(res.data() + 8 + 2 * (size_t)njobs, A + at_sc, 8 * (size_t)njobs * CL_SCALARS, hipMemcpyDeviceToHost));
-    CHK(hipMemcpy(res.data() + 8 + 2 * (size_t)njobs + 2 * (size_t)njobs * CL_SCALARS, A + at_data, 4 * data_words, hipMemcpyDeviceToHost));
-    FILE *g = fopen(argv[2], "wb");
-    if (!g) return fail("cannot open the result file");
-    const size_t put = fwrite(res.data(), 4, res.size(), g);
-    if (fclose(g) != 0 || put != res.size()) return fail("result file: short write");
-    return 0;
+    head[0] = MAGIC; head[1] = 5; head[2] = njobs; head[3] = sp.ncols; head[4] = (int)rows_cap;
+    return write_result(a.out, head.data(), 4 * head.size(), {{c.A + at_sc, sc_bytes}, {c.A + at_data, data_bytes}});
 }

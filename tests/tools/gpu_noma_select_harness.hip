@@ -1,25 +1,15 @@
 // tests/tools/gpu_noma_select_harness.hip — TEST INFRASTRUCTURE (GPU box): prach::noma_summary_kernel and prach::noma_pick_kernel launched directly, through
 // their launch functions, on buffers of this program's own, filled from a case file that tests/tools/noma_select_cases.py writes: per-UE state no simulation
-// leaves behind.  One launch per process, every HIP return checked; every per-job array sits at a 256-byte-aligned device offset, as in the engine's arena
-// (the kernels' 16-byte loads rely on it).  The kernels' source file is compiled into this program as it is; no product entry point is involved.
+// leaves behind.  The kernels' source file is compiled into this program as it is; no product entry point is involved.  The frame (arguments, case file,
+// placement, upload, result file) is tests/tools/harness_frame.h; the file formats are in tests/tools/HARNESS.md.
 //
-// usage: gpu_noma_select_harness CASE RESULT THREADS     THREADS 512 or 1024; exit code 0 = launched, synchronised and written
-//        gpu_noma_select_harness --constants            the kernels' compile-time constants, one "NAME value" per line (no device needed)
-//
-// CASE (int32, little endian):   header[32] = magic, kind (11 summary, 12 pick), njobs, 0, spec (15 or 17 words), 0 ...
-//                                  spec, summary: who, nfields, field[4], nq, permille[8]      pick: who, nclauses, clause[4] = {field, lo, hi}, order, key_field, k
-//                                jobs[njobs][8] = nUE, group (= the job's number), 0, aT, nslots, E, 0, 0
-//                                per job, in job order: logs[nUE][16], then sched[nslots]
-// RESULT summary (int64):        header[4] = magic, 11, threads, njobs; rows[njobs][NSM_WORDS]
-// RESULT pick (int64):           header[4] = magic, 12, threads, njobs; scalars[njobs][PK_SCALARS]; then int32 rows[njobs][k][20] and GUARD words, all filled with
-//                                the pattern 0x7FFF7FFF before the launch (the rows behind a trial's `stored` and the GUARD words must keep it)
+// CASE header[32] = magic, kind (11 summary, 12 pick), njobs, 0, spec (15 or 17 words); a row's group is the job's number, word 5 its E >= 0
+//   spec, summary: who, nfields, field[4], nq, permille[8]      pick: who, nclauses, clause[4] = {field, lo, hi}, order, key_field, k
+// RESULT (int64) header[4] = magic, kind, threads, njobs; everything behind it at PATTERN before the launch; pick: the int32 rows and GUARD words at the end
 #include "../../5g-nr-randomaccess_amd/csrc/prach_noma_select.hip"
 
-#include <climits>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#define HARNESS_PROGRAM "gpu_noma_select_harness"
+#include "harness_frame.h"
 
 // prach_host.c's judgement of the two specs, restated for this program (it links no product object)
 extern "C" int prach_internal_noma_summary_spec_ok(const prach_noma_summary_spec *s) {
@@ -43,57 +33,26 @@ extern "C" int prach_internal_noma_pick_spec_ok(const prach_pick_spec *s) {
     return 1;
 }
 
-namespace {
-
-constexpr int MAGIC = 0x52445543, PATTERN = 0x7FFF7FFF, GUARD = 64;
-constexpr long long MAX_UE_TOTAL = 1ll << 24, MAX_JOBS = 1 << 12;
-
-#define CHK(call)                                                                                                     \
-    do {                                                                                                              \
-        const hipError_t rc_ = (call);                                                                                \
-        if (rc_ != hipSuccess) {                                                                                      \
-            fprintf(stderr, "gpu_noma_select_harness: %s: %s (line %d)\n", #call, hipGetErrorString(rc_), __LINE__); \
-            return 2;                                                                                                 \
-        }                                                                                                             \
-    } while (0)
-
-int fail(const char *what) {
-    fprintf(stderr, "gpu_noma_select_harness: %s\n", what);
-    return 3;
-}
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct JobRow { int nUE, group, form, aT, nslots, E, pad[2]; };
-
-} // namespace
+static const char USAGE[] = "usage: gpu_noma_select_harness CASE RESULT THREADS | --check CASE | --constants";
+constexpr int PATTERN = 0x7FFF7FFF, GUARD = 64;
 
 int main(int argc, char **argv) {
     using namespace prach;
-    if (argc == 2 && !strcmp(argv[1], "--constants")) {
+    Args a;
+    const int rc = arguments(argc, argv, USAGE, [] {
         printf("NS_SCHED_CAP %d\nNS_COARSE %d\nNS_FINE %d\nNS_MAX_KEY %d\nNSM_WORDS %d\nPK_ROW_WORDS %d\nPK_SCALARS %d\nNSM_LDS_WORDS %d\nNS_LDS_WORDS %d\n", noma_select_sched_cap(),
                NS_COARSE, NS_FINE, NS_MAX_KEY, NSM_WORDS, PK_ROW_WORDS, PK_SCALARS, NSM_FIXED_WORDS, NS_FIXED_WORDS);
-        return 0;
-    }
-    if (argc != 4) return fail("usage: gpu_noma_select_harness CASE RESULT THREADS | --constants");
-    const int threads = atoi(argv[3]);
+    }, a);
+    if (rc >= 0) return rc;
+    if (a.n != (a.check ? 0 : 1)) return fail(USAGE);
+    const int threads = a.check ? 512 : atoi(a.v[0]);
     if (threads != 512 && threads != 1024) return fail("THREADS is 512 or 1024");
 
-    // ---- the case file, whole
-    FILE *f = fopen(argv[1], "rb");
-    if (!f) return fail("cannot open the case file");
-    fseek(f, 0, SEEK_END);
-    const long fbytes = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    if (fbytes < 128 || fbytes % 4) { fclose(f); return fail("case file: bad length"); }
-    std::vector<int> w((size_t)fbytes / 4);
-    const size_t got = fread(w.data(), 4, w.size(), f);
-    fclose(f);
-    if (got != w.size()) return fail("case file: short read");
-    if (w[0] != MAGIC || (w[1] != 11 && w[1] != 12)) return fail("case file: bad header");
+    Case c;
+    if (const int e = c.read(a.in, 32, {11, 12}, 1 << 12)) return e;
+    const std::vector<int> &w = c.w;
     const bool summary = w[1] == 11;
-    const int njobs = w[2];
-    if (njobs < 1 || njobs > MAX_JOBS) return fail("case file: njobs out of range");
+    const int njobs = c.njobs;
     prach_noma_summary_spec ss{};
     prach_pick_spec ps{};
     if (summary) {
@@ -103,79 +62,28 @@ int main(int argc, char **argv) {
         if (!prach_internal_noma_summary_spec_ok(&ss)) return fail("case file: summary spec out of range");
     } else {
         ps.who = w[4]; ps.nclauses = w[5]; ps.order = w[18]; ps.key_field = w[19]; ps.k = w[20];
-        for (int c = 0; c < 4; c++) ps.clause[c] = prach_pick_clause{w[6 + 3 * c], w[7 + 3 * c], w[8 + 3 * c]};
+        for (int q = 0; q < 4; q++) ps.clause[q] = prach_pick_clause{w[6 + 3 * q], w[7 + 3 * q], w[8 + 3 * q]};
         if (!prach_internal_noma_pick_spec_ok(&ps)) return fail("case file: pick spec out of range");
     }
-    if (w.size() < 32 + 8 * (size_t)njobs) return fail("case file: job table cut short");
-    const JobRow *const jr = reinterpret_cast<const JobRow *>(w.data() + 32);
-
-    // ---- every array of every job: checked against the file, placed at a 256-byte-aligned arena offset
-    struct Place { size_t src_a, n_a, dst_a, src_b, n_b, dst_b; }; // in ints (src, n) and bytes (dst)
-    std::vector<Place> pl((size_t)njobs);
-    size_t src = 32 + 8 * (size_t)njobs, arena = 0;
-    long long total_ue = 0;
-    int max_slots = 0;
-    for (int j = 0; j < njobs; j++) {
-        const JobRow &r = jr[j];
-        if (r.nUE < 1 || r.group != j) return fail("job: nUE out of range, or a group that is not the job's number");
-        total_ue += r.nUE;
-        if (total_ue > MAX_UE_TOTAL) return fail("case file: too many UEs");
-        if (r.aT < 1 || r.nslots < 1 || r.nslots > (1 << 20) || (long long)r.aT * r.nslots > INT_MAX || r.E < 0) return fail("job: aT / nslots / E out of range");
-        const size_t na = 16 * (size_t)r.nUE, nb = (size_t)r.nslots;
-        if (r.nslots > max_slots) max_slots = r.nslots;
-        if (src + na + nb > w.size()) return fail("case file: arrays cut short");
-        pl[(size_t)j] = Place{src, na, arena, src + na, nb, align256(arena + 4 * na)};
-        arena = align256(pl[(size_t)j].dst_b + 4 * nb);
-        src += na + nb;
-        const int *const s = w.data() + pl[(size_t)j].src_b; // a schedule is non-decreasing and counts UEs of this trial: the kernels' searches assume it
-        for (int q = 0; q < r.nslots; q++)
-            if (s[q] < 0 || s[q] > r.nUE || (q && s[q] < s[q - 1])) return fail("job: schedule not a non-decreasing count of UEs");
-    }
-    if (src != w.size()) return fail("case file: trailing data");
-
-    std::vector<unsigned char> stage(arena, 0xA5); // (the gaps between arrays hold a pattern, never zeros)
-    for (int j = 0; j < njobs; j++) {
-        const Place &p = pl[(size_t)j];
-        memcpy(stage.data() + p.dst_a, w.data() + p.src_a, 4 * p.n_a);
-        memcpy(stage.data() + p.dst_b, w.data() + p.src_b, 4 * p.n_b);
-    }
+    const Rule rule{true, 0, 0, E_NOT_NEGATIVE, 1ll << 24, false}; // (a job's group is its number: the offset of its stores)
+    if (const int e = c.place(rule)) return e;
+    if (a.check) return 0;
 
     // ---- device: arena, job table, patterned outputs; ONE launch
-    unsigned char *A = nullptr;
-    CHK(hipMalloc(reinterpret_cast<void **>(&A), arena));
-    CHK(hipMemcpy(A, stage.data(), arena, hipMemcpyHostToDevice));
-    std::vector<TimelineJob> jobs((size_t)njobs);
-    for (int j = 0; j < njobs; j++)
-        jobs[(size_t)j] = TimelineJob{reinterpret_cast<const int4 *>(A + pl[(size_t)j].dst_a), reinterpret_cast<const int *>(A + pl[(size_t)j].dst_b), jr[j].nUE, j, j, jr[j].aT, jr[j].nslots, jr[j].E};
+    if (const int e = c.upload()) return e;
     TimelineJob *tj = nullptr;
-    CHK(hipMalloc(reinterpret_cast<void **>(&tj), sizeof(TimelineJob) * jobs.size()));
-    CHK(hipMemcpy(tj, jobs.data(), sizeof(TimelineJob) * jobs.size(), hipMemcpyHostToDevice));
-    const int scap = max_slots < noma_select_sched_cap() ? max_slots : noma_select_sched_cap(); // the engine's rule
+    if (const int e = c.timeline_table(rule, tj)) return e;
+    const int scap = c.max_slots < noma_select_sched_cap() ? c.max_slots : noma_select_sched_cap(); // the engine's rule
     // 64-bit words: the summary's rows, or the pick's scalars; then, pick only, the rows and the guard as 32-bit words
     const size_t head_words = summary ? (size_t)njobs * NSM_WORDS : (size_t)njobs * PK_SCALARS;
     const size_t row_ints = summary ? 0 : (size_t)njobs * (size_t)ps.k * 2 * PK_ROW_WORDS + GUARD;
-    std::vector<unsigned long long> head(4 + head_words, 0x7FFF7FFF7FFF7FFFull);
-    std::vector<int> rows(row_ints, PATTERN);
     unsigned long long *H = nullptr;
     int *R = nullptr;
-    CHK(hipMalloc(reinterpret_cast<void **>(&H), 8 * head_words));
-    CHK(hipMemcpy(H, head.data() + 4, 8 * head_words, hipMemcpyHostToDevice));
-    if (summary) {
-        CHK(launch_noma_summary_kernel(tj, njobs, ss, threads, scap, H, nullptr));
-    } else {
-        CHK(hipMalloc(reinterpret_cast<void **>(&R), 4 * row_ints));
-        CHK(hipMemcpy(R, rows.data(), 4 * row_ints, hipMemcpyHostToDevice));
-        CHK(launch_noma_pick_kernel(tj, njobs, ps, threads, scap, reinterpret_cast<unsigned long long *>(R), H, nullptr));
-    }
+    if (const int e = device_words(H, 2 * head_words, PATTERN)) return e;
+    if (const int e = device_words(R, row_ints, PATTERN)) return e;
+    if (summary) CHK(launch_noma_summary_kernel(tj, njobs, ss, threads, scap, H, nullptr));
+    else CHK(launch_noma_pick_kernel(tj, njobs, ps, threads, scap, reinterpret_cast<unsigned long long *>(R), H, nullptr));
     CHK(hipDeviceSynchronize());
-    CHK(hipMemcpy(head.data() + 4, H, 8 * head_words, hipMemcpyDeviceToHost));
-    if (!summary) CHK(hipMemcpy(rows.data(), R, 4 * row_ints, hipMemcpyDeviceToHost));
-
-    head[0] = (unsigned long long)MAGIC; head[1] = summary ? 11ull : 12ull; head[2] = (unsigned long long)threads; head[3] = (unsigned long long)njobs;
-    FILE *g = fopen(argv[2], "wb");
-    if (!g) return fail("cannot open the result file");
-    size_t put = fwrite(head.data(), 8, head.size(), g);
-    put += fwrite(rows.data(), 4, rows.size(), g);
-    if (fclose(g) != 0 || put != head.size() + rows.size()) return fail("result file: short write");
-    return 0;
+    const unsigned long long head[4] = {(unsigned long long)MAGIC, summary ? 11ull : 12ull, (unsigned long long)threads, (unsigned long long)njobs};
+    return write_result(a.out, head, sizeof head, {{H, 8 * head_words}, {R, 4 * row_ints}});
 }

@@ -1,163 +1,59 @@
 // tests/tools/gpu_reduce_harness.hip — TEST INFRASTRUCTURE (GPU box): prach::dist_kernel and prach::timeline_kernel launched directly, through
 // launch_dist_kernel / launch_timeline_kernel, on buffers of this program's own, filled from a case file that tests/tools/reduce_cases.py writes: per-UE
-// state no simulation leaves behind.  One launch per process; every per-job array sits at a 256-byte-aligned device offset, as in the engine's arena
-// (the kernels' 16-byte loads rely on it).  The kernels' source files are compiled into this program as they are; no product entry point is involved.
+// state no simulation leaves behind.  The kernels' source files are compiled into this program as they are; no product entry point is involved.  The frame
+// (arguments, case file, placement, upload, result file) is tests/tools/harness_frame.h; the file formats are in tests/tools/HARNESS.md.
 //
-// usage: gpu_reduce_harness CASE RESULT SCHEME     exit code 0 = launched, synchronised and written; anything else is an error (message on stderr)
-//        gpu_reduce_harness --constants            the kernels' compile-time constants, one "NAME value" per line (no device needed)
-//
-// CASE (int32, little endian):   header[16] = magic, kind (0 dist, 1 timeline), njobs, bins, width, ngroups, 0 ...
-//                                jobs[njobs][8] = nUE, group, form, aT, nslots, 0, 0, 0          (form: dist only; aT, nslots: timeline only)
-//                                per job, in job order:  dist      timers[nUE], then ptc[nUE] (form 0) or rec32[nUE][8] (form 1)
-//                                                        timeline  logs[nUE][16], then sched[nslots]
-// RESULT (uint64):               header[4] = magic, kind, scheme, workgroups
-//                                dist      delay_hist[ngroups][bins], ptc_hist[ngroups][256], scalars[ngroups][8]
-//                                timeline  arrivals, success, sojourn, timer, done: [ngroups][bins] each, then scalars[ngroups][8]
+// usage: gpu_reduce_harness CASE RESULT SCHEME | --check CASE | --constants
+// CASE header[16] = magic, kind (0 dist, 1 timeline), njobs, bins, width, ngroups     RESULT (uint64) header[4] = magic, kind, scheme, workgroups
 #include "../../5g-nr-randomaccess_amd/csrc/prach_dist.hip"
 #include "../../5g-nr-randomaccess_amd/csrc/prach_timeline.hip"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#define HARNESS_PROGRAM "gpu_reduce_harness"
+#include "harness_frame.h"
 
-namespace {
-
-constexpr int MAGIC = 0x52445543;
-constexpr long long MAX_UE_TOTAL = 1ll << 24, MAX_JOBS = 1 << 16, MAX_GROUPS = 4096;
-
-#define CHK(call)                                                                                             \
-    do {                                                                                                      \
-        const hipError_t rc_ = (call);                                                                        \
-        if (rc_ != hipSuccess) {                                                                              \
-            fprintf(stderr, "gpu_reduce_harness: %s: %s (line %d)\n", #call, hipGetErrorString(rc_), __LINE__); \
-            return 2;                                                                                         \
-        }                                                                                                     \
-    } while (0)
-
-int fail(const char *what) {
-    fprintf(stderr, "gpu_reduce_harness: %s\n", what);
-    return 3;
-}
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct JobRow { int nUE, group, form, aT, nslots, pad[3]; };
-
-} // namespace
+static const char USAGE[] = "usage: gpu_reduce_harness CASE RESULT SCHEME | --check CASE | --constants";
 
 int main(int argc, char **argv) {
     using namespace prach;
-    if (argc == 2 && !strcmp(argv[1], "--constants")) {
+    Args a;
+    const int rc = arguments(argc, argv, USAGE, [] {
         printf("DIST_TILE %d\nDIST_THREADS %d\nDIST_PTC_BINS %d\nDIST_SCALARS %d\nTL_TILE %d\nTL_THREADS %d\nTL_WINDOW %d\nTL_MAX_SOJOURN %d\nTL_SCHED_CAP %d\nTL_SCALARS %d\n",
                DIST_TILE, DIST_THREADS, PB, DIST_SCALARS, TL_TILE, TL_THREADS, TL_WINDOW, TL_MAX_SOJOURN, TL_SCHED_CAP, TL_SCALARS);
-        return 0;
-    }
-    if (argc != 4) return fail("usage: gpu_reduce_harness CASE RESULT SCHEME | --constants");
-    const int scheme = atoi(argv[3]);
+    }, a);
+    if (rc >= 0) return rc;
+    if (a.n != (a.check ? 0 : 1)) return fail(USAGE);
+    const int scheme = a.check ? 0 : atoi(a.v[0]);
 
-    // ---- the case file, whole
-    FILE *f = fopen(argv[1], "rb");
-    if (!f) return fail("cannot open the case file");
-    fseek(f, 0, SEEK_END);
-    const long fbytes = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    if (fbytes < 64 || fbytes % 4) { fclose(f); return fail("case file: bad length"); }
-    std::vector<int> w((size_t)fbytes / 4);
-    const size_t got = fread(w.data(), 4, w.size(), f);
-    fclose(f);
-    if (got != w.size()) return fail("case file: short read");
-    const int kind = w[1], njobs = w[2], bins = w[3], width = w[4], ngroups = w[5];
-    if (w[0] != MAGIC || (kind != 0 && kind != 1)) return fail("case file: bad header");
-    if (njobs < 1 || njobs > MAX_JOBS || ngroups < 1 || ngroups > MAX_GROUPS || width < 1) return fail("case file: njobs / ngroups / width out of range");
+    Case c;
+    if (const int e = c.read(a.in, 16, {0, 1}, 1 << 16)) return e;
+    const int kind = c.w[1], bins = c.w[3], width = c.w[4], ngroups = c.w[5];
+    if (ngroups < 1 || ngroups > 4096 || width < 1) return fail("case file: ngroups / width out of range");
     if (bins < 1 || bins > (kind == 0 ? PRACH_DIST_MAX_DELAY_BINS : PRACH_TIMELINE_MAX_BINS)) return fail("case file: bins out of range");
     if (scheme < 0 || scheme > (kind == 0 ? 2 : 1)) return fail("scheme out of range");
-    if (w.size() < 16 + 8 * (size_t)njobs) return fail("case file: job table cut short");
-    const JobRow *const rows = reinterpret_cast<const JobRow *>(w.data() + 16);
-
-    // ---- every array of every job: checked against the file, placed at a 256-byte-aligned arena offset
-    struct Place { size_t src_a, n_a, dst_a, src_b, n_b, dst_b; }; // in ints (src, n) and bytes (dst)
-    std::vector<Place> pl((size_t)njobs);
-    size_t src = 16 + 8 * (size_t)njobs, arena = 0;
-    long long total_ue = 0;
-    int wgs = 0;
-    for (int j = 0; j < njobs; j++) {
-        const JobRow &r = rows[j];
-        if (r.nUE < 1 || r.group < 0 || r.group >= ngroups) return fail("job: nUE / group out of range");
-        total_ue += r.nUE;
-        if (total_ue > MAX_UE_TOTAL) return fail("case file: too many UEs");
-        size_t na, nb;
-        if (kind == 0) {
-            if (r.form != 0 && r.form != 1) return fail("job: form");
-            na = (size_t)r.nUE; nb = r.form ? 8 * (size_t)r.nUE : (size_t)r.nUE;
-            wgs += (r.nUE + DIST_TILE - 1) / DIST_TILE;
-        } else {
-            if (r.aT < 1 || r.nslots < 1 || r.nslots > (1 << 20) || (long long)r.aT * r.nslots > INT_MAX) return fail("job: aT / nslots out of range");
-            na = 16 * (size_t)r.nUE; nb = (size_t)r.nslots;
-            wgs += (r.nUE + TL_TILE - 1) / TL_TILE;
-        }
-        if (src + na + nb > w.size()) return fail("case file: arrays cut short");
-        pl[(size_t)j] = Place{src, na, arena, src + na, nb, align256(arena + 4 * na)};
-        arena = align256(pl[(size_t)j].dst_b + 4 * nb);
-        src += na + nb;
-        if (kind == 1) { // a schedule is non-decreasing and counts UEs of this trial: the kernel's searches assume it
-            const int *const s = w.data() + pl[(size_t)j].src_b;
-            for (int q = 0; q < r.nslots; q++)
-                if (s[q] < 0 || s[q] > r.nUE || (q && s[q] < s[q - 1])) return fail("job: schedule not a non-decreasing count of UEs");
-        }
-    }
-    if (src != w.size()) return fail("case file: trailing data");
-
-    std::vector<unsigned char> stage(arena, 0xA5); // (the gaps between arrays hold a pattern, never zeros)
-    for (int j = 0; j < njobs; j++) {
-        const Place &p = pl[(size_t)j];
-        memcpy(stage.data() + p.dst_a, w.data() + p.src_a, 4 * p.n_a);
-        memcpy(stage.data() + p.dst_b, w.data() + p.src_b, 4 * p.n_b);
-    }
+    const Rule rule{kind == 1, ngroups, kind == 0 ? DIST_TILE : TL_TILE, E_UNUSED, 1ll << 24, false};
+    if (const int e = c.place(rule)) return e;
+    if (a.check) return 0;
 
     // ---- device: arena, job table, zeroed outputs; ONE launch
-    unsigned char *A = nullptr;
-    CHK(hipMalloc(reinterpret_cast<void **>(&A), arena));
-    CHK(hipMemcpy(A, stage.data(), arena, hipMemcpyHostToDevice));
-    const size_t ng = (size_t)ngroups;
-    const size_t per_series = ng * (size_t)bins;
+    if (const int e = c.upload()) return e;
+    const size_t ng = (size_t)ngroups, per_series = ng * (size_t)bins;
     const size_t out_words = kind == 0 ? per_series + ng * PB + ng * DIST_SCALARS : 5 * per_series + ng * TL_SCALARS;
     unsigned long long *O = nullptr;
-    CHK(hipMalloc(reinterpret_cast<void **>(&O), 8 * out_words));
-    CHK(hipMemset(O, 0, 8 * out_words));
-    int wg0 = 0;
+    if (const int e = device_words(O, 2 * out_words, 0)) return e;
     if (kind == 0) {
-        std::vector<DistJob> jobs((size_t)njobs);
-        for (int j = 0; j < njobs; j++) {
-            jobs[(size_t)j] = DistJob{reinterpret_cast<const int *>(A + pl[(size_t)j].dst_a), reinterpret_cast<const int *>(A + pl[(size_t)j].dst_b), rows[j].nUE, rows[j].group, wg0,
-                                      rows[j].form};
-            wg0 += (rows[j].nUE + DIST_TILE - 1) / DIST_TILE;
-        }
         DistJob *dj = nullptr;
-        CHK(hipMalloc(reinterpret_cast<void **>(&dj), sizeof(DistJob) * jobs.size()));
-        CHK(hipMemcpy(dj, jobs.data(), sizeof(DistJob) * jobs.size(), hipMemcpyHostToDevice));
-        CHK(launch_dist_kernel(dj, njobs, wgs, bins, width, scheme, O, O + per_series, O + per_series + ng * PB, nullptr));
+        const int e = c.table(rule, dj, [](const JobRow &r, const unsigned char *t, const unsigned char *p, int group, int wg0) {
+            return DistJob{reinterpret_cast<const int *>(t), reinterpret_cast<const int *>(p), r.nUE, group, wg0, r.form};
+        });
+        if (e) return e;
+        CHK(launch_dist_kernel(dj, c.njobs, c.wgs, bins, width, scheme, O, O + per_series, O + per_series + ng * PB, nullptr));
     } else {
-        std::vector<TimelineJob> jobs((size_t)njobs);
-        for (int j = 0; j < njobs; j++) {
-            jobs[(size_t)j] = TimelineJob{reinterpret_cast<const int4 *>(A + pl[(size_t)j].dst_a), reinterpret_cast<const int *>(A + pl[(size_t)j].dst_b), rows[j].nUE, rows[j].group,
-                                          wg0, rows[j].aT, rows[j].nslots, 0};
-            wg0 += (rows[j].nUE + TL_TILE - 1) / TL_TILE;
-        }
         TimelineJob *tj = nullptr;
-        CHK(hipMalloc(reinterpret_cast<void **>(&tj), sizeof(TimelineJob) * jobs.size()));
-        CHK(hipMemcpy(tj, jobs.data(), sizeof(TimelineJob) * jobs.size(), hipMemcpyHostToDevice));
+        if (const int e = c.timeline_table(rule, tj)) return e;
         const TimelineOut out{O, O + per_series, O + 2 * per_series, O + 3 * per_series, O + 4 * per_series, O + 5 * per_series};
-        CHK(launch_timeline_kernel(tj, njobs, wgs, bins, width, scheme, out, nullptr));
+        CHK(launch_timeline_kernel(tj, c.njobs, c.wgs, bins, width, scheme, out, nullptr));
     }
     CHK(hipDeviceSynchronize());
-
-    std::vector<unsigned long long> res(4 + out_words);
-    res[0] = (unsigned long long)MAGIC; res[1] = (unsigned long long)kind; res[2] = (unsigned long long)scheme; res[3] = (unsigned long long)wgs;
-    CHK(hipMemcpy(res.data() + 4, O, 8 * out_words, hipMemcpyDeviceToHost));
-    FILE *g = fopen(argv[2], "wb");
-    if (!g) return fail("cannot open the result file");
-    const size_t put = fwrite(res.data(), 8, res.size(), g);
-    if (fclose(g) != 0 || put != res.size()) return fail("result file: short write");
-    return 0;
+    const unsigned long long head[4] = {(unsigned long long)MAGIC, (unsigned long long)kind, (unsigned long long)scheme, (unsigned long long)c.wgs};
+    return write_result(a.out, head, sizeof head, {{O, 8 * out_words}});
 }

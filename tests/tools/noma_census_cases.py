@@ -4,10 +4,10 @@ window and the per-wavefront-copy limit, schedule ranges longer than the staged 
 reference, and the glue around tests/tools/gpu_noma_census_harness.hip (case file, result file, one child process per launch).  Shared by
 tests/test_noma_census_cases_cpu.py and tests/test_gpu_noma_census_synthetic.py.  No GPU and no package import here."""
 import os
-import subprocess
 
 import numpy as np
 
+import harness as H
 import noma_census_ref as N
 import reduce_cases as R
 
@@ -15,7 +15,7 @@ TILE = R.TILE
 WINDOW_WORDS, COPY_CELLS = 28672, 1024  # XT_WINDOW_WORDS; NC_COPY_WORDS / the four wavefronts of a workgroup
 CONSTANTS = dict(TL_TILE=8192, TL_THREADS=256, XT_WINDOW_WORDS=WINDOW_WORDS, NC_COPY_WORDS=4096, TILE_SCHED_CAP=2048, NC_SCALARS=16, NCL_SCALARS=4)
 NC_SCALARS, NCL_SCALARS, GUARD, PATTERN = 16, 4, 64, 0x7FFF7FFF
-HARNESS_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpu_noma_census_harness.hip")
+HARNESS = "gpu_noma_census_harness.hip"
 SIZES = (1, 63, 64, 65, TILE - 1, TILE, TILE + 1, 2 * TILE + 1)
 NOMA_KW = dict(variant=2, accessTime=5)  # the product's NOMA.c schedule
 # the columns a case is also written as unless it names its own: the whole menu and three raw words (failCount, the sector, txTime)
@@ -180,24 +180,14 @@ def cases(pkg):
 # ---- the harness --------------------------------------------------------------------------------------------------------------------------------------
 
 def build_harness(out_dir):
-    """Compiles tests/tools/gpu_noma_census_harness.hip (host program + both kernels for gfx950) into out_dir; returns the executable's path."""
-    exe = os.path.join(str(out_dir), "gpu_noma_census_harness")
-    subprocess.check_call([R.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", HARNESS_SRC, "-o", exe])
-    return exe
+    return H.build(HARNESS, out_dir)
 
 
 def write_case(case, path):
     head = np.zeros(32, dtype=np.int32)
     head[:12] = [R.MAGIC, 9, len(case.jobs), case.spec[2], *case.spec[0], *case.spec[1], case.ngroups, len(case.columns)]
     head[12:12 + len(case.columns)] = case.columns
-    rows = np.zeros((len(case.jobs), 8), dtype=np.int32)
-    parts = [head, rows]
-    for k, j in enumerate(case.jobs):
-        rows[k, :6] = [j.nue, j.group, 0, j.access_time, len(j.sched), j.E]
-        parts += [j.logs.reshape(-1), j.sched]
-    with open(path, "wb") as f:
-        for p in parts:
-            f.write(np.ascontiguousarray(p, dtype="<i4").tobytes())
+    H.write_job_case(path, head, *H.log_jobs(case.jobs, lambda k, j: [j.group, j.E]))
 
 
 def read_census(case, path, scheme):
@@ -237,12 +227,13 @@ def read_columns(case, path):
     return data[:, :rows], counts
 
 
+def mode_args(mode):
+    """The harness's own arguments for mode 0 / 1 (the census under that scheme) or "columns"."""
+    return ["columns"] if mode == "columns" else ["census", mode]
+
+
 def run_harness(exe, case, case_path, mode, out_dir, timeout=120):
-    """One launch in a fresh child process under `timeout -k 10`; mode: 0 / 1 (the census under that scheme) or "columns".  Raises on a non-zero or signalled
-    exit and on a timeout: the caller starts nothing more on the device."""
+    """One launch in a fresh child process (harness.run)."""
     res = os.path.join(str(out_dir), f"{case.name}.{mode}.result")
-    args = ["columns"] if mode == "columns" else ["census", str(mode)]
-    p = subprocess.run(["timeout", "-k", "10", str(timeout), exe, case_path, res, *args], capture_output=True, text=True, timeout=timeout + 30)
-    if p.returncode != 0:
-        raise RuntimeError(f"gpu_noma_census_harness {case.name} {mode}: exit {p.returncode}: {p.stderr[-2000:]}")
+    H.run(exe, [case_path, res, *mode_args(mode)], timeout)
     return read_columns(case, res) if mode == "columns" else read_census(case, res, mode)

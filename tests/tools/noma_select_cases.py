@@ -6,10 +6,10 @@ numpy restatement of tests/tools/noma_select_ref.py as their reference, and the 
 one child process per launch).  A CASE is one launch: a kind, a spec and its trials (jobs); every case runs under both THREADS instantiations.  Shared by
 tests/test_noma_select_cases_cpu.py and tests/test_gpu_noma_select_synthetic.py.  No GPU and no package import here."""
 import os
-import subprocess
 
 import numpy as np
 
+import harness as H
 import noma_census_cases as NC
 import noma_census_ref as N
 import noma_select_ref as S
@@ -18,7 +18,7 @@ import reduce_cases as R
 CONSTANTS = dict(NS_SCHED_CAP=12288, NS_COARSE=1024, NS_FINE=64, NS_MAX_KEY=65535, NSM_WORDS=54, PK_ROW_WORDS=10, PK_SCALARS=8, NSM_LDS_WORDS=6284, NS_LDS_WORDS=1168)
 SCHED_CAP, NSM_WORDS, GUARD, PATTERN = 12288, 54, 64, 0x7FFF7FFF
 THREADS = (512, 1024)
-HARNESS_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpu_noma_select_harness.hip")
+HARNESS = "gpu_noma_select_harness.hip"
 SIZES = (1, 63, 64, 65, 511, 512, 513, 1023, 1024, 1025, 2049)
 ARRIVED = N.SERVED | N.PENDING | N.DROPPED
 Job = NC.Job
@@ -165,10 +165,7 @@ def cases(pkg):
 # ---- the harness --------------------------------------------------------------------------------------------------------------------------------------
 
 def build_harness(out_dir):
-    """Compiles tests/tools/gpu_noma_select_harness.hip (host program + both kernels for gfx950) into out_dir; returns the executable's path."""
-    exe = os.path.join(str(out_dir), "gpu_noma_select_harness")
-    subprocess.check_call([R.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", HARNESS_SRC, "-o", exe])
-    return exe
+    return H.build(HARNESS, out_dir)
 
 
 def spec_words(case):
@@ -186,15 +183,8 @@ def write_case(case, path):
     head[:3] = [R.MAGIC, 11 if case.kind == "summary" else 12, len(case.jobs)]
     words = spec_words(case)
     head[4:4 + len(words)] = words
-    rows = np.zeros((len(case.jobs), 8), dtype=np.int32)
-    parts = [head, rows]
-    for k, j in enumerate(case.jobs):
-        assert j.group == k
-        rows[k, :6] = [j.nue, j.group, 0, j.access_time, len(j.sched), j.E]
-        parts += [j.logs.reshape(-1), j.sched]
-    with open(path, "wb") as f:
-        for p in parts:
-            f.write(np.ascontiguousarray(p, dtype="<i4").tobytes())
+    assert all(j.group == k for k, j in enumerate(case.jobs))
+    H.write_job_case(path, head, *H.log_jobs(case.jobs, lambda k, j: [j.group, j.E]))
 
 
 def read_summary(case, path, threads):
@@ -283,10 +273,7 @@ def same(case, got, ref):
 
 
 def run_harness(exe, case, case_path, threads, out_dir, timeout=120):
-    """One launch in a fresh child process under `timeout -k 10`.  Raises on a non-zero or signalled exit and on a timeout: the caller starts nothing more on
-    the device."""
+    """One launch in a fresh child process (harness.run)."""
     res = os.path.join(str(out_dir), f"{case.name}.{threads}.result")
-    p = subprocess.run(["timeout", "-k", "10", str(timeout), exe, case_path, res, str(threads)], capture_output=True, text=True, timeout=timeout + 30)
-    if p.returncode != 0:
-        raise RuntimeError(f"gpu_noma_select_harness {case.name} {threads}: exit {p.returncode}: {p.stderr[-2000:]}")
+    H.run(exe, [case_path, res, threads], timeout)
     return read_summary(case, res, threads) if case.kind == "summary" else read_pick(case, res, threads)

@@ -3,10 +3,10 @@ UE-INDEX order, the keys outside 0 .. 65 535 counted and not ranked) and the glu
 process per launch).  Shared by tests/test_pick_cases_cpu.py and tests/test_gpu_pick_synthetic.py.  No GPU and no package import here."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
+import harness as H
 import pick_ref as P
 import reduce_cases as R
 import xtab_ref as X
@@ -18,7 +18,7 @@ MAX_K = 4096
 CONSTANTS = dict(PK_ROW_WORDS=ROW_WORDS, PK_SCALARS=SCALARS, PK_MAX_KEY=MAX_KEY, PK_SCHED_CAP=SCHED_CAP, PK_COARSE=1024, PK_FINE=64, PRACH_PICK_MAX_K=MAX_K,
                  PRACH_PICK_MAX_CLAUSES=4, TL_MAX_SOJOURN=60006)
 THREADS = (512, 1024)  # the two workgroup shapes of the kernel
-HARNESS_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpu_pick_harness.hip")
+HARNESS = "gpu_pick_harness.hip"
 FILL = 0x5A5A5A5A      # what the harness fills the outputs with: a row the kernel does not write
 ALL = X.SERVED | X.UNSERVED | X.IDLE
 SIZES = (1, 63, 64, 65, 511, 512, 513, 1023, 1024, 1025, 2049)  # around a wavefront, THREADS - 1 .. THREADS + 1 and 2 THREADS + 1 of both shapes
@@ -230,10 +230,7 @@ def cases(pkg):
 # ---- the harness --------------------------------------------------------------------------------------------------------------------------------------
 
 def build_harness(out_dir):
-    """Compiles tests/tools/gpu_pick_harness.hip (host program + the kernel for gfx950) into out_dir; returns the executable's path."""
-    exe = os.path.join(str(out_dir), "gpu_pick_harness")
-    subprocess.check_call([R.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", HARNESS_SRC, "-o", exe])
-    return exe
+    return H.build(HARNESS, out_dir)
 
 
 def write_case(case, path):
@@ -242,14 +239,7 @@ def write_case(case, path):
     for c, cl in enumerate(case.where):
         head[5 + 3 * c:8 + 3 * c] = cl
     head[17:20] = [case.order, case.key, case.k]
-    rows = np.zeros((len(case.jobs), 8), dtype=np.int32)
-    parts = [head, rows]
-    for t, j in enumerate(case.jobs):
-        rows[t, :6] = [j.nue, t, 0, j.access_time, len(j.sched), j.E]
-        parts += [j.logs.reshape(-1), j.sched]
-    with open(path, "wb") as f:
-        for p in parts:
-            f.write(np.ascontiguousarray(p, dtype="<i4").tobytes())
+    H.write_job_case(path, head, *H.log_jobs(case.jobs, lambda t, j: [t, j.E]))
 
 
 def read_result(case, path, threads):
@@ -263,9 +253,7 @@ def read_result(case, path, threads):
 
 
 def run_harness(exe, case, case_path, threads, out_dir, timeout=120):
-    """One launch in a fresh child process.  Raises on a non-zero or signalled exit and on a timeout: the caller starts nothing more on the device."""
+    """One launch in a fresh child process (harness.run)."""
     res = os.path.join(str(out_dir), f"{case.name}.t{threads}.result")
-    p = subprocess.run([exe, case_path, res, str(threads)], capture_output=True, text=True, timeout=timeout)
-    if p.returncode != 0:
-        raise RuntimeError(f"gpu_pick_harness {case.name} threads {threads}: exit {p.returncode}: {p.stderr[-2000:]}")
+    H.run(exe, [case_path, res, threads], timeout)
     return read_result(case, res, threads)

@@ -7,18 +7,20 @@ the mask section)."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
+
+import harness as H
+from harness import constants as harness_constants  # noqa: F401
 
 MAGIC = 0x50524D53
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-HARNESS_SRC = os.path.join(HERE, "gpu_prims_harness.hip")
+HARNESS = "gpu_prims_harness.hip"
 CSRC = os.path.join(ROOT, "5g-nr-randomaccess_amd", "csrc")
 SECTIONS = dict(philox=1, masks=2, wave=3, mod=4, sector=5, granule=6, blocks=7, hot=8, pack=9)
-PRODUCT_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"]
+PRODUCT_FLAGS = ["-ffp-contract=off"]  # on top of harness.FLAGS
 NOBITOP3_FLAGS = ["-DPRACH_NO_BITOP3", "-Xclang", "-target-feature", "-Xclang", "-bitop3-insts"]  # csrc/Makefile, NOBITOP3=1
 BUILDS = ("product", "nobitop3")
 U32 = 0xFFFFFFFF
@@ -27,23 +29,12 @@ INT_MIN, INT_MAX = -2**31, 2**31 - 1
 
 # ---- the harness ------------------------------------------------------------------------------------------------------------------------------------------
 
-def hipcc():
-    return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
 def build_harness(out_dir):
     """Compiles tests/tools/gpu_prims_harness.hip twice, side by side: with the product's flags and with the NOBITOP3 flags of csrc/Makefile on top.
     {build name: executable}."""
-    exes = {b: os.path.join(str(out_dir), f"gpu_prims_harness_{b}") for b in BUILDS}
-    procs = [subprocess.Popen([hipcc()] + PRODUCT_FLAGS + (NOBITOP3_FLAGS if b == "nobitop3" else []) + [HARNESS_SRC, "-o", exes[b]]) for b in BUILDS]
-    rcs = [p.wait() for p in procs]
-    assert rcs == [0, 0], f"hipcc failed: {rcs}"
-    return exes
-
-
-def harness_constants(exe):
-    out = subprocess.run([exe, "--constants"], capture_output=True, text=True, timeout=60, check=True).stdout
-    return {k: int(v) for k, v in (line.split() for line in out.splitlines())}
+    with ThreadPoolExecutor(len(BUILDS)) as pool:
+        exes = pool.map(lambda b: H.build(HARNESS, out_dir, PRODUCT_FLAGS + (NOBITOP3_FLAGS if b == "nobitop3" else []), f"gpu_prims_harness_{b}"), BUILDS)
+        return dict(zip(BUILDS, exes))
 
 
 def write_case(path, section, n, payload, p3=0, p4=0):
@@ -62,11 +53,8 @@ def read_result(path, section, host, n):
 
 
 def run_harness(exe, section, case_path, result_path, host=False, timeout=120):
-    """One section in a fresh child process.  Raises on a non-zero or signalled exit and on a timeout: the caller starts nothing more on the device."""
-    cmd = [exe] + (["--host"] if host else []) + [str(SECTIONS[section]), case_path, result_path]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
-    if p.returncode != 0:
-        raise RuntimeError(f"gpu_prims_harness {'--host ' if host else ''}{section}: exit {p.returncode}: {p.stderr[-2000:]}")
+    """One section in a fresh child process (harness.run)."""
+    H.run(exe, (["--host"] if host else []) + [SECTIONS[section], case_path, result_path], timeout)
 
 
 def u32(a):

@@ -3,10 +3,11 @@ deterministic generator of synthetic per-UE state that no simulation leaves behi
 result file, one child process per launch).  Shared by tests/test_reduce_cases_cpu.py, tests/test_gpu_reduce_synthetic.py, tests/test_gpu_dist.py
 (bincount_dist) and tests/tools/timeline_ref.py (timeline_add).  No GPU and no package import here: what needs the package takes it as an argument."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
+
+import harness as H
+from harness import constants as harness_constants  # noqa: F401  (the tests of the families built on this module reach it through here)
 
 INT_MIN, INT_MAX = -2**31, 2**31 - 1
 TIMER, ACTIVE, TXTIME, PTC, FLAG = 1, 2, 3, 11, 14  # columns of the 16-field per-UE log
@@ -18,7 +19,7 @@ DIST_FIELDS = ("trials", "ues", "success", "delay_overflow", "delay_sum", "ptc_s
 TL_SERIES = ("arrivals", "success", "sojourn_sum", "timer_sum", "done")
 TL_FIELDS = ("trials", "ues", "arrived", "success", "restarted", "arrival_overflow", "done_overflow", "sojourn_sum", "timer_sum", "done_max")
 MAGIC = 0x52445543
-HARNESS_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpu_reduce_harness.hip")
+HARNESS = "gpu_reduce_harness.hip"
 PATTERN = 0x7FFF7FFF  # fills what no reduction may read: as a count or a time it would show in every output
 
 
@@ -463,38 +464,19 @@ def timeline_cases(pkg):
 
 # ---- the harness --------------------------------------------------------------------------------------------------------------------------------------
 
-def hipcc():
-    return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
 def build_harness(out_dir):
-    """Compiles tests/tools/gpu_reduce_harness.hip (host program + both kernels for gfx950) into out_dir; returns the executable's path."""
-    exe = os.path.join(str(out_dir), "gpu_reduce_harness")
-    subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", HARNESS_SRC, "-o", exe])
-    return exe
-
-
-def harness_constants(exe):
-    out = subprocess.run([exe, "--constants"], capture_output=True, text=True, timeout=60, check=True).stdout
-    return {k: int(v) for k, v in (line.split() for line in out.splitlines())}
+    return H.build(HARNESS, out_dir)
 
 
 def write_case(case, path):
     kind = 0 if case.kind == "dist" else 1
     head = np.zeros(16, dtype=np.int32)
     head[:6] = [MAGIC, kind, len(case.jobs), case.bins, case.width, case.ngroups]
+    if kind == 1:
+        return H.write_job_case(path, head, *H.log_jobs(case.jobs, lambda k, j: [j.group]))
     rows = np.zeros((len(case.jobs), 8), dtype=np.int32)
-    parts = [head, rows]
-    for k, j in enumerate(case.jobs):
-        if kind == 0:
-            rows[k, :3] = [j.nue, j.group, j.form]
-            parts += [j.timers, j.data.reshape(-1)]
-        else:
-            rows[k, :5] = [j.nue, j.group, 0, j.access_time, len(j.sched)]
-            parts += [j.logs.reshape(-1), j.sched]
-    with open(path, "wb") as f:
-        for p in parts:
-            f.write(np.ascontiguousarray(p, dtype="<i4").tobytes())
+    rows[:, :3] = [[j.nue, j.group, j.form] for j in case.jobs]
+    H.write_job_case(path, head, rows, [a for j in case.jobs for a in (j.timers, j.data.reshape(-1))])
 
 
 def read_result(case, path, scheme):
@@ -531,9 +513,7 @@ def read_result(case, path, scheme):
 
 
 def run_harness(exe, case, case_path, scheme, out_dir, timeout=120):
-    """One launch in a fresh child process.  Raises on a non-zero or signalled exit and on a timeout: the caller starts nothing more on the device."""
+    """One launch in a fresh child process (harness.run)."""
     res = os.path.join(str(out_dir), f"{case.name}.s{scheme}.result")
-    p = subprocess.run([exe, case_path, res, str(scheme)], capture_output=True, text=True, timeout=timeout)
-    if p.returncode != 0:
-        raise RuntimeError(f"gpu_reduce_harness {case.name} scheme {scheme}: exit {p.returncode}: {p.stderr[-2000:]}")
+    H.run(exe, [case_path, res, scheme], timeout)
     return read_result(case, res, scheme)

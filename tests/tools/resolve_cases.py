@@ -6,16 +6,15 @@ tests/tools/gpu_resolve_harness.hip (case file, result file, one child process p
 tests/test_gpu_resolve_synthetic.py.  No GPU here; the constants of the product's headers come from `gpu_resolve_harness --constants`."""
 import ctypes
 import math
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 
+import harness as H
+
 INT_MAX = 2**31 - 1
 MAGIC = 0x52534C56
-HARNESS_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpu_resolve_harness.hip")
+HARNESS = "gpu_resolve_harness.hip"
 D1_LOW, D1_HIGH, D_MAX = 644245094, 644245095, 2147483646  # the largest d1 with d1 / RAND_MAX < 0.3, the smallest without, the largest rand()
 FILLER = 0x2AAAAAAA  # what lies in a stream in front of and behind a case's draws (even: as a d2 it picks the weaker UE; as a d1, < 0.3 does not hold)
 
@@ -444,21 +443,13 @@ RESET_CASE_NAMES = _reset_names()
 
 # ---- the harness ------------------------------------------------------------------------------------------------------------------------------------------
 
-def hipcc():
-    return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
 def build_harness(out_dir):
     """Compiles tests/tools/gpu_resolve_harness.hip (host program + the three wrapper kernels for gfx950, the product's -ffp-contract=off) into out_dir."""
-    exe = os.path.join(str(out_dir), "gpu_resolve_harness")
-    subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", HARNESS_SRC, "-o", exe])
-    return exe
+    return H.build(HARNESS, out_dir, ["-ffp-contract=off"])
 
 
 def harness_constants(exe):
-    out = subprocess.run([exe, "--constants"], capture_output=True, text=True, timeout=60, check=True).stdout
-    c = dict(line.split() for line in out.splitlines())
-    return {k: float.fromhex(v) if k == "ACT_GAIN_ORDER_BAND" else int(v) for k, v in c.items()}
+    return H.constants(exe, lambda v: float.fromhex(v) if "x" in v else int(v))  # (ACT_GAIN_ORDER_BAND is a hexadecimal float)
 
 
 def _header(mode, ncases):
@@ -570,7 +561,5 @@ def read_mode3(path, cases):
 
 
 def run_harness(exe, case_path, result_path, devact, timeout=120):
-    """One launch in a fresh child process.  Raises on a non-zero or signalled exit and on a timeout: the caller starts nothing more on the device."""
-    p = subprocess.run([exe, case_path, result_path, str(devact)], capture_output=True, text=True, timeout=timeout)
-    if p.returncode != 0:
-        raise RuntimeError(f"gpu_resolve_harness {os.path.basename(case_path)} devact {devact}: exit {p.returncode}: {p.stderr[-2000:]}")
+    """One launch in a fresh child process (harness.run)."""
+    H.run(exe, [case_path, result_path, devact], timeout)

@@ -2,10 +2,10 @@
 package-free reference shape for tests/tools/sojourn_ref.py, and the glue around tests/tools/gpu_sojourn_harness.hip (case file, result file, one child
 process per launch).  Shared by tests/test_sojourn_cases_cpu.py and tests/test_gpu_sojourn_synthetic.py.  No GPU and no package import here."""
 import os
-import subprocess
 
 import numpy as np
 
+import harness as H
 import reduce_cases as R
 import sojourn_ref as S
 
@@ -13,7 +13,7 @@ TILE, MAX_SOJOURN = R.TILE, R.MAX_SOJOURN
 WINDOW_WORDS = 28672  # SJ_WINDOW_WORDS (prach_device.h); tests/test_sojourn_cases_cpu.py holds it and the rest against `gpu_sojourn_harness --constants`
 CONSTANTS = dict(TL_TILE=8192, TL_THREADS=256, TL_MAX_SOJOURN=60006, SJ_WINDOW_WORDS=WINDOW_WORDS, SJ_SCHED_CAP=2048, SJ_SCALARS=8)
 FIELDS = ("trials", "ues", "arrived", "success", "restarted", "arrival_overflow", "delay_overflow", "sojourn_sum", "sojourn_max")
-HARNESS_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpu_sojourn_harness.hip")
+HARNESS = "gpu_sojourn_harness.hip"
 
 
 class RefSojourn:
@@ -151,23 +151,13 @@ def cases(pkg):
 # ---- the harness --------------------------------------------------------------------------------------------------------------------------------------
 
 def build_harness(out_dir):
-    """Compiles tests/tools/gpu_sojourn_harness.hip (host program + the kernel for gfx950) into out_dir; returns the executable's path."""
-    exe = os.path.join(str(out_dir), "gpu_sojourn_harness")
-    subprocess.check_call([R.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", HARNESS_SRC, "-o", exe])
-    return exe
+    return H.build(HARNESS, out_dir)
 
 
 def write_case(case, path):
     head = np.zeros(16, dtype=np.int32)
     head[:8] = [R.MAGIC, 2, len(case.jobs), *case.spec, case.ngroups]
-    rows = np.zeros((len(case.jobs), 8), dtype=np.int32)
-    parts = [head, rows]
-    for k, j in enumerate(case.jobs):
-        rows[k, :5] = [j.nue, j.group, 0, j.access_time, len(j.sched)]
-        parts += [j.logs.reshape(-1), j.sched]
-    with open(path, "wb") as f:
-        for p in parts:
-            f.write(np.ascontiguousarray(p, dtype="<i4").tobytes())
+    H.write_job_case(path, head, *H.log_jobs(case.jobs, lambda k, j: [j.group]))
 
 
 def read_result(case, path, scheme):
@@ -194,9 +184,7 @@ def read_result(case, path, scheme):
 
 
 def run_harness(exe, case, case_path, scheme, out_dir, timeout=120):
-    """One launch in a fresh child process.  Raises on a non-zero or signalled exit and on a timeout: the caller starts nothing more on the device."""
+    """One launch in a fresh child process (harness.run)."""
     res = os.path.join(str(out_dir), f"{case.name}.s{scheme}.result")
-    p = subprocess.run([exe, case_path, res, str(scheme)], capture_output=True, text=True, timeout=timeout)
-    if p.returncode != 0:
-        raise RuntimeError(f"gpu_sojourn_harness {case.name} scheme {scheme}: exit {p.returncode}: {p.stderr[-2000:]}")
+    H.run(exe, [case_path, res, scheme], timeout)
     return read_result(case, res, scheme)

@@ -7,17 +7,18 @@ tests/test_gpu_stream_act_synthetic.py and tests/golden/make_act_boundaries.py. 
 import ctypes as C
 import json
 import os
-import shutil
-import subprocess
 
 import numpy as np
+
+import harness
+from harness import constants as harness_constants  # noqa: F401
 
 MAGIC = 0x53414354
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-HARNESS_SRC = os.path.join(HERE, "gpu_stream_act_harness.hip")
+HARNESS = "gpu_stream_act_harness.hip"
 BOUNDARIES_JSON = os.path.join(ROOT, "tests", "golden", "act_boundaries.json")
-PRODUCT_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"]
+PRODUCT_FLAGS = ["-ffp-contract=off"]  # on top of harness.FLAGS
 FILL_WORD = 0xA5A5A5A5
 DMAX = 2**31 - 1
 PAD_DRAW = DMAX // 3      # what draw() returns past the budget (noma_glibc_trial_kernel's convention)
@@ -30,27 +31,13 @@ ITER_CAP = 4096           # the loop caps of noma_active_ue: `it >= 4096` after 
 
 # ---- the harness ------------------------------------------------------------------------------------------------------------------------------------------
 
-def hipcc():
-    return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
-def build_harness(out_dir, src=HARNESS_SRC):
-    exe = os.path.join(str(out_dir), "gpu_stream_act_harness")
-    rc = subprocess.run([hipcc()] + PRODUCT_FLAGS + [src, "-o", exe]).returncode
-    assert rc == 0, f"hipcc failed: {rc}"
-    return exe
-
-
-def harness_constants(exe):
-    out = subprocess.run([exe, "--constants"], capture_output=True, text=True, timeout=60, check=True).stdout
-    return {k: int(v) for k, v in (line.split() for line in out.splitlines())}
+def build_harness(out_dir):
+    return harness.build(HARNESS, out_dir, PRODUCT_FLAGS)
 
 
 def run_harness(exe, case_path, result_path, timeout=120):
-    """One launch in a fresh child process.  Raises on a non-zero or signalled exit and on a timeout: the caller starts nothing more on the device."""
-    p = subprocess.run([exe, case_path, result_path], capture_output=True, text=True, timeout=timeout)
-    if p.returncode != 0:
-        raise RuntimeError(f"gpu_stream_act_harness {os.path.basename(case_path)}: exit {p.returncode}: {p.stderr[-2000:]}")
+    """One launch in a fresh child process (harness.run)."""
+    harness.run(exe, [case_path, result_path], timeout)
 
 
 # ---- the rand() stream ------------------------------------------------------------------------------------------------------------------------------------

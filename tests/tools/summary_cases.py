@@ -2,10 +2,10 @@
 kernel's raw row restated in numpy, and the glue around tests/tools/gpu_summary_harness.hip (case file, result file, one child process per launch).
 Shared by tests/test_summary_cases_cpu.py and tests/test_gpu_summary_synthetic.py.  No GPU and no package import here."""
 import os
-import subprocess
 
 import numpy as np
 
+import harness as H
 import reduce_cases as R
 import summary_ref as SR
 
@@ -14,7 +14,7 @@ SCHED_CAP = 12288      # SM_SCHED_CAP (prach_summary.hip): a longer schedule is 
 WORDS = 36             # SM_WORDS
 CONSTANTS = dict(SM_WORDS=WORDS, SM_MAX_VALUE=MAX_VALUE, SM_SCHED_CAP=SCHED_CAP, SM_COARSE=1024, SM_FINE=64, PRACH_SUMMARY_MAX_Q=8, TL_MAX_SOJOURN=60006)
 THREADS = (512, 1024)  # the two workgroup shapes of the kernel
-HARNESS_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpu_summary_harness.hip")
+HARNESS = "gpu_summary_harness.hip"
 PTC = SR.PTC
 
 
@@ -168,24 +168,14 @@ def cases(pkg):
 # ---- the harness --------------------------------------------------------------------------------------------------------------------------------------
 
 def build_harness(out_dir):
-    """Compiles tests/tools/gpu_summary_harness.hip (host program + the kernel for gfx950) into out_dir; returns the executable's path."""
-    exe = os.path.join(str(out_dir), "gpu_summary_harness")
-    subprocess.check_call([R.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", HARNESS_SRC, "-o", exe])
-    return exe
+    return H.build(HARNESS, out_dir)
 
 
 def write_case(case, path):
     head = np.zeros(16, dtype=np.int32)
     head[:4] = [R.MAGIC, 3, len(case.jobs), len(case.levels)]
     head[4:4 + len(case.levels)] = case.levels
-    rows = np.zeros((len(case.jobs), 8), dtype=np.int32)
-    parts = [head, rows]
-    for k, j in enumerate(case.jobs):
-        rows[k, :5] = [j.nue, j.group, 0, j.access_time, len(j.sched)]
-        parts += [j.logs.reshape(-1), j.sched]
-    with open(path, "wb") as f:
-        for p in parts:
-            f.write(np.ascontiguousarray(p, dtype="<i4").tobytes())
+    H.write_job_case(path, head, *H.log_jobs(case.jobs, lambda k, j: [j.group]))
 
 
 def read_result(case, path, threads):
@@ -198,9 +188,7 @@ def read_result(case, path, threads):
 
 
 def run_harness(exe, case, case_path, threads, out_dir, timeout=120):
-    """One launch in a fresh child process.  Raises on a non-zero or signalled exit and on a timeout: the caller starts nothing more on the device."""
+    """One launch in a fresh child process (harness.run)."""
     res = os.path.join(str(out_dir), f"{case.name}.t{threads}.result")
-    p = subprocess.run([exe, case_path, res, str(threads)], capture_output=True, text=True, timeout=timeout)
-    if p.returncode != 0:
-        raise RuntimeError(f"gpu_summary_harness {case.name} threads {threads}: exit {p.returncode}: {p.stderr[-2000:]}")
+    H.run(exe, [case_path, res, threads], timeout)
     return read_result(case, res, threads)

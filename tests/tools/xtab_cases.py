@@ -2,10 +2,10 @@
 tests/tools/xtab_ref.py, and the glue around tests/tools/gpu_xtab_harness.hip (case file, result file, one child process per launch).  Shared by
 tests/test_xtab_cases_cpu.py and tests/test_gpu_xtab_synthetic.py.  No GPU and no package import here."""
 import os
-import subprocess
 
 import numpy as np
 
+import harness as H
 import reduce_cases as R
 import xtab_ref as X
 
@@ -14,7 +14,7 @@ WINDOW_WORDS = 28672  # XT_WINDOW_WORDS (prach_device.h); tests/test_xtab_cases_
 CONSTANTS = dict(TL_TILE=8192, TL_THREADS=256, XT_WINDOW_WORDS=WINDOW_WORDS, XT_COPY_WORDS=4096, XT_SCHED_CAP=2048, XT_SCALARS=16)
 SCALARS = 16
 FIELDS = X.FIELDS
-HARNESS_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpu_xtab_harness.hip")
+HARNESS = "gpu_xtab_harness.hip"
 ALL = X.SERVED | X.UNSERVED | X.IDLE
 SIZES = (1, 63, 64, 65, TILE - 1, TILE, TILE + 1, 2 * TILE + 1)  # nUE 1, 63 / 64 / 65, 8191 / 8192 / 8193 and 16 385
 
@@ -170,23 +170,13 @@ def cases(pkg):
 # ---- the harness --------------------------------------------------------------------------------------------------------------------------------------
 
 def build_harness(out_dir):
-    """Compiles tests/tools/gpu_xtab_harness.hip (host program + the kernel for gfx950) into out_dir; returns the executable's path."""
-    exe = os.path.join(str(out_dir), "gpu_xtab_harness")
-    subprocess.check_call([R.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", HARNESS_SRC, "-o", exe])
-    return exe
+    return H.build(HARNESS, out_dir)
 
 
 def write_case(case, path):
     head = np.zeros(16, dtype=np.int32)
     head[:11] = [R.MAGIC, 3, len(case.jobs), case.spec[2], *case.spec[0], *case.spec[1], case.ngroups]
-    rows = np.zeros((len(case.jobs), 8), dtype=np.int32)
-    parts = [head, rows]
-    for k, j in enumerate(case.jobs):
-        rows[k, :6] = [j.nue, j.group, 0, j.access_time, len(j.sched), j.E]
-        parts += [j.logs.reshape(-1), j.sched]
-    with open(path, "wb") as f:
-        for p in parts:
-            f.write(np.ascontiguousarray(p, dtype="<i4").tobytes())
+    H.write_job_case(path, head, *H.log_jobs(case.jobs, lambda k, j: [j.group, j.E]))
 
 
 def read_result(case, path, scheme):
@@ -213,10 +203,7 @@ def read_result(case, path, scheme):
 
 
 def run_harness(exe, case, case_path, scheme, out_dir, timeout=120):
-    """One launch in a fresh child process under `timeout -k 10`.  Raises on a non-zero or signalled exit and on a timeout: the caller starts nothing more on
-    the device."""
+    """One launch in a fresh child process (harness.run)."""
     res = os.path.join(str(out_dir), f"{case.name}.s{scheme}.result")
-    p = subprocess.run(["timeout", "-k", "10", str(timeout), exe, case_path, res, str(scheme)], capture_output=True, text=True, timeout=timeout + 30)
-    if p.returncode != 0:
-        raise RuntimeError(f"gpu_xtab_harness {case.name} scheme {scheme}: exit {p.returncode}: {p.stderr[-2000:]}")
+    H.run(exe, [case_path, res, scheme], timeout)
     return read_result(case, res, scheme)
