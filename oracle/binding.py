@@ -121,6 +121,36 @@ def run_trial(cfg: OracleCfg, rng: Rng, want_ues=True):
     return res, ues
 
 
+GCEN_SUB = 10  # ORACLE_GCEN_SUB
+
+
+def run_trial_grant_census(cfg: OracleCfg, rng: Rng, want_ues=True):
+    """run_trial with the oracle's grant census on (prach_oracle.c: oracle_set_grant_census; off again afterwards).  Returns (res, ues, census): census is a
+    dict of numpy arrays, one entry per subframe with a singleton call — t, ns, left (the grants left at the head of the subframe), off (of its first caller
+    in the caller arrays), sleft[:, 6] (the six sector budgets left) — and per singleton caller in scan order idx, granted, sector.  The census is one
+    process-wide setting: not to be used while another thread runs a trial."""
+    import numpy as np
+    L = lib()
+    L.oracle_set_grant_census.restype = None
+    L.oracle_set_grant_census.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    T = cfg.max_steps if 0 < cfg.max_steps < 60000 else (60000 if cfg.uniform else 10000)
+    sub = np.zeros(T * GCEN_SUB, dtype=np.int32)
+    used = np.zeros(3, dtype=np.int32)
+    call = np.zeros(2 * max(1 << 20, 64 * cfg.nUE), dtype=np.int32)  # (untouched pages cost nothing)
+    L.oracle_set_grant_census(sub.ctypes.data, len(sub), call.ctypes.data, len(call), used.ctypes.data)
+    try:
+        res, ues = run_trial(cfg, rng, want_ues)
+    finally:
+        L.oracle_set_grant_census(None, 0, None, 0, None)
+    if used[2]:
+        raise RuntimeError(f"grant census: {used[2]} subframes dropped")
+    s = sub[:int(used[0]) * GCEN_SUB].reshape(-1, GCEN_SUB)
+    c = call[:2 * int(used[1])].reshape(-1, 2)
+    census = dict(t=s[:, 0].copy(), ns=s[:, 1].copy(), left=s[:, 2].copy(), off=s[:, 3].copy(), sleft=s[:, 4:10].copy(),
+                  idx=c[:, 0].copy(), granted=(c[:, 1] & 1).astype(bool), sector=c[:, 1] >> 1)
+    return res, ues, census
+
+
 def format_logs(ues, nUE) -> bytes:
     n = lib().oracle_format_logs(ues, nUE, None, 0)
     buf = C.create_string_buffer(n + 1)

@@ -72,6 +72,45 @@ static int census_n, census_t;
 void oracle_set_census(int32_t *redraws, int32_t *singles, int32_t *calls, int n) { census_redraws = redraws; census_singles = singles; census_calls = calls; census_n = n; census_t = 0; }
 #define CENSUS(arr) do { if (arr && census_t < census_n) arr[census_t]++; } while (0)
 
+/* Optional grant census (tests/tools/grant_cases.py), off by default: who is granted in a subframe.  Per subframe with a singleton call, ORACLE_GCEN_SUB words
+ * in `sub`: the subframe, ns (its singleton calls), the grants left at its head max(0, nGrantUL - 1 - grantCheck) (Beta.c:336-347: a caller adds 1 FIRST and is
+ * granted while the count stays below nGrantUL), the offset of its first caller in `call`, and the six per-sector budgets left at its head (WithNOMA:626-637;
+ * the same figure six times without sector_grants).  Per singleton caller, in scan order, two words in `call`: the UE index, and granted | sector << 1.
+ * used[0] subframes recorded, used[1] callers recorded, used[2] subframes dropped for want of room.  It reads the trial and writes only its own arrays:
+ * no draw, no counter and no UE field depends on it.  One process-wide setting, as the census above. */
+static int32_t *gcen_sub, *gcen_call, *gcen_used;
+static int gcen_sub_cap, gcen_call_cap, gcen_start, gcen_full;
+static int32_t gcen_head[ORACLE_GCEN_SUB];
+void oracle_set_grant_census(int32_t *sub, int sub_cap, int32_t *call, int call_cap, int32_t *used) {
+    gcen_sub = (sub && call && used) ? sub : NULL;
+    gcen_call = call; gcen_used = used; gcen_sub_cap = sub_cap; gcen_call_cap = call_cap;
+    if (gcen_sub) used[0] = used[1] = used[2] = 0;
+}
+static void gcen_begin(int time, int nGrantUL, int grantCheck, const int *sectorGrants, int per_sector) {
+    gcen_head[0] = time;
+    gcen_head[1] = 0;
+    gcen_head[2] = nGrantUL - 1 - grantCheck > 0 ? nGrantUL - 1 - grantCheck : 0;
+    gcen_head[3] = gcen_start = gcen_used[1];
+    for (int s = 0; s < 6; s++) {
+        const int left = nGrantUL - 1 - (per_sector ? sectorGrants[s] : grantCheck);
+        gcen_head[4 + s] = left > 0 ? left : 0;
+    }
+    gcen_full = 0;
+}
+static void gcen_caller(int idx, int sector, int granted) {
+    gcen_head[1]++;
+    if (gcen_full || gcen_used[1] + 1 > gcen_call_cap / 2) { gcen_full = 1; return; }
+    gcen_call[2 * gcen_used[1]] = idx;
+    gcen_call[2 * gcen_used[1] + 1] = (granted ? 1 : 0) | sector << 1;
+    gcen_used[1]++;
+}
+static void gcen_end(void) {
+    if (gcen_head[1] == 0) return;
+    if (gcen_full || (gcen_used[0] + 1) * ORACLE_GCEN_SUB > gcen_sub_cap) { gcen_used[1] = gcen_start; gcen_used[2]++; return; }
+    memcpy(gcen_sub + gcen_used[0] * ORACLE_GCEN_SUB, gcen_head, sizeof(gcen_head));
+    gcen_used[0]++;
+}
+
 static int draw(ctx_t *c, ue_t *u) {
     c->rng->consumed++;
     if (c->rng->mode == ORACLE_RNG_GLIBC) return glibc_rand(&c->rng->g);
@@ -219,6 +258,7 @@ static void preambleCollision(ctx_t *c, int self, int time, int *grantCheck) {
         } else {
             user->u.txTime++;
         }
+        if (gcen_sub) gcen_caller(self, user->sector, user->u.active == 2);
     } else {
         if (k->variant == ORACLE_VARIANT_WITHNOMA_C) { /* WithNOMA:650-652 */
             c->collisionPreambles += check;
@@ -326,6 +366,7 @@ int oracle_run_trial(const oracle_cfg *cfg, oracle_rng *rng, oracle_result *res,
             grantCheck = 0;
             for (int s = 0; s < 6; s++) sectorGrants[s] = 0;
         }
+        if (gcen_sub) gcen_begin(time, cfg->nGrantUL, grantCheck, sectorGrants, per_sector);
         if (activeCheck >= nUE) activeCheck = nUE;
         if (time % accessTime == 0 && activeCheck != nUE) { /* Beta.c:121-147 */
             if (cfg->uniform) {
@@ -393,6 +434,7 @@ int oracle_run_trial(const oracle_cfg *cfg, oracle_rng *rng, oracle_result *res,
                 if (cfg->scan_mode == ORACLE_SCAN_SETS && is_member(user, time)) set_add(&c, i);
             }
         }
+        if (gcen_sub) gcen_end();
         nSuccessUE = 0; /* successUEs, Beta.c:421-429 */
         for (int i = 0; i < nUE; i++)
             if (c.UE[i].u.msg4Flag == 1) nSuccessUE++;

@@ -2,6 +2,8 @@
 stopped trial judged by an oracle run cut at the same subframe.
 usage: gpu_cut_sweep.py [ROW …]                  the rows named (default: all of cut_cases.CUT_ROWS)
        gpu_cut_sweep.py --scan ROW BASE LO HI    one base of one row at every cut LO .. HI, whatever the generator chose for it
+       gpu_cut_sweep.py --grant [ROW …]          the grant sweep (tests/tools/grant_cases.py): the rows of grant_cases.GRANT_ROWS over its bases, cut behind the
+                                                 chosen subframes; a row runs once per cluster size its bases need, each with the pin predicted for it
 
 One engine per run.  The oracle's prefix runs come first, on a pool of at most 16 threads, distinct trials shared between the rows.  Per row the engine
 options are set and the row's base x cut trials run in calls of cut_cases.trials_per_call trials; after EVERY call prach_timing must show the row's
@@ -23,6 +25,7 @@ import numpy as np
 
 import gpu_kernel_matrix as gkm  # (the comparison, the pin test and the package of the kernel matrix's runner)
 import cut_cases as CC
+from trace_ref import lib_overrides  # (the oracle's sector_grants is the library's PRACH_FLAG_SECTOR_GRANTS)
 
 pkg, ob = gkm.pkg, gkm.ob
 assert set(gkm.DEFAULTS.items()) <= set(CC.OPT_DEFAULTS.items())
@@ -60,7 +63,7 @@ def run_row(eng, row, trials, ref, pipeline):
     bad, digest, calls, kms = {}, 0, 0, 0.0
     for lo in range(0, len(trials), per):
         grp = trials[lo:lo + per]
-        cfgs = [pkg.make_cfg(n, variant=v, rng_mode=r, seed=s, **kw) for _, _, _, (_, v, n, kw, r, s) in grp]
+        cfgs = [pkg.make_cfg(n, variant=v, rng_mode=r, seed=s, **lib_overrides(kw)) for _, _, _, (_, v, n, kw, r, s) in grp]
         res, logs = eng.run_trials(cfgs, want_logs=True)
         tm = eng.timing()
         calls += 1
@@ -71,7 +74,7 @@ def run_row(eng, row, trials, ref, pipeline):
             left = {}
             for name, _, c, t in grp:  # (which of them left the kernel: each alone, the smallest cut per base reported)
                 if len(grp) > 1:
-                    eng.run_trials([pkg.make_cfg(t[2], variant=t[1], rng_mode=t[4], seed=t[5], **t[3])])
+                    eng.run_trials([pkg.make_cfg(t[2], variant=t[1], rng_mode=t[4], seed=t[5], **lib_overrides(t[3]))])
                 if len(grp) == 1 or gkm.pin_failure(row, eng.timing()):
                     bad[(name, c)] = f"left the row's kernel: {gkm.pin_failure(row, eng.timing())}"
                     left.setdefault(name, []).append(c)
@@ -105,6 +108,19 @@ def main(argv):
         row = CC.ROW[rname]
         base = dict(CC.bases_of(row))[bname]
         plan = [(row, [(bname, base, c, CC.with_cut(base, c)) for c in range(lo, hi + 1)])]
+    elif argv[:1] == ["--grant"]:
+        import grant_cases as GC
+        unknown = [n for n in argv[1:] if n not in GC.GROW]
+        assert not unknown, f"no grant row named {unknown}"
+        plan = []
+        for r in GC.GRANT_ROWS:
+            if argv[1:] and r["name"] not in argv[1:]:
+                continue
+            per = {}  # (the row as sized for its trials' cluster size -> its trials)
+            for srow, tag, base, c, t in GC.trials_of(r):
+                g = srow["pin"]["cluster_size"]
+                per.setdefault(g, (dict(srow, label=f"[cluster={g}]" if g > 1 else ""), []))[1].append((tag, base, c, t))
+            plan += list(per.values())
     else:
         unknown = [n for n in argv if n not in CC.ROW]
         assert not unknown, f"no row named {unknown}"
@@ -115,7 +131,7 @@ def main(argv):
     total = nbad = 0
     for row, trials in plan:
         for pipeline in row.get("pipeline", (None,)):
-            tag = "" if pipeline is None else f"[pipeline={pipeline}]"
+            tag = row.get("label", "") + ("" if pipeline is None else f"[pipeline={pipeline}]")
             t1 = time.time()
             try:
                 bad, digest, calls, kms = run_row(eng, row, trials, ref, pipeline)
