@@ -55,7 +55,7 @@ class PrachTiming(C.Structure):
                 ("launches", C.c_int32), ("workgroups", C.c_int32), ("updates", C.c_uint64),
                 ("cluster_size", C.c_int32), ("resident_limit", C.c_int32), ("fallback_trials", C.c_int32), ("spin_timeouts", C.c_int32),
                 ("rec_mode", C.c_int32), ("xcd_packed", C.c_int32), ("group_visits", C.c_uint64), ("event_ues", C.c_uint64),
-                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("noma_summary_ms", C.c_double), ("noma_pick_ms", C.c_double), ("noma_census_ms", C.c_double), ("noma_columns_ms", C.c_double), ("columns_ms", C.c_double), ("pick_ms", C.c_double), ("xtab_ms", C.c_double), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
+                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("noma_trace_ms", C.c_double), ("noma_summary_ms", C.c_double), ("noma_pick_ms", C.c_double), ("noma_census_ms", C.c_double), ("noma_columns_ms", C.c_double), ("columns_ms", C.c_double), ("pick_ms", C.c_double), ("xtab_ms", C.c_double), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
                 ("sojourn_ms", C.c_double)]
 
 
@@ -647,6 +647,79 @@ class NomaCensus(_Reduction):
         return int(lib().prach_xtab_quantile(C.byref(sp), self._rows(g)[0], int(row), float(q)))
 
 
+NOMA_TRACE_SERIES = ("tx", "used", "singles", "granted", "pairs", "pair_one")
+NOMA_TRACE_FIELDS = ("trials", "slots", "tx", "used", "singles", "granted", "pairs", "pair_one", "overflow_tx", "tx_max")
+
+
+class PrachNomaTraceSpec(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("bins", "bin_ms", "ngroups", "reserved")]
+
+
+class PrachNomaTrace(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in NOMA_TRACE_FIELDS[:-1]] + [("tx_max", C.c_int64)]
+
+
+class NomaTrace(_Reduction):
+    """NOMA.c's channel traces of ``ngroups`` trial groups (include/prach.h, prach_noma_trace): ``series`` [6, ngroups, 6 sectors, bins] as numpy uint64, in the
+    order of NOMA_TRACE_SERIES (bin b covers the subframes [b * bin_ms, (b + 1) * bin_ms); an access slot counts where its subframe falls) — tx: preambles
+    sent, used: (sector, preamble) bins with a transmitter, singles: bins with exactly one, granted: UEs whose msg2 was set, pairs: power-domain pairs that
+    received a grant, pair_one: the pairs of which one UE decoded — and ``scalars[field]``, one int64 array of length ngroups per field of NOMA_TRACE_FIELDS.
+    There is no from_logs form: a per-UE log does not hold what happened per slot."""
+    _FIELDS, _STRUCT, _MERGE, _PARAMS = NOMA_TRACE_FIELDS, PrachNomaTrace, "prach_noma_trace_merge", ("bins", "bin_ms")
+
+    def __init__(self, ngroups, bins, bin_ms=5):
+        import numpy as np
+        self.bins, self.bin_ms, self.ngroups = int(bins), int(bin_ms), int(ngroups)
+        self.series = np.zeros((6, self.ngroups, 6, self.bins), dtype=np.uint64)
+        self.scalars = {f: np.zeros(self.ngroups, dtype=np.int64) for f in NOMA_TRACE_FIELDS}
+        self.scalars["tx_max"][:] = -1
+
+    def spec(self):
+        return PrachNomaTraceSpec(self.bins, self.bin_ms, self.ngroups, 0)
+
+    def _arrays(self):
+        return [self.series[q] for q in range(6)]
+
+    def _scalar(self, f):
+        return self.scalars[f]
+
+    def _series(self, g=None):
+        """The six series — of group g, or of all groups — as the uint64_t *[6] the C side takes."""
+        return (C.POINTER(C.c_uint64) * 6)(*[(self.series[q] if g is None else self.series[q, g]).ctypes.data_as(C.POINTER(C.c_uint64)) for q in range(6)])
+
+    def _cargs(self, g):
+        return (self._series(g),)
+
+    def merge(self, other):
+        """Adds every group of ``other`` (same bins, bin_ms and ngroups) to the same group of this one (prach_noma_trace_merge).  Returns self."""
+        if (self.bins, self.bin_ms, self.ngroups) != (other.bins, other.bin_ms, other.ngroups):
+            raise ValueError("traces of different shapes do not merge")
+        for g in range(self.ngroups):
+            self.merge_group(g, other, g)
+        return self
+
+    def named(self, name, group):
+        """Series ``name`` of one group, summed over the sectors: [bins] float64."""
+        import numpy as np
+        return self.series[NOMA_TRACE_SERIES.index(name), group].sum(axis=0).astype(np.float64)
+
+    def collision_ratio(self, group):
+        """(used - singles) / used per bin of one group, all sectors, as float64: the share of the used (sector, preamble) bins that collided (NaN where none
+        was used)."""
+        import numpy as np
+        u, s1 = self.named("used", group), self.named("singles", group)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(u > 0, (u - s1) / u, np.nan)
+
+    def noma_share(self, group):
+        """(2 * pairs - pair_one) / granted per bin of one group, all sectors, as float64: the share of the granted UEs that were granted through a power-domain
+        pair (NaN where nobody was granted)."""
+        import numpy as np
+        g, p, o = self.named("granted", group), self.named("pairs", group), self.named("pair_one", group)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(g > 0, (2 * p - o) / g, np.nan)
+
+
 NOMA_SUMMARY_MAX_FIELDS = 4
 NOMA_SUMMARY_FIXED_METRICS = ("served_ratio", "dropped_ratio", "pending_ratio", "restart_ratio")
 
@@ -933,6 +1006,14 @@ def lib():
         L.prach_results_csv_accumulate.argtypes = [C.POINTER(C.c_double), C.c_char_p]
         L.prach_results_csv_row.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_char_p, C.c_size_t]
         L.prach_results_csv_row.restype = C.c_size_t
+        u64p6 = C.POINTER(C.POINTER(C.c_uint64))
+        L.prach_run_trials_noma_trace.argtypes = [C.c_void_p, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachNomaTraceSpec),
+                                                  C.POINTER(C.c_int32), C.POINTER(PrachNomaTrace), u64p6]
+        L.prach_noma_trace_merge.argtypes = [C.POINTER(PrachNomaTraceSpec), C.POINTER(PrachNomaTrace), u64p6, C.POINTER(PrachNomaTrace), u64p6]
+        L.prach_noma_trace_merge.restype = None
+        L.prach_noma_trace_format_csv.argtypes = [C.POINTER(PrachNomaTraceSpec), C.POINTER(PrachNomaTrace), u64p6, C.c_char_p, C.c_char_p, C.c_size_t]
+        L.prach_noma_trace_format_csv.restype = C.c_size_t
+        L.prach_noma_trace_tile_rows.argtypes = []
         _lib = L
     return _lib
 
@@ -953,7 +1034,8 @@ EXPORTS = ("prach_engine_create", "prach_engine_destroy", "prach_engine_set", "p
            "prach_columns_tile_ues", "prach_run_trials_noma_census", "prach_noma_census_accumulate_logs", "prach_noma_census_merge", "prach_noma_census_format_csv",
            "prach_noma_census_tile_ues", "prach_run_trials_noma_columns", "prach_run_trials_noma_columns_device", "prach_noma_columns_from_logs",
            "prach_run_trials_noma_pick", "prach_noma_pick_from_logs", "prach_noma_pick_format_csv", "prach_run_trials_noma_summary", "prach_noma_summary_from_logs",
-           "prach_noma_summary_stats", "prach_noma_summary_format_csv")
+           "prach_noma_summary_stats", "prach_noma_summary_format_csv", "prach_run_trials_noma_trace", "prach_noma_trace_merge", "prach_noma_trace_format_csv",
+           "prach_noma_trace_tile_rows")
 
 
 def make_cfg(nUE, variant=VARIANT_BETA_C, uniform=0, rng_mode=RNG_GLIBC, seed=0, stream_offset=0, **kw) -> PrachCfg:
@@ -1128,6 +1210,19 @@ class Engine:
         (prach_run_trials_noma_columns, prach_run_trials_noma_columns_device).  device as in run_trials_columns.  Returns (results, logs, NomaColumns)."""
         return self._run_columns("run_trials_noma_columns", "prach_run_trials_noma_columns", cfgs, fields, device, want_logs, noma_columns_spec, noma_columns_header_dtype(),
                                  PrachNomaColumns, NomaColumns)
+
+    def run_trials_noma_trace(self, cfgs, bins, bin_ms=5, groups=None, ngroups=None, want_logs=False):
+        """run_trials plus NOMA.c's channel trace per trial group — per access slot and sector the preambles sent, the bins used and alone, the UEs granted, the
+        power-domain pairs and the pairs that decoded one UE, by time — recorded by prach::noma_kernel while it runs and reduced on the device
+        (prach_run_trials_noma_trace; NOMA.c trials with Philox only).  groups / ngroups / want_logs as in run_trials_dist.  Returns (results, logs, NomaTrace)."""
+        red = NomaTrace(_ngroups(len(cfgs), groups, ngroups), bins, bin_ms)
+        sp = red.spec()
+        gg = (PrachNomaTrace * red.ngroups)()
+        gp = None if groups is None else (C.c_int32 * len(cfgs))(*[int(g) for g in groups])
+        res, logs = self._call("prach_run_trials_noma_trace", cfgs, want_logs, C.byref(sp), gp, gg, red._series())
+        for g in range(red.ngroups):
+            red._store(g, gg[g])
+        return res, logs, red
 
     def run_trials_trace(self, cfgs, bins, bin_ms=1, groups=None, want_logs=False, ngroups=None):
         """run_trials plus the per-subframe preamble trace per trial group — preambles used (calls), decoded (singles) and what the subframes added to
@@ -1354,6 +1449,15 @@ def trace_tile_subframes() -> int:
 def trace_csv(tr: Trace, labels=None) -> bytes:
     """The CSV text of every group (prach_trace_format_csv), labelled labels[g] (default: the group number)."""
     return _csv("prach_trace_format_csv", tr, labels)
+
+
+def noma_trace_tile_rows() -> int:
+    return lib().prach_noma_trace_tile_rows()
+
+
+def noma_trace_csv(tr: NomaTrace, labels=None) -> bytes:
+    """The CSV text of every group (prach_noma_trace_format_csv), labelled labels[g] (default: the group number)."""
+    return _csv("prach_noma_trace_format_csv", tr, labels)
 
 
 def summary_max_value() -> int:

@@ -93,7 +93,9 @@ struct TrialDev {
     unsigned long long *diag;    // diagnostic build (PRACH_STAMPS) only: [CLUSTER_MAX_G][32] per-workgroup phase stamps of a cluster trial; else null
     // prach_run_trials_trace only (else null): [maxTime] one row per subframe, zeroed before the launch — x preambleCollision calls, y the calls with
     // check == 1, z what the subframe added to totalPreambleTxop, w what it added to collisionPreambles.  Written by ONE lane behind the barrier that closes
-    // the subframe's calls (cluster_kernel: by the workgroup that writes DevResult; batch_kernel; trial_kernel), only where a call was made
+    // the subframe's calls (cluster_kernel: by the workgroup that writes DevResult; batch_kernel; trial_kernel), only where a call was made.
+    // prach_run_trials_noma_trace (NOMA.c, else null): [access slots][6 sectors][2] — tx, used, singles, granted | pairs, pair_one, 0, 0 — written by lane 0 of
+    // the sector's resolver wavefront of workgroup 0 (noma_kernel), only where somebody transmitted
     int4 *trace;
 };
 
@@ -299,5 +301,21 @@ struct TraceJob {
 };
 struct TraceOut { unsigned long long *calls, *singles, *txop, *collisions, *scalars; }; // [ngroups][bins] each, [ngroups][TR_SCALARS]
 hipError_t launch_trace_kernel(const TraceJob *jobs, int njobs, int workgroups, int bins, int bin_ms, int scheme, TraceOut out, hipStream_t stream);
+
+// prach_noma_trace.hip: NOMA.c's channel trace of a launch's accepted trials (prach_run_trials_noma_trace).  One job per trial: the rows prach::noma_kernel
+// wrote through TrialDev::trace, two 16-byte words per (access slot, sector) — tx, used, singles, granted | pairs, pair_one, 0, 0 — row r being slot r / 6,
+// sector r % 6, for the slots whose subframe lies in [0, steps).  A workgroup reduces one tile of NT_TILE consecutive rows (NT_TILE / 6 whole slots) of one
+// trial.  Slot s falls into bin s * aT / bin_ms: scheme 1 adds a tile up in an LDS window of 64-bit counters, NT_WINDOW bins from the tile's first on, and
+// flushes the non-zero ones; what falls behind the window (bin_ms < aT only), and everything under scheme 0, goes straight to the call's buffers; both with
+// 64-bit agent-scope atomics.
+constexpr int NT_TILE = 768, NT_THREADS = 256, NT_WINDOW = NT_TILE / 6;
+static_assert(NT_TILE % 6 == 0 && NT_TILE % NT_THREADS == 0, "a tile is whole slots, and whole passes of the workgroup");
+constexpr int NT_SCALARS = 12, NT_SUMS = 8, NT_MAXIMA = 1; // per group: slots, tx, used, singles, granted, pairs, pair_one, overflow_tx | tx_max + 1 (0: no row) | 3 spare
+struct NomaTraceJob {
+    const int4 *rows; // [nrows][2]
+    int nrows, group, wg0, aT; // wg0: the first workgroup of this job
+};
+struct NomaTraceOut { unsigned long long *series[6], *scalars; }; // [ngroups][6 sectors][bins] each, [ngroups][NT_SCALARS]
+hipError_t launch_noma_trace_kernel(const NomaTraceJob *jobs, int njobs, int workgroups, int bins, int bin_ms, int scheme, NomaTraceOut out, hipStream_t stream);
 
 } // namespace prach

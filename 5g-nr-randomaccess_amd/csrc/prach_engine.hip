@@ -163,7 +163,11 @@ LaunchLayout layout_launch(const prach_cfg *cfgs, const int *idx, int m, prach_u
 #else
         L.t[k].diag = 0;
 #endif
-        L.t[k].trace = trace ? take(16 * (size_t)prach_max_time(&cfgs[idx[k]])) : 0;
+        { // (NOMA.c, prach_run_trials_noma_trace: 32 bytes per access slot and sector)
+            const prach_cfg &c = cfgs[idx[k]];
+            const size_t mt = (size_t)prach_max_time(&c);
+            L.t[k].trace = !trace ? 0 : c.variant == PRACH_VARIANT_NOMA_C ? take(32 * 6 * ((mt + (size_t)c.accessTime - 1) / (size_t)c.accessTime)) : take(16 * mt);
+        }
     }
     if (cfgs[idx[0]].variant == PRACH_VARIANT_NOMA_C) L.act_flags = take(4 * (2 + 2 * (size_t)NOMA_ACT_FLAG_CAP));
     L.zero_end = o;
@@ -433,8 +437,8 @@ static int noma_device_activation(prach_engine *e, const TrialDev *dparams, cons
 // the simulation kernel.  What differs between the kinds is stated ONCE per kind: a block of functions behind CallCtx and its row of RED_KINDS.  The generic
 // code (reduction_begin, run_group, reduction_end, run_trials_impl) walks that row and never asks which kind it has; a new kind is an enumerator, a block and
 // a row.
-enum class Red { dist, timeline, sojourn, summary, trace, xtab, pick, columns, noma_census, noma_columns, noma_summary, noma_pick };
-constexpr int RED_MAX_PARTS = 6;
+enum class Red { dist, timeline, sojourn, summary, trace, xtab, pick, columns, noma_census, noma_columns, noma_summary, noma_pick, noma_trace };
+constexpr int RED_MAX_PARTS = 7;
 struct Reduction {
     Red kind;
     const int32_t *group; // nullable: trial k is group k
@@ -780,6 +784,26 @@ hipError_t noma_pick_launch(const prach_engine *e, const Reduction &r, int njobs
     return launch_noma_pick_kernel(timeline_jobs(e), njobs, spec_of<prach_pick_spec>(r), (int)e->opt_pick_threads, std::min(max_slots, noma_select_sched_cap()), d[0], d[1], e->stream);
 }
 
+// noma_trace: the six series tx, used, singles, granted, pairs, pair_one, [6 sectors][bins] per group | scalars; reads the rows prach::noma_kernel writes per
+// (access slot, sector) — of the slots whose subframe lies in [0, steps): what this launch's kernel wrote for the trial, and the zeros behind an early exit
+int noma_trace_parts(const Reduction &r, size_t w[]) { for (int q = 0; q < 6; q++) w[q] = 6 * (size_t)spec_of<prach_noma_trace_spec>(r).bins; w[6] = NT_SCALARS; return 7; }
+int noma_trace_fill_job(void *job, const JobSrc &s) {
+    const int nrows = 6 * ((subframes_run(s) + s.c.accessTime - 1) / s.c.accessTime);
+    *static_cast<NomaTraceJob *>(job) = NomaTraceJob{reinterpret_cast<const int4 *>(s.A + s.L.trace), nrows, s.group, s.wg0, s.c.accessTime};
+    return nrows;
+}
+hipError_t noma_trace_launch(const prach_engine *e, const Reduction &r, int njobs, int wgs, unsigned long long *const *d) {
+    const prach_noma_trace_spec &sp = spec_of<prach_noma_trace_spec>(r);
+    return launch_noma_trace_kernel(reinterpret_cast<const NomaTraceJob *>(e->red_jobs_d), njobs, wgs, sp.bins, sp.bin_ms, (int)e->opt_trace_scheme,
+                                    NomaTraceOut{{d[0], d[1], d[2], d[3], d[4], d[5]}, d[6]}, e->stream);
+}
+int noma_trace_unpack(const Reduction &r, CallCtx &cx, size_t g, const unsigned long long *q) {
+    prach_noma_trace &t = group_of<prach_noma_trace>(r, g);
+    t.trials = cx.trials[g]; t.slots = q[0]; t.tx = q[1]; t.used = q[2]; t.singles = q[3]; t.granted = q[4]; t.pairs = q[5]; t.pair_one = q[6]; t.overflow_tx = q[7];
+    t.tx_max = (int64_t)q[8] - 1;
+    return PRACH_OK;
+}
+
 // in the order of enum class Red:           parts, job bytes, tile, job, device logs, trace rows, "fast" off, launch, empty, unpack, prach_timing field
 const RedKind RED_KINDS[] = {
     {dist_parts, sizeof(DistJob), DIST_TILE, dist_fill_job, false, false, false, dist_launch, empty_group<prach_dist, &prach_dist::delay_max>, dist_unpack, &prach_timing::dist_ms},
@@ -794,8 +818,9 @@ const RedKind RED_KINDS[] = {
     {noma_columns_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, noma_columns_launch, noma_columns_empty, noma_columns_unpack, &prach_timing::noma_columns_ms},
     {noma_summary_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, noma_summary_launch, noma_summary_empty, noma_summary_unpack, &prach_timing::noma_summary_ms},
     {pick_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, noma_pick_launch, pick_empty, pick_unpack, &prach_timing::noma_pick_ms},
+    {noma_trace_parts, sizeof(NomaTraceJob), NT_TILE, noma_trace_fill_job, false, true, false, noma_trace_launch, empty_group<prach_noma_trace, &prach_noma_trace::tx_max>, noma_trace_unpack, &prach_timing::noma_trace_ms},
 };
-static_assert(sizeof(RED_KINDS) / sizeof(RED_KINDS[0]) == (size_t)Red::noma_pick + 1, "one row per kind");
+static_assert(sizeof(RED_KINDS) / sizeof(RED_KINDS[0]) == (size_t)Red::noma_trace + 1, "one row per kind");
 const RedKind &kind_of(const Reduction &r) { return RED_KINDS[(int)r.kind]; }
 
 // How a rerun's launch differs from the first one
@@ -1882,6 +1907,21 @@ int prach_run_trials_noma_pick(prach_engine *e, const prach_cfg *cfgs, int n, pr
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
+int prach_run_trials_noma_trace(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_noma_trace_spec *spec,
+                                const int32_t *group, prach_noma_trace *tr, uint64_t *const series[6]) {
+    // (spec, groups and variants are judged first: what they ask for does not depend on a device)
+    if (!cfgs || !results || n <= 0 || !spec || !tr || !series) return PRACH_ERR_ARG;
+    for (int q = 0; q < 6; q++) if (!series[q]) return PRACH_ERR_ARG;
+    if (spec->bins < 1 || spec->bins > PRACH_TRACE_MAX_BINS || spec->bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
+    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
+    for (int k = 0; k < n; k++) if (!noma_device_cfg(cfgs[k])) return PRACH_ERR_UNSUPPORTED;
+    if (36 * (uint64_t)spec->ngroups * (uint64_t)spec->bins > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
+    if (!e) return PRACH_ERR_ARG;
+    const Reduction red{.kind = Red::noma_trace, .group = group, .ngroups = spec->ngroups, .out = {series[0], series[1], series[2], series[3], series[4], series[5]}, .spec = spec, .groups = tr};
+    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
+}
+
+int prach_noma_trace_tile_rows(void) { return NT_TILE; }
 int prach_noma_census_tile_ues(void) { return TL_TILE; }
 int prach_columns_tile_ues(void) { return TL_TILE; }
 int prach_xtab_tile_ues(void) { return TL_TILE; }

@@ -768,6 +768,43 @@ size_t prach_trace_format_csv(const prach_trace_spec *s, const prach_trace *t, c
     return csv_end(buf, cap, off);
 }
 
+/* ---- NOMA.c's channel trace per trial group (prach_run_trials_noma_trace): merge, CSV ------------- */
+
+static int noma_trace_spec_ok(const prach_noma_trace_spec *s) {
+    return s && s->bins >= 1 && s->bins <= PRACH_TRACE_MAX_BINS && s->bin_ms >= 1;
+}
+
+void prach_noma_trace_merge(const prach_noma_trace_spec *s, prach_noma_trace *into, uint64_t *const into_series[6], const prach_noma_trace *from,
+                            const uint64_t *const from_series[6]) {
+    if (!noma_trace_spec_ok(s) || !into || !into_series || !from || !from_series) return;
+    for (int q = 0; q < 6; q++) if (!into_series[q] || !from_series[q]) return;
+    const int64_t a = into->slots ? into->tx_max : -1, b = from->slots ? from->tx_max : -1;
+    into->trials += from->trials; into->slots += from->slots; into->tx += from->tx; into->used += from->used; into->singles += from->singles;
+    into->granted += from->granted; into->pairs += from->pairs; into->pair_one += from->pair_one; into->overflow_tx += from->overflow_tx;
+    into->tx_max = a > b ? a : b;
+    for (int q = 0; q < 6; q++)
+        for (int i = 0; i < 6 * s->bins; i++) into_series[q][i] += from_series[q][i];
+}
+
+size_t prach_noma_trace_format_csv(const prach_noma_trace_spec *s, const prach_noma_trace *t, const uint64_t *const series[6], const char *label, char *buf, size_t cap) {
+    static const char *const names[6] = {"tx", "used", "singles", "granted", "pairs", "pair_one"};
+    if (!noma_trace_spec_ok(s) || !t || !series || !label) return 0;
+    for (int q = 0; q < 6; q++) if (!series[q]) return 0;
+    size_t off = 0;
+    for (int q = 0; q < 6; q++)
+        for (int b = 0; b < s->bins; b++) {
+            uint64_t all = 0;
+            for (int c = 0; c < 6; c++) {
+                const uint64_t v = series[q][(size_t)c * (size_t)s->bins + (size_t)b];
+                all += v;
+                if (v) CSV_EMIT("%.200s,%s,%d,%lld,%llu\n", label, names[q], c, (long long)b * s->bin_ms, (unsigned long long)v);
+            }
+            if (all) CSV_EMIT("%.200s,%s,all,%lld,%llu\n", label, names[q], (long long)b * s->bin_ms, (unsigned long long)all);
+        }
+    if (t->overflow_tx) CSV_EMIT("%.200s,tx,all,overflow,%llu\n", label, (unsigned long long)t->overflow_tx);
+    return csv_end(buf, cap, off);
+}
+
 /* ---- sojourn histograms by arrival row per trial group (prach_run_trials_sojourn) ---------------- */
 
 static int sojourn_spec_ok(const prach_sojourn_spec *s) {

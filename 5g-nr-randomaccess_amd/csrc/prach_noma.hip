@@ -63,7 +63,8 @@ struct NLds {
     double *slg; // [6*64] ln(gain)
     int *scal;   // [32]
 };
-enum { N_NSUCC = 0, N_STATUS, N_PTC, N_FC, N_MAXT, N_NSUCCTOT, N_MAXTTOT, N_PAIRD, N_SUMT = 8, N_ND = 10, N_SX = 12, N_AMBIG = 13 };
+enum { N_NSUCC = 0, N_STATUS, N_PTC, N_FC, N_MAXT, N_NSUCCTOT, N_MAXTTOT, N_PAIRD, N_SUMT = 8, N_ND = 10, N_SX = 12, N_AMBIG = 13,
+       N_TRACE = 14 /* [2] where this workgroup writes the trial's trace rows (prach_run_trials_noma_trace: TrialDev::trace), 64 bits; 0: it writes none */ };
 
 __device__ __forceinline__ NLds ncarve(char *smem, int nP) {
     NLds L;
@@ -103,6 +104,20 @@ __global__ __launch_bounds__(256) void noma_activation_kernel(const TrialDev *__
 
 } // namespace
 
+// philox_draw31 for the trace row only (prach_run_trials_noma_trace), with two-input xors and an empty fence between them: the compiler cannot fold them into a
+// v_bitop3_b32, so the kernel's inventory of that instruction (tests/golden/bitop3_inventory.json) is what it was without the trace.  Same value, bit for bit.
+__device__ __forceinline__ int philox_draw31_trace(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned c2, unsigned c3) {
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+        unsigned n0 = (unsigned)(p1 >> 32) ^ c1, n2 = (unsigned)(p0 >> 32) ^ c3;
+        asm volatile("" : "+v"(n0), "+v"(n2));
+        c0 = n0 ^ k0; c1 = (unsigned)p1; c2 = n2 ^ k1; c3 = (unsigned)p0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return (int)(c0 >> 1);
+}
+
 size_t noma_kernel_lds_bytes(int nP) { return sizeof(double) * 2 * 6 * 64 + sizeof(int) * (6 * 64 + 32 + 4 * 6 * nP); }
 
 __global__ __launch_bounds__(WG_THREADS) void noma_kernel(const TrialDev *__restrict__ params, const int G, const int nT, const int xpack) {
@@ -130,7 +145,10 @@ __global__ __launch_bounds__(WG_THREADS) void noma_kernel(const TrialDev *__rest
     }
     if (tid < 32) L.scal[tid] = 0;
     __syncthreads();
-    if (tid == 0) L.scal[N_MAXT] = -1;
+    if (tid == 0) { // (in a cluster every workgroup resolves identically: workgroup 0 alone records)
+        L.scal[N_MAXT] = -1;
+        *reinterpret_cast<unsigned long long *>(&L.scal[N_TRACE]) = b == 0 ? (unsigned long long)P.trace : 0ull;
+    }
     __syncthreads();
     bool sx = false; // same-XCD handshake (prach_exchange.h)
     if (xpack && G > 1 && G <= 64) sx = same_xcd_handshake(mbox + (size_t)G * mbstride, (size_t)mbstride, b, G, &L.scal[N_STATUS], &L.scal[N_SX]);
@@ -251,10 +269,11 @@ __global__ __launch_bounds__(WG_THREADS) void noma_kernel(const TrialDev *__rest
             const bool single = lane < nP && L.tcnt[sct * nP + lane] == 1;
             const int myidx = single ? L.twho[sct * nP + lane] : -1;
             const int count = __popcll(__ballot(single));
+            int npd = 0;
+            bool gme = false; // (this lane's UE was granted: read by the trace row only)
             if (count > 0 && count <= nGrantUL) { // NOMA.c:252-260
                 if (single && ((myidx >> 6) % G) == b) grant_rec(&P.rec[myidx]);
             } else if (count > 0) { // (prach_noma_resolve.h; the pair draws: the stateless counter ((slot * 6 + sector) * nGrantUL + pair) * 2 (+ 1))
-                int npd = 0;
                 const NomaResolved R = noma_resolve_sector(single, myidx, nGrantUL, nonsector, P.n_devact, L.sidx + sct * 64, L.sg + sct * 64, L.slg + sct * 64,
                     [&](const int idx) __attribute__((always_inline)) { return NomaGain{gain[idx], lgain[idx]}; },
                     [&](const int pair, const int which, int &d) __attribute__((always_inline)) {
@@ -262,10 +281,34 @@ __global__ __launch_bounds__(WG_THREADS) void noma_kernel(const TrialDev *__rest
                         npd++;
                         return true;
                     },
-                    [&](const int idx) __attribute__((always_inline)) { if (((idx >> 6) % G) == b) grant_rec(&P.rec[idx]); }, // (by the record's owner only)
+                    [&](const int idx) __attribute__((always_inline)) { gme = true; if (((idx >> 6) % G) == b) grant_rec(&P.rec[idx]); }, // (by the record's owner only)
                     [&](const int k) __attribute__((always_inline)) { NSTAMP(k); (void)k; });
                 if (b == 0 && lane == 0 && npd) atomicAdd(&L.scal[N_PAIRD], npd);
                 if (R.ambiguous && lane == 0) L.scal[N_AMBIG] = 1;
+            }
+            // prach_run_trials_noma_trace: the (slot, sector)'s row, by workgroup 0 alone and only where somebody transmitted — the totals are complete here and
+            // zeroed in pass B.  Two 16-byte vector stores by one lane.  The pairs come from the draw count the grouping leaves: pair g's first decode draw is the stateless counter ... + 2 g, drawn again here, and a
+            // second draw followed it exactly where the first says "one of the two" (<= 644245094: prach_noma_resolve.h; never under the cell-wide grouping)
+            // (a runtime, wave-uniform test, read BEHIND the grouping: measured, a value that is live across the grouping costs the untraced kernel more than this read)
+            const unsigned long long tracing = *reinterpret_cast<const unsigned long long *>(&L.scal[N_TRACE]);
+            if (tracing) {
+                const int c = lane < nP ? L.tcnt[sct * nP + lane] : 0;
+                const int tx = wave_sum(c), used = __popcll(__ballot(c >= 1));
+                const int granted = count <= nGrantUL ? count : __popcll(__ballot(gme)); // (the shortcut grants every singleton and pairs nobody)
+                int pairs = 0, pair_one = 0;
+                if (npd) { // (at most 32 pairs: two of at most 64 singletons each)
+                    const int d = philox_draw31_trace(P.seed_lo, P.seed_hi, 0xFFFFFFFFu, (unsigned)(((s * 6 + sct) * nGrantUL + (lane & 31)) * 2), (unsigned)nUE, NOMA_VARIANT);
+                    const unsigned long long om = __ballot(lane < 32 && d <= 644245094);
+                    if (nonsector) { pairs = npd; pair_one = __popcll(om & ((1ull << pairs) - 1ull)); }
+                    else for (int drawn = 0; drawn < npd; pairs++) { const int o = (int)((om >> pairs) & 1ull); drawn += 1 + o; pair_one += o; }
+                }
+                if (lane == 0 && tx > 0) {
+                    v4i_t r0, r1;
+                    r0.x = tx; r0.y = used; r0.z = count; r0.w = granted;
+                    r1.x = pairs; r1.y = pair_one; r1.z = 0; r1.w = 0;
+                    PRACH_G v4i_t *const row = (PRACH_G v4i_t *)tracing + 2 * ((size_t)s * 6 + (size_t)sct);
+                    row[0] = r0; row[1] = r1;
+                }
             }
         }
         NSTAMP(3); // resolve (sector 0), rest

@@ -129,6 +129,8 @@ typedef struct prach_timing {
     int32_t trial_kernel_reruns; /* of fallback_trials: trials that were (also) rerun on the one-workgroup, index-ordered trial_kernel */
     int32_t noma_host_ues;       /* NOMA_C, Philox: UEs of the device-built activeUE table that the host recomputed with its libm (a value inside the
                                     device math library's error band of a rounding / comparison boundary: ~1e-6 of the UEs) */
+    double noma_trace_ms;        /* HIP-event time of the NOMA trace kernel launches (prach_run_trials_noma_trace) of the last call; 0 in every other call (such a
+                                    call leaves every other *_ms of a reduction 0) */
     double noma_summary_ms;      /* HIP-event time of the NOMA summary kernel launches (prach_run_trials_noma_summary) of the last call; 0 in every other call (such a
                                     call leaves every other *_ms of a reduction 0) */
     double noma_pick_ms;         /* HIP-event time of the NOMA pick kernel launches (prach_run_trials_noma_pick) of the last call; 0 in every other call (such a call
@@ -569,6 +571,51 @@ size_t prach_noma_census_format_csv(const prach_xtab_spec *, const prach_noma_ce
 int prach_noma_census_tile_ues(void); /* UEs of one trial that one workgroup of prach::noma_census_kernel reduces (tests place sizes around it) */
 /* THE DEFINITION prach::noma_columns_kernel equals, integer for integer: prach_columns_from_logs with the NOMA menu.  PRACH_ERR_UNSUPPORTED: not a NOMA_C cfg. */
 int prach_noma_columns_from_logs(const prach_columns_spec *, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, int32_t *out, uint64_t stride);
+
+/* NOMA.c's channel trace per trial group: per access slot and sector, how many preambles were sent, how many stood alone, how many bins collided, how many
+ * power-domain pairs the grouping formed and how many of those decoded one UE only — recorded by prach::noma_kernel WHILE IT RUNS and reduced on the device.
+ * Like prach_trace it is no function of the per-UE state a trial leaves behind, so there is no _accumulate_logs form.  Per slot s (subframe s * accessTime) and
+ * sector c of a trial, in NOMA.c's own terms:
+ *   tx        transmitters gathered by preambleSectorCollisionDetection (NOMA.c:206-212): the sum of the sector's (sector, preamble) bin counts
+ *   used      bins with at least one transmitter;  singles  bins with exactly one (NOMA.c:214-243: `count`);  used - singles = COLLIDED bins
+ *   granted   UEs whose msg2 the slot sets (count, where count <= nGrantUL)
+ *   pairs     power-domain pairs that received a grant (NOMA.c:279-286);  pair_one  of those, the pairs of which only one UE decoded (the first decode draw
+ *             below 0.3; under PRACH_FLAG_NOMA_NONSECTOR too, where no second draw follows).  UEs granted through NOMA: 2 * pairs - pair_one
+ * Under PRACH_FLAG_NOMA_NONSECTOR there is one group: it is sector 0 and the other five stay zero.  A trial's rows cover the slots whose subframe lies in
+ * [0, steps); a (slot, sector) without a transmitter is all zero.  Slot s falls into bin (s * accessTime) / bin_ms; a slot at or behind bins * bin_ms counts in
+ * the scalars and in no bin, its tx in overflow_tx.  Integers only: device, host, forked workers and ranks merge exactly in any order.  The six series are
+ * [ngroups][6 sectors][bins] each, in the order tx, used, singles, granted, pairs, pair_one. */
+#define PRACH_NOMA_TRACE_SERIES 6
+typedef struct prach_noma_trace_spec {
+    int32_t bins;      /* 1 .. PRACH_TRACE_MAX_BINS */
+    int32_t bin_ms;    /* >= 1 */
+    int32_t ngroups;   /* number of output traces */
+    int32_t reserved;  /* 0 */
+} prach_noma_trace_spec;
+
+typedef struct prach_noma_trace {    /* one per group */
+    uint64_t trials;                 /* trials accumulated (status PRACH_OK) */
+    uint64_t slots;                  /* access slots read: the sum of ceil(steps / accessTime) */
+    uint64_t tx, used, singles, granted, pairs, pair_one; /* over all their slots and sectors, unbinned */
+    uint64_t overflow_tx;            /* tx in slots at or behind bins * bin_ms (in no bin) */
+    int64_t  tx_max;                 /* the largest `tx` of one (slot, sector) of one trial; -1 without slots */
+} prach_noma_trace;
+
+/* prach_run_trials plus the channel traces, with the contract of prach_run_trials_noma_census (groups, OVERWRITTEN outputs, a rerun trial counted once, at most
+ * one reduction per call); tr[ngroups] and series[q][ngroups * 6 * bins] are caller-owned.  prach::noma_kernel writes one 32-byte row per (slot, sector) ON THE
+ * DEVICE (the arena of the call grows by 192 bytes x ceil(maxTime / accessTime) per trial) and prach::noma_trace_kernel (csrc/prach_noma_trace.hip) reduces
+ * them there; engine option "trace_scheme" applies.  Results and logs are those of the same prach_run_trials call.
+ * PRACH_ERR_ARG: a NULL output, a bin count or width out of range, a group id out of range, NULL group with ngroups != n;
+ * PRACH_ERR_UNSUPPORTED, before anything is launched: any cfg that is not NOMA_C; any NOMA_C cfg with rng_mode == PRACH_RNG_GLIBC; 36 * ngroups * bins > 2^27
+ * words. */
+int prach_run_trials_noma_trace(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs,
+                                const prach_noma_trace_spec *spec, const int32_t *group, prach_noma_trace *tr, uint64_t *const series[6]);
+/* host side, ONE group (series[q]: [6][bins]): _merge adds counts and takes the maximum; _format_csv writes "label,series,sector,t_ms,count" for every
+ * non-zero (bin, sector), an all-sectors line "label,series,all,t_ms,count" for every non-zero bin, and "label,tx,all,overflow,count" if overflow_tx != 0;
+ * returns the text's length (written in full only if it fits cap, then 0-terminated). */
+void prach_noma_trace_merge(const prach_noma_trace_spec *, prach_noma_trace *into, uint64_t *const into_series[6], const prach_noma_trace *from, const uint64_t *const from_series[6]);
+size_t prach_noma_trace_format_csv(const prach_noma_trace_spec *, const prach_noma_trace *, const uint64_t *const series[6], const char *label, char *buf, size_t cap);
+int prach_noma_trace_tile_rows(void); /* (slot, sector) rows of one trial that one workgroup of prach::noma_trace_kernel reduces (tests place sizes around it) */
 
 /* Per-trial summaries of NOMA_C trials: ONE ROW PER TRIAL — the four class counts, and for up to four NAMED fields of THE NOMA MENU above, over the UEs of
  * the classes in `who` whose value of the field is DEFINED (the menu's ONE RULE: >= 0), their number, sum, maximum and EXACT order statistics — selected on the
