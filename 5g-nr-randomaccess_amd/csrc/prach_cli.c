@@ -657,16 +657,16 @@ int main(int argc, char *argv[]) {
     base.rng_mode = rng;
     if (ntr_path && variant != PRACH_VARIANT_NOMA_C) die("--census-trace needs --program noma (the other programs have --trace)");
     if (ntr_path && (nci_path || npk_path || nc_path || pk_path || xt_path || tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--census-trace cannot be combined with another reduction: one reduction per call");
-    if (ntr_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census-trace needs --rng philox (a NOMA.c trial in the reference's stream can finish on the host and leaves no device record)");
+    if (ntr_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census-trace needs --rng philox (NOMA.c in the reference's stream is not wired to the NOMA menu's device calls)");
     if (nci_path && variant != PRACH_VARIANT_NOMA_C) die("--census-ci needs --program noma (the other programs have --ci)");
     if (npk_path && variant != PRACH_VARIANT_NOMA_C) die("--census-pick needs --program noma (the other programs have --pick)");
     if (nci_path && (npk_path || nc_path || pk_path || xt_path || tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--census-ci cannot be combined with --cdf, --timeline, --sojourn, --ci, --trace, --xtab, --pick, --census or --census-pick: one reduction per call");
     if (npk_path && (nc_path || pk_path || xt_path || tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--census-pick cannot be combined with --cdf, --timeline, --sojourn, --ci, --trace, --xtab, --pick or --census: one reduction per call");
-    if (nci_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census-ci needs --rng philox (a NOMA.c trial in the reference's stream can finish on the host and leaves no device record)");
-    if (npk_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census-pick needs --rng philox (a NOMA.c trial in the reference's stream can finish on the host and leaves no device record)");
+    if (nci_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census-ci needs --rng philox (NOMA.c in the reference's stream is not wired to the NOMA menu's device calls)");
+    if (npk_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census-pick needs --rng philox (NOMA.c in the reference's stream is not wired to the NOMA menu's device calls)");
     if (nc_path && variant != PRACH_VARIANT_NOMA_C) die("--census needs --program noma (the other programs have --xtab)");
     if (nc_path && (pk_path || xt_path || tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--census cannot be combined with --cdf, --timeline, --sojourn, --ci, --trace, --xtab or --pick: one reduction per call");
-    if (nc_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census needs --rng philox (a NOMA.c trial in the reference's stream can finish on the host and leaves no device record)");
+    if (nc_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census needs --rng philox (NOMA.c in the reference's stream is not wired to the NOMA menu's device calls)");
     if (pk_path && (xt_path || tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--pick cannot be combined with --cdf, --timeline, --sojourn, --ci, --trace or --xtab: one reduction per call");
     if (pk_path && variant == PRACH_VARIANT_NOMA_C) die("--pick needs --program beta or withnoma (NOMA.c logs no trace of a UE's cycle start)");
     if (xt_path && (tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--xtab cannot be combined with --cdf, --timeline, --sojourn, --ci or --trace: one reduction per call");

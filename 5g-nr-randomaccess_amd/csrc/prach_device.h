@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 #include "../../include/prach.h"
 
 namespace prach {
@@ -166,15 +167,32 @@ int noma_kernel_blocks_per_cu(int maxP);
 constexpr int NOMA_ACT_FLAG_CAP = 8192;
 constexpr int NOMA_AMBIGUOUS = 77; // DevResult::hard_error: a gain comparison of the resolver fell inside the error band (the trial is rerun with the host-built table)
 hipError_t launch_noma_activation(const TrialDev *params, int ntrials, int maxUE, unsigned *flags, hipStream_t stream);
-// NOMA_C in the reference's own rand() stream (prach_noma_glibc.hip): one trial, host-activated arrivals + one device step per access slot
-constexpr int NOMA_GLIBC_AMBIGUOUS_RC = -1077; // run_noma_glibc_batch: a value inside the device libm's error band — run that trial on the host-activated path
-// (sink / sinks[j]: where a finished trial's distributions are added on the host, prach_run_trials_dist; null without a spec)
-struct DistSink { const prach_dist_spec *spec; prach_dist *d; uint64_t *delay_hist, *ptc_hist; }; // one group's host-side accumulators
-int run_noma_glibc_trial(hipStream_t stream, const prach_cfg &c, const int32_t *hstream, unsigned long long len, prach_result *res, prach_ue_log *logs,
-                         double *kernel_ms, const DistSink *sink = nullptr);
-int run_noma_glibc_batch(hipStream_t stream, const prach_cfg *const *cfgs, int n, const unsigned long long *lens, prach_result *const *res, prach_ue_log *const *logs,
-                         double *kernel_ms, int *rcs, const DistSink *sinks = nullptr);
-extern "C" void prach_internal_dist_add_ue(const prach_dist_spec *spec, prach_dist *d, uint64_t *delay_hist, uint64_t *ptc_hist, int32_t timer, int32_t ptc); // prach_host.c
+// NOMA_C in the reference's own rand() stream (prach_noma_glibc.hip), both forms on the engine's arena and pinned mirror.  One launch:
+//   [ TrialArgs[n] | control blocks | finishing blocks | StreamJob[n] | per trial: arrival table, stream seeds ]   staged: built in the mirror, ONE copy
+//   [ per trial: UE records, stream window, list of live UEs, timers, ptc, log records where asked for ]
+// The slot-by-slot form (`slots`, one trial) has no argument blocks, jobs and seeds — the host keeps the stream and uploads the window — and its UE records
+// are part of the staged region: the host writes the arrivals' records there slot after slot.
+struct NomaGlibcTrial { size_t sched, seeds, ue, stream, live, timers, ptc, logs, nsched, nchunks; unsigned long long len; }; // arena offsets (logs 0: none)
+struct NomaGlibcLayout {
+    std::vector<NomaGlibcTrial> t;
+    bool slots = false;
+    int max_ue = 0;
+    size_t ue_bytes = 0, args = 0, ctl = 0, ctl_bytes = 0, live_state = 0, fin = 0, jobs = 0, staged_end = 0, end = 0; // ue_bytes: one UE record; ctl .. + ctl_bytes: what comes back after a launch
+};
+// what a trial's control block says after a launch, in either form.  status: PRACH_OK, PRACH_ERR_STREAM (window too small: once more with a larger one) or
+// NOMA_GLIBC_AMBIGUOUS_RC (single-launch form: a value inside the device libm's error band — run that trial slot by slot); done (slot form): no slot is left
+constexpr int NOMA_GLIBC_AMBIGUOUS_RC = -1077;
+struct NomaGlibcEnd { unsigned long long pos, steps; int status, nSuccess, time_exit, activeCheck; long long delay; int nTxP, failed; bool done; };
+NomaGlibcLayout noma_glibc_layout(const prach_cfg *cfgs, const int *idx, int n, const unsigned long long *lens, prach_ue_log *const *ue_logs, bool slots);
+// fills the staged region of the mirror H for the arena A (every block zeroed first); nAccess[j]: prach_result.nAccessUE of trial j
+void noma_glibc_stage(const NomaGlibcLayout &L, const prach_cfg *cfgs, const int *idx, const char *A, char *H, int32_t *nAccess);
+hipError_t launch_noma_glibc_trials(const NomaGlibcLayout &L, const char *A, hipStream_t stream); // stream windows, noma_glibc_trial_kernel, the finishing kernel
+// slot form, the access slot at subframe t: activates the arrivals [from, to) in the mirror with the reference's libm (hstream: the host copy of the window,
+// *pos moves behind their draws) and fills the slot's control block; PRACH_OK or PRACH_ERR_STREAM
+int noma_glibc_stage_slot(const NomaGlibcLayout &L, const prach_cfg &c, const int32_t *hstream, uint64_t *pos, int t, int from, int to, char *H);
+hipError_t launch_noma_glibc_slot(const NomaGlibcLayout &L, const prach_cfg &c, const char *A, hipStream_t stream);
+hipError_t launch_noma_glibc_finish(const NomaGlibcLayout &L, const char *A, hipStream_t stream);
+NomaGlibcEnd noma_glibc_end(const NomaGlibcLayout &L, const prach_cfg &c, const char *H, int j);
 
 // The reducer kernels below.  What they share is in prach_reduce_tile.h, ONE copy: the job lookup over `wg0`, the 64-bit agent-scope add and maximum, the
 // wavefront folds, the slot range of a tile of UEs with its staging rule (TILE_SCHED_CAP), and the flush of a group's scalar row — the first *_SUMS words of

@@ -486,22 +486,6 @@ struct CallCtx {
     int group_of(int k) const { return red->group ? red->group[k] : k; }
     bool reads_device_logs() const { return red && kind_of(*red).device_logs; }
     bool traces() const { return red && kind_of(*red).trace_rows; }
-    // dist only: NOMA.c in the reference's stream finishes on the host: its groups' accumulators (sized on first use)
-    const prach_dist_spec *dist_spec() const { return red && red->kind == Red::dist ? static_cast<const prach_dist_spec *>(red->spec) : nullptr; }
-    std::vector<prach_dist> host_d;
-    std::vector<uint64_t> host_dh, host_ph;
-    DistSink sink(int k) { // the host-side accumulators of trial k's group
-        const prach_dist_spec *const spec = dist_spec();
-        if (host_d.empty()) {
-            prach_dist z{};
-            z.delay_max = -1;
-            host_d.assign((size_t)spec->ngroups, z);
-            host_dh.assign((size_t)spec->ngroups * (size_t)spec->delay_bins, 0);
-            host_ph.assign((size_t)spec->ngroups * PRACH_DIST_PTC_BINS, 0);
-        }
-        const size_t g = (size_t)group_of(k);
-        return DistSink{spec, &host_d[g], host_dh.data() + g * (size_t)spec->delay_bins, host_ph.data() + g * PRACH_DIST_PTC_BINS};
-    }
 };
 // ---- the kinds of reduction, one block each --------------------------------------------------------------------------------------------------------------
 template <class T> const T &spec_of(const Reduction &r) { return *static_cast<const T *>(r.spec); }
@@ -523,7 +507,7 @@ template <bool STEPS> int fill_timeline_job(void *job, const JobSrc &s) {
 }
 const TimelineJob *timeline_jobs(const prach_engine *e) { return reinterpret_cast<const TimelineJob *>(e->red_jobs_d); }
 
-// dist: delay_hist, ptc_hist | scalars; reads the timers and preamble counts the simulation kernel left in the arena, and adds what finished on the host
+// dist: delay_hist, ptc_hist | scalars; reads the timers and preamble counts the simulation kernel left in the arena
 int dist_parts(const Reduction &r, size_t w[]) { w[0] = (size_t)spec_of<prach_dist_spec>(r).delay_bins; w[1] = PRACH_DIST_PTC_BINS; w[2] = DIST_SCALARS; return 3; }
 int dist_fill_job(void *job, const JobSrc &s) {
     *static_cast<DistJob *>(job) = DistJob{reinterpret_cast<const int *>(s.A + s.L.timers), reinterpret_cast<const int *>(s.A + (s.batch ? s.L.rec32 : s.L.ptc)), s.c.nUE, s.group, s.wg0, s.batch ? 1 : 0};
@@ -534,12 +518,8 @@ hipError_t dist_launch(const prach_engine *e, const Reduction &r, int njobs, int
     return launch_dist_kernel(reinterpret_cast<const DistJob *>(e->red_jobs_d), njobs, wgs, sp.delay_bins, sp.delay_bin_ms, (int)e->opt_dist_scheme, d[0], d[1], d[2], e->stream);
 }
 int dist_unpack(const Reduction &r, CallCtx &cx, size_t g, const unsigned long long *q) {
-    const prach_dist_spec &s = spec_of<prach_dist_spec>(r);
     prach_dist &d = group_of<prach_dist>(r, g);
     d.trials = cx.trials[g]; d.ues = cx.ues[g]; d.success = q[0]; d.delay_overflow = q[1]; d.delay_sum = q[2]; d.ptc_sum = q[3]; d.delay_max = (int64_t)q[4] - 1;
-    if (!cx.host_d.empty())
-        prach_dist_merge(&s, &d, r.out[0] + g * (size_t)s.delay_bins, r.out[1] + g * PRACH_DIST_PTC_BINS, &cx.host_d[g], cx.host_dh.data() + g * (size_t)s.delay_bins,
-                         cx.host_ph.data() + g * PRACH_DIST_PTC_BINS);
     return PRACH_OK;
 }
 
@@ -921,6 +901,41 @@ static int print_launch_diagnostics(const prach_engine *e, const prach_cfg &c, c
     return PRACH_OK;
 }
 
+// The call's reduction over the trials `acc` that a launch finished and its caller accepts — so a trial that is rerun is counted once — behind the
+// simulation kernel on the same stream; it runs while `meanwhile` turns the launch's results into prach_result on the host, and has completed on return
+// (the next launch lays the arena out again and reuses the pinned job table).  Fills in every job's first workgroup; a call without a reduction only
+// runs `meanwhile`.
+template <class F> static int reduce_accepted(prach_engine *e, CallCtx &cx, std::vector<JobSrc> &acc, const F &meanwhile) {
+    bool launched = false;
+    if (cx.red) {
+        const Reduction &R = *cx.red;
+        const RedKind &K = kind_of(R);
+        int njobs = 0, wgs = 0;
+        for (JobSrc &s : acc) {
+            s.wg0 = wgs;
+            const int units = K.fill_job(e->red_jobs_h + K.job_bytes * (size_t)njobs++, s);
+            wgs += (units + K.tile - 1) / K.tile;
+            cx.trials[(size_t)s.group]++;
+            cx.ues[(size_t)s.group] += (uint64_t)s.c.nUE;
+        }
+        if (njobs > 0 && wgs > 0) {
+            HIPCHK(hipMemcpyAsync(e->red_jobs_d, e->red_jobs_h, K.job_bytes * (size_t)njobs, hipMemcpyHostToDevice, e->stream));
+            HIPCHK(hipEventRecord(e->red_ev0, e->stream));
+            HIPCHK(K.launch(e, R, njobs, wgs, cx.d_part));
+            HIPCHK(hipEventRecord(e->red_ev1, e->stream));
+            launched = true;
+        }
+    }
+    { int rc = meanwhile(); if (rc != PRACH_OK) return rc; }
+    if (launched) {
+        HIPCHK(hipStreamSynchronize(e->stream));
+        float rms = 0;
+        HIPCHK(hipEventElapsedTime(&rms, e->red_ev0, e->red_ev1));
+        cx.red_ms += rms;
+    }
+    return PRACH_OK;
+}
+
 // one launch over the trials idx[0..m) (all the same rng_mode); attempt = glibc stream retry level.  Batch-kernel trials that filled a calendar list
 // are appended to cal_overflow.
 static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int attempt, int G, LaunchOpts o, std::vector<int> &cal_overflow) {
@@ -1106,86 +1121,61 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
     if (kc.rec_mode >= 0) e->last.rec_mode = kc.rec_mode;
 
     const DevResult *const drs = reinterpret_cast<const DevResult *>(H);
-    // the call's reduction over the trials this launch finished — the ones the loop below accepts, so a trial that is rerun is counted once — behind the
-    // simulation kernel on the same stream; it runs while the host turns DevResult into prach_result.  dist reads the timers and preamble counts the
-    // simulation kernel left in the arena, timeline and sojourn its log records and the launch's own copy of every arrival schedule
-    bool red_launched = false;
-    if (cx.red) {
-        const Reduction &R = *cx.red;
-        const RedKind &K = kind_of(R);
-        int njobs = 0, wgs = 0;
+    // the call's reduction over the trials the loop below accepts: dist reads the timers and preamble counts the simulation kernel left in the arena,
+    // timeline and sojourn its log records and the launch's own copy of every arrival schedule
+    std::vector<JobSrc> acc;
+    for (int k = 0; k < m && cx.red; k++)
+        if (drs[k].status == PRACH_OK && !(noma && drs[k].hard_error == NOMA_AMBIGUOUS)) acc.push_back(JobSrc{cfgs[idx[k]], LL.t[k], drs[k], A, cx.group_of(idx[k]), 0, batch});
+    return reduce_accepted(e, cx, acc, [&]() -> int {
+        std::vector<int32_t> timers;
         for (int k = 0; k < m; k++) {
-            const DevResult &dr = drs[k];
-            if (dr.status != PRACH_OK || (noma && dr.hard_error == NOMA_AMBIGUOUS)) continue;
             const prach_cfg &c = cfgs[idx[k]];
-            const int g = cx.group_of(idx[k]);
-            const int units = K.fill_job(e->red_jobs_h + K.job_bytes * (size_t)njobs++, JobSrc{c, LL.t[k], dr, A, g, wgs, batch});
-            wgs += (units + K.tile - 1) / K.tile;
-            cx.trials[(size_t)g]++;
-            cx.ues[(size_t)g] += (uint64_t)c.nUE;
+            const TrialLayout &L = LL.t[k];
+            const DevResult &dr = drs[k];
+            prach_result &r = cx.results[idx[k]];
+            std::memset(&r, 0, sizeof(r));
+            r.status = (dr.hard_error && dr.status == PRACH_ERR_TIMEOUT) ? PRACH_ERR_INTERNAL : dr.status; // (a capacity overflow somewhere in the cluster is the cause, a peer's time-out its effect)
+            if (noma && dr.hard_error == NOMA_AMBIGUOUS && r.status == PRACH_OK) { r.status = PRACH_ERR_INTERNAL; cx.noma_ambiguous++; } // (rerun with the host-built table: run_trials)
+            r.time_exit = dr.time_exit;
+            r.maxTime = prach_max_time(&c);
+            r.nSuccessUE = dr.nSuccess;
+            r.failedUEs = c.nUE - dr.nSuccess;
+            r.preambleTxCount = dr.ptcSum;
+            r.failCounts = dr.fcSum;
+            r.collisionPreambles = dr.collisionPreambles;
+            r.totalPreambleTxop = dr.totalPreambleTxop;
+            r.activeCheck = dr.activeCheck;
+            r.nAccessUE = nAccess[k];
+            r.continueFaliedUEs = dr.continueFailed;
+            r.finalSuccessUEs = dr.finalSuccess;
+            r.sumTimer = dr.sumTimer;
+            r.draws = dr.draws;
+            r.steps = steps_of(c, dr);
+            e->last.group_visits += dr.visits;
+            e->last.event_ues += dr.events;
+            if (c.variant == PRACH_VARIANT_NOMA_C && dr.nSuccess == c.nUE && dr.dbg[0] > 0) { // all UEs succeeded: NOMA.c:707-710 breaks there
+                r.time_exit = (int32_t)dr.dbg[0] - 1; // (r.steps: steps_of above)
+            }
+            { int rc = print_launch_diagnostics(e, c, dr, L, A, G, noma); if (rc != PRACH_OK) return rc; }
+            if (batch && dr.status == PRACH_ERR_INTERNAL && (dr.hard_error == 5 || dr.hard_error == 8 || dr.hard_error == 9) && !o.full_calendars) cal_overflow.push_back(idx[k]);
+            if (dr.status != PRACH_OK) continue;
+            // totalDelay is a FLOAT running sum in index order (Beta.c:186,193): exact in integer
+            // arithmetic while it stays below 2^24, otherwise replay the float additions on the host.
+            if (dr.sumTimer < (1ll << 24)) {
+                r.totalDelay = (float)dr.sumTimer;
+            } else {
+                timers.resize((size_t)c.nUE);
+                HIPCHK(hipMemcpy(timers.data(), A + L.timers, 4 * (size_t)c.nUE, hipMemcpyDeviceToHost));
+                float td_ = 0;
+                for (int i = 0; i < c.nUE; i++)
+                    if (timers[i] != INT_MIN) td_ += (float)timers[i];
+                r.totalDelay = td_;
+            }
+            if (L.logs && cx.ue_logs && cx.ue_logs[idx[k]]) // (a timeline call lays out every trial's log; only the ones asked for cross the bus)
+                HIPCHK(hipMemcpy(cx.ue_logs[idx[k]], A + L.logs, sizeof(prach_ue_log) * (size_t)c.nUE, hipMemcpyDeviceToHost));
         }
-        if (njobs > 0 && wgs > 0) {
-            HIPCHK(hipMemcpyAsync(e->red_jobs_d, e->red_jobs_h, K.job_bytes * (size_t)njobs, hipMemcpyHostToDevice, e->stream));
-            HIPCHK(hipEventRecord(e->red_ev0, e->stream));
-            HIPCHK(K.launch(e, R, njobs, wgs, cx.d_part));
-            HIPCHK(hipEventRecord(e->red_ev1, e->stream));
-            red_launched = true;
-        }
-    }
-    std::vector<int32_t> timers;
-    for (int k = 0; k < m; k++) {
-        const prach_cfg &c = cfgs[idx[k]];
-        const TrialLayout &L = LL.t[k];
-        const DevResult &dr = drs[k];
-        prach_result &r = cx.results[idx[k]];
-        std::memset(&r, 0, sizeof(r));
-        r.status = (dr.hard_error && dr.status == PRACH_ERR_TIMEOUT) ? PRACH_ERR_INTERNAL : dr.status; // (a capacity overflow somewhere in the cluster is the cause, a peer's time-out its effect)
-        if (noma && dr.hard_error == NOMA_AMBIGUOUS && r.status == PRACH_OK) { r.status = PRACH_ERR_INTERNAL; cx.noma_ambiguous++; } // (rerun with the host-built table: run_trials)
-        r.time_exit = dr.time_exit;
-        r.maxTime = prach_max_time(&c);
-        r.nSuccessUE = dr.nSuccess;
-        r.failedUEs = c.nUE - dr.nSuccess;
-        r.preambleTxCount = dr.ptcSum;
-        r.failCounts = dr.fcSum;
-        r.collisionPreambles = dr.collisionPreambles;
-        r.totalPreambleTxop = dr.totalPreambleTxop;
-        r.activeCheck = dr.activeCheck;
-        r.nAccessUE = nAccess[k];
-        r.continueFaliedUEs = dr.continueFailed;
-        r.finalSuccessUEs = dr.finalSuccess;
-        r.sumTimer = dr.sumTimer;
-        r.draws = dr.draws;
-        r.steps = steps_of(c, dr);
-        e->last.group_visits += dr.visits;
-        e->last.event_ues += dr.events;
-        if (c.variant == PRACH_VARIANT_NOMA_C && dr.nSuccess == c.nUE && dr.dbg[0] > 0) { // all UEs succeeded: NOMA.c:707-710 breaks there
-            r.time_exit = (int32_t)dr.dbg[0] - 1; // (r.steps: steps_of above)
-        }
-        { int rc = print_launch_diagnostics(e, c, dr, L, A, G, noma); if (rc != PRACH_OK) return rc; }
-        if (batch && dr.status == PRACH_ERR_INTERNAL && (dr.hard_error == 5 || dr.hard_error == 8 || dr.hard_error == 9) && !o.full_calendars) cal_overflow.push_back(idx[k]);
-        if (dr.status != PRACH_OK) continue;
-        // totalDelay is a FLOAT running sum in index order (Beta.c:186,193): exact in integer
-        // arithmetic while it stays below 2^24, otherwise replay the float additions on the host.
-        if (dr.sumTimer < (1ll << 24)) {
-            r.totalDelay = (float)dr.sumTimer;
-        } else {
-            timers.resize((size_t)c.nUE);
-            HIPCHK(hipMemcpy(timers.data(), A + L.timers, 4 * (size_t)c.nUE, hipMemcpyDeviceToHost));
-            float td_ = 0;
-            for (int i = 0; i < c.nUE; i++)
-                if (timers[i] != INT_MIN) td_ += (float)timers[i];
-            r.totalDelay = td_;
-        }
-        if (L.logs && cx.ue_logs && cx.ue_logs[idx[k]]) // (a timeline call lays out every trial's log; only the ones asked for cross the bus)
-            HIPCHK(hipMemcpy(cx.ue_logs[idx[k]], A + L.logs, sizeof(prach_ue_log) * (size_t)c.nUE, hipMemcpyDeviceToHost));
-    }
-    if (red_launched) { // (the next launch lays the arena out again and reuses the pinned job table)
-        HIPCHK(hipStreamSynchronize(e->stream));
-        float rms = 0;
-        HIPCHK(hipEventElapsedTime(&rms, e->red_ev0, e->red_ev1));
-        cx.red_ms += rms;
-    }
-    return PRACH_OK;
+        return PRACH_OK;
+    });
 }
 
 // A trial that a cluster launch could not finish — a per-subframe LDS capacity exceeded (PRACH_ERR_INTERNAL) or a workgroup
@@ -1237,6 +1227,126 @@ static int run_with_retries(prach_engine *e, CallCtx &cx, std::vector<int> todo,
             e->last.spin_timeouts += (int32_t)again.size();
         }
         todo.swap(again);
+    }
+    return PRACH_OK;
+}
+
+// ---- NOMA.c in the reference's OWN rand() stream (prach_noma_glibc.hip): activeUE's rejection loops make every stream position data dependent and its
+// libm calls must be the reference's — the bit-exact-vs-the-reference's-files mode, not the throughput mode.  Both forms lie in the arena like any launch.
+
+// The slot-by-slot form between the engine's two events: one launch per access slot, the slot's arrivals activated by the host between two launches with the
+// libm the reference links, from the host's copy `hs` of the window; the finishing kernel behind the last slot.  PRACH_ERR_STREAM: the window ran out.
+static int noma_glibc_slot_loop(prach_engine *e, const prach_cfg &c, const NomaGlibcLayout &L, const int32_t *hs) {
+    char *const A = e->arena, *const H = e->pinned;
+    const size_t ue = L.t[0].ue, ue_bytes = L.ue_bytes;
+    const int32_t *const sched = reinterpret_cast<const int32_t *>(H + L.t[0].sched);
+    uint64_t pos = 0;
+    for (int s = 0, t = 0, activeCheck = 0;; s++, t += c.accessTime) {
+        const int prevAC = activeCheck;
+        activeCheck = sched[s]; // NOMA.c:675-681
+        int rc = noma_glibc_stage_slot(L, c, hs, &pos, t, prevAC, activeCheck, H);
+        if (rc != PRACH_OK) return rc;
+        if (activeCheck > prevAC)
+            HIPCHK(hipMemcpyAsync(A + ue + ue_bytes * (size_t)prevAC, H + ue + ue_bytes * (size_t)prevAC, ue_bytes * (size_t)(activeCheck - prevAC), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(A + L.ctl, H + L.ctl, L.ctl_bytes, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(launch_noma_glibc_slot(L, c, A, e->stream));
+        HIPCHK(hipMemcpyAsync(H + L.ctl, A + L.ctl, L.ctl_bytes, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        const NomaGlibcEnd end = noma_glibc_end(L, c, H, 0);
+        if (end.status != PRACH_OK) return end.status;
+        pos = end.pos;
+        if (end.done) break;
+    }
+    HIPCHK(launch_noma_glibc_finish(L, A, e->stream));
+    return PRACH_OK;
+}
+
+// One launch over the trials idx[0..m) with the windows lens[]: the single-launch form (side by side, one workgroup each, activeUE on the device) or,
+// `slots`, one trial slot by slot.  A trial whose window ran out is appended to `again`; one with a value inside the device math library's error band
+// (prach_noma_act.h: a few percent of the trials) to `ambiguous`.  The others are finished: prach_result (saveResult, NOMA.c:618-625) from the control
+// blocks, the logs that were asked for straight from the arena, the call's reduction over what the finishing kernel left there.
+static int noma_glibc_launch(prach_engine *e, CallCtx &cx, const int *idx, int m, const unsigned long long *lens, bool slots, std::vector<int> &again, std::vector<int> &ambiguous) {
+    const NomaGlibcLayout L = noma_glibc_layout(cx.cfgs, idx, m, lens, cx.ue_logs, slots);
+    if (L.end > e->mem_budget && m > 1) { // (as run_group: several launches instead of one; one trial alone always runs)
+        int rc = noma_glibc_launch(e, cx, idx, m / 2, lens, slots, again, ambiguous);
+        return rc != PRACH_OK ? rc : noma_glibc_launch(e, cx, idx + m / 2, m - m / 2, lens + m / 2, slots, again, ambiguous);
+    }
+    { int rc = ensure_arena(e, L.end); if (rc != PRACH_OK) return rc; }
+    { int rc = ensure_pinned(e, L.staged_end); if (rc != PRACH_OK) return rc; }
+    char *const A = e->arena, *const H = e->pinned;
+    std::vector<int32_t> nAccess((size_t)m, 0), hs; // hs: the slot form's host copy of the window
+    if (slots) { hs.resize((size_t)lens[0]); prach_glibc_stream((uint32_t)cx.cfgs[idx[0]].seed, cx.cfgs[idx[0]].stream_offset, lens[0], hs.data()); }
+    noma_glibc_stage(L, cx.cfgs, idx, A, H, nAccess.data());
+    e->last.launches++;
+    HIPCHK(hipMemcpyAsync(A, H, L.staged_end, hipMemcpyHostToDevice, e->stream));
+    if (slots) HIPCHK(hipMemcpyAsync(A + L.t[0].stream, hs.data(), 4 * hs.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipEventRecord(e->ev0, e->stream));
+    if (slots) {
+        int rc = noma_glibc_slot_loop(e, cx.cfgs[idx[0]], L, hs.data());
+        if (rc == PRACH_ERR_STREAM) { again.push_back(idx[0]); return PRACH_OK; }
+        if (rc != PRACH_OK) return rc;
+    } else HIPCHK(launch_noma_glibc_trials(L, A, e->stream));
+    HIPCHK(hipEventRecord(e->ev1, e->stream));
+    HIPCHK(hipMemcpyAsync(H + L.ctl, A + L.ctl, L.ctl_bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    cx.kernel_ms += ms;
+    static const DevResult no_result{};
+    std::vector<TrialLayout> tl((size_t)m, TrialLayout{});
+    std::vector<JobSrc> acc;
+    std::vector<int> ok;
+    for (int j = 0; j < m; j++) {
+        const int st = noma_glibc_end(L, cx.cfgs[idx[j]], H, j).status;
+        if (st == PRACH_ERR_STREAM) again.push_back(idx[j]);
+        else if (st == NOMA_GLIBC_AMBIGUOUS_RC) ambiguous.push_back(idx[j]);
+        else if (st != PRACH_OK) return st;
+        else {
+            ok.push_back(j);
+            tl[j].timers = L.t[j].timers; tl[j].ptc = L.t[j].ptc; // (all that dist_fill_job reads)
+            if (cx.red) acc.push_back(JobSrc{cx.cfgs[idx[j]], tl[j], no_result, A, cx.group_of(idx[j]), 0, false});
+        }
+    }
+    return reduce_accepted(e, cx, acc, [&]() -> int {
+        for (int j : ok) {
+            const prach_cfg &c = cx.cfgs[idx[j]];
+            const NomaGlibcEnd t = noma_glibc_end(L, c, H, j);
+            prach_result &r = cx.results[idx[j]];
+            std::memset(&r, 0, sizeof(r));
+            r.status = PRACH_OK; r.time_exit = t.time_exit; r.maxTime = 10000; r.steps = t.steps; r.draws = t.pos;
+            r.nSuccessUE = r.finalSuccessUEs = t.nSuccess; r.failedUEs = c.nUE - t.nSuccess; r.activeCheck = t.activeCheck; r.nAccessUE = nAccess[j];
+            r.preambleTxCount = t.nTxP; r.failCounts = t.failed; r.sumTimer = t.delay; r.totalDelay = (float)t.delay;
+            if (L.t[j].logs) HIPCHK(hipMemcpy(cx.ue_logs[idx[j]], A + L.t[j].logs, sizeof(prach_ue_log) * (size_t)c.nUE, hipMemcpyDeviceToHost));
+        }
+        return PRACH_OK;
+    });
+}
+
+// The NOMA.c trials `todo` of a call in the reference's stream: the single-launch form, then slot by slot what it handed on.  The window of a trial, in
+// either form, is 48, 192, 768, 3072 values per UE (1.2 GB at nUE = 100 000 at most); a trial that has used up the fourth ends the call with PRACH_ERR_STREAM.
+static int run_noma_glibc(prach_engine *e, CallCtx &cx, std::vector<int> todo) {
+    std::vector<int> ambiguous;
+    if (e->opt_noma_ambiguity_test && !e->opt_noma_host_activation) ambiguous.swap(todo); // (test hook: as if the kernel had found a value inside the band in every trial)
+    for (const bool slots : {e->opt_noma_host_activation != 0, true}) {
+        for (int attempt = 0; !todo.empty(); attempt++) {
+            if (attempt >= 4) return PRACH_ERR_STREAM;
+            std::vector<unsigned long long> lens;
+            for (int k : todo) lens.push_back(((unsigned long long)cx.cfgs[k].nUE * 48ull + (1ull << 18)) << (2 * attempt));
+            std::vector<int> again;
+            const int m = (int)todo.size(), per = slots ? 1 : m; // (slot by slot: one trial at a time)
+            for (int j = 0; j < m; j += per) {
+                int rc = noma_glibc_launch(e, cx, todo.data() + j, per, lens.data() + j, slots, again, ambiguous);
+                if (rc != PRACH_OK) return rc;
+            }
+            todo.swap(again);
+        }
+        for (int k : ambiguous) {
+            cx.noma_ambiguous++;
+            e->last.fallback_trials++;
+            if (std::getenv("PRACH_VERBOSE")) std::fprintf(stderr, "[prach] NOMA.c trial nUE=%d in the reference's stream: a value inside the device libm's error band, rerun with host-side activation\n", cx.cfgs[k].nUE);
+        }
+        todo.swap(ambiguous);
+        ambiguous.clear();
     }
     return PRACH_OK;
 }
@@ -1406,66 +1516,12 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
         int rc = reduction_begin(e, cx, n);
         if (rc != PRACH_OK) return rc;
     }
-    // NOMA.c in the reference's OWN rand() stream: activeUE's rejection loops make every stream position data dependent and its libm
-    // calls must be the reference's, so the arrivals are activated on the host between device steps (prach_noma_glibc.hip): one trial
-    // at a time, one launch per access slot — the bit-exact-vs-the-reference's-files mode, not the throughput mode
-    {
-        std::vector<int> todo;
+    { // NOMA.c in the reference's OWN rand() stream (prach_noma_glibc.hip)
+        std::vector<int> idx;
         for (int k = 0; k < n; k++)
-            if (cfgs[k].variant == PRACH_VARIANT_NOMA_C && cfgs[k].rng_mode == PRACH_RNG_GLIBC) todo.push_back(k);
-        // window of trial k at retry level a: 48, 192, 768, 3072 values per UE (1.2 GB at nUE = 100 000 at most, then PRACH_ERR_STREAM)
-        auto window = [&](int k, int a) { return ((unsigned long long)cfgs[k].nUE * 48ull + (1ull << 18)) << (2 * a); };
-        // slot by slot, the arrivals activated by the host with the reference's libm (prach_noma_glibc.hip): the exact form a trial falls back to
-        auto host_form = [&](int k) -> int {
-            int rc = PRACH_ERR_STREAM;
-            for (int attempt = 0; attempt < 4 && rc == PRACH_ERR_STREAM; attempt++) {
-                const unsigned long long len = window(k, attempt);
-                std::vector<int32_t> hs((size_t)len);
-                prach_glibc_stream((uint32_t)cfgs[k].seed, cfgs[k].stream_offset, len, hs.data());
-                DistSink sk{};
-                if (cx.dist_spec()) sk = cx.sink(k);
-                rc = run_noma_glibc_trial(e->stream, cfgs[k], hs.data(), len, &results[k], ue_logs ? ue_logs[k] : nullptr, &cx.kernel_ms, cx.dist_spec() ? &sk : nullptr);
-                e->last.launches++;
-            }
-            return rc;
-        };
-        if (e->opt_noma_host_activation) {
-            for (int k : todo) { int rc = host_form(k); if (rc != PRACH_OK) return rc; }
-            todo.clear();
-        }
-        // the single-launch form: every trial of the call (the seeds of a sweep point) side by side, one workgroup each, activeUE on the device; a value
-        // inside the device math library's error band (prach_noma_act.h: a few percent of the trials) sends that trial to the host form
-        for (int attempt = 0; !todo.empty(); attempt++) {
-            if (attempt >= 4) return PRACH_ERR_STREAM;
-            const int m = (int)todo.size();
-            std::vector<const prach_cfg *> pc(m);
-            std::vector<unsigned long long> lens(m);
-            std::vector<prach_result *> pr(m);
-            std::vector<prach_ue_log *> pl(m);
-            std::vector<int> rcs(m, PRACH_ERR_INTERNAL);
-            std::vector<DistSink> sinks;
-            if (cx.dist_spec()) for (int j = 0; j < m; j++) sinks.push_back(cx.sink(todo[j]));
-            for (int j = 0; j < m; j++) { pc[j] = &cfgs[todo[j]]; lens[j] = window(todo[j], attempt); pr[j] = &results[todo[j]]; pl[j] = ue_logs ? ue_logs[todo[j]] : nullptr; }
-            if (e->opt_noma_ambiguity_test) std::fill(rcs.begin(), rcs.end(), NOMA_GLIBC_AMBIGUOUS_RC); // (test hook: as if the kernel had found a value inside the band)
-            else {
-                int rc = run_noma_glibc_batch(e->stream, pc.data(), m, lens.data(), pr.data(), pl.data(), &cx.kernel_ms, rcs.data(), cx.dist_spec() ? sinks.data() : nullptr);
-                e->last.launches++;
-                if (rc != PRACH_OK) return rc;
-            }
-            std::vector<int> again;
-            for (int j = 0; j < m; j++) {
-                const int k = todo[j];
-                if (rcs[j] == PRACH_OK) continue;
-                if (rcs[j] == PRACH_ERR_STREAM) { again.push_back(k); continue; }
-                if (rcs[j] != NOMA_GLIBC_AMBIGUOUS_RC) return rcs[j];
-                cx.noma_ambiguous++;
-                e->last.fallback_trials++;
-                if (std::getenv("PRACH_VERBOSE")) std::fprintf(stderr, "[prach] NOMA.c trial nUE=%d in the reference's stream: a value inside the device libm's error band, rerun with host-side activation\n", cfgs[k].nUE);
-                int rc = host_form(k);
-                if (rc != PRACH_OK) return rc;
-            }
-            todo.swap(again);
-        }
+            if (cfgs[k].variant == PRACH_VARIANT_NOMA_C && cfgs[k].rng_mode == PRACH_RNG_GLIBC) idx.push_back(k);
+        int rc = run_noma_glibc(e, cx, idx);
+        if (rc != PRACH_OK) return rc;
     }
     { // NOMA.c variant (Philox): its own kernel, G workgroups per trial like the production kernel
         std::vector<int> idx;
@@ -1804,7 +1860,7 @@ int prach_run_trials_pick(prach_engine *e, const prach_cfg *cfgs, int n, prach_r
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
-// a trial the NOMA menu's device calls take: NOMA.c with Philox (in the reference's stream a trial can finish on the host slot by slot and leave no device record)
+// a trial the NOMA menu's device calls take: NOMA.c with Philox (the reference-stream launches, run_noma_glibc, lay out no job the menu's kernels read: not wired to the menu)
 static bool noma_device_cfg(const prach_cfg &c) { return c.variant == PRACH_VARIANT_NOMA_C && c.rng_mode != PRACH_RNG_GLIBC; }
 
 int prach_run_trials_noma_census(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_xtab_spec *spec,

@@ -13,6 +13,9 @@
 //   * noma_glibc_slot_kernel: one launch per access slot, the slot's arrivals activated on the HOST between two launches with the libm the
 //     reference links (prach_noma_activation_stream) — bit-identical by construction, 2000 launches and host round trips per trial; with the same
 //     list of live UEs (kept on the device from launch to launch) 148 ms at nUE = 100 000, one trial at a time.
+// Behind either form noma_glibc_finish_kernel leaves what every trial kernel of the library leaves in the arena: timers, preamble counts, the log records
+// that were asked for, the sums of the result.  The host side at the bottom is a layout of one launch in the engine's arena, the blocks of its staged
+// region and the launches; memory, copies, events, retries and results are the engine's (prach_engine.hip: run_noma_glibc).
 // This is the bit-exact-vs-the-reference's-own-files mode of config 4, not the throughput mode (Philox, prach_noma.hip).  Reference:
 // NOMA.c:131-192 (activeUE), :194-324 / :325-447 (grouping), :449-498 (msg2Results), :499-546 (resourceRequestAllocation), :665-711 (the time step).
 #include "prach_device.h"
@@ -22,10 +25,8 @@
 #pragma clang fp contract(off) // (a * b + c stays two roundings, as in the reference built for baseline x86-64)
 
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 #include <limits.h>
-#include <vector>
 
 namespace prach {
 
@@ -38,11 +39,14 @@ struct alignas(8) NUe { // UserInfo (NOMA.c:8-39), the fields the simulation rea
 };
 static_assert(sizeof(NUe) == 80, "NUe layout");
 
+struct FinSums { long long delay; int nTxP, failed; }; // noma_glibc_finish_kernel: saveResult's sums (NOMA.c:618-625), zero until it has run
+
 struct SlotCtl { // per-launch control block (device memory, mirrored on the host)
     unsigned long long pos;     // in: stream position behind this slot's activations; out: position behind the slot
     unsigned long long stream_len;
     int time, activeCheck, nSuccess, exit_time; // exit_time >= 0: every UE has succeeded at that subframe (NOMA.c:707-710)
     int status, pad;
+    FinSums fin;
 };
 
 struct NParams {
@@ -337,7 +341,7 @@ __global__ __launch_bounds__(WG_THREADS) void noma_glibc_slot_kernel(NUe *ue_, c
 // no start moves (the first arrival's start is right from the beginning, so every round fixes at least one more: two or three rounds in practice).
 // Gains come from the device's math library: prach_noma_act.h flags every value inside its error band, the slot's comparisons do the same —
 // either ends the trial with NOMA_GLIBC_AMBIGUOUS and the host runs it again slot by slot with its own libm.
-struct TrialCtl { unsigned long long pos, steps; int nSuccess, time_exit, status, activeCheck; };
+struct TrialCtl { unsigned long long pos, steps; int nSuccess, time_exit, status, activeCheck; FinSums fin; };
 struct TrialArgs { NUe *ue; const int *stream; const int *sched; int *live; TrialCtl *ctl; unsigned long long slen; float cell_radius; int pad; NParams K; };
 
 // (one workgroup per trial: the trials of a call — the seeds of one sweep point — run side by side)
@@ -419,237 +423,178 @@ __global__ __launch_bounds__(WG_THREADS) void noma_glibc_trial_kernel(const Tria
     }
 }
 
-} // namespace
+// What a finished trial leaves behind, as prach::noma_kernel's dump does (prach_noma.hip): timers and ptc for the call's reduction, the 64-byte log record
+// of every UE where a log region was laid out, saveResult's sums (NOMA.c:618-625) in the trial's control block.  Behind the simulation kernel on the same
+// stream; blockIdx.y: the trial.  A trial that did not end with PRACH_OK (window too small, a value inside the error band) leaves nothing.
+struct FinishArgs { const NUe *ue; const int *status; FinSums *sums; int *timers, *ptc; prach_ue_log *logs; int nUE, pad; };
+constexpr int FIN_THREADS = 256;
 
-// saveResult (NOMA.c:618-625) and the logged fields from the final UE records
-static void noma_glibc_finish(const prach_cfg &c, const NUe *hue, unsigned long long pos, int nSuccess, int time_exit, unsigned long long steps, int activeCheck,
-                              int32_t nAccess, prach_result *res, prach_ue_log *logs, const DistSink *sink) {
-    const int nUE = c.nUE;
-    if (sink) { // prach_run_trials_dist: this trial's successful UEs, as prach_dist_accumulate_logs counts them from the log written below
-        for (int i = 0; i < nUE; i++)
-            if (hue[i].RA == 1) prach_internal_dist_add_ue(sink->spec, sink->d, sink->delay_hist, sink->ptc_hist, hue[i].timer, hue[i].nTxPreamble);
-        sink->d->trials++;
-        sink->d->ues += (uint64_t)nUE;
-    }
+__global__ __launch_bounds__(FIN_THREADS) void noma_glibc_finish_kernel(const FinishArgs *__restrict__ args) {
+    const FinishArgs &A = args[blockIdx.y];
+    if (*(const NG int *)A.status != PRACH_OK) return;
+    const NG NUe *const ue = (const NG NUe *)A.ue;
+    NG int *const timers = (NG int *)A.timers, *const ptc = (NG int *)A.ptc;
+    PRACH_G v4i_t *const logs = (PRACH_G v4i_t *)A.logs;
+    const int nUE = A.nUE;
     long long delay = 0;
     int nTxP = 0, failed = 0;
-    for (int i = 0; i < nUE; i++) {
-        const NUe &u = hue[i];
-        if (u.RA == 1) { delay += u.timer; nTxP += u.nTxPreamble; }
+    for (int i = blockIdx.x * FIN_THREADS + threadIdx.x; i < nUE; i += gridDim.x * FIN_THREADS) {
+        const NG NUe &u = ue[i];
+        const bool ra = u.RA == 1;
+        if (ra) { delay += u.timer; nTxP += u.nTxPreamble; }
         if (u.RaFailed) failed++;
+        timers[i] = ra ? u.timer : INT_MIN;
+        ptc[i] = u.nTxPreamble;
         if (logs) { // (the field mapping of prach_noma.hip's dump)
-            prach_ue_log &o = logs[i];
+            prach_ue_log o;
             o.idx = i; o.timer = u.timer; o.active = u.active; o.txTime = u.txTime; o.firstTxTime = u.firstTxTime; o.secondTxTime = u.secondTxTime;
             o.nowBackoff = u.nowBackoff; o.preamble = u.preamble; o.preambleChange = u.sector; o.rarWindow = u.rarWindow; o.maxRarCounter = u.msg1ReTx;
             o.preambleTxCounter = u.nTxPreamble; o.msg2Flag = u.msg2; o.connectionRequest = u.msg3Wait; o.msg4Flag = u.RA;
             o.failCount = u.RaFailed | (u.msg3Faile << 16);
+            store_log(logs, i, o);
         }
     }
-    std::memset(res, 0, sizeof(*res));
-    res->status = PRACH_OK;
-    res->time_exit = time_exit;
-    res->maxTime = 10000;
-    res->nSuccessUE = nSuccess;
-    res->failedUEs = nUE - nSuccess;
-    res->preambleTxCount = nTxP;
-    res->failCounts = failed;
-    res->activeCheck = activeCheck;
-    res->nAccessUE = nAccess;
-    res->finalSuccessUEs = nSuccess;
-    res->sumTimer = delay;
-    res->totalDelay = (float)delay;
-    res->draws = pos;
-    res->steps = steps;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) delay += __shfl_down(delay, d);
+    nTxP = wave_sum(nTxP); failed = wave_sum(failed);
+    if ((threadIdx.x & 63) == 0) {
+        PRACH_G FinSums *const s = (PRACH_G FinSums *)A.sums;
+        gadd(&s->delay, delay); gadd(&s->nTxP, nTxP); gadd(&s->failed, failed);
+    }
 }
 
-// One NOMA_C trial in the reference's rand() stream.  `hstream`: the host copy of the window [stream_offset, +len) (prach_glibc_stream).
-// Returns PRACH_OK, PRACH_ERR_STREAM (window too small: the caller retries with a larger one) or a device error.
-// This is the slot-by-slot form (the arrivals activated by the host between the launches); run_noma_glibc_batch below is the single-launch form.
-int run_noma_glibc_trial(hipStream_t stream, const prach_cfg &c, const int32_t *hstream, unsigned long long len, prach_result *res, prach_ue_log *logs,
-                         double *kernel_ms, const DistSink *sink) {
-#define NHIP(expr)                                                                                                            \
-    do {                                                                                                                      \
-        hipError_t e_ = (expr);                                                                                               \
-        if (e_ != hipSuccess) {                                                                                               \
-            std::fprintf(stderr, "[prach] HIP error %s at %s:%d: %s\n", hipGetErrorName(e_), __FILE__, __LINE__, hipGetErrorString(e_)); \
-            rc = PRACH_ERR_DEVICE;                                                                                            \
-            goto done;                                                                                                        \
-        }                                                                                                                     \
-    } while (0)
-    int rc = PRACH_OK;
-    const int nUE = c.nUE, aT = c.accessTime, maxTime = 10000;
-    const int stop = (c.max_steps > 0 && c.max_steps < maxTime) ? c.max_steps : maxTime;
-    NUe *d_ue = nullptr;
-    int *d_stream = nullptr;
-    SlotCtl *d_ctl = nullptr, *h_ctl = nullptr;
-    int *d_live = nullptr;
-    LiveState *d_ls = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::vector<NUe> hue((size_t)nUE);
-    std::vector<int32_t> sched((size_t)(maxTime / aT + 2), nUE);
-    int32_t nAccess = 0;
-    NParams K{nUE, c.nPreamble, c.backoff, c.nGrantUL, c.maxRarWindow, c.maxMsg2TxCount, aT, stop, (c.flags & PRACH_FLAG_NOMA_NONSECTOR) ? 1 : 0};
-    unsigned long long pos = 0;
-    int activeCheck = 0, time_exit = stop, nSuccess = 0;
-    unsigned long long steps = 0;
-    prach_arrival_schedule(&c, sched.data(), (int)sched.size(), &nAccess);
-    std::memset(hue.data(), 0, sizeof(NUe) * (size_t)nUE);
-    for (int i = 0; i < nUE; i++) hue[i].sector = -1; // NOMA.c:651-655: everything 0, sector -1
-    NHIP(hipMalloc(reinterpret_cast<void **>(&d_ue), sizeof(NUe) * (size_t)nUE));
-    NHIP(hipMalloc(reinterpret_cast<void **>(&d_stream), 4 * (size_t)(len + 2)));
-    NHIP(hipMalloc(reinterpret_cast<void **>(&d_ctl), sizeof(SlotCtl)));
-    NHIP(hipMalloc(reinterpret_cast<void **>(&d_live), 4 * (size_t)nUE + 64));
-    NHIP(hipMalloc(reinterpret_cast<void **>(&d_ls), sizeof(LiveState)));
-    NHIP(hipMemsetAsync(d_ls, 0, sizeof(LiveState), stream));
-    NHIP(hipHostMalloc(reinterpret_cast<void **>(&h_ctl), sizeof(SlotCtl), hipHostMallocDefault));
-    NHIP(hipEventCreate(&ev0));
-    NHIP(hipEventCreate(&ev1));
-    NHIP(hipMemcpyAsync(d_ue, hue.data(), sizeof(NUe) * (size_t)nUE, hipMemcpyHostToDevice, stream));
-    NHIP(hipMemcpyAsync(d_stream, hstream, 4 * (size_t)len, hipMemcpyHostToDevice, stream));
-    NHIP(hipEventRecord(ev0, stream));
-    for (int s = 0, t = 0; t < stop; s++, t += aT) {
-        // NOMA.c:675-686: this access slot's arrivals, activated on the host in stream order (index order)
-        const int prevAC = activeCheck;
-        activeCheck = sched[s];
-        for (int i = prevAC; i < activeCheck; i++) {
-            NUe &u = hue[i];
-            int32_t pre0, sec;
-            const int arc = prach_noma_activation_stream(&c, hstream, reinterpret_cast<uint64_t *>(&pos), len, &pre0, &sec, &u.gain, &u.lgain);
-            if (arc != PRACH_OK) { rc = arc; goto done; }
-            u.active = 1; u.preamble = pre0; u.nTxPreamble = 1; u.txTime = t + 1; u.timer = 0; u.rarWindow = 0; u.msg1ReTx = 0; u.nowBackoff = 0;
-            u.firstTxTime = t + 1; u.sector = sec;
-        }
-        if (activeCheck > prevAC)
-            NHIP(hipMemcpyAsync(d_ue + prevAC, hue.data() + prevAC, sizeof(NUe) * (size_t)(activeCheck - prevAC), hipMemcpyHostToDevice, stream));
-        h_ctl->pos = pos; h_ctl->stream_len = len; h_ctl->time = t; h_ctl->activeCheck = activeCheck; h_ctl->nSuccess = 0; h_ctl->exit_time = -1;
-        h_ctl->status = PRACH_OK; h_ctl->pad = 0;
-        NHIP(hipMemcpyAsync(d_ctl, h_ctl, sizeof(SlotCtl), hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(noma_glibc_slot_kernel, dim3(1), dim3(WG_THREADS), 0, stream, d_ue, d_stream, d_ctl, d_live, d_ls, K);
-        NHIP(hipGetLastError());
-        NHIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(SlotCtl), hipMemcpyDeviceToHost, stream));
-        NHIP(hipStreamSynchronize(stream));
-        if (h_ctl->status != PRACH_OK) { rc = h_ctl->status; goto done; }
-        pos = h_ctl->pos;
-        nSuccess = h_ctl->nSuccess;
-        if (h_ctl->exit_time >= 0) { time_exit = h_ctl->exit_time; steps = (unsigned long long)h_ctl->exit_time + 1; break; }
-        steps = (unsigned long long)std::min(t + aT, stop);
-    }
-    NHIP(hipEventRecord(ev1, stream));
-    NHIP(hipMemcpyAsync(hue.data(), d_ue, sizeof(NUe) * (size_t)nUE, hipMemcpyDeviceToHost, stream));
-    NHIP(hipStreamSynchronize(stream));
-    {
-        float ms = 0;
-        NHIP(hipEventElapsedTime(&ms, ev0, ev1));
-        if (kernel_ms) *kernel_ms += ms;
-        noma_glibc_finish(c, hue.data(), pos, nSuccess, time_exit, steps, activeCheck, nAccess, res, logs, sink);
-    }
-done:
-    if (d_ue) (void)hipFree(d_ue);
-    if (d_stream) (void)hipFree(d_stream);
-    if (d_ctl) (void)hipFree(d_ctl);
-    if (d_live) (void)hipFree(d_live);
-    if (d_ls) (void)hipFree(d_ls);
-    if (h_ctl) (void)hipHostFree(h_ctl);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    return rc;
-#undef NHIP
-}
+} // namespace
 
-// The single-launch form for the NOMA_C trials of a call (the seeds of one sweep point): one workgroup per trial in ONE launch, the stream windows
-// [stream_offset, + lens[j]) generated on the device before it.  rcs[j]: PRACH_OK (res[j] / logs[j] filled), PRACH_ERR_STREAM (window too small),
-// NOMA_GLIBC_AMBIGUOUS_RC (a value inside the device math library's error band: run that trial slot by slot, run_noma_glibc_trial) or a device error.
-int run_noma_glibc_batch(hipStream_t stream, const prach_cfg *const *cfgs, int n, const unsigned long long *lens, prach_result *const *res, prach_ue_log *const *logs,
-                         double *kernel_ms, int *rcs, const DistSink *sinks) {
-#define BHIP(expr)                                                                                                            \
-    do {                                                                                                                      \
-        hipError_t e_ = (expr);                                                                                               \
-        if (e_ != hipSuccess) {                                                                                               \
-            std::fprintf(stderr, "[prach] HIP error %s at %s:%d: %s\n", hipGetErrorName(e_), __FILE__, __LINE__, hipGetErrorString(e_)); \
-            rc = PRACH_ERR_DEVICE;                                                                                            \
-            goto done;                                                                                                        \
-        }                                                                                                                     \
-    } while (0)
-    int rc = PRACH_OK;
+// ---- host side: where a launch lies in the engine's arena, its argument blocks, its launches.  Memory, copies, events and errors are the engine's. ----
+
+static NParams params_of(const prach_cfg &c) {
     const int maxTime = 10000;
-    char *dbuf = nullptr, *hbuf = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct Off { size_t seeds, sched, ue, stream, live; size_t nsched, nchunks; int32_t nAccess; };
-    std::vector<Off> off((size_t)n);
-    std::vector<NUe> hue;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    // staged prefix (one copy): argument blocks, control blocks (zeroed), stream seeds, arrival tables; then the per-trial arrays
-    size_t o = up(sizeof(TrialArgs) * (size_t)n);
-    const size_t octl = o; o = up(o + sizeof(TrialCtl) * (size_t)n);
-    const size_t ojobs = o; o = up(o + sizeof(StreamJob) * (size_t)n);
+    const int stop = (c.max_steps > 0 && c.max_steps < maxTime) ? c.max_steps : maxTime;
+    return NParams{c.nUE, c.nPreamble, c.backoff, c.nGrantUL, c.maxRarWindow, c.maxMsg2TxCount, c.accessTime, stop, (c.flags & PRACH_FLAG_NOMA_NONSECTOR) ? 1 : 0};
+}
+
+NomaGlibcLayout noma_glibc_layout(const prach_cfg *cfgs, const int *idx, int n, const unsigned long long *lens, prach_ue_log *const *ue_logs, bool slots) {
+    NomaGlibcLayout L;
+    L.slots = slots;
+    L.ue_bytes = sizeof(NUe);
+    L.t.resize((size_t)n);
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) / 256 * 256; return at; };
+    if (!slots) L.args = take(sizeof(TrialArgs) * (size_t)n);
+    L.ctl_bytes = slots ? sizeof(SlotCtl) : sizeof(TrialCtl) * (size_t)n;
+    L.ctl = take(L.ctl_bytes);
+    if (slots) L.live_state = take(sizeof(LiveState));
+    L.fin = take(sizeof(FinishArgs) * (size_t)n);
+    if (!slots) L.jobs = take(sizeof(StreamJob) * (size_t)n);
     for (int j = 0; j < n; j++) {
-        const prach_cfg &c = *cfgs[j];
-        off[j].nsched = (size_t)(maxTime / c.accessTime + 2);
-        off[j].nchunks = (size_t)((lens[j] + STREAM_CHUNK - 1) / STREAM_CHUNK);
-        off[j].seeds = o; o = up(o + 4 * 31 * (off[j].nchunks + 1));
-        off[j].sched = o; o = up(o + 4 * off[j].nsched);
+        const prach_cfg &c = cfgs[idx[j]];
+        NomaGlibcTrial &T = L.t[j];
+        T = NomaGlibcTrial{};
+        T.len = lens[j];
+        T.nsched = (size_t)(10000 / c.accessTime + 2);
+        T.sched = take(4 * T.nsched);
+        if (slots) T.ue = take(sizeof(NUe) * (size_t)c.nUE);
+        else { T.nchunks = (size_t)((T.len + STREAM_CHUNK - 1) / STREAM_CHUNK); T.seeds = take(4 * 31 * (T.nchunks + 1)); }
+        L.max_ue = std::max(L.max_ue, c.nUE);
     }
-    const size_t staged = o;
+    L.staged_end = o;
     for (int j = 0; j < n; j++) {
-        const prach_cfg &c = *cfgs[j];
-        off[j].ue = o; o = up(o + sizeof(NUe) * (size_t)c.nUE);
-        off[j].stream = o; o = up(o + 4 * (size_t)(lens[j] + 2));
-        off[j].live = o; o = up(o + 4 * (size_t)c.nUE + 64);
+        const size_t nUE = (size_t)cfgs[idx[j]].nUE;
+        NomaGlibcTrial &T = L.t[j];
+        if (!slots) T.ue = take(sizeof(NUe) * nUE);
+        T.stream = take(4 * (size_t)(T.len + 2));
+        T.live = take(4 * nUE + 64);
+        T.timers = take(4 * nUE);
+        T.ptc = take(4 * nUE);
+        if (ue_logs && ue_logs[idx[j]]) T.logs = take(sizeof(prach_ue_log) * nUE);
     }
-    BHIP(hipMalloc(reinterpret_cast<void **>(&dbuf), o));
-    BHIP(hipHostMalloc(reinterpret_cast<void **>(&hbuf), staged, hipHostMallocDefault));
-    BHIP(hipEventCreate(&ev0));
-    BHIP(hipEventCreate(&ev1));
-    std::memset(hbuf, 0, staged);
-    for (int j = 0; j < n; j++) {
-        const prach_cfg &c = *cfgs[j];
-        const int stop = (c.max_steps > 0 && c.max_steps < maxTime) ? c.max_steps : maxTime;
-        int32_t *sched = reinterpret_cast<int32_t *>(hbuf + off[j].sched);
-        for (size_t q = 0; q < off[j].nsched; q++) sched[q] = c.nUE;
-        prach_arrival_schedule(&c, sched, (int)off[j].nsched, &off[j].nAccess);
-        prach_internal_glibc_seeds((uint32_t)c.seed, c.stream_offset, off[j].nchunks, STREAM_CHUNK, reinterpret_cast<uint32_t *>(hbuf + off[j].seeds));
-        TrialArgs &A = reinterpret_cast<TrialArgs *>(hbuf)[j];
-        A.ue = reinterpret_cast<NUe *>(dbuf + off[j].ue); A.stream = reinterpret_cast<const int *>(dbuf + off[j].stream);
-        A.sched = reinterpret_cast<const int *>(dbuf + off[j].sched); A.live = reinterpret_cast<int *>(dbuf + off[j].live);
-        A.ctl = reinterpret_cast<TrialCtl *>(dbuf + octl) + j; A.slen = lens[j]; A.cell_radius = c.cellRadius; A.pad = 0;
-        A.K = NParams{c.nUE, c.nPreamble, c.backoff, c.nGrantUL, c.maxRarWindow, c.maxMsg2TxCount, c.accessTime, stop, (c.flags & PRACH_FLAG_NOMA_NONSECTOR) ? 1 : 0};
-        reinterpret_cast<StreamJob *>(hbuf + ojobs)[j] = StreamJob{reinterpret_cast<const unsigned *>(dbuf + off[j].seeds), reinterpret_cast<int *>(dbuf + off[j].stream), lens[j]};
-        rcs[j] = PRACH_ERR_INTERNAL;
+    L.end = o;
+    return L;
+}
+
+void noma_glibc_stage(const NomaGlibcLayout &L, const prach_cfg *cfgs, const int *idx, const char *A_, char *H, int32_t *nAccess) {
+    char *const A = const_cast<char *>(A_); // (device addresses for the blocks; nothing is dereferenced here)
+    std::memset(H, 0, L.staged_end);
+    for (size_t j = 0; j < L.t.size(); j++) {
+        const prach_cfg &c = cfgs[idx[j]];
+        const NomaGlibcTrial &T = L.t[j];
+        int32_t *sched = reinterpret_cast<int32_t *>(H + T.sched);
+        for (size_t q = 0; q < T.nsched; q++) sched[q] = c.nUE;
+        prach_arrival_schedule(&c, sched, (int)T.nsched, &nAccess[j]);
+        FinishArgs &F = reinterpret_cast<FinishArgs *>(H + L.fin)[j];
+        F.ue = reinterpret_cast<const NUe *>(A + T.ue); F.timers = reinterpret_cast<int *>(A + T.timers); F.ptc = reinterpret_cast<int *>(A + T.ptc);
+        F.logs = T.logs ? reinterpret_cast<prach_ue_log *>(A + T.logs) : nullptr; F.nUE = c.nUE;
+        if (L.slots) {
+            SlotCtl *const ctl = reinterpret_cast<SlotCtl *>(A + L.ctl);
+            F.status = &ctl->status; F.sums = &ctl->fin;
+            NUe *const hue = reinterpret_cast<NUe *>(H + T.ue);
+            for (int i = 0; i < c.nUE; i++) hue[i].sector = -1; // NOMA.c:651-655: everything 0, sector -1
+            continue;
+        }
+        TrialCtl *const ctl = reinterpret_cast<TrialCtl *>(A + L.ctl) + j;
+        F.status = &ctl->status; F.sums = &ctl->fin;
+        prach_internal_glibc_seeds((uint32_t)c.seed, c.stream_offset, T.nchunks, STREAM_CHUNK, reinterpret_cast<uint32_t *>(H + T.seeds));
+        TrialArgs &R = reinterpret_cast<TrialArgs *>(H + L.args)[j];
+        R.ue = reinterpret_cast<NUe *>(A + T.ue); R.stream = reinterpret_cast<const int *>(A + T.stream);
+        R.sched = reinterpret_cast<const int *>(A + T.sched); R.live = reinterpret_cast<int *>(A + T.live);
+        R.ctl = ctl; R.slen = T.len; R.cell_radius = c.cellRadius; R.pad = 0;
+        R.K = params_of(c);
+        reinterpret_cast<StreamJob *>(H + L.jobs)[j] = StreamJob{reinterpret_cast<const unsigned *>(A + T.seeds), reinterpret_cast<int *>(A + T.stream), T.len};
     }
-    BHIP(hipMemcpyAsync(dbuf, hbuf, staged, hipMemcpyHostToDevice, stream));
-    BHIP(hipEventRecord(ev0, stream));
-    {
-        unsigned long long max_n = 0;
-        for (int j = 0; j < n; j++) max_n = std::max(max_n, lens[j]);
-        BHIP(launch_glibc_stream_jobs(reinterpret_cast<const StreamJob *>(dbuf + ojobs), n, max_n, stream)); // every window, one launch
+}
+
+hipError_t launch_noma_glibc_finish(const NomaGlibcLayout &L, const char *A, hipStream_t stream) {
+    const unsigned tiles = (unsigned)std::min((L.max_ue + FIN_THREADS - 1) / FIN_THREADS, 1024);
+    hipLaunchKernelGGL(noma_glibc_finish_kernel, dim3(tiles, (unsigned)L.t.size()), dim3(FIN_THREADS), 0, stream, reinterpret_cast<const FinishArgs *>(A + L.fin));
+    return hipGetLastError();
+}
+
+// The single-launch form for the NOMA_C trials of a launch (the seeds of one sweep point): the stream windows [stream_offset, + len) generated on the
+// device, one workgroup per trial, the finishing kernel behind it.
+hipError_t launch_noma_glibc_trials(const NomaGlibcLayout &L, const char *A, hipStream_t stream) {
+    unsigned long long max_n = 0;
+    for (const NomaGlibcTrial &T : L.t) max_n = std::max(max_n, T.len);
+    hipError_t rc = launch_glibc_stream_jobs(reinterpret_cast<const StreamJob *>(A + L.jobs), (int)L.t.size(), max_n, stream); // every window, one launch
+    if (rc != hipSuccess) return rc;
+    hipLaunchKernelGGL(noma_glibc_trial_kernel, dim3((unsigned)L.t.size()), dim3(WG_THREADS), 0, stream, reinterpret_cast<const TrialArgs *>(A + L.args));
+    rc = hipGetLastError();
+    return rc != hipSuccess ? rc : launch_noma_glibc_finish(L, A, stream);
+}
+
+// The slot-by-slot form: NOMA.c:675-686, this access slot's arrivals, activated on the host in stream order (index order)
+int noma_glibc_stage_slot(const NomaGlibcLayout &L, const prach_cfg &c, const int32_t *hstream, uint64_t *pos, int t, int from, int to, char *H) {
+    NUe *const hue = reinterpret_cast<NUe *>(H + L.t[0].ue);
+    for (int i = from; i < to; i++) {
+        NUe &u = hue[i];
+        int32_t pre0, sec;
+        const int arc = prach_noma_activation_stream(&c, hstream, pos, L.t[0].len, &pre0, &sec, &u.gain, &u.lgain);
+        if (arc != PRACH_OK) return arc;
+        u.active = 1; u.preamble = pre0; u.nTxPreamble = 1; u.txTime = t + 1; u.timer = 0; u.rarWindow = 0; u.msg1ReTx = 0; u.nowBackoff = 0;
+        u.firstTxTime = t + 1; u.sector = sec;
     }
-    hipLaunchKernelGGL(noma_glibc_trial_kernel, dim3((unsigned)n), dim3(WG_THREADS), 0, stream, reinterpret_cast<const TrialArgs *>(dbuf));
-    BHIP(hipGetLastError());
-    BHIP(hipEventRecord(ev1, stream));
-    BHIP(hipMemcpyAsync(hbuf + octl, dbuf + octl, sizeof(TrialCtl) * (size_t)n, hipMemcpyDeviceToHost, stream));
-    BHIP(hipStreamSynchronize(stream));
-    {
-        float ms = 0;
-        BHIP(hipEventElapsedTime(&ms, ev0, ev1));
-        if (kernel_ms) *kernel_ms += ms;
+    SlotCtl &h = *reinterpret_cast<SlotCtl *>(H + L.ctl);
+    h = SlotCtl{};
+    h.pos = *pos; h.stream_len = L.t[0].len; h.time = t; h.activeCheck = to; h.exit_time = -1; h.status = PRACH_OK;
+    return PRACH_OK;
+}
+
+hipError_t launch_noma_glibc_slot(const NomaGlibcLayout &L, const prach_cfg &c, const char *A_, hipStream_t stream) {
+    char *const A = const_cast<char *>(A_);
+    const NomaGlibcTrial &T = L.t[0];
+    hipLaunchKernelGGL(noma_glibc_slot_kernel, dim3(1), dim3(WG_THREADS), 0, stream, reinterpret_cast<NUe *>(A + T.ue), reinterpret_cast<const int *>(A + T.stream),
+                       reinterpret_cast<SlotCtl *>(A + L.ctl), reinterpret_cast<int *>(A + T.live), reinterpret_cast<LiveState *>(A + L.live_state), params_of(c));
+    return hipGetLastError();
+}
+
+NomaGlibcEnd noma_glibc_end(const NomaGlibcLayout &L, const prach_cfg &c, const char *H, int j) {
+    if (!L.slots) {
+        const TrialCtl &s = reinterpret_cast<const TrialCtl *>(H + L.ctl)[j];
+        return NomaGlibcEnd{s.pos, s.steps, s.status == NOMA_GLIBC_AMBIGUOUS ? NOMA_GLIBC_AMBIGUOUS_RC : s.status, s.nSuccess, s.time_exit, s.activeCheck, s.fin.delay, s.fin.nTxP, s.fin.failed, true};
     }
-    for (int j = 0; j < n; j++) {
-        const prach_cfg &c = *cfgs[j];
-        const TrialCtl tc = reinterpret_cast<const TrialCtl *>(hbuf + octl)[j];
-        if (tc.status == NOMA_GLIBC_AMBIGUOUS) { rcs[j] = NOMA_GLIBC_AMBIGUOUS_RC; continue; }
-        if (tc.status != PRACH_OK) { rcs[j] = tc.status; continue; }
-        hue.resize((size_t)c.nUE);
-        BHIP(hipMemcpy(hue.data(), dbuf + off[j].ue, sizeof(NUe) * (size_t)c.nUE, hipMemcpyDeviceToHost));
-        noma_glibc_finish(c, hue.data(), tc.pos, tc.nSuccess, tc.time_exit, tc.steps, tc.activeCheck, off[j].nAccess, res[j], logs ? logs[j] : nullptr, sinks ? &sinks[j] : nullptr);
-        rcs[j] = PRACH_OK;
-    }
-done:
-    if (dbuf) (void)hipFree(dbuf);
-    if (hbuf) (void)hipHostFree(hbuf);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    return rc;
-#undef BHIP
+    const SlotCtl &s = *reinterpret_cast<const SlotCtl *>(H + L.ctl);
+    const int stop = params_of(c).stop, next = std::min(s.time + c.accessTime, stop);
+    const bool all = s.exit_time >= 0; // every UE has succeeded: NOMA.c:707-710 breaks there
+    return NomaGlibcEnd{s.pos, (unsigned long long)(all ? s.exit_time + 1 : next), s.status, s.nSuccess, all ? s.exit_time : stop, s.activeCheck, s.fin.delay, s.fin.nTxP, s.fin.failed, all || next == stop};
 }
 
 } // namespace prach

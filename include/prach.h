@@ -519,7 +519,7 @@ int prach_columns_tile_ues(void); /* UEs of one trial that one workgroup of prac
  * ONE RULE as in the xtab block: a NEGATIVE value is UNDEFINED, nothing is refused, nothing is clipped.  Every menu value of a trial fits int32
  * (csrc/prach_noma_menu.h states the bounds).  The channel gain is NOT in the menu: with Philox it is available per UE through prach_noma_activation_table,
  * in the reference's stream it exists only inside the launch.
- * PRACH_RNG_GLIBC trials of NOMA_C can finish on the host slot by slot and leave no device record: the device calls below refuse them, and
+ * PRACH_RNG_GLIBC trials of NOMA_C are not wired to the device calls below (their launches lay out no job the menu's kernels read): the calls refuse them, and
  * prach_run_trials with logs plus the host definitions serves them. */
 #define PRACH_NOMA_SERVED  1
 #define PRACH_NOMA_PENDING 2

@@ -83,7 +83,7 @@ def test_every_kernel_that_leaves_final_state(pkg, ob, eng, row):
         cfgs = [pkg.make_cfg(n, variant=v, rng_mode=row["rng"], seed=s, nGrantUL=12) for _, v, n, s in call]
         res, logs, d = run_checked(pkg, eng, cfgs, 4096)
         tm = eng.timing()
-        assert tm.dist_ms > 0 or row["name"] == "noma_glibc"  # (the reference-stream NOMA.c path finishes on the host)
+        assert tm.dist_ms > 0
         exp = [oracle_ues(ob, prog, v, n, row["rng"], s) for prog, v, n, s in call]
         assert d.same_as(bincount_dist(pkg, [e[0] for e in exp], 4096, 1, range(len(call)), len(call)))
         assert d.delay_sum.tolist() == [e[1] for e in exp] and d.ptc_sum.tolist() == [e[2] for e in exp]
@@ -189,6 +189,26 @@ def test_counted_once_noma_ambiguity_rerun(pkg):
         cfgs = [pkg.make_cfg(n, variant=pkg.VARIANT_NOMA_C, rng_mode=rng, seed=s) for n, s in ((2000, 1), (1000, 2))]
         t0, t1 = undisturbed_then(pkg, cfgs, 4096, lambda e: e.set("noma_ambiguity_test", 1))
         assert t1.fallback_trials >= 1
+
+
+def test_counted_once_noma_glibc_window_retry(pkg):
+    """NOMA.c in the reference's stream: a trial whose first window runs out (test_noma.py: RETRY_CASE) next to an ordinary one, two groups, in the
+    single-launch form, slot by slot, and rerun slot by slot after the test hook — each trial is given a job by the run that finished it."""
+    cfgs = [pkg.make_cfg(300, variant=pkg.VARIANT_NOMA_C, rng_mode=pkg.RNG_GLIBC, seed=3, cellRadius=35.01),
+            pkg.make_cfg(1000, variant=pkg.VARIANT_NOMA_C, rng_mode=pkg.RNG_GLIBC, seed=4)]
+    dists = []
+    for key in (None, "noma_host_activation", "noma_ambiguity_test"):
+        e = pkg.Engine(0)
+        try:
+            if key:
+                e.set(key, 1)
+            res, _, d = run_checked(pkg, e, cfgs, 4096, groups=[0, 1])  # (same_as dist_from_logs of the logs of the same call)
+            assert e.timing().dist_ms > 0 and res[0].draws == 566735
+        finally:
+            e.close()
+        assert int(d.trials.sum()) == 2 and d.trials.tolist() == [1, 1]
+        dists.append(d)
+    assert dists[1].same_as(dists[0]) and dists[2].same_as(dists[0])
 
 
 def test_counted_once_stream_retry(pkg):

@@ -379,6 +379,90 @@ def test_gpu_noma_glibc_small_cell_many_draws_per_ue(pkg, ob, engine, radius):
     assert res.nSuccessUE > 0 and pkg.format_noma_line(cfg, res) == ob.noma_format_line(ocfg, ores)
 
 
+RETRY_CASE = dict(nUE=300, cellRadius=35.01, seed=3, draws=566735)  # (the oracle's count; windows: 276 544 at attempt 0, 1 106 176 at attempt 1)
+_retry_oracle = []
+
+
+def retry_oracle(ob):
+    if not _retry_oracle:
+        ocfg = ob.make_noma_cfg(RETRY_CASE["nUE"], cellRadius=RETRY_CASE["cellRadius"])
+        ores, oues = ob.noma_run_trial(ocfg, ob.Rng(ob.RNG_GLIBC, RETRY_CASE["seed"]))
+        _retry_oracle.append((ores, np.frombuffer(oues, dtype=np.dtype([("i", np.int32, 16), ("g", np.float64)]))["i"].copy()))
+    return _retry_oracle[0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("host_activation", [0, 1])
+def test_gpu_noma_glibc_window_retry(pkg, ob, host_activation):
+    """A trial whose first stream window runs out, in both forms: 300 UEs just outside the exclusion zone draw 566 735 values, more than the attempt-0
+    window of nUE * 48 + 2^18 = 276 544 and fewer than the attempt-1 window, four times that — exactly one retry.  Every counter and every logged field
+    against the oracle."""
+    nUE, draws = RETRY_CASE["nUE"], RETRY_CASE["draws"]
+    assert nUE * 48 + 2 ** 18 == 276544 < draws < 4 * 276544 == 1106176
+    ores, oues = retry_oracle(ob)
+    assert ores.draws == draws
+    cfg = pkg.make_cfg(nUE, variant=pkg.VARIANT_NOMA_C, rng_mode=pkg.RNG_GLIBC, seed=RETRY_CASE["seed"], cellRadius=RETRY_CASE["cellRadius"])
+    e = pkg.Engine(0)
+    try:
+        e.set("noma_host_activation", host_activation)
+        (res,), (logs,) = e.run_trials([cfg], want_logs=True)
+        tm = e.timing()
+    finally:
+        e.close()
+    print(f"noma_host_activation {host_activation}: launches {tm.launches}, fallback_trials {tm.fallback_trials}, draws {res.draws}")
+    assert (res.status, res.nSuccessUE, res.sumTimer, res.preambleTxCount, res.failCounts, res.activeCheck, res.draws, res.time_exit, res.steps) == \
+           (0, ores.nSuccessUE, ores.delay, ores.nTxP, ores.raFailedUEs, ores.activeCheck, draws, ores.time_exit, ores.steps)
+    a = np.frombuffer(logs, dtype=np.int32).reshape(-1, 16)
+    diff = np.where((a != oues).any(axis=1))[0]
+    assert diff.size == 0, (diff[:5], a[diff[:3]], oues[diff[:3]])
+    if host_activation:
+        assert tm.launches >= 2  # (one per slot-form attempt)
+
+
+@pytest.mark.gpu
+def test_gpu_noma_glibc_mem_budget_split(pkg):
+    """Four reference-stream trials of about 1.75 MB of arena each under a 4 MB budget: the single launch is halved, results and logs stay byte for byte."""
+    cfgs = [pkg.make_cfg(2000, variant=pkg.VARIANT_NOMA_C, rng_mode=pkg.RNG_GLIBC, seed=s) for s in range(4)]
+    out = []
+    for budget in (0, 4):
+        e = pkg.Engine(0)
+        try:
+            if budget:
+                e.set("mem_budget_mb", budget)
+            res, logs = e.run_trials(cfgs, want_logs=True)
+            out.append(([bytes(r) for r in res], [bytes(l) for l in logs], e.timing().launches))
+        finally:
+            e.close()
+        assert all(r.status == 0 for r in res)
+    (res0, logs0, launches0), (res1, logs1, launches1) = out
+    assert res1 == res0 and logs1 == logs0
+    assert launches1 > launches0
+
+
+@pytest.mark.gpu
+def test_gpu_noma_glibc_shares_the_arena(pkg):
+    """One engine, one arena: a Philox Beta.c call, a reference-stream NOMA.c call in both forms, the Beta.c call again — nothing of one path survives into
+    the other."""
+    beta = [pkg.make_cfg(n, variant=pkg.VARIANT_BETA_C, rng_mode=pkg.RNG_PHILOX, seed=s) for n, s in ((3000, 1), (5000, 2))]
+    noma = [pkg.make_cfg(2000, variant=pkg.VARIANT_NOMA_C, rng_mode=pkg.RNG_GLIBC, seed=s) for s in (1, 2)]
+    e = pkg.Engine(0)
+    try:
+        res0, logs0 = e.run_trials(beta, want_logs=True)
+        first = [bytes(r) for r in res0], [bytes(l) for l in logs0]
+        nres, nlogs = e.run_trials(noma, want_logs=True)
+        res1, logs1 = e.run_trials(beta, want_logs=True)
+        e.set("noma_host_activation", 1)
+        nres2, nlogs2 = e.run_trials(noma, want_logs=True)
+        res2, logs2 = e.run_trials(beta, want_logs=True)
+    finally:
+        e.close()
+    assert all(r.status == 0 for r in list(res0) + list(nres) + list(nres2))
+    assert ([bytes(r) for r in res1], [bytes(l) for l in logs1]) == first
+    assert ([bytes(r) for r in res2], [bytes(l) for l in logs2]) == first
+    assert [bytes(l) for l in nlogs2] == [bytes(l) for l in nlogs]
+    assert [(r.nSuccessUE, r.sumTimer, r.draws, r.time_exit, r.steps) for r in nres2] == [(r.nSuccessUE, r.sumTimer, r.draws, r.time_exit, r.steps) for r in nres]
+
+
 @pytest.mark.gpu
 def test_gpu_noma_radius_just_above_the_exclusion_zone(pkg, ob, engine, capfd):
     """cellRadius = 35.01 is a valid configuration (NOMA.c:167-172 redraws the distance until it exceeds 35 m: ~1 750 draws per UE here): the device's redraw

@@ -31,7 +31,7 @@ import trace_ref
 #   cluster=1, glibc, maxRarWindow=12  batch_eligible false (batch_max_rar_window() = 11), compact: 10 000 + backoff + accessTime + 64 < 63 000
 #                                                                                 -> CLUSTER_REC_H8 (1), cluster_kernel<true, 1>  (kernel_limits.py: batch_rar12_glibc)
 #   legacy=1, glibc                    run_trials_impl: every trial on trial_kernel (cluster_size 0), trial_kernel<true>
-#   noma_host_activation=1, glibc      run_trials_impl: host_form, one noma_glibc_slot_kernel launch per access slot (no cluster launch: cluster_size 0)
+#   noma_host_activation=1, glibc      run_noma_glibc: noma_glibc_slot_loop, one noma_glibc_slot_kernel launch per access slot (no cluster launch: cluster_size 0)
 NEW_ROWS = [
     dict(name="cluster4_global_philox", kernels=["cluster_kernel<false, 0>"], program="beta", rng=1,
          opts=dict(cluster=4, lds_records=0), pin=dict(rec_mode=0, cluster_size=4)),
@@ -41,7 +41,7 @@ NEW_ROWS = [
          opts=dict(cluster=1), pin=dict(rec_mode=1, cluster_size=1), force=dict(maxRarWindow=12)),
     dict(name="legacy_glibc", kernels=["trial_kernel<true>"], program="beta", rng=0,
          opts=dict(legacy=1), pin=dict(cluster_size=0)),
-    dict(name="noma_glibc_slots", kernels=["noma_glibc_slot_kernel"], program="noma", rng=0,
+    dict(name="noma_glibc_slots", kernels=["noma_glibc_slot_kernel", "noma_glibc_finish_kernel"], program="noma", rng=0,
          opts=dict(noma_host_activation=1), pin=dict(cluster_size=0)),
 ]
 CUT_ROWS = [dict(r) for r in ROWS] + NEW_ROWS

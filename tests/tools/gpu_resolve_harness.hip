@@ -30,10 +30,9 @@
 
 #include <cstdlib>
 
-// host-side externals of prach_noma_glibc.hip's trial drivers, which this program never calls
+// host-side externals of prach_noma_glibc.hip's staging and launch functions, which this program never calls
 extern "C" int prach_arrival_schedule(const prach_cfg *, int32_t *, int, int32_t *) { abort(); }
 extern "C" int prach_noma_activation_stream(const prach_cfg *, const int32_t *, uint64_t *, uint64_t, int32_t *, int32_t *, double *, double *) { abort(); }
-extern "C" void prach_internal_dist_add_ue(const prach_dist_spec *, prach_dist *, uint64_t *, uint64_t *, int32_t, int32_t) { abort(); }
 extern "C" void prach_internal_glibc_seeds(uint32_t, uint64_t, uint64_t, uint64_t, uint32_t *) { abort(); }
 namespace prach {
 hipError_t launch_glibc_stream_jobs(const StreamJob *, int, unsigned long long, hipStream_t) { abort(); }

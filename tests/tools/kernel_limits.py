@@ -199,7 +199,7 @@ _case("ue_index_20bit", "out", "noma1048575", NOMA, 1048575, dict(max_steps=3000
 # of the UEs have arrived): heavily overloaded, so a per-subframe capacity may hand the trial on (LEAVES) — exact on whichever kernel.
 _case("ue_index_20bit", "in", "ue1048574_long", BETA, 1048574, dict(max_steps=4500), PHILOX, {}, dict(rec_mode=0, cluster_size=32), pre=dict(large=1, index_past=1 << 19))
 _case("ue_index_20bit", "in", "noma1048574_long", NOMA, 1048574, dict(max_steps=4500), PHILOX, {}, dict(cluster_size=16), pre=dict(large=1, index_past=1 << 19))
-# NOMA.c in the reference's stream: run_trials_impl hands every size to the single-launch form (run_noma_glibc_batch), which has no `small` / `solo` test in
+# NOMA.c in the reference's stream: run_noma_glibc hands every size to the single-launch form (noma_glibc_launch), which has no `small` / `solo` test in
 # front of it and no granule fields (one workgroup per trial): the same route on both sides, no cluster launch (cluster_size 0), one launch
 _case("ue_index_20bit", "in", "noma1048574_glibc", NOMA, 1048574, dict(max_steps=400), GLIBC, {}, dict(cluster_size=0, launches=1), pre=_BIG)
 _case("ue_index_20bit", "out", "noma1048575_glibc", NOMA, 1048575, dict(max_steps=400), GLIBC, {}, dict(cluster_size=0, launches=1), pre=_BIG)

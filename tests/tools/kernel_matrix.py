@@ -29,8 +29,8 @@ ROWS = [
          opts=dict(cluster=1), calls="one_call", random=False, pin=dict(cluster_size=1)),
     dict(name="noma4_philox", kernels=["noma_kernel", "noma_activation_kernel"], program="noma", rng=1,
          opts=dict(cluster=4), calls="one_call", random=False, pin=dict(cluster_size=4)),
-    # (the single-launch form: a trial it hands to the host-activated form is a fallback trial)
-    dict(name="noma_glibc", kernels=["noma_glibc_trial_kernel"], program="noma", rng=0,
+    # (the single-launch form: a trial it hands to the host-activated form is a fallback trial; the finishing kernel runs behind either form)
+    dict(name="noma_glibc", kernels=["noma_glibc_trial_kernel", "noma_glibc_finish_kernel"], program="noma", rng=0,
          opts=dict(), calls="one_call", random=False, pin=dict()),
     # trial_kernel has only the Philox xor3 table; a cheap row all the same (cluster_size 0: the one-workgroup trial kernel)
     dict(name="legacy_philox", kernels=["trial_kernel<false>"], program="beta", rng=1,
