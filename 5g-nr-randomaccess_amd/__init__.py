@@ -55,7 +55,7 @@ class PrachTiming(C.Structure):
                 ("launches", C.c_int32), ("workgroups", C.c_int32), ("updates", C.c_uint64),
                 ("cluster_size", C.c_int32), ("resident_limit", C.c_int32), ("fallback_trials", C.c_int32), ("spin_timeouts", C.c_int32),
                 ("rec_mode", C.c_int32), ("xcd_packed", C.c_int32), ("group_visits", C.c_uint64), ("event_ues", C.c_uint64),
-                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("noma_trace_ms", C.c_double), ("noma_summary_ms", C.c_double), ("noma_pick_ms", C.c_double), ("noma_census_ms", C.c_double), ("noma_columns_ms", C.c_double), ("columns_ms", C.c_double), ("pick_ms", C.c_double), ("xtab_ms", C.c_double), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
+                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("noma_timeline_ms", C.c_double), ("noma_trace_ms", C.c_double), ("noma_summary_ms", C.c_double), ("noma_pick_ms", C.c_double), ("noma_census_ms", C.c_double), ("noma_columns_ms", C.c_double), ("columns_ms", C.c_double), ("pick_ms", C.c_double), ("xtab_ms", C.c_double), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
                 ("sojourn_ms", C.c_double)]
 
 
@@ -720,6 +720,87 @@ class NomaTrace(_Reduction):
             return np.where(g > 0, (2 * p - o) / g, np.nan)
 
 
+NOMA_TIMELINE_SERIES = ("arrivals", "served", "dropped", "sojourn_sum", "timer_sum", "done")
+NOMA_TIMELINE_FIELDS = ("trials", "ues", "idle", "served", "dropped", "pending", "undefined", "restarted", "arrival_overflow", "done_overflow", "sojourn_sum", "timer_sum",
+                        "done_max")
+
+
+class PrachNomaTimelineSpec(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("bins", "bin_ms", "ngroups", "reserved")]
+
+
+class PrachNomaTimeline(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in NOMA_TIMELINE_FIELDS[:-1]] + [("done_max", C.c_int64)]
+
+
+class NomaTimeline(_Reduction):
+    """NOMA.c's timelines per sector of ``ngroups`` trial groups (include/prach.h, prach_noma_timeline): ``series`` [6, ngroups, 6 sectors, bins] as numpy uint64
+    in the order of NOMA_TIMELINE_SERIES, the layout of NomaTrace.series — and each series under its name as a [ngroups, 6, bins] view: ``arrivals``, ``served``,
+    ``dropped``, ``sojourn_sum`` and ``timer_sum`` by the bin of the UE's ARRIVAL, ``done`` by the bin of its completion — and ``scalars[field]``, one int64 array
+    of length ngroups per field of NOMA_TIMELINE_FIELDS.  The sector is the UE's own, also under FLAG_NOMA_NONSECTOR (where the trace has sector 0 only).
+    A sojourn HISTOGRAM by arrival time is the census's: run_trials_noma_census with rows ARRIVAL, cols SOJOURN, who served, read with NomaCensus.quantile."""
+    _FIELDS, _STRUCT, _MERGE, _PARAMS = NOMA_TIMELINE_FIELDS, PrachNomaTimeline, "prach_noma_timeline_merge", ("bins", "bin_ms")
+
+    def __init__(self, ngroups, bins, bin_ms=5):
+        import numpy as np
+        self.bins, self.bin_ms, self.ngroups = int(bins), int(bin_ms), int(ngroups)
+        self.series = np.zeros((6, self.ngroups, 6, self.bins), dtype=np.uint64)
+        self.arrivals, self.served, self.dropped, self.sojourn_sum, self.timer_sum, self.done = (self.series[q] for q in range(6))
+        self.scalars = {f: np.zeros(self.ngroups, dtype=np.int64) for f in NOMA_TIMELINE_FIELDS}
+        self.scalars["done_max"][:] = -1
+
+    def spec(self):
+        return PrachNomaTimelineSpec(self.bins, self.bin_ms, self.ngroups, 0)
+
+    def _arrays(self):
+        return [self.series[q] for q in range(6)]
+
+    def _scalar(self, f):
+        return self.scalars[f]
+
+    def _series(self, g=None):
+        """The six series — of group g, or of all groups — as the uint64_t *[6] the C side takes."""
+        return (C.POINTER(C.c_uint64) * 6)(*[(self.series[q] if g is None else self.series[q, g]).ctypes.data_as(C.POINTER(C.c_uint64)) for q in range(6)])
+
+    def _cargs(self, g):
+        return (self._series(g),)
+
+    def merge(self, other):
+        """Adds every group of ``other`` (same bins, bin_ms and ngroups) to the same group of this one (prach_noma_timeline_merge).  Returns self."""
+        if (self.bins, self.bin_ms, self.ngroups) != (other.bins, other.bin_ms, other.ngroups):
+            raise ValueError("timelines of different shapes do not merge")
+        for g in range(self.ngroups):
+            self.merge_group(g, other, g)
+        return self
+
+    def named(self, name, group, sector=None):
+        """Series ``name`` of one group — of one sector, or summed over the sectors: [bins] float64."""
+        import numpy as np
+        a = self.series[NOMA_TIMELINE_SERIES.index(name), group]
+        return (a.sum(axis=0) if sector is None else a[sector]).astype(np.float64)
+
+    def _ratio(self, num, den):
+        import numpy as np
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(den > 0, num / den, np.nan)
+
+    def served_ratio(self, g, sector=None):
+        """served / arrivals per arrival bin of one group (one sector, or all), as float64; NaN where nobody arrived."""
+        return self._ratio(self.named("served", g, sector), self.named("arrivals", g, sector))
+
+    def dropped_ratio(self, g, sector=None):
+        """dropped / arrivals per arrival bin; NaN where nobody arrived."""
+        return self._ratio(self.named("dropped", g, sector), self.named("arrivals", g, sector))
+
+    def mean_sojourn(self, g, sector=None):
+        """sojourn_sum / served per arrival bin, in ms: arrival to completion of the served UEs that arrived there; NaN where none was served."""
+        return self._ratio(self.named("sojourn_sum", g, sector), self.named("served", g, sector))
+
+    def mean_lost(self, g, sector=None):
+        """(sojourn_sum - timer_sum) / served per arrival bin, in ms: arrival to the start of the last attempt cycle; NaN where none was served."""
+        return self._ratio(self.named("sojourn_sum", g, sector) - self.named("timer_sum", g, sector), self.named("served", g, sector))
+
+
 NOMA_SUMMARY_MAX_FIELDS = 4
 NOMA_SUMMARY_FIXED_METRICS = ("served_ratio", "dropped_ratio", "pending_ratio", "restart_ratio")
 
@@ -1014,6 +1095,15 @@ def lib():
         L.prach_noma_trace_format_csv.argtypes = [C.POINTER(PrachNomaTraceSpec), C.POINTER(PrachNomaTrace), u64p6, C.c_char_p, C.c_char_p, C.c_size_t]
         L.prach_noma_trace_format_csv.restype = C.c_size_t
         L.prach_noma_trace_tile_rows.argtypes = []
+        L.prach_run_trials_noma_timeline.argtypes = [C.c_void_p, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachNomaTimelineSpec),
+                                                     C.POINTER(C.c_int32), C.POINTER(PrachNomaTimeline), u64p6]
+        L.prach_noma_timeline_accumulate_logs.argtypes = [C.POINTER(PrachNomaTimelineSpec), C.POINTER(PrachCfg), C.c_uint64, C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachNomaTimeline), u64p6]
+        L.prach_noma_timeline_merge.argtypes = [C.POINTER(PrachNomaTimelineSpec), C.POINTER(PrachNomaTimeline), u64p6, C.POINTER(PrachNomaTimeline), u64p6]
+        L.prach_noma_timeline_merge.restype = None
+        L.prach_noma_timeline_format_csv.argtypes = [C.POINTER(PrachNomaTimelineSpec), C.POINTER(PrachNomaTimeline), u64p6, C.c_char_p, C.c_char_p, C.c_size_t]
+        L.prach_noma_timeline_format_csv.restype = C.c_size_t
+        L.prach_noma_timeline_tile_ues.argtypes = []
+        L.prach_noma_timeline_window_bins.argtypes = []
         _lib = L
     return _lib
 
@@ -1035,7 +1125,8 @@ EXPORTS = ("prach_engine_create", "prach_engine_destroy", "prach_engine_set", "p
            "prach_noma_census_tile_ues", "prach_run_trials_noma_columns", "prach_run_trials_noma_columns_device", "prach_noma_columns_from_logs",
            "prach_run_trials_noma_pick", "prach_noma_pick_from_logs", "prach_noma_pick_format_csv", "prach_run_trials_noma_summary", "prach_noma_summary_from_logs",
            "prach_noma_summary_stats", "prach_noma_summary_format_csv", "prach_run_trials_noma_trace", "prach_noma_trace_merge", "prach_noma_trace_format_csv",
-           "prach_noma_trace_tile_rows")
+           "prach_noma_trace_tile_rows", "prach_run_trials_noma_timeline", "prach_noma_timeline_accumulate_logs", "prach_noma_timeline_merge",
+           "prach_noma_timeline_format_csv", "prach_noma_timeline_tile_ues", "prach_noma_timeline_window_bins")
 
 
 def make_cfg(nUE, variant=VARIANT_BETA_C, uniform=0, rng_mode=RNG_GLIBC, seed=0, stream_offset=0, **kw) -> PrachCfg:
@@ -1220,6 +1311,20 @@ class Engine:
         gg = (PrachNomaTrace * red.ngroups)()
         gp = None if groups is None else (C.c_int32 * len(cfgs))(*[int(g) for g in groups])
         res, logs = self._call("prach_run_trials_noma_trace", cfgs, want_logs, C.byref(sp), gp, gg, red._series())
+        for g in range(red.ngroups):
+            red._store(g, gg[g])
+        return res, logs, red
+
+    def run_trials_noma_timeline(self, cfgs, bins, bin_ms=5, groups=None, ngroups=None, want_logs=False):
+        """run_trials plus NOMA.c's timeline per trial group and sector — arrivals, served, dropped, the sojourn and timer sums of the served by arrival time, and
+        the completions by completion time, on the bins of run_trials_noma_trace — reduced on the device from the log records the simulation kernel leaves there
+        (prach_run_trials_noma_timeline; NOMA.c trials with Philox only).  groups / ngroups / want_logs as in run_trials_dist.  Returns
+        (results, logs, NomaTimeline)."""
+        red = NomaTimeline(_ngroups(len(cfgs), groups, ngroups), bins, bin_ms)
+        sp = red.spec()
+        gg = (PrachNomaTimeline * red.ngroups)()
+        gp = None if groups is None else (C.c_int32 * len(cfgs))(*[int(g) for g in groups])
+        res, logs = self._call("prach_run_trials_noma_timeline", cfgs, want_logs, C.byref(sp), gp, gg, red._series())
         for g in range(red.ngroups):
             red._store(g, gg[g])
         return res, logs, red
@@ -1453,6 +1558,35 @@ def trace_csv(tr: Trace, labels=None) -> bytes:
 
 def noma_trace_tile_rows() -> int:
     return lib().prach_noma_trace_tile_rows()
+
+
+def noma_timeline_tile_ues() -> int:
+    return lib().prach_noma_timeline_tile_ues()
+
+
+def noma_timeline_window_bins() -> int:
+    return lib().prach_noma_timeline_window_bins()
+
+
+def noma_timeline_from_logs(cfgs, steps, logs, bins, bin_ms=5, groups=None, ngroups=None) -> NomaTimeline:
+    """The host-side definition of the NOMA timelines (prach_noma_timeline_accumulate_logs): logs[k] is the per-UE log of the NOMA.c trial with config cfgs[k] that
+    ran steps[k] subframes (prach_result.steps) — a ctypes array of PrachUeLog or an int32 array of shape [nUE, 16] — added to group groups[k] (None: group k)."""
+    tl = NomaTimeline(_ngroups(len(logs), groups, ngroups), bins, bin_ms)
+    sp = tl.spec()
+    for k, lg in enumerate(logs):
+        g = k if groups is None else int(groups[k])
+        ptr, nue, _keep = _log_ptr(lg)
+        d = tl._group(g)
+        rc = lib().prach_noma_timeline_accumulate_logs(C.byref(sp), C.byref(cfgs[k]), int(steps[k]), ptr, nue, C.byref(d), tl._series(g))
+        if rc != OK:
+            raise PrachError(rc, "(prach_noma_timeline_accumulate_logs)")
+        tl._store(g, d)
+    return tl
+
+
+def noma_timeline_csv(tl: NomaTimeline, labels=None) -> bytes:
+    """The CSV text of every group (prach_noma_timeline_format_csv), labelled labels[g] (default: the group number)."""
+    return _csv("prach_noma_timeline_format_csv", tl, labels)
 
 
 def noma_trace_csv(tr: NomaTrace, labels=None) -> bytes:

@@ -62,6 +62,11 @@
  * the device) — per sector and all sectors, the preambles sent (tx), the (sector, preamble) bins used and alone (used, singles), the UEs granted, the
  * power-domain pairs and the pairs of which one UE decoded (pairs, pair_one), by time — one group per sweep point with the --times seeds merged, labelled nUE;
  * bins of MS ms (default 5) that cover maxTime; --program noma with Philox only, and not together with another reduction;
+ * --census-timeline FILE [--census-timeline-bin MS]: NOMA.c's timeline per sector (prach_run_trials_noma_timeline: reduced on the device from the log records
+ * prach::noma_kernel leaves there) — per sector and all sectors, the UEs that arrived, were served and were dropped, the sojourn and timer sums of the served,
+ * all by ARRIVAL time, and the completions by completion time — on --census-trace's bins, so that the two files line up; one group per sweep point with the
+ * --times seeds merged, labelled nUE; bins of MS ms (default 5) that cover maxTime + 6; --program noma with Philox only, and not together with another
+ * reduction.  (A sojourn HISTOGRAM by arrival time is --census FILE --census-rows arrival:W:B --census-cols sojourn:W:B --census-who served);
  * --devices LIST: the same with explicit HIP ordinals (an ordinal may repeat);
  * --gpus N: the --times x sweep grid sharded over N devices of the node by host C — one forked child per device,
  * forked BEFORE any HIP call, trials dealt by descending cost (Philox: any trial anywhere; glibc: whole seeds, because
@@ -155,11 +160,13 @@ typedef struct reduction {
     const prach_noma_summary_spec *nsm;
     prach_noma_trial_summary *nsm_rows;
     const prach_noma_trace_spec *ntr; /* --census-trace (--program noma): prach_noma_trace[npts] | six series [npts][6 sectors][bins] each */
+    const prach_noma_timeline_spec *ntl; /* --census-timeline (--program noma): prach_noma_timeline[npts] | six series [npts][6 sectors][bins] each */
 } reduction;
-static int red_on(const reduction *r) { return r->cdf || r->tl || r->sj || r->tr || r->xt || r->nc || r->ntr; }
+static int red_on(const reduction *r) { return r->cdf || r->tl || r->sj || r->tr || r->xt || r->nc || r->ntr || r->ntl; }
 static size_t xt_cells(const prach_xtab_spec *s) { return ((size_t)s->row_bins + 1) * ((size_t)s->col_bins + 1); }
 static size_t sj_cells(const prach_sojourn_spec *s) { return (size_t)s->arrival_bins * (size_t)s->delay_bins; }
 static size_t red_block_bytes(const reduction *r) {
+    if (r->ntl) return (size_t)r->ntl->ngroups * (sizeof(prach_noma_timeline) + 6 * 8 * 6 * (size_t)r->ntl->bins);
     if (r->ntr) return (size_t)r->ntr->ngroups * (sizeof(prach_noma_trace) + 6 * 8 * 6 * (size_t)r->ntr->bins);
     if (r->nc) return (size_t)r->nc->ngroups * (sizeof(prach_noma_census) + 8 * xt_cells(r->nc));
     if (r->xt) return (size_t)r->xt->ngroups * (sizeof(prach_xtab) + 8 * xt_cells(r->xt));
@@ -170,6 +177,7 @@ static size_t red_block_bytes(const reduction *r) {
 }
 /* group g of block b: --cdf its q-th histogram (0 delay, 1 preamble count), --timeline its q-th series, --sojourn 0 hist, 1 row_arrived, 2 row_delay_overflow */
 static uint64_t *red_array(const reduction *r, char *b, int q, int g) {
+    if (r->ntl) return (uint64_t *)(b + (size_t)r->ntl->ngroups * sizeof(prach_noma_timeline)) + ((size_t)q * (size_t)r->ntl->ngroups + (size_t)g) * 6 * (size_t)r->ntl->bins;
     if (r->ntr) return (uint64_t *)(b + (size_t)r->ntr->ngroups * sizeof(prach_noma_trace)) + ((size_t)q * (size_t)r->ntr->ngroups + (size_t)g) * 6 * (size_t)r->ntr->bins;
     if (r->nc) return (uint64_t *)(b + (size_t)r->nc->ngroups * sizeof(prach_noma_census)) + (size_t)g * xt_cells(r->nc);
     if (r->xt) return (uint64_t *)(b + (size_t)r->xt->ngroups * sizeof(prach_xtab)) + (size_t)g * xt_cells(r->xt);
@@ -192,8 +200,16 @@ static void red_init_block(const reduction *r, char *b) {
     for (int g = 0; r->xt && g < r->xt->ngroups; g++) ((prach_xtab *)b)[g].row_max = ((prach_xtab *)b)[g].col_max = -1;
     for (int g = 0; r->nc && g < r->nc->ngroups; g++) ((prach_noma_census *)b)[g].row_max = ((prach_noma_census *)b)[g].col_max = -1;
     for (int g = 0; r->ntr && g < r->ntr->ngroups; g++) ((prach_noma_trace *)b)[g].tx_max = -1;
+    for (int g = 0; r->ntl && g < r->ntl->ngroups; g++) ((prach_noma_timeline *)b)[g].done_max = -1;
 }
 static void red_merge_block(const reduction *r, char *into, char *from) {
+    for (int g = 0; r->ntl && g < r->ntl->ngroups; g++) {
+        uint64_t *a[6];
+        const uint64_t *b[6];
+        for (int q = 0; q < 6; q++) { a[q] = red_array(r, into, q, g); b[q] = red_array(r, from, q, g); }
+        prach_noma_timeline_merge(r->ntl, (prach_noma_timeline *)into + g, a, (prach_noma_timeline *)from + g, b);
+    }
+    if (r->ntl) return;
     for (int g = 0; r->ntr && g < r->ntr->ngroups; g++) {
         uint64_t *a[6];
         const uint64_t *b[6];
@@ -227,6 +243,11 @@ static void red_merge_block(const reduction *r, char *into, char *from) {
 }
 /* the CSV text of group g of block b; returns its length (>= cap: it did not fit) */
 static size_t red_format_group(const reduction *r, char *b, int g, const char *label, char *out, size_t cap) {
+    if (r->ntl) {
+        const uint64_t *ser[6];
+        for (int q = 0; q < 6; q++) ser[q] = red_array(r, b, q, g);
+        return prach_noma_timeline_format_csv(r->ntl, (prach_noma_timeline *)b + g, ser, label, out, cap);
+    }
     if (r->ntr) {
         const uint64_t *ser[6];
         for (int q = 0; q < 6; q++) ser[q] = red_array(r, b, q, g);
@@ -335,6 +356,13 @@ static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *
     if (red->pk) return prach_run_trials_pick(eng, c, n, r, logs, red->pk, pk_hdr, pk_rows);
     if (!red_on(red)) return prach_run_trials(eng, c, n, r, logs);
     char *const b = call_block;
+    if (red->ntl) {
+        uint64_t *ser[6];
+        for (int q = 0; q < 6; q++) ser[q] = red_array(red, b, q, 0);
+        const int rc = prach_run_trials_noma_timeline(eng, c, n, r, logs, red->ntl, grp, (prach_noma_timeline *)b, ser);
+        if (rc == PRACH_OK) red_merge_block(red, worker_block, call_block);
+        return rc;
+    }
     if (red->ntr) {
         uint64_t *ser[6];
         for (int q = 0; q < 6; q++) ser[q] = red_array(red, b, q, 0);
@@ -461,8 +489,8 @@ int main(int argc, char *argv[]) {
     const char *nci_path = NULL, *nci_who = "served", *npk_path = NULL, *npk_who = "all";
     prach_noma_summary_spec nci_spec = {0, 4, {PRACH_NOMA_SOJOURN, PRACH_NOMA_TIMER, PRACH_NOMA_PTC, PRACH_NOMA_LOST}, 3, {500, 950, 990, 0, 0, 0, 0, 0}, {0, 0}};
     prach_pick_spec npk_spec = {0, 0, {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, PRACH_PICK_BY_INDEX, PRACH_NOMA_ONE, 16, 0};
-    int cdf_bins = 4096, cdf_bin_ms = 1, tl_bin_ms = 5, sj_row_ms = 500, sj_bin_ms = 5, tr_bin_ms = 5, ntr_bin_ms = 5;
-    const char *ntr_path = NULL;
+    int cdf_bins = 4096, cdf_bin_ms = 1, tl_bin_ms = 5, sj_row_ms = 500, sj_bin_ms = 5, tr_bin_ms = 5, ntr_bin_ms = 5, ntl_bin_ms = 5;
+    const char *ntr_path = NULL, *ntl_path = NULL;
     int devs[64];
     /* --program must be known before the defaults are laid down */
     for (int i = 1; i + 1 < argc; i += 2)
@@ -571,6 +599,11 @@ int main(int argc, char *argv[]) {
             xt_cols = v;
         } else if (strcmp(a, "--xtab-who") == 0) {
             xt_who = v;
+        } else if (strcmp(a, "--census-timeline") == 0) {
+            ntl_path = v;
+        } else if (strcmp(a, "--census-timeline-bin") == 0) {
+            if (atoi(v) < 1) die("--census-timeline-bin MS: the width of a timeline bin in ms, at least 1");
+            ntl_bin_ms = atoi(v);
         } else if (strcmp(a, "--census-trace") == 0) {
             ntr_path = v;
         } else if (strcmp(a, "--census-trace-bin") == 0) {
@@ -655,6 +688,9 @@ int main(int argc, char *argv[]) {
         }
     }
     base.rng_mode = rng;
+    if (ntl_path && variant != PRACH_VARIANT_NOMA_C) die("--census-timeline needs --program noma (the other programs have --timeline)");
+    if (ntl_path && (ntr_path || nci_path || npk_path || nc_path || pk_path || xt_path || tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--census-timeline cannot be combined with another reduction: one reduction per call");
+    if (ntl_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census-timeline needs --rng philox (NOMA.c in the reference's stream is not wired to the NOMA menu's device calls)");
     if (ntr_path && variant != PRACH_VARIANT_NOMA_C) die("--census-trace needs --program noma (the other programs have --trace)");
     if (ntr_path && (nci_path || npk_path || nc_path || pk_path || xt_path || tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--census-trace cannot be combined with another reduction: one reduction per call");
     if (ntr_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census-trace needs --rng philox (NOMA.c in the reference's stream is not wired to the NOMA menu's device calls)");
@@ -760,7 +796,7 @@ int main(int argc, char *argv[]) {
      * three numbers, per cell and twice per row */
     const reduction red_ = {cdf_path ? &cdf_spec : NULL, tl_path ? &tl_spec : NULL, sj_path ? &sj_spec : NULL, sj_path ? sj_path : tl_path ? tl_path : cdf_path,
                             sj_path ? 64 * ((size_t)sj_rows * ((size_t)sj_bins + 2) + 1) + 1
-                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, 0, NULL, NULL, NULL};
+                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, 0, NULL, NULL, NULL, NULL};
     reduction red_ci = red_;
     /* the trace's bins cover maxTime */
     const int tr_bins = (prach_max_time(&base) + tr_bin_ms - 1) / tr_bin_ms;
@@ -772,6 +808,12 @@ int main(int argc, char *argv[]) {
     const prach_noma_trace_spec ntr_spec = {ntr_bins, ntr_bin_ms, npts, 0};
     if (ntr_path && ntr_bins > PRACH_TRACE_MAX_BINS) die("--census-trace-bin MS: too many bins");
     if (ntr_path && 36 * (uint64_t)npts * (uint64_t)ntr_bins > (1ull << 27)) die("--census-trace: too many bins for this many sweep points");
+    /* --census-timeline: the same for NOMA.c's timeline per sector; its bins cover the completions too (maxTime + 6) */
+    const int ntl_bins = (prach_max_time(&base) + 6 + ntl_bin_ms - 1) / ntl_bin_ms;
+    const prach_noma_timeline_spec ntl_spec = {ntl_bins, ntl_bin_ms, npts, 0};
+    if (ntl_path && ntl_bins > PRACH_TIMELINE_MAX_BINS) die("--census-timeline-bin MS: too many bins");
+    if (ntl_path && 36 * (uint64_t)npts * (uint64_t)ntl_bins > (1ull << 27)) die("--census-timeline: too many bins for this many sweep points");
+    if (ntl_path) { red_ci.ntl = &ntl_spec; red_ci.path = ntl_path; red_ci.text_cap = 80 * (6 * 7 * (size_t)ntl_bins + 2) + 1; } /* (a line: the label, a series name, a sector, two numbers) */
     if (ntr_path) { red_ci.ntr = &ntr_spec; red_ci.path = ntr_path; red_ci.text_cap = 80 * (6 * 7 * (size_t)ntr_bins + 1) + 1; } /* (a line: the label, a series name, a sector, two numbers) */
     /* --xtab: the axes as given, the defaults of a field where width or bins are left out */
     prach_xtab_spec xt_spec = {0, 0, 0, 0, 0, 0, 0, npts, {0, 0}};

@@ -336,4 +336,17 @@ struct NomaTraceJob {
 struct NomaTraceOut { unsigned long long *series[6], *scalars; }; // [ngroups][6 sectors][bins] each, [ngroups][NT_SCALARS]
 hipError_t launch_noma_trace_kernel(const NomaTraceJob *jobs, int njobs, int workgroups, int bins, int bin_ms, int scheme, NomaTraceOut out, hipStream_t stream);
 
+// prach_noma_timeline.hip: NOMA.c's timelines per sector of a launch's accepted trials (prach_run_trials_noma_timeline).  The jobs are the timeline's with
+// E = min(steps, maxTime) in `pad`, and so are tile and workgroup: one tile of TL_TILE consecutive UEs of one trial.  scheme 1 adds a tile up in an LDS window
+// of 32-bit counters, `window` bins x 6 sectors x 6 series from the tile's first arrival bin on, and flushes the non-zero ones; what falls outside — a later
+// arrival bin, a completion bin, a sojourn or timer above NTL_MAX_SOJOURN — and everything under scheme 0 goes straight to the call's buffers; both with 64-bit
+// agent-scope atomics.  `window` is a launch argument (the LDS is dynamic): 1 .. NTL_WINDOW_MAX, NTL_WINDOW where nobody asks (profiles/noma_timeline_kernel.md).
+constexpr int NTL_WINDOW = 256, NTL_WINDOW_MAX = 1024;
+constexpr int NTL_MAX_SOJOURN = 10000 + 6; // c(i) - a(i) of a NOMA.c trial at most: 10 000 subframes, the completion is 6 behind the success (prach_noma_menu.h: THE BOUNDS)
+static_assert((unsigned long long)TL_TILE * NTL_MAX_SOJOURN < (1ull << 32), "a 32-bit LDS counter holds the sojourn sum, and the timer sum, of a whole tile");
+static_assert(4 * (2048 + 36 * NTL_WINDOW_MAX) + 8 * 12 <= 160 * 1024, "the largest window, the staged schedule range and the scalars fit the 160 KiB of LDS of a gfx950 CU");
+constexpr int NTL_SCALARS = 12, NTL_SUMS = 10, NTL_MAXIMA = 1; // per group: idle, served, dropped, pending, undefined, restarted, arrival_overflow, done_overflow, sojourn_sum, timer_sum | done_max + 1 (0: no served UE) | 1 spare
+struct NomaTimelineOut { unsigned long long *series[6], *scalars; }; // [ngroups][6 sectors][bins] each: arrivals, served, dropped, sojourn_sum, timer_sum, done; [ngroups][NTL_SCALARS]
+hipError_t launch_noma_timeline_kernel(const TimelineJob *jobs, int njobs, int workgroups, int bins, int bin_ms, int scheme, int window, NomaTimelineOut out, hipStream_t stream);
+
 } // namespace prach

@@ -62,6 +62,7 @@ struct prach_engine {
     int64_t opt_pick_threads = 1024;    // pick_kernel's workgroup (prach_pick.hip): 512 or 1024 threads, one workgroup per trial
     int64_t opt_xtab_scheme = 1;     // xtab_kernel's binning (prach_xtab.hip): 0 global atomics only, 1 a table that fits privatised in LDS
     int64_t opt_sojourn_scheme = 1;  // sojourn_kernel's binning (prach_sojourn.hip): 0 global atomics only, 1 rows of the histogram privatised in LDS
+    int64_t opt_noma_timeline_window = NTL_WINDOW; // noma_timeline_kernel's LDS window in bins (prach_noma_timeline.hip; measured: profiles/noma_timeline_kernel.md)
     int64_t opt_timeline_scheme = 1; // timeline_kernel's binning (prach_timeline.hip): 0 global atomics only, 1 windows of bins privatised in LDS (measured faster: DESIGN.md 4)
     int64_t opt_dist_scheme = 1;   // dist_kernel's binning of the preamble counts (prach_dist.hip): 0 plain LDS adds, 1 per-wavefront copies (measured fastest), 2 match and aggregate
     prach_timing last{};
@@ -437,7 +438,7 @@ static int noma_device_activation(prach_engine *e, const TrialDev *dparams, cons
 // the simulation kernel.  What differs between the kinds is stated ONCE per kind: a block of functions behind CallCtx and its row of RED_KINDS.  The generic
 // code (reduction_begin, run_group, reduction_end, run_trials_impl) walks that row and never asks which kind it has; a new kind is an enumerator, a block and
 // a row.
-enum class Red { dist, timeline, sojourn, summary, trace, xtab, pick, columns, noma_census, noma_columns, noma_summary, noma_pick, noma_trace };
+enum class Red { dist, timeline, sojourn, summary, trace, xtab, pick, columns, noma_census, noma_columns, noma_summary, noma_pick, noma_trace, noma_timeline };
 constexpr int RED_MAX_PARTS = 7;
 struct Reduction {
     Red kind;
@@ -784,6 +785,21 @@ int noma_trace_unpack(const Reduction &r, CallCtx &cx, size_t g, const unsigned 
     return PRACH_OK;
 }
 
+// noma_timeline: the six series arrivals, served, dropped, sojourn_sum, timer_sum, done, [6 sectors][bins] per group | scalars; reads the log records
+// prach::noma_kernel leaves on the device, the launch's schedule and E (prach_noma_timeline.hip)
+int noma_timeline_parts(const Reduction &r, size_t w[]) { for (int q = 0; q < 6; q++) w[q] = 6 * (size_t)spec_of<prach_noma_timeline_spec>(r).bins; w[6] = NTL_SCALARS; return 7; }
+hipError_t noma_timeline_launch(const prach_engine *e, const Reduction &r, int njobs, int wgs, unsigned long long *const *d) {
+    const prach_noma_timeline_spec &sp = spec_of<prach_noma_timeline_spec>(r);
+    return launch_noma_timeline_kernel(timeline_jobs(e), njobs, wgs, sp.bins, sp.bin_ms, (int)e->opt_timeline_scheme, (int)e->opt_noma_timeline_window,
+                                       NomaTimelineOut{{d[0], d[1], d[2], d[3], d[4], d[5]}, d[6]}, e->stream);
+}
+int noma_timeline_unpack(const Reduction &r, CallCtx &cx, size_t g, const unsigned long long *q) {
+    prach_noma_timeline &t = group_of<prach_noma_timeline>(r, g);
+    t.trials = cx.trials[g]; t.ues = cx.ues[g]; t.idle = q[0]; t.served = q[1]; t.dropped = q[2]; t.pending = q[3]; t.undefined = q[4]; t.restarted = q[5];
+    t.arrival_overflow = q[6]; t.done_overflow = q[7]; t.sojourn_sum = q[8]; t.timer_sum = q[9]; t.done_max = (int64_t)q[10] - 1;
+    return PRACH_OK;
+}
+
 // in the order of enum class Red:           parts, job bytes, tile, job, device logs, trace rows, "fast" off, launch, empty, unpack, prach_timing field
 const RedKind RED_KINDS[] = {
     {dist_parts, sizeof(DistJob), DIST_TILE, dist_fill_job, false, false, false, dist_launch, empty_group<prach_dist, &prach_dist::delay_max>, dist_unpack, &prach_timing::dist_ms},
@@ -799,8 +815,9 @@ const RedKind RED_KINDS[] = {
     {noma_summary_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, noma_summary_launch, noma_summary_empty, noma_summary_unpack, &prach_timing::noma_summary_ms},
     {pick_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, noma_pick_launch, pick_empty, pick_unpack, &prach_timing::noma_pick_ms},
     {noma_trace_parts, sizeof(NomaTraceJob), NT_TILE, noma_trace_fill_job, false, true, false, noma_trace_launch, empty_group<prach_noma_trace, &prach_noma_trace::tx_max>, noma_trace_unpack, &prach_timing::noma_trace_ms},
+    {noma_timeline_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, noma_timeline_launch, empty_group<prach_noma_timeline, &prach_noma_timeline::done_max>, noma_timeline_unpack, &prach_timing::noma_timeline_ms},
 };
-static_assert(sizeof(RED_KINDS) / sizeof(RED_KINDS[0]) == (size_t)Red::noma_trace + 1, "one row per kind");
+static_assert(sizeof(RED_KINDS) / sizeof(RED_KINDS[0]) == (size_t)Red::noma_timeline + 1, "one row per kind");
 const RedKind &kind_of(const Reduction &r) { return RED_KINDS[(int)r.kind]; }
 
 // How a rerun's launch differs from the first one
@@ -1677,6 +1694,7 @@ int prach_engine_set(prach_engine *e, const char *key, int64_t value) {
     if (std::strcmp(key, "batch_waves") == 0) { if (value != 0 && value != 8 && value != 16) return PRACH_ERR_ARG; e->opt_batch_waves = value; return PRACH_OK; }
     if (std::strcmp(key, "dist_scheme") == 0) { if (value < 0 || value > 2) return PRACH_ERR_ARG; e->opt_dist_scheme = value; return PRACH_OK; }
     if (std::strcmp(key, "timeline_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_timeline_scheme = value; return PRACH_OK; }
+    if (std::strcmp(key, "noma_timeline_window") == 0) { if (value < 0 || value > NTL_WINDOW_MAX) return PRACH_ERR_ARG; e->opt_noma_timeline_window = value ? value : NTL_WINDOW; return PRACH_OK; }
     if (std::strcmp(key, "summary_threads") == 0) { if (value != 0 && value != 512 && value != 1024) return PRACH_ERR_ARG; e->opt_summary_threads = value ? value : 1024; return PRACH_OK; }
     if (std::strcmp(key, "pick_threads") == 0) { if (value != 0 && value != 512 && value != 1024) return PRACH_ERR_ARG; e->opt_pick_threads = value ? value : 1024; return PRACH_OK; }
     if (std::strcmp(key, "trace_scheme") == 0) { if (value < 0 || value > 1) return PRACH_ERR_ARG; e->opt_trace_scheme = value; return PRACH_OK; }
@@ -1977,6 +1995,22 @@ int prach_run_trials_noma_trace(prach_engine *e, const prach_cfg *cfgs, int n, p
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
+int prach_run_trials_noma_timeline(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_noma_timeline_spec *spec,
+                                   const int32_t *group, prach_noma_timeline *tl, uint64_t *const series[6]) {
+    // (spec, groups and variants are judged first: what they ask for does not depend on a device)
+    if (!cfgs || !results || n <= 0 || !spec || !tl || !series) return PRACH_ERR_ARG;
+    for (int q = 0; q < 6; q++) if (!series[q]) return PRACH_ERR_ARG;
+    if (spec->bins < 1 || spec->bins > PRACH_TIMELINE_MAX_BINS || spec->bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
+    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
+    for (int k = 0; k < n; k++) if (!noma_device_cfg(cfgs[k])) return PRACH_ERR_UNSUPPORTED;
+    if (36 * (uint64_t)spec->ngroups * (uint64_t)spec->bins > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
+    if (!e) return PRACH_ERR_ARG;
+    const Reduction red{.kind = Red::noma_timeline, .group = group, .ngroups = spec->ngroups, .out = {series[0], series[1], series[2], series[3], series[4], series[5]}, .spec = spec, .groups = tl};
+    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
+}
+
+int prach_noma_timeline_tile_ues(void) { return TL_TILE; }
+int prach_noma_timeline_window_bins(void) { return NTL_WINDOW; }
 int prach_noma_trace_tile_rows(void) { return NT_TILE; }
 int prach_noma_census_tile_ues(void) { return TL_TILE; }
 int prach_columns_tile_ues(void) { return TL_TILE; }

@@ -1122,6 +1122,93 @@ int prach_noma_columns_from_logs(const prach_columns_spec *s, const prach_cfg *c
     return menu_columns(&NOMA_MENU, s, cfg, steps, ue, nUE, out, stride);
 }
 
+/* ---- NOMA.c's timeline per trial group and sector (prach_run_trials_noma_timeline): THE DEFINITION, merge, CSV ---- */
+
+static int noma_timeline_spec_ok(const prach_noma_timeline_spec *s) {
+    return s && s->bins >= 1 && s->bins <= PRACH_TIMELINE_MAX_BINS && s->bin_ms >= 1;
+}
+
+/* THE DEFINITION (include/prach.h), on the menu's own class and values: nothing of a log is refused, what the menu calls undefined is counted */
+int prach_noma_timeline_accumulate_logs(const prach_noma_timeline_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE,
+                                        prach_noma_timeline *t, uint64_t *const series[6]) {
+    if (!noma_timeline_spec_ok(s) || !cfg || !t || !series || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    for (int q = 0; q < 6; q++) if (!series[q]) return PRACH_ERR_ARG;
+    int nslots = 0, rc;
+    int64_t E = 0;
+    int32_t *sched = menu_schedule(&NOMA_MENU, cfg, nUE, steps, &nslots, &E, &rc);
+    if (!sched) return rc;
+    if (t->trials == 0 && t->served == 0) t->done_max = -1; /* (a zero-filled group is an empty one) */
+    uint64_t *const arrivals = series[0], *const served = series[1], *const dropped = series[2], *const sojourn_sum = series[3], *const timer_sum = series[4],
+                    *const done = series[5];
+    int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
+    for (int i = 0; i < nUE; i++) {
+        while (slot < nslots && sched[slot] <= i) slot++;
+        const int64_t a = (int64_t)cfg->accessTime * slot;
+        const prach_ue_log *u = &ue[i];
+        const int cls = noma_class(u);
+        if (cls == PRACH_NOMA_IDLE) { t->idle++; continue; }
+        if (cls == PRACH_NOMA_SERVED) t->served++;
+        else if (cls == PRACH_NOMA_DROPPED) t->dropped++;
+        else t->pending++;
+        const int64_t sec = noma_value(PRACH_NOMA_SECTOR, u, cls, a, E), sj = noma_value(PRACH_NOMA_SOJOURN, u, cls, a, E),
+                      tm = noma_value(PRACH_NOMA_TIMER, u, cls, a, E), c = noma_value(PRACH_NOMA_COMPLETION, u, cls, a, E);
+        if (sec < 0 || sec > 5 || (cls == PRACH_NOMA_SERVED && (sj < 0 || tm < 0 || c < 0))) { t->undefined++; continue; }
+        const int64_t ab = noma_value(PRACH_NOMA_ARRIVAL, u, cls, a, E) / s->bin_ms;
+        const size_t at = (size_t)sec * (size_t)s->bins + (size_t)ab;
+        if (ab < s->bins) arrivals[at]++;
+        else t->arrival_overflow++;
+        if (cls == PRACH_NOMA_DROPPED && ab < s->bins) dropped[at]++;
+        if (cls != PRACH_NOMA_SERVED) continue;
+        const int64_t db = c / s->bin_ms;
+        t->sojourn_sum += (uint64_t)sj;
+        t->timer_sum += (uint64_t)tm;
+        t->restarted += noma_value(PRACH_NOMA_LOST, u, cls, a, E) > 0;
+        if (c > t->done_max) t->done_max = c;
+        if (ab < s->bins) { served[at]++; sojourn_sum[at] += (uint64_t)sj; timer_sum[at] += (uint64_t)tm; }
+        if (db < s->bins) done[(size_t)sec * (size_t)s->bins + (size_t)db]++;
+        else t->done_overflow++;
+    }
+    free(sched);
+    t->trials++;
+    t->ues += (uint64_t)nUE;
+    return PRACH_OK;
+}
+
+void prach_noma_timeline_merge(const prach_noma_timeline_spec *s, prach_noma_timeline *into, uint64_t *const into_series[6], const prach_noma_timeline *from,
+                               const uint64_t *const from_series[6]) {
+    if (!noma_timeline_spec_ok(s) || !into || !into_series || !from || !from_series) return;
+    for (int q = 0; q < 6; q++) if (!into_series[q] || !from_series[q]) return;
+    const int64_t a = into->served ? into->done_max : -1, b = from->served ? from->done_max : -1;
+    into->trials += from->trials; into->ues += from->ues; into->idle += from->idle; into->served += from->served; into->dropped += from->dropped;
+    into->pending += from->pending; into->undefined += from->undefined; into->restarted += from->restarted; into->arrival_overflow += from->arrival_overflow;
+    into->done_overflow += from->done_overflow; into->sojourn_sum += from->sojourn_sum; into->timer_sum += from->timer_sum;
+    into->done_max = a > b ? a : b;
+    for (int q = 0; q < 6; q++)
+        for (int i = 0; i < 6 * s->bins; i++) into_series[q][i] += from_series[q][i];
+}
+
+size_t prach_noma_timeline_format_csv(const prach_noma_timeline_spec *s, const prach_noma_timeline *t, const uint64_t *const series[6], const char *label, char *buf,
+                                      size_t cap) {
+    static const char *const names[6] = {"arrivals", "served", "dropped", "sojourn_sum", "timer_sum", "done"};
+    if (!noma_timeline_spec_ok(s) || !t || !series || !label) return 0;
+    for (int q = 0; q < 6; q++) if (!series[q]) return 0;
+    size_t off = 0;
+    for (int q = 0; q < 6; q++) {
+        for (int b = 0; b < s->bins; b++) {
+            uint64_t all = 0;
+            for (int c = 0; c < 6; c++) {
+                const uint64_t v = series[q][(size_t)c * (size_t)s->bins + (size_t)b];
+                all += v;
+                if (v) CSV_EMIT("%.200s,%s,%d,%lld,%llu\n", label, names[q], c, (long long)b * s->bin_ms, (unsigned long long)v);
+            }
+            if (all) CSV_EMIT("%.200s,%s,all,%lld,%llu\n", label, names[q], (long long)b * s->bin_ms, (unsigned long long)all);
+        }
+        if (q == 0 && t->arrival_overflow) CSV_EMIT("%.200s,arrivals,all,overflow,%llu\n", label, (unsigned long long)t->arrival_overflow);
+        if (q == 5 && t->done_overflow) CSV_EMIT("%.200s,done,all,overflow,%llu\n", label, (unsigned long long)t->done_overflow);
+    }
+    return csv_end(buf, cap, off);
+}
+
 /* THE DEFINITION of the pick (prach_pick_from_logs, prach_noma_pick_from_logs): every match is listed, the list is sorted, the first k are the rows */
 typedef struct pick_cand { int64_t key; int32_t i, arrival; } pick_cand;
 static int cmp_pick_desc(const void *a, const void *b) { /* descending key, equal keys in ascending UE index */

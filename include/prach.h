@@ -129,6 +129,8 @@ typedef struct prach_timing {
     int32_t trial_kernel_reruns; /* of fallback_trials: trials that were (also) rerun on the one-workgroup, index-ordered trial_kernel */
     int32_t noma_host_ues;       /* NOMA_C, Philox: UEs of the device-built activeUE table that the host recomputed with its libm (a value inside the
                                     device math library's error band of a rounding / comparison boundary: ~1e-6 of the UEs) */
+    double noma_timeline_ms;     /* HIP-event time of the NOMA timeline kernel launches (prach_run_trials_noma_timeline) of the last call; 0 in every other call (such
+                                    a call leaves every other *_ms of a reduction 0) */
     double noma_trace_ms;        /* HIP-event time of the NOMA trace kernel launches (prach_run_trials_noma_trace) of the last call; 0 in every other call (such a
                                     call leaves every other *_ms of a reduction 0) */
     double noma_summary_ms;      /* HIP-event time of the NOMA summary kernel launches (prach_run_trials_noma_summary) of the last call; 0 in every other call (such a
@@ -616,6 +618,69 @@ int prach_run_trials_noma_trace(prach_engine *, const prach_cfg *cfgs, int n, pr
 void prach_noma_trace_merge(const prach_noma_trace_spec *, prach_noma_trace *into, uint64_t *const into_series[6], const prach_noma_trace *from, const uint64_t *const from_series[6]);
 size_t prach_noma_trace_format_csv(const prach_noma_trace_spec *, const prach_noma_trace *, const uint64_t *const series[6], const char *label, char *buf, size_t cap);
 int prach_noma_trace_tile_rows(void); /* (slot, sector) rows of one trial that one workgroup of prach::noma_trace_kernel reduces (tests place sizes around it) */
+
+/* NOMA.c's timeline per trial group and SECTOR: what became of the UEs that arrived in each stretch of the simulation, and how long they waited — the other
+ * half of the channel trace above, on the trace's own bins, so that tx / singles / pairs of a (sector, bin) stand next to arrivals / served / dropped / mean
+ * sojourn / mean lost time of the UEs that arrived in it.  Everything is a function of the per-UE log, the arrival schedule and `steps`, so there IS an
+ * _accumulate_logs form, and it is THE DEFINITION.  It uses a(i), E, c(i) = txTime + 6, the four classes and the fields of THE NOMA MENU as they stand.
+ * For UE i with class cls, sector s = SECTOR, arrival bin ab = a(i) / bin_ms and completion bin db = c(i) / bin_ms:
+ *   - every UE counts in its class counter (idle, served, dropped, pending): their sum is `ues`;
+ *   - an arrived UE is UNDEFINED FOR THE TIMELINE if its SECTOR lies outside 0..5, or if it is served and any of SOJOURN, TIMER, COMPLETION is negative (the
+ *     menu's ONE RULE).  It counts in `undefined` and in nothing else below.  No trial produces one;
+ *   - every other arrived UE: ab < bins: arrivals[s][ab] += 1; otherwise arrival_overflow += 1;
+ *   - dropped, with ab < bins: dropped[s][ab] += 1;
+ *   - served: the scalars sojourn_sum += SOJOURN, timer_sum += TIMER, done_max = max(done_max, c(i)), restarted += LOST > 0 (as
+ *     prach_noma_trial_summary.restarted), always; if ab < bins: served[s][ab] += 1, sojourn_sum[s][ab] += SOJOURN, timer_sum[s][ab] += TIMER; if db < bins:
+ *     done[s][db] += 1, otherwise done_overflow += 1.
+ * Pending per (sector, bin) is arrivals - served - dropped; it is not stored.  IDENTITY: sum(arrivals) + arrival_overflow + undefined == served + dropped +
+ * pending.  The six series are [ngroups][6 sectors][bins] each, in the order arrivals, served, dropped, sojourn_sum, timer_sum, done: the layout of
+ * prach_noma_trace's series, so the two line up index for index.  ONE DIFFERENCE from the trace: under PRACH_FLAG_NOMA_NONSECTOR the trace puts the one
+ * cell-wide group into sector 0, while the timeline's sector is still the record's own word — the UE's sector, not the grouping's.
+ * Integers only, 64-bit outputs: device, host, forked workers and ranks merge exactly in any order.
+ * THERE IS NO NOMA SOJOURN KIND: prach_run_trials_noma_census with ARRIVAL by SOJOURN over PRACH_NOMA_SERVED is that histogram, and prach_xtab_quantile reads
+ * it.  The timeline adds what no census cell holds: the sums, the by-completion axis, and both split by sector on the bins of the channel trace. */
+#define PRACH_NOMA_TIMELINE_SERIES 6
+typedef struct prach_noma_timeline_spec {
+    int32_t bins;      /* 1 .. PRACH_TIMELINE_MAX_BINS */
+    int32_t bin_ms;    /* >= 1 */
+    int32_t ngroups;   /* number of output timelines */
+    int32_t reserved;  /* 0 */
+} prach_noma_timeline_spec;
+
+typedef struct prach_noma_timeline { /* one per group */
+    uint64_t trials;                 /* trials accumulated (status PRACH_OK) */
+    uint64_t ues;                    /* sum of their nUE */
+    uint64_t idle, served, dropped, pending; /* the four classes: idle + served + dropped + pending == ues */
+    uint64_t undefined;              /* arrived UEs that are undefined for the timeline (in no series, no overflow and no sum) */
+    uint64_t restarted;              /* served, defined, LOST > 0 */
+    uint64_t arrival_overflow;       /* defined arrived UEs with a(i) at or behind bins * bin_ms */
+    uint64_t done_overflow;          /* defined served UEs with c(i) at or behind bins * bin_ms */
+    uint64_t sojourn_sum, timer_sum; /* over the defined served UEs, unbinned */
+    int64_t  done_max;               /* the largest c(i) of a defined served UE; -1 without one */
+} prach_noma_timeline;
+
+/* prach_run_trials plus the NOMA timelines, with the contract of prach_run_trials_noma_trace word for word (groups, OVERWRITTEN outputs, a rerun trial counted
+ * once, at most one reduction per call); tl[ngroups] and series[q][ngroups * 6 * bins] are caller-owned.  prach::noma_timeline_kernel
+ * (csrc/prach_noma_timeline.hip) reduces the log records prach::noma_kernel wrote on the device; engine option "timeline_scheme" applies.
+ * PRACH_ERR_ARG: a NULL output, a bin count or width out of range, a group id out of range, NULL group with ngroups != n;
+ * PRACH_ERR_UNSUPPORTED, before anything is launched: any cfg that is not NOMA_C; any NOMA_C cfg with rng_mode == PRACH_RNG_GLIBC; 36 * ngroups * bins > 2^27
+ * words.  A refusal writes nothing. */
+int prach_run_trials_noma_timeline(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs,
+                                   const prach_noma_timeline_spec *spec, const int32_t *group, prach_noma_timeline *tl, uint64_t *const series[6]);
+/* host side (no device needed; both RNG modes), ONE group (series[q]: [6][bins]).  prach_noma_timeline_accumulate_logs ADDS one trial's per-UE log to a group:
+ * THE DEFINITION prach::noma_timeline_kernel equals, integer for integer; steps is the trial's prach_result.steps.  PRACH_ERR_UNSUPPORTED: a cfg that is not
+ * NOMA_C.  PRACH_ERR_ARG: a bad spec or cfg, a NULL pointer, nUE != cfg->nUE (no log content is refused).  _merge adds counts and sums and takes the maximum;
+ * _format_csv writes the trace's line shapes — "label,series,sector,t_ms,count" for every non-zero (bin, sector), "label,series,all,t_ms,count" for every
+ * non-zero bin — plus "label,arrivals,all,overflow,count" and "label,done,all,overflow,count" where the overflows are non-zero; returns the text's length
+ * (written in full only if it fits cap, then 0-terminated). */
+int prach_noma_timeline_accumulate_logs(const prach_noma_timeline_spec *, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE,
+                                        prach_noma_timeline *t, uint64_t *const series[6]);
+void prach_noma_timeline_merge(const prach_noma_timeline_spec *, prach_noma_timeline *into, uint64_t *const into_series[6], const prach_noma_timeline *from,
+                               const uint64_t *const from_series[6]);
+size_t prach_noma_timeline_format_csv(const prach_noma_timeline_spec *, const prach_noma_timeline *, const uint64_t *const series[6], const char *label, char *buf,
+                                      size_t cap);
+int prach_noma_timeline_tile_ues(void);    /* UEs of one trial that one workgroup of prach::noma_timeline_kernel reduces (tests place sizes around it) */
+int prach_noma_timeline_window_bins(void); /* bins of the LDS window of prach::noma_timeline_kernel (timeline_scheme 1), anchored at a tile's first arrival bin */
 
 /* Per-trial summaries of NOMA_C trials: ONE ROW PER TRIAL — the four class counts, and for up to four NAMED fields of THE NOMA MENU above, over the UEs of
  * the classes in `who` whose value of the field is DEFINED (the menu's ONE RULE: >= 0), their number, sum, maximum and EXACT order statistics — selected on the
