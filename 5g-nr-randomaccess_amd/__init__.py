@@ -71,10 +71,66 @@ class PrachDist(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in DIST_FIELDS[:-1]] + [("delay_max", C.c_int64)]
 
 
+_U64P = C.POINTER(C.c_uint64)
+
+
 class _Reduction:
-    """What Dist, Timeline, Sojourn and Trace share.  A subclass names its scalar fields (_FIELDS), the C struct of one group (_STRUCT), the library's merge and its
-    defining parameters (_PARAMS), and gives ``_arrays()`` — its [ngroups, n] uint64 arrays in the order of the C ABI — ``_scalar(f)``, the int64 array of
-    length ngroups of scalar field f, and ``_cargs(g)``, group g's arrays as the library's merge and CSV functions take them."""
+    """What the eight grouped kinds share; csrc/prach_grouped.h states the same on the C side.  A subclass DECLARES its kind and implements nothing of it:
+
+    _KIND     the name in prach_run_trials_<kind>, prach_<kind>_merge, prach_<kind>_format_csv and prach_<kind>_accumulate_logs
+    _PARAMS   the constructor's arguments behind ngroups, (name, converter[, default]) each: they become attributes, and same_as and merge compare them
+    _SPEC     the C struct of the spec, and _SPEC_OF, a function of the instance that gives its field values
+    _STRUCT   the C struct of one group; _FIELDS its scalar fields, of which the last _MAXIMA start at -1; they are int64 arrays of length ngroups in the dict
+              ``scalars`` (_SCALAR_ATTRS: attributes of their own instead)
+    _NAMES    the uint64 arrays in the order of the C ABI, and _SHAPE, a function of the instance that gives the shape of one group of each
+    _EXPOSE   how they are held: "attrs" an attribute [ngroups, *shape] per name, "dict" ``series[name]``, "stack" ONE array ``series`` [len(_NAMES), ngroups, *shape]
+              (_VIEWS: and series[q] under its name)
+    _RUN      how the device call and accumulate_logs take the arrays, _HOST how merge and CSV do: "flat" pointers, or one "array" uint64_t *[n]
+    _LOGS     what accumulate_logs takes between the spec and the log: None (the kind has no host-side definition), "", "cfg" or "cfg,steps"
+    """
+    _MAXIMA, _SCALAR_ATTRS, _VIEWS, _RUN, _HOST, _LOGS, _NOUN = 1, False, False, "flat", "flat", None, "reductions"
+
+    def __init__(self, ngroups, *args, **kw):
+        import numpy as np
+        self.ngroups = int(ngroups)
+        if len(args) > len(self._PARAMS):
+            raise TypeError(f"{type(self).__name__} takes ngroups and {len(self._PARAMS)} more arguments")
+        for i, (name, conv, *default) in enumerate(self._PARAMS):
+            if i >= len(args) and name not in kw and not default:
+                raise TypeError(f"{type(self).__name__}: argument {name!r} is missing")
+            setattr(self, name, conv(args[i] if i < len(args) else kw.pop(name, *default)))
+        if kw:
+            raise TypeError(f"{type(self).__name__}: unexpected arguments {sorted(kw)}")
+        shapes = self._SHAPE()
+        if self._EXPOSE == "stack":
+            self.series = np.zeros((len(self._NAMES), self.ngroups) + shapes[0], dtype=np.uint64)
+            arrays = list(self.series)
+        else:
+            arrays = [np.zeros((self.ngroups,) + sh, dtype=np.uint64) for sh in shapes]
+        if self._EXPOSE == "dict":
+            self.series = dict(zip(self._NAMES, arrays))
+        if self._EXPOSE == "attrs" or self._VIEWS:
+            for n, a in zip(self._NAMES, arrays):
+                setattr(self, n, a)
+        scalars = {f: np.zeros(self.ngroups, dtype=np.int64) for f in self._FIELDS}
+        for f in self._FIELDS[-self._MAXIMA:]:
+            scalars[f][:] = -1
+        if self._SCALAR_ATTRS:
+            for f, a in scalars.items():
+                setattr(self, f, a)
+        else:
+            self.scalars = scalars
+
+    def spec(self):
+        return self._SPEC(*self._SPEC_OF())
+
+    def _arrays(self):
+        """The [ngroups, ...] uint64 arrays in the order of the C ABI."""
+        return [getattr(self, n) for n in self._NAMES] if self._EXPOSE == "attrs" else [self.series[n] for n in self._NAMES] if self._EXPOSE == "dict" else list(self.series)
+
+    def _scalar(self, f):
+        """The int64 array of length ngroups of scalar field f."""
+        return getattr(self, f) if self._SCALAR_ATTRS else self.scalars[f]
 
     def _group(self, g):
         return self._STRUCT(*[int(self._scalar(f)[g]) for f in self._FIELDS])
@@ -83,48 +139,73 @@ class _Reduction:
         for f in self._FIELDS:
             self._scalar(f)[g] = getattr(d, f)
 
+    def _ptrs(self, form, g=None):
+        """The arrays — of group g, or of all groups — as the C side takes them in that form."""
+        p = [(a if g is None else a[g]).ctypes.data_as(_U64P) for a in self._arrays()]
+        return ((_U64P * len(p))(*p),) if form == "array" else tuple(p)
+
     def _rows(self, g):
-        return [a[g].ctypes.data_as(C.POINTER(C.c_uint64)) for a in self._arrays()]
+        return list(self._ptrs("flat", g))
+
+    def _series(self, g=None):
+        """The arrays — of group g, or of all groups — as the uint64_t *[n] the C side takes."""
+        return self._ptrs("array", g)[0]
+
+    def _cargs(self, g):
+        """Group g's arrays as the library's merge and CSV functions take them."""
+        return self._ptrs(self._HOST, g)
 
     def merge_group(self, g, other, og):
-        """Adds group ``og`` of ``other`` to group ``g`` (prach_dist_merge / prach_timeline_merge / prach_sojourn_merge)."""
+        """Adds group ``og`` of ``other`` to group ``g`` (the kind's prach_*_merge)."""
         sp, a, b = self.spec(), self._group(g), other._group(og)
-        getattr(lib(), self._MERGE)(C.byref(sp), C.byref(a), *self._cargs(g), C.byref(b), *other._cargs(og))
+        getattr(lib(), f"prach_{self._KIND}_merge")(C.byref(sp), C.byref(a), *self._cargs(g), C.byref(b), *other._cargs(og))
         self._store(g, a)
+
+    def _shape_key(self):
+        return tuple(getattr(self, p[0]) for p in self._PARAMS)
+
+    def merge(self, other):
+        """Adds every group of ``other`` (same parameters and ngroups) to the same group of this one.  Returns self."""
+        if (self._shape_key(), self.ngroups) != (other._shape_key(), other.ngroups):
+            raise ValueError(f"{self._NOUN} of different shapes do not merge")
+        for g in range(self.ngroups):
+            self.merge_group(g, other, g)
+        return self
+
+    def csv(self, labels=None) -> bytes:
+        """The CSV text of every group (the kind's prach_*_format_csv: asked for its size first, then filled), labelled labels[g] (default: the group number)."""
+        out = b""
+        sp, fmt = self.spec(), getattr(lib(), f"prach_{self._KIND}_format_csv")
+        for g in range(self.ngroups):
+            d = self._group(g)
+            args = (C.byref(sp), C.byref(d), *self._cargs(g), str(g if labels is None else labels[g]).encode())
+            need = fmt(*args, None, 0)
+            buf = C.create_string_buffer(need + 1)
+            n = fmt(*args, buf, need + 1)
+            out += buf.raw[:n]
+        return out
 
     def same_as(self, other):
         import numpy as np
-        return all(getattr(self, p) == getattr(other, p) for p in self._PARAMS) and all(np.array_equal(x, y) for x, y in zip(self._arrays(), other._arrays())) and \
+        return self._shape_key() == other._shape_key() and all(np.array_equal(x, y) for x, y in zip(self._arrays(), other._arrays())) and \
             all(np.array_equal(self._scalar(f), other._scalar(f)) for f in self._FIELDS)
+
+    @classmethod
+    def from_logs(cls, logs, *params, cfgs=None, steps=None, groups=None, ngroups=None):
+        """The kind's host-side definition (prach_*_accumulate_logs) over the logs: see _from_logs."""
+        return _from_logs(cls(_ngroups(len(logs), groups, ngroups), *params), logs, groups, cfgs, steps)
 
 
 class Dist(_Reduction):
     """The distributions of ``ngroups`` trial groups (include/prach.h, prach_dist): ``delay_hist`` [ngroups, delay_bins] and ``ptc_hist``
     [ngroups, 256] as numpy uint64, and one int64 array of length ngroups per scalar field of DIST_FIELDS."""
-    _FIELDS, _STRUCT, _MERGE, _PARAMS = DIST_FIELDS, PrachDist, "prach_dist_merge", ("delay_bins", "delay_bin_ms")
-
-    def __init__(self, ngroups, delay_bins, delay_bin_ms=1):
-        import numpy as np
-        self.delay_bins, self.delay_bin_ms, self.ngroups = int(delay_bins), int(delay_bin_ms), int(ngroups)
-        self.delay_hist = np.zeros((self.ngroups, self.delay_bins), dtype=np.uint64)
-        self.ptc_hist = np.zeros((self.ngroups, DIST_PTC_BINS), dtype=np.uint64)
-        for f in DIST_FIELDS:
-            setattr(self, f, np.zeros(self.ngroups, dtype=np.int64))
-        self.delay_max[:] = -1
-
-    def spec(self):
-        return PrachDistSpec(self.delay_bins, self.delay_bin_ms, self.ngroups, 0)
-
-    def _arrays(self):
-        return [self.delay_hist, self.ptc_hist]
-
-    def _scalar(self, f):
-        return getattr(self, f)
+    _KIND, _PARAMS, _LOGS = "dist", (("delay_bins", int), ("delay_bin_ms", int, 1)), ""
+    _SPEC, _SPEC_OF = PrachDistSpec, lambda s: (s.delay_bins, s.delay_bin_ms, s.ngroups, 0)
+    _STRUCT, _FIELDS, _SCALAR_ATTRS = PrachDist, DIST_FIELDS, True
+    _NAMES, _SHAPE, _EXPOSE = ("delay_hist", "ptc_hist"), lambda s: ((s.delay_bins,), (DIST_PTC_BINS,)), "attrs"
 
     def _hists(self, g):
         return tuple(self._rows(g))
-
-    _cargs = _hists
 
 
 TIMELINE_MAX_BINS = 65536
@@ -144,30 +225,10 @@ class Timeline(_Reduction):
     """The timelines of ``ngroups`` trial groups (include/prach.h, prach_timeline): ``series[name]`` [ngroups, bins] as numpy uint64 for every name of
     TIMELINE_SERIES (bin b covers [b * bin_ms, (b + 1) * bin_ms)), and ``scalars[field]``, one int64 array of length ngroups per field of
     TIMELINE_FIELDS.  (Two dicts: `success` and `sojourn_sum` name a series and a scalar.)"""
-    _FIELDS, _STRUCT, _MERGE, _PARAMS = TIMELINE_FIELDS, PrachTimeline, "prach_timeline_merge", ("bins", "bin_ms")
-
-    def __init__(self, ngroups, bins, bin_ms=1):
-        import numpy as np
-        self.bins, self.bin_ms, self.ngroups = int(bins), int(bin_ms), int(ngroups)
-        self.series = {n: np.zeros((self.ngroups, self.bins), dtype=np.uint64) for n in TIMELINE_SERIES}
-        self.scalars = {f: np.zeros(self.ngroups, dtype=np.int64) for f in TIMELINE_FIELDS}
-        self.scalars["done_max"][:] = -1
-
-    def spec(self):
-        return PrachTimelineSpec(self.bins, self.bin_ms, self.ngroups, 0)
-
-    def _arrays(self):
-        return [self.series[n] for n in TIMELINE_SERIES]
-
-    def _scalar(self, f):
-        return self.scalars[f]
-
-    def _series(self, g):
-        """The five series of group g as the uint64_t *[5] the C side takes."""
-        return (C.POINTER(C.c_uint64) * 5)(*self._rows(g))
-
-    def _cargs(self, g):
-        return (self._series(g),)
+    _KIND, _PARAMS, _HOST, _LOGS, _NOUN = "timeline", (("bins", int), ("bin_ms", int, 1)), "array", "cfg", "timelines"
+    _SPEC, _SPEC_OF = PrachTimelineSpec, lambda s: (s.bins, s.bin_ms, s.ngroups, 0)
+    _STRUCT, _FIELDS = PrachTimeline, TIMELINE_FIELDS
+    _NAMES, _SHAPE, _EXPOSE = TIMELINE_SERIES, lambda s: ((s.bins,),) * 5, "dict"
 
 
 SOJOURN_MAX_ARRIVAL_BINS, SOJOURN_MAX_DELAY_BINS = 4096, 16384
@@ -186,29 +247,11 @@ class Sojourn(_Reduction):
     """The sojourn histograms of ``ngroups`` trial groups (include/prach.h, prach_sojourn): ``hist`` [ngroups, arrival_bins, delay_bins], ``row_arrived`` and
     ``row_delay_overflow`` [ngroups, arrival_bins] as numpy uint64 (row r covers arrivals in [r * arrival_bin_ms, (r + 1) * arrival_bin_ms)), and
     ``scalars[field]``, one int64 array of length ngroups per field of SOJOURN_FIELDS."""
-    _FIELDS, _STRUCT, _MERGE, _PARAMS = SOJOURN_FIELDS, PrachSojourn, "prach_sojourn_merge", ("arrival_bins", "arrival_bin_ms", "delay_bins", "delay_bin_ms")
-
-    def __init__(self, ngroups, arrival_bins, arrival_bin_ms, delay_bins, delay_bin_ms=1):
-        import numpy as np
-        self.arrival_bins, self.arrival_bin_ms, self.delay_bins, self.delay_bin_ms = int(arrival_bins), int(arrival_bin_ms), int(delay_bins), int(delay_bin_ms)
-        self.ngroups = int(ngroups)
-        self.hist = np.zeros((self.ngroups, self.arrival_bins, self.delay_bins), dtype=np.uint64)
-        self.row_arrived = np.zeros((self.ngroups, self.arrival_bins), dtype=np.uint64)
-        self.row_delay_overflow = np.zeros((self.ngroups, self.arrival_bins), dtype=np.uint64)
-        self.scalars = {f: np.zeros(self.ngroups, dtype=np.int64) for f in SOJOURN_FIELDS}
-        self.scalars["sojourn_max"][:] = -1
-
-    def spec(self):
-        return PrachSojournSpec(self.arrival_bins, self.arrival_bin_ms, self.delay_bins, self.delay_bin_ms, self.ngroups, 0)
-
-    def _arrays(self):
-        return [self.hist, self.row_arrived, self.row_delay_overflow]
-
-    def _scalar(self, f):
-        return self.scalars[f]
-
-    def _cargs(self, g):
-        return tuple(self._rows(g))
+    _KIND, _LOGS = "sojourn", "cfg"
+    _PARAMS = (("arrival_bins", int), ("arrival_bin_ms", int), ("delay_bins", int), ("delay_bin_ms", int, 1))
+    _SPEC, _SPEC_OF = PrachSojournSpec, lambda s: (s.arrival_bins, s.arrival_bin_ms, s.delay_bins, s.delay_bin_ms, s.ngroups, 0)
+    _STRUCT, _FIELDS = PrachSojourn, SOJOURN_FIELDS
+    _NAMES, _SHAPE, _EXPOSE = ("hist", "row_arrived", "row_delay_overflow"), lambda s: ((s.arrival_bins, s.delay_bins), (s.arrival_bins,), (s.arrival_bins,)), "attrs"
 
     def quantile(self, g, row, q):
         """Lower edge (ms) of the delay bin holding the max(1, ceil(q * n))-th smallest sojourn of arrival row ``row`` of group g (row -1: pooled over all
@@ -235,42 +278,10 @@ class Trace(_Reduction):
     name of TRACE_SERIES (bin b covers the subframes [b * bin_ms, (b + 1) * bin_ms)) — calls: preambles used, singles: preambles decoded, txop and
     collisions: what the subframes added to totalPreambleTxop and collisionPreambles, as the programs count them — and ``scalars[field]``, one int64
     array of length ngroups per field of TRACE_FIELDS.  There is no from_logs form: a per-UE log does not hold what happened per subframe."""
-    _FIELDS, _STRUCT, _MERGE, _PARAMS = TRACE_FIELDS, PrachTrace, "prach_trace_merge", ("bins", "bin_ms")
-
-    def __init__(self, ngroups, bins, bin_ms=1):
-        import numpy as np
-        self.bins, self.bin_ms, self.ngroups = int(bins), int(bin_ms), int(ngroups)
-        self.series = {n: np.zeros((self.ngroups, self.bins), dtype=np.uint64) for n in TRACE_SERIES}
-        self.scalars = {f: np.zeros(self.ngroups, dtype=np.int64) for f in TRACE_FIELDS}
-        self.scalars["calls_max"][:] = -1
-
-    def spec(self):
-        return PrachTraceSpec(self.bins, self.bin_ms, self.ngroups, 0)
-
-    def _arrays(self):
-        return [self.series[n] for n in TRACE_SERIES]
-
-    def _scalar(self, f):
-        return self.scalars[f]
-
-    def _series(self, g):
-        """The four series of group g as the uint64_t *[4] the C side takes."""
-        return (C.POINTER(C.c_uint64) * 4)(*self._rows(g))
-
-    def _cargs(self, g):
-        return (self._series(g),)
-
-    def merge(self, other):
-        """Adds every group of ``other`` (same bins, bin_ms and ngroups) to the same group of this one (prach_trace_merge).  Returns self."""
-        if (self.bins, self.bin_ms, self.ngroups) != (other.bins, other.bin_ms, other.ngroups):
-            raise ValueError("traces of different shapes do not merge")
-        for g in range(self.ngroups):
-            self.merge_group(g, other, g)
-        return self
-
-    def csv(self, labels=None) -> bytes:
-        """The CSV text of every group (prach_trace_format_csv), labelled labels[g] (default: the group number)."""
-        return _csv("prach_trace_format_csv", self, labels)
+    _KIND, _PARAMS, _HOST, _NOUN = "trace", (("bins", int), ("bin_ms", int, 1)), "array", "traces"
+    _SPEC, _SPEC_OF = PrachTraceSpec, lambda s: (s.bins, s.bin_ms, s.ngroups, 0)
+    _STRUCT, _FIELDS = PrachTrace, TRACE_FIELDS
+    _NAMES, _SHAPE, _EXPOSE = TRACE_SERIES, lambda s: ((s.bins,),) * 4, "dict"
 
     def collision_ratio(self, group):
         """(calls - singles) / calls per bin of one group, as float64: the share of the used preambles that collided (NaN where no preamble was used)."""
@@ -318,6 +329,8 @@ class Summary:
     """One row per trial (include/prach.h, prach_trial_summary): ``rows`` is a numpy structured array (summary_row_dtype) in trial order, ``permille`` the
     levels of its q[quantity][level] columns."""
 
+    _FORMAT_CSV = "prach_summary_format_csv"
+
     def __init__(self, n, permille=(500, 950, 990)):
         import numpy as np
         self.permille = tuple(int(m) for m in permille)
@@ -335,6 +348,9 @@ class Summary:
 
     def _rows_ptr(self):
         return self.rows.ctypes.data_as(C.POINTER(PrachTrialSummary))
+
+    def _out_ptrs(self):
+        return (self._rows_ptr(),)
 
     def stats(self, groups=None, ngroups=None):
         """Mean and spread per trial group (prach_summary_stats): a structured array [ngroups, 5 + 3 nq] of n, mean, sd, sem, min, max, the metrics in the
@@ -392,27 +408,10 @@ class Xtab(_Reduction):
     """The outcome cross-tabulations of ``ngroups`` trial groups (include/prach.h, prach_xtab): ``cells`` [ngroups, row_bins + 1, col_bins + 1] as numpy uint64
     (the last index of an axis is its overflow bin) and ``scalars[field]``, one int64 array of length ngroups per field of XTAB_FIELDS.  rows, cols: an axis
     each, (field, width, bins); who: the classes that enter, bits XTAB_SERVED | XTAB_UNSERVED | XTAB_IDLE."""
-    _FIELDS, _STRUCT, _MERGE, _PARAMS = XTAB_FIELDS, PrachXtab, "prach_xtab_merge", ("who", "rows", "cols")
-
-    def __init__(self, ngroups, rows, cols, who=XTAB_WHO["all"]):
-        import numpy as np
-        self.rows, self.cols, self.who, self.ngroups = xtab_axis(rows), xtab_axis(cols), int(who), int(ngroups)
-        self.cells = np.zeros((self.ngroups, max(self.rows[2], 0) + 1, max(self.cols[2], 0) + 1), dtype=np.uint64)
-        self.scalars = {f: np.zeros(self.ngroups, dtype=np.int64) for f in XTAB_FIELDS}
-        self.scalars["row_max"][:] = -1
-        self.scalars["col_max"][:] = -1
-
-    def spec(self):
-        return PrachXtabSpec(self.who, *self.rows, *self.cols, self.ngroups, (C.c_int32 * 2)(0, 0))
-
-    def _arrays(self):
-        return [self.cells]
-
-    def _scalar(self, f):
-        return self.scalars[f]
-
-    def _cargs(self, g):
-        return tuple(self._rows(g))
+    _KIND, _PARAMS, _LOGS = "xtab", (("rows", xtab_axis), ("cols", xtab_axis), ("who", int, XTAB_WHO["all"])), "cfg,steps"
+    _SPEC, _SPEC_OF = PrachXtabSpec, lambda s: (s.who, *s.rows, *s.cols, s.ngroups, (C.c_int32 * 2)(0, 0))
+    _STRUCT, _FIELDS, _MAXIMA = PrachXtab, XTAB_FIELDS, 2
+    _NAMES, _SHAPE, _EXPOSE = ("cells",), lambda s: ((max(s.rows[2], 0) + 1, max(s.cols[2], 0) + 1),), "attrs"
 
     def cell_clauses(self, row_bin, col_bin):
         """The two clauses (field, lo, hi) of a pick (Engine.run_trials_pick, where=) that select exactly the UEs counted in cell [row_bin, col_bin]; the last
@@ -509,6 +508,9 @@ class Pick:
 
     def _rows_ptr(self, t=0):
         return C.cast(self.rows.ctypes.data + t * self.rows.strides[0], C.POINTER(PrachPickRow))
+
+    def _out_ptrs(self):
+        return self._headers_ptr(), self._rows_ptr()
 
     def same_as(self, other):
         import numpy as np
@@ -608,27 +610,10 @@ class NomaCensus(_Reduction):
     """The NOMA.c outcome census of ``ngroups`` trial groups (include/prach.h, prach_noma_census): ``cells`` [ngroups, row_bins + 1, col_bins + 1] as numpy uint64
     (the last index of an axis is its overflow bin) and ``scalars[field]``, one int64 array of length ngroups per field of NOMA_CENSUS_FIELDS.  rows, cols: an
     axis each, (field, width, bins), a field of NOMA_FIELD_NAMES; who: the classes that enter, bits NOMA_SERVED | NOMA_PENDING | NOMA_IDLE | NOMA_DROPPED."""
-    _FIELDS, _STRUCT, _MERGE, _PARAMS = NOMA_CENSUS_FIELDS, PrachNomaCensus, "prach_noma_census_merge", ("who", "rows", "cols")
-
-    def __init__(self, ngroups, rows, cols, who=NOMA_WHO["all"]):
-        import numpy as np
-        self.rows, self.cols, self.who, self.ngroups = noma_axis(rows), noma_axis(cols), int(who), int(ngroups)
-        self.cells = np.zeros((self.ngroups, max(self.rows[2], 0) + 1, max(self.cols[2], 0) + 1), dtype=np.uint64)
-        self.scalars = {f: np.zeros(self.ngroups, dtype=np.int64) for f in NOMA_CENSUS_FIELDS}
-        self.scalars["row_max"][:] = -1
-        self.scalars["col_max"][:] = -1
-
-    def spec(self):
-        return PrachXtabSpec(self.who, *self.rows, *self.cols, self.ngroups, (C.c_int32 * 2)(0, 0))
-
-    def _arrays(self):
-        return [self.cells]
-
-    def _scalar(self, f):
-        return self.scalars[f]
-
-    def _cargs(self, g):
-        return tuple(self._rows(g))
+    _KIND, _PARAMS, _LOGS = "noma_census", (("rows", noma_axis), ("cols", noma_axis), ("who", int, NOMA_WHO["all"])), "cfg,steps"
+    _SPEC, _SPEC_OF = PrachXtabSpec, Xtab._SPEC_OF
+    _STRUCT, _FIELDS, _MAXIMA = PrachNomaCensus, NOMA_CENSUS_FIELDS, 2
+    _NAMES, _SHAPE, _EXPOSE = ("cells",), Xtab._SHAPE, "attrs"
 
     def cell_clauses(self, row_bin, col_bin):
         """The two clauses (field, lo, hi) that describe exactly the UEs counted in cell [row_bin, col_bin] — NOMA field ids; the last bin of an axis is its
@@ -665,38 +650,10 @@ class NomaTrace(_Reduction):
     sent, used: (sector, preamble) bins with a transmitter, singles: bins with exactly one, granted: UEs whose msg2 was set, pairs: power-domain pairs that
     received a grant, pair_one: the pairs of which one UE decoded — and ``scalars[field]``, one int64 array of length ngroups per field of NOMA_TRACE_FIELDS.
     There is no from_logs form: a per-UE log does not hold what happened per slot."""
-    _FIELDS, _STRUCT, _MERGE, _PARAMS = NOMA_TRACE_FIELDS, PrachNomaTrace, "prach_noma_trace_merge", ("bins", "bin_ms")
-
-    def __init__(self, ngroups, bins, bin_ms=5):
-        import numpy as np
-        self.bins, self.bin_ms, self.ngroups = int(bins), int(bin_ms), int(ngroups)
-        self.series = np.zeros((6, self.ngroups, 6, self.bins), dtype=np.uint64)
-        self.scalars = {f: np.zeros(self.ngroups, dtype=np.int64) for f in NOMA_TRACE_FIELDS}
-        self.scalars["tx_max"][:] = -1
-
-    def spec(self):
-        return PrachNomaTraceSpec(self.bins, self.bin_ms, self.ngroups, 0)
-
-    def _arrays(self):
-        return [self.series[q] for q in range(6)]
-
-    def _scalar(self, f):
-        return self.scalars[f]
-
-    def _series(self, g=None):
-        """The six series — of group g, or of all groups — as the uint64_t *[6] the C side takes."""
-        return (C.POINTER(C.c_uint64) * 6)(*[(self.series[q] if g is None else self.series[q, g]).ctypes.data_as(C.POINTER(C.c_uint64)) for q in range(6)])
-
-    def _cargs(self, g):
-        return (self._series(g),)
-
-    def merge(self, other):
-        """Adds every group of ``other`` (same bins, bin_ms and ngroups) to the same group of this one (prach_noma_trace_merge).  Returns self."""
-        if (self.bins, self.bin_ms, self.ngroups) != (other.bins, other.bin_ms, other.ngroups):
-            raise ValueError("traces of different shapes do not merge")
-        for g in range(self.ngroups):
-            self.merge_group(g, other, g)
-        return self
+    _KIND, _PARAMS, _RUN, _HOST, _NOUN = "noma_trace", (("bins", int), ("bin_ms", int, 5)), "array", "array", "traces"
+    _SPEC, _SPEC_OF = PrachNomaTraceSpec, lambda s: (s.bins, s.bin_ms, s.ngroups, 0)
+    _STRUCT, _FIELDS = PrachNomaTrace, NOMA_TRACE_FIELDS
+    _NAMES, _SHAPE, _EXPOSE = NOMA_TRACE_SERIES, lambda s: ((6, s.bins),) * 6, "stack"
 
     def named(self, name, group):
         """Series ``name`` of one group, summed over the sectors: [bins] float64."""
@@ -739,39 +696,10 @@ class NomaTimeline(_Reduction):
     ``dropped``, ``sojourn_sum`` and ``timer_sum`` by the bin of the UE's ARRIVAL, ``done`` by the bin of its completion — and ``scalars[field]``, one int64 array
     of length ngroups per field of NOMA_TIMELINE_FIELDS.  The sector is the UE's own, also under FLAG_NOMA_NONSECTOR (where the trace has sector 0 only).
     A sojourn HISTOGRAM by arrival time is the census's: run_trials_noma_census with rows ARRIVAL, cols SOJOURN, who served, read with NomaCensus.quantile."""
-    _FIELDS, _STRUCT, _MERGE, _PARAMS = NOMA_TIMELINE_FIELDS, PrachNomaTimeline, "prach_noma_timeline_merge", ("bins", "bin_ms")
-
-    def __init__(self, ngroups, bins, bin_ms=5):
-        import numpy as np
-        self.bins, self.bin_ms, self.ngroups = int(bins), int(bin_ms), int(ngroups)
-        self.series = np.zeros((6, self.ngroups, 6, self.bins), dtype=np.uint64)
-        self.arrivals, self.served, self.dropped, self.sojourn_sum, self.timer_sum, self.done = (self.series[q] for q in range(6))
-        self.scalars = {f: np.zeros(self.ngroups, dtype=np.int64) for f in NOMA_TIMELINE_FIELDS}
-        self.scalars["done_max"][:] = -1
-
-    def spec(self):
-        return PrachNomaTimelineSpec(self.bins, self.bin_ms, self.ngroups, 0)
-
-    def _arrays(self):
-        return [self.series[q] for q in range(6)]
-
-    def _scalar(self, f):
-        return self.scalars[f]
-
-    def _series(self, g=None):
-        """The six series — of group g, or of all groups — as the uint64_t *[6] the C side takes."""
-        return (C.POINTER(C.c_uint64) * 6)(*[(self.series[q] if g is None else self.series[q, g]).ctypes.data_as(C.POINTER(C.c_uint64)) for q in range(6)])
-
-    def _cargs(self, g):
-        return (self._series(g),)
-
-    def merge(self, other):
-        """Adds every group of ``other`` (same bins, bin_ms and ngroups) to the same group of this one (prach_noma_timeline_merge).  Returns self."""
-        if (self.bins, self.bin_ms, self.ngroups) != (other.bins, other.bin_ms, other.ngroups):
-            raise ValueError("timelines of different shapes do not merge")
-        for g in range(self.ngroups):
-            self.merge_group(g, other, g)
-        return self
+    _KIND, _PARAMS, _RUN, _HOST, _LOGS, _NOUN = "noma_timeline", (("bins", int), ("bin_ms", int, 5)), "array", "array", "cfg,steps", "timelines"
+    _SPEC, _SPEC_OF = PrachNomaTimelineSpec, lambda s: (s.bins, s.bin_ms, s.ngroups, 0)
+    _STRUCT, _FIELDS = PrachNomaTimeline, NOMA_TIMELINE_FIELDS
+    _NAMES, _SHAPE, _EXPOSE, _VIEWS = NOMA_TIMELINE_SERIES, lambda s: ((6, s.bins),) * 6, "stack", True
 
     def named(self, name, group, sector=None):
         """Series ``name`` of one group — of one sector, or summed over the sectors: [bins] float64."""
@@ -831,6 +759,8 @@ class NomaSummary:
     ``fields`` the up to four fields of NOMA_FIELD_NAMES behind n[x], sum[x], max[x] and q[x][level], ``permille`` the levels, ``who`` the classes whose UEs
     enter (bits NOMA_SERVED | NOMA_PENDING | NOMA_IDLE | NOMA_DROPPED)."""
 
+    _FORMAT_CSV = "prach_noma_summary_format_csv"
+
     def __init__(self, n, fields=("sojourn", "timer", "ptc", "lost"), who=NOMA_WHO["served"], permille=(500, 950, 990)):
         import numpy as np
         self.field_ids = tuple(noma_field(f) for f in fields)
@@ -853,6 +783,8 @@ class NomaSummary:
 
     def _rows_ptr(self):
         return self.rows.ctypes.data_as(C.POINTER(PrachNomaTrialSummary))
+
+    _out_ptrs = Summary._out_ptrs
 
     def stats(self, groups=None, ngroups=None):
         """Mean and spread per trial group (prach_noma_summary_stats): a structured array [ngroups, 4 + nfields (1 + nq)] of n, mean, sd, sem, min, max, the
@@ -969,48 +901,27 @@ def lib():
         L.prach_run_trials.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog))]
         L.prach_last_timing.argtypes = [vp, C.POINTER(PrachTiming)]
         u64p = C.POINTER(C.c_uint64)
-        L.prach_run_trials_dist.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachDistSpec),
-                                            C.POINTER(C.c_int32), C.POINTER(PrachDist), u64p, u64p]
-        L.prach_dist_accumulate_logs.argtypes = [C.POINTER(PrachDistSpec), C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachDist), u64p, u64p]
-        L.prach_dist_merge.argtypes = [C.POINTER(PrachDistSpec), C.POINTER(PrachDist), u64p, u64p, C.POINTER(PrachDist), u64p, u64p]
-        L.prach_dist_merge.restype = None
+        # the three or four public functions of every grouped kind, from the class declarations (_Reduction)
+        cfgp, uep = C.POINTER(PrachCfg), C.POINTER(PrachUeLog)
+        for R in (Dist, Timeline, Sojourn, Trace, Xtab, NomaCensus, NomaTrace, NomaTimeline):
+            sp, gp, ptrs = C.POINTER(R._SPEC), C.POINTER(R._STRUCT), {"flat": [u64p] * len(R._NAMES), "array": [C.POINTER(u64p)]}
+            getattr(L, f"prach_run_trials_{R._KIND}").argtypes = [vp, cfgp, C.c_int, C.POINTER(PrachResult), C.POINTER(uep), sp, C.POINTER(C.c_int32), gp] + ptrs[R._RUN]
+            merge, fmt = getattr(L, f"prach_{R._KIND}_merge"), getattr(L, f"prach_{R._KIND}_format_csv")
+            merge.argtypes, merge.restype = [sp, gp] + ptrs[R._HOST] + [gp] + ptrs[R._HOST], None
+            fmt.argtypes, fmt.restype = [sp, gp] + ptrs[R._HOST] + [C.c_char_p, C.c_char_p, C.c_size_t], C.c_size_t
+            if R._LOGS is not None:
+                getattr(L, f"prach_{R._KIND}_accumulate_logs").argtypes = [sp] + {"": [], "cfg": [cfgp], "cfg,steps": [cfgp, C.c_uint64]}[R._LOGS] + [uep, C.c_int, gp] + ptrs[R._RUN]
         L.prach_dist_delay_quantile.argtypes = [C.POINTER(PrachDistSpec), C.POINTER(PrachDist), u64p, C.c_double]
         L.prach_dist_delay_quantile.restype = C.c_int64
-        L.prach_dist_format_csv.argtypes = [C.POINTER(PrachDistSpec), C.POINTER(PrachDist), u64p, u64p, C.c_char_p, C.c_char_p, C.c_size_t]
-        L.prach_dist_format_csv.restype = C.c_size_t
         L.prach_dist_tile_ues.argtypes = []
-        u64pp = C.POINTER(u64p)
-        L.prach_run_trials_timeline.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachTimelineSpec),
-                                                C.POINTER(C.c_int32), C.POINTER(PrachTimeline), u64p, u64p, u64p, u64p, u64p]
-        L.prach_timeline_accumulate_logs.argtypes = [C.POINTER(PrachTimelineSpec), C.POINTER(PrachCfg), C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachTimeline),
-                                                     u64p, u64p, u64p, u64p, u64p]
-        L.prach_timeline_merge.argtypes = [C.POINTER(PrachTimelineSpec), C.POINTER(PrachTimeline), u64pp, C.POINTER(PrachTimeline), u64pp]
-        L.prach_timeline_merge.restype = None
-        L.prach_timeline_format_csv.argtypes = [C.POINTER(PrachTimelineSpec), C.POINTER(PrachTimeline), u64pp, C.c_char_p, C.c_char_p, C.c_size_t]
-        L.prach_timeline_format_csv.restype = C.c_size_t
         L.prach_timeline_tile_ues.argtypes = []
         L.prach_timeline_window_bins.argtypes = []
-        L.prach_run_trials_sojourn.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachSojournSpec),
-                                               C.POINTER(C.c_int32), C.POINTER(PrachSojourn), u64p, u64p, u64p]
-        L.prach_sojourn_accumulate_logs.argtypes = [C.POINTER(PrachSojournSpec), C.POINTER(PrachCfg), C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachSojourn),
-                                                    u64p, u64p, u64p]
-        L.prach_sojourn_merge.argtypes = [C.POINTER(PrachSojournSpec), C.POINTER(PrachSojourn), u64p, u64p, u64p, C.POINTER(PrachSojourn), u64p, u64p, u64p]
-        L.prach_sojourn_merge.restype = None
         L.prach_sojourn_quantile.argtypes = [C.POINTER(PrachSojournSpec), u64p, u64p, C.c_int, C.c_double]
         L.prach_sojourn_quantile.restype = C.c_int64
-        L.prach_sojourn_format_csv.argtypes = [C.POINTER(PrachSojournSpec), C.POINTER(PrachSojourn), u64p, u64p, u64p, C.c_char_p, C.c_char_p, C.c_size_t]
-        L.prach_sojourn_format_csv.restype = C.c_size_t
         L.prach_sojourn_tile_ues.argtypes = []
         L.prach_sojourn_window_words.argtypes = []
-        L.prach_run_trials_xtab.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachXtabSpec),
-                                            C.POINTER(C.c_int32), C.POINTER(PrachXtab), u64p]
-        L.prach_xtab_accumulate_logs.argtypes = [C.POINTER(PrachXtabSpec), C.POINTER(PrachCfg), C.c_uint64, C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachXtab), u64p]
-        L.prach_xtab_merge.argtypes = [C.POINTER(PrachXtabSpec), C.POINTER(PrachXtab), u64p, C.POINTER(PrachXtab), u64p]
-        L.prach_xtab_merge.restype = None
         L.prach_xtab_quantile.argtypes = [C.POINTER(PrachXtabSpec), u64p, C.c_int, C.c_double]
         L.prach_xtab_quantile.restype = C.c_int64
-        L.prach_xtab_format_csv.argtypes = [C.POINTER(PrachXtabSpec), C.POINTER(PrachXtab), u64p, C.c_char_p, C.c_char_p, C.c_size_t]
-        L.prach_xtab_format_csv.restype = C.c_size_t
         L.prach_xtab_tile_ues.argtypes = []
         L.prach_xtab_window_words.argtypes = []
         L.prach_run_trials_summary.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachSummarySpec),
@@ -1030,13 +941,6 @@ def lib():
         L.prach_run_trials_columns_device.argtypes = L.prach_run_trials_columns.argtypes
         L.prach_columns_from_logs.argtypes = [C.POINTER(PrachColumnsSpec), C.POINTER(PrachCfg), C.c_uint64, C.POINTER(PrachUeLog), C.c_int, C.c_void_p, C.c_uint64]
         L.prach_columns_tile_ues.argtypes = []
-        L.prach_run_trials_noma_census.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachXtabSpec),
-                                                   C.POINTER(C.c_int32), C.POINTER(PrachNomaCensus), u64p]
-        L.prach_noma_census_accumulate_logs.argtypes = [C.POINTER(PrachXtabSpec), C.POINTER(PrachCfg), C.c_uint64, C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachNomaCensus), u64p]
-        L.prach_noma_census_merge.argtypes = [C.POINTER(PrachXtabSpec), C.POINTER(PrachNomaCensus), u64p, C.POINTER(PrachNomaCensus), u64p]
-        L.prach_noma_census_merge.restype = None
-        L.prach_noma_census_format_csv.argtypes = [C.POINTER(PrachXtabSpec), C.POINTER(PrachNomaCensus), u64p, C.c_char_p, C.c_char_p, C.c_size_t]
-        L.prach_noma_census_format_csv.restype = C.c_size_t
         L.prach_noma_census_tile_ues.argtypes = []
         L.prach_run_trials_noma_columns.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachColumnsSpec),
                                                     C.POINTER(PrachNomaColumns), C.c_void_p, C.c_uint64]
@@ -1052,12 +956,6 @@ def lib():
         L.prach_noma_pick_format_csv.argtypes = L.prach_pick_format_csv.argtypes
         L.prach_noma_pick_format_csv.restype = C.c_size_t
         L.prach_noma_columns_from_logs.argtypes = [C.POINTER(PrachColumnsSpec), C.POINTER(PrachCfg), C.c_uint64, C.POINTER(PrachUeLog), C.c_int, C.c_void_p, C.c_uint64]
-        L.prach_run_trials_trace.argtypes = [vp, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachTraceSpec),
-                                             C.POINTER(C.c_int32), C.POINTER(PrachTrace), u64p, u64p, u64p, u64p]
-        L.prach_trace_merge.argtypes = [C.POINTER(PrachTraceSpec), C.POINTER(PrachTrace), u64pp, C.POINTER(PrachTrace), u64pp]
-        L.prach_trace_merge.restype = None
-        L.prach_trace_format_csv.argtypes = [C.POINTER(PrachTraceSpec), C.POINTER(PrachTrace), u64pp, C.c_char_p, C.c_char_p, C.c_size_t]
-        L.prach_trace_format_csv.restype = C.c_size_t
         L.prach_trace_tile_subframes.argtypes = []
         L.prach_cfg_defaults.argtypes = [C.POINTER(PrachCfg), C.c_int]
         L.prach_cfg_defaults.restype = None
@@ -1087,21 +985,7 @@ def lib():
         L.prach_results_csv_accumulate.argtypes = [C.POINTER(C.c_double), C.c_char_p]
         L.prach_results_csv_row.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_char_p, C.c_size_t]
         L.prach_results_csv_row.restype = C.c_size_t
-        u64p6 = C.POINTER(C.POINTER(C.c_uint64))
-        L.prach_run_trials_noma_trace.argtypes = [C.c_void_p, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachNomaTraceSpec),
-                                                  C.POINTER(C.c_int32), C.POINTER(PrachNomaTrace), u64p6]
-        L.prach_noma_trace_merge.argtypes = [C.POINTER(PrachNomaTraceSpec), C.POINTER(PrachNomaTrace), u64p6, C.POINTER(PrachNomaTrace), u64p6]
-        L.prach_noma_trace_merge.restype = None
-        L.prach_noma_trace_format_csv.argtypes = [C.POINTER(PrachNomaTraceSpec), C.POINTER(PrachNomaTrace), u64p6, C.c_char_p, C.c_char_p, C.c_size_t]
-        L.prach_noma_trace_format_csv.restype = C.c_size_t
         L.prach_noma_trace_tile_rows.argtypes = []
-        L.prach_run_trials_noma_timeline.argtypes = [C.c_void_p, C.POINTER(PrachCfg), C.c_int, C.POINTER(PrachResult), C.POINTER(C.POINTER(PrachUeLog)), C.POINTER(PrachNomaTimelineSpec),
-                                                     C.POINTER(C.c_int32), C.POINTER(PrachNomaTimeline), u64p6]
-        L.prach_noma_timeline_accumulate_logs.argtypes = [C.POINTER(PrachNomaTimelineSpec), C.POINTER(PrachCfg), C.c_uint64, C.POINTER(PrachUeLog), C.c_int, C.POINTER(PrachNomaTimeline), u64p6]
-        L.prach_noma_timeline_merge.argtypes = [C.POINTER(PrachNomaTimelineSpec), C.POINTER(PrachNomaTimeline), u64p6, C.POINTER(PrachNomaTimeline), u64p6]
-        L.prach_noma_timeline_merge.restype = None
-        L.prach_noma_timeline_format_csv.argtypes = [C.POINTER(PrachNomaTimelineSpec), C.POINTER(PrachNomaTimeline), u64p6, C.c_char_p, C.c_char_p, C.c_size_t]
-        L.prach_noma_timeline_format_csv.restype = C.c_size_t
         L.prach_noma_timeline_tile_ues.argtypes = []
         L.prach_noma_timeline_window_bins.argtypes = []
         _lib = L
@@ -1178,15 +1062,21 @@ class Engine:
             raise PrachError(rc, f"({name})")
         return list(res), logs
 
-    def _call_reduced(self, name, cfgs, red, groups, want_logs):
-        """... with the reduction `red` (a Dist, a Timeline or a Sojourn), which takes what the device made.  Returns (results, logs, red)."""
+    def _call_reduced(self, red, cfgs, groups, want_logs):
+        """... with the grouped reduction `red` (a _Reduction), which takes what the device made.  Returns (results, logs, red)."""
         sp = red.spec()
         gg = (red._STRUCT * red.ngroups)()
         gp = None if groups is None else (C.c_int32 * len(cfgs))(*[int(g) for g in groups])
-        res, logs = self._call(name, cfgs, want_logs, C.byref(sp), gp, gg, *[a.ctypes.data_as(C.POINTER(C.c_uint64)) for a in red._arrays()])
+        res, logs = self._call(f"prach_run_trials_{red._KIND}", cfgs, want_logs, C.byref(sp), gp, gg, *red._ptrs(red._RUN))
         for g in range(red.ngroups):
             red._store(g, gg[g])
         return res, logs, red
+
+    def _call_per_trial(self, name, out, cfgs, want_logs):
+        """... with `out` (a Summary, a NomaSummary, a Pick or a NomaPick), whose rows per trial the device fills.  Returns (results, logs, out)."""
+        sp = out.spec()
+        res, logs = self._call(name, cfgs, want_logs, C.byref(sp), *out._out_ptrs())
+        return res, logs, out
 
     def run_trials(self, cfgs, want_logs=False):
         """Run the trials concurrently on the device. Returns (results, logs) — logs[k] is a ctypes
@@ -1198,46 +1088,39 @@ class Engine:
         """run_trials plus the distributions of access delay and preamble transmissions of the successful UEs, reduced on the device
         (prach_run_trials_dist).  groups: the group of every trial (None: one group per trial); ngroups: the number of groups (default: the
         largest group id + 1).  Returns (results, logs, Dist)."""
-        return self._call_reduced("prach_run_trials_dist", cfgs, Dist(_ngroups(len(cfgs), groups, ngroups), delay_bins, delay_bin_ms), groups, want_logs)
+        return self._call_reduced(Dist(_ngroups(len(cfgs), groups, ngroups), delay_bins, delay_bin_ms), cfgs, groups, want_logs)
 
     def run_trials_timeline(self, cfgs, bins, bin_ms=1, groups=None, want_logs=False, ngroups=None):
         """run_trials plus the timelines per trial group — arrivals, successes, sojourn and timer sums by arrival time, completions by completion time —
         reduced on the device from the per-UE log records the simulation kernels leave there (prach_run_trials_timeline; Beta.c and
         RandomAccessWithNOMA trials only).  groups / ngroups / want_logs as in run_trials_dist.  Returns (results, logs, Timeline)."""
-        return self._call_reduced("prach_run_trials_timeline", cfgs, Timeline(_ngroups(len(cfgs), groups, ngroups), bins, bin_ms), groups, want_logs)
+        return self._call_reduced(Timeline(_ngroups(len(cfgs), groups, ngroups), bins, bin_ms), cfgs, groups, want_logs)
 
     def run_trials_sojourn(self, cfgs, arrival_bins, arrival_bin_ms, delay_bins, delay_bin_ms, groups=None, want_logs=False, ngroups=None):
         """run_trials plus the histogram of the time from arrival to Msg4 by arrival row per trial group, reduced on the device from the per-UE log records
         the simulation kernels leave there (prach_run_trials_sojourn; Beta.c and RandomAccessWithNOMA trials only).  groups / ngroups / want_logs as in
         run_trials_dist.  Returns (results, logs, Sojourn)."""
-        return self._call_reduced("prach_run_trials_sojourn", cfgs,
-                                  Sojourn(_ngroups(len(cfgs), groups, ngroups), arrival_bins, arrival_bin_ms, delay_bins, delay_bin_ms), groups, want_logs)
+        return self._call_reduced(Sojourn(_ngroups(len(cfgs), groups, ngroups), arrival_bins, arrival_bin_ms, delay_bins, delay_bin_ms), cfgs, groups, want_logs)
 
     def run_trials_xtab(self, cfgs, rows=("arrival", 500, 20), cols=("state", 1, 7), who=XTAB_WHO["all"], groups=None, want_logs=False, ngroups=None):
         """run_trials plus the outcome cross-tabulation per trial group — a table of two per-UE quantities (rows, cols: (field, width, bins), a field of
         XTAB_FIELD_NAMES) over the classes of UEs in ``who`` — reduced on the device from the per-UE log records the simulation kernels leave there
         (prach_run_trials_xtab; Beta.c and RandomAccessWithNOMA trials only).  The default: what became of the UEs by when they arrived.  groups / ngroups /
         want_logs as in run_trials_dist.  Returns (results, logs, Xtab)."""
-        return self._call_reduced("prach_run_trials_xtab", cfgs, Xtab(_ngroups(len(cfgs), groups, ngroups), rows, cols, who), groups, want_logs)
+        return self._call_reduced(Xtab(_ngroups(len(cfgs), groups, ngroups), rows, cols, who), cfgs, groups, want_logs)
 
     def run_trials_summary(self, cfgs, permille=(500, 950, 990), want_logs=False):
         """run_trials plus one summary row per trial — counts, sums, maxima and exact order statistics (levels in permille) of the sojourn, of `timer` and of
         the preamble transmissions over the trial's successful UEs — selected on the device (prach_run_trials_summary; Beta.c and RandomAccessWithNOMA
         trials only).  Returns (results, logs, Summary); Summary.stats() gives mean and spread across the trials."""
-        sm = Summary(len(cfgs), permille)
-        sp = sm.spec()
-        res, logs = self._call("prach_run_trials_summary", cfgs, want_logs, C.byref(sp), sm._rows_ptr())
-        return res, logs, sm
+        return self._call_per_trial("prach_run_trials_summary", Summary(len(cfgs), permille), cfgs, want_logs)
 
     def run_trials_pick(self, cfgs, where=(), order="index", key=None, k=16, who=XTAB_WHO["all"], want_logs=False):
         """run_trials plus, per trial, the k UEs that match the clauses ``where`` ((field, lo, hi), a field of XTAB_FIELD_NAMES, lo <= value <= hi) among the
         classes ``who`` — the first k by UE index (order "index"), or the k with the "largest" / "smallest" value of the field ``key``, equal keys in ascending
         UE index — as records, and the exact number of matches, selected on the device (prach_run_trials_pick; Beta.c and RandomAccessWithNOMA trials only).
         Xtab.cell_clauses gives the ``where`` of a cell of a cross-tabulation.  Returns (results, logs, Pick)."""
-        pk = Pick(len(cfgs), where, order, key, k, who)
-        sp = pk.spec()
-        res, logs = self._call("prach_run_trials_pick", cfgs, want_logs, C.byref(sp), pk._headers_ptr(), pk._rows_ptr())
-        return res, logs, pk
+        return self._call_per_trial("prach_run_trials_pick", Pick(len(cfgs), where, order, key, k, who), cfgs, want_logs)
 
     def run_trials_columns(self, cfgs, fields, device=False, want_logs=False):
         """run_trials plus the per-UE columns: for every UE of every trial the asked-for ``fields`` — names of XTAB_FIELD_NAMES, the menu of the
@@ -1276,25 +1159,19 @@ class Engine:
         NOMA_FIELD_NAMES) over the classes of UEs in ``who`` — reduced on the device from the log records prach::noma_kernel leaves there
         (prach_run_trials_noma_census; NOMA.c trials with Philox only).  The default: what became of the UEs by when they arrived.  groups / ngroups /
         want_logs as in run_trials_dist.  Returns (results, logs, NomaCensus)."""
-        return self._call_reduced("prach_run_trials_noma_census", cfgs, NomaCensus(_ngroups(len(cfgs), groups, ngroups), rows, cols, who), groups, want_logs)
+        return self._call_reduced(NomaCensus(_ngroups(len(cfgs), groups, ngroups), rows, cols, who), cfgs, groups, want_logs)
 
     def run_trials_noma_summary(self, cfgs, fields=("sojourn", "timer", "ptc", "lost"), who=NOMA_WHO["served"], permille=(500, 950, 990), want_logs=False):
         """run_trials plus one summary row per NOMA.c trial — the four class counts and, for up to four ``fields`` of NOMA_FIELD_NAMES over the UEs of the
         classes ``who`` whose value is defined, their number, sum, maximum and EXACT order statistics at the levels ``permille`` — selected on the device
         (prach_run_trials_noma_summary; NOMA.c trials with Philox only).  NomaSummary.stats gives the spread between the trials of a group.  Returns
         (results, logs, NomaSummary)."""
-        sm = NomaSummary(len(cfgs), fields, who, permille)
-        sp = sm.spec()
-        res, logs = self._call("prach_run_trials_noma_summary", cfgs, want_logs, C.byref(sp), sm._rows_ptr())
-        return res, logs, sm
+        return self._call_per_trial("prach_run_trials_noma_summary", NomaSummary(len(cfgs), fields, who, permille), cfgs, want_logs)
 
     def run_trials_noma_pick(self, cfgs, where=(), order="index", key=None, k=16, who=NOMA_WHO["all"], want_logs=False):
         """run_trials_pick for NOMA.c trials with Philox: clauses, key and ``who`` over the NOMA menu (fields of NOMA_FIELD_NAMES, classes of NOMA_WHO), selected
         on the device (prach_run_trials_noma_pick).  NomaCensus.cell_clauses gives the ``where`` of a census cell.  Returns (results, logs, NomaPick)."""
-        pk = NomaPick(len(cfgs), where, order, key, k, who)
-        sp = pk.spec()
-        res, logs = self._call("prach_run_trials_noma_pick", cfgs, want_logs, C.byref(sp), pk._headers_ptr(), pk._rows_ptr())
-        return res, logs, pk
+        return self._call_per_trial("prach_run_trials_noma_pick", NomaPick(len(cfgs), where, order, key, k, who), cfgs, want_logs)
 
     def run_trials_noma_columns(self, cfgs, fields, device=False, want_logs=False):
         """run_trials_columns for NOMA.c trials with Philox: ``fields`` are names of NOMA_FIELD_NAMES, -1 where undefined, or ``raw:NAME``
@@ -1306,35 +1183,21 @@ class Engine:
         """run_trials plus NOMA.c's channel trace per trial group — per access slot and sector the preambles sent, the bins used and alone, the UEs granted, the
         power-domain pairs and the pairs that decoded one UE, by time — recorded by prach::noma_kernel while it runs and reduced on the device
         (prach_run_trials_noma_trace; NOMA.c trials with Philox only).  groups / ngroups / want_logs as in run_trials_dist.  Returns (results, logs, NomaTrace)."""
-        red = NomaTrace(_ngroups(len(cfgs), groups, ngroups), bins, bin_ms)
-        sp = red.spec()
-        gg = (PrachNomaTrace * red.ngroups)()
-        gp = None if groups is None else (C.c_int32 * len(cfgs))(*[int(g) for g in groups])
-        res, logs = self._call("prach_run_trials_noma_trace", cfgs, want_logs, C.byref(sp), gp, gg, red._series())
-        for g in range(red.ngroups):
-            red._store(g, gg[g])
-        return res, logs, red
+        return self._call_reduced(NomaTrace(_ngroups(len(cfgs), groups, ngroups), bins, bin_ms), cfgs, groups, want_logs)
 
     def run_trials_noma_timeline(self, cfgs, bins, bin_ms=5, groups=None, ngroups=None, want_logs=False):
         """run_trials plus NOMA.c's timeline per trial group and sector — arrivals, served, dropped, the sojourn and timer sums of the served by arrival time, and
         the completions by completion time, on the bins of run_trials_noma_trace — reduced on the device from the log records the simulation kernel leaves there
         (prach_run_trials_noma_timeline; NOMA.c trials with Philox only).  groups / ngroups / want_logs as in run_trials_dist.  Returns
         (results, logs, NomaTimeline)."""
-        red = NomaTimeline(_ngroups(len(cfgs), groups, ngroups), bins, bin_ms)
-        sp = red.spec()
-        gg = (PrachNomaTimeline * red.ngroups)()
-        gp = None if groups is None else (C.c_int32 * len(cfgs))(*[int(g) for g in groups])
-        res, logs = self._call("prach_run_trials_noma_timeline", cfgs, want_logs, C.byref(sp), gp, gg, red._series())
-        for g in range(red.ngroups):
-            red._store(g, gg[g])
-        return res, logs, red
+        return self._call_reduced(NomaTimeline(_ngroups(len(cfgs), groups, ngroups), bins, bin_ms), cfgs, groups, want_logs)
 
     def run_trials_trace(self, cfgs, bins, bin_ms=1, groups=None, want_logs=False, ngroups=None):
         """run_trials plus the per-subframe preamble trace per trial group — preambles used (calls), decoded (singles) and what the subframes added to
         totalPreambleTxop and collisionPreambles, by time — recorded by the simulation kernels while they run and reduced on the device
         (prach_run_trials_trace; Beta.c and RandomAccessWithNOMA trials only).  groups / ngroups / want_logs as in run_trials_dist.  Returns
         (results, logs, Trace)."""
-        return self._call_reduced("prach_run_trials_trace", cfgs, Trace(_ngroups(len(cfgs), groups, ngroups), bins, bin_ms), groups, want_logs)
+        return self._call_reduced(Trace(_ngroups(len(cfgs), groups, ngroups), bins, bin_ms), cfgs, groups, want_logs)
 
     @staticmethod
     def _log_buffers(cfgs, want_logs):
@@ -1463,38 +1326,27 @@ def _log_ptr(lg):
     return C.cast(lg, C.POINTER(PrachUeLog)), len(lg), lg
 
 
-def _from_logs(name, red, logs, groups, cfgs=None):
-    """Adds every log to its group of `red` with the library's host-side definition `name` (which takes the trial's config in front of the log, if cfgs)."""
+def _from_logs(red, logs, groups, cfgs=None, steps=None):
+    """Adds every log to its group of `red` with the kind's host-side definition, prach_<kind>_accumulate_logs, which takes the trial's config (if cfgs) and
+    the subframes it ran (if steps) in front of the log."""
+    name = f"prach_{red._KIND}_accumulate_logs"
     sp = red.spec()
     for k, lg in enumerate(logs):
         g = k if groups is None else int(groups[k])
         ptr, nue, _keep = _log_ptr(lg)
         d = red._group(g)
-        rc = getattr(lib(), name)(C.byref(sp), *([C.byref(cfgs[k])] if cfgs is not None else []), ptr, nue, C.byref(d), *red._rows(g))
+        more = ([C.byref(cfgs[k])] if cfgs is not None else []) + ([int(steps[k])] if steps is not None else [])
+        rc = getattr(lib(), name)(C.byref(sp), *more, ptr, nue, C.byref(d), *red._ptrs(red._RUN, g))
         if rc != OK:
             raise PrachError(rc, f"({name})")
         red._store(g, d)
     return red
 
 
-def _csv(name, red, labels):
-    """The CSV text of every group of `red` from the library's formatter `name`: asked for its size first, then filled."""
-    out = b""
-    sp = red.spec()
-    for g in range(red.ngroups):
-        d = red._group(g)
-        args = (C.byref(sp), C.byref(d), *red._cargs(g), str(g if labels is None else labels[g]).encode())
-        need = getattr(lib(), name)(*args, None, 0)
-        buf = C.create_string_buffer(need + 1)
-        n = getattr(lib(), name)(*args, buf, need + 1)
-        out += buf.raw[:n]
-    return out
-
-
 def dist_from_logs(logs, delay_bins, delay_bin_ms=1, groups=None, ngroups=None) -> Dist:
     """The host-side definition of the distributions (prach_dist_accumulate_logs): logs[k] is one trial's per-UE log — a ctypes array of PrachUeLog
     or an int32 array of shape [nUE, 16] — added to group groups[k] (None: group k)."""
-    return _from_logs("prach_dist_accumulate_logs", Dist(_ngroups(len(logs), groups, ngroups), delay_bins, delay_bin_ms), logs, groups)
+    return Dist.from_logs(logs, delay_bins, delay_bin_ms, groups=groups, ngroups=ngroups)
 
 
 def dist_quantile(dist: Dist, g: int, q: float) -> int:
@@ -1505,7 +1357,7 @@ def dist_quantile(dist: Dist, g: int, q: float) -> int:
 
 def dist_csv(dist: Dist, labels=None) -> bytes:
     """The CSV text of every group (prach_dist_format_csv), labelled labels[g] (default: the group number)."""
-    return _csv("prach_dist_format_csv", dist, labels)
+    return dist.csv(labels)
 
 
 def timeline_tile_ues() -> int:
@@ -1519,12 +1371,12 @@ def timeline_window_bins() -> int:
 def timeline_from_logs(cfgs, logs, bins, bin_ms=1, groups=None, ngroups=None) -> Timeline:
     """The host-side definition of the timelines (prach_timeline_accumulate_logs): logs[k] is the per-UE log of the trial with config cfgs[k] — a ctypes
     array of PrachUeLog or an int32 array of shape [nUE, 16] — added to group groups[k] (None: group k)."""
-    return _from_logs("prach_timeline_accumulate_logs", Timeline(_ngroups(len(logs), groups, ngroups), bins, bin_ms), logs, groups, cfgs)
+    return Timeline.from_logs(logs, bins, bin_ms, cfgs=cfgs, groups=groups, ngroups=ngroups)
 
 
 def timeline_csv(tl: Timeline, labels=None) -> bytes:
     """The CSV text of every group (prach_timeline_format_csv), labelled labels[g] (default: the group number)."""
-    return _csv("prach_timeline_format_csv", tl, labels)
+    return tl.csv(labels)
 
 
 def sojourn_tile_ues() -> int:
@@ -1538,13 +1390,12 @@ def sojourn_window_words() -> int:
 def sojourn_from_logs(cfgs, logs, arrival_bins, arrival_bin_ms, delay_bins, delay_bin_ms, groups=None, ngroups=None) -> Sojourn:
     """The host-side definition of the sojourn histograms (prach_sojourn_accumulate_logs): logs[k] is the per-UE log of the trial with config cfgs[k] — a
     ctypes array of PrachUeLog or an int32 array of shape [nUE, 16] — added to group groups[k] (None: group k)."""
-    return _from_logs("prach_sojourn_accumulate_logs", Sojourn(_ngroups(len(logs), groups, ngroups), arrival_bins, arrival_bin_ms, delay_bins, delay_bin_ms),
-                      logs, groups, cfgs)
+    return Sojourn.from_logs(logs, arrival_bins, arrival_bin_ms, delay_bins, delay_bin_ms, cfgs=cfgs, groups=groups, ngroups=ngroups)
 
 
 def sojourn_csv(sj: Sojourn, labels=None) -> bytes:
     """The CSV text of every group (prach_sojourn_format_csv), labelled labels[g] (default: the group number)."""
-    return _csv("prach_sojourn_format_csv", sj, labels)
+    return sj.csv(labels)
 
 
 def trace_tile_subframes() -> int:
@@ -1553,7 +1404,7 @@ def trace_tile_subframes() -> int:
 
 def trace_csv(tr: Trace, labels=None) -> bytes:
     """The CSV text of every group (prach_trace_format_csv), labelled labels[g] (default: the group number)."""
-    return _csv("prach_trace_format_csv", tr, labels)
+    return tr.csv(labels)
 
 
 def noma_trace_tile_rows() -> int:
@@ -1571,27 +1422,17 @@ def noma_timeline_window_bins() -> int:
 def noma_timeline_from_logs(cfgs, steps, logs, bins, bin_ms=5, groups=None, ngroups=None) -> NomaTimeline:
     """The host-side definition of the NOMA timelines (prach_noma_timeline_accumulate_logs): logs[k] is the per-UE log of the NOMA.c trial with config cfgs[k] that
     ran steps[k] subframes (prach_result.steps) — a ctypes array of PrachUeLog or an int32 array of shape [nUE, 16] — added to group groups[k] (None: group k)."""
-    tl = NomaTimeline(_ngroups(len(logs), groups, ngroups), bins, bin_ms)
-    sp = tl.spec()
-    for k, lg in enumerate(logs):
-        g = k if groups is None else int(groups[k])
-        ptr, nue, _keep = _log_ptr(lg)
-        d = tl._group(g)
-        rc = lib().prach_noma_timeline_accumulate_logs(C.byref(sp), C.byref(cfgs[k]), int(steps[k]), ptr, nue, C.byref(d), tl._series(g))
-        if rc != OK:
-            raise PrachError(rc, "(prach_noma_timeline_accumulate_logs)")
-        tl._store(g, d)
-    return tl
+    return NomaTimeline.from_logs(logs, bins, bin_ms, cfgs=cfgs, steps=steps, groups=groups, ngroups=ngroups)
 
 
 def noma_timeline_csv(tl: NomaTimeline, labels=None) -> bytes:
     """The CSV text of every group (prach_noma_timeline_format_csv), labelled labels[g] (default: the group number)."""
-    return _csv("prach_noma_timeline_format_csv", tl, labels)
+    return tl.csv(labels)
 
 
 def noma_trace_csv(tr: NomaTrace, labels=None) -> bytes:
     """The CSV text of every group (prach_noma_trace_format_csv), labelled labels[g] (default: the group number)."""
-    return _csv("prach_noma_trace_format_csv", tr, labels)
+    return tr.csv(labels)
 
 
 def summary_max_value() -> int:
@@ -1615,14 +1456,15 @@ def summary_from_logs(cfgs, logs, permille=(500, 950, 990)) -> Summary:
 def summary_csv(sm: Summary, groups=None, ngroups=None, labels=None) -> bytes:
     """The CSV text of the statistics of every group of trials (prach_summary_stats, prach_summary_format_csv), labelled labels[g] (default: the group
     number): `label,metric,n,mean,sd,sem,min,max`."""
+    fmt = getattr(lib(), sm._FORMAT_CSV)
     st = sm.stats(groups, ngroups)
     sp = sm.spec()
     out = b""
     for g in range(st.shape[0]):
         args = (C.byref(sp), st[g].ctypes.data_as(C.POINTER(PrachStat)), str(g if labels is None else labels[g]).encode())
-        need = lib().prach_summary_format_csv(*args, None, 0)
+        need = fmt(*args, None, 0)
         buf = C.create_string_buffer(need + 1)
-        n = lib().prach_summary_format_csv(*args, buf, need + 1)
+        n = fmt(*args, buf, need + 1)
         out += buf.raw[:n]
     return out
 
@@ -1644,16 +1486,7 @@ def noma_summary_from_logs(cfgs, steps, logs, fields=("sojourn", "timer", "ptc",
 def noma_summary_csv(sm: NomaSummary, groups=None, ngroups=None, labels=None) -> bytes:
     """The CSV text of the statistics of every group of trials (prach_noma_summary_stats, prach_noma_summary_format_csv), labelled labels[g] (default: the
     group number): `label,metric,n,mean,sd,sem,min,max`."""
-    st = sm.stats(groups, ngroups)
-    sp = sm.spec()
-    out = b""
-    for g in range(st.shape[0]):
-        args = (C.byref(sp), st[g].ctypes.data_as(C.POINTER(PrachStat)), str(g if labels is None else labels[g]).encode())
-        need = lib().prach_noma_summary_format_csv(*args, None, 0)
-        buf = C.create_string_buffer(need + 1)
-        n = lib().prach_noma_summary_format_csv(*args, buf, need + 1)
-        out += buf.raw[:n]
-    return out
+    return summary_csv(sm, groups, ngroups, labels)
 
 
 def _pick_from_logs(fn, pk, cfgs, steps, logs):
@@ -1712,36 +1545,25 @@ def xtab_window_words() -> int:
 def xtab_from_logs(cfgs, steps, logs, rows=("arrival", 500, 20), cols=("state", 1, 7), who=XTAB_WHO["all"], groups=None, ngroups=None) -> Xtab:
     """The host-side definition of the cross-tabulation (prach_xtab_accumulate_logs): logs[k] is the per-UE log of the trial with config cfgs[k] that ran
     steps[k] subframes (prach_result.steps) — a ctypes array of PrachUeLog or an int32 array of shape [nUE, 16] — added to group groups[k] (None: group k)."""
-    xt = Xtab(_ngroups(len(logs), groups, ngroups), rows, cols, who)
-    sp = xt.spec()
-    for k, lg in enumerate(logs):
-        g = k if groups is None else int(groups[k])
-        ptr, nue, _keep = _log_ptr(lg)
-        d = xt._group(g)
-        rc = lib().prach_xtab_accumulate_logs(C.byref(sp), C.byref(cfgs[k]), int(steps[k]), ptr, nue, C.byref(d), *xt._rows(g))
-        if rc != OK:
-            raise PrachError(rc, "(prach_xtab_accumulate_logs)")
-        xt._store(g, d)
-    return xt
+    return Xtab.from_logs(logs, rows, cols, who, cfgs=cfgs, steps=steps, groups=groups, ngroups=ngroups)
 
 
 def xtab_csv(xt: Xtab, labels=None) -> bytes:
     """The CSV text of every group (prach_xtab_format_csv), labelled labels[g] (default: the group number)."""
-    return _csv("prach_xtab_format_csv", xt, labels)
+    return xt.csv(labels)
 
 
 def columns_tile_ues() -> int:
     return lib().prach_columns_tile_ues()
 
 
-def columns_from_logs(cfgs, steps, logs, fields) -> Columns:
-    """The host-side definition of the columns (prach_columns_from_logs): trial k from logs[k], the per-UE log of the trial with config cfgs[k] that ran
-    steps[k] subframes (prach_result.steps) — a ctypes array of PrachUeLog, as Engine.run_trials returns it, or an int32 array of shape [nUE, 16].  The class
-    counts of the headers are those of the definition's own STATE column."""
+def _columns_from_logs(name, make_spec, hdr_dtype, classes, cls, cfgs, steps, logs, fields):
+    """What columns_from_logs and noma_columns_from_logs share.  classes: the headers' class counts in the order of the menu's STATE values, the last one taking
+    every state from its own on."""
     import numpy as np
-    sp, ids = columns_spec(fields)
-    state, _ = columns_spec(["state"])
-    hdr = np.zeros(len(logs), dtype=columns_header_dtype())
+    sp, ids = make_spec(fields)
+    state, _ = make_spec(["state"])
+    hdr = np.zeros(len(logs), dtype=hdr_dtype)
     ptrs = [_log_ptr(lg) for lg in logs]
     hdr["nUE"] = [nue for _, nue, _ in ptrs]
     hdr["offset"] = np.concatenate([[0], np.cumsum(hdr["nUE"], dtype=np.uint64)[:-1]]) if len(logs) else []
@@ -1750,11 +1572,19 @@ def columns_from_logs(cfgs, steps, logs, fields) -> Columns:
     for k, (ptr, nue, _keep) in enumerate(ptrs):
         st = np.empty(nue, dtype=np.int32)
         for spec, out, stride in ((sp, data.ctypes.data + 4 * int(hdr["offset"][k]), rows), (state, st.ctypes.data, nue)):
-            rc = lib().prach_columns_from_logs(C.byref(spec), C.byref(cfgs[k]), int(steps[k]), ptr, nue, out, stride)
+            rc = getattr(lib(), name)(C.byref(spec), C.byref(cfgs[k]), int(steps[k]), ptr, nue, out, stride)
             if rc != OK:
-                raise PrachError(rc, "(prach_columns_from_logs)")
-        hdr["idle"][k], hdr["served"][k], hdr["unserved"][k] = (st == 0).sum(), (st == 1).sum(), (st >= 2).sum()
-    return Columns(ids, hdr, data[:len(ids)])
+                raise PrachError(rc, f"({name})")
+        for v, c in enumerate(classes):
+            hdr[c][k] = (st == v).sum() if v < len(classes) - 1 else (st >= v).sum()
+    return cls(ids, hdr, data[:len(ids)])
+
+
+def columns_from_logs(cfgs, steps, logs, fields) -> Columns:
+    """The host-side definition of the columns (prach_columns_from_logs): trial k from logs[k], the per-UE log of the trial with config cfgs[k] that ran
+    steps[k] subframes (prach_result.steps) — a ctypes array of PrachUeLog, as Engine.run_trials returns it, or an int32 array of shape [nUE, 16].  The class
+    counts of the headers are those of the definition's own STATE column."""
+    return _columns_from_logs("prach_columns_from_logs", columns_spec, columns_header_dtype(), ("idle", "served", "unserved"), Columns, cfgs, steps, logs, fields)
 
 
 def noma_census_tile_ues() -> int:
@@ -1764,41 +1594,16 @@ def noma_census_tile_ues() -> int:
 def noma_census_from_logs(cfgs, steps, logs, rows=("arrival", 500, 20), cols=("state", 1, 9), who=NOMA_WHO["all"], groups=None, ngroups=None) -> NomaCensus:
     """The host-side definition of the NOMA census (prach_noma_census_accumulate_logs): logs[k] is the per-UE log of the NOMA.c trial with config cfgs[k] that
     ran steps[k] subframes (prach_result.steps) — a ctypes array of PrachUeLog or an int32 array of shape [nUE, 16] — added to group groups[k] (None: group k)."""
-    cs = NomaCensus(_ngroups(len(logs), groups, ngroups), rows, cols, who)
-    sp = cs.spec()
-    for k, lg in enumerate(logs):
-        g = k if groups is None else int(groups[k])
-        ptr, nue, _keep = _log_ptr(lg)
-        d = cs._group(g)
-        rc = lib().prach_noma_census_accumulate_logs(C.byref(sp), C.byref(cfgs[k]), int(steps[k]), ptr, nue, C.byref(d), *cs._rows(g))
-        if rc != OK:
-            raise PrachError(rc, "(prach_noma_census_accumulate_logs)")
-        cs._store(g, d)
-    return cs
+    return NomaCensus.from_logs(logs, rows, cols, who, cfgs=cfgs, steps=steps, groups=groups, ngroups=ngroups)
 
 
 def noma_census_csv(cs: NomaCensus, labels=None) -> bytes:
     """The CSV text of every group (prach_noma_census_format_csv: the lines of xtab_csv), labelled labels[g] (default: the group number)."""
-    return _csv("prach_noma_census_format_csv", cs, labels)
+    return cs.csv(labels)
 
 
 def noma_columns_from_logs(cfgs, steps, logs, fields) -> NomaColumns:
     """The host-side definition of the NOMA columns (prach_noma_columns_from_logs), as columns_from_logs.  The class counts of the headers are those of the
     definition's own STATE column."""
-    import numpy as np
-    sp, ids = noma_columns_spec(fields)
-    state, _ = noma_columns_spec(["state"])
-    hdr = np.zeros(len(logs), dtype=noma_columns_header_dtype())
-    ptrs = [_log_ptr(lg) for lg in logs]
-    hdr["nUE"] = [nue for _, nue, _ in ptrs]
-    hdr["offset"] = np.concatenate([[0], np.cumsum(hdr["nUE"], dtype=np.uint64)[:-1]]) if len(logs) else []
-    rows = int(hdr["nUE"].sum())
-    data = np.empty((max(len(ids), 1), rows), dtype=np.int32)
-    for k, (ptr, nue, _keep) in enumerate(ptrs):
-        st = np.empty(nue, dtype=np.int32)
-        for spec, out, stride in ((sp, data.ctypes.data + 4 * int(hdr["offset"][k]), rows), (state, st.ctypes.data, nue)):
-            rc = lib().prach_noma_columns_from_logs(C.byref(spec), C.byref(cfgs[k]), int(steps[k]), ptr, nue, out, stride)
-            if rc != OK:
-                raise PrachError(rc, "(prach_noma_columns_from_logs)")
-        hdr["idle"][k], hdr["served"][k], hdr["dropped"][k], hdr["pending"][k] = (st == 0).sum(), (st == 1).sum(), (st == 2).sum(), (st >= 3).sum()
-    return NomaColumns(ids, hdr, data[:len(ids)])
+    return _columns_from_logs("prach_noma_columns_from_logs", noma_columns_spec, noma_columns_header_dtype(), ("idle", "served", "dropped", "pending"), NomaColumns, cfgs, steps,
+                              logs, fields)

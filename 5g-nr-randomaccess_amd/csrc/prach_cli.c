@@ -74,7 +74,7 @@
  * reference runs the grid serially (RandomAccessWithNOMA.c:216-221).
  */
 #define _GNU_SOURCE
-#include "../../include/prach.h"
+#include "prach_grouped.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -135,138 +135,72 @@ static double now_s(void) {
     return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
-/* The reduction a run makes on the device next to its results: the distributions (--cdf, prach_run_trials_dist), the timelines (--timeline,
- * prach_run_trials_timeline) or the sojourn histograms (--sojourn, prach_run_trials_sojourn), never two of them; no spec: none, plain prach_run_trials.  A block holds the groups of one worker or of one call, one group per
- * sweep point: --cdf prach_dist[npts] | delay_hist[npts][bins] | ptc_hist[npts][256]; --timeline prach_timeline[npts] | five series [npts][bins] each
- * (arrivals, success, sojourn_sum, timer_sum, done); --sojourn prach_sojourn[npts] | hist[npts][rows][bins] | row_arrived[npts][rows] | row_delay_overflow[npts][rows]. */
+/* The reduction a run makes on the device next to its results, never two of them.  A GROUPED kind (csrc/prach_grouped.h: --cdf, --timeline, --sojourn, --trace,
+ * --xtab, --census, --census-trace, --census-timeline) is a block of groups, one group per sweep point; a block holds the groups of one worker or of one call:
+ * the kind's structs [npts], then its arrays in the order of the C ABI, array q of all groups [npts][words of q] — e.g. --cdf prach_dist[npts] |
+ * delay_hist[npts][bins] | ptc_hist[npts][256]; --sojourn prach_sojourn[npts] | hist[npts][rows][bins] | row_arrived[npts][rows] | row_delay_overflow[npts][rows].
+ * The library's row of the kind says the sizes; shape, merge, run and CSV are the library's generic functions.  No kind, no per-trial spec: plain prach_run_trials. */
 typedef struct reduction {
-    const prach_dist_spec *cdf;
-    const prach_timeline_spec *tl;
-    const prach_sojourn_spec *sj;
+    int kind;         /* PRACH_G_*; -1: no block of groups */
+    const void *spec; /* the kind's prach_*_spec */
     const char *path; /* the CSV file */
     size_t text_cap;  /* the CSV text of one group at most */
     /* --ci (prach_run_trials_summary) is no block of groups: one row per trial of the grid, in a shared mapping like the results; the parent computes the statistics */
     const prach_summary_spec *sm;
     prach_trial_summary *sm_rows;
-    const prach_trace_spec *tr; /* --trace: prach_trace[npts] | four series [npts][bins] each (calls, singles, txop, collisions) */
-    const prach_xtab_spec *xt;  /* --xtab: prach_xtab[npts] | cells[npts][row_bins + 1][col_bins + 1] */
     /* --pick (prach_run_trials_pick), like --ci: one header and k rows per trial of the grid, in shared mappings; the parent writes them in trial order */
     const prach_pick_spec *pk;
     prach_pick *pk_hdr;
     prach_pick_row *pk_rows;
-    const prach_xtab_spec *nc;  /* --census (--program noma): prach_noma_census[npts] | cells[npts][row_bins + 1][col_bins + 1] */
     int pk_noma;                /* --census-pick: `pk` is over the NOMA menu (prach_run_trials_noma_pick) */
     /* --census-ci (prach_run_trials_noma_summary), like --ci: one row per trial of the grid in a shared mapping; the parent computes the statistics */
     const prach_noma_summary_spec *nsm;
     prach_noma_trial_summary *nsm_rows;
-    const prach_noma_trace_spec *ntr; /* --census-trace (--program noma): prach_noma_trace[npts] | six series [npts][6 sectors][bins] each */
-    const prach_noma_timeline_spec *ntl; /* --census-timeline (--program noma): prach_noma_timeline[npts] | six series [npts][6 sectors][bins] each */
 } reduction;
-static int red_on(const reduction *r) { return r->cdf || r->tl || r->sj || r->tr || r->xt || r->nc || r->ntr || r->ntl; }
+static int red_on(const reduction *r) { return r->kind >= 0; }
 static size_t xt_cells(const prach_xtab_spec *s) { return ((size_t)s->row_bins + 1) * ((size_t)s->col_bins + 1); }
-static size_t sj_cells(const prach_sojourn_spec *s) { return (size_t)s->arrival_bins * (size_t)s->delay_bins; }
+static size_t red_ngroups(const reduction *r) { return (size_t)*(const int32_t *)((const char *)r->spec + prach_internal_grouped_row(r->kind)->ngroups_at); }
 static size_t red_block_bytes(const reduction *r) {
-    if (r->ntl) return (size_t)r->ntl->ngroups * (sizeof(prach_noma_timeline) + 6 * 8 * 6 * (size_t)r->ntl->bins);
-    if (r->ntr) return (size_t)r->ntr->ngroups * (sizeof(prach_noma_trace) + 6 * 8 * 6 * (size_t)r->ntr->bins);
-    if (r->nc) return (size_t)r->nc->ngroups * (sizeof(prach_noma_census) + 8 * xt_cells(r->nc));
-    if (r->xt) return (size_t)r->xt->ngroups * (sizeof(prach_xtab) + 8 * xt_cells(r->xt));
-    if (r->tr) return (size_t)r->tr->ngroups * (sizeof(prach_trace) + 4 * 8 * (size_t)r->tr->bins);
-    if (r->tl) return (size_t)r->tl->ngroups * (sizeof(prach_timeline) + 5 * 8 * (size_t)r->tl->bins);
-    if (r->sj) return (size_t)r->sj->ngroups * (sizeof(prach_sojourn) + 8 * (sj_cells(r->sj) + 2 * (size_t)r->sj->arrival_bins));
-    return r->cdf ? (size_t)r->cdf->ngroups * (sizeof(prach_dist) + 8 * ((size_t)r->cdf->delay_bins + PRACH_DIST_PTC_BINS)) : 0;
+    size_t words[PRACH_G_MAX_ARRAYS], group = red_on(r) ? prach_internal_grouped_row(r->kind)->group_bytes : 0;
+    const int na = red_on(r) ? prach_internal_grouped_shape(r->kind, r->spec, words) : 0;
+    for (int q = 0; q < na; q++) group += 8 * words[q];
+    return na ? red_ngroups(r) * group : 0;
 }
-/* group g of block b: --cdf its q-th histogram (0 delay, 1 preamble count), --timeline its q-th series, --sojourn 0 hist, 1 row_arrived, 2 row_delay_overflow */
+/* group g of block b: its struct, and its q-th array */
+static void *red_group(const reduction *r, char *b, int g) { return b + (size_t)g * prach_internal_grouped_row(r->kind)->group_bytes; }
 static uint64_t *red_array(const reduction *r, char *b, int q, int g) {
-    if (r->ntl) return (uint64_t *)(b + (size_t)r->ntl->ngroups * sizeof(prach_noma_timeline)) + ((size_t)q * (size_t)r->ntl->ngroups + (size_t)g) * 6 * (size_t)r->ntl->bins;
-    if (r->ntr) return (uint64_t *)(b + (size_t)r->ntr->ngroups * sizeof(prach_noma_trace)) + ((size_t)q * (size_t)r->ntr->ngroups + (size_t)g) * 6 * (size_t)r->ntr->bins;
-    if (r->nc) return (uint64_t *)(b + (size_t)r->nc->ngroups * sizeof(prach_noma_census)) + (size_t)g * xt_cells(r->nc);
-    if (r->xt) return (uint64_t *)(b + (size_t)r->xt->ngroups * sizeof(prach_xtab)) + (size_t)g * xt_cells(r->xt);
-    if (r->tr) return (uint64_t *)(b + (size_t)r->tr->ngroups * sizeof(prach_trace)) + ((size_t)q * (size_t)r->tr->ngroups + (size_t)g) * (size_t)r->tr->bins;
-    if (r->sj) {
-        uint64_t *const h = (uint64_t *)(b + (size_t)r->sj->ngroups * sizeof(prach_sojourn));
-        const size_t ng = (size_t)r->sj->ngroups, rows = (size_t)r->sj->arrival_bins;
-        return q == 0 ? h + (size_t)g * sj_cells(r->sj) : h + ng * sj_cells(r->sj) + ((size_t)(q - 1) * ng + (size_t)g) * rows;
-    }
-    if (r->tl) return (uint64_t *)(b + (size_t)r->tl->ngroups * sizeof(prach_timeline)) + ((size_t)q * (size_t)r->tl->ngroups + (size_t)g) * (size_t)r->tl->bins;
-    uint64_t *const dh = (uint64_t *)(b + (size_t)r->cdf->ngroups * sizeof(prach_dist));
-    return q == 0 ? dh + (size_t)g * (size_t)r->cdf->delay_bins : dh + (size_t)r->cdf->ngroups * (size_t)r->cdf->delay_bins + (size_t)g * PRACH_DIST_PTC_BINS;
+    size_t words[PRACH_G_MAX_ARRAYS];
+    prach_internal_grouped_shape(r->kind, r->spec, words);
+    uint64_t *a = (uint64_t *)red_group(r, b, (int)red_ngroups(r));
+    for (int i = 0; i < q; i++) a += red_ngroups(r) * words[i];
+    return a + (size_t)g * words[q];
 }
-/* a zero-filled block becomes one of empty groups */
+/* the arrays of group g of block b, as the library's generic functions take them; returns their number */
+static int red_arrays(const reduction *r, char *b, int g, uint64_t *arrays[PRACH_G_MAX_ARRAYS]) {
+    size_t words[PRACH_G_MAX_ARRAYS];
+    const int na = prach_internal_grouped_shape(r->kind, r->spec, words);
+    for (int q = 0; q < na; q++) arrays[q] = red_array(r, b, q, g);
+    return na;
+}
+/* a zero-filled block becomes one of empty groups: a maximum over nothing is -1 */
 static void red_init_block(const reduction *r, char *b) {
-    for (int g = 0; r->tl && g < r->tl->ngroups; g++) ((prach_timeline *)b)[g].done_max = -1;
-    for (int g = 0; r->cdf && g < r->cdf->ngroups; g++) ((prach_dist *)b)[g].delay_max = -1;
-    for (int g = 0; r->sj && g < r->sj->ngroups; g++) ((prach_sojourn *)b)[g].sojourn_max = -1;
-    for (int g = 0; r->tr && g < r->tr->ngroups; g++) ((prach_trace *)b)[g].calls_max = -1;
-    for (int g = 0; r->xt && g < r->xt->ngroups; g++) ((prach_xtab *)b)[g].row_max = ((prach_xtab *)b)[g].col_max = -1;
-    for (int g = 0; r->nc && g < r->nc->ngroups; g++) ((prach_noma_census *)b)[g].row_max = ((prach_noma_census *)b)[g].col_max = -1;
-    for (int g = 0; r->ntr && g < r->ntr->ngroups; g++) ((prach_noma_trace *)b)[g].tx_max = -1;
-    for (int g = 0; r->ntl && g < r->ntl->ngroups; g++) ((prach_noma_timeline *)b)[g].done_max = -1;
+    const prach_grouped_row *k = prach_internal_grouped_row(r->kind);
+    for (size_t g = 0; g < red_ngroups(r); g++)
+        for (int m = 0; m < k->maxima; m++) ((int64_t *)red_group(r, b, (int)g))[k->counters + m] = -1;
 }
 static void red_merge_block(const reduction *r, char *into, char *from) {
-    for (int g = 0; r->ntl && g < r->ntl->ngroups; g++) {
-        uint64_t *a[6];
-        const uint64_t *b[6];
-        for (int q = 0; q < 6; q++) { a[q] = red_array(r, into, q, g); b[q] = red_array(r, from, q, g); }
-        prach_noma_timeline_merge(r->ntl, (prach_noma_timeline *)into + g, a, (prach_noma_timeline *)from + g, b);
+    for (size_t g = 0; g < red_ngroups(r); g++) {
+        uint64_t *a[PRACH_G_MAX_ARRAYS], *b[PRACH_G_MAX_ARRAYS];
+        red_arrays(r, into, (int)g, a);
+        red_arrays(r, from, (int)g, b);
+        prach_internal_grouped_merge(r->kind, r->spec, red_group(r, into, (int)g), a, red_group(r, from, (int)g), (const uint64_t *const *)b);
     }
-    if (r->ntl) return;
-    for (int g = 0; r->ntr && g < r->ntr->ngroups; g++) {
-        uint64_t *a[6];
-        const uint64_t *b[6];
-        for (int q = 0; q < 6; q++) { a[q] = red_array(r, into, q, g); b[q] = red_array(r, from, q, g); }
-        prach_noma_trace_merge(r->ntr, (prach_noma_trace *)into + g, a, (prach_noma_trace *)from + g, b);
-    }
-    if (r->ntr) return;
-    for (int g = 0; r->nc && g < r->nc->ngroups; g++)
-        prach_noma_census_merge(r->nc, (prach_noma_census *)into + g, red_array(r, into, 0, g), (prach_noma_census *)from + g, red_array(r, from, 0, g));
-    if (r->nc) return;
-    for (int g = 0; r->xt && g < r->xt->ngroups; g++) prach_xtab_merge(r->xt, (prach_xtab *)into + g, red_array(r, into, 0, g), (prach_xtab *)from + g, red_array(r, from, 0, g));
-    if (r->xt) return;
-    for (int g = 0; r->tr && g < r->tr->ngroups; g++) {
-        uint64_t *a[4];
-        const uint64_t *b[4];
-        for (int q = 0; q < 4; q++) { a[q] = red_array(r, into, q, g); b[q] = red_array(r, from, q, g); }
-        prach_trace_merge(r->tr, (prach_trace *)into + g, a, (prach_trace *)from + g, b);
-    }
-    if (r->tr) return;
-    for (int g = 0; r->tl && g < r->tl->ngroups; g++) {
-        uint64_t *a[5];
-        const uint64_t *b[5];
-        for (int q = 0; q < 5; q++) { a[q] = red_array(r, into, q, g); b[q] = red_array(r, from, q, g); }
-        prach_timeline_merge(r->tl, (prach_timeline *)into + g, a, (prach_timeline *)from + g, b);
-    }
-    for (int g = 0; r->sj && g < r->sj->ngroups; g++)
-        prach_sojourn_merge(r->sj, (prach_sojourn *)into + g, red_array(r, into, 0, g), red_array(r, into, 1, g), red_array(r, into, 2, g), (prach_sojourn *)from + g,
-                            red_array(r, from, 0, g), red_array(r, from, 1, g), red_array(r, from, 2, g));
-    for (int g = 0; r->cdf && g < r->cdf->ngroups; g++)
-        prach_dist_merge(r->cdf, (prach_dist *)into + g, red_array(r, into, 0, g), red_array(r, into, 1, g), (prach_dist *)from + g, red_array(r, from, 0, g), red_array(r, from, 1, g));
 }
 /* the CSV text of group g of block b; returns its length (>= cap: it did not fit) */
 static size_t red_format_group(const reduction *r, char *b, int g, const char *label, char *out, size_t cap) {
-    if (r->ntl) {
-        const uint64_t *ser[6];
-        for (int q = 0; q < 6; q++) ser[q] = red_array(r, b, q, g);
-        return prach_noma_timeline_format_csv(r->ntl, (prach_noma_timeline *)b + g, ser, label, out, cap);
-    }
-    if (r->ntr) {
-        const uint64_t *ser[6];
-        for (int q = 0; q < 6; q++) ser[q] = red_array(r, b, q, g);
-        return prach_noma_trace_format_csv(r->ntr, (prach_noma_trace *)b + g, ser, label, out, cap);
-    }
-    if (r->nc) return prach_noma_census_format_csv(r->nc, (prach_noma_census *)b + g, red_array(r, b, 0, g), label, out, cap);
-    if (r->xt) return prach_xtab_format_csv(r->xt, (prach_xtab *)b + g, red_array(r, b, 0, g), label, out, cap);
-    if (r->tr) {
-        const uint64_t *ser[4];
-        for (int q = 0; q < 4; q++) ser[q] = red_array(r, b, q, g);
-        return prach_trace_format_csv(r->tr, (prach_trace *)b + g, ser, label, out, cap);
-    }
-    if (r->tl) {
-        const uint64_t *ser[5];
-        for (int q = 0; q < 5; q++) ser[q] = red_array(r, b, q, g);
-        return prach_timeline_format_csv(r->tl, (prach_timeline *)b + g, ser, label, out, cap);
-    }
-    if (r->sj) return prach_sojourn_format_csv(r->sj, (prach_sojourn *)b + g, red_array(r, b, 0, g), red_array(r, b, 1, g), red_array(r, b, 2, g), label, out, cap);
-    return prach_dist_format_csv(r->cdf, (prach_dist *)b + g, red_array(r, b, 0, g), red_array(r, b, 1, g), label, out, cap);
+    uint64_t *a[PRACH_G_MAX_ARRAYS];
+    red_arrays(r, b, g, a);
+    return prach_internal_grouped_format_csv(r->kind, r->spec, red_group(r, b, g), (const uint64_t *const *)a, label, out, cap);
 }
 
 /* FIELD[:WIDTH[:BINS]] of --xtab-rows / --xtab-cols.  Defaults: width 500 for arrival, otherwise 1; as many bins as cover max_time (arrival) or max_time + 6 (the
@@ -355,29 +289,9 @@ static int run_call(prach_engine *eng, const prach_cfg *c, int n, prach_result *
     if (red->pk && red->pk_noma) return prach_run_trials_noma_pick(eng, c, n, r, logs, red->pk, pk_hdr, pk_rows);
     if (red->pk) return prach_run_trials_pick(eng, c, n, r, logs, red->pk, pk_hdr, pk_rows);
     if (!red_on(red)) return prach_run_trials(eng, c, n, r, logs);
-    char *const b = call_block;
-    if (red->ntl) {
-        uint64_t *ser[6];
-        for (int q = 0; q < 6; q++) ser[q] = red_array(red, b, q, 0);
-        const int rc = prach_run_trials_noma_timeline(eng, c, n, r, logs, red->ntl, grp, (prach_noma_timeline *)b, ser);
-        if (rc == PRACH_OK) red_merge_block(red, worker_block, call_block);
-        return rc;
-    }
-    if (red->ntr) {
-        uint64_t *ser[6];
-        for (int q = 0; q < 6; q++) ser[q] = red_array(red, b, q, 0);
-        const int rc = prach_run_trials_noma_trace(eng, c, n, r, logs, red->ntr, grp, (prach_noma_trace *)b, ser);
-        if (rc == PRACH_OK) red_merge_block(red, worker_block, call_block);
-        return rc;
-    }
-    const int rc = red->nc ? prach_run_trials_noma_census(eng, c, n, r, logs, red->nc, grp, (prach_noma_census *)b, red_array(red, b, 0, 0))
-                   : red->xt ? prach_run_trials_xtab(eng, c, n, r, logs, red->xt, grp, (prach_xtab *)b, red_array(red, b, 0, 0))
-                   : red->tr ? prach_run_trials_trace(eng, c, n, r, logs, red->tr, grp, (prach_trace *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0), red_array(red, b, 2, 0),
-                                                    red_array(red, b, 3, 0))
-                   : red->tl ? prach_run_trials_timeline(eng, c, n, r, logs, red->tl, grp, (prach_timeline *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0),
-                                                       red_array(red, b, 2, 0), red_array(red, b, 3, 0), red_array(red, b, 4, 0))
-                   : red->sj ? prach_run_trials_sojourn(eng, c, n, r, logs, red->sj, grp, (prach_sojourn *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0), red_array(red, b, 2, 0))
-                           : prach_run_trials_dist(eng, c, n, r, logs, red->cdf, grp, (prach_dist *)b, red_array(red, b, 0, 0), red_array(red, b, 1, 0));
+    uint64_t *arrays[PRACH_G_MAX_ARRAYS];
+    red_arrays(red, call_block, 0, arrays);
+    const int rc = prach_internal_grouped_run(red->kind, eng, c, n, r, logs, red->spec, grp, call_block, arrays);
     if (rc == PRACH_OK) red_merge_block(red, worker_block, call_block);
     return rc;
 }
@@ -794,15 +708,16 @@ int main(int argc, char *argv[]) {
     if (sj_path && sj_bins > PRACH_SOJOURN_MAX_DELAY_BINS) die("--sojourn-bin MS: too many bins");
     /* a line of --cdf: a label of at most 10 digits, three numbers, a share; of --timeline: the label, a series name, two numbers; of --sojourn: the label and
      * three numbers, per cell and twice per row */
-    const reduction red_ = {cdf_path ? &cdf_spec : NULL, tl_path ? &tl_spec : NULL, sj_path ? &sj_spec : NULL, sj_path ? sj_path : tl_path ? tl_path : cdf_path,
+    const reduction red_ = {sj_path ? PRACH_G_SOJOURN : tl_path ? PRACH_G_TIMELINE : cdf_path ? PRACH_G_DIST : -1,
+                            sj_path ? (const void *)&sj_spec : tl_path ? (const void *)&tl_spec : (const void *)&cdf_spec, sj_path ? sj_path : tl_path ? tl_path : cdf_path,
                             sj_path ? 64 * ((size_t)sj_rows * ((size_t)sj_bins + 2) + 1) + 1
-                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, 0, NULL, NULL, NULL, NULL};
+                            : tl_path ? 64 * (5 * (size_t)tl_bins + 2) + 1 : 64 * ((size_t)cdf_bins + PRACH_DIST_PTC_BINS + 1) + 1, NULL, NULL, NULL, NULL, NULL, 0, NULL, NULL};
     reduction red_ci = red_;
     /* the trace's bins cover maxTime */
     const int tr_bins = (prach_max_time(&base) + tr_bin_ms - 1) / tr_bin_ms;
     const prach_trace_spec tr_spec = {tr_bins, tr_bin_ms, npts, 0};
     if (tr_path && tr_bins > PRACH_TRACE_MAX_BINS) die("--trace-bin MS: too many bins");
-    if (tr_path) { red_ci.tr = &tr_spec; red_ci.path = tr_path; red_ci.text_cap = 64 * (4 * (size_t)tr_bins + 1) + 1; } /* (a line: the label, a series name, two numbers) */
+    if (tr_path) { red_ci.kind = PRACH_G_TRACE; red_ci.spec = &tr_spec; red_ci.path = tr_path; red_ci.text_cap = 64 * (4 * (size_t)tr_bins + 1) + 1; } /* (a line: the label, a series name, two numbers) */
     /* --census-trace: the same for NOMA.c's channel trace */
     const int ntr_bins = (prach_max_time(&base) + ntr_bin_ms - 1) / ntr_bin_ms;
     const prach_noma_trace_spec ntr_spec = {ntr_bins, ntr_bin_ms, npts, 0};
@@ -813,8 +728,8 @@ int main(int argc, char *argv[]) {
     const prach_noma_timeline_spec ntl_spec = {ntl_bins, ntl_bin_ms, npts, 0};
     if (ntl_path && ntl_bins > PRACH_TIMELINE_MAX_BINS) die("--census-timeline-bin MS: too many bins");
     if (ntl_path && 36 * (uint64_t)npts * (uint64_t)ntl_bins > (1ull << 27)) die("--census-timeline: too many bins for this many sweep points");
-    if (ntl_path) { red_ci.ntl = &ntl_spec; red_ci.path = ntl_path; red_ci.text_cap = 80 * (6 * 7 * (size_t)ntl_bins + 2) + 1; } /* (a line: the label, a series name, a sector, two numbers) */
-    if (ntr_path) { red_ci.ntr = &ntr_spec; red_ci.path = ntr_path; red_ci.text_cap = 80 * (6 * 7 * (size_t)ntr_bins + 1) + 1; } /* (a line: the label, a series name, a sector, two numbers) */
+    if (ntl_path) { red_ci.kind = PRACH_G_NOMA_TIMELINE; red_ci.spec = &ntl_spec; red_ci.path = ntl_path; red_ci.text_cap = 80 * (6 * 7 * (size_t)ntl_bins + 2) + 1; } /* (a line: the label, a series name, a sector, two numbers) */
+    if (ntr_path) { red_ci.kind = PRACH_G_NOMA_TRACE; red_ci.spec = &ntr_spec; red_ci.path = ntr_path; red_ci.text_cap = 80 * (6 * 7 * (size_t)ntr_bins + 1) + 1; } /* (a line: the label, a series name, a sector, two numbers) */
     /* --xtab: the axes as given, the defaults of a field where width or bins are left out */
     prach_xtab_spec xt_spec = {0, 0, 0, 0, 0, 0, 0, npts, {0, 0}};
     if (xt_path) {
@@ -824,7 +739,7 @@ int main(int argc, char *argv[]) {
         if (!xtab_axis(xt_rows, prach_max_time(&base), &xt_spec.row_field, &xt_spec.row_width, &xt_spec.row_bins)) die("--xtab-rows FIELD[:WIDTH[:BINS]]: a field of the menu, a width of at least 1, 1 to 65536 bins");
         if (!xtab_axis(xt_cols, prach_max_time(&base), &xt_spec.col_field, &xt_spec.col_width, &xt_spec.col_bins)) die("--xtab-cols FIELD[:WIDTH[:BINS]]: a field of the menu, a width of at least 1, 1 to 65536 bins");
         if ((uint64_t)npts * xt_cells(&xt_spec) > (1ull << 24)) die("--xtab: too many cells");
-        red_ci.xt = &xt_spec; red_ci.path = xt_path; red_ci.text_cap = 64 * (xt_cells(&xt_spec) + 1) + 1; /* (a line: the label, two edges, a count) */
+        red_ci.kind = PRACH_G_XTAB; red_ci.spec = &xt_spec; red_ci.path = xt_path; red_ci.text_cap = 64 * (xt_cells(&xt_spec) + 1) + 1; /* (a line: the label, two edges, a count) */
     }
     /* --census: the NOMA menu's axes as given, the defaults of a field where width or bins are left out */
     prach_xtab_spec nc_spec = {0, 0, 0, 0, 0, 0, 0, npts, {0, 0}};
@@ -836,7 +751,7 @@ int main(int argc, char *argv[]) {
         if (!noma_axis(nc_rows, prach_max_time(&base), &nc_spec.row_field, &nc_spec.row_width, &nc_spec.row_bins)) die("--census-rows FIELD[:WIDTH[:BINS]]: a field of the NOMA menu, a width of at least 1, 1 to 65536 bins");
         if (!noma_axis(nc_cols, prach_max_time(&base), &nc_spec.col_field, &nc_spec.col_width, &nc_spec.col_bins)) die("--census-cols FIELD[:WIDTH[:BINS]]: a field of the NOMA menu, a width of at least 1, 1 to 65536 bins");
         if ((uint64_t)npts * xt_cells(&nc_spec) > (1ull << 24)) die("--census: too many cells");
-        red_ci.nc = &nc_spec; red_ci.path = nc_path; red_ci.text_cap = 64 * (xt_cells(&nc_spec) + 1) + 1; /* (a line: the label, two edges, a count) */
+        red_ci.kind = PRACH_G_NOMA_CENSUS; red_ci.spec = &nc_spec; red_ci.path = nc_path; red_ci.text_cap = 64 * (xt_cells(&nc_spec) + 1) + 1; /* (a line: the label, two edges, a count) */
     }
     if (ci_path) { /* --ci: the rows of the whole grid, filled by the workers */
         red_ci.sm = &ci_spec;

@@ -4,6 +4,7 @@
 // seeds of a whole launch with ONE copy, launches the trial kernels and turns DevResult into prach_result.
 // There is NO CPU fallback: without a gfx950 device every entry point that simulates returns PRACH_ERR_DEVICE.
 #include "prach_device.h"
+#include "prach_grouped.h"
 
 #include <algorithm>
 #include <chrono>
@@ -437,7 +438,9 @@ static int noma_device_activation(prach_engine *e, const TrialDev *dparams, cons
 // which the engine unpacks into the caller's per-group structs.  Every launch of the call gets one job per trial it finished, and the kind's kernel behind
 // the simulation kernel.  What differs between the kinds is stated ONCE per kind: a block of functions behind CallCtx and its row of RED_KINDS.  The generic
 // code (reduction_begin, run_group, reduction_end, run_trials_impl) walks that row and never asks which kind it has; a new kind is an enumerator, a block and
-// a row.
+// a row.  The HOST-SIDE row of a grouped kind (one struct and a few arrays per trial group) is in GROUPED of prach_host.c, stated by csrc/prach_grouped.h: its
+// sizes, the shape of its arrays, its spec's judge, the trials it takes, its CSV lines.  There a new grouped kind costs an enumerator, that row, an entry of
+// GROUPED_RED below and its three public functions as wrappers; the refusals (prach_internal_grouped_run), merge, CSV dispatch and the CLI's blocks are generic.
 enum class Red { dist, timeline, sojourn, summary, trace, xtab, pick, columns, noma_census, noma_columns, noma_summary, noma_pick, noma_trace, noma_timeline };
 constexpr int RED_MAX_PARTS = 7;
 struct Reduction {
@@ -1777,49 +1780,83 @@ int prach_run_trials(prach_engine *e, const prach_cfg *cfgs, int n, prach_result
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs);)
 }
 
+// a trial the NOMA menu's device calls take: NOMA.c with Philox (the reference-stream launches, run_noma_glibc, lay out no job the menu's kernels read: not wired to the menu)
+static bool noma_device_cfg(const prach_cfg &c) { return c.variant == PRACH_VARIANT_NOMA_C && c.rng_mode != PRACH_RNG_GLIBC; }
+
+// The grouped kinds (csrc/prach_grouped.h): the Red of each, in the order of PRACH_G_*.  What else the host side knows about a kind — the sizes, the shape of its
+// arrays, where ngroups and the reserved words sit in its spec, the trials it takes — is its row of GROUPED in prach_host.c
+static const Red GROUPED_RED[PRACH_G_KINDS] = {Red::dist, Red::timeline, Red::sojourn, Red::trace, Red::xtab, Red::noma_census, Red::noma_trace, Red::noma_timeline};
+
+// THE refusal sequence of every grouped call.  Arguments first (pointers, spec, ngroups, reserved, group ids), then what is not supported (the trials' programs,
+// then the cap of 2^27 words = 1 GiB of device buffer), then the missing engine: spec, groups and variants are judged first, what they ask for does not depend
+// on a device
+int prach_internal_grouped_run(int kind, prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const void *spec,
+                               const int32_t *group, void *groups, uint64_t *const arrays[]) {
+    const prach_grouped_row *const k = prach_internal_grouped_row(kind);
+    size_t words[PRACH_G_MAX_ARRAYS];
+    const int narrays = k ? k->shape(spec, words) : 0;
+    if (!cfgs || !results || n <= 0 || !narrays || !groups || !arrays) return PRACH_ERR_ARG;
+    uint64_t group_words = 0;
+    for (int q = 0; q < narrays; q++) {
+        if (!arrays[q]) return PRACH_ERR_ARG;
+        group_words += words[q];
+    }
+    const int ngroups = *reinterpret_cast<const int32_t *>(static_cast<const char *>(spec) + k->ngroups_at);
+    const int32_t *const reserved = reinterpret_cast<const int32_t *>(static_cast<const char *>(spec) + k->reserved_at);
+    if (ngroups < 1) return PRACH_ERR_ARG;
+    for (int r = 0; r < k->reserved_words; r++) if (reserved[r] != 0) return PRACH_ERR_ARG;
+    if (!groups_ok(group, ngroups, n)) return PRACH_ERR_ARG;
+    for (int t = 0; t < n; t++) // (NOMA.c has a menu and a resolver of its own, and its kinds take no other program: include/prach.h)
+        if (k->trials == PRACH_G_TRIALS_NOT_NOMA_C ? cfgs[t].variant == PRACH_VARIANT_NOMA_C : k->trials == PRACH_G_TRIALS_NOMA_C_PHILOX && !noma_device_cfg(cfgs[t]))
+            return PRACH_ERR_UNSUPPORTED;
+    if ((uint64_t)ngroups * group_words > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
+    if (!e) return PRACH_ERR_ARG;
+    Reduction red{.kind = GROUPED_RED[kind], .group = group, .ngroups = ngroups, .out = {}, .spec = spec, .groups = groups};
+    for (int q = 0; q < narrays; q++) red.out[q] = arrays[q];
+    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
+}
+
 int prach_run_trials_dist(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_dist_spec *spec,
                           const int32_t *group, prach_dist *dist, uint64_t *delay_hist, uint64_t *ptc_hist) {
-    // (the spec is judged first: what it asks for does not depend on a device)
-    if (!cfgs || !results || n <= 0 || !spec || !dist || !delay_hist || !ptc_hist) return PRACH_ERR_ARG;
-    if (spec->delay_bins < 1 || spec->delay_bins > PRACH_DIST_MAX_DELAY_BINS || spec->delay_bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
-    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
-    if ((uint64_t)spec->ngroups * (uint64_t)(spec->delay_bins + PRACH_DIST_PTC_BINS) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
-    if (!e) return PRACH_ERR_ARG;
-    const Reduction red{.kind = Red::dist, .group = group, .ngroups = spec->ngroups, .out = {delay_hist, ptc_hist}, .spec = spec, .groups = dist};
-    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
+    uint64_t *const arrays[] = {delay_hist, ptc_hist};
+    return prach_internal_grouped_run(PRACH_G_DIST, e, cfgs, n, results, ue_logs, spec, group, dist, arrays);
+}
+int prach_run_trials_timeline(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_timeline_spec *spec,
+                              const int32_t *group, prach_timeline *tl, uint64_t *arrivals, uint64_t *success, uint64_t *sojourn_sum, uint64_t *timer_sum, uint64_t *done) {
+    uint64_t *const arrays[] = {arrivals, success, sojourn_sum, timer_sum, done};
+    return prach_internal_grouped_run(PRACH_G_TIMELINE, e, cfgs, n, results, ue_logs, spec, group, tl, arrays);
+}
+int prach_run_trials_sojourn(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_sojourn_spec *spec,
+                             const int32_t *group, prach_sojourn *sj, uint64_t *hist, uint64_t *row_arrived, uint64_t *row_delay_overflow) {
+    uint64_t *const arrays[] = {hist, row_arrived, row_delay_overflow};
+    return prach_internal_grouped_run(PRACH_G_SOJOURN, e, cfgs, n, results, ue_logs, spec, group, sj, arrays);
+}
+int prach_run_trials_trace(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_trace_spec *spec,
+                           const int32_t *group, prach_trace *tr, uint64_t *calls, uint64_t *singles, uint64_t *txop, uint64_t *collisions) {
+    uint64_t *const arrays[] = {calls, singles, txop, collisions};
+    return prach_internal_grouped_run(PRACH_G_TRACE, e, cfgs, n, results, ue_logs, spec, group, tr, arrays);
+}
+int prach_run_trials_xtab(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_xtab_spec *spec,
+                          const int32_t *group, prach_xtab *xt, uint64_t *cells) {
+    return prach_internal_grouped_run(PRACH_G_XTAB, e, cfgs, n, results, ue_logs, spec, group, xt, &cells);
+}
+int prach_run_trials_noma_census(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_xtab_spec *spec,
+                                 const int32_t *group, prach_noma_census *cs, uint64_t *cells) {
+    return prach_internal_grouped_run(PRACH_G_NOMA_CENSUS, e, cfgs, n, results, ue_logs, spec, group, cs, &cells);
+}
+int prach_run_trials_noma_trace(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_noma_trace_spec *spec,
+                                const int32_t *group, prach_noma_trace *tr, uint64_t *const series[6]) {
+    return prach_internal_grouped_run(PRACH_G_NOMA_TRACE, e, cfgs, n, results, ue_logs, spec, group, tr, series);
+}
+int prach_run_trials_noma_timeline(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_noma_timeline_spec *spec,
+                                   const int32_t *group, prach_noma_timeline *tl, uint64_t *const series[6]) {
+    return prach_internal_grouped_run(PRACH_G_NOMA_TIMELINE, e, cfgs, n, results, ue_logs, spec, group, tl, series);
 }
 
 int prach_dist_tile_ues(void) { return DIST_TILE; }
 
-int prach_run_trials_timeline(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_timeline_spec *spec,
-                              const int32_t *group, prach_timeline *tl, uint64_t *arrivals, uint64_t *success, uint64_t *sojourn_sum, uint64_t *timer_sum, uint64_t *done) {
-    // (spec, groups and variants are judged first: what they ask for does not depend on a device)
-    if (!cfgs || !results || n <= 0 || !spec || !tl || !arrivals || !success || !sojourn_sum || !timer_sum || !done) return PRACH_ERR_ARG;
-    if (spec->bins < 1 || spec->bins > PRACH_TIMELINE_MAX_BINS || spec->bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
-    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
-    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c has a menu of its own: include/prach.h)
-    if (5 * (uint64_t)spec->ngroups * (uint64_t)spec->bins > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
-    if (!e) return PRACH_ERR_ARG;
-    const Reduction red{.kind = Red::timeline, .group = group, .ngroups = spec->ngroups, .out = {arrivals, success, sojourn_sum, timer_sum, done}, .spec = spec, .groups = tl};
-    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
-}
-
 int prach_timeline_tile_ues(void) { return TL_TILE; }
 int prach_timeline_window_bins(void) { return TL_WINDOW; }
-
-int prach_run_trials_sojourn(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_sojourn_spec *spec,
-                             const int32_t *group, prach_sojourn *sj, uint64_t *hist, uint64_t *row_arrived, uint64_t *row_delay_overflow) {
-    // (spec, groups and variants are judged first: what they ask for does not depend on a device)
-    if (!cfgs || !results || n <= 0 || !spec || !sj || !hist || !row_arrived || !row_delay_overflow) return PRACH_ERR_ARG;
-    if (spec->arrival_bins < 1 || spec->arrival_bins > PRACH_SOJOURN_MAX_ARRIVAL_BINS || spec->arrival_bin_ms < 1 || spec->delay_bins < 1 ||
-        spec->delay_bins > PRACH_SOJOURN_MAX_DELAY_BINS || spec->delay_bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
-    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
-    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c has a menu of its own: include/prach.h)
-    if ((uint64_t)spec->ngroups * (uint64_t)spec->arrival_bins * ((uint64_t)spec->delay_bins + 2) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
-    if (!e) return PRACH_ERR_ARG;
-    const Reduction red{.kind = Red::sojourn, .group = group, .ngroups = spec->ngroups, .out = {hist, row_arrived, row_delay_overflow}, .spec = spec, .groups = sj};
-    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
-}
 
 int prach_run_trials_summary(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_summary_spec *spec,
                              prach_trial_summary *rows) {
@@ -1834,38 +1871,10 @@ int prach_run_trials_summary(prach_engine *e, const prach_cfg *cfgs, int n, prac
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
-int prach_run_trials_trace(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_trace_spec *spec,
-                           const int32_t *group, prach_trace *tr, uint64_t *calls, uint64_t *singles, uint64_t *txop, uint64_t *collisions) {
-    // (spec, groups and variants are judged first: what they ask for does not depend on a device)
-    if (!cfgs || !results || n <= 0 || !spec || !tr || !calls || !singles || !txop || !collisions) return PRACH_ERR_ARG;
-    if (spec->bins < 1 || spec->bins > PRACH_TRACE_MAX_BINS || spec->bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
-    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
-    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c's resolver is another one: include/prach.h)
-    if (4 * (uint64_t)spec->ngroups * (uint64_t)spec->bins > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
-    if (!e) return PRACH_ERR_ARG;
-    const Reduction red{.kind = Red::trace, .group = group, .ngroups = spec->ngroups, .out = {calls, singles, txop, collisions}, .spec = spec, .groups = tr};
-    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
-}
-
 int prach_trace_tile_subframes(void) { return TR_TILE; }
 
 int prach_sojourn_tile_ues(void) { return TL_TILE; }
 int prach_sojourn_window_words(void) { return SJ_WINDOW_WORDS; }
-
-int prach_run_trials_xtab(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_xtab_spec *spec,
-                          const int32_t *group, prach_xtab *xt, uint64_t *cells) {
-    // (spec, groups and variants are judged first: what they ask for does not depend on a device)
-    if (!cfgs || !results || n <= 0 || !spec || !xt || !cells) return PRACH_ERR_ARG;
-    auto axis_ok = [](int f, int w, int b) { return f >= 0 && f < PRACH_XTAB_NFIELDS && w >= 1 && b >= 1 && b <= PRACH_XTAB_MAX_BINS; };
-    if (spec->who <= 0 || (spec->who & ~(PRACH_XTAB_SERVED | PRACH_XTAB_UNSERVED | PRACH_XTAB_IDLE)) != 0 || !axis_ok(spec->row_field, spec->row_width, spec->row_bins) ||
-        !axis_ok(spec->col_field, spec->col_width, spec->col_bins) || spec->ngroups < 1 || spec->reserved[0] != 0 || spec->reserved[1] != 0) return PRACH_ERR_ARG;
-    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
-    for (int k = 0; k < n; k++) if (cfgs[k].variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED; // (NOMA.c has a menu of its own: include/prach.h)
-    if ((uint64_t)spec->ngroups * ((uint64_t)spec->row_bins + 1) * ((uint64_t)spec->col_bins + 1) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
-    if (!e) return PRACH_ERR_ARG;
-    const Reduction red{.kind = Red::xtab, .group = group, .ngroups = spec->ngroups, .out = {cells}, .spec = spec, .groups = xt};
-    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
-}
 
 int prach_run_trials_pick(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_pick_spec *spec,
                           prach_pick *picks, prach_pick_row *rows) {
@@ -1875,22 +1884,6 @@ int prach_run_trials_pick(prach_engine *e, const prach_cfg *cfgs, int n, prach_r
     if ((uint64_t)n * ((uint64_t)spec->k * PK_ROW_WORDS + PK_SCALARS) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
     const Reduction red{.kind = Red::pick, .group = nullptr, .ngroups = n, .out = {reinterpret_cast<uint64_t *>(rows)}, .spec = spec, .groups = picks};
-    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
-}
-
-// a trial the NOMA menu's device calls take: NOMA.c with Philox (the reference-stream launches, run_noma_glibc, lay out no job the menu's kernels read: not wired to the menu)
-static bool noma_device_cfg(const prach_cfg &c) { return c.variant == PRACH_VARIANT_NOMA_C && c.rng_mode != PRACH_RNG_GLIBC; }
-
-int prach_run_trials_noma_census(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_xtab_spec *spec,
-                                 const int32_t *group, prach_noma_census *cs, uint64_t *cells) {
-    // (spec, groups and variants are judged first: what they ask for does not depend on a device)
-    if (!cfgs || !results || n <= 0 || !spec || !cs || !cells) return PRACH_ERR_ARG;
-    if (!prach_internal_noma_census_spec_ok(spec) || spec->ngroups < 1) return PRACH_ERR_ARG;
-    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
-    for (int k = 0; k < n; k++) if (!noma_device_cfg(cfgs[k])) return PRACH_ERR_UNSUPPORTED;
-    if ((uint64_t)spec->ngroups * ((uint64_t)spec->row_bins + 1) * ((uint64_t)spec->col_bins + 1) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
-    if (!e) return PRACH_ERR_ARG;
-    const Reduction red{.kind = Red::noma_census, .group = group, .ngroups = spec->ngroups, .out = {cells}, .spec = spec, .groups = cs};
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 
@@ -1978,34 +1971,6 @@ int prach_run_trials_noma_pick(prach_engine *e, const prach_cfg *cfgs, int n, pr
     if ((uint64_t)n * ((uint64_t)spec->k * PK_ROW_WORDS + PK_SCALARS) > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
     const Reduction red{.kind = Red::noma_pick, .group = nullptr, .ngroups = n, .out = {reinterpret_cast<uint64_t *>(rows)}, .spec = spec, .groups = picks};
-    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
-}
-
-int prach_run_trials_noma_trace(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_noma_trace_spec *spec,
-                                const int32_t *group, prach_noma_trace *tr, uint64_t *const series[6]) {
-    // (spec, groups and variants are judged first: what they ask for does not depend on a device)
-    if (!cfgs || !results || n <= 0 || !spec || !tr || !series) return PRACH_ERR_ARG;
-    for (int q = 0; q < 6; q++) if (!series[q]) return PRACH_ERR_ARG;
-    if (spec->bins < 1 || spec->bins > PRACH_TRACE_MAX_BINS || spec->bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
-    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
-    for (int k = 0; k < n; k++) if (!noma_device_cfg(cfgs[k])) return PRACH_ERR_UNSUPPORTED;
-    if (36 * (uint64_t)spec->ngroups * (uint64_t)spec->bins > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
-    if (!e) return PRACH_ERR_ARG;
-    const Reduction red{.kind = Red::noma_trace, .group = group, .ngroups = spec->ngroups, .out = {series[0], series[1], series[2], series[3], series[4], series[5]}, .spec = spec, .groups = tr};
-    PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
-}
-
-int prach_run_trials_noma_timeline(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_noma_timeline_spec *spec,
-                                   const int32_t *group, prach_noma_timeline *tl, uint64_t *const series[6]) {
-    // (spec, groups and variants are judged first: what they ask for does not depend on a device)
-    if (!cfgs || !results || n <= 0 || !spec || !tl || !series) return PRACH_ERR_ARG;
-    for (int q = 0; q < 6; q++) if (!series[q]) return PRACH_ERR_ARG;
-    if (spec->bins < 1 || spec->bins > PRACH_TIMELINE_MAX_BINS || spec->bin_ms < 1 || spec->ngroups < 1 || spec->reserved != 0) return PRACH_ERR_ARG;
-    if (!groups_ok(group, spec->ngroups, n)) return PRACH_ERR_ARG;
-    for (int k = 0; k < n; k++) if (!noma_device_cfg(cfgs[k])) return PRACH_ERR_UNSUPPORTED;
-    if (36 * (uint64_t)spec->ngroups * (uint64_t)spec->bins > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
-    if (!e) return PRACH_ERR_ARG;
-    const Reduction red{.kind = Red::noma_timeline, .group = group, .ngroups = spec->ngroups, .out = {series[0], series[1], series[2], series[3], series[4], series[5]}, .spec = spec, .groups = tl};
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
 

@@ -7,12 +7,13 @@
  * (SURVEY.md §8b).
  */
 #define _GNU_SOURCE
-#include "../../include/prach.h"
+#include "prach_grouped.h"
 
 #include <errno.h>
 #include <math.h>
 #include <pthread.h>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -586,10 +587,19 @@ static size_t csv_end(char *buf, size_t cap, size_t off) {
     return off;
 }
 
+/* a kind's shape function (prach_grouped.h) is the judge of its spec */
+static int spec_ok(int (*shape)(const void *, size_t *), const void *spec) {
+    size_t words[PRACH_G_MAX_ARRAYS];
+    return shape(spec, words) != 0;
+}
+
 /* ---- distributions of the successful UEs (prach_run_trials_dist) -------------------------------- */
 
-static int dist_spec_ok(const prach_dist_spec *s) {
-    return s && s->delay_bins >= 1 && s->delay_bins <= PRACH_DIST_MAX_DELAY_BINS && s->delay_bin_ms >= 1;
+static int dist_shape(const void *spec, size_t words[]) {
+    const prach_dist_spec *s = (const prach_dist_spec *)spec;
+    if (!s || s->delay_bins < 1 || s->delay_bins > PRACH_DIST_MAX_DELAY_BINS || s->delay_bin_ms < 1) return 0;
+    words[0] = (size_t)s->delay_bins; words[1] = PRACH_DIST_PTC_BINS;
+    return 2;
 }
 
 /* one successful UE (timer >= 0): what prach::dist_kernel does per lane */
@@ -605,7 +615,7 @@ void prach_internal_dist_add_ue(const prach_dist_spec *s, prach_dist *d, uint64_
 }
 
 int prach_dist_accumulate_logs(const prach_dist_spec *s, const prach_ue_log *ue, int nUE, prach_dist *d, uint64_t *delay_hist, uint64_t *ptc_hist) {
-    if (!dist_spec_ok(s) || !d || !delay_hist || !ptc_hist || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    if (!spec_ok(dist_shape, s) || !d || !delay_hist || !ptc_hist || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
     for (int i = 0; i < nUE; i++)
         if (ue[i].msg4Flag == 1 && ue[i].timer < 0) return PRACH_ERR_ARG;
     if (d->trials == 0 && d->success == 0) d->delay_max = -1; /* (a zero-filled group is an empty one) */
@@ -616,19 +626,8 @@ int prach_dist_accumulate_logs(const prach_dist_spec *s, const prach_ue_log *ue,
     return PRACH_OK;
 }
 
-void prach_dist_merge(const prach_dist_spec *s, prach_dist *into, uint64_t *dh_into, uint64_t *ph_into, const prach_dist *from, const uint64_t *dh_from,
-                      const uint64_t *ph_from) {
-    if (!dist_spec_ok(s) || !into || !dh_into || !ph_into || !from || !dh_from || !ph_from) return;
-    const int64_t a = into->success ? into->delay_max : -1, b = from->success ? from->delay_max : -1;
-    into->trials += from->trials; into->ues += from->ues; into->success += from->success; into->delay_overflow += from->delay_overflow;
-    into->delay_sum += from->delay_sum; into->ptc_sum += from->ptc_sum;
-    into->delay_max = a > b ? a : b;
-    for (int i = 0; i < s->delay_bins; i++) dh_into[i] += dh_from[i];
-    for (int i = 0; i < PRACH_DIST_PTC_BINS; i++) ph_into[i] += ph_from[i];
-}
-
 int64_t prach_dist_delay_quantile(const prach_dist_spec *s, const prach_dist *d, const uint64_t *delay_hist, double q) {
-    if (!dist_spec_ok(s) || !d || !delay_hist || d->success == 0 || !(q >= 0.0) || q > 1.0) return -1;
+    if (!spec_ok(dist_shape, s) || !d || !delay_hist || d->success == 0 || !(q >= 0.0) || q > 1.0) return -1;
     uint64_t rank = (uint64_t)ceil(q * (double)d->success);
     if (rank < 1) rank = 1;
     if (rank > d->success) rank = d->success;
@@ -640,9 +639,10 @@ int64_t prach_dist_delay_quantile(const prach_dist_spec *s, const prach_dist *d,
     return -1; /* in the overflow */
 }
 
-size_t prach_dist_format_csv(const prach_dist_spec *s, const prach_dist *d, const uint64_t *delay_hist, const uint64_t *ptc_hist, const char *label, char *buf,
-                             size_t cap) {
-    if (!dist_spec_ok(s) || !d || !delay_hist || !ptc_hist || !label) return 0;
+static size_t dist_csv(const void *spec, const void *group, const uint64_t *const arrays[], const char *label, char *buf, size_t cap) {
+    const prach_dist_spec *s = (const prach_dist_spec *)spec;
+    const prach_dist *d = (const prach_dist *)group;
+    const uint64_t *const delay_hist = arrays[0], *const ptc_hist = arrays[1];
     size_t off = 0;
     const double tot = d->success ? (double)d->success : 1.0;
     uint64_t cum = 0;
@@ -661,16 +661,58 @@ size_t prach_dist_format_csv(const prach_dist_spec *s, const prach_dist *d, cons
     return csv_end(buf, cap, off);
 }
 
+/* ---- the four kinds of series by time (timeline, trace, noma_trace, noma_timeline): one shape, one formatter ---- */
+
+/* nseries arrays of sectors * bins words each */
+static int series_shape(int bins, int bin_ms, int max_bins, int nseries, int sectors, size_t words[]) {
+    if (bins < 1 || bins > max_bins || bin_ms < 1) return 0;
+    for (int q = 0; q < nseries; q++) words[q] = (size_t)sectors * (size_t)bins;
+    return nseries;
+}
+
+/* a kind's lines: its series in order, a line per non-zero bin (per sector and over all sectors where there are 6); behind series `after` an overflow line
+   under the name of series `name`, from the counter at byte `at` of the group struct if that is non-zero */
+typedef struct series_overflow { int after, name; size_t at; } series_overflow;
+typedef struct series_lines {
+    const char *const *names;
+    int nseries, sectors, noverflow;
+    series_overflow overflow[2];
+} series_lines;
+static size_t series_csv(const series_lines *k, int bins, int bin_ms, const void *group, const uint64_t *const series[], const char *label, char *buf, size_t cap) {
+    size_t off = 0;
+    for (int q = 0; q < k->nseries; q++) {
+        for (int b = 0; b < bins; b++) {
+            if (k->sectors == 1) {
+                if (series[q][b]) CSV_EMIT("%.200s,%s,%lld,%llu\n", label, k->names[q], (long long)b * bin_ms, (unsigned long long)series[q][b]);
+                continue;
+            }
+            uint64_t all = 0;
+            for (int c = 0; c < k->sectors; c++) {
+                const uint64_t v = series[q][(size_t)c * (size_t)bins + (size_t)b];
+                all += v;
+                if (v) CSV_EMIT("%.200s,%s,%d,%lld,%llu\n", label, k->names[q], c, (long long)b * bin_ms, (unsigned long long)v);
+            }
+            if (all) CSV_EMIT("%.200s,%s,all,%lld,%llu\n", label, k->names[q], (long long)b * bin_ms, (unsigned long long)all);
+        }
+        for (int o = 0; o < k->noverflow; o++) {
+            const uint64_t v = *(const uint64_t *)((const char *)group + k->overflow[o].at);
+            if (k->overflow[o].after == q && v) CSV_EMIT(k->sectors == 1 ? "%.200s,%s,overflow,%llu\n" : "%.200s,%s,all,overflow,%llu\n", label, k->names[k->overflow[o].name], (unsigned long long)v);
+        }
+    }
+    return csv_end(buf, cap, off);
+}
+
 /* ---- timelines per trial group (prach_run_trials_timeline) -------------------------------------- */
 
-static int timeline_spec_ok(const prach_timeline_spec *s) {
-    return s && s->bins >= 1 && s->bins <= PRACH_TIMELINE_MAX_BINS && s->bin_ms >= 1;
+static int timeline_shape(const void *spec, size_t words[]) {
+    const prach_timeline_spec *s = (const prach_timeline_spec *)spec;
+    return s ? series_shape(s->bins, s->bin_ms, PRACH_TIMELINE_MAX_BINS, 5, 1, words) : 0;
 }
 
 /* THE DEFINITION (include/prach.h).  Two passes: the first only judges, so that a refused log leaves nothing behind */
 int prach_timeline_accumulate_logs(const prach_timeline_spec *s, const prach_cfg *cfg, const prach_ue_log *ue, int nUE, prach_timeline *t, uint64_t *arrivals,
                                    uint64_t *success, uint64_t *sojourn_sum, uint64_t *timer_sum, uint64_t *done) {
-    if (!timeline_spec_ok(s) || !cfg || !t || !arrivals || !success || !sojourn_sum || !timer_sum || !done || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    if (!spec_ok(timeline_shape, s) || !cfg || !t || !arrivals || !success || !sojourn_sum || !timer_sum || !done || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
     if (cfg->variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED;
     if (prach_cfg_validate(cfg) != PRACH_OK || nUE != cfg->nUE) return PRACH_ERR_ARG;
     const int nslots = (prach_max_time(cfg) + cfg->accessTime - 1) / cfg->accessTime;
@@ -712,110 +754,55 @@ int prach_timeline_accumulate_logs(const prach_timeline_spec *s, const prach_cfg
     return PRACH_OK;
 }
 
-void prach_timeline_merge(const prach_timeline_spec *s, prach_timeline *into, uint64_t *const into_series[5], const prach_timeline *from,
-                          const uint64_t *const from_series[5]) {
-    if (!timeline_spec_ok(s) || !into || !into_series || !from || !from_series) return;
-    for (int q = 0; q < 5; q++) if (!into_series[q] || !from_series[q]) return;
-    const int64_t a = into->success ? into->done_max : -1, b = from->success ? from->done_max : -1;
-    into->trials += from->trials; into->ues += from->ues; into->arrived += from->arrived; into->success += from->success; into->restarted += from->restarted;
-    into->arrival_overflow += from->arrival_overflow; into->done_overflow += from->done_overflow; into->sojourn_sum += from->sojourn_sum;
-    into->timer_sum += from->timer_sum;
-    into->done_max = a > b ? a : b;
-    for (int q = 0; q < 5; q++)
-        for (int i = 0; i < s->bins; i++) into_series[q][i] += from_series[q][i];
-}
-
-size_t prach_timeline_format_csv(const prach_timeline_spec *s, const prach_timeline *t, const uint64_t *const series[5], const char *label, char *buf, size_t cap) {
+static size_t timeline_csv(const void *spec, const void *group, const uint64_t *const series[], const char *label, char *buf, size_t cap) {
     static const char *const names[5] = {"arrivals", "success", "sojourn_sum", "timer_sum", "done"};
-    if (!timeline_spec_ok(s) || !t || !series || !label) return 0;
-    for (int q = 0; q < 5; q++) if (!series[q]) return 0;
-    size_t off = 0;
-    for (int q = 0; q < 5; q++) {
-        for (int b = 0; b < s->bins; b++)
-            if (series[q][b]) CSV_EMIT("%.200s,%s,%lld,%llu\n", label, names[q], (long long)b * s->bin_ms, (unsigned long long)series[q][b]);
-        if (q == 0 && t->arrival_overflow) CSV_EMIT("%.200s,arrivals,overflow,%llu\n", label, (unsigned long long)t->arrival_overflow);
-        if (q == 4 && t->done_overflow) CSV_EMIT("%.200s,done,overflow,%llu\n", label, (unsigned long long)t->done_overflow);
-    }
-    return csv_end(buf, cap, off);
+    static const series_lines lines = {names, 5, 1, 2, {{0, 0, offsetof(prach_timeline, arrival_overflow)}, {4, 4, offsetof(prach_timeline, done_overflow)}}};
+    const prach_timeline_spec *s = (const prach_timeline_spec *)spec;
+    return series_csv(&lines, s->bins, s->bin_ms, group, series, label, buf, cap);
 }
 
 /* ---- per-subframe preamble traces per trial group (prach_run_trials_trace) ----------------------- */
 
-static int trace_spec_ok(const prach_trace_spec *s) {
-    return s && s->bins >= 1 && s->bins <= PRACH_TRACE_MAX_BINS && s->bin_ms >= 1;
+static int trace_shape(const void *spec, size_t words[]) {
+    const prach_trace_spec *s = (const prach_trace_spec *)spec;
+    return s ? series_shape(s->bins, s->bin_ms, PRACH_TRACE_MAX_BINS, 4, 1, words) : 0;
 }
 
-void prach_trace_merge(const prach_trace_spec *s, prach_trace *into, uint64_t *const into_series[4], const prach_trace *from, const uint64_t *const from_series[4]) {
-    if (!trace_spec_ok(s) || !into || !into_series || !from || !from_series) return;
-    for (int q = 0; q < 4; q++) if (!into_series[q] || !from_series[q]) return;
-    const int64_t a = into->subframes ? into->calls_max : -1, b = from->subframes ? from->calls_max : -1;
-    into->trials += from->trials; into->subframes += from->subframes; into->calls += from->calls; into->singles += from->singles; into->txop += from->txop;
-    into->collisions += from->collisions; into->overflow_calls += from->overflow_calls;
-    into->calls_max = a > b ? a : b;
-    for (int q = 0; q < 4; q++)
-        for (int i = 0; i < s->bins; i++) into_series[q][i] += from_series[q][i];
-}
-
-size_t prach_trace_format_csv(const prach_trace_spec *s, const prach_trace *t, const uint64_t *const series[4], const char *label, char *buf, size_t cap) {
+static size_t trace_csv(const void *spec, const void *group, const uint64_t *const series[], const char *label, char *buf, size_t cap) {
     static const char *const names[4] = {"calls", "singles", "txop", "collisions"};
-    if (!trace_spec_ok(s) || !t || !series || !label) return 0;
-    for (int q = 0; q < 4; q++) if (!series[q]) return 0;
-    size_t off = 0;
-    for (int q = 0; q < 4; q++)
-        for (int b = 0; b < s->bins; b++)
-            if (series[q][b]) CSV_EMIT("%.200s,%s,%lld,%llu\n", label, names[q], (long long)b * s->bin_ms, (unsigned long long)series[q][b]);
-    if (t->overflow_calls) CSV_EMIT("%.200s,calls,overflow,%llu\n", label, (unsigned long long)t->overflow_calls);
-    return csv_end(buf, cap, off);
+    static const series_lines lines = {names, 4, 1, 1, {{3, 0, offsetof(prach_trace, overflow_calls)}, {0, 0, 0}}};
+    const prach_trace_spec *s = (const prach_trace_spec *)spec;
+    return series_csv(&lines, s->bins, s->bin_ms, group, series, label, buf, cap);
 }
 
-/* ---- NOMA.c's channel trace per trial group (prach_run_trials_noma_trace): merge, CSV ------------- */
+/* ---- NOMA.c's channel trace per trial group (prach_run_trials_noma_trace) -------------------------- */
 
-static int noma_trace_spec_ok(const prach_noma_trace_spec *s) {
-    return s && s->bins >= 1 && s->bins <= PRACH_TRACE_MAX_BINS && s->bin_ms >= 1;
+static int noma_trace_shape(const void *spec, size_t words[]) {
+    const prach_noma_trace_spec *s = (const prach_noma_trace_spec *)spec;
+    return s ? series_shape(s->bins, s->bin_ms, PRACH_TRACE_MAX_BINS, 6, 6, words) : 0;
 }
 
-void prach_noma_trace_merge(const prach_noma_trace_spec *s, prach_noma_trace *into, uint64_t *const into_series[6], const prach_noma_trace *from,
-                            const uint64_t *const from_series[6]) {
-    if (!noma_trace_spec_ok(s) || !into || !into_series || !from || !from_series) return;
-    for (int q = 0; q < 6; q++) if (!into_series[q] || !from_series[q]) return;
-    const int64_t a = into->slots ? into->tx_max : -1, b = from->slots ? from->tx_max : -1;
-    into->trials += from->trials; into->slots += from->slots; into->tx += from->tx; into->used += from->used; into->singles += from->singles;
-    into->granted += from->granted; into->pairs += from->pairs; into->pair_one += from->pair_one; into->overflow_tx += from->overflow_tx;
-    into->tx_max = a > b ? a : b;
-    for (int q = 0; q < 6; q++)
-        for (int i = 0; i < 6 * s->bins; i++) into_series[q][i] += from_series[q][i];
-}
-
-size_t prach_noma_trace_format_csv(const prach_noma_trace_spec *s, const prach_noma_trace *t, const uint64_t *const series[6], const char *label, char *buf, size_t cap) {
+static size_t noma_trace_csv(const void *spec, const void *group, const uint64_t *const series[], const char *label, char *buf, size_t cap) {
     static const char *const names[6] = {"tx", "used", "singles", "granted", "pairs", "pair_one"};
-    if (!noma_trace_spec_ok(s) || !t || !series || !label) return 0;
-    for (int q = 0; q < 6; q++) if (!series[q]) return 0;
-    size_t off = 0;
-    for (int q = 0; q < 6; q++)
-        for (int b = 0; b < s->bins; b++) {
-            uint64_t all = 0;
-            for (int c = 0; c < 6; c++) {
-                const uint64_t v = series[q][(size_t)c * (size_t)s->bins + (size_t)b];
-                all += v;
-                if (v) CSV_EMIT("%.200s,%s,%d,%lld,%llu\n", label, names[q], c, (long long)b * s->bin_ms, (unsigned long long)v);
-            }
-            if (all) CSV_EMIT("%.200s,%s,all,%lld,%llu\n", label, names[q], (long long)b * s->bin_ms, (unsigned long long)all);
-        }
-    if (t->overflow_tx) CSV_EMIT("%.200s,tx,all,overflow,%llu\n", label, (unsigned long long)t->overflow_tx);
-    return csv_end(buf, cap, off);
+    static const series_lines lines = {names, 6, 6, 1, {{5, 0, offsetof(prach_noma_trace, overflow_tx)}, {0, 0, 0}}};
+    const prach_noma_trace_spec *s = (const prach_noma_trace_spec *)spec;
+    return series_csv(&lines, s->bins, s->bin_ms, group, series, label, buf, cap);
 }
 
 /* ---- sojourn histograms by arrival row per trial group (prach_run_trials_sojourn) ---------------- */
 
-static int sojourn_spec_ok(const prach_sojourn_spec *s) {
-    return s && s->arrival_bins >= 1 && s->arrival_bins <= PRACH_SOJOURN_MAX_ARRIVAL_BINS && s->arrival_bin_ms >= 1 && s->delay_bins >= 1 &&
-           s->delay_bins <= PRACH_SOJOURN_MAX_DELAY_BINS && s->delay_bin_ms >= 1;
+static int sojourn_shape(const void *spec, size_t words[]) {
+    const prach_sojourn_spec *s = (const prach_sojourn_spec *)spec;
+    if (!s || s->arrival_bins < 1 || s->arrival_bins > PRACH_SOJOURN_MAX_ARRIVAL_BINS || s->arrival_bin_ms < 1 || s->delay_bins < 1 ||
+        s->delay_bins > PRACH_SOJOURN_MAX_DELAY_BINS || s->delay_bin_ms < 1) return 0;
+    words[0] = (size_t)s->arrival_bins * (size_t)s->delay_bins; words[1] = words[2] = (size_t)s->arrival_bins;
+    return 3;
 }
 
 /* THE DEFINITION (include/prach.h).  Two passes, like the timeline's: the first only judges, so that a refused log leaves nothing behind */
 int prach_sojourn_accumulate_logs(const prach_sojourn_spec *s, const prach_cfg *cfg, const prach_ue_log *ue, int nUE, prach_sojourn *j, uint64_t *hist,
                                   uint64_t *row_arrived, uint64_t *row_delay_overflow) {
-    if (!sojourn_spec_ok(s) || !cfg || !j || !hist || !row_arrived || !row_delay_overflow || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    if (!spec_ok(sojourn_shape, s) || !cfg || !j || !hist || !row_arrived || !row_delay_overflow || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
     if (cfg->variant == PRACH_VARIANT_NOMA_C) return PRACH_ERR_UNSUPPORTED;
     if (prach_cfg_validate(cfg) != PRACH_OK || nUE != cfg->nUE) return PRACH_ERR_ARG;
     const int nslots = (prach_max_time(cfg) + cfg->accessTime - 1) / cfg->accessTime;
@@ -857,20 +844,8 @@ int prach_sojourn_accumulate_logs(const prach_sojourn_spec *s, const prach_cfg *
     return PRACH_OK;
 }
 
-void prach_sojourn_merge(const prach_sojourn_spec *s, prach_sojourn *into, uint64_t *hist_into, uint64_t *arrived_into, uint64_t *overflow_into,
-                         const prach_sojourn *from, const uint64_t *hist_from, const uint64_t *arrived_from, const uint64_t *overflow_from) {
-    if (!sojourn_spec_ok(s) || !into || !hist_into || !arrived_into || !overflow_into || !from || !hist_from || !arrived_from || !overflow_from) return;
-    const int64_t a = into->success ? into->sojourn_max : -1, b = from->success ? from->sojourn_max : -1;
-    into->trials += from->trials; into->ues += from->ues; into->arrived += from->arrived; into->success += from->success; into->restarted += from->restarted;
-    into->arrival_overflow += from->arrival_overflow; into->delay_overflow += from->delay_overflow; into->sojourn_sum += from->sojourn_sum;
-    into->sojourn_max = a > b ? a : b;
-    const size_t cells = (size_t)s->arrival_bins * (size_t)s->delay_bins;
-    for (size_t i = 0; i < cells; i++) hist_into[i] += hist_from[i];
-    for (int r = 0; r < s->arrival_bins; r++) { arrived_into[r] += arrived_from[r]; overflow_into[r] += overflow_from[r]; }
-}
-
 int64_t prach_sojourn_quantile(const prach_sojourn_spec *s, const uint64_t *hist, const uint64_t *row_delay_overflow, int row, double q) {
-    if (!sojourn_spec_ok(s) || !hist || !row_delay_overflow || row < -1 || row >= s->arrival_bins || !(q >= 0.0) || q > 1.0) return -1;
+    if (!spec_ok(sojourn_shape, s) || !hist || !row_delay_overflow || row < -1 || row >= s->arrival_bins || !(q >= 0.0) || q > 1.0) return -1;
     const int r0 = row < 0 ? 0 : row, r1 = row < 0 ? s->arrival_bins : row + 1;
     uint64_t n = 0;
     for (int r = r0; r < r1; r++) {
@@ -889,9 +864,10 @@ int64_t prach_sojourn_quantile(const prach_sojourn_spec *s, const uint64_t *hist
     return -1; /* in the overflow */
 }
 
-size_t prach_sojourn_format_csv(const prach_sojourn_spec *s, const prach_sojourn *j, const uint64_t *hist, const uint64_t *row_arrived,
-                                const uint64_t *row_delay_overflow, const char *label, char *buf, size_t cap) {
-    if (!sojourn_spec_ok(s) || !j || !hist || !row_arrived || !row_delay_overflow || !label) return 0;
+static size_t sojourn_csv(const void *spec, const void *group, const uint64_t *const arrays[], const char *label, char *buf, size_t cap) {
+    const prach_sojourn_spec *s = (const prach_sojourn_spec *)spec;
+    const prach_sojourn *j = (const prach_sojourn *)group;
+    const uint64_t *const hist = arrays[0], *const row_arrived = arrays[1], *const row_delay_overflow = arrays[2];
     size_t off = 0;
     for (int r = 0; r < s->arrival_bins; r++) {
         const long long edge = (long long)r * s->arrival_bin_ms;
@@ -1028,7 +1004,14 @@ static int menu_pick_spec_ok(const host_menu *m, const prach_pick_spec *s) {
     return 1;
 }
 /* (the engine judges a spec with these too: csrc/prach_device.h) */
-static int xtab_spec_ok(const prach_xtab_spec *s) { return menu_census_spec_ok(&XTAB_MENU, s); }
+static int census_shape(const host_menu *m, const void *spec, size_t words[]) {
+    const prach_xtab_spec *s = (const prach_xtab_spec *)spec;
+    if (!menu_census_spec_ok(m, s)) return 0;
+    words[0] = ((size_t)s->row_bins + 1) * ((size_t)s->col_bins + 1);
+    return 1;
+}
+static int xtab_shape(const void *spec, size_t words[]) { return census_shape(&XTAB_MENU, spec, words); }
+static int noma_census_shape(const void *spec, size_t words[]) { return census_shape(&NOMA_MENU, spec, words); }
 int prach_internal_noma_census_spec_ok(const prach_xtab_spec *s) { return menu_census_spec_ok(&NOMA_MENU, s); }
 int prach_internal_columns_spec_ok(const prach_columns_spec *s) { return menu_columns_spec_ok(&XTAB_MENU, s); }
 int prach_internal_noma_columns_spec_ok(const prach_columns_spec *s) { return menu_columns_spec_ok(&NOMA_MENU, s); }
@@ -1122,16 +1105,17 @@ int prach_noma_columns_from_logs(const prach_columns_spec *s, const prach_cfg *c
     return menu_columns(&NOMA_MENU, s, cfg, steps, ue, nUE, out, stride);
 }
 
-/* ---- NOMA.c's timeline per trial group and sector (prach_run_trials_noma_timeline): THE DEFINITION, merge, CSV ---- */
+/* ---- NOMA.c's timeline per trial group and sector (prach_run_trials_noma_timeline): THE DEFINITION, CSV ---- */
 
-static int noma_timeline_spec_ok(const prach_noma_timeline_spec *s) {
-    return s && s->bins >= 1 && s->bins <= PRACH_TIMELINE_MAX_BINS && s->bin_ms >= 1;
+static int noma_timeline_shape(const void *spec, size_t words[]) {
+    const prach_noma_timeline_spec *s = (const prach_noma_timeline_spec *)spec;
+    return s ? series_shape(s->bins, s->bin_ms, PRACH_TIMELINE_MAX_BINS, 6, 6, words) : 0;
 }
 
 /* THE DEFINITION (include/prach.h), on the menu's own class and values: nothing of a log is refused, what the menu calls undefined is counted */
 int prach_noma_timeline_accumulate_logs(const prach_noma_timeline_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE,
                                         prach_noma_timeline *t, uint64_t *const series[6]) {
-    if (!noma_timeline_spec_ok(s) || !cfg || !t || !series || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    if (!spec_ok(noma_timeline_shape, s) || !cfg || !t || !series || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
     for (int q = 0; q < 6; q++) if (!series[q]) return PRACH_ERR_ARG;
     int nslots = 0, rc;
     int64_t E = 0;
@@ -1174,39 +1158,11 @@ int prach_noma_timeline_accumulate_logs(const prach_noma_timeline_spec *s, const
     return PRACH_OK;
 }
 
-void prach_noma_timeline_merge(const prach_noma_timeline_spec *s, prach_noma_timeline *into, uint64_t *const into_series[6], const prach_noma_timeline *from,
-                               const uint64_t *const from_series[6]) {
-    if (!noma_timeline_spec_ok(s) || !into || !into_series || !from || !from_series) return;
-    for (int q = 0; q < 6; q++) if (!into_series[q] || !from_series[q]) return;
-    const int64_t a = into->served ? into->done_max : -1, b = from->served ? from->done_max : -1;
-    into->trials += from->trials; into->ues += from->ues; into->idle += from->idle; into->served += from->served; into->dropped += from->dropped;
-    into->pending += from->pending; into->undefined += from->undefined; into->restarted += from->restarted; into->arrival_overflow += from->arrival_overflow;
-    into->done_overflow += from->done_overflow; into->sojourn_sum += from->sojourn_sum; into->timer_sum += from->timer_sum;
-    into->done_max = a > b ? a : b;
-    for (int q = 0; q < 6; q++)
-        for (int i = 0; i < 6 * s->bins; i++) into_series[q][i] += from_series[q][i];
-}
-
-size_t prach_noma_timeline_format_csv(const prach_noma_timeline_spec *s, const prach_noma_timeline *t, const uint64_t *const series[6], const char *label, char *buf,
-                                      size_t cap) {
+static size_t noma_timeline_csv(const void *spec, const void *group, const uint64_t *const series[], const char *label, char *buf, size_t cap) {
     static const char *const names[6] = {"arrivals", "served", "dropped", "sojourn_sum", "timer_sum", "done"};
-    if (!noma_timeline_spec_ok(s) || !t || !series || !label) return 0;
-    for (int q = 0; q < 6; q++) if (!series[q]) return 0;
-    size_t off = 0;
-    for (int q = 0; q < 6; q++) {
-        for (int b = 0; b < s->bins; b++) {
-            uint64_t all = 0;
-            for (int c = 0; c < 6; c++) {
-                const uint64_t v = series[q][(size_t)c * (size_t)s->bins + (size_t)b];
-                all += v;
-                if (v) CSV_EMIT("%.200s,%s,%d,%lld,%llu\n", label, names[q], c, (long long)b * s->bin_ms, (unsigned long long)v);
-            }
-            if (all) CSV_EMIT("%.200s,%s,all,%lld,%llu\n", label, names[q], (long long)b * s->bin_ms, (unsigned long long)all);
-        }
-        if (q == 0 && t->arrival_overflow) CSV_EMIT("%.200s,arrivals,all,overflow,%llu\n", label, (unsigned long long)t->arrival_overflow);
-        if (q == 5 && t->done_overflow) CSV_EMIT("%.200s,done,all,overflow,%llu\n", label, (unsigned long long)t->done_overflow);
-    }
-    return csv_end(buf, cap, off);
+    static const series_lines lines = {names, 6, 6, 2, {{0, 0, offsetof(prach_noma_timeline, arrival_overflow)}, {5, 5, offsetof(prach_noma_timeline, done_overflow)}}};
+    const prach_noma_timeline_spec *s = (const prach_noma_timeline_spec *)spec;
+    return series_csv(&lines, s->bins, s->bin_ms, group, series, label, buf, cap);
 }
 
 /* THE DEFINITION of the pick (prach_pick_from_logs, prach_noma_pick_from_logs): every match is listed, the list is sorted, the first k are the rows */
@@ -1275,23 +1231,10 @@ int prach_noma_pick_from_logs(const prach_pick_spec *s, const prach_cfg *cfg, ui
     return menu_pick(&NOMA_MENU, s, cfg, steps, ue, nUE, hdr, rows);
 }
 
-/* ---- outcome cross-tabulation per trial group (prach_run_trials_xtab): merge, quantile, CSV ---------- */
-
-void prach_xtab_merge(const prach_xtab_spec *s, prach_xtab *into, uint64_t *cells_into, const prach_xtab *from, const uint64_t *cells_from) {
-    if (!xtab_spec_ok(s) || !into || !cells_into || !from || !cells_from) return;
-    const int64_t ra = into->binned ? into->row_max : -1, rb = from->binned ? from->row_max : -1;
-    const int64_t ca = into->binned ? into->col_max : -1, cb = from->binned ? from->col_max : -1;
-    into->trials += from->trials; into->ues += from->ues; into->idle += from->idle; into->served += from->served; into->unserved += from->unserved;
-    into->selected += from->selected; into->binned += from->binned; into->undefined += from->undefined; into->row_sum += from->row_sum;
-    into->col_sum += from->col_sum;
-    into->row_max = ra > rb ? ra : rb;
-    into->col_max = ca > cb ? ca : cb;
-    const size_t n = ((size_t)s->row_bins + 1) * ((size_t)s->col_bins + 1);
-    for (size_t i = 0; i < n; i++) cells_into[i] += cells_from[i];
-}
+/* ---- outcome cross-tabulation per trial group (prach_run_trials_xtab) and the NOMA census (prach_run_trials_noma_census): quantile, CSV ---------- */
 
 int64_t prach_xtab_quantile(const prach_xtab_spec *s, const uint64_t *cells, int row, double q) {
-    if (!xtab_spec_ok(s) || !cells || row < -1 || row > s->row_bins || !(q >= 0.0) || q > 1.0) return -1;
+    if (!spec_ok(xtab_shape, s) || !cells || row < -1 || row > s->row_bins || !(q >= 0.0) || q > 1.0) return -1;
     const int r0 = row < 0 ? 0 : row, r1 = row < 0 ? s->row_bins + 1 : row + 1;
     const size_t W = (size_t)s->col_bins + 1;
     uint64_t n = 0;
@@ -1309,8 +1252,8 @@ int64_t prach_xtab_quantile(const prach_xtab_spec *s, const uint64_t *cells, int
     return -1; /* in the overflow column */
 }
 
-size_t prach_xtab_format_csv(const prach_xtab_spec *s, const prach_xtab *x, const uint64_t *cells, const char *label, char *buf, size_t cap) {
-    if (!xtab_spec_ok(s) || !x || !cells || !label) return 0;
+/* the lines of both: only widths, bin counts and `undefined` enter them */
+static size_t census_lines(const prach_xtab_spec *s, uint64_t undefined, const uint64_t *cells, const char *label, char *buf, size_t cap) {
     size_t off = 0;
     const size_t W = (size_t)s->col_bins + 1;
     for (int r = 0; r <= s->row_bins; r++)
@@ -1322,33 +1265,133 @@ size_t prach_xtab_format_csv(const prach_xtab_spec *s, const prach_xtab *x, cons
             if (c < s->col_bins) snprintf(ce, sizeof ce, "%lld", (long long)c * s->col_width); else strcpy(ce, "overflow");
             CSV_EMIT("%.200s,%s,%s,%llu\n", label, re, ce, (unsigned long long)v);
         }
-    if (x->undefined) CSV_EMIT("%.200s,undefined,,%llu\n", label, (unsigned long long)x->undefined);
+    if (undefined) CSV_EMIT("%.200s,undefined,,%llu\n", label, (unsigned long long)undefined);
     return csv_end(buf, cap, off);
 }
-
-/* ---- the NOMA census (prach_run_trials_noma_census): merge, CSV ---------------------------------------- */
-
-void prach_noma_census_merge(const prach_xtab_spec *s, prach_noma_census *into, uint64_t *cells_into, const prach_noma_census *from, const uint64_t *cells_from) {
-    if (!prach_internal_noma_census_spec_ok(s) || !into || !cells_into || !from || !cells_from) return;
-    const int64_t ra = into->binned ? into->row_max : -1, rb = from->binned ? from->row_max : -1;
-    const int64_t ca = into->binned ? into->col_max : -1, cb = from->binned ? from->col_max : -1;
-    into->trials += from->trials; into->ues += from->ues; into->idle += from->idle; into->served += from->served; into->dropped += from->dropped;
-    into->pending += from->pending; into->selected += from->selected; into->binned += from->binned; into->undefined += from->undefined;
-    into->row_sum += from->row_sum; into->col_sum += from->col_sum;
-    into->row_max = ra > rb ? ra : rb;
-    into->col_max = ca > cb ? ca : cb;
-    const size_t n = ((size_t)s->row_bins + 1) * ((size_t)s->col_bins + 1);
-    for (size_t i = 0; i < n; i++) cells_into[i] += cells_from[i];
+static size_t xtab_csv(const void *spec, const void *group, const uint64_t *const arrays[], const char *label, char *buf, size_t cap) {
+    return census_lines((const prach_xtab_spec *)spec, ((const prach_xtab *)group)->undefined, arrays[0], label, buf, cap);
+}
+static size_t noma_census_csv(const void *spec, const void *group, const uint64_t *const arrays[], const char *label, char *buf, size_t cap) {
+    return census_lines((const prach_xtab_spec *)spec, ((const prach_noma_census *)group)->undefined, arrays[0], label, buf, cap);
 }
 
+/* ---- the grouped kinds (prach_grouped.h): one row each, the generic shape, merge and CSV over the rows, and the public functions as wrappers ---- */
+
+#define GROUPED_ROW(SPEC, GROUP, GUARD, MAXIMA, RESERVED_WORDS, TRIALS, SHAPE, FORMAT) \
+    {sizeof(SPEC), sizeof(GROUP), (int)(sizeof(GROUP) / 8) - (MAXIMA), MAXIMA, (int)(offsetof(GROUP, GUARD) / 8), SHAPE, offsetof(SPEC, ngroups), offsetof(SPEC, reserved), \
+     RESERVED_WORDS, TRIALS, FORMAT}
+/* in the order of the enumerators PRACH_G_*:  spec, group struct, guard counter, maxima, reserved words, trials, shape, CSV */
+static const prach_grouped_row GROUPED[PRACH_G_KINDS] = {
+    GROUPED_ROW(prach_dist_spec, prach_dist, success, 1, 1, PRACH_G_TRIALS_ANY, dist_shape, dist_csv),
+    GROUPED_ROW(prach_timeline_spec, prach_timeline, success, 1, 1, PRACH_G_TRIALS_NOT_NOMA_C, timeline_shape, timeline_csv),
+    GROUPED_ROW(prach_sojourn_spec, prach_sojourn, success, 1, 1, PRACH_G_TRIALS_NOT_NOMA_C, sojourn_shape, sojourn_csv),
+    GROUPED_ROW(prach_trace_spec, prach_trace, subframes, 1, 1, PRACH_G_TRIALS_NOT_NOMA_C, trace_shape, trace_csv),
+    GROUPED_ROW(prach_xtab_spec, prach_xtab, binned, 2, 2, PRACH_G_TRIALS_NOT_NOMA_C, xtab_shape, xtab_csv),
+    GROUPED_ROW(prach_xtab_spec, prach_noma_census, binned, 2, 2, PRACH_G_TRIALS_NOMA_C_PHILOX, noma_census_shape, noma_census_csv),
+    GROUPED_ROW(prach_noma_trace_spec, prach_noma_trace, slots, 1, 1, PRACH_G_TRIALS_NOMA_C_PHILOX, noma_trace_shape, noma_trace_csv),
+    GROUPED_ROW(prach_noma_timeline_spec, prach_noma_timeline, served, 1, 1, PRACH_G_TRIALS_NOMA_C_PHILOX, noma_timeline_shape, noma_timeline_csv),
+};
+
+const prach_grouped_row *prach_internal_grouped_row(int kind) { return kind >= 0 && kind < PRACH_G_KINDS ? &GROUPED[kind] : NULL; }
+
+int prach_internal_grouped_shape(int kind, const void *spec, size_t words[PRACH_G_MAX_ARRAYS]) {
+    const prach_grouped_row *k = prach_internal_grouped_row(kind);
+    return k ? k->shape(spec, words) : 0;
+}
+
+/* the shape of a call on one group: 0 unless the spec is good and the group and every array are there */
+static int grouped_args(int kind, const void *spec, const void *group, const uint64_t *const arrays[], size_t words[PRACH_G_MAX_ARRAYS]) {
+    const int na = prach_internal_grouped_shape(kind, spec, words);
+    if (!na || !group || !arrays) return 0;
+    for (int q = 0; q < na; q++) if (!arrays[q]) return 0;
+    return na;
+}
+
+void prach_internal_grouped_merge(int kind, const void *spec, void *into, uint64_t *const into_arrays[], const void *from, const uint64_t *const from_arrays[]) {
+    size_t words[PRACH_G_MAX_ARRAYS];
+    const int na = grouped_args(kind, spec, into, (const uint64_t *const *)into_arrays, words);
+    if (!na || !grouped_args(kind, spec, from, from_arrays, words)) return;
+    const prach_grouped_row *k = &GROUPED[kind];
+    uint64_t *const a = (uint64_t *)into;
+    const uint64_t *const b = (const uint64_t *)from;
+    int64_t *const amax = (int64_t *)into + k->counters;
+    const int64_t *const bmax = (const int64_t *)from + k->counters;
+    for (int m = 0; m < k->maxima; m++) { /* (a maximum only counts if the guard counter is non-zero: judged before the counters are added) */
+        const int64_t x = a[k->guard] ? amax[m] : -1, y = b[k->guard] ? bmax[m] : -1;
+        amax[m] = x > y ? x : y;
+    }
+    for (int c = 0; c < k->counters; c++) a[c] += b[c];
+    for (int q = 0; q < na; q++)
+        for (size_t i = 0; i < words[q]; i++) into_arrays[q][i] += from_arrays[q][i];
+}
+
+size_t prach_internal_grouped_format_csv(int kind, const void *spec, const void *group, const uint64_t *const arrays[], const char *label, char *buf, size_t cap) {
+    size_t words[PRACH_G_MAX_ARRAYS];
+    if (!grouped_args(kind, spec, group, arrays, words) || !label) return 0;
+    return GROUPED[kind].format(spec, group, arrays, label, buf, cap);
+}
+
+void prach_dist_merge(const prach_dist_spec *s, prach_dist *into, uint64_t *dh_into, uint64_t *ph_into, const prach_dist *from, const uint64_t *dh_from,
+                      const uint64_t *ph_from) {
+    uint64_t *const a[2] = {dh_into, ph_into};
+    const uint64_t *const b[2] = {dh_from, ph_from};
+    prach_internal_grouped_merge(PRACH_G_DIST, s, into, a, from, b);
+}
+size_t prach_dist_format_csv(const prach_dist_spec *s, const prach_dist *d, const uint64_t *delay_hist, const uint64_t *ptc_hist, const char *label, char *buf,
+                             size_t cap) {
+    const uint64_t *const a[2] = {delay_hist, ptc_hist};
+    return prach_internal_grouped_format_csv(PRACH_G_DIST, s, d, a, label, buf, cap);
+}
+void prach_timeline_merge(const prach_timeline_spec *s, prach_timeline *into, uint64_t *const into_series[5], const prach_timeline *from,
+                          const uint64_t *const from_series[5]) {
+    prach_internal_grouped_merge(PRACH_G_TIMELINE, s, into, into_series, from, from_series);
+}
+size_t prach_timeline_format_csv(const prach_timeline_spec *s, const prach_timeline *t, const uint64_t *const series[5], const char *label, char *buf, size_t cap) {
+    return prach_internal_grouped_format_csv(PRACH_G_TIMELINE, s, t, series, label, buf, cap);
+}
+void prach_sojourn_merge(const prach_sojourn_spec *s, prach_sojourn *into, uint64_t *hist_into, uint64_t *arrived_into, uint64_t *overflow_into,
+                         const prach_sojourn *from, const uint64_t *hist_from, const uint64_t *arrived_from, const uint64_t *overflow_from) {
+    uint64_t *const a[3] = {hist_into, arrived_into, overflow_into};
+    const uint64_t *const b[3] = {hist_from, arrived_from, overflow_from};
+    prach_internal_grouped_merge(PRACH_G_SOJOURN, s, into, a, from, b);
+}
+size_t prach_sojourn_format_csv(const prach_sojourn_spec *s, const prach_sojourn *j, const uint64_t *hist, const uint64_t *row_arrived,
+                                const uint64_t *row_delay_overflow, const char *label, char *buf, size_t cap) {
+    const uint64_t *const a[3] = {hist, row_arrived, row_delay_overflow};
+    return prach_internal_grouped_format_csv(PRACH_G_SOJOURN, s, j, a, label, buf, cap);
+}
+void prach_trace_merge(const prach_trace_spec *s, prach_trace *into, uint64_t *const into_series[4], const prach_trace *from, const uint64_t *const from_series[4]) {
+    prach_internal_grouped_merge(PRACH_G_TRACE, s, into, into_series, from, from_series);
+}
+size_t prach_trace_format_csv(const prach_trace_spec *s, const prach_trace *t, const uint64_t *const series[4], const char *label, char *buf, size_t cap) {
+    return prach_internal_grouped_format_csv(PRACH_G_TRACE, s, t, series, label, buf, cap);
+}
+void prach_xtab_merge(const prach_xtab_spec *s, prach_xtab *into, uint64_t *cells_into, const prach_xtab *from, const uint64_t *cells_from) {
+    prach_internal_grouped_merge(PRACH_G_XTAB, s, into, &cells_into, from, &cells_from);
+}
+size_t prach_xtab_format_csv(const prach_xtab_spec *s, const prach_xtab *x, const uint64_t *cells, const char *label, char *buf, size_t cap) {
+    return prach_internal_grouped_format_csv(PRACH_G_XTAB, s, x, &cells, label, buf, cap);
+}
+void prach_noma_census_merge(const prach_xtab_spec *s, prach_noma_census *into, uint64_t *cells_into, const prach_noma_census *from, const uint64_t *cells_from) {
+    prach_internal_grouped_merge(PRACH_G_NOMA_CENSUS, s, into, &cells_into, from, &cells_from);
+}
 size_t prach_noma_census_format_csv(const prach_xtab_spec *s, const prach_noma_census *x, const uint64_t *cells, const char *label, char *buf, size_t cap) {
-    if (!prach_internal_noma_census_spec_ok(s) || !x || !cells || !label) return 0;
-    /* xtab's lines: only widths, bin counts and `undefined` enter them */
-    prach_xtab_spec t = *s;
-    t.who = PRACH_XTAB_SERVED; t.row_field = t.col_field = PRACH_XTAB_ONE;
-    prach_xtab u = {0};
-    u.undefined = x->undefined;
-    return prach_xtab_format_csv(&t, &u, cells, label, buf, cap);
+    return prach_internal_grouped_format_csv(PRACH_G_NOMA_CENSUS, s, x, &cells, label, buf, cap);
+}
+void prach_noma_trace_merge(const prach_noma_trace_spec *s, prach_noma_trace *into, uint64_t *const into_series[6], const prach_noma_trace *from,
+                            const uint64_t *const from_series[6]) {
+    prach_internal_grouped_merge(PRACH_G_NOMA_TRACE, s, into, into_series, from, from_series);
+}
+size_t prach_noma_trace_format_csv(const prach_noma_trace_spec *s, const prach_noma_trace *t, const uint64_t *const series[6], const char *label, char *buf, size_t cap) {
+    return prach_internal_grouped_format_csv(PRACH_G_NOMA_TRACE, s, t, series, label, buf, cap);
+}
+void prach_noma_timeline_merge(const prach_noma_timeline_spec *s, prach_noma_timeline *into, uint64_t *const into_series[6], const prach_noma_timeline *from,
+                               const uint64_t *const from_series[6]) {
+    prach_internal_grouped_merge(PRACH_G_NOMA_TIMELINE, s, into, into_series, from, from_series);
+}
+size_t prach_noma_timeline_format_csv(const prach_noma_timeline_spec *s, const prach_noma_timeline *t, const uint64_t *const series[6], const char *label, char *buf,
+                                      size_t cap) {
+    return prach_internal_grouped_format_csv(PRACH_G_NOMA_TIMELINE, s, t, series, label, buf, cap);
 }
 
 /* ---- picks: the UEs behind a count, per trial (prach_run_trials_pick, prach_run_trials_noma_pick): CSV ---- */
