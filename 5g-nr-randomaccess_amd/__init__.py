@@ -55,7 +55,8 @@ class PrachTiming(C.Structure):
                 ("launches", C.c_int32), ("workgroups", C.c_int32), ("updates", C.c_uint64),
                 ("cluster_size", C.c_int32), ("resident_limit", C.c_int32), ("fallback_trials", C.c_int32), ("spin_timeouts", C.c_int32),
                 ("rec_mode", C.c_int32), ("xcd_packed", C.c_int32), ("group_visits", C.c_uint64), ("event_ues", C.c_uint64),
-                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("noma_timeline_ms", C.c_double), ("noma_trace_ms", C.c_double), ("noma_summary_ms", C.c_double), ("noma_pick_ms", C.c_double), ("noma_census_ms", C.c_double), ("noma_columns_ms", C.c_double), ("columns_ms", C.c_double), ("pick_ms", C.c_double), ("xtab_ms", C.c_double), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
+                ("trial_kernel_reruns", C.c_int32), ("noma_host_ues", C.c_int32), ("noma_gain_host_ues", C.c_int32), ("noma_gain_pad", C.c_int32), ("noma_gain_ms", C.c_double),
+                ("noma_timeline_ms", C.c_double), ("noma_trace_ms", C.c_double), ("noma_summary_ms", C.c_double), ("noma_pick_ms", C.c_double), ("noma_census_ms", C.c_double), ("noma_columns_ms", C.c_double), ("columns_ms", C.c_double), ("pick_ms", C.c_double), ("xtab_ms", C.c_double), ("trace_ms", C.c_double), ("summary_ms", C.c_double), ("dist_ms", C.c_double), ("timeline_ms", C.c_double),
                 ("sojourn_ms", C.c_double)]
 
 
@@ -75,7 +76,7 @@ _U64P = C.POINTER(C.c_uint64)
 
 
 class _Reduction:
-    """What the eight grouped kinds share; csrc/prach_grouped.h states the same on the C side.  A subclass DECLARES its kind and implements nothing of it:
+    """What the grouped kinds share; csrc/prach_grouped.h states the same on the C side.  A subclass DECLARES its kind and implements nothing of it:
 
     _KIND     the name in prach_run_trials_<kind>, prach_<kind>_merge, prach_<kind>_format_csv and prach_<kind>_accumulate_logs
     _PARAMS   the constructor's arguments behind ngroups, (name, converter[, default]) each: they become attributes, and same_as and merge compare them
@@ -677,6 +678,67 @@ class NomaTrace(_Reduction):
             return np.where(g > 0, (2 * p - o) / g, np.nan)
 
 
+NOMA_GAIN_MAX_BINS, NOMA_GAIN_NO_LEVEL = 4096, -2 ** 31
+NOMA_GAIN_SERIES = ("arrived", "served", "dropped", "sojourn_sum", "lost_sum", "ptc_sum")
+NOMA_GAIN_FIELDS = ("trials", "ues", "idle", "served", "dropped", "pending", "undefined", "below", "above", "restarted", "sojourn_sum", "lost_sum", "ptc_sum", "defined",
+                    "level_max", "neg_level_max")
+
+
+class PrachNomaGainSpec(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("bins", "width", "lo", "ngroups", "reserved")]
+
+
+class PrachNomaGain(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in NOMA_GAIN_FIELDS[:-2]] + [("level_max", C.c_int64), ("neg_level_max", C.c_int64)]
+
+
+class NomaGain(_Reduction):
+    """NOMA.c's near-far profiles of ``ngroups`` trial groups (include/prach.h, prach_noma_gain): ``series`` [6, ngroups, 6 sectors, bins] as numpy uint64 in the
+    order of NOMA_GAIN_SERIES — and each series under its name as a [ngroups, 6, bins] view — by the bin of the UE's GAIN LEVEL floor(1000 ln g): bin b covers the
+    levels [lo + b * width, lo + (b + 1) * width); ``scalars[field]``, one int64 array of length ngroups per field of NOMA_GAIN_FIELDS (level_max and
+    neg_level_max are -1 where ``defined`` is 0).  The sector is the UE's own, also under FLAG_NOMA_NONSECTOR."""
+    _KIND, _PARAMS, _RUN, _HOST, _LOGS, _NOUN = "noma_gain", (("bins", int, 65), ("width", int, 200), ("lo", int, -16200)), "array", "array", "cfg,steps", "profiles"
+    _SPEC, _SPEC_OF = PrachNomaGainSpec, lambda s: (s.bins, s.width, s.lo, s.ngroups, 0)
+    _STRUCT, _FIELDS, _MAXIMA = PrachNomaGain, NOMA_GAIN_FIELDS, 2
+    _NAMES, _SHAPE, _EXPOSE, _VIEWS = NOMA_GAIN_SERIES, lambda s: ((6, s.bins),) * 6, "stack", True
+
+    def edges(self):
+        """The lower edge of every bin, in level units (hundredths of 10 ln g): [bins] int64."""
+        import numpy as np
+        return self.lo + self.width * np.arange(self.bins, dtype=np.int64)
+
+    def named(self, name, group, sector=None):
+        """Series ``name`` of one group — of one sector, or summed over the sectors: [bins] float64."""
+        import numpy as np
+        a = self.series[NOMA_GAIN_SERIES.index(name), group]
+        return (a.sum(axis=0) if sector is None else a[sector]).astype(np.float64)
+
+    def _ratio(self, num, den):
+        import numpy as np
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(den > 0, num / den, np.nan)
+
+    def served_ratio(self, g, sector=None):
+        """served / arrived per gain bin of one group (one sector, or all), as float64; NaN where nobody arrived."""
+        return self._ratio(self.named("served", g, sector), self.named("arrived", g, sector))
+
+    def dropped_ratio(self, g, sector=None):
+        """dropped / arrived per gain bin; NaN where nobody arrived."""
+        return self._ratio(self.named("dropped", g, sector), self.named("arrived", g, sector))
+
+    def mean_sojourn(self, g, sector=None):
+        """sojourn_sum / served per gain bin, in ms: arrival to completion of the served UEs of that gain; NaN where none was served."""
+        return self._ratio(self.named("sojourn_sum", g, sector), self.named("served", g, sector))
+
+    def mean_lost(self, g, sector=None):
+        """lost_sum / served per gain bin, in ms: arrival to the start of the last cycle; NaN where none was served."""
+        return self._ratio(self.named("lost_sum", g, sector), self.named("served", g, sector))
+
+    def mean_ptc(self, g, sector=None):
+        """ptc_sum / served per gain bin: preamble transmissions of the served UEs of that gain; NaN where none was served."""
+        return self._ratio(self.named("ptc_sum", g, sector), self.named("served", g, sector))
+
+
 NOMA_TIMELINE_SERIES = ("arrivals", "served", "dropped", "sojourn_sum", "timer_sum", "done")
 NOMA_TIMELINE_FIELDS = ("trials", "ues", "idle", "served", "dropped", "pending", "undefined", "restarted", "arrival_overflow", "done_overflow", "sojourn_sum", "timer_sum",
                         "done_max")
@@ -903,7 +965,7 @@ def lib():
         u64p = C.POINTER(C.c_uint64)
         # the three or four public functions of every grouped kind, from the class declarations (_Reduction)
         cfgp, uep = C.POINTER(PrachCfg), C.POINTER(PrachUeLog)
-        for R in (Dist, Timeline, Sojourn, Trace, Xtab, NomaCensus, NomaTrace, NomaTimeline):
+        for R in (Dist, Timeline, Sojourn, Trace, Xtab, NomaCensus, NomaTrace, NomaTimeline, NomaGain):
             sp, gp, ptrs = C.POINTER(R._SPEC), C.POINTER(R._STRUCT), {"flat": [u64p] * len(R._NAMES), "array": [C.POINTER(u64p)]}
             getattr(L, f"prach_run_trials_{R._KIND}").argtypes = [vp, cfgp, C.c_int, C.POINTER(PrachResult), C.POINTER(uep), sp, C.POINTER(C.c_int32), gp] + ptrs[R._RUN]
             merge, fmt = getattr(L, f"prach_{R._KIND}_merge"), getattr(L, f"prach_{R._KIND}_format_csv")
@@ -988,6 +1050,11 @@ def lib():
         L.prach_noma_trace_tile_rows.argtypes = []
         L.prach_noma_timeline_tile_ues.argtypes = []
         L.prach_noma_timeline_window_bins.argtypes = []
+        L.prach_noma_gain_level.argtypes, L.prach_noma_gain_level.restype = [C.c_double], C.c_int32
+        L.prach_noma_gain_levels.argtypes = [cfgp, C.c_void_p]
+        L.prach_noma_gain_accumulate_levels.argtypes = [C.POINTER(PrachNomaGainSpec), cfgp, C.c_uint64, uep, C.c_int, C.c_void_p, C.POINTER(PrachNomaGain), C.POINTER(u64p)]
+        L.prach_noma_gain_tile_ues.argtypes = []
+        L.prach_noma_gain_lds_max_bins.argtypes = []
         _lib = L
     return _lib
 
@@ -1010,7 +1077,9 @@ EXPORTS = ("prach_engine_create", "prach_engine_destroy", "prach_engine_set", "p
            "prach_run_trials_noma_pick", "prach_noma_pick_from_logs", "prach_noma_pick_format_csv", "prach_run_trials_noma_summary", "prach_noma_summary_from_logs",
            "prach_noma_summary_stats", "prach_noma_summary_format_csv", "prach_run_trials_noma_trace", "prach_noma_trace_merge", "prach_noma_trace_format_csv",
            "prach_noma_trace_tile_rows", "prach_run_trials_noma_timeline", "prach_noma_timeline_accumulate_logs", "prach_noma_timeline_merge",
-           "prach_noma_timeline_format_csv", "prach_noma_timeline_tile_ues", "prach_noma_timeline_window_bins")
+           "prach_noma_timeline_format_csv", "prach_noma_timeline_tile_ues", "prach_noma_timeline_window_bins", "prach_run_trials_noma_gain", "prach_noma_gain_level",
+           "prach_noma_gain_levels", "prach_noma_gain_accumulate_levels", "prach_noma_gain_accumulate_logs", "prach_noma_gain_merge", "prach_noma_gain_format_csv",
+           "prach_noma_gain_tile_ues", "prach_noma_gain_lds_max_bins")
 
 
 def make_cfg(nUE, variant=VARIANT_BETA_C, uniform=0, rng_mode=RNG_GLIBC, seed=0, stream_offset=0, **kw) -> PrachCfg:
@@ -1191,6 +1260,13 @@ class Engine:
         (prach_run_trials_noma_timeline; NOMA.c trials with Philox only).  groups / ngroups / want_logs as in run_trials_dist.  Returns
         (results, logs, NomaTimeline)."""
         return self._call_reduced(NomaTimeline(_ngroups(len(cfgs), groups, ngroups), bins, bin_ms), cfgs, groups, want_logs)
+
+    def run_trials_noma_gain(self, cfgs, bins=65, width=200, lo=-16200, groups=None, ngroups=None, want_logs=False):
+        """run_trials plus NOMA.c's near-far profiles per trial group and sector — arrived, served, dropped, sojourn, lost-time and preamble-count sums by the
+        UE's channel-gain level floor(1000 ln g) — reduced on the device from the log records and the launch's own activation table
+        (prach_run_trials_noma_gain; NOMA.c trials with Philox only).  The defaults cover -162.00 ... -32.00 in 10 ln g, the whole range a trial can produce.
+        groups / ngroups / want_logs as in run_trials_dist.  Returns (results, logs, NomaGain)."""
+        return self._call_reduced(NomaGain(_ngroups(len(cfgs), groups, ngroups), bins, width, lo), cfgs, groups, want_logs)
 
     def run_trials_trace(self, cfgs, bins, bin_ms=1, groups=None, want_logs=False, ngroups=None):
         """run_trials plus the per-subframe preamble trace per trial group — preambles used (calls), decoded (singles) and what the subframes added to
@@ -1417,6 +1493,59 @@ def noma_timeline_tile_ues() -> int:
 
 def noma_timeline_window_bins() -> int:
     return lib().prach_noma_timeline_window_bins()
+
+
+def noma_gain_tile_ues() -> int:
+    return lib().prach_noma_gain_tile_ues()
+
+
+def noma_gain_lds_max_bins() -> int:
+    return lib().prach_noma_gain_lds_max_bins()
+
+
+def noma_gain_level(lgain: float) -> int:
+    """The gain level of ln(gain): floor(1000 * lgain), NOMA_GAIN_NO_LEVEL where there is none (prach_noma_gain_level)."""
+    return int(lib().prach_noma_gain_level(float(lgain)))
+
+
+def noma_gain_levels(cfg):
+    """The host's gain levels of every UE of a NOMA.c Philox trial, as an int32 array [nUE] (prach_noma_gain_levels): joins with run_trials_noma_columns."""
+    import numpy as np
+    out = np.empty(max(int(cfg.nUE), 0), dtype=np.int32)
+    rc = lib().prach_noma_gain_levels(C.byref(cfg), out.ctypes.data_as(C.c_void_p))
+    if rc != OK:
+        raise PrachError(rc, "(prach_noma_gain_levels)")
+    return out
+
+
+def noma_gain_from_logs(cfgs, steps, logs, bins=65, width=200, lo=-16200, groups=None, ngroups=None) -> NomaGain:
+    """The host-side definition of the near-far profiles with the host's own levels (prach_noma_gain_accumulate_logs): logs[k] is the per-UE log of the NOMA.c
+    Philox trial with config cfgs[k] that ran steps[k] subframes — a ctypes array of PrachUeLog or an int32 array [nUE, 16] — added to group groups[k]."""
+    return NomaGain.from_logs(logs, bins, width, lo, cfgs=cfgs, steps=steps, groups=groups, ngroups=ngroups)
+
+
+def noma_gain_from_levels(cfgs, steps, logs, levels, bins=65, width=200, lo=-16200, groups=None, ngroups=None) -> NomaGain:
+    """THE DEFINITION with the levels as given (prach_noma_gain_accumulate_levels; any RNG mode): levels[k] is an int32 array [nUE] next to logs[k]."""
+    import numpy as np
+    red = NomaGain(_ngroups(len(logs), groups, ngroups), bins, width, lo)
+    sp = red.spec()
+    for k, lg in enumerate(logs):
+        g = k if groups is None else int(groups[k])
+        ptr, nue, _keep = _log_ptr(lg)
+        lv = np.ascontiguousarray(levels[k], dtype=np.int32)
+        if lv.shape != (nue,):
+            raise ValueError("one level per UE of the log")
+        d = red._group(g)
+        rc = lib().prach_noma_gain_accumulate_levels(C.byref(sp), C.byref(cfgs[k]), int(steps[k]), ptr, nue, lv.ctypes.data_as(C.c_void_p), C.byref(d), *red._ptrs("array", g))
+        if rc != OK:
+            raise PrachError(rc, "(prach_noma_gain_accumulate_levels)")
+        red._store(g, d)
+    return red
+
+
+def noma_gain_csv(gn: NomaGain, labels=None) -> bytes:
+    """The CSV text of every group (prach_noma_gain_format_csv), labelled labels[g] (default: the group number)."""
+    return gn.csv(labels)
 
 
 def noma_timeline_from_logs(cfgs, steps, logs, bins, bin_ms=5, groups=None, ngroups=None) -> NomaTimeline:

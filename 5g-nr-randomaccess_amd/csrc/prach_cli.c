@@ -67,6 +67,11 @@
  * all by ARRIVAL time, and the completions by completion time — on --census-trace's bins, so that the two files line up; one group per sweep point with the
  * --times seeds merged, labelled nUE; bins of MS ms (default 5) that cover maxTime + 6; --program noma with Philox only, and not together with another
  * reduction.  (A sojourn HISTOGRAM by arrival time is --census FILE --census-rows arrival:W:B --census-cols sojourn:W:B --census-who served);
+ * --census-gain FILE [--census-gain-bins N] [--census-gain-width W] [--census-gain-lo L]: NOMA.c's near-far profile (prach_run_trials_noma_gain: reduced on the
+ * device from the log records and the launch's own activation table) — per sector and all sectors, the UEs that arrived, were served and were dropped, and the
+ * sojourn, lost-time and preamble-count sums of the served, by the UE's channel-gain LEVEL floor(1000 ln g): N bins (default 65, at most 4096) of W levels
+ * (default 200) from level L on (default -16200: -162.00 ... -32.00 in 10 ln g, every gain a trial can draw); one group per sweep point with the --times seeds
+ * merged, labelled nUE; --program noma with Philox only, and not together with another reduction;
  * --devices LIST: the same with explicit HIP ordinals (an ordinal may repeat);
  * --gpus N: the --times x sweep grid sharded over N devices of the node by host C — one forked child per device,
  * forked BEFORE any HIP call, trials dealt by descending cost (Philox: any trial anywhere; glibc: whole seeds, because
@@ -136,7 +141,7 @@ static double now_s(void) {
 }
 
 /* The reduction a run makes on the device next to its results, never two of them.  A GROUPED kind (csrc/prach_grouped.h: --cdf, --timeline, --sojourn, --trace,
- * --xtab, --census, --census-trace, --census-timeline) is a block of groups, one group per sweep point; a block holds the groups of one worker or of one call:
+ * --xtab, --census, --census-trace, --census-timeline, --census-gain) is a block of groups, one group per sweep point; a block holds the groups of one worker or of one call:
  * the kind's structs [npts], then its arrays in the order of the C ABI, array q of all groups [npts][words of q] — e.g. --cdf prach_dist[npts] |
  * delay_hist[npts][bins] | ptc_hist[npts][256]; --sojourn prach_sojourn[npts] | hist[npts][rows][bins] | row_arrived[npts][rows] | row_delay_overflow[npts][rows].
  * The library's row of the kind says the sizes; shape, merge, run and CSV are the library's generic functions.  No kind, no per-trial spec: plain prach_run_trials. */
@@ -404,7 +409,8 @@ int main(int argc, char *argv[]) {
     prach_noma_summary_spec nci_spec = {0, 4, {PRACH_NOMA_SOJOURN, PRACH_NOMA_TIMER, PRACH_NOMA_PTC, PRACH_NOMA_LOST}, 3, {500, 950, 990, 0, 0, 0, 0, 0}, {0, 0}};
     prach_pick_spec npk_spec = {0, 0, {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, PRACH_PICK_BY_INDEX, PRACH_NOMA_ONE, 16, 0};
     int cdf_bins = 4096, cdf_bin_ms = 1, tl_bin_ms = 5, sj_row_ms = 500, sj_bin_ms = 5, tr_bin_ms = 5, ntr_bin_ms = 5, ntl_bin_ms = 5;
-    const char *ntr_path = NULL, *ntl_path = NULL;
+    const char *ntr_path = NULL, *ntl_path = NULL, *ng_path = NULL;
+    int ng_bins = 65, ng_width = 200, ng_lo = -16200;
     int devs[64];
     /* --program must be known before the defaults are laid down */
     for (int i = 1; i + 1 < argc; i += 2)
@@ -513,6 +519,16 @@ int main(int argc, char *argv[]) {
             xt_cols = v;
         } else if (strcmp(a, "--xtab-who") == 0) {
             xt_who = v;
+        } else if (strcmp(a, "--census-gain") == 0) {
+            ng_path = v;
+        } else if (strcmp(a, "--census-gain-bins") == 0) {
+            if (atoi(v) < 1 || atoi(v) > PRACH_NOMA_GAIN_MAX_BINS) die("--census-gain-bins N: the number of gain-level bins, 1 to 4096");
+            ng_bins = atoi(v);
+        } else if (strcmp(a, "--census-gain-width") == 0) {
+            if (atoi(v) < 1) die("--census-gain-width W: the width of a gain-level bin in levels (hundredths of 10 ln g), at least 1");
+            ng_width = atoi(v);
+        } else if (strcmp(a, "--census-gain-lo") == 0) {
+            ng_lo = atoi(v);
         } else if (strcmp(a, "--census-timeline") == 0) {
             ntl_path = v;
         } else if (strcmp(a, "--census-timeline-bin") == 0) {
@@ -602,6 +618,9 @@ int main(int argc, char *argv[]) {
         }
     }
     base.rng_mode = rng;
+    if (ng_path && variant != PRACH_VARIANT_NOMA_C) die("--census-gain needs --program noma (the other programs draw no channel gain)");
+    if (ng_path && (ntl_path || ntr_path || nci_path || npk_path || nc_path || pk_path || xt_path || tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--census-gain cannot be combined with another reduction: one reduction per call");
+    if (ng_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census-gain needs --rng philox (NOMA.c in the reference's stream is not wired to the NOMA menu's device calls)");
     if (ntl_path && variant != PRACH_VARIANT_NOMA_C) die("--census-timeline needs --program noma (the other programs have --timeline)");
     if (ntl_path && (ntr_path || nci_path || npk_path || nc_path || pk_path || xt_path || tr_path || ci_path || sj_path || tl_path || cdf_path)) die("--census-timeline cannot be combined with another reduction: one reduction per call");
     if (ntl_path && rng_given && rng == PRACH_RNG_GLIBC) die("--census-timeline needs --rng philox (NOMA.c in the reference's stream is not wired to the NOMA menu's device calls)");
@@ -729,6 +748,10 @@ int main(int argc, char *argv[]) {
     if (ntl_path && ntl_bins > PRACH_TIMELINE_MAX_BINS) die("--census-timeline-bin MS: too many bins");
     if (ntl_path && 36 * (uint64_t)npts * (uint64_t)ntl_bins > (1ull << 27)) die("--census-timeline: too many bins for this many sweep points");
     if (ntl_path) { red_ci.kind = PRACH_G_NOMA_TIMELINE; red_ci.spec = &ntl_spec; red_ci.path = ntl_path; red_ci.text_cap = 80 * (6 * 7 * (size_t)ntl_bins + 2) + 1; } /* (a line: the label, a series name, a sector, two numbers) */
+    /* --census-gain: NOMA.c's near-far profile per sector */
+    const prach_noma_gain_spec ng_spec = {ng_bins, ng_width, ng_lo, npts, 0};
+    if (ng_path && 36 * (uint64_t)npts * (uint64_t)ng_bins > (1ull << 27)) die("--census-gain: too many bins for this many sweep points");
+    if (ng_path) { red_ci.kind = PRACH_G_NOMA_GAIN; red_ci.spec = &ng_spec; red_ci.path = ng_path; red_ci.text_cap = 80 * (6 * 7 * (size_t)ng_bins + 2) + 1; } /* (a line: the label, a series name, a sector, two numbers) */
     if (ntr_path) { red_ci.kind = PRACH_G_NOMA_TRACE; red_ci.spec = &ntr_spec; red_ci.path = ntr_path; red_ci.text_cap = 80 * (6 * 7 * (size_t)ntr_bins + 1) + 1; } /* (a line: the label, a series name, a sector, two numbers) */
     /* --xtab: the axes as given, the defaults of a field where width or bins are left out */
     prach_xtab_spec xt_spec = {0, 0, 0, 0, 0, 0, 0, npts, {0, 0}};

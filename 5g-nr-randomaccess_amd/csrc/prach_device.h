@@ -349,4 +349,34 @@ constexpr int NTL_SCALARS = 12, NTL_SUMS = 10, NTL_MAXIMA = 1; // per group: idl
 struct NomaTimelineOut { unsigned long long *series[6], *scalars; }; // [ngroups][6 sectors][bins] each: arrivals, served, dropped, sojourn_sum, timer_sum, done; [ngroups][NTL_SCALARS]
 hipError_t launch_noma_timeline_kernel(const TimelineJob *jobs, int njobs, int workgroups, int bins, int bin_ms, int scheme, int window, NomaTimelineOut out, hipStream_t stream);
 
+// prach_noma_gain.hip: NOMA.c's near-far profile of a launch's accepted trials (prach_run_trials_noma_gain).  A job is the timeline's with E in `pad`, plus the
+// trial's ln(gain) column of the activation table and its 4-byte-per-UE LEVEL column; tile and workgroup are the timeline's.  Two kernels:
+//   the level pre-pass   level[i] = floor(1000 x lgain[i]) for every UE of every job; a UE whose product lies within NG_LEVEL_BAND of an integer, outside the
+//                        range the band is derived for, or that has no level is EDGE: appended as (job, UE) to a list of NG_EDGE_CAP entries behind two
+//                        header words (the count — which goes on counting past the capacity — and a spare), for the host to resolve;
+//   the reducer          scheme 1 keeps all 6 series x 6 sectors x bins 32-bit counters of a tile in LDS when bins <= NG_LDS_MAX_BINS and flushes the non-zero
+//                        ones; otherwise, and under scheme 0, everything goes straight to the call's buffers.  Both with 64-bit agent-scope atomics.
+// THE BAND.  With a device-built table (n_devact) the gain of an unflagged UE is within ACT_GAIN_ULP_ASSERTED ulps of the host libm's (prach_noma_act.h), so
+// ln g is off by at most that many ulps of 1.0 (d ln g = dg / g) plus the ulps of the two logarithms themselves (NG_LOG_ULPS for the device's, one for the
+// host's), each an ulp of a value below 32 (a trial's |ln g| is below 16.2): 2^-48.  Times 1000, plus one ulp of the product (two roundings of half an ulp of a
+// value below 2^15: 2^-37).  The band is a hundred times that.
+constexpr int NG_EDGE_CAP = 4096;
+constexpr double NG_LEVEL_RANGE = 32768.0; // |1000 ln g| below this: what the band is derived for (a product outside is EDGE)
+constexpr int NG_LOG_ULPS = 2;
+constexpr double NG_LEVEL_BAND = 1e-8;
+constexpr double NG_LEVEL_ERROR = 1000.0 * (32 /* ACT_GAIN_ULP_ASSERTED */ * 0x1p-52 + (NG_LOG_ULPS + 1) * 0x1p-48) + 0x1p-37;
+static_assert(NG_LEVEL_BAND >= 100.0 * NG_LEVEL_ERROR, "the level band covers the error of 1000 ln g of a device-built table a hundred times over");
+static_assert(NG_LEVEL_BAND < 1e-6, "... and stays narrow: about 2 x band of the UEs go to the host");
+constexpr int NG_LDS_MAX_BINS = 511;
+static_assert(4 * (2048 + 36 * NG_LDS_MAX_BINS) + 8 * 16 <= 80 * 1024, "the counters, the staged schedule range and the scalars take at most half the 160 KiB of LDS of a gfx950 CU: two workgroups per CU");
+constexpr int NG_MAX_ADDEND = NTL_MAX_SOJOURN; // a sojourn, lost time or preamble count up to this goes into a tile's 32-bit LDS counter; a larger one straight out
+constexpr int NG_SCALARS = 16, NG_SUMS = 12, NG_MAXIMA = 2; // per group: idle, served, dropped, pending, undefined, below, above, restarted, sojourn_sum, lost_sum, ptc_sum, defined | level_max + 2^31, -level_min + 2^31 (0: no defined UE) | 2 spare
+struct NomaGainJob : TimelineJob {
+    const double *lgain; // [nUE] the activation table's ln(gain)
+    int *level;          // [nUE] the level column
+};
+struct NomaGainOut { unsigned long long *series[6], *scalars; }; // [ngroups][6 sectors][bins] each: arrived, served, dropped, sojourn_sum, lost_sum, ptc_sum; [ngroups][NG_SCALARS]
+hipError_t launch_noma_gain_levels(const NomaGainJob *jobs, int njobs, int workgroups, unsigned *edges, int edge_cap, hipStream_t stream); // edges: [2 + 2 x edge_cap], zeroed
+hipError_t launch_noma_gain_kernel(const NomaGainJob *jobs, int njobs, int workgroups, int bins, int width, int lo, int scheme, NomaGainOut out, hipStream_t stream);
+
 } // namespace prach

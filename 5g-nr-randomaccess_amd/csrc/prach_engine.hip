@@ -101,6 +101,7 @@ struct TrialLayout {
     size_t rec, ptc, ftt, stt, fcnt, nd, evbuf, evbuf2, sidx, sched, stream, logs, timers, out, mbox, cand;
     size_t trace; // prach_run_trials_trace: one 16-byte row per subframe, in the zeroed region (0: none)
     size_t n_pre0, n_sector, n_gain, n_lgain, n_nd0, sector;
+    size_t n_level, gain_edges; // prach_run_trials_noma_gain: the trial's 4-byte-per-UE level column; the launch's list of EDGE UEs (in the zeroed region, the same in every trial; 0: none)
     size_t rec32, chunks, ctab, cpool, jcal, qov, evov; // batch kernel
     int calcap, calslots, npool, tcap;
     size_t diag;                 // diagnostic build: per-workgroup stamps (zeroed region)
@@ -136,7 +137,8 @@ size_t mbox_bytes(const prach_cfg &c, int G, int &evw, int &mbstride) {
 // stream_len[k]: glibc draw-stream window of trial k (0 in Philox mode); G: workgroups per trial (0 = trial_kernel)
 // all_logs: every trial gets a device log region (the call's reduction reads it there: prach_run_trials_timeline, prach_run_trials_sojourn), not only the ones whose log the host asked for
 // trace: every trial gets its per-subframe rows (prach_run_trials_trace): 16 bytes x maxTime, zeroed with the rest of the zeroed region
-LaunchLayout layout_launch(const prach_cfg *cfgs, const int *idx, int m, prach_ue_log *const *ue_logs, bool all_logs, bool trace, const std::vector<size_t> &stream_len, int G, bool batch, bool full_calendars, int64_t calendar_cap) {
+// levels: every NOMA.c trial gets a level column and the launch a list of EDGE UEs (prach_run_trials_noma_gain)
+LaunchLayout layout_launch(const prach_cfg *cfgs, const int *idx, int m, prach_ue_log *const *ue_logs, bool all_logs, bool trace, bool levels, const std::vector<size_t> &stream_len, int G, bool batch, bool full_calendars, int64_t calendar_cap) {
     LaunchLayout L;
     L.t.resize(m);
     size_t o = align_up(sizeof(TrialDev) * (size_t)m, 256);
@@ -172,6 +174,7 @@ LaunchLayout layout_launch(const prach_cfg *cfgs, const int *idx, int m, prach_u
         }
     }
     if (cfgs[idx[0]].variant == PRACH_VARIANT_NOMA_C) L.act_flags = take(4 * (2 + 2 * (size_t)NOMA_ACT_FLAG_CAP));
+    const size_t gain_edges = levels ? take(4 * (2 + 2 * (size_t)NG_EDGE_CAP)) : 0;
     L.zero_end = o;
     for (int k = 0; k < m; k++) {
         const prach_cfg &c = cfgs[idx[k]];
@@ -215,6 +218,8 @@ LaunchLayout layout_launch(const prach_cfg *cfgs, const int *idx, int m, prach_u
         if (c.variant == PRACH_VARIANT_NOMA_C) {
             T.n_pre0 = take(4 * n); T.n_sector = take(4 * n); T.n_gain = take(8 * n); T.n_lgain = take(8 * n); T.n_nd0 = take(4 * n);
         }
+        T.n_level = levels && c.variant == PRACH_VARIANT_NOMA_C ? take(4 * n) : 0;
+        T.gain_edges = gain_edges;
     }
     L.end = o;
     return L;
@@ -441,7 +446,7 @@ static int noma_device_activation(prach_engine *e, const TrialDev *dparams, cons
 // a row.  The HOST-SIDE row of a grouped kind (one struct and a few arrays per trial group) is in GROUPED of prach_host.c, stated by csrc/prach_grouped.h: its
 // sizes, the shape of its arrays, its spec's judge, the trials it takes, its CSV lines.  There a new grouped kind costs an enumerator, that row, an entry of
 // GROUPED_RED below and its three public functions as wrappers; the refusals (prach_internal_grouped_run), merge, CSV dispatch and the CLI's blocks are generic.
-enum class Red { dist, timeline, sojourn, summary, trace, xtab, pick, columns, noma_census, noma_columns, noma_summary, noma_pick, noma_trace, noma_timeline };
+enum class Red { dist, timeline, sojourn, summary, trace, xtab, pick, columns, noma_census, noma_columns, noma_summary, noma_pick, noma_trace, noma_timeline, noma_gain };
 constexpr int RED_MAX_PARTS = 7;
 struct Reduction {
     Red kind;
@@ -472,6 +477,10 @@ struct RedKind {
     void (*empty)(const Reduction &, size_t g, const prach_cfg *cfgs); // the caller's struct of group g before anything ran
     int (*unpack)(const Reduction &, CallCtx &, size_t g, const unsigned long long *q); // ... and from the group's scalar words at the end of the call
     double prach_timing::*ms;                 // where the kernel time of the call goes
+    // a kind whose kernel needs something prepared per launch, behind the jobs' upload and in front of the kernel (nullptr: nothing): the jobs of the accepted
+    // trials are on the device (and at e->red_jobs_h); `levels`: every NOMA.c trial of the call's launches gets a level column and the launch a list of EDGE UEs
+    int (*prepass)(prach_engine *e, CallCtx &, const std::vector<JobSrc> &acc, int njobs, int wgs) = nullptr;
+    bool levels = false;
 };
 const RedKind &kind_of(const Reduction &r);
 
@@ -482,6 +491,7 @@ struct CallCtx {
     prach_ue_log *const *ue_logs;
     double kernel_ms = 0, upload_ms = 0;
     int noma_flagged = 0, noma_ambiguous = 0; // UEs recomputed on the host, trials rerun with the host-built table
+    int gain_host_ues = 0;                    // prach_run_trials_noma_gain: UEs whose level the host resolved
     // the call's reduction (red == nullptr: plain prach_run_trials, nothing below is touched)
     const Reduction *red = nullptr;
     double red_ms = 0;
@@ -490,6 +500,7 @@ struct CallCtx {
     int group_of(int k) const { return red->group ? red->group[k] : k; }
     bool reads_device_logs() const { return red && kind_of(*red).device_logs; }
     bool traces() const { return red && kind_of(*red).trace_rows; }
+    bool levels() const { return red && kind_of(*red).levels; }
 };
 // ---- the kinds of reduction, one block each --------------------------------------------------------------------------------------------------------------
 template <class T> const T &spec_of(const Reduction &r) { return *static_cast<const T *>(r.spec); }
@@ -803,6 +814,85 @@ int noma_timeline_unpack(const Reduction &r, CallCtx &cx, size_t g, const unsign
     return PRACH_OK;
 }
 
+template <class F> static void parallel_for(int nth, size_t n, const F &f); // (below)
+
+// noma_gain: the six series arrived, served, dropped, sojourn_sum, lost_sum, ptc_sum, [6 sectors][bins] per group | scalars; reads the log records, the launch's
+// schedule and E like the NOMA timeline, and the level column its pre-pass fills from the launch's activation table (prach_noma_gain.hip)
+int noma_gain_parts(const Reduction &r, size_t w[]) { for (int q = 0; q < 6; q++) w[q] = 6 * (size_t)spec_of<prach_noma_gain_spec>(r).bins; w[6] = NG_SCALARS; return 7; }
+int noma_gain_fill_job(void *job, const JobSrc &s) {
+    NomaGainJob *const j = static_cast<NomaGainJob *>(job);
+    const int n = fill_timeline_job<true>(static_cast<TimelineJob *>(j), s);
+    j->lgain = reinterpret_cast<const double *>(s.A + s.L.n_lgain);
+    j->level = reinterpret_cast<int *>(s.A + s.L.n_level);
+    return n;
+}
+// The level pre-pass of a launch's accepted trials, then the host's part: the listed EDGE UEs are recomputed with the host's libm (prach_noma_activation_range,
+// prach_noma_gain_level) and their 4-byte levels patched into the column — as noma_device_activation patches the activation table; when the list overflowed,
+// every level of the launch is built on the host, never silently.  On the engine's stream, completed on return: the reducer starts behind it.
+int noma_gain_prepass(prach_engine *e, CallCtx &cx, const std::vector<JobSrc> &acc, int njobs, int wgs) {
+    if (njobs != (int)acc.size() || !acc[0].L.gain_edges) return PRACH_ERR_INTERNAL;
+    for (const JobSrc &s : acc) if (!s.L.n_level || !s.L.n_lgain) return PRACH_ERR_INTERNAL; // (a launch that laid out no level column: not a NOMA.c Philox launch)
+    unsigned *const dedges = reinterpret_cast<unsigned *>(acc[0].A + acc[0].L.gain_edges);
+    HIPCHK(launch_noma_gain_levels(reinterpret_cast<const NomaGainJob *>(e->red_jobs_d), njobs, wgs, dedges, NG_EDGE_CAP, e->stream));
+    unsigned nedge = 0;
+    HIPCHK(hipMemcpyAsync(&nedge, dedges, 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (!nedge) return PRACH_OK;
+    struct Act { int32_t pre0, sec; double gn, lg; uint32_t nd0; };
+    if (nedge > (unsigned)NG_EDGE_CAP) {
+        std::fprintf(stderr, "[prach] the gain-level pre-pass listed %u UEs (more than its list holds): the levels of this launch are built on the host\n", nedge);
+        for (const JobSrc &s : acc) {
+            std::vector<int32_t> lv((size_t)s.c.nUE);
+            const int step = 4096;
+            std::vector<int> rcs((size_t)(s.c.nUE + step - 1) / step, PRACH_OK);
+            parallel_for(host_threads(e), rcs.size(), [&](size_t q) {
+                const int lo = (int)q * step, hi = std::min(s.c.nUE, lo + step);
+                std::vector<Act> a((size_t)(hi - lo));
+                for (int i = lo; i < hi && rcs[q] == PRACH_OK; i++) {
+                    Act &x = a[(size_t)(i - lo)];
+                    rcs[q] = prach_noma_activation_range(&s.c, i, i + 1, &x.pre0, &x.sec, &x.gn, &x.lg, &x.nd0);
+                    lv[(size_t)i] = prach_noma_gain_level(x.lg);
+                }
+            });
+            for (int rc : rcs) if (rc != PRACH_OK) return rc;
+            HIPCHK(hipMemcpyAsync(s.A + s.L.n_level, lv.data(), 4 * lv.size(), hipMemcpyHostToDevice, e->stream));
+            HIPCHK(hipStreamSynchronize(e->stream)); // (lv is pageable host memory that goes away)
+            cx.gain_host_ues += s.c.nUE;
+        }
+        return PRACH_OK;
+    }
+    std::vector<unsigned> ed(2 * (size_t)nedge);
+    HIPCHK(hipMemcpyAsync(ed.data(), dedges + 2, 8 * (size_t)nedge, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    std::vector<int32_t> lv(nedge); // (staged until the copies have completed on the engine's stream)
+    for (unsigned q = 0; q < nedge; q++) {
+        const int j = (int)ed[2 * q], i = (int)ed[2 * q + 1];
+        if (j < 0 || j >= njobs || i < 0 || i >= acc[(size_t)j].c.nUE) return PRACH_ERR_INTERNAL;
+        const JobSrc &s = acc[(size_t)j];
+        Act x;
+        const int arc = prach_noma_activation_range(&s.c, i, i + 1, &x.pre0, &x.sec, &x.gn, &x.lg, &x.nd0);
+        if (arc != PRACH_OK) return arc;
+        lv[q] = prach_noma_gain_level(x.lg);
+        HIPCHK(hipMemcpyAsync(s.A + s.L.n_level + 4 * (size_t)i, &lv[q], 4, hipMemcpyHostToDevice, e->stream));
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));
+    cx.gain_host_ues += (int)nedge;
+    return PRACH_OK;
+}
+hipError_t noma_gain_launch(const prach_engine *e, const Reduction &r, int njobs, int wgs, unsigned long long *const *d) {
+    const prach_noma_gain_spec &sp = spec_of<prach_noma_gain_spec>(r);
+    return launch_noma_gain_kernel(reinterpret_cast<const NomaGainJob *>(e->red_jobs_d), njobs, wgs, sp.bins, sp.width, sp.lo, (int)e->opt_timeline_scheme,
+                                   NomaGainOut{{d[0], d[1], d[2], d[3], d[4], d[5]}, d[6]}, e->stream);
+}
+int noma_gain_unpack(const Reduction &r, CallCtx &cx, size_t g, const unsigned long long *q) {
+    prach_noma_gain &t = group_of<prach_noma_gain>(r, g);
+    t.trials = cx.trials[g]; t.ues = cx.ues[g]; t.idle = q[0]; t.served = q[1]; t.dropped = q[2]; t.pending = q[3]; t.undefined = q[4]; t.below = q[5]; t.above = q[6];
+    t.restarted = q[7]; t.sojourn_sum = q[8]; t.lost_sum = q[9]; t.ptc_sum = q[10]; t.defined = q[11];
+    t.level_max = q[11] ? (int64_t)q[12] - (1ll << 31) : -1;
+    t.neg_level_max = q[11] ? (int64_t)q[13] - (1ll << 31) : -1;
+    return PRACH_OK;
+}
+
 // in the order of enum class Red:           parts, job bytes, tile, job, device logs, trace rows, "fast" off, launch, empty, unpack, prach_timing field
 const RedKind RED_KINDS[] = {
     {dist_parts, sizeof(DistJob), DIST_TILE, dist_fill_job, false, false, false, dist_launch, empty_group<prach_dist, &prach_dist::delay_max>, dist_unpack, &prach_timing::dist_ms},
@@ -819,8 +909,9 @@ const RedKind RED_KINDS[] = {
     {pick_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, noma_pick_launch, pick_empty, pick_unpack, &prach_timing::noma_pick_ms},
     {noma_trace_parts, sizeof(NomaTraceJob), NT_TILE, noma_trace_fill_job, false, true, false, noma_trace_launch, empty_group<prach_noma_trace, &prach_noma_trace::tx_max>, noma_trace_unpack, &prach_timing::noma_trace_ms},
     {noma_timeline_parts, sizeof(TimelineJob), TL_TILE, fill_timeline_job<true>, true, false, false, noma_timeline_launch, empty_group<prach_noma_timeline, &prach_noma_timeline::done_max>, noma_timeline_unpack, &prach_timing::noma_timeline_ms},
+    {noma_gain_parts, sizeof(NomaGainJob), TL_TILE, noma_gain_fill_job, true, false, false, noma_gain_launch, empty_group<prach_noma_gain, &prach_noma_gain::level_max, &prach_noma_gain::neg_level_max>, noma_gain_unpack, &prach_timing::noma_gain_ms, noma_gain_prepass, true},
 };
-static_assert(sizeof(RED_KINDS) / sizeof(RED_KINDS[0]) == (size_t)Red::noma_timeline + 1, "one row per kind");
+static_assert(sizeof(RED_KINDS) / sizeof(RED_KINDS[0]) == (size_t)Red::noma_gain + 1, "one row per kind");
 const RedKind &kind_of(const Reduction &r) { return RED_KINDS[(int)r.kind]; }
 
 // How a rerun's launch differs from the first one
@@ -941,6 +1032,7 @@ template <class F> static int reduce_accepted(prach_engine *e, CallCtx &cx, std:
         if (njobs > 0 && wgs > 0) {
             HIPCHK(hipMemcpyAsync(e->red_jobs_d, e->red_jobs_h, K.job_bytes * (size_t)njobs, hipMemcpyHostToDevice, e->stream));
             HIPCHK(hipEventRecord(e->red_ev0, e->stream));
+            if (K.prepass) { int rc = K.prepass(e, cx, acc, njobs, wgs); if (rc != PRACH_OK) return rc; }
             HIPCHK(K.launch(e, R, njobs, wgs, cx.d_part));
             HIPCHK(hipEventRecord(e->red_ev1, e->stream));
             launched = true;
@@ -975,7 +1067,7 @@ static int run_group(prach_engine *e, CallCtx &cx, const int *idx, int m, int at
         if ((cfgs[idx[k]].flags & PRACH_FLAG_SECTOR_GRANTS) && G > 0 && !batch) return PRACH_ERR_INTERNAL;
     // NOMA.c's activeUE table: built by the device (noma_activation_kernel) unless the option or a rerun asks for the host's libm
     const bool host_act = noma && (e->opt_noma_host_activation || o.host_act);
-    const LaunchLayout LL = layout_launch(cfgs, idx, m, cx.ue_logs, cx.reads_device_logs(), cx.traces(), slen, G, batch, o.full_calendars, e->opt_calendar_cap);
+    const LaunchLayout LL = layout_launch(cfgs, idx, m, cx.ue_logs, cx.reads_device_logs(), cx.traces(), cx.levels(), slen, G, batch, o.full_calendars, e->opt_calendar_cap);
     if (LL.end > e->mem_budget && m > 1) { // (e.g. the 10 000-trial grid with its calendars on ONE GPU: two or three launches instead of one)
         const int h = m / 2;
         int rc = run_group(e, cx, idx, h, attempt, G, o, cal_overflow);
@@ -1626,6 +1718,7 @@ static int run_trials_impl(prach_engine *e, const prach_cfg *cfgs, int n, prach_
     if (seen > 0) e->draws_per_ue_seen = seen; // (sizes the stream windows of the next call: stream_budget)
     e->last.kernel_ms = cx.kernel_ms;
     e->last.noma_host_ues = cx.noma_flagged;
+    e->last.noma_gain_host_ues = cx.gain_host_ues;
     e->last.upload_ms = cx.upload_ms;
     e->last.updates = upd;
     if (red) {
@@ -1786,6 +1879,8 @@ static bool noma_device_cfg(const prach_cfg &c) { return c.variant == PRACH_VARI
 // The grouped kinds (csrc/prach_grouped.h): the Red of each, in the order of PRACH_G_*.  What else the host side knows about a kind — the sizes, the shape of its
 // arrays, where ngroups and the reserved words sit in its spec, the trials it takes — is its row of GROUPED in prach_host.c
 static const Red GROUPED_RED[PRACH_G_KINDS] = {Red::dist, Red::timeline, Red::sojourn, Red::trace, Red::xtab, Red::noma_census, Red::noma_trace, Red::noma_timeline};
+static const Red GROUPED_RED_MORE[PRACH_G_MORE_END - PRACH_G_MORE] = {Red::noma_gain}; // ... and of the enumerators from PRACH_G_MORE on
+static Red grouped_red(int kind) { return kind < PRACH_G_KINDS ? GROUPED_RED[kind] : GROUPED_RED_MORE[kind - PRACH_G_MORE]; } // (a kind that has a row)
 
 // THE refusal sequence of every grouped call.  Arguments first (pointers, spec, ngroups, reserved, group ids), then what is not supported (the trials' programs,
 // then the cap of 2^27 words = 1 GiB of device buffer), then the missing engine: spec, groups and variants are judged first, what they ask for does not depend
@@ -1811,7 +1906,7 @@ int prach_internal_grouped_run(int kind, prach_engine *e, const prach_cfg *cfgs,
             return PRACH_ERR_UNSUPPORTED;
     if ((uint64_t)ngroups * group_words > (1ull << 27)) return PRACH_ERR_UNSUPPORTED;
     if (!e) return PRACH_ERR_ARG;
-    Reduction red{.kind = GROUPED_RED[kind], .group = group, .ngroups = ngroups, .out = {}, .spec = spec, .groups = groups};
+    Reduction red{.kind = grouped_red(kind), .group = group, .ngroups = ngroups, .out = {}, .spec = spec, .groups = groups};
     for (int q = 0; q < narrays; q++) red.out[q] = arrays[q];
     PRACH_GUARD(return run_trials_impl(e, cfgs, n, results, ue_logs, &red);)
 }
@@ -1851,6 +1946,11 @@ int prach_run_trials_noma_trace(prach_engine *e, const prach_cfg *cfgs, int n, p
 int prach_run_trials_noma_timeline(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_noma_timeline_spec *spec,
                                    const int32_t *group, prach_noma_timeline *tl, uint64_t *const series[6]) {
     return prach_internal_grouped_run(PRACH_G_NOMA_TIMELINE, e, cfgs, n, results, ue_logs, spec, group, tl, series);
+}
+
+int prach_run_trials_noma_gain(prach_engine *e, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs, const prach_noma_gain_spec *spec,
+                               const int32_t *group, prach_noma_gain *g, uint64_t *const series[6]) {
+    return prach_internal_grouped_run(PRACH_G_NOMA_GAIN, e, cfgs, n, results, ue_logs, spec, group, g, series);
 }
 
 int prach_dist_tile_ues(void) { return DIST_TILE; }
@@ -1976,6 +2076,8 @@ int prach_run_trials_noma_pick(prach_engine *e, const prach_cfg *cfgs, int n, pr
 
 int prach_noma_timeline_tile_ues(void) { return TL_TILE; }
 int prach_noma_timeline_window_bins(void) { return NTL_WINDOW; }
+int prach_noma_gain_tile_ues(void) { return TL_TILE; }
+int prach_noma_gain_lds_max_bins(void) { return NG_LDS_MAX_BINS; }
 int prach_noma_trace_tile_rows(void) { return NT_TILE; }
 int prach_noma_census_tile_ues(void) { return TL_TILE; }
 int prach_columns_tile_ues(void) { return TL_TILE; }

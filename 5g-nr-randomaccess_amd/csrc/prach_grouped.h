@@ -2,8 +2,8 @@
  * prach_engine.hip (the one refusal sequence in front of run_trials_impl) and prach_cli.c (the block of groups of a worker) know about a kind.  Internal:
  * include/prach.h states the 24 public functions, which are wrappers that gather their pointers into an array and call the generic function.
  *
- * A new grouped kind is an enumerator here, a row of GROUPED in prach_host.c (with its shape function and its CSV lines) and an entry of the engine's
- * GROUPED_RED; the generic functions and the CLI's block code do not change. */
+ * A new grouped kind is an enumerator here (of the second block: PRACH_G_MORE), a row of GROUPED_MORE in prach_host.c (with its shape function and its CSV
+ * lines) and an entry of the engine's GROUPED_RED_MORE; the generic functions and the CLI's block code do not change. */
 #ifndef PRACH_GROUPED_H
 #define PRACH_GROUPED_H
 
@@ -14,6 +14,9 @@ extern "C" {
 #endif
 
 enum { PRACH_G_DIST, PRACH_G_TIMELINE, PRACH_G_SOJOURN, PRACH_G_TRACE, PRACH_G_XTAB, PRACH_G_NOMA_CENSUS, PRACH_G_NOMA_TRACE, PRACH_G_NOMA_TIMELINE, PRACH_G_KINDS };
+/* The kinds behind the first eight: PRACH_G_KINDS is the size of the first block of GROUPED and stays what the checks of that block know it as; a later kind
+ * counts from PRACH_G_MORE in a second block of the same rows.  Every generic function takes the kinds of both blocks. */
+enum { PRACH_G_MORE = 16, PRACH_G_NOMA_GAIN = PRACH_G_MORE, PRACH_G_MORE_END };
 #define PRACH_G_MAX_ARRAYS 6
 /* the trials a kind's device call takes: any; every program but NOMA.c; NOMA.c with Philox only */
 enum { PRACH_G_TRIALS_ANY, PRACH_G_TRIALS_NOT_NOMA_C, PRACH_G_TRIALS_NOMA_C_PHILOX };

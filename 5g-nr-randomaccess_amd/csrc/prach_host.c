@@ -1165,6 +1165,119 @@ static size_t noma_timeline_csv(const void *spec, const void *group, const uint6
     return series_csv(&lines, s->bins, s->bin_ms, group, series, label, buf, cap);
 }
 
+/* ---- NOMA.c's near-far profile per trial group, sector and gain level (prach_run_trials_noma_gain): the level, THE DEFINITION, CSV ---- */
+
+/* floor(1000.0 * lgain): ONE IEEE product (no contraction: there is nothing to contract with), floor towards minus infinity */
+int32_t prach_noma_gain_level(double lgain) {
+    const double p = 1000.0 * lgain;
+    if (!isfinite(p) || fabs(p) >= 1073741824.0) return PRACH_NOMA_GAIN_NO_LEVEL;
+    return (int32_t)floor(p);
+}
+
+int prach_noma_gain_levels(const prach_cfg *cfg, int32_t *level) {
+    if (!cfg || !level) return PRACH_ERR_ARG;
+    if (cfg->variant != PRACH_VARIANT_NOMA_C || cfg->rng_mode == PRACH_RNG_GLIBC) return PRACH_ERR_UNSUPPORTED;
+    if (prach_cfg_validate(cfg) != PRACH_OK) return PRACH_ERR_ARG;
+    const size_t n = (size_t)(cfg->nUE > 0 ? cfg->nUE : 1);
+    int32_t *pre = (int32_t *)malloc(4 * n), *sec = (int32_t *)malloc(4 * n);
+    uint32_t *nd = (uint32_t *)malloc(4 * n);
+    double *gn = (double *)malloc(8 * n), *lg = (double *)malloc(8 * n);
+    int rc = pre && sec && nd && gn && lg ? prach_noma_activation_table(cfg, pre, sec, gn, lg, nd) : PRACH_ERR_INTERNAL;
+    for (int i = 0; rc == PRACH_OK && i < cfg->nUE; i++) level[i] = prach_noma_gain_level(lg[i]);
+    free(pre); free(sec); free(nd); free(gn); free(lg);
+    return rc;
+}
+
+static int noma_gain_shape(const void *spec, size_t words[]) {
+    const prach_noma_gain_spec *s = (const prach_noma_gain_spec *)spec;
+    if (!s || s->bins < 1 || s->bins > PRACH_NOMA_GAIN_MAX_BINS || s->width < 1) return 0;
+    for (int q = 0; q < PRACH_NOMA_GAIN_SERIES; q++) words[q] = 6 * (size_t)s->bins;
+    return PRACH_NOMA_GAIN_SERIES;
+}
+
+/* THE DEFINITION (include/prach.h), on the menu's own class and values and the levels as given */
+int prach_noma_gain_accumulate_levels(const prach_noma_gain_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, const int32_t *level,
+                                      prach_noma_gain *g, uint64_t *const series[6]) {
+    if (!spec_ok(noma_gain_shape, s) || !cfg || !g || !series || nUE < 0 || (nUE > 0 && (!ue || !level))) return PRACH_ERR_ARG;
+    for (int q = 0; q < 6; q++) if (!series[q]) return PRACH_ERR_ARG;
+    int nslots = 0, rc;
+    int64_t E = 0;
+    int32_t *sched = menu_schedule(&NOMA_MENU, cfg, nUE, steps, &nslots, &E, &rc);
+    if (!sched) return rc;
+    if (g->defined == 0) g->level_max = g->neg_level_max = -1; /* (a zero-filled group is an empty one) */
+    uint64_t *const arrived = series[0], *const served = series[1], *const dropped = series[2], *const sojourn_sum = series[3], *const lost_sum = series[4],
+                    *const ptc_sum = series[5];
+    const int64_t lo = s->lo, hi = (int64_t)s->lo + (int64_t)s->bins * (int64_t)s->width;
+    int slot = 0; /* UEs are activated in index order: the slot of UE i is not before the slot of UE i - 1 */
+    for (int i = 0; i < nUE; i++) {
+        while (slot < nslots && sched[slot] <= i) slot++;
+        const int64_t a = (int64_t)cfg->accessTime * slot;
+        const prach_ue_log *u = &ue[i];
+        const int cls = noma_class(u);
+        if (cls == PRACH_NOMA_IDLE) { g->idle++; continue; }
+        if (cls == PRACH_NOMA_SERVED) g->served++;
+        else if (cls == PRACH_NOMA_DROPPED) g->dropped++;
+        else g->pending++;
+        const int64_t sec = noma_value(PRACH_NOMA_SECTOR, u, cls, a, E), sj = noma_value(PRACH_NOMA_SOJOURN, u, cls, a, E),
+                      lost = noma_value(PRACH_NOMA_LOST, u, cls, a, E), ptc = noma_value(PRACH_NOMA_PTC, u, cls, a, E), L = level[i];
+        if (sec < 0 || sec > 5 || L == PRACH_NOMA_GAIN_NO_LEVEL || (cls == PRACH_NOMA_SERVED && (sj < 0 || lost < 0 || ptc < 0))) { g->undefined++; continue; }
+        if (g->defined++ == 0 || L > g->level_max) g->level_max = L;
+        if (g->defined == 1 || -L > g->neg_level_max) g->neg_level_max = -L;
+        const int in = L >= lo && L < hi;
+        const size_t at = in ? (size_t)sec * (size_t)s->bins + (size_t)((L - lo) / s->width) : 0;
+        if (L < lo) g->below++;
+        else if (!in) g->above++;
+        else arrived[at]++;
+        if (cls == PRACH_NOMA_DROPPED && in) dropped[at]++;
+        if (cls != PRACH_NOMA_SERVED) continue;
+        g->sojourn_sum += (uint64_t)sj;
+        g->lost_sum += (uint64_t)lost;
+        g->ptc_sum += (uint64_t)ptc;
+        g->restarted += lost > 0;
+        if (in) { served[at]++; sojourn_sum[at] += (uint64_t)sj; lost_sum[at] += (uint64_t)lost; ptc_sum[at] += (uint64_t)ptc; }
+    }
+    free(sched);
+    g->trials++;
+    g->ues += (uint64_t)nUE;
+    return PRACH_OK;
+}
+
+int prach_noma_gain_accumulate_logs(const prach_noma_gain_spec *s, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_noma_gain *g,
+                                    uint64_t *const series[6]) {
+    if (!spec_ok(noma_gain_shape, s) || !cfg || !g || !series || nUE < 0 || (nUE > 0 && !ue)) return PRACH_ERR_ARG;
+    for (int q = 0; q < 6; q++) if (!series[q]) return PRACH_ERR_ARG;
+    if (cfg->variant != PRACH_VARIANT_NOMA_C || cfg->rng_mode == PRACH_RNG_GLIBC) return PRACH_ERR_UNSUPPORTED;
+    if (prach_cfg_validate(cfg) != PRACH_OK || nUE != cfg->nUE) return PRACH_ERR_ARG;
+    int32_t *level = (int32_t *)malloc(4 * (size_t)(nUE > 0 ? nUE : 1));
+    if (!level) return PRACH_ERR_INTERNAL;
+    int rc = prach_noma_gain_levels(cfg, level);
+    if (rc == PRACH_OK) rc = prach_noma_gain_accumulate_levels(s, cfg, steps, ue, nUE, level, g, series);
+    free(level);
+    return rc;
+}
+
+static size_t noma_gain_csv(const void *spec, const void *group, const uint64_t *const series[], const char *label, char *buf, size_t cap) {
+    static const char *const names[6] = {"arrived", "served", "dropped", "sojourn_sum", "lost_sum", "ptc_sum"};
+    const prach_noma_gain_spec *s = (const prach_noma_gain_spec *)spec;
+    const prach_noma_gain *g = (const prach_noma_gain *)group;
+    size_t off = 0;
+    for (int q = 0; q < 6; q++) {
+        if (q == 0 && g->below) CSV_EMIT("%.200s,%s,all,below,%llu\n", label, names[0], (unsigned long long)g->below);
+        for (int b = 0; b < s->bins; b++) {
+            const long long edge = (long long)s->lo + (long long)b * s->width;
+            uint64_t all = 0;
+            for (int c = 0; c < 6; c++) {
+                const uint64_t v = series[q][(size_t)c * (size_t)s->bins + (size_t)b];
+                all += v;
+                if (v) CSV_EMIT("%.200s,%s,%d,%lld,%llu\n", label, names[q], c, edge, (unsigned long long)v);
+            }
+            if (all) CSV_EMIT("%.200s,%s,all,%lld,%llu\n", label, names[q], edge, (unsigned long long)all);
+        }
+        if (q == 0 && g->above) CSV_EMIT("%.200s,%s,all,above,%llu\n", label, names[0], (unsigned long long)g->above);
+    }
+    return csv_end(buf, cap, off);
+}
+
 /* THE DEFINITION of the pick (prach_pick_from_logs, prach_noma_pick_from_logs): every match is listed, the list is sorted, the first k are the rows */
 typedef struct pick_cand { int64_t key; int32_t i, arrival; } pick_cand;
 static int cmp_pick_desc(const void *a, const void *b) { /* descending key, equal keys in ascending UE index */
@@ -1291,8 +1404,14 @@ static const prach_grouped_row GROUPED[PRACH_G_KINDS] = {
     GROUPED_ROW(prach_noma_trace_spec, prach_noma_trace, slots, 1, 1, PRACH_G_TRIALS_NOMA_C_PHILOX, noma_trace_shape, noma_trace_csv),
     GROUPED_ROW(prach_noma_timeline_spec, prach_noma_timeline, served, 1, 1, PRACH_G_TRIALS_NOMA_C_PHILOX, noma_timeline_shape, noma_timeline_csv),
 };
+/* ... and of the enumerators from PRACH_G_MORE on */
+static const prach_grouped_row GROUPED_MORE[PRACH_G_MORE_END - PRACH_G_MORE] = {
+    GROUPED_ROW(prach_noma_gain_spec, prach_noma_gain, defined, 2, 1, PRACH_G_TRIALS_NOMA_C_PHILOX, noma_gain_shape, noma_gain_csv),
+};
 
-const prach_grouped_row *prach_internal_grouped_row(int kind) { return kind >= 0 && kind < PRACH_G_KINDS ? &GROUPED[kind] : NULL; }
+const prach_grouped_row *prach_internal_grouped_row(int kind) {
+    return kind >= 0 && kind < PRACH_G_KINDS ? &GROUPED[kind] : kind >= PRACH_G_MORE && kind < PRACH_G_MORE_END ? &GROUPED_MORE[kind - PRACH_G_MORE] : NULL;
+}
 
 int prach_internal_grouped_shape(int kind, const void *spec, size_t words[PRACH_G_MAX_ARRAYS]) {
     const prach_grouped_row *k = prach_internal_grouped_row(kind);
@@ -1311,14 +1430,15 @@ void prach_internal_grouped_merge(int kind, const void *spec, void *into, uint64
     size_t words[PRACH_G_MAX_ARRAYS];
     const int na = grouped_args(kind, spec, into, (const uint64_t *const *)into_arrays, words);
     if (!na || !grouped_args(kind, spec, from, from_arrays, words)) return;
-    const prach_grouped_row *k = &GROUPED[kind];
+    const prach_grouped_row *k = prach_internal_grouped_row(kind);
     uint64_t *const a = (uint64_t *)into;
     const uint64_t *const b = (const uint64_t *)from;
     int64_t *const amax = (int64_t *)into + k->counters;
     const int64_t *const bmax = (const int64_t *)from + k->counters;
-    for (int m = 0; m < k->maxima; m++) { /* (a maximum only counts if the guard counter is non-zero: judged before the counters are added) */
-        const int64_t x = a[k->guard] ? amax[m] : -1, y = b[k->guard] ? bmax[m] : -1;
-        amax[m] = x > y ? x : y;
+    for (int m = 0; m < k->maxima; m++) { /* (a maximum only counts if the guard counter is non-zero: judged before the counters are added; -1 where neither
+                                             counts, and a side that does not count never wins: the gain profile's maxima may lie below -1) */
+        const int64_t x = amax[m], y = bmax[m];
+        amax[m] = !a[k->guard] ? (b[k->guard] ? y : -1) : !b[k->guard] || x > y ? x : y;
     }
     for (int c = 0; c < k->counters; c++) a[c] += b[c];
     for (int q = 0; q < na; q++)
@@ -1328,7 +1448,7 @@ void prach_internal_grouped_merge(int kind, const void *spec, void *into, uint64
 size_t prach_internal_grouped_format_csv(int kind, const void *spec, const void *group, const uint64_t *const arrays[], const char *label, char *buf, size_t cap) {
     size_t words[PRACH_G_MAX_ARRAYS];
     if (!grouped_args(kind, spec, group, arrays, words) || !label) return 0;
-    return GROUPED[kind].format(spec, group, arrays, label, buf, cap);
+    return prach_internal_grouped_row(kind)->format(spec, group, arrays, label, buf, cap);
 }
 
 void prach_dist_merge(const prach_dist_spec *s, prach_dist *into, uint64_t *dh_into, uint64_t *ph_into, const prach_dist *from, const uint64_t *dh_from,
@@ -1392,6 +1512,14 @@ void prach_noma_timeline_merge(const prach_noma_timeline_spec *s, prach_noma_tim
 size_t prach_noma_timeline_format_csv(const prach_noma_timeline_spec *s, const prach_noma_timeline *t, const uint64_t *const series[6], const char *label, char *buf,
                                       size_t cap) {
     return prach_internal_grouped_format_csv(PRACH_G_NOMA_TIMELINE, s, t, series, label, buf, cap);
+}
+
+void prach_noma_gain_merge(const prach_noma_gain_spec *s, prach_noma_gain *into, uint64_t *const into_series[6], const prach_noma_gain *from,
+                           const uint64_t *const from_series[6]) {
+    prach_internal_grouped_merge(PRACH_G_NOMA_GAIN, s, into, into_series, from, from_series);
+}
+size_t prach_noma_gain_format_csv(const prach_noma_gain_spec *s, const prach_noma_gain *g, const uint64_t *const series[6], const char *label, char *buf, size_t cap) {
+    return prach_internal_grouped_format_csv(PRACH_G_NOMA_GAIN, s, g, series, label, buf, cap);
 }
 
 /* ---- picks: the UEs behind a count, per trial (prach_run_trials_pick, prach_run_trials_noma_pick): CSV ---- */

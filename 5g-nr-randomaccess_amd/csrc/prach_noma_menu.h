@@ -11,7 +11,8 @@
 // LOST are at most 10 006, TIMER, PTC, RETX, SECTOR and PREAMBLE are logged int32 words, MSG3FAIL is the upper half of one, STATE is at most 8; nm_value
 // computes in 64 bits.  A NEGATIVE value is UNDEFINED (the one rule of the menu).
 //
-// The channel gain is NOT here: with Philox the host has it per UE (prach_noma_activation_table), in the reference's stream it exists only inside the launch.
+// The channel gain is not a field here: it is the axis of a kind of its own (prach_run_trials_noma_gain, prach_noma_gain.hip).  With Philox the host has it
+// per UE as well (prach_noma_activation_table), in the reference's stream it exists only inside the launch.
 #pragma once
 #include "prach_device.h"
 

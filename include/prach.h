@@ -129,6 +129,12 @@ typedef struct prach_timing {
     int32_t trial_kernel_reruns; /* of fallback_trials: trials that were (also) rerun on the one-workgroup, index-ordered trial_kernel */
     int32_t noma_host_ues;       /* NOMA_C, Philox: UEs of the device-built activeUE table that the host recomputed with its libm (a value inside the
                                     device math library's error band of a rounding / comparison boundary: ~1e-6 of the UEs) */
+    int32_t noma_gain_host_ues;  /* prach_run_trials_noma_gain: UEs whose gain level the host resolved in the last call (1000 ln g within the error band of an
+                                    integer, or no level: ~2e-8 of the UEs; every UE of a launch whose list of such UEs overflowed); 0 in every other call */
+    int32_t noma_gain_pad;       /* 0 */
+    double noma_gain_ms;         /* HIP-event time of the gain-level pre-pass and the NOMA gain kernel launches (prach_run_trials_noma_gain) of the last call, the
+                                    host's work on the listed UEs between the two included; 0 in every other call (such a call leaves every other *_ms of a
+                                    reduction 0) */
     double noma_timeline_ms;     /* HIP-event time of the NOMA timeline kernel launches (prach_run_trials_noma_timeline) of the last call; 0 in every other call (such
                                     a call leaves every other *_ms of a reduction 0) */
     double noma_trace_ms;        /* HIP-event time of the NOMA trace kernel launches (prach_run_trials_noma_trace) of the last call; 0 in every other call (such a
@@ -519,8 +525,9 @@ int prach_columns_tile_ues(void); /* UEs of one trial that one workgroup of prac
  * with active == 1, nowBackoff <= 0 and txTime below the current subframe is never touched again, only its timer ticks to the end of the run.  NOMA.c reports
  * no such UE; the backoff's off-by-one makes them.
  * ONE RULE as in the xtab block: a NEGATIVE value is UNDEFINED, nothing is refused, nothing is clipped.  Every menu value of a trial fits int32
- * (csrc/prach_noma_menu.h states the bounds).  The channel gain is NOT in the menu: with Philox it is available per UE through prach_noma_activation_table,
- * in the reference's stream it exists only inside the launch.
+ * (csrc/prach_noma_menu.h states the bounds).  The channel gain is not a FIELD of the menu (the field count is fixed); it is the axis of a kind of its own,
+ * prach_run_trials_noma_gain below.  With Philox it is also available per UE through prach_noma_activation_table and prach_noma_gain_levels; in the
+ * reference's stream it exists only inside the launch.
  * PRACH_RNG_GLIBC trials of NOMA_C are not wired to the device calls below (their launches lay out no job the menu's kernels read): the calls refuse them, and
  * prach_run_trials with logs plus the host definitions serves them. */
 #define PRACH_NOMA_SERVED  1
@@ -681,6 +688,79 @@ size_t prach_noma_timeline_format_csv(const prach_noma_timeline_spec *, const pr
                                       size_t cap);
 int prach_noma_timeline_tile_ues(void);    /* UEs of one trial that one workgroup of prach::noma_timeline_kernel reduces (tests place sizes around it) */
 int prach_noma_timeline_window_bins(void); /* bins of the LDS window of prach::noma_timeline_kernel (timeline_scheme 1), anchored at a tile's first arrival bin */
+
+/* NOMA_C's NEAR-FAR PROFILE: per trial group, SECTOR and CHANNEL-GAIN LEVEL, what became of the UEs — the NOMA timeline with the arrival-bin axis replaced by
+ * a gain-level axis.  The Rayleigh channel gain a UE draws at activation (NOMA.c:185-189) is the one quantity the pairing rests on (10*log(high) - 10*log(low)
+ * against 15.0, NOMA.c:276) and it is not a field of THE NOMA MENU (the menu's field count is fixed); it is the axis of this kind instead.
+ * THE GAIN LEVEL of a UE is L = prach_noma_gain_level(lgain), lgain = ln(gain) as prach_noma_activation_table gives it: L = floor(1000.0 * lgain), the product
+ * ONE IEEE double multiplication, the floor towards minus infinity — the gain in hundredths of NOMA.c's own pairing unit 10 ln g: two UEs can pair when their
+ * levels are 1500 apart.  The activation loop keeps gain >= 1e-7, so the levels of a trial lie in about -16 119 ... -3 350.  INT32_MIN is NO LEVEL: a
+ * non-finite lgain, or |1000 lgain| >= 2^30.
+ * THE DEFINITION is prach_noma_gain_accumulate_levels.  Class, SECTOR, SOJOURN, LOST and PTC are THE NOMA MENU's as they stand.  For UE i with level L:
+ *   - every UE counts in its class counter (idle, served, dropped, pending): their sum is `ues`; an idle UE counts in nothing else;
+ *   - an arrived UE is UNDEFINED FOR THE PROFILE if its SECTOR lies outside 0..5, if L is INT32_MIN, or if it is served and any of SOJOURN, LOST, PTC is negative
+ *     (the menu's ONE RULE).  It counts in `undefined` and in nothing else below;
+ *   - every other arrived UE counts in `defined` and in level_max / neg_level_max, and: L < lo: below += 1; L >= lo + bins * width (formed in 64 bits):
+ *     above += 1; otherwise b = (L - lo) / width and arrived[s][b] += 1;
+ *   - dropped and in a bin: dropped[s][b] += 1;
+ *   - served: the scalars sojourn_sum += SOJOURN, lost_sum += LOST, ptc_sum += PTC, restarted += LOST > 0, always; in a bin: served[s][b] += 1 and the three
+ *     sums at [s][b].
+ * Pending per (sector, bin) is arrived - served - dropped; it is not stored.  IDENTITY: sum(arrived) + below + above + undefined == served + dropped + pending.
+ * Under PRACH_FLAG_NOMA_NONSECTOR the sector is the UE's own, as in the timeline.  The six series are [ngroups][6 sectors][bins] each, in the order arrived,
+ * served, dropped, sojourn_sum, lost_sum, ptc_sum.  Integers only, 64-bit outputs: device, host, forked workers and ranks merge exactly in any order. */
+#define PRACH_NOMA_GAIN_SERIES 6
+#define PRACH_NOMA_GAIN_MAX_BINS 4096
+#define PRACH_NOMA_GAIN_NO_LEVEL INT32_MIN
+typedef struct prach_noma_gain_spec {
+    int32_t bins;      /* 1 .. PRACH_NOMA_GAIN_MAX_BINS */
+    int32_t width;     /* >= 1, in level units */
+    int32_t lo;        /* the level of the lower edge of bin 0: any int32 */
+    int32_t ngroups;   /* number of output profiles */
+    int32_t reserved;  /* 0 */
+} prach_noma_gain_spec;
+
+typedef struct prach_noma_gain { /* one per group */
+    uint64_t trials;             /* trials accumulated (status PRACH_OK) */
+    uint64_t ues;                /* sum of their nUE */
+    uint64_t idle, served, dropped, pending; /* the four classes: idle + served + dropped + pending == ues */
+    uint64_t undefined;          /* arrived UEs that are undefined for the profile (in no series, no sum, not below, not above) */
+    uint64_t below, above;       /* defined arrived UEs with a level under bin 0 / at or above lo + bins * width */
+    uint64_t restarted;          /* served, defined, LOST > 0 */
+    uint64_t sojourn_sum, lost_sum, ptc_sum; /* over the defined served UEs, unbinned */
+    uint64_t defined;            /* arrived UEs that are defined (each has a level): sum(arrived) + below + above; guards the two maxima */
+    int64_t  level_max;          /* the largest level of a defined arrived UE; -1 where `defined` is 0 (a level may be -1: ask `defined`) */
+    int64_t  neg_level_max;      /* the largest -L, i.e. minus the smallest level; -1 where `defined` is 0 */
+} prach_noma_gain;
+
+int32_t prach_noma_gain_level(double lgain);
+/* the levels of every UE of a NOMA_C Philox cfg from prach_noma_activation_table (the host's libm): level[nUE].  PRACH_ERR_UNSUPPORTED: not NOMA_C, or
+ * PRACH_RNG_GLIBC (the gain exists only inside the launch) */
+int prach_noma_gain_levels(const prach_cfg *cfg, int32_t *level);
+/* prach_run_trials plus the profiles, with the contract of prach_run_trials_noma_timeline word for word (groups, OVERWRITTEN outputs, a rerun trial counted
+ * once, at most one reduction per call; results and logs are those of the same prach_run_trials call); g[ngroups] and series[q][ngroups * 6 * bins] are
+ * caller-owned.  A pre-pass writes every UE's level from the launch's activation table on the device; the few UEs whose 1000 ln g lies within the error band
+ * of an integer are resolved by the host (prach_timing.noma_gain_host_ues), so the result equals prach_noma_gain_accumulate_logs integer for integer whichever
+ * side built the table; then prach::noma_gain_kernel (csrc/prach_noma_gain.hip) reduces.  Engine option "timeline_scheme" applies.
+ * PRACH_ERR_ARG: a NULL output, bins or width out of range, a group id out of range, NULL group with ngroups != n;
+ * PRACH_ERR_UNSUPPORTED, before anything is launched: any cfg that is not NOMA_C; any NOMA_C cfg with rng_mode == PRACH_RNG_GLIBC; 36 * ngroups * bins > 2^27
+ * words.  A refusal writes nothing. */
+int prach_run_trials_noma_gain(prach_engine *, const prach_cfg *cfgs, int n, prach_result *results, prach_ue_log *const *ue_logs,
+                               const prach_noma_gain_spec *spec, const int32_t *group, prach_noma_gain *g, uint64_t *const series[6]);
+/* host side (no device needed), ONE group (series[q]: [6][bins]).  _accumulate_levels ADDS one trial's per-UE log with the levels AS GIVEN (any RNG mode:
+ * THE DEFINITION); _accumulate_logs takes the levels from prach_noma_gain_levels(cfg) and calls it (PRACH_ERR_UNSUPPORTED: a cfg that is not NOMA_C or is
+ * PRACH_RNG_GLIBC).  steps is the trial's prach_result.steps.  PRACH_ERR_ARG: a bad spec or cfg, a NULL pointer, nUE != cfg->nUE.  _merge adds counts and sums
+ * and takes the maxima; _format_csv writes "label,series,sector,level,count" for every non-zero cell (level: the bin's lower edge lo + b * width),
+ * "label,series,all,level,count" for every non-zero bin, and "label,arrived,all,below,count" / "label,arrived,all,above,count" where non-zero; returns the
+ * text's length (written in full only if it fits cap, then 0-terminated). */
+int prach_noma_gain_accumulate_levels(const prach_noma_gain_spec *, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, const int32_t *level,
+                                      prach_noma_gain *g, uint64_t *const series[6]);
+int prach_noma_gain_accumulate_logs(const prach_noma_gain_spec *, const prach_cfg *cfg, uint64_t steps, const prach_ue_log *ue, int nUE, prach_noma_gain *g,
+                                    uint64_t *const series[6]);
+void prach_noma_gain_merge(const prach_noma_gain_spec *, prach_noma_gain *into, uint64_t *const into_series[6], const prach_noma_gain *from,
+                           const uint64_t *const from_series[6]);
+size_t prach_noma_gain_format_csv(const prach_noma_gain_spec *, const prach_noma_gain *, const uint64_t *const series[6], const char *label, char *buf, size_t cap);
+int prach_noma_gain_tile_ues(void);      /* UEs of one trial that one workgroup of prach::noma_gain_kernel reduces (tests place sizes around it) */
+int prach_noma_gain_lds_max_bins(void);  /* the most bins whose counters the kernel keeps in LDS (timeline_scheme 1); more bins go straight to the global counters */
 
 /* Per-trial summaries of NOMA_C trials: ONE ROW PER TRIAL — the four class counts, and for up to four NAMED fields of THE NOMA MENU above, over the UEs of
  * the classes in `who` whose value of the field is DEFINED (the menu's ONE RULE: >= 0), their number, sum, maximum and EXACT order statistics — selected on the
